@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- patches/s of the EfficientNet-B0 feature-extraction hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line (`value`, `ms_per_step`).
+`--full` adds what takes runs of its own: the spread over further timed blocks, the per-kernel roofline
+(HIP-event profile passes) and the CPU baseline.  `--dump-outputs DIR` writes the features of the last timed
+step of the first block (the one `value` comes from) as DIR/features.npy, float32: (G * 256, 1280) for G ranks,
+rank-major, exactly the rows a caller of the gathered path receives for that step.
 
 One "step" = one pass of the hot path over one batch of 256 synthetic 224x224 u8 patches per
 GPU (BASELINE.json configs[1]: "EfficientNet-B0 forward, batch=256 random 224x224 patches"),
@@ -217,15 +223,23 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-passes", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also the spread over --spread-blocks, the per-kernel roofline and the CPU baseline (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's features as DIR/features.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--profile-passes", type=int, default=5, help="--full: HIP-event profile passes behind the roofline")
     ap.add_argument("--gather-every", type=int, default=0,
                     help="N > 1: all-gather the rank block once per this many steps (0 = once, at the end, over all K steps' rows)")
-    ap.add_argument("--spread-blocks", type=int, default=3, help="timed blocks of --steps for the spread (the first one is `value`)")
+    ap.add_argument("--spread-blocks", type=int, default=3,
+                    help="--full: timed blocks of --steps for the spread (the first one is `value`)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / gather plumbing on gloo, no GPU work")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dry_run and args.dump_outputs:
+        raise SystemExit("--dump-outputs needs the GPU path: a dry run computes no features")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))     # nothing above has imported torch or touched the GPU
 
@@ -355,20 +369,49 @@ def main():
             dt = float(t.item())
         return dt
 
-    # `value` comes from the FIRST block of exactly K steps (the contract); the further blocks only feed `spread`.
-    times = [timed_block() for _ in range(max(1, args.spread_blocks))]
-    elapsed = times[0]
-    if use_dist:
+    # `value` comes from the FIRST block of exactly K steps (the contract); the further blocks (--full) only feed `spread`.
+    # The dump is taken right after that block, before a further block or a profile pass overwrites the buffers.
+    if use_dist:                                   # the gather that holds the last step's rows, and its rows per rank
         lastg = tailg if tailg is not None else gats[((K - 1) // G) % nblk]
         nrows = ((K % G) or G) * BATCH
+    times = [timed_block()]
+    dump = None
+    if args.dump_outputs:
+        if use_dist:
+            dump = lastg.out.view(world, nrows, 1280)[:, -BATCH:].reshape(world * BATCH, 1280).cpu().numpy()
+        else:
+            dump = feats.cpu().numpy()
+    if args.full:
+        times += [timed_block() for _ in range(max(1, args.spread_blocks) - 1)]
+    elapsed = times[0]
+    if use_dist:
         mine = lastg.out[rank * nrows:(rank + 1) * nrows]
         if not torch.equal(mine[-BATCH:], feats):
             raise SystemExit("gathered feature block differs from the local features")
     if not np.isfinite(feats.float().sum().item()):
         raise SystemExit("non-finite features")
 
+    if rank == 0 and dump is not None:
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        np.save(out_dir / "features.npy", dump.astype(np.float32, copy=False))
+
     if rank == 0:
         value = world * BATCH * args.steps / elapsed
+        out = {
+            "metric": "patches/sec (224x224 EfficientNet-B0)", "value": value, "unit": "patches/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+            "config": {"workload": "EfficientNet-B0 forward, batch=256 random 224x224 u8 patches per GPU -> (256,1280) fp32"
+                                   + ("; " + gather_desc(world, K, G, overlap) if use_dist else ""),
+                       "per_gpu_batch": BATCH, "global_batch": world * BATCH, "weights": "synthetic seed 0",
+                       "input_batches_rotated": NBUF,
+                       "lanes_per_gpu": bb.lanes,
+                       **({"gather_every_steps": G, "gathers_per_run": -(-K // G), "gather_overlap": overlap} if use_dist else {}),
+                       "parallelism": f"patch-sharded x{world}"},
+        }
+    if rank == 0 and args.full:
         vals = [world * BATCH * args.steps / t for t in times]
         # per-kernel durations, HIP events on the launch stream, same resident workload
         per_kernel = defaultdict(lambda: [0.0, 0, 0, 0])  # ms, launches, algorithmic bytes, algorithmic flops
@@ -418,26 +461,14 @@ def main():
                     "whole_net": {"alg_GB_per_step": tot["bytes"] / 1e9,
                                   "hbm_frac_at_value": tot["bytes_per_patch"] * value / 1e9 / schedule.HBM_PEAK_GBS,
                                   "mfma_frac_at_value": tot["flops_per_patch"] * value / 1e12 / schedule.MFMA_F16_PEAK_TFLOPS}}
-        out = {
-            "metric": "patches/sec (224x224 EfficientNet-B0)", "value": value, "unit": "patches/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-            "spread": {"unit": "patches/s", "blocks": len(times), "steps_per_block": K,
-                       "min": min(vals), "median": float(np.median(vals)), "max": max(vals)},
-            "config": {"workload": "EfficientNet-B0 forward, batch=256 random 224x224 u8 patches per GPU -> (256,1280) fp32"
-                                   + ("; " + gather_desc(world, K, G, overlap) if use_dist else ""),
-                       "per_gpu_batch": BATCH, "global_batch": world * BATCH, "weights": "synthetic seed 0",
-                       "input_batches_rotated": NBUF,
-                       "lanes_per_gpu": bb.lanes,
-                       **({"gather_every_steps": G, "gathers_per_run": -(-K // G), "gather_overlap": overlap} if use_dist else {}),
-                       "parallelism": f"patch-sharded x{world}"},
-            "roofline": roofline,
-        }
+        out["spread"] = {"unit": "patches/s", "blocks": len(times), "steps_per_block": K,
+                         "min": min(vals), "median": float(np.median(vals)), "max": max(vals)}
+        out["roofline"] = roofline
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd)
         kernels = sorted(((k, v[0] / args.profile_passes) for k, v in per_kernel.items()), key=lambda kv: -kv[1])
         print("# per-kernel ms/step (HIP events): " + ", ".join(f"{k}={v:.3f}" for k, v in kernels), file=sys.stderr)
+    if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)
     if use_dist:
         dist.barrier()

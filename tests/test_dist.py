@@ -175,6 +175,38 @@ def test_bench_rejects_a_world_size_that_contradicts_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
 
 
+def test_bench_rejects_zero_steps_and_a_dump_without_features(tmp_path):
+    r = _run_bench(["--dry-run", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+    r = _run_bench(["--dry-run", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not (tmp_path / "out").exists()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_timed_step(tmp_path):
+    """A plain run prints the headline only (spread, roofline and CPU baseline are --full) over exactly --steps timed steps;
+    --dump-outputs writes the last timed step's features, the same bits with and without --full (the dump comes from the
+    first timed block, the one `value` is measured on)."""
+    import json
+    runs = {"plain": [], "full": ["--full", "--no-cpu-baseline", "--profile-passes", "1", "--spread-blocks", "2"]}
+    outs, feats = {}, {}
+    for name, extra in runs.items():
+        r = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / name)] + extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        outs[name] = out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "patches/s" and out["higher_is_better"] is True
+        assert out["dtype"] == "f16" and out["value"] > 0
+        assert out["value"] * out["ms_per_step"] * 1e-3 == pytest.approx(256)      # one step = 256 patches
+        feats[name] = f = np.load(tmp_path / name / "features.npy")
+        assert f.shape == (256, 1280) and f.dtype == np.float32 and np.isfinite(f).all()
+    assert not {"spread", "roofline", "cpu_baseline"} & outs["plain"].keys()
+    assert outs["full"]["spread"]["blocks"] == 2 and outs["full"]["roofline"]["launches_per_step"] > 0
+    assert "cpu_baseline" not in outs["full"]
+    np.testing.assert_array_equal(feats["plain"], feats["full"])
+
+
 @pytest.mark.gpu
 def test_two_rank_rccl_gather_is_in_patch_order():
     """gather_features over RCCL with a ragged n_total, one rank per GPU -- needs two GPUs (the 1-GPU test box skips it; RCCL

@@ -16,7 +16,7 @@ MODE=${1:?mode}; TAG=${2:?tag}; shift 2
 O=gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-BENCH_CMD=${CMD_OVERRIDE:-"python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --profile-passes 1 --spread-blocks 1"}
+BENCH_CMD=${CMD_OVERRIDE:-"python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --profile-passes 1 --spread-blocks 1"}
 line() { python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$1', round(d['value']), 'patches/s', round(d['ms_per_step'],3), 'ms', r['kernel'], round(r['avg_launch_us'],1), 'us frac', round(r['frac'],4))"; }
 
 pmc() { # name, counters...
@@ -31,7 +31,7 @@ counters() {
   pmc write WRITE_SIZE
 }
 stats() {
-  local cmd=${CMD_OVERRIDE:-"python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --profile-passes 1 --spread-blocks 1"}
+  local cmd=${CMD_OVERRIDE:-"python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --profile-passes 1 --spread-blocks 1"}
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $cmd > $O/stats.log 2>&1; echo "rocprof stats exit $?"
 }
 
@@ -42,19 +42,19 @@ iter)
   python tools/layer_profile.py 2>&1 | tee $O/lp.log | grep -v amdgpu.ids
   for t in ${TUNES:-0}; do
     MMC_T7_TUNE0=$t python tools/tail_phases.py 256 2>&1 | tee -a $O/tp.log | grep -v amdgpu.ids
-    MMC_T7_TUNE0=$t python bench.py --no-cpu-baseline 2> $O/bench.err | tee $O/bench.json | line bench
+    MMC_T7_TUNE0=$t python bench.py --full --no-cpu-baseline 2> $O/bench.err | tee $O/bench.json | line bench
   done ;;
 round)
   python -m pytest tests -x -q -m gpu -s > $O/pytest.log 2>&1; rc=$?; echo "pytest exit $rc"; tail -2 $O/pytest.log
   [ $rc -ne 0 ] && exit $rc
-  python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; cat $O/bench.json; tail -1 $O/bench.err
+  python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; cat $O/bench.json; tail -1 $O/bench.err
   python tools/layer_profile.py > $O/lp.log 2>&1
   python tools/tail_phases.py 256 > $O/tp.log 2>&1
   stats && counters ;;
 counters) counters ;;
 stats) stats ;;
 lanes)
-  for l in 1 2 3 4; do MMC_LANES=$l python bench.py --no-cpu-baseline 2> $O/l$l.err | line "lanes $l" | tee -a $O/lanes.log; done ;;
+  for l in 1 2 3 4; do MMC_LANES=$l python bench.py --full --no-cpu-baseline 2> $O/l$l.err | line "lanes $l" | tee -a $O/lanes.log; done ;;
 libvar)
   what=${1:-bench}
   for f in mermaid_classifier_amd/libmermaid_mi355.so build_variants/*.so; do
@@ -62,7 +62,7 @@ libvar)
     case $what in
     bench)
       MMC_LIBRARY=$f python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "golden or batch" > $O/$n.pytest 2>&1; tail -1 $O/$n.pytest
-      MMC_LIBRARY=$f python bench.py --no-cpu-baseline 2> $O/$n.err | line $n | tee -a $O/libvar.log ;;
+      MMC_LIBRARY=$f python bench.py --full --no-cpu-baseline 2> $O/$n.err | line $n | tee -a $O/libvar.log ;;
     lp) MMC_LIBRARY=$f python tools/layer_profile.py > $O/$n.lp 2>&1; grep "${2:-sum of}" $O/$n.lp ;;
     tp) MMC_LIBRARY=$f python tools/tail_phases.py 256 2>&1 | grep -v amdgpu | tee $O/$n.tp ;;
     esac

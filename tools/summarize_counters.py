@@ -53,7 +53,7 @@ def load(d):
 def main():
     tag, base = sys.argv[1], sys.argv[2]
     suffix = sys.argv[3] if len(sys.argv) > 3 else ""
-    what = sys.argv[4] if len(sys.argv) > 4 else ("python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --profile-passes 1` (tools/gpu.sh counters; one counter "
+    what = sys.argv[4] if len(sys.argv) > 4 else ("python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --profile-passes 1` (tools/gpu.sh counters; one counter "
                                                   "group per run; every launch covers one lane = 128 patches")
     passes = {p: load(f"{base}/{p}") for p in ("sq1", "sq2", "tcc", "fetch", "write")}
 
