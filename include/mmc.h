@@ -180,8 +180,40 @@ int mmc_trainer_get_params(mmc_trainer* t, float* const* W, float* const* b);
  * reference pickles as the optimizer state dict (torch_classifier.py:404-415). */
 int mmc_trainer_adam_state(mmc_trainer* t, int which, int set, float* const* W, float* const* b, long long* step);
 /* Raw logits of the current parameters: X n x dims[0] host -> logits n x K host (the softmax / float64 renormalisation of
- * _forward_probs, torch_classifier.py:332-376, stays on the host). */
+ * _forward_probs, torch_classifier.py:332-376, stays on the host; mmc_calibrator_add_features / mmc_trainer_evaluate below do it on
+ * the device). */
 int mmc_trainer_logits(mmc_trainer* t, const float* X, int64_t n, float* logits, void* hip_stream);
+
+/* ---- evaluation and Platt calibration of the trained classifier ------------------------------------------------------
+ * Replaces the host steps the reference's MermaidTrainer takes after partial_fit, all fed there by predict_proba:
+ *   mmc_trainer_evaluate: _calc_acc_batched (mermaid_classifier/pyspacer/trainer.py:295-307) and
+ *     _calc_acc_and_log_loss_batched (:309-342) -- accuracy_score and sklearn.metrics.log_loss(labels=classes_) of predict_proba;
+ *   mmc_calibrator_*: _calibrate_in_batches (:344-396) -- sklearn.calibration._fit_calibrator(clf, predict_proba, y, classes_,
+ *     "sigmoid"): one Platt sigmoid per class (objective and start point of _sigmoid_calibration; damped Newton in fp64 on the
+ *     device).  The calibrated model is then served by mmc_head_* with a / b.
+ * The probabilities are those of mmc_trainer_logits + _forward_probs (fp32 softmax, float64 renormalisation); they stay on the
+ * device (fp32, class-major).  Host pointers throughout; every call synchronises `hip_stream` before returning.
+ * Labels y are class indices in [0, K).  Results are bit-reproducible; the fit does not depend on how the rows are split over calls. */
+typedef struct mmc_calibrator mmc_calibrator;
+int mmc_calibrator_create(int K, int device, mmc_calibrator** out);          /* K >= 3 (CalibratedHead is multiclass only) */
+void mmc_calibrator_destroy(mmc_calibrator* c);
+/* rows of X (host, n x dims[0] fp32) through t's current parameters; probabilities stay on the device */
+int mmc_calibrator_add_features(mmc_calibrator* c, mmc_trainer* t, const float* X, const int32_t* y, int64_t n, void* hip_stream);
+/* caller-computed scores (host, n x K float64, row-major), e.g. another model's predict_proba / decision values; stored as fp32,
+ * so non-finite scores and |score| > FLT_MAX are rejected */
+int mmc_calibrator_add_scores(mmc_calibrator* c, const double* scores, const int32_t* y, int64_t n, void* hip_stream);
+/* per-class Platt slope / intercept (K doubles each) over every row added so far: calibrated p_k = 1 / (1 + exp(a_k s + b_k)),
+ * as _SigmoidCalibration.predict; iterations: K int32 (Newton trial points evaluated per class, at most 100) or NULL */
+int mmc_calibrator_fit(mmc_calibrator* c, double* a, double* b, int32_t* iterations, void* hip_stream);
+/* sums over the n rows: correct argmax count and sum of -log(clip(p_y)); the caller divides (streams add up).
+ * The per-row term is rounded to 2^-32 and summed exactly in int64; *sum_log_loss is that sum as a double, which adds up
+ * exactly over calls only while the total stays below 2^21.  At most 2^25 rows per call. */
+int mmc_trainer_evaluate(mmc_trainer* t, const float* X, const int32_t* y, int64_t n, int64_t* n_correct,
+                         double* sum_log_loss, void* hip_stream);
+/* The same with the log-loss sum as the int64 it is computed in (units of 2^-32): integer sums over calls are exact for any
+ * split of the rows.  (No reference counterpart; what the Python evaluate() accumulates.) */
+int mmc_trainer_evaluate_q32(mmc_trainer* t, const float* X, const int32_t* y, int64_t n, int64_t* n_correct,
+                             int64_t* sum_log_loss_q32, void* hip_stream);
 
 /* ---- multi-GPU: the gather of the sharded path --------------------------------------------------------------------
  * The path shards by patches (contiguous blocks of the row range per rank, weights replicated, no exchange during compute);

@@ -24,7 +24,8 @@ SYMBOLS = [
     "mmc_backbone_profile", "mmc_backbone_graph_stats", "mmc_crop_patches",
     "mmc_head_create", "mmc_head_destroy", "mmc_head_input_dim", "mmc_head_num_classes", "mmc_head_predict",
     "mmc_trainer_create", "mmc_trainer_destroy", "mmc_trainer_partial_fit", "mmc_trainer_partial_fit_ordered", "mmc_trainer_get_params", "mmc_trainer_adam_state",
-    "mmc_trainer_logits",
+    "mmc_trainer_logits", "mmc_trainer_evaluate", "mmc_trainer_evaluate_q32",
+    "mmc_calibrator_create", "mmc_calibrator_destroy", "mmc_calibrator_add_features", "mmc_calibrator_add_scores", "mmc_calibrator_fit",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -106,6 +107,20 @@ def _load() -> C.CDLL:
     lib.mmc_trainer_adam_state.argtypes = [vp, i32, i32, C.POINTER(fp), C.POINTER(fp), C.POINTER(C.c_longlong)]
     lib.mmc_trainer_logits.restype = i32
     lib.mmc_trainer_logits.argtypes = [vp, vp, i64, vp, vp]
+    lib.mmc_trainer_evaluate.restype = i32
+    lib.mmc_trainer_evaluate.argtypes = [vp, vp, vp, i64, C.POINTER(i64), C.POINTER(f64), vp]
+    lib.mmc_trainer_evaluate_q32.restype = i32
+    lib.mmc_trainer_evaluate_q32.argtypes = [vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), vp]
+    lib.mmc_calibrator_create.restype = i32
+    lib.mmc_calibrator_create.argtypes = [i32, i32, C.POINTER(vp)]
+    lib.mmc_calibrator_destroy.restype = None
+    lib.mmc_calibrator_destroy.argtypes = [vp]
+    lib.mmc_calibrator_add_features.restype = i32
+    lib.mmc_calibrator_add_features.argtypes = [vp, vp, vp, vp, i64, vp]
+    lib.mmc_calibrator_add_scores.restype = i32
+    lib.mmc_calibrator_add_scores.argtypes = [vp, vp, vp, i64, vp]
+    lib.mmc_calibrator_fit.restype = i32
+    lib.mmc_calibrator_fit.argtypes = [vp, vp, vp, vp, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

@@ -21,6 +21,7 @@
 
 #include "../../include/mmc.h"
 #include "kernels.h"
+#include "trainer_internal.h"
 
 namespace {
 
@@ -250,6 +251,8 @@ struct mmc_trainer {
     double lr = 1e-3, beta1 = 0.9, beta2 = 0.999, eps = 1e-8, alpha = 1e-4;   // kept in double: torch derives its fp32 scalars from python floats
     long long t = 0;                                    // Adam step count
     std::vector<float> cw_host;
+    void* scratch = nullptr;                            // trainer_scratch (calib.hip's evaluation buffers)
+    size_t scratch_bytes = 0;
 };
 
 #define T_TRY(expr)                                                                                   \
@@ -277,7 +280,7 @@ extern "C" void mmc_trainer_destroy(mmc_trainer* t)
     for (size_t l = 1; l < t->H.size(); ++l) hipFree(t->H[l]);
     for (size_t l = 1; l < t->dZ.size(); ++l) hipFree(t->dZ[l]);
     hipFree(t->cw); hipFree(t->X); hipFree(t->row_loss); hipFree(t->partials); hipFree(t->losses); hipFree(t->y);
-    hipFree(t->Xn); hipFree(t->yn); hipFree(t->order);
+    hipFree(t->Xn); hipFree(t->yn); hipFree(t->order); hipFree(t->scratch);
     delete t;
 }
 
@@ -500,6 +503,41 @@ extern "C" int mmc_trainer_adam_state(mmc_trainer* t, int which, int set, float*
     return MMC_OK;
 }
 
+// forward of the current parameters (eval mode) on n <= kTrainerForwardRows host rows: uploads X into the trainer's input buffer
+// and leaves the logits [n][K] in its last activation buffer (valid until the next call on `t`)
+int trainer_forward(mmc_trainer* t, const float* X, int n, hipStream_t st, const float** logits)
+{
+    if (n < 1 || n > kTrainerForwardRows) return mmc_fail(MMC_ERR_ARG, "trainer_forward: n = %d outside [1, %d]", n, kTrainerForwardRows);
+    T_TRY(hipSetDevice(t->device));
+    int r = trainer_reserve(t, n, n, 1);
+    if (r) return r;
+    T_TRY(hipMemcpyAsync(t->X, X, (size_t)n * t->dims[0] * 4, hipMemcpyHostToDevice, st));
+    t->H[0] = t->X;
+    for (int l = 0; l < t->L; ++l)
+        T_K((launch_tgemm<false, true>(t->H[l], t->W[l], t->H[l + 1], n, t->dims[l + 1], t->dims[l],
+                                      l == t->L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU, t->b[l], 0.f, st)));
+    *logits = t->H[t->L];
+    return MMC_OK;
+}
+
+int trainer_scratch(mmc_trainer* t, size_t bytes, void** out)
+{
+    if (bytes > t->scratch_bytes) {
+        T_TRY(hipSetDevice(t->device));
+        hipFree(t->scratch);   // only on growth: the buffer is kept for the trainer's lifetime
+        t->scratch = nullptr;
+        t->scratch_bytes = 0;
+        T_TRY(hipMalloc(&t->scratch, bytes));
+        t->scratch_bytes = bytes;
+    }
+    *out = t->scratch;
+    return MMC_OK;
+}
+
+int trainer_classes(const mmc_trainer* t) { return t->K; }
+int trainer_input_dim(const mmc_trainer* t) { return t->dims[0]; }
+int trainer_device(const mmc_trainer* t) { return t->device; }
+
 // logits of the current parameters (eval mode): X n x dims[0] host -> logits n x K host
 extern "C" int mmc_trainer_logits(mmc_trainer* t, const float* X, int64_t n, float* logits, void* hip_stream)
 {
@@ -508,18 +546,12 @@ extern "C" int mmc_trainer_logits(mmc_trainer* t, const float* X, int64_t n, flo
     if (n == 0) return MMC_OK;
     if (!X || !logits) return mmc_fail(MMC_ERR_ARG, "X/logits is NULL");
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    T_TRY(hipSetDevice(t->device));
-    const int64_t chunk = 16384;
-    for (int64_t off = 0; off < n; off += chunk) {
-        const int cur = (int)((n - off) < chunk ? (n - off) : chunk);
-        int r = trainer_reserve(t, cur, cur, 1);
+    for (int64_t off = 0; off < n; off += kTrainerForwardRows) {
+        const int cur = (int)((n - off) < kTrainerForwardRows ? (n - off) : kTrainerForwardRows);
+        const float* z = nullptr;
+        int r = trainer_forward(t, X + (size_t)off * t->dims[0], cur, st, &z);
         if (r) return r;
-        T_TRY(hipMemcpyAsync(t->X, X + (size_t)off * t->dims[0], (size_t)cur * t->dims[0] * 4, hipMemcpyHostToDevice, st));
-        t->H[0] = t->X;
-        for (int l = 0; l < t->L; ++l)
-            T_K((launch_tgemm<false, true>(t->H[l], t->W[l], t->H[l + 1], cur, t->dims[l + 1], t->dims[l],
-                                          l == t->L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU, t->b[l], 0.f, st)));
-        T_TRY(hipMemcpyAsync(logits + (size_t)off * t->K, t->H[t->L], (size_t)cur * t->K * 4, hipMemcpyDeviceToHost, st));
+        T_TRY(hipMemcpyAsync(logits + (size_t)off * t->K, z, (size_t)cur * t->K * 4, hipMemcpyDeviceToHost, st));
         T_TRY(hipStreamSynchronize(st));
     }
     return MMC_OK;

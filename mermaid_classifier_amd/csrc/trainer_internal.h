@@ -1,0 +1,25 @@
+// trainer_internal.h -- what calib.hip takes from trainer.hip: the eval-mode forward of a trainer's current parameters.
+// Library-internal; not part of the C ABI (include/mmc.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+struct mmc_trainer;
+
+// sets the thread-local message mmc_last_error() returns and hands back `code` (defined in mmc_api.cpp)
+int mmc_fail(int code, const char* fmt, ...);
+
+// rows per trainer_forward call (the trainer's activation buffers are sized for at most this many)
+constexpr int kTrainerForwardRows = 16384;
+
+int trainer_classes(const mmc_trainer* t);     // K = dims[n_layers]
+int trainer_input_dim(const mmc_trainer* t);   // dims[0]
+int trainer_device(const mmc_trainer* t);
+
+// *out = a device buffer of at least `bytes` owned by the trainer (grown on demand, freed with it), for work that runs on the
+// trainer's stream: calib.hip's evaluation labels and partial sums, so that an evaluation per batch allocates nothing.
+int trainer_scratch(mmc_trainer* t, size_t bytes, void** out);
+
+// Uploads n (1..kTrainerForwardRows) host rows X[n][dims[0]] and runs Linear/ReLU ... Linear on `st` with the exact kernels of
+// a training step's forward; *logits = device [n][K] fp32, valid until the next call on `t` (stream-ordered, no sync).
+int trainer_forward(mmc_trainer* t, const float* X, int n, hipStream_t st, const float** logits);
