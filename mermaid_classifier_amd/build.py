@@ -28,7 +28,7 @@ SOURCES = {
     "k_early.hip": KERNEL_HEADERS,
     "k_mid.hip": KERNEL_HEADERS,
     "k_tail.hip": KERNEL_HEADERS,
-    "trainer.hip": ["../../include/mmc.h", "trainer_internal.h"],
+    "trainer.hip": ["../../include/mmc.h", "trainer_internal.h", "kernels.h"],
     "calib.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "mmc_api.cpp": ["kernels.h", "../../include/mmc.h"],
     "mmc_dist.cpp": ["../../include/mmc.h"],

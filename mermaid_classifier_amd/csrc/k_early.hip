@@ -1117,7 +1117,7 @@ __global__ __launch_bounds__(256) void stem_dw_kernel(const uint8_t* __restrict_
 // =============================================================================================
 // Host-side launchers (plain C++ signatures declared in kernels.h)
 // =============================================================================================
-int thin_proj_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }   // the k-step counts launch_thin_proj instantiates
+int thin_proj_has(int ksteps) { return ksteps >= 1 && ksteps <= 5; }   // the k-step counts launch_thin_proj instantiates
 
 int launch_thin_proj(const GemmArgs& a, int patches, hipStream_t st)
 {
@@ -1143,8 +1143,6 @@ int launch_thin_proj(const GemmArgs& a, int patches, hipStream_t st)
     else if (ks == 4) TP_GO(4, false);
     else if (ks == 5 && a.res) TP_GO(5, true);
     else if (ks == 5) TP_GO(5, false);
-    else if (ks == 6 && a.res) TP_GO(6, true);
-    else if (ks == 6) TP_GO(6, false);
     else return -15;
 #undef TP_GO
     LAUNCH_CHECK();

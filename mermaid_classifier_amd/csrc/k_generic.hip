@@ -834,13 +834,10 @@ __global__ __launch_bounds__(256) void se_small_kernel(const float* __restrict__
     }
 }
 
-// se_wide_kernel: the same computation without the size limits (any C, any Cs; pooled vectors and squeeze units in
-// dynamic LDS) -- the squeeze-excite of the generic per-layer schedule (EfficientNet-B4: C <= 2688, Cs <= 112).
-// One workgroup takes PB consecutive patches so that a weight element fetched from L2 serves PB patches (one workgroup per
-// patch re-read up to 1.2 MB per FC: 19 % of B4's time); each patch's own arithmetic sequence is that of PB = 1, so results
-// do not depend on how patches are grouped.
-template <int PB>
-__global__ __launch_bounds__(1024) void se_wide_kernel(const float* __restrict__ pool_part, int nparts, int nB, int C, int Cs,
+// se_wide_kernel: the same computation without the size limits (any C, any Cs; pooled vector and squeeze units in
+// dynamic LDS) -- the squeeze-excite of the generic per-layer schedule (EfficientNet-B4: C <= 2688, Cs <= 112).  One workgroup
+// per patch.
+__global__ __launch_bounds__(1024) void se_wide_kernel(const float* __restrict__ pool_part, int nparts, int C, int Cs,
                                                       const float* __restrict__ wr,   // [Cs][C], carries 1/(HW log2e)
                                                       const float* __restrict__ br,   // [Cs]
                                                       const float* __restrict__ we,   // [Cs][C] (transposed: lanes read neighbours)
@@ -848,78 +845,61 @@ __global__ __launch_bounds__(1024) void se_wide_kernel(const float* __restrict__
                                                       float* __restrict__ gate)       // [B][C]
 {
     extern __shared__ float se_sm[];
-    float* pooled = se_sm;            // [PB][C]
-    float* rs = se_sm + PB * C;       // [PB][Cs]
+    float* pooled = se_sm;            // [C]
+    float* rs = se_sm + C;            // [Cs]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b0 = blockIdx.x * PB;
-    const int nb = (nB - b0) < PB ? (nB - b0) : PB;
-    for (int pb = 0; pb < nb; ++pb)
-        for (int c = tid; c < C; c += 1024) {
-            const float* pp = pool_part + (size_t)(b0 + pb) * nparts * C + c;
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-            int p = 0;
-            for (; p + 3 < nparts; p += 4) {
-                s0 += pp[(size_t)p * C];
-                s1 += pp[(size_t)(p + 1) * C];
-                s2 += pp[(size_t)(p + 2) * C];
-                s3 += pp[(size_t)(p + 3) * C];
-            }
-            for (; p < nparts; ++p) s0 += pp[(size_t)p * C];
-            pooled[pb * C + c] = (s0 + s1) + (s2 + s3);
+    const int b = blockIdx.x;
+    for (int c = tid; c < C; c += 1024) {
+        const float* pp = pool_part + (size_t)b * nparts * C + c;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int p = 0;
+        for (; p + 3 < nparts; p += 4) {
+            s0 += pp[(size_t)p * C];
+            s1 += pp[(size_t)(p + 1) * C];
+            s2 += pp[(size_t)(p + 2) * C];
+            s3 += pp[(size_t)(p + 3) * C];
         }
-    for (int pb = nb; pb < PB; ++pb)
-        for (int c = tid; c < C; c += 1024) pooled[pb * C + c] = 0.f;
+        for (; p < nparts; ++p) s0 += pp[(size_t)p * C];
+        pooled[c] = (s0 + s1) + (s2 + s3);
+    }
     __syncthreads();
     for (int j = wave; j < Cs; j += 16) {   // 16 waves: the FC1 rows are a latency chain per wave
-        float s[PB];
-#pragma unroll
-        for (int pb = 0; pb < PB; ++pb) s[pb] = 0.f;
+        float s = 0.f;
         // sixteen weights requested per round trip (unconditional, clamped; round 3: the loop was load -> wait -> fma, one exposed L2
         // round trip per 64 channels -- up to 42 per row); the products are summed in the same order as before
         for (int c0 = lane; c0 < C; c0 += 1024) {
             float w[16];
 #pragma unroll
             for (int u = 0; u < 16; ++u) w[u] = wr[(size_t)j * C + (c0 + 64 * u < C ? c0 + 64 * u : C - 1)];
-            // (the pool sums of eight channels x PB patches per LDS round trip: read inside the FMA loop they were one exposed round
-            // trip per FMA)
+            // (the pool sums of eight channels per LDS round trip: read inside the FMA loop they were one exposed round trip per FMA)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                float x[8][PB];
+                float x[8];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int c = c0 + 64 * (8 * h + u);
-                    const int cl = c < C ? c : C - 1;
-#pragma unroll
-                    for (int pb = 0; pb < PB; ++pb) x[u][pb] = pooled[pb * C + cl];
+                    x[u] = pooled[c < C ? c : C - 1];
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int c = c0 + 64 * (8 * h + u);
-#pragma unroll
-                    for (int pb = 0; pb < PB; ++pb) s[pb] = c < C ? __builtin_fmaf(x[u][pb], w[8 * h + u], s[pb]) : s[pb];
+                    s = c < C ? __builtin_fmaf(x[u], w[8 * h + u], s) : s;
                 }
             }
         }
 #pragma unroll
-        for (int pb = 0; pb < PB; ++pb) {
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) s[pb] += __shfl_xor(s[pb], o);
-            if (lane == 0) rs[pb * Cs + j] = silu_f(s[pb] + br[j]);
-        }
+        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0) rs[j] = silu_f(s + br[j]);
     }
     __syncthreads();
     // excite FC: a thread's (up to three) channels advance together, sixteen squeeze units per round trip: 48 requests in flight
     // (round 3: one request, one wait, one fma -- up to 3 x 112 exposed L2 round trips per thread); same summation order per channel
     {
         constexpr int NC = 3;   // C <= 3072
-        float acc[NC][PB];
+        float acc[NC];
 #pragma unroll
-        for (int k = 0; k < NC; ++k) {
-            const int c = tid + 1024 * k < C ? tid + 1024 * k : C - 1;
-#pragma unroll
-            for (int pb = 0; pb < PB; ++pb) acc[k][pb] = be[c];
-        }
+        for (int k = 0; k < NC; ++k) acc[k] = be[tid + 1024 * k < C ? tid + 1024 * k : C - 1];
         for (int j0 = 0; j0 < Cs; j0 += 16) {
             float w[NC][16];
 #pragma unroll
@@ -930,29 +910,21 @@ __global__ __launch_bounds__(1024) void se_wide_kernel(const float* __restrict__
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                float r[8][PB];   // (eight squeeze units x PB patches per LDS round trip)
+                float r[8];   // (eight squeeze units per LDS round trip)
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int j = j0 + 8 * h + u < Cs ? j0 + 8 * h + u : Cs - 1;
-#pragma unroll
-                    for (int pb = 0; pb < PB; ++pb) r[u][pb] = rs[pb * Cs + j];
-                }
+                for (int u = 0; u < 8; ++u) r[u] = rs[j0 + 8 * h + u < Cs ? j0 + 8 * h + u : Cs - 1];
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
 #pragma unroll
-                    for (int pb = 0; pb < PB; ++pb)
-#pragma unroll
-                        for (int k = 0; k < NC; ++k)
-                            acc[k][pb] = j0 + 8 * h + u < Cs ? __builtin_fmaf(r[u][pb], w[k][8 * h + u], acc[k][pb]) : acc[k][pb];
+                    for (int k = 0; k < NC; ++k)
+                        acc[k] = j0 + 8 * h + u < Cs ? __builtin_fmaf(r[u], w[k][8 * h + u], acc[k]) : acc[k];
             }
         }
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
             const int c = tid + 1024 * k;
-#pragma unroll
-            for (int pb = 0; pb < PB; ++pb)
-                if (c < C && pb < nb) gate[(size_t)(b0 + pb) * C + c] = sigmoid_f(acc[k][pb]);
+            if (c < C) gate[(size_t)b * C + c] = sigmoid_f(acc[k]);
         }
     }
 }
@@ -1246,13 +1218,8 @@ int launch_se_small(const float* pool_part, int nparts, int B, int C, int Cs, co
 int launch_se_wide(const float* pool_part, int nparts, int B, int C, int Cs, const float* wr, const float* br,
                    const float* we_t, const float* be, float* gate, hipStream_t st)
 {
-    static const int PB = [] { const char* e = getenv("MMC_SE_PB"); const int v = e ? atoi(e) : 1; return v == 2 || v == 4 ? v : 1; }();
-    if (B < 1 || C < 1 || C > 3072 || Cs < 1 || (size_t)PB * (C + Cs) * 4 > 64000) return -12;   // (3072: three channels per thread in the excite FC)
-    const dim3 grid((B + PB - 1) / PB);
-    const size_t shm = (size_t)PB * (C + Cs) * sizeof(float);
-    if (PB == 1) hipLaunchKernelGGL(se_wide_kernel<1>, grid, dim3(1024), shm, st, pool_part, nparts, B, C, Cs, wr, br, we_t, be, gate);
-    else if (PB == 2) hipLaunchKernelGGL(se_wide_kernel<2>, grid, dim3(1024), shm, st, pool_part, nparts, B, C, Cs, wr, br, we_t, be, gate);
-    else hipLaunchKernelGGL(se_wide_kernel<4>, grid, dim3(1024), shm, st, pool_part, nparts, B, C, Cs, wr, br, we_t, be, gate);
+    if (B < 1 || C < 1 || C > 3072 || Cs < 1 || (size_t)(C + Cs) * 4 > 64000) return -12;   // (3072: three channels per thread in the excite FC)
+    hipLaunchKernelGGL(se_wide_kernel, dim3(B), dim3(1024), (size_t)(C + Cs) * sizeof(float), st, pool_part, nparts, C, Cs, wr, br, we_t, be, gate);
     LAUNCH_CHECK();
     return 0;
 }

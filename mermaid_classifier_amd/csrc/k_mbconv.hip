@@ -22,7 +22,8 @@
 // PB > 1 (whole-image tiles only: 7x7 layers): one workgroup takes PB consecutive patches, so the chunk's
 // weight fragments are streamed once per PB patches and all four waves have MFMA fragments to work on.
 // WLDS: the chunk's expand weights (fragment order, Wfrag) are copied to LDS in one burst at kernel start and
-// read back lane-linearly per MFMA; otherwise fragments stream from L2 (Wexp rows), one fragment ahead.
+// read back lane-linearly per MFMA; otherwise fragments stream from L2 (Wexp rows), one fragment ahead.  (The launchers
+// instantiate WLDS = false only: no layer's tile configuration selects the LDS copy.)
 // PRE (block 1 only): the kernel's input is block 0's DEPTHWISE output [B][H][W][32]; block 0's squeeze-excite scale and
 // project conv (32 -> 16, one MFMA per 16 positions) run on the freshly loaded fragments, so block 0's output tensor and
 // its project launch do not exist.  The project result lands as 4 consecutive channels per lane (4q..4q+3); the expand
@@ -549,31 +550,16 @@ template <int KS, int ST, int TW, int KSTEPS, int NPAIR, int CC, int TWO, int PB
 static int launch_mbconv_t(const MbArgs& a, hipStream_t st)
 {
     dim3 grid(a.tiles_x * a.tiles_y, a.Ce / a.CC, (a.B + PB - 1) / PB);
-    if (a.wlds) {
-        static bool attr_done = false;  // more than the default 64 KB of dynamic LDS
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&mbconv_a_kernel<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB, true>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-            attr_done = true;
-        }
-        hipLaunchKernelGGL((mbconv_a_kernel<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB, true>), grid, dim3(256), a.lds_bytes,
-                           st, a.X, a.Wexp, a.bexp, a.Wdw, a.bdw, a.out, a.pool_part, a.H, a.W, a.Cin, a.Ce, a.Ho, a.Wo,
-                           a.pad, a.TH, a.tiles_x, a.wl_off, a.red_off, a.B, a.Wfrag, a.wfr_off);
-    } else {
-        static bool attr_done2 = false;
-        if (!attr_done2 && a.lds_bytes > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&mbconv_a_kernel<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB, false>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-            attr_done2 = true;
-        }
-        hipLaunchKernelGGL((mbconv_a_kernel<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB, false>), grid, dim3(256), a.lds_bytes,
-                           st, a.X, a.Wexp, a.bexp, a.Wdw, a.bdw, a.out, a.pool_part, a.H, a.W, a.Cin, a.Ce, a.Ho, a.Wo,
-                           a.pad, a.TH, a.tiles_x, a.wl_off, a.red_off, a.B, a.Wfrag, a.wfr_off);
+    static bool attr_done = false;
+    if (!attr_done && a.lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mbconv_a_kernel<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB, false>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return (int)e;
+        attr_done = true;
     }
+    hipLaunchKernelGGL((mbconv_a_kernel<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB, false>), grid, dim3(256), a.lds_bytes, st, a.X, a.Wexp,
+                       a.bexp, a.Wdw, a.bdw, a.out, a.pool_part, a.H, a.W, a.Cin, a.Ce, a.Ho, a.Wo, a.pad, a.TH, a.tiles_x, a.wl_off,
+                       a.red_off, a.B, a.Wfrag, a.wfr_off);
     LAUNCH_CHECK();
     return 0;
 }
@@ -582,7 +568,7 @@ int launch_mbconv_pre(const MbArgs& a, const _Float16* pre_w, const float* pre_b
 {
     // block 1 with block 0's squeeze-excite scale + project conv folded in (mbconv_a_kernel, PRE)
     if (!(a.ks == 3 && a.stride == 2 && a.tw == 2 && a.ksteps == 1 && a.npair == 3 && a.CC == 48 && a.TWo == 8 && a.pb == 1 &&
-          a.Cin == 32 && !a.wlds))
+          a.Cin == 32))
         return -13;
     dim3 grid(a.tiles_x * a.tiles_y, a.Ce / a.CC, a.B);
     hipLaunchKernelGGL((mbconv_a_kernel<3, 2, 2, 1, 3, 48, 8, 1, false, true>), grid, dim3(256), a.lds_bytes, st, a.X, a.Wexp,
@@ -603,11 +589,8 @@ int launch_mbconv_a(const MbArgs& a, hipStream_t st)
     MB_CASE(3, 1, 2, 1, 2, 48, 14, 1)    // b2
     MB_CASE(5, 2, 2, 1, 3, 48, 14, 1)    // b3
     MB_CASE(5, 1, 2, 2, 3, 48, 14, 1)    // b4
-    MB_CASE(3, 2, 2, 2, 2, 80, 14, 1)    // b5
     MB_CASE(3, 1, 2, 3, 2, 96, 14, 1)    // b6, b7
-    MB_CASE(5, 1, 1, 6, 1, 192, 7, 1)    // b12-b14, one patch per workgroup
-    MB_CASE(3, 1, 1, 6, 1, 192, 7, 1)    // b15
-    MB_CASE(5, 1, 1, 6, 1, 96, 7, 2)     // b12-b14, two patches per workgroup
+    MB_CASE(5, 1, 1, 6, 1, 96, 7, 2)     // b12-b14
     MB_CASE(5, 1, 2, 3, 2, 48, 14, 1)    // b8
     MB_CASE(5, 1, 2, 4, 2, 48, 14, 1)    // b9, b10
     MB_CASE(5, 2, 1, 4, 2, 48, 7, 1)     // b11
@@ -616,9 +599,8 @@ int launch_mbconv_a(const MbArgs& a, hipStream_t st)
     // EfficientNet-B4 (generic_fuse_cfg): blocks 2-9 and 16 reuse the instantiations above
     MB_CASE(3, 2, 2, 2, 2, 48, 14, 1)    // B4 b10
     MB_CASE(3, 1, 2, 4, 2, 96, 14, 1)    // B4 b11-b15
-    MB_CASE(5, 1, 2, 5, 2, 48, 14, 1)    // B4 b17-b21
-    MB_CASE(5, 1, 2, 5, 2, 96, 14, 1)    // (MMC_B4_CC14=96)
-    MB_CASE(5, 1, 2, 4, 2, 96, 14, 1)
+    MB_CASE(5, 1, 2, 4, 2, 96, 14, 1)    // B4 b16
+    MB_CASE(5, 1, 2, 5, 2, 96, 14, 1)    // B4 b17-b21
     MB_CASE(5, 2, 1, 5, 2, 48, 7, 1)     // B4 b22
     MB_CASE(5, 1, 1, 9, 1, 96, 7, 2)     // B4 b23-b29
     MB_CASE(3, 1, 1, 9, 1, 96, 7, 2)     // B4 b30

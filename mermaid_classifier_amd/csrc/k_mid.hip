@@ -16,15 +16,10 @@
 //            channels: 128-byte segments); pool sums per band -> LDS -> one value per channel.
 // Output: D[B][196][CE] and pool[B][CE] -- what proj_patch_kernel consumes.
 // ---------------------------------------------------------------------------------------------
-// ST = 2 (block 11: 5x5 stride 2, 14x14 -> 7x7, TF-same pad 1): the same expand; a depthwise thread = (channel, band of 2
-// output rows) with the same 7x7 pixel-pair window (input rows 4*band-1 .. 4*band+5); output x reads pairs x-1, x, x+1 with the
-// tap pairs (0,k0), (k1,k2), (k3,k4) -- the odd-x variant of the stride-1 taps; four bands, output D[B][49][CE].
-template <int CKS, int KSD, int CE, int ST = 1>
+template <int CKS, int KSD, int CE>
 __global__ __launch_bounds__(512) void mid14_kernel(Mid14Args a)
 {
-    static_assert(ST == 1 || (ST == 2 && KSD == 5), "stride 2 is the 5x5 block 11");
-    constexpr int HW = 196, CH = 96, NCHK = CE / CH, NPF = 13, NTILE = 6 * NPF;
-    constexpr int HWO = ST == 1 ? 196 : 49, NBAND = ST == 1 ? 5 : 4;
+    constexpr int HW = 196, CH = 96, NCHK = CE / CH, NPF = 13, NTILE = 6 * NPF, NBAND = 5;
     constexpr int ES2 = 416;                // bytes per row of E2[98 pixel pairs][96 channels] (one dword = pixels 2p, 2p+1 of a
                                             // channel); 104 dwords: the four lane quarters of a store land in disjoint banks
     constexpr int R = KSD / 2, NP = KSD == 5 ? 3 : 2;
@@ -32,7 +27,7 @@ __global__ __launch_bounds__(512) void mid14_kernel(Mid14Args a)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // Zero rows above and below the image (ZT / ZB input rows of 7 pairs): a depthwise window row outside the image reads zeros
     // instead of being selected to zero register by register (35-49 v_cndmask per thread and chunk).  Written once, below.
-    constexpr int ZT = ST == 1 ? R : 1, ZB = ST == 1 ? R + 1 : 4;
+    constexpr int ZT = R, ZB = R + 1;
     unsigned char* E = smem + ZT * 7 * ES2;                  // pair row 0 of the image
     float* pband = reinterpret_cast<float*>(smem + (98 + 7 * (ZT + ZB)) * ES2);   // [5][96]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(512) void mid14_kernel(Mid14Args a)
         unsigned char* zr = smem + (row < ZT * 7 ? row : row + 98) * ES2 + 16 * c16;
         *reinterpret_cast<uint4*>(zr) = uint4{0u, 0u, 0u, 0u};
     }
-    constexpr bool KEEP_XB = KSD == 5 && ST == 1;
+    constexpr bool KEEP_XB = KSD == 5;
     h8 xb[2][CKS];
     auto load_xb = [&]() {
 #pragma unroll
@@ -160,52 +155,15 @@ __global__ __launch_bounds__(512) void mid14_kernel(Mid14Args a)
         T7_BAR();
         // ---------------- depthwise ----------------
         {
-            constexpr int NR = ST == 1 ? 3 + 2 * R : 7;   // input rows of a band (3 output rows; stride 2: 2 output rows)
-            const unsigned char* col = E + 4 * cd + ((ST == 1 ? rb - R : 4 * band - 1) * 7) * ES2;   // (may start in the zero rows)
+            constexpr int NR = 3 + 2 * R;   // input rows of a band (3 output rows)
+            const unsigned char* col = E + 4 * cd + ((rb - R) * 7) * ES2;   // (may start in the zero rows)
             uint32_t P[NR][7];
 #pragma unroll
             for (int r = 0; r < NR; ++r)
 #pragma unroll
                 for (int pp = 0; pp < 7; ++pp) P[r][pp] = *reinterpret_cast<const uint32_t*>(col + (r * 7 + pp) * ES2);
             f2 psum2 = {0.f, 0.f};
-            float psum1 = 0.f;
-            uint16_t* dg = reinterpret_cast<uint16_t*>(a.D + (size_t)b * HWO * CE + chunk * CH + cd);
-            if (ST == 2) {
-#pragma unroll
-                for (int ro = 0; ro < 2; ++ro) {
-                    const int oy = 2 * band + ro;
-                    if (oy < 7) {
-                        float acc[7];
-                        bool started[7] = {false, false, false, false, false, false, false};
-#pragma unroll
-                        for (int ky = 0; ky < 5; ++ky) {
-                            const uint32_t r0 = raw[3 * ky], r1 = raw[3 * ky + 1], r2 = raw[3 * ky + 2];
-                            const uint32_t wq[3] = {r0 << 16, __builtin_amdgcn_alignbit(r1, r0, 16), __builtin_amdgcn_alignbit(r2, r1, 16)};
-#pragma unroll
-                            for (int ip = 0; ip < 3; ++ip)
-#pragma unroll
-                                for (int ox = 0; ox < 7; ++ox) {
-                                    const int xpc = ox - 1 + ip;
-                                    if (xpc < 0 || xpc > 6) continue;
-                                    if (!started[ox]) { acc[ox] = dot2_from(P[2 * ro + ky][xpc], wq[ip], dbias); started[ox] = true; }
-                                    else acc[ox] = __builtin_amdgcn_fdot2(*reinterpret_cast<const h2*>(&P[2 * ro + ky][xpc]),
-                                                                          *reinterpret_cast<const h2*>(&wq[ip]), acc[ox], false);
-                                }
-                        }
-                        silu_scaled_staged(acc);
-#pragma unroll
-                        for (int ox = 0; ox < 6; ox += 2) {
-                            const f2 v = {acc[ox], acc[ox + 1]};
-                            psum2 = psum2 + v;
-                            const uint32_t hv = cvt_pk_f16(acc[ox], acc[ox + 1]);
-                            dg[(size_t)(oy * 7 + ox) * CE] = (uint16_t)hv;
-                            dg[(size_t)(oy * 7 + ox + 1) * CE] = (uint16_t)(hv >> 16);
-                        }
-                        psum1 += acc[6];
-                        reinterpret_cast<_Float16*>(dg)[(size_t)(oy * 7 + 6) * CE] = (_Float16)acc[6];
-                    }
-                }
-            } else
+            uint16_t* dg = reinterpret_cast<uint16_t*>(a.D + (size_t)b * HW * CE + chunk * CH + cd);
 #pragma unroll
             for (int ro = 0; ro < 3; ++ro) {
                 const int oy = rb + ro;
@@ -248,12 +206,12 @@ __global__ __launch_bounds__(512) void mid14_kernel(Mid14Args a)
                     }
                 }
             }
-            pband[band * CH + cd] = (psum2.x + psum2.y) + psum1;
+            pband[band * CH + cd] = (psum2.x + psum2.y) + 0.f;   // (+ 0.f: a -0 sum is stored as +0, as it always has been)
         }
         T7_BAR();
         if (tid < CH)
             a.pool[(size_t)b * CE + chunk * CH + tid] =
-                ((pband[tid] + pband[CH + tid]) + pband[2 * CH + tid]) + pband[3 * CH + tid] + (NBAND == 5 ? pband[4 * CH + tid] : 0.f);
+                ((pband[tid] + pband[CH + tid]) + pband[2 * CH + tid]) + pband[3 * CH + tid] + pband[4 * CH + tid];
         // (the next chunk's expand writes E only after every wave passed the barrier above; pband is rewritten only
         // after the next chunk's first barrier)
     }
@@ -934,21 +892,21 @@ int proj_patch_has(int K, int N, int HW, int res)
     return 0;
 }
 
-template <int CKS, int KSD, int CE, int ST = 1>
+template <int CKS, int KSD, int CE>
 static int launch_mid14_t(const Mid14Args& a, hipStream_t st)
 {
     // E2 chunk with its zero rows above and below the image (mid14_kernel's ZT + ZB), pool partials of the row bands, scratch
     // words of the expand's masked stores
-    constexpr int ZROWS = ST == 1 ? 2 * (KSD / 2) + 1 : 5;
+    constexpr int ZROWS = 2 * (KSD / 2) + 1;
     const int lds = (98 + 7 * ZROWS) * 416 + 5 * 96 * 4 + 512;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mid14_kernel<CKS, KSD, CE, ST>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mid14_kernel<CKS, KSD, CE>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return (int)e;
         attr_done = true;
     }
-    hipLaunchKernelGGL((mid14_kernel<CKS, KSD, CE, ST>), dim3(a.B, a.nsplit < 1 ? 1 : a.nsplit), dim3(512), lds, st, a);
+    hipLaunchKernelGGL((mid14_kernel<CKS, KSD, CE>), dim3(a.B, a.nsplit < 1 ? 1 : a.nsplit), dim3(512), lds, st, a);
     LAUNCH_CHECK();
     return 0;
 }
@@ -974,14 +932,9 @@ int launch_mid14(const Mid14Args& a, hipStream_t st)
 {
     if (a.B < 1) return -14;
     const int cks = (a.Cin + 31) / 32;
-    if (a.dwdiag && a.stride == 1) {   // depthwise on the matrix pipe (mid14m_kernel)
+    if (a.dwdiag) {   // depthwise on the matrix pipe (mid14m_kernel)
         if (cks == 4 && a.ks == 5 && a.Ce == 672) return launch_mid14m_t<4, 5, 672>(a, st);   // b9, b10
         if (cks == 3 && a.ks == 5 && a.Ce == 480) return launch_mid14m_t<3, 5, 480>(a, st);   // b8
-        if (cks == 3 && a.ks == 3 && a.Ce == 480) return launch_mid14m_t<3, 3, 480>(a, st);   // b6, b7
-        return -5;
-    }
-    if (a.stride == 2) {
-        if (cks == 4 && a.ks == 5 && a.Ce == 672) return launch_mid14_t<4, 5, 672, 2>(a, st);   // b11
         return -5;
     }
     if (cks == 4 && a.ks == 5 && a.Ce == 672) return launch_mid14_t<4, 5, 672>(a, st);   // b9, b10

@@ -58,7 +58,7 @@ struct DwArgs {
 struct MbArgs {
     const _Float16* X;      // [B][H][W][Cin]
     const _Float16* Wexp;   // [Ce][32*ksteps] natural rows, zero-padded K
-    const _Float16* Wfrag;  // the same weights in MFMA fragment order [Ce/16][ksteps][64][8] (wlds)
+    const _Float16* Wfrag;  // the same weights in MFMA fragment order [Ce/16][ksteps][64][8]
     const float* bexp;
     const float* Wdw;       // [ks*ks][Ce]
     const float* bdw;
@@ -67,7 +67,7 @@ struct MbArgs {
     int B, H, W, Cin, Ce, Ho, Wo, pad;
     int ks, stride, tw, ksteps, npair, pb;
     int TH, TWo, tiles_x, tiles_y, CC, CCG, S;
-    int wl_off, red_off, lds_bytes, wlds, wfr_off;
+    int wl_off, red_off, lds_bytes, wfr_off;
 };
 
 // One 7x7 MBConv block (192 -> 1152 -> cout, depthwise 5x5 or 3x3, stride 1) packed for tail7_kernel.
@@ -86,7 +86,6 @@ struct TailBlock {
     const float* bproj;     // [cout]
     int cout;               // 192 (skip connection, b12..b14) or 320 (b15, no skip; must be the last block)
     int ks;                 // depthwise kernel size: 5 or 3
-    const _Float16* dwtoe;  // [72][ks][2][64][4] Toeplitz depthwise fragments of v_mfma_f32_4x4x4_16B_f16 (TailArgs::dw4), or null
 };
 struct TailArgs {
     const _Float16* X;      // [B][49][192] block input (or [B][49][320] when in_wide); unused with pre_D
@@ -119,9 +118,6 @@ struct TailArgs {
     float* feat;                // [B][1280]
     float inv_hw;               // 1 / (49 log2 e)
     int in_wide;                // input X is [B][49][320] (head-only launches)
-    int tune[4];                // experiment knobs (env MMC_T7_TUNE0..3, read by launch_tail7); 0 = off
-    int dw4;                    // 1: blocks run expand + depthwise as one wave-private phase with the depthwise conv on 4x4x4 MFMA blocks
-                                // (every TailBlock::dwtoe set); 0: the round-2 phases
 };
 int launch_tail7(const TailArgs& a, hipStream_t st);
 
@@ -170,7 +166,6 @@ struct Mid14Args {
     float* pool;              // [B][Ce] pool sums
     int B, Cin, Ce, ks;
     int nsplit;               // workgroups per patch (each takes every nsplit-th chunk of 96 channels)
-    int stride;               // 1, or 2 (block 11: D is [B][49][Ce])
     float* dbg_clk;           // optional [B][8 workgroups][16]: shader cycles of the first chunk's phases (MMC_TAIL_CLK=1)
     const _Float16* dwdiag;   // optional [Ce/16][ks][2][64][4]: Toeplitz depthwise fragments of v_mfma_f32_4x4x4_16B_f16 -> mid14m_kernel
 };

@@ -2,6 +2,7 @@
 // Host C++ only; kernels live in k_*.hip.  No torch, no CUDA shims.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -178,68 +179,210 @@ static int pick_nt(int N, bool small_m)
     return 1;
 }
 
+// ------------------------------------------------------------------------------------------
+// schedule switches: read once per handle, by mmc_backbone_create_ex; nothing else on the backbone
+// path reads the environment
+// ------------------------------------------------------------------------------------------
+struct Options {
+    bool keep, graph, tail_clk, profile_serial;
+    bool fuse, fuse_b0, mb1, mbt, mbt2, mbt4, mb_dot2, mid14, mid14m, projse, se_small, thin_proj, b1_planar;
+    bool tail, tail_full, tail_b11;
+    int lanes, fp8_maxh;
+};
+static bool env_starts(const char* name, char c)
+{
+    const char* e = getenv(name);
+    return e && e[0] == c;
+}
+static Options read_options()
+{
+    auto on = [](const char* name) { return !env_starts(name, '0'); };   // default-on switches: a leading 0 turns them off
+    Options o;
+    o.keep = env_starts("MMC_KEEP_ACTIVATIONS", '1');
+    o.graph = on("MMC_GRAPH") && !o.keep;
+    o.tail_clk = env_starts("MMC_TAIL_CLK", '1') && !o.keep;
+    o.profile_serial = env_starts("MMC_PROFILE_SERIAL", '1');
+    o.fuse = on("MMC_FUSE");
+    o.fuse_b0 = on("MMC_FUSE_B0");
+    o.mb1 = on("MMC_MB1");
+    o.mbt = on("MMC_MBT");
+    o.mbt2 = on("MMC_MBT2");
+    o.mbt4 = on("MMC_MBT4");
+    o.mb_dot2 = on("MMC_MB_DOT2");
+    o.projse = on("MMC_PROJSE");
+    o.se_small = on("MMC_SE_SMALL");
+    o.thin_proj = on("MMC_THIN_PROJ");
+    o.b1_planar = on("MMC_B1_PLANAR");
+    o.tail = on("MMC_TAIL");
+    o.tail_full = on("MMC_TAIL_FULL");
+    o.tail_b11 = on("MMC_TAIL_B11");
+    const char* e = getenv("MMC_MID14");
+    o.mid14 = !e || atoi(e) != 0;
+    e = getenv("MMC_MID14M");
+    o.mid14m = !e || atoi(e) >= 1;
+    e = getenv("MMC_LANES");
+    o.lanes = e ? atoi(e) : 2;
+    e = getenv("MMC_FP8_MAXH");
+    o.fp8_maxh = e && atoi(e) > 7 ? atoi(e) : 7;
+    return o;
+}
+
+// ------------------------------------------------------------------------------------------
+// the plan: which kernels run each block, decided at create time before any weight is packed
+// ------------------------------------------------------------------------------------------
+// front half (expand + depthwise) of a block
+enum class Front {
+    StemDw,    // block 0 with the stem (stem_dw_kernel)
+    Mbt,       // mbt_kernel / mbt2_kernel / mbt4_kernel
+    Mid14,     // mid14_kernel / mid14m_kernel
+    Mb1,       // block 1 with block 0's project folded in (mb1_kernel)
+    MbPre,     // ... on mbconv_a_kernel PRE
+    MbD,       // mbconv_d_kernel
+    MbA,       // mbconv_a_kernel
+    Unfused,   // expand GEMM + dwconv
+    Tail,      // inside the pass's tail7 launch
+};
+// back half (squeeze-excite + project) of a block
+enum class Back {
+    ProjPatch,   // proj_patch_kernel
+    SeProject,   // squeeze-excite, then the project conv
+    SeFolded,    // block 0: squeeze-excite only, its project runs inside block 1's kernel
+    Tail,        // inside the pass's tail7 launch
+};
+enum class Se { Wide, Small, Fused };
+enum class Proj { Thin, Fp8, Gemm };
+// how the pass ends
+enum class TailRoute {
+    None,     // head GEMM
+    B12,      // b12-15.tail + head GEMM
+    B11,      // b11-head.tail (block 11's back half, blocks 12..15, head); per-tensor mode: b11.tail, b<j>.tail, head.tail
+    B11All,   // b11all-head.tail (all of block 11 too)
+};
+
 struct BlockW {
     BlockDef d;
+    // ---- geometry ----
     int H = 0, Ho = 0, ce = 0, cs = 0, cs4 = 0, pad = 0;
     bool has_expand = false, skip = false;
+    int tw = 0, CG = 0, S = 0, iters = 0, parts = 0, nz = 1;   // dwconv
+    bool fusable = false;   // mbconv_a's tile / chunk geometry (in `mb`) fits
+    bool d_fits = false;    // ... and so does mbconv_d's (d_npair .. d_lds)
+    int d_npair = 0, d_wl_off = 0, d_red_off = 0, d_lds = 0;
+    MbArgs mb{};            // mbconv_a / mbconv_d / mbconv_a PRE: everything but the buffers and the batch
+    // ---- plan ----
+    Front front = Front::Unfused;
+    Back back = Back::SeProject;
+    Se se = Se::Fused;
+    Proj proj = Proj::Gemm;
+    bool mbt4 = false, mid14m = false;   // depthwise on 4x4x4 MFMA blocks (mbt4_kernel / mid14m_kernel)
+    bool planar = false;                 // block 1: depthwise output as 32-channel planes between mb1_kernel and thin_proj_kernel
+    int nparts = 0;                      // pool partials per patch left by the front half
+    // ---- packed weights ----
     PwLayer expand, project;
-    Fp8Layer p8;             // the project conv on fp8 operands (MMC_PRECISION_FP8, blocks from fp8_from on)
+    Fp8Layer p8;             // the project conv on fp8 operands (Proj::Fp8)
     float *dw_w = nullptr, *dw_b = nullptr;                    // [k*k][ce], [ce]
     float *se_br = nullptr, *se_be = nullptr;
-    float *se_wrp = nullptr, *se_wep = nullptr;   // fragment-ordered fp32 squeeze-excite weights
-    float *se_wr_nat = nullptr, *se_we_nat = nullptr, *se_br_nat = nullptr;   // natural fp32 copies for se_small_kernel (C <= 256)
-    // depthwise launch geometry
-    int tw = 0, CG = 0, S = 0, iters = 0, parts = 0, nz = 1;
-    // fused expand+depthwise (mbconv_a_kernel) geometry; fused == false -> separate GEMM + dwconv
-    bool fused = false;
-    _Float16* exp_nat = nullptr;  // [ce][32*f_ksteps] natural rows
-    int f_TH = 0, f_TWo = 0, f_CC = 0, f_tw = 0, f_ksteps = 0, f_CCG = 0, f_S = 0, f_tiles_x = 0, f_tiles_y = 0,
-        f_red_off = 0, f_lds = 0, f_npair = 0, f_wl_off = 0, f_pb = 1, f_wlds = 0, f_wfr_off = 0;
-    // geometry of the dot2 variant (mbconv_d_kernel): pair-aligned windows are a little wider
-    bool use_d = false;
-    int d_npair = 0, d_wl_off = 0, d_red_off = 0, d_lds = 0;
+    float *se_wrp = nullptr, *se_wep = nullptr;   // fragment-ordered fp32 squeeze-excite weights (se_fused_kernel)
+    float *se_wr_nat = nullptr, *se_we_nat = nullptr, *se_br_nat = nullptr;   // natural fp32 copies (se_small_kernel, se_wide_kernel)
+    _Float16* exp_nat = nullptr;   // [ce][32*ksteps] natural rows (mbconv_a / mbconv_d)
     _Float16* exp_frag = nullptr;  // expand weights in MFMA fragment order
-    // tail7_kernel packing (7x7 blocks 12..14): project weights in plain fragment order, depthwise tap pairs
-    _Float16* t_wproj = nullptr;
-    uint32_t* t_dwp = nullptr;
-    uint32_t* t_dwp4 = nullptr;  // taps + bias, [4][ce][4] dwords (16-byte requests)
-    _Float16* dw_diag = nullptr;  // mid14m_kernel: Toeplitz depthwise fragments [ce/16][k][2][64][4] for v_mfma_f32_4x4x4_16B_f16 (depthwise on the matrix pipe)
+    uint32_t* t_dwp = nullptr;     // depthwise taps as fp16 pairs [15][ce] (mbt)
+    uint32_t* t_dwp4 = nullptr;    // taps + bias, [4][ce][4] dwords (16-byte requests: mid14, tail7)
+    _Float16* dw_diag = nullptr;   // Toeplitz depthwise fragments [ce/16][k][2][64][4] for v_mfma_f32_4x4x4_16B_f16 (mbt4, mid14m)
+    _Float16* t_wproj = nullptr;   // tail7 blocks: project weights in plain fragment order
     _Float16 *t_wr = nullptr, *t_we = nullptr;   // squeeze-excite FCs transposed (fp16) for matrix-vector use
     _Float16* t_wrg = nullptr;                   // ... the squeeze FC as proj_patch_kernel reads it (ProjPatchArgs::wr_g)
     _Float16 *t_wr2 = nullptr, *t_we2 = nullptr; // ... blocks 12-15: paired rows for tail7_kernel's 16-byte requests
-    // proj_patch_kernel packing (blocks 3..10): project weights/bias padded to whole fragments, SE FCs as above with
-    // Cs padded to a multiple of 4
-    bool pp = false;
-    _Float16* pp_w = nullptr;
+    _Float16* pp_w = nullptr;                    // proj_patch_kernel: project weights / bias padded to whole fragments
     float *pp_b = nullptr, *pp_br = nullptr;
-    int pp_csp = 0;
 };
 
 // Output tile (TH x TWo) and channel chunk CC of the fused kernel, per B0 block (index 1..15):
 // chosen so that E[P][CC] + the pool scratch stay <= 64 KB of LDS (>= 2 workgroups per CU) while
 // the halo recompute and the per-chunk re-read of the (small) block input stay low.
-struct FuseCfg { int TH, TWo, CC, TW, PB, WLDS; };
+struct FuseCfg { int TH, TWo, CC, TW, PB; };
 static const FuseCfg B0_FUSE[16] = {
-    {0, 0, 0, 0, 1, 0},     {8, 8, 48, 2, 1, 0},    {14, 14, 48, 2, 1, 0},  {4, 14, 48, 2, 1, 0},   {14, 14, 48, 2, 1, 0},
-    {7, 14, 80, 2, 1, 0},   {14, 14, 96, 2, 1, 0},  {14, 14, 96, 2, 1, 0},  {14, 14, 48, 2, 1, 0},  {14, 14, 48, 2, 1, 0},
-    {14, 14, 48, 2, 1, 0},  {7, 7, 48, 1, 1, 0},    {7, 7, 96, 1, 2, 0},    {7, 7, 96, 1, 2, 0},    {7, 7, 96, 1, 2, 0},
-    {7, 7, 96, 1, 2, 0}};
+    {0, 0, 0, 0, 1},     {8, 8, 48, 2, 1},    {14, 14, 48, 2, 1},  {4, 14, 48, 2, 1},   {14, 14, 48, 2, 1},
+    {7, 14, 80, 2, 1},   {14, 14, 96, 2, 1},  {14, 14, 96, 2, 1},  {14, 14, 48, 2, 1},  {14, 14, 48, 2, 1},
+    {14, 14, 48, 2, 1},  {7, 7, 48, 1, 1},    {7, 7, 96, 1, 2},    {7, 7, 96, 1, 2},    {7, 7, 96, 1, 2},
+    {7, 7, 96, 1, 2}};
+// dot2 depthwise variant (mbconv_d_kernel): only where it measured faster (5x5 stride-1 blocks; MI355X, batch 128/256)
+static const bool B0_DOT2[16] = {0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1, 0, 1, 1, 1, 0};
 
 // The same choices by layer geometry for the other members of the family (B4): the tile and chunk B0 uses at that
-// resolution / stride / kernel size, with CC a divisor of the expanded width.
-static FuseCfg generic_fuse_cfg(int H, int k, int s, int ce, int cc5)
+// resolution / stride / kernel size, with CC a divisor of the expanded width (5x5 layers at 14x14: CC 96 measured +1.3 %
+// over 48).
+static FuseCfg generic_fuse_cfg(int H, int k, int s, int ce)
 {
-    FuseCfg fc{0, 0, 0, 0, 1, 0};
-    if (H == 112 && s == 2) fc = {8, 8, 48, 2, 1, 0};
-    else if (H == 56 && s == 1) fc = {14, 14, 48, 2, 1, 0};
-    else if (H == 56 && s == 2) fc = {4, 14, 48, 2, 1, 0};
-    else if (H == 28 && s == 1) fc = {14, 14, 48, 2, 1, 0};
-    else if (H == 28 && s == 2) fc = {2, 14, 48, 2, 1, 0};
-    else if (H == 14 && s == 1) fc = {14, 14, k == 3 ? 96 : cc5, 2, 1, 0};
-    else if (H == 14 && s == 2) fc = {7, 7, 48, 1, 1, 0};
-    else if (H == 7 && s == 1) fc = {7, 7, 96, 1, 2, 0};
+    FuseCfg fc{0, 0, 0, 0, 1};
+    if (H == 112 && s == 2) fc = {8, 8, 48, 2, 1};
+    else if (H == 56 && s == 1) fc = {14, 14, 48, 2, 1};
+    else if (H == 56 && s == 2) fc = {4, 14, 48, 2, 1};
+    else if (H == 28 && s == 1) fc = {14, 14, 48, 2, 1};
+    else if (H == 28 && s == 2) fc = {2, 14, 48, 2, 1};
+    else if (H == 14 && s == 1) fc = {14, 14, 96, 2, 1};
+    else if (H == 14 && s == 2) fc = {7, 7, 48, 1, 1};
+    else if (H == 7 && s == 1) fc = {7, 7, 96, 1, 2};
     if (fc.CC && ce % fc.CC) fc.TH = 0;
     return fc;
+}
+
+// Geometry of block B (d, H filled in): pure arithmetic, no switch but `fuse` (whether a tile / chunk geometry is wanted)
+static void block_geometry(BlockW& B, bool is_b0, int i, bool fuse)
+{
+    const int H = B.H, k = B.d.k, s = B.d.s;
+    B.ce = B.d.cin * B.d.e;
+    B.cs = B.d.cin / 4 > 1 ? B.d.cin / 4 : 1;
+    B.cs4 = (B.cs + 3) / 4 * 4;
+    B.has_expand = B.d.e != 1;
+    B.skip = s == 1 && B.d.cin == B.d.cout;
+    same_pad(H, k, s, &B.pad, &B.Ho);
+    // depthwise (dwconv_kernel)
+    B.tw = (B.Ho % 4 == 0) ? 4 : (B.Ho % 7 == 0 && B.Ho <= 7 ? 7 : 2);
+    B.CG = B.ce / 8;
+    B.nz = 1;
+    while (B.CG / B.nz > 256 || B.CG % B.nz) ++B.nz;   // layers wider than 2048 channels: split the channel groups
+    B.CG /= B.nz;
+    B.S = 256 / B.CG > 0 ? 256 / B.CG : 1;
+    const int strips = B.Ho * (B.Ho / B.tw);
+    const int passes = (strips + B.S - 1) / B.S;
+    B.iters = passes >= 8 ? 4 : 1;
+    B.parts = (passes + B.iters - 1) / B.iters;
+    // fused expand + depthwise (mbconv_a_kernel; mbconv_d_kernel's pair-aligned windows are a little wider)
+    if (!B.has_expand || !fuse) return;
+    const FuseCfg fc = is_b0 ? B0_FUSE[i] : generic_fuse_cfg(H, k, s, B.ce);
+    if (!(fc.TH > 0 && B.Ho % fc.TH == 0 && B.Ho % fc.TWo == 0 && B.ce % fc.CC == 0 && fc.CC % 16 == 0)) return;
+    MbArgs& a = B.mb;
+    a.H = a.W = H; a.Cin = B.d.cin; a.Ce = B.ce; a.Ho = a.Wo = B.Ho; a.pad = B.pad; a.ks = k; a.stride = s;
+    a.TH = fc.TH; a.TWo = fc.TWo; a.CC = fc.CC; a.tw = fc.TW;
+    a.ksteps = (B.d.cin + 31) / 32;
+    a.CCG = fc.CC / 8;
+    a.S = 256 / a.CCG;
+    a.tiles_x = B.Ho / fc.TWo; a.tiles_y = B.Ho / fc.TH;
+    const int wh = std::min((fc.TH - 1) * s + k, H), wwid = std::min((fc.TWo - 1) * s + k, H);
+    a.pb = fc.PB;
+    const int ppad = (a.pb * wh * wwid + 15) / 16 * 16;
+    a.npair = (ppad / 16 + 7) / 8;
+    a.wfr_off = ppad * (fc.CC * 2 + 16);                       // E | taps+bias
+    a.wl_off = a.wfr_off;
+    a.lds_bytes = a.wl_off + (k * k + 1) * fc.CC * 4;
+    a.red_off = 0;  // pool scratch [PB][S][CC] aliases E when it fits, else gets its own space
+    if (a.pb * a.S * fc.CC * 4 > a.wfr_off) { a.red_off = a.lds_bytes; a.lds_bytes += a.pb * a.S * fc.CC * 4; }
+    B.fusable = a.lds_bytes <= 128 * 1024 && fc.TWo % a.tw == 0;
+    if (!B.fusable || !is_b0) return;
+    int rowlen = 0;   // window of mbconv_d_kernel: rows as above, columns widened to whole pixel pairs (even absolute x)
+    for (int tx = 0; tx < a.tiles_x; ++tx) {
+        const int x0 = std::max(tx * fc.TWo * s - B.pad, 0), x1 = std::min((tx * fc.TWo + fc.TWo - 1) * s - B.pad + k, H);
+        rowlen = std::max(rowlen, 2 * (((x1 + 1) >> 1) - (x0 >> 1)));
+    }
+    const int dpad = (a.pb * wh * rowlen + 15) / 16 * 16;
+    const int np = (B.pad % 2 + s + k + 1) / 2;
+    B.d_npair = (dpad / 16 + 7) / 8;
+    B.d_wl_off = dpad * fc.CC * 2;
+    B.d_lds = B.d_wl_off + k * 2 * np * fc.CC * 4 + fc.CC * 4;
+    B.d_red_off = 0;
+    if (a.pb * a.S * fc.CC * 4 > B.d_wl_off) { B.d_red_off = B.d_lds; B.d_lds += a.pb * a.S * fc.CC * 4; }
+    B.d_fits = B.d_lds <= 128 * 1024;
 }
 
 struct Saved {
@@ -254,6 +397,7 @@ struct Saved {
 struct mmc_backbone {
     int device = 0, max_batch = 0;
     int arch = MMC_ARCH_B0, nblk = 16, stem_ch = 32, head_in = 320, feat = 1280;
+    Options opt;
     _Float16* stem_w = nullptr;
     float *stem_b = nullptr, *stem_pad = nullptr;
     std::vector<BlockW> blk;
@@ -292,32 +436,18 @@ struct mmc_backbone {
     float* out_stage = nullptr;
     size_t ws_bytes = 0;
     std::vector<void*> allocs;
-    bool keep = false, fuse_stem = false;
+    bool keep = false;
+    bool fuse_stem = false;          // block 0's depthwise conv inside the stem launch (stem_dw_kernel): no stem tensor
+    bool fuse_b0b1 = false;          // block 0's SE scale + project conv folded into block 1's kernel: no b0 output tensor
+    TailRoute tail = TailRoute::None;
+    bool fp8 = false;                // MMC_PRECISION_FP8: project convs of the narrow late blocks on e4m3 MFMA operands
     float* dbg_clk = nullptr;        // keep mode: per-patch phase cycle counts of the patch-resident kernels
     float* mid_clk = nullptr;        // MMC_TAIL_CLK=1: [max_batch][8 workgroups][16] phase cycle counts of block 10's mid14 launch
     float* tail_clk = nullptr;       // MMC_TAIL_CLK=1: [max_batch][8 sections][8] phase cycle counts of the production tail7 launch
-    // tail7 extensions: block 11's squeeze-excite + project (pre-block) and the head conv inside the same launch
-    // block 0's SE scale + project conv folded into block 1's fused kernel (mbconv_a_kernel PRE): no b0 output tensor
-    bool fuse_b0b1 = false;
-    bool mbt = false;                // blocks 2 and 4 on mbt_kernel (tiled, window-in-registers depthwise)
-    bool mbt2 = false;               // ... and the stride-2 blocks 3 and 5 on mbt2_kernel
-    bool mb1 = false;                // block 1 on mb1_kernel (window-in-registers depthwise) instead of mbconv_a PRE
-    bool mid14 = false;              // 14x14 blocks: per-patch front half (mid14_kernel) instead of tile/chunk workgroups
-    int mid14_last = 8;              // ... for blocks 6..mid14_last
-    bool mid14_b11 = false;          // ... and block 11 (5x5 stride 2) on mid14_kernel<4,5,672,2>
-    bool b1_planar = true;           // block 1's depthwise output as 32-channel planes between mb1 and thin_proj (MMC_B1_PLANAR=0)
-    bool thin_proj = true;           // B4 blocks 0/1: thin_proj_kernel instead of pw_gemm for the tiny-K project convs (MMC_THIN_PROJ=0)
-    bool se_small = true;            // light per-patch squeeze-excite kernel for the early blocks (MMC_SE_SMALL=0: se_fused)
-    _Float16 *b0_pre_w = nullptr, *b1_exp_pre = nullptr;
-    bool tail_full = false;
-    bool tail_b11 = false;           // block 11's front half (expand + depthwise stride 2) inside tail7_kernel too: no b11 launch at all
-    _Float16 *pre_wproj = nullptr, *head_wfrag = nullptr;
-    bool fp8 = false;                // MMC_PRECISION_FP8: project convs of blocks fp8_from .. on e4m3 MFMA operands
-    int fp8_from = 0;
-    TailBlock* tail_tab = nullptr;   // device table for tail7_kernel (blocks 12..14), null = separate launches
-    bool tail_dw4 = true;            // every tail block has its Toeplitz depthwise fragments (only with MMC_TAIL_DW4=1)
+    _Float16 *b0_pre_w = nullptr, *b1_exp_pre = nullptr;   // fuse_b0b1: block 0's project as one MFMA fragment, block 1's K-permuted expand
+    _Float16 *pre_wproj = nullptr, *head_wfrag = nullptr;  // tail7: block 11's project, the head conv (plain fragment order)
+    TailBlock* tail_tab = nullptr;   // device table for tail7_kernel (blocks 12..15)
     std::map<std::string, Saved> saved;
-    int last_n = 0;
     // One pass at a time per handle (lane workspaces, fork/done events and the staging buffers are shared): calls are
     // serialised on the host by `mu`, and a call on a different stream than the previous one waits for that one's work.
     std::mutex mu;
@@ -450,6 +580,72 @@ extern "C" int mmc_backbone_create(const void* packed, size_t nbytes, int arch, 
     return mmc_backbone_create_ex(packed, nbytes, arch, device, max_batch, 0u, out);
 }
 
+// W[n][k] (rows of ld elements, n < N, k < K) times `scale` as fp16 in MFMA fragment order [nf][ks][64 lanes][8]: element (n, k)
+// at ((n/16 * ks + k/32) * 64 + (k%32)/8 * 16 + n%16) * 8 + k%8 -- lane (q*16 + m) of fragment (f, kstep) holds
+// W[16f + m][32 kstep + 8q .. +8].  Fragments and k-steps beyond the tensor stay zero.  (A source already in fp16 is only
+// permuted: the expand weights keep the rounding of their natural fp16 rows.)
+template <typename T>
+static std::vector<_Float16> pack_frag(const T* w, int N, int K, int ld, int nf, int ks, double scale)
+{
+    std::vector<_Float16> wf((size_t)nf * ks * 512, (_Float16)0.0f);
+    for (int c = 0; c < N; ++c)
+        for (int k = 0; k < K; ++k)
+            wf[((((size_t)(c / 16) * ks + k / 32) * 64) + ((k % 32) / 8) * 16 + (c % 16)) * 8 + (k % 8)] =
+                (_Float16)(float)(w[(size_t)c * ld + k] * scale);
+    return wf;
+}
+
+// Plan block i (geometry done) under the handle's switches.  Pass-level choices (stem, b0/b1 fold, tail route) are in bb.
+static void plan_block(const mmc_backbone* bb, BlockW& B, int i)
+{
+    const Options& o = bb->opt;
+    const bool is_b0 = bb->arch == MMC_ARCH_B0;
+    const int HWo = B.Ho * B.Ho;
+    const bool tail_blk = (bb->tail == TailRoute::B11All && i >= 11) || (bb->tail != TailRoute::None && i >= 12);
+    // front half
+    const bool mbt = o.fuse && o.mbt && (B.d.s == 1 || o.mbt2) && mbt_has(B.H, B.d.k, B.d.s, B.d.cin, B.ce);
+    const bool mid14 = is_b0 && o.fuse && o.projse && o.mid14 && i >= 6 && i <= 10;
+    if (i == 0 && bb->fuse_stem) B.front = Front::StemDw;
+    else if (tail_blk) B.front = Front::Tail;
+    else if (B.fusable && mbt) B.front = Front::Mbt;
+    else if (B.fusable && mid14) B.front = Front::Mid14;
+    else if (B.fusable && is_b0 && o.mb_dot2 && B0_DOT2[i] && B.d_fits) B.front = Front::MbD;
+    else if (B.fusable && i == 1 && bb->fuse_b0b1) B.front = o.mb1 ? Front::Mb1 : Front::MbPre;
+    else if (B.fusable) B.front = Front::MbA;
+    else B.front = Front::Unfused;
+    B.mbt4 = B.front == Front::Mbt && o.mbt4 && B.d.s == 1 && B.H == 28 && B.d.k == 5 && B.ce % 16 == 0;
+    B.mid14m = B.front == Front::Mid14 && o.mid14m && i >= 8 && B.H == 14 && B.d.s == 1 && B.ce % 16 == 0;
+    if (B.front == Front::MbD) {
+        B.mb.npair = B.d_npair; B.mb.wl_off = B.d_wl_off; B.mb.red_off = B.d_red_off; B.mb.lds_bytes = B.d_lds;
+    }
+    switch (B.front) {
+    case Front::StemDw: B.nparts = 49; break;
+    case Front::Mbt: B.nparts = B.d.s == 2 ? (B.Ho / 7) * (B.Ho / 14) : (B.H / 14) * (B.H / 28); break;
+    case Front::Mid14: B.nparts = 1; break;
+    case Front::Mb1: B.nparts = 14; break;
+    case Front::MbPre: case Front::MbD: case Front::MbA: B.nparts = B.mb.tiles_x * B.mb.tiles_y; break;
+    default: B.nparts = B.parts; break;
+    }
+    // back half
+    const bool fp8_blk = bb->fp8 && B.Ho <= o.fp8_maxh;
+    const bool proj_patch = o.fuse && o.projse && B.fusable && B.has_expand && B.cs4 <= 28 &&
+                            proj_patch_has(B.ce, B.d.cout, HWo, B.skip ? 1 : 0) && (is_b0 ? i >= 3 && i <= 10 : !fp8_blk);
+    if (tail_blk || (i == 11 && bb->tail == TailRoute::B11)) B.back = Back::Tail;
+    else if (proj_patch) B.back = Back::ProjPatch;
+    else if (i == 0 && bb->fuse_b0b1) B.back = Back::SeFolded;
+    else B.back = Back::SeProject;
+    B.se = !is_b0 ? Se::Wide : (o.se_small && B.ce <= 256 && B.cs <= 16) ? Se::Small : Se::Fused;
+    // small-K, small-N project on a big image: thin_proj_kernel (up to 5 k-steps since the gate is folded into the weight
+    // fragments: B0's b2 30.8 vs 43.7 us on pw_gemm; a shape without an instantiation stays on pw_gemm)
+    const PwLayer& P = B.project;
+    const bool thin = o.thin_proj && P.nt == 2 && P.n_chunks == 1 && thin_proj_has(P.Kp / 32) && P.N <= 32 && (P.N & 7) == 0 &&
+                      (HWo & 15) == 0 && HWo >= 3136;
+    B.proj = thin ? Proj::Thin : fp8_blk ? Proj::Fp8 : Proj::Gemm;
+    // block 1's depthwise output as three 32-channel planes between mb1_kernel and thin_proj_kernel (see mb1_kernel); per-tensor
+    // mode keeps the interleaved tensor it hands out
+    B.planar = B.front == Front::Mb1 && thin && o.b1_planar && !o.keep && P.K == 96;
+}
+
 extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arch, int device, int max_batch, unsigned flags,
                                       mmc_backbone** out)
 {
@@ -479,26 +675,64 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
     bb->device = device;
     bb->max_batch = max_batch;
     bb->fp8 = (flags & MMC_PRECISION_FP8) != 0;
+    bb->opt = read_options();
+    const Options& o = bb->opt;
     const ArchDef AD = make_arch(arch);
     const bool is_b0 = arch == MMC_ARCH_B0;
     const int STEM_CH = AD.stem, HEAD_IN = AD.head_in, FEAT = AD.feat, NBLK = (int)AD.blocks.size();
     bb->arch = arch; bb->nblk = NBLK; bb->stem_ch = STEM_CH; bb->head_in = HEAD_IN; bb->feat = FEAT;
     bb->blk.resize(NBLK);
-    const char* keep = getenv("MMC_KEEP_ACTIVATIONS");
-    bb->keep = keep && keep[0] == '1';
-    { const char* e = getenv("MMC_GRAPH"); bb->use_graph = !(e && e[0] == '0') && !bb->keep; }
-    { const char* e = getenv("MMC_SE_SMALL"); bb->se_small = !(e && e[0] == '0'); }
-    if (bb->keep) { int r__ = dev_alloc(bb, &bb->dbg_clk, (size_t)max_batch * 8); if (r__) { mmc_backbone_destroy(bb); return r__; } }
-    { const char* e = getenv("MMC_TAIL_CLK");
-      if (e && e[0] == '1' && !bb->keep) {
-          // rows are indexed lane * lane_cap + row with lane_cap = ceil(max_batch / lanes): up to lanes - 1 <= 3 rows more than max_batch
-          const size_t clk_rows = (size_t)max_batch + 4;
-          int r__ = dev_alloc(bb, &bb->tail_clk, clk_rows * 64); if (r__) { mmc_backbone_destroy(bb); return r__; }
-          hipMemset(bb->tail_clk, 0, clk_rows * 64 * sizeof(float));
-          r__ = dev_alloc(bb, &bb->mid_clk, clk_rows * 128); if (r__) { mmc_backbone_destroy(bb); return r__; }
-          hipMemset(bb->mid_clk, 0, clk_rows * 128 * sizeof(float));
-          bb->use_graph = false;
-      } }
+    bb->keep = o.keep;
+    bb->use_graph = o.graph;
+#define TRY_OR_FREE(expr)                          \
+    do { int r__ = (expr); if (r__) { mmc_backbone_destroy(bb); return r__; } } while (0)
+    if (bb->keep) TRY_OR_FREE(dev_alloc(bb, &bb->dbg_clk, (size_t)max_batch * 8));
+    if (o.tail_clk) {
+        // rows are indexed lane * lane_cap + row with lane_cap = ceil(max_batch / lanes): up to lanes - 1 <= 3 rows more than max_batch
+        const size_t clk_rows = (size_t)max_batch + 4;
+        TRY_OR_FREE(dev_alloc(bb, &bb->tail_clk, clk_rows * 64));
+        hipMemset(bb->tail_clk, 0, clk_rows * 64 * sizeof(float));
+        TRY_OR_FREE(dev_alloc(bb, &bb->mid_clk, clk_rows * 128));
+        hipMemset(bb->mid_clk, 0, clk_rows * 128 * sizeof(float));
+        bb->use_graph = false;
+    }
+
+    // ---- 1. geometry: per block, pure arithmetic ----
+    for (int i = 0, H = IMG / 2; i < NBLK; ++i) {
+        BlockW& B = bb->blk[i];
+        B.d = AD.blocks[i];
+        B.H = H;
+        block_geometry(B, is_b0, i, o.fuse);
+        B.project.N = B.d.cout;   // pack_pw's layout (the thin_proj choice reads it)
+        B.project.K = B.ce;
+        B.project.Kp = (B.ce + 31) / 32 * 32;
+        B.project.nt = pick_nt(B.d.cout, B.Ho <= 14);
+        B.project.n_chunks = (B.d.cout + 16 * B.project.nt - 1) / (16 * B.project.nt);
+        H = B.Ho;
+    }
+    // ---- 2. plan: pass-level routes, then each block ----
+    {
+        const std::vector<BlockW>& K = bb->blk;
+        bb->fuse_stem = is_b0 && o.fuse;
+        // block 0's project as one MFMA fragment in block 1's kernel: the tile of mbconv_a_kernel PRE / mb1_kernel
+        const MbArgs& m1 = K[1].mb;
+        bb->fuse_b0b1 = o.fuse_b0 && bb->fuse_stem && K[0].ce == 32 && K[0].d.cout == 16 && K[1].d.cin == 16 && K[1].fusable &&
+                        !(o.mb_dot2 && B0_DOT2[1] && K[1].d_fits) && m1.TH == 8 && m1.TWo == 8 && m1.CC == 48 && m1.tw == 2 &&
+                        m1.pb == 1 && m1.npair == 3;
+        // tail7_kernel: blocks 12..15 at 7x7 (192 -> 1152 -> 192 / 320, SE width 48); block 11's back half (672 -> 192, SE width
+        // 28) and the head; block 11's front half (5x5 stride 2 from 14x14)
+        bool t12 = is_b0 && o.fuse && o.tail && NBLK == 16;
+        for (int i = 12; i <= 15 && t12; ++i)
+            t12 = K[i].fusable && K[i].H == 7 && K[i].d.s == 1 && K[i].d.cin == 192 && K[i].ce == 1152 && K[i].cs == 48;
+        const BlockW& B11 = K[11 < NBLK ? 11 : 0];
+        const bool t11 = t12 && o.tail_full && HEAD_IN % 32 == 0 && B11.fusable && B11.ce == 672 && B11.d.cout == 192 &&
+                         B11.cs4 == 28 && B11.mb.tiles_x * B11.mb.tiles_y == 1;
+        const bool t11all = t11 && o.tail_b11 && !o.keep && B11.mb.ksteps == 4 && B11.d.k == 5 && B11.d.s == 2 && B11.H == 14;
+        bb->tail = t11all ? TailRoute::B11All : t11 ? TailRoute::B11 : t12 ? TailRoute::B12 : TailRoute::None;
+        for (int i = 0; i < NBLK; ++i) plan_block(bb, bb->blk[i], i);
+    }
+
+    // ---- 3. packing: what the plan launches, reading the blob's tensors in their fixed order ----
     std::vector<uint64_t> table(2 * (size_t)nt);
     memcpy(table.data(), base + 16, (size_t)nt * 16);
     BlobReader rd{base, nbytes, nt, table.data()};
@@ -506,8 +740,6 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
 #define TAKE(var, n, what)                         \
     const float* var = rd.take((n), what, &err);   \
     if (!var) { mmc_backbone_destroy(bb); return err; }
-#define TRY_OR_FREE(expr)                          \
-    do { int r__ = (expr); if (r__) { mmc_backbone_destroy(bb); return r__; } } while (0)
 
     // ---- stem: [Cstem][27] folded (ky,kx,c), bias[Cstem], padval[3] ----
     {
@@ -534,68 +766,35 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         TRY_OR_FREE(dev_upload(bb, &bb->stem_pad, pvv));
     }
     // ---- blocks ----
-    const char* fuse_env = getenv("MMC_FUSE");
-    const bool fuse_generic_early = !is_b0 && !(fuse_env && fuse_env[0] == '0');   // (= fuse_generic, needed before its definition)
-    const bool fuse_enabled = is_b0 && !(fuse_env && fuse_env[0] == '0');   // the fused kernels are shaped for B0's layers
-    const char* dot2_env = getenv("MMC_MB_DOT2");
-    const bool dot2_enabled = !(dot2_env && dot2_env[0] == '0');
-    const bool fuse_generic = !is_b0 && !(fuse_env && fuse_env[0] == '0');   // B4: fused expand+depthwise where an instantiation fits
-    const int b4_cc14 = [] { const char* e = getenv("MMC_B4_CC14"); return e && atoi(e) == 48 ? 48 : 96; }();   // 5x5 layers at 14x14: 96 measured +1.3 %
-    { const char* e = getenv("MMC_THIN_PROJ"); bb->thin_proj = !(e && e[0] == '0'); }
-    { const char* e = getenv("MMC_B1_PLANAR"); bb->b1_planar = !(e && e[0] == '0'); }
-    bb->fuse_stem = fuse_enabled;
-    const char* pp_env = getenv("MMC_PROJSE");
-    const bool projse_enabled = fuse_enabled && !(pp_env && pp_env[0] == '0');
-    const char* mid_env = getenv("MMC_MID14");
-    // MMC_MID14: 0 = off (tile/chunk kernels), 1 (default) = blocks 6..10, 2 = blocks 6..8 only
-    const int mid14_mode = !(fuse_enabled && projse_enabled) ? 0 : (mid_env ? atoi(mid_env) : 1);
-    const bool mid14_enabled = mid14_mode != 0;
-    bb->mid14 = mid14_enabled;
-    bb->mid14_last = mid14_mode == 1 ? 10 : 8;
-    { const char* e = getenv("MMC_MID14_B11"); bb->mid14_b11 = mid14_mode == 1 && e && e[0] == '1'; }   // block 11's front half (stride 2) too: measured equal (35.7 vs 33.0 us), opt-in
-    // MMC_MID14M (default 2): mid14m_kernel -- depthwise conv on 4x4x4 MFMA blocks (block = channel), wave-private channel groups, one
-    // barrier per kernel -- 2: on the 5x5 blocks 8..10 (13-24 % ahead of mid14_kernel alone on the chip, one workgroup per patch: bench
-    // 228.4 k vs 227.1 k patches/s), 1: on blocks 6..10 (the 3x3 blocks are equal alone and lose in the bench), 0: mid14_kernel everywhere
-    // (MMC_MID14M=2: only the 5x5 blocks 8..10, where it is 13-24 % ahead alone on the chip; the 3x3 blocks stay on mid14_kernel)
-    const int mid14m_mode = [] { const char* e = getenv("MMC_MID14M"); return e ? atoi(e) : 2; }();
-    const bool mid14m_enabled = mid14_enabled && mid14m_mode >= 1;
-    // MMC_TAIL_DW4=1 (default 0): tail7_kernel's blocks 12..15 with the depthwise conv on 4x4x4 MFMA blocks, fused with the expand into one
-    // wave-private phase.  Parity-tested; measured 44-45 k cycles per block for expand + depthwise against 40.6 k for the round-2 phases
-    // (45 % fewer vector instructions, but the 4x4x4 MFMAs hold the issue port half their time and the phase does not
-    // overlap its matrix and vector halves at two waves per SIMD), so it stays opt-in.
-    const bool tail_dw4 = [] { const char* e = getenv("MMC_TAIL_DW4"); return e && e[0] == '1'; }();
-    const char* mbt_env = getenv("MMC_MBT");
-    const bool mbt_enabled = (fuse_enabled || fuse_generic_early) && !(mbt_env && mbt_env[0] == '0');
-    // MMC_MBT4 (default 1): the 5x5 stride-1 layers at 28x28 (b4; B4's b7..b9) on mbt4_kernel (depthwise conv on 4x4x4 MFMA blocks)
-    const bool mbt4_enabled = [] { const char* e = getenv("MMC_MBT4"); return !(e && e[0] == '0'); }();   // default since the pair-interleaved tile: b2 66 vs 78.5 us, b4 42.6 vs 59.5
-    bb->mbt = mbt_enabled;
-    { const char* e = getenv("MMC_MBT2"); bb->mbt2 = mbt_enabled && !(e && e[0] == '0'); }
-    const char* tail_env = getenv("MMC_TAIL");
-    const bool tail_enabled = fuse_enabled && !(tail_env && tail_env[0] == '0');
-    int H = IMG / 2;
-    // MMC_PRECISION_FP8: the project convs of the blocks whose OUTPUT is at most fp8_maxh pixels wide run on e4m3 operands.  Default 7
-    // (the 7x7 stage: the CPU study of the operand format puts feature cosine >= 0.997 there); MMC_FP8_MAXH=14 adds the 14x14 stages.
-    const int fp8_maxh = [] { const char* e = getenv("MMC_FP8_MAXH"); const int v = e ? atoi(e) : 7; return v < 7 ? 7 : v; }();
-    bb->fp8_from = NBLK;
-    size_t max_act = (size_t)H * H * STEM_CH, max_exp = 0, max_dw = 0, max_pool = 0;
+    size_t max_act = (size_t)(IMG / 2) * (IMG / 2) * STEM_CH, max_exp = 0, max_dw = 0, max_pool = 0;
     int max_c = 0;
     for (int i = 0; i < NBLK; ++i) {
         BlockW& B = bb->blk[i];
-        B.d = AD.blocks[i];
-        B.H = H;
-        B.ce = B.d.cin * B.d.e;
-        B.cs = B.d.cin / 4 > 1 ? B.d.cin / 4 : 1;
-        B.has_expand = B.d.e != 1;
-        B.skip = B.d.s == 1 && B.d.cin == B.d.cout;
-        same_pad(H, B.d.k, B.d.s, &B.pad, &B.Ho);
+        const int H = B.H;
+        const bool tail_blk = B.front == Front::Tail && i >= 12;               // a row of tail7's block table
+        const bool tail_pre = i == 11 && bb->tail != TailRoute::None && bb->tail != TailRoute::B12;   // tail7's block 11
+        const bool frag_exp = B.front == Front::Mbt || B.front == Front::Mid14 || tail_blk || (tail_pre && bb->tail == TailRoute::B11All);
         char nm[64];
-        const float* exp_w_host = nullptr;
         if (B.has_expand) {
             snprintf(nm, sizeof nm, "b%d.expand", i);
             TAKE(w, (size_t)B.ce * B.d.cin, nm);
             TAKE(b, B.ce, nm);
             TRY_OR_FREE(pack_pw(bb, &B.expand, w, b, B.ce, B.d.cin, 0, LOG2E, LOG2E));
-            exp_w_host = w;
+            const int kp = 32 * B.mb.ksteps;
+            std::vector<_Float16> wn((size_t)B.ce * kp, (_Float16)0.0f);   // natural rows, K zero padded
+            for (int c = 0; c < B.ce && B.fusable; ++c)
+                for (int k = 0; k < B.d.cin; ++k) wn[(size_t)c * kp + k] = (_Float16)(float)(w[(size_t)c * B.d.cin + k] * LOG2E);
+            if (B.front == Front::MbA || B.front == Front::MbD) TRY_OR_FREE(dev_upload(bb, &B.exp_nat, wn));
+            if (B.front == Front::Mb1 || B.front == Front::MbPre) {
+                // K-permuted copy for block 0's folded project: MFMA slot 8q+j holds input channel 4q+j (j < 4), the rest zero --
+                // the layout block 0's in-kernel project leaves in the lanes
+                std::vector<_Float16> wq((size_t)B.ce * 32, (_Float16)0.0f);
+                for (int c = 0; c < B.ce; ++c)
+                    for (int qq = 0; qq < 4; ++qq)
+                        for (int j = 0; j < 4; ++j) wq[(size_t)c * 32 + 8 * qq + j] = wn[(size_t)c * kp + 4 * qq + j];
+                TRY_OR_FREE(dev_upload(bb, &bb->b1_exp_pre, wq));
+            }
+            if (frag_exp) TRY_OR_FREE(dev_upload(bb, &B.exp_frag, pack_frag(wn.data(), B.ce, B.d.cin, kp, B.ce / 16, B.mb.ksteps, 1.0)));
         }
         {
             snprintf(nm, sizeof nm, "b%d.dw", i);
@@ -612,7 +811,8 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
             std::vector<float> db(B.ce);
             for (int c = 0; c < B.ce; ++c) db[c] = (float)(b[c] * LOG2E);
             TRY_OR_FREE(dev_upload(bb, &B.dw_b, db));
-            if ((tail_enabled && i >= 11 && i <= 15) || (mid14_enabled && i >= 6 && i <= 11) || (mbt_enabled && mbt_has(H, B.d.k, B.d.s, B.d.cin, B.ce))) {
+            const bool dwp4 = B.front == Front::Mid14 || tail_blk || (tail_pre && bb->tail == TailRoute::B11All);
+            if (B.front == Front::Mbt || dwp4) {
                 // taps of tail7_kernel / mid14_kernel / mbt_kernel as fp16 pairs: kernel row ky = (k0,k1), (k2,k3), (k4,0); the kernel derives the
                 // odd-output pairs by shifts, giving the same values as mbconv_d_kernel's wl2 table
                 std::vector<uint32_t> dp((size_t)15 * B.ce, 0u);
@@ -627,21 +827,23 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
                             memcpy(&u, h, 4);
                             dp[(size_t)(ky * 3 + d) * B.ce + c] = u;
                         }
-                TRY_OR_FREE(dev_upload(bb, &B.t_dwp, dp));
-                // the same 15 dwords + the bias (as the 16th) in 16-byte requests: [4][ce][4] -- request j of channel c holds slots
-                // 4j .. 4j+3; a wave's request is 1 KB contiguous (16 dword loads per thread were 16 wave-instructions of 256 bytes)
-                std::vector<uint32_t> dp4((size_t)16 * B.ce, 0u);
-                for (int c = 0; c < B.ce; ++c)
-                    for (int t = 0; t < 16; ++t) {
-                        uint32_t v = 0u;
-                        if (t < 15) v = dp[(size_t)t * B.ce + c];
-                        else memcpy(&v, &db[c], 4);   // the bias exactly as dw_b holds it
-                        dp4[((size_t)(t / 4) * B.ce + c) * 4 + (t % 4)] = v;
-                    }
-                TRY_OR_FREE(dev_upload(bb, &B.t_dwp4, dp4));
+                if (B.front == Front::Mbt) TRY_OR_FREE(dev_upload(bb, &B.t_dwp, dp));
+                if (dwp4) {
+                    // the same 15 dwords + the bias (as the 16th) in 16-byte requests: [4][ce][4] -- request j of channel c holds slots
+                    // 4j .. 4j+3; a wave's request is 1 KB contiguous (16 dword loads per thread were 16 wave-instructions of 256 bytes)
+                    std::vector<uint32_t> dp4((size_t)16 * B.ce, 0u);
+                    for (int c = 0; c < B.ce; ++c)
+                        for (int t = 0; t < 16; ++t) {
+                            uint32_t v = 0u;
+                            if (t < 15) v = dp[(size_t)t * B.ce + c];
+                            else memcpy(&v, &db[c], 4);   // the bias exactly as dw_b holds it
+                            dp4[((size_t)(t / 4) * B.ce + c) * 4 + (t % 4)] = v;
+                        }
+                    TRY_OR_FREE(dev_upload(bb, &B.t_dwp4, dp4));
+                }
             }
-            if (((mid14m_enabled && i >= (mid14m_mode == 2 ? 8 : 6) && i <= 10 && H == 14) || (mbt4_enabled && mbt_enabled && H == 28 && B.d.k == 5 && mbt_has(H, B.d.k, B.d.s, B.d.cin, B.ce)) || (tail_dw4 && tail_enabled && i >= 12 && i <= 15 && H == 7)) && B.d.s == 1 && B.ce % 16 == 0) {
-                // Depthwise on the matrix pipe (mid14m_kernel, v_mfma_f32_4x4x4_16B_f16: 16 independent blocks = 16 channels).  A operand
+            if (B.mbt4 || B.mid14m) {
+                // Depthwise on the matrix pipe (v_mfma_f32_4x4x4_16B_f16: 16 independent blocks = 16 channels).  A operand
                 // of block c, kernel row ky, input quad h (columns x0 - 2 + 4h .. +3 of an output tile x0 .. x0+3): the Toeplitz slice
                 // A[i][k] = w[c][ky][k - i + 4h - 2 + R] (zero outside 0 .. K-1), lane 4 blk + i holding k = 0 .. 3, block blk = channel
                 // 2 (blk & 3) + ((blk >> 2) & 1) + 8 (blk >> 3) of the group (channels 2k, 2k+1 in neighbouring 16-lane rows: the kernel
@@ -669,41 +871,57 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
             TAKE(br, B.cs, nm);
             TAKE(we, (size_t)B.ce * B.cs, nm);
             TAKE(be, B.ce, nm);
-            // Squeeze-excite weights, fp32 in MFMA fragment order (se_fused_kernel): 3 output/k fragments of 16
-            // cover Cs <= 48.  FC1 carries 1/(HW*log2e): the pooled sums are over HW pixels of log2(e)-scaled
-            // activations.
-            B.cs4 = (B.cs + 3) / 4 * 4;
-            const double psc = 1.0 / ((double)B.Ho * B.Ho * LOG2E);
-            const int ng = is_b0 ? B.ce / 16 : 0;   // (se_fused_kernel's packing: B0 only, Cs <= 48)
-            std::vector<float> wrp((size_t)ng * 3 * 64 * 4 + 4, 0.f), wep((size_t)ng * 3 * 64 * 4 + 4, 0.f);
-            for (int g = 0; g < ng; ++g)
-                for (int t = 0; t < 3; ++t)
-                    for (int ln = 0; ln < 64; ++ln)
-                        for (int e = 0; e < 4; ++e) {
-                            const int ii = ln & 15, qq = ln >> 4;
-                            const size_t off = (((size_t)g * 3 + t) * 64 + ln) * 4 + e;
-                            const int j = 16 * t + ii, c = 16 * g + 4 * qq + e;         // FC1: Wr[j][c]
-                            if (j < B.cs) wrp[off] = (float)(wr[(size_t)j * B.ce + c] * psc);
-                            const int n = 16 * g + ii, k = 16 * t + 4 * qq + e;         // FC2: We[n][k] (T = g, k-group = t)
-                            if (k < B.cs) wep[off] = we[(size_t)n * B.cs + k];
-                        }
-            // B4: squeeze-excite + project per patch wherever proj_patch_kernel has the shape (blocks 6-15) and Cs fits its 32 slots
-            const bool fp8_blk = bb->fp8 && B.Ho <= fp8_maxh;
-            const bool b4_pp = !fp8_blk && fuse_generic && !(pp_env && pp_env[0] == '0') && B.has_expand && B.cs <= 28 &&
-                               proj_patch_has(B.ce, B.d.cout, B.Ho * B.Ho, B.skip ? 1 : 0);
-            const bool pp_blk = (projse_enabled && i >= 3 && i <= 10) || (tail_enabled && i == 11) || b4_pp;
-            if ((tail_enabled && i >= 12 && i <= 15 && B.cs == 48) || pp_blk) {
+            const bool se_launch = B.back == Back::SeProject || B.back == Back::SeFolded;
+            const double psc = 1.0 / ((double)B.Ho * B.Ho * LOG2E);   // FC1 on pooled sums of HW log2(e)-scaled activations
+            if (se_launch && B.se == Se::Fused) {
+                // Squeeze-excite weights, fp32 in MFMA fragment order (se_fused_kernel): 3 output/k fragments of 16 cover Cs <= 48
+                const int ng = B.ce / 16;
+                std::vector<float> wrp((size_t)ng * 3 * 64 * 4 + 4, 0.f), wep((size_t)ng * 3 * 64 * 4 + 4, 0.f);
+                for (int g = 0; g < ng; ++g)
+                    for (int t = 0; t < 3; ++t)
+                        for (int ln = 0; ln < 64; ++ln)
+                            for (int e = 0; e < 4; ++e) {
+                                const int ii = ln & 15, qq = ln >> 4;
+                                const size_t off = (((size_t)g * 3 + t) * 64 + ln) * 4 + e;
+                                const int j = 16 * t + ii, c = 16 * g + 4 * qq + e;         // FC1: Wr[j][c]
+                                if (j < B.cs) wrp[off] = (float)(wr[(size_t)j * B.ce + c] * psc);
+                                const int n = 16 * g + ii, k = 16 * t + 4 * qq + e;         // FC2: We[n][k] (T = g, k-group = t)
+                                if (k < B.cs) wep[off] = we[(size_t)n * B.cs + k];
+                            }
+                TRY_OR_FREE(dev_upload(bb, &B.se_wrp, wrp));
+                TRY_OR_FREE(dev_upload(bb, &B.se_wep, wep));
+            }
+            if (se_launch && B.se != Se::Fused) {   // natural fp32 rows: se_small_kernel; se_wide_kernel reads the excite FC transposed
+                std::vector<float> wrn((size_t)B.cs * B.ce);
+                for (size_t e = 0; e < wrn.size(); ++e) wrn[e] = (float)(wr[e] * psc);
+                TRY_OR_FREE(dev_upload(bb, &B.se_wr_nat, wrn));
+                if (B.se == Se::Small) {
+                    TRY_OR_FREE(dev_upload(bb, &B.se_we_nat, std::vector<float>(we, we + (size_t)B.ce * B.cs)));
+                } else {   // [Cs][C]: neighbouring lanes, neighbouring words
+                    std::vector<float> wet((size_t)B.cs * B.ce);
+                    for (int c = 0; c < B.ce; ++c)
+                        for (int j = 0; j < B.cs; ++j) wet[(size_t)j * B.ce + c] = we[(size_t)c * B.cs + j];
+                    TRY_OR_FREE(dev_upload(bb, &B.se_we_nat, wet));
+                }
+                TRY_OR_FREE(dev_upload(bb, &B.se_br_nat, std::vector<float>(br, br + B.cs)));
+            }
+            if (B.back == Back::ProjPatch || tail_pre || tail_blk) {
                 // fp16, transposed for matrix-vector use: Wr^T [ce][csp], We^T [csp][ce] (csp = Cs padded to 4)
-                const int csp = (B.cs + 3) / 4 * 4;
+                const int csp = B.cs4;
                 std::vector<_Float16> wrt((size_t)B.ce * csp, (_Float16)0.0f), wet((size_t)csp * B.ce, (_Float16)0.0f);
                 for (int c = 0; c < B.ce; ++c)
                     for (int j = 0; j < B.cs; ++j) {
                         wrt[(size_t)c * csp + j] = (_Float16)wr[(size_t)j * B.ce + c];
                         wet[(size_t)j * B.ce + c] = (_Float16)we[(size_t)c * B.cs + j];
                     }
-                TRY_OR_FREE(dev_upload(bb, &B.t_wr, wrt));
-                TRY_OR_FREE(dev_upload(bb, &B.t_we, wet));
-                if (pp_blk && csp <= 28) {
+                if (B.back == Back::ProjPatch || tail_pre) {
+                    TRY_OR_FREE(dev_upload(bb, &B.t_wr, wrt));
+                    TRY_OR_FREE(dev_upload(bb, &B.t_we, wet));
+                    std::vector<float> brp(csp > 32 ? csp : 32, 0.f);
+                    for (int j = 0; j < B.cs; ++j) brp[j] = br[j];
+                    TRY_OR_FREE(dev_upload(bb, &B.pp_br, brp));
+                }
+                if (B.back == Back::ProjPatch) {
                     // proj_patch_kernel's FC1: [group of four outputs][channel row][4] (ProjPatchArgs::wr_g), zero beyond ce
                     const int rows = proj_patch_fc1_rows(B.ce);
                     std::vector<_Float16> wrg((size_t)(csp / 4) * rows * 4, (_Float16)0.0f);
@@ -712,7 +930,7 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
                             for (int e = 0; e < 4; ++e) wrg[((size_t)g * rows + c) * 4 + e] = wrt[(size_t)c * csp + 4 * g + e];
                     TRY_OR_FREE(dev_upload(bb, &B.t_wrg, wrg));
                 }
-                if (tail_enabled && i >= 12 && i <= 15 && B.cs == 48 && B.ce == 1152) {
+                if (tail_blk) {
                     // tail7_kernel's 16-byte request layout (TailBlock::wr_t / we_t): two rows of the transposed matrices per request
                     std::vector<_Float16> wr2((size_t)18 * 384 * 8), we2((size_t)24 * 288 * 8);
                     for (int p = 0; p < 18; ++p)
@@ -727,38 +945,20 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
                     TRY_OR_FREE(dev_upload(bb, &B.t_wr2, wr2));
                     TRY_OR_FREE(dev_upload(bb, &B.t_we2, we2));
                 }
-                std::vector<float> brp(csp > 32 ? csp : 32, 0.f);
-                for (int j = 0; j < B.cs; ++j) brp[j] = br[j];
-                TRY_OR_FREE(dev_upload(bb, &B.pp_br, brp));
-                B.pp_csp = csp;
             }
-            if ((B.ce <= 256 && B.cs <= 16) || !is_b0) {   // early blocks: light per-patch squeeze-excite kernel; generic schedule: se_wide
-                std::vector<float> wrn((size_t)B.cs * B.ce);
-                for (size_t e = 0; e < wrn.size(); ++e) wrn[e] = (float)(wr[e] * psc);
-                TRY_OR_FREE(dev_upload(bb, &B.se_wr_nat, wrn));
-                if (is_b0) {
-                    TRY_OR_FREE(dev_upload(bb, &B.se_we_nat, std::vector<float>(we, we + (size_t)B.ce * B.cs)));
-                } else {   // se_wide_kernel reads the excite FC transposed ([Cs][C]): neighbouring lanes, neighbouring words
-                    std::vector<float> wet((size_t)B.cs * B.ce);
-                    for (int c = 0; c < B.ce; ++c)
-                        for (int j = 0; j < B.cs; ++j) wet[(size_t)j * B.ce + c] = we[(size_t)c * B.cs + j];
-                    TRY_OR_FREE(dev_upload(bb, &B.se_we_nat, wet));
-                }
-                TRY_OR_FREE(dev_upload(bb, &B.se_br_nat, std::vector<float>(br, br + B.cs)));
+            if ((se_launch && B.se == Se::Fused) || tail_blk) {   // se_fused_kernel's and tail7's FC1 bias, zero padded to 48
+                std::vector<float> brs(B.cs > 48 ? B.cs : 48, 0.f);
+                for (int j = 0; j < B.cs; ++j) brs[j] = br[j];
+                TRY_OR_FREE(dev_upload(bb, &B.se_br, brs));
             }
-            TRY_OR_FREE(dev_upload(bb, &B.se_wrp, wrp));
-            TRY_OR_FREE(dev_upload(bb, &B.se_wep, wep));
-            std::vector<float> brs(B.cs > 48 ? B.cs : 48, 0.f);
-            for (int j = 0; j < B.cs; ++j) brs[j] = br[j];
-            TRY_OR_FREE(dev_upload(bb, &B.se_br, brs));
             TRY_OR_FREE(dev_upload(bb, &B.se_be, std::vector<float>(be, be + B.ce)));
         }
         {
             snprintf(nm, sizeof nm, "b%d.project", i);
             TAKE(w, (size_t)B.d.cout * B.ce, nm);
             TAKE(b, B.d.cout, nm);
-            TRY_OR_FREE(pack_pw(bb, &B.project, w, b, B.d.cout, B.ce, B.Ho <= 14 ? pick_nt(B.d.cout, true) : 0, 1.0 / LOG2E, 1.0));
-            if (bb->fp8 && B.Ho <= fp8_maxh) {
+            TRY_OR_FREE(pack_pw(bb, &B.project, w, b, B.d.cout, B.ce, B.project.nt, 1.0 / LOG2E, 1.0));
+            if (B.proj == Proj::Fp8 && (B.back == Back::SeProject || B.back == Back::SeFolded)) {
                 // e4m3 weights for pw_gemm_fp8_kernel: per-output-channel scale amax / 448 (the 1 / log2 e of the scaled domain rides in the
                 // scale), fragment f = channels 16 f .. +15, k-step of 128, lane (i, q) holds k = 128 ks + 32 q .. +31 of channel 16 f + i
                 Fp8Layer& L = B.p8;
@@ -779,191 +979,44 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
                 TRY_OR_FREE(dev_upload(bb, &L.w8, w8));
                 TRY_OR_FREE(dev_upload(bb, &L.sw, sw));
                 TRY_OR_FREE(dev_upload(bb, &L.b, bp));
-                if (i < bb->fp8_from) bb->fp8_from = i;
             }
-            if (i == 0 && fuse_enabled && B.ce == 32 && B.d.cout == 16) {
-                // block 0's project conv as ONE MFMA fragment (16 outputs x 32 inputs) for mbconv_a_kernel PRE
-                std::vector<_Float16> wf(512, (_Float16)0.0f);
-                for (int c = 0; c < 16; ++c)
-                    for (int k = 0; k < 32; ++k) wf[((k / 8) * 16 + c) * 8 + (k % 8)] = (_Float16)(float)(w[(size_t)c * 32 + k] * (1.0 / LOG2E));
-                TRY_OR_FREE(dev_upload(bb, &bb->b0_pre_w, wf));
-            }
-            if ((projse_enabled && i >= 3 && i <= 10) ||
-                (fuse_generic && !(pp_env && pp_env[0] == '0') && B.has_expand && B.cs <= 28 &&
-                 proj_patch_has(B.ce, B.d.cout, B.Ho * B.Ho, B.skip ? 1 : 0))) {
-                // proj_patch_kernel: fragment order as below, K and N zero-padded to whole fragments
-                const int ks32 = proj_patch_ksteps(B.ce), nf = (B.d.cout + 15) / 16;
-                std::vector<_Float16> wf((size_t)nf * ks32 * 512, (_Float16)0.0f);
-                for (int c = 0; c < B.d.cout; ++c)
-                    for (int k = 0; k < B.ce; ++k)
-                        wf[((((size_t)(c / 16) * ks32 + k / 32) * 64) + ((k % 32) / 8) * 16 + (c % 16)) * 8 + (k % 8)] =
-                            (_Float16)(float)(w[(size_t)c * B.ce + k] * (1.0 / LOG2E));
-                TRY_OR_FREE(dev_upload(bb, &B.pp_w, wf));
+            if (B.back == Back::SeFolded)   // block 0's project conv as ONE MFMA fragment (16 outputs x 32 inputs)
+                TRY_OR_FREE(dev_upload(bb, &bb->b0_pre_w, pack_frag(w, 16, 32, 32, 1, 1, 1.0 / LOG2E)));
+            if (B.back == Back::ProjPatch) {   // proj_patch_kernel: K and N zero-padded to whole fragments
+                const int nf = (B.d.cout + 15) / 16;
+                TRY_OR_FREE(dev_upload(bb, &B.pp_w, pack_frag(w, B.d.cout, B.ce, B.ce, nf, proj_patch_ksteps(B.ce), 1.0 / LOG2E)));
                 std::vector<float> bp((size_t)16 * nf, 0.f);
                 for (int c = 0; c < B.d.cout; ++c) bp[c] = b[c];
                 TRY_OR_FREE(dev_upload(bb, &B.pp_b, bp));
-                B.pp = true;
             }
-            if (tail_enabled && i == 11 && B.ce == 672 && B.d.cout == 192) {
-                // tail7 pre-block: fragment order [12][24][64][8], k-steps 21..23 zero (its k-loop runs 4 steps at a time)
-                std::vector<_Float16> wf((size_t)12 * 24 * 512, (_Float16)0.0f);
-                for (int c = 0; c < B.d.cout; ++c)
-                    for (int k = 0; k < B.ce; ++k)
-                        wf[((((size_t)(c / 16) * 24 + k / 32) * 64) + ((k % 32) / 8) * 16 + (c % 16)) * 8 + (k % 8)] =
-                            (_Float16)(float)(w[(size_t)c * B.ce + k] * (1.0 / LOG2E));
-                TRY_OR_FREE(dev_upload(bb, &bb->pre_wproj, wf));
-            }
-            if (tail_enabled && i >= 12 && i <= 15) {
-                // plain MFMA fragment order [cout/16][ce/32][64 lanes][8]: lane (q*16 + m) holds W[16nf + m][32ks + 8q ..+8]
-                const int ks32 = B.ce / 32;
-                std::vector<_Float16> wf((size_t)B.d.cout * B.ce);
-                for (int c = 0; c < B.d.cout; ++c)
-                    for (int k = 0; k < B.ce; ++k)
-                        wf[((((size_t)(c / 16) * ks32 + k / 32) * 64) + ((k % 32) / 8) * 16 + (c % 16)) * 8 + (k % 8)] =
-                            (_Float16)(float)(w[(size_t)c * B.ce + k] * (1.0 / LOG2E));
-                TRY_OR_FREE(dev_upload(bb, &B.t_wproj, wf));
-            }
+            if (tail_pre)   // tail7 pre-block: [12][24][64][8], k-steps 21..23 zero (its k-loop runs 4 steps at a time)
+                TRY_OR_FREE(dev_upload(bb, &bb->pre_wproj, pack_frag(w, B.d.cout, B.ce, B.ce, 12, 24, 1.0 / LOG2E)));
+            if (tail_blk)
+                TRY_OR_FREE(dev_upload(bb, &B.t_wproj, pack_frag(w, B.d.cout, B.ce, B.ce, B.d.cout / 16, B.ce / 32, 1.0 / LOG2E)));
         }
-        // depthwise geometry
-        B.tw = (B.Ho % 4 == 0) ? 4 : (B.Ho % 7 == 0 && B.Ho <= 7 ? 7 : 2);
-        B.CG = B.ce / 8;
-        B.nz = 1;
-        while (B.CG / B.nz > 256 || B.CG % B.nz) ++B.nz;   // layers wider than 2048 channels: split the channel groups
-        B.CG /= B.nz;
-        B.S = 256 / B.CG > 0 ? 256 / B.CG : 1;
-        const int strips = B.Ho * (B.Ho / B.tw);
-        const int passes = (strips + B.S - 1) / B.S;
-        B.iters = passes >= 8 ? 4 : 1;
-        B.parts = (passes + B.iters - 1) / B.iters;
-        if (B.has_expand && ((fuse_enabled && i < 16) || fuse_generic)) {
-            FuseCfg fc = is_b0 ? B0_FUSE[i] : generic_fuse_cfg(H, B.d.k, B.d.s, B.ce, b4_cc14);
-            if (const char* ov = getenv("MMC_FUSE_CFG")) {   // "i:TH,TWo,CC;..." experiment override
-                char key[16];
-                snprintf(key, sizeof key, "%d:", i);
-                const char* hit = strstr(ov, key);
-                while (hit && hit != ov && hit[-1] != ';') hit = strstr(hit + 1, key);
-                if (hit) sscanf(hit + strlen(key), "%d,%d,%d,%d,%d,%d", &fc.TH, &fc.TWo, &fc.CC, &fc.TW, &fc.PB, &fc.WLDS);
-            }
-            if (fc.TH > 0 && B.Ho % fc.TH == 0 && B.Ho % fc.TWo == 0 && B.ce % fc.CC == 0 && fc.CC % 16 == 0) {
-                B.f_TH = fc.TH; B.f_TWo = fc.TWo; B.f_CC = fc.CC;
-                B.f_tw = fc.TW;
-                B.f_ksteps = (B.d.cin + 31) / 32;
-                B.f_CCG = fc.CC / 8;
-                B.f_S = 256 / B.f_CCG;
-                B.f_tiles_x = B.Ho / fc.TWo; B.f_tiles_y = B.Ho / fc.TH;
-                int wh = (fc.TH - 1) * B.d.s + B.d.k, wwid = (fc.TWo - 1) * B.d.s + B.d.k;
-                if (wh > H) wh = H;
-                if (wwid > H) wwid = H;
-                B.f_pb = fc.PB < 1 ? 1 : fc.PB;
-                const int ppad = (B.f_pb * wh * wwid + 15) / 16 * 16;
-                B.f_npair = (ppad / 16 + 7) / 8;
-                B.f_wlds = fc.WLDS ? 1 : 0;
-                B.f_wfr_off = ppad * (fc.CC * 2 + 16);                       // E | [weight fragments] | taps+bias
-                B.f_wl_off = B.f_wfr_off + (B.f_wlds ? (fc.CC / 16) * B.f_ksteps * 1024 : 0);
-                B.f_lds = B.f_wl_off + (B.d.k * B.d.k + 1) * fc.CC * 4;
-                B.f_red_off = 0;  // pool scratch [PB][S][CC] aliases E when it fits, else gets its own space
-                if (B.f_pb * B.f_S * fc.CC * 4 > B.f_wfr_off) { B.f_red_off = B.f_lds; B.f_lds += B.f_pb * B.f_S * fc.CC * 4; }
-                const int kp = 32 * B.f_ksteps;
-                if (B.f_lds <= 128 * 1024 && fc.TWo % B.f_tw == 0) {
-                    std::vector<_Float16> wn((size_t)B.ce * kp, (_Float16)0.0f);
-                    for (int c = 0; c < B.ce; ++c)
-                        for (int k = 0; k < B.d.cin; ++k) wn[(size_t)c * kp + k] = (_Float16)(float)(exp_w_host[(size_t)c * B.d.cin + k] * LOG2E);
-                    TRY_OR_FREE(dev_upload(bb, &B.exp_nat, wn));
-                    if (i == 1 && B.d.cin == 16 && kp == 32) {
-                        // K-permuted copy for mbconv_a_kernel PRE: MFMA slot 8q+j holds input channel 4q+j (j < 4), the
-                        // rest zero -- the layout block 0's in-kernel project leaves in the lanes
-                        std::vector<_Float16> wq((size_t)B.ce * 32, (_Float16)0.0f);
-                        for (int c = 0; c < B.ce; ++c)
-                            for (int qq = 0; qq < 4; ++qq)
-                                for (int j = 0; j < 4; ++j) wq[(size_t)c * 32 + 8 * qq + j] = wn[(size_t)c * kp + 4 * qq + j];
-                        TRY_OR_FREE(dev_upload(bb, &bb->b1_exp_pre, wq));
-                    }
-                    {   // fragment order: ((c/16 * ksteps + k/32) * 64 + (k%32)/8 * 16 + c%16) * 8 + k%8
-                        std::vector<_Float16> wf((size_t)B.ce * kp, (_Float16)0.0f);
-                        for (int c = 0; c < B.ce; ++c)
-                            for (int k = 0; k < B.d.cin; ++k)
-                                wf[((((size_t)(c / 16) * B.f_ksteps + k / 32) * 64) + ((k % 32) / 8) * 16 + (c % 16)) * 8 + (k % 8)] = wn[(size_t)c * kp + k];
-                        TRY_OR_FREE(dev_upload(bb, &B.exp_frag, wf));
-                    }
-                    B.fused = true;
-                    // dot2 depthwise variant: only where it measured faster (5x5 stride-1 blocks; MI355X, batch 128/256)
-                    static const bool B0_DOT2[16] = {0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1, 0, 1, 1, 1, 0};
-                    if (is_b0 && dot2_enabled && (B0_DOT2[i] || (dot2_env && dot2_env[0] == '2'))) {
-                        // window of mbconv_d_kernel: rows as above, columns widened to whole pixel pairs (even absolute x)
-                        const int padb = B.pad;
-                        int rowlen = 0;
-                        for (int tx = 0; tx < B.f_tiles_x; ++tx) {
-                            int x0 = tx * fc.TWo * B.d.s - padb, x1 = (tx * fc.TWo + fc.TWo - 1) * B.d.s - padb + B.d.k;
-                            x0 = x0 < 0 ? 0 : x0;
-                            x1 = x1 > H ? H : x1;
-                            const int rl = 2 * (((x1 + 1) >> 1) - (x0 >> 1));
-                            if (rl > rowlen) rowlen = rl;
-                        }
-                        const int dpad = (B.f_pb * wh * rowlen + 15) / 16 * 16;
-                        const int np = (B.pad % 2 + B.d.s + B.d.k + 1) / 2;
-                        B.d_npair = (dpad / 16 + 7) / 8;
-                        B.d_wl_off = dpad * fc.CC * 2;
-                        B.d_lds = B.d_wl_off + B.d.k * 2 * np * fc.CC * 4 + fc.CC * 4;
-                        B.d_red_off = 0;
-                        if (B.f_pb * B.f_S * fc.CC * 4 > B.d_wl_off) { B.d_red_off = B.d_lds; B.d_lds += B.f_pb * B.f_S * fc.CC * 4; }
-                        B.use_d = B.d_lds <= 128 * 1024;
-                    }
-                    const size_t pp = (size_t)B.f_tiles_x * B.f_tiles_y * B.ce;
-                    if (pp > max_pool) max_pool = pp;
-                }
-            }
-        }
-        if ((size_t)H * H * B.ce > max_exp && B.has_expand && !B.fused) max_exp = (size_t)H * H * B.ce;
-        if ((size_t)B.Ho * B.Ho * B.ce > max_dw) max_dw = (size_t)B.Ho * B.Ho * B.ce;
-        if ((size_t)B.Ho * B.Ho * B.d.cout > max_act) max_act = (size_t)B.Ho * B.Ho * B.d.cout;
-        if ((size_t)B.parts * B.ce > max_pool) max_pool = (size_t)B.parts * B.ce;
-        if (i == 0 && (size_t)49 * B.ce > max_pool) max_pool = (size_t)49 * B.ce;
-        if (B.ce > max_c) max_c = B.ce;
-        H = B.Ho;
+        if (B.fusable) max_pool = std::max(max_pool, (size_t)B.mb.tiles_x * B.mb.tiles_y * B.ce);
+        if ((size_t)H * H * B.ce > max_exp && B.has_expand && !B.fusable) max_exp = (size_t)H * H * B.ce;
+        max_dw = std::max(max_dw, (size_t)B.Ho * B.Ho * B.ce);
+        max_act = std::max(max_act, (size_t)B.Ho * B.Ho * B.d.cout);
+        max_pool = std::max(max_pool, (size_t)B.parts * B.ce);
+        if (i == 0) max_pool = std::max(max_pool, (size_t)49 * B.ce);
+        max_c = std::max(max_c, B.ce);
     }
     {
         TAKE(w, (size_t)FEAT * HEAD_IN, "head.weight");
         TAKE(b, FEAT, "head.bias");
         TRY_OR_FREE(pack_pw(bb, &bb->head, w, b, FEAT, HEAD_IN, 4, LOG2E, LOG2E));
-        if (tail_enabled && HEAD_IN % 32 == 0) {   // the same weights in plain fragment order [80][10][64][8] for tail7's head phase
-            std::vector<_Float16> wf((size_t)FEAT * HEAD_IN);
-            for (int c = 0; c < FEAT; ++c)
-                for (int k = 0; k < HEAD_IN; ++k)
-                    wf[((((size_t)(c / 16) * (HEAD_IN / 32) + k / 32) * 64) + ((k % 32) / 8) * 16 + (c % 16)) * 8 + (k % 8)] =
-                        (_Float16)(float)(w[(size_t)c * HEAD_IN + k] * LOG2E);
-            TRY_OR_FREE(dev_upload(bb, &bb->head_wfrag, wf));
-        }
+        if (bb->tail == TailRoute::B11 || bb->tail == TailRoute::B11All)   // the same weights in plain fragment order for tail7's head phase
+            TRY_OR_FREE(dev_upload(bb, &bb->head_wfrag, pack_frag(w, FEAT, HEAD_IN, HEAD_IN, FEAT / 16, HEAD_IN / 32, LOG2E)));
     }
-    if (tail_enabled) {
-        bool ok = NBLK == 16;
-        for (int i = 12; i <= 15 && ok; ++i) {
-            const BlockW& B = bb->blk[i];
-            ok = ok && B.exp_frag && B.t_wr2 && B.t_we2 && B.t_dwp && B.t_wproj && B.H == 7 && B.d.s == 1 && B.d.cin == 192 && B.ce == 1152;
+    if (bb->tail != TailRoute::None) {
+        std::vector<TailBlock> tab(4);
+        for (int j = 0; j < 4; ++j) {
+            const BlockW& B = bb->blk[12 + j];
+            tab[j] = TailBlock{B.exp_frag, B.expand.b, B.t_dwp4, B.dw_b, B.t_wr2, B.se_br, B.t_we2, B.se_be, B.t_wproj, B.project.b,
+                               B.d.cout, B.d.k};
         }
-        if (ok) {
-            std::vector<TailBlock> tab(4);
-            for (int j = 0; j < 4; ++j) {
-                const BlockW& B = bb->blk[12 + j];
-                tab[j] = TailBlock{B.exp_frag, B.expand.b, B.t_dwp4, B.dw_b, B.t_wr2, B.se_br, B.t_we2, B.se_be, B.t_wproj, B.project.b,
-                                   B.d.cout, B.d.k, B.dw_diag};
-                bb->tail_dw4 = bb->tail_dw4 && B.dw_diag != nullptr;
-            }
-            TRY_OR_FREE(dev_upload(bb, &bb->tail_tab, tab));
-            const char* tf = getenv("MMC_TAIL_FULL");
-            const BlockW& B11 = bb->blk[11];
-            bb->tail_full = !(tf && tf[0] == '0') && bb->pre_wproj && bb->head_wfrag && B11.t_wr && B11.pp_csp == 28 && B11.fused &&
-                            B11.f_tiles_x * B11.f_tiles_y == 1;
-            const char* tb = getenv("MMC_TAIL_B11");
-            bb->tail_b11 = bb->tail_full && !(tb && tb[0] == '0') && B11.exp_frag && B11.t_dwp && B11.f_ksteps == 4 && B11.ce == 672 &&
-                           B11.d.k == 5 && B11.d.s == 2 && B11.H == 14;
-        }
-    }
-    {
-        const char* e = getenv("MMC_FUSE_B0");
-        const BlockW& B1 = bb->blk[1];
-        { const char* m1 = getenv("MMC_MB1"); bb->mb1 = !(m1 && m1[0] == '0'); }
-        bb->fuse_b0b1 = !(e && e[0] == '0') && bb->fuse_stem && bb->b0_pre_w && bb->b1_exp_pre && B1.fused && !B1.use_d && B1.f_TH == 8 &&
-                        B1.f_TWo == 8 && B1.f_CC == 48 && B1.f_tw == 2 && B1.f_pb == 1 && !B1.f_wlds && B1.f_npair == 3;
+        TRY_OR_FREE(dev_upload(bb, &bb->tail_tab, tab));
     }
     if (rd.next != nt) {
         mmc_backbone_destroy(bb);
@@ -971,10 +1024,7 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
     }
     const size_t mb = (size_t)max_batch;
     {
-        const char* ls = getenv("MMC_LANES");
-        int nl = ls ? atoi(ls) : 2;
-        if (nl < 1) nl = 1;
-        if (nl > 4) nl = 4;
+        int nl = std::max(1, std::min(o.lanes, 4));
         if (bb->keep || max_batch < 2 * nl) nl = 1;
         bb->nlanes = nl;
         bb->lane_cap = (max_batch + nl - 1) / nl;
@@ -1075,147 +1125,86 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             prof->entries.push_back(pe_);                                               \
         }                                                                               \
     } while (0)
+    // per-tensor mode (MMC_KEEP_ACTIVATIONS=1): copy a tensor out under its name
+#define SAVE(name, dev, elems, is_half)                                                                  \
+    do {                                                                                                 \
+        if (bb->keep) { int r_ = save_act(bb, name, dev, elems, is_half, st); if (r_) return r_; }      \
+    } while (0)
     char nm[64];
     _Float16* x = ws.act0;
     _Float16* y = ws.act1;
-    const bool stem_fused = bb->fuse_stem;   // then the stem tensor never exists in HBM (no "stem" activation to keep)
-    if (!stem_fused) {
+    auto swap_xy = [&] { _Float16* t = x; x = y; y = t; };
+    const int lane_idx = (int)(&ws - bb->lanes);
+    if (!bb->fuse_stem) {   // (fused: the stem tensor never exists in HBM, no "stem" activation to keep)
         STEP("stem", "stem_conv", launch_stem(patches_dev, bb->stem_w, bb->stem_b, bb->stem_pad, x, n, bb->stem_ch, st));
-        if (bb->keep) { int r = save_act(bb, "stem", x, (size_t)n * 112 * 112 * bb->stem_ch, true, st); if (r) return r; }
+        SAVE("stem", x, (size_t)n * 112 * 112 * bb->stem_ch, true);
     }
-    bool tail_done = false;
-    const bool se_small_enabled = bb->se_small;
-    const int FEAT = bb->feat;
-    (void)FEAT;
     for (int i = 0; i < bb->nblk; ++i) {
-        if (i == 12 && bb->tail_tab) {
-            // blocks 12..15 in one launch, one patch per workgroup, tensors resident in LDS (tail7_kernel)
-            if (!bb->keep) {
-                TailArgs ta{};
-                ta.X = x; ta.Y = y; ta.B = n; ta.nblk = 4; ta.blk = bb->tail_tab; ta.dw4 = bb->tail_dw4;
-                STEP("b12-15.tail", "tail7", launch_tail7(ta, st));
-                _Float16* t = x; x = y; y = t;
-            } else {
-                for (int j = 0; j < 4; ++j) {   // block at a time so every intermediate tensor can be read back
-                    TailArgs ta{};
-                    ta.X = x; ta.Y = y; ta.B = n; ta.nblk = 1; ta.blk = bb->tail_tab + j; ta.dw4 = bb->tail_dw4;
-                    ta.dbg_dw = ws.dwbuf; ta.dbg_gate = ws.gate; ta.dbg_clk = ws.pool_part;
-                    snprintf(nm, sizeof nm, "b%d.tail", 12 + j);
-                    STEP(nm, "tail7", launch_tail7(ta, st));
-                    int r;
-                    snprintf(nm, sizeof nm, "b%d.dw", 12 + j);
-                    if ((r = save_act(bb, nm, ws.dwbuf, (size_t)n * 49 * bb->blk[12 + j].ce, true, st))) return r;
-                    snprintf(nm, sizeof nm, "b%d.gate", 12 + j);
-                    if ((r = save_act(bb, nm, ws.gate, (size_t)n * bb->blk[12 + j].ce, false, st))) return r;
-                    snprintf(nm, sizeof nm, "b%d.out", 12 + j);
-                    if ((r = save_act(bb, nm, y, (size_t)n * 49 * bb->blk[12 + j].d.cout, true, st))) return r;
-                    snprintf(nm, sizeof nm, "b%d.clk", 12 + j);
-                    if ((r = save_act(bb, nm, ws.pool_part, (size_t)n * 8, false, st))) return r;
-                    _Float16* t = x; x = y; y = t;
-                }
-            }
-            i = 15;
-            continue;
-        }
         BlockW& B = bb->blk[i];
+        if (B.front == Front::Tail) break;
         const int HWi = B.H * B.H, HWo = B.Ho * B.Ho;
-        int nparts = B.parts;
-        // small-K, small-N project on a big image: thin_proj_kernel (up to 5 k-steps since the gate is folded into the weight
-        // fragments: B0's b2 30.8 vs 43.7 us on pw_gemm; MMC_THIN_PROJ_KS moves the limit, clamped to what is instantiated, and a
-        // shape without an instantiation stays on pw_gemm)
-        static const int thin_max = [] { const char* e = getenv("MMC_THIN_PROJ_KS"); const int v = e ? atoi(e) : 5; return v < 0 ? 0 : (v > 6 ? 6 : v); }();
-        const bool use_thin = bb->thin_proj && B.project.nt == 2 && B.project.n_chunks == 1 && B.project.Kp / 32 <= thin_max &&
-                              thin_proj_has(B.project.Kp / 32) && B.project.N <= 32 &&
-                              (B.project.N & 7) == 0 && (HWo & 15) == 0 && HWo >= 3136;
-        // block 1's depthwise output as three 32-channel planes between mb1_kernel and thin_proj_kernel (see mb1_kernel); per-tensor
-        // mode keeps the interleaved tensor it hands out (MMC_B1_PLANAR=0 switches the planes off)
-        const bool b1_planar = i == 1 && use_thin && bb->b1_planar && !bb->keep && B.project.K == 96;
-        bool d_planar = false;   // set where mb1_kernel is the producer
-        if (i == 11 && bb->tail_full && bb->tail_b11 && !bb->keep) {
-            // the whole of block 11, blocks 12..15 and the head conv in ONE launch: from block 10's output to the feature vector
-            TailArgs ta{};
-            ta.B = n; ta.blk = bb->tail_tab; ta.nblk = 4; ta.dw4 = bb->tail_dw4;
-            ta.pre_X = x; ta.pre_wexp = B.exp_frag; ta.pre_bexp = B.expand.b; ta.pre_dwp = B.t_dwp4; ta.pre_bdw = B.dw_b;
-            ta.pre_wr_t = B.t_wr; ta.pre_br = B.pp_br; ta.pre_we_t = B.t_we; ta.pre_be = B.se_be; ta.pre_wproj = bb->pre_wproj;
-            ta.pre_bproj = B.project.b; ta.inv_hw = (float)(1.0 / (49.0 * LOG2E));
-            ta.head_w = bb->head_wfrag; ta.head_b = bb->head.b; ta.feat = out_dev;
-            if (bb->tail_clk) {   // debug clock: rows of this lane's patches (out_dev is the lane's slice of the caller's matrix)
-                ta.dbg_clk = bb->tail_clk + (size_t)(&ws - bb->lanes) * bb->lane_cap * 64; ta.clk_sections = 1;
-            }
-            STEP("b11all-head.tail", "tail7", launch_tail7(ta, st));
-            tail_done = true;
-            break;
-        }
-        if (i == 0 && stem_fused) {
+        snprintf(nm, sizeof nm, "b%d.mbconv", i);
+        char fl[48];
+        switch (B.front) {
+        case Front::StemDw:
             // with block 0's project folded into block 1's kernel the depthwise output goes to the spare activation
             // buffer (block 1 reads it while writing its own depthwise output to dwbuf)
             STEP("stem+b0.dw", "stem_dw", launch_stem_dw(patches_dev, bb->stem_w, bb->stem_b, bb->stem_pad, B.dw_w, B.dw_b,
                                                           bb->fuse_b0b1 ? y : ws.dwbuf, ws.pool_part, n, st));
-            nparts = 49;
-        } else if (B.fused && B.t_dwp && B.exp_frag && (B.d.s == 1 ? bb->mbt : bb->mbt2) && mbt_has(B.H, B.d.k, B.d.s, B.d.cin, B.ce)) {
+            break;
+        case Front::Mbt: {
             MbtArgs ta{};
             ta.X = x; ta.wexp = B.exp_frag; ta.bexp = B.expand.b; ta.dwp = B.t_dwp; ta.bdw = B.dw_b; ta.D = ws.dwbuf;
             ta.pool = ws.pool_part; ta.B = n; ta.H = B.H; ta.Cin = B.d.cin; ta.Ce = B.ce; ta.ks = B.d.k; ta.stride = B.d.s;
-            ta.dwtoe = (B.d.s == 1 && B.H == 28 && B.d.k == 5) ? B.dw_diag : nullptr;
-            nparts = B.d.s == 2 ? (B.Ho / 7) * (B.Ho / 14) : (B.H / 14) * (B.H / 28);
-            snprintf(nm, sizeof nm, "b%d.mbconv", i);
-            char ml[48];   // the instantiation's template arguments, as rocprofv3 names it
-            snprintf(ml, sizeof ml, "%s<%d,%d,%d,%d>", B.d.s == 2 ? "mbt2" : "mbt", B.d.k, (B.d.cin + 31) / 32, B.ce, B.H);
-            if (ta.dwtoe) snprintf(ml, sizeof ml, "mbt4<%d,%d>", (B.d.cin + 31) / 32, B.ce);
-            STEP(nm, ml, launch_mbt(ta, st));
-        } else if (B.fused && bb->mid14 && ((i >= 6 && i <= bb->mid14_last) || (i == 11 && bb->mid14_b11)) && B.t_dwp && B.exp_frag) {
+            ta.dwtoe = B.mbt4 ? B.dw_diag : nullptr;
+            // the instantiation's template arguments, as rocprofv3 names it
+            if (B.mbt4) snprintf(fl, sizeof fl, "mbt4<%d,%d>", (B.d.cin + 31) / 32, B.ce);
+            else snprintf(fl, sizeof fl, "%s<%d,%d,%d,%d>", B.d.s == 2 ? "mbt2" : "mbt", B.d.k, (B.d.cin + 31) / 32, B.ce, B.H);
+            STEP(nm, fl, launch_mbt(ta, st));
+            break;
+        }
+        case Front::Mid14: {
             Mid14Args ma{};
             ma.X = x; ma.wexp = B.exp_frag; ma.bexp = B.expand.b; ma.dwp = B.t_dwp4; ma.bdw = B.dw_b; ma.D = ws.dwbuf;
             ma.pool = ws.pool_part; ma.B = n; ma.Cin = B.d.cin; ma.Ce = B.ce; ma.ks = B.d.k;
-            ma.dwdiag = (B.d.s == 1) ? B.dw_diag : nullptr;
-            { const char* e = getenv("MMC_MID14_SPLIT"); ma.nsplit = e ? atoi(e) : (ma.dwdiag ? 1 : (B.d.s == 2 ? 7 : 4)); }
-            ma.stride = B.d.s;
-            if (bb->mid_clk && i == 10) ma.dbg_clk = bb->mid_clk + (size_t)(&ws - bb->lanes) * bb->lane_cap * 128;
-            nparts = 1;
-            snprintf(nm, sizeof nm, "b%d.mbconv", i);
-            char ml[48];
-            snprintf(ml, sizeof ml, ma.dwdiag ? "mid14m<%d,%d,%d,%d>" : "mid14<%d,%d,%d,%d>", (B.d.cin + 31) / 32, B.d.k, B.ce, B.d.s);
-            STEP(nm, ml, launch_mid14(ma, st));
-        } else if (B.fused) {
-            MbArgs a{};
+            ma.dwdiag = B.mid14m ? B.dw_diag : nullptr;
+            ma.nsplit = B.mid14m ? 1 : 4;
+            if (bb->mid_clk && i == 10) ma.dbg_clk = bb->mid_clk + (size_t)lane_idx * bb->lane_cap * 128;
+            snprintf(fl, sizeof fl, B.mid14m ? "mid14m<%d,%d,%d,%d>" : "mid14<%d,%d,%d,%d>", (B.d.cin + 31) / 32, B.d.k, B.ce, B.d.s);
+            STEP(nm, fl, launch_mid14(ma, st));
+            break;
+        }
+        case Front::Mb1: {
+            Mb1Args m1{};
+            m1.X = y; m1.pre_w = bb->b0_pre_w; m1.pre_b = bb->blk[0].project.b; m1.pre_gate = ws.gate; m1.wexp = bb->b1_exp_pre;
+            m1.bexp = B.expand.b; m1.wdw = B.dw_w; m1.bdw = B.dw_b; m1.D = ws.dwbuf; m1.pool = ws.pool_part; m1.B = n;
+            m1.planar = B.planar ? 1 : 0;
+            STEP("b0.project+b1.mbconv", "mb1", launch_mb1(m1, st));
+            break;
+        }
+        case Front::MbPre: case Front::MbD: case Front::MbA: {
+            MbArgs a = B.mb;
             a.X = x; a.Wexp = B.exp_nat; a.bexp = B.expand.b; a.Wdw = B.dw_w; a.bdw = B.dw_b; a.out = ws.dwbuf;
-            a.pool_part = ws.pool_part; a.B = n; a.H = B.H; a.W = B.H; a.Cin = B.d.cin; a.Ce = B.ce; a.Ho = B.Ho;
-            a.Wo = B.Ho; a.pad = B.pad; a.ks = B.d.k; a.stride = B.d.s; a.tw = B.f_tw; a.ksteps = B.f_ksteps;
-            a.TH = B.f_TH; a.TWo = B.f_TWo; a.tiles_x = B.f_tiles_x; a.tiles_y = B.f_tiles_y; a.CC = B.f_CC;
-            a.CCG = B.f_CCG; a.S = B.f_S; a.red_off = B.f_red_off; a.lds_bytes = B.f_lds; a.npair = B.f_npair; a.pb = B.f_pb; a.wlds = B.f_wlds; a.wfr_off = B.f_wfr_off; a.Wfrag = B.exp_frag;
-            a.wl_off = B.f_wl_off;
-            nparts = B.f_tiles_x * B.f_tiles_y;
-            snprintf(nm, sizeof nm, "b%d.mbconv", i);
-            char fl[48];
-            if (B.use_d) {
-                a.npair = B.d_npair; a.wl_off = B.d_wl_off; a.red_off = B.d_red_off; a.lds_bytes = B.d_lds;
+            a.pool_part = ws.pool_part; a.B = n;
+            if (B.front == Front::MbD) {
                 snprintf(fl, sizeof fl, "mbconv_d<%d,%d,%d,%d,%d,%d,%d>", a.ks, a.stride, a.ksteps, a.npair, a.CC, a.TWo, a.pb);
                 STEP(nm, fl, launch_mbconv_d(a, st));
+            } else if (B.front == Front::MbPre) {
+                a.X = y; a.Cin = 32; a.Wexp = bb->b1_exp_pre;   // block 0's depthwise output; its gate is in ws.gate
+                STEP("b0.project+b1.mbconv", "mbconv_a_pre", launch_mbconv_pre(a, bb->b0_pre_w, bb->blk[0].project.b, ws.gate, st));
             } else {
-                snprintf(fl, sizeof fl, "mbconv_a<%d,%d,%d,%d,%d,%d,%d,%d>", a.ks, a.stride, a.tw, a.ksteps, a.npair, a.CC, a.pb, a.wlds);
-                if (i == 1 && bb->fuse_b0b1 && bb->mb1) {
-                    Mb1Args m1{};
-                    m1.X = y; m1.pre_w = bb->b0_pre_w; m1.pre_b = bb->blk[0].project.b; m1.pre_gate = ws.gate; m1.wexp = bb->b1_exp_pre;
-                    m1.bexp = B.expand.b; m1.wdw = B.dw_w; m1.bdw = B.dw_b; m1.D = ws.dwbuf; m1.pool = ws.pool_part; m1.B = n;
-                    m1.planar = b1_planar ? 1 : 0;
-                    d_planar = b1_planar;
-                    nparts = 14;
-                    snprintf(nm, sizeof nm, "b0.project+b1.mbconv");
-                    STEP(nm, "mb1", launch_mb1(m1, st));
-                } else if (i == 1 && bb->fuse_b0b1) {
-                    a.X = y; a.Cin = 32; a.Wexp = bb->b1_exp_pre;   // block 0's depthwise output; its gate is in ws.gate
-                    snprintf(nm, sizeof nm, "b0.project+b1.mbconv");
-                    STEP(nm, "mbconv_a_pre", launch_mbconv_pre(a, bb->b0_pre_w, bb->blk[0].project.b, ws.gate, st));
-                } else
+                snprintf(fl, sizeof fl, "mbconv_a<%d,%d,%d,%d,%d,%d,%d,0>", a.ks, a.stride, a.tw, a.ksteps, a.npair, a.CC, a.pb);
                 STEP(nm, fl, launch_mbconv_a(a, st));
             }
-        } else {
+            break;
+        }
+        default: {   // Front::Unfused
             const _Float16* dw_in = x;
             if (B.has_expand) {
                 snprintf(nm, sizeof nm, "b%d.expand", i);
                 STEP(nm, gemm_label(B.expand, n * HWi, EPI_SILU, false, false),
                      run_gemm(B.expand, x, n * HWi, ws.expbuf, EPI_SILU, nullptr, HWi, nullptr, nullptr, st));
-                if (bb->keep) { int r = save_act(bb, nm, ws.expbuf, (size_t)n * HWi * B.ce, true, st); if (r) return r; }
+                SAVE(nm, ws.expbuf, (size_t)n * HWi * B.ce, true);
                 dw_in = ws.expbuf;
             }
             DwArgs d{};
@@ -1223,107 +1212,135 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             d.B = n; d.H = B.H; d.W = B.H; d.C = B.ce; d.Ho = B.Ho; d.Wo = B.Ho; d.pad_t = B.pad; d.pad_l = B.pad;
             d.ks = B.d.k; d.stride = B.d.s; d.tw = B.tw; d.CG = B.CG; d.S = B.S; d.iters = B.iters; d.parts = B.parts; d.nz = B.nz;
             snprintf(nm, sizeof nm, "b%d.dw", i);
-            char dl[48];
-            snprintf(dl, sizeof dl, "dwconv<%d,%d,%d>", d.ks, d.stride, d.tw);
-            STEP(nm, dl, launch_dwconv(d, st));
+            snprintf(fl, sizeof fl, "dwconv<%d,%d,%d>", d.ks, d.stride, d.tw);
+            STEP(nm, fl, launch_dwconv(d, st));
+        }
         }
         snprintf(nm, sizeof nm, "b%d.dw", i);
-        if (bb->keep) {
-            int r = save_act(bb, nm, (i == 0 && bb->fuse_b0b1 && stem_fused) ? y : ws.dwbuf, (size_t)n * HWo * B.ce, true, st);
-            if (r) return r;
-        }
-        if (i == 11 && bb->tail_full) {
-            // block 11's squeeze-excite + project, blocks 12..15 and the head conv in ONE launch (tail7_kernel): from
-            // the last 14x14 depthwise output straight to the feature vector.  Per-tensor mode runs it in pieces.
-            const BlockW& B11 = B;
-            TailArgs ta{};
-            ta.B = n; ta.blk = bb->tail_tab; ta.dw4 = bb->tail_dw4;
-            ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part; ta.pre_wr_t = B11.t_wr; ta.pre_br = B11.pp_br; ta.pre_we_t = B11.t_we;
-            ta.pre_be = B11.se_be; ta.pre_wproj = bb->pre_wproj; ta.pre_bproj = B11.project.b;
-            ta.inv_hw = (float)(1.0 / (49.0 * LOG2E));
-            if (!bb->keep) {
-                ta.nblk = 4; ta.head_w = bb->head_wfrag; ta.head_b = bb->head.b; ta.feat = out_dev;
-                STEP("b11-head.tail", "tail7", launch_tail7(ta, st));
-                tail_done = true;
-                break;
-            }
-            int r;
-            ta.nblk = 0; ta.Y = y; ta.dbg_gate = ws.gate;
-            STEP("b11.tail", "tail7", launch_tail7(ta, st));
-            if ((r = save_act(bb, "b11.gate", ws.gate, (size_t)n * B.ce, false, st))) return r;
-            if ((r = save_act(bb, "b11.out", y, (size_t)n * 49 * 192, true, st))) return r;
-            _Float16* t = x; x = y; y = t;
-            continue;
-        }
-        if (B.pp && B.fused && B.t_wrg) {
+        SAVE(nm, (i == 0 && bb->fuse_b0b1) ? y : ws.dwbuf, (size_t)n * HWo * B.ce, true);
+        if (B.back == Back::Tail) break;   // block 11's back half: the tail launch below
+        if (B.back == Back::ProjPatch) {
             // squeeze-excite + project, one patch per workgroup (proj_patch_kernel): no gate tensor, one launch
             ProjPatchArgs pa{};
             pa.X = ws.dwbuf; pa.pool_part = ws.pool_part; pa.wr_g = B.t_wrg; pa.br = B.pp_br; pa.we_t = B.t_we; pa.be = B.se_be;
             pa.wfrag = B.pp_w; pa.bias = B.pp_b; pa.res = B.skip ? x : nullptr; pa.Y = y;
             pa.dbg_gate = bb->keep ? ws.gate : nullptr;
             pa.dbg_clk = bb->keep ? bb->dbg_clk : nullptr;
-            pa.B = n; pa.HW = HWo; pa.K = B.ce; pa.N = B.d.cout; pa.CSP = B.pp_csp; pa.nparts = nparts;
+            pa.B = n; pa.HW = HWo; pa.K = B.ce; pa.N = B.d.cout; pa.CSP = B.cs4; pa.nparts = B.nparts;
             pa.psc = (float)(1.0 / ((double)HWo * LOG2E));
             snprintf(nm, sizeof nm, "b%d.projse", i);
-            char pl[48];
-            snprintf(pl, sizeof pl, "proj_patch<%d,%d,%d,%d>", proj_patch_ksteps(B.ce), (B.d.cout + 15) / 16, HWo, B.skip ? 1 : 0);
-            STEP(nm, pl, launch_proj_patch(pa, st));
-            if (bb->keep) {
-                int r;
-                snprintf(nm, sizeof nm, "b%d.gate", i);
-                if ((r = save_act(bb, nm, ws.gate, (size_t)n * B.ce, false, st))) return r;
-                snprintf(nm, sizeof nm, "b%d.out", i);
-                if ((r = save_act(bb, nm, y, (size_t)n * HWo * B.d.cout, true, st))) return r;
-                snprintf(nm, sizeof nm, "b%d.clk", i);
-                if ((r = save_act(bb, nm, bb->dbg_clk, (size_t)n * 8, false, st))) return r;
-            }
-            _Float16* t = x; x = y; y = t;
+            snprintf(fl, sizeof fl, "proj_patch<%d,%d,%d,%d>", proj_patch_ksteps(B.ce), (B.d.cout + 15) / 16, HWo, B.skip ? 1 : 0);
+            STEP(nm, fl, launch_proj_patch(pa, st));
+            snprintf(nm, sizeof nm, "b%d.gate", i);
+            SAVE(nm, ws.gate, (size_t)n * B.ce, false);
+            snprintf(nm, sizeof nm, "b%d.out", i);
+            SAVE(nm, y, (size_t)n * HWo * B.d.cout, true);
+            snprintf(nm, sizeof nm, "b%d.clk", i);
+            SAVE(nm, bb->dbg_clk, (size_t)n * 8, false);
+            swap_xy();
             continue;
         }
         snprintf(nm, sizeof nm, "b%d.gate", i);
-        if (bb->arch != MMC_ARCH_B0)
-            STEP(nm, "se_wide", launch_se_wide(ws.pool_part, nparts, n, B.ce, B.cs, B.se_wr_nat, B.se_br_nat, B.se_we_nat, B.se_be,
+        if (B.se == Se::Wide)
+            STEP(nm, "se_wide", launch_se_wide(ws.pool_part, B.nparts, n, B.ce, B.cs, B.se_wr_nat, B.se_br_nat, B.se_we_nat, B.se_be,
                                                ws.gate, st));
-        else if (B.se_wr_nat && se_small_enabled)
-            STEP(nm, "se_small", launch_se_small(ws.pool_part, nparts, n, B.ce, B.cs, B.se_wr_nat, B.se_br_nat, B.se_we_nat, B.se_be,
+        else if (B.se == Se::Small)
+            STEP(nm, "se_small", launch_se_small(ws.pool_part, B.nparts, n, B.ce, B.cs, B.se_wr_nat, B.se_br_nat, B.se_we_nat, B.se_be,
                                                  ws.gate, st));
         else
-        STEP(nm, "se_fused", launch_se_gate(ws.pool_part, nparts, n, B.ce, B.cs4, B.se_wrp, B.se_br, B.se_wep, B.se_be,
-                                            ws.gate, st));
-        if (bb->keep) { int r = save_act(bb, nm, ws.gate, (size_t)n * B.ce, false, st); if (r) return r; }
-        if (i == 0 && bb->fuse_b0b1 && stem_fused) continue;   // block 0's project runs inside block 1's kernel
+            STEP(nm, "se_fused", launch_se_gate(ws.pool_part, B.nparts, n, B.ce, B.cs4, B.se_wrp, B.se_br, B.se_wep, B.se_be,
+                                                ws.gate, st));
+        SAVE(nm, ws.gate, (size_t)n * B.ce, false);
+        if (B.back == Back::SeFolded) continue;   // block 0's project runs inside block 1's kernel
         snprintf(nm, sizeof nm, "b%d.project", i);
-        const int pks = B.project.Kp / 32;
-        if (use_thin) {
+        if (B.proj == Proj::Thin) {
             // small-K, small-N project on a big image (B4 blocks 0, 1; B0 block 1): stream one patch's fragments per workgroup
             GemmArgs a{};
             a.X = ws.dwbuf; a.M = n * HWo; a.K = B.project.K; a.Wp = B.project.w; a.Kp = B.project.Kp; a.bias = B.project.b; a.Y = y;
             a.N = B.project.N; a.nt = B.project.nt; a.n_chunks = B.project.n_chunks; a.epi = EPI_LINEAR; a.gate = ws.gate; a.HW = HWo;
             a.res = B.skip ? x : nullptr;
-            a.x_plane_rows = d_planar ? n * HWo : 0;
+            a.x_plane_rows = B.planar ? n * HWo : 0;
             STEP(nm, "thin_proj", launch_thin_proj(a, n, st));
-        } else if (B.p8.w8) {
+        } else if (B.proj == Proj::Fp8) {
             Fp8GemmArgs fa{};
             fa.X = ws.dwbuf; fa.M = n * HWo; fa.K = B.p8.K; fa.W8 = B.p8.w8; fa.KS128 = B.p8.KS128; fa.NFp = B.p8.NFp; fa.sw = B.p8.sw;
             fa.bias = B.p8.b; fa.Y = y; fa.N = B.p8.N; fa.gate = ws.gate; fa.HW = HWo; fa.res = B.skip ? x : nullptr;
             STEP(nm, "pw_gemm_fp8", launch_pw_gemm_fp8(fa, st));
         } else
-        STEP(nm, gemm_label(B.project, n * HWo, EPI_LINEAR, true, B.skip), run_gemm(B.project, ws.dwbuf, n * HWo, y, EPI_LINEAR, ws.gate, HWo, B.skip ? x : nullptr, nullptr, st));
+            STEP(nm, gemm_label(B.project, n * HWo, EPI_LINEAR, true, B.skip),
+                 run_gemm(B.project, ws.dwbuf, n * HWo, y, EPI_LINEAR, ws.gate, HWo, B.skip ? x : nullptr, nullptr, st));
         snprintf(nm, sizeof nm, "b%d.out", i);
-        if (bb->keep) { int r = save_act(bb, nm, y, (size_t)n * HWo * B.d.cout, true, st); if (r) return r; }
-        _Float16* t = x; x = y; y = t;
+        SAVE(nm, y, (size_t)n * HWo * B.d.cout, true);
+        swap_xy();
     }
-    const int HWh = bb->blk[bb->nblk - 1].Ho * bb->blk[bb->nblk - 1].Ho;
-    if (tail_done) {
-        // features already written by tail7_kernel
-    } else if (bb->tail_full) {   // per-tensor mode: the head phase of tail7_kernel on its own
+    // ---- the tail and the head ----
+    const float inv_hw7 = (float)(1.0 / (49.0 * LOG2E));
+    if (bb->tail == TailRoute::B11All || (bb->tail == TailRoute::B11 && !bb->keep)) {
+        // from block 11's input (B11All) or its depthwise output (B11) through blocks 12..15 and the head conv to the features, ONE launch
+        const BlockW& B11 = bb->blk[11];
+        TailArgs ta{};
+        ta.B = n; ta.blk = bb->tail_tab; ta.nblk = 4;
+        if (bb->tail == TailRoute::B11All) {
+            ta.pre_X = x; ta.pre_wexp = B11.exp_frag; ta.pre_bexp = B11.expand.b; ta.pre_dwp = B11.t_dwp4; ta.pre_bdw = B11.dw_b;
+        } else {
+            ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part;
+        }
+        ta.pre_wr_t = B11.t_wr; ta.pre_br = B11.pp_br; ta.pre_we_t = B11.t_we; ta.pre_be = B11.se_be; ta.pre_wproj = bb->pre_wproj;
+        ta.pre_bproj = B11.project.b; ta.inv_hw = inv_hw7;
+        ta.head_w = bb->head_wfrag; ta.head_b = bb->head.b; ta.feat = out_dev;
+        if (bb->tail == TailRoute::B11All && bb->tail_clk) {   // debug clock: rows of this lane's patches
+            ta.dbg_clk = bb->tail_clk + (size_t)lane_idx * bb->lane_cap * 64; ta.clk_sections = 1;
+        }
+        STEP(bb->tail == TailRoute::B11All ? "b11all-head.tail" : "b11-head.tail", "tail7", launch_tail7(ta, st));
+        return 0;
+    }
+    if (bb->tail == TailRoute::B11) {   // per-tensor mode: block 11's back half on its own
+        const BlockW& B11 = bb->blk[11];
+        TailArgs ta{};
+        ta.B = n; ta.blk = bb->tail_tab; ta.nblk = 0; ta.Y = y; ta.dbg_gate = ws.gate;
+        ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part; ta.pre_wr_t = B11.t_wr; ta.pre_br = B11.pp_br; ta.pre_we_t = B11.t_we;
+        ta.pre_be = B11.se_be; ta.pre_wproj = bb->pre_wproj; ta.pre_bproj = B11.project.b; ta.inv_hw = inv_hw7;
+        STEP("b11.tail", "tail7", launch_tail7(ta, st));
+        SAVE("b11.gate", ws.gate, (size_t)n * B11.ce, false);
+        SAVE("b11.out", y, (size_t)n * 49 * 192, true);
+        swap_xy();
+    }
+    if (bb->tail != TailRoute::None && !bb->keep) {
+        // blocks 12..15 in one launch, one patch per workgroup, tensors resident in LDS (tail7_kernel)
+        TailArgs ta{};
+        ta.X = x; ta.Y = y; ta.B = n; ta.nblk = 4; ta.blk = bb->tail_tab;
+        STEP("b12-15.tail", "tail7", launch_tail7(ta, st));
+        swap_xy();
+    } else if (bb->tail != TailRoute::None) {
+        for (int j = 0; j < 4; ++j) {   // block at a time so every intermediate tensor can be read back
+            const BlockW& B = bb->blk[12 + j];
+            TailArgs ta{};
+            ta.X = x; ta.Y = y; ta.B = n; ta.nblk = 1; ta.blk = bb->tail_tab + j;
+            ta.dbg_dw = ws.dwbuf; ta.dbg_gate = ws.gate; ta.dbg_clk = ws.pool_part;
+            snprintf(nm, sizeof nm, "b%d.tail", 12 + j);
+            STEP(nm, "tail7", launch_tail7(ta, st));
+            snprintf(nm, sizeof nm, "b%d.dw", 12 + j);
+            SAVE(nm, ws.dwbuf, (size_t)n * 49 * B.ce, true);
+            snprintf(nm, sizeof nm, "b%d.gate", 12 + j);
+            SAVE(nm, ws.gate, (size_t)n * B.ce, false);
+            snprintf(nm, sizeof nm, "b%d.out", 12 + j);
+            SAVE(nm, y, (size_t)n * 49 * B.d.cout, true);
+            snprintf(nm, sizeof nm, "b%d.clk", 12 + j);
+            SAVE(nm, ws.pool_part, (size_t)n * 8, false);
+            swap_xy();
+        }
+    }
+    if (bb->tail == TailRoute::B11) {   // per-tensor mode: the head phase of tail7_kernel on its own
         TailArgs ta{};
         ta.X = x; ta.B = n; ta.nblk = 0; ta.blk = bb->tail_tab; ta.in_wide = 1;
-        ta.head_w = bb->head_wfrag; ta.head_b = bb->head.b; ta.feat = out_dev; ta.inv_hw = (float)(1.0 / (49.0 * LOG2E));
+        ta.head_w = bb->head_wfrag; ta.head_b = bb->head.b; ta.feat = out_dev; ta.inv_hw = inv_hw7;
         STEP("head.tail", "tail7", launch_tail7(ta, st));
-    } else
-        STEP("head", gemm_label(bb->head, n * HWh, EPI_GAP, false, false), run_gemm(bb->head, x, n * HWh, nullptr, EPI_GAP, nullptr, HWh, nullptr, out_dev, st));
-    bb->last_n = n;
+    } else {
+        const int HWh = bb->blk[bb->nblk - 1].Ho * bb->blk[bb->nblk - 1].Ho;
+        STEP("head", gemm_label(bb->head, n * HWh, EPI_GAP, false, false),
+             run_gemm(bb->head, x, n * HWh, nullptr, EPI_GAP, nullptr, HWh, nullptr, out_dev, st));
+    }
+#undef SAVE
 #undef STEP
     return 0;
 }
@@ -1337,9 +1354,8 @@ static int forward_pass(mmc_backbone* bb, const uint8_t* patches_dev, int n, flo
 {
     // Profiling records HIP events on each lane's own stream, i.e. durations as they are with the lanes running
     // concurrently (what rocprofv3 sees); MMC_PROFILE_SERIAL=1 profiles one lane at a time instead (isolated kernels).
-    static const bool serial_prof = [] { const char* e = getenv("MMC_PROFILE_SERIAL"); return e && e[0] == '1'; }();
     const size_t psz = (size_t)IMG * IMG * 3, FEAT = (size_t)bb->feat;
-    if (bb->nlanes == 1 || (prof && serial_prof) || n < 2 * bb->nlanes) {
+    if (bb->nlanes == 1 || (prof && bb->opt.profile_serial) || n < 2 * bb->nlanes) {
         for (int off = 0; off < n; off += bb->lane_cap) {
             const int cur = n - off < bb->lane_cap ? n - off : bb->lane_cap;
             int r = forward_lane(bb, bb->lanes[0], patches_dev + (size_t)off * psz, cur, out_dev + (size_t)off * FEAT, st, prof);

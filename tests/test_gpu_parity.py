@@ -393,7 +393,7 @@ def test_full_batch_size_independent_properties(checkpoint_path, golden_backbone
     bb.close()
 
 
-@pytest.mark.parametrize("knob", ["MMC_FUSE_B0", "MMC_SE_SMALL", "MMC_PROJSE", "MMC_TAIL_B11", "MMC_TAIL_FULL", "MMC_TAIL", "MMC_MB_DOT2", "MMC_MID14", "MMC_MID14=2", "MMC_MID14_B11=1", "MMC_MID14M=1", "MMC_MID14M=0", "MMC_MBT4=0", "MMC_TAIL_DW4=1", "MMC_MB1", "MMC_MBT", "MMC_MBT2", "MMC_THIN_PROJ", "MMC_B1_PLANAR", "MMC_GRAPH",
+@pytest.mark.parametrize("knob", ["MMC_FUSE_B0", "MMC_SE_SMALL", "MMC_PROJSE", "MMC_TAIL_B11", "MMC_TAIL_FULL", "MMC_TAIL", "MMC_MB_DOT2", "MMC_MID14", "MMC_MID14=2", "MMC_MID14M=1", "MMC_MID14M=0", "MMC_MBT4=0", "MMC_MB1", "MMC_MBT", "MMC_MBT2", "MMC_THIN_PROJ", "MMC_B1_PLANAR", "MMC_GRAPH",
                                   "MMC_LANES"])
 def test_every_schedule_variant_meets_the_same_gates(checkpoint_path, golden_backbone, knob, monkeypatch):
     """Each fusion has an environment switch (the separate kernels stay in the library as the reference
@@ -419,12 +419,14 @@ def test_every_schedule_variant_meets_the_same_gates(checkpoint_path, golden_bac
     assert rel_l2(got, base).max() < TOL_NATURAL
     if knob == "MMC_LANES":
         assert np.array_equal(got, base)          # lanes only split the batch: bitwise identical
+    if knob in ("MMC_MID14=2", "MMC_MID14M=1"):
+        assert np.array_equal(got, base)          # on/off switches: any non-zero value is the default schedule
 
 
-@pytest.mark.parametrize("knob", ["MMC_THIN_PROJ", "MMC_PROJSE", "MMC_FUSE", "MMC_B4_CC14=48", "MMC_LANES"])
+@pytest.mark.parametrize("knob", ["MMC_THIN_PROJ", "MMC_PROJSE", "MMC_FUSE", "MMC_LANES"])
 def test_b4_schedule_variants(synth_sd_b4, knob, monkeypatch):
     """B4's schedule switches: lanes only split the batch (bitwise equal); thin_proj (gate folded into the weight fragments) /
-    proj_patch / the fused expand+depthwise / the chunk width change rounding points only."""
+    proj_patch / the fused expand+depthwise change rounding points only."""
     from mermaid_classifier_amd.backbone import Backbone
     from oracle import efficientnet_b0_ref as ref
     sd = {k: v.numpy() for k, v in synth_sd_b4.items()}

@@ -2,7 +2,7 @@
 # The GPU-box run scripts, one entry point (run through gpurun from the repo root):
 #   bash tools/gpu.sh <mode> <tag> [args]        outputs under gpurun_out/<tag>/
 # modes
-#   iter      quick parity subset, isolated per-launch profile, tail7 phase clocks, one bench line         [TUNES="0 1" for MMC_T7_TUNE0]
+#   iter      quick parity subset, isolated per-launch profile, tail7 phase clocks, one bench line
 #   round     whole GPU suite, bench line, layer profile, tail phases, rocprofv3 kernel stats, then `counters`
 #   counters  rocprofv3 --pmc passes over the bench workload, one run per counter group (program directly after `--`)
 #             CMD_OVERRIDE="python3 tools/b4_throughput.py ..." profiles another command with the same groups
@@ -10,7 +10,6 @@
 #   lanes     bench.py under MMC_LANES = 1..4
 #   libvar    alternative builds build_variants/*.so via MMC_LIBRARY: args = bench | lp [grep] | tp   (timing experiments; such
 #             builds may compute wrong results on purpose; `bench` also runs the golden/batch parity subset on each)
-#   tune      tail7 experiment knobs MMC_T7_TUNE0..3 (timing only)
 set -o pipefail
 MODE=${1:?mode}; TAG=${2:?tag}; shift 2
 O=gpurun_out/$TAG
@@ -40,10 +39,8 @@ iter)
   python -m pytest tests/test_gpu_parity.py tests/test_gpu_layers.py -x -q -m gpu > $O/pytest.log 2>&1; rc=$?; tail -3 $O/pytest.log
   [ $rc -ne 0 ] && exit $rc
   python tools/layer_profile.py 2>&1 | tee $O/lp.log | grep -v amdgpu.ids
-  for t in ${TUNES:-0}; do
-    MMC_T7_TUNE0=$t python tools/tail_phases.py 256 2>&1 | tee -a $O/tp.log | grep -v amdgpu.ids
-    MMC_T7_TUNE0=$t python bench.py --full --no-cpu-baseline 2> $O/bench.err | tee $O/bench.json | line bench
-  done ;;
+  python tools/tail_phases.py 256 2>&1 | tee -a $O/tp.log | grep -v amdgpu.ids
+  python bench.py --full --no-cpu-baseline 2> $O/bench.err | tee $O/bench.json | line bench ;;
 round)
   python -m pytest tests -x -q -m gpu -s > $O/pytest.log 2>&1; rc=$?; echo "pytest exit $rc"; tail -2 $O/pytest.log
   [ $rc -ne 0 ] && exit $rc
@@ -66,11 +63,6 @@ libvar)
     lp) MMC_LIBRARY=$f python tools/layer_profile.py > $O/$n.lp 2>&1; grep "${2:-sum of}" $O/$n.lp ;;
     tp) MMC_LIBRARY=$f python tools/tail_phases.py 256 2>&1 | grep -v amdgpu | tee $O/$n.tp ;;
     esac
-  done ;;
-tune)
-  for cfg in "0 0 0 0" "0 1 0 0" "0 2 0 0" "0 3 0 0" "0 0 1 0"; do
-    set -- $cfg
-    MMC_T7_TUNE0=$1 MMC_T7_TUNE1=$2 MMC_T7_TUNE2=$3 MMC_T7_TUNE3=$4 python tools/tail_phases.py 256 2>&1 | tee -a $O/tp.log | grep -v amdgpu.ids
   done ;;
 *) echo "unknown mode $MODE"; exit 2 ;;
 esac

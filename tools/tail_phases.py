@@ -27,16 +27,12 @@ def main():
     torch.cuda.synchronize()
     clk = bb.read_activation("tail.clk", n * 64).reshape(n, 8, 8)
     med = np.median(clk, axis=0)
-    print("tune", [os.environ.get(f"MMC_T7_TUNE{i}", "0") for i in range(4)])
     print("b11 : " + "  ".join(f"{nm} {c:7.0f}" for nm, c in zip(["front", "se", "gate", "project"], med[0][:4])) + f"   total {med[0][:4].sum():8.0f}")
     names = ["expand", "dw", "fc1", "fc2", "gate", "project"]
     for s in range(1, 5):
         print(f"b{11 + s} : " + "  ".join(f"{nm} {c:7.0f}" for nm, c in zip(names, med[s][:6])) + f"   total {med[s][:6].sum():8.0f}")
-    if med[7].any():
-        print("b12 group loop (DW4), sums over 9 groups: expand MFMAs | SiLU + store | depthwise MFMAs | epilogue")
-        print("  wave 0: " + " | ".join(f"{c:7.0f}" for c in med[7][:4]) + "    wave 4: " + " | ".join(f"{c:7.0f}" for c in med[7][4:]))
-    if os.environ.get("MMC_MID14M") != "1":
-        print(f"head: {med[5][0]:7.0f}   whole kernel {med[6][0]:8.0f} cycles (median over {n} workgroups)")
+    print(f"head: {med[5][0]:7.0f}   whole kernel {med[6][0]:8.0f} cycles (median over {n} workgroups)")
+    if os.environ.get("MMC_MID14M") == "0":
         return
     mc = bb.read_activation("mid14.clk", n * 128).reshape(n, 8, 16)[:, :2, :]       # 2 workgroups per patch (mid14m)
     mm = np.median(mc.reshape(-1, 16), axis=0)
