@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "kernels.h"
@@ -164,4 +166,53 @@ static __device__ __forceinline__ T gload(const GLOBAL_AS void* base, unsigned b
         hipError_t e__ = hipGetLastError();     \
         if (e__ != hipSuccess) return (int)e__; \
     } while (0)
+
+// Raises Kernel's dynamic LDS limit to `bytes`, once per device: one flag per kernel instantiation and device index, atomic
+// because handles on several devices may launch from several threads (a race costs a repeated call, nothing else).  Whether
+// this runtime keeps the attribute per device has not been measured; per device is the reading that cannot go wrong.
+// Returns 0 or the HIP error.
+template <auto Kernel>
+static int set_max_lds(int bytes)
+{
+    static std::atomic<bool> done[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    const bool tracked = dev >= 0 && dev < 64;   // (a device index beyond the table sets the attribute on every launch)
+    if (tracked && done[dev].load(std::memory_order_acquire)) return 0;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return (int)e;
+    if (tracked) done[dev].store(true, std::memory_order_release);
+    return 0;
+}
+
+// One row of a launcher's instantiation table: the run-time key (NK shape numbers, named above each table), the label
+// mmc_backbone_profile reports and the launcher of that instantiation.  A family's table is the only statement of what
+// exists: its launcher dispatches on it and its *_label() query (kernels.h) answers from it.
+template <int NK, typename Args>
+struct Inst {
+    int key[NK];
+    const char* label;
+    int (*launch)(const Args&, hipStream_t);
+};
+template <int NK, typename Args, size_t N>
+static const Inst<NK, Args>* find_inst(const Inst<NK, Args> (&table)[N], const int (&key)[NK])
+{
+    for (const auto& t : table)
+        if (std::equal(key, key + NK, t.key)) return &t;
+    return nullptr;
+}
+// the label of the row with this key, or null
+template <int NK, typename Args, size_t N>
+static const char* inst_label(const Inst<NK, Args> (&table)[N], const int (&key)[NK])
+{
+    const auto* t = find_inst(table, key);
+    return t ? t->label : nullptr;
+}
+// launches the row with this key; `none` when there is no such row
+template <int NK, typename Args, size_t N>
+static int inst_launch(const Inst<NK, Args> (&table)[N], const int (&key)[NK], const Args& a, hipStream_t st, int none)
+{
+    const auto* t = find_inst(table, key);
+    return t ? t->launch(a, st) : none;
+}
 

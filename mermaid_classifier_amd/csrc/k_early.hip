@@ -1117,7 +1117,28 @@ __global__ __launch_bounds__(256) void stem_dw_kernel(const uint8_t* __restrict_
 // =============================================================================================
 // Host-side launchers (plain C++ signatures declared in kernels.h)
 // =============================================================================================
-int thin_proj_has(int ksteps) { return ksteps >= 1 && ksteps <= 5; }   // the k-step counts launch_thin_proj instantiates
+template <int KSTEPS, bool RES>
+static int launch_thin_proj_t(const GemmArgs& a, hipStream_t st)
+{
+    const int nfrag = a.HW / 16, patches = a.M / a.HW;
+    int per = (int)(((long)nfrag * patches / 2048 + 3) / 4 * 4);   // fragments per workgroup: ~2048 workgroups, whole rounds of 4 waves
+    if (per < 8) per = 8;
+    if (per > 112) per = 112;
+    if (nfrag < per) per = nfrag;
+    dim3 grid((nfrag + per - 1) / per, patches);
+    hipLaunchKernelGGL((thin_proj_kernel<KSTEPS, RES>), grid, dim3(256), 0, st, a.X, a.K, a.Wp, a.bias, a.Y, a.N, a.gate, a.HW, per, a.res,
+                       a.x_plane_rows);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// thin_proj_kernel's instantiations.  Key: k-steps of 32, skip connection.  (B0: b1 96 -> 24, b2 144 -> 24 + skip; B4: b0 48 -> 24,
+// b1 24 -> 24 + skip, b2 144 -> 32)
+#define TP(KSTEPS, RES) {{KSTEPS, RES}, "thin_proj", launch_thin_proj_t<KSTEPS, RES != 0>},
+static const Inst<2, GemmArgs> THIN_PROJ_TABLE[] = {TP(1, 1) TP(2, 0) TP(3, 0) TP(5, 0) TP(5, 1)};
+#undef TP
+
+const char* thin_proj_label(int ksteps, int res) { return inst_label(THIN_PROJ_TABLE, {ksteps, res}); }
 
 int launch_thin_proj(const GemmArgs& a, int patches, hipStream_t st)
 {
@@ -1125,28 +1146,7 @@ int launch_thin_proj(const GemmArgs& a, int patches, hipStream_t st)
     if (a.nt != 2 || a.n_chunks != 1 || a.K > 192 || (a.K & 7) || a.N > 32 || (a.N & 7) || (a.HW & 15) || !a.gate || a.epi != EPI_LINEAR ||
         a.M != patches * a.HW || (a.x_plane_rows && (a.x_plane_rows != a.M || (a.K & 31))))
         return -15;
-    const int nfrag = a.HW / 16;
-    int per = (int)(((long)nfrag * patches / 2048 + 3) / 4 * 4);   // fragments per workgroup: ~2048 workgroups, whole rounds of 4 waves
-    if (per < 8) per = 8;
-    if (per > 112) per = 112;
-    if (nfrag < per) per = nfrag;
-    dim3 grid((nfrag + per - 1) / per, patches);
-    const int ks = a.Kp / 32;
-#define TP_GO(KS_, RES_) hipLaunchKernelGGL((thin_proj_kernel<KS_, RES_>), grid, dim3(256), 0, st, a.X, a.K, a.Wp, a.bias, a.Y, a.N, a.gate, a.HW, per, a.res, a.x_plane_rows)
-    if (ks == 1 && a.res) TP_GO(1, true);
-    else if (ks == 1) TP_GO(1, false);
-    else if (ks == 2 && a.res) TP_GO(2, true);
-    else if (ks == 2) TP_GO(2, false);
-    else if (ks == 3 && a.res) TP_GO(3, true);
-    else if (ks == 3) TP_GO(3, false);
-    else if (ks == 4 && a.res) TP_GO(4, true);
-    else if (ks == 4) TP_GO(4, false);
-    else if (ks == 5 && a.res) TP_GO(5, true);
-    else if (ks == 5) TP_GO(5, false);
-    else return -15;
-#undef TP_GO
-    LAUNCH_CHECK();
-    return 0;
+    return inst_launch(THIN_PROJ_TABLE, {a.Kp / 32, a.res ? 1 : 0}, a, st, -15);
 }
 
 int launch_stem_dw(const uint8_t* patches, const _Float16* w, const float* bias, const float* padval, const float* Wdw,
@@ -1161,14 +1161,8 @@ int launch_mb1(const Mb1Args& a, hipStream_t st)
 {
     if (a.B < 1) return -15;
     const int lds = 62 * 8 * 160 + 16 * 32 * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mb1_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mb1_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (int r = set_max_lds<&mb1_kernel<false>>(lds)) return r;
+    if (int r = set_max_lds<&mb1_kernel<true>>(lds)) return r;
     // one workgroup per (tile, patch): walks the three channel chunks
     if (a.planar) hipLaunchKernelGGL(mb1_kernel<true>, dim3(14, 1, a.B), dim3(512), lds, st, a);
     else hipLaunchKernelGGL(mb1_kernel<false>, dim3(14, 1, a.B), dim3(512), lds, st, a);
@@ -1181,13 +1175,7 @@ static int launch_mbt_t(const MbtArgs& a, hipStream_t st)
 {
     constexpr int NROWS = 14 + 2 * (KSD / 2), WW = HIMG == 28 ? 28 : 30, NPF = (NROWS * WW + 15) / 16;
     const int lds = NPF * 16 * 112 + 10 * 48 * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mbt_kernel<KSD, CKS, CE, HIMG>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (int r = set_max_lds<&mbt_kernel<KSD, CKS, CE, HIMG>>(lds)) return r;
     hipLaunchKernelGGL((mbt_kernel<KSD, CKS, CE, HIMG>), dim3((HIMG / 14) * (HIMG / 28), CE / 48, a.B), dim3(512), lds, st, a);
     LAUNCH_CHECK();
     return 0;
@@ -1197,12 +1185,7 @@ template <int CKS, int CE>
 static int launch_mbt4_t(const MbtArgs& a, hipStream_t st)
 {
     const int lds = 48 * 1160 + 8 * 56 * 32 + 8 * 48 * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mbt4_kernel<CKS, CE>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (int r = set_max_lds<&mbt4_kernel<CKS, CE>>(lds)) return r;
     hipLaunchKernelGGL((mbt4_kernel<CKS, CE>), dim3(2, CE / 48, a.B), dim3(512), lds, st, a);
     LAUNCH_CHECK();
     return 0;
@@ -1213,44 +1196,37 @@ static int launch_mbt2_t(const MbtArgs& a, hipStream_t st)
 {
     constexpr int NROWS = 12 + KSD, WW = KSD == 5 ? 32 : 30, NPF = (NROWS * WW + 15) / 16, NS = (NPF + 7) / 8, HOUT = HIMG / 2;
     const int lds = NS * 64 * 224 + 14 * 48 * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mbt2_kernel<KSD, CKS, CE, HIMG>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (int r = set_max_lds<&mbt2_kernel<KSD, CKS, CE, HIMG>>(lds)) return r;
     hipLaunchKernelGGL((mbt2_kernel<KSD, CKS, CE, HIMG>), dim3((HOUT / 7) * (HOUT / 14), CE / 48, a.B), dim3(512), lds, st, a);
     LAUNCH_CHECK();
     return 0;
 }
 
+// The instantiations of mbt_kernel, mbt2_kernel (stride 2) and mbt4_kernel (DW4: depthwise conv on 4x4x4 MFMA blocks).
+// Key: image height, depthwise kernel size, stride, Cin, Ce, DW4.
+#define MBT(KSD, CKS, CE, HIMG, CIN) {{HIMG, KSD, 1, CIN, CE, 0}, "mbt<" #KSD "," #CKS "," #CE "," #HIMG ">", launch_mbt_t<KSD, CKS, CE, HIMG>},
+#define MBT2(KSD, CKS, CE, HIMG, CIN) {{HIMG, KSD, 2, CIN, CE, 0}, "mbt2<" #KSD "," #CKS "," #CE "," #HIMG ">", launch_mbt2_t<KSD, CKS, CE, HIMG>},
+#define MBT4(CKS, CE, CIN) {{28, 5, 1, CIN, CE, 1}, "mbt4<" #CKS "," #CE ">", launch_mbt4_t<CKS, CE>},
+static const Inst<6, MbtArgs> MBT_TABLE[] = {
+    MBT(3, 1, 144, 56, 24)    // b2
+    MBT(5, 2, 240, 28, 40)    // b4
+    MBT4(2, 240, 40)          // b4
+    MBT2(5, 1, 144, 56, 24)   // b3
+    MBT2(3, 2, 240, 28, 40)   // b5
+    MBT(3, 1, 192, 56, 32)    // B4 b3-b5
+    MBT(5, 2, 336, 28, 56)    // B4 b7-b9
+    MBT4(2, 336, 56)          // B4 b7-b9
+    MBT2(5, 1, 192, 56, 32)   // B4 b6
+    MBT2(3, 2, 336, 28, 56)   // B4 b10
+};
+#undef MBT4
+#undef MBT2
+#undef MBT
+
+const char* mbt_label(int H, int ks, int stride, int Cin, int Ce, int dw4) { return inst_label(MBT_TABLE, {H, ks, stride, Cin, Ce, dw4}); }
+
 int launch_mbt(const MbtArgs& a, hipStream_t st)
 {
     if (a.B < 1) return -16;
-    if (a.stride == 2) {
-        if (a.H == 56 && a.ks == 5 && a.Cin == 24 && a.Ce == 144) return launch_mbt2_t<5, 1, 144, 56>(a, st);   // b3
-        if (a.H == 28 && a.ks == 3 && a.Cin == 40 && a.Ce == 240) return launch_mbt2_t<3, 2, 240, 28>(a, st);   // b5
-        if (a.H == 56 && a.ks == 5 && a.Cin == 32 && a.Ce == 192) return launch_mbt2_t<5, 1, 192, 56>(a, st);   // B4 b6
-        if (a.H == 28 && a.ks == 3 && a.Cin == 56 && a.Ce == 336) return launch_mbt2_t<3, 2, 336, 28>(a, st);   // B4 b10
-        return -5;
-    }
-    if (a.H == 56 && a.ks == 3 && a.Cin == 24 && a.Ce == 144) return launch_mbt_t<3, 1, 144, 56>(a, st);   // b2
-    if (a.dwtoe && a.H == 28 && a.ks == 5 && a.Cin == 40 && a.Ce == 240) return launch_mbt4_t<2, 240>(a, st);   // b4, depthwise on 4x4x4 MFMA blocks
-    if (a.dwtoe && a.H == 28 && a.ks == 5 && a.Cin == 56 && a.Ce == 336) return launch_mbt4_t<2, 336>(a, st);   // B4 b7-b9
-    if (a.H == 28 && a.ks == 5 && a.Cin == 40 && a.Ce == 240) return launch_mbt_t<5, 2, 240, 28>(a, st);   // b4
-    if (a.H == 56 && a.ks == 3 && a.Cin == 32 && a.Ce == 192) return launch_mbt_t<3, 1, 192, 56>(a, st);   // B4 b3-b5
-    if (a.H == 28 && a.ks == 5 && a.Cin == 56 && a.Ce == 336) return launch_mbt_t<5, 2, 336, 28>(a, st);   // B4 b7-b9
-    return -5;
+    return inst_launch(MBT_TABLE, {a.H, a.ks, a.stride, a.Cin, a.Ce, a.dwtoe ? 1 : 0}, a, st, -5);
 }
-
-// the layer shapes launch_mbt has an instantiation for
-int mbt_has(int H, int ks, int stride, int Cin, int Ce)
-{
-    static const int T[][5] = {{56, 3, 1, 24, 144}, {28, 5, 1, 40, 240}, {56, 5, 2, 24, 144}, {28, 3, 2, 40, 240},
-                               {56, 3, 1, 32, 192}, {28, 5, 1, 56, 336}, {56, 5, 2, 32, 192}, {28, 3, 2, 56, 336}};
-    for (auto& t : T)
-        if (t[0] == H && t[1] == ks && t[2] == stride && t[3] == Cin && t[4] == Ce) return 1;
-    return 0;
-}
-

@@ -546,101 +546,6 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const _Float16* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Squeeze-excite gate in two launches:
-//   pooled[c] = inv_hw * sum_p pool_part[b][p][c]
-//   r[j]      = silu(b_r[j] + sum_c W_r[j][c] pooled[c])        j < Cs   (wave-reduced dot products)
-//   gate[c]   = sigmoid(b_e[c] + sum_j W_e[c][j] r[j])      (W_e stored transposed, [Cs][C])
-// ---------------------------------------------------------------------------------------------
-// Both squeeze-excite FCs are batch GEMMs over the patches, run on the exact-f32 MFMA
-// (v_mfma_f32_16x16x4_f32) so that a weight row is fetched once per 16 patches, not once per patch.
-//   XMODE 1: X[row][k] = sum_{p<nslab} Xs[(row*nslab + p)*K + k]        (pool partial sums of a patch)
-//   XMODE 2: X[row][k] = silu(xbias[k] + sum_{z<nslab} Xs[(z*M + row)*K + k])   (split-K partials of FC1)
-//   ACT 0: Y slab z = partial products over this z's K range (no bias)   ACT 2: sigmoid(acc + bias)
-// Lane (i=l&15, q=l>>4) feeds 4 consecutive k per 16-k group (one per MFMA step); outputs land as
-// lane (i,q) -> columns n0 + 16t + 4q + j of row i (operands swapped, as in the other GEMMs).
-template <int XMODE, int ACT>
-__global__ __launch_bounds__(256) void se_gemm_f32_kernel(const float* __restrict__ Xs, int nslab, int M, int K,
-                                                          const float* __restrict__ xbias,
-                                                          const float* __restrict__ W,   // [N][K]
-                                                          const float* __restrict__ bias, float* __restrict__ Y,
-                                                          int N, int kz)
-{
-    constexpr int NT = 4;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 15, q = lane >> 4;
-    const int row = (blockIdx.x * 4 + wave) * 16 + i;
-    const bool rok = row < M;
-    const int n0 = blockIdx.y * 16 * NT;
-    const int kbeg = blockIdx.z * kz;
-    const int kend = (kbeg + kz) < K ? (kbeg + kz) : K;
-    f4 acc[NT][2];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t][0] = acc[t][1] = (f4){0.f, 0.f, 0.f, 0.f};
-    // U k-groups per batch: every load of a batch is issued before its MFMAs (these GEMMs are pure
-    // latency chains: tiny, with all operands a fresh L2/HBM round trip away)
-    constexpr int U = 3;
-    for (int k0 = kbeg; k0 < kend; k0 += 16 * U) {
-        f4 xv[U], wv[U][NT];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = k0 + 16 * u + 4 * q;
-            const bool kok = k < kend;
-            f4 x = {0.f, 0.f, 0.f, 0.f};
-            if (rok && kok) {
-                if (XMODE == 1) {
-                    const float* xp = Xs + (size_t)row * nslab * K + k;
-                    f4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s0, s3 = s0;
-                    int p = 0;
-                    for (; p + 3 < nslab; p += 4) {
-                        s0 += *reinterpret_cast<const f4*>(xp + (size_t)p * K);
-                        s1 += *reinterpret_cast<const f4*>(xp + (size_t)(p + 1) * K);
-                        s2 += *reinterpret_cast<const f4*>(xp + (size_t)(p + 2) * K);
-                        s3 += *reinterpret_cast<const f4*>(xp + (size_t)(p + 3) * K);
-                    }
-                    for (; p < nslab; ++p) s0 += *reinterpret_cast<const f4*>(xp + (size_t)p * K);
-                    x = (s0 + s1) + (s2 + s3);
-                } else {
-                    f4 sum = *reinterpret_cast<const f4*>(xbias + k);
-#pragma unroll 8
-                    for (int z = 0; z < nslab; ++z)
-                        sum += *reinterpret_cast<const f4*>(Xs + ((size_t)z * M + row) * K + k);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) x[j] = silu_f(sum[j]);
-                }
-            }
-            xv[u] = x;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int n = n0 + t * 16 + i;
-                f4 w = {0.f, 0.f, 0.f, 0.f};
-                if (n < N && kok) w = *reinterpret_cast<const f4*>(W + (size_t)n * K + k);
-                wv[u][t] = w;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    acc[t][s & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u][t][s], xv[u][s], acc[t][s & 1], 0, 0, 0);
-    }
-    if (!rok) return;
-    float* yo = Y + (ACT == 0 ? (size_t)blockIdx.z * M * N : 0);
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + t * 16 + 4 * q + j;
-            if (n < N) {
-                float v = acc[t][0][j] + acc[t][1][j];
-                if (ACT == 2) v = sigmoid_f(v + bias[n]);
-                yo[(size_t)row * N + n] = v;
-            }
-        }
-}
-
-// ---------------------------------------------------------------------------------------------
 // Squeeze-excite in ONE launch: both FCs for 16 patches per workgroup of 16 waves.  The two tiny
 // GEMMs are pure latency chains, so the workgroup is wide instead of deep:
 //   FC1  r[16][Cs4] = silu(br + P[16][C] . Wr^T): the 16 waves split K (each sums its pool-partial slabs on
@@ -1092,74 +997,51 @@ int launch_stem(const uint8_t* patches, const _Float16* w, const float* bias, co
     return 0;
 }
 
-template <int MT, int NT, int UK, bool DG>
-static int launch_gemm_uk(const GemmArgs& a, hipStream_t st)
+template <int MT, int NT, int EPI, bool GATE, bool RES, bool DG>
+static int launch_gemm_t(const GemmArgs& a, hipStream_t st)
 {
-    const int rows_per_wg = 64 * MT;
-    dim3 grid((a.M + rows_per_wg - 1) / rows_per_wg, a.n_chunks, 1);
-    dim3 block(256);
-#define GEMM_GO(EPI, GATE, RES)                                                                                    \
-    hipLaunchKernelGGL((pw_gemm_kernel<MT, NT, EPI, GATE, RES, UK, DG>), grid, block, 0, st, a.X, a.M, a.K, a.Wp, a.Kp / 32,   \
-                       a.bias, a.Y, a.N, a.gate, a.HW, a.res, a.gap_out, a.inv_hw)
-    if (a.epi == EPI_SILU) GEMM_GO(EPI_SILU, false, false);
-    else if (a.epi == EPI_LINEAR) {
-        if (a.gate && a.res) GEMM_GO(EPI_LINEAR, true, true);
-        else if (a.gate) GEMM_GO(EPI_LINEAR, true, false);
-        else if (a.res) GEMM_GO(EPI_LINEAR, false, true);
-        else GEMM_GO(EPI_LINEAR, false, false);
-    } else return -1;
-#undef GEMM_GO
+    constexpr int UK = MT * NT <= 4 ? 4 : 2;   // k-steps per LDS batch, bounded by registers
+    static_assert(!DG || (GATE && MT == 1 && UK == 4), "the deferred gate exists for gated one-fragment forms only");
+    // EPI_GAP: one workgroup per patch (its HW <= 64 rows) and chunk
+    const dim3 grid(EPI == EPI_GAP ? a.M / a.HW : (a.M + 64 * MT - 1) / (64 * MT), a.n_chunks, 1);
+    hipLaunchKernelGGL((pw_gemm_kernel<MT, NT, EPI, GATE, RES, UK, DG>), grid, dim3(256), 0, st, a.X, a.M, a.K, a.Wp, a.Kp / 32,
+                       a.bias, a.Y, a.N, a.gate, a.HW, a.res, a.gap_out, a.inv_hw);
     LAUNCH_CHECK();
     return 0;
 }
 
-template <int MT, int NT>
-static int launch_gemm_nt(const GemmArgs& a, hipStream_t st)
-{
-    // k-steps per LDS batch (UK) is bounded by registers; 7x7 project layers use the deferred-gate variant
-    if (MT * NT <= 4) {
-        if (MT == 1 && a.defer_gate) return launch_gemm_uk<MT, (MT * NT <= 4 ? NT : 1), 4, (MT == 1)>(a, st);
-        return launch_gemm_uk<MT, (MT * NT <= 4 ? NT : 1), 4, false>(a, st);
-    }
-    return launch_gemm_uk<MT, NT, 2, false>(a, st);
-}
+// pw_gemm_kernel's instantiations.  Key: MT, NT, EPI, GATE, RES, DG (deferred gate: 7x7 project layers).  The chunk widths
+// are what pick_nt (mmc_api.cpp) gives the layers of B0 and B4: an expand conv (SiLU, never gated) has 3, 5, 6, 7 or 8
+// fragments per chunk, a project conv (linear, always gated, with or without skip) 1 to 4, the head (GAP) is packed with 4.
+static_assert(EPI_SILU == 0 && EPI_LINEAR == 1 && EPI_GAP == 2, "the labels below spell the epilogues as numbers");
+#define G(MT, NT, EPI, GATE, RES, DG) \
+    {{MT, NT, EPI, GATE, RES, DG}, "pw_gemm<" #MT "," #NT "," #EPI "," #GATE "," #RES ">", launch_gemm_t<MT, NT, EPI, GATE != 0, RES != 0, DG != 0>},
+#define EXPAND(NT) G(1, NT, 0, 0, 0, 0) G(2, NT, 0, 0, 0, 0)
+#define PROJECT(NT, RES) G(1, NT, 1, 1, RES, 0) G(1, NT, 1, 1, RES, 1) G(2, NT, 1, 1, RES, 0)
+static const Inst<6, GemmArgs> PW_GEMM_TABLE[] = {
+    EXPAND(3) EXPAND(5) EXPAND(6) EXPAND(7) EXPAND(8)
+    PROJECT(1, 0) PROJECT(2, 0) PROJECT(3, 0) PROJECT(4, 0)
+    PROJECT(1, 1) PROJECT(2, 1) PROJECT(3, 1) PROJECT(4, 1)
+    G(1, 4, 2, 0, 0, 0)
+};
+#undef PROJECT
+#undef EXPAND
+#undef G
 
-template <int NT>
-static int launch_gap_nt(const GemmArgs& a, hipStream_t st)
+// the gate is deferred where the form allows it: one row fragment per wave, four k-steps per LDS batch
+static int gemm_dg(int mt, int nt, bool gate, int defer_gate) { return (defer_gate && gate && mt == 1 && nt <= 4) ? 1 : 0; }
+
+const char* pw_gemm_label(int mt, int nt, int epi, int gate, int res, int defer_gate)
 {
-    dim3 grid(a.M / a.HW, a.n_chunks, 1);
-    hipLaunchKernelGGL((pw_gemm_kernel<1, NT, EPI_GAP, false, false, (NT <= 4 ? 4 : 2), false>), grid, dim3(256), 0, st, a.X, a.M, a.K, a.Wp,
-                       a.Kp / 32, a.bias, a.Y, a.N, a.gate, a.HW, a.res, a.gap_out, a.inv_hw);
-    LAUNCH_CHECK();
-    return 0;
+    if (epi == EPI_GAP) mt = 1;   // one form, whatever the batch
+    return inst_label(PW_GEMM_TABLE, {mt, nt, epi, gate, res, gemm_dg(mt, nt, gate != 0, defer_gate)});
 }
 
 int launch_pw_gemm(const GemmArgs& a, hipStream_t st)
 {
-    if (a.epi == EPI_GAP) {
-        if (a.HW > 64) return -2;
-        switch (a.nt) {
-            case 4: return launch_gap_nt<4>(a, st);
-            case 5: return launch_gap_nt<5>(a, st);
-            case 8: return launch_gap_nt<8>(a, st);
-            default: return -3;
-        }
-    }
-#define CASE_NT(n)                                              \
-    case n:                                                     \
-        return a.mt == 2 ? launch_gemm_nt<2, n>(a, st) : launch_gemm_nt<1, n>(a, st);
-    switch (a.nt) {
-        CASE_NT(1)
-        CASE_NT(2)
-        CASE_NT(3)
-        CASE_NT(4)
-        CASE_NT(5)
-        CASE_NT(6)
-        CASE_NT(7)
-        CASE_NT(8)
-        default: return -3;
-    }
-#undef CASE_NT
+    if (a.epi == EPI_GAP && a.HW > 64) return -2;
+    const int mt = (a.mt == 2 && a.epi != EPI_GAP) ? 2 : 1;
+    return inst_launch(PW_GEMM_TABLE, {mt, a.nt, a.epi, a.gate ? 1 : 0, a.res ? 1 : 0, gemm_dg(mt, a.nt, a.gate, a.defer_gate)}, a, st, -3);
 }
 
 int launch_pw_gemm_fp8(const Fp8GemmArgs& a, hipStream_t st)
@@ -1186,25 +1068,17 @@ static int launch_dw_t(const DwArgs& a, hipStream_t st)
     return 0;
 }
 
-int launch_dwconv(const DwArgs& a, hipStream_t st)
-{
-#define DW_CASE(KS, ST, TW) \
-    if (a.ks == KS && a.stride == ST && a.tw == TW) return launch_dw_t<KS, ST, TW>(a, st);
-    DW_CASE(3, 1, 4)
-    DW_CASE(3, 1, 2)
-    DW_CASE(3, 1, 7)
-    DW_CASE(3, 2, 4)
-    DW_CASE(3, 2, 2)
-    DW_CASE(3, 2, 7)
-    DW_CASE(5, 1, 4)
-    DW_CASE(5, 1, 2)
-    DW_CASE(5, 1, 7)
-    DW_CASE(5, 2, 4)
-    DW_CASE(5, 2, 2)
-    DW_CASE(5, 2, 7)
-#undef DW_CASE
-    return -4;
-}
+// dwconv_kernel's instantiations.  Key: kernel size, stride, outputs per thread along x (4 where Ho divides by 4, 7 at 7x7,
+// else 2: no stride-2 3x3 layer lands on 7x7 and no stride-2 5x5 layer on 14x14)
+#define DW(KS, ST, TW) {{KS, ST, TW}, "dwconv<" #KS "," #ST "," #TW ">", launch_dw_t<KS, ST, TW>},
+static const Inst<3, DwArgs> DWCONV_TABLE[] = {
+    DW(3, 1, 4) DW(3, 1, 2) DW(3, 1, 7) DW(3, 2, 4) DW(3, 2, 2)
+    DW(5, 1, 4) DW(5, 1, 2) DW(5, 1, 7) DW(5, 2, 4) DW(5, 2, 7)
+};
+#undef DW
+
+const char* dwconv_label(int ks, int stride, int tw) { return inst_label(DWCONV_TABLE, {ks, stride, tw}); }
+int launch_dwconv(const DwArgs& a, hipStream_t st) { return inst_launch(DWCONV_TABLE, {a.ks, a.stride, a.tw}, a, st, -4); }
 
 int launch_se_small(const float* pool_part, int nparts, int B, int C, int Cs, const float* wr, const float* br,
                     const float* we, const float* be, float* gate, hipStream_t st)

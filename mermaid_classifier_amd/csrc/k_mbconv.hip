@@ -550,13 +550,8 @@ template <int KS, int ST, int TW, int KSTEPS, int NPAIR, int CC, int TWO, int PB
 static int launch_mbconv_t(const MbArgs& a, hipStream_t st)
 {
     dim3 grid(a.tiles_x * a.tiles_y, a.Ce / a.CC, (a.B + PB - 1) / PB);
-    static bool attr_done = false;
-    if (!attr_done && a.lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mbconv_a_kernel<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (a.lds_bytes > 64 * 1024)
+        if (int r = set_max_lds<&mbconv_a_kernel<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB, false>>(160 * 1024)) return r;
     hipLaunchKernelGGL((mbconv_a_kernel<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB, false>), grid, dim3(256), a.lds_bytes, st, a.X, a.Wexp,
                        a.bexp, a.Wdw, a.bdw, a.out, a.pool_part, a.H, a.W, a.Cin, a.Ce, a.Ho, a.Wo, a.pad, a.TH, a.tiles_x, a.wl_off,
                        a.red_off, a.B, a.Wfrag, a.wfr_off);
@@ -564,12 +559,60 @@ static int launch_mbconv_t(const MbArgs& a, hipStream_t st)
     return 0;
 }
 
+// mbconv_a_kernel's instantiations.  Key: depthwise kernel size, stride, outputs per thread along x, k-steps of the expand,
+// fragment pairs per wave, channel chunk, output tile width, patches per workgroup.  (The label leaves out the tile width and ends
+// in a constant 0: the reports under profiles/ and the tools key on that text.)
+#define MB(KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB)                                                                   \
+    {{KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB}, "mbconv_a<" #KS "," #ST "," #TW "," #KSTEPS "," #NPAIR "," #CC "," #PB ",0>", \
+     launch_mbconv_t<KS, ST, TW, KSTEPS, NPAIR, CC, TWO, PB>},
+static const Inst<8, MbArgs> MBCONV_A_TABLE[] = {
+    MB(3, 2, 2, 1, 3, 48, 8, 1)     // b1
+    MB(3, 1, 2, 1, 2, 48, 14, 1)    // b2
+    MB(5, 2, 2, 1, 3, 48, 14, 1)    // b3
+    MB(5, 1, 2, 2, 3, 48, 14, 1)    // b4
+    MB(3, 1, 2, 3, 2, 96, 14, 1)    // b6, b7
+    MB(5, 1, 1, 6, 1, 96, 7, 2)     // b12-b14
+    MB(5, 1, 2, 3, 2, 48, 14, 1)    // b8
+    MB(5, 1, 2, 4, 2, 48, 14, 1)    // b9, b10
+    MB(5, 2, 1, 4, 2, 48, 7, 1)     // b11
+    MB(3, 1, 1, 6, 1, 96, 7, 2)     // b15
+    MB(3, 2, 2, 2, 4, 80, 14, 1)    // b5 with a 7x14 output tile: less halo, full depthwise passes (28.4 vs 32.8 us)
+    // EfficientNet-B4 (generic_fuse_cfg): blocks 2-9 and 16 reuse the instantiations above
+    MB(3, 2, 2, 2, 2, 48, 14, 1)    // B4 b10
+    MB(3, 1, 2, 4, 2, 96, 14, 1)    // B4 b11-b15
+    MB(5, 1, 2, 4, 2, 96, 14, 1)    // B4 b16
+    MB(5, 1, 2, 5, 2, 96, 14, 1)    // B4 b17-b21
+    MB(5, 2, 1, 5, 2, 48, 7, 1)     // B4 b22
+    MB(5, 1, 1, 9, 1, 96, 7, 2)     // B4 b23-b29
+    MB(3, 1, 1, 9, 1, 96, 7, 2)     // B4 b30
+    MB(3, 1, 1, 14, 1, 96, 7, 2)    // B4 b31
+};
+#undef MB
+
+// a workgroup that holds several patches (PB > 1) holds whole ones: one tile per patch
+static bool mbconv_tiles_ok(const MbArgs& a) { return a.pb <= 1 || (a.tiles_x * a.tiles_y == 1 && a.TH == a.Ho && a.TWo == a.Wo); }
+
+const char* mbconv_a_label(const MbArgs& a)
+{
+    return mbconv_tiles_ok(a) ? inst_label(MBCONV_A_TABLE, {a.ks, a.stride, a.tw, a.ksteps, a.npair, a.CC, a.TWo, a.pb}) : nullptr;
+}
+int launch_mbconv_a(const MbArgs& a, hipStream_t st)
+{
+    if (!mbconv_tiles_ok(a)) return -8;
+    return inst_launch(MBCONV_A_TABLE, {a.ks, a.stride, a.tw, a.ksteps, a.npair, a.CC, a.TWo, a.pb}, a, st, -5);
+}
+
+// block 1 with block 0's squeeze-excite scale + project conv folded in (mbconv_a_kernel, PRE): the one instantiation, for
+// block 1's geometry read from block 0's 32-channel depthwise output
+const char* mbconv_pre_label(const MbArgs& a)
+{
+    const bool ok = a.ks == 3 && a.stride == 2 && a.tw == 2 && a.ksteps == 1 && a.npair == 3 && a.CC == 48 && a.TWo == 8 && a.pb == 1;
+    return ok ? "mbconv_a_pre" : nullptr;
+}
+
 int launch_mbconv_pre(const MbArgs& a, const _Float16* pre_w, const float* pre_b, const float* pre_gate, hipStream_t st)
 {
-    // block 1 with block 0's squeeze-excite scale + project conv folded in (mbconv_a_kernel, PRE)
-    if (!(a.ks == 3 && a.stride == 2 && a.tw == 2 && a.ksteps == 1 && a.npair == 3 && a.CC == 48 && a.TWo == 8 && a.pb == 1 &&
-          a.Cin == 32))
-        return -13;
+    if (!mbconv_pre_label(a) || a.Cin != 32) return -13;
     dim3 grid(a.tiles_x * a.tiles_y, a.Ce / a.CC, a.B);
     hipLaunchKernelGGL((mbconv_a_kernel<3, 2, 2, 1, 3, 48, 8, 1, false, true>), grid, dim3(256), a.lds_bytes, st, a.X, a.Wexp,
                        a.bexp, a.Wdw, a.bdw, a.out, a.pool_part, a.H, a.W, a.Cin, a.Ce, a.Ho, a.Wo, a.pad, a.TH, a.tiles_x,
@@ -578,48 +621,12 @@ int launch_mbconv_pre(const MbArgs& a, const _Float16* pre_w, const float* pre_b
     return 0;
 }
 
-int launch_mbconv_a(const MbArgs& a, hipStream_t st)
-{
-    if (a.pb > 1 && (a.tiles_x * a.tiles_y != 1 || a.TH != a.Ho || a.TWo != a.Wo)) return -8;
-#define MB_CASE(KS_, ST_, TW_, KSTEPS_, NPAIR_, CC_, TWO_, PB_)                                              \
-    if (a.ks == KS_ && a.stride == ST_ && a.tw == TW_ && a.ksteps == KSTEPS_ && a.npair == NPAIR_ &&         \
-        a.CC == CC_ && a.TWo == TWO_ && a.pb == PB_)                                                         \
-        return launch_mbconv_t<KS_, ST_, TW_, KSTEPS_, NPAIR_, CC_, TWO_, PB_>(a, st);
-    MB_CASE(3, 2, 2, 1, 3, 48, 8, 1)     // b1
-    MB_CASE(3, 1, 2, 1, 2, 48, 14, 1)    // b2
-    MB_CASE(5, 2, 2, 1, 3, 48, 14, 1)    // b3
-    MB_CASE(5, 1, 2, 2, 3, 48, 14, 1)    // b4
-    MB_CASE(3, 1, 2, 3, 2, 96, 14, 1)    // b6, b7
-    MB_CASE(5, 1, 1, 6, 1, 96, 7, 2)     // b12-b14
-    MB_CASE(5, 1, 2, 3, 2, 48, 14, 1)    // b8
-    MB_CASE(5, 1, 2, 4, 2, 48, 14, 1)    // b9, b10
-    MB_CASE(5, 2, 1, 4, 2, 48, 7, 1)     // b11
-    MB_CASE(3, 1, 1, 6, 1, 96, 7, 2)     // b15
-    MB_CASE(3, 2, 2, 2, 4, 80, 14, 1)    // b5 with a 7x14 output tile: less halo, full depthwise passes (28.4 vs 32.8 us)
-    // EfficientNet-B4 (generic_fuse_cfg): blocks 2-9 and 16 reuse the instantiations above
-    MB_CASE(3, 2, 2, 2, 2, 48, 14, 1)    // B4 b10
-    MB_CASE(3, 1, 2, 4, 2, 96, 14, 1)    // B4 b11-b15
-    MB_CASE(5, 1, 2, 4, 2, 96, 14, 1)    // B4 b16
-    MB_CASE(5, 1, 2, 5, 2, 96, 14, 1)    // B4 b17-b21
-    MB_CASE(5, 2, 1, 5, 2, 48, 7, 1)     // B4 b22
-    MB_CASE(5, 1, 1, 9, 1, 96, 7, 2)     // B4 b23-b29
-    MB_CASE(3, 1, 1, 9, 1, 96, 7, 2)     // B4 b30
-    MB_CASE(3, 1, 1, 14, 1, 96, 7, 2)    // B4 b31
-#undef MB_CASE
-    return -5;
-}
-
 template <int KS, int ST, int KSTEPS, int NPAIR, int CC, int TWO, int PB>
 static int launch_mbconv_d_t(const MbArgs& a, hipStream_t st)
 {
     dim3 grid(a.tiles_x * a.tiles_y, a.Ce / a.CC, (a.B + PB - 1) / PB);
-    static bool attr_done = false;
-    if (!attr_done && a.lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mbconv_d_kernel<KS, ST, KSTEPS, NPAIR, CC, TWO, PB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (a.lds_bytes > 64 * 1024)
+        if (int r = set_max_lds<&mbconv_d_kernel<KS, ST, KSTEPS, NPAIR, CC, TWO, PB>>(160 * 1024)) return r;
     hipLaunchKernelGGL((mbconv_d_kernel<KS, ST, KSTEPS, NPAIR, CC, TWO, PB>), grid, dim3(256), a.lds_bytes, st, a.X, a.Wexp,
                        a.bexp, a.Wdw, a.bdw, a.out, a.pool_part, a.H, a.W, a.Cin, a.Ce, a.Ho, a.Wo, a.TH, a.tiles_x,
                        a.wl_off, a.red_off, a.B);
@@ -627,18 +634,23 @@ static int launch_mbconv_d_t(const MbArgs& a, hipStream_t st)
     return 0;
 }
 
+// mbconv_d_kernel's instantiations.  Key (and label): the template arguments, mbconv_a's without the outputs per thread.
+#define MD(KS, ST, KSTEPS, NPAIR, CC, TWO, PB)                                                                           \
+    {{KS, ST, KSTEPS, NPAIR, CC, TWO, PB}, "mbconv_d<" #KS "," #ST "," #KSTEPS "," #NPAIR "," #CC "," #TWO "," #PB ">", \
+     launch_mbconv_d_t<KS, ST, KSTEPS, NPAIR, CC, TWO, PB>},
+static const Inst<7, MbArgs> MBCONV_D_TABLE[] = {
+    MD(5, 1, 2, 3, 48, 14, 1)    // b4
+    MD(5, 1, 4, 2, 48, 14, 1)    // b9, b10
+    MD(5, 1, 6, 1, 96, 7, 2)     // b12-b14
+};
+#undef MD
+
+const char* mbconv_d_label(const MbArgs& a)
+{
+    return mbconv_tiles_ok(a) ? inst_label(MBCONV_D_TABLE, {a.ks, a.stride, a.ksteps, a.npair, a.CC, a.TWo, a.pb}) : nullptr;
+}
 int launch_mbconv_d(const MbArgs& a, hipStream_t st)
 {
-    if (a.pb > 1 && (a.tiles_x * a.tiles_y != 1 || a.TH != a.Ho || a.TWo != a.Wo)) return -8;
-#define MD_CASE(KS_, ST_, KSTEPS_, NPAIR_, CC_, TWO_, PB_)                                                   \
-    if (a.ks == KS_ && a.stride == ST_ && a.ksteps == KSTEPS_ && a.npair == NPAIR_ && a.CC == CC_ &&         \
-        a.TWo == TWO_ && a.pb == PB_)                                                                        \
-        return launch_mbconv_d_t<KS_, ST_, KSTEPS_, NPAIR_, CC_, TWO_, PB_>(a, st);
-    MD_CASE(5, 1, 2, 3, 48, 14, 1)    // b4
-    MD_CASE(5, 1, 4, 2, 48, 14, 1)    // b9, b10
-    MD_CASE(5, 1, 6, 1, 96, 7, 2)     // b12-b14
-#undef MD_CASE
-    return -5;
+    if (!mbconv_tiles_ok(a)) return -8;
+    return inst_launch(MBCONV_D_TABLE, {a.ks, a.stride, a.ksteps, a.npair, a.CC, a.TWo, a.pb}, a, st, -5);
 }
-
-

@@ -849,47 +849,36 @@ template <int KS, int NF, int HW, bool RES>
 static int launch_proj_patch_t(const ProjPatchArgs& a, hipStream_t st)
 {
     const int lds = NF * KS * 1024 + 2 * 32 * KS * 4 + 128;   // project weights, pooled + gate vectors, squeeze activations
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&proj_patch_kernel<KS, NF, HW, RES>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (int r = set_max_lds<&proj_patch_kernel<KS, NF, HW, RES>>(lds)) return r;
     hipLaunchKernelGGL((proj_patch_kernel<KS, NF, HW, RES>), dim3(a.B), dim3(512), lds, st, a);
     LAUNCH_CHECK();
     return 0;
 }
 
+// proj_patch_kernel's instantiations.  Key: k-steps of the weight image (proj_patch_ksteps), output fragments, pixels per patch,
+// skip connection.
+#define PP(KS, NF, HW, RES) {{KS, NF, HW, RES}, "proj_patch<" #KS "," #NF "," #HW "," #RES ">", launch_proj_patch_t<KS, NF, HW, RES != 0>},
+static const Inst<4, ProjPatchArgs> PROJ_PATCH_TABLE[] = {
+    PP(5, 3, 784, 0)     // b3: 144 -> 40 @ 28x28
+    PP(8, 3, 784, 1)     // b4: 240 -> 40
+    PP(8, 5, 196, 0)     // b5: 240 -> 80 @ 14x14
+    PP(15, 5, 196, 1)    // b6, b7: 480 -> 80
+    PP(15, 7, 196, 0)    // b8: 480 -> 112
+    PP(21, 7, 196, 1)    // b9, b10: 672 -> 112 (and B4 b11-b15)
+    PP(6, 4, 784, 0)     // B4 b6: 192 -> 56 @ 28x28
+    PP(12, 4, 784, 1)    // B4 b7-b9: 336 -> 56 (10.5 k-steps, padded to 12 = two chunks of 6)
+    PP(12, 7, 196, 0)    // B4 b10: 336 -> 112 @ 14x14
+};
+#undef PP
+
+// (the schedule asks before packing a layer for it)
+const char* proj_patch_label(int K, int N, int HW, int res) { return inst_label(PROJ_PATCH_TABLE, {proj_patch_ksteps(K), (N + 15) / 16, HW, res}); }
+
 int launch_proj_patch(const ProjPatchArgs& a, hipStream_t st)
 {
     // CSP <= 28: FC1's output groups are waves 0 .. CSP / 4 - 1 and wave 7 (the DMA path) must not be one of them
     if (a.B < 1 || a.CSP < 4 || a.CSP > 28 || (a.CSP & 3) || a.nparts < 1) return -11;
-    const int ks = proj_patch_ksteps(a.K), nf = (a.N + 15) / 16;
-#define PP_CASE(KS_, NF_, HW_, RES_) \
-    if (ks == KS_ && nf == NF_ && a.HW == HW_ && (a.res != nullptr) == RES_) return launch_proj_patch_t<KS_, NF_, HW_, RES_>(a, st);
-    PP_CASE(5, 3, 784, false)    // b3: 144 -> 40 @ 28x28
-    PP_CASE(8, 3, 784, true)     // b4: 240 -> 40
-    PP_CASE(8, 5, 196, false)    // b5: 240 -> 80 @ 14x14
-    PP_CASE(15, 5, 196, true)    // b6, b7: 480 -> 80
-    PP_CASE(15, 7, 196, false)   // b8: 480 -> 112
-    PP_CASE(21, 7, 196, true)    // b9, b10: 672 -> 112 (and B4 b11-b15)
-    PP_CASE(6, 4, 784, false)    // B4 b6: 192 -> 56 @ 28x28
-    PP_CASE(12, 4, 784, true)    // B4 b7-b9: 336 -> 56 (10.5 k-steps, padded to 12 = two chunks of 6)
-    PP_CASE(12, 7, 196, false)   // B4 b10: 336 -> 112 @ 14x14
-#undef PP_CASE
-    return -5;
-}
-
-// the shapes launch_proj_patch has an instantiation for (the schedule asks before packing a layer for it)
-int proj_patch_has(int K, int N, int HW, int res)
-{
-    const int ks = proj_patch_ksteps(K), nf = (N + 15) / 16;
-    static const int T[][4] = {{5, 3, 784, 0}, {8, 3, 784, 1}, {8, 5, 196, 0}, {15, 5, 196, 1}, {15, 7, 196, 0}, {21, 7, 196, 1},
-                               {6, 4, 784, 0}, {12, 4, 784, 1}, {12, 7, 196, 0}};
-    for (auto& t : T)
-        if (t[0] == ks && t[1] == nf && t[2] == HW && t[3] == (res ? 1 : 0)) return 1;
-    return 0;
+    return inst_launch(PROJ_PATCH_TABLE, {proj_patch_ksteps(a.K), (a.N + 15) / 16, a.HW, a.res ? 1 : 0}, a, st, -5);
 }
 
 template <int CKS, int KSD, int CE>
@@ -899,13 +888,7 @@ static int launch_mid14_t(const Mid14Args& a, hipStream_t st)
     // words of the expand's masked stores
     constexpr int ZROWS = 2 * (KSD / 2) + 1;
     const int lds = (98 + 7 * ZROWS) * 416 + 5 * 96 * 4 + 512;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mid14_kernel<CKS, KSD, CE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (int r = set_max_lds<&mid14_kernel<CKS, KSD, CE>>(lds)) return r;
     hipLaunchKernelGGL((mid14_kernel<CKS, KSD, CE>), dim3(a.B, a.nsplit < 1 ? 1 : a.nsplit), dim3(512), lds, st, a);
     LAUNCH_CHECK();
     return 0;
@@ -915,31 +898,29 @@ template <int CKS, int KSD, int CE>
 static int launch_mid14m_t(const Mid14Args& a, hipStream_t st)
 {
     const int lds = 196 * (64 * CKS + 16) + 8 * (16 * 736 + 56 * 32);   // staged block input + eight wave-private planar regions and transpose tiles
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mid14m_kernel<CKS, KSD, CE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (int r = set_max_lds<&mid14m_kernel<CKS, KSD, CE>>(lds)) return r;
     // two workgroups per patch: 16 waves share the CE / 16 channel groups (256 workgroups per 128-patch lane: one round)
     hipLaunchKernelGGL((mid14m_kernel<CKS, KSD, CE>), dim3(a.B, a.nsplit < 1 ? 1 : a.nsplit), dim3(512), lds, st, a);
     LAUNCH_CHECK();
     return 0;
 }
 
+// The instantiations of mid14_kernel and mid14m_kernel (DWM: depthwise conv on the matrix pipe).  Key: k-steps of the expand,
+// depthwise kernel size, Ce, DWM.  (The label's fourth number is the stride, 1 for every 14x14 block these kernels take.)
+#define MID14(CKS, KSD, CE) {{CKS, KSD, CE, 0}, "mid14<" #CKS "," #KSD "," #CE ",1>", launch_mid14_t<CKS, KSD, CE>},
+#define MID14M(CKS, KSD, CE) {{CKS, KSD, CE, 1}, "mid14m<" #CKS "," #KSD "," #CE ",1>", launch_mid14m_t<CKS, KSD, CE>},
+static const Inst<4, Mid14Args> MID14_TABLE[] = {
+    MID14(4, 5, 672) MID14M(4, 5, 672)   // b9, b10
+    MID14(3, 5, 480) MID14M(3, 5, 480)   // b8
+    MID14(3, 3, 480)                     // b6, b7
+};
+#undef MID14M
+#undef MID14
+
+const char* mid14_label(int Cin, int ks, int Ce, int dwm) { return inst_label(MID14_TABLE, {(Cin + 31) / 32, ks, Ce, dwm}); }
+
 int launch_mid14(const Mid14Args& a, hipStream_t st)
 {
     if (a.B < 1) return -14;
-    const int cks = (a.Cin + 31) / 32;
-    if (a.dwdiag) {   // depthwise on the matrix pipe (mid14m_kernel)
-        if (cks == 4 && a.ks == 5 && a.Ce == 672) return launch_mid14m_t<4, 5, 672>(a, st);   // b9, b10
-        if (cks == 3 && a.ks == 5 && a.Ce == 480) return launch_mid14m_t<3, 5, 480>(a, st);   // b8
-        return -5;
-    }
-    if (cks == 4 && a.ks == 5 && a.Ce == 672) return launch_mid14_t<4, 5, 672>(a, st);   // b9, b10
-    if (cks == 3 && a.ks == 5 && a.Ce == 480) return launch_mid14_t<3, 5, 480>(a, st);   // b8
-    if (cks == 3 && a.ks == 3 && a.Ce == 480) return launch_mid14_t<3, 3, 480>(a, st);   // b6, b7
-    return -5;
+    return inst_launch(MID14_TABLE, {(a.Cin + 31) / 32, a.ks, a.Ce, a.dwdiag ? 1 : 0}, a, st, -5);
 }
-

@@ -1085,12 +1085,7 @@ int launch_tail7(const TailArgs& a, hipStream_t st)
     if (a.nblk < 0 || a.nblk > 4 || a.B < 1) return -9;
     if (a.nblk == 0 && !a.pre_D && !a.pre_X && !a.head_w) return -9;
     if (a.pre_X && (!a.pre_wexp || !a.pre_bexp || !a.pre_dwp || !a.pre_bdw)) return -9;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tail7_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, T7_LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (int r = set_max_lds<&tail7_kernel>(T7_LDS)) return r;
     hipLaunchKernelGGL(tail7_kernel, dim3(a.B), dim3(512), T7_LDS, st, a);
     LAUNCH_CHECK();
     return 0;

@@ -5,6 +5,10 @@
 
 enum { EPI_SILU = 0, EPI_LINEAR = 1, EPI_GAP = 2 };
 
+// Each templated family keeps ONE table of its instantiations next to its launcher.  launch_<family>() dispatches on it and
+// <family>_label() answers from it: the label (as mmc_backbone_profile reports it) of the instantiation that would run a shape,
+// or null when there is none.  mmc_backbone_create asks for every launch it plans, so a missing shape fails there.
+
 // sets the thread-local message mmc_last_error() returns and hands back `code` (defined in mmc_api.cpp)
 int mmc_fail(int code, const char* fmt, ...);
 
@@ -152,8 +156,7 @@ struct MbtArgs {
     const _Float16* dwtoe;    // optional [Ce/16][ks][2][64][4]: Toeplitz depthwise fragments -> mbt4_kernel (5x5 stride 1 at 28x28)
 };
 int launch_mbt(const MbtArgs& a, hipStream_t st);
-int thin_proj_has(int ksteps);                          // 1 when launch_thin_proj has an instantiation for this many k-steps
-int mbt_has(int H, int ks, int stride, int Cin, int Ce);   // 1 when launch_mbt has an instantiation for this layer
+const char* mbt_label(int H, int ks, int stride, int Cin, int Ce, int dw4);   // dw4: with MbtArgs::dwtoe (mbt4_kernel)
 
 // Front half of a 14x14 MBConv block for one patch per workgroup (mid14_kernel)
 struct Mid14Args {
@@ -170,6 +173,7 @@ struct Mid14Args {
     const _Float16* dwdiag;   // optional [Ce/16][ks][2][64][4]: Toeplitz depthwise fragments of v_mfma_f32_4x4x4_16B_f16 -> mid14m_kernel
 };
 int launch_mid14(const Mid14Args& a, hipStream_t st);
+const char* mid14_label(int Cin, int ks, int Ce, int dwm);   // dwm: with Mid14Args::dwdiag (mid14m_kernel)
 
 // Squeeze-excite + project conv of one patch per workgroup (proj_patch_kernel)
 struct ProjPatchArgs {
@@ -191,9 +195,12 @@ struct ProjPatchArgs {
 int launch_proj_patch(const ProjPatchArgs& a, hipStream_t st);
 int proj_patch_ksteps(int K);                        // k-steps (of 32) its weight image must be packed with
 int proj_patch_fc1_rows(int K);                      // channel rows per output group of ProjPatchArgs::wr_g (64 x the kernel's FC1 iterations)
-int proj_patch_has(int K, int N, int HW, int res);   // 1 when launch_proj_patch has an instantiation for this layer shape
+const char* proj_patch_label(int K, int N, int HW, int res);
 
 int launch_mbconv_a(const MbArgs& a, hipStream_t st);
+const char* mbconv_a_label(const MbArgs& a);     // (these three read the geometry fields only)
+const char* mbconv_pre_label(const MbArgs& a);
+const char* mbconv_d_label(const MbArgs& a);
 // block 1 reading block 0's depthwise output, with block 0's SE scale + project conv folded in
 int launch_mbconv_pre(const MbArgs& a, const _Float16* pre_w, const float* pre_b, const float* pre_gate, hipStream_t st);
 int launch_mbconv_d(const MbArgs& a, hipStream_t st);   // dot2 depthwise variant (pair-interleaved LDS tile)
@@ -202,9 +209,12 @@ int launch_stem(const uint8_t* patches, const _Float16* w, const float* bias, co
 int launch_stem_dw(const uint8_t* patches, const _Float16* w, const float* bias, const float* padval, const float* Wdw,
                    const float* bdw, _Float16* out, float* pool_part, int B, hipStream_t st);
 int launch_pw_gemm(const GemmArgs& a, hipStream_t st);
+const char* pw_gemm_label(int mt, int nt, int epi, int gate, int res, int defer_gate);
 // SE-scale + project (+ skip) for K <= 64, N <= 32 (pack_pw weights with nt = 2): one patch's pixel fragments streamed per workgroup
 int launch_thin_proj(const GemmArgs& a, int patches, hipStream_t st);
+const char* thin_proj_label(int ksteps, int res);
 int launch_dwconv(const DwArgs& a, hipStream_t st);
+const char* dwconv_label(int ks, int stride, int tw);
 int launch_se_gate(const float* pool_part, int nparts, int B, int C, int Cs4, const float* WrP, const float* br,
                    const float* WeP, const float* be, float* gate, hipStream_t st);
 int launch_se_small(const float* pool_part, int nparts, int B, int C, int Cs, const float* wr, const float* br,

@@ -120,6 +120,7 @@ struct PwLayer {
     int N = 0, K = 0, Kp = 0, nt = 0, n_chunks = 0;
     _Float16* w = nullptr;  // device [n_chunks*16*nt][Kp]
     float* b = nullptr;     // device [n_chunks*16*nt]
+    const char* label[2] = {nullptr, nullptr};   // plan: its pw_gemm instantiation with one / two row fragments per wave (gemm_mt)
 };
 
 // A project conv with e4m3 weights for pw_gemm_fp8_kernel (MMC_PRECISION_FP8)
@@ -277,6 +278,7 @@ struct BlockW {
     bool mbt4 = false, mid14m = false;   // depthwise on 4x4x4 MFMA blocks (mbt4_kernel / mid14m_kernel)
     bool planar = false;                 // block 1: depthwise output as 32-channel planes between mb1_kernel and thin_proj_kernel
     int nparts = 0;                      // pool partials per patch left by the front half
+    const char *front_label = nullptr, *back_label = nullptr;   // the templated instantiation the front half / proj_patch runs on
     // ---- packed weights ----
     PwLayer expand, project;
     Fp8Layer p8;             // the project conv on fp8 operands (Proj::Fp8)
@@ -524,13 +526,12 @@ static int dev_upload(mmc_backbone* bb, T** p, const std::vector<T>& host)
 // fragment (chunk, kstep, t) = 1 KB at ((chunk*KS32 + kstep)*nt + t)*512 halves; inside it lane
 // (q*16 + m) holds W[channel(chunk, t, m)][kstep*32 + q*8 .. +8], with the row permutation
 // fragment row (t*16 + 4qr + jr) <- channel (chunk*16nt + qr*4nt + 4t + jr).
-static int pack_pw(mmc_backbone* bb, PwLayer* L, const float* w, const float* b, int N, int K, int force_nt,
-                   double wscale, double bscale)
+static int pack_pw(mmc_backbone* bb, PwLayer* L, const float* w, const float* b, int N, int K, int nt, double wscale, double bscale)
 {
     L->N = N;
     L->K = K;
     L->Kp = (K + 31) / 32 * 32;
-    L->nt = force_nt > 0 ? force_nt : pick_nt(N, false);
+    L->nt = nt;
     const int cw = 16 * L->nt;
     L->n_chunks = (N + cw - 1) / cw;
     const int Np = L->n_chunks * cw;
@@ -595,16 +596,29 @@ static std::vector<_Float16> pack_frag(const T* w, int N, int K, int ld, int nf,
     return wf;
 }
 
+// 7x7 layers: few workgroups, deep K -> the gated GEMM overlaps its loads with MFMAs (pw_gemm's deferred-gate forms)
+static int gemm_defer_gate(bool gate, int HW) { return (gate && HW <= 49) ? 1 : 0; }
+
+// Looks up both pw_gemm forms layer L can take, whatever max_batch is (gemm_mt picks per call); the head's GAP form has one
+static bool plan_gemm(PwLayer& L, int epi, bool gate, bool res, int HW)
+{
+    L.label[0] = pw_gemm_label(1, L.nt, epi, gate, res, gemm_defer_gate(gate, HW));
+    L.label[1] = epi == EPI_GAP ? L.label[0] : pw_gemm_label(2, L.nt, epi, gate, res, 0);
+    return L.label[0] && L.label[1] && (epi != EPI_GAP || HW <= 64);
+}
+
 // Plan block i (geometry done) under the handle's switches.  Pass-level choices (stem, b0/b1 fold, tail route) are in bb.
-static void plan_block(const mmc_backbone* bb, BlockW& B, int i)
+// Every templated launch it plans is looked up in that family's instantiation table (kernels.h) here, once: a shape
+// without an instantiation takes the fallback where there is one and fails the create call where there is none.
+static int plan_block(const mmc_backbone* bb, BlockW& B, int i)
 {
     const Options& o = bb->opt;
     const bool is_b0 = bb->arch == MMC_ARCH_B0;
     const int HWo = B.Ho * B.Ho;
     const bool tail_blk = (bb->tail == TailRoute::B11All && i >= 11) || (bb->tail != TailRoute::None && i >= 12);
     // front half
-    const bool mbt = o.fuse && o.mbt && (B.d.s == 1 || o.mbt2) && mbt_has(B.H, B.d.k, B.d.s, B.d.cin, B.ce);
-    const bool mid14 = is_b0 && o.fuse && o.projse && o.mid14 && i >= 6 && i <= 10;
+    const bool mbt = o.fuse && o.mbt && (B.d.s == 1 || o.mbt2) && mbt_label(B.H, B.d.k, B.d.s, B.d.cin, B.ce, 0);
+    const bool mid14 = is_b0 && o.fuse && o.projse && o.mid14 && i >= 6 && i <= 10 && mid14_label(B.d.cin, B.d.k, B.ce, 0);
     if (i == 0 && bb->fuse_stem) B.front = Front::StemDw;
     else if (tail_blk) B.front = Front::Tail;
     else if (B.fusable && mbt) B.front = Front::Mbt;
@@ -613,37 +627,60 @@ static void plan_block(const mmc_backbone* bb, BlockW& B, int i)
     else if (B.fusable && i == 1 && bb->fuse_b0b1) B.front = o.mb1 ? Front::Mb1 : Front::MbPre;
     else if (B.fusable) B.front = Front::MbA;
     else B.front = Front::Unfused;
-    B.mbt4 = B.front == Front::Mbt && o.mbt4 && B.d.s == 1 && B.H == 28 && B.d.k == 5 && B.ce % 16 == 0;
-    B.mid14m = B.front == Front::Mid14 && o.mid14m && i >= 8 && B.H == 14 && B.d.s == 1 && B.ce % 16 == 0;
+    B.mbt4 = B.front == Front::Mbt && o.mbt4 && B.ce % 16 == 0 && mbt_label(B.H, B.d.k, B.d.s, B.d.cin, B.ce, 1);
+    B.mid14m = B.front == Front::Mid14 && o.mid14m && i >= 8 && B.ce % 16 == 0 && mid14_label(B.d.cin, B.d.k, B.ce, 1);
     if (B.front == Front::MbD) {
         B.mb.npair = B.d_npair; B.mb.wl_off = B.d_wl_off; B.mb.red_off = B.d_red_off; B.mb.lds_bytes = B.d_lds;
     }
+    const char* family = nullptr;   // the front half's templated family, where a missing instantiation has no fallback
+    const int tiles = B.mb.tiles_x * B.mb.tiles_y;
     switch (B.front) {
     case Front::StemDw: B.nparts = 49; break;
-    case Front::Mbt: B.nparts = B.d.s == 2 ? (B.Ho / 7) * (B.Ho / 14) : (B.H / 14) * (B.H / 28); break;
-    case Front::Mid14: B.nparts = 1; break;
     case Front::Mb1: B.nparts = 14; break;
-    case Front::MbPre: case Front::MbD: case Front::MbA: B.nparts = B.mb.tiles_x * B.mb.tiles_y; break;
-    default: B.nparts = B.parts; break;
+    case Front::Tail: B.nparts = B.parts; break;
+    case Front::Mbt:
+        B.nparts = B.d.s == 2 ? (B.Ho / 7) * (B.Ho / 14) : (B.H / 14) * (B.H / 28);
+        B.front_label = mbt_label(B.H, B.d.k, B.d.s, B.d.cin, B.ce, B.mbt4);
+        break;
+    case Front::Mid14: B.nparts = 1; B.front_label = mid14_label(B.d.cin, B.d.k, B.ce, B.mid14m); break;
+    case Front::MbPre: B.nparts = tiles; family = "mbconv_a PRE"; B.front_label = mbconv_pre_label(B.mb); break;
+    case Front::MbD: B.nparts = tiles; family = "mbconv_d"; B.front_label = mbconv_d_label(B.mb); break;
+    case Front::MbA: B.nparts = tiles; family = "mbconv_a"; B.front_label = mbconv_a_label(B.mb); break;
+    case Front::Unfused:
+        B.nparts = B.parts;
+        family = "dwconv";
+        B.front_label = dwconv_label(B.d.k, B.d.s, B.tw);
+        if (B.front_label && B.has_expand && !plan_gemm(B.expand, EPI_SILU, false, false, B.H * B.H)) {
+            family = "pw_gemm (expand)";
+            B.front_label = nullptr;
+        }
+        break;
     }
+    if (family && !B.front_label)
+        return fail(MMC_ERR_ARG, "block %d: no %s instantiation for %dx%d, kernel %d, stride %d, %d -> %d channels (tile %dx%d, chunk %d)",
+                    i, family, B.H, B.H, B.d.k, B.d.s, B.d.cin, B.ce, B.mb.TH, B.mb.TWo, B.mb.CC);
     // back half
     const bool fp8_blk = bb->fp8 && B.Ho <= o.fp8_maxh;
-    const bool proj_patch = o.fuse && o.projse && B.fusable && B.has_expand && B.cs4 <= 28 &&
-                            proj_patch_has(B.ce, B.d.cout, HWo, B.skip ? 1 : 0) && (is_b0 ? i >= 3 && i <= 10 : !fp8_blk);
+    const char* pp = proj_patch_label(B.ce, B.d.cout, HWo, B.skip ? 1 : 0);
+    const bool proj_patch = o.fuse && o.projse && B.fusable && B.has_expand && B.cs4 <= 28 && pp && (is_b0 ? i >= 3 && i <= 10 : !fp8_blk);
     if (tail_blk || (i == 11 && bb->tail == TailRoute::B11)) B.back = Back::Tail;
     else if (proj_patch) B.back = Back::ProjPatch;
     else if (i == 0 && bb->fuse_b0b1) B.back = Back::SeFolded;
     else B.back = Back::SeProject;
+    B.back_label = B.back == Back::ProjPatch ? pp : nullptr;
     B.se = !is_b0 ? Se::Wide : (o.se_small && B.ce <= 256 && B.cs <= 16) ? Se::Small : Se::Fused;
     // small-K, small-N project on a big image: thin_proj_kernel (up to 5 k-steps since the gate is folded into the weight
     // fragments: B0's b2 30.8 vs 43.7 us on pw_gemm; a shape without an instantiation stays on pw_gemm)
-    const PwLayer& P = B.project;
-    const bool thin = o.thin_proj && P.nt == 2 && P.n_chunks == 1 && thin_proj_has(P.Kp / 32) && P.N <= 32 && (P.N & 7) == 0 &&
-                      (HWo & 15) == 0 && HWo >= 3136;
+    PwLayer& P = B.project;
+    const bool thin = o.thin_proj && P.nt == 2 && P.n_chunks == 1 && thin_proj_label(P.Kp / 32, B.skip ? 1 : 0) && P.N <= 32 &&
+                      (P.N & 7) == 0 && (HWo & 15) == 0 && HWo >= 3136;
     B.proj = thin ? Proj::Thin : fp8_blk ? Proj::Fp8 : Proj::Gemm;
+    if (B.back == Back::SeProject && B.proj == Proj::Gemm && !plan_gemm(P, EPI_LINEAR, true, B.skip, HWo))
+        return fail(MMC_ERR_ARG, "block %d: no pw_gemm (project) instantiation for %d -> %d channels at %dx%d", i, B.ce, B.d.cout, B.Ho, B.Ho);
     // block 1's depthwise output as three 32-channel planes between mb1_kernel and thin_proj_kernel (see mb1_kernel); per-tensor
     // mode keeps the interleaved tensor it hands out
     B.planar = B.front == Front::Mb1 && thin && o.b1_planar && !o.keep && P.K == 96;
+    return 0;
 }
 
 extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arch, int device, int max_batch, unsigned flags,
@@ -703,7 +740,8 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         B.d = AD.blocks[i];
         B.H = H;
         block_geometry(B, is_b0, i, o.fuse);
-        B.project.N = B.d.cout;   // pack_pw's layout (the thin_proj choice reads it)
+        B.expand.nt = pick_nt(B.ce, false);   // pack_pw's layouts (the plan reads them)
+        B.project.N = B.d.cout;
         B.project.K = B.ce;
         B.project.Kp = (B.ce + 31) / 32 * 32;
         B.project.nt = pick_nt(B.d.cout, B.Ho <= 14);
@@ -729,7 +767,13 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
                          B11.cs4 == 28 && B11.mb.tiles_x * B11.mb.tiles_y == 1;
         const bool t11all = t11 && o.tail_b11 && !o.keep && B11.mb.ksteps == 4 && B11.d.k == 5 && B11.d.s == 2 && B11.H == 14;
         bb->tail = t11all ? TailRoute::B11All : t11 ? TailRoute::B11 : t12 ? TailRoute::B12 : TailRoute::None;
-        for (int i = 0; i < NBLK; ++i) plan_block(bb, bb->blk[i], i);
+        for (int i = 0; i < NBLK; ++i) TRY_OR_FREE(plan_block(bb, bb->blk[i], i));
+        bb->head.nt = 4;
+        const int HWh = K[NBLK - 1].Ho * K[NBLK - 1].Ho;
+        if (bb->tail != TailRoute::B11 && bb->tail != TailRoute::B11All && !plan_gemm(bb->head, EPI_GAP, false, false, HWh)) {
+            mmc_backbone_destroy(bb);
+            return fail(MMC_ERR_ARG, "head: no pw_gemm (average pool) instantiation for nt %d at %d pixels per patch", bb->head.nt, HWh);
+        }
     }
 
     // ---- 3. packing: what the plan launches, reading the blob's tensors in their fixed order ----
@@ -779,7 +823,7 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
             snprintf(nm, sizeof nm, "b%d.expand", i);
             TAKE(w, (size_t)B.ce * B.d.cin, nm);
             TAKE(b, B.ce, nm);
-            TRY_OR_FREE(pack_pw(bb, &B.expand, w, b, B.ce, B.d.cin, 0, LOG2E, LOG2E));
+            TRY_OR_FREE(pack_pw(bb, &B.expand, w, b, B.ce, B.d.cin, B.expand.nt, LOG2E, LOG2E));
             const int kp = 32 * B.mb.ksteps;
             std::vector<_Float16> wn((size_t)B.ce * kp, (_Float16)0.0f);   // natural rows, K zero padded
             for (int c = 0; c < B.ce && B.fusable; ++c)
@@ -1005,7 +1049,7 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
     {
         TAKE(w, (size_t)FEAT * HEAD_IN, "head.weight");
         TAKE(b, FEAT, "head.bias");
-        TRY_OR_FREE(pack_pw(bb, &bb->head, w, b, FEAT, HEAD_IN, 4, LOG2E, LOG2E));
+        TRY_OR_FREE(pack_pw(bb, &bb->head, w, b, FEAT, HEAD_IN, bb->head.nt, LOG2E, LOG2E));
         if (bb->tail == TailRoute::B11 || bb->tail == TailRoute::B11All)   // the same weights in plain fragment order for tail7's head phase
             TRY_OR_FREE(dev_upload(bb, &bb->head_wfrag, pack_frag(w, FEAT, HEAD_IN, HEAD_IN, FEAT / 16, HEAD_IN / 32, LOG2E)));
     }
@@ -1088,13 +1132,6 @@ static int gemm_mt(const PwLayer& L, int M)
     return wgs2 >= 1024 ? 2 : 1;
 }
 
-static std::string gemm_label(const PwLayer& L, int M, int epi, bool gate, bool res)
-{
-    char b[64];
-    snprintf(b, sizeof b, "pw_gemm<%d,%d,%d,%d,%d>", epi == EPI_GAP ? 1 : gemm_mt(L, M), L.nt, epi, gate ? 1 : 0, res ? 1 : 0);
-    return b;
-}
-
 static int run_gemm(const PwLayer& L, const _Float16* X, int M, _Float16* Y, int epi, const float* gate, int HW,
                     const _Float16* res, float* gap_out, hipStream_t st)
 {
@@ -1103,7 +1140,7 @@ static int run_gemm(const PwLayer& L, const _Float16* X, int M, _Float16* Y, int
     a.nt = L.nt; a.n_chunks = L.n_chunks; a.epi = epi; a.gate = gate; a.HW = HW; a.res = res;
     a.gap_out = gap_out; a.inv_hw = (float)(1.0 / ((double)HW * LOG2E));  // GAP input is log2(e)-scaled
     a.mt = gemm_mt(L, M);
-    a.defer_gate = (gate && HW <= 49) ? 1 : 0;   // 7x7 layers: few workgroups, deep K -> overlap loads with MFMAs
+    a.defer_gate = gemm_defer_gate(gate != nullptr, HW);
     return launch_pw_gemm(a, st);
 }
 
@@ -1144,7 +1181,6 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
         if (B.front == Front::Tail) break;
         const int HWi = B.H * B.H, HWo = B.Ho * B.Ho;
         snprintf(nm, sizeof nm, "b%d.mbconv", i);
-        char fl[48];
         switch (B.front) {
         case Front::StemDw:
             // with block 0's project folded into block 1's kernel the depthwise output goes to the spare activation
@@ -1157,10 +1193,7 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             ta.X = x; ta.wexp = B.exp_frag; ta.bexp = B.expand.b; ta.dwp = B.t_dwp; ta.bdw = B.dw_b; ta.D = ws.dwbuf;
             ta.pool = ws.pool_part; ta.B = n; ta.H = B.H; ta.Cin = B.d.cin; ta.Ce = B.ce; ta.ks = B.d.k; ta.stride = B.d.s;
             ta.dwtoe = B.mbt4 ? B.dw_diag : nullptr;
-            // the instantiation's template arguments, as rocprofv3 names it
-            if (B.mbt4) snprintf(fl, sizeof fl, "mbt4<%d,%d>", (B.d.cin + 31) / 32, B.ce);
-            else snprintf(fl, sizeof fl, "%s<%d,%d,%d,%d>", B.d.s == 2 ? "mbt2" : "mbt", B.d.k, (B.d.cin + 31) / 32, B.ce, B.H);
-            STEP(nm, fl, launch_mbt(ta, st));
+            STEP(nm, B.front_label, launch_mbt(ta, st));
             break;
         }
         case Front::Mid14: {
@@ -1170,8 +1203,7 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             ma.dwdiag = B.mid14m ? B.dw_diag : nullptr;
             ma.nsplit = B.mid14m ? 1 : 4;
             if (bb->mid_clk && i == 10) ma.dbg_clk = bb->mid_clk + (size_t)lane_idx * bb->lane_cap * 128;
-            snprintf(fl, sizeof fl, B.mid14m ? "mid14m<%d,%d,%d,%d>" : "mid14<%d,%d,%d,%d>", (B.d.cin + 31) / 32, B.d.k, B.ce, B.d.s);
-            STEP(nm, fl, launch_mid14(ma, st));
+            STEP(nm, B.front_label, launch_mid14(ma, st));
             break;
         }
         case Front::Mb1: {
@@ -1187,14 +1219,12 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             a.X = x; a.Wexp = B.exp_nat; a.bexp = B.expand.b; a.Wdw = B.dw_w; a.bdw = B.dw_b; a.out = ws.dwbuf;
             a.pool_part = ws.pool_part; a.B = n;
             if (B.front == Front::MbD) {
-                snprintf(fl, sizeof fl, "mbconv_d<%d,%d,%d,%d,%d,%d,%d>", a.ks, a.stride, a.ksteps, a.npair, a.CC, a.TWo, a.pb);
-                STEP(nm, fl, launch_mbconv_d(a, st));
+                STEP(nm, B.front_label, launch_mbconv_d(a, st));
             } else if (B.front == Front::MbPre) {
                 a.X = y; a.Cin = 32; a.Wexp = bb->b1_exp_pre;   // block 0's depthwise output; its gate is in ws.gate
-                STEP("b0.project+b1.mbconv", "mbconv_a_pre", launch_mbconv_pre(a, bb->b0_pre_w, bb->blk[0].project.b, ws.gate, st));
+                STEP("b0.project+b1.mbconv", B.front_label, launch_mbconv_pre(a, bb->b0_pre_w, bb->blk[0].project.b, ws.gate, st));
             } else {
-                snprintf(fl, sizeof fl, "mbconv_a<%d,%d,%d,%d,%d,%d,%d,0>", a.ks, a.stride, a.tw, a.ksteps, a.npair, a.CC, a.pb);
-                STEP(nm, fl, launch_mbconv_a(a, st));
+                STEP(nm, B.front_label, launch_mbconv_a(a, st));
             }
             break;
         }
@@ -1202,7 +1232,7 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             const _Float16* dw_in = x;
             if (B.has_expand) {
                 snprintf(nm, sizeof nm, "b%d.expand", i);
-                STEP(nm, gemm_label(B.expand, n * HWi, EPI_SILU, false, false),
+                STEP(nm, B.expand.label[gemm_mt(B.expand, n * HWi) - 1],
                      run_gemm(B.expand, x, n * HWi, ws.expbuf, EPI_SILU, nullptr, HWi, nullptr, nullptr, st));
                 SAVE(nm, ws.expbuf, (size_t)n * HWi * B.ce, true);
                 dw_in = ws.expbuf;
@@ -1212,8 +1242,7 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             d.B = n; d.H = B.H; d.W = B.H; d.C = B.ce; d.Ho = B.Ho; d.Wo = B.Ho; d.pad_t = B.pad; d.pad_l = B.pad;
             d.ks = B.d.k; d.stride = B.d.s; d.tw = B.tw; d.CG = B.CG; d.S = B.S; d.iters = B.iters; d.parts = B.parts; d.nz = B.nz;
             snprintf(nm, sizeof nm, "b%d.dw", i);
-            snprintf(fl, sizeof fl, "dwconv<%d,%d,%d>", d.ks, d.stride, d.tw);
-            STEP(nm, fl, launch_dwconv(d, st));
+            STEP(nm, B.front_label, launch_dwconv(d, st));
         }
         }
         snprintf(nm, sizeof nm, "b%d.dw", i);
@@ -1229,8 +1258,7 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             pa.B = n; pa.HW = HWo; pa.K = B.ce; pa.N = B.d.cout; pa.CSP = B.cs4; pa.nparts = B.nparts;
             pa.psc = (float)(1.0 / ((double)HWo * LOG2E));
             snprintf(nm, sizeof nm, "b%d.projse", i);
-            snprintf(fl, sizeof fl, "proj_patch<%d,%d,%d,%d>", proj_patch_ksteps(B.ce), (B.d.cout + 15) / 16, HWo, B.skip ? 1 : 0);
-            STEP(nm, fl, launch_proj_patch(pa, st));
+            STEP(nm, B.back_label, launch_proj_patch(pa, st));
             snprintf(nm, sizeof nm, "b%d.gate", i);
             SAVE(nm, ws.gate, (size_t)n * B.ce, false);
             snprintf(nm, sizeof nm, "b%d.out", i);
@@ -1267,7 +1295,7 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             fa.bias = B.p8.b; fa.Y = y; fa.N = B.p8.N; fa.gate = ws.gate; fa.HW = HWo; fa.res = B.skip ? x : nullptr;
             STEP(nm, "pw_gemm_fp8", launch_pw_gemm_fp8(fa, st));
         } else
-            STEP(nm, gemm_label(B.project, n * HWo, EPI_LINEAR, true, B.skip),
+            STEP(nm, B.project.label[gemm_mt(B.project, n * HWo) - 1],
                  run_gemm(B.project, ws.dwbuf, n * HWo, y, EPI_LINEAR, ws.gate, HWo, B.skip ? x : nullptr, nullptr, st));
         snprintf(nm, sizeof nm, "b%d.out", i);
         SAVE(nm, y, (size_t)n * HWo * B.d.cout, true);
@@ -1337,7 +1365,7 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
         STEP("head.tail", "tail7", launch_tail7(ta, st));
     } else {
         const int HWh = bb->blk[bb->nblk - 1].Ho * bb->blk[bb->nblk - 1].Ho;
-        STEP("head", gemm_label(bb->head, n * HWh, EPI_GAP, false, false),
+        STEP("head", bb->head.label[0],
              run_gemm(bb->head, x, n * HWh, nullptr, EPI_GAP, nullptr, HWh, nullptr, out_dev, st));
     }
 #undef SAVE

@@ -131,6 +131,24 @@ def test_abi_exports_every_declared_symbol():
     assert lib.mmc_device_count() >= 0
 
 
+def test_only_launchable_pw_gemm_forms_are_compiled():
+    """Every pw_gemm_kernel<MT, NT, EPI, GATE, RES, UK, DG> in the built library is a form its launcher's table can reach: an
+    expand conv (SiLU) never has a gate, a project conv (linear) always has one, the head's average-pool form has none;
+    the k-steps per LDS batch follow from MT * NT; the deferred gate exists only for gated forms with one row fragment per
+    wave and four k-steps per batch.  (Kernel symbols are plain text in the shared object.)"""
+    import os
+    from mermaid_classifier_amd import _lib
+    blob = Path(os.environ.get("MMC_LIBRARY", _lib.LIB_PATH)).read_bytes()
+    forms = set(re.findall(rb"_Z14pw_gemm_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELb([01])ELi(\d+)ELb([01])EE\w*\.kd", blob))
+    assert 1 <= len(forms) <= 35, len(forms)
+    for form in sorted(forms):
+        mt, nt, epi, gate, res, uk, dg = (int(v) for v in form)
+        assert (epi, gate) in ((0, 0), (1, 1), (2, 0)), form     # EPI_SILU / EPI_LINEAR / EPI_GAP
+        assert uk == (4 if mt * nt <= 4 else 2), form
+        assert not dg or (gate and mt == 1 and mt * nt <= 4), form
+        assert mt in (1, 2) and not (res and epi != 1), form
+
+
 def test_no_cpu_fallback_without_device(checkpoint_path):
     """Without a HIP device the product path refuses loudly instead of computing on the CPU."""
     from mermaid_classifier_amd import _lib
