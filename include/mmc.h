@@ -29,7 +29,7 @@ extern "C" {
 #define MMC_ARCH_B4 1   /* efficientnet-b4 (width 1.4, depth 1.8) on 224x224 patches: BASELINE.json configs[4]; not in the
                          * reference; fused expand+depthwise kernels plus the shape-generic squeeze-excite / project / head kernels, feature_dim 1792 */
 
-/* memory-kind flags for mmc_backbone_extract / mmc_head_predict / mmc_crop_patches */
+/* memory-kind flags for mmc_backbone_extract / mmc_head_predict / mmc_head_topk / mmc_classify_patches / mmc_crop_patches */
 #define MMC_IN_DEVICE 0u
 #define MMC_IN_HOST 1u   /* `patches`/`feats`/`image` is host memory: staged with hipMemcpyAsync */
 #define MMC_OUT_DEVICE 0u
@@ -149,6 +149,31 @@ int mmc_head_num_classes(const mmc_head* h);
 /* feats: n x input_dim fp32; proba: n x K fp32; argmax: n int32 (may be NULL). */
 int mmc_head_predict(mmc_head* h, const float* feats, int64_t n, float* proba, int32_t* argmax,
                      unsigned flags, void* hip_stream);
+
+/* The k best classes per row instead of (or next to) the probabilities.
+ * Replaces: mermaid_classifier/pyspacer/annotation.py:251-261 (predict_proba + per-point sorted(...)[:k]): row i of idx / scores
+ *   holds the class indices and calibrated probabilities of sorted(zip(labels, proba_i), key=itemgetter(1), reverse=True)[:k] --
+ *   score descending and, the sort being stable, equal scores in class order; k is the reference's predictions_per_point
+ *   (annotation.py:231-233).  The probabilities are those of mmc_head_predict, bit for bit (same launches for the Linear layers, same
+ *   calibration arithmetic); the selection runs in the calibration kernel, so nothing but n x k indices and scores has to leave the device.
+ * feats: n x input_dim fp32; idx: n x k int32; scores: n x k fp32; proba: n x K fp32 or NULL.  1 <= k <= K.
+ * flags: MMC_IN_HOST for feats, MMC_OUT_HOST for idx / scores / proba together.  Asynchronous on `hip_stream` unless MMC_OUT_HOST is set.
+ * Rows with NaN features still get k distinct classes in [0, K); their order is unspecified (as Python's sorted leaves it). */
+int mmc_head_topk(mmc_head* h, const float* feats, int64_t n, int k,
+                  int32_t* idx /* n x k */, float* scores /* n x k */, float* proba /* n x K or NULL */,
+                  unsigned flags, void* hip_stream);
+
+/* ---- patches -> labels in one call ------------------------------------------------------
+ * Replaces: the device work of AnnotationRun.__init__ (mermaid_classifier/pyspacer/annotation.py:241-261): extractor(image, rowcols)
+ *   -> get_array per point -> predict_proba -> sorted(...)[:k], for patches already cut (mmc_crop_patches cuts them).
+ * patches (n x 224 x 224 x 3 u8) -> backbone -> head -> top-k on one stream; features stay in a device buffer owned by
+ * the head handle (grown on demand, stable between calls so the backbone's graph cache keeps hitting): no allocation per call in
+ * the steady state.  More than 4096 patches are worked through in chunks of 4096, so the same (patches chunk, feature buffer, n)
+ * combinations recur and the graph cache documented at mmc_backbone_extract applies.  The handles must live on one device and
+ * mmc_feature_dim must equal mmc_head_input_dim.  flags: MMC_IN_HOST for patches, MMC_OUT_HOST for idx / scores (the only
+ * data copied back); asynchronous unless MMC_OUT_HOST is set.  Same bits as mmc_backbone_extract + mmc_head_topk. */
+int mmc_classify_patches(mmc_backbone* bb, mmc_head* h, const void* patches, int64_t n, int k,
+                         int32_t* idx, float* scores, unsigned flags, void* hip_stream);
 
 /* ---- MLP classifier training on precomputed feature vectors --------------------------------
  * Replaces: the arithmetic of TorchMLPClassifier.partial_fit (mermaid_classifier/pyspacer/torch_classifier.py:226-303)

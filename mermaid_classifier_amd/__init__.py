@@ -6,11 +6,13 @@ first use and its absence is an error (there is no CPU fallback)."""
 from .extractor import EfficientNetExtractor, build_extractor_class, resolve_device, verify_device_numerics  # noqa: F401
 from .inference import ManifestError, Predictor, load_predictor, SCHEMA_VERSION, TASK_NAME  # noqa: F401
 from .backbone import Backbone, crop_patches_device, FEATURE_DIM  # noqa: F401
+from .classify import PointClassifier, PointPredictions  # noqa: F401
 from .calibration import CalibratedMLP, ParityError, calibrate, evaluate, export_artifact  # noqa: F401
 
 __all__ = [
     "EfficientNetExtractor", "build_extractor_class", "resolve_device", "verify_device_numerics",
     "ManifestError", "Predictor", "load_predictor", "SCHEMA_VERSION", "TASK_NAME",
     "Backbone", "crop_patches_device", "FEATURE_DIM",
+    "PointClassifier", "PointPredictions",
     "CalibratedMLP", "ParityError", "calibrate", "evaluate", "export_artifact",
 ]

@@ -22,7 +22,7 @@ SYMBOLS = [
     "mmc_backbone_create", "mmc_backbone_create_ex", "mmc_fp8_e4m3_encode", "mmc_backbone_destroy", "mmc_feature_dim", "mmc_backbone_max_batch", "mmc_backbone_lanes",
     "mmc_backbone_workspace_bytes", "mmc_backbone_extract", "mmc_backbone_read_activation",
     "mmc_backbone_profile", "mmc_backbone_graph_stats", "mmc_crop_patches",
-    "mmc_head_create", "mmc_head_destroy", "mmc_head_input_dim", "mmc_head_num_classes", "mmc_head_predict",
+    "mmc_head_create", "mmc_head_destroy", "mmc_head_input_dim", "mmc_head_num_classes", "mmc_head_predict", "mmc_head_topk", "mmc_classify_patches",
     "mmc_trainer_create", "mmc_trainer_destroy", "mmc_trainer_partial_fit", "mmc_trainer_partial_fit_ordered", "mmc_trainer_get_params", "mmc_trainer_adam_state",
     "mmc_trainer_logits", "mmc_trainer_evaluate", "mmc_trainer_evaluate_q32",
     "mmc_calibrator_create", "mmc_calibrator_destroy", "mmc_calibrator_add_features", "mmc_calibrator_add_scores", "mmc_calibrator_fit",
@@ -91,6 +91,10 @@ def _load() -> C.CDLL:
     lib.mmc_head_num_classes.argtypes = [vp]
     lib.mmc_head_predict.restype = i32
     lib.mmc_head_predict.argtypes = [vp, vp, i64, vp, vp, u32, vp]
+    lib.mmc_head_topk.restype = i32
+    lib.mmc_head_topk.argtypes = [vp, vp, i64, i32, vp, vp, vp, u32, vp]
+    lib.mmc_classify_patches.restype = i32
+    lib.mmc_classify_patches.argtypes = [vp, vp, vp, i64, i32, vp, vp, u32, vp]
     f32 = C.c_float
     f64 = C.c_double
     lib.mmc_trainer_create.restype = i32

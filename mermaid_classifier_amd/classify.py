@@ -1,0 +1,177 @@
+"""Image + points -> top-k labels and calibrated scores per point, ranked on the device.
+
+Mirrors what ``AnnotationRun.__init__`` does with a classifier (mermaid_classifier/pyspacer/annotation.py:231-262):
+``extractor(image, rowcols)`` -> ``predictor.predict_proba(feature_batch)`` -> per point
+``sorted(zip(labels, proba), key=itemgetter(1), reverse=True)[:predictions_per_point]`` into the ``annotations`` and ``scores``
+dictionaries.  Here the features never leave the GPU: ``mmc_classify_patches`` runs backbone, head and the top-k selection on one
+stream, and only the ``(n, k)`` class indices and scores are copied back.  Order and ties are the reference's (score descending,
+equal scores in class order); the probabilities are those of ``Predictor.predict_proba``, bit for bit.
+"""
+
+from __future__ import annotations
+
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from .backbone import PATCH, _current_stream_ptr
+from .pipeline import PatchBatcher, prepare_image
+
+
+class PointPredictions:
+    """The predictions for one image's points (or one patch batch): ``rowcols`` [(row, col)] (None for bare patches),
+    ``indices`` (n, k) int32 class indices, ``scores`` (n, k) float64, ``labels`` the class names, best first."""
+
+    def __init__(self, rowcols: Optional[List[Tuple[int, int]]], indices: np.ndarray, scores: np.ndarray, classes: Sequence[str]):
+        self.rowcols = rowcols
+        self.indices = np.ascontiguousarray(indices, dtype=np.int32)
+        self.scores = np.ascontiguousarray(scores, dtype=np.float64)
+        if self.indices.ndim != 2 or self.indices.shape != self.scores.shape:
+            raise ValueError(f"indices {self.indices.shape} / scores {self.scores.shape} must be equal (n, k) shapes")
+        if rowcols is not None and len(rowcols) != self.indices.shape[0]:
+            raise ValueError(f"{len(rowcols)} points but {self.indices.shape[0]} prediction rows")
+        self.labels: List[List[str]] = [[classes[j] for j in row] for row in self.indices.tolist()]
+
+    def __len__(self) -> int:
+        return self.indices.shape[0]
+
+    def as_dicts(self) -> Tuple[Dict[Tuple[int, int], List[str]], Dict[Tuple[int, int], List[float]]]:
+        """(annotations, scores): the two ``{(row, col): list}`` mappings annotation.py:256-261 fills, in point order; a point
+        listed twice keeps its later entry, as the dict assignment there does."""
+        if self.rowcols is None:
+            raise ValueError("these predictions were made from bare patches: there are no (row, col) keys")
+        annotations: Dict[Tuple[int, int], List[str]] = {}
+        scores: Dict[Tuple[int, int], List[float]] = {}
+        for (row, col), labels, sc in zip(self.rowcols, self.labels, self.scores.tolist()):
+            annotations[(row, col)] = labels
+            scores[(row, col)] = sc
+        return annotations, scores
+
+
+def _check_k(k) -> int:
+    if isinstance(k, bool) or int(k) != k or k < 1:
+        raise ValueError(f"k must be an integer >= 1; got {k!r}")
+    return int(k)
+
+
+class _Batcher(PatchBatcher):
+    """PatchBatcher whose pass is mmc_classify_patches: each flush ends in (fill, k) indices and scores in pinned memory."""
+
+    def __init__(self, owner: "PointClassifier"):
+        super().__init__(owner.backbone, owner.batch_patches)
+        self.owner = owner
+        self._out: Dict[int, tuple] = {}     # k -> per slot (device idx, device scores, pinned idx, pinned scores)
+
+    def buffers(self, k: int):
+        import torch
+        if k not in self._out:
+            self._out[k] = tuple((torch.empty((self.cap, k), dtype=torch.int32, device=self.dev),
+                                  torch.empty((self.cap, k), dtype=torch.float32, device=self.dev),
+                                  torch.empty((self.cap, k), dtype=torch.int32).pin_memory(),
+                                  torch.empty((self.cap, k), dtype=torch.float32).pin_memory()) for _ in range(2))
+        return self._out[k]
+
+    def _launch(self, slot, patches, fill, k):
+        di, ds, _, _ = self.buffers(k)[slot]
+        self.owner._classify_device(patches, fill, k, di, ds)
+
+    def _download(self, slot, fill, k):
+        di, ds, hi, hs = self.buffers(k)[slot]
+        hi[:fill].copy_(di[:fill], non_blocking=True)
+        hs[:fill].copy_(ds[:fill], non_blocking=True)
+
+    def _fetch(self, slot, count, k):
+        _, _, hi, hs = self.buffers(k)[slot]
+        return hi[:count].numpy().copy(), hs[:count].numpy().copy()
+
+
+class PointClassifier:
+    """``Backbone`` + ``Predictor`` as one patches -> labels pipeline on the GPU.  ``batch_patches`` bounds the device patch
+    buffers of ``classify_image(s)``, as in ``BatchedExtractor``.  ``k`` is the reference's ``predictions_per_point``; more than
+    the head has classes gives all of them (the reference's ``[:k]`` slice clamps the same way)."""
+
+    def __init__(self, backbone, predictor, batch_patches: int = 1024):
+        if int(batch_patches) < 1:
+            raise ValueError(f"batch_patches must be >= 1; got {batch_patches}")
+        if backbone.feature_dim != predictor.input_dim:
+            raise ValueError(f"backbone feature_dim {backbone.feature_dim} != predictor input_dim {predictor.input_dim}")
+        self.backbone = backbone
+        self.predictor = predictor
+        self.classes = list(predictor.classes)
+        self.batch_patches = int(batch_patches)
+        self._batcher: Optional[_Batcher] = None     # device buffers are made on first use
+
+    def _k(self, k) -> int:
+        return min(_check_k(k), len(self.classes))
+
+    def _classify_device(self, patches, n: int, k: int, idx_dev, scores_dev) -> None:
+        """mmc_classify_patches on device-resident patches into device outputs, asynchronous on the current stream."""
+        bb, head = self.backbone, self.predictor._head
+        _lib.check(_lib.lib().mmc_classify_patches(bb._h, head._h, patches.data_ptr(), n, k, idx_dev.data_ptr(),
+                                                   scores_dev.data_ptr(), 0, _current_stream_ptr(bb.device_index)))
+
+    def topk_device(self, patches, k: int = 1):
+        """Device in, device out: contiguous uint8 cuda tensor (N,224,224,3) -> (idx (N,k') int32, scores (N,k') float32) cuda
+        tensors, asynchronous on the current stream (what ``dist.classify_sharded`` gathers)."""
+        import torch
+        kk = self._k(k)
+        if (not isinstance(patches, torch.Tensor) or not patches.is_cuda or patches.dtype != torch.uint8 or patches.dim() != 4
+                or tuple(patches.shape[1:]) != (PATCH, PATCH, 3) or not patches.is_contiguous()):
+            raise ValueError("device patches must be a contiguous uint8 cuda tensor (N,224,224,3)")
+        if patches.device.index != self.backbone.device_index:
+            raise ValueError(f"patches live on {patches.device}, backbone on device {self.backbone.device_index}")
+        n = patches.shape[0]
+        idx = torch.empty((n, kk), dtype=torch.int32, device=patches.device)
+        scores = torch.empty((n, kk), dtype=torch.float32, device=patches.device)
+        if n:
+            self._classify_device(patches, n, kk, idx, scores)
+        return idx, scores
+
+    def classify_patches(self, patches, k: int = 1) -> PointPredictions:
+        """patches: (N,224,224,3) uint8 -- numpy (host) or a cuda tensor on the backbone's device."""
+        kk = self._k(k)
+        if isinstance(patches, np.ndarray):
+            p = np.ascontiguousarray(patches)
+            if p.dtype != np.uint8 or p.ndim != 4 or p.shape[1:] != (PATCH, PATCH, 3):
+                raise ValueError(f"patches must be uint8 (N,{PATCH},{PATCH},3); got {p.dtype} {p.shape}")
+            n = p.shape[0]
+            idx = np.empty((n, kk), dtype=np.int32)
+            scores = np.empty((n, kk), dtype=np.float32)
+            if n:
+                bb, head = self.backbone, self.predictor._head
+                _lib.check(_lib.lib().mmc_classify_patches(bb._h, head._h, p.ctypes.data, n, kk, idx.ctypes.data, scores.ctypes.data,
+                                                           _lib.MMC_IN_HOST | _lib.MMC_OUT_HOST, _current_stream_ptr(bb.device_index)))
+            return PointPredictions(None, idx, scores, self.classes)
+        try:
+            import torch
+            is_tensor = isinstance(patches, torch.Tensor)
+        except ImportError:
+            is_tensor = False
+        if not is_tensor:
+            raise TypeError("patches must be a numpy array or a torch tensor")
+        idx, scores = self.topk_device(patches, kk)
+        return PointPredictions(None, idx.cpu().numpy(), scores.cpu().numpy(), self.classes)
+
+    def classify_images(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]],
+                        k: int = 1) -> List[PointPredictions]:
+        """One ``PointPredictions`` per image, rows in ``rowcols`` order (empty for an image without points).  Inputs are checked
+        as ``BatchedExtractor`` checks them, all of them before the GPU is touched; points of consecutive images share passes."""
+        kk = self._k(k)
+        prepared = [prepare_image(i, im, rc) for i, (im, rc) in enumerate(zip(images, rowcols_per_image))]
+        if self._batcher is None:
+            self._batcher = _Batcher(self)
+        out, points = self._batcher._run([im for im, _ in prepared], [rc for _, rc in prepared], ctx=kk)
+        res = []
+        for o, rc in zip(out, points):
+            pts = [(int(r), int(c)) for r, c in rc]
+            if o is None:
+                res.append(PointPredictions(pts, np.zeros((0, kk), np.int32), np.zeros((0, kk), np.float64), self.classes))
+            else:
+                res.append(PointPredictions(pts, o[0], o[1], self.classes))
+        return res
+
+    def classify_image(self, image: np.ndarray, rowcols: Sequence[Tuple[int, int]], k: int = 1) -> PointPredictions:
+        """annotation.py:239-261 for one image: ``classify_image(loaded_image, rowcols, k).as_dicts()`` are its ``annotations`` /
+        ``scores`` entries."""
+        return self.classify_images([image], [list(rowcols)], k)[0]

@@ -15,6 +15,7 @@
 //   dwconv_kernel      _depthwise_conv + _bn1 + swish, plus the squeeze-excite partial sums
 //   se_gate_kernel     adaptive_avg_pool2d + _se_reduce + swish + _se_expand + sigmoid
 //   mlp_gemm_f32_kernel / calibrate_kernel   CalibratedHead.forward (inference/head.py:66-89)
+//   calibrate_topk_kernel   the same + the per-point sorted(...)[:k] of AnnotationRun (pyspacer/annotation.py:251-261)
 //   crop_kernel        pyspacer crop_patches (reflect pad + slice)
 #include "device_common.h"
 
@@ -902,8 +903,46 @@ __global__ __launch_bounds__(256) void mlp_gemm_f32_kernel(const float* __restri
         }
 }
 
-// One wave per row: softmax -> Platt sigmoid -> row normalise (uniform row when the sum is 0)
-// -> sklearn overshoot clip -> argmax (first maximum, like numpy/torch argmax).   head.py:75-89
+// The calibration arithmetic of CalibratedHead.forward (head.py:75-89), one wave per row, lane l owning classes l, l + 64, ...:
+// softmax -> Platt sigmoid -> row normalise (uniform row when the sum is 0) -> sklearn overshoot clip.  calibrate_kernel and
+// calibrate_topk_kernel are both built from these pieces, so a probability has the same bits whichever of them wrote it.
+__device__ __forceinline__ float wave_max_f(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_sum_f(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// the row's maximum logit and the sum of exp(x - max)
+__device__ __forceinline__ void calib_softmax_stats(const float* __restrict__ x, int K, int lane, float& mx, float& se)
+{
+    mx = -INFINITY;
+    for (int k = lane; k < K; k += 64) mx = fmaxf(mx, x[k]);
+    mx = wave_max_f(mx);
+    se = 0.f;
+    for (int k = lane; k < K; k += 64) se += expf(x[k] - mx);
+    se = wave_sum_f(se);
+}
+// one class before normalisation: sigmoid(-(a p + b)) of its softmax probability p
+__device__ __forceinline__ float calib_sigmoid(float xk, float mx, float se, float ak, float bk)
+{
+    const float p = expf(xk - mx) / se;
+    return 1.0f / (1.0f + expf(ak * p + bk));
+}
+// c / (row sum cs), the uniform row when cs is 0, values in (1, 1 + 1e-5] clipped to 1
+__device__ __forceinline__ float calib_normalise(float c, float cs, int K)
+{
+    float v = (cs != 0.f) ? c / cs : 1.0f / (float)K;
+    if (v > 1.0f && v <= 1.00001f) v = 1.0f;
+    return v;
+}
+
+// One wave per row: the calibration above -> argmax (first maximum, like numpy/torch argmax).   head.py:75-89
 __global__ __launch_bounds__(256) void calibrate_kernel(const float* __restrict__ logits, int M, int K,
                                                         const float* __restrict__ a, const float* __restrict__ bcal,
                                                         float* __restrict__ proba, int32_t* __restrict__ argmax_out)
@@ -912,28 +951,19 @@ __global__ __launch_bounds__(256) void calibrate_kernel(const float* __restrict_
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const float* x = logits + (size_t)row * K;
-    float mx = -INFINITY;
-    for (int k = lane; k < K; k += 64) mx = fmaxf(mx, x[k]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    float se = 0.f;
-    for (int k = lane; k < K; k += 64) se += expf(x[k] - mx);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+    float mx, se;
+    calib_softmax_stats(x, K, lane, mx, se);
     float cs = 0.f;
     for (int k = lane; k < K; k += 64) {
-        const float p = expf(x[k] - mx) / se;
-        const float c = 1.0f / (1.0f + expf(a[k] * p + bcal[k]));  // sigmoid(-(a p + b))
+        const float c = calib_sigmoid(x[k], mx, se, a[k], bcal[k]);
         proba[(size_t)row * K + k] = c;
         cs += c;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o);
+    cs = wave_sum_f(cs);
     float best = -INFINITY;
     int besti = 0x7fffffff;
     for (int k = lane; k < K; k += 64) {
-        float v = (cs != 0.f) ? proba[(size_t)row * K + k] / cs : 1.0f / (float)K;
-        if (v > 1.0f && v <= 1.00001f) v = 1.0f;
+        const float v = calib_normalise(proba[(size_t)row * K + k], cs, K);
         proba[(size_t)row * K + k] = v;
         if (v > best) { best = v; besti = k; }
     }
@@ -944,6 +974,77 @@ __global__ __launch_bounds__(256) void calibrate_kernel(const float* __restrict_
         if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
     }
     if (argmax_out && lane == 0) argmax_out[row] = besti;
+}
+
+// ---------------------------------------------------------------------------------------------
+// calibrate_topk_kernel: the same calibration, then the k best classes of the row in the order of the reference's
+// sorted(zip(labels, proba), key=itemgetter(1), reverse=True)[:k] (mermaid_classifier/pyspacer/annotation.py:253-255): score
+// descending, and -- the sort is stable -- equal scores in class order.
+// One wave per row, four rows per workgroup.  A probability is >= 0, so its fp32 bit pattern orders like its value; the
+// 64-bit key (bits << 32) | (0xFFFFFFFF - class) therefore orders a row exactly as the reference does, keys are distinct, and
+// one wave-wide maximum per round picks the next class.  Nothing is marked as taken: keys leave in strictly decreasing order,
+// so after a round the lane that owned the winner looks among its own classes for its largest key BELOW the winner -- which
+// holds for every bit pattern, NaN included: k rounds, k distinct classes in [0, K), whatever the logits are.
+// A lane only ever reads the row entries it wrote itself (classes lane, lane + 64, ...), so the row needs no barrier; it sits
+// in a wave-private LDS row (ROW_IN_LDS: K <= TOPK_LDS_MAX_K, bank-conflict free) and is not re-read from HBM between rounds.
+// Wider heads keep the same algorithm with the row in `rowbuf` (M x K floats in global memory: the caller's proba or scratch).
+// ---------------------------------------------------------------------------------------------
+#define TOPK_LDS_MAX_K 2048   // 4 rows x 2048 classes x 4 B = 32 KB of LDS per workgroup
+__device__ __forceinline__ unsigned long long topk_key(float v, int cls)
+{
+    return ((unsigned long long)__float_as_uint(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)cls);
+}
+template <bool ROW_IN_LDS>
+__global__ __launch_bounds__(256) void calibrate_topk_kernel(const float* __restrict__ logits, int M, int K,
+                                                             const float* __restrict__ a, const float* __restrict__ bcal, int k,
+                                                             int32_t* __restrict__ idx_out,   // [M][k]
+                                                             float* __restrict__ score_out,   // [M][k]
+                                                             float* proba,                    // [M][K] or NULL
+                                                             float* rowbuf)                   // [M][K] when !ROW_IN_LDS
+{
+    extern __shared__ float topk_rows[];   // [4][K] when ROW_IN_LDS
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= M) return;
+    const float* x = logits + (size_t)row * K;
+    float* r = ROW_IN_LDS ? topk_rows + (size_t)wave * K : rowbuf + (size_t)row * K;
+    float mx, se;
+    calib_softmax_stats(x, K, lane, mx, se);
+    float cs = 0.f;
+    for (int c = lane; c < K; c += 64) {
+        const float v = calib_sigmoid(x[c], mx, se, a[c], bcal[c]);
+        r[c] = v;
+        cs += v;
+    }
+    cs = wave_sum_f(cs);
+    unsigned long long cur = 0;   // this lane's largest key not yet selected; 0 = none (a real key's low word is >= 0xFFFFFFFF - K > 0)
+    for (int c = lane; c < K; c += 64) {
+        const float v = calib_normalise(r[c], cs, K);
+        r[c] = v;
+        if (proba) proba[(size_t)row * K + c] = v;
+        const unsigned long long key = topk_key(v, c);
+        cur = key > cur ? key : cur;
+    }
+    for (int j = 0; j < k; ++j) {   // k <= K (checked by the launcher): a real key is left in every round
+        unsigned long long win = cur;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_xor(win, o);
+            win = t > win ? t : win;
+        }
+        if (lane == 0) {
+            idx_out[(size_t)row * k + j] = (int32_t)(0xFFFFFFFFu - (unsigned)win);
+            score_out[(size_t)row * k + j] = __uint_as_float((unsigned)(win >> 32));
+        }
+        if (cur == win) {   // the owner (keys are distinct): its next candidate is its largest key below the winner
+            unsigned long long nb = 0;
+            for (int c = lane; c < K; c += 64) {
+                const unsigned long long key = topk_key(r[c], c);
+                nb = (key < win && key > nb) ? key : nb;
+            }
+            cur = nb;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1134,6 +1235,25 @@ int launch_calibrate(const float* logits, int M, int K, const float* a, const fl
                      hipStream_t st)
 {
     hipLaunchKernelGGL(calibrate_kernel, dim3((M + 3) / 4), dim3(256), 0, st, logits, M, K, a, b, proba, argmax);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_calibrate_topk(const float* logits, int M, int K, const float* a, const float* b, int k, int32_t* idx, float* scores,
+                          float* proba, float* rowbuf, hipStream_t st)
+{
+    if (M < 1 || K < 1 || k < 1 || k > K || !idx || !scores) return -18;
+    const dim3 grid((M + 3) / 4);
+    if (K <= TOPK_LDS_MAX_K) {
+        hipLaunchKernelGGL((calibrate_topk_kernel<true>), grid, dim3(256), (size_t)4 * K * sizeof(float), st, logits, M, K, a, b, k,
+                           idx, scores, proba, (float*)nullptr);
+    } else {
+        // the row lives in global memory: in the probability output when the caller wants one, else in the scratch rows
+        float* rows = proba ? proba : rowbuf;
+        if (!rows) return -18;
+        hipLaunchKernelGGL((calibrate_topk_kernel<false>), grid, dim3(256), 0, st, logits, M, K, a, b, k, idx, scores,
+                           (float*)nullptr, rows);
+    }
     LAUNCH_CHECK();
     return 0;
 }

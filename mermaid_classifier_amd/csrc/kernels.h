@@ -225,4 +225,8 @@ int launch_mlp_layer(const float* X, int M, int K, const float* W, const float* 
                      hipStream_t st);
 int launch_calibrate(const float* logits, int M, int K, const float* a, const float* b, float* proba, int32_t* argmax,
                      hipStream_t st);
+// calibration + the k best classes per row (score descending, ties in class order); proba may be NULL; rowbuf: M x K scratch floats,
+// needed only when K > 2048 and proba is NULL
+int launch_calibrate_topk(const float* logits, int M, int K, const float* a, const float* b, int k, int32_t* idx, float* scores,
+                          float* proba, float* rowbuf, hipStream_t st);
 int launch_crop(const uint8_t* image, int H, int W, const int32_t* rowcols, int n, uint8_t* out, hipStream_t st);

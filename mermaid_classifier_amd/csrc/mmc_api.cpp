@@ -1741,6 +1741,13 @@ struct mmc_head {
     float *buf0 = nullptr, *buf1 = nullptr, *in_stage = nullptr, *proba_stage = nullptr;
     int32_t* arg_stage = nullptr;
     int64_t cap_rows = 0;
+    // mmc_head_topk: device staging of the (rows, k) outputs for MMC_OUT_HOST, grown on demand
+    int32_t* topk_idx_stage = nullptr;
+    float* topk_score_stage = nullptr;
+    int64_t topk_cap = 0;             // elements (rows * k)
+    // mmc_classify_patches: the features between backbone and head, grown on demand up to CLASSIFY_CHUNK rows
+    float* cls_feats = nullptr;
+    int64_t cls_cap = 0;              // rows
 };
 
 extern "C" void mmc_head_destroy(mmc_head* h)
@@ -1751,6 +1758,7 @@ extern "C" void mmc_head_destroy(mmc_head* h)
     for (float* p : h->b) hipFree(p);
     hipFree(h->a); hipFree(h->bc); hipFree(h->buf0); hipFree(h->buf1);
     hipFree(h->in_stage); hipFree(h->proba_stage); hipFree(h->arg_stage);
+    hipFree(h->topk_idx_stage); hipFree(h->topk_score_stage); hipFree(h->cls_feats);
     delete h;
 }
 
@@ -1821,6 +1829,28 @@ static int head_reserve(mmc_head* h, int64_t rows)
     return 0;
 }
 
+// the Linear layers of one chunk (rows staged / padded as needed): returns the last layer's logits (cur x K) in *logits
+static int head_logits(mmc_head* h, const float* x, int cur, unsigned flags, hipStream_t st, const float** logits)
+{
+    const hipMemcpyKind kin = (flags & MMC_IN_HOST) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    if ((flags & MMC_IN_HOST) || h->in_pad != h->input_dim) {
+        if (h->in_pad != h->input_dim) HIP_TRY(hipMemsetAsync(h->in_stage, 0, (size_t)cur * h->in_pad * 4, st));
+        HIP_TRY(hipMemcpy2DAsync(h->in_stage, (size_t)h->in_pad * 4, x, (size_t)h->input_dim * 4,
+                                 (size_t)h->input_dim * 4, cur, kin, st));
+        x = h->in_stage;
+    }
+    float* pa = h->buf0;
+    float* pb = h->buf1;
+    for (int l = 0; l < h->n_layers; ++l) {
+        const bool last = l == h->n_layers - 1;
+        KTRY(launch_mlp_layer(x, cur, h->dims_pad[l], h->W[l], h->b[l], pa, h->dims_pad[l + 1], !last, st));
+        x = pa;
+        float* t = pa; pa = pb; pb = t;
+    }
+    *logits = x;
+    return 0;
+}
+
 extern "C" int mmc_head_predict(mmc_head* h, const float* feats, int64_t n, float* proba, int32_t* argmax,
                                 unsigned flags, void* hip_stream)
 {
@@ -1835,22 +1865,8 @@ extern "C" int mmc_head_predict(mmc_head* h, const float* feats, int64_t n, floa
         const int cur = (int)((n - off) < chunk ? (n - off) : chunk);
         int r = head_reserve(h, cur);
         if (r) return r;
-        const float* x = feats + (size_t)off * h->input_dim;
-        const hipMemcpyKind kin = (flags & MMC_IN_HOST) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        if ((flags & MMC_IN_HOST) || h->in_pad != h->input_dim) {
-            if (h->in_pad != h->input_dim) HIP_TRY(hipMemsetAsync(h->in_stage, 0, (size_t)cur * h->in_pad * 4, st));
-            HIP_TRY(hipMemcpy2DAsync(h->in_stage, (size_t)h->in_pad * 4, x, (size_t)h->input_dim * 4,
-                                     (size_t)h->input_dim * 4, cur, kin, st));
-            x = h->in_stage;
-        }
-        float* pa = h->buf0;
-        float* pb = h->buf1;
-        for (int l = 0; l < h->n_layers; ++l) {
-            const bool last = l == h->n_layers - 1;
-            KTRY(launch_mlp_layer(x, cur, h->dims_pad[l], h->W[l], h->b[l], pa, h->dims_pad[l + 1], !last, st));
-            x = pa;
-            float* t = pa; pa = pb; pb = t;
-        }
+        const float* x = nullptr;
+        if ((r = head_logits(h, feats + (size_t)off * h->input_dim, cur, flags, st, &x))) return r;
         float* pout = (flags & MMC_OUT_HOST) ? h->proba_stage : proba + (size_t)off * h->K;
         int32_t* aout = argmax ? ((flags & MMC_OUT_HOST) ? h->arg_stage : argmax + off) : nullptr;
         KTRY(launch_calibrate(x, cur, h->K, h->a, h->bc, pout, aout, st));
@@ -1859,6 +1875,90 @@ extern "C" int mmc_head_predict(mmc_head* h, const float* feats, int64_t n, floa
             if (argmax) HIP_TRY(hipMemcpyAsync(argmax + off, aout, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
+    }
+    return MMC_OK;
+}
+
+static int head_topk_reserve(mmc_head* h, int64_t elems)
+{
+    if (elems <= h->topk_cap) return 0;
+    hipFree(h->topk_idx_stage); hipFree(h->topk_score_stage);
+    h->topk_idx_stage = nullptr; h->topk_score_stage = nullptr; h->topk_cap = 0;
+    HIP_TRY(hipMalloc((void**)&h->topk_idx_stage, (size_t)elems * 4 + 256));
+    HIP_TRY(hipMalloc((void**)&h->topk_score_stage, (size_t)elems * 4 + 256));
+    h->topk_cap = elems;
+    return 0;
+}
+
+extern "C" int mmc_head_topk(mmc_head* h, const float* feats, int64_t n, int k, int32_t* idx, float* scores, float* proba,
+                             unsigned flags, void* hip_stream)
+{
+    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
+    if (n < 0) return fail(MMC_ERR_ARG, "n = %lld is negative", (long long)n);
+    if (k < 1 || k > h->K) return fail(MMC_ERR_ARG, "k = %d is outside [1, %d] (the head has %d classes)", k, h->K, h->K);
+    if (n == 0) return MMC_OK;
+    if (!feats) return fail(MMC_ERR_ARG, "feats is NULL");
+    if (!idx || !scores) return fail(MMC_ERR_ARG, "idx/scores is NULL");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipSetDevice(h->device));
+    const bool out_host = (flags & MMC_OUT_HOST) != 0;
+    const int64_t chunk = 65536;   // the chunking of mmc_head_predict: same launches, same bits
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int cur = (int)((n - off) < chunk ? (n - off) : chunk);
+        int r = head_reserve(h, cur);
+        if (r) return r;
+        if (out_host && (r = head_topk_reserve(h, (int64_t)cur * k))) return r;
+        const float* logits = nullptr;
+        if ((r = head_logits(h, feats + (size_t)off * h->input_dim, cur, flags, st, &logits))) return r;
+        int32_t* iout = out_host ? h->topk_idx_stage : idx + (size_t)off * k;
+        float* sout = out_host ? h->topk_score_stage : scores + (size_t)off * k;
+        float* pout = proba ? (out_host ? h->proba_stage : proba + (size_t)off * h->K) : nullptr;
+        KTRY(launch_calibrate_topk(logits, cur, h->K, h->a, h->bc, k, iout, sout, pout, h->proba_stage, st));
+        if (out_host) {
+            HIP_TRY(hipMemcpyAsync(idx + (size_t)off * k, iout, (size_t)cur * k * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(scores + (size_t)off * k, sout, (size_t)cur * k * 4, hipMemcpyDeviceToHost, st));
+            if (proba) HIP_TRY(hipMemcpyAsync(proba + (size_t)off * h->K, pout, (size_t)cur * h->K * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+    }
+    return MMC_OK;
+}
+
+// rows of features mmc_classify_patches keeps between backbone and head: a larger call works through chunks of exactly this size
+// (and one remainder), so the (patches chunk, feature buffer, n) combinations of a repeated call recur and keep their graphs
+static const int64_t CLASSIFY_CHUNK = 4096;
+
+extern "C" int mmc_classify_patches(mmc_backbone* bb, mmc_head* h, const void* patches, int64_t n, int k, int32_t* idx,
+                                    float* scores, unsigned flags, void* hip_stream)
+{
+    if (!bb) return fail(MMC_ERR_ARG, "backbone handle is NULL");
+    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
+    if (bb->device != h->device)
+        return fail(MMC_ERR_ARG, "backbone lives on device %d, head on device %d", bb->device, h->device);
+    if (bb->feat != h->input_dim)
+        return fail(MMC_ERR_ARG, "backbone feature_dim %d != head input_dim %d", bb->feat, h->input_dim);
+    if (n < 0) return fail(MMC_ERR_ARG, "n = %lld is negative", (long long)n);
+    if (k < 1 || k > h->K) return fail(MMC_ERR_ARG, "k = %d is outside [1, %d] (the head has %d classes)", k, h->K, h->K);
+    if (n == 0) return MMC_OK;
+    if (!patches) return fail(MMC_ERR_ARG, "patches is NULL");
+    if (!idx || !scores) return fail(MMC_ERR_ARG, "idx/scores is NULL");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t want = n < CLASSIFY_CHUNK ? n : CLASSIFY_CHUNK;
+    if (want > h->cls_cap) {   // (hipFree waits for whatever still reads the old buffer)
+        hipFree(h->cls_feats);
+        h->cls_feats = nullptr; h->cls_cap = 0;
+        HIP_TRY(hipMalloc((void**)&h->cls_feats, (size_t)want * h->input_dim * 4 + 256));
+        h->cls_cap = want;
+    }
+    const size_t psz = (size_t)IMG * IMG * 3;
+    const uint8_t* in = static_cast<const uint8_t*>(patches);
+    for (int64_t off = 0; off < n; off += CLASSIFY_CHUNK) {
+        const int64_t cur = (n - off) < CLASSIFY_CHUNK ? (n - off) : CLASSIFY_CHUNK;
+        int r = mmc_backbone_extract(bb, in + (size_t)off * psz, cur, h->cls_feats, flags & MMC_IN_HOST, st);
+        if (r) return r;
+        r = mmc_head_topk(h, h->cls_feats, cur, k, idx + (size_t)off * k, scores + (size_t)off * k, nullptr, flags & MMC_OUT_HOST, st);
+        if (r) return r;
     }
     return MMC_OK;
 }

@@ -159,3 +159,36 @@ def extract_sharded(extract_fn: Callable, patches, group=None):
     lo, hi = shard_range(n_total, rank, world)
     local = extract_fn(patches[lo:hi])
     return gather_features(local, n_total, group=group)
+
+
+def gather_topk(idx_local, scores_local, n_total: int, group=None):
+    """All-gather the ranks' top-k blocks -- ``idx_local`` (n_local, k) int32 and ``scores_local`` (n_local, k) float32 torch
+    tensors for this rank's contiguous ``shard_range`` block -- into (n_total, k) indices and scores in global patch order on
+    every rank.  Labels and scores travel in ONE collective: the score bits viewed as int32 ride next to the indices in an
+    (n_local, 2k) int32 block through ``FeatureGatherer``'s padded single all_gather_into_tensor, so scores come back bit for bit."""
+    import torch
+    if idx_local.dim() != 2 or tuple(idx_local.shape) != tuple(scores_local.shape):
+        raise ValueError(f"expected equal (n_local, k) blocks, got {tuple(idx_local.shape)} and {tuple(scores_local.shape)}")
+    if idx_local.dtype != torch.int32 or scores_local.dtype != torch.float32:
+        raise ValueError(f"expected int32 indices and float32 scores, got {idx_local.dtype} and {scores_local.dtype}")
+    k = idx_local.shape[1]
+    packed = torch.cat([idx_local, scores_local.contiguous().view(torch.int32)], dim=1)
+    full = FeatureGatherer(n_total, 2 * k, packed, group=group).gather(packed)
+    return full[:, :k].contiguous(), full[:, k:].contiguous().view(torch.float32)
+
+
+def classify_sharded(classify_fn: Callable, patches, k: int, group=None):
+    """Each rank classifies its block of `patches` (indexable, length n_total; only the local block is touched) with
+    ``classify_fn(block, k) -> (idx (n_local, k) int32, scores (n_local, k) float32)`` -- e.g. ``PointClassifier.topk_device`` --
+    and gets the gathered (n_total, k) indices and scores back.  ``k`` must not exceed the number of classes (the blocks of
+    all ranks need one width)."""
+    import torch.distributed as dist
+
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    n_total = len(patches)
+    lo, hi = shard_range(n_total, rank, world)
+    idx, scores = classify_fn(patches[lo:hi], k)
+    if idx.shape[1] != k:
+        raise ValueError(f"classify_fn returned {idx.shape[1]} predictions per point, expected k = {k}")
+    return gather_topk(idx, scores, n_total, group=group)

@@ -155,6 +155,41 @@ class DeviceHead:
                                             arg.data_ptr() if want_argmax else None, 0, st))
         return proba, arg
 
+    def topk(self, feats, k: int, want_proba: bool = False):
+        """The k best classes per row (mmc_head_topk): feats as in ``predict``.  Returns (idx (N,k) int32, scores (N,k)
+        float32) of the same kind as ``feats`` -- plus the (N,K) float32 probabilities when ``want_proba`` -- ordered like the
+        reference's ``sorted(zip(labels, proba), key=itemgetter(1), reverse=True)[:k]`` (annotation.py:253-255): score
+        descending, equal scores in class order.  1 <= k <= K."""
+        k = int(k)
+        if not 1 <= k <= self.n_classes:
+            raise ValueError(f"k = {k} is outside [1, {self.n_classes}]")
+        lib = _lib.lib()
+        if isinstance(feats, np.ndarray):
+            x = np.ascontiguousarray(feats, dtype=np.float32)
+            if x.ndim != 2 or x.shape[1] != self.input_dim:
+                raise ValueError(f"features must be (N, {self.input_dim}); got {x.shape}")
+            n = x.shape[0]
+            idx = np.empty((n, k), dtype=np.int32)
+            scores = np.empty((n, k), dtype=np.float32)
+            proba = np.empty((n, self.n_classes), dtype=np.float32) if want_proba else None
+            if n:
+                _lib.check(lib.mmc_head_topk(self._h, x.ctypes.data, n, k, idx.ctypes.data, scores.ctypes.data,
+                                             proba.ctypes.data if want_proba else None,
+                                             _lib.MMC_IN_HOST | _lib.MMC_OUT_HOST, _current_stream_ptr(self.device_index)))
+            return (idx, scores, proba) if want_proba else (idx, scores)
+        import torch
+        x = feats.contiguous()
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.input_dim:
+            raise ValueError(f"features must be a float32 cuda tensor (N, {self.input_dim}); got {tuple(x.shape)}")
+        n = x.shape[0]
+        idx = torch.empty((n, k), dtype=torch.int32, device=x.device)
+        scores = torch.empty((n, k), dtype=torch.float32, device=x.device)
+        proba = torch.empty((n, self.n_classes), dtype=torch.float32, device=x.device) if want_proba else None
+        if n:
+            _lib.check(lib.mmc_head_topk(self._h, x.data_ptr(), n, k, idx.data_ptr(), scores.data_ptr(),
+                                         proba.data_ptr() if want_proba else None, 0, _current_stream_ptr(self.device_index)))
+        return (idx, scores, proba) if want_proba else (idx, scores)
+
 
 class Predictor:
     """A loaded classifier head: feature batch -> calibrated probabilities (loader.py:16-35)."""
@@ -181,6 +216,22 @@ class Predictor:
             raise ValueError(f"features must be (N, {self.input_dim}); got {arr.shape}.")
         _, arg = self._head.predict(arr, want_argmax=True)
         return [self.classes[i] for i in arg.tolist()]
+
+    def predict_topk(self, features: Any, k: int = 1):
+        """The per-point ranking of AnnotationRun (annotation.py:251-261) for a feature batch: (labels, scores) with
+        ``labels[i]`` the ``k' = min(k, K)`` best class names of row i and ``scores`` the float64 ``(N, k')`` calibrated
+        probabilities beside them -- ``sorted(zip(classes, predict_proba(features)[i]), key=itemgetter(1), reverse=True)[:k]``
+        (the slice clamps k the same way), ranked on the device: only N x k' indices and scores come back."""
+        if int(k) != k or k < 1:
+            raise ValueError(f"k must be an integer >= 1; got {k!r}")
+        arr = np.asarray(features, dtype=np.float32)
+        if arr.ndim != 2 or arr.shape[1] != self.input_dim:
+            raise ValueError(f"features must be (N, {self.input_dim}); got {arr.shape}.")
+        kk = min(int(k), len(self.classes))
+        if arr.shape[0] == 0:
+            return [], np.zeros((0, kk), dtype=np.float64)
+        idx, scores = self._head.topk(arr, kk)
+        return [[self.classes[j] for j in row] for row in idx.tolist()], scores.astype(np.float64)
 
 
 def load_predictor(model_pt_path, model_json_path, device="cuda", probe_tol: float = 1e-5) -> Predictor:

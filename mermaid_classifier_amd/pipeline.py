@@ -33,23 +33,41 @@ def check_extract_inputs(image: np.ndarray, rowcols: Sequence[Tuple[int, int]], 
         raise ValueError(f"{name}: image {h}x{w} must exceed the {PATCH}-pixel crop in both dimensions")
 
 
-class BatchedExtractor:
-    """Feeds a ``Backbone`` with cross-image batches.  ``batch_patches`` bounds the device patch buffer."""
+def prepare_image(idx: int, image, rowcols) -> Tuple[np.ndarray, np.ndarray]:
+    """One image and its points as the front-ends take them: grayscale promoted to RGB, contiguous uint8 (H,W,3), points as
+    (n,2) int32, every point checked against the image (``check_extract_inputs``).  Host work only."""
+    im = np.asarray(image)
+    if im.ndim == 2:
+        im = np.stack([im] * 3, axis=-1)
+    if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] < 3:
+        raise ValueError(f"image {idx}: expected uint8 (H,W,3); got {im.dtype} {im.shape}")
+    im = np.ascontiguousarray(im[..., :3])
+    rc = np.ascontiguousarray(np.asarray(list(rowcols), dtype=np.int32).reshape(-1, 2))
+    if len(rc):
+        check_extract_inputs(im, rc, name=f"image {idx}")
+    return im, rc
+
+
+class PatchBatcher:
+    """The buffer / flush machinery of the cross-image front-ends (``BatchedExtractor``: features, ``classify.PointClassifier``:
+    top-k labels): two device patch buffers filled by ``mmc_crop_patches`` on a copy stream, one pass per full buffer on the
+    compute stream, the previous pass's results collected from pinned memory while the next one runs.  A subclass says what a
+    pass is: ``_launch(slot, patches, fill, ctx)`` enqueues the work on the current stream, ``_download(slot, fill, ctx)`` the copy of
+    its results into pinned memory, ``_fetch(slot, count, ctx)`` returns them (a tuple of host arrays with ``count`` rows each) once
+    the pass is done."""
 
     def __init__(self, backbone: Backbone, batch_patches: int = 1024):
         import torch
         self.bb = backbone
         self.cap = int(batch_patches)
+        if self.cap < 1:
+            raise ValueError(f"batch_patches must be >= 1; got {batch_patches}")
         self.dev = torch.device("cuda", backbone.device_index)
         # two patch buffers: while the backbone works through one, the next images are cut / uploaded into the other on a
         # separate copy stream (a buffer is refilled only after the pass that read it has finished: per-buffer event)
         self._bufs = [torch.empty((self.cap, PATCH, PATCH, 3), dtype=torch.uint8, device=self.dev) for _ in range(2)]
         self._free = [torch.cuda.Event(), torch.cuda.Event()]
         self._done = [torch.cuda.Event(), torch.cuda.Event()]
-        self._host = [torch.empty((self.cap, backbone.feature_dim), dtype=torch.float32).pin_memory() for _ in range(2)]
-        # one device feature buffer per slot: a pass sees the same (patches, features) pair every time its slot comes round, so the
-        # library's HIP-graph cache keeps hitting (a fresh output tensor per flush would mint a new combination per pass)
-        self._fdev = [torch.empty((self.cap, backbone.feature_dim), dtype=torch.float32, device=self.dev) for _ in range(2)]
         self._copy_stream = torch.cuda.Stream(device=self.dev)
         self._buf = self._bufs[0]
 
@@ -60,14 +78,25 @@ class BatchedExtractor:
                                                dst.data_ptr(), _lib.MMC_IN_HOST, self.bb.device_index,
                                                int(self._copy_stream.cuda_stream)))
 
-    def extract_images(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]]) -> List[np.ndarray]:
-        """-> one (n_points, 1280) float32 array per image (empty arrays for images without points)."""
+    def _launch(self, slot: int, patches, fill: int, ctx) -> None:
+        raise NotImplementedError
+
+    def _download(self, slot: int, fill: int, ctx) -> None:
+        raise NotImplementedError
+
+    def _fetch(self, slot: int, count: int, ctx) -> tuple:
+        raise NotImplementedError
+
+    def _run(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]], ctx=None):
+        """-> (per image: a tuple of arrays, one per result kind, rows in ``rowcols`` order; None for an image without points,
+        the checked (n, 2) int32 points per image)."""
         import torch
-        out: List[Optional[np.ndarray]] = []
+        out: List[Optional[tuple]] = []
+        points: List[np.ndarray] = []
         pending: List[Tuple[int, int, int]] = []   # (image index, offset in buffer, n)
         fill = 0
         cur = 0                                     # buffer being filled
-        in_flight = None                            # (device features, pending list) of the pass launched last
+        in_flight = None                            # (slot, count, pending list) of the pass launched last
         compute = torch.cuda.current_stream(self.dev)
         self._buf = self._bufs[cur]
         self._copy_stream.wait_stream(compute)      # whatever wrote these buffers before is done before the first cut lands
@@ -75,19 +104,19 @@ class BatchedExtractor:
         def collect(job):
             slot, count, items = job
             self._done[slot].synchronize()                       # this pass's D2H only -- not whatever was enqueued after it
-            feats = self._host[slot][:count].numpy().copy()
+            res = self._fetch(slot, count, ctx)
             for idx, off, n in items:
-                part = feats[off:off + n]
-                out[idx] = part if out[idx] is None else np.concatenate([out[idx], part])
+                part = tuple(a[off:off + n] for a in res)
+                out[idx] = part if out[idx] is None else tuple(np.concatenate([o, q]) for o, q in zip(out[idx], part))
 
         def flush():
             nonlocal fill, pending, cur, in_flight
             if fill == 0:
                 return
             compute.wait_stream(self._copy_stream)              # the cuts of this buffer have landed
-            feats_dev = self.bb.extract(self._bufs[cur][:fill], out=self._fdev[cur][:fill])  # asynchronous on the compute stream
+            self._launch(cur, self._bufs[cur][:fill], fill, ctx)   # asynchronous on the compute stream
             self._free[cur].record(compute)
-            self._host[cur][:fill].copy_(feats_dev, non_blocking=True)   # pinned: the D2H is stream-ordered too
+            self._download(cur, fill, ctx)                       # pinned: the D2H is stream-ordered too
             self._done[cur].record(compute)
             job = (cur, fill, pending)
             if in_flight is not None:
@@ -99,16 +128,9 @@ class BatchedExtractor:
             self._copy_stream.wait_event(self._free[cur])        # refill only after the pass that read this buffer
 
         for idx, (image, rowcols) in enumerate(zip(images, rowcols_per_image)):
-            im = np.asarray(image)
-            if im.ndim == 2:
-                im = np.stack([im] * 3, axis=-1)
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] < 3:
-                raise ValueError(f"image {idx}: expected uint8 (H,W,3); got {im.dtype} {im.shape}")
-            im = np.ascontiguousarray(im[..., :3])
-            rc = np.ascontiguousarray(np.asarray(list(rowcols), dtype=np.int32).reshape(-1, 2))
-            if len(rc):
-                check_extract_inputs(im, rc, name=f"image {idx}")
-            out.append(None if len(rc) else np.zeros((0, self.bb.feature_dim), np.float32))
+            im, rc = prepare_image(idx, image, rowcols)
+            out.append(None)
+            points.append(rc)
             start = 0
             while start < len(rc):                      # an image with more points than the buffer spans flushes
                 take = min(len(rc) - start, self.cap - fill)
@@ -122,7 +144,33 @@ class BatchedExtractor:
         flush()
         if in_flight is not None:
             collect(in_flight)
-        return [o if o is not None else np.zeros((0, self.bb.feature_dim), np.float32) for o in out]
+        return out, points
+
+
+class BatchedExtractor(PatchBatcher):
+    """Feeds a ``Backbone`` with cross-image batches.  ``batch_patches`` bounds the device patch buffer."""
+
+    def __init__(self, backbone: Backbone, batch_patches: int = 1024):
+        import torch
+        super().__init__(backbone, batch_patches)
+        self._host = [torch.empty((self.cap, backbone.feature_dim), dtype=torch.float32).pin_memory() for _ in range(2)]
+        # one device feature buffer per slot: a pass sees the same (patches, features) pair every time its slot comes round, so the
+        # library's HIP-graph cache keeps hitting (a fresh output tensor per flush would mint a new combination per pass)
+        self._fdev = [torch.empty((self.cap, backbone.feature_dim), dtype=torch.float32, device=self.dev) for _ in range(2)]
+
+    def _launch(self, slot, patches, fill, ctx):
+        self.bb.extract(patches, out=self._fdev[slot][:fill])
+
+    def _download(self, slot, fill, ctx):
+        self._host[slot][:fill].copy_(self._fdev[slot][:fill], non_blocking=True)
+
+    def _fetch(self, slot, count, ctx):
+        return (self._host[slot][:count].numpy().copy(),)
+
+    def extract_images(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]]) -> List[np.ndarray]:
+        """-> one (n_points, 1280) float32 array per image (empty arrays for images without points)."""
+        out, _ = self._run(images, rowcols_per_image)
+        return [o[0] if o is not None else np.zeros((0, self.bb.feature_dim), np.float32) for o in out]
 
     def extract_image_features(self, images, rowcols_per_image) -> List[ImageFeatures]:
         rowcols_per_image = [list(rc) for rc in rowcols_per_image]
