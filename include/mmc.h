@@ -240,6 +240,53 @@ int mmc_trainer_evaluate(mmc_trainer* t, const float* X, const int32_t* y, int64
 int mmc_trainer_evaluate_q32(mmc_trainer* t, const float* X, const int32_t* y, int64_t n, int64_t* n_correct,
                              int64_t* sum_log_loss_q32, void* hip_stream);
 
+/* ---- device-resident labelled feature sets: train, evaluate and calibrate without re-uploading a split ---------------------
+ * Replaces: the per-epoch streaming of MermaidTrainer.__call__ (mermaid_classifier/pyspacer/trainer.py:138-168): there
+ *   labels.train.load_data_in_batches(batch_size, random_seed=epoch) (:141-145) re-reads the train split from disk every epoch, and
+ *   _calc_acc_batched (:295-307), _calc_acc_and_log_loss_batched (:309-342) and _calibrate_in_batches (:344-396) re-read ref / val,
+ *   because a CPU box cannot hold N x dim floats (settings.training_batch_size sizes the batches from free RAM).  An MI355X holds a
+ *   production split once (5 KB per row of 288 GB): a set is filled once -- from host rows, or from device rows such as
+ *   mmc_backbone_extract's output, which then never visit the host -- and every later pass, evaluation and calibration reads it in place.
+ * Storage: fp32 rows, row-major, and int32 class indices on the device, with a host mirror of the labels (argument checks, class-weight
+ *   sums).  Capacity grows geometrically with a device-to-device copy; `reserve_rows` > 0 allocates up front and avoids the growth.  A
+ *   failed allocation returns MMC_ERR_NOMEM and leaves the set as it was.
+ * Every call synchronises `hip_stream` before returning.  One caller at a time per handle; a set must outlive the calls that read it. */
+typedef struct mmc_featureset mmc_featureset;
+int     mmc_featureset_create(int dim, int n_classes, int device, int64_t reserve_rows, mmc_featureset** out);
+void    mmc_featureset_destroy(mmc_featureset* fs);
+int64_t mmc_featureset_rows(const mmc_featureset* fs);   /* 0 for NULL */
+int     mmc_featureset_dim(const mmc_featureset* fs);    /* 0 for NULL */
+/* X: n x dim fp32, host (MMC_IN_HOST) or device memory on the set's device; y: n class indices in [0, n_classes), always host */
+int mmc_featureset_append(mmc_featureset* fs, const float* X, const int32_t* y, int64_t n, unsigned flags, void* hip_stream);
+/* rows [first, first+n) back to host buffers (either may be NULL): tests, export, debugging */
+int mmc_featureset_read(mmc_featureset* fs, int64_t first, int64_t n, float* X, int32_t* y, void* hip_stream);
+
+/* mmc_trainer_partial_fit_ordered (one epoch's clf.partial_fit, trainer.py:145) on rows that are resident: position i of the pass
+ * visits row visit[i] of the set (visit == NULL: rows 0..rows-1 in order, n == rows).  The only upload is `visit`, 8 bytes per row.
+ * The visited rows and labels are gathered into the trainer's mini-batch staging in chunks of whole mini-batches, each chunk followed
+ * by its steps on the same stream; the steps launch the kernels of the host-fed pass on the same values, so parameters, Adam moments
+ * and *avg_loss have the bits of mmc_trainer_partial_fit_ordered on the same rows.  Any feature width (16-byte lanes when dim % 4 == 0,
+ * dwords otherwise).  Env MMC_TRAIN_CHUNK_ROWS, read at every call, bounds the chunk: its size is the largest multiple of the
+ * mini-batch size not above the bound, and at least one mini-batch; default MMC_TRAIN_CHUNK_ROWS_DEFAULT rows (84 MB of staging at
+ * 1280 columns).  Results do not depend on it.  A value that is not a positive integer is MMC_ERR_ARG.
+ * Everything is checked before anything is launched -- visit[i] in [0, rows), the set's dim / n_classes / device against the
+ * trainer's, a mini-batch of zero total class weight, the env value -- so a rejected pass leaves parameters, moments and step
+ * count as they were. */
+#define MMC_TRAIN_CHUNK_ROWS_DEFAULT 16384
+int mmc_trainer_partial_fit_set(mmc_trainer* t, mmc_featureset* fs, const int64_t* visit, int64_t n, int batch_size,
+                                double* avg_loss, void* hip_stream);
+/* mmc_trainer_evaluate_q32 (trainer.py:295-342) on rows [first, first+n) of the set: the forward and the labels read the set, the
+ * per-chunk int64 totals add up on the device, and the call makes one 16-byte device-to-host copy and one synchronisation.  The sums
+ * are integers, so they equal the host-fed call's on the same rows for any first / n, and add up exactly over any split.  n is bounded
+ * only by what the int64 total holds: a row adds at most -log(DBL_EPSILON) * 2^32 < 36.05 * 2^32, so MMC_EVALUATE_SET_MAX_ROWS
+ * (< 2^31 / 36.05) rows per call cannot overflow it. */
+#define MMC_EVALUATE_SET_MAX_ROWS 59000000
+int mmc_trainer_evaluate_set_q32(mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n,
+                                 int64_t* n_correct, int64_t* sum_log_loss_q32, void* hip_stream);
+/* mmc_calibrator_add_features (trainer.py:344-396) on rows [first, first+n) of the set: same probabilities, labels copied device to
+ * device, one synchronisation. */
+int mmc_calibrator_add_set(mmc_calibrator* c, mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n, void* hip_stream);
+
 /* ---- multi-GPU: the gather of the sharded path --------------------------------------------------------------------
  * The path shards by patches (contiguous blocks of the row range per rank, weights replicated, no exchange during compute);
  * its one exchange step is the all-gather of the ranks' (n_r, 1280) feature blocks.  Replaces: nothing in the reference's

@@ -8,6 +8,8 @@ from .inference import ManifestError, Predictor, load_predictor, SCHEMA_VERSION,
 from .backbone import Backbone, crop_patches_device, FEATURE_DIM  # noqa: F401
 from .classify import PointClassifier, PointPredictions  # noqa: F401
 from .calibration import CalibratedMLP, ParityError, calibrate, evaluate, export_artifact  # noqa: F401
+from .featureset import FeatureSet  # noqa: F401
+from .training import epoch_loop, train_classifier  # noqa: F401
 
 __all__ = [
     "EfficientNetExtractor", "build_extractor_class", "resolve_device", "verify_device_numerics",
@@ -15,4 +17,5 @@ __all__ = [
     "Backbone", "crop_patches_device", "FEATURE_DIM",
     "PointClassifier", "PointPredictions",
     "CalibratedMLP", "ParityError", "calibrate", "evaluate", "export_artifact",
+    "FeatureSet", "epoch_loop", "train_classifier",
 ]

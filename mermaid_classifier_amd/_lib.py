@@ -26,6 +26,8 @@ SYMBOLS = [
     "mmc_trainer_create", "mmc_trainer_destroy", "mmc_trainer_partial_fit", "mmc_trainer_partial_fit_ordered", "mmc_trainer_get_params", "mmc_trainer_adam_state",
     "mmc_trainer_logits", "mmc_trainer_evaluate", "mmc_trainer_evaluate_q32",
     "mmc_calibrator_create", "mmc_calibrator_destroy", "mmc_calibrator_add_features", "mmc_calibrator_add_scores", "mmc_calibrator_fit",
+    "mmc_featureset_create", "mmc_featureset_destroy", "mmc_featureset_rows", "mmc_featureset_dim", "mmc_featureset_append", "mmc_featureset_read",
+    "mmc_trainer_partial_fit_set", "mmc_trainer_evaluate_set_q32", "mmc_calibrator_add_set",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -125,6 +127,24 @@ def _load() -> C.CDLL:
     lib.mmc_calibrator_add_scores.argtypes = [vp, vp, vp, i64, vp]
     lib.mmc_calibrator_fit.restype = i32
     lib.mmc_calibrator_fit.argtypes = [vp, vp, vp, vp, vp]
+    lib.mmc_featureset_create.restype = i32
+    lib.mmc_featureset_create.argtypes = [i32, i32, i32, i64, C.POINTER(vp)]
+    lib.mmc_featureset_destroy.restype = None
+    lib.mmc_featureset_destroy.argtypes = [vp]
+    lib.mmc_featureset_rows.restype = i64
+    lib.mmc_featureset_rows.argtypes = [vp]
+    lib.mmc_featureset_dim.restype = i32
+    lib.mmc_featureset_dim.argtypes = [vp]
+    lib.mmc_featureset_append.restype = i32
+    lib.mmc_featureset_append.argtypes = [vp, vp, vp, i64, u32, vp]
+    lib.mmc_featureset_read.restype = i32
+    lib.mmc_featureset_read.argtypes = [vp, i64, i64, vp, vp, vp]
+    lib.mmc_trainer_partial_fit_set.restype = i32
+    lib.mmc_trainer_partial_fit_set.argtypes = [vp, vp, vp, i64, i32, C.POINTER(C.c_double), vp]
+    lib.mmc_trainer_evaluate_set_q32.restype = i32
+    lib.mmc_trainer_evaluate_set_q32.argtypes = [vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64), vp]
+    lib.mmc_calibrator_add_set.restype = i32
+    lib.mmc_calibrator_add_set.argtypes = [vp, vp, vp, i64, i64, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

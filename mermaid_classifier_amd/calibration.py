@@ -14,7 +14,9 @@ reference                                              here
 =====================================================  ===================================================================
 
 ``data`` is ``(X, y)`` or an iterable of ``(x, y)`` batches (what ``labels.load_data_in_batches`` yields); labels are mapped
-through ``clf._labels_to_indices``.  Features never sit on the host beyond one batch.  The device side is csrc/calib.hip
+through ``clf._labels_to_indices``.  Features never sit on the host beyond one batch.  ``data`` may also be a ``FeatureSet``
+(featureset.py): the split is then read where it lies on the device (``mmc_trainer_evaluate_set_q32``, ``mmc_calibrator_add_set``),
+with the same results as the host-fed route on the same rows.  The device side is csrc/calib.hip
 (``mmc_trainer_evaluate``, ``mmc_calibrator_*``); the calibrated head is served by the existing ``mmc_head_*`` kernels
 (``inference.DeviceHead``).  No sklearn in the path: ``to_sklearn`` imports it lazily for callers that store the sklearn object.
 
@@ -32,6 +34,7 @@ import numpy as np
 
 from . import _lib
 from .backbone import _current_stream_ptr, _device_index
+from .featureset import FeatureSet
 from .inference import SCHEMA_VERSION, TASK_NAME, DeviceHead, HeadParams, Predictor
 
 __all__ = ["evaluate", "calibrate", "CalibratedMLP", "export_artifact", "build_head_module", "ParityError"]
@@ -78,6 +81,14 @@ def evaluate(clf, data) -> Tuple[float, float]:
     lib = _lib.lib()
     st = _current_stream_ptr(_device_index(clf.device))
     n = correct = loss_q32 = 0
+    if isinstance(data, FeatureSet):
+        data._check_against(clf)
+        n = len(data)
+        if n:
+            nc, q = C.c_int64(0), C.c_int64(0)
+            _lib.check(lib.mmc_trainer_evaluate_set_q32(clf._h, data._handle(), 0, n, C.byref(nc), C.byref(q), st))
+            correct, loss_q32 = int(nc.value), int(q.value)
+        data = ()   # nothing left to stream
     for x, y in _batches(data):
         X, yi = _batch_arrays(clf, x, y)
         nc, q = C.c_int64(0), C.c_int64(0)
@@ -102,6 +113,9 @@ class _Calibrator:
     def add_features(self, clf, X: np.ndarray, y_idx: np.ndarray) -> None:
         _lib.check(_lib.lib().mmc_calibrator_add_features(self._h, clf._h, X.ctypes.data, y_idx.ctypes.data, X.shape[0],
                                                           _current_stream_ptr(self.device_index)))
+
+    def add_set(self, clf, fs: FeatureSet) -> None:
+        _lib.check(_lib.lib().mmc_calibrator_add_set(self._h, clf._h, fs._handle(), 0, len(fs), _current_stream_ptr(self.device_index)))
 
     def add_scores(self, scores, y_idx) -> None:
         S = np.ascontiguousarray(np.asarray(scores, dtype=np.float64))
@@ -215,9 +229,14 @@ def calibrate(clf, data) -> CalibratedMLP:
     K = len(clf.classes_)
     if K < 3:
         raise ValueError(f"calibrate: {K} classes; one Platt sigmoid per class is defined here for K >= 3 only")
+    if isinstance(data, FeatureSet):
+        data._check_against(clf)
     weights, biases = clf.parameters()   # the snapshot (read before the forward passes: the same parameters)
     cal = _Calibrator(K, clf.device)
     try:
+        if isinstance(data, FeatureSet):
+            cal.add_set(clf, data)
+            data = ()   # nothing left to stream
         for x, y in _batches(data):
             X, yi = _batch_arrays(clf, x, y)
             cal.add_features(clf, X, yi)

@@ -176,7 +176,9 @@ __global__ __launch_bounds__(256) void eval_rows_kernel(const float* __restrict_
     }
 }
 
-// out[0..2) = column sums of slab[nb][2] (one workgroup)
+// out[0..2) = column sums of slab[nb][2] (one workgroup).  ACC: out += instead -- the chunks of one call over a resident feature set
+// add up on the device, in stream order, and the host reads the two totals once.
+template <bool ACC>
 __global__ __launch_bounds__(256) void eval_finalize_kernel(const long long* __restrict__ slab, int nb, long long* __restrict__ out)
 {
     __shared__ long long red[256][2];
@@ -189,7 +191,10 @@ __global__ __launch_bounds__(256) void eval_finalize_kernel(const long long* __r
         if (threadIdx.x < o) { red[threadIdx.x][0] += red[threadIdx.x + o][0]; red[threadIdx.x][1] += red[threadIdx.x + o][1]; }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { out[0] = red[0][0]; out[1] = red[0][1]; }
+    if (threadIdx.x == 0) {
+        out[0] = (ACC ? out[0] : 0) + red[0][0];
+        out[1] = (ACC ? out[1] : 0) + red[0][1];
+    }
 }
 
 // grid (K, G): stats[(k G + g) * 2] = { #(y == k), max|F| } over chunk g of class k
@@ -484,6 +489,53 @@ extern "C" int mmc_calibrator_add_features(mmc_calibrator* c, mmc_trainer* t, co
     return MMC_OK;
 }
 
+static int check_set_range(const mmc_featureset* fs, int64_t first, int64_t n)
+{
+    if (first < 0 || n < 0 || first > fs->n || n > fs->n - first)
+        return mmc_fail(MMC_ERR_ARG, "rows [%lld, %lld + %lld) outside the set's %lld rows", (long long)first, (long long)first, (long long)n,
+                        (long long)fs->n);
+    return MMC_OK;
+}
+
+static int check_set_matches(const mmc_featureset* fs, mmc_trainer* t)
+{
+    if (fs->dim != trainer_input_dim(t)) return mmc_fail(MMC_ERR_ARG, "feature set has %d columns, trainer expects %d", fs->dim, trainer_input_dim(t));
+    if (fs->K != trainer_classes(t)) return mmc_fail(MMC_ERR_ARG, "feature set has %d classes, trainer %d", fs->K, trainer_classes(t));
+    if (fs->device != trainer_device(t)) return mmc_fail(MMC_ERR_ARG, "feature set is on device %d, trainer on device %d", fs->device, trainer_device(t));
+    return MMC_OK;
+}
+
+// mmc_calibrator_add_features on rows [first, first + n) of a resident feature set: the forward reads the set, the labels move device to
+// device, and the stream is synchronised once
+extern "C" int mmc_calibrator_add_set(mmc_calibrator* c, mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n, void* hip_stream)
+{
+    if (!c || !t) return mmc_fail(MMC_ERR_ARG, "calibrator/trainer handle is NULL");
+    if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
+    if (trainer_classes(t) != c->K) return mmc_fail(MMC_ERR_ARG, "trainer has K = %d classes, calibrator K = %d", trainer_classes(t), c->K);
+    if (trainer_device(t) != c->device) return mmc_fail(MMC_ERR_ARG, "trainer is on device %d, calibrator on device %d", trainer_device(t), c->device);
+    int r = check_set_matches(fs, t);
+    if (r) return r;
+    r = check_set_range(fs, first, n);
+    if (r) return r;
+    if (n == 0) return MMC_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    C_TRY(hipSetDevice(c->device));
+    r = calib_reserve(c, c->n + n, st);
+    if (r) return r;
+    for (int64_t off = 0; off < n; off += kTrainerForwardRows) {
+        const int cur = (int)((n - off) < kTrainerForwardRows ? (n - off) : kTrainerForwardRows);
+        const float* z = nullptr;
+        r = trainer_forward_device(t, fs->X + (size_t)(first + off) * fs->dim, cur, st, &z);
+        if (r) return r;
+        hipLaunchKernelGGL(softmax_store_kernel, dim3((cur + 63) / 64), dim3(256), 0, st, z, cur, c->K, c->P, c->cap, c->n + off);
+        C_TRY(hipGetLastError());
+    }
+    C_TRY(hipMemcpyAsync(c->y + c->n, fs->y + first, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    C_TRY(hipStreamSynchronize(st));
+    c->n += n;
+    return MMC_OK;
+}
+
 extern "C" int mmc_calibrator_add_scores(mmc_calibrator* c, const double* scores, const int32_t* y, int64_t n, void* hip_stream)
 {
     if (!c) return mmc_fail(MMC_ERR_ARG, "calibrator handle is NULL");
@@ -592,7 +644,7 @@ static int trainer_evaluate(mmc_trainer* t, const float* X, const int32_t* y, in
         if (r) return r;
         C_TRY(hipMemcpyAsync(dy, y + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(eval_rows_kernel, dim3(nb), dim3(256), 0, st, z, dy, cur, K, slab);
-        hipLaunchKernelGGL(eval_finalize_kernel, dim3(1), dim3(256), 0, st, slab, nb, totals);
+        hipLaunchKernelGGL(eval_finalize_kernel<false>, dim3(1), dim3(256), 0, st, slab, nb, totals);
         C_TRY(hipGetLastError());
         C_TRY(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
         C_TRY(hipStreamSynchronize(st));   // before the next chunk reuses the labels / slab
@@ -618,4 +670,50 @@ extern "C" int mmc_trainer_evaluate_q32(mmc_trainer* t, const float* X, const in
                                         int64_t* sum_log_loss_q32, void* hip_stream)
 {
     return trainer_evaluate(t, X, y, n, n_correct, sum_log_loss_q32, hip_stream);
+}
+
+// mmc_trainer_evaluate_q32 on rows [first, first + n) of a resident feature set.  The forward and the labels read the set; every
+// chunk's totals are added on the device; one 16-byte copy and one synchronisation per call.
+extern "C" int mmc_trainer_evaluate_set_q32(mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n, int64_t* n_correct,
+                                            int64_t* sum_log_loss_q32, void* hip_stream)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
+    if (!n_correct || !sum_log_loss_q32) return mmc_fail(MMC_ERR_ARG, "n_correct/sum_log_loss is NULL");
+    *n_correct = 0;
+    *sum_log_loss_q32 = 0;
+    int r = check_set_matches(fs, t);
+    if (r) return r;
+    r = check_set_range(fs, first, n);
+    if (r) return r;
+    // a row adds at most -log(DBL_EPSILON) * 2^32 < 36.05 * 2^32, so the int64 total holds 2^31 / 36.05 > 5.95e7 rows of the largest loss
+    if (n > MMC_EVALUATE_SET_MAX_ROWS)
+        return mmc_fail(MMC_ERR_ARG, "n = %lld rows in one call: split it (at most %lld)", (long long)n, (long long)MMC_EVALUATE_SET_MAX_ROWS);
+    if (n == 0) return MMC_OK;
+    const int K = trainer_classes(t);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    C_TRY(hipSetDevice(trainer_device(t)));
+    const int max_nb = (kTrainerForwardRows + 3) / 4;
+    void* scratch = nullptr;
+    r = trainer_scratch(t, ((size_t)max_nb * 2 + 2) * 8, &scratch);   // slab [max_nb][2] int64, then the two totals
+    if (r) return r;
+    long long* slab = static_cast<long long*>(scratch);
+    long long* totals = slab + 2 * max_nb;
+    C_TRY(hipMemsetAsync(totals, 0, 16, st));
+    for (int64_t off = 0; off < n; off += kTrainerForwardRows) {
+        const int cur = (int)((n - off) < kTrainerForwardRows ? (n - off) : kTrainerForwardRows);
+        const int nb = (cur + 3) / 4;
+        const float* z = nullptr;
+        r = trainer_forward_device(t, fs->X + (size_t)(first + off) * fs->dim, cur, st, &z);
+        if (r) return r;
+        hipLaunchKernelGGL(eval_rows_kernel, dim3(nb), dim3(256), 0, st, z, fs->y + first + off, cur, K, slab);
+        hipLaunchKernelGGL(eval_finalize_kernel<true>, dim3(1), dim3(256), 0, st, slab, nb, totals);
+        C_TRY(hipGetLastError());
+    }
+    long long h[2] = {0, 0};
+    C_TRY(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
+    C_TRY(hipStreamSynchronize(st));
+    *n_correct = h[0];
+    *sum_log_loss_q32 = h[1];
+    return MMC_OK;
 }

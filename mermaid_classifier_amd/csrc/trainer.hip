@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include "../../include/mmc.h"
@@ -212,6 +213,30 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
     (void)n;
 }
 
+// A chunk of a pass over a resident feature set (mmc_trainer_partial_fit_set): Xo[i][:] = Xs[src(i)][:], yo[i] = ys[src(i)] with
+// src(i) = visit[i], or first + i without a visiting order.  One wave per row, four rows per workgroup.  Any width: V4 moves 16-byte
+// lanes (dim % 4 == 0: every row of either matrix then starts on a 16-byte boundary), otherwise dwords.
+template <bool V4>
+__global__ __launch_bounds__(256) void gather_set_rows_kernel(const float* __restrict__ Xs, const int32_t* __restrict__ ys,
+                                                              const int64_t* __restrict__ visit, int64_t first, int rows, int dim,
+                                                              float* __restrict__ Xo, int32_t* __restrict__ yo)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= rows) return;
+    const int64_t src = visit ? visit[i] : first + i;
+    const float* s = Xs + (size_t)src * dim;
+    float* d = Xo + (size_t)i * dim;
+    if (V4) {
+        const float4* s4 = reinterpret_cast<const float4*>(s);
+        float4* d4 = reinterpret_cast<float4*>(d);
+        for (int k = lane; k < dim / 4; k += 64) d4[k] = s4[k];
+    } else {
+        for (int k = lane; k < dim; k += 64) d[k] = s[k];
+    }
+    if (lane == 0) yo[i] = ys[src];
+}
+
 template <bool TA, bool TB>
 int launch_tgemm(const float* A, const float* B, float* C, int M, int N, int K, int epi, const float* aux, float scale, hipStream_t st)
 {
@@ -246,7 +271,8 @@ struct mmc_trainer {
     float* Xn = nullptr;            // natural-order staging of a pass (device-side shuffle)
     int32_t* yn = nullptr;
     int64_t* order = nullptr;
-    int64_t cap_n = 0, cap_nn = 0;
+    int64_t* visit = nullptr;       // visiting order of a pass over a resident feature set
+    int64_t cap_n = 0, cap_nn = 0, cap_visit = 0;
     int cap_mb = 0, cap_steps = 0;
     double lr = 1e-3, beta1 = 0.9, beta2 = 0.999, eps = 1e-8, alpha = 1e-4;   // kept in double: torch derives its fp32 scalars from python floats
     long long t = 0;                                    // Adam step count
@@ -280,7 +306,7 @@ extern "C" void mmc_trainer_destroy(mmc_trainer* t)
     for (size_t l = 1; l < t->H.size(); ++l) hipFree(t->H[l]);
     for (size_t l = 1; l < t->dZ.size(); ++l) hipFree(t->dZ[l]);
     hipFree(t->cw); hipFree(t->X); hipFree(t->row_loss); hipFree(t->partials); hipFree(t->losses); hipFree(t->y);
-    hipFree(t->Xn); hipFree(t->yn); hipFree(t->order); hipFree(t->scratch);
+    hipFree(t->Xn); hipFree(t->yn); hipFree(t->order); hipFree(t->visit); hipFree(t->scratch);
     delete t;
 }
 
@@ -472,6 +498,92 @@ extern "C" int mmc_trainer_partial_fit(mmc_trainer* t, const float* X, const int
     return mmc_trainer_partial_fit_ordered(t, X, y, nullptr, n, batch_size, avg_loss, hip_stream);
 }
 
+// The pass of mmc_trainer_partial_fit_ordered over rows that are already on the device: position i visits row visit[i] of `fs`.
+// Nothing but `visit` is uploaded.  The visited rows and labels are gathered into the mini-batch staging (t->X / t->y) a chunk of whole
+// mini-batches at a time, and that chunk's steps follow on the same stream, so the steps run the kernels of the host-fed pass on the
+// same values: same bits.
+extern "C" int mmc_trainer_partial_fit_set(mmc_trainer* t, mmc_featureset* fs, const int64_t* visit, int64_t n, int batch_size,
+                                           double* avg_loss, void* hip_stream)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
+    if (fs->dim != t->dims[0]) return mmc_fail(MMC_ERR_ARG, "feature set has %d columns, trainer expects %d", fs->dim, t->dims[0]);
+    if (fs->K != t->K) return mmc_fail(MMC_ERR_ARG, "feature set has %d classes, trainer %d", fs->K, t->K);
+    if (fs->device != t->device) return mmc_fail(MMC_ERR_ARG, "feature set is on device %d, trainer on device %d", fs->device, t->device);
+    if (n < 1) return mmc_fail(MMC_ERR_ARG, "n = %lld must be positive", (long long)n);
+    if (batch_size < 1) return mmc_fail(MMC_ERR_ARG, "batch_size = %d must be positive", batch_size);
+    if (!visit && n != fs->n) return mmc_fail(MMC_ERR_ARG, "without a visiting order n must be the set's %lld rows (got %lld)", (long long)fs->n, (long long)n);
+    if (visit)
+        for (int64_t i = 0; i < n; ++i)
+            if (visit[i] < 0 || visit[i] >= fs->n)
+                return mmc_fail(MMC_ERR_ARG, "visit[%lld] = %lld outside [0, %lld)", (long long)i, (long long)visit[i], (long long)fs->n);
+    int64_t bound = MMC_TRAIN_CHUNK_ROWS_DEFAULT;
+    if (const char* env = std::getenv("MMC_TRAIN_CHUNK_ROWS")) {
+        char* end = nullptr;
+        const long long v = std::strtoll(env, &end, 10);
+        if (end == env || *end || v < 1) return mmc_fail(MMC_ERR_ARG, "MMC_TRAIN_CHUNK_ROWS = '%s' is not a positive integer", env);
+        bound = v;
+    }
+    const int mb = (int)(batch_size < n ? batch_size : n);
+    if ((n + mb - 1) / mb > (int64_t)1 << 30) return mmc_fail(MMC_ERR_ARG, "%lld rows in mini-batches of %d: too many steps for one pass", (long long)n, mb);
+    const int steps = (int)((n + mb - 1) / mb);
+    // the largest multiple of the mini-batch not above the bound, at least one mini-batch, and no more than a gather's grid / `rows` hold
+    int64_t chunk = bound / mb * mb;
+    if (chunk < mb) chunk = mb;
+    const int64_t chunk_max = ((int64_t)1 << 30) / mb * mb;
+    if (chunk > chunk_max) chunk = chunk_max;
+    const int64_t steps_per_chunk = chunk / mb;
+    const int64_t stage_rows = chunk < n ? chunk : n;
+    // as in the host-fed pass: every mini-batch's weight sum is checked before anything is uploaded or launched
+    std::vector<double> wsums(steps);
+    const int32_t* yh = fs->y_host.data();
+    for (int s = 0; s < steps; ++s) {
+        const int64_t start = (int64_t)s * mb;
+        const int cur = (int)((n - start) < mb ? (n - start) : mb);
+        double wsum = 0.0;
+        if (t->cw) { for (int i = 0; i < cur; ++i) wsum += t->cw_host[yh[visit ? visit[start + i] : start + i]]; } else wsum = cur;
+        if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "mini-batch %d has zero total class weight", s);
+        wsums[s] = wsum;
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    T_TRY(hipSetDevice(t->device));
+    int r = trainer_reserve(t, stage_rows, mb, steps);
+    if (r) return r;
+    if (visit) {
+        if (n > t->cap_visit) {
+            hipFree(t->visit);
+            t->visit = nullptr; t->cap_visit = 0;
+            T_TRY(hipMalloc((void**)&t->visit, (size_t)n * 8 + 256));
+            t->cap_visit = n;
+        }
+        T_TRY(hipMemcpyAsync(t->visit, visit, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    }
+    std::vector<int> sizes(steps);
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int rows = (int)((n - c0) < chunk ? (n - c0) : chunk);
+        const int64_t* vis = visit ? t->visit + c0 : nullptr;
+        if (fs->dim & 3)
+            hipLaunchKernelGGL(gather_set_rows_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, rows, fs->dim, t->X, t->y);
+        else
+            hipLaunchKernelGGL(gather_set_rows_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, rows, fs->dim, t->X, t->y);
+        T_TRY(hipGetLastError());
+        for (int64_t off = 0; off < rows; off += mb) {
+            const int s = (int)(c0 / chunk * steps_per_chunk + off / mb);
+            const int cur = (int)((rows - off) < mb ? (rows - off) : mb);
+            sizes[s] = cur;
+            r = trainer_step(t, off, cur, (float)(1.0 / wsums[s]), t->losses + s, st);
+            if (r) return r;
+        }
+    }
+    std::vector<float> h(steps);
+    T_TRY(hipMemcpyAsync(h.data(), t->losses, (size_t)steps * 4, hipMemcpyDeviceToHost, st));
+    T_TRY(hipStreamSynchronize(st));
+    double tot = 0.0;
+    for (int s = 0; s < steps; ++s) tot += (double)h[s] * sizes[s];   // torch_classifier.py:293-298: loss.item() * mb_size
+    if (avg_loss) *avg_loss = tot / (double)n;
+    return MMC_OK;
+}
+
 extern "C" int mmc_trainer_get_params(mmc_trainer* t, float* const* W, float* const* b)
 {
     if (!t || !W || !b) return mmc_fail(MMC_ERR_ARG, "NULL argument");
@@ -512,7 +624,16 @@ int trainer_forward(mmc_trainer* t, const float* X, int n, hipStream_t st, const
     int r = trainer_reserve(t, n, n, 1);
     if (r) return r;
     T_TRY(hipMemcpyAsync(t->X, X, (size_t)n * t->dims[0] * 4, hipMemcpyHostToDevice, st));
-    t->H[0] = t->X;
+    return trainer_forward_device(t, t->X, n, st, logits);
+}
+
+int trainer_forward_device(mmc_trainer* t, const float* X_dev, int n, hipStream_t st, const float** logits)
+{
+    if (n < 1 || n > kTrainerForwardRows) return mmc_fail(MMC_ERR_ARG, "trainer_forward: n = %d outside [1, %d]", n, kTrainerForwardRows);
+    T_TRY(hipSetDevice(t->device));
+    int r = trainer_reserve(t, 0, n, 1);   // activations only: the input is read where it lies
+    if (r) return r;
+    t->H[0] = const_cast<float*>(X_dev);
     for (int l = 0; l < t->L; ++l)
         T_K((launch_tgemm<false, true>(t->H[l], t->W[l], t->H[l + 1], n, t->dims[l + 1], t->dims[l],
                                       l == t->L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU, t->b[l], 0.f, st)));

@@ -1,10 +1,22 @@
-// trainer_internal.h -- what calib.hip takes from trainer.hip: the eval-mode forward of a trainer's current parameters.
+// trainer_internal.h -- what calib.hip takes from trainer.hip: the eval-mode forward of a trainer's current parameters; and the
+// device-resident feature set (featureset.hip) that trainer.hip and calib.hip read rows and labels from.
 // Library-internal; not part of the C ABI (include/mmc.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 struct mmc_trainer;
+
+// mmc_featureset_*: n labelled rows resident on one device.  X / y hold `cap` rows; growth is geometric (featureset.hip).
+struct mmc_featureset {
+    int dim = 0, K = 0, device = 0;
+    int64_t n = 0, cap = 0;
+    float* X = nullptr;               // [cap][dim] fp32, row-major
+    int32_t* y = nullptr;             // [cap] class indices
+    std::vector<int32_t> y_host;      // host mirror of y[0..n): argument checks and per-mini-batch class-weight sums
+};
 
 // sets the thread-local message mmc_last_error() returns and hands back `code` (defined in mmc_api.cpp)
 int mmc_fail(int code, const char* fmt, ...);
@@ -23,3 +35,5 @@ int trainer_scratch(mmc_trainer* t, size_t bytes, void** out);
 // Uploads n (1..kTrainerForwardRows) host rows X[n][dims[0]] and runs Linear/ReLU ... Linear on `st` with the exact kernels of
 // a training step's forward; *logits = device [n][K] fp32, valid until the next call on `t` (stream-ordered, no sync).
 int trainer_forward(mmc_trainer* t, const float* X, int n, hipStream_t st, const float** logits);
+// The same on rows that are already on the trainer's device (a feature set's): nothing is uploaded, the first layer reads X.
+int trainer_forward_device(mmc_trainer* t, const float* X_dev, int n, hipStream_t st, const float** logits);

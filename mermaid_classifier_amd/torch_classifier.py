@@ -17,7 +17,8 @@ and error strings included): ``__init__`` (:95-136, the argument validation and 
 ``_forward_probs``.  Written here, with no counterpart there: ``_initial_parameters`` (host Glorot draw handed to the
 device), ``_create_trainer``, the device half of ``partial_fit`` (``mmc_trainer_partial_fit_ordered``), ``_forward_probs``'s
 logits call (``mmc_trainer_logits``), ``parameters`` / ``_module`` / ``_adam_state`` (state read back through the C ABI),
-``__getstate__`` / ``__setstate__`` (the pickle carries host copies of weights and Adam moments), ``_release``.
+``__getstate__`` / ``__setstate__`` (the pickle carries host copies of weights and Adam moments), ``_release``,
+``partial_fit_rows`` (``partial_fit`` over rows of a device-resident ``FeatureSet``: ``mmc_trainer_partial_fit_set``).
 """
 
 from __future__ import annotations
@@ -173,6 +174,52 @@ class TorchMLPClassifier:
             yo = np.ascontiguousarray(y_indices[order].astype(np.int32))
             _lib.check(_lib.lib().mmc_trainer_partial_fit(self._h, Xo.ctypes.data, yo.ctypes.data, n_samples, int(batch_size),
                                                           C.byref(avg), _current_stream_ptr(di)))
+        self.loss_curve_.append(float(avg.value))
+        self.n_iter_ += 1
+        return self
+
+    def partial_fit_rows(self, fs, rows=None, classes: Sequence[Any] | None = None) -> "TorchMLPClassifier":
+        """``partial_fit(X[rows], y[rows], classes)`` for rows that are resident in the ``FeatureSet`` ``fs`` (``rows=None``: every
+        row, in stored order): same first-call initialisation, mini-batch size, shuffle, ``loss_curve_`` / ``n_iter_`` -- and the
+        same bits.  The shuffle is composed with ``rows`` on the host; only the indices are uploaded
+        (``mmc_trainer_partial_fit_set``).  The set's label indices are the classifier's, so ``fs.classes`` must equal
+        ``classes_`` and ``fs.dim`` ``n_features_in_`` (``ValueError``); on a first call without ``classes`` the set's class list
+        is taken (``partial_fit`` would take the labels present in the rows)."""
+        if rows is None:
+            n_samples = len(fs)
+            rows_arr = None
+        else:
+            rows_arr = np.asarray(rows)
+            if rows_arr.ndim != 1 or not (np.issubdtype(rows_arr.dtype, np.integer) or rows_arr.size == 0):
+                raise ValueError(f"rows must be a 1D array of row indices, got {rows_arr.dtype} {rows_arr.shape}")
+            rows_arr = rows_arr.astype(np.int64)
+            n_samples = int(rows_arr.shape[0])
+        if not self._fitted():
+            classes_ = fs.classes if classes is None else np.unique(np.asarray(classes))
+            if not np.array_equal(fs.classes, classes_):
+                raise ValueError(f"the feature set's classes {fs.classes.tolist()} differ from classes_ {classes_.tolist()}")
+            self.classes_ = classes_
+            self.n_features_in_ = int(fs.dim)
+            self.n_iter_ = 0
+            self.loss_curve_ = []
+            self._class_weight_vector = self._build_class_weight_vector()
+            self._create_trainer(*self._initial_parameters())
+        else:
+            fs._check_against(self)
+        if n_samples < 1:
+            raise ValueError("partial_fit_rows: no rows")
+        batch_size = self._resolve_batch_size(n_samples)
+        rng = self._seed_rng()
+        order = np.arange(n_samples)
+        if self.shuffle:
+            rng.shuffle(order)
+        if rows_arr is None and not self.shuffle:
+            visit = None
+        else:
+            visit = np.ascontiguousarray((order if rows_arr is None else rows_arr[order]).astype(np.int64))
+        avg = C.c_double(0.0)
+        _lib.check(_lib.lib().mmc_trainer_partial_fit_set(self._h, fs._handle(), None if visit is None else visit.ctypes.data, n_samples,
+                                                          int(batch_size), C.byref(avg), _current_stream_ptr(_device_index(self.device))))
         self.loss_curve_.append(float(avg.value))
         self.n_iter_ += 1
         return self

@@ -1,0 +1,141 @@
+"""The epoch loop of the reference's ``MermaidTrainer.__call__`` (``mermaid_classifier/pyspacer/trainer.py:83-293``) over splits
+that are resident on the MI355X.
+
+``epoch_loop`` is the host bookkeeping of :128-259 in this project's words -- epochs, early stopping on the validation loss,
+best-snapshot restore, the per-epoch callback and the stop summary -- with the three device steps passed in as callables, so it
+runs (and is tested) without a device.  ``train_classifier`` binds those callables to ``FeatureSet`` splits
+(``TorchMLPClassifier.partial_fit_rows``, ``calibration.evaluate``) and ends, as :261-265 does, with the Platt calibration on the
+ref split.  What follows there -- ``evaluate_classifier`` on val, ``ValResults``, the previous models' accuracies (:267-293) -- is
+not part of this module.
+"""
+
+from __future__ import annotations
+
+import copy
+import time
+from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
+
+import numpy as np
+
+from .calibration import CalibratedMLP, calibrate, evaluate
+from .featureset import FeatureSet
+from .torch_classifier import TorchMLPClassifier
+
+__all__ = ["epoch_loop", "train_classifier"]
+
+
+def epoch_loop(clf, train_epoch: Callable[[Any, int], None], eval_ref: Callable[[Any], float],
+               eval_val: Callable[[Any], Tuple[float, float]], nbr_epochs: int, early_stopping_patience: Optional[int] = None,
+               on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None) -> Tuple[Any, Dict[str, Any]]:
+    """Run up to ``nbr_epochs`` epochs of ``train_epoch(clf, epoch)``, each followed by ``eval_ref(clf) -> accuracy`` and
+    ``eval_val(clf) -> (accuracy, log_loss)``.  -> ``(clf, info)``.
+
+    With ``early_stopping_patience`` set, an epoch whose validation loss is strictly below every earlier one becomes the best
+    epoch and ``copy.deepcopy(clf)`` is kept (a tie or a NaN is no improvement); the loop stops once ``patience`` epochs in a row
+    brought none; and whenever the best epoch is not the last one run -- after an early stop or a used-up budget alike -- the
+    snapshot is what is returned.  With ``None`` no snapshot is ever taken and the classifier of the last epoch is returned.
+
+    ``on_epoch_end`` gets a dict per epoch: ``epoch`` (0-based), ``ref_accuracy``, ``val_accuracy``, ``val_loss``,
+    ``training_loss`` (``clf.loss_curve_[-1]``, or None), ``cumulative_seconds``; on the last epoch run also ``final_epoch``
+    (1-based), ``early_stopped`` and, when a best epoch exists, ``best_val_epoch`` (1-based) / ``best_val_loss``.
+
+    ``info``: ``enabled``, ``patience``, ``stop_reason`` ("early_stopping" or "budget_exhausted"), ``final_epoch``,
+    ``best_val_epoch``, ``best_val_loss`` (None without a best epoch) -- the reference's ``_early_stop_info``."""
+    if int(nbr_epochs) < 1:
+        raise ValueError(f"nbr_epochs must be >= 1, got {nbr_epochs!r}")
+    patience = early_stopping_patience
+    if patience is not None and patience < 1:
+        raise ValueError(f"early_stopping_patience must be >= 1 or None, got {patience!r}")
+    best_loss, best_epoch, best_clf = float("inf"), None, None
+    since_best = 0
+    stop_reason = "budget_exhausted"
+    t0 = time.time()
+    epoch = 0
+    for epoch in range(int(nbr_epochs)):
+        train_epoch(clf, epoch)
+        ref_acc = eval_ref(clf)
+        val_acc, val_loss = eval_val(clf)
+        if patience is not None:
+            if val_loss < best_loss:
+                best_loss, best_epoch, best_clf = val_loss, epoch, copy.deepcopy(clf)
+                since_best = 0
+            else:
+                since_best += 1
+        out_of_patience = patience is not None and since_best >= patience
+        if on_epoch_end is not None:
+            curve = getattr(clf, "loss_curve_", [None])
+            metrics: Dict[str, Any] = {"epoch": epoch, "ref_accuracy": ref_acc, "val_accuracy": val_acc, "val_loss": val_loss,
+                                       "training_loss": curve[-1] if curve else None, "cumulative_seconds": time.time() - t0}
+            if out_of_patience or epoch == nbr_epochs - 1:
+                metrics["final_epoch"] = epoch + 1
+                metrics["early_stopped"] = out_of_patience
+                if best_epoch is not None:
+                    metrics["best_val_epoch"] = best_epoch + 1
+                    metrics["best_val_loss"] = best_loss
+            on_epoch_end(metrics)
+        if out_of_patience:
+            stop_reason = "early_stopping"
+            break
+    if best_clf is not None and best_epoch != epoch:
+        clf = best_clf
+    info = {"enabled": patience is not None, "patience": patience, "stop_reason": stop_reason, "final_epoch": epoch + 1,
+            "best_val_epoch": None if best_epoch is None else best_epoch + 1,
+            "best_val_loss": None if best_epoch is None else best_loss}
+    return clf, info
+
+
+def _contiguous_batches(n_rows: int, batch_size: int) -> Callable[[int], Iterable[np.ndarray]]:
+    def batches(epoch: int):
+        for start in range(0, n_rows, batch_size):
+            yield np.arange(start, min(start + batch_size, n_rows), dtype=np.int64)
+    return batches
+
+
+def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_epochs: int, *, batch_size: int,
+                     class_weight: Optional[dict] = None, early_stopping_patience: Optional[int] = None,
+                     on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None,
+                     batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None,
+                     clf: Optional[TorchMLPClassifier] = None) -> Tuple[CalibratedMLP, Dict[str, Any], List[float]]:
+    """Train, early-stop and calibrate the MLP head on three resident splits.  -> ``(calibrated, info, ref_accs)``:
+    the ``CalibratedMLP`` of the returned classifier on ``ref``, ``epoch_loop``'s ``info``, and the ref accuracy after every
+    epoch run (the reference's ``TrainClassifierReturnMsg.ref_accs``).
+
+    ``clf`` defaults to the production head (trainer.py:118-123): hidden layers (500, 300, 100), ``learning_rate_init=1e-4``,
+    ``random_state=0``, with ``class_weight``; a classifier passed in keeps its own ``class_weight``.  The three sets must share
+    one class list, which is what the first ``partial_fit_rows`` is given.
+
+    Each epoch makes one ``partial_fit_rows(train, rows)`` call per array that ``batches(epoch)`` yields -- one array stands for
+    one batch of ``labels.train.load_data_in_batches(batch_size, random_seed=epoch)`` (:141-145).  The default is contiguous
+    slices of ``batch_size`` rows in stored order, the same every epoch.  pyspacer's shuffle of the images behind that loader is
+    not reproduced here; ``batches`` is the hook for it (any callable ``epoch -> iterable of row-index arrays``).  Within a batch
+    the classifier shuffles as ``partial_fit`` does."""
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size!r}")
+    for name, fs in (("train", train), ("ref", ref), ("val", val)):
+        if not isinstance(fs, FeatureSet):
+            raise ValueError(f"{name} must be a FeatureSet, got {type(fs).__name__}")
+        if not np.array_equal(fs.classes, ref.classes) or fs.dim != ref.dim:
+            raise ValueError(f"the {name} set's classes / width differ from the ref set's")
+        if len(fs) < 1:
+            raise ValueError(f"the {name} set is empty")
+    if clf is None:
+        clf = TorchMLPClassifier(hidden_layer_sizes=(500, 300, 100), learning_rate_init=1e-4, class_weight=class_weight,
+                                 random_state=0, device=ref.device)
+    elif class_weight is not None:
+        raise ValueError("pass class_weight either here or on clf, not both")
+    classes = ref.classes.tolist()
+    if batches is None:
+        batches = _contiguous_batches(len(train), int(batch_size))
+    ref_accs: List[float] = []
+
+    def train_epoch(c, epoch):
+        for rows in batches(epoch):
+            c.partial_fit_rows(train, rows, classes=classes)
+
+    def eval_ref(c):
+        ref_accs.append(evaluate(c, ref)[0])
+        return ref_accs[-1]
+
+    clf, info = epoch_loop(clf, train_epoch, eval_ref, lambda c: evaluate(c, val), nbr_epochs,
+                           early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end)
+    return calibrate(clf, ref), info, ref_accs
