@@ -287,6 +287,46 @@ int mmc_trainer_evaluate_set_q32(mmc_trainer* t, mmc_featureset* fs, int64_t fir
  * device, one synchronisation. */
 int mmc_calibrator_add_set(mmc_calibrator* c, mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n, void* hip_stream);
 
+/* ---- validation of a calibrated head --------------------------------------------------------------------------------
+ * Replaces: what MermaidTrainer.__call__ computes after the calibration (mermaid_classifier/pyspacer/trainer.py:267-293:
+ *   evaluate_classifier on val, ValResults, acc, the previous models' accuracies) and the per-row reductions the metrics make of the
+ *   N x K probability matrix that MetricsCoordinator._precompute_probabilities builds on the host (metrics/coordinator.py:59-76):
+ *   the rank of the true class (_compute_topk_mrr, metrics/ranking.py:42-65) and its clipped probability (the per-sample log-loss,
+ *   metrics/probability.py:43-49).  The probabilities never leave the device and are never written: with v the row's calibrated
+ *   values (the bits of mmc_head_predict: same launches for the Linear layers, same calibration arithmetic) and g its true class,
+ *     est[i]    = the first maximum of v (numpy.argmax);   score[i] = v[est]
+ *     p_true[i] = v[g]
+ *     rank[i]   = the 1-based position of g in numpy.argsort(-v, kind="stable"): score descending and EQUAL SCORES IN CLASS ORDER.
+ *                 The reference's np.argsort(-proba) (ranking.py:55) leaves the order of exactly equal probabilities undefined; the
+ *                 rule here is the one mmc_head_topk and annotation.py:253-255 use.
+ *   and, over the rows of the call, as exact integers that depend on neither row order nor on how rows are split over calls (the
+ *   caller adds the totals of several calls):
+ *     totals[0] rows the call went through       totals[1] rows with est == g
+ *     totals[2] rows of an unknown class         totals[3] rows with a non-finite calibrated value
+ *     totals[4] sum of round(-log(clip((double)p_true, 1e-15, 1.0)) * 2^32): probability.py:49 in 2^-32 fixed point
+ *     confusion[g * K + est] (K x K, or NULL)    rank_hist[rank - 1] (K, or NULL)
+ * y[i] is a class index of the head, or -- with label_map (n_labels entries in [-1, K)) -- an index into label_map, which gives the
+ *   head's class or -1 for a class this head does not know.  An unknown row counts in totals[2] only: it is never correct and is left
+ *   out of confusion, rank_hist and the loss sum; its rank is 0 and its p_true 0.  A row with a NaN (or infinite) calibrated value
+ *   still gets est in [0, K) and rank in [1, K] from the key order, counts in totals[3] and is left out of totals[1], confusion,
+ *   rank_hist and the loss sum.  Its neighbours are unaffected.
+ * feats: n x input_dim fp32, host memory (flags = MMC_IN_HOST) or memory on the head's device.  y, label_map and every output are
+ *   host pointers; est / score / rank / p_true (n each), confusion and rank_hist may each be NULL.  Only 16 bytes per row and the
+ *   integer tables come back.  The call synchronises `hip_stream` before returning.  The _set form reads rows [first, first + n) and
+ *   their labels where they lie; the set's class count must be K, or n_labels when a map is given.
+ * Everything is checked before the first launch: NULL handles, n < 0 (n == 0 is MMC_OK with zeroed totals), y[i] outside [0, K) (or
+ *   [0, n_labels) with a map), map entries outside [-1, K), the set's width / device / class count, first / n outside the set, and
+ *   n > MMC_EVALUATE_SET_MAX_ROWS (a row adds at most -log(1e-15) * 2^32 < 36.05 * 2^32 to the int64 loss total).
+ * Staging for labels, per-row outputs and totals belongs to the head handle, grows on demand and is freed with the handle: a
+ *   repeated call allocates nothing.  One caller at a time per handle. */
+#define MMC_EVAL_TOTALS 5
+int mmc_head_evaluate(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
+                      int32_t* est, float* score, int32_t* rank, float* p_true, int64_t totals[MMC_EVAL_TOTALS],
+                      int64_t* confusion /* K*K or NULL */, int64_t* rank_hist /* K or NULL */, unsigned flags, void* hip_stream);
+int mmc_head_evaluate_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
+                          int32_t* est, float* score, int32_t* rank, float* p_true, int64_t totals[MMC_EVAL_TOTALS],
+                          int64_t* confusion /* K*K or NULL */, int64_t* rank_hist /* K or NULL */, void* hip_stream);
+
 /* ---- multi-GPU: the gather of the sharded path --------------------------------------------------------------------
  * The path shards by patches (contiguous blocks of the row range per rank, weights replicated, no exchange during compute);
  * its one exchange step is the all-gather of the ranks' (n_r, 1280) feature blocks.  Replaces: nothing in the reference's

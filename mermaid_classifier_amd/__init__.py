@@ -9,7 +9,8 @@ from .backbone import Backbone, crop_patches_device, FEATURE_DIM  # noqa: F401
 from .classify import PointClassifier, PointPredictions  # noqa: F401
 from .calibration import CalibratedMLP, ParityError, calibrate, evaluate, export_artifact  # noqa: F401
 from .featureset import FeatureSet  # noqa: F401
-from .training import epoch_loop, train_classifier  # noqa: F401
+from .training import epoch_loop, train_and_validate, train_classifier  # noqa: F401
+from .validation import Validation, previous_accuracies, validate  # noqa: F401
 
 __all__ = [
     "EfficientNetExtractor", "build_extractor_class", "resolve_device", "verify_device_numerics",
@@ -17,5 +18,6 @@ __all__ = [
     "Backbone", "crop_patches_device", "FEATURE_DIM",
     "PointClassifier", "PointPredictions",
     "CalibratedMLP", "ParityError", "calibrate", "evaluate", "export_artifact",
-    "FeatureSet", "epoch_loop", "train_classifier",
+    "FeatureSet", "epoch_loop", "train_classifier", "train_and_validate",
+    "Validation", "validate", "previous_accuracies",
 ]

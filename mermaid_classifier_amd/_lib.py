@@ -15,6 +15,7 @@ LIB_PATH = _HERE / LIB_NAME
 MMC_OK, MMC_ERR_ARG, MMC_ERR_WEIGHTS, MMC_ERR_HIP, MMC_ERR_NOMEM = 0, 1, 2, 3, 4
 MMC_PRECISION_FP8 = 1   # include/mmc.h: flags of mmc_backbone_create_ex
 MMC_IN_HOST, MMC_OUT_HOST = 1, 2
+MMC_EVAL_TOTALS = 5   # include/mmc.h: length of mmc_head_evaluate's totals
 
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
@@ -28,6 +29,7 @@ SYMBOLS = [
     "mmc_calibrator_create", "mmc_calibrator_destroy", "mmc_calibrator_add_features", "mmc_calibrator_add_scores", "mmc_calibrator_fit",
     "mmc_featureset_create", "mmc_featureset_destroy", "mmc_featureset_rows", "mmc_featureset_dim", "mmc_featureset_append", "mmc_featureset_read",
     "mmc_trainer_partial_fit_set", "mmc_trainer_evaluate_set_q32", "mmc_calibrator_add_set",
+    "mmc_head_evaluate", "mmc_head_evaluate_set",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -145,6 +147,10 @@ def _load() -> C.CDLL:
     lib.mmc_trainer_evaluate_set_q32.argtypes = [vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64), vp]
     lib.mmc_calibrator_add_set.restype = i32
     lib.mmc_calibrator_add_set.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.mmc_head_evaluate.restype = i32
+    lib.mmc_head_evaluate.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+    lib.mmc_head_evaluate_set.restype = i32
+    lib.mmc_head_evaluate_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

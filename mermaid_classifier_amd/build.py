@@ -31,7 +31,7 @@ SOURCES = {
     "trainer.hip": ["../../include/mmc.h", "trainer_internal.h", "kernels.h"],
     "calib.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "featureset.hip": ["../../include/mmc.h", "trainer_internal.h"],
-    "mmc_api.cpp": ["kernels.h", "../../include/mmc.h"],
+    "mmc_api.cpp": ["kernels.h", "trainer_internal.h", "../../include/mmc.h"],
     "mmc_dist.cpp": ["../../include/mmc.h"],
 }
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",

@@ -16,6 +16,8 @@
 //   se_gate_kernel     adaptive_avg_pool2d + _se_reduce + swish + _se_expand + sigmoid
 //   mlp_gemm_f32_kernel / calibrate_kernel   CalibratedHead.forward (inference/head.py:66-89)
 //   calibrate_topk_kernel   the same + the per-point sorted(...)[:k] of AnnotationRun (pyspacer/annotation.py:251-261)
+//   calibrate_eval_kernel   the same + per-row est / score / rank / p_true and the integer totals of a validation pass
+//                           (pyspacer/trainer.py:271-291, metrics/ranking.py:54-65, metrics/probability.py:47-49)
 //   crop_kernel        pyspacer crop_patches (reflect pad + slice)
 #include "device_common.h"
 
@@ -1048,6 +1050,114 @@ __global__ __launch_bounds__(256) void calibrate_topk_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
+// calibrate_eval_kernel: the same calibration, then what a validation pass keeps of a row whose true class g is known
+// (mermaid_classifier/pyspacer/trainer.py:271-291, metrics/ranking.py:54-65, metrics/probability.py:47-49):
+//   est    = class of the largest topk_key (the first maximum, as numpy.argmax and the stable sort give it), score = v[est]
+//   p_true = v[g];   rank = 1 + #{c : topk_key(v[c], c) > topk_key(v[g], g)}: the 1-based place of g in argsort(-v, stable)
+// and the totals over the rows: rows seen, correct, unknown (mapped label -1), non-finite, sum of round(-log(clip(p_true, 1e-15,
+// 1)) * 2^32), confusion[g][est], rank_hist[rank - 1].  Every total is an integer added with integer atomics, so it depends on
+// neither the row order nor the grid nor how the rows are split over launches; the caller zeroes them.
+// Rows as in calibrate_topk_kernel (one wave per row, wave-private LDS row or `rowbuf`), but a workgroup walks the rows with the
+// grid's stride and keeps its partial totals on chip: the five counters in lane 0's registers, the rank histogram in LDS
+// (ROW_IN_LDS), flushed with one atomic per touched destination at the end.  confusion goes straight to memory (one atomic per
+// row, spread over the K x K table).  A lane reads only the row entries it wrote; v[g] comes from its owner lane by shuffle.
+// y[row] is the caller's label; with label_map it is label_map[y[row]].  A label outside the table or the head is treated as -1.
+// ---------------------------------------------------------------------------------------------
+template <bool ROW_IN_LDS>
+__global__ __launch_bounds__(256) void calibrate_eval_kernel(const float* __restrict__ logits, int M, int K,
+                                                             const float* __restrict__ a, const float* __restrict__ bcal,
+                                                             const int32_t* __restrict__ y, const int32_t* __restrict__ label_map, int n_labels,
+                                                             int32_t* __restrict__ est_out, float* __restrict__ score_out,   // [M] or NULL
+                                                             int32_t* __restrict__ rank_out, float* __restrict__ ptrue_out,  // [M] or NULL
+                                                             unsigned long long* __restrict__ totals,      // [EVAL_TOTALS]
+                                                             unsigned long long* __restrict__ confusion,   // [K][K] or NULL
+                                                             unsigned long long* __restrict__ rank_hist,   // [K] or NULL
+                                                             float* rowbuf)                                // [M][K] when !ROW_IN_LDS
+{
+    extern __shared__ float eval_lds[];   // ROW_IN_LDS: [4][K] rows, then [K] unsigned rank counts
+    __shared__ unsigned long long red[4][EVAL_TOTALS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned* hist = reinterpret_cast<unsigned*>(eval_lds + (size_t)4 * K);
+    if (ROW_IN_LDS) {
+        for (int c = threadIdx.x; c < K; c += 256) hist[c] = 0;
+        __syncthreads();
+    }
+    unsigned long long tot[EVAL_TOTALS] = {0, 0, 0, 0, 0};   // lane 0's are the wave's
+    for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
+        const float* x = logits + (size_t)row * K;
+        float* r = ROW_IN_LDS ? eval_lds + (size_t)wave * K : rowbuf + (size_t)row * K;
+        float mx, se;
+        calib_softmax_stats(x, K, lane, mx, se);
+        float cs = 0.f;
+        for (int c = lane; c < K; c += 64) {
+            const float v = calib_sigmoid(x[c], mx, se, a[c], bcal[c]);
+            r[c] = v;
+            cs += v;
+        }
+        cs = wave_sum_f(cs);
+        unsigned long long best = 0;
+        bool bad = false;
+        for (int c = lane; c < K; c += 64) {
+            const float v = calib_normalise(r[c], cs, K);
+            r[c] = v;
+            bad |= !(fabsf(v) <= 3.402823466e+38f);   // NaN or infinite
+            const unsigned long long key = topk_key(v, c);
+            best = key > best ? key : best;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_xor(best, o);
+            best = t > best ? t : best;
+        }
+        bad = __ballot(bad) != 0;
+        const int est = (int)(0xFFFFFFFFu - (unsigned)best);
+        int g = y[row];
+        if (label_map) g = (g >= 0 && g < n_labels) ? label_map[g] : -1;
+        if (g < 0 || g >= K) g = -1;
+        int rank = 0;
+        float pt = 0.f;
+        if (g >= 0) {   // (wave-uniform)
+            const int owner = g & 63;
+            pt = __shfl(lane == owner ? r[g] : 0.f, owner);
+            const unsigned long long keyg = topk_key(pt, g);
+            int above = 0;
+            for (int c = lane; c < K; c += 64) above += topk_key(r[c], c) > keyg;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o);
+            rank = 1 + above;
+        }
+        if (lane == 0) {
+            if (est_out) est_out[row] = est;
+            if (score_out) score_out[row] = __uint_as_float((unsigned)(best >> 32));
+            if (rank_out) rank_out[row] = rank;
+            if (ptrue_out) ptrue_out[row] = pt;
+            tot[0] += 1;
+            if (g < 0) tot[2] += 1;
+            else if (bad) tot[3] += 1;
+            else {
+                tot[1] += est == g;
+                tot[4] += (unsigned long long)llrint(-log(fmin(fmax((double)pt, 1e-15), 1.0)) * 4294967296.0);
+                if (confusion) atomicAdd(&confusion[(size_t)g * K + est], 1ull);
+                if (rank_hist) {
+                    if (ROW_IN_LDS) atomicAdd(&hist[rank - 1], 1u);
+                    else atomicAdd(&rank_hist[rank - 1], 1ull);
+                }
+            }
+        }
+    }
+    if (lane == 0)
+        for (int i = 0; i < EVAL_TOTALS; ++i) red[wave][i] = tot[i];
+    __syncthreads();
+    if (threadIdx.x < EVAL_TOTALS) {
+        const unsigned long long s = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+        if (s) atomicAdd(&totals[threadIdx.x], s);
+    }
+    if (ROW_IN_LDS && rank_hist)
+        for (int c = threadIdx.x; c < K; c += 256)
+            if (hist[c]) atomicAdd(&rank_hist[c], (unsigned long long)hist[c]);
+}
+
+// ---------------------------------------------------------------------------------------------
 // crop_patches: reflect-pad + slice as pure index arithmetic on the resident image.
 // numpy 'reflect': index i<0 -> -i ; i>=n -> 2(n-1)-i.  One thread = 4 output pixels (12 bytes).
 // ---------------------------------------------------------------------------------------------
@@ -1253,6 +1363,29 @@ int launch_calibrate_topk(const float* logits, int M, int K, const float* a, con
         if (!rows) return -18;
         hipLaunchKernelGGL((calibrate_topk_kernel<false>), grid, dim3(256), 0, st, logits, M, K, a, b, k, idx, scores,
                            (float*)nullptr, rows);
+    }
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_calibrate_eval(const float* logits, int M, int K, const float* a, const float* b, const int32_t* y, const int32_t* label_map,
+                          int n_labels, int32_t* est, float* score, int32_t* rank, float* p_true, long long* totals, long long* confusion,
+                          long long* rank_hist, float* rowbuf, hipStream_t st)
+{
+    if (M < 1 || K < 1 || !y || !totals || (label_map && n_labels < 1)) return -18;
+    // a workgroup keeps its partial totals on chip while it walks rows: enough workgroups to fill the chip, no more
+    const int nb = (M + 3) / 4;
+    const dim3 grid(nb < 2048 ? nb : 2048);
+    unsigned long long* t = reinterpret_cast<unsigned long long*>(totals);
+    unsigned long long* cf = reinterpret_cast<unsigned long long*>(confusion);
+    unsigned long long* rh = reinterpret_cast<unsigned long long*>(rank_hist);
+    if (K <= TOPK_LDS_MAX_K) {
+        hipLaunchKernelGGL((calibrate_eval_kernel<true>), grid, dim3(256), (size_t)5 * K * sizeof(float), st, logits, M, K, a, b, y, label_map,
+                           n_labels, est, score, rank, p_true, t, cf, rh, (float*)nullptr);
+    } else {
+        if (!rowbuf) return -18;
+        hipLaunchKernelGGL((calibrate_eval_kernel<false>), grid, dim3(256), 0, st, logits, M, K, a, b, y, label_map, n_labels, est, score,
+                           rank, p_true, t, cf, rh, rowbuf);
     }
     LAUNCH_CHECK();
     return 0;

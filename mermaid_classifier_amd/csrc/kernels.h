@@ -229,4 +229,12 @@ int launch_calibrate(const float* logits, int M, int K, const float* a, const fl
 // needed only when K > 2048 and proba is NULL
 int launch_calibrate_topk(const float* logits, int M, int K, const float* a, const float* b, int k, int32_t* idx, float* scores,
                           float* proba, float* rowbuf, hipStream_t st);
+// calibration + per row: best class and its score, rank and probability of the true class y[row] (through label_map when given;
+// -1 = unknown); the four per-row outputs may be NULL.  Adds into totals[EVAL_TOTALS] = {rows, correct, unknown, non-finite,
+// sum of the 2^-32 fixed-point log-loss}, confusion [K][K] and rank_hist [K] (either may be NULL) with integer atomics: the caller
+// zeroes them.  rowbuf: M x K scratch floats, needed only when K > 2048
+constexpr int EVAL_TOTALS = 5;
+int launch_calibrate_eval(const float* logits, int M, int K, const float* a, const float* b, const int32_t* y, const int32_t* label_map,
+                          int n_labels, int32_t* est, float* score, int32_t* rank, float* p_true, long long* totals, long long* confusion,
+                          long long* rank_hist, float* rowbuf, hipStream_t st);
 int launch_crop(const uint8_t* image, int H, int W, const int32_t* rowcols, int n, uint8_t* out, hipStream_t st);

@@ -16,6 +16,7 @@
 
 #include "../../include/mmc.h"
 #include "kernels.h"
+#include "trainer_internal.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -1748,6 +1749,14 @@ struct mmc_head {
     // mmc_classify_patches: the features between backbone and head, grown on demand up to CLASSIFY_CHUNK rows
     float* cls_feats = nullptr;
     int64_t cls_cap = 0;              // rows
+    // mmc_head_evaluate*: one chunk's labels and per-row outputs ([5][eval_rows_cap] dwords), the label map, and the int64
+    // totals / rank histogram / confusion table, each grown on demand
+    int32_t* eval_rows = nullptr;
+    int64_t eval_rows_cap = 0;        // rows
+    int32_t* eval_map = nullptr;
+    int64_t eval_map_cap = 0;         // labels
+    long long* eval_tot = nullptr;
+    int64_t eval_tot_cap = 0;         // int64 elements
 };
 
 extern "C" void mmc_head_destroy(mmc_head* h)
@@ -1759,6 +1768,7 @@ extern "C" void mmc_head_destroy(mmc_head* h)
     hipFree(h->a); hipFree(h->bc); hipFree(h->buf0); hipFree(h->buf1);
     hipFree(h->in_stage); hipFree(h->proba_stage); hipFree(h->arg_stage);
     hipFree(h->topk_idx_stage); hipFree(h->topk_score_stage); hipFree(h->cls_feats);
+    hipFree(h->eval_rows); hipFree(h->eval_map); hipFree(h->eval_tot);
     delete h;
 }
 
@@ -1922,6 +1932,138 @@ extern "C" int mmc_head_topk(mmc_head* h, const float* feats, int64_t n, int k, 
         }
     }
     return MMC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// validation of a calibrated head: mmc_head_evaluate / mmc_head_evaluate_set
+// ------------------------------------------------------------------------------------------
+static_assert(MMC_EVAL_TOTALS == EVAL_TOTALS, "include/mmc.h and kernels.h disagree on the totals");
+static const int64_t HEAD_CHUNK = 65536;   // the chunking of mmc_head_predict: same launches, same bits
+
+template <class T>
+static int eval_grow(T** p, int64_t* cap, int64_t want, size_t elem_bytes)
+{
+    if (want <= *cap) return 0;
+    hipFree(*p);   // (waits for whatever still reads the old buffer)
+    *p = nullptr; *cap = 0;
+    HIP_TRY(hipMalloc((void**)p, (size_t)want * elem_bytes + 256));
+    *cap = want;
+    return 0;
+}
+
+struct EvalOut {
+    int32_t* est; float* score; int32_t* rank; float* p_true;
+    int64_t* totals; int64_t* confusion; int64_t* rank_hist;
+};
+
+static int eval_check_common(const mmc_head* h, int64_t n, const int32_t* label_map, int n_labels, const EvalOut& o)
+{
+    if (n < 0) return fail(MMC_ERR_ARG, "n = %lld is negative", (long long)n);
+    if (!o.totals) return fail(MMC_ERR_ARG, "totals is NULL");
+    // the int64 loss total: a row adds at most -log(1e-15) * 2^32 < 36.05 * 2^32 (see MMC_EVALUATE_SET_MAX_ROWS)
+    if (n > MMC_EVALUATE_SET_MAX_ROWS)
+        return fail(MMC_ERR_ARG, "n = %lld rows in one call: split it (at most %lld)", (long long)n, (long long)MMC_EVALUATE_SET_MAX_ROWS);
+    if (!label_map && n_labels != 0) return fail(MMC_ERR_ARG, "n_labels = %d without a label_map (pass NULL, 0)", n_labels);
+    if (label_map) {
+        if (n_labels < 1) return fail(MMC_ERR_ARG, "n_labels = %d with a label_map: must be positive", n_labels);
+        for (int i = 0; i < n_labels; ++i)
+            if (label_map[i] < -1 || label_map[i] >= h->K)
+                return fail(MMC_ERR_ARG, "label_map[%d] = %d outside [-1, %d)", i, label_map[i], h->K);
+    }
+    return MMC_OK;
+}
+
+// rows X[n][input_dim] (host with MMC_IN_HOST in `flags`, else on the head's device) with labels y_host (uploaded per chunk) or
+// y_dev (read in place); every argument has been checked
+static int head_evaluate(mmc_head* h, const float* X, unsigned flags, const int32_t* y_host, const int32_t* y_dev, int64_t n,
+                         const int32_t* label_map, int n_labels, const EvalOut& o, hipStream_t st)
+{
+    const int K = h->K;
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t rows = n < HEAD_CHUNK ? n : HEAD_CHUNK;
+    const int64_t ntot = EVAL_TOTALS + K + (o.confusion ? (int64_t)K * K : 0);
+    int r;
+    if ((r = eval_grow(&h->eval_rows, &h->eval_rows_cap, rows, 5 * sizeof(int32_t)))) return r;
+    if ((r = eval_grow(&h->eval_tot, &h->eval_tot_cap, ntot, sizeof(long long)))) return r;
+    if (label_map && (r = eval_grow(&h->eval_map, &h->eval_map_cap, n_labels, sizeof(int32_t)))) return r;
+    const int64_t cap = h->eval_rows_cap;
+    int32_t* dy = h->eval_rows;
+    int32_t* dest = o.est ? h->eval_rows + cap : nullptr;
+    float* dscore = o.score ? reinterpret_cast<float*>(h->eval_rows + 2 * cap) : nullptr;
+    int32_t* drank = o.rank ? h->eval_rows + 3 * cap : nullptr;
+    float* dptrue = o.p_true ? reinterpret_cast<float*>(h->eval_rows + 4 * cap) : nullptr;
+    long long* dtot = h->eval_tot;
+    long long* dhist = dtot + EVAL_TOTALS;
+    long long* dconf = o.confusion ? dhist + K : nullptr;
+    HIP_TRY(hipMemsetAsync(dtot, 0, (size_t)ntot * sizeof(long long), st));
+    if (label_map) HIP_TRY(hipMemcpyAsync(h->eval_map, label_map, (size_t)n_labels * 4, hipMemcpyHostToDevice, st));
+    for (int64_t off = 0; off < n; off += HEAD_CHUNK) {
+        const int cur = (int)((n - off) < HEAD_CHUNK ? (n - off) : HEAD_CHUNK);
+        if ((r = head_reserve(h, cur))) return r;
+        const float* logits = nullptr;
+        if ((r = head_logits(h, X + (size_t)off * h->input_dim, cur, flags, st, &logits))) return r;
+        const int32_t* yc = y_dev ? y_dev + off : dy;
+        if (!y_dev) HIP_TRY(hipMemcpyAsync(dy, y_host + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
+        KTRY(launch_calibrate_eval(logits, cur, K, h->a, h->bc, yc, label_map ? h->eval_map : nullptr, n_labels, dest, dscore, drank, dptrue,
+                                   dtot, dconf, dhist, h->proba_stage, st));
+        // stream order keeps the next chunk's kernel behind these copies
+        if (o.est) HIP_TRY(hipMemcpyAsync(o.est + off, dest, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
+        if (o.score) HIP_TRY(hipMemcpyAsync(o.score + off, dscore, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
+        if (o.rank) HIP_TRY(hipMemcpyAsync(o.rank + off, drank, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
+        if (o.p_true) HIP_TRY(hipMemcpyAsync(o.p_true + off, dptrue, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(o.totals, dtot, EVAL_TOTALS * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (o.rank_hist) HIP_TRY(hipMemcpyAsync(o.rank_hist, dhist, (size_t)K * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (o.confusion) HIP_TRY(hipMemcpyAsync(o.confusion, dconf, (size_t)K * K * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MMC_OK;
+}
+
+static void eval_clear(const mmc_head* h, const EvalOut& o)
+{
+    if (o.totals) memset(o.totals, 0, EVAL_TOTALS * sizeof(int64_t));
+    if (h && o.rank_hist) memset(o.rank_hist, 0, (size_t)h->K * sizeof(int64_t));
+    if (h && o.confusion) memset(o.confusion, 0, (size_t)h->K * h->K * sizeof(int64_t));
+}
+
+extern "C" int mmc_head_evaluate(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
+                                 int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
+                                 int64_t* rank_hist, unsigned flags, void* hip_stream)
+{
+    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
+    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
+    int r = eval_check_common(h, n, label_map, n_labels, o);
+    if (r) return r;
+    eval_clear(h, o);
+    if (n == 0) return MMC_OK;
+    if (!feats || !y) return fail(MMC_ERR_ARG, "feats/y is NULL");
+    const int hi = label_map ? n_labels : h->K;
+    for (int64_t i = 0; i < n; ++i)
+        if (y[i] < 0 || y[i] >= hi) return fail(MMC_ERR_ARG, "label index y[%lld] = %d outside [0, %d)", (long long)i, y[i], hi);
+    return head_evaluate(h, feats, flags & MMC_IN_HOST, y, nullptr, n, label_map, n_labels, o, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int mmc_head_evaluate_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
+                                     int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
+                                     int64_t* rank_hist, void* hip_stream)
+{
+    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
+    if (!fs) return fail(MMC_ERR_ARG, "feature set handle is NULL");
+    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
+    if (fs->dim != h->input_dim) return fail(MMC_ERR_ARG, "feature set has %d columns, head expects %d", fs->dim, h->input_dim);
+    if (fs->device != h->device) return fail(MMC_ERR_ARG, "feature set is on device %d, head on device %d", fs->device, h->device);
+    if (first < 0 || n < 0 || first > fs->n || n > fs->n - first)
+        return fail(MMC_ERR_ARG, "rows [%lld, %lld + %lld) outside the set's %lld rows", (long long)first, (long long)first, (long long)n,
+                    (long long)fs->n);
+    int r = eval_check_common(h, n, label_map, n_labels, o);
+    if (r) return r;
+    // the set's labels lie in [0, fs->K): that range must be the head's classes, or the map's domain
+    if (label_map ? fs->K != n_labels : fs->K != h->K)
+        return fail(MMC_ERR_ARG, "feature set has %d classes, %s %d", fs->K, label_map ? "label_map covers" : "head", label_map ? n_labels : h->K);
+    eval_clear(h, o);
+    if (n == 0) return MMC_OK;
+    return head_evaluate(h, fs->X + (size_t)first * fs->dim, 0u, nullptr, fs->y + first, n, label_map, n_labels, o,
+                         static_cast<hipStream_t>(hip_stream));
 }
 
 // rows of features mmc_classify_patches keeps between backbone and head: a larger call works through chunks of exactly this size

@@ -1,4 +1,4 @@
-"""Minimal stand-ins for the few pyspacer types the extractor contract touches, used only
+"""Minimal stand-ins for the few pyspacer types the extractor and trainer contracts touch, used only
 when the real ``spacer`` package is not importable (it is absent offline).
 With pyspacer installed, ``extractor.build_extractor_class()`` subclasses the real
 ``spacer.extractors.EfficientNetExtractor`` instead and none of this is used.
@@ -103,6 +103,31 @@ class ImageFeatures:
 @dataclass
 class ExtractFeaturesReturnMsg:
     extractor_loaded_remotely: bool
+    runtime: float
+
+
+@dataclass
+class ValResults:
+    """``spacer.data_classes.ValResults`` as the reference fills it (mermaid_classifier/pyspacer/trainer.py:279-284): per validation
+    row the score of the estimated class and the indices of the true and the estimated class in ``classes``."""
+    scores: List[float]
+    gt: List[int]
+    est: List[int]
+    classes: List
+
+    def __post_init__(self):
+        if not (len(self.scores) == len(self.gt) == len(self.est)):
+            raise ValueError("scores, gt and est must have one entry per row")
+        if self.gt and not (0 <= min(self.gt + self.est) and max(self.gt + self.est) < len(self.classes)):
+            raise ValueError("gt / est must index into classes")
+
+
+@dataclass
+class TrainClassifierReturnMsg:
+    """``spacer.messages.TrainClassifierReturnMsg`` (trainer.py:286-291)."""
+    acc: float
+    pc_accs: List[float]
+    ref_accs: List[float]
     runtime: float
 
 

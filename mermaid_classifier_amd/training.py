@@ -5,23 +5,24 @@ that are resident on the MI355X.
 best-snapshot restore, the per-epoch callback and the stop summary -- with the three device steps passed in as callables, so it
 runs (and is tested) without a device.  ``train_classifier`` binds those callables to ``FeatureSet`` splits
 (``TorchMLPClassifier.partial_fit_rows``, ``calibration.evaluate``) and ends, as :261-265 does, with the Platt calibration on the
-ref split.  What follows there -- ``evaluate_classifier`` on val, ``ValResults``, the previous models' accuracies (:267-293) -- is
-not part of this module.
+ref split.  ``train_and_validate`` adds what follows there (:267-293) -- ``evaluate_classifier`` on val, ``ValResults``, the
+previous models' accuracies -- through ``validation.validate``, and returns the reference's triple.
 """
 
 from __future__ import annotations
 
 import copy
 import time
-from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
+from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .calibration import CalibratedMLP, calibrate, evaluate
 from .featureset import FeatureSet
 from .torch_classifier import TorchMLPClassifier
+from .validation import previous_accuracies, validate
 
-__all__ = ["epoch_loop", "train_classifier"]
+__all__ = ["epoch_loop", "train_classifier", "train_and_validate"]
 
 
 def epoch_loop(clf, train_epoch: Callable[[Any, int], None], eval_ref: Callable[[Any], float],
@@ -139,3 +140,23 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
     clf, info = epoch_loop(clf, train_epoch, eval_ref, lambda c: evaluate(c, val), nbr_epochs,
                            early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end)
     return calibrate(clf, ref), info, ref_accs
+
+
+def train_and_validate(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_epochs: int, *, batch_size: int,
+                       pc_models: Sequence[Any] = (), **kwargs):
+    """``MermaidTrainer.__call__`` to its end (trainer.py:83-293) on three resident splits.  -> ``(calibrated, val_results,
+    return_msg)``: ``train_classifier``'s ``CalibratedMLP`` (which takes ``kwargs``), the ``ValResults`` of that model on ``val``
+    (``Validation.val_results``) and a ``TrainClassifierReturnMsg`` with ``acc`` (the validation accuracy), ``pc_accs`` (the
+    accuracy of every model in ``pc_models`` -- ``Predictor`` or ``CalibratedMLP`` -- on ``val``), ``ref_accs`` (one entry per
+    epoch run) and ``runtime`` in seconds.  pyspacer's message classes are used when importable, ``spacer_shim``'s otherwise.
+    The validation rows are scored where they lie (``validation.validate``)."""
+    t0 = time.time()
+    calibrated, _info, ref_accs = train_classifier(train, ref, val, nbr_epochs, batch_size=batch_size, **kwargs)
+    scored = validate(calibrated, val)
+    pc_accs = previous_accuracies(pc_models, val)
+    try:
+        from spacer.messages import TrainClassifierReturnMsg  # type: ignore
+    except ImportError:
+        from .spacer_shim import TrainClassifierReturnMsg
+    msg = TrainClassifierReturnMsg(acc=scored.accuracy, pc_accs=pc_accs, ref_accs=ref_accs, runtime=time.time() - t0)
+    return calibrated, scored.val_results(), msg

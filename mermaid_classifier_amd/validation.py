@@ -1,0 +1,276 @@
+"""Score a validation split with a calibrated head on the MI355X: what ``MermaidTrainer.__call__`` computes after the calibration
+(``mermaid_classifier/pyspacer/trainer.py:267-293``) and the per-row reductions of the reference's metrics.
+
+=====================================================  ===================================================================
+reference                                              here
+=====================================================  ===================================================================
+``evaluate_classifier(clf_calibrated, labels.val)``    ``validate(model, data)`` -> ``Validation`` (``est``, ``scores``, ``gt``)
+``ValResults(scores, gt, est, classes)`` (:279-284)    ``Validation.val_results()``
+``accuracy_score(val_gts, val_ests)`` (:287)           ``Validation.accuracy``
+the previous models' accuracies (:273-277)             ``previous_accuracies(pc_models, val)``
+``_compute_topk_mrr`` (metrics/ranking.py:42-65)       ``Validation.topk_accuracy(k)``, ``Validation.mrr`` (from ``rank_hist``)
+per-sample log-loss (metrics/probability.py:43-49)     ``Validation.log_loss`` (from ``nll_q32``), ``Validation.p_true``
+=====================================================  ===================================================================
+
+The reference builds the N x K probability matrix on the host (``metrics/coordinator.py:59-76``) and reduces it to one rank and
+one probability per row.  Here ``calibrate_eval_kernel`` (``mmc_head_evaluate`` / ``mmc_head_evaluate_set``) ends every row in its
+label, its score, the rank and the probability of its true class and adds the totals as integers: the matrix is never written, and
+16 bytes per row plus the integer tables come back.  A ``FeatureSet`` is read where it lies on the device.
+
+Equal probabilities rank in class order (the rule of ``Predictor.predict_topk``); the reference's ``np.argsort(-proba)`` leaves
+that order undefined.  No CPU fallback."""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, List, Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+from .backbone import _current_stream_ptr
+from .calibration import CalibratedMLP, _batches
+from .featureset import FeatureSet
+from .inference import Predictor
+
+__all__ = ["Validation", "validate", "previous_accuracies", "label_map"]
+
+MAX_ROWS_PER_CALL = 59000000   # include/mmc.h MMC_EVALUATE_SET_MAX_ROWS
+
+
+def label_map(model_classes: Sequence[Any], data_classes: Sequence[Any]) -> np.ndarray:
+    """-> int32 ``m`` with ``m[j]`` the position of ``data_classes[j]`` in ``model_classes``, or -1 for a class the model lacks."""
+    where = {c: i for i, c in enumerate(np.asarray(model_classes).tolist())}
+    if len(where) != len(model_classes):
+        raise ValueError("the model's class list holds duplicates")
+    return np.asarray([where.get(c, -1) for c in np.asarray(data_classes).tolist()], dtype=np.int32)
+
+
+class Validation:
+    """The outcome of ``validate``.  Per row (``None`` when ``validate(..., rows=False)``): ``gt`` / ``est`` (indices into
+    ``classes``; ``gt`` is -1 for a class the model lacks), ``scores`` (float64, the probability of ``est``), ``ranks`` (1-based
+    rank of the true class, 0 for an unknown one), ``p_true`` (float32, its probability).  Totals, exact integers: ``n``,
+    ``n_correct``, ``n_unknown``, ``n_nonfinite`` (rows whose probabilities hold a NaN: kept out of everything below),
+    ``confusion[gt, est]``, ``rank_hist[rank - 1]`` and ``nll_q32`` = sum of round(-log(clip(p_true, 1e-15, 1)) * 2^32)."""
+
+    def __init__(self, classes, gt, est, scores, ranks, p_true, confusion, rank_hist, n, n_correct, n_unknown, n_nonfinite, nll_q32):
+        self.classes = np.asarray(classes).tolist()
+        K = len(self.classes)
+        rows = (gt, est, scores, ranks, p_true)
+        if any(v is None for v in rows) and not all(v is None for v in rows):
+            raise ValueError("per-row values must be given all or none")
+        self.gt = None if gt is None else np.asarray(gt, dtype=np.int32)
+        self.est = None if est is None else np.asarray(est, dtype=np.int32)
+        self.scores = None if scores is None else np.asarray(scores, dtype=np.float64)
+        self.ranks = None if ranks is None else np.asarray(ranks, dtype=np.int32)
+        self.p_true = None if p_true is None else np.asarray(p_true, dtype=np.float32)
+        self.confusion = np.asarray(confusion, dtype=np.int64)
+        self.rank_hist = np.asarray(rank_hist, dtype=np.int64)
+        self.n, self.n_correct, self.n_unknown = int(n), int(n_correct), int(n_unknown)
+        self.n_nonfinite, self.nll_q32 = int(n_nonfinite), int(nll_q32)
+        if self.confusion.shape != (K, K) or self.rank_hist.shape != (K,):
+            raise ValueError(f"confusion {self.confusion.shape} / rank_hist {self.rank_hist.shape} do not fit {K} classes")
+        if self.gt is not None and any(v.shape != (self.n,) for v in (self.gt, self.est, self.scores, self.ranks, self.p_true)):
+            raise ValueError(f"per-row values must have shape ({self.n},)")
+
+    @property
+    def has_rows(self) -> bool:
+        return self.gt is not None
+
+    @property
+    def n_scored(self) -> int:
+        """Rows that entered ``confusion``, ``rank_hist`` and the loss sum."""
+        return self.n - self.n_unknown - self.n_nonfinite
+
+    @property
+    def accuracy(self) -> float:
+        """``n_correct / n``: a row of a class the model lacks counts as wrong, as the reference's comparison of label strings
+        counts it."""
+        return self.n_correct / self.n if self.n else float("nan")
+
+    @property
+    def log_loss(self) -> float:
+        """Mean of -log(clip(p_true, 1e-15, 1)) over the scored rows (probability.py:49): one int / int division."""
+        return self.nll_q32 / (self.n_scored << 32) if self.n_scored else float("nan")
+
+    def topk_accuracy(self, k: int) -> float:
+        """``np.mean(ranks <= k)`` (ranking.py:63) from the histogram; rows outside it (unknown, non-finite) count as misses."""
+        if int(k) != k or k < 1:
+            raise ValueError(f"k must be an integer >= 1; got {k!r}")
+        return int(self.rank_hist[: int(k)].sum()) / self.n if self.n else float("nan")
+
+    @property
+    def mrr(self) -> float:
+        """``np.mean(1 / ranks)`` (ranking.py:64) from the histogram."""
+        if not self.n:
+            return float("nan")
+        return float((self.rank_hist / np.arange(1, len(self.rank_hist) + 1, dtype=np.float64)).sum() / self.n)
+
+    def merge(self, other: "Validation") -> "Validation":
+        """The validation of this one's rows followed by ``other``'s: integer adds and row concatenation."""
+        if self.classes != other.classes:
+            raise ValueError("merge: the class lists differ")
+        if self.has_rows != other.has_rows:
+            raise ValueError("merge: one side has per-row values, the other has none")
+        cat = (lambda a, b: np.concatenate([a, b])) if self.has_rows else (lambda a, b: None)
+        return Validation(self.classes, cat(self.gt, other.gt), cat(self.est, other.est), cat(self.scores, other.scores),
+                          cat(self.ranks, other.ranks), cat(self.p_true, other.p_true), self.confusion + other.confusion,
+                          self.rank_hist + other.rank_hist, self.n + other.n, self.n_correct + other.n_correct,
+                          self.n_unknown + other.n_unknown, self.n_nonfinite + other.n_nonfinite, self.nll_q32 + other.nll_q32)
+
+    def val_results(self):
+        """-> ``ValResults(scores, gt, est, classes)`` of plain Python lists (trainer.py:279-284): pyspacer's class when it is
+        importable, ``spacer_shim.ValResults`` otherwise."""
+        if not self.has_rows:
+            raise ValueError("val_results needs the per-row values: validate(..., rows=True)")
+        if self.n_unknown:
+            raise ValueError(f"{self.n_unknown} rows carry a class the model lacks: ValResults indexes gt into the model's classes "
+                             "(the reference's classes.index raises there too)")
+        try:
+            from spacer.data_classes import ValResults  # type: ignore
+        except ImportError:
+            from .spacer_shim import ValResults
+        return ValResults(scores=self.scores.tolist(), gt=self.gt.tolist(), est=self.est.tolist(), classes=list(self.classes))
+
+
+def _model_parts(model):
+    """-> (DeviceHead or None until needed, class list, input width)."""
+    if isinstance(model, CalibratedMLP):
+        return model._device_head, model.classes_.tolist(), model.n_features_in_
+    if isinstance(model, Predictor):
+        return (lambda: model._head), list(model.classes), int(model.input_dim)
+    raise ValueError(f"model must be a CalibratedMLP or a Predictor, got {type(model).__name__}")
+
+
+def _host_labels(classes: List[Any], y, n: int, strict: bool):
+    """Host labels -> (y int32, map or None): indices into the model's classes; when some label is unknown to the model (and that is
+    allowed) indices into the K + 1 entry map [0 .. K-1, -1]."""
+    y = np.asarray(y)
+    if y.shape != (n,):
+        raise ValueError(f"y has shape {y.shape}, expected ({n},)")
+    uniq, inv = np.unique(y, return_inverse=True)
+    idx = label_map(classes, uniq)[inv.reshape(-1)] if n else np.zeros(0, np.int32)
+    if np.all(idx >= 0):
+        return np.ascontiguousarray(idx, dtype=np.int32), None
+    if strict:
+        bad = sorted(set(uniq[label_map(classes, uniq) < 0].tolist()))
+        raise ValueError(f"Labels {bad} are not in the model's classes {classes}.")
+    K = len(classes)
+    return (np.ascontiguousarray(np.where(idx < 0, K, idx), dtype=np.int32),
+            np.ascontiguousarray(np.append(np.arange(K, dtype=np.int32), np.int32(-1))))
+
+
+class _Acc:
+    """Collects the outputs of the calls of one ``validate``."""
+
+    def __init__(self, K: int, rows: bool):
+        self.K, self.rows = K, rows
+        self.totals = np.zeros(_lib.MMC_EVAL_TOTALS, np.int64)
+        self.confusion = np.zeros((K, K), np.int64)
+        self.rank_hist = np.zeros(K, np.int64)
+        self.parts: List[tuple] = []
+
+    def buffers(self, n: int):
+        tot = np.zeros(_lib.MMC_EVAL_TOTALS, np.int64)
+        conf = np.zeros((self.K, self.K), np.int64)
+        hist = np.zeros(self.K, np.int64)
+        per_row = (np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.float32)) if self.rows else None
+        return tot, conf, hist, per_row
+
+    def add(self, gt, tot, conf, hist, per_row):
+        self.totals += tot
+        self.confusion += conf
+        self.rank_hist += hist
+        if self.rows:
+            self.parts.append((gt,) + per_row)
+
+    def result(self, classes) -> Validation:
+        t = self.totals.tolist()
+        if self.rows:
+            gt, est, score, rank, p_true = (np.concatenate([p[i] for p in self.parts]) for i in range(5))
+        else:
+            gt = est = score = rank = p_true = None
+        return Validation(classes, gt, est, None if score is None else score.astype(np.float64), rank, p_true, self.confusion,
+                          self.rank_hist, t[0], t[1], t[2], t[3], t[4])
+
+
+def _ptr(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data
+
+
+def _validate(model, data, rows: bool, strict: bool) -> Validation:
+    if not isinstance(rows, bool):
+        raise ValueError(f"rows must be True or False, got {rows!r}")
+    get_head, classes, dim = _model_parts(model)
+    K = len(classes)
+    acc = _Acc(K, rows)
+    if isinstance(data, FeatureSet):
+        if data.dim != dim:
+            raise ValueError(f"the feature set has {data.dim} features, expected {dim}")
+        n = len(data)
+        if n == 0:
+            raise ValueError("validate: no rows")
+        same = data.classes.tolist() == classes
+        lmap = None if same else np.ascontiguousarray(label_map(classes, data.classes))
+        head = get_head()
+        lib = _lib.lib()
+        st = _current_stream_ptr(head.device_index)
+        for first in range(0, n, MAX_ROWS_PER_CALL):
+            cur = min(MAX_ROWS_PER_CALL, n - first)
+            tot, conf, hist, per_row = acc.buffers(cur)
+            est, score, rank, p_true = per_row if rows else (None,) * 4
+            _lib.check(lib.mmc_head_evaluate_set(head._h, data._handle(), first, cur, _ptr(lmap), 0 if lmap is None else len(lmap),
+                                                 _ptr(est), _ptr(score), _ptr(rank), _ptr(p_true), tot.ctypes.data, conf.ctypes.data,
+                                                 hist.ctypes.data, st))
+            gt = None
+            if rows:   # the labels alone come back (no feature row does)
+                yi = np.empty(cur, np.int32)
+                _lib.check(lib.mmc_featureset_read(data._handle(), first, cur, None, yi.ctypes.data, st))
+                gt = yi if lmap is None else lmap[yi]
+            acc.add(gt, tot, conf, hist, per_row)
+        return acc.result(classes)
+    # host batches: every argument of every batch is checked before the first reaches the device
+    batches = []
+    for x, y in _batches(data):
+        X = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+        if X.ndim != 2:
+            raise ValueError(f"X must be 2D, got shape {X.shape}")
+        if X.shape[1] != dim:
+            raise ValueError(f"X has {X.shape[1]} features, expected {dim}")
+        yi, lmap = _host_labels(classes, y, X.shape[0], strict)
+        if X.shape[0]:
+            batches.append((X, yi, lmap))
+    if not batches:
+        raise ValueError("validate: no rows")
+    head = get_head()
+    lib = _lib.lib()
+    st = _current_stream_ptr(head.device_index)
+    for X, yi, lmap in batches:
+        for first in range(0, X.shape[0], MAX_ROWS_PER_CALL):
+            cur = min(MAX_ROWS_PER_CALL, X.shape[0] - first)
+            tot, conf, hist, per_row = acc.buffers(cur)
+            est, score, rank, p_true = per_row if rows else (None,) * 4
+            ys = yi[first:first + cur]
+            _lib.check(lib.mmc_head_evaluate(head._h, X[first:first + cur].ctypes.data, ys.ctypes.data, cur, _ptr(lmap),
+                                             0 if lmap is None else len(lmap), _ptr(est), _ptr(score), _ptr(rank), _ptr(p_true),
+                                             tot.ctypes.data, conf.ctypes.data, hist.ctypes.data, _lib.MMC_IN_HOST, st))
+            acc.add(ys if lmap is None else lmap[ys], tot, conf, hist, per_row)
+    return acc.result(classes)
+
+
+def validate(model, data, *, rows: bool = True) -> Validation:
+    """Score every row of ``data`` with ``model`` (a ``CalibratedMLP`` or a ``Predictor``) on the device.  ``data`` is a
+    ``FeatureSet`` (read in place), an ``(X, y)`` pair or an iterable of such batches (the forms ``calibration.evaluate`` takes);
+    ``y`` are class labels.  A ``FeatureSet`` whose class list differs from the model's goes through a label map built on the
+    host, and a class the model lacks maps to -1 (``Validation.n_unknown``); a label of a host batch that is not among the model's
+    classes is a ``ValueError``.  ``rows=False`` asks for the totals only: nothing per row is computed into host memory."""
+    return _validate(model, data, rows, strict=True)
+
+
+def previous_accuracies(pc_models, val) -> List[float]:
+    """``[accuracy_score(gts, ests)]`` of every earlier model on the validation data (trainer.py:273-277).  Each model has its own
+    class list: the labels go through a map built per model, and a row whose class a model lacks counts as wrong for it, as the
+    reference's comparison of label strings does.  Totals only."""
+    if not isinstance(val, (FeatureSet, tuple, list)):
+        val = list(val)   # an iterator of batches is walked once per model
+    return [_validate(m, val, False, strict=False).accuracy for m in pc_models]
