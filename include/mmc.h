@@ -327,6 +327,74 @@ int mmc_head_evaluate_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_
                           int32_t* est, float* score, int32_t* rank, float* p_true, int64_t totals[MMC_EVAL_TOTALS],
                           int64_t* confusion /* K*K or NULL */, int64_t* rank_hist /* K or NULL */, void* hip_stream);
 
+/* ---- grouped validation: cover, per-source, reliability --------------------------------------------------------------
+ * Replaces: the whole-split passes of MetricsCoordinator.compute_and_log_all (mermaid_classifier/pyspacer/metrics/coordinator.py)
+ *   that mmc_head_evaluate's totals cannot answer and that otherwise need every row back on the host:
+ *     compute_cover (metrics/cover.py:44-72)            per-image class counts, then per-class bias / RMSE / MAE / R^2 over images
+ *     compute_per_source (metrics/per_source.py:88-140) accuracy, balanced accuracy, macro P/R/F1, cross-branch rate per data source
+ *     _adaptive_ece (metrics/calibration.py:32-79)      equal-mass bins over the sorted confidences
+ *     metrics/probability.py:43-60, calibration.py:139-140   per-category log-loss, accuracy and mean confidence
+ * The call is mmc_head_evaluate(_set) -- same arguments, and est / score / rank / p_true / totals / confusion / rank_hist come back
+ * with the same bits -- followed by one more pass over the call's rows on the device.
+ * Group inputs (host):
+ *   image_offsets[n_images + 1]  image i owns rows [image_offsets[i], image_offsets[i+1]) of the call (cover.py:34-36 relies on the
+ *                                same contiguity); image_offsets[0] = 0, strictly increasing (no empty image: the reference would
+ *                                divide by zero), image_offsets[n_images] = n
+ *   source_of_image[n_images]    in [0, n_sources); NULL or n_sources = 0: no per-source table
+ *   n_bins                       in [1, MMC_GROUPED_MAX_BINS]
+ * A row is SCORED exactly when mmc_head_evaluate adds it to confusion: its class is known and all its calibrated values are finite.
+ * Unscored rows enter none of the tables below; an image's point count is its number of scored rows; an image without a scored row is
+ * left out of the cover sums.  With g the true class of a scored row (outputs are host pointers, each may be NULL):
+ *   support[g], nll_q32[g], score_q32[g]   K each: rows, sum of round(-log(clip(p_true, 1e-15, 1)) * 2^32) (the term of totals[4]) and
+ *                                sum of llrint((double)score * 2^32), per true class.  Integer atomics: order-free, and any class ->
+ *                                category grouping follows on the host by integer adds.
+ *   source_confusion[(s * K + g) * K + est]   n_sources x K x K.  n_sources * K * K <= MMC_GROUPED_MAX_SOURCE_CELLS.
+ *   cover_sums[c * MMC_COVER_SUMS + j]   with t = true_cnt[i][c] / points[i] and p = pred_cnt[i][c] / points[i] in fp64 over the
+ *                                *n_images_used images with points > 0 (the int32 count tables live in the handle's scratch:
+ *                                n_images * K <= MMC_GROUPED_MAX_COVER_CELLS):
+ *                                  j = 0 sum t    1 sum p    2 sum (p - t)    3 sum (p - t)^2    4 sum |p - t|    5 min t    6 max t
+ *                                  7 sum (t - tbar)^2, tbar = sum t / n_images_used, from a second pass over the resident table
+ *                                max t > min t is the reference's true_col.std() > 0 gate.  Sums, not means; no float atomics:
+ *                                per-workgroup partials reduced in a fixed order that depends on n_images alone, so a repeated call
+ *                                returns the same bits.
+ *   bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max   n_bins each.  Every scored row gets the 31-bit key
+ *                                (bits(score) << 1) | (est == g); the rows are taken in key order -- the reference's order of
+ *                                np.argsort(confidences), with equal scores wrong before right where the reference leaves the order
+ *                                undefined -- and bin b holds the sorted positions [b * n_scored / n_bins, (b + 1) * n_scored /
+ *                                n_bins) (integer division: np.linspace(0, n, n_bins + 1, dtype=int)).  Per bin: rows, rows with
+ *                                est == g, sum of llrint((double)score * 2^32), and the scores of its first and last key.  Found by a
+ *                                radix select of the edge keys and one binned-sum pass, without sorting; equal-key rows are split
+ *                                between bins by integer position arithmetic.  An empty bin (n_scored < n_bins) has count 0 and 0 in
+ *                                every column.
+ * One call covers a whole split, n <= MMC_EVALUATE_SET_MAX_ROWS: the cover second pass and the global order do not merge across calls.
+ * Everything is checked before the first launch -- the checks of mmc_head_evaluate(_set), and: image_offsets NULL, not starting at 0,
+ *   not strictly increasing or not ending at n; n_images < 1 or > n; source_of_image[i] outside [0, n_sources); n_sources < 0; n_bins
+ *   outside [1, MMC_GROUPED_MAX_BINS]; either cap exceeded -- and a rejected call returns MMC_ERR_ARG with nothing launched and every
+ *   output whose size the arguments determine zeroed (the bin tables only for a valid n_bins, source_confusion only within its cap).
+ *   n == 0 with n_images == 0 is MMC_OK with zeroed outputs.
+ * Scratch (4 B of key per row, the count tables, the select histograms, the slabs) belongs to the head handle, grows on demand and is
+ *   freed with it.  The call synchronises `hip_stream` once, at the end. */
+#define MMC_GROUPED_MAX_BINS 64
+#define MMC_GROUPED_MAX_SOURCE_CELLS 67108864LL  /* 2^26 */
+#define MMC_GROUPED_MAX_COVER_CELLS 268435456LL  /* 2^28 */
+#define MMC_COVER_SUMS 8
+int mmc_head_evaluate_grouped(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
+                              int32_t* est, float* score, int32_t* rank, float* p_true, int64_t totals[MMC_EVAL_TOTALS],
+                              int64_t* confusion /* K*K or NULL */, int64_t* rank_hist /* K or NULL */,
+                              const int64_t* image_offsets, int64_t n_images, const int32_t* source_of_image, int n_sources, int n_bins,
+                              int64_t* support, int64_t* nll_q32, int64_t* score_q32, int64_t* source_confusion,
+                              double* cover_sums /* K*MMC_COVER_SUMS */, int64_t* n_images_used,
+                              int64_t* bin_count, int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min, float* bin_conf_max,
+                              unsigned flags, void* hip_stream);
+int mmc_head_evaluate_grouped_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
+                                  int32_t* est, float* score, int32_t* rank, float* p_true, int64_t totals[MMC_EVAL_TOTALS],
+                                  int64_t* confusion /* K*K or NULL */, int64_t* rank_hist /* K or NULL */,
+                                  const int64_t* image_offsets, int64_t n_images, const int32_t* source_of_image, int n_sources, int n_bins,
+                                  int64_t* support, int64_t* nll_q32, int64_t* score_q32, int64_t* source_confusion,
+                                  double* cover_sums /* K*MMC_COVER_SUMS */, int64_t* n_images_used,
+                                  int64_t* bin_count, int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min, float* bin_conf_max,
+                                  void* hip_stream);
+
 /* ---- multi-GPU: the gather of the sharded path --------------------------------------------------------------------
  * The path shards by patches (contiguous blocks of the row range per rank, weights replicated, no exchange during compute);
  * its one exchange step is the all-gather of the ranks' (n_r, 1280) feature blocks.  Replaces: nothing in the reference's

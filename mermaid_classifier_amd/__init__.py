@@ -11,6 +11,7 @@ from .calibration import CalibratedMLP, ParityError, calibrate, evaluate, export
 from .featureset import FeatureSet  # noqa: F401
 from .training import epoch_loop, train_and_validate, train_classifier  # noqa: F401
 from .validation import Validation, previous_accuracies, validate  # noqa: F401
+from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, grouped_validate  # noqa: F401
 
 __all__ = [
     "EfficientNetExtractor", "build_extractor_class", "resolve_device", "verify_device_numerics",
@@ -20,4 +21,5 @@ __all__ = [
     "CalibratedMLP", "ParityError", "calibrate", "evaluate", "export_artifact",
     "FeatureSet", "epoch_loop", "train_classifier", "train_and_validate",
     "Validation", "validate", "previous_accuracies",
+    "grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability",
 ]

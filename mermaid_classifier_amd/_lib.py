@@ -16,6 +16,8 @@ MMC_OK, MMC_ERR_ARG, MMC_ERR_WEIGHTS, MMC_ERR_HIP, MMC_ERR_NOMEM = 0, 1, 2, 3, 4
 MMC_PRECISION_FP8 = 1   # include/mmc.h: flags of mmc_backbone_create_ex
 MMC_IN_HOST, MMC_OUT_HOST = 1, 2
 MMC_EVAL_TOTALS = 5   # include/mmc.h: length of mmc_head_evaluate's totals
+MMC_GROUPED_MAX_BINS, MMC_COVER_SUMS = 64, 8   # include/mmc.h: mmc_head_evaluate_grouped
+MMC_GROUPED_MAX_SOURCE_CELLS, MMC_GROUPED_MAX_COVER_CELLS = 1 << 26, 1 << 28
 
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
@@ -29,7 +31,7 @@ SYMBOLS = [
     "mmc_calibrator_create", "mmc_calibrator_destroy", "mmc_calibrator_add_features", "mmc_calibrator_add_scores", "mmc_calibrator_fit",
     "mmc_featureset_create", "mmc_featureset_destroy", "mmc_featureset_rows", "mmc_featureset_dim", "mmc_featureset_append", "mmc_featureset_read",
     "mmc_trainer_partial_fit_set", "mmc_trainer_evaluate_set_q32", "mmc_calibrator_add_set",
-    "mmc_head_evaluate", "mmc_head_evaluate_set",
+    "mmc_head_evaluate", "mmc_head_evaluate_set", "mmc_head_evaluate_grouped", "mmc_head_evaluate_grouped_set",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -151,6 +153,12 @@ def _load() -> C.CDLL:
     lib.mmc_head_evaluate.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, u32, vp]
     lib.mmc_head_evaluate_set.restype = i32
     lib.mmc_head_evaluate_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    # the arguments of mmc_head_evaluate(_set), then image_offsets, n_images, source_of_image, n_sources, n_bins and the 11 group outputs
+    grouped = [vp, i64, vp, i32, i32] + [vp] * 11
+    lib.mmc_head_evaluate_grouped.restype = i32
+    lib.mmc_head_evaluate_grouped.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + grouped + [u32, vp]
+    lib.mmc_head_evaluate_grouped_set.restype = i32
+    lib.mmc_head_evaluate_grouped_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + grouped + [vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

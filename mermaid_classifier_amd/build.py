@@ -2,7 +2,7 @@
 
     python -m mermaid_classifier_amd.build [--force]
 
-One object per translation unit (the kernels are five .hip files by layer group, plus the trainer, the calibrator, the feature set and the C-ABI / schedule),
+One object per translation unit (the kernels are five .hip files by layer group, plus the trainer, the calibrator, the feature set, the grouped metrics and the C-ABI / schedule),
 compiled in parallel and only when the source or one of its headers is newer than the object; then one link.  Objects live in
 csrc/_obj/ (git-ignored and gpurun-ignored: only the linked library travels to the GPU box).
 """
@@ -31,6 +31,7 @@ SOURCES = {
     "trainer.hip": ["../../include/mmc.h", "trainer_internal.h", "kernels.h"],
     "calib.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "featureset.hip": ["../../include/mmc.h", "trainer_internal.h"],
+    "metrics.hip": ["kernels.h"],
     "mmc_api.cpp": ["kernels.h", "trainer_internal.h", "../../include/mmc.h"],
     "mmc_dist.cpp": ["../../include/mmc.h"],
 }

@@ -1062,6 +1062,7 @@ __global__ __launch_bounds__(256) void calibrate_topk_kernel(const float* __rest
 // (ROW_IN_LDS), flushed with one atomic per touched destination at the end.  confusion goes straight to memory (one atomic per
 // row, spread over the K x K table).  A lane reads only the row entries it wrote; v[g] comes from its owner lane by shuffle.
 // y[row] is the caller's label; with label_map it is label_map[y[row]].  A label outside the table or the head is treated as -1.
+// scored_out (the grouped pass of metrics.hip reads it) gets g for a row that entered confusion / rank_hist / the loss sum, else -1.
 // ---------------------------------------------------------------------------------------------
 template <bool ROW_IN_LDS>
 __global__ __launch_bounds__(256) void calibrate_eval_kernel(const float* __restrict__ logits, int M, int K,
@@ -1072,6 +1073,7 @@ __global__ __launch_bounds__(256) void calibrate_eval_kernel(const float* __rest
                                                              unsigned long long* __restrict__ totals,      // [EVAL_TOTALS]
                                                              unsigned long long* __restrict__ confusion,   // [K][K] or NULL
                                                              unsigned long long* __restrict__ rank_hist,   // [K] or NULL
+                                                             int32_t* __restrict__ scored_out,             // [M] or NULL
                                                              float* rowbuf)                                // [M][K] when !ROW_IN_LDS
 {
     extern __shared__ float eval_lds[];   // ROW_IN_LDS: [4][K] rows, then [K] unsigned rank counts
@@ -1131,6 +1133,7 @@ __global__ __launch_bounds__(256) void calibrate_eval_kernel(const float* __rest
             if (score_out) score_out[row] = __uint_as_float((unsigned)(best >> 32));
             if (rank_out) rank_out[row] = rank;
             if (ptrue_out) ptrue_out[row] = pt;
+            if (scored_out) scored_out[row] = (g >= 0 && !bad) ? g : -1;
             tot[0] += 1;
             if (g < 0) tot[2] += 1;
             else if (bad) tot[3] += 1;
@@ -1370,7 +1373,7 @@ int launch_calibrate_topk(const float* logits, int M, int K, const float* a, con
 
 int launch_calibrate_eval(const float* logits, int M, int K, const float* a, const float* b, const int32_t* y, const int32_t* label_map,
                           int n_labels, int32_t* est, float* score, int32_t* rank, float* p_true, long long* totals, long long* confusion,
-                          long long* rank_hist, float* rowbuf, hipStream_t st)
+                          long long* rank_hist, int32_t* scored, float* rowbuf, hipStream_t st)
 {
     if (M < 1 || K < 1 || !y || !totals || (label_map && n_labels < 1)) return -18;
     // a workgroup keeps its partial totals on chip while it walks rows: enough workgroups to fill the chip, no more
@@ -1381,11 +1384,11 @@ int launch_calibrate_eval(const float* logits, int M, int K, const float* a, con
     unsigned long long* rh = reinterpret_cast<unsigned long long*>(rank_hist);
     if (K <= TOPK_LDS_MAX_K) {
         hipLaunchKernelGGL((calibrate_eval_kernel<true>), grid, dim3(256), (size_t)5 * K * sizeof(float), st, logits, M, K, a, b, y, label_map,
-                           n_labels, est, score, rank, p_true, t, cf, rh, (float*)nullptr);
+                           n_labels, est, score, rank, p_true, t, cf, rh, scored, (float*)nullptr);
     } else {
         if (!rowbuf) return -18;
         hipLaunchKernelGGL((calibrate_eval_kernel<false>), grid, dim3(256), 0, st, logits, M, K, a, b, y, label_map, n_labels, est, score,
-                           rank, p_true, t, cf, rh, rowbuf);
+                           rank, p_true, t, cf, rh, scored, rowbuf);
     }
     LAUNCH_CHECK();
     return 0;

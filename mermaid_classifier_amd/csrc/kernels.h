@@ -232,9 +232,44 @@ int launch_calibrate_topk(const float* logits, int M, int K, const float* a, con
 // calibration + per row: best class and its score, rank and probability of the true class y[row] (through label_map when given;
 // -1 = unknown); the four per-row outputs may be NULL.  Adds into totals[EVAL_TOTALS] = {rows, correct, unknown, non-finite,
 // sum of the 2^-32 fixed-point log-loss}, confusion [K][K] and rank_hist [K] (either may be NULL) with integer atomics: the caller
-// zeroes them.  rowbuf: M x K scratch floats, needed only when K > 2048
+// zeroes them.  scored [M] or NULL: the true class of a row that entered those tables, -1 for an unknown or non-finite row.
+// rowbuf: M x K scratch floats, needed only when K > 2048
 constexpr int EVAL_TOTALS = 5;
 int launch_calibrate_eval(const float* logits, int M, int K, const float* a, const float* b, const int32_t* y, const int32_t* label_map,
                           int n_labels, int32_t* est, float* score, int32_t* rank, float* p_true, long long* totals, long long* confusion,
-                          long long* rank_hist, float* rowbuf, hipStream_t st);
+                          long long* rank_hist, int32_t* scored, float* rowbuf, hipStream_t st);
 int launch_crop(const uint8_t* image, int H, int W, const int32_t* rowcols, int n, uint8_t* out, hipStream_t st);
+
+// ---- grouped validation (metrics.hip) ----
+constexpr int GROUP_MAX_BINS = 64;
+constexpr int GROUP_MAX_TARGETS = 2 * GROUP_MAX_BINS;            // the sorted positions of every bin's first and last key
+constexpr int GROUP_HIST_WORDS = GROUP_MAX_TARGETS * 1024;       // counters of one radix-select level: slots x 2^10 (level 1: 1 x 2^11)
+constexpr uint32_t GROUP_KEY_NONE = 0xFFFFFFFFu;                 // the reliability key of a row that is not scored
+struct GroupSelect {   // device state of the radix select; after launch_group_select: tgt_prefix = the keys at the targets' sorted
+                       // positions, slot_prefix[0 .. n_slots) = the distinct ones among them, ascending
+    uint32_t n_scored, n_targets, n_slots, pad;
+    uint32_t tgt_prefix[GROUP_MAX_TARGETS], tgt_rank[GROUP_MAX_TARGETS], tgt_slot[GROUP_MAX_TARGETS], slot_prefix[GROUP_MAX_TARGETS];
+};
+struct GroupRowsArgs {
+    const int32_t* scored; const int32_t* est; const float* score; const float* p_true;   // one chunk: launch_calibrate_eval's outputs
+    int rows; int K; int64_t row0;                       // the chunk holds rows [row0, row0 + rows) of the call
+    const int64_t* offsets; int64_t n_images;            // [n_images + 1], offsets[0] = 0 < ... < offsets[n_images] = rows of the call
+    const int32_t* source_of_image;                      // [n_images] in [0, sources), or NULL
+    int32_t* true_cnt; int32_t* pred_cnt; int32_t* points;   // [n_images][K] x 2, [n_images]
+    unsigned long long* cls_tab;                         // [3][K]: support, nll_q32, score_q32 per true class
+    unsigned long long* source_conf;                     // [sources][K][K], or NULL
+    uint32_t* keys;                                      // [rows of the call]
+};
+// one chunk's scored rows into the integer tables (the caller zeroes them once per call) and its reliability keys
+int launch_group_rows(const GroupRowsArgs& a, hipStream_t st);
+// the image chunking of the cover reduction (a function of n_images alone); slab of launch_group_cover: chunks x K x 8 doubles
+void group_cover_chunks(int64_t n_images, int64_t* per_chunk, int* chunks);
+// cov[K][8] = sum t, sum p, sum (p - t), sum (p - t)^2, sum |p - t|, min t, max t, sum (t - mean t)^2 over the images with points > 0
+// (t = true_cnt / points, p = pred_cnt / points, fp64, fixed order); *n_used = the number of such images
+int launch_group_cover(const int32_t* true_cnt, const int32_t* pred_cnt, const int32_t* points, int64_t n_images, int K, double* slab,
+                       double* cov, long long* n_used, hipStream_t st);
+// radix select of the bin-edge keys among keys[n] (n_scored = totals[0] - totals[2] - totals[3], read on the device), then
+// raw[4][GROUP_MAX_TARGETS]: per distinct edge key e_j the rows equal to it, and count / n_correct / conf_q32 of e_j < key < e_j+1.
+// hist: GROUP_HIST_WORDS counters of scratch
+int launch_group_select(const uint32_t* keys, int64_t n, const long long* totals, int n_bins, GroupSelect* sel, uint32_t* hist,
+                        unsigned long long* raw, hipStream_t st);

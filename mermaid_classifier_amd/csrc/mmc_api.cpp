@@ -1757,6 +1757,9 @@ struct mmc_head {
     int64_t eval_map_cap = 0;         // labels
     long long* eval_tot = nullptr;
     int64_t eval_tot_cap = 0;         // int64 elements
+    // mmc_head_evaluate_grouped*: offsets, per-image counts, per-class and per-source tables, reliability keys, select state, slabs
+    char* grp = nullptr;
+    int64_t grp_cap = 0;              // bytes
 };
 
 extern "C" void mmc_head_destroy(mmc_head* h)
@@ -1768,7 +1771,7 @@ extern "C" void mmc_head_destroy(mmc_head* h)
     hipFree(h->a); hipFree(h->bc); hipFree(h->buf0); hipFree(h->buf1);
     hipFree(h->in_stage); hipFree(h->proba_stage); hipFree(h->arg_stage);
     hipFree(h->topk_idx_stage); hipFree(h->topk_score_stage); hipFree(h->cls_feats);
-    hipFree(h->eval_rows); hipFree(h->eval_map); hipFree(h->eval_tot);
+    hipFree(h->eval_rows); hipFree(h->eval_map); hipFree(h->eval_tot); hipFree(h->grp);
     delete h;
 }
 
@@ -1955,6 +1958,14 @@ struct EvalOut {
     int32_t* est; float* score; int32_t* rank; float* p_true;
     int64_t* totals; int64_t* confusion; int64_t* rank_hist;
 };
+// the group inputs and outputs of mmc_head_evaluate_grouped* (include/mmc.h)
+struct GroupIO {
+    const int64_t* offsets; int64_t n_images; const int32_t* source; int n_sources; int n_bins;
+    int64_t *support, *nll_q32, *score_q32, *source_confusion;
+    double* cover; int64_t* n_images_used;
+    int64_t *bin_count, *bin_correct, *bin_conf_q32; float *bin_conf_min, *bin_conf_max;
+};
+static int head_evaluate_groups(mmc_head* h, int64_t n, const GroupIO& g, hipStream_t st);
 
 static int eval_check_common(const mmc_head* h, int64_t n, const int32_t* label_map, int n_labels, const EvalOut& o)
 {
@@ -1973,25 +1984,86 @@ static int eval_check_common(const mmc_head* h, int64_t n, const int32_t* label_
     return MMC_OK;
 }
 
+// where the grouped pass keeps its device state inside h->grp (every part 256-byte aligned); the first `zero_bytes` are the integer
+// tables a call starts from zero
+struct GroupLayout {
+    size_t true_cnt, pred_cnt, points, cls_tab, source_conf, zero_bytes, offsets, source, keys, slab, cov, n_used, sel, raw, hist, bytes;
+    int chunks;
+};
+static GroupLayout group_layout(int K, int64_t n, const GroupIO& g)
+{
+    GroupLayout L{};
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+    const bool src = g.source && g.n_sources > 0;
+    int64_t per_chunk;
+    group_cover_chunks(g.n_images, &per_chunk, &L.chunks);
+    L.true_cnt = take((size_t)g.n_images * K * 4);
+    L.pred_cnt = take((size_t)g.n_images * K * 4);
+    L.points = take((size_t)g.n_images * 4);
+    L.cls_tab = take((size_t)3 * K * 8);
+    L.source_conf = take(src ? (size_t)g.n_sources * K * K * 8 : 0);
+    L.zero_bytes = at;
+    L.offsets = take((size_t)(g.n_images + 1) * 8);
+    L.source = take(src ? (size_t)g.n_images * 4 : 0);
+    L.keys = take((size_t)n * 4);
+    L.slab = take((size_t)L.chunks * K * 8 * 8);
+    L.cov = take((size_t)K * 8 * 8);
+    L.n_used = take(8);
+    L.sel = take(sizeof(GroupSelect));
+    L.raw = take((size_t)4 * GROUP_MAX_TARGETS * 8);
+    L.hist = take((size_t)GROUP_HIST_WORDS * 4);
+    L.bytes = at;
+    return L;
+}
+
+// grows h->grp, zeroes the integer tables, uploads offsets and source ids, and fills the chunk-independent kernel arguments
+static int group_prepare(mmc_head* h, int64_t n, const GroupIO& g, hipStream_t st, GroupRowsArgs* a)
+{
+    const GroupLayout L = group_layout(h->K, n, g);
+    int r;
+    if ((r = eval_grow(&h->grp, &h->grp_cap, (int64_t)L.bytes, 1))) return r;
+    char* b = h->grp;
+    const bool src = g.source && g.n_sources > 0;
+    HIP_TRY(hipMemsetAsync(b, 0, L.zero_bytes, st));
+    HIP_TRY(hipMemcpyAsync(b + L.offsets, g.offsets, (size_t)(g.n_images + 1) * 8, hipMemcpyHostToDevice, st));
+    if (src) HIP_TRY(hipMemcpyAsync(b + L.source, g.source, (size_t)g.n_images * 4, hipMemcpyHostToDevice, st));
+    a->K = h->K;
+    a->offsets = reinterpret_cast<const int64_t*>(b + L.offsets);
+    a->n_images = g.n_images;
+    a->source_of_image = src ? reinterpret_cast<const int32_t*>(b + L.source) : nullptr;
+    a->true_cnt = reinterpret_cast<int32_t*>(b + L.true_cnt);
+    a->pred_cnt = reinterpret_cast<int32_t*>(b + L.pred_cnt);
+    a->points = reinterpret_cast<int32_t*>(b + L.points);
+    a->cls_tab = reinterpret_cast<unsigned long long*>(b + L.cls_tab);
+    a->source_conf = src ? reinterpret_cast<unsigned long long*>(b + L.source_conf) : nullptr;
+    a->keys = reinterpret_cast<uint32_t*>(b + L.keys);
+    return 0;
+}
+
 // rows X[n][input_dim] (host with MMC_IN_HOST in `flags`, else on the head's device) with labels y_host (uploaded per chunk) or
 // y_dev (read in place); every argument has been checked
+// with `grp`: every chunk's scored rows also go into the grouped tables, and head_evaluate_groups ends the call
 static int head_evaluate(mmc_head* h, const float* X, unsigned flags, const int32_t* y_host, const int32_t* y_dev, int64_t n,
-                         const int32_t* label_map, int n_labels, const EvalOut& o, hipStream_t st)
+                         const int32_t* label_map, int n_labels, const EvalOut& o, hipStream_t st, const GroupIO* grp = nullptr)
 {
     const int K = h->K;
     HIP_TRY(hipSetDevice(h->device));
     const int64_t rows = n < HEAD_CHUNK ? n : HEAD_CHUNK;
     const int64_t ntot = EVAL_TOTALS + K + (o.confusion ? (int64_t)K * K : 0);
     int r;
-    if ((r = eval_grow(&h->eval_rows, &h->eval_rows_cap, rows, 5 * sizeof(int32_t)))) return r;
+    if ((r = eval_grow(&h->eval_rows, &h->eval_rows_cap, rows, 6 * sizeof(int32_t)))) return r;
     if ((r = eval_grow(&h->eval_tot, &h->eval_tot_cap, ntot, sizeof(long long)))) return r;
     if (label_map && (r = eval_grow(&h->eval_map, &h->eval_map_cap, n_labels, sizeof(int32_t)))) return r;
     const int64_t cap = h->eval_rows_cap;
     int32_t* dy = h->eval_rows;
-    int32_t* dest = o.est ? h->eval_rows + cap : nullptr;
-    float* dscore = o.score ? reinterpret_cast<float*>(h->eval_rows + 2 * cap) : nullptr;
+    int32_t* dest = (o.est || grp) ? h->eval_rows + cap : nullptr;
+    float* dscore = (o.score || grp) ? reinterpret_cast<float*>(h->eval_rows + 2 * cap) : nullptr;
     int32_t* drank = o.rank ? h->eval_rows + 3 * cap : nullptr;
-    float* dptrue = o.p_true ? reinterpret_cast<float*>(h->eval_rows + 4 * cap) : nullptr;
+    float* dptrue = (o.p_true || grp) ? reinterpret_cast<float*>(h->eval_rows + 4 * cap) : nullptr;
+    int32_t* dscored = grp ? h->eval_rows + 5 * cap : nullptr;
+    GroupRowsArgs ga{};
+    if (grp && (r = group_prepare(h, n, *grp, st, &ga))) return r;
     long long* dtot = h->eval_tot;
     long long* dhist = dtot + EVAL_TOTALS;
     long long* dconf = o.confusion ? dhist + K : nullptr;
@@ -2005,7 +2077,12 @@ static int head_evaluate(mmc_head* h, const float* X, unsigned flags, const int3
         const int32_t* yc = y_dev ? y_dev + off : dy;
         if (!y_dev) HIP_TRY(hipMemcpyAsync(dy, y_host + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
         KTRY(launch_calibrate_eval(logits, cur, K, h->a, h->bc, yc, label_map ? h->eval_map : nullptr, n_labels, dest, dscore, drank, dptrue,
-                                   dtot, dconf, dhist, h->proba_stage, st));
+                                   dtot, dconf, dhist, dscored, h->proba_stage, st));
+        if (grp) {
+            ga.scored = dscored; ga.est = dest; ga.score = dscore; ga.p_true = dptrue;
+            ga.rows = cur; ga.row0 = off;
+            KTRY(launch_group_rows(ga, st));
+        }
         // stream order keeps the next chunk's kernel behind these copies
         if (o.est) HIP_TRY(hipMemcpyAsync(o.est + off, dest, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
         if (o.score) HIP_TRY(hipMemcpyAsync(o.score + off, dscore, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
@@ -2015,6 +2092,7 @@ static int head_evaluate(mmc_head* h, const float* X, unsigned flags, const int3
     HIP_TRY(hipMemcpyAsync(o.totals, dtot, EVAL_TOTALS * sizeof(long long), hipMemcpyDeviceToHost, st));
     if (o.rank_hist) HIP_TRY(hipMemcpyAsync(o.rank_hist, dhist, (size_t)K * sizeof(long long), hipMemcpyDeviceToHost, st));
     if (o.confusion) HIP_TRY(hipMemcpyAsync(o.confusion, dconf, (size_t)K * K * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (grp) return head_evaluate_groups(h, n, *grp, st);
     HIP_TRY(hipStreamSynchronize(st));
     return MMC_OK;
 }
@@ -2064,6 +2142,194 @@ extern "C" int mmc_head_evaluate_set(mmc_head* h, mmc_featureset* fs, int64_t fi
     if (n == 0) return MMC_OK;
     return head_evaluate(h, fs->X + (size_t)first * fs->dim, 0u, nullptr, fs->y + first, n, label_map, n_labels, o,
                          static_cast<hipStream_t>(hip_stream));
+}
+
+// ------------------------------------------------------------------------------------------
+// grouped validation: mmc_head_evaluate_grouped / mmc_head_evaluate_grouped_set
+// ------------------------------------------------------------------------------------------
+static_assert(MMC_GROUPED_MAX_BINS == GROUP_MAX_BINS, "include/mmc.h and kernels.h disagree on the bins");
+
+// the per-bin tables from the edge keys and the per-edge-key sums: in sorted order the rows are [== e_0][between e_0 and e_1][== e_1]
+// ... [== e_last]; a between-region lies in one bin, an equal-key group is split by its positions (all its rows contribute alike)
+static int group_bins(const GroupSelect& s, const unsigned long long* raw, const GroupIO& g)
+{
+    const int nb = g.n_bins;
+    const int64_t ns = s.n_scored;
+    std::vector<int64_t> count(nb, 0), correct(nb, 0), conf(nb, 0);
+    std::vector<float> cmin(nb, 0.f), cmax(nb, 0.f);
+    if (ns > 0) {
+        if (s.n_targets != 2u * nb || s.n_slots < 1 || s.n_slots > s.n_targets) return fail(MMC_ERR_HIP, "grouped validation: select state is inconsistent");
+        auto edge = [&](int b) { return (int64_t)b * ns / nb; };
+        auto score_of = [](uint32_t key) { const uint32_t u = key >> 1; float f; memcpy(&f, &u, 4); return f; };
+        int64_t pos = 0;
+        int b = 0;
+        for (uint32_t j = 0; j < s.n_slots; ++j) {
+            const uint32_t key = s.slot_prefix[j];
+            const int64_t q = llrint((double)score_of(key) * 4294967296.0);
+            int64_t at = pos, end = pos + (int64_t)raw[j];
+            while (at < end) {
+                while (b < nb - 1 && edge(b + 1) <= at) ++b;
+                const int64_t hi = edge(b + 1) < end ? edge(b + 1) : end, m = hi - at;
+                if (m <= 0) return fail(MMC_ERR_HIP, "grouped validation: bin positions are inconsistent");
+                count[b] += m; correct[b] += (key & 1u) ? m : 0; conf[b] += m * q;
+                at = hi;
+            }
+            pos = end;
+            const int64_t ic = (int64_t)raw[GROUP_MAX_TARGETS + j];
+            if (ic > 0) {
+                while (b < nb - 1 && edge(b + 1) <= pos) ++b;
+                count[b] += ic; correct[b] += (int64_t)raw[2 * GROUP_MAX_TARGETS + j]; conf[b] += (int64_t)raw[3 * GROUP_MAX_TARGETS + j];
+                pos += ic;
+            }
+        }
+        if (pos != ns) return fail(MMC_ERR_HIP, "grouped validation: %lld keys binned, %lld rows scored", (long long)pos, (long long)ns);
+        for (int i = 0; i < nb; ++i) {
+            if (count[i] != edge(i + 1) - edge(i)) return fail(MMC_ERR_HIP, "grouped validation: bin %d holds %lld rows", i, (long long)count[i]);
+            if (count[i]) { cmin[i] = score_of(s.tgt_prefix[2 * i]); cmax[i] = score_of(s.tgt_prefix[2 * i + 1]); }
+        }
+    }
+    if (g.bin_count) memcpy(g.bin_count, count.data(), (size_t)nb * 8);
+    if (g.bin_correct) memcpy(g.bin_correct, correct.data(), (size_t)nb * 8);
+    if (g.bin_conf_q32) memcpy(g.bin_conf_q32, conf.data(), (size_t)nb * 8);
+    if (g.bin_conf_min) memcpy(g.bin_conf_min, cmin.data(), (size_t)nb * 4);
+    if (g.bin_conf_max) memcpy(g.bin_conf_max, cmax.data(), (size_t)nb * 4);
+    return MMC_OK;
+}
+
+// after the last chunk: the cover reduction and the select on the device, the tables to the host, one synchronisation, the bins
+static int head_evaluate_groups(mmc_head* h, int64_t n, const GroupIO& g, hipStream_t st)
+{
+    const int K = h->K;
+    const GroupLayout L = group_layout(K, n, g);
+    char* b = h->grp;
+    const bool src = g.source && g.n_sources > 0;
+    KTRY(launch_group_cover(reinterpret_cast<int32_t*>(b + L.true_cnt), reinterpret_cast<int32_t*>(b + L.pred_cnt),
+                            reinterpret_cast<int32_t*>(b + L.points), g.n_images, K, reinterpret_cast<double*>(b + L.slab),
+                            reinterpret_cast<double*>(b + L.cov), reinterpret_cast<long long*>(b + L.n_used), st));
+    KTRY(launch_group_select(reinterpret_cast<uint32_t*>(b + L.keys), n, h->eval_tot, g.n_bins, reinterpret_cast<GroupSelect*>(b + L.sel),
+                             reinterpret_cast<uint32_t*>(b + L.hist), reinterpret_cast<unsigned long long*>(b + L.raw), st));
+    GroupSelect sel;
+    std::vector<unsigned long long> raw((size_t)4 * GROUP_MAX_TARGETS);
+    const char* cls = b + L.cls_tab;
+    if (g.support) HIP_TRY(hipMemcpyAsync(g.support, cls, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    if (g.nll_q32) HIP_TRY(hipMemcpyAsync(g.nll_q32, cls + (size_t)K * 8, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    if (g.score_q32) HIP_TRY(hipMemcpyAsync(g.score_q32, cls + (size_t)2 * K * 8, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    if (g.source_confusion && src)
+        HIP_TRY(hipMemcpyAsync(g.source_confusion, b + L.source_conf, (size_t)g.n_sources * K * K * 8, hipMemcpyDeviceToHost, st));
+    if (g.cover) HIP_TRY(hipMemcpyAsync(g.cover, b + L.cov, (size_t)K * 8 * 8, hipMemcpyDeviceToHost, st));
+    if (g.n_images_used) HIP_TRY(hipMemcpyAsync(g.n_images_used, b + L.n_used, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&sel, b + L.sel, sizeof(sel), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(raw.data(), b + L.raw, raw.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return group_bins(sel, raw.data(), g);
+}
+
+// zeroes every group output whose size the arguments determine
+static void group_clear(const mmc_head* h, const GroupIO& g)
+{
+    if (!h) return;
+    const size_t K = (size_t)h->K;
+    if (g.support) memset(g.support, 0, K * 8);
+    if (g.nll_q32) memset(g.nll_q32, 0, K * 8);
+    if (g.score_q32) memset(g.score_q32, 0, K * 8);
+    if (g.source_confusion && g.n_sources > 0 && (int64_t)g.n_sources * h->K * h->K <= MMC_GROUPED_MAX_SOURCE_CELLS)
+        memset(g.source_confusion, 0, (size_t)g.n_sources * K * K * 8);
+    if (g.cover) memset(g.cover, 0, K * MMC_COVER_SUMS * 8);
+    if (g.n_images_used) *g.n_images_used = 0;
+    if (g.n_bins >= 1 && g.n_bins <= MMC_GROUPED_MAX_BINS) {
+        if (g.bin_count) memset(g.bin_count, 0, (size_t)g.n_bins * 8);
+        if (g.bin_correct) memset(g.bin_correct, 0, (size_t)g.n_bins * 8);
+        if (g.bin_conf_q32) memset(g.bin_conf_q32, 0, (size_t)g.n_bins * 8);
+        if (g.bin_conf_min) memset(g.bin_conf_min, 0, (size_t)g.n_bins * 4);
+        if (g.bin_conf_max) memset(g.bin_conf_max, 0, (size_t)g.n_bins * 4);
+    }
+}
+
+static int group_check(const mmc_head* h, int64_t n, const GroupIO& g)
+{
+    if (g.n_bins < 1 || g.n_bins > MMC_GROUPED_MAX_BINS)
+        return fail(MMC_ERR_ARG, "n_bins = %d outside [1, %d]", g.n_bins, MMC_GROUPED_MAX_BINS);
+    if (g.n_sources < 0) return fail(MMC_ERR_ARG, "n_sources = %d is negative", g.n_sources);
+    if (g.n_images < 0) return fail(MMC_ERR_ARG, "n_images = %lld is negative", (long long)g.n_images);
+    if (n == 0) return g.n_images == 0 ? MMC_OK : fail(MMC_ERR_ARG, "%lld images over no rows", (long long)g.n_images);
+    if (!g.offsets) return fail(MMC_ERR_ARG, "image_offsets is NULL");
+    if (g.n_images < 1 || g.n_images > n) return fail(MMC_ERR_ARG, "n_images = %lld for %lld rows: every image owns at least one row", (long long)g.n_images, (long long)n);
+    if (g.n_images * h->K > MMC_GROUPED_MAX_COVER_CELLS)
+        return fail(MMC_ERR_ARG, "n_images * K = %lld cells of per-image counts: at most %lld", (long long)(g.n_images * h->K), (long long)MMC_GROUPED_MAX_COVER_CELLS);
+    if (g.offsets[0] != 0) return fail(MMC_ERR_ARG, "image_offsets[0] = %lld: must be 0", (long long)g.offsets[0]);
+    for (int64_t i = 0; i < g.n_images; ++i)
+        if (g.offsets[i + 1] <= g.offsets[i])
+            return fail(MMC_ERR_ARG, "image_offsets[%lld] = %lld is not above image_offsets[%lld] = %lld (offsets increase strictly: no empty image)",
+                        (long long)(i + 1), (long long)g.offsets[i + 1], (long long)i, (long long)g.offsets[i]);
+    if (g.offsets[g.n_images] != n) return fail(MMC_ERR_ARG, "image_offsets[n_images] = %lld: must be n = %lld", (long long)g.offsets[g.n_images], (long long)n);
+    if (g.source && g.n_sources > 0) {
+        if ((int64_t)g.n_sources * h->K * h->K > MMC_GROUPED_MAX_SOURCE_CELLS)
+            return fail(MMC_ERR_ARG, "n_sources * K * K = %lld cells of per-source confusion: at most %lld", (long long)g.n_sources * h->K * h->K,
+                        (long long)MMC_GROUPED_MAX_SOURCE_CELLS);
+        for (int64_t i = 0; i < g.n_images; ++i)
+            if (g.source[i] < 0 || g.source[i] >= g.n_sources)
+                return fail(MMC_ERR_ARG, "source_of_image[%lld] = %d outside [0, %d)", (long long)i, g.source[i], g.n_sources);
+    }
+    return MMC_OK;
+}
+
+extern "C" int mmc_head_evaluate_grouped(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
+                                         int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
+                                         int64_t* rank_hist, const int64_t* image_offsets, int64_t n_images, const int32_t* source_of_image,
+                                         int n_sources, int n_bins, int64_t* support, int64_t* nll_q32, int64_t* score_q32,
+                                         int64_t* source_confusion, double* cover_sums, int64_t* n_images_used, int64_t* bin_count,
+                                         int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min, float* bin_conf_max, unsigned flags,
+                                         void* hip_stream)
+{
+    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
+    const GroupIO g{image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32, source_confusion,
+                    cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max};
+    eval_clear(h, o);
+    group_clear(h, g);
+    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
+    int r = eval_check_common(h, n, label_map, n_labels, o);
+    if (r) return r;
+    if ((r = group_check(h, n, g))) return r;
+    if (n == 0) return MMC_OK;
+    if (!feats || !y) return fail(MMC_ERR_ARG, "feats/y is NULL");
+    const int hi = label_map ? n_labels : h->K;
+    for (int64_t i = 0; i < n; ++i)
+        if (y[i] < 0 || y[i] >= hi) return fail(MMC_ERR_ARG, "label index y[%lld] = %d outside [0, %d)", (long long)i, y[i], hi);
+    r = head_evaluate(h, feats, flags & MMC_IN_HOST, y, nullptr, n, label_map, n_labels, o, static_cast<hipStream_t>(hip_stream), &g);
+    if (r) { eval_clear(h, o); group_clear(h, g); }
+    return r;
+}
+
+extern "C" int mmc_head_evaluate_grouped_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
+                                             int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
+                                             int64_t* rank_hist, const int64_t* image_offsets, int64_t n_images,
+                                             const int32_t* source_of_image, int n_sources, int n_bins, int64_t* support, int64_t* nll_q32,
+                                             int64_t* score_q32, int64_t* source_confusion, double* cover_sums, int64_t* n_images_used,
+                                             int64_t* bin_count, int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min,
+                                             float* bin_conf_max, void* hip_stream)
+{
+    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
+    const GroupIO g{image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32, source_confusion,
+                    cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max};
+    eval_clear(h, o);
+    group_clear(h, g);
+    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
+    if (!fs) return fail(MMC_ERR_ARG, "feature set handle is NULL");
+    if (fs->dim != h->input_dim) return fail(MMC_ERR_ARG, "feature set has %d columns, head expects %d", fs->dim, h->input_dim);
+    if (fs->device != h->device) return fail(MMC_ERR_ARG, "feature set is on device %d, head on device %d", fs->device, h->device);
+    if (first < 0 || n < 0 || first > fs->n || n > fs->n - first)
+        return fail(MMC_ERR_ARG, "rows [%lld, %lld + %lld) outside the set's %lld rows", (long long)first, (long long)first, (long long)n,
+                    (long long)fs->n);
+    int r = eval_check_common(h, n, label_map, n_labels, o);
+    if (r) return r;
+    if (label_map ? fs->K != n_labels : fs->K != h->K)
+        return fail(MMC_ERR_ARG, "feature set has %d classes, %s %d", fs->K, label_map ? "label_map covers" : "head", label_map ? n_labels : h->K);
+    if ((r = group_check(h, n, g))) return r;
+    if (n == 0) return MMC_OK;
+    r = head_evaluate(h, fs->X + (size_t)first * fs->dim, 0u, nullptr, fs->y + first, n, label_map, n_labels, o,
+                      static_cast<hipStream_t>(hip_stream), &g);
+    if (r) { eval_clear(h, o); group_clear(h, g); }
+    return r;
 }
 
 // rows of features mmc_classify_patches keeps between backbone and head: a larger call works through chunks of exactly this size

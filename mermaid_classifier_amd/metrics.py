@@ -1,0 +1,307 @@
+"""Grouped validation on the MI355X: the whole-split metric groups of the reference's ``MetricsCoordinator.compute_and_log_all``
+(``mermaid_classifier/pyspacer/metrics/coordinator.py``) that ``validate``'s totals cannot answer.
+
+===========================================================  ==============================================================
+reference                                                    here
+===========================================================  ==============================================================
+``compute_cover`` (metrics/cover.py:24-146)                  ``GroupedValidation.cover``: ``CoverStats.table()``, ``.scalars()``
+``compute_per_source`` (metrics/per_source.py:43-183)        ``GroupedValidation.sources``: ``SourceStats.table()``, ``.scalars()``
+``_adaptive_ece`` (metrics/calibration.py:32-79)             ``GroupedValidation.reliability``: ``Reliability.ece``, ``.bins``
+per-category log-loss (metrics/probability.py:43-60) and     ``GroupedValidation.by_class(category_of_class)``
+accuracy / mean confidence (metrics/calibration.py:139-140)
+===========================================================  ==============================================================
+
+The reference walks ``ValResults`` row by row on the host.  Here ``mmc_head_evaluate_grouped(_set)`` adds one pass on the device to
+``validate``'s evaluation and returns tables: exact integers wherever the quantity is a count (per-class sums, one confusion table
+per source, the reliability bins found by a radix select instead of a sort), and fp64 sums reduced in a fixed order for the cover
+statistics (per-image class counts stay in device scratch).  The objects below turn the tables into the reference's scalars and
+table columns; like ``Validation`` they can be built from arrays.  No pandas, sklearn or matplotlib; no CPU fallback for the pass."""
+
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+from .backbone import _current_stream_ptr
+from .featureset import FeatureSet
+from .validation import MAX_ROWS_PER_CALL, Validation, _host_labels, _model_parts, _ptr, label_map
+
+__all__ = ["grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability"]
+
+COVER_COLUMNS = ("sum_true", "sum_pred", "sum_err", "sum_sq_err", "sum_abs_err", "min_true", "max_true", "sum_sq_dev_true")
+
+
+class CoverStats:
+    """Per-class sums over the images of the split.  ``sums[c] = (sum t, sum p, sum (p - t), sum (p - t)^2, sum |p - t|, min t,
+    max t, sum (t - mean t)^2)`` with ``t`` / ``p`` the true / predicted cover fraction of class ``c`` in an image, over the
+    ``n_images_used`` images that hold a scored row."""
+
+    def __init__(self, sums, n_images_used: int):
+        self.sums = np.asarray(sums, dtype=np.float64)
+        self.n_images_used = int(n_images_used)
+        if self.sums.ndim != 2 or self.sums.shape[1] != len(COVER_COLUMNS):
+            raise ValueError(f"sums has shape {self.sums.shape}, expected (K, {len(COVER_COLUMNS)})")
+        if self.n_images_used < 0:
+            raise ValueError(f"n_images_used = {n_images_used} is negative")
+
+    def table(self) -> Dict[str, np.ndarray]:
+        """The columns of ``cover/per_class_cover_metrics`` (cover.py:62-86) but the names: ``class`` (index), ``mean_true_cover_pct``,
+        ``bias_pct``, ``rmse_pct``, ``mae_pct``, ``r_squared`` (NaN where the true cover is the same in every image), for the classes
+        that occur in gt or est, by mean true cover descending (equal covers in class order)."""
+        s, n = self.sums, self.n_images_used
+        if n == 0:
+            keep = np.zeros(0, np.int64)
+        else:
+            keep = np.flatnonzero((s[:, 0] > 0) | (s[:, 1] > 0))
+        s = s[keep]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean_true = s[:, 0] / n * 100 if n else np.zeros(0)
+            r2 = np.where(s[:, 6] > s[:, 5], 1.0 - s[:, 3] / s[:, 7], np.nan)
+        order = np.argsort(-mean_true, kind="stable")
+        cols = {"class": keep, "mean_true_cover_pct": mean_true}
+        if n:
+            cols.update(bias_pct=s[:, 2] / n * 100, rmse_pct=np.sqrt(s[:, 3] / n) * 100, mae_pct=s[:, 4] / n * 100, r_squared=r2)
+        else:
+            cols.update(bias_pct=np.zeros(0), rmse_pct=np.zeros(0), mae_pct=np.zeros(0), r_squared=np.zeros(0))
+        return {k: np.asarray(v)[order] for k, v in cols.items()}
+
+    def scalars(self) -> Dict[str, float]:
+        """``cover_mean_abs_bias_pct``, ``cover_mean_rmse_pct``, ``cover_mean_mae_pct``, ``cover_median_r_squared`` over the classes
+        with more than 0.5 % mean true cover; the median skips NaN (NaN when nothing is left); all 0.0 without such a class
+        (cover.py:88-120)."""
+        t = self.table()
+        sig = t["mean_true_cover_pct"] > 0.5
+        names = ("cover_mean_abs_bias_pct", "cover_mean_rmse_pct", "cover_mean_mae_pct", "cover_median_r_squared")
+        if not sig.any():
+            return dict.fromkeys(names, 0.0)
+        r2 = t["r_squared"][sig]
+        r2 = r2[~np.isnan(r2)]
+        return {names[0]: float(np.abs(t["bias_pct"][sig]).mean()), names[1]: float(t["rmse_pct"][sig].mean()),
+                names[2]: float(t["mae_pct"][sig].mean()), names[3]: float(np.median(r2)) if len(r2) else float("nan")}
+
+
+class SourceStats:
+    """One confusion table per data source: ``confusion[s, gt, est]`` (int64)."""
+
+    def __init__(self, confusion):
+        self.confusion = np.asarray(confusion, dtype=np.int64)
+        if self.confusion.ndim != 3 or self.confusion.shape[1] != self.confusion.shape[2]:
+            raise ValueError(f"confusion has shape {self.confusion.shape}, expected (sources, K, K)")
+
+    def _source(self, s: int, top):
+        c = self.confusion[s]
+        n = int(c.sum())
+        tp = np.diag(c).astype(np.float64)
+        support, predicted = c.sum(1).astype(np.float64), c.sum(0).astype(np.float64)
+        present = (support + predicted) > 0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            recall_supported = tp[support > 0] / support[support > 0]
+            precision = np.where(predicted > 0, tp / predicted, 0.0)[present]
+            recall = np.where(support > 0, tp / support, 0.0)[present]
+            f1 = np.where(support + predicted > 0, 2 * tp / (support + predicted), 0.0)[present]
+        wrong = n - int(np.trace(c))
+        out = dict(n=n, accuracy=int(np.trace(c)) / n, balanced_accuracy=float(recall_supported.mean()), f1_macro=float(f1.mean()),
+                   precision_macro=float(precision.mean()), recall_macro=float(recall.mean()))
+        if top is not None:
+            cross = int(c[top[:, None] != top[None, :]].sum())   # (different top level implies off the diagonal)
+            out["cross_branch_error_rate"] = cross / wrong if wrong else 0.0
+        return out
+
+    def _rows(self, top_of_class):
+        top = None
+        if top_of_class is not None:
+            top = np.asarray(top_of_class)
+            if top.shape != (self.confusion.shape[1],) or top.dtype.kind not in "iu":
+                raise ValueError(f"top_of_class must be {self.confusion.shape[1]} integers")
+        return [(s, self._source(s, top)) for s in range(len(self.confusion)) if self.confusion[s].any()]
+
+    def table(self, source_keys: Sequence[Any], images_per_source: Sequence[int], top_of_class=None) -> Dict[str, list]:
+        """The rows of ``per_source/metrics`` (per_source.py:88-165) as a dict of columns: accuracy, sklearn's balanced accuracy
+        (mean recall over the classes with support), macro precision / recall / F1 over the labels present in gt or est of the
+        source (``zero_division=0``), and -- with ``top_of_class[c]`` the integer id of class c's top-level ancestor -- the share
+        of the errors that cross top-level branches.  Rounded to 4 decimals and sorted by annotations descending (equal counts in
+        source order), as the reference does; sources without a scored row are left out."""
+        S = len(self.confusion)
+        if len(source_keys) != S or len(images_per_source) != S:
+            raise ValueError(f"source_keys / images_per_source must have {S} entries")
+        rows = self._rows(top_of_class)
+        rows.sort(key=lambda r: -r[1]["n"])
+        cols: Dict[str, list] = {"source_key": [source_keys[s] for s, _ in rows],
+                                 "num_val_images": [int(images_per_source[s]) for s, _ in rows],
+                                 "num_val_annotations": [r["n"] for _, r in rows]}
+        for name in ("accuracy", "balanced_accuracy", "f1_macro", "precision_macro", "recall_macro", "cross_branch_error_rate"):
+            if rows and name not in rows[0][1]:
+                continue
+            cols[name] = [round(r[name], 4) for _, r in rows]
+        return cols
+
+    def scalars(self) -> Dict[str, float]:
+        """``per_source/n_sources``, ``per_source/min_accuracy``, ``per_source/max_accuracy`` (per_source.py:169-175); empty without
+        a source that holds a scored row."""
+        acc = [r["accuracy"] for _, r in self._rows(None)]
+        if not acc:
+            return {}
+        return {"per_source/n_sources": float(len(acc)), "per_source/min_accuracy": float(min(acc)), "per_source/max_accuracy": float(max(acc))}
+
+
+class Reliability:
+    """The equal-mass reliability bins of ``_adaptive_ece`` (calibration.py:32-79) from per-bin integers: ``count``, ``n_correct``,
+    ``conf_q32`` = sum of llrint(score * 2^32), and ``conf_min`` / ``conf_max``, the scores of the bin's first and last row in
+    (score, correct) order."""
+
+    def __init__(self, count, n_correct, conf_q32, conf_min, conf_max):
+        self.count = np.asarray(count, dtype=np.int64)
+        self.n_correct = np.asarray(n_correct, dtype=np.int64)
+        self.conf_q32 = np.asarray(conf_q32, dtype=np.int64)
+        self.conf_min = np.asarray(conf_min, dtype=np.float32)
+        self.conf_max = np.asarray(conf_max, dtype=np.float32)
+        if self.count.ndim != 1 or any(v.shape != self.count.shape for v in (self.n_correct, self.conf_q32, self.conf_min, self.conf_max)):
+            raise ValueError("the per-bin columns must be 1-D and equally long")
+
+    @property
+    def bins(self) -> List[Dict[str, Any]]:
+        """The dicts of ``_adaptive_ece`` plus ``gap`` (calibration.py:95), empty bins skipped."""
+        out = []
+        for c, k, q, lo, hi in zip(self.count.tolist(), self.n_correct.tolist(), self.conf_q32.tolist(), self.conf_min.tolist(),
+                                   self.conf_max.tolist()):
+            if c == 0:
+                continue
+            conf, acc = q / (c << 32), k / c
+            out.append({"avg_confidence": conf, "avg_accuracy": acc, "count": c, "conf_min": lo, "conf_max": hi, "gap": conf - acc})
+        return out
+
+    @property
+    def ece(self) -> float:
+        n = int(self.count.sum())
+        ece = 0.0
+        for b in self.bins:
+            ece += abs(b["avg_accuracy"] - b["avg_confidence"]) * b["count"] / n
+        return ece
+
+
+class GroupedValidation:
+    """The outcome of ``grouped_validate``: ``validation`` (an ordinary ``Validation``), ``cover`` (``CoverStats``), ``sources``
+    (``SourceStats``, or None without ``source_of_image``), ``reliability`` (``Reliability``) and the per-true-class integer sums
+    ``support``, ``nll_q32``, ``score_q32``."""
+
+    def __init__(self, validation: Validation, cover: CoverStats, sources: Optional[SourceStats], reliability: Reliability, support, nll_q32,
+                 score_q32):
+        self.validation, self.cover, self.sources, self.reliability = validation, cover, sources, reliability
+        K = len(validation.classes)
+        self.support = np.asarray(support, dtype=np.int64)
+        self.nll_q32 = np.asarray(nll_q32, dtype=np.int64)
+        self.score_q32 = np.asarray(score_q32, dtype=np.int64)
+        if any(v.shape != (K,) for v in (self.support, self.nll_q32, self.score_q32)):
+            raise ValueError(f"support / nll_q32 / score_q32 must have shape ({K},)")
+
+    def by_class(self, category_of_class, min_samples: int = 30) -> Dict[int, Dict[str, float]]:
+        """Per category (``category_of_class[c]``: an integer id, negative = leave the class out): ``log_loss``
+        (probability.py:43-60), ``accuracy`` and ``avg_confidence`` (calibration.py:139-140) and ``n_samples`` over the scored rows
+        whose true class lies in it, from integer adds; categories with fewer than ``min_samples`` rows are left out."""
+        cat = np.asarray(category_of_class)
+        if cat.shape != self.support.shape or cat.dtype.kind not in "iu":
+            raise ValueError(f"category_of_class must be {len(self.support)} integers")
+        correct = np.diag(self.validation.confusion)
+        out = {}
+        for c in sorted(set(cat[cat >= 0].tolist())):
+            m = cat == c
+            n = int(self.support[m].sum())
+            if n < max(1, int(min_samples)):
+                continue
+            out[c] = {"log_loss": int(self.nll_q32[m].sum()) / (n << 32), "accuracy": int(correct[m].sum()) / n,
+                      "avg_confidence": int(self.score_q32[m].sum()) / (n << 32), "n_samples": n}
+        return out
+
+
+def _check_groups(n: int, image_sizes, source_of_image, n_bins):
+    """-> (offsets int64, sources int32 or None, number of sources); every complaint is a ValueError."""
+    sizes = np.asarray(image_sizes)
+    if sizes.ndim != 1 or len(sizes) == 0 or sizes.dtype.kind not in "iu":
+        raise ValueError("image_sizes must be a non-empty 1-D sequence of integers")
+    if int(sizes.min()) < 1:
+        raise ValueError(f"image_sizes[{int(sizes.argmin())}] = {int(sizes.min())}: every image holds at least one point")
+    if int(sizes.sum(dtype=np.int64)) != n:
+        raise ValueError(f"image_sizes add up to {int(sizes.sum(dtype=np.int64))}, the data has {n} rows")
+    if isinstance(n_bins, bool) or int(n_bins) != n_bins or not 1 <= n_bins <= _lib.MMC_GROUPED_MAX_BINS:
+        raise ValueError(f"n_bins must be an integer in [1, {_lib.MMC_GROUPED_MAX_BINS}]; got {n_bins!r}")
+    offsets = np.zeros(len(sizes) + 1, np.int64)
+    np.cumsum(sizes, out=offsets[1:])
+    if source_of_image is None:
+        return offsets, None, 0
+    src = np.asarray(source_of_image)
+    if src.shape != sizes.shape:
+        raise ValueError(f"source_of_image has shape {src.shape}, expected {sizes.shape}")
+    if src.dtype.kind not in "iu" or int(src.min()) < 0:
+        raise ValueError("source_of_image must hold integers >= 0")
+    return offsets, np.ascontiguousarray(src, dtype=np.int32), int(src.max()) + 1
+
+
+def grouped_validate(model, data, image_sizes, *, source_of_image=None, n_bins: int = 20, rows: bool = False) -> GroupedValidation:
+    """``validate(model, data, rows=rows)`` plus the grouped tables, in one call on the device.  ``data`` is a ``FeatureSet``
+    (read in place) or one ``(X, y)`` pair; ``image_sizes[i]`` is the number of points of image ``i``, in row order (each image's
+    points are contiguous, cover.py:34-36); ``source_of_image[i]`` an integer source id.  Everything is checked on the host before
+    the device is touched.  One call covers a whole split: more than ``MAX_ROWS_PER_CALL`` rows is a ``ValueError``."""
+    if not isinstance(rows, bool):
+        raise ValueError(f"rows must be True or False, got {rows!r}")
+    get_head, classes, dim = _model_parts(model)
+    K = len(classes)
+    if isinstance(data, FeatureSet):
+        if data.dim != dim:
+            raise ValueError(f"the feature set has {data.dim} features, expected {dim}")
+        n = len(data)
+        X = yi = None
+        lmap = None if data.classes.tolist() == classes else np.ascontiguousarray(label_map(classes, data.classes))
+    else:
+        if not (isinstance(data, (tuple, list)) and len(data) == 2):
+            raise ValueError("data must be a FeatureSet or one (X, y) pair")
+        X = np.ascontiguousarray(np.asarray(data[0], dtype=np.float32))
+        if X.ndim != 2:
+            raise ValueError(f"X must be 2D, got shape {X.shape}")
+        if X.shape[1] != dim:
+            raise ValueError(f"X has {X.shape[1]} features, expected {dim}")
+        n = X.shape[0]
+        yi, lmap = _host_labels(classes, data[1], n, True)
+    if n == 0:
+        raise ValueError("grouped_validate: no rows")
+    if n > MAX_ROWS_PER_CALL:
+        raise ValueError(f"{n} rows: one grouped call covers a whole split of at most {MAX_ROWS_PER_CALL} rows")
+    offsets, src, S = _check_groups(n, image_sizes, source_of_image, n_bins)
+    if len(offsets) - 1 > _lib.MMC_GROUPED_MAX_COVER_CELLS // K:
+        raise ValueError(f"{len(offsets) - 1} images x {K} classes: at most {_lib.MMC_GROUPED_MAX_COVER_CELLS} per-image counts")
+    if S * K * K > _lib.MMC_GROUPED_MAX_SOURCE_CELLS:
+        raise ValueError(f"{S} sources x {K} x {K} classes: at most {_lib.MMC_GROUPED_MAX_SOURCE_CELLS} per-source cells")
+    n_bins = int(n_bins)
+    tot = np.zeros(_lib.MMC_EVAL_TOTALS, np.int64)
+    conf, hist = np.zeros((K, K), np.int64), np.zeros(K, np.int64)
+    est, score, rank, p_true = ((np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.float32))
+                                if rows else (None,) * 4)
+    support, nll, sq = np.zeros(K, np.int64), np.zeros(K, np.int64), np.zeros(K, np.int64)
+    sconf = np.zeros((S, K, K), np.int64) if S else None
+    cover = np.zeros((K, _lib.MMC_COVER_SUMS), np.float64)
+    used = np.zeros(1, np.int64)
+    bc, bk, bq = np.zeros(n_bins, np.int64), np.zeros(n_bins, np.int64), np.zeros(n_bins, np.int64)
+    bmin, bmax = np.zeros(n_bins, np.float32), np.zeros(n_bins, np.float32)
+    head = get_head()
+    lib = _lib.lib()
+    st = _current_stream_ptr(head.device_index)
+    common = (_ptr(lmap), 0 if lmap is None else len(lmap), _ptr(est), _ptr(score), _ptr(rank), _ptr(p_true), tot.ctypes.data,
+              conf.ctypes.data, hist.ctypes.data, offsets.ctypes.data, len(offsets) - 1, _ptr(src), S, n_bins, support.ctypes.data,
+              nll.ctypes.data, sq.ctypes.data, _ptr(sconf), cover.ctypes.data, used.ctypes.data, bc.ctypes.data, bk.ctypes.data,
+              bq.ctypes.data, bmin.ctypes.data, bmax.ctypes.data)
+    if X is None:
+        _lib.check(lib.mmc_head_evaluate_grouped_set(head._h, data._handle(), 0, n, *common, st))
+        gt = None
+        if rows:
+            y0 = np.empty(n, np.int32)
+            _lib.check(lib.mmc_featureset_read(data._handle(), 0, n, None, y0.ctypes.data, st))
+            gt = y0 if lmap is None else lmap[y0]
+    else:
+        _lib.check(lib.mmc_head_evaluate_grouped(head._h, X.ctypes.data, yi.ctypes.data, n, *common, _lib.MMC_IN_HOST, st))
+        gt = (yi if lmap is None else lmap[yi]) if rows else None
+    t = tot.tolist()
+    val = Validation(classes, gt, est, None if score is None else score.astype(np.float64), rank, p_true, conf, hist, t[0], t[1], t[2],
+                     t[3], t[4])
+    return GroupedValidation(val, CoverStats(cover, int(used[0])), SourceStats(sconf) if S else None, Reliability(bc, bk, bq, bmin, bmax),
+                             support, nll, sq)
