@@ -2,7 +2,8 @@
 
     python -m mermaid_classifier_amd.build [--force]
 
-One object per translation unit (the kernels are five .hip files by layer group, plus the trainer, the calibrator, the feature set, the grouped metrics and the C-ABI / schedule),
+One object per translation unit (the kernels are five .hip files by layer group, plus the trainer, the calibrator, the feature set, the grouped metrics, and the two host units of the C ABI:
+mmc_api.cpp with the backbone schedule and mmc_head.cpp with the calibrated head),
 compiled in parallel and only when the source or one of its headers is newer than the object; then one link.  Objects live in
 csrc/_obj/ (git-ignored and gpurun-ignored: only the linked library travels to the GPU box).
 """
@@ -32,7 +33,8 @@ SOURCES = {
     "calib.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "featureset.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "metrics.hip": ["kernels.h"],
-    "mmc_api.cpp": ["kernels.h", "trainer_internal.h", "../../include/mmc.h"],
+    "mmc_api.cpp": ["kernels.h", "api_internal.h", "../../include/mmc.h"],
+    "mmc_head.cpp": ["kernels.h", "api_internal.h", "trainer_internal.h", "../../include/mmc.h"],
     "mmc_dist.cpp": ["../../include/mmc.h"],
 }
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",

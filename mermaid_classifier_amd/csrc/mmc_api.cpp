@@ -1,4 +1,5 @@
-// mmc_api.cpp -- C ABI (include/mmc.h) and the EfficientNet-B0 launch schedule.
+// mmc_api.cpp -- the backbone half of the C ABI (include/mmc.h): the error buffer, the EfficientNet-B0 launch schedule and the crop.
+// The calibrated head (predict, top-k, evaluate, classify) is the unit next to this one; the two share api_internal.h.
 // Host C++ only; kernels live in k_*.hip.  No torch, no CUDA shims.
 #include <hip/hip_runtime.h>
 
@@ -15,34 +16,15 @@
 #include <vector>
 
 #include "../../include/mmc.h"
+#include "api_internal.h"
 #include "kernels.h"
-#include "trainer_internal.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
 // ------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));    \
-    } while (0)
-#define KTRY(expr)                                                                                 \
-    do {                                                                                           \
-        int r_ = (expr);                                                                           \
-        if (r_ != 0) return fail(MMC_ERR_HIP, "%s failed (%d: %s)", #expr, r_,                     \
-                                 r_ > 0 ? hipGetErrorString((hipError_t)r_) : "unsupported shape"); \
-    } while (0)
 
-// error plumbing for the other translation units (trainer.hip)
+// every translation unit reports through this (api_internal.h, kernels.h, trainer_internal.h)
 int mmc_fail(int code, const char* fmt, ...)
 {
     va_list ap;
@@ -1104,6 +1086,7 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
 }
 
 extern "C" int mmc_feature_dim(const mmc_backbone* bb) { return bb ? bb->feat : 0; }
+int mmc_backbone_device(const mmc_backbone* bb) { return bb->device; }
 extern "C" int mmc_backbone_max_batch(const mmc_backbone* bb) { return bb ? bb->max_batch : 0; }
 extern "C" int mmc_backbone_lanes(const mmc_backbone* bb) { return bb ? bb->nlanes : 0; }
 extern "C" size_t mmc_backbone_workspace_bytes(const mmc_backbone* bb) { return bb ? bb->ws_bytes : 0; }
@@ -1728,645 +1711,5 @@ extern "C" int mmc_crop_patches(const void* image, int height, int width, const 
     // device-resident image and points: the kernel clamps each point into the image (see crop_kernel)
     int r = launch_crop(img, height, width, rc, (int)n, static_cast<uint8_t*>(patches_out_dev), st);
     if (r) return fail(MMC_ERR_HIP, "crop kernel launch failed (%d)", r);
-    return MMC_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// calibrated MLP head
-// ------------------------------------------------------------------------------------------
-struct mmc_head {
-    int device = 0, n_layers = 0, K = 0, input_dim = 0, in_pad = 0;
-    std::vector<int> dims_pad;        // padded widths (multiples of 4), last = K (unpadded)
-    std::vector<float*> W, b;         // device
-    float *a = nullptr, *bc = nullptr;
-    float *buf0 = nullptr, *buf1 = nullptr, *in_stage = nullptr, *proba_stage = nullptr;
-    int32_t* arg_stage = nullptr;
-    int64_t cap_rows = 0;
-    // mmc_head_topk: device staging of the (rows, k) outputs for MMC_OUT_HOST, grown on demand
-    int32_t* topk_idx_stage = nullptr;
-    float* topk_score_stage = nullptr;
-    int64_t topk_cap = 0;             // elements (rows * k)
-    // mmc_classify_patches: the features between backbone and head, grown on demand up to CLASSIFY_CHUNK rows
-    float* cls_feats = nullptr;
-    int64_t cls_cap = 0;              // rows
-    // mmc_head_evaluate*: one chunk's labels and per-row outputs ([5][eval_rows_cap] dwords), the label map, and the int64
-    // totals / rank histogram / confusion table, each grown on demand
-    int32_t* eval_rows = nullptr;
-    int64_t eval_rows_cap = 0;        // rows
-    int32_t* eval_map = nullptr;
-    int64_t eval_map_cap = 0;         // labels
-    long long* eval_tot = nullptr;
-    int64_t eval_tot_cap = 0;         // int64 elements
-    // mmc_head_evaluate_grouped*: offsets, per-image counts, per-class and per-source tables, reliability keys, select state, slabs
-    char* grp = nullptr;
-    int64_t grp_cap = 0;              // bytes
-};
-
-extern "C" void mmc_head_destroy(mmc_head* h)
-{
-    if (!h) return;
-    hipSetDevice(h->device);
-    for (float* p : h->W) hipFree(p);
-    for (float* p : h->b) hipFree(p);
-    hipFree(h->a); hipFree(h->bc); hipFree(h->buf0); hipFree(h->buf1);
-    hipFree(h->in_stage); hipFree(h->proba_stage); hipFree(h->arg_stage);
-    hipFree(h->topk_idx_stage); hipFree(h->topk_score_stage); hipFree(h->cls_feats);
-    hipFree(h->eval_rows); hipFree(h->eval_map); hipFree(h->eval_tot); hipFree(h->grp);
-    delete h;
-}
-
-extern "C" int mmc_head_create(const float* const* W, const float* const* b, const int* dims, int n_layers,
-                               const float* a, const float* bcal, int K, int device, mmc_head** out)
-{
-    if (!out) return fail(MMC_ERR_ARG, "out is NULL");
-    *out = nullptr;
-    if (!W || !b || !dims || !a || !bcal) return fail(MMC_ERR_ARG, "NULL argument");
-    if (n_layers < 1 || n_layers > 16) return fail(MMC_ERR_ARG, "n_layers %d out of range [1,16]", n_layers);
-    if (K <= 2) return fail(MMC_ERR_ARG, "CalibratedHead only supports the multiclass (K > 2) path; got K=%d", K);
-    if (dims[n_layers] != K) return fail(MMC_ERR_ARG, "dims[n_layers]=%d != K=%d", dims[n_layers], K);
-    for (int l = 0; l <= n_layers; ++l)
-        if (dims[l] < 1) return fail(MMC_ERR_ARG, "dims[%d]=%d must be positive", l, dims[l]);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(MMC_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(MMC_ERR_ARG, "device %d out of range (%d visible)", device, ndev);
-    HIP_TRY(hipSetDevice(device));
-    mmc_head* h = new mmc_head();
-    h->device = device; h->n_layers = n_layers; h->K = K; h->input_dim = dims[0];
-    h->dims_pad.resize(n_layers + 1);
-    for (int l = 0; l <= n_layers; ++l) h->dims_pad[l] = (l == n_layers) ? dims[l] : (dims[l] + 3) / 4 * 4;
-    h->in_pad = h->dims_pad[0];
-    for (int l = 0; l < n_layers; ++l) {
-        const int kin = dims[l], kp = h->dims_pad[l], nout = dims[l + 1], np = h->dims_pad[l + 1];
-        std::vector<float> wp((size_t)np * kp, 0.f), bp(np, 0.f);
-        for (int n = 0; n < nout; ++n) {
-            memcpy(&wp[(size_t)n * kp], W[l] + (size_t)n * kin, (size_t)kin * sizeof(float));
-            bp[n] = b[l][n];
-        }
-        float *dw = nullptr, *db = nullptr;
-        if (hipMalloc((void**)&dw, wp.size() * 4 + 256) != hipSuccess || hipMalloc((void**)&db, bp.size() * 4 + 256) != hipSuccess) {
-            mmc_head_destroy(h);
-            return fail(MMC_ERR_NOMEM, "hipMalloc failed for head layer %d", l);
-        }
-        h->W.push_back(dw); h->b.push_back(db);
-        hipMemcpy(dw, wp.data(), wp.size() * 4, hipMemcpyHostToDevice);
-        hipMemcpy(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice);
-    }
-    if (hipMalloc((void**)&h->a, K * 4 + 256) != hipSuccess || hipMalloc((void**)&h->bc, K * 4 + 256) != hipSuccess) {
-        mmc_head_destroy(h);
-        return fail(MMC_ERR_NOMEM, "hipMalloc failed for calibration parameters");
-    }
-    hipMemcpy(h->a, a, K * 4, hipMemcpyHostToDevice);
-    hipMemcpy(h->bc, bcal, K * 4, hipMemcpyHostToDevice);
-    *out = h;
-    return MMC_OK;
-}
-
-extern "C" int mmc_head_input_dim(const mmc_head* h) { return h ? h->input_dim : 0; }
-extern "C" int mmc_head_num_classes(const mmc_head* h) { return h ? h->K : 0; }
-
-static int head_reserve(mmc_head* h, int64_t rows)
-{
-    if (rows <= h->cap_rows) return 0;
-    hipFree(h->buf0); hipFree(h->buf1); hipFree(h->in_stage); hipFree(h->proba_stage); hipFree(h->arg_stage);
-    h->buf0 = h->buf1 = h->in_stage = h->proba_stage = nullptr; h->arg_stage = nullptr; h->cap_rows = 0;
-    int wmax = h->K;
-    for (int d : h->dims_pad) wmax = d > wmax ? d : wmax;
-    const size_t nb = (size_t)rows * wmax * 4 + 256;
-    HIP_TRY(hipMalloc((void**)&h->buf0, nb));
-    HIP_TRY(hipMalloc((void**)&h->buf1, nb));
-    HIP_TRY(hipMalloc((void**)&h->in_stage, (size_t)rows * h->in_pad * 4 + 256));
-    HIP_TRY(hipMalloc((void**)&h->proba_stage, (size_t)rows * h->K * 4 + 256));
-    HIP_TRY(hipMalloc((void**)&h->arg_stage, (size_t)rows * 4 + 256));
-    h->cap_rows = rows;
-    return 0;
-}
-
-// the Linear layers of one chunk (rows staged / padded as needed): returns the last layer's logits (cur x K) in *logits
-static int head_logits(mmc_head* h, const float* x, int cur, unsigned flags, hipStream_t st, const float** logits)
-{
-    const hipMemcpyKind kin = (flags & MMC_IN_HOST) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    if ((flags & MMC_IN_HOST) || h->in_pad != h->input_dim) {
-        if (h->in_pad != h->input_dim) HIP_TRY(hipMemsetAsync(h->in_stage, 0, (size_t)cur * h->in_pad * 4, st));
-        HIP_TRY(hipMemcpy2DAsync(h->in_stage, (size_t)h->in_pad * 4, x, (size_t)h->input_dim * 4,
-                                 (size_t)h->input_dim * 4, cur, kin, st));
-        x = h->in_stage;
-    }
-    float* pa = h->buf0;
-    float* pb = h->buf1;
-    for (int l = 0; l < h->n_layers; ++l) {
-        const bool last = l == h->n_layers - 1;
-        KTRY(launch_mlp_layer(x, cur, h->dims_pad[l], h->W[l], h->b[l], pa, h->dims_pad[l + 1], !last, st));
-        x = pa;
-        float* t = pa; pa = pb; pb = t;
-    }
-    *logits = x;
-    return 0;
-}
-
-extern "C" int mmc_head_predict(mmc_head* h, const float* feats, int64_t n, float* proba, int32_t* argmax,
-                                unsigned flags, void* hip_stream)
-{
-    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
-    if (n < 0) return fail(MMC_ERR_ARG, "n = %lld is negative", (long long)n);
-    if (n == 0) return MMC_OK;
-    if (!feats || !proba) return fail(MMC_ERR_ARG, "feats/proba is NULL");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t chunk = 65536;
-    for (int64_t off = 0; off < n; off += chunk) {
-        const int cur = (int)((n - off) < chunk ? (n - off) : chunk);
-        int r = head_reserve(h, cur);
-        if (r) return r;
-        const float* x = nullptr;
-        if ((r = head_logits(h, feats + (size_t)off * h->input_dim, cur, flags, st, &x))) return r;
-        float* pout = (flags & MMC_OUT_HOST) ? h->proba_stage : proba + (size_t)off * h->K;
-        int32_t* aout = argmax ? ((flags & MMC_OUT_HOST) ? h->arg_stage : argmax + off) : nullptr;
-        KTRY(launch_calibrate(x, cur, h->K, h->a, h->bc, pout, aout, st));
-        if (flags & MMC_OUT_HOST) {
-            HIP_TRY(hipMemcpyAsync(proba + (size_t)off * h->K, pout, (size_t)cur * h->K * 4, hipMemcpyDeviceToHost, st));
-            if (argmax) HIP_TRY(hipMemcpyAsync(argmax + off, aout, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-    }
-    return MMC_OK;
-}
-
-static int head_topk_reserve(mmc_head* h, int64_t elems)
-{
-    if (elems <= h->topk_cap) return 0;
-    hipFree(h->topk_idx_stage); hipFree(h->topk_score_stage);
-    h->topk_idx_stage = nullptr; h->topk_score_stage = nullptr; h->topk_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->topk_idx_stage, (size_t)elems * 4 + 256));
-    HIP_TRY(hipMalloc((void**)&h->topk_score_stage, (size_t)elems * 4 + 256));
-    h->topk_cap = elems;
-    return 0;
-}
-
-extern "C" int mmc_head_topk(mmc_head* h, const float* feats, int64_t n, int k, int32_t* idx, float* scores, float* proba,
-                             unsigned flags, void* hip_stream)
-{
-    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
-    if (n < 0) return fail(MMC_ERR_ARG, "n = %lld is negative", (long long)n);
-    if (k < 1 || k > h->K) return fail(MMC_ERR_ARG, "k = %d is outside [1, %d] (the head has %d classes)", k, h->K, h->K);
-    if (n == 0) return MMC_OK;
-    if (!feats) return fail(MMC_ERR_ARG, "feats is NULL");
-    if (!idx || !scores) return fail(MMC_ERR_ARG, "idx/scores is NULL");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    HIP_TRY(hipSetDevice(h->device));
-    const bool out_host = (flags & MMC_OUT_HOST) != 0;
-    const int64_t chunk = 65536;   // the chunking of mmc_head_predict: same launches, same bits
-    for (int64_t off = 0; off < n; off += chunk) {
-        const int cur = (int)((n - off) < chunk ? (n - off) : chunk);
-        int r = head_reserve(h, cur);
-        if (r) return r;
-        if (out_host && (r = head_topk_reserve(h, (int64_t)cur * k))) return r;
-        const float* logits = nullptr;
-        if ((r = head_logits(h, feats + (size_t)off * h->input_dim, cur, flags, st, &logits))) return r;
-        int32_t* iout = out_host ? h->topk_idx_stage : idx + (size_t)off * k;
-        float* sout = out_host ? h->topk_score_stage : scores + (size_t)off * k;
-        float* pout = proba ? (out_host ? h->proba_stage : proba + (size_t)off * h->K) : nullptr;
-        KTRY(launch_calibrate_topk(logits, cur, h->K, h->a, h->bc, k, iout, sout, pout, h->proba_stage, st));
-        if (out_host) {
-            HIP_TRY(hipMemcpyAsync(idx + (size_t)off * k, iout, (size_t)cur * k * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(scores + (size_t)off * k, sout, (size_t)cur * k * 4, hipMemcpyDeviceToHost, st));
-            if (proba) HIP_TRY(hipMemcpyAsync(proba + (size_t)off * h->K, pout, (size_t)cur * h->K * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-    }
-    return MMC_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// validation of a calibrated head: mmc_head_evaluate / mmc_head_evaluate_set
-// ------------------------------------------------------------------------------------------
-static_assert(MMC_EVAL_TOTALS == EVAL_TOTALS, "include/mmc.h and kernels.h disagree on the totals");
-static const int64_t HEAD_CHUNK = 65536;   // the chunking of mmc_head_predict: same launches, same bits
-
-template <class T>
-static int eval_grow(T** p, int64_t* cap, int64_t want, size_t elem_bytes)
-{
-    if (want <= *cap) return 0;
-    hipFree(*p);   // (waits for whatever still reads the old buffer)
-    *p = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc((void**)p, (size_t)want * elem_bytes + 256));
-    *cap = want;
-    return 0;
-}
-
-struct EvalOut {
-    int32_t* est; float* score; int32_t* rank; float* p_true;
-    int64_t* totals; int64_t* confusion; int64_t* rank_hist;
-};
-// the group inputs and outputs of mmc_head_evaluate_grouped* (include/mmc.h)
-struct GroupIO {
-    const int64_t* offsets; int64_t n_images; const int32_t* source; int n_sources; int n_bins;
-    int64_t *support, *nll_q32, *score_q32, *source_confusion;
-    double* cover; int64_t* n_images_used;
-    int64_t *bin_count, *bin_correct, *bin_conf_q32; float *bin_conf_min, *bin_conf_max;
-};
-static int head_evaluate_groups(mmc_head* h, int64_t n, const GroupIO& g, hipStream_t st);
-
-static int eval_check_common(const mmc_head* h, int64_t n, const int32_t* label_map, int n_labels, const EvalOut& o)
-{
-    if (n < 0) return fail(MMC_ERR_ARG, "n = %lld is negative", (long long)n);
-    if (!o.totals) return fail(MMC_ERR_ARG, "totals is NULL");
-    // the int64 loss total: a row adds at most -log(1e-15) * 2^32 < 36.05 * 2^32 (see MMC_EVALUATE_SET_MAX_ROWS)
-    if (n > MMC_EVALUATE_SET_MAX_ROWS)
-        return fail(MMC_ERR_ARG, "n = %lld rows in one call: split it (at most %lld)", (long long)n, (long long)MMC_EVALUATE_SET_MAX_ROWS);
-    if (!label_map && n_labels != 0) return fail(MMC_ERR_ARG, "n_labels = %d without a label_map (pass NULL, 0)", n_labels);
-    if (label_map) {
-        if (n_labels < 1) return fail(MMC_ERR_ARG, "n_labels = %d with a label_map: must be positive", n_labels);
-        for (int i = 0; i < n_labels; ++i)
-            if (label_map[i] < -1 || label_map[i] >= h->K)
-                return fail(MMC_ERR_ARG, "label_map[%d] = %d outside [-1, %d)", i, label_map[i], h->K);
-    }
-    return MMC_OK;
-}
-
-// where the grouped pass keeps its device state inside h->grp (every part 256-byte aligned); the first `zero_bytes` are the integer
-// tables a call starts from zero
-struct GroupLayout {
-    size_t true_cnt, pred_cnt, points, cls_tab, source_conf, zero_bytes, offsets, source, keys, slab, cov, n_used, sel, raw, hist, bytes;
-    int chunks;
-};
-static GroupLayout group_layout(int K, int64_t n, const GroupIO& g)
-{
-    GroupLayout L{};
-    size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
-    const bool src = g.source && g.n_sources > 0;
-    int64_t per_chunk;
-    group_cover_chunks(g.n_images, &per_chunk, &L.chunks);
-    L.true_cnt = take((size_t)g.n_images * K * 4);
-    L.pred_cnt = take((size_t)g.n_images * K * 4);
-    L.points = take((size_t)g.n_images * 4);
-    L.cls_tab = take((size_t)3 * K * 8);
-    L.source_conf = take(src ? (size_t)g.n_sources * K * K * 8 : 0);
-    L.zero_bytes = at;
-    L.offsets = take((size_t)(g.n_images + 1) * 8);
-    L.source = take(src ? (size_t)g.n_images * 4 : 0);
-    L.keys = take((size_t)n * 4);
-    L.slab = take((size_t)L.chunks * K * 8 * 8);
-    L.cov = take((size_t)K * 8 * 8);
-    L.n_used = take(8);
-    L.sel = take(sizeof(GroupSelect));
-    L.raw = take((size_t)4 * GROUP_MAX_TARGETS * 8);
-    L.hist = take((size_t)GROUP_HIST_WORDS * 4);
-    L.bytes = at;
-    return L;
-}
-
-// grows h->grp, zeroes the integer tables, uploads offsets and source ids, and fills the chunk-independent kernel arguments
-static int group_prepare(mmc_head* h, int64_t n, const GroupIO& g, hipStream_t st, GroupRowsArgs* a)
-{
-    const GroupLayout L = group_layout(h->K, n, g);
-    int r;
-    if ((r = eval_grow(&h->grp, &h->grp_cap, (int64_t)L.bytes, 1))) return r;
-    char* b = h->grp;
-    const bool src = g.source && g.n_sources > 0;
-    HIP_TRY(hipMemsetAsync(b, 0, L.zero_bytes, st));
-    HIP_TRY(hipMemcpyAsync(b + L.offsets, g.offsets, (size_t)(g.n_images + 1) * 8, hipMemcpyHostToDevice, st));
-    if (src) HIP_TRY(hipMemcpyAsync(b + L.source, g.source, (size_t)g.n_images * 4, hipMemcpyHostToDevice, st));
-    a->K = h->K;
-    a->offsets = reinterpret_cast<const int64_t*>(b + L.offsets);
-    a->n_images = g.n_images;
-    a->source_of_image = src ? reinterpret_cast<const int32_t*>(b + L.source) : nullptr;
-    a->true_cnt = reinterpret_cast<int32_t*>(b + L.true_cnt);
-    a->pred_cnt = reinterpret_cast<int32_t*>(b + L.pred_cnt);
-    a->points = reinterpret_cast<int32_t*>(b + L.points);
-    a->cls_tab = reinterpret_cast<unsigned long long*>(b + L.cls_tab);
-    a->source_conf = src ? reinterpret_cast<unsigned long long*>(b + L.source_conf) : nullptr;
-    a->keys = reinterpret_cast<uint32_t*>(b + L.keys);
-    return 0;
-}
-
-// rows X[n][input_dim] (host with MMC_IN_HOST in `flags`, else on the head's device) with labels y_host (uploaded per chunk) or
-// y_dev (read in place); every argument has been checked
-// with `grp`: every chunk's scored rows also go into the grouped tables, and head_evaluate_groups ends the call
-static int head_evaluate(mmc_head* h, const float* X, unsigned flags, const int32_t* y_host, const int32_t* y_dev, int64_t n,
-                         const int32_t* label_map, int n_labels, const EvalOut& o, hipStream_t st, const GroupIO* grp = nullptr)
-{
-    const int K = h->K;
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t rows = n < HEAD_CHUNK ? n : HEAD_CHUNK;
-    const int64_t ntot = EVAL_TOTALS + K + (o.confusion ? (int64_t)K * K : 0);
-    int r;
-    if ((r = eval_grow(&h->eval_rows, &h->eval_rows_cap, rows, 6 * sizeof(int32_t)))) return r;
-    if ((r = eval_grow(&h->eval_tot, &h->eval_tot_cap, ntot, sizeof(long long)))) return r;
-    if (label_map && (r = eval_grow(&h->eval_map, &h->eval_map_cap, n_labels, sizeof(int32_t)))) return r;
-    const int64_t cap = h->eval_rows_cap;
-    int32_t* dy = h->eval_rows;
-    int32_t* dest = (o.est || grp) ? h->eval_rows + cap : nullptr;
-    float* dscore = (o.score || grp) ? reinterpret_cast<float*>(h->eval_rows + 2 * cap) : nullptr;
-    int32_t* drank = o.rank ? h->eval_rows + 3 * cap : nullptr;
-    float* dptrue = (o.p_true || grp) ? reinterpret_cast<float*>(h->eval_rows + 4 * cap) : nullptr;
-    int32_t* dscored = grp ? h->eval_rows + 5 * cap : nullptr;
-    GroupRowsArgs ga{};
-    if (grp && (r = group_prepare(h, n, *grp, st, &ga))) return r;
-    long long* dtot = h->eval_tot;
-    long long* dhist = dtot + EVAL_TOTALS;
-    long long* dconf = o.confusion ? dhist + K : nullptr;
-    HIP_TRY(hipMemsetAsync(dtot, 0, (size_t)ntot * sizeof(long long), st));
-    if (label_map) HIP_TRY(hipMemcpyAsync(h->eval_map, label_map, (size_t)n_labels * 4, hipMemcpyHostToDevice, st));
-    for (int64_t off = 0; off < n; off += HEAD_CHUNK) {
-        const int cur = (int)((n - off) < HEAD_CHUNK ? (n - off) : HEAD_CHUNK);
-        if ((r = head_reserve(h, cur))) return r;
-        const float* logits = nullptr;
-        if ((r = head_logits(h, X + (size_t)off * h->input_dim, cur, flags, st, &logits))) return r;
-        const int32_t* yc = y_dev ? y_dev + off : dy;
-        if (!y_dev) HIP_TRY(hipMemcpyAsync(dy, y_host + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
-        KTRY(launch_calibrate_eval(logits, cur, K, h->a, h->bc, yc, label_map ? h->eval_map : nullptr, n_labels, dest, dscore, drank, dptrue,
-                                   dtot, dconf, dhist, dscored, h->proba_stage, st));
-        if (grp) {
-            ga.scored = dscored; ga.est = dest; ga.score = dscore; ga.p_true = dptrue;
-            ga.rows = cur; ga.row0 = off;
-            KTRY(launch_group_rows(ga, st));
-        }
-        // stream order keeps the next chunk's kernel behind these copies
-        if (o.est) HIP_TRY(hipMemcpyAsync(o.est + off, dest, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
-        if (o.score) HIP_TRY(hipMemcpyAsync(o.score + off, dscore, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
-        if (o.rank) HIP_TRY(hipMemcpyAsync(o.rank + off, drank, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
-        if (o.p_true) HIP_TRY(hipMemcpyAsync(o.p_true + off, dptrue, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(o.totals, dtot, EVAL_TOTALS * sizeof(long long), hipMemcpyDeviceToHost, st));
-    if (o.rank_hist) HIP_TRY(hipMemcpyAsync(o.rank_hist, dhist, (size_t)K * sizeof(long long), hipMemcpyDeviceToHost, st));
-    if (o.confusion) HIP_TRY(hipMemcpyAsync(o.confusion, dconf, (size_t)K * K * sizeof(long long), hipMemcpyDeviceToHost, st));
-    if (grp) return head_evaluate_groups(h, n, *grp, st);
-    HIP_TRY(hipStreamSynchronize(st));
-    return MMC_OK;
-}
-
-static void eval_clear(const mmc_head* h, const EvalOut& o)
-{
-    if (o.totals) memset(o.totals, 0, EVAL_TOTALS * sizeof(int64_t));
-    if (h && o.rank_hist) memset(o.rank_hist, 0, (size_t)h->K * sizeof(int64_t));
-    if (h && o.confusion) memset(o.confusion, 0, (size_t)h->K * h->K * sizeof(int64_t));
-}
-
-extern "C" int mmc_head_evaluate(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
-                                 int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
-                                 int64_t* rank_hist, unsigned flags, void* hip_stream)
-{
-    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
-    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
-    int r = eval_check_common(h, n, label_map, n_labels, o);
-    if (r) return r;
-    eval_clear(h, o);
-    if (n == 0) return MMC_OK;
-    if (!feats || !y) return fail(MMC_ERR_ARG, "feats/y is NULL");
-    const int hi = label_map ? n_labels : h->K;
-    for (int64_t i = 0; i < n; ++i)
-        if (y[i] < 0 || y[i] >= hi) return fail(MMC_ERR_ARG, "label index y[%lld] = %d outside [0, %d)", (long long)i, y[i], hi);
-    return head_evaluate(h, feats, flags & MMC_IN_HOST, y, nullptr, n, label_map, n_labels, o, static_cast<hipStream_t>(hip_stream));
-}
-
-extern "C" int mmc_head_evaluate_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
-                                     int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
-                                     int64_t* rank_hist, void* hip_stream)
-{
-    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
-    if (!fs) return fail(MMC_ERR_ARG, "feature set handle is NULL");
-    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
-    if (fs->dim != h->input_dim) return fail(MMC_ERR_ARG, "feature set has %d columns, head expects %d", fs->dim, h->input_dim);
-    if (fs->device != h->device) return fail(MMC_ERR_ARG, "feature set is on device %d, head on device %d", fs->device, h->device);
-    if (first < 0 || n < 0 || first > fs->n || n > fs->n - first)
-        return fail(MMC_ERR_ARG, "rows [%lld, %lld + %lld) outside the set's %lld rows", (long long)first, (long long)first, (long long)n,
-                    (long long)fs->n);
-    int r = eval_check_common(h, n, label_map, n_labels, o);
-    if (r) return r;
-    // the set's labels lie in [0, fs->K): that range must be the head's classes, or the map's domain
-    if (label_map ? fs->K != n_labels : fs->K != h->K)
-        return fail(MMC_ERR_ARG, "feature set has %d classes, %s %d", fs->K, label_map ? "label_map covers" : "head", label_map ? n_labels : h->K);
-    eval_clear(h, o);
-    if (n == 0) return MMC_OK;
-    return head_evaluate(h, fs->X + (size_t)first * fs->dim, 0u, nullptr, fs->y + first, n, label_map, n_labels, o,
-                         static_cast<hipStream_t>(hip_stream));
-}
-
-// ------------------------------------------------------------------------------------------
-// grouped validation: mmc_head_evaluate_grouped / mmc_head_evaluate_grouped_set
-// ------------------------------------------------------------------------------------------
-static_assert(MMC_GROUPED_MAX_BINS == GROUP_MAX_BINS, "include/mmc.h and kernels.h disagree on the bins");
-
-// the per-bin tables from the edge keys and the per-edge-key sums: in sorted order the rows are [== e_0][between e_0 and e_1][== e_1]
-// ... [== e_last]; a between-region lies in one bin, an equal-key group is split by its positions (all its rows contribute alike)
-static int group_bins(const GroupSelect& s, const unsigned long long* raw, const GroupIO& g)
-{
-    const int nb = g.n_bins;
-    const int64_t ns = s.n_scored;
-    std::vector<int64_t> count(nb, 0), correct(nb, 0), conf(nb, 0);
-    std::vector<float> cmin(nb, 0.f), cmax(nb, 0.f);
-    if (ns > 0) {
-        if (s.n_targets != 2u * nb || s.n_slots < 1 || s.n_slots > s.n_targets) return fail(MMC_ERR_HIP, "grouped validation: select state is inconsistent");
-        auto edge = [&](int b) { return (int64_t)b * ns / nb; };
-        auto score_of = [](uint32_t key) { const uint32_t u = key >> 1; float f; memcpy(&f, &u, 4); return f; };
-        int64_t pos = 0;
-        int b = 0;
-        for (uint32_t j = 0; j < s.n_slots; ++j) {
-            const uint32_t key = s.slot_prefix[j];
-            const int64_t q = llrint((double)score_of(key) * 4294967296.0);
-            int64_t at = pos, end = pos + (int64_t)raw[j];
-            while (at < end) {
-                while (b < nb - 1 && edge(b + 1) <= at) ++b;
-                const int64_t hi = edge(b + 1) < end ? edge(b + 1) : end, m = hi - at;
-                if (m <= 0) return fail(MMC_ERR_HIP, "grouped validation: bin positions are inconsistent");
-                count[b] += m; correct[b] += (key & 1u) ? m : 0; conf[b] += m * q;
-                at = hi;
-            }
-            pos = end;
-            const int64_t ic = (int64_t)raw[GROUP_MAX_TARGETS + j];
-            if (ic > 0) {
-                while (b < nb - 1 && edge(b + 1) <= pos) ++b;
-                count[b] += ic; correct[b] += (int64_t)raw[2 * GROUP_MAX_TARGETS + j]; conf[b] += (int64_t)raw[3 * GROUP_MAX_TARGETS + j];
-                pos += ic;
-            }
-        }
-        if (pos != ns) return fail(MMC_ERR_HIP, "grouped validation: %lld keys binned, %lld rows scored", (long long)pos, (long long)ns);
-        for (int i = 0; i < nb; ++i) {
-            if (count[i] != edge(i + 1) - edge(i)) return fail(MMC_ERR_HIP, "grouped validation: bin %d holds %lld rows", i, (long long)count[i]);
-            if (count[i]) { cmin[i] = score_of(s.tgt_prefix[2 * i]); cmax[i] = score_of(s.tgt_prefix[2 * i + 1]); }
-        }
-    }
-    if (g.bin_count) memcpy(g.bin_count, count.data(), (size_t)nb * 8);
-    if (g.bin_correct) memcpy(g.bin_correct, correct.data(), (size_t)nb * 8);
-    if (g.bin_conf_q32) memcpy(g.bin_conf_q32, conf.data(), (size_t)nb * 8);
-    if (g.bin_conf_min) memcpy(g.bin_conf_min, cmin.data(), (size_t)nb * 4);
-    if (g.bin_conf_max) memcpy(g.bin_conf_max, cmax.data(), (size_t)nb * 4);
-    return MMC_OK;
-}
-
-// after the last chunk: the cover reduction and the select on the device, the tables to the host, one synchronisation, the bins
-static int head_evaluate_groups(mmc_head* h, int64_t n, const GroupIO& g, hipStream_t st)
-{
-    const int K = h->K;
-    const GroupLayout L = group_layout(K, n, g);
-    char* b = h->grp;
-    const bool src = g.source && g.n_sources > 0;
-    KTRY(launch_group_cover(reinterpret_cast<int32_t*>(b + L.true_cnt), reinterpret_cast<int32_t*>(b + L.pred_cnt),
-                            reinterpret_cast<int32_t*>(b + L.points), g.n_images, K, reinterpret_cast<double*>(b + L.slab),
-                            reinterpret_cast<double*>(b + L.cov), reinterpret_cast<long long*>(b + L.n_used), st));
-    KTRY(launch_group_select(reinterpret_cast<uint32_t*>(b + L.keys), n, h->eval_tot, g.n_bins, reinterpret_cast<GroupSelect*>(b + L.sel),
-                             reinterpret_cast<uint32_t*>(b + L.hist), reinterpret_cast<unsigned long long*>(b + L.raw), st));
-    GroupSelect sel;
-    std::vector<unsigned long long> raw((size_t)4 * GROUP_MAX_TARGETS);
-    const char* cls = b + L.cls_tab;
-    if (g.support) HIP_TRY(hipMemcpyAsync(g.support, cls, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-    if (g.nll_q32) HIP_TRY(hipMemcpyAsync(g.nll_q32, cls + (size_t)K * 8, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-    if (g.score_q32) HIP_TRY(hipMemcpyAsync(g.score_q32, cls + (size_t)2 * K * 8, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-    if (g.source_confusion && src)
-        HIP_TRY(hipMemcpyAsync(g.source_confusion, b + L.source_conf, (size_t)g.n_sources * K * K * 8, hipMemcpyDeviceToHost, st));
-    if (g.cover) HIP_TRY(hipMemcpyAsync(g.cover, b + L.cov, (size_t)K * 8 * 8, hipMemcpyDeviceToHost, st));
-    if (g.n_images_used) HIP_TRY(hipMemcpyAsync(g.n_images_used, b + L.n_used, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&sel, b + L.sel, sizeof(sel), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(raw.data(), b + L.raw, raw.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return group_bins(sel, raw.data(), g);
-}
-
-// zeroes every group output whose size the arguments determine
-static void group_clear(const mmc_head* h, const GroupIO& g)
-{
-    if (!h) return;
-    const size_t K = (size_t)h->K;
-    if (g.support) memset(g.support, 0, K * 8);
-    if (g.nll_q32) memset(g.nll_q32, 0, K * 8);
-    if (g.score_q32) memset(g.score_q32, 0, K * 8);
-    if (g.source_confusion && g.n_sources > 0 && (int64_t)g.n_sources * h->K * h->K <= MMC_GROUPED_MAX_SOURCE_CELLS)
-        memset(g.source_confusion, 0, (size_t)g.n_sources * K * K * 8);
-    if (g.cover) memset(g.cover, 0, K * MMC_COVER_SUMS * 8);
-    if (g.n_images_used) *g.n_images_used = 0;
-    if (g.n_bins >= 1 && g.n_bins <= MMC_GROUPED_MAX_BINS) {
-        if (g.bin_count) memset(g.bin_count, 0, (size_t)g.n_bins * 8);
-        if (g.bin_correct) memset(g.bin_correct, 0, (size_t)g.n_bins * 8);
-        if (g.bin_conf_q32) memset(g.bin_conf_q32, 0, (size_t)g.n_bins * 8);
-        if (g.bin_conf_min) memset(g.bin_conf_min, 0, (size_t)g.n_bins * 4);
-        if (g.bin_conf_max) memset(g.bin_conf_max, 0, (size_t)g.n_bins * 4);
-    }
-}
-
-static int group_check(const mmc_head* h, int64_t n, const GroupIO& g)
-{
-    if (g.n_bins < 1 || g.n_bins > MMC_GROUPED_MAX_BINS)
-        return fail(MMC_ERR_ARG, "n_bins = %d outside [1, %d]", g.n_bins, MMC_GROUPED_MAX_BINS);
-    if (g.n_sources < 0) return fail(MMC_ERR_ARG, "n_sources = %d is negative", g.n_sources);
-    if (g.n_images < 0) return fail(MMC_ERR_ARG, "n_images = %lld is negative", (long long)g.n_images);
-    if (n == 0) return g.n_images == 0 ? MMC_OK : fail(MMC_ERR_ARG, "%lld images over no rows", (long long)g.n_images);
-    if (!g.offsets) return fail(MMC_ERR_ARG, "image_offsets is NULL");
-    if (g.n_images < 1 || g.n_images > n) return fail(MMC_ERR_ARG, "n_images = %lld for %lld rows: every image owns at least one row", (long long)g.n_images, (long long)n);
-    if (g.n_images * h->K > MMC_GROUPED_MAX_COVER_CELLS)
-        return fail(MMC_ERR_ARG, "n_images * K = %lld cells of per-image counts: at most %lld", (long long)(g.n_images * h->K), (long long)MMC_GROUPED_MAX_COVER_CELLS);
-    if (g.offsets[0] != 0) return fail(MMC_ERR_ARG, "image_offsets[0] = %lld: must be 0", (long long)g.offsets[0]);
-    for (int64_t i = 0; i < g.n_images; ++i)
-        if (g.offsets[i + 1] <= g.offsets[i])
-            return fail(MMC_ERR_ARG, "image_offsets[%lld] = %lld is not above image_offsets[%lld] = %lld (offsets increase strictly: no empty image)",
-                        (long long)(i + 1), (long long)g.offsets[i + 1], (long long)i, (long long)g.offsets[i]);
-    if (g.offsets[g.n_images] != n) return fail(MMC_ERR_ARG, "image_offsets[n_images] = %lld: must be n = %lld", (long long)g.offsets[g.n_images], (long long)n);
-    if (g.source && g.n_sources > 0) {
-        if ((int64_t)g.n_sources * h->K * h->K > MMC_GROUPED_MAX_SOURCE_CELLS)
-            return fail(MMC_ERR_ARG, "n_sources * K * K = %lld cells of per-source confusion: at most %lld", (long long)g.n_sources * h->K * h->K,
-                        (long long)MMC_GROUPED_MAX_SOURCE_CELLS);
-        for (int64_t i = 0; i < g.n_images; ++i)
-            if (g.source[i] < 0 || g.source[i] >= g.n_sources)
-                return fail(MMC_ERR_ARG, "source_of_image[%lld] = %d outside [0, %d)", (long long)i, g.source[i], g.n_sources);
-    }
-    return MMC_OK;
-}
-
-extern "C" int mmc_head_evaluate_grouped(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
-                                         int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
-                                         int64_t* rank_hist, const int64_t* image_offsets, int64_t n_images, const int32_t* source_of_image,
-                                         int n_sources, int n_bins, int64_t* support, int64_t* nll_q32, int64_t* score_q32,
-                                         int64_t* source_confusion, double* cover_sums, int64_t* n_images_used, int64_t* bin_count,
-                                         int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min, float* bin_conf_max, unsigned flags,
-                                         void* hip_stream)
-{
-    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
-    const GroupIO g{image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32, source_confusion,
-                    cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max};
-    eval_clear(h, o);
-    group_clear(h, g);
-    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
-    int r = eval_check_common(h, n, label_map, n_labels, o);
-    if (r) return r;
-    if ((r = group_check(h, n, g))) return r;
-    if (n == 0) return MMC_OK;
-    if (!feats || !y) return fail(MMC_ERR_ARG, "feats/y is NULL");
-    const int hi = label_map ? n_labels : h->K;
-    for (int64_t i = 0; i < n; ++i)
-        if (y[i] < 0 || y[i] >= hi) return fail(MMC_ERR_ARG, "label index y[%lld] = %d outside [0, %d)", (long long)i, y[i], hi);
-    r = head_evaluate(h, feats, flags & MMC_IN_HOST, y, nullptr, n, label_map, n_labels, o, static_cast<hipStream_t>(hip_stream), &g);
-    if (r) { eval_clear(h, o); group_clear(h, g); }
-    return r;
-}
-
-extern "C" int mmc_head_evaluate_grouped_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
-                                             int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
-                                             int64_t* rank_hist, const int64_t* image_offsets, int64_t n_images,
-                                             const int32_t* source_of_image, int n_sources, int n_bins, int64_t* support, int64_t* nll_q32,
-                                             int64_t* score_q32, int64_t* source_confusion, double* cover_sums, int64_t* n_images_used,
-                                             int64_t* bin_count, int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min,
-                                             float* bin_conf_max, void* hip_stream)
-{
-    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
-    const GroupIO g{image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32, source_confusion,
-                    cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max};
-    eval_clear(h, o);
-    group_clear(h, g);
-    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
-    if (!fs) return fail(MMC_ERR_ARG, "feature set handle is NULL");
-    if (fs->dim != h->input_dim) return fail(MMC_ERR_ARG, "feature set has %d columns, head expects %d", fs->dim, h->input_dim);
-    if (fs->device != h->device) return fail(MMC_ERR_ARG, "feature set is on device %d, head on device %d", fs->device, h->device);
-    if (first < 0 || n < 0 || first > fs->n || n > fs->n - first)
-        return fail(MMC_ERR_ARG, "rows [%lld, %lld + %lld) outside the set's %lld rows", (long long)first, (long long)first, (long long)n,
-                    (long long)fs->n);
-    int r = eval_check_common(h, n, label_map, n_labels, o);
-    if (r) return r;
-    if (label_map ? fs->K != n_labels : fs->K != h->K)
-        return fail(MMC_ERR_ARG, "feature set has %d classes, %s %d", fs->K, label_map ? "label_map covers" : "head", label_map ? n_labels : h->K);
-    if ((r = group_check(h, n, g))) return r;
-    if (n == 0) return MMC_OK;
-    r = head_evaluate(h, fs->X + (size_t)first * fs->dim, 0u, nullptr, fs->y + first, n, label_map, n_labels, o,
-                      static_cast<hipStream_t>(hip_stream), &g);
-    if (r) { eval_clear(h, o); group_clear(h, g); }
-    return r;
-}
-
-// rows of features mmc_classify_patches keeps between backbone and head: a larger call works through chunks of exactly this size
-// (and one remainder), so the (patches chunk, feature buffer, n) combinations of a repeated call recur and keep their graphs
-static const int64_t CLASSIFY_CHUNK = 4096;
-
-extern "C" int mmc_classify_patches(mmc_backbone* bb, mmc_head* h, const void* patches, int64_t n, int k, int32_t* idx,
-                                    float* scores, unsigned flags, void* hip_stream)
-{
-    if (!bb) return fail(MMC_ERR_ARG, "backbone handle is NULL");
-    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
-    if (bb->device != h->device)
-        return fail(MMC_ERR_ARG, "backbone lives on device %d, head on device %d", bb->device, h->device);
-    if (bb->feat != h->input_dim)
-        return fail(MMC_ERR_ARG, "backbone feature_dim %d != head input_dim %d", bb->feat, h->input_dim);
-    if (n < 0) return fail(MMC_ERR_ARG, "n = %lld is negative", (long long)n);
-    if (k < 1 || k > h->K) return fail(MMC_ERR_ARG, "k = %d is outside [1, %d] (the head has %d classes)", k, h->K, h->K);
-    if (n == 0) return MMC_OK;
-    if (!patches) return fail(MMC_ERR_ARG, "patches is NULL");
-    if (!idx || !scores) return fail(MMC_ERR_ARG, "idx/scores is NULL");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t want = n < CLASSIFY_CHUNK ? n : CLASSIFY_CHUNK;
-    if (want > h->cls_cap) {   // (hipFree waits for whatever still reads the old buffer)
-        hipFree(h->cls_feats);
-        h->cls_feats = nullptr; h->cls_cap = 0;
-        HIP_TRY(hipMalloc((void**)&h->cls_feats, (size_t)want * h->input_dim * 4 + 256));
-        h->cls_cap = want;
-    }
-    const size_t psz = (size_t)IMG * IMG * 3;
-    const uint8_t* in = static_cast<const uint8_t*>(patches);
-    for (int64_t off = 0; off < n; off += CLASSIFY_CHUNK) {
-        const int64_t cur = (n - off) < CLASSIFY_CHUNK ? (n - off) : CLASSIFY_CHUNK;
-        int r = mmc_backbone_extract(bb, in + (size_t)off * psz, cur, h->cls_feats, flags & MMC_IN_HOST, st);
-        if (r) return r;
-        r = mmc_head_topk(h, h->cls_feats, cur, k, idx + (size_t)off * k, scores + (size_t)off * k, nullptr, flags & MMC_OUT_HOST, st);
-        if (r) return r;
-    }
     return MMC_OK;
 }

@@ -128,31 +128,37 @@ class DeviceHead:
         except Exception:
             pass
 
-    def predict(self, feats, want_argmax: bool = True):
-        """feats: (N,input_dim) float32, numpy (host) or torch cuda tensor.
-        Returns (proba (N,K) float32, argmax (N,) int32) of the same kind."""
-        lib = _lib.lib()
-        st = _current_stream_ptr(self.device_index)
+    def _input(self, feats):
+        """feats -> (x, pointer, n, flags, alloc): numpy rows are read from and answered in host memory, a float32 cuda tensor on
+        the device.  ``alloc(shape, dtype_name)`` -> (an empty output of the same kind as ``feats``, its pointer); ``x`` owns the
+        memory behind ``pointer``."""
         if isinstance(feats, np.ndarray):
             x = np.ascontiguousarray(feats, dtype=np.float32)
-            n = x.shape[0]
-            proba = np.empty((n, self.n_classes), dtype=np.float32)
-            arg = np.empty((n,), dtype=np.int32)
-            if n:
-                _lib.check(lib.mmc_head_predict(self._h, x.ctypes.data, n, proba.ctypes.data,
-                                                arg.ctypes.data if want_argmax else None,
-                                                _lib.MMC_IN_HOST | _lib.MMC_OUT_HOST, st))
-            return proba, arg
+            if x.ndim != 2 or x.shape[1] != self.input_dim:
+                raise ValueError(f"features must be (N, {self.input_dim}); got {x.shape}")
+
+            def alloc(shape, dt):
+                a = np.empty(shape, dtype=getattr(np, dt))
+                return a, a.ctypes.data
+            return x, x.ctypes.data, x.shape[0], _lib.MMC_IN_HOST | _lib.MMC_OUT_HOST, alloc
         import torch
         x = feats.contiguous()
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.input_dim:
             raise ValueError(f"features must be a float32 cuda tensor (N, {self.input_dim}); got {tuple(x.shape)}")
-        n = x.shape[0]
-        proba = torch.empty((n, self.n_classes), dtype=torch.float32, device=x.device)
-        arg = torch.empty((n,), dtype=torch.int32, device=x.device)
+
+        def alloc(shape, dt):
+            a = torch.empty(shape, dtype=getattr(torch, dt), device=x.device)
+            return a, a.data_ptr()
+        return x, x.data_ptr(), x.shape[0], 0, alloc
+
+    def predict(self, feats, want_argmax: bool = True):
+        """feats: (N,input_dim) float32, numpy (host) or torch cuda tensor.
+        Returns (proba (N,K) float32, argmax (N,) int32) of the same kind."""
+        x, ptr, n, flags, alloc = self._input(feats)
+        (proba, pp), (arg, ap) = alloc((n, self.n_classes), "float32"), alloc((n,), "int32")
         if n:
-            _lib.check(lib.mmc_head_predict(self._h, x.data_ptr(), n, proba.data_ptr(),
-                                            arg.data_ptr() if want_argmax else None, 0, st))
+            _lib.check(_lib.lib().mmc_head_predict(self._h, ptr, n, pp, ap if want_argmax else None, flags,
+                                                   _current_stream_ptr(self.device_index)))
         return proba, arg
 
     def topk(self, feats, k: int, want_proba: bool = False):
@@ -163,31 +169,11 @@ class DeviceHead:
         k = int(k)
         if not 1 <= k <= self.n_classes:
             raise ValueError(f"k = {k} is outside [1, {self.n_classes}]")
-        lib = _lib.lib()
-        if isinstance(feats, np.ndarray):
-            x = np.ascontiguousarray(feats, dtype=np.float32)
-            if x.ndim != 2 or x.shape[1] != self.input_dim:
-                raise ValueError(f"features must be (N, {self.input_dim}); got {x.shape}")
-            n = x.shape[0]
-            idx = np.empty((n, k), dtype=np.int32)
-            scores = np.empty((n, k), dtype=np.float32)
-            proba = np.empty((n, self.n_classes), dtype=np.float32) if want_proba else None
-            if n:
-                _lib.check(lib.mmc_head_topk(self._h, x.ctypes.data, n, k, idx.ctypes.data, scores.ctypes.data,
-                                             proba.ctypes.data if want_proba else None,
-                                             _lib.MMC_IN_HOST | _lib.MMC_OUT_HOST, _current_stream_ptr(self.device_index)))
-            return (idx, scores, proba) if want_proba else (idx, scores)
-        import torch
-        x = feats.contiguous()
-        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.input_dim:
-            raise ValueError(f"features must be a float32 cuda tensor (N, {self.input_dim}); got {tuple(x.shape)}")
-        n = x.shape[0]
-        idx = torch.empty((n, k), dtype=torch.int32, device=x.device)
-        scores = torch.empty((n, k), dtype=torch.float32, device=x.device)
-        proba = torch.empty((n, self.n_classes), dtype=torch.float32, device=x.device) if want_proba else None
+        x, ptr, n, flags, alloc = self._input(feats)
+        (idx, ip), (scores, sp) = alloc((n, k), "int32"), alloc((n, k), "float32")
+        proba, pp = alloc((n, self.n_classes), "float32") if want_proba else (None, None)
         if n:
-            _lib.check(lib.mmc_head_topk(self._h, x.data_ptr(), n, k, idx.data_ptr(), scores.data_ptr(),
-                                         proba.data_ptr() if want_proba else None, 0, _current_stream_ptr(self.device_index)))
+            _lib.check(_lib.lib().mmc_head_topk(self._h, ptr, n, k, ip, sp, pp, flags, _current_stream_ptr(self.device_index)))
         return (idx, scores, proba) if want_proba else (idx, scores)
 
 

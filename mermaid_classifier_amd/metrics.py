@@ -25,8 +25,7 @@ import numpy as np
 
 from . import _lib
 from .backbone import _current_stream_ptr
-from .featureset import FeatureSet
-from .validation import MAX_ROWS_PER_CALL, Validation, _host_labels, _model_parts, _ptr, label_map
+from .validation import MAX_ROWS_PER_CALL, Validation, _Outputs, _prepare, _ptr, _set_labels
 
 __all__ = ["grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability"]
 
@@ -243,28 +242,8 @@ def grouped_validate(model, data, image_sizes, *, source_of_image=None, n_bins: 
     (read in place) or one ``(X, y)`` pair; ``image_sizes[i]`` is the number of points of image ``i``, in row order (each image's
     points are contiguous, cover.py:34-36); ``source_of_image[i]`` an integer source id.  Everything is checked on the host before
     the device is touched.  One call covers a whole split: more than ``MAX_ROWS_PER_CALL`` rows is a ``ValueError``."""
-    if not isinstance(rows, bool):
-        raise ValueError(f"rows must be True or False, got {rows!r}")
-    get_head, classes, dim = _model_parts(model)
-    K = len(classes)
-    if isinstance(data, FeatureSet):
-        if data.dim != dim:
-            raise ValueError(f"the feature set has {data.dim} features, expected {dim}")
-        n = len(data)
-        X = yi = None
-        lmap = None if data.classes.tolist() == classes else np.ascontiguousarray(label_map(classes, data.classes))
-    else:
-        if not (isinstance(data, (tuple, list)) and len(data) == 2):
-            raise ValueError("data must be a FeatureSet or one (X, y) pair")
-        X = np.ascontiguousarray(np.asarray(data[0], dtype=np.float32))
-        if X.ndim != 2:
-            raise ValueError(f"X must be 2D, got shape {X.shape}")
-        if X.shape[1] != dim:
-            raise ValueError(f"X has {X.shape[1]} features, expected {dim}")
-        n = X.shape[0]
-        yi, lmap = _host_labels(classes, data[1], n, True)
-    if n == 0:
-        raise ValueError("grouped_validate: no rows")
+    get_head, classes, ((rows_src, yi, lmap),) = _prepare(model, data, rows, True, "grouped_validate", one_pair=True)
+    K, n = len(classes), len(rows_src)
     if n > MAX_ROWS_PER_CALL:
         raise ValueError(f"{n} rows: one grouped call covers a whole split of at most {MAX_ROWS_PER_CALL} rows")
     offsets, src, S = _check_groups(n, image_sizes, source_of_image, n_bins)
@@ -273,10 +252,8 @@ def grouped_validate(model, data, image_sizes, *, source_of_image=None, n_bins: 
     if S * K * K > _lib.MMC_GROUPED_MAX_SOURCE_CELLS:
         raise ValueError(f"{S} sources x {K} x {K} classes: at most {_lib.MMC_GROUPED_MAX_SOURCE_CELLS} per-source cells")
     n_bins = int(n_bins)
-    tot = np.zeros(_lib.MMC_EVAL_TOTALS, np.int64)
-    conf, hist = np.zeros((K, K), np.int64), np.zeros(K, np.int64)
-    est, score, rank, p_true = ((np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.float32))
-                                if rows else (None,) * 4)
+    out = _Outputs(K, rows)
+    c = out.call(n)
     support, nll, sq = np.zeros(K, np.int64), np.zeros(K, np.int64), np.zeros(K, np.int64)
     sconf = np.zeros((S, K, K), np.int64) if S else None
     cover = np.zeros((K, _lib.MMC_COVER_SUMS), np.float64)
@@ -286,22 +263,15 @@ def grouped_validate(model, data, image_sizes, *, source_of_image=None, n_bins: 
     head = get_head()
     lib = _lib.lib()
     st = _current_stream_ptr(head.device_index)
-    common = (_ptr(lmap), 0 if lmap is None else len(lmap), _ptr(est), _ptr(score), _ptr(rank), _ptr(p_true), tot.ctypes.data,
-              conf.ctypes.data, hist.ctypes.data, offsets.ctypes.data, len(offsets) - 1, _ptr(src), S, n_bins, support.ctypes.data,
-              nll.ctypes.data, sq.ctypes.data, _ptr(sconf), cover.ctypes.data, used.ctypes.data, bc.ctypes.data, bk.ctypes.data,
-              bq.ctypes.data, bmin.ctypes.data, bmax.ctypes.data)
-    if X is None:
-        _lib.check(lib.mmc_head_evaluate_grouped_set(head._h, data._handle(), 0, n, *common, st))
-        gt = None
+    common = (_ptr(lmap), 0 if lmap is None else len(lmap), *c.args, offsets.ctypes.data, len(offsets) - 1, _ptr(src), S, n_bins,
+              support.ctypes.data, nll.ctypes.data, sq.ctypes.data, _ptr(sconf), cover.ctypes.data, used.ctypes.data, bc.ctypes.data,
+              bk.ctypes.data, bq.ctypes.data, bmin.ctypes.data, bmax.ctypes.data)
+    if yi is None:
+        _lib.check(lib.mmc_head_evaluate_grouped_set(head._h, rows_src._handle(), 0, n, *common, st))
         if rows:
-            y0 = np.empty(n, np.int32)
-            _lib.check(lib.mmc_featureset_read(data._handle(), 0, n, None, y0.ctypes.data, st))
-            gt = y0 if lmap is None else lmap[y0]
+            c.gt = _set_labels(rows_src, 0, n, lmap, st)
     else:
-        _lib.check(lib.mmc_head_evaluate_grouped(head._h, X.ctypes.data, yi.ctypes.data, n, *common, _lib.MMC_IN_HOST, st))
-        gt = (yi if lmap is None else lmap[yi]) if rows else None
-    t = tot.tolist()
-    val = Validation(classes, gt, est, None if score is None else score.astype(np.float64), rank, p_true, conf, hist, t[0], t[1], t[2],
-                     t[3], t[4])
-    return GroupedValidation(val, CoverStats(cover, int(used[0])), SourceStats(sconf) if S else None, Reliability(bc, bk, bq, bmin, bmax),
-                             support, nll, sq)
+        _lib.check(lib.mmc_head_evaluate_grouped(head._h, rows_src.ctypes.data, yi.ctypes.data, n, *common, _lib.MMC_IN_HOST, st))
+        c.gt = yi if lmap is None else lmap[yi]
+    return GroupedValidation(out.result(classes), CoverStats(cover, int(used[0])), SourceStats(sconf) if S else None,
+                             Reliability(bc, bk, bq, bmin, bmax), support, nll, sq)

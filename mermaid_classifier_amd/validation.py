@@ -160,78 +160,28 @@ def _host_labels(classes: List[Any], y, n: int, strict: bool):
             np.ascontiguousarray(np.append(np.arange(K, dtype=np.int32), np.int32(-1))))
 
 
-class _Acc:
-    """Collects the outputs of the calls of one ``validate``."""
-
-    def __init__(self, K: int, rows: bool):
-        self.K, self.rows = K, rows
-        self.totals = np.zeros(_lib.MMC_EVAL_TOTALS, np.int64)
-        self.confusion = np.zeros((K, K), np.int64)
-        self.rank_hist = np.zeros(K, np.int64)
-        self.parts: List[tuple] = []
-
-    def buffers(self, n: int):
-        tot = np.zeros(_lib.MMC_EVAL_TOTALS, np.int64)
-        conf = np.zeros((self.K, self.K), np.int64)
-        hist = np.zeros(self.K, np.int64)
-        per_row = (np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.float32)) if self.rows else None
-        return tot, conf, hist, per_row
-
-    def add(self, gt, tot, conf, hist, per_row):
-        self.totals += tot
-        self.confusion += conf
-        self.rank_hist += hist
-        if self.rows:
-            self.parts.append((gt,) + per_row)
-
-    def result(self, classes) -> Validation:
-        t = self.totals.tolist()
-        if self.rows:
-            gt, est, score, rank, p_true = (np.concatenate([p[i] for p in self.parts]) for i in range(5))
-        else:
-            gt = est = score = rank = p_true = None
-        return Validation(classes, gt, est, None if score is None else score.astype(np.float64), rank, p_true, self.confusion,
-                          self.rank_hist, t[0], t[1], t[2], t[3], t[4])
-
-
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data
 
 
-def _validate(model, data, rows: bool, strict: bool) -> Validation:
+def _prepare(model, data, rows, strict: bool, who: str, one_pair: bool = False):
+    """What ``validate`` and ``grouped_validate`` do before the device is touched -> (head getter, classes, sources).  ``sources`` is
+    ``[(FeatureSet, None, map)]`` or the non-empty host batches ``[(X float32, y int32, map), ...]``, every one checked; ``map`` is the
+    label map of that source, or None when its labels index the model's classes."""
     if not isinstance(rows, bool):
         raise ValueError(f"rows must be True or False, got {rows!r}")
     get_head, classes, dim = _model_parts(model)
-    K = len(classes)
-    acc = _Acc(K, rows)
     if isinstance(data, FeatureSet):
         if data.dim != dim:
             raise ValueError(f"the feature set has {data.dim} features, expected {dim}")
-        n = len(data)
-        if n == 0:
-            raise ValueError("validate: no rows")
+        if len(data) == 0:
+            raise ValueError(f"{who}: no rows")
         same = data.classes.tolist() == classes
-        lmap = None if same else np.ascontiguousarray(label_map(classes, data.classes))
-        head = get_head()
-        lib = _lib.lib()
-        st = _current_stream_ptr(head.device_index)
-        for first in range(0, n, MAX_ROWS_PER_CALL):
-            cur = min(MAX_ROWS_PER_CALL, n - first)
-            tot, conf, hist, per_row = acc.buffers(cur)
-            est, score, rank, p_true = per_row if rows else (None,) * 4
-            _lib.check(lib.mmc_head_evaluate_set(head._h, data._handle(), first, cur, _ptr(lmap), 0 if lmap is None else len(lmap),
-                                                 _ptr(est), _ptr(score), _ptr(rank), _ptr(p_true), tot.ctypes.data, conf.ctypes.data,
-                                                 hist.ctypes.data, st))
-            gt = None
-            if rows:   # the labels alone come back (no feature row does)
-                yi = np.empty(cur, np.int32)
-                _lib.check(lib.mmc_featureset_read(data._handle(), first, cur, None, yi.ctypes.data, st))
-                gt = yi if lmap is None else lmap[yi]
-            acc.add(gt, tot, conf, hist, per_row)
-        return acc.result(classes)
-    # host batches: every argument of every batch is checked before the first reaches the device
-    batches = []
-    for x, y in _batches(data):
+        return get_head, classes, [(data, None, None if same else np.ascontiguousarray(label_map(classes, data.classes)))]
+    if one_pair and not (isinstance(data, (tuple, list)) and len(data) == 2):
+        raise ValueError("data must be a FeatureSet or one (X, y) pair")
+    sources = []
+    for x, y in ([(data[0], data[1])] if one_pair else _batches(data)):
         X = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
         if X.ndim != 2:
             raise ValueError(f"X must be 2D, got shape {X.shape}")
@@ -239,23 +189,74 @@ def _validate(model, data, rows: bool, strict: bool) -> Validation:
             raise ValueError(f"X has {X.shape[1]} features, expected {dim}")
         yi, lmap = _host_labels(classes, y, X.shape[0], strict)
         if X.shape[0]:
-            batches.append((X, yi, lmap))
-    if not batches:
-        raise ValueError("validate: no rows")
+            sources.append((X, yi, lmap))
+    if not sources:
+        raise ValueError(f"{who}: no rows")
+    return get_head, classes, sources
+
+
+class _Call:
+    """One ``mmc_head_evaluate*`` call's host outputs: ``args`` are its (est, score, rank, p_true, totals, confusion, rank_hist)
+    arguments; ``gt`` is set by the caller when rows are kept."""
+
+    def __init__(self, K: int, n: int, rows: bool):
+        self.gt = None
+        self.per_row = (np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.float32)) if rows else (None,) * 4
+        self.tables = (np.zeros(_lib.MMC_EVAL_TOTALS, np.int64), np.zeros((K, K), np.int64), np.zeros(K, np.int64))
+        self.args = tuple(_ptr(a) for a in self.per_row + self.tables)
+
+
+class _Outputs:
+    """Allocates the evaluate outputs of the calls of one validation and turns them into a ``Validation``."""
+
+    def __init__(self, K: int, rows: bool):
+        self.K, self.rows, self.calls = K, rows, []
+
+    def call(self, n: int) -> _Call:
+        self.calls.append(_Call(self.K, n, self.rows))
+        return self.calls[-1]
+
+    def result(self, classes) -> Validation:
+        tot, conf, hist = (sum(c.tables[i] for c in self.calls) for i in range(3))
+        if self.rows:
+            cat = (lambda v: v[0]) if len(self.calls) == 1 else np.concatenate
+            gt = cat([c.gt for c in self.calls])
+            est, score, rank, p_true = (cat([c.per_row[i] for c in self.calls]) for i in range(4))
+            score = score.astype(np.float64)
+        else:
+            gt = est = score = rank = p_true = None
+        return Validation(classes, gt, est, score, rank, p_true, conf, hist, *tot.tolist())
+
+
+def _set_labels(data: FeatureSet, first: int, n: int, lmap, st) -> np.ndarray:
+    """The ground truth of rows [first, first + n) of a feature set as model class indices: the labels alone come back (no feature
+    row does)."""
+    y = np.empty(n, np.int32)
+    _lib.check(_lib.lib().mmc_featureset_read(data._handle(), first, n, None, y.ctypes.data, st))
+    return y if lmap is None else lmap[y]
+
+
+def _validate(model, data, rows: bool, strict: bool) -> Validation:
+    get_head, classes, sources = _prepare(model, data, rows, strict, "validate")
+    out = _Outputs(len(classes), rows)
     head = get_head()
     lib = _lib.lib()
     st = _current_stream_ptr(head.device_index)
-    for X, yi, lmap in batches:
-        for first in range(0, X.shape[0], MAX_ROWS_PER_CALL):
-            cur = min(MAX_ROWS_PER_CALL, X.shape[0] - first)
-            tot, conf, hist, per_row = acc.buffers(cur)
-            est, score, rank, p_true = per_row if rows else (None,) * 4
-            ys = yi[first:first + cur]
-            _lib.check(lib.mmc_head_evaluate(head._h, X[first:first + cur].ctypes.data, ys.ctypes.data, cur, _ptr(lmap),
-                                             0 if lmap is None else len(lmap), _ptr(est), _ptr(score), _ptr(rank), _ptr(p_true),
-                                             tot.ctypes.data, conf.ctypes.data, hist.ctypes.data, _lib.MMC_IN_HOST, st))
-            acc.add(ys if lmap is None else lmap[ys], tot, conf, hist, per_row)
-    return acc.result(classes)
+    for src, yi, lmap in sources:
+        map_args = (_ptr(lmap), 0 if lmap is None else len(lmap))
+        for first in range(0, len(src), MAX_ROWS_PER_CALL):
+            cur = min(MAX_ROWS_PER_CALL, len(src) - first)
+            c = out.call(cur)
+            if yi is None:
+                _lib.check(lib.mmc_head_evaluate_set(head._h, src._handle(), first, cur, *map_args, *c.args, st))
+                if rows:
+                    c.gt = _set_labels(src, first, cur, lmap, st)
+            else:
+                ys = yi[first:first + cur]
+                _lib.check(lib.mmc_head_evaluate(head._h, src[first:first + cur].ctypes.data, ys.ctypes.data, cur, *map_args, *c.args,
+                                                 _lib.MMC_IN_HOST, st))
+                c.gt = ys if lmap is None else lmap[ys]
+    return out.result(classes)
 
 
 def validate(model, data, *, rows: bool = True) -> Validation:

@@ -44,8 +44,9 @@ def _sizes(rng, n, hi=40):
     return np.array(out, np.int64)
 
 
-def c_grouped(head, X, y, sizes, source=None, n_sources=0, n_bins=20, lmap=None, fs=None, offsets=None, expect=0):
-    """mmc_head_evaluate_grouped on host rows, or _set on the rows of ``fs``; every output starts from -7.  -> dict of outputs."""
+def c_grouped(head, X, y, sizes, source=None, n_sources=0, n_bins=20, lmap=None, fs=None, offsets=None, expect=0, first=0):
+    """mmc_head_evaluate_grouped on host rows, or _set on rows [first, first + len(y)) of ``fs``; every output starts from -7.
+    -> dict of outputs."""
     from mermaid_classifier_amd import _lib
     K, n = head.n_classes, len(y)
     y = np.ascontiguousarray(y, np.int32)
@@ -66,7 +67,7 @@ def c_grouped(head, X, y, sizes, source=None, n_sources=0, n_bins=20, lmap=None,
                                          "bin_correct", "bin_conf_q32", "bin_conf_min", "bin_conf_max")]
     lib = _lib.lib()
     if fs is not None:
-        status = lib.mmc_head_evaluate_grouped_set(head._h, fs._handle(), 0, n, *common, None)
+        status = lib.mmc_head_evaluate_grouped_set(head._h, fs._handle(), first, n, *common, None)
     else:
         X = np.ascontiguousarray(X, np.float32)
         status = lib.mmc_head_evaluate_grouped(head._h, X.ctypes.data, y.ctypes.data, n, *common, _lib.MMC_IN_HOST, None)
@@ -369,3 +370,88 @@ def test_grouped_validate_agrees_with_validate_and_the_restatement():
     assert np.array_equal(gs.validation.confusion, plain.confusion) and np.array_equal(gs.sources.confusion, gv.sources.confusion)
     assert gs.cover.sums.tobytes() == gv.cover.sums.tobytes() and gs.reliability.ece == gv.reliability.ece
     fs.close()
+
+
+# ---- the host paths every entry point shares: one handle's growing buffers, the padded input, a set slice ----
+
+def test_interleaved_entry_points_on_one_handle_match_fresh_handles():
+    """predict, evaluate, top-k and grouped evaluate share one handle's device buffers, and each call grows the ones it needs:
+    8 rows, 512, 300, 512, 512, 8 on one head, every output bit for bit the same call's on a head that has done nothing else."""
+    from mermaid_classifier_amd.inference import DeviceHead
+    from test_gpu_validation import c_evaluate, same_outputs
+    params = _load("head_fixture")._head.params
+    X = np.load(GOLDEN / "head_fixture_io.npz")["X"]
+    assert X.shape == (512, 8)
+    rng = np.random.default_rng(5)
+    y = rng.integers(0, 5, 512).astype(np.int32)
+    sizes = _sizes(rng, 512, 30)
+    source = rng.integers(0, 3, len(sizes))
+    calls = [lambda h: h.predict(X[:8]),
+             lambda h: c_evaluate(h, X, y),
+             lambda h: h.topk(X[:300], 3),
+             lambda h: c_grouped(h, X, y, sizes, source, 3),
+             lambda h: h.predict(X),
+             lambda h: h.topk(X[:8], 3)]
+    one = DeviceHead(params)
+    for i, call in enumerate(calls):
+        got, want = call(one), call(DeviceHead(params))
+        if isinstance(got, dict) and "support" in got:
+            same_bits(got, want)
+        elif isinstance(got, dict):
+            same_outputs(got, want)
+        else:
+            for a, b in zip(got, want):
+                assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f"call {i}"
+
+
+def test_input_width_that_is_no_multiple_of_4_matches_the_zero_padded_twin():
+    """A 6 -> 16 -> 5 head pads its rows to 8 columns on the device (memset + strided copy, for host rows, device rows and a feature
+    set alike); its twin 8 -> 16 -> 5 with two zero weight columns, fed the rows with two zero columns, computes on the same
+    padded data.  predict, top-k and evaluate of the narrow head must give the twin's bits on every route; 37 rows: the last
+    workgroup is ragged."""
+    import torch
+    from mermaid_classifier_amd import FeatureSet
+    from mermaid_classifier_amd.inference import DeviceHead, HeadParams
+    from test_gpu_validation import c_evaluate, c_evaluate_set, same_outputs
+    rng = np.random.default_rng(6)
+    W1, b1 = rng.normal(0, 0.5, (16, 6)).astype(np.float32), rng.normal(0, 0.2, 16).astype(np.float32)
+    W2, b2 = rng.normal(0, 0.5, (5, 16)).astype(np.float32), rng.normal(0, 0.2, 5).astype(np.float32)
+    a, b = rng.uniform(-9, -4, 5).astype(np.float32), rng.uniform(0.5, 3, 5).astype(np.float32)
+    narrow = DeviceHead(HeadParams([W1, W2], [b1, b2], a, b))
+    twin = DeviceHead(HeadParams([np.concatenate([W1, np.zeros((16, 2), np.float32)], 1), W2], [b1, b2], a, b))
+    assert (narrow.input_dim, twin.input_dim) == (6, 8)
+    X6 = rng.normal(0.3, 0.6, (37, 6)).astype(np.float32)
+    X8 = np.concatenate([X6, np.zeros((37, 2), np.float32)], 1)
+    y = rng.integers(0, 5, 37).astype(np.int32)
+
+    def bits(got, want, what):
+        for g, w in zip(got, want):
+            g = g.cpu().numpy() if isinstance(g, torch.Tensor) else g
+            assert g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes(), what
+
+    want_predict, want_topk, want_eval = twin.predict(X8), twin.topk(X8, 3, want_proba=True), c_evaluate(twin, X8, y)
+    assert len(np.unique(want_predict[1])) > 1
+    xd = torch.from_numpy(X6).cuda()
+    bits(narrow.predict(X6), want_predict, "predict, host rows")
+    bits(narrow.predict(xd), want_predict, "predict, device rows")
+    bits(narrow.topk(X6, 3, want_proba=True), want_topk, "topk, host rows")
+    bits(narrow.topk(xd, 3, want_proba=True), want_topk, "topk, device rows")
+    same_outputs(c_evaluate(narrow, X6, y), want_eval)
+    same_outputs(c_evaluate(narrow, X6, y, device=True), want_eval)
+    same_outputs(c_evaluate_set(narrow, FeatureSet(6, list(range(5))).append(X6, y), 0, 37), want_eval)
+
+
+def test_grouped_set_from_a_later_first_row_matches_the_host_slice():
+    """mmc_head_evaluate_grouped_set on rows [11, 512) of a set (the image offsets cover those rows) == mmc_head_evaluate_grouped on
+    the host slice, in every table and every bit."""
+    head = _load("head_fixture")._head
+    X = np.load(GOLDEN / "head_fixture_io.npz")["X"]
+    rng = np.random.default_rng(8)
+    _, arg = head.predict(X)
+    y = np.where(rng.random(512) < 0.6, arg, rng.integers(0, 5, 512)).astype(np.int32)
+    sizes = _sizes(rng, 512 - 11, 30)
+    source = rng.integers(0, 3, len(sizes))
+    host = c_grouped(head, X[11:], y[11:], sizes, source, 3)
+    sliced = c_grouped(head, None, y[11:], sizes, source, 3, fs=_set_of(head, X, y), first=11)
+    same_bits(host, sliced)
+    assert host["totals"][0] == 501 and host["support"].sum() == 501 and (host["est"] >= 0).all()
