@@ -395,6 +395,47 @@ int mmc_head_evaluate_grouped_set(mmc_head* h, mmc_featureset* fs, int64_t first
                                   int64_t* bin_count, int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min, float* bin_conf_max,
                                   void* hip_stream);
 
+/* ---- ranking validation: per-class ranks, hierarchical top-k -----------------------------------------------------------
+ * Replaces: the parts of compute_ranking (mermaid_classifier/pyspacer/metrics/ranking.py) that need more than the overall rank
+ *   histogram and that otherwise need the N x K probability matrix and np.argsort(-proba) on the host:
+ *     per-category top-k / MRR (ranking.py:88-128)   the rank of the true class, broken down by true class
+ *     hierarchical top-k (ranking.py:163-209)        per row the kmax best classes in order and the largest taxonomic similarity to
+ *                                                    the true class among the first k of them
+ * The call is mmc_head_evaluate(_set) -- same arguments, and est / score / rank / p_true / totals / confusion / rank_hist come back
+ * with the same bits -- with one more kernel per chunk on the chunk's logits.  Extra arguments (host pointers):
+ *   sim_level[g * K + c]   uint8, K x K, row = true class: the similarity of classes g and c as a level code in [0, n_levels).  Codes
+ *                          are monotone in the similarity (the caller keeps the code -> value table), so the largest level is the
+ *                          largest similarity.  NULL together with hier_hist: only class_rank_hist is made, no selection runs.
+ *   n_levels               in [1, 256]
+ *   kmax                   in [1, min(K, MMC_RANKED_MAX_K)]: selection rounds per row
+ * A row is SCORED exactly when mmc_head_evaluate adds it to confusion; unscored rows enter neither table.  With g the true class of
+ * a scored row (int64 counts, integer atomics: independent of row order and of how rows are split over chunks or calls):
+ *   class_rank_hist[g * K + rank - 1]    K x K, or NULL.  Its column sums are rank_hist, its row sums the scored rows per class,
+ *                                        class_rank_hist[g * K] = confusion[g * K + g].
+ *   hier_hist[j * n_levels + m]          kmax x n_levels, or NULL: rows whose largest sim_level[g][c_i] over i <= j is m, where
+ *                                        c_0, c_1, ... are the row's classes in the order of mmc_head_topk: score descending and EQUAL
+ *                                        SCORES IN CLASS ORDER (the reference's np.argsort(-proba) leaves ties open).  Every row
+ *                                        j sums to the number of scored rows.
+ * Everything is checked before the first launch -- the checks of mmc_head_evaluate(_set), and: n_levels or kmax out of range, a
+ *   sim_level entry >= n_levels, sim_level without hier_hist or the reverse -- and a rejected call returns MMC_ERR_ARG with nothing
+ *   launched and totals / confusion / rank_hist / class_rank_hist zeroed (the K-sized ones only with a head handle), hier_hist when
+ *   n_levels lies in [1, 256] and kmax in [1, MMC_RANKED_MAX_K].  n == 0 is MMC_OK with zeroed tables.
+ * The uploaded levels and the device tables live in scratch that belongs to the head handle, grows on demand and is freed with it.
+ *   The call synchronises `hip_stream` once, at the end. */
+#define MMC_RANKED_MAX_K 16
+int mmc_head_evaluate_ranked(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
+                             int32_t* est, float* score, int32_t* rank, float* p_true, int64_t totals[MMC_EVAL_TOTALS],
+                             int64_t* confusion /* K*K or NULL */, int64_t* rank_hist /* K or NULL */,
+                             const uint8_t* sim_level /* K*K or NULL */, int n_levels, int kmax,
+                             int64_t* class_rank_hist /* K*K or NULL */, int64_t* hier_hist /* kmax*n_levels or NULL */,
+                             unsigned flags, void* hip_stream);
+int mmc_head_evaluate_ranked_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
+                                 int32_t* est, float* score, int32_t* rank, float* p_true, int64_t totals[MMC_EVAL_TOTALS],
+                                 int64_t* confusion /* K*K or NULL */, int64_t* rank_hist /* K or NULL */,
+                                 const uint8_t* sim_level /* K*K or NULL */, int n_levels, int kmax,
+                                 int64_t* class_rank_hist /* K*K or NULL */, int64_t* hier_hist /* kmax*n_levels or NULL */,
+                                 void* hip_stream);
+
 /* ---- multi-GPU: the gather of the sharded path --------------------------------------------------------------------
  * The path shards by patches (contiguous blocks of the row range per rank, weights replicated, no exchange during compute);
  * its one exchange step is the all-gather of the ranks' (n_r, 1280) feature blocks.  Replaces: nothing in the reference's

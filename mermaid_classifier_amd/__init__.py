@@ -12,6 +12,7 @@ from .featureset import FeatureSet  # noqa: F401
 from .training import epoch_loop, train_and_validate, train_classifier  # noqa: F401
 from .validation import Validation, previous_accuracies, validate  # noqa: F401
 from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, grouped_validate  # noqa: F401
+from .ranking import RankedValidation, ranking_validate, similarity_levels  # noqa: F401
 
 __all__ = [
     "EfficientNetExtractor", "build_extractor_class", "resolve_device", "verify_device_numerics",
@@ -22,4 +23,5 @@ __all__ = [
     "FeatureSet", "epoch_loop", "train_classifier", "train_and_validate",
     "Validation", "validate", "previous_accuracies",
     "grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability",
+    "ranking_validate", "RankedValidation", "similarity_levels",
 ]

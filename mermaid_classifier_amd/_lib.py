@@ -18,6 +18,7 @@ MMC_IN_HOST, MMC_OUT_HOST = 1, 2
 MMC_EVAL_TOTALS = 5   # include/mmc.h: length of mmc_head_evaluate's totals
 MMC_GROUPED_MAX_BINS, MMC_COVER_SUMS = 64, 8   # include/mmc.h: mmc_head_evaluate_grouped
 MMC_GROUPED_MAX_SOURCE_CELLS, MMC_GROUPED_MAX_COVER_CELLS = 1 << 26, 1 << 28
+MMC_RANKED_MAX_K = 16   # include/mmc.h: selection rounds of mmc_head_evaluate_ranked
 
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
@@ -32,6 +33,7 @@ SYMBOLS = [
     "mmc_featureset_create", "mmc_featureset_destroy", "mmc_featureset_rows", "mmc_featureset_dim", "mmc_featureset_append", "mmc_featureset_read",
     "mmc_trainer_partial_fit_set", "mmc_trainer_evaluate_set_q32", "mmc_calibrator_add_set",
     "mmc_head_evaluate", "mmc_head_evaluate_set", "mmc_head_evaluate_grouped", "mmc_head_evaluate_grouped_set",
+    "mmc_head_evaluate_ranked", "mmc_head_evaluate_ranked_set",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -159,6 +161,12 @@ def _load() -> C.CDLL:
     lib.mmc_head_evaluate_grouped.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + grouped + [u32, vp]
     lib.mmc_head_evaluate_grouped_set.restype = i32
     lib.mmc_head_evaluate_grouped_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + grouped + [vp]
+    # the arguments of mmc_head_evaluate(_set), then sim_level, n_levels, kmax, class_rank_hist, hier_hist
+    ranked = [vp, i32, i32, vp, vp]
+    lib.mmc_head_evaluate_ranked.restype = i32
+    lib.mmc_head_evaluate_ranked.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + ranked + [u32, vp]
+    lib.mmc_head_evaluate_ranked_set.restype = i32
+    lib.mmc_head_evaluate_ranked_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + ranked + [vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

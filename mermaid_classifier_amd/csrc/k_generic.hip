@@ -1161,6 +1161,89 @@ __global__ __launch_bounds__(256) void calibrate_eval_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
+// rank_rows_kernel: the ranking tables of a validation pass (mermaid_classifier/pyspacer/metrics/ranking.py:88-128, :163-209).  It
+// runs behind calibrate_eval_kernel on the same chunk of logits and reads that kernel's per-row `scored` (the true class g of a row
+// that entered confusion / rank_hist, else -1) and `rank`.  An unscored row does nothing.  For a scored row:
+//   class_rank_hist[g][rank - 1] += 1                      the rank histogram of calibrate_eval_kernel, broken down by true class
+//   hier_hist[j][m_j] += 1 for j = 0 .. kmax - 1           c_0, c_1, ... are the row's classes in the order of calibrate_topk_kernel
+//                                                          (score descending, equal scores in class order) and m_j is the largest
+//                                                          sim_level[g][c_i] over i <= j: the running maximum of ranking.py:184
+// The calibration and the selection rounds are those of calibrate_topk_kernel, helper for helper, so c_j is the class mmc_head_topk
+// names.  Without sim_level only the first table is made and no row is calibrated.
+// Rows as in calibrate_eval_kernel (one wave per row, wave-private LDS row or `rowbuf`, the grid's stride).  hier_hist is kept as
+// 32-bit counters in LDS behind the rows (a chunk holds fewer than 2^32 rows) and flushed with one 64-bit atomic per non-zero cell;
+// class_rank_hist goes straight to memory, one atomic per row spread over the K x K table.  Integer atomics only: the tables depend
+// on neither the row order nor the grid nor the chunking; the caller zeroes them.
+// ---------------------------------------------------------------------------------------------
+template <bool ROW_IN_LDS>
+__global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict__ logits, int M, int K,
+                                                        const float* __restrict__ a, const float* __restrict__ bcal,
+                                                        const int32_t* __restrict__ scored, const int32_t* __restrict__ rank,   // [M]
+                                                        const uint8_t* __restrict__ sim_level,             // [K][K] or NULL
+                                                        int n_levels, int kmax,
+                                                        unsigned long long* __restrict__ class_rank_hist,  // [K][K] or NULL
+                                                        unsigned long long* __restrict__ hier_hist,        // [kmax][n_levels] or NULL
+                                                        float* rowbuf)                                     // [M][K] when !ROW_IN_LDS
+{
+    extern __shared__ float rank_lds[];   // [4][K] rows when ROW_IN_LDS, then [kmax][n_levels] unsigned counts
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned* hh = reinterpret_cast<unsigned*>(rank_lds + (ROW_IN_LDS ? (size_t)4 * K : 0));
+    const int cells = sim_level ? kmax * n_levels : 0;
+    for (int i = threadIdx.x; i < cells; i += 256) hh[i] = 0;
+    __syncthreads();
+    for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
+        const int g = scored[row];
+        if (g < 0) continue;   // (wave-uniform)
+        if (class_rank_hist && lane == 0) atomicAdd(&class_rank_hist[(size_t)g * K + (rank[row] - 1)], 1ull);
+        if (!sim_level) continue;
+        const float* x = logits + (size_t)row * K;
+        float* r = ROW_IN_LDS ? rank_lds + (size_t)wave * K : rowbuf + (size_t)row * K;
+        float mx, se;
+        calib_softmax_stats(x, K, lane, mx, se);
+        float cs = 0.f;
+        for (int c = lane; c < K; c += 64) {
+            const float v = calib_sigmoid(x[c], mx, se, a[c], bcal[c]);
+            r[c] = v;
+            cs += v;
+        }
+        cs = wave_sum_f(cs);
+        unsigned long long cur = 0;   // this lane's largest key not yet selected (calibrate_topk_kernel)
+        for (int c = lane; c < K; c += 64) {
+            const float v = calib_normalise(r[c], cs, K);
+            r[c] = v;
+            const unsigned long long key = topk_key(v, c);
+            cur = key > cur ? key : cur;
+        }
+        const uint8_t* lv = sim_level + (size_t)g * K;
+        unsigned m = 0;   // lane 0's: the running maximum level
+        for (int j = 0; j < kmax; ++j) {   // kmax <= K (checked by the launcher): a real key is left in every round
+            unsigned long long win = cur;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long t = __shfl_xor(win, o);
+                win = t > win ? t : win;
+            }
+            if (lane == 0) {
+                const unsigned l = lv[0xFFFFFFFFu - (unsigned)win];
+                m = l > m ? l : m;
+                atomicAdd(&hh[j * n_levels + m], 1u);
+            }
+            if (cur == win) {   // the owner: its largest key below the winner
+                unsigned long long nb = 0;
+                for (int c = lane; c < K; c += 64) {
+                    const unsigned long long key = topk_key(r[c], c);
+                    nb = (key < win && key > nb) ? key : nb;
+                }
+                cur = nb;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < cells; i += 256)
+        if (hh[i]) atomicAdd(&hier_hist[i], (unsigned long long)hh[i]);
+}
+
+// ---------------------------------------------------------------------------------------------
 // crop_patches: reflect-pad + slice as pure index arithmetic on the resident image.
 // numpy 'reflect': index i<0 -> -i ; i>=n -> 2(n-1)-i.  One thread = 4 output pixels (12 bytes).
 // ---------------------------------------------------------------------------------------------
@@ -1389,6 +1472,30 @@ int launch_calibrate_eval(const float* logits, int M, int K, const float* a, con
         if (!rowbuf) return -18;
         hipLaunchKernelGGL((calibrate_eval_kernel<false>), grid, dim3(256), 0, st, logits, M, K, a, b, y, label_map, n_labels, est, score,
                            rank, p_true, t, cf, rh, scored, rowbuf);
+    }
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_rank_rows(const float* logits, int M, int K, const float* a, const float* b, const int32_t* scored, const int32_t* rank,
+                     const uint8_t* sim_level, int n_levels, int kmax, long long* class_rank_hist, long long* hier_hist, float* rowbuf,
+                     hipStream_t st)
+{
+    if (M < 1 || K < 1 || !scored || !rank || (sim_level == nullptr) != (hier_hist == nullptr)) return -18;
+    if (sim_level && (n_levels < 1 || n_levels > 256 || kmax < 1 || kmax > K || kmax > RANK_MAX_K)) return -18;
+    if (!sim_level && !class_rank_hist) return 0;   // nothing to add
+    const int nb = (M + 3) / 4;
+    const dim3 grid(nb < 2048 ? nb : 2048);   // as calibrate_eval_kernel: the partial tables stay on chip while a workgroup walks rows
+    unsigned long long* ch = reinterpret_cast<unsigned long long*>(class_rank_hist);
+    unsigned long long* hh = reinterpret_cast<unsigned long long*>(hier_hist);
+    const size_t cells = sim_level ? (size_t)kmax * n_levels * sizeof(unsigned) : 0;   // at most 16 KB
+    if (K <= TOPK_LDS_MAX_K) {
+        hipLaunchKernelGGL((rank_rows_kernel<true>), grid, dim3(256), (size_t)4 * K * sizeof(float) + cells, st, logits, M, K, a, b, scored,
+                           rank, sim_level, n_levels, kmax, ch, hh, (float*)nullptr);
+    } else {
+        if (sim_level && !rowbuf) return -18;
+        hipLaunchKernelGGL((rank_rows_kernel<false>), grid, dim3(256), cells, st, logits, M, K, a, b, scored, rank, sim_level, n_levels,
+                           kmax, ch, hh, rowbuf);
     }
     LAUNCH_CHECK();
     return 0;

@@ -238,6 +238,15 @@ constexpr int EVAL_TOTALS = 5;
 int launch_calibrate_eval(const float* logits, int M, int K, const float* a, const float* b, const int32_t* y, const int32_t* label_map,
                           int n_labels, int32_t* est, float* score, int32_t* rank, float* p_true, long long* totals, long long* confusion,
                           long long* rank_hist, int32_t* scored, float* rowbuf, hipStream_t st);
+// behind launch_calibrate_eval on the same chunk (its `scored` and `rank` outputs, on the device): adds every scored row into
+// class_rank_hist [K][K] (true class x rank - 1; may be NULL) and, with sim_level [K][K] (uint8 < n_levels, row = true class), into
+// hier_hist [kmax][n_levels]: round j of the top-k selection x the largest level among the row's j + 1 best classes.  sim_level and
+// hier_hist come together or not at all; integer atomics, the caller zeroes both tables.  rowbuf: M x K scratch floats, needed
+// only when K > 2048 and sim_level is given
+constexpr int RANK_MAX_K = 16;
+int launch_rank_rows(const float* logits, int M, int K, const float* a, const float* b, const int32_t* scored, const int32_t* rank,
+                     const uint8_t* sim_level, int n_levels, int kmax, long long* class_rank_hist, long long* hier_hist, float* rowbuf,
+                     hipStream_t st);
 int launch_crop(const uint8_t* image, int H, int W, const int32_t* rowcols, int n, uint8_t* out, hipStream_t st);
 
 // ---- grouped validation (metrics.hip) ----

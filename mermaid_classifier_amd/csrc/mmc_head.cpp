@@ -52,6 +52,8 @@ struct mmc_head {
     DevBuf<long long> eval_tot;
     // mmc_head_evaluate_grouped*: offsets, per-image counts, per-class and per-source tables, reliability keys, select state, slabs
     DevBuf<char> grp;
+    // mmc_head_evaluate_ranked*: the int64 class_rank_hist and hier_hist tables, then the uploaded similarity levels
+    DevBuf<char> rnk;
 };
 
 extern "C" void mmc_head_destroy(mmc_head* h)
@@ -328,10 +330,36 @@ static int group_prepare(mmc_head* h, int64_t n, const GroupIO& g, hipStream_t s
 }
 static int head_evaluate_groups(mmc_head* h, int64_t n, const GroupIO& g, const GroupScratch& s, hipStream_t st);
 
+// the extra inputs and outputs of mmc_head_evaluate_ranked* (include/mmc.h)
+struct RankIO {
+    const uint8_t* sim_level; int n_levels; int kmax;
+    int64_t *class_rank_hist, *hier_hist;
+};
+static_assert(MMC_RANKED_MAX_K == RANK_MAX_K, "include/mmc.h and kernels.h disagree on the selection rounds");
+// the ranked pass's device state inside h->rnk (sim_level / hier_hist are null without a level table, class_hist when not asked for)
+struct RankScratch { long long *class_hist, *hier_hist; uint8_t* sim_level; };
+
+// once per ranked call: lays out and grows h->rnk, zeroes the two tables, uploads the level table
+static int rank_prepare(mmc_head* h, const RankIO& k, hipStream_t st, RankScratch* s)
+{
+    const size_t cells = (size_t)h->K * h->K;
+    const size_t class_bytes = k.class_rank_hist ? cells * 8 : 0, hier_bytes = k.sim_level ? (size_t)k.kmax * k.n_levels * 8 : 0;
+    int r;
+    if ((r = h->rnk.reserve((int64_t)(class_bytes + hier_bytes + (k.sim_level ? cells : 0))))) return r;
+    char* b = h->rnk.p;
+    s->class_hist = k.class_rank_hist ? reinterpret_cast<long long*>(b) : nullptr;
+    s->hier_hist = k.sim_level ? reinterpret_cast<long long*>(b + class_bytes) : nullptr;
+    s->sim_level = k.sim_level ? reinterpret_cast<uint8_t*>(b + class_bytes + hier_bytes) : nullptr;
+    if (class_bytes + hier_bytes) HIP_TRY(hipMemsetAsync(b, 0, class_bytes + hier_bytes, st));
+    if (k.sim_level) HIP_TRY(hipMemcpyAsync(s->sim_level, k.sim_level, cells, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
 // scores the rows of `src` (every argument has been checked) and ends in one synchronisation
 // with `grp`: every chunk's scored rows also go into the grouped tables, and head_evaluate_groups ends the call
+// with `rnk`: every chunk's scored rows also go into the ranking tables (rank_rows_kernel, on the chunk's logits)
 static int head_evaluate(mmc_head* h, const EvalSrc& src, const int32_t* label_map, int n_labels, const EvalOut& o, hipStream_t st,
-                         const GroupIO* grp)
+                         const GroupIO* grp, const RankIO* rnk)
 {
     const int K = h->K;
     const int64_t n = src.n;
@@ -347,11 +375,13 @@ static int head_evaluate(mmc_head* h, const EvalSrc& src, const int32_t* label_m
     int32_t* dy = h->eval_rows.p;
     int32_t* dest = (o.est || grp) ? dy + rows : nullptr;
     float* dscore = (o.score || grp) ? reinterpret_cast<float*>(dy + 2 * rows) : nullptr;
-    int32_t* drank = o.rank ? dy + 3 * rows : nullptr;
+    int32_t* drank = (o.rank || rnk) ? dy + 3 * rows : nullptr;
     float* dptrue = (o.p_true || grp) ? reinterpret_cast<float*>(dy + 4 * rows) : nullptr;
-    int32_t* dscored = grp ? dy + 5 * rows : nullptr;
+    int32_t* dscored = (grp || rnk) ? dy + 5 * rows : nullptr;
     GroupScratch gs{};
     if (grp && (r = group_prepare(h, n, *grp, st, &gs))) return r;
+    RankScratch rs{};
+    if (rnk && (r = rank_prepare(h, *rnk, st, &rs))) return r;
     GroupRowsArgs ga{};   // (rows and row0 are set per chunk)
     if (grp) {
         ga.scored = dscored; ga.est = dest; ga.score = dscore; ga.p_true = dptrue;
@@ -373,6 +403,9 @@ static int head_evaluate(mmc_head* h, const EvalSrc& src, const int32_t* label_m
             ga.rows = cur; ga.row0 = off;
             KTRY(launch_group_rows(ga, st));
         }
+        if (rnk)
+            KTRY(launch_rank_rows(logits, cur, K, h->a, h->bc, dscored, drank, rs.sim_level, rnk->n_levels, rnk->kmax, rs.class_hist,
+                                  rs.hier_hist, h->proba_stage.p, st));
         // stream order keeps the next chunk's kernel behind these copies
         if (o.est) HIP_TRY(hipMemcpyAsync(o.est + off, dest, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
         if (o.score) HIP_TRY(hipMemcpyAsync(o.score + off, dscore, (size_t)cur * 4, hipMemcpyDeviceToHost, st));
@@ -384,6 +417,10 @@ static int head_evaluate(mmc_head* h, const EvalSrc& src, const int32_t* label_m
     HIP_TRY(hipMemcpyAsync(o.totals, dtot, EVAL_TOTALS * sizeof(long long), hipMemcpyDeviceToHost, st));
     if (o.rank_hist) HIP_TRY(hipMemcpyAsync(o.rank_hist, dhist, (size_t)K * sizeof(long long), hipMemcpyDeviceToHost, st));
     if (o.confusion) HIP_TRY(hipMemcpyAsync(o.confusion, dconf, (size_t)K * K * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (rnk && rnk->class_rank_hist)
+        HIP_TRY(hipMemcpyAsync(rnk->class_rank_hist, rs.class_hist, (size_t)K * K * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (rnk && rnk->hier_hist)
+        HIP_TRY(hipMemcpyAsync(rnk->hier_hist, rs.hier_hist, (size_t)rnk->kmax * rnk->n_levels * sizeof(long long), hipMemcpyDeviceToHost, st));
     if (grp) return head_evaluate_groups(h, n, *grp, gs, st);
     HIP_TRY(hipStreamSynchronize(st));
     return MMC_OK;
@@ -518,8 +555,30 @@ static int group_check(const mmc_head* h, int64_t n, const GroupIO& g)
     return MMC_OK;
 }
 
+// zeroes every ranking output whose size the arguments determine
+static void rank_clear(const mmc_head* h, const RankIO& k)
+{
+    if (h && k.class_rank_hist) memset(k.class_rank_hist, 0, (size_t)h->K * h->K * 8);
+    if (k.hier_hist && k.n_levels >= 1 && k.n_levels <= 256 && k.kmax >= 1 && k.kmax <= MMC_RANKED_MAX_K)
+        memset(k.hier_hist, 0, (size_t)k.kmax * k.n_levels * 8);
+}
+
+static int rank_check(const mmc_head* h, const RankIO& k)
+{
+    if (k.n_levels < 1 || k.n_levels > 256) return fail(MMC_ERR_ARG, "n_levels = %d outside [1, 256]", k.n_levels);
+    const int top = h->K < MMC_RANKED_MAX_K ? h->K : MMC_RANKED_MAX_K;
+    if (k.kmax < 1 || k.kmax > top) return fail(MMC_ERR_ARG, "kmax = %d outside [1, %d] (the head has %d classes)", k.kmax, top, h->K);
+    if (k.sim_level && !k.hier_hist) return fail(MMC_ERR_ARG, "sim_level without hier_hist");
+    if (!k.sim_level && k.hier_hist) return fail(MMC_ERR_ARG, "hier_hist without sim_level");
+    if (k.sim_level)
+        for (int64_t i = 0, e = (int64_t)h->K * h->K; i < e; ++i)
+            if (k.sim_level[i] >= k.n_levels)
+                return fail(MMC_ERR_ARG, "sim_level[%lld] = %d outside [0, %d)", (long long)i, (int)k.sim_level[i], k.n_levels);
+    return MMC_OK;
+}
+
 // ------------------------------------------------------------------------------------------
-// the four evaluate entry points: each names its source, its outputs and (grouped) its groups, and makes one call
+// the six evaluate entry points: each names its source, its outputs and (grouped, ranked) its extra tables, and makes one call
 // ------------------------------------------------------------------------------------------
 // the feature-set form: the slice, then the common checks, then the classes (the set's labels lie in [0, fs->K): that range must be
 // the head's classes, or the map's domain)
@@ -550,22 +609,24 @@ static int eval_check_labels(const mmc_head* h, const EvalSrc& s, const int32_t*
 }
 
 static int evaluate(mmc_head* h, const EvalSrc& s, const int32_t* label_map, int n_labels, const EvalOut& o, const GroupIO* g,
-                    void* hip_stream)
+                    const RankIO* k, void* hip_stream)
 {
-    // When the outputs are zeroed is part of each pair's contract (include/mmc.h) and differs on purpose.  A grouped call zeroes
+    // When the outputs are zeroed is part of each pair's contract (include/mmc.h) and differs on purpose.  A grouped or ranked call zeroes
     // them before any check, the NULL-handle check included, and again when the pass fails: whatever it returns, no table holds
     // stale or partial counts.  A plain call zeroes them only once its arguments have passed: a rejected call writes nothing.
-    const bool clear_first = g != nullptr;
-    if (clear_first) { eval_clear(h, o); group_clear(h, *g); }
+    const bool clear_first = g != nullptr || k != nullptr;
+    auto clear_all = [&] { eval_clear(h, o); if (g) group_clear(h, *g); if (k) rank_clear(h, *k); };
+    if (clear_first) clear_all();
     if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
     int r = s.set ? eval_check_set(h, s, label_map, n_labels, o) : eval_check_common(h, s.n, label_map, n_labels, o);
     if (r) return r;
     if (g && (r = group_check(h, s.n, *g))) return r;
+    if (k && (r = rank_check(h, *k))) return r;
     if (!clear_first) eval_clear(h, o);
     if (s.n == 0) return MMC_OK;
     if (!s.set && (r = eval_check_labels(h, s, label_map, n_labels))) return r;
-    r = head_evaluate(h, s, label_map, n_labels, o, static_cast<hipStream_t>(hip_stream), g);
-    if (r && clear_first) { eval_clear(h, o); group_clear(h, *g); }
+    r = head_evaluate(h, s, label_map, n_labels, o, static_cast<hipStream_t>(hip_stream), g, k);
+    if (r && clear_first) clear_all();
     return r;
 }
 
@@ -577,7 +638,7 @@ extern "C" int mmc_head_evaluate(mmc_head* h, const float* feats, const int32_t*
                                  int64_t* rank_hist, unsigned flags, void* hip_stream)
 {
     const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
-    return evaluate(h, host_rows(feats, y, n, flags), label_map, n_labels, o, nullptr, hip_stream);
+    return evaluate(h, host_rows(feats, y, n, flags), label_map, n_labels, o, nullptr, nullptr, hip_stream);
 }
 
 extern "C" int mmc_head_evaluate_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
@@ -585,7 +646,7 @@ extern "C" int mmc_head_evaluate_set(mmc_head* h, mmc_featureset* fs, int64_t fi
                                      int64_t* rank_hist, void* hip_stream)
 {
     const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
-    return evaluate(h, set_rows(fs, first, n), label_map, n_labels, o, nullptr, hip_stream);
+    return evaluate(h, set_rows(fs, first, n), label_map, n_labels, o, nullptr, nullptr, hip_stream);
 }
 
 // the group arguments of the two grouped entry points, in the order of include/mmc.h
@@ -609,7 +670,7 @@ extern "C" int mmc_head_evaluate_grouped(mmc_head* h, const float* feats, const 
     const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
     const GroupIO g = group_io(image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32, source_confusion,
                                cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max);
-    return evaluate(h, host_rows(feats, y, n, flags), label_map, n_labels, o, &g, hip_stream);
+    return evaluate(h, host_rows(feats, y, n, flags), label_map, n_labels, o, &g, nullptr, hip_stream);
 }
 
 extern "C" int mmc_head_evaluate_grouped_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
@@ -623,7 +684,27 @@ extern "C" int mmc_head_evaluate_grouped_set(mmc_head* h, mmc_featureset* fs, in
     const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
     const GroupIO g = group_io(image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32, source_confusion,
                                cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max);
-    return evaluate(h, set_rows(fs, first, n), label_map, n_labels, o, &g, hip_stream);
+    return evaluate(h, set_rows(fs, first, n), label_map, n_labels, o, &g, nullptr, hip_stream);
+}
+
+extern "C" int mmc_head_evaluate_ranked(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
+                                        int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
+                                        int64_t* rank_hist, const uint8_t* sim_level, int n_levels, int kmax, int64_t* class_rank_hist,
+                                        int64_t* hier_hist, unsigned flags, void* hip_stream)
+{
+    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
+    const RankIO k{sim_level, n_levels, kmax, class_rank_hist, hier_hist};
+    return evaluate(h, host_rows(feats, y, n, flags), label_map, n_labels, o, nullptr, &k, hip_stream);
+}
+
+extern "C" int mmc_head_evaluate_ranked_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
+                                            int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
+                                            int64_t* rank_hist, const uint8_t* sim_level, int n_levels, int kmax, int64_t* class_rank_hist,
+                                            int64_t* hier_hist, void* hip_stream)
+{
+    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
+    const RankIO k{sim_level, n_levels, kmax, class_rank_hist, hier_hist};
+    return evaluate(h, set_rows(fs, first, n), label_map, n_labels, o, nullptr, &k, hip_stream);
 }
 
 // ------------------------------------------------------------------------------------------
