@@ -243,9 +243,15 @@ __global__ __launch_bounds__(512) void mid14_kernel(Mid14Args a)
 // Pixel tiles of the expand are image ROWS (14 pixels + 2 repeats): a lane's LDS addresses are base + row * immediate.
 // Output: D[B][196][CE], pool[B][CE] -- what mid14_kernel writes (sums in another, equally fixed, order).
 // ---------------------------------------------------------------------------------------------
-template <int CKS, int KSD, int CE>
-__global__ __launch_bounds__(512) void mid14m_kernel(Mid14Args a)
+// The body is a device function so that chain14_kernel can run it as one of its phases (CHAIN: one workgroup per patch, the thread
+// index handed in, no phase clock).  The patch is blockIdx.x either way.
+template <int CKS, int KSD, int CE, bool CHAIN>
+static __device__ __forceinline__ void mid14m_body(const Mid14Args& args, const int chain_tid)
 {
+    const Mid14Args a = args;   // (a private copy, as a kernel's by-value argument is: no store of the body can alias it)
+    constexpr bool DBG = !CHAIN;
+    const int tid = CHAIN ? chain_tid : (int)threadIdx.x;
+    const int by = CHAIN ? 0 : (int)blockIdx.y, ny = CHAIN ? 1 : (int)gridDim.y;
     constexpr int HW = 196, NG = CE / 16, R = KSD / 2;
     constexpr int XSTR = 64 * CKS + 16;          // bytes per staged block-input row (k zero padded to 32 CKS)
     constexpr int ERS = 40;                      // bytes per planar row: columns x = 0 .. 15 (quads at 0, 4, 8, 12; 14, 15 stay zero) + 8 spare
@@ -254,7 +260,7 @@ __global__ __launch_bounds__(512) void mid14m_kernel(Mid14Args a)
     constexpr int TREG = 56 * 32;                // a wave's transpose tile: [4 rows x 14 pixels][16 channels] fp16
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* XS = smem;                                   // [196][XSTR]
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned char* EW = smem + HW * XSTR + wave * (EREG + TREG);   // this wave's planar region
     unsigned char* TW = EW + EREG;                                 // ... and its transpose tile
     const int n16 = lane & 15, q = lane >> 4;    // expand role: channel n16 of the group, pixels 4q .. 4q+3 of an image row
@@ -269,7 +275,7 @@ __global__ __launch_bounds__(512) void mid14m_kernel(Mid14Args a)
     const GLOBAL_AS float* bexp = sgpr_ptr<float>(a.bexp);
     const GLOBAL_AS _Float16* dwt = sgpr_ptr<_Float16>(a.dwdiag);
     const GLOBAL_AS float* bdw = sgpr_ptr<float>(a.bdw);
-    const bool clk = a.dbg_clk != nullptr;
+    const bool clk = DBG && a.dbg_clk != nullptr;
     long long ck[5] = {clk ? (long long)__builtin_readcyclecounter() : 0, 0, 0, 0, 0};
     // ---- stage the block input (k zero padded) and zero this wave's planar region (borders stay zero for the whole kernel) ----
     {
@@ -321,11 +327,11 @@ __global__ __launch_bounds__(512) void mid14m_kernel(Mid14Args a)
         b2 = gload<float>(bdw, (unsigned)(16 * g + c) * 4u);
     };
     {
-        const int g0 = blockIdx.y * 8 + wave;
+        const int g0 = by * 8 + wave;
         request_group(g0 < NG ? g0 : 0, wen, tan, ben, bdn);
     }
 #pragma unroll 1
-    for (int g = blockIdx.y * 8 + wave; g < NG; g += 8 * gridDim.y) {
+    for (int g = by * 8 + wave; g < NG; g += 8 * ny) {
 #pragma unroll
         for (int ks = 0; ks < CKS; ++ks) we[ks] = wen[ks];
 #pragma unroll
@@ -333,7 +339,7 @@ __global__ __launch_bounds__(512) void mid14m_kernel(Mid14Args a)
         be = ben;
         bd = bdn;
         {
-            const int gn = g + 8 * (int)gridDim.y;
+            const int gn = g + 8 * ny;
             request_group(gn < NG ? gn : g, wen, tan, ben, bdn);   // (the last group re-requests itself: unused)
         }
         PIN_VMEM();
@@ -485,9 +491,15 @@ __global__ __launch_bounds__(512) void mid14m_kernel(Mid14Args a)
     }
     if (clk && lane == 0 && (wave == 0 || wave == 4 || wave == 7)) {   // staging | first group: expand | depthwise | all remaining groups
         ck[4] = (long long)__builtin_readcyclecounter();
-        float* dst = a.dbg_clk + ((size_t)b * 8 + blockIdx.y) * 16 + (wave == 0 ? 0 : (wave == 4 ? 4 : 8));
+        float* dst = a.dbg_clk + ((size_t)b * 8 + by) * 16 + (wave == 0 ? 0 : (wave == 4 ? 4 : 8));
         dst[0] = (float)(ck[1] - ck[0]); dst[1] = (float)(ck[2] - ck[1]); dst[2] = (float)(ck[3] - ck[2]); dst[3] = (float)(ck[4] - ck[3]);
     }
+}
+
+template <int CKS, int KSD, int CE>
+__global__ __launch_bounds__(512) void mid14m_kernel(Mid14Args a)
+{
+    mid14m_body<CKS, KSD, CE, false>(a, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -503,9 +515,15 @@ __global__ __launch_bounds__(512) void mid14m_kernel(Mid14Args a)
 // next chunk's pixel fragments in flight.  Template: KS = k-steps of 32 (K zero-padded), NF = 16-channel output
 // fragments (N zero-padded), HW = pixels per patch, RES = skip connection.
 // ---------------------------------------------------------------------------------------------
-template <int KS, int NF, int HW, bool RES>
-__global__ __launch_bounds__(512) void proj_patch_kernel(ProjPatchArgs a)
+// (a device function, as mid14m_body; CHAIN compiles the debug outputs out)
+template <int KS, int NF, int HW, bool RES, bool CHAIN>
+static __device__ __forceinline__ void proj_patch_body(const ProjPatchArgs& args, const int chain_tid)
 {
+    const ProjPatchArgs a = args;   // (a private copy, as in mid14m_body)
+    constexpr bool DBG = !CHAIN;
+    const int tid = CHAIN ? chain_tid : (int)threadIdx.x;
+    float* const dbg_clk = DBG ? a.dbg_clk : nullptr;
+    float* const dbg_gate = DBG ? a.dbg_gate : nullptr;
     // k-steps per chunk of pixel fragments (the next chunk is in flight while one computes).  Small chunks put fewer bytes in front
     // of the first MFMA (the prologue is bound by them): KS = 21 -> 3 (22.2 -> 21.4 us), KS = 15 -> 3 with five output fragments
     // (16.0 -> 15.5 us) but 5 with seven (3: 16.6 -> 17.2 us), KS = 12 -> 6.
@@ -522,12 +540,12 @@ __global__ __launch_bounds__(512) void proj_patch_kernel(ProjPatchArgs a)
     float* pooled = reinterpret_cast<float*>(smem + NF * KS * 1024);    // [KP]
     float* gate = pooled + KP;                                          // [KP]
     float* rs = gate + KP;                                              // [32] squeeze activations
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 15, q = lane >> 4;
     const int b = blockIdx.x;
     const int K = a.K, CSP = a.CSP;
     long long tk0 = 0, tk1 = 0, tk2 = 0;
-    if (a.dbg_clk) tk0 = (long long)__builtin_readcyclecounter();
+    if (dbg_clk) tk0 = (long long)__builtin_readcyclecounter();
     const GLOBAL_AS _Float16* wfrag = sgpr_ptr<_Float16>(a.wfrag);
     const GLOBAL_AS _Float16* wr_g = sgpr_ptr<_Float16>(a.wr_g);
     const GLOBAL_AS _Float16* we_t = sgpr_ptr<_Float16>(a.we_t);
@@ -655,7 +673,7 @@ __global__ __launch_bounds__(512) void proj_patch_kernel(ProjPatchArgs a)
     if (pk0 < KP) pooled[pk0] = pk0 < K ? ps0 : 0.f;
     if (pk1 < KP) pooled[pk1] = pk1 < K ? ps1 : 0.f;
     T7_BAR();
-    if (a.dbg_clk && tid == 0) a.dbg_clk[(size_t)b * 8 + 3] = (float)((long long)__builtin_readcyclecounter() - tk0);
+    if (dbg_clk && tid == 0) dbg_clk[(size_t)b * 8 + 3] = (float)((long long)__builtin_readcyclecounter() - tk0);
     // ---- FC1: r = silu(br + psc * pooled . Wr^T) ----
     // (The bulk loads -- 147 KB of project weights and the first pixel fragments, 33 x 16 bytes per thread -- used to be issued
     // HERE, in front of FC1: their address processing alone takes ~4 k cycles per workgroup and FC1's barrier came 9-10 k cycles
@@ -690,9 +708,9 @@ __global__ __launch_bounds__(512) void proj_patch_kernel(ProjPatchArgs a)
         }
     }
     T7_BAR();
-    if (a.dbg_clk && tid == 0) {
-        a.dbg_clk[(size_t)b * 8 + 4] = (float)((long long)__builtin_readcyclecounter() - tk0);
-        a.dbg_clk[(size_t)b * 8 + 5] = a.dbg_clk[(size_t)b * 8 + 4];   // (the reduce stage is gone: same stamp)
+    if (dbg_clk && tid == 0) {
+        dbg_clk[(size_t)b * 8 + 4] = (float)((long long)__builtin_readcyclecounter() - tk0);
+        dbg_clk[(size_t)b * 8 + 5] = dbg_clk[(size_t)b * 8 + 4];   // (the reduce stage is gone: same stamp)
     }
     // first pixel fragments of every wave (wave 7's behind the last DMA slice), unconditional: every layer has at least seven
     // pairs of pixel fragments, and a load behind a branch would cost the chain its counted waits.  Behind FC1's barrier (a wave
@@ -718,17 +736,17 @@ __global__ __launch_bounds__(512) void proj_patch_kernel(ProjPatchArgs a)
             const float g0 = fc2_thr ? sigmoid_f(a0) : 0.f, g1 = fc2_thr ? sigmoid_f(a1) : 0.f;
             gate[k2] = g0;
             gate[k2 + 1] = g1;
-            if (a.dbg_gate && fc2_thr) {
-                a.dbg_gate[(size_t)b * K + k2] = g0;
-                a.dbg_gate[(size_t)b * K + k2 + 1] = g1;
+            if (dbg_gate && fc2_thr) {
+                dbg_gate[(size_t)b * K + k2] = g0;
+                dbg_gate[(size_t)b * K + k2 + 1] = g1;
             }
         }
     }
-    if (a.dbg_clk && tid == 0) a.dbg_clk[(size_t)b * 8 + 6] = (float)((long long)__builtin_readcyclecounter() - tk0);
+    if (dbg_clk && tid == 0) dbg_clk[(size_t)b * 8 + 6] = (float)((long long)__builtin_readcyclecounter() - tk0);
     T7_BAR();
     }
-    if (a.dbg_clk && tid == 0) a.dbg_clk[(size_t)b * 8 + 7] = (float)((long long)__builtin_readcyclecounter() - tk0);
-    if (a.dbg_clk) tk1 = (long long)__builtin_readcyclecounter();
+    if (dbg_clk && tid == 0) dbg_clk[(size_t)b * 8 + 7] = (float)((long long)__builtin_readcyclecounter() - tk0);
+    if (dbg_clk) tk1 = (long long)__builtin_readcyclecounter();
     // ---- project: Y[pixel][n] = sum_k (X[pixel][k] * gate[k]) W[n][k] + bias (+ residual) ----
 #pragma unroll 1
     for (int pr = wave; pr < NPAIR; pr += 8) {
@@ -760,7 +778,7 @@ __global__ __launch_bounds__(512) void proj_patch_kernel(ProjPatchArgs a)
         for (int nf = 0; nf < NF; ++nf) wcur[nf] = *reinterpret_cast<const h8*>(wl + ((nf * KS) * 64 + lane) * 16);
         f4 gc0 = *reinterpret_cast<const f4*>(gate + 8 * q), gc1 = *reinterpret_cast<const f4*>(gate + 8 * q + 4);
         long long tka = 0;
-        if (a.dbg_clk) tka = (long long)__builtin_readcyclecounter();
+        if (dbg_clk) tka = (long long)__builtin_readcyclecounter();
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
             // the next chunk (of this pair, or the first one of the wave's next pair) is in flight while this one computes
@@ -802,7 +820,7 @@ __global__ __launch_bounds__(512) void proj_patch_kernel(ProjPatchArgs a)
 #pragma unroll
                 for (int u = 0; u < CK; ++u) xc[i][u] = xn[i][u];
         }
-        if (a.dbg_clk && tid == 0) a.dbg_clk[(size_t)b * 8 + 2] = (float)((long long)__builtin_readcyclecounter() - tka);
+        if (dbg_clk && tid == 0) dbg_clk[(size_t)b * 8 + 2] = (float)((long long)__builtin_readcyclecounter() - tka);
         if (!EARLY_RES) load_res();
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -826,10 +844,56 @@ __global__ __launch_bounds__(512) void proj_patch_kernel(ProjPatchArgs a)
             }
         }
     }
-    if (a.dbg_clk) {
+    if (dbg_clk) {
         T7_BAR();
         tk2 = (long long)__builtin_readcyclecounter();
-        if (tid == 0) { a.dbg_clk[(size_t)b * 8] = (float)(tk1 - tk0); a.dbg_clk[(size_t)b * 8 + 1] = (float)(tk2 - tk1); }
+        if (tid == 0) { dbg_clk[(size_t)b * 8] = (float)(tk1 - tk0); dbg_clk[(size_t)b * 8 + 1] = (float)(tk2 - tk1); }
+    }
+}
+
+template <int KS, int NF, int HW, bool RES>
+__global__ __launch_bounds__(512) void proj_patch_kernel(ProjPatchArgs a)
+{
+    proj_patch_body<KS, NF, HW, RES, false>(a, 0);
+}
+
+// ---------------------------------------------------------------------------------------------
+// chain14_kernel: blocks 7 (back half) .. 10 of B0 for ONE patch per workgroup in ONE launch.  From b7.projse to b10.projse every
+// launch is one workgroup per patch, and workgroup b reads only what workgroup b of the launch before wrote (the depthwise output
+// and pool sums of its patch, its rows of the activations): the device-wide dependency between those launches orders nothing the
+// result needs.  Here a workgroup walks the phases on its own -- the same bodies, in the same order, on the same arguments, so the
+// same bits -- and a patch's time is the sum of its own phases, not of every launch's slowest workgroup plus its launch boundary.
+//
+// Phase boundary: every wave's global stores complete and visible to the other waves of the workgroup, every LDS read done, then
+// the next phase.  __syncthreads() is exactly that (workgroup-scope release, s_barrier, workgroup-scope acquire): producer and
+// consumer are waves of one workgroup on one CU behind one vector L1 (threadgroup-split mode is off in this build).  NOT a device-scope
+// fence -- it writes back and invalidates L2 at every phase.  What the phases hand over (activations, depthwise output, pool sums)
+// is read with vector loads only; the scalar cache sees weights and kernel arguments alone.  Every path of a body reaches its end
+// with the same barrier count (proj_patch's wave 7: four, like the others).
+// The workgroups are not in step: the host must not let two tensors of different row width share a buffer region inside the chain
+// (their patches overlap across workgroups; mmc_api.cpp forward_lane places them).
+// ---------------------------------------------------------------------------------------------
+enum { CH_PP_15_5_R = 0, CH_MID_3_480 = 1, CH_PP_15_7 = 2, CH_MID_4_672 = 3, CH_PP_21_7_R = 4 };
+__global__ __launch_bounds__(512) void chain14_kernel(Chain14Args c)
+{
+#pragma unroll 1
+    for (int p = 0; p < c.nph; ++p) {
+        const Chain14Phase& ph = c.ph[p];
+        // The thread index is made opaque per phase: what a body derives from it (lane roles, LDS addresses) would otherwise be
+        // hoisted out of this loop and stay live through every other body -- 103 spilled registers.
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        __builtin_assume(tid >= 0 && tid < 512);
+        switch (ph.kind) {   // each body is inlined once: the table repeats kinds 3 and 4
+        case CH_PP_15_5_R: proj_patch_body<15, 5, 196, true, true>(ph.pp, tid); break;
+        case CH_MID_3_480: mid14m_body<3, 5, 480, true>(ph.mid, tid); break;
+        case CH_PP_15_7: proj_patch_body<15, 7, 196, false, true>(ph.pp, tid); break;
+        case CH_MID_4_672: mid14m_body<4, 5, 672, true>(ph.mid, tid); break;
+        default: proj_patch_body<21, 7, 196, true, true>(ph.pp, tid); break;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -923,4 +987,52 @@ int launch_mid14(const Mid14Args& a, hipStream_t st)
 {
     if (a.B < 1) return -14;
     return inst_launch(MID14_TABLE, {(a.Cin + 31) / 32, a.ks, a.Ce, a.dwdiag ? 1 : 0}, a, st, -5);
+}
+
+// ---- chain14_kernel ----
+static int proj_patch_lds(int KS, int NF) { return NF * KS * 1024 + 2 * 32 * KS * 4 + 128; }             // (launch_proj_patch_t's)
+static int mid14m_lds(int CKS) { return 196 * (64 * CKS + 16) + 8 * (16 * 736 + 56 * 32); }              // (launch_mid14m_t's)
+
+int chain14_proj_kind(int K, int N, int HW, int res)
+{
+    const int ks = proj_patch_ksteps(K), nf = (N + 15) / 16;
+    if (HW != 196) return -1;
+    if (ks == 15 && nf == 5 && res) return CH_PP_15_5_R;
+    if (ks == 15 && nf == 7 && !res) return CH_PP_15_7;
+    if (ks == 21 && nf == 7 && res) return CH_PP_21_7_R;
+    return -1;
+}
+
+int chain14_mid_kind(int Cin, int ks, int Ce)
+{
+    const int cks = (Cin + 31) / 32;
+    if (ks != 5) return -1;
+    if (cks == 3 && Ce == 480) return CH_MID_3_480;
+    if (cks == 4 && Ce == 672) return CH_MID_4_672;
+    return -1;
+}
+
+int launch_chain14(const Chain14Args& a, hipStream_t st)
+{
+    if (a.B < 1 || a.nph < 1 || a.nph > CHAIN14_MAX_PHASES) return -14;
+    int lds = 0;
+    for (int p = 0; p < a.nph; ++p) {   // every phase is what its own launcher would accept, on the instantiation its kind names
+        const Chain14Phase& ph = a.ph[p];
+        int need;
+        if (ph.kind == CH_MID_3_480 || ph.kind == CH_MID_4_672) {
+            const Mid14Args& m = ph.mid;
+            if (m.B != a.B || m.nsplit != 1 || !m.dwdiag || chain14_mid_kind(m.Cin, m.ks, m.Ce) != ph.kind) return -14;
+            need = mid14m_lds((m.Cin + 31) / 32);
+        } else {
+            const ProjPatchArgs& q = ph.pp;
+            if (q.B != a.B || q.CSP < 4 || q.CSP > 28 || (q.CSP & 3) || q.nparts < 1) return -11;
+            if (chain14_proj_kind(q.K, q.N, q.HW, q.res ? 1 : 0) != ph.kind) return -5;
+            need = proj_patch_lds(proj_patch_ksteps(q.K), (q.N + 15) / 16);
+        }
+        lds = need > lds ? need : lds;
+    }
+    if (int r = set_max_lds<&chain14_kernel>(mid14m_lds(4))) return r;   // the largest phase: mid14m<4,5,672>, 161 856 of 163 840 bytes
+    hipLaunchKernelGGL(chain14_kernel, dim3(a.B), dim3(512), lds, st, a);
+    LAUNCH_CHECK();
+    return 0;
 }

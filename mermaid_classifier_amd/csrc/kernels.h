@@ -197,6 +197,25 @@ int proj_patch_ksteps(int K);                        // k-steps (of 32) its weig
 int proj_patch_fc1_rows(int K);                      // channel rows per output group of ProjPatchArgs::wr_g (64 x the kernel's FC1 iterations)
 const char* proj_patch_label(int K, int N, int HW, int res);
 
+// A run of per-patch launches of the 14x14 blocks as ONE launch (chain14_kernel): workgroup b runs the phases one after the other
+// on patch b.  Each phase is a mid14m_kernel (nsplit 1) or proj_patch_kernel body with the arguments its own launch would get
+// (debug pointers unused); consecutive phases may only exchange rows of their own patch.
+enum { CHAIN14_MAX_PHASES = 7 };
+struct Chain14Phase {
+    int kind;                 // chain14_proj_kind() / chain14_mid_kind()
+    union {
+        ProjPatchArgs pp;
+        Mid14Args mid;
+    };
+};
+struct Chain14Args {
+    int B, nph;
+    Chain14Phase ph[CHAIN14_MAX_PHASES];
+};
+int chain14_proj_kind(int K, int N, int HW, int res);   // the phase kind of a proj_patch / mid14m shape, or -1: not in the chain kernel
+int chain14_mid_kind(int Cin, int ks, int Ce);
+int launch_chain14(const Chain14Args& a, hipStream_t st);
+
 int launch_mbconv_a(const MbArgs& a, hipStream_t st);
 const char* mbconv_a_label(const MbArgs& a);     // (these three read the geometry fields only)
 const char* mbconv_pre_label(const MbArgs& a);

@@ -171,6 +171,7 @@ struct Options {
     bool keep, graph, tail_clk, profile_serial;
     bool fuse, fuse_b0, mb1, mbt, mbt2, mbt4, mb_dot2, mid14, mid14m, projse, se_small, thin_proj, b1_planar;
     bool tail, tail_full, tail_b11;
+    bool chain;
     int lanes, fp8_maxh;
 };
 static bool env_starts(const char* name, char c)
@@ -200,6 +201,7 @@ static Options read_options()
     o.tail = on("MMC_TAIL");
     o.tail_full = on("MMC_TAIL_FULL");
     o.tail_b11 = on("MMC_TAIL_B11");
+    o.chain = on("MMC_CHAIN");
     const char* e = getenv("MMC_MID14");
     o.mid14 = !e || atoi(e) != 0;
     e = getenv("MMC_MID14M");
@@ -398,7 +400,7 @@ struct mmc_backbone {
     };
     Lane lanes[4];
     // optional (MMC_GRAPH=1): a pass over device-resident buffers is captured once per (input, output, n) into a HIP graph
-    // and replayed -- the ~26 launches per lane then cost one graph launch
+    // and replayed -- the ~20 launches per lane then cost one graph launch
     // (least recently used entry evicted beyond MMC_GRAPH_CACHE combinations)
     struct GraphEntry { const void* in; float* out; int n; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;
@@ -425,6 +427,8 @@ struct mmc_backbone {
     bool fuse_stem = false;          // block 0's depthwise conv inside the stem launch (stem_dw_kernel): no stem tensor
     bool fuse_b0b1 = false;          // block 0's SE scale + project conv folded into block 1's kernel: no b0 output tensor
     TailRoute tail = TailRoute::None;
+    int chain_first = -1, chain_last = -1;   // b<first>.projse .. b<last>.projse run as ONE chain14_kernel launch (-1: separate launches)
+    int chain_cout = 0, chain_ce = 0;        // ... the widest block output / expanded tensor among them (see forward_lane)
     bool fp8 = false;                // MMC_PRECISION_FP8: project convs of the narrow late blocks on e4m3 MFMA operands
     float* dbg_clk = nullptr;        // keep mode: per-patch phase cycle counts of the patch-resident kernels
     float* mid_clk = nullptr;        // MMC_TAIL_CLK=1: [max_batch][8 workgroups][16] phase cycle counts of block 10's mid14 launch
@@ -751,6 +755,32 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         const bool t11all = t11 && o.tail_b11 && !o.keep && B11.mb.ksteps == 4 && B11.d.k == 5 && B11.d.s == 2 && B11.H == 14;
         bb->tail = t11all ? TailRoute::B11All : t11 ? TailRoute::B11 : t12 ? TailRoute::B12 : TailRoute::None;
         for (int i = 0; i < NBLK; ++i) TRY_OR_FREE(plan_block(bb, bb->blk[i], i));
+        // chain14_kernel: the maximal run of consecutive launches that are one workgroup per patch on a body the chain kernel holds
+        // (proj_patch, or mid14m with nsplit 1).  Launch 2 i is block i's front half, 2 i + 1 its back half.  Per-tensor mode and the
+        // debug clocks keep separate launches.
+        if (o.chain && is_b0 && !o.keep && !o.tail_clk) {
+            auto chainable = [&](int l) {
+                const BlockW& B = K[l >> 1];
+                if (l & 1) return B.back == Back::ProjPatch && chain14_proj_kind(B.ce, B.d.cout, B.Ho * B.Ho, B.skip ? 1 : 0) >= 0;
+                return B.front == Front::Mid14 && B.mid14m && chain14_mid_kind(B.d.cin, B.d.k, B.ce) >= 0;
+            };
+            int best0 = 0, bestn = 0;
+            for (int l = 0, run = 0; l < 2 * NBLK; ++l) {
+                run = chainable(l) ? run + 1 : 0;
+                if (run > bestn) { bestn = run; best0 = l - run + 1; }
+            }
+            // only the schedule the chain was built and measured for, b7.projse .. b10.projse: any other run (MMC_MID14M=0,
+            // MMC_PROJSE=0, ...) stays separate launches
+            // ... whose tensors come in at most two row widths per buffer, the first block's and a wider one (forward_lane places them)
+            bool two = K[7].skip;
+            int cw = K[7].d.cout, ew = K[7].ce;
+            for (int i = 8; i <= 10; ++i) { cw = std::max(cw, K[i].d.cout); ew = std::max(ew, K[i].ce); }
+            for (int i = 8; i <= 10; ++i)
+                two = two && (K[i].d.cout == K[7].d.cout || K[i].d.cout == cw) && (K[i].ce == K[7].ce || K[i].ce == ew);
+            if (bestn == CHAIN14_MAX_PHASES && best0 == 2 * 7 + 1 && two) {
+                bb->chain_first = 7; bb->chain_last = 10; bb->chain_cout = cw; bb->chain_ce = ew;
+            }
+        }
         bb->head.nt = 4;
         const int HWh = K[NBLK - 1].Ho * K[NBLK - 1].Ho;
         if (bb->tail != TailRoute::B11 && bb->tail != TailRoute::B11All && !plan_gemm(bb->head, EPI_GAP, false, false, HWh)) {
@@ -1049,6 +1079,12 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         mmc_backbone_destroy(bb);
         return fail(MMC_ERR_WEIGHTS, "weights blob has %u tensors, expected %u", nt, rd.next);
     }
+    if (bb->chain_first >= 0) {   // room for the chained launch's second tensor per buffer (the 112 x 112 layers already need more)
+        const size_t hw = (size_t)bb->blk[bb->chain_first].Ho * bb->blk[bb->chain_first].Ho;
+        max_act = std::max(max_act, 2 * hw * bb->chain_cout);
+        max_dw = std::max(max_dw, 2 * hw * bb->chain_ce);
+        max_pool = std::max(max_pool, (size_t)2 * bb->chain_ce);
+    }
     const size_t mb = (size_t)max_batch;
     {
         int nl = std::max(1, std::min(o.lanes, 4));
@@ -1156,6 +1192,19 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
     _Float16* y = ws.act1;
     auto swap_xy = [&] { _Float16* t = x; x = y; y = t; };
     const int lane_idx = (int)(&ws - bb->lanes);
+    // The chained launch: its members' arguments are collected in launch order and go out with the last one.  Its workgroups are
+    // NOT in step: while workgroup b writes a phase's output, another may still be reading an earlier phase's input.  A buffer's
+    // patch b starts at b x (pixels x row width), so two tensors of different row width in one buffer overlap ACROSS patches --
+    // between separate launches that is harmless, inside the chain it is a race.  So a chained tensor whose row width differs from
+    // what its buffer holds when the chain starts (block ch0's widths) lives in the buffer's upper part, beyond lane_cap patches of
+    // the widest tensor: every region then holds ONE row width, and a workgroup only ever touches its own patch's rows of it.
+    Chain14Args ca{};
+    const int ch0 = bb->chain_first, ch1 = bb->chain_last;
+    const size_t ch_hw = ch0 >= 0 ? (size_t)bb->blk[ch0].Ho * bb->blk[ch0].Ho : 0;
+    auto ch_act = [&](_Float16* base, int cout) { return base + (cout == bb->blk[ch0].d.cout ? 0 : (size_t)bb->lane_cap * ch_hw * bb->chain_cout); };
+    auto ch_dw = [&](int ce) { return ws.dwbuf + (ce == bb->blk[ch0].ce ? 0 : (size_t)bb->lane_cap * ch_hw * bb->chain_ce); };
+    auto ch_pool = [&](int ce) { return ws.pool_part + (ce == bb->blk[ch0].ce ? 0 : (size_t)bb->lane_cap * bb->chain_ce); };
+    _Float16 *xbase = nullptr, *ybase = nullptr;   // inside the chain: the buffers x and the next output live in
     if (!bb->fuse_stem) {   // (fused: the stem tensor never exists in HBM, no "stem" activation to keep)
         STEP("stem", "stem_conv", launch_stem(patches_dev, bb->stem_w, bb->stem_b, bb->stem_pad, x, n, bb->stem_ch, st));
         SAVE("stem", x, (size_t)n * 112 * 112 * bb->stem_ch, true);
@@ -1187,6 +1236,14 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             ma.dwdiag = B.mid14m ? B.dw_diag : nullptr;
             ma.nsplit = B.mid14m ? 1 : 4;
             if (bb->mid_clk && i == 10) ma.dbg_clk = bb->mid_clk + (size_t)lane_idx * bb->lane_cap * 128;
+            if (ch0 >= 0 && i > ch0 && i <= ch1) {
+                ma.D = ch_dw(B.ce);
+                ma.pool = ch_pool(B.ce);
+                Chain14Phase& ph = ca.ph[ca.nph++];
+                ph.kind = chain14_mid_kind(ma.Cin, ma.ks, ma.Ce);
+                ph.mid = ma;
+                break;
+            }
             STEP(nm, B.front_label, launch_mid14(ma, st));
             break;
         }
@@ -1241,6 +1298,24 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             pa.dbg_clk = bb->keep ? bb->dbg_clk : nullptr;
             pa.B = n; pa.HW = HWo; pa.K = B.ce; pa.N = B.d.cout; pa.CSP = B.cs4; pa.nparts = B.nparts;
             pa.psc = (float)(1.0 / ((double)HWo * LOG2E));
+            if (ch0 >= 0 && i >= ch0 && i <= ch1) {
+                if (i == ch0) { xbase = x; ybase = y; }
+                pa.X = ch_dw(B.ce);
+                pa.pool_part = ch_pool(B.ce);
+                pa.Y = ch_act(ybase, B.d.cout);
+                Chain14Phase& ph = ca.ph[ca.nph++];
+                ph.kind = chain14_proj_kind(pa.K, pa.N, pa.HW, pa.res ? 1 : 0);
+                ph.pp = pa;
+                x = pa.Y;
+                std::swap(xbase, ybase);
+                y = ybase;   // (after the chain: the other buffer, whose tensors are dead by then)
+                if (i == ch1) {
+                    ca.B = n;
+                    snprintf(nm, sizeof nm, "b%d.projse-b%d.projse.chain", ch0, ch1);
+                    STEP(nm, "chain14", launch_chain14(ca, st));
+                }
+                continue;
+            }
             snprintf(nm, sizeof nm, "b%d.projse", i);
             STEP(nm, B.back_label, launch_proj_patch(pa, st));
             snprintf(nm, sizeof nm, "b%d.gate", i);

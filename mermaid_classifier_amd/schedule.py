@@ -15,7 +15,7 @@ from .weights import B0_BLOCKS, FEATURE_DIM
 
 class Launch(NamedTuple):
     name: str
-    kind: str          # stem | expand | dw | se | project | head
+    kind: str          # stem | expand | dw | se | project | head, or a fused alternative: mbconv | stem_dw | projse | tail | chain
     bytes: int         # algorithmic HBM bytes
     flops: int         # 2*MAC (MFMA/VALU useful work)
 
@@ -52,6 +52,10 @@ def b0_launches(batch: int) -> List[Launch]:
             out.append(Launch(f"b{i}.projse", "projse", m_out * (ce + cout) * 2 + res + batch * ce * 4 + cout * ce * 2 + 2 * cs * ce * 2,
                               2 * m_out * ce * cout + 2 * batch * 2 * cs * ce))
         h = ho
+    # b7.projse .. b10.projse as one launch (chain14_kernel): the members' kernels one after the other per patch, so their sums
+    chain = ["b7.projse"] + [f"b{i}.{half}" for i in (8, 9, 10) for half in ("mbconv", "projse")]
+    members = [l for l in out if l.name in chain]
+    out.append(Launch("b7.projse-b10.projse.chain", "chain", sum(l.bytes for l in members), sum(l.flops for l in members)))
     # blocks 12..15 chained in one launch (tail7_kernel): only the 7x7 block input/output and the weights move
     tail = [l for l in out if l.name.split(".")[0] in ("b12", "b13", "b14", "b15") and l.kind in ("mbconv", "se", "project")]
     w_bytes = 4 * (1152 * 192 * 2 + 15 * 1152 * 4 + 2 * 48 * 1152 * 2) + (3 * 192 + 320) * 1152 * 2
@@ -80,7 +84,7 @@ def totals(batch: int, launched=None) -> Dict[str, float]:
         names = set(launched)
         ls = [l for l in ls if l.name in names]
     else:
-        ls = [l for l in ls if l.kind not in ("mbconv", "stem_dw", "tail", "projse")]
+        ls = [l for l in ls if l.kind not in ("mbconv", "stem_dw", "tail", "projse", "chain")]
     return {"bytes": float(sum(l.bytes for l in ls)), "flops": float(sum(l.flops for l in ls)),
             "bytes_per_patch": sum(l.bytes for l in ls) / batch, "flops_per_patch": sum(l.flops for l in ls) / batch}
 
