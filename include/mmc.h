@@ -275,6 +275,25 @@ int mmc_featureset_read(mmc_featureset* fs, int64_t first, int64_t n, float* X, 
 #define MMC_TRAIN_CHUNK_ROWS_DEFAULT 16384
 int mmc_trainer_partial_fit_set(mmc_trainer* t, mmc_featureset* fs, const int64_t* visit, int64_t n, int batch_size,
                                 double* avg_loss, void* hip_stream);
+/* A sweep's pass: mmc_trainer_partial_fit_set for `count` trainers over one set, in the launches of one pass.
+ * Replaces: S runs of the epoch body of MermaidTrainer.__call__ (mermaid_classifier/pyspacer/trainer.py:138-145), one per configuration
+ *   of a hyper-parameter sweep -- what docs/research/hidden-layer-experiments.md (architectures x learning rates) and
+ *   docs/research/balancing-experiments.md (15 configurations screened, 3 confirmed) ran as separate processes.  One Adam step of one
+ *   head is some 30 small launches that leave most of the device idle; here step s of the pass is issued once for every member that
+ *   still has a step s, each kind of launch once with the member as a grid dimension, on `hip_stream` alone.
+ * For every member m the call does what mmc_trainer_partial_fit_set(trainers[m], fs, visit[m], n[m], batch_size[m], &avg_loss[m],
+ *   hip_stream) does: same parameters, Adam moments, step count and avg_loss[m], bit for bit (each member's arithmetic and every
+ *   reduction's decomposition are the solo kernels'), independent of MMC_TRAIN_CHUNK_ROWS.  The members stay ordinary trainers: every
+ *   other mmc_trainer_* / mmc_calibrator_* call and later solo passes work on them unchanged.
+ * Members may differ in depth, widths, optimizer hyper-parameters, class weights, step count so far, n, visiting order and mini-batch
+ *   size (so they finish at different steps); they share dims[0], the class count and the device with the set.
+ * Everything is checked, and every member's buffers are reserved, before the first launch: NULL arrays, count outside
+ *   [1, MMC_TRAINER_GROUP_MAX], a NULL member, one handle twice, and per member whatever mmc_trainer_partial_fit_set rejects (the
+ *   message names the member) return MMC_ERR_ARG; a failed allocation returns MMC_ERR_NOMEM.  Either way no member's parameters,
+ *   moments or step count change.  avg_loss (count doubles, or NULL) is zeroed on failure whenever count is in range. */
+#define MMC_TRAINER_GROUP_MAX 16
+int mmc_trainer_group_partial_fit_set(mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit,
+                                      const int64_t* n, const int* batch_size, double* avg_loss, void* hip_stream);
 /* mmc_trainer_evaluate_q32 (trainer.py:295-342) on rows [first, first+n) of the set: the forward and the labels read the set, the
  * per-chunk int64 totals add up on the device, and the call makes one 16-byte device-to-host copy and one synchronisation.  The sums
  * are integers, so they equal the host-fed call's on the same rows for any first / n, and add up exactly over any split.  n is bounded

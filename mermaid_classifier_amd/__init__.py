@@ -10,6 +10,7 @@ from .classify import PointClassifier, PointPredictions  # noqa: F401
 from .calibration import CalibratedMLP, ParityError, calibrate, evaluate, export_artifact  # noqa: F401
 from .featureset import FeatureSet  # noqa: F401
 from .training import epoch_loop, train_and_validate, train_classifier  # noqa: F401
+from .sweep import SweepConfig, partial_fit_rows_group, sweep_loop, train_sweep  # noqa: F401
 from .validation import Validation, previous_accuracies, validate  # noqa: F401
 from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, grouped_validate  # noqa: F401
 from .ranking import RankedValidation, ranking_validate, similarity_levels  # noqa: F401
@@ -21,6 +22,7 @@ __all__ = [
     "PointClassifier", "PointPredictions",
     "CalibratedMLP", "ParityError", "calibrate", "evaluate", "export_artifact",
     "FeatureSet", "epoch_loop", "train_classifier", "train_and_validate",
+    "SweepConfig", "partial_fit_rows_group", "sweep_loop", "train_sweep",
     "Validation", "validate", "previous_accuracies",
     "grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability",
     "ranking_validate", "RankedValidation", "similarity_levels",

@@ -19,6 +19,7 @@ MMC_EVAL_TOTALS = 5   # include/mmc.h: length of mmc_head_evaluate's totals
 MMC_GROUPED_MAX_BINS, MMC_COVER_SUMS = 64, 8   # include/mmc.h: mmc_head_evaluate_grouped
 MMC_GROUPED_MAX_SOURCE_CELLS, MMC_GROUPED_MAX_COVER_CELLS = 1 << 26, 1 << 28
 MMC_RANKED_MAX_K = 16   # include/mmc.h: selection rounds of mmc_head_evaluate_ranked
+MMC_TRAINER_GROUP_MAX = 16   # include/mmc.h: members of one mmc_trainer_group_partial_fit_set call
 
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
@@ -31,7 +32,7 @@ SYMBOLS = [
     "mmc_trainer_logits", "mmc_trainer_evaluate", "mmc_trainer_evaluate_q32",
     "mmc_calibrator_create", "mmc_calibrator_destroy", "mmc_calibrator_add_features", "mmc_calibrator_add_scores", "mmc_calibrator_fit",
     "mmc_featureset_create", "mmc_featureset_destroy", "mmc_featureset_rows", "mmc_featureset_dim", "mmc_featureset_append", "mmc_featureset_read",
-    "mmc_trainer_partial_fit_set", "mmc_trainer_evaluate_set_q32", "mmc_calibrator_add_set",
+    "mmc_trainer_partial_fit_set", "mmc_trainer_group_partial_fit_set", "mmc_trainer_evaluate_set_q32", "mmc_calibrator_add_set",
     "mmc_head_evaluate", "mmc_head_evaluate_set", "mmc_head_evaluate_grouped", "mmc_head_evaluate_grouped_set",
     "mmc_head_evaluate_ranked", "mmc_head_evaluate_ranked_set",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
@@ -147,6 +148,9 @@ def _load() -> C.CDLL:
     lib.mmc_featureset_read.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.mmc_trainer_partial_fit_set.restype = i32
     lib.mmc_trainer_partial_fit_set.argtypes = [vp, vp, vp, i64, i32, C.POINTER(C.c_double), vp]
+    lib.mmc_trainer_group_partial_fit_set.restype = i32
+    lib.mmc_trainer_group_partial_fit_set.argtypes = [C.POINTER(vp), i32, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(i32),
+                                                      C.POINTER(C.c_double), vp]
     lib.mmc_trainer_evaluate_set_q32.restype = i32
     lib.mmc_trainer_evaluate_set_q32.argtypes = [vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64), vp]
     lib.mmc_calibrator_add_set.restype = i32

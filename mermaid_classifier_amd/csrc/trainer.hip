@@ -16,7 +16,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
@@ -31,16 +33,24 @@ enum { TEPI_NONE = 0, TEPI_BIAS_RELU = 1, TEPI_BIAS = 2, TEPI_MASK = 3, TEPI_L2 
 // C[M][N] = op(A)[M][K] . op(B)[K][N] (+ epilogue).  TA: A is stored [K][M]; TB: B is stored [N][K].
 // 64x64 output tile per 256-thread workgroup, K in steps of 16 through LDS (k-major tiles, so every transpose flavour is
 // index arithmetic at staging time); wave w owns the 32x32 quadrant (w>>1, w&1) as 2x2 MFMA fragments.
+//
+// Every kernel of a step is a __device__ body called from two __global__ kernels: the solo one (one trainer per launch) and the
+// grouped one (mmc_trainer_group_partial_fit_set: a member of the group per blockIdx.z, its operands in a by-value descriptor).  Both
+// inline the same body with the same template arguments, so a member's arithmetic -- and every bit it produces -- is the solo one's.
+// LDS is declared by the kernel and handed in, so a grouped kernel that switches between two epilogues holds one pair of tiles.
+// Which multiply-add pairs are fused is part of the arithmetic, and the compiler does not decide it alike for two callers of one body
+// (left alone it fused v * beta2 + ... of adam_elems in the grouped kernel only).  So the bodies compile with contraction off and
+// spell out the fusions the solo kernels have always had: fmaf where they fuse, plain operators where they round twice.
 template <bool TA, bool TB, int EPI>
-__global__ __launch_bounds__(256) void tgemm_f32_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                                                        float* __restrict__ C, int M, int N, int K,
-                                                        const float* __restrict__ aux,   // bias[N] | mask[M][N] | W[M][N]
-                                                        float scale)                     // EPI_L2: alpha / mb
+__device__ __forceinline__ void tgemm_f32_tile(float (&As)[16][68], float (&Bs)[16][68], int tile_m, int tile_n,
+                                               const float* __restrict__ A, const float* __restrict__ B,
+                                               float* __restrict__ C, int M, int N, int K,
+                                               const float* __restrict__ aux,   // bias[N] | mask[M][N] | W[M][N]
+                                               float scale)                     // EPI_L2: alpha / mb
 {
-    __shared__ float As[16][68];
-    __shared__ float Bs[16][68];
+#pragma clang fp contract(off)   // the one fused operation (EPI_L2) is written as fmaf
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = blockIdx.x * 64, n0 = blockIdx.y * 64;
+    const int m0 = tile_m * 64, n0 = tile_n * 64;
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
     const int li = lane & 15, lq = lane >> 4;
     typedef float f4 __attribute__((ext_vector_type(4)));
@@ -97,19 +107,55 @@ __global__ __launch_bounds__(256) void tgemm_f32_kernel(const float* __restrict_
                 if (EPI == TEPI_BIAS_RELU) v = fmaxf(v + aux[n], 0.f);
                 if (EPI == TEPI_BIAS) v = v + aux[n];
                 if (EPI == TEPI_MASK) v = aux[(size_t)m * N + n] > 0.f ? v : 0.f;
-                if (EPI == TEPI_L2) v = v + scale * aux[(size_t)m * N + n];
+                if (EPI == TEPI_L2) v = fmaf(scale, aux[(size_t)m * N + n], v);
                 C[(size_t)m * N + n] = v;
             }
 }
 
+template <bool TA, bool TB, int EPI>
+__global__ __launch_bounds__(256) void tgemm_f32_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                        float* __restrict__ C, int M, int N, int K, const float* __restrict__ aux,
+                                                        float scale)
+{
+    __shared__ float As[16][68];
+    __shared__ float Bs[16][68];
+    tgemm_f32_tile<TA, TB, EPI>(As, Bs, blockIdx.x, blockIdx.y, A, B, C, M, N, K, aux, scale);
+}
+
+// ---- grouped forms: one member per blockIdx.z; the grid is the largest member's and a workgroup outside its own member's extent
+// leaves before its first barrier (the test reads kernel arguments and block indices only: block-uniform).
+struct GemmDesc {
+    const float *A, *B;
+    float* C;
+    const float* aux;
+    int M, N, K, epi;
+    float scale;
+};
+struct GemmGroup { GemmDesc d[MMC_TRAINER_GROUP_MAX]; };
+
+// EPI0 / EPI1: the epilogues the members of one launch can have (forward: hidden layer or a member's last; otherwise one kind)
+template <bool TA, bool TB, int EPI0, int EPI1>
+__global__ __launch_bounds__(256) void tgemm_f32_group_kernel(const GemmGroup g)
+{
+    __shared__ float As[16][68];
+    __shared__ float Bs[16][68];
+    const GemmDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 64 >= d.M || (int)blockIdx.y * 64 >= d.N) return;
+    if (EPI0 == EPI1 || d.epi == EPI0)
+        tgemm_f32_tile<TA, TB, EPI0>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale);
+    else
+        tgemm_f32_tile<TA, TB, EPI1>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale);
+}
+
 // One wave per row: log-softmax, weighted negative log-likelihood, gradient of the weighted-mean loss w.r.t. the logits.
 // F.cross_entropy(logits, y, weight=w) = sum_i w[y_i] * nll_i / sum_i w[y_i]   (torch_classifier.py:278)
-__global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
-                                                      const float* __restrict__ cw,   // [K] or null
-                                                      float inv_wsum, float* __restrict__ dlogits, float* __restrict__ row_loss)
+__device__ __forceinline__ void ce_grad_rows(int block, const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
+                                             const float* __restrict__ cw,   // [K] or null
+                                             float inv_wsum, float* __restrict__ dlogits, float* __restrict__ row_loss)
 {
+#pragma clang fp contract(off)   // nothing here has ever been fused
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int row = block * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const float* z = logits + (size_t)row * K;
     float mx = -INFINITY;
@@ -131,10 +177,34 @@ __global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ 
     if (lane == 0) row_loss[row] = w * (lse - (z[yi] - mx)) * inv_wsum;
 }
 
-// db[n] = sum_m dZ[m][n]; thread per column, rows in order (four chains)
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ dZ, int M, int N, float* __restrict__ db)
+__global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
+                                                      const float* __restrict__ cw, float inv_wsum, float* __restrict__ dlogits,
+                                                      float* __restrict__ row_loss)
 {
-    const int n = blockIdx.x * 256 + threadIdx.x;
+    ce_grad_rows(blockIdx.x, logits, y, M, K, cw, inv_wsum, dlogits, row_loss);
+}
+
+struct CeDesc {
+    const float* logits;
+    const int32_t* y;
+    const float* cw;
+    float *dlogits, *row_loss;
+    int M, K;
+    float inv_wsum;
+};
+struct CeGroup { CeDesc d[MMC_TRAINER_GROUP_MAX]; };
+
+__global__ __launch_bounds__(256) void ce_grad_group_kernel(const CeGroup g)
+{
+    const CeDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 4 >= d.M) return;
+    ce_grad_rows(blockIdx.x, d.logits, d.y, d.M, d.K, d.cw, d.inv_wsum, d.dlogits, d.row_loss);
+}
+
+// db[n] = sum_m dZ[m][n]; thread per column, rows in order (four chains)
+__device__ __forceinline__ void colsum_cols(int block, const float* __restrict__ dZ, int M, int N, float* __restrict__ db)
+{
+    const int n = block * 256 + threadIdx.x;
     if (n >= N) return;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     int m = 0;
@@ -148,12 +218,31 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ d
     db[n] = (s0 + s1) + (s2 + s3);
 }
 
-// partial[blockIdx.x] = sum of x[i]^2 over this block's grid-stride slice (fixed order: per-thread chain, then LDS tree)
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, size_t n, float* __restrict__ partial)
+__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ dZ, int M, int N, float* __restrict__ db)
 {
-    __shared__ float red[256];
+    colsum_cols(blockIdx.x, dZ, M, N, db);
+}
+
+struct ColsumDesc {
+    const float* dZ;
+    float* db;
+    int M, N;
+};
+struct ColsumGroup { ColsumDesc d[MMC_TRAINER_GROUP_MAX]; };
+
+__global__ __launch_bounds__(256) void colsum_group_kernel(const ColsumGroup g)
+{
+    const ColsumDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 256 >= d.N) return;
+    colsum_cols(blockIdx.x, d.dZ, d.M, d.N, d.db);
+}
+
+// partial[blockIdx.x] = sum of x[i]^2 over this block's grid-stride slice (fixed order: per-thread chain, then LDS tree)
+__device__ __forceinline__ void sumsq_slice(float (&red)[256], const float* __restrict__ x, size_t n, float* __restrict__ partial)
+{
+#pragma clang fp contract(off)
     float s = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) s += x[i] * x[i];
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) s = fmaf(x[i], x[i], s);
     red[threadIdx.x] = s;
     __syncthreads();
     for (int o = 128; o >= 1; o >>= 1) {
@@ -163,15 +252,36 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
-// loss_out[0] = sum(row_loss[0..M)) + reg_scale * sum(partials[0..P))   (one workgroup, fixed order)
-__global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ row_loss, int M, const float* __restrict__ partials,
-                                                            int P, float reg_scale, float* __restrict__ loss_out)
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, size_t n, float* __restrict__ partial)
 {
     __shared__ float red[256];
+    sumsq_slice(red, x, n, partial);
+}
+
+struct SumsqDesc {
+    const float* x;
+    float* partial;
+    size_t n;
+};
+struct SumsqGroup { SumsqDesc d[MMC_TRAINER_GROUP_MAX]; };
+
+// gridDim.x is the solo launch's 256 blocks, so a member's slices and partials are the solo ones
+__global__ __launch_bounds__(256) void sumsq_group_kernel(const SumsqGroup g)
+{
+    __shared__ float red[256];
+    const SumsqDesc& d = g.d[blockIdx.z];
+    sumsq_slice(red, d.x, d.n, d.partial);
+}
+
+// loss_out[0] = sum(row_loss[0..M)) + reg_scale * sum(partials[0..P))   (one workgroup, fixed order)
+__device__ __forceinline__ void loss_finalize_one(float (&red)[256], const float* __restrict__ row_loss, int M,
+                                                  const float* __restrict__ partials, int P, float reg_scale, float* __restrict__ loss_out)
+{
+#pragma clang fp contract(off)
     float s = 0.f, q = 0.f;
     for (int i = threadIdx.x; i < M; i += 256) s += row_loss[i];
     for (int i = threadIdx.x; i < P; i += 256) q += partials[i];
-    red[threadIdx.x] = s + reg_scale * q;
+    red[threadIdx.x] = fmaf(reg_scale, q, s);
     __syncthreads();
     for (int o = 128; o >= 1; o >>= 1) {
         if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
@@ -180,13 +290,36 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
     if (threadIdx.x == 0) loss_out[0] = red[0];
 }
 
+__global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ row_loss, int M, const float* __restrict__ partials,
+                                                            int P, float reg_scale, float* __restrict__ loss_out)
+{
+    __shared__ float red[256];
+    loss_finalize_one(red, row_loss, M, partials, P, reg_scale, loss_out);
+}
+
+struct LossDesc {
+    const float *row_loss, *partials;
+    float* loss_out;
+    int M, P;
+    float reg_scale;
+};
+struct LossGroup { LossDesc d[MMC_TRAINER_GROUP_MAX]; };
+
+__global__ __launch_bounds__(256) void loss_finalize_group_kernel(const LossGroup g)
+{
+    __shared__ float red[256];
+    const LossDesc& d = g.d[blockIdx.z];
+    loss_finalize_one(red, d.row_loss, d.M, d.partials, d.P, d.reg_scale, d.loss_out);
+}
+
 // torch.optim.Adam (single-tensor path), in its order of operations:
 //   exp_avg.lerp_(grad, 1 - beta1); exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
 //   denom = exp_avg_sq.sqrt() / sqrt(1 - beta2^t) + eps;  param.addcdiv_(exp_avg, denom, value=-(lr / (1 - beta1^t)))
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, size_t n, float om_beta1, float beta2, float om_beta2, float eps,
-                                                   float step_size, float bc2_sqrt)
+__device__ __forceinline__ void adam_elems(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, size_t n, float om_beta1, float beta2, float om_beta2, float eps,
+                                           float step_size, float bc2_sqrt)
 {
+#pragma clang fp contract(off)   // two roundings each in mi, vi and denom; the parameter update is one fused multiply-add
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float gi = g[i];
@@ -196,7 +329,29 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     m[i] = mi;
     v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - step_size * (mi / denom);
+    p[i] = fmaf(-step_size, mi / denom, p[i]);
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, size_t n, float om_beta1, float beta2, float om_beta2, float eps,
+                                                   float step_size, float bc2_sqrt)
+{
+    adam_elems(p, g, m, v, n, om_beta1, beta2, om_beta2, eps, step_size, bc2_sqrt);
+}
+
+struct AdamDesc {
+    float* p;
+    const float* g;
+    float *m, *v;
+    size_t n;
+    float om_beta1, beta2, om_beta2, eps, step_size, bc2_sqrt;
+};
+struct AdamGroup { AdamDesc d[MMC_TRAINER_GROUP_MAX]; };
+
+__global__ __launch_bounds__(256) void adam_group_kernel(const AdamGroup g)
+{
+    const AdamDesc& d = g.d[blockIdx.z];
+    adam_elems(d.p, d.g, d.m, d.v, d.n, d.om_beta1, d.beta2, d.om_beta2, d.eps, d.step_size, d.bc2_sqrt);
 }
 
 // Xo[i][:] = Xn[order[i]][:], yo[i] = yn[order[i]]: the visiting order of a pass applied on the device (one float4 per thread)
@@ -498,6 +653,112 @@ extern "C" int mmc_trainer_partial_fit(mmc_trainer* t, const float* X, const int
     return mmc_trainer_partial_fit_ordered(t, X, y, nullptr, n, batch_size, avg_loss, hip_stream);
 }
 
+// ---- passes over a resident feature set: what the solo call and the grouped call share ------------------------------------
+namespace {
+
+// how one trainer takes one pass over rows of a set: mini-batch, steps, its chunks of whole mini-batches, every step's weight sum
+struct SetPass {
+    int mb = 0, steps = 0;
+    int64_t chunk = 0, steps_per_chunk = 0, stage_rows = 0;
+    std::vector<double> wsums;
+};
+
+// `who` prefixes the message: "" for the solo call, "member 3: " for a member of a group
+int check_set_pass(const char* who, const mmc_trainer* t, const mmc_featureset* fs, const int64_t* visit, int64_t n, int batch_size)
+{
+    if (fs->dim != t->dims[0]) return mmc_fail(MMC_ERR_ARG, "%sfeature set has %d columns, trainer expects %d", who, fs->dim, t->dims[0]);
+    if (fs->K != t->K) return mmc_fail(MMC_ERR_ARG, "%sfeature set has %d classes, trainer %d", who, fs->K, t->K);
+    if (fs->device != t->device) return mmc_fail(MMC_ERR_ARG, "%sfeature set is on device %d, trainer on device %d", who, fs->device, t->device);
+    if (n < 1) return mmc_fail(MMC_ERR_ARG, "%sn = %lld must be positive", who, (long long)n);
+    if (batch_size < 1) return mmc_fail(MMC_ERR_ARG, "%sbatch_size = %d must be positive", who, batch_size);
+    if (!visit && n != fs->n) return mmc_fail(MMC_ERR_ARG, "%swithout a visiting order n must be the set's %lld rows (got %lld)", who, (long long)fs->n, (long long)n);
+    if (visit)
+        for (int64_t i = 0; i < n; ++i)
+            if (visit[i] < 0 || visit[i] >= fs->n)
+                return mmc_fail(MMC_ERR_ARG, "%svisit[%lld] = %lld outside [0, %lld)", who, (long long)i, (long long)visit[i], (long long)fs->n);
+    return 0;
+}
+
+int train_chunk_bound(int64_t* bound)
+{
+    *bound = MMC_TRAIN_CHUNK_ROWS_DEFAULT;
+    if (const char* env = std::getenv("MMC_TRAIN_CHUNK_ROWS")) {
+        char* end = nullptr;
+        const long long v = std::strtoll(env, &end, 10);
+        if (end == env || *end || v < 1) return mmc_fail(MMC_ERR_ARG, "MMC_TRAIN_CHUNK_ROWS = '%s' is not a positive integer", env);
+        *bound = v;
+    }
+    return 0;
+}
+
+int plan_set_pass(const char* who, const mmc_trainer* t, const mmc_featureset* fs, const int64_t* visit, int64_t n, int batch_size,
+                  int64_t bound, SetPass* p)
+{
+    const int mb = (int)(batch_size < n ? batch_size : n);
+    if ((n + mb - 1) / mb > (int64_t)1 << 30) return mmc_fail(MMC_ERR_ARG, "%s%lld rows in mini-batches of %d: too many steps for one pass", who, (long long)n, mb);
+    p->mb = mb;
+    p->steps = (int)((n + mb - 1) / mb);
+    // the largest multiple of the mini-batch not above the bound, at least one mini-batch, and no more than a gather's grid / `rows` hold
+    int64_t chunk = bound / mb * mb;
+    if (chunk < mb) chunk = mb;
+    const int64_t chunk_max = ((int64_t)1 << 30) / mb * mb;
+    if (chunk > chunk_max) chunk = chunk_max;
+    p->chunk = chunk;
+    p->steps_per_chunk = chunk / mb;
+    p->stage_rows = chunk < n ? chunk : n;
+    // as in the host-fed pass: every mini-batch's weight sum is checked before anything is uploaded or launched
+    p->wsums.resize(p->steps);
+    const int32_t* yh = fs->y_host.data();
+    for (int s = 0; s < p->steps; ++s) {
+        const int64_t start = (int64_t)s * mb;
+        const int cur = (int)((n - start) < mb ? (n - start) : mb);
+        double wsum = 0.0;
+        if (t->cw) { for (int i = 0; i < cur; ++i) wsum += t->cw_host[yh[visit ? visit[start + i] : start + i]]; } else wsum = cur;
+        if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "%smini-batch %d has zero total class weight", who, s);
+        p->wsums[s] = wsum;
+    }
+    return 0;
+}
+
+// the trainer's staging, activations and loss slots for the pass, and its device copy of the visiting order (not yet uploaded)
+int reserve_set_pass(mmc_trainer* t, const SetPass& p, const int64_t* visit, int64_t n)
+{
+    int r = trainer_reserve(t, p.stage_rows, p.mb, p.steps);
+    if (r) return r;
+    if (visit && n > t->cap_visit) {
+        hipFree(t->visit);
+        t->visit = nullptr; t->cap_visit = 0;
+        T_TRY(hipMalloc((void**)&t->visit, (size_t)n * 8 + 256));
+        t->cap_visit = n;
+    }
+    return 0;
+}
+
+// rows [c0, c0 + rows) of the pass into the staging t->X / t->y
+int gather_chunk(mmc_trainer* t, const mmc_featureset* fs, bool visited, int64_t c0, int rows, hipStream_t st)
+{
+    const int64_t* vis = visited ? t->visit + c0 : nullptr;
+    if (fs->dim & 3)
+        hipLaunchKernelGGL(gather_set_rows_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, rows, fs->dim, t->X, t->y);
+    else
+        hipLaunchKernelGGL(gather_set_rows_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, rows, fs->dim, t->X, t->y);
+    T_TRY(hipGetLastError());
+    return 0;
+}
+
+// torch_classifier.py:293-298: sum of loss.item() * mb_size over the steps, over n
+double pass_avg_loss(const std::vector<float>& h, const SetPass& p, int64_t n)
+{
+    double tot = 0.0;
+    for (int s = 0; s < p.steps; ++s) {
+        const int64_t start = (int64_t)s * p.mb;
+        tot += (double)h[s] * (double)(int)((n - start) < p.mb ? (n - start) : p.mb);
+    }
+    return tot / (double)n;
+}
+
+}  // namespace
+
 // The pass of mmc_trainer_partial_fit_ordered over rows that are already on the device: position i visits row visit[i] of `fs`.
 // Nothing but `visit` is uploaded.  The visited rows and labels are gathered into the mini-batch staging (t->X / t->y) a chunk of whole
 // mini-batches at a time, and that chunk's steps follow on the same stream, so the steps run the kernels of the host-fed pass on the
@@ -507,80 +768,226 @@ extern "C" int mmc_trainer_partial_fit_set(mmc_trainer* t, mmc_featureset* fs, c
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
-    if (fs->dim != t->dims[0]) return mmc_fail(MMC_ERR_ARG, "feature set has %d columns, trainer expects %d", fs->dim, t->dims[0]);
-    if (fs->K != t->K) return mmc_fail(MMC_ERR_ARG, "feature set has %d classes, trainer %d", fs->K, t->K);
-    if (fs->device != t->device) return mmc_fail(MMC_ERR_ARG, "feature set is on device %d, trainer on device %d", fs->device, t->device);
-    if (n < 1) return mmc_fail(MMC_ERR_ARG, "n = %lld must be positive", (long long)n);
-    if (batch_size < 1) return mmc_fail(MMC_ERR_ARG, "batch_size = %d must be positive", batch_size);
-    if (!visit && n != fs->n) return mmc_fail(MMC_ERR_ARG, "without a visiting order n must be the set's %lld rows (got %lld)", (long long)fs->n, (long long)n);
-    if (visit)
-        for (int64_t i = 0; i < n; ++i)
-            if (visit[i] < 0 || visit[i] >= fs->n)
-                return mmc_fail(MMC_ERR_ARG, "visit[%lld] = %lld outside [0, %lld)", (long long)i, (long long)visit[i], (long long)fs->n);
-    int64_t bound = MMC_TRAIN_CHUNK_ROWS_DEFAULT;
-    if (const char* env = std::getenv("MMC_TRAIN_CHUNK_ROWS")) {
-        char* end = nullptr;
-        const long long v = std::strtoll(env, &end, 10);
-        if (end == env || *end || v < 1) return mmc_fail(MMC_ERR_ARG, "MMC_TRAIN_CHUNK_ROWS = '%s' is not a positive integer", env);
-        bound = v;
-    }
-    const int mb = (int)(batch_size < n ? batch_size : n);
-    if ((n + mb - 1) / mb > (int64_t)1 << 30) return mmc_fail(MMC_ERR_ARG, "%lld rows in mini-batches of %d: too many steps for one pass", (long long)n, mb);
-    const int steps = (int)((n + mb - 1) / mb);
-    // the largest multiple of the mini-batch not above the bound, at least one mini-batch, and no more than a gather's grid / `rows` hold
-    int64_t chunk = bound / mb * mb;
-    if (chunk < mb) chunk = mb;
-    const int64_t chunk_max = ((int64_t)1 << 30) / mb * mb;
-    if (chunk > chunk_max) chunk = chunk_max;
-    const int64_t steps_per_chunk = chunk / mb;
-    const int64_t stage_rows = chunk < n ? chunk : n;
-    // as in the host-fed pass: every mini-batch's weight sum is checked before anything is uploaded or launched
-    std::vector<double> wsums(steps);
-    const int32_t* yh = fs->y_host.data();
-    for (int s = 0; s < steps; ++s) {
-        const int64_t start = (int64_t)s * mb;
-        const int cur = (int)((n - start) < mb ? (n - start) : mb);
-        double wsum = 0.0;
-        if (t->cw) { for (int i = 0; i < cur; ++i) wsum += t->cw_host[yh[visit ? visit[start + i] : start + i]]; } else wsum = cur;
-        if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "mini-batch %d has zero total class weight", s);
-        wsums[s] = wsum;
-    }
+    int r = check_set_pass("", t, fs, visit, n, batch_size);
+    if (r) return r;
+    int64_t bound = 0;
+    if ((r = train_chunk_bound(&bound))) return r;
+    SetPass p;
+    if ((r = plan_set_pass("", t, fs, visit, n, batch_size, bound, &p))) return r;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     T_TRY(hipSetDevice(t->device));
-    int r = trainer_reserve(t, stage_rows, mb, steps);
-    if (r) return r;
-    if (visit) {
-        if (n > t->cap_visit) {
-            hipFree(t->visit);
-            t->visit = nullptr; t->cap_visit = 0;
-            T_TRY(hipMalloc((void**)&t->visit, (size_t)n * 8 + 256));
-            t->cap_visit = n;
-        }
-        T_TRY(hipMemcpyAsync(t->visit, visit, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    }
-    std::vector<int> sizes(steps);
-    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
-        const int rows = (int)((n - c0) < chunk ? (n - c0) : chunk);
-        const int64_t* vis = visit ? t->visit + c0 : nullptr;
-        if (fs->dim & 3)
-            hipLaunchKernelGGL(gather_set_rows_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, rows, fs->dim, t->X, t->y);
-        else
-            hipLaunchKernelGGL(gather_set_rows_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, rows, fs->dim, t->X, t->y);
-        T_TRY(hipGetLastError());
-        for (int64_t off = 0; off < rows; off += mb) {
-            const int s = (int)(c0 / chunk * steps_per_chunk + off / mb);
-            const int cur = (int)((rows - off) < mb ? (rows - off) : mb);
-            sizes[s] = cur;
-            r = trainer_step(t, off, cur, (float)(1.0 / wsums[s]), t->losses + s, st);
+    if ((r = reserve_set_pass(t, p, visit, n))) return r;
+    if (visit) T_TRY(hipMemcpyAsync(t->visit, visit, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
+        const int rows = (int)((n - c0) < p.chunk ? (n - c0) : p.chunk);
+        if ((r = gather_chunk(t, fs, visit != nullptr, c0, rows, st))) return r;
+        for (int64_t off = 0; off < rows; off += p.mb) {
+            const int s = (int)(c0 / p.chunk * p.steps_per_chunk + off / p.mb);
+            const int cur = (int)((rows - off) < p.mb ? (rows - off) : p.mb);
+            r = trainer_step(t, off, cur, (float)(1.0 / p.wsums[s]), t->losses + s, st);
             if (r) return r;
         }
     }
-    std::vector<float> h(steps);
-    T_TRY(hipMemcpyAsync(h.data(), t->losses, (size_t)steps * 4, hipMemcpyDeviceToHost, st));
+    std::vector<float> h(p.steps);
+    T_TRY(hipMemcpyAsync(h.data(), t->losses, (size_t)p.steps * 4, hipMemcpyDeviceToHost, st));
     T_TRY(hipStreamSynchronize(st));
-    double tot = 0.0;
-    for (int s = 0; s < steps; ++s) tot += (double)h[s] * sizes[s];   // torch_classifier.py:293-298: loss.item() * mb_size
-    if (avg_loss) *avg_loss = tot / (double)n;
+    if (avg_loss) *avg_loss = pass_avg_loss(h, p, n);
+    return MMC_OK;
+}
+
+// ---- a group of trainers, one pass each, in the launches of one ------------------------------------------------------------
+namespace {
+
+struct GroupMember {
+    mmc_trainer* t = nullptr;
+    const int64_t* visit = nullptr;
+    int64_t n = 0;
+    SetPass p;
+    int cur = 0;                        // this step's mini-batch rows
+    float inv_wsum = 0.f;               // this step's 1 / sum of class weights
+    float step_size = 0.f, bc2_sqrt = 0.f;   // this step's Adam scalars
+};
+
+template <bool TA, bool TB, int EPI0, int EPI1>
+int launch_tgemm_group(const GemmGroup& g, int cnt, hipStream_t st)
+{
+    int tm = 0, tn = 0;
+    for (int i = 0; i < cnt; ++i) {
+        tm = std::max(tm, (g.d[i].M + 63) / 64);
+        tn = std::max(tn, (g.d[i].N + 63) / 64);
+    }
+    hipLaunchKernelGGL((tgemm_f32_group_kernel<TA, TB, EPI0, EPI1>), dim3(tm, tn, cnt), dim3(256), 0, st, g);
+    return (int)hipGetLastError();
+}
+
+// trainer_step for every member in `act` at once: each kind of launch once, the member as blockIdx.z.  A member takes part in the
+// launches of the layers it has; the order of its own launches is trainer_step's.
+int trainer_group_step(GroupMember* const* act, int cnt, const int64_t* off, const int* slot, hipStream_t st)
+{
+    int Lmax = 0;
+    for (int i = 0; i < cnt; ++i) {
+        mmc_trainer* t = act[i]->t;
+        t->H[0] = t->X + (size_t)off[i] * t->dims[0];
+        Lmax = std::max(Lmax, t->L);
+    }
+    for (int l = 0; l < Lmax; ++l) {
+        GemmGroup g;
+        int k = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i]->t;
+            if (l >= t->L) continue;
+            g.d[k++] = GemmDesc{t->H[l], t->W[l], t->H[l + 1], t->b[l], act[i]->cur, t->dims[l + 1], t->dims[l],
+                                l == t->L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU, 0.f};
+        }
+        T_K((launch_tgemm_group<false, true, TEPI_BIAS_RELU, TEPI_BIAS>(g, k, st)));
+    }
+    {
+        CeGroup g;
+        int mmax = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i]->t;
+            g.d[i] = CeDesc{t->H[t->L], t->y + off[i], t->cw, t->dZ[t->L], t->row_loss, act[i]->cur, t->K, act[i]->inv_wsum};
+            mmax = std::max(mmax, act[i]->cur);
+        }
+        hipLaunchKernelGGL(ce_grad_group_kernel, dim3((mmax + 3) / 4, 1, cnt), dim3(256), 0, st, g);
+    }
+    for (int l = 0; l < Lmax; ++l) {
+        SumsqGroup g;
+        int k = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i]->t;
+            if (l < t->L) g.d[k++] = SumsqDesc{t->W[l], t->partials + 256 * l, (size_t)t->dims[l + 1] * t->dims[l]};
+        }
+        hipLaunchKernelGGL(sumsq_group_kernel, dim3(256, 1, k), dim3(256), 0, st, g);
+    }
+    {
+        LossGroup g;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i]->t;
+            g.d[i] = LossDesc{t->row_loss, t->partials, t->losses + slot[i], act[i]->cur, 256 * t->L,
+                              (float)(0.5 * t->alpha / (double)act[i]->cur)};
+        }
+        hipLaunchKernelGGL(loss_finalize_group_kernel, dim3(1, 1, cnt), dim3(256), 0, st, g);
+    }
+    for (int l = Lmax - 1; l >= 0; --l) {
+        GemmGroup gw, gz;
+        ColsumGroup gc;
+        int k = 0, kz = 0, nmax = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i]->t;
+            if (l >= t->L) continue;
+            const int no = t->dims[l + 1], ni = t->dims[l], mb = act[i]->cur;
+            gw.d[k] = GemmDesc{t->dZ[l + 1], t->H[l], t->gW[l], t->W[l], no, ni, mb, TEPI_L2, (float)(t->alpha / (double)mb)};
+            gc.d[k] = ColsumDesc{t->dZ[l + 1], t->gb[l], mb, no};
+            ++k;
+            nmax = std::max(nmax, no);
+            if (l > 0) gz.d[kz++] = GemmDesc{t->dZ[l + 1], t->W[l], t->dZ[l], t->H[l], mb, ni, no, TEPI_MASK, 0.f};
+        }
+        T_K((launch_tgemm_group<true, false, TEPI_L2, TEPI_L2>(gw, k, st)));
+        hipLaunchKernelGGL(colsum_group_kernel, dim3((nmax + 255) / 256, 1, k), dim3(256), 0, st, gc);
+        if (kz) T_K((launch_tgemm_group<false, false, TEPI_MASK, TEPI_MASK>(gz, kz, st)));
+    }
+    for (int i = 0; i < cnt; ++i) {
+        mmc_trainer* t = act[i]->t;
+        ++t->t;
+        const double bc1 = 1.0 - std::pow(t->beta1, (double)t->t), bc2 = 1.0 - std::pow(t->beta2, (double)t->t);
+        act[i]->step_size = (float)(t->lr / bc1);
+        act[i]->bc2_sqrt = (float)std::sqrt(bc2);
+    }
+    for (int l = 0; l < Lmax; ++l) {
+        AdamGroup gw, gb;
+        int k = 0;
+        size_t wmax = 0, bmax = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i]->t;
+            if (l >= t->L) continue;
+            const size_t nw = (size_t)t->dims[l + 1] * t->dims[l], nb = (size_t)t->dims[l + 1];
+            const float om1 = (float)(1.0 - t->beta1), om2 = (float)(1.0 - t->beta2), b2f = (float)t->beta2, epsf = (float)t->eps;
+            gw.d[k] = AdamDesc{t->W[l], t->gW[l], t->mW[l], t->vW[l], nw, om1, b2f, om2, epsf, act[i]->step_size, act[i]->bc2_sqrt};
+            gb.d[k] = AdamDesc{t->b[l], t->gb[l], t->mb[l], t->vb[l], nb, om1, b2f, om2, epsf, act[i]->step_size, act[i]->bc2_sqrt};
+            ++k;
+            wmax = std::max(wmax, nw);
+            bmax = std::max(bmax, nb);
+        }
+        hipLaunchKernelGGL(adam_group_kernel, dim3((unsigned)((wmax + 255) / 256), 1, k), dim3(256), 0, st, gw);
+        hipLaunchKernelGGL(adam_group_kernel, dim3((unsigned)((bmax + 255) / 256), 1, k), dim3(256), 0, st, gb);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "trainer group step launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+}  // namespace
+
+// mmc_trainer_partial_fit_set for `count` trainers over one set, step s of every member's pass issued together (include/mmc.h).
+extern "C" int mmc_trainer_group_partial_fit_set(mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit,
+                                                 const int64_t* n, const int* batch_size, double* avg_loss, void* hip_stream)
+{
+    if (avg_loss && count >= 1 && count <= MMC_TRAINER_GROUP_MAX)
+        for (int m = 0; m < count; ++m) avg_loss[m] = 0.0;
+    if (!trainers || !visit || !n || !batch_size) return mmc_fail(MMC_ERR_ARG, "trainers / visit / n / batch_size is NULL");
+    if (count < 1 || count > MMC_TRAINER_GROUP_MAX) return mmc_fail(MMC_ERR_ARG, "count = %d outside [1, %d]", count, MMC_TRAINER_GROUP_MAX);
+    for (int m = 0; m < count; ++m) {
+        if (!trainers[m]) return mmc_fail(MMC_ERR_ARG, "member %d: trainer handle is NULL", m);
+        for (int o = 0; o < m; ++o)
+            if (trainers[o] == trainers[m]) return mmc_fail(MMC_ERR_ARG, "member %d is the same trainer as member %d", m, o);
+    }
+    if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
+    std::vector<GroupMember> mem(count);
+    char who[32];
+    int r = 0;
+    for (int m = 0; m < count; ++m) {
+        std::snprintf(who, sizeof who, "member %d: ", m);
+        if ((r = check_set_pass(who, trainers[m], fs, visit[m], n[m], batch_size[m]))) return r;
+    }
+    int64_t bound = 0;
+    if ((r = train_chunk_bound(&bound))) return r;
+    int max_steps = 0;
+    for (int m = 0; m < count; ++m) {
+        std::snprintf(who, sizeof who, "member %d: ", m);
+        mem[m].t = trainers[m]; mem[m].visit = visit[m]; mem[m].n = n[m];
+        if ((r = plan_set_pass(who, trainers[m], fs, visit[m], n[m], batch_size[m], bound, &mem[m].p))) return r;
+        max_steps = std::max(max_steps, mem[m].p.steps);
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    T_TRY(hipSetDevice(fs->device));
+    // every member's buffers before the first launch: a pass that cannot be staged changes no member
+    for (int m = 0; m < count; ++m)
+        if (reserve_set_pass(mem[m].t, mem[m].p, mem[m].visit, mem[m].n)) {
+            (void)hipGetLastError();
+            return mmc_fail(MMC_ERR_NOMEM, "member %d: could not allocate the buffers of its pass (%lld staged rows, mini-batch %d)", m,
+                            (long long)mem[m].p.stage_rows, mem[m].p.mb);
+        }
+    for (int m = 0; m < count; ++m)
+        if (mem[m].visit) T_TRY(hipMemcpyAsync(mem[m].t->visit, mem[m].visit, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
+    GroupMember* act[MMC_TRAINER_GROUP_MAX];
+    int64_t off[MMC_TRAINER_GROUP_MAX];
+    int slot[MMC_TRAINER_GROUP_MAX];
+    for (int s = 0; s < max_steps; ++s) {
+        int cnt = 0;
+        for (int m = 0; m < count; ++m) {
+            GroupMember& g = mem[m];
+            if (s >= g.p.steps) continue;   // this member's pass is over
+            const int64_t start = (int64_t)s * g.p.mb, c0 = s / g.p.steps_per_chunk * g.p.chunk;
+            if (start == c0) {              // its first step of a chunk: stage the chunk's rows first
+                const int rows = (int)((g.n - c0) < g.p.chunk ? (g.n - c0) : g.p.chunk);
+                if ((r = gather_chunk(g.t, fs, g.visit != nullptr, c0, rows, st))) return r;
+            }
+            g.cur = (int)((g.n - start) < g.p.mb ? (g.n - start) : g.p.mb);
+            g.inv_wsum = (float)(1.0 / g.p.wsums[s]);
+            act[cnt] = &g; off[cnt] = start - c0; slot[cnt] = s;
+            ++cnt;
+        }
+        if ((r = trainer_group_step(act, cnt, off, slot, st))) return r;
+    }
+    std::vector<std::vector<float>> h(count);
+    for (int m = 0; m < count; ++m) {
+        h[m].resize(mem[m].p.steps);
+        T_TRY(hipMemcpyAsync(h[m].data(), mem[m].t->losses, (size_t)mem[m].p.steps * 4, hipMemcpyDeviceToHost, st));
+    }
+    T_TRY(hipStreamSynchronize(st));
+    if (avg_loss)
+        for (int m = 0; m < count; ++m) avg_loss[m] = pass_avg_loss(h[m], mem[m].p, mem[m].n);
     return MMC_OK;
 }
 

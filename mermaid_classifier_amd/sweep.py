@@ -1,0 +1,188 @@
+"""A hyper-parameter sweep of MLP heads trained in lockstep on the MI355X.
+
+The reference trains one head per run of ``MermaidTrainer.__call__`` (``mermaid_classifier/pyspacer/trainer.py:83-293``); the
+sweeps that fixed its production recipe (``docs/research/hidden-layer-experiments.md``: architectures x learning rates;
+``docs/research/balancing-experiments.md``: 15 configurations screened, 3 confirmed) were S such runs side by side.  On one
+MI355X a single head's Adam step is some 30 small launches that leave most of the device idle, so S runs one after the other are
+the worst way to spend it.  Here the S models advance together:
+
+``partial_fit_rows_group``  one pass of ``TorchMLPClassifier.partial_fit_rows`` for each of several classifiers over one resident
+                            ``FeatureSet``, in one ``mmc_trainer_group_partial_fit_set`` call per 16 of them -- every kind of
+                            launch of a step once for the whole group.  Same bits as the passes made one by one.
+``SweepConfig``             what a sweep varies: the classifier's constructor arguments and the row-subset hook.
+``sweep_loop``              ``training.epoch_loop`` for several models at once, device steps passed in (testable without a device).
+``train_sweep``             ``training.train_classifier`` for every configuration, in lockstep: entry i of the result is what
+                            ``train_classifier`` returns for configuration i run alone.
+
+Evaluation and calibration stay per model (``calibration.evaluate`` / ``calibrate``): they are forward-only at 16 384 rows a
+chunk and fill the device on their own.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from .backbone import _current_stream_ptr, _device_index
+from .calibration import CalibratedMLP, calibrate, evaluate
+from .featureset import FeatureSet
+from .torch_classifier import TorchMLPClassifier
+from .training import EarlyStopping, _check_splits, _contiguous_batches
+
+__all__ = ["SweepConfig", "partial_fit_rows_group", "sweep_loop", "train_sweep"]
+
+
+def _rows_per_classifier(rows, count: int) -> List[Any]:
+    """``rows`` as one entry per classifier: None and a single index array stand for every classifier; a list / tuple whose
+    entries are all None or arrays is taken per classifier and must have ``count`` entries."""
+    if rows is None:
+        return [None] * count
+    if isinstance(rows, (list, tuple)) and len(rows) > 0 and all(r is None or np.ndim(r) >= 1 for r in rows):
+        if len(rows) != count:
+            raise ValueError(f"rows has {len(rows)} entries for {count} classifiers")
+        entries = list(rows)
+    else:
+        entries = [rows] * count
+    for r in entries:
+        if r is None:
+            continue
+        arr = np.asarray(r)
+        if arr.ndim != 1 or not (np.issubdtype(arr.dtype, np.integer) or arr.size == 0):
+            raise ValueError(f"rows must be a 1D array of row indices, got {arr.dtype} {arr.shape}")
+    return entries
+
+
+def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, rows=None,
+                           classes: Optional[Sequence[Any]] = None) -> List[TorchMLPClassifier]:
+    """``clf.partial_fit_rows(fs, rows_m, classes)`` for every classifier of ``clfs``, with the device work of all of them in one
+    ``mmc_trainer_group_partial_fit_set`` call per ``MMC_TRAINER_GROUP_MAX`` (16) classifiers.  Parameters, Adam state,
+    ``loss_curve_`` and ``n_iter_`` of each end up exactly as after its own ``partial_fit_rows``.
+
+    ``rows``: None (every row of the set, for everyone), one index array for all, or a list with one entry -- array or None --
+    per classifier.  The classifiers may differ in everything a ``TorchMLPClassifier`` can be configured with (depth, widths,
+    optimizer settings, class weights, mini-batch size, shuffle, seed) and in how many passes they have behind them.
+
+    ``ValueError`` before any device work: ``rows`` that do not fit ``clfs``, the same classifier twice, a classifier on another
+    device than the set.  A pass the library rejects (an index outside the set, a mini-batch of zero class weight, ...) raises
+    as ``partial_fit_rows`` does and changes none of the classifiers of that call."""
+    clfs = list(clfs)
+    entries = _rows_per_classifier(rows, len(clfs))
+    if len({id(c) for c in clfs}) != len(clfs):
+        raise ValueError("the same classifier appears twice in clfs")
+    for i, clf in enumerate(clfs):
+        if _device_index(clf.device) != fs.device_index:
+            raise ValueError(f"classifier {i} is on device {_device_index(clf.device)}, the feature set on device {fs.device_index}")
+    lib = _lib.lib()
+    for first in range(0, len(clfs), _lib.MMC_TRAINER_GROUP_MAX):
+        group = clfs[first:first + _lib.MMC_TRAINER_GROUP_MAX]
+        passes = [clf._begin_rows_pass(fs, r, classes) for clf, r in zip(group, entries[first:])]
+        count = len(group)
+        handles = (C.c_void_p * count)(*[clf._h.value for clf in group])
+        visit = (C.c_void_p * count)(*[None if v is None else v.ctypes.data for v, _, _ in passes])
+        n = (C.c_int64 * count)(*[int(p[1]) for p in passes])
+        batch = (C.c_int * count)(*[int(p[2]) for p in passes])
+        avg = (C.c_double * count)()
+        _lib.check(lib.mmc_trainer_group_partial_fit_set(handles, count, fs._handle(), visit, n, batch, avg,
+                                                         _current_stream_ptr(fs.device_index)))
+        for clf, a in zip(group, avg):
+            clf._end_pass(a)
+    return clfs
+
+
+@dataclass
+class SweepConfig:
+    """One configuration of a sweep: the ``TorchMLPClassifier`` constructor arguments a sweep varies (the defaults are the
+    production head's, trainer.py:118-123) and ``batches``, ``train_classifier``'s row-subset hook -- a callable
+    ``epoch -> iterable of row-index arrays`` into the train set, e.g. a class-balancing subsample; None takes contiguous
+    slices of ``train_sweep``'s ``batch_size`` rows."""
+    hidden_layer_sizes: Tuple[int, ...] = (500, 300, 100)
+    learning_rate_init: float = 1e-4
+    alpha: float = 1e-4
+    class_weight: Optional[dict] = None
+    random_state: Optional[int] = 0
+    batch_size: Any = "auto"
+    beta_1: float = 0.9
+    beta_2: float = 0.999
+    epsilon: float = 1e-8
+    batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None
+
+    def classifier(self, device=0) -> TorchMLPClassifier:
+        """The untrained classifier of this configuration."""
+        return TorchMLPClassifier(hidden_layer_sizes=tuple(self.hidden_layer_sizes), learning_rate_init=self.learning_rate_init,
+                                  alpha=self.alpha, class_weight=self.class_weight, random_state=self.random_state,
+                                  batch_size=self.batch_size, beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.epsilon,
+                                  device=device)
+
+
+def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[Any]]],
+               fit_group: Callable[[List[Any], List[Any]], None], eval_ref: Callable[[Any], float],
+               eval_val: Callable[[Any], Tuple[float, float]], nbr_epochs: int, early_stopping_patience: Optional[int] = None,
+               on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None) -> List[Tuple[Any, Dict[str, Any]]]:
+    """``training.epoch_loop`` for the models ``clfs`` in lockstep.  -> one ``(clf, info)`` per model, each what ``epoch_loop``
+    returns for that model alone.
+
+    An epoch walks the outer batch positions: at position p, ``fit_group(models, rows)`` is called once with the models whose
+    ``batches[i](epoch)`` has a p-th entry and those entries (a model with fewer batches sits the later positions out).  Then every
+    model still running is scored -- ``eval_ref(clf) -> accuracy``, ``eval_val(clf) -> (accuracy, log_loss)`` -- and its own
+    ``EarlyStopping`` decides: best snapshot, patience, stop.  A model that has stopped takes no further part.
+    ``on_epoch_end`` gets ``epoch_loop``'s dict plus ``"config"``, the model's index, once per model and epoch."""
+    clfs = list(clfs)
+    if len(batches) != len(clfs):
+        raise ValueError(f"{len(batches)} batch callables for {len(clfs)} models")
+    states = [EarlyStopping(nbr_epochs, early_stopping_patience) for _ in clfs]
+    live = list(range(len(clfs)))
+    done = object()
+    for epoch in range(int(nbr_epochs)):
+        its = {i: iter(batches[i](epoch)) for i in live}
+        while its:
+            rows = {i: next(it, done) for i, it in its.items()}
+            its = {i: it for i, it in its.items() if rows[i] is not done}
+            if its:
+                fit_group([clfs[i] for i in its], [rows[i] for i in its])
+        for i in live:
+            ref_acc = eval_ref(clfs[i])
+            val_acc, val_loss = eval_val(clfs[i])
+            metrics = states[i].epoch_done(clfs[i], epoch, ref_acc, val_acc, val_loss)
+            if on_epoch_end is not None:
+                metrics["config"] = i
+                on_epoch_end(metrics)
+        live = [i for i in live if not states[i].stopped]
+        if not live:
+            break
+    return [state.result(clf) for state, clf in zip(states, clfs)]
+
+
+def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Sequence[SweepConfig], nbr_epochs: int, *,
+                batch_size: int, early_stopping_patience: Optional[int] = None,
+                on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None
+                ) -> List[Tuple[CalibratedMLP, Dict[str, Any], List[float]]]:
+    """Train, early-stop and calibrate one head per configuration on three resident splits, all heads advancing in the same
+    launches.  -> one ``(calibrated, info, ref_accs)`` per configuration, equal to
+    ``train_classifier(train, ref, val, nbr_epochs, batch_size=batch_size, early_stopping_patience=..., batches=cfg.batches,
+    clf=cfg.classifier(ref.device))`` run alone: parameters, Platt a / b, ``info`` and ``ref_accs``.
+
+    Per epoch: one ``partial_fit_rows_group`` per outer batch position over the models that have a batch there, then
+    ``evaluate`` on ``ref`` and ``val`` per model, then each model's early-stopping decision; a stopped model drops out.  At the
+    end ``calibrate`` per returned classifier.  ``on_epoch_end`` gets ``epoch_loop``'s dict plus ``"config"``."""
+    configs = list(configs)
+    if not configs:
+        raise ValueError("configs is empty")
+    _check_splits(train, ref, val, batch_size)
+    classes = ref.classes.tolist()
+    clfs = [cfg.classifier(ref.device) for cfg in configs]
+    batches = [cfg.batches if cfg.batches is not None else _contiguous_batches(len(train), int(batch_size)) for cfg in configs]
+    ref_accs: Dict[int, List[float]] = {id(c): [] for c in clfs}
+
+    def eval_ref(c):
+        acc = evaluate(c, ref)[0]
+        ref_accs[id(c)].append(acc)
+        return acc
+
+    results = sweep_loop(clfs, batches, lambda group, rows: partial_fit_rows_group(group, train, rows, classes=classes),
+                         eval_ref, lambda c: evaluate(c, val), nbr_epochs, early_stopping_patience=early_stopping_patience,
+                         on_epoch_end=on_epoch_end)
+    return [(calibrate(clf, ref), info, ref_accs[id(live)]) for (clf, info), live in zip(results, clfs)]

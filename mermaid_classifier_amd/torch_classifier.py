@@ -18,7 +18,8 @@ and error strings included): ``__init__`` (:95-136, the argument validation and 
 device), ``_create_trainer``, the device half of ``partial_fit`` (``mmc_trainer_partial_fit_ordered``), ``_forward_probs``'s
 logits call (``mmc_trainer_logits``), ``parameters`` / ``_module`` / ``_adam_state`` (state read back through the C ABI),
 ``__getstate__`` / ``__setstate__`` (the pickle carries host copies of weights and Adam moments), ``_release``,
-``partial_fit_rows`` (``partial_fit`` over rows of a device-resident ``FeatureSet``: ``mmc_trainer_partial_fit_set``).
+``partial_fit_rows`` (``partial_fit`` over rows of a device-resident ``FeatureSet``: ``mmc_trainer_partial_fit_set``) and its
+two halves ``_begin_rows_pass`` / ``_end_pass``, which ``sweep.partial_fit_rows_group`` puts around one grouped call.
 """
 
 from __future__ import annotations
@@ -185,6 +186,18 @@ class TorchMLPClassifier:
         (``mmc_trainer_partial_fit_set``).  The set's label indices are the classifier's, so ``fs.classes`` must equal
         ``classes_`` and ``fs.dim`` ``n_features_in_`` (``ValueError``); on a first call without ``classes`` the set's class list
         is taken (``partial_fit`` would take the labels present in the rows)."""
+        visit, n_samples, batch_size = self._begin_rows_pass(fs, rows, classes)
+        avg = C.c_double(0.0)
+        _lib.check(_lib.lib().mmc_trainer_partial_fit_set(self._h, fs._handle(), None if visit is None else visit.ctypes.data, n_samples,
+                                                          int(batch_size), C.byref(avg), _current_stream_ptr(_device_index(self.device))))
+        self._end_pass(avg.value)
+        return self
+
+    def _begin_rows_pass(self, fs, rows, classes):
+        """The host half of a pass over rows of ``fs``, before any device work on the pass: argument checks, first-call
+        initialisation, mini-batch size and shuffle.  -> ``(visit, n, batch_size)``: the visiting order as contiguous int64 row
+        indices of the set, or None for every row in stored order.  (``sweep.partial_fit_rows_group`` runs this per classifier
+        and hands the results to one grouped call.)"""
         if rows is None:
             n_samples = len(fs)
             rows_arr = None
@@ -217,12 +230,11 @@ class TorchMLPClassifier:
             visit = None
         else:
             visit = np.ascontiguousarray((order if rows_arr is None else rows_arr[order]).astype(np.int64))
-        avg = C.c_double(0.0)
-        _lib.check(_lib.lib().mmc_trainer_partial_fit_set(self._h, fs._handle(), None if visit is None else visit.ctypes.data, n_samples,
-                                                          int(batch_size), C.byref(avg), _current_stream_ptr(_device_index(self.device))))
-        self.loss_curve_.append(float(avg.value))
+        return visit, n_samples, batch_size
+
+    def _end_pass(self, avg: float) -> None:
+        self.loss_curve_.append(float(avg))
         self.n_iter_ += 1
-        return self
 
     def fit(self, X, y) -> "TorchMLPClassifier":
         y_arr = np.asarray(y)

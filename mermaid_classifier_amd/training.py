@@ -22,7 +22,57 @@ from .featureset import FeatureSet
 from .torch_classifier import TorchMLPClassifier
 from .validation import previous_accuracies, validate
 
-__all__ = ["epoch_loop", "train_classifier", "train_and_validate"]
+__all__ = ["EarlyStopping", "epoch_loop", "train_classifier", "train_and_validate"]
+
+
+class EarlyStopping:
+    """``epoch_loop``'s bookkeeping for one model: best validation loss so far with its epoch and ``copy.deepcopy`` snapshot,
+    epochs since the last improvement, and what the callback dict and the stop summary are made of.  ``epoch_loop`` keeps one,
+    ``sweep.sweep_loop`` one per model of the sweep."""
+
+    def __init__(self, nbr_epochs: int, patience: Optional[int] = None):
+        if int(nbr_epochs) < 1:
+            raise ValueError(f"nbr_epochs must be >= 1, got {nbr_epochs!r}")
+        if patience is not None and patience < 1:
+            raise ValueError(f"early_stopping_patience must be >= 1 or None, got {patience!r}")
+        self.nbr_epochs, self.patience = nbr_epochs, patience
+        self.best_loss, self.best_epoch, self.best_clf = float("inf"), None, None
+        self.since_best = 0
+        self.epoch = 0            # the last epoch run (0-based)
+        self.stopped = False      # out of patience
+        self.t0 = time.time()
+
+    def epoch_done(self, clf, epoch: int, ref_acc: float, val_acc: float, val_loss: float) -> Dict[str, Any]:
+        """Record epoch ``epoch`` of ``clf`` (snapshot it when it is the best so far).  -> the epoch's callback dict; ``stopped``
+        says whether the patience has run out."""
+        self.epoch = epoch
+        if self.patience is not None:
+            if val_loss < self.best_loss:
+                self.best_loss, self.best_epoch, self.best_clf = val_loss, epoch, copy.deepcopy(clf)
+                self.since_best = 0
+            else:
+                self.since_best += 1
+        self.stopped = self.patience is not None and self.since_best >= self.patience
+        curve = getattr(clf, "loss_curve_", [None])
+        metrics: Dict[str, Any] = {"epoch": epoch, "ref_accuracy": ref_acc, "val_accuracy": val_acc, "val_loss": val_loss,
+                                   "training_loss": curve[-1] if curve else None, "cumulative_seconds": time.time() - self.t0}
+        if self.stopped or epoch == self.nbr_epochs - 1:
+            metrics["final_epoch"] = epoch + 1
+            metrics["early_stopped"] = self.stopped
+            if self.best_epoch is not None:
+                metrics["best_val_epoch"] = self.best_epoch + 1
+                metrics["best_val_loss"] = self.best_loss
+        return metrics
+
+    def result(self, clf) -> Tuple[Any, Dict[str, Any]]:
+        """-> ``(clf, info)`` after the last epoch run: the best snapshot when the best epoch is not the last one."""
+        if self.best_clf is not None and self.best_epoch != self.epoch:
+            clf = self.best_clf
+        info = {"enabled": self.patience is not None, "patience": self.patience,
+                "stop_reason": "early_stopping" if self.stopped else "budget_exhausted", "final_epoch": self.epoch + 1,
+                "best_val_epoch": None if self.best_epoch is None else self.best_epoch + 1,
+                "best_val_loss": None if self.best_epoch is None else self.best_loss}
+        return clf, info
 
 
 def epoch_loop(clf, train_epoch: Callable[[Any, int], None], eval_ref: Callable[[Any], float],
@@ -42,47 +92,17 @@ def epoch_loop(clf, train_epoch: Callable[[Any, int], None], eval_ref: Callable[
 
     ``info``: ``enabled``, ``patience``, ``stop_reason`` ("early_stopping" or "budget_exhausted"), ``final_epoch``,
     ``best_val_epoch``, ``best_val_loss`` (None without a best epoch) -- the reference's ``_early_stop_info``."""
-    if int(nbr_epochs) < 1:
-        raise ValueError(f"nbr_epochs must be >= 1, got {nbr_epochs!r}")
-    patience = early_stopping_patience
-    if patience is not None and patience < 1:
-        raise ValueError(f"early_stopping_patience must be >= 1 or None, got {patience!r}")
-    best_loss, best_epoch, best_clf = float("inf"), None, None
-    since_best = 0
-    stop_reason = "budget_exhausted"
-    t0 = time.time()
-    epoch = 0
+    state = EarlyStopping(nbr_epochs, early_stopping_patience)
     for epoch in range(int(nbr_epochs)):
         train_epoch(clf, epoch)
         ref_acc = eval_ref(clf)
         val_acc, val_loss = eval_val(clf)
-        if patience is not None:
-            if val_loss < best_loss:
-                best_loss, best_epoch, best_clf = val_loss, epoch, copy.deepcopy(clf)
-                since_best = 0
-            else:
-                since_best += 1
-        out_of_patience = patience is not None and since_best >= patience
+        metrics = state.epoch_done(clf, epoch, ref_acc, val_acc, val_loss)
         if on_epoch_end is not None:
-            curve = getattr(clf, "loss_curve_", [None])
-            metrics: Dict[str, Any] = {"epoch": epoch, "ref_accuracy": ref_acc, "val_accuracy": val_acc, "val_loss": val_loss,
-                                       "training_loss": curve[-1] if curve else None, "cumulative_seconds": time.time() - t0}
-            if out_of_patience or epoch == nbr_epochs - 1:
-                metrics["final_epoch"] = epoch + 1
-                metrics["early_stopped"] = out_of_patience
-                if best_epoch is not None:
-                    metrics["best_val_epoch"] = best_epoch + 1
-                    metrics["best_val_loss"] = best_loss
             on_epoch_end(metrics)
-        if out_of_patience:
-            stop_reason = "early_stopping"
+        if state.stopped:
             break
-    if best_clf is not None and best_epoch != epoch:
-        clf = best_clf
-    info = {"enabled": patience is not None, "patience": patience, "stop_reason": stop_reason, "final_epoch": epoch + 1,
-            "best_val_epoch": None if best_epoch is None else best_epoch + 1,
-            "best_val_loss": None if best_epoch is None else best_loss}
-    return clf, info
+    return state.result(clf)
 
 
 def _contiguous_batches(n_rows: int, batch_size: int) -> Callable[[int], Iterable[np.ndarray]]:
@@ -90,6 +110,18 @@ def _contiguous_batches(n_rows: int, batch_size: int) -> Callable[[int], Iterabl
         for start in range(0, n_rows, batch_size):
             yield np.arange(start, min(start + batch_size, n_rows), dtype=np.int64)
     return batches
+
+
+def _check_splits(train, ref, val, batch_size) -> None:
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size!r}")
+    for name, fs in (("train", train), ("ref", ref), ("val", val)):
+        if not isinstance(fs, FeatureSet):
+            raise ValueError(f"{name} must be a FeatureSet, got {type(fs).__name__}")
+        if not np.array_equal(fs.classes, ref.classes) or fs.dim != ref.dim:
+            raise ValueError(f"the {name} set's classes / width differ from the ref set's")
+        if len(fs) < 1:
+            raise ValueError(f"the {name} set is empty")
 
 
 def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_epochs: int, *, batch_size: int,
@@ -110,15 +142,7 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
     slices of ``batch_size`` rows in stored order, the same every epoch.  pyspacer's shuffle of the images behind that loader is
     not reproduced here; ``batches`` is the hook for it (any callable ``epoch -> iterable of row-index arrays``).  Within a batch
     the classifier shuffles as ``partial_fit`` does."""
-    if int(batch_size) < 1:
-        raise ValueError(f"batch_size must be >= 1, got {batch_size!r}")
-    for name, fs in (("train", train), ("ref", ref), ("val", val)):
-        if not isinstance(fs, FeatureSet):
-            raise ValueError(f"{name} must be a FeatureSet, got {type(fs).__name__}")
-        if not np.array_equal(fs.classes, ref.classes) or fs.dim != ref.dim:
-            raise ValueError(f"the {name} set's classes / width differ from the ref set's")
-        if len(fs) < 1:
-            raise ValueError(f"the {name} set is empty")
+    _check_splits(train, ref, val, batch_size)
     if clf is None:
         clf = TorchMLPClassifier(hidden_layer_sizes=(500, 300, 100), learning_rate_init=1e-4, class_weight=class_weight,
                                  random_state=0, device=ref.device)
