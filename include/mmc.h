@@ -305,6 +305,28 @@ int mmc_trainer_evaluate_set_q32(mmc_trainer* t, mmc_featureset* fs, int64_t fir
 /* mmc_calibrator_add_features (trainer.py:344-396) on rows [first, first+n) of the set: same probabilities, labels copied device to
  * device, one synchronisation. */
 int mmc_calibrator_add_set(mmc_calibrator* c, mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n, void* hip_stream);
+/* Class-wise evaluation of the uncalibrated classifier: mmc_trainer_evaluate_q32 / mmc_trainer_evaluate_set_q32 that also keep each
+ * row's (true class, prediction) pair, as a K x K table of int64 counts.
+ * Replaces: per epoch, the confusion-matrix groups of MetricsCoordinator -- compute_precision_recall_f1 and
+ *   compute_balanced_accuracy_mcc (mermaid_classifier/pyspacer/metrics/classification.py:171-302) -- which the reference runs once,
+ *   after training, on the host.  The balancing study ranks configurations by balanced_accuracy and f1_macro
+ *   (docs/research/balancing-experiments.md:17-19, 43) and finds them moving apart from accuracy over the epochs (:67, 82;
+ *   hidden-layer-experiments.md:20-28); with the table per epoch the Python side (metrics.ClassScores) computes them every epoch.
+ * confusion[g * K + est] = the rows with true class g whose prediction is est: the argmax of the renormalised probabilities, first
+ *   index on ties (numpy.argmax) -- the argmax *n_correct is counted from.  Exact integers (64-bit integer atomics on the device):
+ *   the table does not depend on row order, chunking or how the rows are split over calls, and the caller adds the tables of
+ *   several calls.  Its trace is *n_correct and row g sums to the number of labels g.  (A row whose probabilities are all NaN has no
+ *   argmax: it counts as wrong and enters no cell.)
+ * *n_correct and *sum_log_loss_q32 carry the bits of mmc_trainer_evaluate_q32 / mmc_trainer_evaluate_set_q32 on the same rows; the
+ *   arguments, checks and row limits are theirs, and confusion == NULL is MMC_ERR_ARG as well.  The device table lives in the
+ *   trainer's scratch (grown on demand, freed with the handle); it is zeroed on the stream at the start of a call and accumulated
+ *   over the call's chunks.  The _set form makes one device-to-host copy (totals and table) and one synchronisation per call; the
+ *   host-fed form one synchronisation per 16 384-row chunk, as mmc_trainer_evaluate_q32.
+ * A rejected call launches nothing and zeroes *n_correct, *sum_log_loss_q32 (when not NULL) and, when `t` is not NULL, the table. */
+int mmc_trainer_evaluate_classes(mmc_trainer* t, const float* X, const int32_t* y, int64_t n, int64_t* n_correct,
+                                 int64_t* sum_log_loss_q32, int64_t* confusion /* K*K */, void* hip_stream);
+int mmc_trainer_evaluate_classes_set(mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n, int64_t* n_correct,
+                                     int64_t* sum_log_loss_q32, int64_t* confusion /* K*K */, void* hip_stream);
 
 /* ---- validation of a calibrated head --------------------------------------------------------------------------------
  * Replaces: what MermaidTrainer.__call__ computes after the calibration (mermaid_classifier/pyspacer/trainer.py:267-293:

@@ -7,10 +7,12 @@ from .extractor import EfficientNetExtractor, build_extractor_class, resolve_dev
 from .inference import ManifestError, Predictor, load_predictor, SCHEMA_VERSION, TASK_NAME  # noqa: F401
 from .backbone import Backbone, crop_patches_device, FEATURE_DIM  # noqa: F401
 from .classify import PointClassifier, PointPredictions  # noqa: F401
-from .calibration import CalibratedMLP, ParityError, calibrate, evaluate, export_artifact  # noqa: F401
+from .calibration import CalibratedMLP, ParityError, calibrate, evaluate, evaluate_classes, export_artifact  # noqa: F401
+from .class_scores import ClassScores  # noqa: F401
 from .featureset import FeatureSet  # noqa: F401
 from .training import epoch_loop, train_and_validate, train_classifier  # noqa: F401
-from .sweep import SweepConfig, partial_fit_rows_group, sweep_loop, train_sweep  # noqa: F401
+from .sweep import SweepConfig, partial_fit_rows_group, rank_sweep, sweep_loop, train_sweep  # noqa: F401
+from .sampling import class_counts, effective_number_weights, row_batches, subsample_rows, subsample_targets  # noqa: F401
 from .validation import Validation, previous_accuracies, validate  # noqa: F401
 from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, grouped_validate  # noqa: F401
 from .ranking import RankedValidation, ranking_validate, similarity_levels  # noqa: F401
@@ -22,7 +24,9 @@ __all__ = [
     "PointClassifier", "PointPredictions",
     "CalibratedMLP", "ParityError", "calibrate", "evaluate", "export_artifact",
     "FeatureSet", "epoch_loop", "train_classifier", "train_and_validate",
-    "SweepConfig", "partial_fit_rows_group", "sweep_loop", "train_sweep",
+    "SweepConfig", "partial_fit_rows_group", "sweep_loop", "train_sweep", "rank_sweep",
+    "evaluate_classes", "ClassScores",
+    "class_counts", "effective_number_weights", "subsample_targets", "subsample_rows", "row_batches",
     "Validation", "validate", "previous_accuracies",
     "grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability",
     "ranking_validate", "RankedValidation", "similarity_levels",

@@ -33,6 +33,7 @@ SYMBOLS = [
     "mmc_calibrator_create", "mmc_calibrator_destroy", "mmc_calibrator_add_features", "mmc_calibrator_add_scores", "mmc_calibrator_fit",
     "mmc_featureset_create", "mmc_featureset_destroy", "mmc_featureset_rows", "mmc_featureset_dim", "mmc_featureset_append", "mmc_featureset_read",
     "mmc_trainer_partial_fit_set", "mmc_trainer_group_partial_fit_set", "mmc_trainer_evaluate_set_q32", "mmc_calibrator_add_set",
+    "mmc_trainer_evaluate_classes", "mmc_trainer_evaluate_classes_set",
     "mmc_head_evaluate", "mmc_head_evaluate_set", "mmc_head_evaluate_grouped", "mmc_head_evaluate_grouped_set",
     "mmc_head_evaluate_ranked", "mmc_head_evaluate_ranked_set",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
@@ -155,6 +156,10 @@ def _load() -> C.CDLL:
     lib.mmc_trainer_evaluate_set_q32.argtypes = [vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64), vp]
     lib.mmc_calibrator_add_set.restype = i32
     lib.mmc_calibrator_add_set.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.mmc_trainer_evaluate_classes.restype = i32
+    lib.mmc_trainer_evaluate_classes.argtypes = [vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), vp, vp]
+    lib.mmc_trainer_evaluate_classes_set.restype = i32
+    lib.mmc_trainer_evaluate_classes_set.argtypes = [vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64), vp, vp]
     lib.mmc_head_evaluate.restype = i32
     lib.mmc_head_evaluate.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, u32, vp]
     lib.mmc_head_evaluate_set.restype = i32

@@ -8,6 +8,8 @@ reference                                              here
 =====================================================  ===================================================================
 ``_calc_acc_batched`` (:295-307)                       ``evaluate(clf, data)[0]``
 ``_calc_acc_and_log_loss_batched`` (:309-342)          ``evaluate(clf, data)``
+the same, plus the confusion-matrix scores of          ``evaluate_classes(clf, data)`` -> accuracy, log-loss and
+``metrics/classification.py:171-302`` per epoch        ``ClassScores``
 ``_calibrate_in_batches`` (:344-396)                   ``calibrate(clf, data)`` -> ``CalibratedMLP`` (``.to_sklearn()`` gives
                                                        the ``CalibratedClassifierCV`` the reference returns)
 ``inference/export.py:24-94`` ``export_artifact``      ``export_artifact(calibrated, output_dir, reference_features)``
@@ -34,10 +36,11 @@ import numpy as np
 
 from . import _lib
 from .backbone import _current_stream_ptr, _device_index
+from .class_scores import ClassScores
 from .featureset import FeatureSet
 from .inference import SCHEMA_VERSION, TASK_NAME, DeviceHead, HeadParams, Predictor
 
-__all__ = ["evaluate", "calibrate", "CalibratedMLP", "export_artifact", "build_head_module", "ParityError"]
+__all__ = ["evaluate", "evaluate_classes", "calibrate", "CalibratedMLP", "export_artifact", "build_head_module", "ParityError"]
 
 
 class ParityError(Exception):
@@ -99,6 +102,41 @@ def evaluate(clf, data) -> Tuple[float, float]:
     if n == 0:
         raise ValueError("evaluate: no rows")
     return correct / n, loss_q32 / (n << 32)   # int / int: one correctly rounded division
+
+
+def evaluate_classes(clf, data) -> Tuple[float, float, ClassScores]:
+    """-> (accuracy, log_loss, ``ClassScores``): ``evaluate(clf, data)`` -- the same two floats, from the same integers -- plus the
+    K x K table of (true class, argmax) counts of the same pass (``mmc_trainer_evaluate_classes``, ``_set`` for a
+    ``FeatureSet``), wrapped as ``ClassScores``: balanced accuracy, macro precision / recall / f1 and MCC of the uncalibrated
+    classifier, which the reference computes once after training (metrics/classification.py:171-302) and a sweep wants per epoch.
+    The tables of the batches are added as integers."""
+    _require_fitted(clf)
+    lib = _lib.lib()
+    st = _current_stream_ptr(_device_index(clf.device))
+    K = len(clf.classes_)
+    n = correct = loss_q32 = 0
+    table = np.zeros((K, K), np.int64)
+    part = np.zeros((K, K), np.int64)
+    if isinstance(data, FeatureSet):
+        data._check_against(clf)
+        n = len(data)
+        if n:
+            nc, q = C.c_int64(0), C.c_int64(0)
+            _lib.check(lib.mmc_trainer_evaluate_classes_set(clf._h, data._handle(), 0, n, C.byref(nc), C.byref(q), table.ctypes.data, st))
+            correct, loss_q32 = int(nc.value), int(q.value)
+        data = ()   # nothing left to stream
+    for x, y in _batches(data):
+        X, yi = _batch_arrays(clf, x, y)
+        nc, q = C.c_int64(0), C.c_int64(0)
+        _lib.check(lib.mmc_trainer_evaluate_classes(clf._h, X.ctypes.data, yi.ctypes.data, X.shape[0], C.byref(nc), C.byref(q),
+                                                    part.ctypes.data, st))
+        n += X.shape[0]
+        correct += int(nc.value)
+        loss_q32 += int(q.value)
+        table += part
+    if n == 0:
+        raise ValueError("evaluate_classes: no rows")
+    return correct / n, loss_q32 / (n << 32), ClassScores(table, clf.classes_)
 
 
 class _Calibrator:

@@ -5,6 +5,9 @@
 //                              argmax == y count and sum of sklearn.metrics.log_loss's per-row term
 //   mmc_calibrator_*           _calibrate_in_batches (trainer.py:344-396) -> sklearn.calibration._fit_calibrator(.., "sigmoid"):
 //                              one Platt sigmoid per class, all classes fitted at once
+//   mmc_trainer_evaluate_classes(_set)   the same evaluation that also keeps the K x K table of (true class, argmax) counts: what
+//                              compute_precision_recall_f1 / compute_balanced_accuracy_mcc (metrics/classification.py:171-302) are
+//                              functions of, per epoch
 //
 // Probability store.  add_features runs the trainer's own forward (trainer_forward: the tgemm kernels of a training step) and
 // softmax_store_kernel writes the probabilities of _forward_probs (torch_classifier.py here: fp32 max-subtract, exp, sum, divide,
@@ -24,7 +27,8 @@
 //                        system (1e-12 ridge on the diagonal) for the next trial point; then compact the active list.
 // The host reads one pinned "classes still active" counter per iteration.  At most 100 trial evaluations per class.
 //
-// Every reduction runs in a fixed order (no atomics), so a run is bit-reproducible; the fit's row chunks depend only on N, so
+// Every floating-point reduction runs in a fixed order (the only atomics are the integer adds of the class-wise table, which are
+// exact in any order), so a run is bit-reproducible; the fit's row chunks depend only on N, so
 // the same rows added in any number of calls give the same a / b bits.  mmc_trainer_evaluate sums the per-row log-loss as
 // 2^-32 fixed point in int64 (exact and order-free); mmc_trainer_evaluate_q32 returns that integer, so sums over any split of
 // the rows into calls are the same integer.
@@ -141,8 +145,13 @@ __global__ __launch_bounds__(256) void scores_store_kernel(const double* __restr
 
 // One wave per row: argmax of the renormalised probabilities (first index on ties, as np.argmax) == y, and
 // -log(clip(p_y, DBL_EPSILON, 1 - DBL_EPSILON)) as 2^-32 fixed point.  slab[2 b] = correct rows, slab[2 b + 1] = loss of workgroup b.
+// CONF (mmc_trainer_evaluate_classes*): the row's (true class, argmax) pair is kept as well -- lane 0 adds 1 to
+// confusion[y * K + argmax], a 64-bit integer atomic on device memory, so the table is exact and order-free.  One atomic per row
+// next to a forward of dims[0] x hidden MACs per row; no per-workgroup pre-aggregation (profiles/class_eval.txt).  A row whose
+// probabilities are all NaN has no argmax (arg stays K) and enters no cell.
+template <bool CONF>
 __global__ __launch_bounds__(256) void eval_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
-                                                        long long* __restrict__ slab)
+                                                        long long* __restrict__ slab, unsigned long long* __restrict__ confusion)
 {
     __shared__ long long red[4][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -167,6 +176,7 @@ __global__ __launch_bounds__(256) void eval_rows_kernel(const float* __restrict_
         const double py = fmin(fmax(row_prob(z, yi, r), DBL_EPSILON), 1.0 - DBL_EPSILON);
         correct = arg == yi;
         q = llrint(-log(py) * kLossFix);
+        if (CONF && lane == 0 && arg < K) atomicAdd(&confusion[(size_t)yi * K + arg], 1ull);
     }
     if (lane == 0) { red[wave][0] = correct; red[wave][1] = q; }
     __syncthreads();
@@ -643,7 +653,7 @@ static int trainer_evaluate(mmc_trainer* t, const float* X, const int32_t* y, in
         r = trainer_forward(t, X + (size_t)off * d0, cur, st, &z);
         if (r) return r;
         C_TRY(hipMemcpyAsync(dy, y + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(eval_rows_kernel, dim3(nb), dim3(256), 0, st, z, dy, cur, K, slab);
+        hipLaunchKernelGGL(eval_rows_kernel<false>, dim3(nb), dim3(256), 0, st, z, dy, cur, K, slab, (unsigned long long*)nullptr);
         hipLaunchKernelGGL(eval_finalize_kernel<false>, dim3(1), dim3(256), 0, st, slab, nb, totals);
         C_TRY(hipGetLastError());
         C_TRY(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
@@ -706,7 +716,8 @@ extern "C" int mmc_trainer_evaluate_set_q32(mmc_trainer* t, mmc_featureset* fs, 
         const float* z = nullptr;
         r = trainer_forward_device(t, fs->X + (size_t)(first + off) * fs->dim, cur, st, &z);
         if (r) return r;
-        hipLaunchKernelGGL(eval_rows_kernel, dim3(nb), dim3(256), 0, st, z, fs->y + first + off, cur, K, slab);
+        hipLaunchKernelGGL(eval_rows_kernel<false>, dim3(nb), dim3(256), 0, st, z, fs->y + first + off, cur, K, slab,
+                           (unsigned long long*)nullptr);
         hipLaunchKernelGGL(eval_finalize_kernel<true>, dim3(1), dim3(256), 0, st, slab, nb, totals);
         C_TRY(hipGetLastError());
     }
@@ -716,4 +727,89 @@ extern "C" int mmc_trainer_evaluate_set_q32(mmc_trainer* t, mmc_featureset* fs, 
     *n_correct = h[0];
     *sum_log_loss_q32 = h[1];
     return MMC_OK;
+}
+
+// The class-wise form of the two evaluations above.  Scratch: slab [max_nb][2] int64, the two totals, the K x K table (totals and
+// table are contiguous: one copy brings both back), then -- host-fed only -- the chunk's labels.  Totals and table are zeroed on
+// the stream, every chunk adds to them on the device (eval_finalize_kernel<ACC>, the kernel's atomics), and the host reads them
+// once after the last chunk.  Integer adds: the totals are those of the calls above on the same rows.
+static int trainer_evaluate_classes(mmc_trainer* t, const float* X, const int32_t* y, mmc_featureset* fs, bool from_set, int64_t first,
+                                    int64_t n, int64_t* n_correct, int64_t* sum_q32, int64_t* confusion, void* hip_stream)
+{
+    if (n_correct) *n_correct = 0;
+    if (sum_q32) *sum_q32 = 0;
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    const int K = trainer_classes(t);
+    const size_t cells = (size_t)K * K;
+    if (confusion) for (size_t i = 0; i < cells; ++i) confusion[i] = 0;
+    if (!n_correct || !sum_q32) return mmc_fail(MMC_ERR_ARG, "n_correct/sum_log_loss is NULL");
+    if (!confusion) return mmc_fail(MMC_ERR_ARG, "confusion is NULL");
+    int r;
+    if (from_set) {
+        if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
+        r = check_set_matches(fs, t);
+        if (r) return r;
+        r = check_set_range(fs, first, n);
+        if (r) return r;
+        if (n > MMC_EVALUATE_SET_MAX_ROWS)
+            return mmc_fail(MMC_ERR_ARG, "n = %lld rows in one call: split it (at most %lld)", (long long)n, (long long)MMC_EVALUATE_SET_MAX_ROWS);
+    } else {
+        if (n < 0) return mmc_fail(MMC_ERR_ARG, "n = %lld is negative", (long long)n);
+        if (n > ((int64_t)1 << 25)) return mmc_fail(MMC_ERR_ARG, "n = %lld rows in one call: split it (at most 2^25)", (long long)n);
+    }
+    if (n == 0) return MMC_OK;
+    if (!from_set) {
+        if (!X || !y) return mmc_fail(MMC_ERR_ARG, "X/y is NULL");
+        r = check_labels(y, n, K);
+        if (r) return r;
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    C_TRY(hipSetDevice(trainer_device(t)));
+    const int max_nb = (kTrainerForwardRows + 3) / 4;
+    void* scratch = nullptr;
+    r = trainer_scratch(t, ((size_t)max_nb * 2 + 2 + cells) * 8 + (from_set ? 0 : (size_t)kTrainerForwardRows * 4), &scratch);
+    if (r) return r;
+    long long* slab = static_cast<long long*>(scratch);
+    long long* totals = slab + 2 * max_nb;
+    unsigned long long* table = reinterpret_cast<unsigned long long*>(totals + 2);
+    int32_t* dy = reinterpret_cast<int32_t*>(table + cells);   // (host-fed only)
+    const int d0 = trainer_input_dim(t);
+    C_TRY(hipMemsetAsync(totals, 0, (2 + cells) * 8, st));
+    for (int64_t off = 0; off < n; off += kTrainerForwardRows) {
+        const int cur = (int)((n - off) < kTrainerForwardRows ? (n - off) : kTrainerForwardRows);
+        const int nb = (cur + 3) / 4;
+        const float* z = nullptr;
+        const int32_t* labels = dy;
+        if (from_set) {
+            r = trainer_forward_device(t, fs->X + (size_t)(first + off) * fs->dim, cur, st, &z);
+            labels = fs->y + first + off;
+        } else {
+            if (off) C_TRY(hipStreamSynchronize(st));   // the previous chunk has read the labels this one overwrites
+            r = trainer_forward(t, X + (size_t)off * d0, cur, st, &z);
+        }
+        if (r) return r;
+        if (!from_set) C_TRY(hipMemcpyAsync(dy, y + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(eval_rows_kernel<true>, dim3(nb), dim3(256), 0, st, z, labels, cur, K, slab, table);
+        hipLaunchKernelGGL(eval_finalize_kernel<true>, dim3(1), dim3(256), 0, st, slab, nb, totals);
+        C_TRY(hipGetLastError());
+    }
+    std::vector<long long> h(2 + cells, 0);
+    C_TRY(hipMemcpyAsync(h.data(), totals, (2 + cells) * 8, hipMemcpyDeviceToHost, st));
+    C_TRY(hipStreamSynchronize(st));
+    *n_correct = h[0];
+    *sum_q32 = h[1];
+    for (size_t i = 0; i < cells; ++i) confusion[i] = h[2 + i];
+    return MMC_OK;
+}
+
+extern "C" int mmc_trainer_evaluate_classes(mmc_trainer* t, const float* X, const int32_t* y, int64_t n, int64_t* n_correct,
+                                            int64_t* sum_log_loss_q32, int64_t* confusion, void* hip_stream)
+{
+    return trainer_evaluate_classes(t, X, y, nullptr, false, 0, n, n_correct, sum_log_loss_q32, confusion, hip_stream);
+}
+
+extern "C" int mmc_trainer_evaluate_classes_set(mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n, int64_t* n_correct,
+                                                int64_t* sum_log_loss_q32, int64_t* confusion, void* hip_stream)
+{
+    return trainer_evaluate_classes(t, nullptr, nullptr, fs, true, first, n, n_correct, sum_log_loss_q32, confusion, hip_stream);
 }

@@ -14,8 +14,15 @@ the worst way to spend it.  Here the S models advance together:
 ``train_sweep``             ``training.train_classifier`` for every configuration, in lockstep: entry i of the result is what
                             ``train_classifier`` returns for configuration i run alone.
 
-Evaluation and calibration stay per model (``calibration.evaluate`` / ``calibrate``): they are forward-only at 16 384 rows a
-chunk and fill the device on their own.
+``rank_sweep``              the study's promotion rule over ``train_sweep``'s result: every calibrated model scored on the validation
+                            split (``validate`` / ``grouped_validate``), sorted by balanced accuracy, then macro f1.
+
+What a balancing configuration is made of comes from ``sampling.py``: ``effective_number_weights`` -> ``SweepConfig.class_weight``,
+``subsample_targets`` / ``subsample_rows`` / ``row_batches`` -> ``SweepConfig.batches``.  With ``class_scores=True`` every epoch's
+callback dict carries the validation balanced accuracy and macro f1 next to the accuracy (``calibration.evaluate_classes``).
+
+Evaluation and calibration stay per model (``calibration.evaluate`` / ``evaluate_classes`` / ``calibrate``): they are forward-only
+at 16 384 rows a chunk and fill the device on their own.
 """
 
 from __future__ import annotations
@@ -28,12 +35,14 @@ import numpy as np
 
 from . import _lib
 from .backbone import _current_stream_ptr, _device_index
-from .calibration import CalibratedMLP, calibrate, evaluate
+from .calibration import CalibratedMLP, calibrate, evaluate, evaluate_classes
 from .featureset import FeatureSet
+from .metrics import grouped_validate
 from .torch_classifier import TorchMLPClassifier
-from .training import EarlyStopping, _check_splits, _contiguous_batches
+from .training import EarlyStopping, _check_splits, _contiguous_batches, _val_entries
+from .validation import validate
 
-__all__ = ["SweepConfig", "partial_fit_rows_group", "sweep_loop", "train_sweep"]
+__all__ = ["SweepConfig", "partial_fit_rows_group", "sweep_loop", "train_sweep", "rank_sweep"]
 
 
 def _rows_per_classifier(rows, count: int) -> List[Any]:
@@ -121,7 +130,8 @@ class SweepConfig:
 def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[Any]]],
                fit_group: Callable[[List[Any], List[Any]], None], eval_ref: Callable[[Any], float],
                eval_val: Callable[[Any], Tuple[float, float]], nbr_epochs: int, early_stopping_patience: Optional[int] = None,
-               on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None) -> List[Tuple[Any, Dict[str, Any]]]:
+               on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None, class_scores: bool = False
+               ) -> List[Tuple[Any, Dict[str, Any]]]:
     """``training.epoch_loop`` for the models ``clfs`` in lockstep.  -> one ``(clf, info)`` per model, each what ``epoch_loop``
     returns for that model alone.
 
@@ -129,7 +139,9 @@ def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[A
     ``batches[i](epoch)`` has a p-th entry and those entries (a model with fewer batches sits the later positions out).  Then every
     model still running is scored -- ``eval_ref(clf) -> accuracy``, ``eval_val(clf) -> (accuracy, log_loss)`` -- and its own
     ``EarlyStopping`` decides: best snapshot, patience, stop.  A model that has stopped takes no further part.
-    ``on_epoch_end`` gets ``epoch_loop``'s dict plus ``"config"``, the model's index, once per model and epoch."""
+    ``on_epoch_end`` gets ``epoch_loop``'s dict plus ``"config"``, the model's index, once per model and epoch.  With
+    ``class_scores=True``, ``eval_val(clf)`` returns ``(accuracy, log_loss, ClassScores)`` and the dict gains
+    ``val_balanced_accuracy`` and ``val_f1_macro``, as in ``epoch_loop``; the decisions still read ``val_loss`` alone."""
     clfs = list(clfs)
     if len(batches) != len(clfs):
         raise ValueError(f"{len(batches)} batch callables for {len(clfs)} models")
@@ -145,8 +157,8 @@ def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[A
                 fit_group([clfs[i] for i in its], [rows[i] for i in its])
         for i in live:
             ref_acc = eval_ref(clfs[i])
-            val_acc, val_loss = eval_val(clfs[i])
-            metrics = states[i].epoch_done(clfs[i], epoch, ref_acc, val_acc, val_loss)
+            val_acc, val_loss, extra = _val_entries(eval_val(clfs[i]), class_scores)
+            metrics = states[i].epoch_done(clfs[i], epoch, ref_acc, val_acc, val_loss, extra=extra)
             if on_epoch_end is not None:
                 metrics["config"] = i
                 on_epoch_end(metrics)
@@ -158,7 +170,7 @@ def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[A
 
 def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Sequence[SweepConfig], nbr_epochs: int, *,
                 batch_size: int, early_stopping_patience: Optional[int] = None,
-                on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None
+                on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None, class_scores: bool = False
                 ) -> List[Tuple[CalibratedMLP, Dict[str, Any], List[float]]]:
     """Train, early-stop and calibrate one head per configuration on three resident splits, all heads advancing in the same
     launches.  -> one ``(calibrated, info, ref_accs)`` per configuration, equal to
@@ -167,7 +179,9 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
 
     Per epoch: one ``partial_fit_rows_group`` per outer batch position over the models that have a batch there, then
     ``evaluate`` on ``ref`` and ``val`` per model, then each model's early-stopping decision; a stopped model drops out.  At the
-    end ``calibrate`` per returned classifier.  ``on_epoch_end`` gets ``epoch_loop``'s dict plus ``"config"``."""
+    end ``calibrate`` per returned classifier.  ``on_epoch_end`` gets ``epoch_loop``'s dict plus ``"config"``.
+    ``class_scores=True`` scores ``val`` through ``calibration.evaluate_classes``: the dict gains ``val_balanced_accuracy`` and
+    ``val_f1_macro`` per model and epoch, and nothing returned changes."""
     configs = list(configs)
     if not configs:
         raise ValueError("configs is empty")
@@ -182,7 +196,40 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
         ref_accs[id(c)].append(acc)
         return acc
 
+    eval_val = evaluate_classes if class_scores else evaluate
     results = sweep_loop(clfs, batches, lambda group, rows: partial_fit_rows_group(group, train, rows, classes=classes),
-                         eval_ref, lambda c: evaluate(c, val), nbr_epochs, early_stopping_patience=early_stopping_patience,
-                         on_epoch_end=on_epoch_end)
+                         eval_ref, lambda c: eval_val(c, val), nbr_epochs, early_stopping_patience=early_stopping_patience,
+                         on_epoch_end=on_epoch_end, class_scores=class_scores)
     return [(calibrate(clf, ref), info, ref_accs[id(live)]) for (clf, info), live in zip(results, clfs)]
+
+
+def rank_sweep(results: Sequence[Tuple[CalibratedMLP, Dict[str, Any], Any]], val, *, image_sizes=None,
+               n_bins: int = 20) -> List[Dict[str, Any]]:
+    """Rank the configurations of a sweep the way the balancing study promotes them (docs/research/balancing-experiments.md:43):
+    by ``balanced_accuracy`` descending, ties by ``f1_macro`` descending, then by configuration index.
+
+    ``results`` is what ``train_sweep`` returned (or any sequence of ``(calibrated, info, ...)``); every calibrated model is scored
+    on ``val`` on the device, totals only -- ``validate(model, val, rows=False)``, or ``grouped_validate(model, val, image_sizes,
+    n_bins=n_bins)`` when ``image_sizes`` is given.  -> one dict per configuration, best first: ``config`` (its index in
+    ``results``), ``balanced_accuracy``, ``f1_macro``, ``mcc`` (``Validation.class_scores()``), ``accuracy``, ``log_loss`` (the
+    ``Validation``'s), ``best_val_epoch`` and ``final_epoch`` (from ``info``; the screen-versus-confirmation caveat of :67, 82 is
+    about how early these are); with ``image_sizes`` also ``cover_median_r_squared`` (``CoverStats.scalars()``) and ``ece``
+    (``Reliability.ece``), the columns the study reports beside the ranking (:17-19)."""
+    rows = []
+    for i, entry in enumerate(results):
+        model, info = entry[0], entry[1]
+        if image_sizes is None:
+            grouped, scored = None, validate(model, val, rows=False)
+        else:
+            grouped = grouped_validate(model, val, image_sizes, n_bins=n_bins)
+            scored = grouped.validation
+        cs = scored.class_scores()
+        row = {"config": i, "balanced_accuracy": cs.balanced_accuracy, "f1_macro": cs.f1_macro, "accuracy": scored.accuracy,
+               "mcc": cs.mcc, "log_loss": scored.log_loss, "best_val_epoch": info.get("best_val_epoch"),
+               "final_epoch": info.get("final_epoch")}
+        if grouped is not None:
+            row["cover_median_r_squared"] = grouped.cover.scalars()["cover_median_r_squared"]
+            row["ece"] = grouped.reliability.ece
+        rows.append(row)
+    rows.sort(key=lambda r: (-r["balanced_accuracy"], -r["f1_macro"], r["config"]))
+    return rows

@@ -17,7 +17,7 @@ from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tupl
 
 import numpy as np
 
-from .calibration import CalibratedMLP, calibrate, evaluate
+from .calibration import CalibratedMLP, calibrate, evaluate, evaluate_classes
 from .featureset import FeatureSet
 from .torch_classifier import TorchMLPClassifier
 from .validation import previous_accuracies, validate
@@ -42,9 +42,10 @@ class EarlyStopping:
         self.stopped = False      # out of patience
         self.t0 = time.time()
 
-    def epoch_done(self, clf, epoch: int, ref_acc: float, val_acc: float, val_loss: float) -> Dict[str, Any]:
+    def epoch_done(self, clf, epoch: int, ref_acc: float, val_acc: float, val_loss: float, *,
+                   extra: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """Record epoch ``epoch`` of ``clf`` (snapshot it when it is the best so far).  -> the epoch's callback dict; ``stopped``
-        says whether the patience has run out."""
+        says whether the patience has run out.  ``extra`` entries are added to the dict and decide nothing."""
         self.epoch = epoch
         if self.patience is not None:
             if val_loss < self.best_loss:
@@ -56,6 +57,8 @@ class EarlyStopping:
         curve = getattr(clf, "loss_curve_", [None])
         metrics: Dict[str, Any] = {"epoch": epoch, "ref_accuracy": ref_acc, "val_accuracy": val_acc, "val_loss": val_loss,
                                    "training_loss": curve[-1] if curve else None, "cumulative_seconds": time.time() - self.t0}
+        if extra:
+            metrics.update(extra)
         if self.stopped or epoch == self.nbr_epochs - 1:
             metrics["final_epoch"] = epoch + 1
             metrics["early_stopped"] = self.stopped
@@ -77,7 +80,8 @@ class EarlyStopping:
 
 def epoch_loop(clf, train_epoch: Callable[[Any, int], None], eval_ref: Callable[[Any], float],
                eval_val: Callable[[Any], Tuple[float, float]], nbr_epochs: int, early_stopping_patience: Optional[int] = None,
-               on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None) -> Tuple[Any, Dict[str, Any]]:
+               on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None, class_scores: bool = False
+               ) -> Tuple[Any, Dict[str, Any]]:
     """Run up to ``nbr_epochs`` epochs of ``train_epoch(clf, epoch)``, each followed by ``eval_ref(clf) -> accuracy`` and
     ``eval_val(clf) -> (accuracy, log_loss)``.  -> ``(clf, info)``.
 
@@ -90,19 +94,33 @@ def epoch_loop(clf, train_epoch: Callable[[Any, int], None], eval_ref: Callable[
     ``training_loss`` (``clf.loss_curve_[-1]``, or None), ``cumulative_seconds``; on the last epoch run also ``final_epoch``
     (1-based), ``early_stopped`` and, when a best epoch exists, ``best_val_epoch`` (1-based) / ``best_val_loss``.
 
+    With ``class_scores=True``, ``eval_val(clf)`` returns ``(accuracy, log_loss, ClassScores)`` (``calibration.evaluate_classes``)
+    and the dict gains ``val_balanced_accuracy`` and ``val_f1_macro`` -- the metrics the balancing study ranks by, which move
+    differently from accuracy over the epochs (docs/research/balancing-experiments.md:67, 82).  Early stopping still reads
+    ``val_loss`` alone: everything else in the dict and everything returned is what ``class_scores=False`` gives.
+
     ``info``: ``enabled``, ``patience``, ``stop_reason`` ("early_stopping" or "budget_exhausted"), ``final_epoch``,
     ``best_val_epoch``, ``best_val_loss`` (None without a best epoch) -- the reference's ``_early_stop_info``."""
     state = EarlyStopping(nbr_epochs, early_stopping_patience)
     for epoch in range(int(nbr_epochs)):
         train_epoch(clf, epoch)
         ref_acc = eval_ref(clf)
-        val_acc, val_loss = eval_val(clf)
-        metrics = state.epoch_done(clf, epoch, ref_acc, val_acc, val_loss)
+        val_acc, val_loss, extra = _val_entries(eval_val(clf), class_scores)
+        metrics = state.epoch_done(clf, epoch, ref_acc, val_acc, val_loss, extra=extra)
         if on_epoch_end is not None:
             on_epoch_end(metrics)
         if state.stopped:
             break
     return state.result(clf)
+
+
+def _val_entries(result, class_scores: bool) -> Tuple[float, float, Optional[Dict[str, float]]]:
+    """``eval_val``'s return value -> (accuracy, log_loss, the extra callback entries or None)."""
+    if not class_scores:
+        val_acc, val_loss = result
+        return val_acc, val_loss, None
+    val_acc, val_loss, scores = result
+    return val_acc, val_loss, {"val_balanced_accuracy": scores.balanced_accuracy, "val_f1_macro": scores.f1_macro}
 
 
 def _contiguous_batches(n_rows: int, batch_size: int) -> Callable[[int], Iterable[np.ndarray]]:
@@ -128,7 +146,8 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
                      class_weight: Optional[dict] = None, early_stopping_patience: Optional[int] = None,
                      on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None,
                      batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None,
-                     clf: Optional[TorchMLPClassifier] = None) -> Tuple[CalibratedMLP, Dict[str, Any], List[float]]:
+                     clf: Optional[TorchMLPClassifier] = None, class_scores: bool = False
+                     ) -> Tuple[CalibratedMLP, Dict[str, Any], List[float]]:
     """Train, early-stop and calibrate the MLP head on three resident splits.  -> ``(calibrated, info, ref_accs)``:
     the ``CalibratedMLP`` of the returned classifier on ``ref``, ``epoch_loop``'s ``info``, and the ref accuracy after every
     epoch run (the reference's ``TrainClassifierReturnMsg.ref_accs``).
@@ -141,7 +160,10 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
     one batch of ``labels.train.load_data_in_batches(batch_size, random_seed=epoch)`` (:141-145).  The default is contiguous
     slices of ``batch_size`` rows in stored order, the same every epoch.  pyspacer's shuffle of the images behind that loader is
     not reproduced here; ``batches`` is the hook for it (any callable ``epoch -> iterable of row-index arrays``).  Within a batch
-    the classifier shuffles as ``partial_fit`` does."""
+    the classifier shuffles as ``partial_fit`` does.
+
+    ``class_scores=True`` scores ``val`` through ``calibration.evaluate_classes`` instead of ``evaluate``: the ``on_epoch_end``
+    dict gains ``val_balanced_accuracy`` and ``val_f1_macro`` (see ``epoch_loop``); nothing returned changes."""
     _check_splits(train, ref, val, batch_size)
     if clf is None:
         clf = TorchMLPClassifier(hidden_layer_sizes=(500, 300, 100), learning_rate_init=1e-4, class_weight=class_weight,
@@ -161,8 +183,9 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
         ref_accs.append(evaluate(c, ref)[0])
         return ref_accs[-1]
 
-    clf, info = epoch_loop(clf, train_epoch, eval_ref, lambda c: evaluate(c, val), nbr_epochs,
-                           early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end)
+    eval_val = evaluate_classes if class_scores else evaluate
+    clf, info = epoch_loop(clf, train_epoch, eval_ref, lambda c: eval_val(c, val), nbr_epochs,
+                           early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end, class_scores=class_scores)
     return calibrate(clf, ref), info, ref_accs
 
 

@@ -10,6 +10,9 @@ reference                                              here
 the previous models' accuracies (:273-277)             ``previous_accuracies(pc_models, val)``
 ``_compute_topk_mrr`` (metrics/ranking.py:42-65)       ``Validation.topk_accuracy(k)``, ``Validation.mrr`` (from ``rank_hist``)
 per-sample log-loss (metrics/probability.py:43-49)     ``Validation.log_loss`` (from ``nll_q32``), ``Validation.p_true``
+``compute_precision_recall_f1`` and                    ``Validation.class_scores()`` (``class_scores.ClassScores`` of
+``compute_balanced_accuracy_mcc``                      ``confusion``)
+(metrics/classification.py:171-302)
 =====================================================  ===================================================================
 
 The reference builds the N x K probability matrix on the host (``metrics/coordinator.py:59-76``) and reduces it to one rank and
@@ -30,6 +33,7 @@ import numpy as np
 from . import _lib
 from .backbone import _current_stream_ptr
 from .calibration import CalibratedMLP, _batches
+from .class_scores import ClassScores
 from .featureset import FeatureSet
 from .inference import Predictor
 
@@ -105,6 +109,12 @@ class Validation:
         if not self.n:
             return float("nan")
         return float((self.rank_hist / np.arange(1, len(self.rank_hist) + 1, dtype=np.float64)).sum() / self.n)
+
+    def class_scores(self) -> ClassScores:
+        """-> ``ClassScores(self.confusion, self.classes)``: per-class precision / recall / f1, the macro averages, balanced accuracy
+        and MCC of the scored rows (``compute_precision_recall_f1`` and ``compute_balanced_accuracy_mcc``,
+        metrics/classification.py:171-302)."""
+        return ClassScores(self.confusion, self.classes)
 
     def merge(self, other: "Validation") -> "Validation":
         """The validation of this one's rows followed by ``other``'s: integer adds and row concatenation."""
