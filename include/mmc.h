@@ -436,6 +436,57 @@ int mmc_head_evaluate_grouped_set(mmc_head* h, mmc_featureset* fs, int64_t first
                                   int64_t* bin_count, int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min, float* bin_conf_max,
                                   void* hip_stream);
 
+/* ---- category validation: per-category reliability bins ----------------------------------------------------------------
+ * Replaces: the second half of compute_calibration (mermaid_classifier/pyspacer/metrics/calibration.py:120-161): one _adaptive_ece
+ *   table per top-level category, over the rows whose true class lies in that category, with the category's own bin count
+ *   n_bins_cat = min(20, max(2, n // 10)) (calibration.py:137).  That needs the order of the scores inside each category, which the
+ *   grouped call does not keep; without this call the only route is est / score per row back to the host and np.argsort per category.
+ * The call is mmc_head_evaluate_grouped(_set) -- same arguments, and every per-row, evaluation and group output comes back with the same
+ * bits -- followed by one more select per category on the device.  Extra arguments (host pointers):
+ *   category_of_class[K]   int32 in [-1, n_categories): the category of each class of the head (the label map has been applied), -1 for
+ *                          a class that belongs to no category
+ *   n_categories           in [1, MMC_CATEGORY_MAX]
+ * A row is SCORED exactly when mmc_head_evaluate adds it to confusion; unscored rows and rows of a class without a category enter no
+ * category table.  With n_c the scored rows whose true class lies in category c (outputs, each may be NULL):
+ *   cat_rows[c]            n_categories: n_c
+ *   cat_n_bins[c]          n_categories: nb_c = min(MMC_CATEGORY_MAX_BINS, max(MMC_CATEGORY_MIN_BINS, n_c / MMC_CATEGORY_ROWS_PER_BIN))
+ *                          for n_c > 0, else 0
+ *   cat_bin_count, cat_bin_correct, cat_bin_conf_q32, cat_bin_conf_min, cat_bin_conf_max   [n_categories][MMC_CATEGORY_MAX_BINS]: per
+ *                          category what bin_count ... bin_conf_max are for the whole split: the category's rows in the order of the
+ *                          31-bit key (bits(score) << 1) | (est == g), bin b = sorted positions [b * n_c / nb_c, (b + 1) * n_c / nb_c),
+ *                          equal-key rows split by integer position arithmetic.  Empty bins and the bins at index nb_c and above are 0
+ *                          in every column.  Integer atomics only: the tables depend on neither row order, grid nor chunking.
+ * Everything is checked before the first launch -- the checks of mmc_head_evaluate_grouped(_set), and: category_of_class NULL, an
+ *   entry outside [-1, n_categories), n_categories outside [1, MMC_CATEGORY_MAX] -- and a rejected call returns MMC_ERR_ARG with nothing
+ *   launched and every output whose size the arguments determine zeroed (the category tables only for a valid n_categories).  n == 0
+ *   with n_images == 0 is MMC_OK with zeroed outputs.
+ * Scratch (one more byte and one more 4 B key per row, one select state per category) belongs to the head handle, grows on demand and
+ *   is freed with it.  The call synchronises `hip_stream` once, at the end. */
+#define MMC_CATEGORY_MAX 64
+#define MMC_CATEGORY_MAX_BINS 20     /* calibration.py:137: min(20, ...          */
+#define MMC_CATEGORY_MIN_BINS 2      /* calibration.py:137:      ... max(2, ...   */
+#define MMC_CATEGORY_ROWS_PER_BIN 10 /* calibration.py:137:            ... n // 10)) */
+int mmc_head_evaluate_categories(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
+                                 int32_t* est, float* score, int32_t* rank, float* p_true, int64_t totals[MMC_EVAL_TOTALS],
+                                 int64_t* confusion /* K*K or NULL */, int64_t* rank_hist /* K or NULL */,
+                                 const int64_t* image_offsets, int64_t n_images, const int32_t* source_of_image, int n_sources, int n_bins,
+                                 int64_t* support, int64_t* nll_q32, int64_t* score_q32, int64_t* source_confusion,
+                                 double* cover_sums /* K*MMC_COVER_SUMS */, int64_t* n_images_used,
+                                 int64_t* bin_count, int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min, float* bin_conf_max,
+                                 const int32_t* category_of_class /* K */, int n_categories, int64_t* cat_rows, int32_t* cat_n_bins,
+                                 int64_t* cat_bin_count, int64_t* cat_bin_correct, int64_t* cat_bin_conf_q32, float* cat_bin_conf_min,
+                                 float* cat_bin_conf_max, unsigned flags, void* hip_stream);
+int mmc_head_evaluate_categories_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
+                                     int32_t* est, float* score, int32_t* rank, float* p_true, int64_t totals[MMC_EVAL_TOTALS],
+                                     int64_t* confusion /* K*K or NULL */, int64_t* rank_hist /* K or NULL */,
+                                     const int64_t* image_offsets, int64_t n_images, const int32_t* source_of_image, int n_sources, int n_bins,
+                                     int64_t* support, int64_t* nll_q32, int64_t* score_q32, int64_t* source_confusion,
+                                     double* cover_sums /* K*MMC_COVER_SUMS */, int64_t* n_images_used,
+                                     int64_t* bin_count, int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min, float* bin_conf_max,
+                                     const int32_t* category_of_class /* K */, int n_categories, int64_t* cat_rows, int32_t* cat_n_bins,
+                                     int64_t* cat_bin_count, int64_t* cat_bin_correct, int64_t* cat_bin_conf_q32, float* cat_bin_conf_min,
+                                     float* cat_bin_conf_max, void* hip_stream);
+
 /* ---- ranking validation: per-class ranks, hierarchical top-k -----------------------------------------------------------
  * Replaces: the parts of compute_ranking (mermaid_classifier/pyspacer/metrics/ranking.py) that need more than the overall rank
  *   histogram and that otherwise need the N x K probability matrix and np.argsort(-proba) on the host:

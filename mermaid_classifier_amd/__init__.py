@@ -14,7 +14,8 @@ from .training import epoch_loop, train_and_validate, train_classifier  # noqa: 
 from .sweep import SweepConfig, partial_fit_rows_group, rank_sweep, sweep_loop, train_sweep  # noqa: F401
 from .sampling import class_counts, effective_number_weights, row_batches, subsample_rows, subsample_targets  # noqa: F401
 from .validation import Validation, previous_accuracies, validate  # noqa: F401
-from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, grouped_validate  # noqa: F401
+from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, category_bins, grouped_validate  # noqa: F401
+from .taxonomy import TaxonomicScores  # noqa: F401
 from .ranking import RankedValidation, ranking_validate, similarity_levels  # noqa: F401
 
 __all__ = [
@@ -30,4 +31,5 @@ __all__ = [
     "Validation", "validate", "previous_accuracies",
     "grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability",
     "ranking_validate", "RankedValidation", "similarity_levels",
+    "category_bins", "TaxonomicScores",
 ]

@@ -18,6 +18,8 @@ MMC_IN_HOST, MMC_OUT_HOST = 1, 2
 MMC_EVAL_TOTALS = 5   # include/mmc.h: length of mmc_head_evaluate's totals
 MMC_GROUPED_MAX_BINS, MMC_COVER_SUMS = 64, 8   # include/mmc.h: mmc_head_evaluate_grouped
 MMC_GROUPED_MAX_SOURCE_CELLS, MMC_GROUPED_MAX_COVER_CELLS = 1 << 26, 1 << 28
+MMC_CATEGORY_MAX, MMC_CATEGORY_MAX_BINS = 64, 20   # include/mmc.h: mmc_head_evaluate_categories
+MMC_CATEGORY_MIN_BINS, MMC_CATEGORY_ROWS_PER_BIN = 2, 10   # calibration.py:137: n_bins_cat = min(20, max(2, n // 10))
 MMC_RANKED_MAX_K = 16   # include/mmc.h: selection rounds of mmc_head_evaluate_ranked
 MMC_TRAINER_GROUP_MAX = 16   # include/mmc.h: members of one mmc_trainer_group_partial_fit_set call
 
@@ -35,6 +37,7 @@ SYMBOLS = [
     "mmc_trainer_partial_fit_set", "mmc_trainer_group_partial_fit_set", "mmc_trainer_evaluate_set_q32", "mmc_calibrator_add_set",
     "mmc_trainer_evaluate_classes", "mmc_trainer_evaluate_classes_set",
     "mmc_head_evaluate", "mmc_head_evaluate_set", "mmc_head_evaluate_grouped", "mmc_head_evaluate_grouped_set",
+    "mmc_head_evaluate_categories", "mmc_head_evaluate_categories_set",
     "mmc_head_evaluate_ranked", "mmc_head_evaluate_ranked_set",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
@@ -170,6 +173,12 @@ def _load() -> C.CDLL:
     lib.mmc_head_evaluate_grouped.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + grouped + [u32, vp]
     lib.mmc_head_evaluate_grouped_set.restype = i32
     lib.mmc_head_evaluate_grouped_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + grouped + [vp]
+    # the arguments of mmc_head_evaluate_grouped(_set), then category_of_class, n_categories and the 7 category outputs
+    categories = grouped + [vp, i32] + [vp] * 7
+    lib.mmc_head_evaluate_categories.restype = i32
+    lib.mmc_head_evaluate_categories.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + categories + [u32, vp]
+    lib.mmc_head_evaluate_categories_set.restype = i32
+    lib.mmc_head_evaluate_categories_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + categories + [vp]
     # the arguments of mmc_head_evaluate(_set), then sim_level, n_levels, kmax, class_rank_hist, hier_hist
     ranked = [vp, i32, i32, vp, vp]
     lib.mmc_head_evaluate_ranked.restype = i32

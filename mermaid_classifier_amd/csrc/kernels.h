@@ -273,6 +273,12 @@ constexpr int GROUP_MAX_BINS = 64;
 constexpr int GROUP_MAX_TARGETS = 2 * GROUP_MAX_BINS;            // the sorted positions of every bin's first and last key
 constexpr int GROUP_HIST_WORDS = GROUP_MAX_TARGETS * 1024;       // counters of one radix-select level: slots x 2^10 (level 1: 1 x 2^11)
 constexpr uint32_t GROUP_KEY_NONE = 0xFFFFFFFFu;                 // the reliability key of a row that is not scored
+constexpr int GROUP_MAX_CATEGORIES = 64;                         // categories of mmc_head_evaluate_categories (ids fit the category byte)
+constexpr uint8_t GROUP_SEG_NONE = 0xFF;                         // the category byte of a row that enters no category table
+// the bins of a category of n rows: n_bins_cat = min(20, max(2, n // 10)) (mermaid_classifier/pyspacer/metrics/calibration.py:137)
+#define GROUP_CAT_BINS_MAX 20
+#define GROUP_CAT_BINS_MIN 2
+#define GROUP_CAT_ROWS_PER_BIN 10
 struct GroupSelect {   // device state of the radix select; after launch_group_select: tgt_prefix = the keys at the targets' sorted
                        // positions, slot_prefix[0 .. n_slots) = the distinct ones among them, ascending
     uint32_t n_scored, n_targets, n_slots, pad;
@@ -287,6 +293,9 @@ struct GroupRowsArgs {
     unsigned long long* cls_tab;                         // [3][K]: support, nll_q32, score_q32 per true class
     unsigned long long* source_conf;                     // [sources][K][K], or NULL
     uint32_t* keys;                                      // [rows of the call]
+    const int32_t* category_of_class;                    // [K] in [-1, categories), or NULL: no category bytes
+    uint8_t* seg;                                        // [rows of the call]: the category of the row's true class, GROUP_SEG_NONE for an
+                                                         // unscored row or a class without a category; NULL without category_of_class
 };
 // one chunk's scored rows into the integer tables (the caller zeroes them once per call) and its reliability keys
 int launch_group_rows(const GroupRowsArgs& a, hipStream_t st);
@@ -301,3 +310,11 @@ int launch_group_cover(const int32_t* true_cnt, const int32_t* pred_cnt, const i
 // hist: GROUP_HIST_WORDS counters of scratch
 int launch_group_select(const uint32_t* keys, int64_t n, const long long* totals, int n_bins, GroupSelect* sel, uint32_t* hist,
                         unsigned long long* raw, hipStream_t st);
+// cat_rows[c] = sum of support[k] over the classes with category_of_class[k] == c, cat_bins[c] = its bin count (0 without a row), for
+// c < n_categories <= GROUP_MAX_CATEGORIES; both on the device
+int launch_group_category_counts(const unsigned long long* support, const int32_t* category_of_class, int K, int n_categories,
+                                 long long* cat_rows, int32_t* cat_bins, hipStream_t st);
+// launch_group_select over the rows of category c alone: ckeys[r] = seg[r] == c ? keys[r] : GROUP_KEY_NONE (n entries of scratch), the
+// targets seeded from cat_rows[c] / cat_bins[c] on the device, then the same select and binned sums into this category's sel / raw
+int launch_group_select_category(const uint32_t* keys, const uint8_t* seg, int64_t n, int c, const long long* cat_rows, const int32_t* cat_bins,
+                                 uint32_t* ckeys, GroupSelect* sel, uint32_t* hist, unsigned long long* raw, hipStream_t st);

@@ -29,6 +29,13 @@
 // ballot).  After level 3 the slots are the distinct edge keys e_0 < e_1 < ...; bin_sums_kernel counts, in LDS, the rows equal to
 // each e_j and count / n_correct / conf_q32 of the rows strictly between e_j and e_j+1.  Such a region lies inside one bin, and rows
 // with equal keys contribute identically, so the host splits the equal-key groups between bins by position arithmetic on integers.
+//
+// Per-category bins (mmc_head_evaluate_categories; calibration.py:120-161, one _adaptive_ece per top-level category over the rows whose
+// true class lies in it, n_bins = min(20, max(2, n // 10)) at :137).  group_rows_kernel also stores one category byte per row;
+// category_counts_kernel sums support over each category's classes for its rows and bins; then, per category, category_mask_kernel
+// copies the keys of its rows into a second key buffer (GROUP_KEY_NONE elsewhere), select_init_category_kernel seeds the targets
+// from the category's own counts, and the select and bin_sums kernels above run unchanged on that buffer into the category's own
+// GroupSelect / raw slot.  9 kernels and 4 memsets per category; five of the kernels read 4 or 5 B per row of the call.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -82,6 +89,10 @@ __global__ __launch_bounds__(256) void group_rows_kernel(GroupRowsArgs a)
             key = (bits << 1) | (uint32_t)(est == g);
         }
         a.keys[row] = key;
+        if (a.seg) {
+            const int c = g >= 0 ? a.category_of_class[g] : -1;
+            a.seg[row] = c >= 0 ? (uint8_t)c : GROUP_SEG_NONE;
+        }
     }
     if (CLS_IN_LDS) {
         __syncthreads();
@@ -167,9 +178,8 @@ __global__ __launch_bounds__(256) void cover_reduce2_kernel(const double* __rest
 // ---- reliability bins: radix select of the keys at the bin edges ---------------------------------------------------------
 // target 2 b / 2 b + 1 = the sorted position of bin b's first / last key (an empty bin: both its first position, which always
 // exists); positions never decrease with the target index, so neither do the prefixes
-__global__ __launch_bounds__(GROUP_MAX_TARGETS) void select_init_kernel(const long long* __restrict__ totals, int n_bins, GroupSelect* sel)
+__device__ void select_seed(long long ns, int n_bins, GroupSelect* sel)
 {
-    const long long ns = totals[0] - totals[2] - totals[3];
     const int t = threadIdx.x;
     if (ns > 0 && t < 2 * n_bins) {
         const long long b = t >> 1;
@@ -184,6 +194,45 @@ __global__ __launch_bounds__(GROUP_MAX_TARGETS) void select_init_kernel(const lo
         sel->n_slots = ns > 0 ? 1u : 0u;
         sel->slot_prefix[0] = 0;
     }
+}
+
+__global__ __launch_bounds__(GROUP_MAX_TARGETS) void select_init_kernel(const long long* __restrict__ totals, int n_bins, GroupSelect* sel)
+{
+    select_seed(totals[0] - totals[2] - totals[3], n_bins, sel);
+}
+
+// the targets of one category: its rows and its bins as category_counts_kernel left them
+__global__ __launch_bounds__(GROUP_MAX_TARGETS) void select_init_category_kernel(const long long* __restrict__ cat_rows,
+                                                                                 const int32_t* __restrict__ cat_bins, int c, GroupSelect* sel)
+{
+    select_seed(cat_rows[c], cat_bins[c], sel);
+}
+
+// ---- per-category reliability bins ----------------------------------------------------------------------------------------
+// lane = category: the rows of its classes, and from them its bins
+__global__ __launch_bounds__(GROUP_MAX_CATEGORIES) void category_counts_kernel(const unsigned long long* __restrict__ support,
+                                                                               const int32_t* __restrict__ category_of_class, int K,
+                                                                               int n_categories, long long* __restrict__ cat_rows,
+                                                                               int32_t* __restrict__ cat_bins)
+{
+    const int c = threadIdx.x;
+    if (c >= n_categories) return;
+    long long n = 0;
+    for (int k = 0; k < K; ++k)
+        if (category_of_class[k] == c) n += (long long)support[k];
+    long long nb = n / GROUP_CAT_ROWS_PER_BIN;
+    nb = nb < GROUP_CAT_BINS_MIN ? GROUP_CAT_BINS_MIN : nb;
+    nb = nb > GROUP_CAT_BINS_MAX ? GROUP_CAT_BINS_MAX : nb;
+    cat_rows[c] = n;
+    cat_bins[c] = n > 0 ? (int32_t)nb : 0;
+}
+
+// the keys of category c's rows, GROUP_KEY_NONE elsewhere: the select kernels then see that category alone
+__global__ __launch_bounds__(256) void category_mask_kernel(const uint32_t* __restrict__ keys, const uint8_t* __restrict__ seg, int64_t n, int c,
+                                                            uint32_t* __restrict__ ckeys)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        ckeys[i] = seg[i] == (uint8_t)c ? keys[i] : GROUP_KEY_NONE;
 }
 
 // hist[(slot << bits) | digit] += 1 for every key whose bits above (shift + bits) are a slot's prefix; digit = (key >> shift) % 2^bits
@@ -320,7 +369,7 @@ int pass_grid(int64_t n)
 int launch_group_rows(const GroupRowsArgs& a, hipStream_t st)
 {
     if (a.rows < 1 || a.K < 1 || a.n_images < 1 || !a.scored || !a.est || !a.score || !a.p_true || !a.offsets || !a.true_cnt || !a.pred_cnt ||
-        !a.points || !a.cls_tab || !a.keys || (a.source_of_image && !a.source_conf))
+        !a.points || !a.cls_tab || !a.keys || (a.source_of_image && !a.source_conf) || (a.seg && !a.category_of_class))
         return -19;
     const int grid = (a.rows + 1023) / 1024;   // a workgroup walks about 1024 rows before it flushes its per-class sums
     if (a.K <= GROUP_CLS_LDS_MAX_K) hipLaunchKernelGGL((group_rows_kernel<true>), dim3(grid), dim3(256), (size_t)3 * a.K * 8, st, a);
@@ -353,12 +402,10 @@ int launch_group_cover(const int32_t* true_cnt, const int32_t* pred_cnt, const i
     return 0;
 }
 
-int launch_group_select(const uint32_t* keys, int64_t n, const long long* totals, int n_bins, GroupSelect* sel, uint32_t* hist,
-                        unsigned long long* raw, hipStream_t st)
+// the three select levels and the binned sums over keys[n], from the targets a select_init*_kernel has seeded in sel
+static int select_levels(const uint32_t* keys, int64_t n, GroupSelect* sel, uint32_t* hist, unsigned long long* raw, hipStream_t st)
 {
-    if (n < 1 || !keys || !totals || n_bins < 1 || n_bins > GROUP_MAX_BINS || !sel || !hist || !raw) return -19;
     static const int level_bits[3] = {11, 10, 10};
-    hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(GROUP_MAX_TARGETS), 0, st, totals, n_bins, sel);
     int shift = 31;
     for (int l = 0; l < 3; ++l) {
         const int bits = level_bits[l];
@@ -371,4 +418,31 @@ int launch_group_select(const uint32_t* keys, int64_t n, const long long* totals
     hipLaunchKernelGGL(bin_sums_kernel, dim3(pass_grid(n)), dim3(256), 0, st, keys, n, sel, raw);
     M_LAUNCH_CHECK();
     return 0;
+}
+
+int launch_group_select(const uint32_t* keys, int64_t n, const long long* totals, int n_bins, GroupSelect* sel, uint32_t* hist,
+                        unsigned long long* raw, hipStream_t st)
+{
+    if (n < 1 || !keys || !totals || n_bins < 1 || n_bins > GROUP_MAX_BINS || !sel || !hist || !raw) return -19;
+    hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(GROUP_MAX_TARGETS), 0, st, totals, n_bins, sel);
+    return select_levels(keys, n, sel, hist, raw, st);
+}
+
+int launch_group_category_counts(const unsigned long long* support, const int32_t* category_of_class, int K, int n_categories,
+                                 long long* cat_rows, int32_t* cat_bins, hipStream_t st)
+{
+    if (!support || !category_of_class || K < 1 || n_categories < 1 || n_categories > GROUP_MAX_CATEGORIES || !cat_rows || !cat_bins) return -19;
+    hipLaunchKernelGGL(category_counts_kernel, dim3(1), dim3(GROUP_MAX_CATEGORIES), 0, st, support, category_of_class, K, n_categories, cat_rows,
+                       cat_bins);
+    M_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_group_select_category(const uint32_t* keys, const uint8_t* seg, int64_t n, int c, const long long* cat_rows, const int32_t* cat_bins,
+                                 uint32_t* ckeys, GroupSelect* sel, uint32_t* hist, unsigned long long* raw, hipStream_t st)
+{
+    if (n < 1 || !keys || !seg || c < 0 || c >= GROUP_MAX_CATEGORIES || !cat_rows || !cat_bins || !ckeys || !sel || !hist || !raw) return -19;
+    hipLaunchKernelGGL(category_mask_kernel, dim3(pass_grid(n)), dim3(256), 0, st, keys, seg, n, c, ckeys);
+    hipLaunchKernelGGL(select_init_category_kernel, dim3(1), dim3(GROUP_MAX_TARGETS), 0, st, cat_rows, cat_bins, c, sel);
+    return select_levels(ckeys, n, sel, hist, raw, st);
 }

@@ -233,6 +233,10 @@ struct GroupIO {
     int64_t *support, *nll_q32, *score_q32, *source_confusion;
     double* cover; int64_t* n_images_used;
     int64_t *bin_count, *bin_correct, *bin_conf_q32; float *bin_conf_min, *bin_conf_max;
+    // mmc_head_evaluate_categories* only (with_cat): the category of every class and the per-category tables
+    bool with_cat; const int32_t* category_of_class; int n_categories;
+    int64_t* cat_rows; int32_t* cat_n_bins;
+    int64_t *cat_bin_count, *cat_bin_correct, *cat_bin_conf_q32; float *cat_bin_conf_min, *cat_bin_conf_max;
 };
 // where the rows and labels of an evaluation come from: rows X (host with MMC_IN_HOST in `flags`, else on the head's device) with
 // host labels y, uploaded per chunk; or (`set`) rows [first, first + n) of a feature set, rows and labels read where they lie
@@ -262,7 +266,8 @@ static int eval_check_common(const mmc_head* h, int64_t n, const int32_t* label_
 // where the grouped pass keeps its device state inside h->grp (every part 256-byte aligned); the first `zero_bytes` are the integer
 // tables a call starts from zero
 struct GroupLayout {
-    size_t true_cnt, pred_cnt, points, cls_tab, source_conf, zero_bytes, offsets, source, keys, slab, cov, n_used, sel, raw, hist, bytes;
+    size_t true_cnt, pred_cnt, points, cls_tab, source_conf, zero_bytes, offsets, source, keys, slab, cov, n_used, sel, raw, hist;
+    size_t cat_of_class, seg, ckeys, cat_rows, cat_bins, cat_sel, cat_raw, bytes;   // (all empty without categories)
     int chunks;
 };
 static GroupLayout group_layout(int K, int64_t n, const GroupIO& g)
@@ -288,6 +293,14 @@ static GroupLayout group_layout(int K, int64_t n, const GroupIO& g)
     L.sel = take(sizeof(GroupSelect));
     L.raw = take((size_t)4 * GROUP_MAX_TARGETS * 8);
     L.hist = take((size_t)GROUP_HIST_WORDS * 4);
+    const size_t nc = g.with_cat ? (size_t)g.n_categories : 0;
+    L.cat_of_class = take(nc ? (size_t)K * 4 : 0);
+    L.seg = take(nc ? (size_t)n : 0);
+    L.ckeys = take(nc ? (size_t)n * 4 : 0);
+    L.cat_rows = take(nc * 8);
+    L.cat_bins = take(nc * 4);
+    L.cat_sel = take(nc * sizeof(GroupSelect));
+    L.cat_raw = take(nc * 4 * GROUP_MAX_TARGETS * 8);
     L.bytes = at;
     return L;
 }
@@ -299,6 +312,8 @@ struct GroupScratch {
     int64_t* offsets; int32_t* source; uint32_t* keys;
     double *slab, *cov; long long* n_used;
     GroupSelect* sel; unsigned long long* raw; uint32_t* hist;
+    // null without categories; cat_sel / cat_raw hold one GroupSelect / one raw table per category
+    int32_t* cat_of_class; uint8_t* seg; uint32_t* ckeys; long long* cat_rows; int32_t* cat_bins; GroupSelect* cat_sel; unsigned long long* cat_raw;
 };
 
 // once per grouped call: lays out and grows h->grp, zeroes the integer tables, uploads offsets and source ids
@@ -326,6 +341,16 @@ static int group_prepare(mmc_head* h, int64_t n, const GroupIO& g, hipStream_t s
     HIP_TRY(hipMemsetAsync(b, 0, L.zero_bytes, st));
     HIP_TRY(hipMemcpyAsync(s->offsets, g.offsets, (size_t)(g.n_images + 1) * 8, hipMemcpyHostToDevice, st));
     if (src) HIP_TRY(hipMemcpyAsync(s->source, g.source, (size_t)g.n_images * 4, hipMemcpyHostToDevice, st));
+    if (g.with_cat) {
+        s->cat_of_class = reinterpret_cast<int32_t*>(b + L.cat_of_class);
+        s->seg = reinterpret_cast<uint8_t*>(b + L.seg);
+        s->ckeys = reinterpret_cast<uint32_t*>(b + L.ckeys);
+        s->cat_rows = reinterpret_cast<long long*>(b + L.cat_rows);
+        s->cat_bins = reinterpret_cast<int32_t*>(b + L.cat_bins);
+        s->cat_sel = reinterpret_cast<GroupSelect*>(b + L.cat_sel);
+        s->cat_raw = reinterpret_cast<unsigned long long*>(b + L.cat_raw);
+        HIP_TRY(hipMemcpyAsync(s->cat_of_class, g.category_of_class, (size_t)h->K * 4, hipMemcpyHostToDevice, st));
+    }
     return 0;
 }
 static int head_evaluate_groups(mmc_head* h, int64_t n, const GroupIO& g, const GroupScratch& s, hipStream_t st);
@@ -388,6 +413,7 @@ static int head_evaluate(mmc_head* h, const EvalSrc& src, const int32_t* label_m
         ga.K = K; ga.offsets = gs.offsets; ga.n_images = grp->n_images; ga.source_of_image = gs.source;
         ga.true_cnt = gs.true_cnt; ga.pred_cnt = gs.pred_cnt; ga.points = gs.points;
         ga.cls_tab = gs.cls_tab; ga.source_conf = gs.source_conf; ga.keys = gs.keys;
+        ga.category_of_class = gs.cat_of_class; ga.seg = gs.seg;
     }
     long long* dtot = h->eval_tot.p;
     long long* dhist = dtot + EVAL_TOTALS;
@@ -440,12 +466,12 @@ static_assert(MMC_GROUPED_MAX_BINS == GROUP_MAX_BINS, "include/mmc.h and kernels
 
 // the per-bin tables from the edge keys and the per-edge-key sums: in sorted order the rows are [== e_0][between e_0 and e_1][== e_1]
 // ... [== e_last]; a between-region lies in one bin, an equal-key group is split by its positions (all its rows contribute alike)
-static int group_bins(const GroupSelect& s, const unsigned long long* raw, const GroupIO& g)
+// count / correct / conf / cmin / cmax: nb entries each, zeroed here
+static int bins_from_select(const GroupSelect& s, const unsigned long long* raw, int nb, int64_t* count, int64_t* correct, int64_t* conf,
+                            float* cmin, float* cmax)
 {
-    const int nb = g.n_bins;
     const int64_t ns = s.n_scored;
-    std::vector<int64_t> count(nb, 0), correct(nb, 0), conf(nb, 0);
-    std::vector<float> cmin(nb, 0.f), cmax(nb, 0.f);
+    for (int i = 0; i < nb; ++i) { count[i] = correct[i] = conf[i] = 0; cmin[i] = cmax[i] = 0.f; }
     if (ns > 0) {
         if (s.n_targets != 2u * nb || s.n_slots < 1 || s.n_slots > s.n_targets) return fail(MMC_ERR_HIP, "grouped validation: select state is inconsistent");
         auto edge = [&](int b) { return (int64_t)b * ns / nb; };
@@ -477,12 +503,35 @@ static int group_bins(const GroupSelect& s, const unsigned long long* raw, const
             if (count[i]) { cmin[i] = score_of(s.tgt_prefix[2 * i]); cmax[i] = score_of(s.tgt_prefix[2 * i + 1]); }
         }
     }
+    return MMC_OK;
+}
+
+// the bins of the whole split
+static int group_bins(const GroupSelect& s, const unsigned long long* raw, const GroupIO& g)
+{
+    const int nb = g.n_bins;
+    std::vector<int64_t> count(nb), correct(nb), conf(nb);
+    std::vector<float> cmin(nb), cmax(nb);
+    int r = bins_from_select(s, raw, nb, count.data(), correct.data(), conf.data(), cmin.data(), cmax.data());
+    if (r) return r;
     if (g.bin_count) memcpy(g.bin_count, count.data(), (size_t)nb * 8);
     if (g.bin_correct) memcpy(g.bin_correct, correct.data(), (size_t)nb * 8);
     if (g.bin_conf_q32) memcpy(g.bin_conf_q32, conf.data(), (size_t)nb * 8);
     if (g.bin_conf_min) memcpy(g.bin_conf_min, cmin.data(), (size_t)nb * 4);
     if (g.bin_conf_max) memcpy(g.bin_conf_max, cmax.data(), (size_t)nb * 4);
     return MMC_OK;
+}
+
+static_assert(MMC_CATEGORY_MAX == GROUP_MAX_CATEGORIES && MMC_CATEGORY_MAX_BINS == GROUP_CAT_BINS_MAX &&
+                  MMC_CATEGORY_MIN_BINS == GROUP_CAT_BINS_MIN && MMC_CATEGORY_ROWS_PER_BIN == GROUP_CAT_ROWS_PER_BIN &&
+                  2 * GROUP_CAT_BINS_MAX <= GROUP_MAX_TARGETS,
+              "include/mmc.h and kernels.h disagree on the categories");
+// the bins of a category of `rows` > 0 rows (calibration.py:137), as category_counts_kernel computes them on the device
+static int category_bins(int64_t rows)
+{
+    int64_t nb = rows / GROUP_CAT_ROWS_PER_BIN;
+    nb = nb < GROUP_CAT_BINS_MIN ? GROUP_CAT_BINS_MIN : nb;
+    return (int)(nb > GROUP_CAT_BINS_MAX ? GROUP_CAT_BINS_MAX : nb);
 }
 
 // after the last chunk: the cover reduction and the select on the device, the tables to the host, one synchronisation, the bins
@@ -502,13 +551,56 @@ static int head_evaluate_groups(mmc_head* h, int64_t n, const GroupIO& g, const 
     if (g.n_images_used) HIP_TRY(hipMemcpyAsync(g.n_images_used, s.n_used, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&sel, s.sel, sizeof(sel), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(raw.data(), s.raw, raw.size() * 8, hipMemcpyDeviceToHost, st));
+    // per category: its rows and bins from the per-class support, then the same select over its rows alone (metrics.hip)
+    const int nc = g.with_cat ? g.n_categories : 0;
+    std::vector<GroupSelect> cat_sel(nc);
+    std::vector<unsigned long long> cat_raw((size_t)nc * 4 * GROUP_MAX_TARGETS);
+    std::vector<long long> cat_rows(nc);
+    if (nc) {
+        KTRY(launch_group_category_counts(s.cls_tab, s.cat_of_class, K, nc, s.cat_rows, s.cat_bins, st));
+        for (int c = 0; c < nc; ++c)
+            KTRY(launch_group_select_category(s.keys, s.seg, n, c, s.cat_rows, s.cat_bins, s.ckeys, s.cat_sel + c, s.hist,
+                                              s.cat_raw + (size_t)c * 4 * GROUP_MAX_TARGETS, st));
+        HIP_TRY(hipMemcpyAsync(cat_rows.data(), s.cat_rows, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cat_sel.data(), s.cat_sel, (size_t)nc * sizeof(GroupSelect), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cat_raw.data(), s.cat_raw, cat_raw.size() * 8, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
-    return group_bins(sel, raw.data(), g);
+    int r = group_bins(sel, raw.data(), g);
+    if (r) return r;
+    for (int c = 0; c < nc; ++c) {
+        const int64_t rows = cat_rows[c];
+        const int nb = rows > 0 ? category_bins(rows) : 0;
+        int64_t count[MMC_CATEGORY_MAX_BINS] = {}, correct[MMC_CATEGORY_MAX_BINS] = {}, conf[MMC_CATEGORY_MAX_BINS] = {};
+        float cmin[MMC_CATEGORY_MAX_BINS] = {}, cmax[MMC_CATEGORY_MAX_BINS] = {};
+        if ((int64_t)cat_sel[c].n_scored != rows)
+            return fail(MMC_ERR_HIP, "category validation: category %d selected over %u rows, holds %lld", c, cat_sel[c].n_scored, (long long)rows);
+        if ((r = bins_from_select(cat_sel[c], cat_raw.data() + (size_t)c * 4 * GROUP_MAX_TARGETS, nb, count, correct, conf, cmin, cmax))) return r;
+        const size_t at = (size_t)c * MMC_CATEGORY_MAX_BINS;
+        if (g.cat_rows) g.cat_rows[c] = rows;
+        if (g.cat_n_bins) g.cat_n_bins[c] = nb;
+        if (g.cat_bin_count) memcpy(g.cat_bin_count + at, count, sizeof(count));
+        if (g.cat_bin_correct) memcpy(g.cat_bin_correct + at, correct, sizeof(correct));
+        if (g.cat_bin_conf_q32) memcpy(g.cat_bin_conf_q32 + at, conf, sizeof(conf));
+        if (g.cat_bin_conf_min) memcpy(g.cat_bin_conf_min + at, cmin, sizeof(cmin));
+        if (g.cat_bin_conf_max) memcpy(g.cat_bin_conf_max + at, cmax, sizeof(cmax));
+    }
+    return MMC_OK;
 }
 
 // zeroes every group output whose size the arguments determine
 static void group_clear(const mmc_head* h, const GroupIO& g)
 {
+    if (g.with_cat && g.n_categories >= 1 && g.n_categories <= MMC_CATEGORY_MAX) {
+        const size_t nc = (size_t)g.n_categories, cells = nc * MMC_CATEGORY_MAX_BINS;
+        if (g.cat_rows) memset(g.cat_rows, 0, nc * 8);
+        if (g.cat_n_bins) memset(g.cat_n_bins, 0, nc * 4);
+        if (g.cat_bin_count) memset(g.cat_bin_count, 0, cells * 8);
+        if (g.cat_bin_correct) memset(g.cat_bin_correct, 0, cells * 8);
+        if (g.cat_bin_conf_q32) memset(g.cat_bin_conf_q32, 0, cells * 8);
+        if (g.cat_bin_conf_min) memset(g.cat_bin_conf_min, 0, cells * 4);
+        if (g.cat_bin_conf_max) memset(g.cat_bin_conf_max, 0, cells * 4);
+    }
     if (!h) return;
     const size_t K = (size_t)h->K;
     if (g.support) memset(g.support, 0, K * 8);
@@ -533,6 +625,14 @@ static int group_check(const mmc_head* h, int64_t n, const GroupIO& g)
         return fail(MMC_ERR_ARG, "n_bins = %d outside [1, %d]", g.n_bins, MMC_GROUPED_MAX_BINS);
     if (g.n_sources < 0) return fail(MMC_ERR_ARG, "n_sources = %d is negative", g.n_sources);
     if (g.n_images < 0) return fail(MMC_ERR_ARG, "n_images = %lld is negative", (long long)g.n_images);
+    if (g.with_cat) {
+        if (g.n_categories < 1 || g.n_categories > MMC_CATEGORY_MAX)
+            return fail(MMC_ERR_ARG, "n_categories = %d outside [1, %d]", g.n_categories, MMC_CATEGORY_MAX);
+        if (!g.category_of_class) return fail(MMC_ERR_ARG, "category_of_class is NULL");
+        for (int k = 0; k < h->K; ++k)
+            if (g.category_of_class[k] < -1 || g.category_of_class[k] >= g.n_categories)
+                return fail(MMC_ERR_ARG, "category_of_class[%d] = %d outside [-1, %d)", k, g.category_of_class[k], g.n_categories);
+    }
     if (n == 0) return g.n_images == 0 ? MMC_OK : fail(MMC_ERR_ARG, "%lld images over no rows", (long long)g.n_images);
     if (!g.offsets) return fail(MMC_ERR_ARG, "image_offsets is NULL");
     if (g.n_images < 1 || g.n_images > n) return fail(MMC_ERR_ARG, "n_images = %lld for %lld rows: every image owns at least one row", (long long)g.n_images, (long long)n);
@@ -578,7 +678,7 @@ static int rank_check(const mmc_head* h, const RankIO& k)
 }
 
 // ------------------------------------------------------------------------------------------
-// the six evaluate entry points: each names its source, its outputs and (grouped, ranked) its extra tables, and makes one call
+// the eight evaluate entry points: each names its source, its outputs and (grouped, categories, ranked) its extra tables, and makes one call
 // ------------------------------------------------------------------------------------------
 // the feature-set form: the slice, then the common checks, then the classes (the set's labels lie in [0, fs->K): that range must be
 // the head's classes, or the map's domain)
@@ -656,7 +756,8 @@ static GroupIO group_io(const int64_t* image_offsets, int64_t n_images, const in
                         float* bin_conf_max)
 {
     return {image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32, source_confusion,
-            cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max};
+            cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max,
+            false, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 }
 
 extern "C" int mmc_head_evaluate_grouped(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
@@ -684,6 +785,56 @@ extern "C" int mmc_head_evaluate_grouped_set(mmc_head* h, mmc_featureset* fs, in
     const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
     const GroupIO g = group_io(image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32, source_confusion,
                                cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min, bin_conf_max);
+    return evaluate(h, set_rows(fs, first, n), label_map, n_labels, o, &g, nullptr, hip_stream);
+}
+
+// the category arguments of the two category entry points, in the order of include/mmc.h, onto the group arguments
+static GroupIO with_categories(GroupIO g, const int32_t* category_of_class, int n_categories, int64_t* cat_rows, int32_t* cat_n_bins,
+                               int64_t* cat_bin_count, int64_t* cat_bin_correct, int64_t* cat_bin_conf_q32, float* cat_bin_conf_min,
+                               float* cat_bin_conf_max)
+{
+    g.with_cat = true; g.category_of_class = category_of_class; g.n_categories = n_categories;
+    g.cat_rows = cat_rows; g.cat_n_bins = cat_n_bins;
+    g.cat_bin_count = cat_bin_count; g.cat_bin_correct = cat_bin_correct; g.cat_bin_conf_q32 = cat_bin_conf_q32;
+    g.cat_bin_conf_min = cat_bin_conf_min; g.cat_bin_conf_max = cat_bin_conf_max;
+    return g;
+}
+
+extern "C" int mmc_head_evaluate_categories(mmc_head* h, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
+                                            int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals, int64_t* confusion,
+                                            int64_t* rank_hist, const int64_t* image_offsets, int64_t n_images, const int32_t* source_of_image,
+                                            int n_sources, int n_bins, int64_t* support, int64_t* nll_q32, int64_t* score_q32,
+                                            int64_t* source_confusion, double* cover_sums, int64_t* n_images_used, int64_t* bin_count,
+                                            int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min, float* bin_conf_max,
+                                            const int32_t* category_of_class, int n_categories, int64_t* cat_rows, int32_t* cat_n_bins,
+                                            int64_t* cat_bin_count, int64_t* cat_bin_correct, int64_t* cat_bin_conf_q32, float* cat_bin_conf_min,
+                                            float* cat_bin_conf_max, unsigned flags, void* hip_stream)
+{
+    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
+    const GroupIO g = with_categories(group_io(image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32,
+                                               source_confusion, cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min,
+                                               bin_conf_max),
+                                      category_of_class, n_categories, cat_rows, cat_n_bins, cat_bin_count, cat_bin_correct, cat_bin_conf_q32,
+                                      cat_bin_conf_min, cat_bin_conf_max);
+    return evaluate(h, host_rows(feats, y, n, flags), label_map, n_labels, o, &g, nullptr, hip_stream);
+}
+
+extern "C" int mmc_head_evaluate_categories_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map,
+                                                int n_labels, int32_t* est, float* score, int32_t* rank, float* p_true, int64_t* totals,
+                                                int64_t* confusion, int64_t* rank_hist, const int64_t* image_offsets, int64_t n_images,
+                                                const int32_t* source_of_image, int n_sources, int n_bins, int64_t* support, int64_t* nll_q32,
+                                                int64_t* score_q32, int64_t* source_confusion, double* cover_sums, int64_t* n_images_used,
+                                                int64_t* bin_count, int64_t* bin_correct, int64_t* bin_conf_q32, float* bin_conf_min,
+                                                float* bin_conf_max, const int32_t* category_of_class, int n_categories, int64_t* cat_rows,
+                                                int32_t* cat_n_bins, int64_t* cat_bin_count, int64_t* cat_bin_correct, int64_t* cat_bin_conf_q32,
+                                                float* cat_bin_conf_min, float* cat_bin_conf_max, void* hip_stream)
+{
+    const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
+    const GroupIO g = with_categories(group_io(image_offsets, n_images, source_of_image, n_sources, n_bins, support, nll_q32, score_q32,
+                                               source_confusion, cover_sums, n_images_used, bin_count, bin_correct, bin_conf_q32, bin_conf_min,
+                                               bin_conf_max),
+                                      category_of_class, n_categories, cat_rows, cat_n_bins, cat_bin_count, cat_bin_correct, cat_bin_conf_q32,
+                                      cat_bin_conf_min, cat_bin_conf_max);
     return evaluate(h, set_rows(fs, first, n), label_map, n_labels, o, &g, nullptr, hip_stream);
 }
 

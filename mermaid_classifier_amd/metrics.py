@@ -9,6 +9,7 @@ reference                                                    here
 ``_adaptive_ece`` (metrics/calibration.py:32-79)             ``GroupedValidation.reliability``: ``Reliability.ece``, ``.bins``
 per-category log-loss (metrics/probability.py:43-60) and     ``GroupedValidation.by_class(category_of_class)``
 accuracy / mean confidence (metrics/calibration.py:139-140)
+per-category ECE (metrics/calibration.py:120-161)            ``GroupedValidation.category_reliability``, ``.category_calibration()``
 ===========================================================  ==============================================================
 
 The reference walks ``ValResults`` row by row on the host.  Here ``mmc_head_evaluate_grouped(_set)`` adds one pass on the device to
@@ -27,7 +28,7 @@ from . import _lib
 from .backbone import _current_stream_ptr
 from .validation import MAX_ROWS_PER_CALL, Validation, _Outputs, _prepare, _ptr, _set_labels
 
-__all__ = ["grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability"]
+__all__ = ["grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability", "category_bins"]
 
 COVER_COLUMNS = ("sum_true", "sum_pred", "sum_err", "sum_sq_err", "sum_abs_err", "min_true", "max_true", "sum_sq_dev_true")
 
@@ -183,11 +184,17 @@ class Reliability:
 class GroupedValidation:
     """The outcome of ``grouped_validate``: ``validation`` (an ordinary ``Validation``), ``cover`` (``CoverStats``), ``sources``
     (``SourceStats``, or None without ``source_of_image``), ``reliability`` (``Reliability``) and the per-true-class integer sums
-    ``support``, ``nll_q32``, ``score_q32``."""
+    ``support``, ``nll_q32``, ``score_q32``.  With ``category_of_class`` given to ``grouped_validate``: ``category_of_class`` (K
+    integers, -1 = no category) and ``category_reliability``, one ``Reliability`` per category that holds a scored row, with the
+    category's own bin count ``min(20, max(2, n // 10))`` (calibration.py:137); both None otherwise."""
 
     def __init__(self, validation: Validation, cover: CoverStats, sources: Optional[SourceStats], reliability: Reliability, support, nll_q32,
-                 score_q32):
+                 score_q32, category_of_class=None, category_reliability: Optional[Dict[int, Reliability]] = None):
         self.validation, self.cover, self.sources, self.reliability = validation, cover, sources, reliability
+        if (category_of_class is None) != (category_reliability is None):
+            raise ValueError("category_of_class and category_reliability go together")
+        self.category_of_class = None if category_of_class is None else _check_categories(category_of_class, len(validation.classes))[0]
+        self.category_reliability = None if category_reliability is None else dict(category_reliability)
         K = len(validation.classes)
         self.support = np.asarray(support, dtype=np.int64)
         self.nll_q32 = np.asarray(nll_q32, dtype=np.int64)
@@ -214,6 +221,45 @@ class GroupedValidation:
         return out
 
 
+    def category_calibration(self, min_samples: int = 30) -> List[Dict[str, Any]]:
+        """The rows of ``calibration/per_category_ece`` (calibration.py:133-151): ``category`` (the integer id), ``ece``, ``accuracy``,
+        ``avg_confidence``, ``n_samples``, by ``ece`` descending (equal ``ece`` by category id ascending: the reference's stable sort
+        leaves insertion order there); categories with fewer than ``min_samples`` scored rows are left out.  ``accuracy`` and
+        ``avg_confidence`` come from the integers ``by_class`` uses.  Needs ``grouped_validate(..., category_of_class=...)``."""
+        if self.category_reliability is None:
+            raise ValueError("no category tables: call grouped_validate(..., category_of_class=...)")
+        sums = self.by_class(self.category_of_class, min_samples=min_samples)
+        rows = []
+        for c in sorted(self.category_reliability):
+            if c not in sums:
+                continue
+            rel = self.category_reliability[c]
+            if int(rel.count.sum()) != sums[c]["n_samples"]:
+                raise ValueError(f"category {c}: the bins hold {int(rel.count.sum())} rows, the per-class sums {sums[c]['n_samples']}")
+            rows.append({"category": c, "ece": rel.ece, "accuracy": sums[c]["accuracy"], "avg_confidence": sums[c]["avg_confidence"],
+                         "n_samples": sums[c]["n_samples"]})
+        rows.sort(key=lambda r: -r["ece"])
+        return rows
+
+
+def category_bins(n: int) -> int:
+    """``n_bins_cat`` of a category of ``n`` rows (calibration.py:137); 0 without a row."""
+    return min(_lib.MMC_CATEGORY_MAX_BINS, max(_lib.MMC_CATEGORY_MIN_BINS, n // _lib.MMC_CATEGORY_ROWS_PER_BIN)) if n > 0 else 0
+
+
+def _check_categories(category_of_class, K: int):
+    """-> (int32 array with every negative entry -1, number of categories); every complaint is a ValueError."""
+    cat = np.asarray(category_of_class)
+    if cat.shape != (K,) or cat.dtype.kind not in "iu":
+        raise ValueError(f"category_of_class must be {K} integers")
+    cat = np.where(cat < 0, -1, cat)
+    if int(cat.max()) < 0:
+        raise ValueError("category_of_class names no category")
+    if int(cat.max()) >= _lib.MMC_CATEGORY_MAX:
+        raise ValueError(f"category_of_class: category ids must lie below {_lib.MMC_CATEGORY_MAX}; got {int(cat.max())}")
+    return np.ascontiguousarray(cat, dtype=np.int32), int(cat.max()) + 1
+
+
 def _check_groups(n: int, image_sizes, source_of_image, n_bins):
     """-> (offsets int64, sources int32 or None, number of sources); every complaint is a ValueError."""
     sizes = np.asarray(image_sizes)
@@ -237,11 +283,14 @@ def _check_groups(n: int, image_sizes, source_of_image, n_bins):
     return offsets, np.ascontiguousarray(src, dtype=np.int32), int(src.max()) + 1
 
 
-def grouped_validate(model, data, image_sizes, *, source_of_image=None, n_bins: int = 20, rows: bool = False) -> GroupedValidation:
+def grouped_validate(model, data, image_sizes, *, source_of_image=None, n_bins: int = 20, rows: bool = False,
+                     category_of_class=None) -> GroupedValidation:
     """``validate(model, data, rows=rows)`` plus the grouped tables, in one call on the device.  ``data`` is a ``FeatureSet``
     (read in place) or one ``(X, y)`` pair; ``image_sizes[i]`` is the number of points of image ``i``, in row order (each image's
     points are contiguous, cover.py:34-36); ``source_of_image[i]`` an integer source id.  Everything is checked on the host before
-    the device is touched.  One call covers a whole split: more than ``MAX_ROWS_PER_CALL`` rows is a ``ValueError``."""
+    the device is touched.  One call covers a whole split: more than ``MAX_ROWS_PER_CALL`` rows is a ``ValueError``.
+    ``category_of_class`` (K integers below 64, negative = the class has no category) adds one reliability table per category
+    (``mmc_head_evaluate_categories``): ``category_reliability`` and ``category_calibration()`` of the result."""
     get_head, classes, ((rows_src, yi, lmap),) = _prepare(model, data, rows, True, "grouped_validate", one_pair=True)
     K, n = len(classes), len(rows_src)
     if n > MAX_ROWS_PER_CALL:
@@ -252,6 +301,7 @@ def grouped_validate(model, data, image_sizes, *, source_of_image=None, n_bins: 
     if S * K * K > _lib.MMC_GROUPED_MAX_SOURCE_CELLS:
         raise ValueError(f"{S} sources x {K} x {K} classes: at most {_lib.MMC_GROUPED_MAX_SOURCE_CELLS} per-source cells")
     n_bins = int(n_bins)
+    cat, C_ = (None, 0) if category_of_class is None else _check_categories(category_of_class, K)
     out = _Outputs(K, rows)
     c = out.call(n)
     support, nll, sq = np.zeros(K, np.int64), np.zeros(K, np.int64), np.zeros(K, np.int64)
@@ -266,12 +316,25 @@ def grouped_validate(model, data, image_sizes, *, source_of_image=None, n_bins: 
     common = (_ptr(lmap), 0 if lmap is None else len(lmap), *c.args, offsets.ctypes.data, len(offsets) - 1, _ptr(src), S, n_bins,
               support.ctypes.data, nll.ctypes.data, sq.ctypes.data, _ptr(sconf), cover.ctypes.data, used.ctypes.data, bc.ctypes.data,
               bk.ctypes.data, bq.ctypes.data, bmin.ctypes.data, bmax.ctypes.data)
+    evaluate_set, evaluate_rows = lib.mmc_head_evaluate_grouped_set, lib.mmc_head_evaluate_grouped
+    if cat is not None:
+        B = _lib.MMC_CATEGORY_MAX_BINS
+        crows, cnb = np.zeros(C_, np.int64), np.zeros(C_, np.int32)
+        cc, ck, cq = np.zeros((C_, B), np.int64), np.zeros((C_, B), np.int64), np.zeros((C_, B), np.int64)
+        cmin, cmax = np.zeros((C_, B), np.float32), np.zeros((C_, B), np.float32)
+        common += (cat.ctypes.data, C_, crows.ctypes.data, cnb.ctypes.data, cc.ctypes.data, ck.ctypes.data, cq.ctypes.data, cmin.ctypes.data,
+                   cmax.ctypes.data)
+        evaluate_set, evaluate_rows = lib.mmc_head_evaluate_categories_set, lib.mmc_head_evaluate_categories
     if yi is None:
-        _lib.check(lib.mmc_head_evaluate_grouped_set(head._h, rows_src._handle(), 0, n, *common, st))
+        _lib.check(evaluate_set(head._h, rows_src._handle(), 0, n, *common, st))
         if rows:
             c.gt = _set_labels(rows_src, 0, n, lmap, st)
     else:
-        _lib.check(lib.mmc_head_evaluate_grouped(head._h, rows_src.ctypes.data, yi.ctypes.data, n, *common, _lib.MMC_IN_HOST, st))
+        _lib.check(evaluate_rows(head._h, rows_src.ctypes.data, yi.ctypes.data, n, *common, _lib.MMC_IN_HOST, st))
         c.gt = yi if lmap is None else lmap[yi]
+    cat_rel = None
+    if cat is not None:
+        cat_rel = {c: Reliability(cc[c, :nb], ck[c, :nb], cq[c, :nb], cmin[c, :nb], cmax[c, :nb])
+                   for c, nb in enumerate(cnb.tolist()) if crows[c] > 0}
     return GroupedValidation(out.result(classes), CoverStats(cover, int(used[0])), SourceStats(sconf) if S else None,
-                             Reliability(bc, bk, bq, bmin, bmax), support, nll, sq)
+                             Reliability(bc, bk, bq, bmin, bmax), support, nll, sq, cat, cat_rel)
