@@ -208,6 +208,36 @@ int mmc_trainer_adam_state(mmc_trainer* t, int which, int set, float* const* W, 
  * _forward_probs, torch_classifier.py:332-376, stays on the host; mmc_calibrator_add_features / mmc_trainer_evaluate below do it on
  * the device). */
 int mmc_trainer_logits(mmc_trainer* t, const float* X, int64_t n, float* logits, void* hip_stream);
+/* The loss formulation of the trainer's steps: label smoothing, focal modulation and a logit prior, each a per-trainer option.
+ * Extends: the F.cross_entropy(weight=class_weight) of a step (torch_classifier.py:278), the only loss the reference has, to what its
+ *   research reports point at next (docs/research/hidden-layer-experiments.md:119, docs/research/balancing-experiments.md:96-100, 142).
+ * With logits z (the last Linear's output), t = y_i, class weights w (ones when none), logit_prior o (zeros when NULL),
+ *   eps = label_smoothing and gamma = focal_gamma, a mini-batch's data term is
+ *     u      = z + o                                   (fp32 add; inside the loss only)
+ *     logp_c = u_c - max u - log sum_c exp(u_c - max u),  p_t = exp(logp_t),  nll = -logp_t,  q = 1 - p_t,  m = q^gamma  (gamma = 0: m = 1)
+ *     l_i    = (1 - eps) w_t m nll + (eps / K) sum_c w_c (-logp_c)
+ *     L      = sum_i l_i / sum_i w[y_i]                 (+ the L2 term, unchanged)
+ *   gamma = 0: torch's F.cross_entropy(weight=w, label_smoothing=eps) exactly; eps = 0, gamma > 0: the weighted focal loss
+ *   (Lin et al. 2017) over the weight sum; o: the logit-adjusted loss (Menon et al. 2021).  The gradient written is the derivative of
+ *   L: with g = 1 / sum_i w[y_i], W = sum_c w_c and f = m + gamma p_t q^(gamma-1) nll,
+ *     dL/dz_c = g [ (1 - eps) w_t f (p_c - [c == t]) + (eps / K) (p_c W - w_c) ].
+ *   The kernel's fp32 scalars are (float)(1.0 - eps), (float)(eps / K), (float)gamma and W as the float of the double sum of the fp32
+ *   weights in class order (K without weights); q is sum_{c != t} e_c / sum_c e_c, so rows whose p_t rounds to 1 or to 0 give finite
+ *   losses and gradients.  Evaluation, calibration, mmc_trainer_logits and export read the raw logits: none of the three options.
+ * Allowed between passes.  Checked before anything changes: a NULL trainer, label_smoothing outside [0, 1), focal_gamma other than 0 or
+ *   [1, 8] (below 1, q^(gamma-1) is unbounded at saturated rows), a non-finite logit_prior entry (K floats in classes_ order, host, copied)
+ *   -> MMC_ERR_ARG, and the trainer is as it was.  (0, 0, NULL) restores the plain loss.
+ * Bits: all defaults run the kernel instantiation, and give the bits, of a trainer this was never called on; any other setting runs the
+ *   general instantiation, whose row sums have a fixed order (no atomics), so passes stay bit-reproducible, solo and grouped alike. */
+int mmc_trainer_set_loss(mmc_trainer* t, double label_smoothing, double focal_gamma, const float* logit_prior /* K or NULL */);
+/* The loss stage of a step on caller logits: logits n x K fp32 and y n class indices (host) -> dlogits n x K, the gradient of the
+ * data term above, and row_loss n, the per-row terms l_i g (host).  It launches the step's own kernel with the trainer's class
+ * weights and loss options and g = 1 / sum of w[y_i] over these n rows, as a step derives it -- for callers who bring their own
+ * logits, and for checking the loss stage per element.  Parameters, moments and step count are not touched.
+ * Checked before anything is launched: NULL arguments, n outside [1, 16384], a label outside [0, K), a zero total weight
+ * -> MMC_ERR_ARG.  Synchronises `hip_stream` before returning.  Same bits as the loss stage of a step on the same rows. */
+int mmc_trainer_loss_gradient(mmc_trainer* t, const float* logits, const int32_t* y, int64_t n, float* dlogits, float* row_loss,
+                              void* hip_stream);
 
 /* ---- evaluation and Platt calibration of the trained classifier ------------------------------------------------------
  * Replaces the host steps the reference's MermaidTrainer takes after partial_fit, all fed there by predict_proba:

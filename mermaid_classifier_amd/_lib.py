@@ -31,7 +31,7 @@ SYMBOLS = [
     "mmc_backbone_profile", "mmc_backbone_graph_stats", "mmc_crop_patches",
     "mmc_head_create", "mmc_head_destroy", "mmc_head_input_dim", "mmc_head_num_classes", "mmc_head_predict", "mmc_head_topk", "mmc_classify_patches",
     "mmc_trainer_create", "mmc_trainer_destroy", "mmc_trainer_partial_fit", "mmc_trainer_partial_fit_ordered", "mmc_trainer_get_params", "mmc_trainer_adam_state",
-    "mmc_trainer_logits", "mmc_trainer_evaluate", "mmc_trainer_evaluate_q32",
+    "mmc_trainer_logits", "mmc_trainer_evaluate", "mmc_trainer_evaluate_q32", "mmc_trainer_set_loss", "mmc_trainer_loss_gradient",
     "mmc_calibrator_create", "mmc_calibrator_destroy", "mmc_calibrator_add_features", "mmc_calibrator_add_scores", "mmc_calibrator_fit",
     "mmc_featureset_create", "mmc_featureset_destroy", "mmc_featureset_rows", "mmc_featureset_dim", "mmc_featureset_append", "mmc_featureset_read",
     "mmc_trainer_partial_fit_set", "mmc_trainer_group_partial_fit_set", "mmc_trainer_evaluate_set_q32", "mmc_calibrator_add_set",
@@ -124,6 +124,10 @@ def _load() -> C.CDLL:
     lib.mmc_trainer_adam_state.argtypes = [vp, i32, i32, C.POINTER(fp), C.POINTER(fp), C.POINTER(C.c_longlong)]
     lib.mmc_trainer_logits.restype = i32
     lib.mmc_trainer_logits.argtypes = [vp, vp, i64, vp, vp]
+    lib.mmc_trainer_set_loss.restype = i32
+    lib.mmc_trainer_set_loss.argtypes = [vp, f64, f64, fp]
+    lib.mmc_trainer_loss_gradient.restype = i32
+    lib.mmc_trainer_loss_gradient.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     lib.mmc_trainer_evaluate.restype = i32
     lib.mmc_trainer_evaluate.argtypes = [vp, vp, vp, i64, C.POINTER(i64), C.POINTER(f64), vp]
     lib.mmc_trainer_evaluate_q32.restype = i32

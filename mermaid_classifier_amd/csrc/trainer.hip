@@ -8,7 +8,8 @@
 //
 // One step on a resident mini-batch H0 [mb][d0]:
 //   forward   H(l+1) = relu(H(l) W(l)^T + b(l)), logits = H(L) without relu           gemm<TA=0,TB=1>, EPI_BIAS(_RELU)
-//   loss      per-row weighted CE, dZ(L) = w(y)/sum_w * (softmax - onehot)             ce_grad_kernel
+//   loss      per-row weighted CE, dZ(L) = w(y)/sum_w * (softmax - onehot)             ce_grad_kernel<false>
+//             or, per trainer: label smoothing, focal modulation, logit prior          ce_grad_kernel<true>  (mmc_trainer_set_loss)
 //   backward  dW(l) = dZ(l+1)^T H(l) + (alpha/mb) W(l)                                 gemm<TA=1,TB=0>, EPI_L2
 //             db(l) = column sums of dZ(l+1)                                           colsum_kernel
 //             dZ(l) = (dZ(l+1) W(l)) * (H(l) > 0)                                      gemm<TA=0,TB=0>, EPI_MASK
@@ -147,17 +148,94 @@ __global__ __launch_bounds__(256) void tgemm_f32_group_kernel(const GemmGroup g)
         tgemm_f32_tile<TA, TB, EPI1>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale);
 }
 
+// The loss formulation of a trainer (mmc_trainer_set_loss): the fp32 scalars of the general instantiation below, made from doubles
+// on the host as the other hyper-parameters are.  All defaults (no smoothing, no focusing, no prior) select the plain instantiation.
+struct CeLoss {
+    const float* prior;   // [K] offset added to the logits inside the loss only, or null
+    float om_eps;         // (float)(1.0 - label_smoothing)
+    float eps_k;          // (float)(label_smoothing / K)
+    float gamma;          // (float)focal_gamma: 0 or in [1, 8]
+    float w_total;        // sum of the class weights (K without class weights)
+};
+
+// a per-lane partial over the whole wave, the same value in every lane (commutative butterfly: a fixed order, no atomics)
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
 // One wave per row: log-softmax, weighted negative log-likelihood, gradient of the weighted-mean loss w.r.t. the logits.
-// F.cross_entropy(logits, y, weight=w) = sum_i w[y_i] * nll_i / sum_i w[y_i]   (torch_classifier.py:278)
+// GENERAL = false: F.cross_entropy(logits, y, weight=w) = sum_i w[y_i] * nll_i / sum_i w[y_i]   (torch_classifier.py:278)
+// GENERAL = true:  label smoothing, focal modulation and a logit prior (include/mmc.h, mmc_trainer_set_loss); with u = z + prior,
+//   t = y_i, p = softmax(u), q = 1 - p_t taken as sum_{c != t} e_c / sum_c e_c (no cancellation), pw = q^(gamma-1), m = pw q:
+//   l_i      = om_eps w_t m nll + eps_k sum_c w_c (-logp_c)
+//   dl_i/dz_c = om_eps w_t f (p_c - [c == t]) + eps_k (p_c w_total - w_c),   f = m + gamma p_t pw nll   (gamma = 0: m = f = 1)
+//   The two extra row sums are lane-strided sums and the butterfly of the softmax denominator.  Everything is finite on a finite
+//   row: q = 0 (p_t rounds to 1) gives m = 0 and pw in {0, 1}; p_t = 0 leaves f = m.
+template <bool GENERAL>
 __device__ __forceinline__ void ce_grad_rows(int block, const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
                                              const float* __restrict__ cw,   // [K] or null
-                                             float inv_wsum, float* __restrict__ dlogits, float* __restrict__ row_loss)
+                                             float inv_wsum, float* __restrict__ dlogits, float* __restrict__ row_loss, const CeLoss& ls)
 {
 #pragma clang fp contract(off)   // nothing here has ever been fused
     const int lane = threadIdx.x & 63;
     const int row = block * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const float* z = logits + (size_t)row * K;
+    if (GENERAL) {
+        const float* pr = ls.prior;
+        const int yi = y[row];
+        float mx = -INFINITY;
+        for (int c = lane; c < K; c += 64) mx = fmaxf(mx, pr ? z[c] + pr[c] : z[c]);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        float s = 0.f, so = 0.f;   // sum_c e_c; sum_{c != t} e_c
+        for (int c = lane; c < K; c += 64) {
+            const float e = expf((pr ? z[c] + pr[c] : z[c]) - mx);
+            s += e;
+            so += c == yi ? 0.f : e;
+        }
+        s = wave_sum(s);
+        so = wave_sum(so);
+        const float w = cw ? cw[yi] : 1.0f;
+        const float lse = logf(s);
+        const bool smooth = ls.eps_k != 0.f;
+        float sw = 0.f;            // sum_c w_c logp_c
+        if (smooth) {
+            for (int c = lane; c < K; c += 64) {
+                const float lp = (pr ? z[c] + pr[c] : z[c]) - mx - lse;
+                sw += cw ? cw[c] * lp : lp;
+            }
+            sw = wave_sum(sw);
+        }
+        const float ut = pr ? z[yi] + pr[yi] : z[yi];
+        const float nll = lse - (ut - mx);
+        float m = 1.0f, f = 1.0f;
+        if (ls.gamma != 0.f) {
+            const float q = so / s;
+            const float pt = expf(ut - mx - lse);
+            const float pw = powf(q, ls.gamma - 1.0f);
+            m = pw * q;
+            f = m + ls.gamma * pt * pw * nll;
+        }
+        const float a = ls.om_eps * w;
+        const float af = a * f;
+        for (int c = lane; c < K; c += 64) {
+            const float p = expf((pr ? z[c] + pr[c] : z[c]) - mx - lse);
+            float d = af * (p - (c == yi ? 1.0f : 0.0f));
+            if (smooth) d = d + ls.eps_k * (p * ls.w_total - (cw ? cw[c] : 1.0f));
+            dlogits[(size_t)row * K + c] = inv_wsum * d;
+        }
+        if (lane == 0) {
+            float l = a * m * nll;
+            if (smooth) l = l - ls.eps_k * sw;
+            row_loss[row] = l * inv_wsum;
+        }
+        return;
+    }
     float mx = -INFINITY;
     for (int c = lane; c < K; c += 64) mx = fmaxf(mx, z[c]);
 #pragma unroll
@@ -177,11 +255,12 @@ __device__ __forceinline__ void ce_grad_rows(int block, const float* __restrict_
     if (lane == 0) row_loss[row] = w * (lse - (z[yi] - mx)) * inv_wsum;
 }
 
+template <bool GENERAL>
 __global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
                                                       const float* __restrict__ cw, float inv_wsum, float* __restrict__ dlogits,
-                                                      float* __restrict__ row_loss)
+                                                      float* __restrict__ row_loss, const CeLoss ls)
 {
-    ce_grad_rows(blockIdx.x, logits, y, M, K, cw, inv_wsum, dlogits, row_loss);
+    ce_grad_rows<GENERAL>(blockIdx.x, logits, y, M, K, cw, inv_wsum, dlogits, row_loss, ls);
 }
 
 struct CeDesc {
@@ -191,6 +270,8 @@ struct CeDesc {
     float *dlogits, *row_loss;
     int M, K;
     float inv_wsum;
+    int general;   // which instantiation this member runs: a group may mix plain and general members
+    CeLoss loss;
 };
 struct CeGroup { CeDesc d[MMC_TRAINER_GROUP_MAX]; };
 
@@ -198,7 +279,10 @@ __global__ __launch_bounds__(256) void ce_grad_group_kernel(const CeGroup g)
 {
     const CeDesc& d = g.d[blockIdx.z];
     if ((int)blockIdx.x * 4 >= d.M) return;
-    ce_grad_rows(blockIdx.x, d.logits, d.y, d.M, d.K, d.cw, d.inv_wsum, d.dlogits, d.row_loss);
+    if (d.general)
+        ce_grad_rows<true>(blockIdx.x, d.logits, d.y, d.M, d.K, d.cw, d.inv_wsum, d.dlogits, d.row_loss, d.loss);
+    else
+        ce_grad_rows<false>(blockIdx.x, d.logits, d.y, d.M, d.K, d.cw, d.inv_wsum, d.dlogits, d.row_loss, d.loss);
 }
 
 // db[n] = sum_m dZ[m][n]; thread per column, rows in order (four chains)
@@ -432,7 +516,12 @@ struct mmc_trainer {
     double lr = 1e-3, beta1 = 0.9, beta2 = 0.999, eps = 1e-8, alpha = 1e-4;   // kept in double: torch derives its fp32 scalars from python floats
     long long t = 0;                                    // Adam step count
     std::vector<float> cw_host;
-    void* scratch = nullptr;                            // trainer_scratch (calib.hip's evaluation buffers)
+    // loss formulation (mmc_trainer_set_loss); all defaults = the plain weighted cross-entropy and its instantiation of the kernel
+    double label_smoothing = 0.0, focal_gamma = 0.0;
+    float* prior = nullptr;                             // logit prior [K] or null
+    bool general = false;
+    float w_total = 0.f;                                // the float of the double sum of the class weights in class order; K without
+    void* scratch = nullptr;                           // trainer_scratch (calib.hip's evaluation buffers)
     size_t scratch_bytes = 0;
 };
 
@@ -460,7 +549,7 @@ extern "C" void mmc_trainer_destroy(mmc_trainer* t)
     free_all(t->W); free_all(t->b); free_all(t->gW); free_all(t->gb); free_all(t->mW); free_all(t->vW); free_all(t->mb); free_all(t->vb);
     for (size_t l = 1; l < t->H.size(); ++l) hipFree(t->H[l]);
     for (size_t l = 1; l < t->dZ.size(); ++l) hipFree(t->dZ[l]);
-    hipFree(t->cw); hipFree(t->X); hipFree(t->row_loss); hipFree(t->partials); hipFree(t->losses); hipFree(t->y);
+    hipFree(t->cw); hipFree(t->prior); hipFree(t->X); hipFree(t->row_loss); hipFree(t->partials); hipFree(t->losses); hipFree(t->y);
     hipFree(t->Xn); hipFree(t->yn); hipFree(t->order); hipFree(t->visit); hipFree(t->scratch);
     delete t;
 }
@@ -506,6 +595,12 @@ extern "C" int mmc_trainer_create(const float* const* W, const float* const* b, 
              hipMemcpy(t->cw, class_weight, (size_t)K * 4, hipMemcpyHostToDevice) == hipSuccess;
         t->cw_host.assign(class_weight, class_weight + K);
     }
+    double wtot = (double)K;
+    if (class_weight) {
+        wtot = 0.0;
+        for (int c = 0; c < K; ++c) wtot += (double)class_weight[c];
+    }
+    t->w_total = (float)wtot;
     if (ok) ok = hipMalloc((void**)&t->partials, 256 * 4 * 16 + 256) == hipSuccess;
     if (!ok) {
         mmc_trainer_destroy(t);
@@ -514,6 +609,55 @@ extern "C" int mmc_trainer_create(const float* const* W, const float* const* b, 
     t->H.assign(n_layers + 1, nullptr);
     t->dZ.assign(n_layers + 1, nullptr);
     *out = t;
+    return MMC_OK;
+}
+
+// the kernel's fp32 scalars of the trainer's loss options, each the float of a double expression (include/mmc.h)
+static CeLoss trainer_ce_loss(const mmc_trainer* t)
+{
+    return CeLoss{t->prior, (float)(1.0 - t->label_smoothing), (float)(t->label_smoothing / (double)t->K), (float)t->focal_gamma, t->w_total};
+}
+
+// the loss stage of a step: which instantiation runs is a function of the trainer's options alone
+static void launch_ce_grad(const mmc_trainer* t, const float* logits, const int32_t* y, int mb, float inv_wsum, float* dlogits,
+                           float* row_loss, hipStream_t st)
+{
+    const CeLoss ls = trainer_ce_loss(t);
+    if (t->general)
+        hipLaunchKernelGGL(ce_grad_kernel<true>, dim3((mb + 3) / 4), dim3(256), 0, st, logits, y, mb, t->K, t->cw, inv_wsum, dlogits, row_loss, ls);
+    else
+        hipLaunchKernelGGL(ce_grad_kernel<false>, dim3((mb + 3) / 4), dim3(256), 0, st, logits, y, mb, t->K, t->cw, inv_wsum, dlogits, row_loss, ls);
+}
+
+extern "C" int mmc_trainer_set_loss(mmc_trainer* t, double label_smoothing, double focal_gamma, const float* logit_prior)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!(label_smoothing >= 0.0 && label_smoothing < 1.0))
+        return mmc_fail(MMC_ERR_ARG, "label_smoothing = %g outside [0, 1)", label_smoothing);
+    if (!(focal_gamma == 0.0 || (focal_gamma >= 1.0 && focal_gamma <= 8.0)))
+        return mmc_fail(MMC_ERR_ARG, "focal_gamma = %g is neither 0 nor in [1, 8]", focal_gamma);
+    if (logit_prior)
+        for (int c = 0; c < t->K; ++c)
+            if (!std::isfinite(logit_prior[c])) return mmc_fail(MMC_ERR_ARG, "logit_prior[%d] = %g is not finite", c, logit_prior[c]);
+    T_TRY(hipSetDevice(t->device));
+    // passes synchronise their stream before they return, so nothing in flight reads the prior that is replaced here
+    float* prior = nullptr;
+    if (logit_prior) {
+        if (hipMalloc((void**)&prior, (size_t)t->K * 4 + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the logit prior (%d classes)", t->K);
+        }
+        hipError_t e = hipMemcpy(prior, logit_prior, (size_t)t->K * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hipFree(prior);
+            return mmc_fail(MMC_ERR_HIP, "uploading the logit prior: %s", hipGetErrorString(e));
+        }
+    }
+    hipFree(t->prior);
+    t->prior = prior;
+    t->label_smoothing = label_smoothing;
+    t->focal_gamma = focal_gamma;
+    t->general = label_smoothing != 0.0 || focal_gamma != 0.0 || prior != nullptr;
     return MMC_OK;
 }
 
@@ -552,8 +696,7 @@ static int trainer_step(mmc_trainer* t, int64_t start, int mb, float inv_wsum, f
     for (int l = 0; l < L; ++l)
         T_K((launch_tgemm<false, true>(t->H[l], t->W[l], t->H[l + 1], mb, t->dims[l + 1], t->dims[l], l == L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU,
                                       t->b[l], 0.f, st)));
-    hipLaunchKernelGGL(ce_grad_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, t->H[L], t->y + start, mb, t->K, t->cw, inv_wsum, t->dZ[L],
-                       t->row_loss);
+    launch_ce_grad(t, t->H[L], t->y + start, mb, inv_wsum, t->dZ[L], t->row_loss, st);
     // regularised loss of this mini-batch (before the update): data + (0.5 alpha / mb) sum W^2
     for (int l = 0; l < L; ++l)
         hipLaunchKernelGGL(sumsq_kernel, dim3(256), dim3(256), 0, st, t->W[l], (size_t)t->dims[l + 1] * t->dims[l], t->partials + 256 * l);
@@ -846,7 +989,8 @@ int trainer_group_step(GroupMember* const* act, int cnt, const int64_t* off, con
         int mmax = 0;
         for (int i = 0; i < cnt; ++i) {
             const mmc_trainer* t = act[i]->t;
-            g.d[i] = CeDesc{t->H[t->L], t->y + off[i], t->cw, t->dZ[t->L], t->row_loss, act[i]->cur, t->K, act[i]->inv_wsum};
+            g.d[i] = CeDesc{t->H[t->L], t->y + off[i], t->cw, t->dZ[t->L], t->row_loss, act[i]->cur, t->K, act[i]->inv_wsum,
+                            t->general ? 1 : 0, trainer_ce_loss(t)};
             mmax = std::max(mmax, act[i]->cur);
         }
         hipLaunchKernelGGL(ce_grad_group_kernel, dim3((mmax + 3) / 4, 1, cnt), dim3(256), 0, st, g);
@@ -1082,5 +1226,36 @@ extern "C" int mmc_trainer_logits(mmc_trainer* t, const float* X, int64_t n, flo
         T_TRY(hipMemcpyAsync(logits + (size_t)off * t->K, z, (size_t)cur * t->K * 4, hipMemcpyDeviceToHost, st));
         T_TRY(hipStreamSynchronize(st));
     }
+    return MMC_OK;
+}
+
+// the loss stage of trainer_step on caller logits: the step's kernel, class weights, loss options and 1 / sum of w[y_i] (include/mmc.h)
+extern "C" int mmc_trainer_loss_gradient(mmc_trainer* t, const float* logits, const int32_t* y, int64_t n, float* dlogits, float* row_loss,
+                                         void* hip_stream)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!logits || !y || !dlogits || !row_loss) return mmc_fail(MMC_ERR_ARG, "logits / y / dlogits / row_loss is NULL");
+    if (n < 1 || n > kTrainerForwardRows) return mmc_fail(MMC_ERR_ARG, "n = %lld outside [1, %d]", (long long)n, kTrainerForwardRows);
+    double wsum = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (y[i] < 0 || y[i] >= t->K) return mmc_fail(MMC_ERR_ARG, "label index y[%lld] = %d outside [0, %d)", (long long)i, y[i], t->K);
+        wsum += t->cw ? (double)t->cw_host[y[i]] : 1.0;
+    }
+    if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "the rows have zero total class weight");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    T_TRY(hipSetDevice(t->device));
+    const int mb = (int)n, L = t->L;
+    int r = trainer_reserve(t, 0, mb, 1);   // the step's own logits / gradient / row-loss buffers
+    if (r) return r;
+    void* yd = nullptr;
+    if ((r = trainer_scratch(t, (size_t)mb * 4, &yd))) return r;
+    const size_t cells = (size_t)mb * t->K;
+    T_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
+    T_TRY(hipMemcpyAsync(yd, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
+    launch_ce_grad(t, t->H[L], static_cast<const int32_t*>(yd), mb, (float)(1.0 / wsum), t->dZ[L], t->row_loss, st);
+    T_TRY(hipGetLastError());
+    T_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
+    T_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
+    T_TRY(hipStreamSynchronize(st));
     return MMC_OK;
 }

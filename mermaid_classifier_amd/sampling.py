@@ -5,6 +5,7 @@ reference                                                      here
 =============================================================  ==========================================================
 ``compute_class_weights`` (``mermaid_classifier/training/      ``effective_number_weights(counts, beta, weight_ratio_cap)``
 sample_weighting/effective_number.py:38-75``)                  -> ``SweepConfig.class_weight``
+(none: Menon et al. 2021, logit adjustment)                    ``logit_adjustment(counts, tau)`` -> ``SweepConfig.logit_prior``
 ``compute_per_class_targets`` (``training/subsample/           ``subsample_targets(counts, strategy, total_annotations,
 registry.py:53-181``): ``stratified``, ``balanced``            min_per_class)``
 ``TrainingDataset._apply_subsample`` (``training/              ``subsample_rows(labels, targets, order)``: the first
@@ -25,7 +26,7 @@ import numpy as np
 
 from .featureset import FeatureSet
 
-__all__ = ["class_counts", "effective_number_weights", "subsample_targets", "subsample_rows", "row_batches", "STRATEGIES"]
+__all__ = ["class_counts", "effective_number_weights", "logit_adjustment", "subsample_targets", "subsample_rows", "row_batches", "STRATEGIES"]
 
 STRATEGIES = ("stratified", "balanced")
 
@@ -80,6 +81,22 @@ def effective_number_weights(counts: Mapping[Any, int], beta: float = 0.9999, we
             if weight > ceiling:
                 weights[label] = ceiling
     return weights
+
+
+def logit_adjustment(counts: Mapping[Any, int], tau: float = 1.0) -> Dict[Any, float]:
+    """The per-class offsets of the logit-adjusted loss (Menon et al. 2021): ``tau * log(n_c / N)`` with ``N`` the sum of the
+    counts -- ``SweepConfig.logit_prior`` / ``TorchMLPClassifier(logit_prior=)``, added to the logits inside the training loss only.
+    Takes the ``counts`` mapping of ``effective_number_weights``; no counterpart in the reference.  ``ValueError``: an empty mapping,
+    a count below 1 (its logarithm is not finite), a ``tau`` that is not finite."""
+    if not counts:
+        raise ValueError("counts is empty")
+    if not np.isfinite(tau):
+        raise ValueError(f"tau must be finite, got {tau!r}")
+    for label, count in counts.items():
+        if int(count) != count or count < 1:
+            raise ValueError(f"count for {label!r} must be an integer >= 1, got {count!r}")
+    total = sum(int(c) for c in counts.values())
+    return {label: float(tau) * float(np.log(int(count) / total)) for label, count in counts.items()}
 
 
 def subsample_targets(counts: Mapping[Any, int], strategy: str, total_annotations: int, min_per_class: int = 0) -> Dict[Any, int]:

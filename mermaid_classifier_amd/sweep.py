@@ -18,7 +18,8 @@ the worst way to spend it.  Here the S models advance together:
                             split (``validate`` / ``grouped_validate``), sorted by balanced accuracy, then macro f1.
 
 What a balancing configuration is made of comes from ``sampling.py``: ``effective_number_weights`` -> ``SweepConfig.class_weight``,
-``subsample_targets`` / ``subsample_rows`` / ``row_batches`` -> ``SweepConfig.batches``.  With ``class_scores=True`` every epoch's
+``subsample_targets`` / ``subsample_rows`` / ``row_batches`` -> ``SweepConfig.batches``, ``logit_adjustment`` ->
+``SweepConfig.logit_prior``.  With ``class_scores=True`` every epoch's
 callback dict carries the validation balanced accuracy and macro f1 next to the accuracy (``calibration.evaluate_classes``).
 
 Evaluation and calibration stay per model (``calibration.evaluate`` / ``evaluate_classes`` / ``calibrate``): they are forward-only
@@ -107,7 +108,8 @@ class SweepConfig:
     """One configuration of a sweep: the ``TorchMLPClassifier`` constructor arguments a sweep varies (the defaults are the
     production head's, trainer.py:118-123) and ``batches``, ``train_classifier``'s row-subset hook -- a callable
     ``epoch -> iterable of row-index arrays`` into the train set, e.g. a class-balancing subsample; None takes contiguous
-    slices of ``train_sweep``'s ``batch_size`` rows."""
+    slices of ``train_sweep``'s ``batch_size`` rows.  ``label_smoothing`` / ``focal_gamma`` / ``logit_prior`` are the classifier's loss
+    formulation (``mmc_trainer_set_loss``): the members of one grouped pass may each have their own."""
     hidden_layer_sizes: Tuple[int, ...] = (500, 300, 100)
     learning_rate_init: float = 1e-4
     alpha: float = 1e-4
@@ -118,13 +120,17 @@ class SweepConfig:
     beta_2: float = 0.999
     epsilon: float = 1e-8
     batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None
+    label_smoothing: float = 0.0
+    focal_gamma: float = 0.0
+    logit_prior: Optional[dict] = None
 
     def classifier(self, device=0) -> TorchMLPClassifier:
         """The untrained classifier of this configuration."""
         return TorchMLPClassifier(hidden_layer_sizes=tuple(self.hidden_layer_sizes), learning_rate_init=self.learning_rate_init,
                                   alpha=self.alpha, class_weight=self.class_weight, random_state=self.random_state,
                                   batch_size=self.batch_size, beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.epsilon,
-                                  device=device)
+                                  device=device, label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma,
+                                  logit_prior=self.logit_prior)
 
 
 def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[Any]]],

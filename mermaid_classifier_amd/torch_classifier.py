@@ -19,7 +19,9 @@ device), ``_create_trainer``, the device half of ``partial_fit`` (``mmc_trainer_
 logits call (``mmc_trainer_logits``), ``parameters`` / ``_module`` / ``_adam_state`` (state read back through the C ABI),
 ``__getstate__`` / ``__setstate__`` (the pickle carries host copies of weights and Adam moments), ``_release``,
 ``partial_fit_rows`` (``partial_fit`` over rows of a device-resident ``FeatureSet``: ``mmc_trainer_partial_fit_set``) and its
-two halves ``_begin_rows_pass`` / ``_end_pass``, which ``sweep.partial_fit_rows_group`` puts around one grouped call.
+two halves ``_begin_rows_pass`` / ``_end_pass``, which ``sweep.partial_fit_rows_group`` puts around one grouped call; and the loss
+formulation -- ``label_smoothing`` / ``focal_gamma`` / ``logit_prior``, ``_check_loss_scalars``, ``_build_logit_prior_vector``
+(``mmc_trainer_set_loss``) -- whose defaults are the reference's weighted cross-entropy.
 """
 
 from __future__ import annotations
@@ -42,8 +44,23 @@ def _ptr_array(arrays: List[np.ndarray]):
     return (fp * len(arrays))(*[a.ctypes.data_as(fp) for a in arrays])
 
 
+def _check_loss_scalars(label_smoothing, focal_gamma) -> None:
+    """The ranges ``mmc_trainer_set_loss`` accepts (include/mmc.h)."""
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing!r}.")
+    if isinstance(focal_gamma, bool) or not isinstance(focal_gamma, (int, float, np.integer, np.floating)) \
+            or not (float(focal_gamma) == 0.0 or 1.0 <= float(focal_gamma) <= 8.0):
+        raise ValueError(f"focal_gamma must be 0 or lie in [1, 8], got {focal_gamma!r}.")
+
+
 class TorchMLPClassifier:
-    """See the module docstring; argument meaning as in the reference (torch_classifier.py:93-135)."""
+    """See the module docstring; argument meaning as in the reference (torch_classifier.py:93-135).  Three arguments have no
+    counterpart there, the loss formulation of ``mmc_trainer_set_loss`` (include/mmc.h): ``label_smoothing`` in [0, 1) with
+    ``F.cross_entropy(label_smoothing=)``'s meaning, ``focal_gamma`` (0, or in [1, 8]: focal loss) and ``logit_prior``, a dict from
+    label to a finite offset added to the logits inside the loss only (``sampling.logit_adjustment``); like ``class_weight`` it is
+    resolved in ``classes_`` order at the first fit.  Training alone reads them: ``predict_proba``, evaluation, calibration and
+    export see the raw logits.  The defaults train with the plain loss, bit for bit."""
 
     _estimator_type = "classifier"
 
@@ -51,11 +68,13 @@ class TorchMLPClassifier:
                  alpha: float = 0.0001, batch_size: int | str = "auto", learning_rate_init: float = 0.001,
                  max_iter: int = 200, shuffle: bool = True, random_state: int | None = None, tol: float = 1e-4,
                  beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-8,
-                 class_weight: dict | None = None, device=0):
+                 class_weight: dict | None = None, device=0, *, label_smoothing: float = 0.0, focal_gamma: float = 0.0,
+                 logit_prior: dict | None = None):
         if activation != "relu":
             raise ValueError(f"TorchMLPClassifier only supports activation='relu', got {activation!r}.")
         if solver != "adam":
             raise ValueError(f"TorchMLPClassifier only supports solver='adam', got {solver!r}.")
+        _check_loss_scalars(label_smoothing, focal_gamma)
         self.hidden_layer_sizes = tuple(hidden_layer_sizes)
         self.activation = activation
         self.solver = solver
@@ -71,6 +90,9 @@ class TorchMLPClassifier:
         self.epsilon = epsilon
         self.class_weight = class_weight
         self.device = device
+        self.label_smoothing = label_smoothing
+        self.focal_gamma = focal_gamma
+        self.logit_prior = logit_prior
 
     # ---- host bookkeeping, restated from the reference ------------------------------------------------------------
     def _resolve_batch_size(self, n_samples: int) -> int:
@@ -109,6 +131,21 @@ class TorchMLPClassifier:
             weights.append(w)
         return np.asarray(weights, dtype=np.float32)
 
+    def _build_logit_prior_vector(self):
+        """``logit_prior`` in ``classes_`` order as float32, or None."""
+        prior = getattr(self, "logit_prior", None)
+        if prior is None:
+            return None
+        missing = [cls for cls in self.classes_.tolist() if cls not in prior]
+        if missing:
+            raise ValueError(f"logit_prior is missing offsets for {sorted(missing)!r}. Pass an offset for every class in classes_.")
+        with np.errstate(over="ignore"):   # an offset beyond float32 becomes inf and is reported below
+            vec = np.asarray([float(prior[cls]) for cls in self.classes_.tolist()], dtype=np.float64).astype(np.float32)
+        if not np.isfinite(vec).all():
+            bad = [cls for cls, v in zip(self.classes_.tolist(), vec) if not np.isfinite(v)]
+            raise ValueError(f"logit_prior for {bad!r} is not finite.")
+        return vec
+
     def _initial_parameters(self):
         """Glorot-uniform weights / zero biases drawn exactly as the reference's ``_MLPModule`` draws them
         (torch_classifier.py:53-76, 176-184): the Linear layers are constructed first (their default init consumes the
@@ -136,6 +173,14 @@ class TorchMLPClassifier:
                                           float(self.epsilon), float(self.alpha),
                                           cw.ctypes.data_as(C.POINTER(C.c_float)) if cw is not None else None,
                                           _device_index(self.device), C.byref(self._h)))
+        # the loss options are read here, like every other hyper-parameter; all defaults select the plain loss
+        prior = getattr(self, "_logit_prior_vector", None)
+        try:
+            _lib.check(lib.mmc_trainer_set_loss(self._h, float(self.label_smoothing), float(self.focal_gamma),
+                                                prior.ctypes.data_as(C.POINTER(C.c_float)) if prior is not None else None))
+        except Exception:
+            self._release()
+            raise
 
     def _fitted(self) -> bool:
         return getattr(self, "_h", None) is not None and bool(self._h.value)
@@ -151,6 +196,7 @@ class TorchMLPClassifier:
             self.n_iter_ = 0
             self.loss_curve_ = []
             self._class_weight_vector = self._build_class_weight_vector()
+            self._logit_prior_vector = self._build_logit_prior_vector()
             self._create_trainer(*self._initial_parameters())
         elif X_arr.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {X_arr.shape[1]} features, expected {self.n_features_in_}")
@@ -216,6 +262,7 @@ class TorchMLPClassifier:
             self.n_iter_ = 0
             self.loss_curve_ = []
             self._class_weight_vector = self._build_class_weight_vector()
+            self._logit_prior_vector = self._build_logit_prior_vector()
             self._create_trainer(*self._initial_parameters())
         else:
             fs._check_against(self)
@@ -337,7 +384,8 @@ class TorchMLPClassifier:
                 "alpha": self.alpha, "batch_size": self.batch_size, "learning_rate_init": self.learning_rate_init,
                 "max_iter": self.max_iter, "shuffle": self.shuffle, "random_state": self.random_state, "tol": self.tol,
                 "beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon,
-                "class_weight": getattr(self, "class_weight", None)}
+                "class_weight": getattr(self, "class_weight", None), "label_smoothing": self.label_smoothing,
+                "focal_gamma": self.focal_gamma, "logit_prior": self.logit_prior}
 
     def set_params(self, **params: Any) -> "TorchMLPClassifier":
         for key, value in params.items():
@@ -358,6 +406,9 @@ class TorchMLPClassifier:
         params = state.pop("_module_state", None)
         opt = state.pop("_optimizer_state", None)
         self.__dict__.update(state)
+        # a pickle made before the loss options existed loads as the plain loss
+        for key, default in (("label_smoothing", 0.0), ("focal_gamma", 0.0), ("logit_prior", None), ("_logit_prior_vector", None)):
+            self.__dict__.setdefault(key, default)
         self._h = None
         if params is not None:
             self._create_trainer(*params)

@@ -8,6 +8,9 @@ turn, five times each; median and spread (min .. max) per route.  S in 1, 4, 8, 
 
 --solo-only: the solo leg alone.  It needs nothing this script's commit added to the library, so it runs on an older checkout
 too: that is how the solo figure is checked to be the earlier code's.
+--loss KIND: the members' loss formulation (mmc_trainer_set_loss): plain (the default: no option is passed, so the leg runs on a
+checkout from before the options too), smooth (label smoothing 0.1), focal (gamma 2), prior (0.7 log of a Dirichlet draw), all
+(the three together), mixed (member m takes plain, smooth, focal, prior, all in turn: one group launch runs both instantiations).
 --rows N / --sizes 1,4: smaller runs."""
 import argparse
 import ctypes as C
@@ -27,6 +30,7 @@ ap.add_argument("--solo-only", action="store_true")
 ap.add_argument("--rows", type=int, default=200000)
 ap.add_argument("--sizes", default="1,4,8,16")
 ap.add_argument("--repeats", type=int, default=5)
+ap.add_argument("--loss", choices=["plain", "smooth", "focal", "prior", "all", "mixed"], default="plain")
 args = ap.parse_args()
 sizes = [int(s) for s in args.sizes.split(",")]
 k, nf, n, mb = 108, 1280, args.rows, 200
@@ -37,11 +41,17 @@ X = np.abs(rng.standard_normal((n, nf), dtype=np.float32) * np.float32(0.4) + np
 fs = FeatureSet(nf, np.arange(k), reserve=n).append(X, yi)
 del X
 lib = _lib.lib()
+prior = (0.7 * np.log(np.random.default_rng(1).dirichlet(np.ones(k)))).astype(np.float32)
+LOSSES = {"plain": {}, "smooth": {"label_smoothing": 0.1}, "focal": {"focal_gamma": 2.0}, "prior": {},
+          "all": {"label_smoothing": 0.1, "focal_gamma": 2.0}}
 members = []
 for m in range(max(sizes)):
-    clf = TorchMLPClassifier(hidden_layer_sizes=(500, 300, 100), learning_rate_init=1e-4, random_state=m)
+    kind = list(LOSSES)[m % len(LOSSES)] if args.loss == "mixed" else args.loss
+    clf = TorchMLPClassifier(hidden_layer_sizes=(500, 300, 100), learning_rate_init=1e-4, random_state=m, **LOSSES[kind])
     clf.classes_, clf.n_features_in_, clf.n_iter_, clf.loss_curve_ = np.arange(k), nf, 0, []
     clf._class_weight_vector = None
+    if kind in ("prior", "all"):
+        clf._logit_prior_vector = prior
     clf._create_trainer(*clf._initial_parameters())
     members.append((clf, np.ascontiguousarray(np.random.default_rng(m).permutation(n).astype(np.int64))))
 
@@ -67,6 +77,7 @@ def stats(ms):
 
 steps = -(-n // mb)
 print(f"{n} resident rows x {nf}, {k} classes, 1280 -> 500 -> 300 -> 100 -> {k}, mini-batches of {mb}: {steps} Adam steps per model and pass")
+print(f"loss formulation of the members: {args.loss}")
 print(f"host clock around calls that end in a stream synchronise; one warm-up per shape, then the routes in turn, {args.repeats} times each; "
       "median (min .. max) in ms")
 routes = [("solo", solo)] if args.solo_only else [("solo", solo), ("group", group)]
