@@ -312,8 +312,8 @@ int mmc_trainer_partial_fit_set(mmc_trainer* t, mmc_featureset* fs, const int64_
  *   head is some 30 small launches that leave most of the device idle; here step s of the pass is issued once for every member that
  *   still has a step s, each kind of launch once with the member as a grid dimension, on `hip_stream` alone.
  * For every member m the call does what mmc_trainer_partial_fit_set(trainers[m], fs, visit[m], n[m], batch_size[m], &avg_loss[m],
- *   hip_stream) does: same parameters, Adam moments, step count and avg_loss[m], bit for bit (each member's arithmetic and every
- *   reduction's decomposition are the solo kernels'), independent of MMC_TRAIN_CHUNK_ROWS.  The members stay ordinary trainers: every
+ *   hip_stream) does: same parameters, Adam moments, step count and avg_loss[m], bit for bit (that call is this one with a single
+ *   member: the same kernels, and no reduction's decomposition depends on the group), independent of MMC_TRAIN_CHUNK_ROWS.  The members stay ordinary trainers: every
  *   other mmc_trainer_* / mmc_calibrator_* call and later solo passes work on them unchanged.
  * Members may differ in depth, widths, optimizer hyper-parameters, class weights, step count so far, n, visiting order and mini-batch
  *   size (so they finish at different steps); they share dims[0], the class count and the device with the set.

@@ -7,13 +7,18 @@
 // (v_mfma_f32_16x16x4_f32); every reduction runs in a fixed order (no atomics), so a run is bit-reproducible.
 //
 // One step on a resident mini-batch H0 [mb][d0]:
-//   forward   H(l+1) = relu(H(l) W(l)^T + b(l)), logits = H(L) without relu           gemm<TA=0,TB=1>, EPI_BIAS(_RELU)
-//   loss      per-row weighted CE, dZ(L) = w(y)/sum_w * (softmax - onehot)             ce_grad_kernel<false>
-//             or, per trainer: label smoothing, focal modulation, logit prior          ce_grad_kernel<true>  (mmc_trainer_set_loss)
-//   backward  dW(l) = dZ(l+1)^T H(l) + (alpha/mb) W(l)                                 gemm<TA=1,TB=0>, EPI_L2
+//   forward   H(l+1) = relu(H(l) W(l)^T + b(l)), logits = H(L) without relu           tgemm_f32_kernel<TA=0,TB=1>, EPI_BIAS(_RELU)
+//   loss      per-row weighted CE, dZ(L) = w(y)/sum_w * (softmax - onehot)             ce_grad_kernel, ce_grad_rows<false>
+//             or, per trainer: label smoothing, focal modulation, logit prior          ce_grad_kernel, ce_grad_rows<true>  (mmc_trainer_set_loss)
+//   backward  dW(l) = dZ(l+1)^T H(l) + (alpha/mb) W(l)                                 tgemm_f32_kernel<TA=1,TB=0>, EPI_L2
 //             db(l) = column sums of dZ(l+1)                                           colsum_kernel
-//             dZ(l) = (dZ(l+1) W(l)) * (H(l) > 0)                                      gemm<TA=0,TB=0>, EPI_MASK
+//             dZ(l) = (dZ(l+1) W(l)) * (H(l) > 0)                                      tgemm_f32_kernel<TA=0,TB=0>, EPI_MASK
 //   update    Adam exactly in torch's order of operations (lerp, addcmul, addcdiv)     adam_kernel
+//
+// Every step is the step of a group of trainers (trainer_group_step): each kind of launch once, one member per blockIdx.z, the
+// member's operands in a by-value descriptor array.  A trainer on its own -- the host-fed pass, mmc_trainer_partial_fit_set, the
+// eval-mode forward, mmc_trainer_loss_gradient -- is a group of one, so there is one compiled copy of every kernel body and a
+// member of a sweep computes the bits it computes alone because it runs the same code.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -35,13 +40,11 @@ enum { TEPI_NONE = 0, TEPI_BIAS_RELU = 1, TEPI_BIAS = 2, TEPI_MASK = 3, TEPI_L2 
 // 64x64 output tile per 256-thread workgroup, K in steps of 16 through LDS (k-major tiles, so every transpose flavour is
 // index arithmetic at staging time); wave w owns the 32x32 quadrant (w>>1, w&1) as 2x2 MFMA fragments.
 //
-// Every kernel of a step is a __device__ body called from two __global__ kernels: the solo one (one trainer per launch) and the
-// grouped one (mmc_trainer_group_partial_fit_set: a member of the group per blockIdx.z, its operands in a by-value descriptor).  Both
-// inline the same body with the same template arguments, so a member's arithmetic -- and every bit it produces -- is the solo one's.
-// LDS is declared by the kernel and handed in, so a grouped kernel that switches between two epilogues holds one pair of tiles.
-// Which multiply-add pairs are fused is part of the arithmetic, and the compiler does not decide it alike for two callers of one body
-// (left alone it fused v * beta2 + ... of adam_elems in the grouped kernel only).  So the bodies compile with contraction off and
-// spell out the fusions the solo kernels have always had: fmaf where they fuse, plain operators where they round twice.
+// Every kernel of a step is a __device__ body with one __global__ caller, which picks its member's descriptor by blockIdx.z.
+// LDS is declared by the kernel and handed in, so a kernel that switches between two epilogues holds one pair of tiles.
+// Which multiply-add pairs are fused is part of the arithmetic, and the compiler does not decide it alike for every caller of a body
+// (left alone it once fused v * beta2 + ... of adam_elems in one of two callers only).  So the bodies compile with contraction off
+// and spell out the fusions these kernels have always had: fmaf where they fuse, plain operators where they round twice.
 template <bool TA, bool TB, int EPI>
 __device__ __forceinline__ void tgemm_f32_tile(float (&As)[16][68], float (&Bs)[16][68], int tile_m, int tile_n,
                                                const float* __restrict__ A, const float* __restrict__ B,
@@ -113,17 +116,7 @@ __device__ __forceinline__ void tgemm_f32_tile(float (&As)[16][68], float (&Bs)[
             }
 }
 
-template <bool TA, bool TB, int EPI>
-__global__ __launch_bounds__(256) void tgemm_f32_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                                                        float* __restrict__ C, int M, int N, int K, const float* __restrict__ aux,
-                                                        float scale)
-{
-    __shared__ float As[16][68];
-    __shared__ float Bs[16][68];
-    tgemm_f32_tile<TA, TB, EPI>(As, Bs, blockIdx.x, blockIdx.y, A, B, C, M, N, K, aux, scale);
-}
-
-// ---- grouped forms: one member per blockIdx.z; the grid is the largest member's and a workgroup outside its own member's extent
+// ---- the kernels: one member per blockIdx.z; the grid is the largest member's and a workgroup outside its own member's extent
 // leaves before its first barrier (the test reads kernel arguments and block indices only: block-uniform).
 struct GemmDesc {
     const float *A, *B;
@@ -136,7 +129,7 @@ struct GemmGroup { GemmDesc d[MMC_TRAINER_GROUP_MAX]; };
 
 // EPI0 / EPI1: the epilogues the members of one launch can have (forward: hidden layer or a member's last; otherwise one kind)
 template <bool TA, bool TB, int EPI0, int EPI1>
-__global__ __launch_bounds__(256) void tgemm_f32_group_kernel(const GemmGroup g)
+__global__ __launch_bounds__(256) void tgemm_f32_kernel(const GemmGroup g)
 {
     __shared__ float As[16][68];
     __shared__ float Bs[16][68];
@@ -255,14 +248,6 @@ __device__ __forceinline__ void ce_grad_rows(int block, const float* __restrict_
     if (lane == 0) row_loss[row] = w * (lse - (z[yi] - mx)) * inv_wsum;
 }
 
-template <bool GENERAL>
-__global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
-                                                      const float* __restrict__ cw, float inv_wsum, float* __restrict__ dlogits,
-                                                      float* __restrict__ row_loss, const CeLoss ls)
-{
-    ce_grad_rows<GENERAL>(blockIdx.x, logits, y, M, K, cw, inv_wsum, dlogits, row_loss, ls);
-}
-
 struct CeDesc {
     const float* logits;
     const int32_t* y;
@@ -275,7 +260,7 @@ struct CeDesc {
 };
 struct CeGroup { CeDesc d[MMC_TRAINER_GROUP_MAX]; };
 
-__global__ __launch_bounds__(256) void ce_grad_group_kernel(const CeGroup g)
+__global__ __launch_bounds__(256) void ce_grad_kernel(const CeGroup g)
 {
     const CeDesc& d = g.d[blockIdx.z];
     if ((int)blockIdx.x * 4 >= d.M) return;
@@ -302,11 +287,6 @@ __device__ __forceinline__ void colsum_cols(int block, const float* __restrict__
     db[n] = (s0 + s1) + (s2 + s3);
 }
 
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ dZ, int M, int N, float* __restrict__ db)
-{
-    colsum_cols(blockIdx.x, dZ, M, N, db);
-}
-
 struct ColsumDesc {
     const float* dZ;
     float* db;
@@ -314,7 +294,7 @@ struct ColsumDesc {
 };
 struct ColsumGroup { ColsumDesc d[MMC_TRAINER_GROUP_MAX]; };
 
-__global__ __launch_bounds__(256) void colsum_group_kernel(const ColsumGroup g)
+__global__ __launch_bounds__(256) void colsum_kernel(const ColsumGroup g)
 {
     const ColsumDesc& d = g.d[blockIdx.z];
     if ((int)blockIdx.x * 256 >= d.N) return;
@@ -336,12 +316,6 @@ __device__ __forceinline__ void sumsq_slice(float (&red)[256], const float* __re
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, size_t n, float* __restrict__ partial)
-{
-    __shared__ float red[256];
-    sumsq_slice(red, x, n, partial);
-}
-
 struct SumsqDesc {
     const float* x;
     float* partial;
@@ -349,8 +323,8 @@ struct SumsqDesc {
 };
 struct SumsqGroup { SumsqDesc d[MMC_TRAINER_GROUP_MAX]; };
 
-// gridDim.x is the solo launch's 256 blocks, so a member's slices and partials are the solo ones
-__global__ __launch_bounds__(256) void sumsq_group_kernel(const SumsqGroup g)
+// gridDim.x is 256 blocks whatever the group, so a member's slices and partials do not depend on who trains beside it
+__global__ __launch_bounds__(256) void sumsq_kernel(const SumsqGroup g)
 {
     __shared__ float red[256];
     const SumsqDesc& d = g.d[blockIdx.z];
@@ -374,13 +348,6 @@ __device__ __forceinline__ void loss_finalize_one(float (&red)[256], const float
     if (threadIdx.x == 0) loss_out[0] = red[0];
 }
 
-__global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ row_loss, int M, const float* __restrict__ partials,
-                                                            int P, float reg_scale, float* __restrict__ loss_out)
-{
-    __shared__ float red[256];
-    loss_finalize_one(red, row_loss, M, partials, P, reg_scale, loss_out);
-}
-
 struct LossDesc {
     const float *row_loss, *partials;
     float* loss_out;
@@ -389,7 +356,7 @@ struct LossDesc {
 };
 struct LossGroup { LossDesc d[MMC_TRAINER_GROUP_MAX]; };
 
-__global__ __launch_bounds__(256) void loss_finalize_group_kernel(const LossGroup g)
+__global__ __launch_bounds__(256) void loss_finalize_kernel(const LossGroup g)
 {
     __shared__ float red[256];
     const LossDesc& d = g.d[blockIdx.z];
@@ -416,13 +383,6 @@ __device__ __forceinline__ void adam_elems(float* __restrict__ p, const float* _
     p[i] = fmaf(-step_size, mi / denom, p[i]);
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, size_t n, float om_beta1, float beta2, float om_beta2, float eps,
-                                                   float step_size, float bc2_sqrt)
-{
-    adam_elems(p, g, m, v, n, om_beta1, beta2, om_beta2, eps, step_size, bc2_sqrt);
-}
-
 struct AdamDesc {
     float* p;
     const float* g;
@@ -432,7 +392,7 @@ struct AdamDesc {
 };
 struct AdamGroup { AdamDesc d[MMC_TRAINER_GROUP_MAX]; };
 
-__global__ __launch_bounds__(256) void adam_group_kernel(const AdamGroup g)
+__global__ __launch_bounds__(256) void adam_kernel(const AdamGroup g)
 {
     const AdamDesc& d = g.d[blockIdx.z];
     adam_elems(d.p, d.g, d.m, d.v, d.n, d.om_beta1, d.beta2, d.om_beta2, d.eps, d.step_size, d.bc2_sqrt);
@@ -474,23 +434,6 @@ __global__ __launch_bounds__(256) void gather_set_rows_kernel(const float* __res
         for (int k = lane; k < dim; k += 64) d[k] = s[k];
     }
     if (lane == 0) yo[i] = ys[src];
-}
-
-template <bool TA, bool TB>
-int launch_tgemm(const float* A, const float* B, float* C, int M, int N, int K, int epi, const float* aux, float scale, hipStream_t st)
-{
-    dim3 grid((M + 63) / 64, (N + 63) / 64);
-#define GO(E) hipLaunchKernelGGL((tgemm_f32_kernel<TA, TB, E>), grid, dim3(256), 0, st, A, B, C, M, N, K, aux, scale)
-    switch (epi) {
-        case TEPI_NONE: GO(TEPI_NONE); break;
-        case TEPI_BIAS_RELU: GO(TEPI_BIAS_RELU); break;
-        case TEPI_BIAS: GO(TEPI_BIAS); break;
-        case TEPI_MASK: GO(TEPI_MASK); break;
-        case TEPI_L2: GO(TEPI_L2); break;
-        default: return -1;
-    }
-#undef GO
-    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -618,17 +561,6 @@ static CeLoss trainer_ce_loss(const mmc_trainer* t)
     return CeLoss{t->prior, (float)(1.0 - t->label_smoothing), (float)(t->label_smoothing / (double)t->K), (float)t->focal_gamma, t->w_total};
 }
 
-// the loss stage of a step: which instantiation runs is a function of the trainer's options alone
-static void launch_ce_grad(const mmc_trainer* t, const float* logits, const int32_t* y, int mb, float inv_wsum, float* dlogits,
-                           float* row_loss, hipStream_t st)
-{
-    const CeLoss ls = trainer_ce_loss(t);
-    if (t->general)
-        hipLaunchKernelGGL(ce_grad_kernel<true>, dim3((mb + 3) / 4), dim3(256), 0, st, logits, y, mb, t->K, t->cw, inv_wsum, dlogits, row_loss, ls);
-    else
-        hipLaunchKernelGGL(ce_grad_kernel<false>, dim3((mb + 3) / 4), dim3(256), 0, st, logits, y, mb, t->K, t->cw, inv_wsum, dlogits, row_loss, ls);
-}
-
 extern "C" int mmc_trainer_set_loss(mmc_trainer* t, double label_smoothing, double focal_gamma, const float* logit_prior)
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
@@ -688,41 +620,167 @@ static int trainer_reserve(mmc_trainer* t, int64_t n, int mb, int steps)
     return 0;
 }
 
-// one optimizer step on rows [start, start+mb) of the resident X / y
-static int trainer_step(mmc_trainer* t, int64_t start, int mb, float inv_wsum, float* loss_slot, hipStream_t st)
+// ---- the step ------------------------------------------------------------------------------------------------------------
+namespace {
+
+// one trainer's part in a step: its mini-batch is rows [off, off + cur) of its staging X / y, its loss goes to losses[slot]
+struct StepMember {
+    mmc_trainer* t;
+    int64_t off;
+    int cur;
+    float inv_wsum;   // 1 / sum of the mini-batch's class weights
+    int slot;
+};
+
+template <bool TA, bool TB, int EPI0, int EPI1>
+int launch_tgemm(const GemmGroup& g, int cnt, hipStream_t st)
 {
-    const int L = t->L;
-    t->H[0] = t->X + (size_t)start * t->dims[0];
-    for (int l = 0; l < L; ++l)
-        T_K((launch_tgemm<false, true>(t->H[l], t->W[l], t->H[l + 1], mb, t->dims[l + 1], t->dims[l], l == L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU,
-                                      t->b[l], 0.f, st)));
-    launch_ce_grad(t, t->H[L], t->y + start, mb, inv_wsum, t->dZ[L], t->row_loss, st);
-    // regularised loss of this mini-batch (before the update): data + (0.5 alpha / mb) sum W^2
-    for (int l = 0; l < L; ++l)
-        hipLaunchKernelGGL(sumsq_kernel, dim3(256), dim3(256), 0, st, t->W[l], (size_t)t->dims[l + 1] * t->dims[l], t->partials + 256 * l);
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, t->row_loss, mb, t->partials, 256 * L, (float)(0.5 * t->alpha / (double)mb),
-                       loss_slot);
-    for (int l = L - 1; l >= 0; --l) {
-        const int no = t->dims[l + 1], ni = t->dims[l];
-        T_K((launch_tgemm<true, false>(t->dZ[l + 1], t->H[l], t->gW[l], no, ni, mb, TEPI_L2, t->W[l], (float)(t->alpha / (double)mb), st)));
-        hipLaunchKernelGGL(colsum_kernel, dim3((no + 255) / 256), dim3(256), 0, st, t->dZ[l + 1], mb, no, t->gb[l]);
-        if (l > 0) T_K((launch_tgemm<false, false>(t->dZ[l + 1], t->W[l], t->dZ[l], mb, ni, no, TEPI_MASK, t->H[l], 0.f, st)));
+    int tm = 0, tn = 0;
+    for (int i = 0; i < cnt; ++i) {
+        tm = std::max(tm, (g.d[i].M + 63) / 64);
+        tn = std::max(tn, (g.d[i].N + 63) / 64);
     }
-    ++t->t;
-    const double bc1 = 1.0 - std::pow(t->beta1, (double)t->t), bc2 = 1.0 - std::pow(t->beta2, (double)t->t);
-    const float step_size = (float)(t->lr / bc1), bc2_sqrt = (float)std::sqrt(bc2);
-    const float om1 = (float)(1.0 - t->beta1), om2 = (float)(1.0 - t->beta2), b2f = (float)t->beta2, epsf = (float)t->eps;
-    for (int l = 0; l < L; ++l) {
-        const size_t nw = (size_t)t->dims[l + 1] * t->dims[l], nb = (size_t)t->dims[l + 1];
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, t->W[l], t->gW[l], t->mW[l], t->vW[l], nw,
-                           om1, b2f, om2, epsf, step_size, bc2_sqrt);
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, t->b[l], t->gb[l], t->mb[l], t->vb[l], nb,
-                           om1, b2f, om2, epsf, step_size, bc2_sqrt);
+    hipLaunchKernelGGL((tgemm_f32_kernel<TA, TB, EPI0, EPI1>), dim3(tm, tn, cnt), dim3(256), 0, st, g);
+    return (int)hipGetLastError();
+}
+
+// layer l of the forward on mb rows of t->H[l]
+GemmDesc forward_desc(const mmc_trainer* t, int l, int mb)
+{
+    return GemmDesc{t->H[l], t->W[l], t->H[l + 1], t->b[l], mb, t->dims[l + 1], t->dims[l], l == t->L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU, 0.f};
+}
+
+// the loss stage on mb rows of logits: which instantiation runs is a function of the trainer's options alone
+CeDesc ce_desc(const mmc_trainer* t, const float* logits, const int32_t* y, int mb, float inv_wsum)
+{
+    return CeDesc{logits, y, t->cw, t->dZ[t->L], t->row_loss, mb, t->K, inv_wsum, t->general ? 1 : 0, trainer_ce_loss(t)};
+}
+
+// One optimizer step of every member in `act`: each kind of launch once, the member as blockIdx.z.  A member takes part in the
+// launches of the layers it has, in the order forward, loss, regularised loss, backward from the last layer, Adam.
+int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
+{
+    int Lmax = 0;
+    for (int i = 0; i < cnt; ++i) {
+        mmc_trainer* t = act[i].t;
+        t->H[0] = t->X + (size_t)act[i].off * t->dims[0];
+        Lmax = std::max(Lmax, t->L);
+    }
+    for (int l = 0; l < Lmax; ++l) {
+        GemmGroup g;
+        int k = 0;
+        for (int i = 0; i < cnt; ++i)
+            if (l < act[i].t->L) g.d[k++] = forward_desc(act[i].t, l, act[i].cur);
+        T_K((launch_tgemm<false, true, TEPI_BIAS_RELU, TEPI_BIAS>(g, k, st)));
+    }
+    {
+        CeGroup g;
+        int mmax = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i].t;
+            g.d[i] = ce_desc(t, t->H[t->L], t->y + act[i].off, act[i].cur, act[i].inv_wsum);
+            mmax = std::max(mmax, act[i].cur);
+        }
+        hipLaunchKernelGGL(ce_grad_kernel, dim3((mmax + 3) / 4, 1, cnt), dim3(256), 0, st, g);
+    }
+    // regularised loss of this mini-batch (before the update): data + (0.5 alpha / mb) sum W^2
+    for (int l = 0; l < Lmax; ++l) {
+        SumsqGroup g;
+        int k = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i].t;
+            if (l < t->L) g.d[k++] = SumsqDesc{t->W[l], t->partials + 256 * l, (size_t)t->dims[l + 1] * t->dims[l]};
+        }
+        hipLaunchKernelGGL(sumsq_kernel, dim3(256, 1, k), dim3(256), 0, st, g);
+    }
+    {
+        LossGroup g;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i].t;
+            g.d[i] = LossDesc{t->row_loss, t->partials, t->losses + act[i].slot, act[i].cur, 256 * t->L,
+                              (float)(0.5 * t->alpha / (double)act[i].cur)};
+        }
+        hipLaunchKernelGGL(loss_finalize_kernel, dim3(1, 1, cnt), dim3(256), 0, st, g);
+    }
+    for (int l = Lmax - 1; l >= 0; --l) {
+        GemmGroup gw, gz;
+        ColsumGroup gc;
+        int k = 0, kz = 0, nmax = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i].t;
+            if (l >= t->L) continue;
+            const int no = t->dims[l + 1], ni = t->dims[l], mb = act[i].cur;
+            gw.d[k] = GemmDesc{t->dZ[l + 1], t->H[l], t->gW[l], t->W[l], no, ni, mb, TEPI_L2, (float)(t->alpha / (double)mb)};
+            gc.d[k] = ColsumDesc{t->dZ[l + 1], t->gb[l], mb, no};
+            ++k;
+            nmax = std::max(nmax, no);
+            if (l > 0) gz.d[kz++] = GemmDesc{t->dZ[l + 1], t->W[l], t->dZ[l], t->H[l], mb, ni, no, TEPI_MASK, 0.f};
+        }
+        T_K((launch_tgemm<true, false, TEPI_L2, TEPI_L2>(gw, k, st)));
+        hipLaunchKernelGGL(colsum_kernel, dim3((nmax + 255) / 256, 1, k), dim3(256), 0, st, gc);
+        if (kz) T_K((launch_tgemm<false, false, TEPI_MASK, TEPI_MASK>(gz, kz, st)));
+    }
+    float step_size[MMC_TRAINER_GROUP_MAX], bc2_sqrt[MMC_TRAINER_GROUP_MAX];
+    for (int i = 0; i < cnt; ++i) {
+        mmc_trainer* t = act[i].t;
+        ++t->t;
+        const double bc1 = 1.0 - std::pow(t->beta1, (double)t->t), bc2 = 1.0 - std::pow(t->beta2, (double)t->t);
+        step_size[i] = (float)(t->lr / bc1);
+        bc2_sqrt[i] = (float)std::sqrt(bc2);
+    }
+    for (int l = 0; l < Lmax; ++l) {
+        AdamGroup gw, gb;
+        int k = 0;
+        size_t wmax = 0, bmax = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i].t;
+            if (l >= t->L) continue;
+            const size_t nw = (size_t)t->dims[l + 1] * t->dims[l], nb = (size_t)t->dims[l + 1];
+            const float om1 = (float)(1.0 - t->beta1), om2 = (float)(1.0 - t->beta2), b2f = (float)t->beta2, epsf = (float)t->eps;
+            gw.d[k] = AdamDesc{t->W[l], t->gW[l], t->mW[l], t->vW[l], nw, om1, b2f, om2, epsf, step_size[i], bc2_sqrt[i]};
+            gb.d[k] = AdamDesc{t->b[l], t->gb[l], t->mb[l], t->vb[l], nb, om1, b2f, om2, epsf, step_size[i], bc2_sqrt[i]};
+            ++k;
+            wmax = std::max(wmax, nw);
+            bmax = std::max(bmax, nb);
+        }
+        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((wmax + 255) / 256), 1, k), dim3(256), 0, st, gw);
+        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((bmax + 255) / 256), 1, k), dim3(256), 0, st, gb);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "trainer step launch failed: %s", hipGetErrorString(e));
     return 0;
 }
+
+// rows of the mini-batch that starts at row `start` of a pass over n rows
+int batch_rows(int64_t n, int64_t start, int mb) { return (int)((n - start) < mb ? (n - start) : mb); }
+
+// wsums[s] = the class-weight sum of mini-batch s (the mean reduction of the weighted CE), whose i-th row carries the label
+// y[idx ? idx[i] : i]; a mini-batch without weight is rejected.  Every pass calls this before it uploads or launches anything, so
+// a rejected pass leaves the weights, the Adam moments and the step counter exactly as they were.
+int minibatch_wsums(const char* who, const mmc_trainer* t, const int32_t* y, const int64_t* idx, int64_t n, int mb, std::vector<double>* wsums)
+{
+    const int steps = (int)((n + mb - 1) / mb);
+    wsums->resize(steps);
+    for (int s = 0; s < steps; ++s) {
+        const int64_t start = (int64_t)s * mb;
+        const int cur = batch_rows(n, start, mb);
+        double wsum = 0.0;
+        if (t->cw) { for (int i = 0; i < cur; ++i) wsum += t->cw_host[y[idx ? idx[start + i] : start + i]]; } else wsum = cur;
+        if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "%smini-batch %d has zero total class weight", who, s);
+        (*wsums)[s] = wsum;
+    }
+    return 0;
+}
+
+// torch_classifier.py:293-298: sum of loss.item() * mb_size over the steps, over n
+double pass_avg_loss(const std::vector<float>& h, int mb, int64_t n)
+{
+    double tot = 0.0;
+    for (size_t s = 0; s < h.size(); ++s) tot += (double)h[s] * (double)batch_rows(n, (int64_t)s * mb, mb);
+    return tot / (double)n;
+}
+
+}  // namespace
 
 // `order` (n int64 row indices, or NULL = rows are already in visiting order): the shuffle of torch_classifier.py:251-257 applied
 // on the device -- the natural-order matrix is uploaded as it is and a gather kernel builds the visiting order (when the
@@ -742,20 +800,11 @@ extern "C" int mmc_trainer_partial_fit_ordered(mmc_trainer* t, const float* X, c
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     T_TRY(hipSetDevice(t->device));
     const int mb = (int)(batch_size < n ? batch_size : n);
-    const int steps = (int)((n + mb - 1) / mb);
-    // every mini-batch's weight sum (mean reduction of the weighted CE) is checked BEFORE anything is uploaded or launched, so
-    // a rejected pass leaves the weights, the Adam moments and the step counter exactly as they were
-    std::vector<double> wsums(steps);
-    for (int s = 0; s < steps; ++s) {
-        const int64_t start = (int64_t)s * mb;
-        const int cur = (int)((n - start) < mb ? (n - start) : mb);
-        double wsum = 0.0;
-        if (t->cw) { for (int i = 0; i < cur; ++i) wsum += t->cw_host[y[order ? order[start + i] : start + i]]; } else wsum = cur;
-        if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "mini-batch %d has zero total class weight", s);
-        wsums[s] = wsum;
-    }
-    int r = trainer_reserve(t, n, mb, steps);
+    std::vector<double> wsums;
+    int r = minibatch_wsums("", t, y, order, n, mb, &wsums);
     if (r) return r;
+    const int steps = (int)wsums.size();
+    if ((r = trainer_reserve(t, n, mb, steps))) return r;
     if (order) {
         if (n > t->cap_nn) {
             hipFree(t->Xn); hipFree(t->yn); hipFree(t->order);
@@ -773,20 +822,15 @@ extern "C" int mmc_trainer_partial_fit_ordered(mmc_trainer* t, const float* X, c
         T_TRY(hipMemcpyAsync(t->X, X, (size_t)n * t->dims[0] * 4, hipMemcpyHostToDevice, st));
         T_TRY(hipMemcpyAsync(t->y, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
     }
-    std::vector<int> sizes(steps);
     for (int s = 0; s < steps; ++s) {
         const int64_t start = (int64_t)s * mb;
-        const int cur = (int)((n - start) < mb ? (n - start) : mb);
-        sizes[s] = cur;
-        r = trainer_step(t, start, cur, (float)(1.0 / wsums[s]), t->losses + s, st);
-        if (r) return r;
+        const StepMember one{t, start, batch_rows(n, start, mb), (float)(1.0 / wsums[s]), s};
+        if ((r = trainer_group_step(&one, 1, st))) return r;
     }
     std::vector<float> h(steps);
     T_TRY(hipMemcpyAsync(h.data(), t->losses, (size_t)steps * 4, hipMemcpyDeviceToHost, st));
     T_TRY(hipStreamSynchronize(st));
-    double tot = 0.0;
-    for (int s = 0; s < steps; ++s) tot += (double)h[s] * sizes[s];   // torch_classifier.py:293-298: loss.item() * mb_size
-    if (avg_loss) *avg_loss = tot / (double)n;
+    if (avg_loss) *avg_loss = pass_avg_loss(h, mb, n);
     return MMC_OK;
 }
 
@@ -796,11 +840,14 @@ extern "C" int mmc_trainer_partial_fit(mmc_trainer* t, const float* X, const int
     return mmc_trainer_partial_fit_ordered(t, X, y, nullptr, n, batch_size, avg_loss, hip_stream);
 }
 
-// ---- passes over a resident feature set: what the solo call and the grouped call share ------------------------------------
+// ---- passes over a resident feature set -----------------------------------------------------------------------------------
 namespace {
 
 // how one trainer takes one pass over rows of a set: mini-batch, steps, its chunks of whole mini-batches, every step's weight sum
 struct SetPass {
+    mmc_trainer* t = nullptr;
+    const int64_t* visit = nullptr;
+    int64_t n = 0;
     int mb = 0, steps = 0;
     int64_t chunk = 0, steps_per_chunk = 0, stage_rows = 0;
     std::vector<double> wsums;
@@ -834,11 +881,12 @@ int train_chunk_bound(int64_t* bound)
     return 0;
 }
 
-int plan_set_pass(const char* who, const mmc_trainer* t, const mmc_featureset* fs, const int64_t* visit, int64_t n, int batch_size,
+int plan_set_pass(const char* who, mmc_trainer* t, const mmc_featureset* fs, const int64_t* visit, int64_t n, int batch_size,
                   int64_t bound, SetPass* p)
 {
     const int mb = (int)(batch_size < n ? batch_size : n);
     if ((n + mb - 1) / mb > (int64_t)1 << 30) return mmc_fail(MMC_ERR_ARG, "%s%lld rows in mini-batches of %d: too many steps for one pass", who, (long long)n, mb);
+    p->t = t; p->visit = visit; p->n = n;
     p->mb = mb;
     p->steps = (int)((n + mb - 1) / mb);
     // the largest multiple of the mini-batch not above the bound, at least one mini-batch, and no more than a gather's grid / `rows` hold
@@ -849,30 +897,20 @@ int plan_set_pass(const char* who, const mmc_trainer* t, const mmc_featureset* f
     p->chunk = chunk;
     p->steps_per_chunk = chunk / mb;
     p->stage_rows = chunk < n ? chunk : n;
-    // as in the host-fed pass: every mini-batch's weight sum is checked before anything is uploaded or launched
-    p->wsums.resize(p->steps);
-    const int32_t* yh = fs->y_host.data();
-    for (int s = 0; s < p->steps; ++s) {
-        const int64_t start = (int64_t)s * mb;
-        const int cur = (int)((n - start) < mb ? (n - start) : mb);
-        double wsum = 0.0;
-        if (t->cw) { for (int i = 0; i < cur; ++i) wsum += t->cw_host[yh[visit ? visit[start + i] : start + i]]; } else wsum = cur;
-        if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "%smini-batch %d has zero total class weight", who, s);
-        p->wsums[s] = wsum;
-    }
-    return 0;
+    return minibatch_wsums(who, t, fs->y_host.data(), visit, n, mb, &p->wsums);
 }
 
 // the trainer's staging, activations and loss slots for the pass, and its device copy of the visiting order (not yet uploaded)
-int reserve_set_pass(mmc_trainer* t, const SetPass& p, const int64_t* visit, int64_t n)
+int reserve_set_pass(const SetPass& p)
 {
+    mmc_trainer* t = p.t;
     int r = trainer_reserve(t, p.stage_rows, p.mb, p.steps);
     if (r) return r;
-    if (visit && n > t->cap_visit) {
+    if (p.visit && p.n > t->cap_visit) {
         hipFree(t->visit);
         t->visit = nullptr; t->cap_visit = 0;
-        T_TRY(hipMalloc((void**)&t->visit, (size_t)n * 8 + 256));
-        t->cap_visit = n;
+        T_TRY(hipMalloc((void**)&t->visit, (size_t)p.n * 8 + 256));
+        t->cap_visit = p.n;
     }
     return 0;
 }
@@ -889,181 +927,78 @@ int gather_chunk(mmc_trainer* t, const mmc_featureset* fs, bool visited, int64_t
     return 0;
 }
 
-// torch_classifier.py:293-298: sum of loss.item() * mb_size over the steps, over n
-double pass_avg_loss(const std::vector<float>& h, const SetPass& p, int64_t n)
+// One pass of `count` trainers over rows of `fs`, step s of every member's pass issued together: position i of member m visits row
+// visit[m][i].  Nothing but the visiting orders is uploaded.  A member's visited rows and labels are gathered into its mini-batch
+// staging (t->X / t->y) a chunk of whole mini-batches at a time, and that chunk's steps follow on the same stream, so the steps
+// run the kernels of the host-fed pass on the same values: same bits.  `grouped` is the entry point's way of naming a member and of
+// reporting a failed reservation; the solo entry is a group of one that names nobody.
+int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit, const int64_t* n,
+             const int* batch_size, double* avg_loss, hipStream_t st)
 {
-    double tot = 0.0;
-    for (int s = 0; s < p.steps; ++s) {
-        const int64_t start = (int64_t)s * p.mb;
-        tot += (double)h[s] * (double)(int)((n - start) < p.mb ? (n - start) : p.mb);
+    std::vector<SetPass> mem(count);
+    char who[MMC_TRAINER_GROUP_MAX][32];
+    int r = 0;
+    for (int m = 0; m < count; ++m) {
+        who[m][0] = 0;
+        if (grouped) std::snprintf(who[m], sizeof who[m], "member %d: ", m);
+        if ((r = check_set_pass(who[m], trainers[m], fs, visit[m], n[m], batch_size[m]))) return r;
     }
-    return tot / (double)n;
+    int64_t bound = 0;
+    if ((r = train_chunk_bound(&bound))) return r;
+    int max_steps = 0;
+    for (int m = 0; m < count; ++m) {
+        if ((r = plan_set_pass(who[m], trainers[m], fs, visit[m], n[m], batch_size[m], bound, &mem[m]))) return r;
+        max_steps = std::max(max_steps, mem[m].steps);
+    }
+    T_TRY(hipSetDevice(fs->device));
+    // every member's buffers before the first launch: a pass that cannot be staged changes no member
+    for (int m = 0; m < count; ++m)
+        if ((r = reserve_set_pass(mem[m]))) {
+            if (!grouped) return r;
+            (void)hipGetLastError();
+            return mmc_fail(MMC_ERR_NOMEM, "member %d: could not allocate the buffers of its pass (%lld staged rows, mini-batch %d)", m,
+                            (long long)mem[m].stage_rows, mem[m].mb);
+        }
+    for (int m = 0; m < count; ++m)
+        if (mem[m].visit) T_TRY(hipMemcpyAsync(mem[m].t->visit, mem[m].visit, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
+    StepMember act[MMC_TRAINER_GROUP_MAX];
+    for (int s = 0; s < max_steps; ++s) {
+        int cnt = 0;
+        for (int m = 0; m < count; ++m) {
+            const SetPass& p = mem[m];
+            if (s >= p.steps) continue;   // this member's pass is over
+            const int64_t start = (int64_t)s * p.mb, c0 = s / p.steps_per_chunk * p.chunk;
+            if (start == c0) {            // its first step of a chunk: stage the chunk's rows first
+                const int rows = (int)((p.n - c0) < p.chunk ? (p.n - c0) : p.chunk);
+                if ((r = gather_chunk(p.t, fs, p.visit != nullptr, c0, rows, st))) return r;
+            }
+            act[cnt++] = StepMember{p.t, start - c0, batch_rows(p.n, start, p.mb), (float)(1.0 / p.wsums[s]), s};
+        }
+        if ((r = trainer_group_step(act, cnt, st))) return r;
+    }
+    std::vector<std::vector<float>> h(count);
+    for (int m = 0; m < count; ++m) {
+        h[m].resize(mem[m].steps);
+        T_TRY(hipMemcpyAsync(h[m].data(), mem[m].t->losses, (size_t)mem[m].steps * 4, hipMemcpyDeviceToHost, st));
+    }
+    T_TRY(hipStreamSynchronize(st));
+    if (avg_loss)
+        for (int m = 0; m < count; ++m) avg_loss[m] = pass_avg_loss(h[m], mem[m].mb, mem[m].n);
+    return MMC_OK;
 }
 
 }  // namespace
 
-// The pass of mmc_trainer_partial_fit_ordered over rows that are already on the device: position i visits row visit[i] of `fs`.
-// Nothing but `visit` is uploaded.  The visited rows and labels are gathered into the mini-batch staging (t->X / t->y) a chunk of whole
-// mini-batches at a time, and that chunk's steps follow on the same stream, so the steps run the kernels of the host-fed pass on the
-// same values: same bits.
+// The pass of mmc_trainer_partial_fit_ordered over rows that are already on the device: a group of one (include/mmc.h).
 extern "C" int mmc_trainer_partial_fit_set(mmc_trainer* t, mmc_featureset* fs, const int64_t* visit, int64_t n, int batch_size,
                                            double* avg_loss, void* hip_stream)
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
-    int r = check_set_pass("", t, fs, visit, n, batch_size);
-    if (r) return r;
-    int64_t bound = 0;
-    if ((r = train_chunk_bound(&bound))) return r;
-    SetPass p;
-    if ((r = plan_set_pass("", t, fs, visit, n, batch_size, bound, &p))) return r;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    T_TRY(hipSetDevice(t->device));
-    if ((r = reserve_set_pass(t, p, visit, n))) return r;
-    if (visit) T_TRY(hipMemcpyAsync(t->visit, visit, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
-        const int rows = (int)((n - c0) < p.chunk ? (n - c0) : p.chunk);
-        if ((r = gather_chunk(t, fs, visit != nullptr, c0, rows, st))) return r;
-        for (int64_t off = 0; off < rows; off += p.mb) {
-            const int s = (int)(c0 / p.chunk * p.steps_per_chunk + off / p.mb);
-            const int cur = (int)((rows - off) < p.mb ? (rows - off) : p.mb);
-            r = trainer_step(t, off, cur, (float)(1.0 / p.wsums[s]), t->losses + s, st);
-            if (r) return r;
-        }
-    }
-    std::vector<float> h(p.steps);
-    T_TRY(hipMemcpyAsync(h.data(), t->losses, (size_t)p.steps * 4, hipMemcpyDeviceToHost, st));
-    T_TRY(hipStreamSynchronize(st));
-    if (avg_loss) *avg_loss = pass_avg_loss(h, p, n);
-    return MMC_OK;
+    return set_pass(false, &t, 1, fs, &visit, &n, &batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
 }
 
-// ---- a group of trainers, one pass each, in the launches of one ------------------------------------------------------------
-namespace {
-
-struct GroupMember {
-    mmc_trainer* t = nullptr;
-    const int64_t* visit = nullptr;
-    int64_t n = 0;
-    SetPass p;
-    int cur = 0;                        // this step's mini-batch rows
-    float inv_wsum = 0.f;               // this step's 1 / sum of class weights
-    float step_size = 0.f, bc2_sqrt = 0.f;   // this step's Adam scalars
-};
-
-template <bool TA, bool TB, int EPI0, int EPI1>
-int launch_tgemm_group(const GemmGroup& g, int cnt, hipStream_t st)
-{
-    int tm = 0, tn = 0;
-    for (int i = 0; i < cnt; ++i) {
-        tm = std::max(tm, (g.d[i].M + 63) / 64);
-        tn = std::max(tn, (g.d[i].N + 63) / 64);
-    }
-    hipLaunchKernelGGL((tgemm_f32_group_kernel<TA, TB, EPI0, EPI1>), dim3(tm, tn, cnt), dim3(256), 0, st, g);
-    return (int)hipGetLastError();
-}
-
-// trainer_step for every member in `act` at once: each kind of launch once, the member as blockIdx.z.  A member takes part in the
-// launches of the layers it has; the order of its own launches is trainer_step's.
-int trainer_group_step(GroupMember* const* act, int cnt, const int64_t* off, const int* slot, hipStream_t st)
-{
-    int Lmax = 0;
-    for (int i = 0; i < cnt; ++i) {
-        mmc_trainer* t = act[i]->t;
-        t->H[0] = t->X + (size_t)off[i] * t->dims[0];
-        Lmax = std::max(Lmax, t->L);
-    }
-    for (int l = 0; l < Lmax; ++l) {
-        GemmGroup g;
-        int k = 0;
-        for (int i = 0; i < cnt; ++i) {
-            const mmc_trainer* t = act[i]->t;
-            if (l >= t->L) continue;
-            g.d[k++] = GemmDesc{t->H[l], t->W[l], t->H[l + 1], t->b[l], act[i]->cur, t->dims[l + 1], t->dims[l],
-                                l == t->L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU, 0.f};
-        }
-        T_K((launch_tgemm_group<false, true, TEPI_BIAS_RELU, TEPI_BIAS>(g, k, st)));
-    }
-    {
-        CeGroup g;
-        int mmax = 0;
-        for (int i = 0; i < cnt; ++i) {
-            const mmc_trainer* t = act[i]->t;
-            g.d[i] = CeDesc{t->H[t->L], t->y + off[i], t->cw, t->dZ[t->L], t->row_loss, act[i]->cur, t->K, act[i]->inv_wsum,
-                            t->general ? 1 : 0, trainer_ce_loss(t)};
-            mmax = std::max(mmax, act[i]->cur);
-        }
-        hipLaunchKernelGGL(ce_grad_group_kernel, dim3((mmax + 3) / 4, 1, cnt), dim3(256), 0, st, g);
-    }
-    for (int l = 0; l < Lmax; ++l) {
-        SumsqGroup g;
-        int k = 0;
-        for (int i = 0; i < cnt; ++i) {
-            const mmc_trainer* t = act[i]->t;
-            if (l < t->L) g.d[k++] = SumsqDesc{t->W[l], t->partials + 256 * l, (size_t)t->dims[l + 1] * t->dims[l]};
-        }
-        hipLaunchKernelGGL(sumsq_group_kernel, dim3(256, 1, k), dim3(256), 0, st, g);
-    }
-    {
-        LossGroup g;
-        for (int i = 0; i < cnt; ++i) {
-            const mmc_trainer* t = act[i]->t;
-            g.d[i] = LossDesc{t->row_loss, t->partials, t->losses + slot[i], act[i]->cur, 256 * t->L,
-                              (float)(0.5 * t->alpha / (double)act[i]->cur)};
-        }
-        hipLaunchKernelGGL(loss_finalize_group_kernel, dim3(1, 1, cnt), dim3(256), 0, st, g);
-    }
-    for (int l = Lmax - 1; l >= 0; --l) {
-        GemmGroup gw, gz;
-        ColsumGroup gc;
-        int k = 0, kz = 0, nmax = 0;
-        for (int i = 0; i < cnt; ++i) {
-            const mmc_trainer* t = act[i]->t;
-            if (l >= t->L) continue;
-            const int no = t->dims[l + 1], ni = t->dims[l], mb = act[i]->cur;
-            gw.d[k] = GemmDesc{t->dZ[l + 1], t->H[l], t->gW[l], t->W[l], no, ni, mb, TEPI_L2, (float)(t->alpha / (double)mb)};
-            gc.d[k] = ColsumDesc{t->dZ[l + 1], t->gb[l], mb, no};
-            ++k;
-            nmax = std::max(nmax, no);
-            if (l > 0) gz.d[kz++] = GemmDesc{t->dZ[l + 1], t->W[l], t->dZ[l], t->H[l], mb, ni, no, TEPI_MASK, 0.f};
-        }
-        T_K((launch_tgemm_group<true, false, TEPI_L2, TEPI_L2>(gw, k, st)));
-        hipLaunchKernelGGL(colsum_group_kernel, dim3((nmax + 255) / 256, 1, k), dim3(256), 0, st, gc);
-        if (kz) T_K((launch_tgemm_group<false, false, TEPI_MASK, TEPI_MASK>(gz, kz, st)));
-    }
-    for (int i = 0; i < cnt; ++i) {
-        mmc_trainer* t = act[i]->t;
-        ++t->t;
-        const double bc1 = 1.0 - std::pow(t->beta1, (double)t->t), bc2 = 1.0 - std::pow(t->beta2, (double)t->t);
-        act[i]->step_size = (float)(t->lr / bc1);
-        act[i]->bc2_sqrt = (float)std::sqrt(bc2);
-    }
-    for (int l = 0; l < Lmax; ++l) {
-        AdamGroup gw, gb;
-        int k = 0;
-        size_t wmax = 0, bmax = 0;
-        for (int i = 0; i < cnt; ++i) {
-            const mmc_trainer* t = act[i]->t;
-            if (l >= t->L) continue;
-            const size_t nw = (size_t)t->dims[l + 1] * t->dims[l], nb = (size_t)t->dims[l + 1];
-            const float om1 = (float)(1.0 - t->beta1), om2 = (float)(1.0 - t->beta2), b2f = (float)t->beta2, epsf = (float)t->eps;
-            gw.d[k] = AdamDesc{t->W[l], t->gW[l], t->mW[l], t->vW[l], nw, om1, b2f, om2, epsf, act[i]->step_size, act[i]->bc2_sqrt};
-            gb.d[k] = AdamDesc{t->b[l], t->gb[l], t->mb[l], t->vb[l], nb, om1, b2f, om2, epsf, act[i]->step_size, act[i]->bc2_sqrt};
-            ++k;
-            wmax = std::max(wmax, nw);
-            bmax = std::max(bmax, nb);
-        }
-        hipLaunchKernelGGL(adam_group_kernel, dim3((unsigned)((wmax + 255) / 256), 1, k), dim3(256), 0, st, gw);
-        hipLaunchKernelGGL(adam_group_kernel, dim3((unsigned)((bmax + 255) / 256), 1, k), dim3(256), 0, st, gb);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "trainer group step launch failed: %s", hipGetErrorString(e));
-    return 0;
-}
-
-}  // namespace
-
-// mmc_trainer_partial_fit_set for `count` trainers over one set, step s of every member's pass issued together (include/mmc.h).
+// mmc_trainer_partial_fit_set for `count` trainers over one set in the launches of one pass (include/mmc.h).
 extern "C" int mmc_trainer_group_partial_fit_set(mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit,
                                                  const int64_t* n, const int* batch_size, double* avg_loss, void* hip_stream)
 {
@@ -1077,62 +1012,7 @@ extern "C" int mmc_trainer_group_partial_fit_set(mmc_trainer* const* trainers, i
             if (trainers[o] == trainers[m]) return mmc_fail(MMC_ERR_ARG, "member %d is the same trainer as member %d", m, o);
     }
     if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
-    std::vector<GroupMember> mem(count);
-    char who[32];
-    int r = 0;
-    for (int m = 0; m < count; ++m) {
-        std::snprintf(who, sizeof who, "member %d: ", m);
-        if ((r = check_set_pass(who, trainers[m], fs, visit[m], n[m], batch_size[m]))) return r;
-    }
-    int64_t bound = 0;
-    if ((r = train_chunk_bound(&bound))) return r;
-    int max_steps = 0;
-    for (int m = 0; m < count; ++m) {
-        std::snprintf(who, sizeof who, "member %d: ", m);
-        mem[m].t = trainers[m]; mem[m].visit = visit[m]; mem[m].n = n[m];
-        if ((r = plan_set_pass(who, trainers[m], fs, visit[m], n[m], batch_size[m], bound, &mem[m].p))) return r;
-        max_steps = std::max(max_steps, mem[m].p.steps);
-    }
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    T_TRY(hipSetDevice(fs->device));
-    // every member's buffers before the first launch: a pass that cannot be staged changes no member
-    for (int m = 0; m < count; ++m)
-        if (reserve_set_pass(mem[m].t, mem[m].p, mem[m].visit, mem[m].n)) {
-            (void)hipGetLastError();
-            return mmc_fail(MMC_ERR_NOMEM, "member %d: could not allocate the buffers of its pass (%lld staged rows, mini-batch %d)", m,
-                            (long long)mem[m].p.stage_rows, mem[m].p.mb);
-        }
-    for (int m = 0; m < count; ++m)
-        if (mem[m].visit) T_TRY(hipMemcpyAsync(mem[m].t->visit, mem[m].visit, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
-    GroupMember* act[MMC_TRAINER_GROUP_MAX];
-    int64_t off[MMC_TRAINER_GROUP_MAX];
-    int slot[MMC_TRAINER_GROUP_MAX];
-    for (int s = 0; s < max_steps; ++s) {
-        int cnt = 0;
-        for (int m = 0; m < count; ++m) {
-            GroupMember& g = mem[m];
-            if (s >= g.p.steps) continue;   // this member's pass is over
-            const int64_t start = (int64_t)s * g.p.mb, c0 = s / g.p.steps_per_chunk * g.p.chunk;
-            if (start == c0) {              // its first step of a chunk: stage the chunk's rows first
-                const int rows = (int)((g.n - c0) < g.p.chunk ? (g.n - c0) : g.p.chunk);
-                if ((r = gather_chunk(g.t, fs, g.visit != nullptr, c0, rows, st))) return r;
-            }
-            g.cur = (int)((g.n - start) < g.p.mb ? (g.n - start) : g.p.mb);
-            g.inv_wsum = (float)(1.0 / g.p.wsums[s]);
-            act[cnt] = &g; off[cnt] = start - c0; slot[cnt] = s;
-            ++cnt;
-        }
-        if ((r = trainer_group_step(act, cnt, off, slot, st))) return r;
-    }
-    std::vector<std::vector<float>> h(count);
-    for (int m = 0; m < count; ++m) {
-        h[m].resize(mem[m].p.steps);
-        T_TRY(hipMemcpyAsync(h[m].data(), mem[m].t->losses, (size_t)mem[m].p.steps * 4, hipMemcpyDeviceToHost, st));
-    }
-    T_TRY(hipStreamSynchronize(st));
-    if (avg_loss)
-        for (int m = 0; m < count; ++m) avg_loss[m] = pass_avg_loss(h[m], mem[m].p, mem[m].n);
-    return MMC_OK;
+    return set_pass(true, trainers, count, fs, visit, n, batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
 }
 
 extern "C" int mmc_trainer_get_params(mmc_trainer* t, float* const* W, float* const* b)
@@ -1185,9 +1065,11 @@ int trainer_forward_device(mmc_trainer* t, const float* X_dev, int n, hipStream_
     int r = trainer_reserve(t, 0, n, 1);   // activations only: the input is read where it lies
     if (r) return r;
     t->H[0] = const_cast<float*>(X_dev);
-    for (int l = 0; l < t->L; ++l)
-        T_K((launch_tgemm<false, true>(t->H[l], t->W[l], t->H[l + 1], n, t->dims[l + 1], t->dims[l],
-                                      l == t->L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU, t->b[l], 0.f, st)));
+    for (int l = 0; l < t->L; ++l) {
+        GemmGroup g;
+        g.d[0] = forward_desc(t, l, n);
+        T_K((launch_tgemm<false, true, TEPI_BIAS_RELU, TEPI_BIAS>(g, 1, st)));
+    }
     *logits = t->H[t->L];
     return MMC_OK;
 }
@@ -1229,7 +1111,7 @@ extern "C" int mmc_trainer_logits(mmc_trainer* t, const float* X, int64_t n, flo
     return MMC_OK;
 }
 
-// the loss stage of trainer_step on caller logits: the step's kernel, class weights, loss options and 1 / sum of w[y_i] (include/mmc.h)
+// the loss stage of a step on caller logits: the step's kernel, class weights, loss options and 1 / sum of w[y_i] (include/mmc.h)
 extern "C" int mmc_trainer_loss_gradient(mmc_trainer* t, const float* logits, const int32_t* y, int64_t n, float* dlogits, float* row_loss,
                                          void* hip_stream)
 {
@@ -1252,7 +1134,9 @@ extern "C" int mmc_trainer_loss_gradient(mmc_trainer* t, const float* logits, co
     const size_t cells = (size_t)mb * t->K;
     T_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
     T_TRY(hipMemcpyAsync(yd, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
-    launch_ce_grad(t, t->H[L], static_cast<const int32_t*>(yd), mb, (float)(1.0 / wsum), t->dZ[L], t->row_loss, st);
+    CeGroup g;
+    g.d[0] = ce_desc(t, t->H[L], static_cast<const int32_t*>(yd), mb, (float)(1.0 / wsum));
+    hipLaunchKernelGGL(ce_grad_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
     T_TRY(hipGetLastError());
     T_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
     T_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));

@@ -4,8 +4,8 @@ and ``train_sweep``.
 CPU: C-ABI and Python argument errors that need no device; ``sweep_loop``'s bookkeeping with fake classifiers and scripted
 validation losses, against ``epoch_loop`` on the same script.
 GPU (-m gpu): every comparison is ``np.array_equal`` on parameters, both Adam moments, step count, ``loss_curve_`` and
-``n_iter_`` against clones trained by the solo ``partial_fit_rows`` -- a member's launches run the solo kernels' bodies with the
-solo decomposition of every reduction, so there is nothing to tolerate.  Data: tests/golden/trainer_fixture.npz (730 x 64,
+``n_iter_`` against clones trained by the solo ``partial_fit_rows`` -- the solo call is a group of one in the same kernels, and no
+reduction's decomposition depends on the group, so there is nothing to tolerate.  Data: tests/golden/trainer_fixture.npz (730 x 64,
 7 classes; the weighted variant has one class of weight 0)."""
 
 import ctypes as C

@@ -3,6 +3,8 @@
 csrc/calib.hip) at K = 108 classes.
 
     python tools/calibration_throughput.py                 fit / calibrate / evaluate timings (+ host sklearn fit at 1e5)
+    python tools/calibration_throughput.py --features-only the calibrate-from-features and evaluate lines alone (the trainer's forward
+                                                           at 16384 rows a call; no score matrices, no host sklearn fit)
     python tools/calibration_throughput.py --fit-only N    one warm-up fit and one fit at N rows (for a rocprofv3 run)
     python tools/calibration_throughput.py --summarize kernel_trace.csv N
                                                            platt_pass_kernel launches of that rocprofv3 trace: bytes of F read
@@ -43,11 +45,11 @@ def device_fit(S, y):
     return dt, it
 
 
-def main():
+def main(features_only=False):
     import torch  # noqa: F401  (HIP runtime of torch first, as the package does)
     from mermaid_classifier_amd.calibration import calibrate, evaluate
     from mermaid_classifier_amd.torch_classifier import TorchMLPClassifier
-    for n in (100_000, 1_000_000):
+    for n in () if features_only else (100_000, 1_000_000):
         S, y = scores(n)
         dt, it = device_fit(S, y)
         print(f"fit N={n} K={K}: {dt * 1e3:.2f} ms wall (device-synchronised), Newton trial points per class max {it.max()} "
@@ -72,6 +74,8 @@ def main():
         evaluate(clf, ((X, yl) for _ in range(reps)))
         dt = time.perf_counter() - t0
         print(f"evaluate N={n}: {n / dt:,.0f} rows/s ({dt:.2f} s)")
+    if features_only:
+        return
     try:
         from sklearn.calibration import _SigmoidCalibration
     except ImportError:
@@ -122,4 +126,4 @@ if __name__ == "__main__":
     elif len(sys.argv) > 1 and sys.argv[1] == "--summarize":
         summarize(sys.argv[2], int(sys.argv[3]))
     else:
-        main()
+        main(features_only="--features-only" in sys.argv[1:])
