@@ -135,6 +135,31 @@ int mmc_backbone_profile(mmc_backbone* bb, const void* patches_dev, int64_t n, f
 int mmc_crop_patches(const void* image, int height, int width, const int32_t* rowcols, int64_t n,
                      void* patches_out_dev, unsigned flags, int device, void* hip_stream);
 
+/* ---- patch views -----------------------------------------------------------------------
+ * No reference counterpart (the reference cuts one fixed window per point): the eight orientations of a patch and a 2x context
+ * crop, so that a frozen backbone can be shown a point several ways (averaged by mmc_head_topk_views, or appended to a
+ * training set as extra rows).
+ * A view is an integer v in 0..15 with r = v & 3, f = (v >> 2) & 1, z = (v >> 3) & 1.  For a point (row, col):
+ *   base patch B (224 x 224 x 3 u8)
+ *     z = 0: the patch of mmc_crop_patches, with its bytes.
+ *     z = 1: the 448 x 448 window Wn of rows row-224 .. row+223 and columns col-224 .. col+223, indexed with numpy 'reflect'
+ *            (i < 0 -> -i, i >= n -> 2(n-1)-i; one reflection suffices because both image dimensions must exceed 224), reduced
+ *            2:1 per channel in integers:
+ *            B[y,x,c] = (Wn[2y,2x,c] + Wn[2y,2x+1,c] + Wn[2y+1,2x,c] + Wn[2y+1,2x+1,c] + 2) >> 2.
+ *   orientation
+ *     P = np.rot90(B[:, ::-1] if f else B, k=r, axes=(0, 1)).
+ * View 0 is the patch of mmc_crop_patches.
+ *
+ * mmc_crop_patches_views: patch i is view views[i] of point i (a caller who wants G views of a point lists it G times).
+ * `views` (n codes, or NULL = all 0) lives where `rowcols` lives: host memory under MMC_IN_HOST, else device memory.  Host codes
+ * above 15 are rejected with MMC_ERR_ARG naming the index; device codes are masked to 4 bits by the kernel (as device points are
+ * clamped).  Everything else -- the point checks, the choice between the host cut and upload + kernel, streams -- is as in
+ * mmc_crop_patches, and the three routes give the same bytes for every view. */
+#define MMC_VIEWS_MAX 16   /* view codes 0 .. 15; also the most rows (views) per point of mmc_head_topk_views */
+int mmc_crop_patches_views(const void* image, int height, int width, const int32_t* rowcols, int64_t n,
+                           const uint8_t* views /* n codes, NULL = all 0 */, void* patches_out_dev,
+                           unsigned flags, int device, void* hip_stream);
+
 /* ---- calibrated MLP head -------------------------------------------------------------
  * Replaces: CalibratedHead.forward (mermaid_classifier/pyspacer/inference/head.py:66-89) as run by
  *   Predictor.predict_proba (mermaid_classifier/pyspacer/inference/loader.py:30-35).
@@ -174,6 +199,20 @@ int mmc_head_topk(mmc_head* h, const float* feats, int64_t n, int k,
  * data copied back); asynchronous unless MMC_OUT_HOST is set.  Same bits as mmc_backbone_extract + mmc_head_topk. */
 int mmc_classify_patches(mmc_backbone* bb, mmc_head* h, const void* patches, int64_t n, int k,
                          int32_t* idx, float* scores, unsigned flags, void* hip_stream);
+
+/* ---- the mean over a point's views, then top-k ---------------------------------------------
+ * Rows p*G .. p*G+G-1 of feats (or patches) are the G views of point p, 1 <= G <= 16.  Per point and class the value is
+ *   m = (v_0 + v_1 + ... + v_{G-1}) / (float)G      in fp32, summed left to right in view order,
+ * with v_g the probability mmc_head_predict writes for that row, bit for bit.  The k best classes of m are chosen as mmc_head_topk
+ * chooses them (score descending, equal scores in class order, k distinct classes even for NaN rows); with G = 1 the outputs have
+ * the bits of mmc_head_topk / mmc_classify_patches.  idx, scores: n_points x k; proba: the n_points x K means, or NULL.
+ * Internal chunks hold whole points only (the head's row chunk and the 4096-patch chunk are rounded down to multiples of G).
+ * Flags, streams, the feature buffer and the graph-cache behaviour are those of mmc_head_topk / mmc_classify_patches. */
+int mmc_head_topk_views(mmc_head* h, const float* feats /* (n_points*G) x input_dim, point-major */, int64_t n_points, int G, int k,
+                        int32_t* idx /* n_points x k */, float* scores /* n_points x k */, float* proba /* n_points x K or NULL */,
+                        unsigned flags, void* hip_stream);
+int mmc_classify_patches_views(mmc_backbone* bb, mmc_head* h, const void* patches /* (n_points*G) x 224x224x3 */,
+                               int64_t n_points, int G, int k, int32_t* idx, float* scores, unsigned flags, void* hip_stream);
 
 /* ---- MLP classifier training on precomputed feature vectors --------------------------------
  * Replaces: the arithmetic of TorchMLPClassifier.partial_fit (mermaid_classifier/pyspacer/torch_classifier.py:226-303)

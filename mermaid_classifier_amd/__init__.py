@@ -5,7 +5,7 @@ first use and its absence is an error (there is no CPU fallback)."""
 
 from .extractor import EfficientNetExtractor, build_extractor_class, resolve_device, verify_device_numerics  # noqa: F401
 from .inference import ManifestError, Predictor, load_predictor, SCHEMA_VERSION, TASK_NAME  # noqa: F401
-from .backbone import Backbone, crop_patches_device, FEATURE_DIM  # noqa: F401
+from .backbone import ALL_ORIENTATIONS, Backbone, check_views, crop_patches_device, FEATURE_DIM  # noqa: F401
 from .classify import PointClassifier, PointPredictions  # noqa: F401
 from .calibration import CalibratedMLP, ParityError, calibrate, evaluate, evaluate_classes, export_artifact  # noqa: F401
 from .class_scores import ClassScores  # noqa: F401
@@ -21,7 +21,7 @@ from .ranking import RankedValidation, ranking_validate, similarity_levels  # no
 __all__ = [
     "EfficientNetExtractor", "build_extractor_class", "resolve_device", "verify_device_numerics",
     "ManifestError", "Predictor", "load_predictor", "SCHEMA_VERSION", "TASK_NAME",
-    "Backbone", "crop_patches_device", "FEATURE_DIM",
+    "Backbone", "crop_patches_device", "FEATURE_DIM", "check_views", "ALL_ORIENTATIONS",
     "PointClassifier", "PointPredictions",
     "CalibratedMLP", "ParityError", "calibrate", "evaluate", "export_artifact",
     "FeatureSet", "epoch_loop", "train_classifier", "train_and_validate",

@@ -22,14 +22,16 @@ MMC_CATEGORY_MAX, MMC_CATEGORY_MAX_BINS = 64, 20   # include/mmc.h: mmc_head_eva
 MMC_CATEGORY_MIN_BINS, MMC_CATEGORY_ROWS_PER_BIN = 2, 10   # calibration.py:137: n_bins_cat = min(20, max(2, n // 10))
 MMC_RANKED_MAX_K = 16   # include/mmc.h: selection rounds of mmc_head_evaluate_ranked
 MMC_TRAINER_GROUP_MAX = 16   # include/mmc.h: members of one mmc_trainer_group_partial_fit_set call
+MMC_VIEWS_MAX = 16   # include/mmc.h MMC_VIEWS_MAX: view codes 0..15, and at most 16 views per point
 
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
     "mmc_last_error", "mmc_version", "mmc_device_count",
     "mmc_backbone_create", "mmc_backbone_create_ex", "mmc_fp8_e4m3_encode", "mmc_backbone_destroy", "mmc_feature_dim", "mmc_backbone_max_batch", "mmc_backbone_lanes",
     "mmc_backbone_workspace_bytes", "mmc_backbone_extract", "mmc_backbone_read_activation",
-    "mmc_backbone_profile", "mmc_backbone_graph_stats", "mmc_crop_patches",
+    "mmc_backbone_profile", "mmc_backbone_graph_stats", "mmc_crop_patches", "mmc_crop_patches_views",
     "mmc_head_create", "mmc_head_destroy", "mmc_head_input_dim", "mmc_head_num_classes", "mmc_head_predict", "mmc_head_topk", "mmc_classify_patches",
+    "mmc_head_topk_views", "mmc_classify_patches_views",
     "mmc_trainer_create", "mmc_trainer_destroy", "mmc_trainer_partial_fit", "mmc_trainer_partial_fit_ordered", "mmc_trainer_get_params", "mmc_trainer_adam_state",
     "mmc_trainer_logits", "mmc_trainer_evaluate", "mmc_trainer_evaluate_q32", "mmc_trainer_set_loss", "mmc_trainer_loss_gradient",
     "mmc_calibrator_create", "mmc_calibrator_destroy", "mmc_calibrator_add_features", "mmc_calibrator_add_scores", "mmc_calibrator_fit",
@@ -94,6 +96,8 @@ def _load() -> C.CDLL:
     lib.mmc_backbone_graph_stats.argtypes = [vp, C.POINTER(i64)]
     lib.mmc_crop_patches.restype = i32
     lib.mmc_crop_patches.argtypes = [vp, i32, i32, vp, i64, vp, u32, i32, vp]
+    lib.mmc_crop_patches_views.restype = i32
+    lib.mmc_crop_patches_views.argtypes = [vp, i32, i32, vp, i64, vp, vp, u32, i32, vp]
     lib.mmc_head_create.restype = i32
     lib.mmc_head_create.argtypes = [C.POINTER(fp), C.POINTER(fp), C.POINTER(i32), i32, fp, fp, i32, i32, C.POINTER(vp)]
     lib.mmc_head_destroy.restype = None
@@ -108,6 +112,10 @@ def _load() -> C.CDLL:
     lib.mmc_head_topk.argtypes = [vp, vp, i64, i32, vp, vp, vp, u32, vp]
     lib.mmc_classify_patches.restype = i32
     lib.mmc_classify_patches.argtypes = [vp, vp, vp, i64, i32, vp, vp, u32, vp]
+    lib.mmc_head_topk_views.restype = i32
+    lib.mmc_head_topk_views.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, u32, vp]
+    lib.mmc_classify_patches_views.restype = i32
+    lib.mmc_classify_patches_views.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, u32, vp]
     f32 = C.c_float
     f64 = C.c_double
     lib.mmc_trainer_create.restype = i32

@@ -34,6 +34,48 @@ def _device_index(device) -> int:
     raise ValueError(f"device {device!r} is not a HIP device (use 'cuda' or 'cuda:N')")
 
 
+ALL_ORIENTATIONS = tuple(range(8))   # the eight symmetries of the square at the patch's own scale (view codes 0..7)
+
+
+def check_views(views) -> Tuple[int, ...]:
+    """``views`` as every front-end takes it -> a tuple of view codes; ValueError unless it is a non-empty sequence of at most 16
+    integers in 0..15.  Host work only.
+
+    The definition, in the words of include/mmc.h ("patch views"):
+
+    A view is an integer v in 0..15 with r = v & 3, f = (v >> 2) & 1, z = (v >> 3) & 1.  For a point (row, col):
+      base patch B (224 x 224 x 3 u8)
+        z = 0: the patch of mmc_crop_patches, with its bytes.
+        z = 1: the 448 x 448 window Wn of rows row-224 .. row+223 and columns col-224 .. col+223, indexed with numpy 'reflect'
+               (i < 0 -> -i, i >= n -> 2(n-1)-i; one reflection suffices because both image dimensions must exceed 224), reduced
+               2:1 per channel in integers:
+               B[y,x,c] = (Wn[2y,2x,c] + Wn[2y,2x+1,c] + Wn[2y+1,2x,c] + Wn[2y+1,2x+1,c] + 2) >> 2.
+      orientation
+        P = np.rot90(B[:, ::-1] if f else B, k=r, axes=(0, 1)).
+    View 0 is the patch of mmc_crop_patches.
+    """
+    try:
+        codes = list(views)
+    except TypeError:
+        raise ValueError(f"views must be a sequence of view codes; got {views!r}") from None
+    if not 1 <= len(codes) <= _lib.MMC_VIEWS_MAX:
+        raise ValueError(f"views must hold 1 to {_lib.MMC_VIEWS_MAX} view codes; got {len(codes)}")
+    for v in codes:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < _lib.MMC_VIEWS_MAX:
+            raise ValueError(f"a view code must be an integer in 0..{_lib.MMC_VIEWS_MAX - 1}; got {v!r}")
+    return tuple(int(v) for v in codes)
+
+
+def check_views_per_point(n_rows: int, views_per_point) -> int:
+    """``views_per_point`` of the entries that take already-cut views: an integer in 1..16 that divides the row count."""
+    g = views_per_point
+    if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 1 <= int(g) <= _lib.MMC_VIEWS_MAX:
+        raise ValueError(f"views_per_point must be an integer in 1..{_lib.MMC_VIEWS_MAX}; got {g!r}")
+    if n_rows % int(g):
+        raise ValueError(f"{n_rows} rows are not a whole number of points at views_per_point = {int(g)}")
+    return int(g)
+
+
 def _current_stream_ptr(device_index: int) -> int:
     try:
         import torch
@@ -156,10 +198,13 @@ class Backbone:
         return [(names[i].value.decode(), float(ms[i])) for i in range(n_out.value)]
 
 
-def crop_patches_device(image: np.ndarray, rowcols, device=0):
+def crop_patches_device(image: np.ndarray, rowcols, device=0, views=None):
     """GPU crop_patches: (H,W,3) uint8 host image + [(row,col)] -> torch uint8 cuda tensor
-    (N,224,224,3).  Replaces pyspacer ``crop_patches`` (reflect-pad 224 + slice)."""
+    (N,224,224,3).  Replaces pyspacer ``crop_patches`` (reflect-pad 224 + slice).
+    ``views`` (see ``check_views``): G view codes -> (N*G,224,224,3), point-major: patch ``p*G + g`` is view ``views[g]`` of
+    point ``p``.  None is today's call and today's bytes."""
     import torch
+    vw = None if views is None else check_views(views)
     im = np.asarray(image)
     if im.ndim == 2:
         im = np.stack([im] * 3, axis=-1)
@@ -167,10 +212,16 @@ def crop_patches_device(image: np.ndarray, rowcols, device=0):
         raise ValueError(f"image must be uint8 (H,W,3); got {im.dtype} {im.shape}")
     im = np.ascontiguousarray(im[..., :3])
     rc = np.ascontiguousarray(np.asarray(rowcols, dtype=np.int32).reshape(-1, 2))
-    n = rc.shape[0]
     di = _device_index(device)
+    if vw is not None:
+        codes = np.ascontiguousarray(np.tile(np.asarray(vw, np.uint8), rc.shape[0]))
+        rc = np.ascontiguousarray(np.repeat(rc, len(vw), axis=0))
+    n = rc.shape[0]
     out = torch.empty((n, PATCH, PATCH, 3), dtype=torch.uint8, device=f"cuda:{di}")
-    if n:
+    if n and vw is not None:
+        _lib.check(_lib.lib().mmc_crop_patches_views(im.ctypes.data, im.shape[0], im.shape[1], rc.ctypes.data, n, codes.ctypes.data,
+                                                     out.data_ptr(), _lib.MMC_IN_HOST, di, _current_stream_ptr(di)))
+    elif n:
         _lib.check(_lib.lib().mmc_crop_patches(im.ctypes.data, im.shape[0], im.shape[1], rc.ctypes.data, n,
                                                out.data_ptr(), _lib.MMC_IN_HOST, di, _current_stream_ptr(di)))
     return out

@@ -15,7 +15,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .backbone import PATCH, _current_stream_ptr
+from .backbone import PATCH, _current_stream_ptr, check_views, check_views_per_point
 from .pipeline import PatchBatcher, prepare_image
 
 
@@ -56,7 +56,10 @@ def _check_k(k) -> int:
 
 
 class _Batcher(PatchBatcher):
-    """PatchBatcher whose pass is mmc_classify_patches: each flush ends in (fill, k) indices and scores in pinned memory."""
+    """PatchBatcher whose pass is mmc_classify_patches (mmc_classify_patches_views when the owner has views): each flush ends in
+    (points, k) indices and scores in pinned memory."""
+
+    mean_over_views = True
 
     def __init__(self, owner: "PointClassifier"):
         super().__init__(owner.backbone, owner.batch_patches)
@@ -74,7 +77,7 @@ class _Batcher(PatchBatcher):
 
     def _launch(self, slot, patches, fill, k):
         di, ds, _, _ = self.buffers(k)[slot]
-        self.owner._classify_device(patches, fill, k, di, ds)
+        self.owner._classify_device(patches, fill, k, di, ds, 1 if self.owner.views == (0,) else len(self.owner.views))
 
     def _download(self, slot, fill, k):
         di, ds, hi, hs = self.buffers(k)[slot]
@@ -89,11 +92,18 @@ class _Batcher(PatchBatcher):
 class PointClassifier:
     """``Backbone`` + ``Predictor`` as one patches -> labels pipeline on the GPU.  ``batch_patches`` bounds the device patch
     buffers of ``classify_image(s)``, as in ``BatchedExtractor``.  ``k`` is the reference's ``predictions_per_point``; more than
-    the head has classes gives all of them (the reference's ``[:k]`` slice clamps the same way)."""
+    the head has classes gives all of them (the reference's ``[:k]`` slice clamps the same way).
 
-    def __init__(self, backbone, predictor, batch_patches: int = 1024):
+    ``views`` (``backbone.check_views``): ``classify_image(s)`` cut every point once per view code and return one row per point,
+    the top-k of the mean of the views' calibrated probabilities (``mmc_classify_patches_views``: fp32, summed in ``views`` order,
+    divided by their number).  ``views=(0,)`` is the single fixed window, through the calls and with the bits of before."""
+
+    def __init__(self, backbone, predictor, batch_patches: int = 1024, views: Sequence[int] = (0,)):
         if int(batch_patches) < 1:
             raise ValueError(f"batch_patches must be >= 1; got {batch_patches}")
+        self.views = check_views(views)
+        if int(batch_patches) < len(self.views):
+            raise ValueError(f"batch_patches = {batch_patches} cannot hold the {len(self.views)} views of one point")
         if backbone.feature_dim != predictor.input_dim:
             raise ValueError(f"backbone feature_dim {backbone.feature_dim} != predictor input_dim {predictor.input_dim}")
         self.backbone = backbone
@@ -105,15 +115,21 @@ class PointClassifier:
     def _k(self, k) -> int:
         return min(_check_k(k), len(self.classes))
 
-    def _classify_device(self, patches, n: int, k: int, idx_dev, scores_dev) -> None:
-        """mmc_classify_patches on device-resident patches into device outputs, asynchronous on the current stream."""
+    def _classify_device(self, patches, n: int, k: int, idx_dev, scores_dev, g: int = 1) -> None:
+        """mmc_classify_patches on ``n`` device-resident patches into device outputs, asynchronous on the current stream; with
+        ``g`` > 1 views per point mmc_classify_patches_views on ``n // g`` points."""
         bb, head = self.backbone, self.predictor._head
-        _lib.check(_lib.lib().mmc_classify_patches(bb._h, head._h, patches.data_ptr(), n, k, idx_dev.data_ptr(),
-                                                   scores_dev.data_ptr(), 0, _current_stream_ptr(bb.device_index)))
+        if g == 1:
+            _lib.check(_lib.lib().mmc_classify_patches(bb._h, head._h, patches.data_ptr(), n, k, idx_dev.data_ptr(),
+                                                       scores_dev.data_ptr(), 0, _current_stream_ptr(bb.device_index)))
+        else:
+            _lib.check(_lib.lib().mmc_classify_patches_views(bb._h, head._h, patches.data_ptr(), n // g, g, k, idx_dev.data_ptr(),
+                                                             scores_dev.data_ptr(), 0, _current_stream_ptr(bb.device_index)))
 
-    def topk_device(self, patches, k: int = 1):
-        """Device in, device out: contiguous uint8 cuda tensor (N,224,224,3) -> (idx (N,k') int32, scores (N,k') float32) cuda
-        tensors, asynchronous on the current stream (what ``dist.classify_sharded`` gathers)."""
+    def topk_device(self, patches, k: int = 1, views_per_point: int = 1):
+        """Device in, device out: contiguous uint8 cuda tensor (N,224,224,3) -> (idx (N/G,k') int32, scores (N/G,k') float32) cuda
+        tensors, asynchronous on the current stream (what ``dist.classify_sharded`` gathers).  G = ``views_per_point``: patches
+        ``p*G .. p*G+G-1`` are already-cut views of point ``p`` and the row is the top-k of their mean."""
         import torch
         kk = self._k(k)
         if (not isinstance(patches, torch.Tensor) or not patches.is_cuda or patches.dtype != torch.uint8 or patches.dim() != 4
@@ -122,26 +138,34 @@ class PointClassifier:
         if patches.device.index != self.backbone.device_index:
             raise ValueError(f"patches live on {patches.device}, backbone on device {self.backbone.device_index}")
         n = patches.shape[0]
-        idx = torch.empty((n, kk), dtype=torch.int32, device=patches.device)
-        scores = torch.empty((n, kk), dtype=torch.float32, device=patches.device)
+        g = check_views_per_point(n, views_per_point)
+        idx = torch.empty((n // g, kk), dtype=torch.int32, device=patches.device)
+        scores = torch.empty((n // g, kk), dtype=torch.float32, device=patches.device)
         if n:
-            self._classify_device(patches, n, kk, idx, scores)
+            self._classify_device(patches, n, kk, idx, scores, g)
         return idx, scores
 
-    def classify_patches(self, patches, k: int = 1) -> PointPredictions:
-        """patches: (N,224,224,3) uint8 -- numpy (host) or a cuda tensor on the backbone's device."""
+    def classify_patches(self, patches, k: int = 1, views_per_point: int = 1) -> PointPredictions:
+        """patches: (N,224,224,3) uint8 -- numpy (host) or a cuda tensor on the backbone's device.  ``views_per_point`` = G:
+        patches ``p*G .. p*G+G-1`` are already-cut views of point ``p``; one prediction row per point, from their mean."""
         kk = self._k(k)
         if isinstance(patches, np.ndarray):
             p = np.ascontiguousarray(patches)
             if p.dtype != np.uint8 or p.ndim != 4 or p.shape[1:] != (PATCH, PATCH, 3):
                 raise ValueError(f"patches must be uint8 (N,{PATCH},{PATCH},3); got {p.dtype} {p.shape}")
             n = p.shape[0]
-            idx = np.empty((n, kk), dtype=np.int32)
-            scores = np.empty((n, kk), dtype=np.float32)
+            g = check_views_per_point(n, views_per_point)
+            idx = np.empty((n // g, kk), dtype=np.int32)
+            scores = np.empty((n // g, kk), dtype=np.float32)
             if n:
                 bb, head = self.backbone, self.predictor._head
-                _lib.check(_lib.lib().mmc_classify_patches(bb._h, head._h, p.ctypes.data, n, kk, idx.ctypes.data, scores.ctypes.data,
-                                                           _lib.MMC_IN_HOST | _lib.MMC_OUT_HOST, _current_stream_ptr(bb.device_index)))
+                flags = _lib.MMC_IN_HOST | _lib.MMC_OUT_HOST
+                if g == 1:
+                    _lib.check(_lib.lib().mmc_classify_patches(bb._h, head._h, p.ctypes.data, n, kk, idx.ctypes.data, scores.ctypes.data,
+                                                               flags, _current_stream_ptr(bb.device_index)))
+                else:
+                    _lib.check(_lib.lib().mmc_classify_patches_views(bb._h, head._h, p.ctypes.data, n // g, g, kk, idx.ctypes.data,
+                                                                     scores.ctypes.data, flags, _current_stream_ptr(bb.device_index)))
             return PointPredictions(None, idx, scores, self.classes)
         try:
             import torch
@@ -150,7 +174,7 @@ class PointClassifier:
             is_tensor = False
         if not is_tensor:
             raise TypeError("patches must be a numpy array or a torch tensor")
-        idx, scores = self.topk_device(patches, kk)
+        idx, scores = self.topk_device(patches, kk, views_per_point)
         return PointPredictions(None, idx.cpu().numpy(), scores.cpu().numpy(), self.classes)
 
     def classify_images(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]],
@@ -161,7 +185,7 @@ class PointClassifier:
         prepared = [prepare_image(i, im, rc) for i, (im, rc) in enumerate(zip(images, rowcols_per_image))]
         if self._batcher is None:
             self._batcher = _Batcher(self)
-        out, points = self._batcher._run([im for im, _ in prepared], [rc for _, rc in prepared], ctx=kk)
+        out, points = self._batcher._run([im for im, _ in prepared], [rc for _, rc in prepared], ctx=kk, views=self.views)
         res = []
         for o, rc in zip(out, points):
             pts = [(int(r), int(c)) for r, c in rc]

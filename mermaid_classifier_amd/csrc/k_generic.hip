@@ -1050,6 +1050,71 @@ __global__ __launch_bounds__(256) void calibrate_topk_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
+// mean_topk_kernel: a point is G consecutive rows (its views).  Per class m = (v_0 + v_1 + ... + v_{G-1}) / (float)G, summed left
+// to right, v_g = the probability calibrate_kernel writes for row g (same helpers, same lane order of the row sums); then the k
+// best classes of m by the rounds of calibrate_topk_kernel.  One wave per point, four points per workgroup; the mean row lives
+// where calibrate_topk_kernel keeps its row (wave-private LDS row, or rowbuf [P][K]).  A view takes two passes over its logits
+// after the softmax statistics: the row sum of its sigmoids, then sigmoid again -> normalise -> add into the mean row; recomputing
+// the sigmoid (same helper, same operands: same bits) is what saves a second scratch row per wave.  G = 1: m = v_0 / 1.0f = v_0,
+// the bits of calibrate_topk_kernel.
+// ---------------------------------------------------------------------------------------------
+template <bool ROW_IN_LDS>
+__global__ __launch_bounds__(256) void mean_topk_kernel(const float* __restrict__ logits, int P, int G, int K,
+                                                        const float* __restrict__ a, const float* __restrict__ bcal, int k,
+                                                        int32_t* __restrict__ idx_out,   // [P][k]
+                                                        float* __restrict__ score_out,   // [P][k]
+                                                        float* proba,                    // [P][K] or NULL
+                                                        float* rowbuf)                   // [P][K] when !ROW_IN_LDS
+{
+    extern __shared__ float topk_rows[];   // [4][K] when ROW_IN_LDS
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pt = blockIdx.x * 4 + wave;
+    if (pt >= P) return;
+    float* r = ROW_IN_LDS ? topk_rows + (size_t)wave * K : rowbuf + (size_t)pt * K;
+    for (int g = 0; g < G; ++g) {
+        const float* x = logits + ((size_t)pt * G + g) * K;
+        float mx, se;
+        calib_softmax_stats(x, K, lane, mx, se);
+        float cs = 0.f;
+        for (int c = lane; c < K; c += 64) cs += calib_sigmoid(x[c], mx, se, a[c], bcal[c]);
+        cs = wave_sum_f(cs);
+        for (int c = lane; c < K; c += 64) {
+            const float v = calib_normalise(calib_sigmoid(x[c], mx, se, a[c], bcal[c]), cs, K);
+            r[c] = g == 0 ? v : r[c] + v;
+        }
+    }
+    const float den = (float)G;
+    unsigned long long cur = 0;   // this lane's largest key not yet selected (calibrate_topk_kernel)
+    for (int c = lane; c < K; c += 64) {
+        const float m = r[c] / den;
+        r[c] = m;
+        if (proba) proba[(size_t)pt * K + c] = m;
+        const unsigned long long key = topk_key(m, c);
+        cur = key > cur ? key : cur;
+    }
+    for (int j = 0; j < k; ++j) {
+        unsigned long long win = cur;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_xor(win, o);
+            win = t > win ? t : win;
+        }
+        if (lane == 0) {
+            idx_out[(size_t)pt * k + j] = (int32_t)(0xFFFFFFFFu - (unsigned)win);
+            score_out[(size_t)pt * k + j] = __uint_as_float((unsigned)(win >> 32));
+        }
+        if (cur == win) {
+            unsigned long long nb = 0;
+            for (int c = lane; c < K; c += 64) {
+                const unsigned long long key = topk_key(r[c], c);
+                nb = (key < win && key > nb) ? key : nb;
+            }
+            cur = nb;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // calibrate_eval_kernel: the same calibration, then what a validation pass keeps of a row whose true class g is known
 // (mermaid_classifier/pyspacer/trainer.py:271-291, metrics/ranking.py:54-65, metrics/probability.py:47-49):
 //   est    = class of the largest topk_key (the first maximum, as numpy.argmax and the stable sort give it), score = v[est]
@@ -1280,6 +1345,57 @@ __global__ __launch_bounds__(256) void crop_kernel(const uint8_t* __restrict__ i
     dst[2] = w[2];
 }
 
+// ---------------------------------------------------------------------------------------------
+// crop_views_kernel: patch p = view views[p] of point p (include/mmc.h, "patch views"), on crop_kernel's scheme: one thread =
+// 4 consecutive output pixels, one 12-byte store.  view_source() says where an output pixel lies in the base patch; the base patch
+// is crop_kernel's window (z = 0) or the rounded mean of the 2x2 footprint in the 448-pixel window (z = 1), both reflected once
+// (H, W > 224 bound every index: a window reaches at most 224 pixels past an edge).  For odd r the four pixels of a thread come
+// from four source rows; the image lines a workgroup touches are shared with its neighbours through the caches.
+// The view is uniform per workgroup (blockIdx.y = patch), so the branches below do not diverge.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int reflect1(int i, int n)
+{
+    i = i < 0 ? -i : i;
+    return i >= n ? 2 * (n - 1) - i : i;
+}
+__global__ __launch_bounds__(256) void crop_views_kernel(const uint8_t* __restrict__ image, int H, int W,
+                                                         const int32_t* __restrict__ rowcols, const uint8_t* __restrict__ views,
+                                                         uint8_t* __restrict__ out)
+{
+    const int p = blockIdx.y;
+    const int idx = blockIdx.x * 256 + threadIdx.x;  // over 224*56 groups of 4 pixels
+    if (idx >= 224 * 56) return;
+    const int i = idx / 56, jg = idx - i * 56;
+    const int v = views ? (views[p] & 15) : 0;       // device codes are masked, as device points are clamped
+    int row = rowcols[2 * p], col = rowcols[2 * p + 1];
+    row = row < 0 ? 0 : (row >= H ? H - 1 : row);
+    col = col < 0 ? 0 : (col >= W ? W - 1 : col);
+    uint32_t w[3] = {0, 0, 0};
+    uint8_t* wb = reinterpret_cast<uint8_t*>(w);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        int by, bx;
+        view_source(v, i, jg * 4 + e, by, bx);
+        if (!(v & 8)) {
+            const uint8_t* src = image + ((size_t)reflect1(row - 112 + by, H) * W + reflect1(col - 112 + bx, W)) * 3;
+            wb[3 * e + 0] = src[0];
+            wb[3 * e + 1] = src[1];
+            wb[3 * e + 2] = src[2];
+        } else {
+            const size_t y0 = (size_t)reflect1(row - 224 + 2 * by, H) * W, y1 = (size_t)reflect1(row - 223 + 2 * by, H) * W;
+            const int x0 = reflect1(col - 224 + 2 * bx, W), x1 = reflect1(col - 223 + 2 * bx, W);
+            const uint8_t *s00 = image + (y0 + x0) * 3, *s01 = image + (y0 + x1) * 3;
+            const uint8_t *s10 = image + (y1 + x0) * 3, *s11 = image + (y1 + x1) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) wb[3 * e + c] = (uint8_t)(((int)s00[c] + s01[c] + s10[c] + s11[c] + 2) >> 2);
+        }
+    }
+    uint32_t* dst = reinterpret_cast<uint32_t*>(out + ((size_t)p * 224 * 224 + (size_t)i * 224 + jg * 4) * 3);
+    dst[0] = w[0];
+    dst[1] = w[1];
+    dst[2] = w[2];
+}
+
 // =============================================================================================
 // Host-side launchers (plain C++ signatures declared in kernels.h)
 // =============================================================================================
@@ -1454,6 +1570,24 @@ int launch_calibrate_topk(const float* logits, int M, int K, const float* a, con
     return 0;
 }
 
+int launch_mean_topk(const float* logits, int P, int G, int K, const float* a, const float* b, int k, int32_t* idx, float* scores,
+                     float* proba, float* rowbuf, hipStream_t st)
+{
+    if (P < 1 || G < 1 || G > VIEWS_MAX || K < 1 || k < 1 || k > K || !idx || !scores) return -18;
+    const dim3 grid((P + 3) / 4);
+    if (K <= TOPK_LDS_MAX_K) {
+        hipLaunchKernelGGL((mean_topk_kernel<true>), grid, dim3(256), (size_t)4 * K * sizeof(float), st, logits, P, G, K, a, b, k, idx,
+                           scores, proba, (float*)nullptr);
+    } else {
+        float* rows = proba ? proba : rowbuf;   // as launch_calibrate_topk: the mean row lives in the output when there is one
+        if (!rows) return -18;
+        hipLaunchKernelGGL((mean_topk_kernel<false>), grid, dim3(256), 0, st, logits, P, G, K, a, b, k, idx, scores, (float*)nullptr,
+                           rows);
+    }
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_calibrate_eval(const float* logits, int M, int K, const float* a, const float* b, const int32_t* y, const int32_t* label_map,
                           int n_labels, int32_t* est, float* score, int32_t* rank, float* p_true, long long* totals, long long* confusion,
                           long long* rank_hist, int32_t* scored, float* rowbuf, hipStream_t st)
@@ -1505,6 +1639,15 @@ int launch_crop(const uint8_t* image, int H, int W, const int32_t* rowcols, int 
 {
     dim3 grid((224 * 56 + 255) / 256, n, 1);
     hipLaunchKernelGGL(crop_kernel, grid, dim3(256), 0, st, image, H, W, rowcols, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_crop_views(const uint8_t* image, int H, int W, const int32_t* rowcols, const uint8_t* views, int n, uint8_t* out,
+                      hipStream_t st)
+{
+    dim3 grid((224 * 56 + 255) / 256, n, 1);
+    hipLaunchKernelGGL(crop_views_kernel, grid, dim3(256), 0, st, image, H, W, rowcols, views, out);
     LAUNCH_CHECK();
     return 0;
 }

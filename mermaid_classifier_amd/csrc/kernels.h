@@ -267,6 +267,24 @@ int launch_rank_rows(const float* logits, int M, int K, const float* a, const fl
                      const uint8_t* sim_level, int n_levels, int kmax, long long* class_rank_hist, long long* hier_hist, float* rowbuf,
                      hipStream_t st);
 int launch_crop(const uint8_t* image, int H, int W, const int32_t* rowcols, int n, uint8_t* out, hipStream_t st);
+// calibration of the G rows of each point -> their mean per class (left to right in row order, / (float)G) -> the k best classes
+// of the mean, chosen as launch_calibrate_topk chooses them.  logits: (P * G) x K, rows p G .. p G + G - 1 = point p.
+// idx / scores: P x k; proba: P x K means or NULL; rowbuf: P x K scratch floats, needed only when K > 2048 and proba is NULL
+constexpr int VIEWS_MAX = 16;   // view codes 0 .. 15, and at most this many rows per point
+int launch_mean_topk(const float* logits, int P, int G, int K, const float* a, const float* b, int k, int32_t* idx, float* scores,
+                     float* proba, float* rowbuf, hipStream_t st);
+// patch i = view views[i] (masked to 4 bits) of point i (include/mmc.h, "patch views")
+int launch_crop_views(const uint8_t* image, int H, int W, const int32_t* rowcols, const uint8_t* views, int n, uint8_t* out,
+                      hipStream_t st);
+// Patch views, the orientation half: output pixel (i, j) of view v is pixel (by, bx) of the base patch B, so that
+// P = rot90(fliplr(B) if f else B, k = r) with r = v & 3, f = (v >> 2) & 1.  Shared by the kernel and the host cut.
+__host__ __device__ inline void view_source(int v, int i, int j, int& by, int& bx)
+{
+    const int r = v & 3, f = (v >> 2) & 1;
+    const int y = (r & 1) ? j : i, x = (r & 1) ? i : j;           // r odd transposes
+    by = (r & 2) ? 223 - y : y;                                   // r = 2, 3 walk B's rows backwards
+    bx = (f ^ ((r ^ (r >> 1)) & 1)) ? 223 - x : x;                // columns backwards for (r, f) in {(0,1), (1,0), (2,0), (3,1)}
+}
 
 // ---- grouped validation (metrics.hip) ----
 constexpr int GROUP_MAX_BINS = 64;

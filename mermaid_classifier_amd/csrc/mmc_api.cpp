@@ -1674,11 +1674,15 @@ PinnedSlot g_slots[4];
 int g_slot_next = 0;
 std::mutex g_slot_mu;
 // upload path of mmc_crop_patches (dense points on a host image): per-device staging buffers kept between calls
+// (rc holds the points and, behind them, the view codes of mmc_crop_patches_views)
 struct CropStage { void* img = nullptr; size_t img_cap = 0; void* rc = nullptr; size_t rc_cap = 0; hipEvent_t ev = nullptr; };
 CropStage g_crop_stage[16];
 }  // namespace
 
-static int crop_on_host(const uint8_t* img, int H, int W, const int32_t* rowcols, int64_t n, void* out_dev, hipStream_t st)
+// views: one code per point (checked by the caller) or NULL = all 0; view 0 is the row-memcpy cut, every other view goes pixel by
+// pixel through view_source(), the mapping the kernel uses
+static int crop_on_host(const uint8_t* img, int H, int W, const int32_t* rowcols, const uint8_t* views, int64_t n, void* out_dev,
+                        hipStream_t st)
 {
     std::lock_guard<std::mutex> lock(g_slot_mu);
     PinnedSlot& s = g_slots[g_slot_next];
@@ -1697,6 +1701,26 @@ static int crop_on_host(const uint8_t* img, int H, int W, const int32_t* rowcols
     auto cut = [&](int64_t p0, int64_t p1) {
         for (int64_t p = p0; p < p1; ++p) {
             const int row = rowcols[2 * p], col = rowcols[2 * p + 1];
+            const int v = views ? views[p] : 0;
+            if (v != 0) {
+                uint8_t* d = dst + (size_t)p * psz;
+                for (int i = 0; i < IMG; ++i)
+                    for (int j = 0; j < IMG; ++j, d += 3) {
+                        int by, bx;
+                        view_source(v, i, j, by, bx);
+                        if (!(v & 8)) {
+                            const uint8_t* src = img + ((size_t)refl(row - IMG / 2 + by, H) * W + refl(col - IMG / 2 + bx, W)) * 3;
+                            d[0] = src[0]; d[1] = src[1]; d[2] = src[2];
+                        } else {   // the 2x2 footprint in the 448-pixel window, rounded mean
+                            const size_t y0 = (size_t)refl(row - IMG + 2 * by, H) * W, y1 = (size_t)refl(row - IMG + 2 * by + 1, H) * W;
+                            const int x0 = refl(col - IMG + 2 * bx, W), x1 = refl(col - IMG + 2 * bx + 1, W);
+                            for (int c = 0; c < 3; ++c)
+                                d[c] = (uint8_t)((img[(y0 + x0) * 3 + c] + img[(y0 + x1) * 3 + c] + img[(y1 + x0) * 3 + c] +
+                                                  img[(y1 + x1) * 3 + c] + 2) >> 2);
+                        }
+                    }
+                continue;
+            }
             const int sx0 = col - IMG / 2;
             const bool inside = sx0 >= 0 && sx0 + IMG <= W;
             for (int y = 0; y < IMG; ++y) {
@@ -1729,14 +1753,19 @@ static int crop_on_host(const uint8_t* img, int H, int W, const int32_t* rowcols
     return MMC_OK;
 }
 
-extern "C" int mmc_crop_patches(const void* image, int height, int width, const int32_t* rowcols, int64_t n,
-                                void* patches_out_dev, unsigned flags, int device, void* hip_stream)
+// mmc_crop_patches (with_views false: crop_kernel and the row-memcpy cut, as ever) and mmc_crop_patches_views (views may be NULL)
+static int crop_patches(const void* image, int height, int width, const int32_t* rowcols, int64_t n, bool with_views,
+                        const uint8_t* views, void* patches_out_dev, unsigned flags, int device, void* hip_stream)
 {
     if (!image || !rowcols || !patches_out_dev) return fail(MMC_ERR_ARG, "NULL argument");
     if (n < 0 || n > 65535) return fail(MMC_ERR_ARG, "n = %lld out of range [0,65535]", (long long)n);
     if (n == 0) return MMC_OK;
     if (height <= IMG || width <= IMG)
         return fail(MMC_ERR_ARG, "image %dx%d must exceed the crop size %d in both dimensions", height, width, IMG);
+    if (views && (flags & MMC_IN_HOST))   // host codes are checked (no device needed); device codes are masked by the kernel
+        for (int64_t i = 0; i < n; ++i)
+            if (views[i] >= VIEWS_MAX)
+                return fail(MMC_ERR_ARG, "view code %d of patch %lld is outside [0, 15]", (int)views[i], (long long)i);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     HIP_TRY(hipSetDevice(device));
     const uint8_t* img = static_cast<const uint8_t*>(image);
@@ -1753,11 +1782,11 @@ extern "C" int mmc_crop_patches(const void* image, int height, int width, const 
         // ring slot -- and upload only the patches.  Dense points keep the upload + crop_kernel path.  MMC_CROP_HOST=0/1 forces.
         static const int force = [] { const char* e = getenv("MMC_CROP_HOST"); return e ? atoi(e) : -1; }();
         const bool host_crop = force >= 0 ? force != 0 : (size_t)n * IMG * IMG * 3 * 6 <= ib;
-        if (host_crop) return crop_on_host(img, height, width, rowcols, n, patches_out_dev, st);
+        if (host_crop) return crop_on_host(img, height, width, rowcols, views, n, patches_out_dev, st);
         // dense points: upload the image once into a per-device staging buffer that is kept between calls (grown on demand)
         std::lock_guard<std::mutex> lock(g_slot_mu);
         CropStage& cs = g_crop_stage[device & 15];
-        const size_t rb = (size_t)n * 8;
+        const size_t rb = (size_t)n * 8 + (views ? (size_t)n : 0);
         if (cs.img_cap < ib) {
             if (cs.img) { hipStreamSynchronize(st); hipFree(cs.img); }
             cs.img = nullptr; cs.img_cap = 0;
@@ -1774,17 +1803,34 @@ extern "C" int mmc_crop_patches(const void* image, int height, int width, const 
         if (cs.ev) HIP_TRY(hipStreamWaitEvent(st, cs.ev, 0));
         else HIP_TRY(hipEventCreateWithFlags(&cs.ev, hipEventDisableTiming));
         HIP_TRY(hipMemcpyAsync(cs.img, image, ib, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(cs.rc, rowcols, rb, hipMemcpyHostToDevice, st));
-        int r = launch_crop(static_cast<const uint8_t*>(cs.img), height, width, static_cast<const int32_t*>(cs.rc), (int)n,
-                            static_cast<uint8_t*>(patches_out_dev), st);
+        HIP_TRY(hipMemcpyAsync(cs.rc, rowcols, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        const uint8_t* vdev = views ? static_cast<const uint8_t*>(cs.rc) + (size_t)n * 8 : nullptr;
+        if (views) HIP_TRY(hipMemcpyAsync(const_cast<uint8_t*>(vdev), views, (size_t)n, hipMemcpyHostToDevice, st));
+        int r = with_views ? launch_crop_views(static_cast<const uint8_t*>(cs.img), height, width, static_cast<const int32_t*>(cs.rc),
+                                               vdev, (int)n, static_cast<uint8_t*>(patches_out_dev), st)
+                           : launch_crop(static_cast<const uint8_t*>(cs.img), height, width, static_cast<const int32_t*>(cs.rc), (int)n,
+                                         static_cast<uint8_t*>(patches_out_dev), st);
         HIP_TRY(hipEventRecord(cs.ev, st));
         // the host image / rowcols are pageable caller memory the caller may free or overwrite right after this call
         HIP_TRY(hipStreamSynchronize(st));
         if (r) return fail(MMC_ERR_HIP, "crop kernel launch failed (%d)", r);
         return MMC_OK;
     }
-    // device-resident image and points: the kernel clamps each point into the image (see crop_kernel)
-    int r = launch_crop(img, height, width, rc, (int)n, static_cast<uint8_t*>(patches_out_dev), st);
+    // device-resident image and points: the kernel clamps each point into the image (see crop_kernel) and masks each view code
+    int r = with_views ? launch_crop_views(img, height, width, rc, views, (int)n, static_cast<uint8_t*>(patches_out_dev), st)
+                       : launch_crop(img, height, width, rc, (int)n, static_cast<uint8_t*>(patches_out_dev), st);
     if (r) return fail(MMC_ERR_HIP, "crop kernel launch failed (%d)", r);
     return MMC_OK;
+}
+
+extern "C" int mmc_crop_patches(const void* image, int height, int width, const int32_t* rowcols, int64_t n,
+                                void* patches_out_dev, unsigned flags, int device, void* hip_stream)
+{
+    return crop_patches(image, height, width, rowcols, n, false, nullptr, patches_out_dev, flags, device, hip_stream);
+}
+
+extern "C" int mmc_crop_patches_views(const void* image, int height, int width, const int32_t* rowcols, int64_t n, const uint8_t* views,
+                                      void* patches_out_dev, unsigned flags, int device, void* hip_stream)
+{
+    return crop_patches(image, height, width, rowcols, n, true, views, patches_out_dev, flags, device, hip_stream);
 }

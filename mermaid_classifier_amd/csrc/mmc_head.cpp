@@ -145,13 +145,14 @@ static const int64_t HEAD_CHUNK = 65536;
 // of HEAD_CHUNK; per chunk it grows the activation buffers, runs the Linear layers and calls each(offset, rows, logits), which
 // enqueues what its entry point does with the logits (and synchronises, if it must, before the next chunk reuses the buffers).
 // predict, top-k and evaluate all come through here, so the same rows see the same launches and give the same bits.
+// (`chunk`: mmc_head_topk_views walks in the largest multiple of its G rows per point below HEAD_CHUNK, so no point is split.)
 template <class F>
-static int head_for_chunks(mmc_head* h, const float* x, int64_t n, unsigned flags, hipStream_t st, F each)
+static int head_for_chunks(mmc_head* h, const float* x, int64_t n, unsigned flags, hipStream_t st, F each, int64_t chunk = HEAD_CHUNK)
 {
     int wmax = h->K;
     for (int d : h->dims_pad) wmax = d > wmax ? d : wmax;
-    for (int64_t off = 0; off < n; off += HEAD_CHUNK) {
-        const int cur = (int)((n - off) < HEAD_CHUNK ? (n - off) : HEAD_CHUNK);
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int cur = (int)((n - off) < chunk ? (n - off) : chunk);
         int r;
         if ((r = h->buf0.reserve((int64_t)cur * wmax)) || (r = h->buf1.reserve((int64_t)cur * wmax)) ||
             (r = h->in_stage.reserve((int64_t)cur * h->in_pad)) || (r = h->proba_stage.reserve((int64_t)cur * h->K)) ||
@@ -217,6 +218,45 @@ extern "C" int mmc_head_topk(mmc_head* h, const float* feats, int64_t n, int k, 
         }
         return MMC_OK;
     });
+}
+
+static_assert(MMC_VIEWS_MAX == VIEWS_MAX, "include/mmc.h and kernels.h disagree on the views per point");
+extern "C" int mmc_head_topk_views(mmc_head* h, const float* feats, int64_t n_points, int G, int k, int32_t* idx, float* scores,
+                                   float* proba, unsigned flags, void* hip_stream)
+{
+    if (G < 1 || G > VIEWS_MAX) return fail(MMC_ERR_ARG, "G = %d views per point is outside [1, %d]", G, VIEWS_MAX);
+    if (k < 1) return fail(MMC_ERR_ARG, "k = %d must be at least 1", k);
+    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
+    if (n_points < 0) return fail(MMC_ERR_ARG, "n_points = %lld is negative", (long long)n_points);
+    if (k > h->K) return fail(MMC_ERR_ARG, "k = %d is outside [1, %d] (the head has %d classes)", k, h->K, h->K);
+    if (n_points == 0) return MMC_OK;
+    if (!feats) return fail(MMC_ERR_ARG, "feats is NULL");
+    if (!idx || !scores) return fail(MMC_ERR_ARG, "idx/scores is NULL");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipSetDevice(h->device));
+    const bool out_host = (flags & MMC_OUT_HOST) != 0;
+    const int64_t chunk = HEAD_CHUNK / G * G;   // rows: whole points only
+    if (out_host) {
+        const int64_t stage = (n_points < chunk / G ? n_points : chunk / G) * k;
+        int r;
+        if ((r = h->topk_idx_stage.reserve(stage)) || (r = h->topk_score_stage.reserve(stage))) return r;
+    }
+    // the means of a chunk's points go to the front of proba_stage (rows x K floats: room for points x K)
+    return head_for_chunks(h, feats, n_points * G, flags, st, [&](int64_t off, int cur, const float* logits) -> int {
+        const int64_t p0 = off / G;
+        const int pts = cur / G;
+        int32_t* iout = out_host ? h->topk_idx_stage.p : idx + (size_t)p0 * k;
+        float* sout = out_host ? h->topk_score_stage.p : scores + (size_t)p0 * k;
+        float* pout = proba ? (out_host ? h->proba_stage.p : proba + (size_t)p0 * h->K) : nullptr;
+        KTRY(launch_mean_topk(logits, pts, G, h->K, h->a, h->bc, k, iout, sout, pout, h->proba_stage.p, st));
+        if (out_host) {
+            HIP_TRY(hipMemcpyAsync(idx + (size_t)p0 * k, iout, (size_t)pts * k * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(scores + (size_t)p0 * k, sout, (size_t)pts * k * 4, hipMemcpyDeviceToHost, st));
+            if (proba) HIP_TRY(hipMemcpyAsync(proba + (size_t)p0 * h->K, pout, (size_t)pts * h->K * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return MMC_OK;
+    }, chunk);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -889,6 +929,39 @@ extern "C" int mmc_classify_patches(mmc_backbone* bb, mmc_head* h, const void* p
         const int64_t cur = (n - off) < CLASSIFY_CHUNK ? (n - off) : CLASSIFY_CHUNK;
         if ((r = mmc_backbone_extract(bb, in + (size_t)off * psz, cur, h->cls_feats.p, flags & MMC_IN_HOST, st))) return r;
         if ((r = mmc_head_topk(h, h->cls_feats.p, cur, k, idx + (size_t)off * k, scores + (size_t)off * k, nullptr, flags & MMC_OUT_HOST, st)))
+            return r;
+    }
+    return MMC_OK;
+}
+
+extern "C" int mmc_classify_patches_views(mmc_backbone* bb, mmc_head* h, const void* patches, int64_t n_points, int G, int k, int32_t* idx,
+                                          float* scores, unsigned flags, void* hip_stream)
+{
+    if (G < 1 || G > VIEWS_MAX) return fail(MMC_ERR_ARG, "G = %d views per point is outside [1, %d]", G, VIEWS_MAX);
+    if (k < 1) return fail(MMC_ERR_ARG, "k = %d must be at least 1", k);
+    if (!bb) return fail(MMC_ERR_ARG, "backbone handle is NULL");
+    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
+    if (mmc_backbone_device(bb) != h->device)
+        return fail(MMC_ERR_ARG, "backbone lives on device %d, head on device %d", mmc_backbone_device(bb), h->device);
+    if (mmc_feature_dim(bb) != h->input_dim)
+        return fail(MMC_ERR_ARG, "backbone feature_dim %d != head input_dim %d", mmc_feature_dim(bb), h->input_dim);
+    if (n_points < 0) return fail(MMC_ERR_ARG, "n_points = %lld is negative", (long long)n_points);
+    if (k > h->K) return fail(MMC_ERR_ARG, "k = %d is outside [1, %d] (the head has %d classes)", k, h->K, h->K);
+    if (n_points == 0) return MMC_OK;
+    if (!patches) return fail(MMC_ERR_ARG, "patches is NULL");
+    if (!idx || !scores) return fail(MMC_ERR_ARG, "idx/scores is NULL");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t chunk = CLASSIFY_CHUNK / G * G, n = n_points * G;   // patches: whole points only
+    int r = h->cls_feats.reserve((n < chunk ? n : chunk) * h->input_dim);
+    if (r) return r;
+    const size_t psz = (size_t)MMC_PATCH * MMC_PATCH * 3;
+    const uint8_t* in = static_cast<const uint8_t*>(patches);
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t cur = (n - off) < chunk ? (n - off) : chunk, p0 = off / G;
+        if ((r = mmc_backbone_extract(bb, in + (size_t)off * psz, cur, h->cls_feats.p, flags & MMC_IN_HOST, st))) return r;
+        if ((r = mmc_head_topk_views(h, h->cls_feats.p, cur / G, G, k, idx + (size_t)p0 * k, scores + (size_t)p0 * k, nullptr,
+                                     flags & MMC_OUT_HOST, st)))
             return r;
     }
     return MMC_OK;

@@ -181,7 +181,8 @@ def classify_sharded(classify_fn: Callable, patches, k: int, group=None):
     """Each rank classifies its block of `patches` (indexable, length n_total; only the local block is touched) with
     ``classify_fn(block, k) -> (idx (n_local, k) int32, scores (n_local, k) float32)`` -- e.g. ``PointClassifier.topk_device`` --
     and gets the gathered (n_total, k) indices and scores back.  ``k`` must not exceed the number of classes (the blocks of
-    all ranks need one width)."""
+    all ranks need one width).  Shards are cut on rows: a batch of several views per point (``views_per_point`` > 1) would be
+    split inside a point and is out of scope here -- shard the points yourself and classify each shard with views."""
     import torch.distributed as dist
 
     world = dist.get_world_size(group)

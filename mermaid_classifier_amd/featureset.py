@@ -77,7 +77,10 @@ class FeatureSet:
         return np.ascontiguousarray(idx.astype(np.int32))
 
     def append(self, X, y) -> "FeatureSet":
-        """Host rows ``X`` (n, dim) with labels ``y`` (n,) out of ``classes``."""
+        """Host rows ``X`` (n, dim) with labels ``y`` (n,) out of ``classes``.
+        Patch views as augmentation need nothing more: ``append(F, np.repeat(y, G))`` of one image's
+        ``BatchedExtractor.extract_images(..., views=views)`` rows ``F`` (G = len(views), point-major) adds G rows per annotation.
+        Keep the views of one annotation in one split: split by annotation first, expand to views afterwards."""
         X_arr = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
         if X_arr.ndim != 2:
             raise ValueError(f"X must be 2D, got shape {X_arr.shape}")

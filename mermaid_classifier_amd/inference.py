@@ -25,7 +25,7 @@ from typing import Any, List, Sequence
 import numpy as np
 
 from . import _lib
-from .backbone import _current_stream_ptr, _device_index
+from .backbone import _current_stream_ptr, _device_index, check_views_per_point
 
 SCHEMA_VERSION = 1
 TASK_NAME = "pyspacer_mlp_classifier"
@@ -161,19 +161,26 @@ class DeviceHead:
                                                    _current_stream_ptr(self.device_index)))
         return proba, arg
 
-    def topk(self, feats, k: int, want_proba: bool = False):
+    def topk(self, feats, k: int, want_proba: bool = False, views_per_point: int = 1):
         """The k best classes per row (mmc_head_topk): feats as in ``predict``.  Returns (idx (N,k) int32, scores (N,k)
         float32) of the same kind as ``feats`` -- plus the (N,K) float32 probabilities when ``want_proba`` -- ordered like the
         reference's ``sorted(zip(labels, proba), key=itemgetter(1), reverse=True)[:k]`` (annotation.py:253-255): score
-        descending, equal scores in class order.  1 <= k <= K."""
+        descending, equal scores in class order.  1 <= k <= K.
+        ``views_per_point`` = G > 1 (mmc_head_topk_views): rows ``p*G .. p*G+G-1`` are the views of point ``p``; the outputs have
+        N / G rows, ranked on the fp32 mean of the views' probabilities (summed in row order, divided by G), which is also what
+        ``want_proba`` returns."""
         k = int(k)
         if not 1 <= k <= self.n_classes:
             raise ValueError(f"k = {k} is outside [1, {self.n_classes}]")
         x, ptr, n, flags, alloc = self._input(feats)
-        (idx, ip), (scores, sp) = alloc((n, k), "int32"), alloc((n, k), "float32")
-        proba, pp = alloc((n, self.n_classes), "float32") if want_proba else (None, None)
-        if n:
+        g = check_views_per_point(n, views_per_point)
+        m = n // g
+        (idx, ip), (scores, sp) = alloc((m, k), "int32"), alloc((m, k), "float32")
+        proba, pp = alloc((m, self.n_classes), "float32") if want_proba else (None, None)
+        if n and g == 1:
             _lib.check(_lib.lib().mmc_head_topk(self._h, ptr, n, k, ip, sp, pp, flags, _current_stream_ptr(self.device_index)))
+        elif n:
+            _lib.check(_lib.lib().mmc_head_topk_views(self._h, ptr, m, g, k, ip, sp, pp, flags, _current_stream_ptr(self.device_index)))
         return (idx, scores, proba) if want_proba else (idx, scores)
 
 
@@ -203,20 +210,23 @@ class Predictor:
         _, arg = self._head.predict(arr, want_argmax=True)
         return [self.classes[i] for i in arg.tolist()]
 
-    def predict_topk(self, features: Any, k: int = 1):
+    def predict_topk(self, features: Any, k: int = 1, views_per_point: int = 1):
         """The per-point ranking of AnnotationRun (annotation.py:251-261) for a feature batch: (labels, scores) with
         ``labels[i]`` the ``k' = min(k, K)`` best class names of row i and ``scores`` the float64 ``(N, k')`` calibrated
         probabilities beside them -- ``sorted(zip(classes, predict_proba(features)[i]), key=itemgetter(1), reverse=True)[:k]``
-        (the slice clamps k the same way), ranked on the device: only N x k' indices and scores come back."""
+        (the slice clamps k the same way), ranked on the device: only N x k' indices and scores come back.
+        ``views_per_point`` = G: rows ``p*G .. p*G+G-1`` are the features of G views of point ``p`` (``extract_images(..., views=...)``
+        returns them so); one ranking per point, of the mean of its views' probabilities (``DeviceHead.topk``)."""
         if int(k) != k or k < 1:
             raise ValueError(f"k must be an integer >= 1; got {k!r}")
         arr = np.asarray(features, dtype=np.float32)
         if arr.ndim != 2 or arr.shape[1] != self.input_dim:
             raise ValueError(f"features must be (N, {self.input_dim}); got {arr.shape}.")
+        g = check_views_per_point(arr.shape[0], views_per_point)
         kk = min(int(k), len(self.classes))
         if arr.shape[0] == 0:
             return [], np.zeros((0, kk), dtype=np.float64)
-        idx, scores = self._head.topk(arr, kk)
+        idx, scores = self._head.topk(arr, kk, views_per_point=g)
         return [[self.classes[j] for j in row] for row in idx.tolist()], scores.astype(np.float64)
 
 

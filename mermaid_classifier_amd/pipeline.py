@@ -18,7 +18,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .backbone import Backbone, PATCH, _current_stream_ptr
+from .backbone import Backbone, PATCH, _current_stream_ptr, check_views
 from .spacer_shim import ImageFeatures, PointFeatures
 
 
@@ -54,7 +54,14 @@ class PatchBatcher:
     compute stream, the previous pass's results collected from pinned memory while the next one runs.  A subclass says what a
     pass is: ``_launch(slot, patches, fill, ctx)`` enqueues the work on the current stream, ``_download(slot, fill, ctx)`` the copy of
     its results into pinned memory, ``_fetch(slot, count, ctx)`` returns them (a tuple of host arrays with ``count`` rows each) once
-    the pass is done."""
+    the pass is done.
+
+    With ``views`` (``backbone.check_views``) other than ``(0,)`` every point is cut G = len(views) times, point-major, by
+    ``mmc_crop_patches_views``; a point's G patches never straddle a pass (for the run the buffer capacity is rounded down to a
+    multiple of G).  ``fill`` counts patches; ``_download`` / ``_fetch`` count result rows: G per point, or one per point for a
+    subclass with ``mean_over_views`` (its pass averages a point's views)."""
+
+    mean_over_views = False
 
     def __init__(self, backbone: Backbone, batch_patches: int = 1024):
         import torch
@@ -78,6 +85,16 @@ class PatchBatcher:
                                                dst.data_ptr(), _lib.MMC_IN_HOST, self.bb.device_index,
                                                int(self._copy_stream.cuda_stream)))
 
+    def _crop_views_into(self, image: np.ndarray, rowcols: np.ndarray, views: Tuple[int, ...], offset: int) -> None:
+        g = len(views)
+        rc = np.ascontiguousarray(np.repeat(rowcols, g, axis=0))
+        codes = np.ascontiguousarray(np.tile(np.asarray(views, np.uint8), rowcols.shape[0]))
+        n = rc.shape[0]
+        dst = self._buf[offset:offset + n]
+        _lib.check(_lib.lib().mmc_crop_patches_views(image.ctypes.data, image.shape[0], image.shape[1], rc.ctypes.data, n,
+                                                     codes.ctypes.data, dst.data_ptr(), _lib.MMC_IN_HOST, self.bb.device_index,
+                                                     int(self._copy_stream.cuda_stream)))
+
     def _launch(self, slot: int, patches, fill: int, ctx) -> None:
         raise NotImplementedError
 
@@ -87,10 +104,17 @@ class PatchBatcher:
     def _fetch(self, slot: int, count: int, ctx) -> tuple:
         raise NotImplementedError
 
-    def _run(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]], ctx=None):
+    def _run(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]], ctx=None,
+             views: Tuple[int, ...] = (0,)):
         """-> (per image: a tuple of arrays, one per result kind, rows in ``rowcols`` order; None for an image without points,
         the checked (n, 2) int32 points per image)."""
         import torch
+        plain = tuple(views) == (0,)                # today's path: mmc_crop_patches, one patch and one result row per point
+        g = len(views)
+        if self.cap < g:
+            raise ValueError(f"batch_patches = {self.cap} cannot hold the {g} views of one point")
+        cap = self.cap // g * g                     # patches per pass: whole points only
+        rpp = 1 if self.mean_over_views else g      # result rows per point
         out: List[Optional[tuple]] = []
         points: List[np.ndarray] = []
         pending: List[Tuple[int, int, int]] = []   # (image index, offset in buffer, n)
@@ -116,9 +140,9 @@ class PatchBatcher:
             compute.wait_stream(self._copy_stream)              # the cuts of this buffer have landed
             self._launch(cur, self._bufs[cur][:fill], fill, ctx)   # asynchronous on the compute stream
             self._free[cur].record(compute)
-            self._download(cur, fill, ctx)                       # pinned: the D2H is stream-ordered too
+            self._download(cur, fill // g * rpp, ctx)            # pinned: the D2H is stream-ordered too
             self._done[cur].record(compute)
-            job = (cur, fill, pending)
+            job = (cur, fill // g * rpp, pending)
             if in_flight is not None:
                 collect(in_flight)                               # the previous pass; this one keeps running meanwhile
             in_flight = job
@@ -133,13 +157,16 @@ class PatchBatcher:
             points.append(rc)
             start = 0
             while start < len(rc):                      # an image with more points than the buffer spans flushes
-                take = min(len(rc) - start, self.cap - fill)
+                take = min(len(rc) - start, (cap - fill) // g)             # points
                 if take == 0:
                     flush()
                     continue
-                self._crop_into(im, rc[start:start + take], fill)
-                pending.append((idx, fill, take))
-                fill += take
+                if plain:
+                    self._crop_into(im, rc[start:start + take], fill)
+                else:
+                    self._crop_views_into(im, rc[start:start + take], views, fill)
+                pending.append((idx, fill // g * rpp, take * rpp))
+                fill += take * g
                 start += take
         flush()
         if in_flight is not None:
@@ -167,9 +194,13 @@ class BatchedExtractor(PatchBatcher):
     def _fetch(self, slot, count, ctx):
         return (self._host[slot][:count].numpy().copy(),)
 
-    def extract_images(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]]) -> List[np.ndarray]:
-        """-> one (n_points, 1280) float32 array per image (empty arrays for images without points)."""
-        out, _ = self._run(images, rowcols_per_image)
+    def extract_images(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]],
+                       views: Sequence[int] = (0,)) -> List[np.ndarray]:
+        """-> one (n_points * G, 1280) float32 array per image (empty arrays for images without points), G = len(views): row
+        ``p*G + g`` is view ``views[g]`` (``backbone.check_views``) of point ``p``.  ``views=(0,)`` is one row per point, through the
+        calls and with the bits of before views existed.  ``batch_patches < G`` is a ValueError."""
+        vw = check_views(views)
+        out, _ = self._run(images, rowcols_per_image, views=vw)
         return [o[0] if o is not None else np.zeros((0, self.bb.feature_dim), np.float32) for o in out]
 
     def extract_image_features(self, images, rowcols_per_image) -> List[ImageFeatures]:

@@ -142,7 +142,9 @@ def subsample_rows(labels, targets_by_class_index: Mapping[int, int], order=None
     ``target`` rows of that class in ``order`` -- the ``_rn <= target_n`` of dataset.py:292-310, whose ``ROW_NUMBER()`` runs over
     the primary-key order within a class.  ``labels`` are class indices (array or ``FeatureSet``); ``order`` is a permutation of
     the row indices standing for the primary-key order (``order[0]`` is the first row), ``None`` the stored order.  A class
-    without a target is dropped (the inner join of :300-310); a target above the class's row count is a ``ValueError``."""
+    without a target is dropped (the inner join of :300-310); a target above the class's row count is a ``ValueError``.
+    Rows are rows: in a set built from ``extract_images(..., views=...)`` every annotation has G of them (its views), and a
+    subsample counts and keeps views, not annotations.  The views of one annotation must stay in one split."""
     y = _label_indices(labels).astype(np.int64)
     n = len(y)
     if order is None:
