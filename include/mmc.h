@@ -597,6 +597,64 @@ int mmc_head_evaluate_ranked_set(mmc_head* h, mmc_featureset* fs, int64_t first,
                                  int64_t* class_rank_hist /* K*K or NULL */, int64_t* hier_hist /* kmax*n_levels or NULL */,
                                  void* hip_stream);
 
+/* ---- cover estimation: counts, soft cover, EM prior adaptation -------------------------------------------------------------
+ * Extends: compute_cover's predicted counts (mermaid_classifier/pyspacer/metrics/cover.py:49-60), which exist in the reference only
+ *   as a validation metric, to the serving side: percent cover per image, transect or source, from the calibrated probabilities
+ *   where they lie.  docs/research/hidden-layer-experiments.md section 5 names cover R^2 as the metric of record, and
+ *   docs/research/balancing-experiments.md closes on a per-source accuracy range that balancing does not remove: the signature of
+ *   label shift.  mmc_trainer_set_loss's logit_prior is the training-time half of the standard remedy; this is the test-time half
+ *   (Saerens, Latinne and Decaestecker 2002): each group's class prior is re-estimated from its calibrated probabilities by EM, and
+ *   cover and labels are read off the adapted posteriors.  No reference counterpart: THIS TEXT IS THE DEFINITION.
+ * Rows are points.  v is a point's calibrated probability row with the bits mmc_head_predict writes; with G > 1 views per point, v
+ *   is the mean m that mmc_head_topk_views writes.  Groups are contiguous: group g owns points [group_offsets[g], group_offsets[g+1])
+ *   (group_offsets[0] = 0, never decreasing -- a group may be empty --, group_offsets[n_groups] = n).  A point is USABLE when all K
+ *   values are finite; unusable points are counted in unusable[g] and enter nothing else.  n_g is the number of usable points of
+ *   group g.  train_prior: K doubles, every entry > 0, summing to 1 within 1e-6; NULL means 1/K.
+ * Per group (host pointers; count, soft_q32, prior: n_groups x K, unusable: n_groups):
+ *   count[g*K + c]     int64: the usable points whose first maximum is c -- est of mmc_head_evaluate, cover.py's predicted count.
+ *   soft_q32[g*K + c]  int64: the sum over the usable points of llrint((double)v[c] * 2^32).  Order-free and exact.
+ *   prior[g*K + c]     fp64: pi_iters[c] of the EM that starts from pi_0 = train_prior and runs for t = 1 .. iters:
+ *                        w      = pi_{t-1} / train_prior                                         in fp64
+ *                        tq[c]  = (double)v[c] * w[c],  Z = sum_c tq[c]                          per usable point
+ *                        q      = tq / Z when Z is finite and > 0, otherwise q = (double)v
+ *                        pi_t[c] = (sum over the usable points of q[c] + strength * train_prior[c]) / (n_g + strength)
+ *                      strength >= 0 is a Dirichlet pseudo-count (with strength = 0 a 25-point image collapses onto the classes it
+ *                      shows).  A group with n_g = 0 keeps train_prior.
+ *   Sum order: the order of the fp64 sums on the device is unspecified; it depends only on group_offsets and K, so a repeated call
+ *   returns the same bits.  No float atomics are used.
+ * Adapted top-k (idx / scores: n x k, host with MMC_OUT_HOST in flags, else on the device; both NULL: skipped, and k is ignored):
+ *   q is computed from w = pi_iters / train_prior as above (for every point: an unusable point has a non-finite Z, so q = v),
+ *   score = (float)q[c], and the k best classes are chosen by the key rule of mmc_head_topk: fp32 score descending (by bit pattern),
+ *   equal scores in class order, k distinct classes even for unusable rows.
+ * Everything is checked before the first launch: n < 0, n * K > MMC_COVER_MAX_CELLS, n_groups < 0 or n_groups * K >
+ *   MMC_COVER_MAX_CELLS, offsets not starting at 0, decreasing or not ending at n (n_groups = 0 needs n = 0), a train_prior entry
+ *   that is not a positive finite number or a sum off 1 by more than 1e-6, strength negative or not finite, iters outside
+ *   [0, MMC_COVER_MAX_ITERS], idx without scores or the reverse, k outside [1, K] when they are given, NULL tables, G outside
+ *   [1, MMC_VIEWS_MAX], the set's width / device / rows.  A rejected call returns MMC_ERR_ARG, launches nothing and zeroes every
+ *   host output whose size the arguments determine (the tables when n_groups * K is within the cap; idx / scores when they are host
+ *   memory and n, k are valid).  n = 0 is MMC_OK: zero counts, and train_prior in every row of prior.
+ * mmc_cover_proba runs the stage on caller probabilities (n x K fp32, host with MMC_IN_HOST in flags, else on `device`): for
+ *   probabilities made elsewhere, and for checking the stage per element.  Its scratch is kept per device for the life of the process.
+ * mmc_head_cover / mmc_head_cover_set score feats ((n_points * G) x input_dim, host with MMC_IN_HOST, else on the head's device) or
+ *   rows [first, first + n_points * G) of a feature set through the head's chunk loop -- the launches of mmc_head_predict (G = 1) or
+ *   mmc_head_topk_views (G > 1), each chunk written straight into a resident n_points x K matrix -- and run the stage on it.  The
+ *   matrix and the stage's scratch belong to the head handle, grow on demand and are freed with it: a repeated call allocates nothing.
+ * Each call synchronises `hip_stream` once, at the end: uploads, chunks, the two launches of every EM iteration and the copies
+ *   back are enqueued back to back.  One caller at a time per handle; mmc_cover_proba calls are serialised inside the library. */
+#define MMC_COVER_MAX_ITERS 1000
+#define MMC_COVER_MAX_CELLS 1073741824LL  /* 2^30: 4 GiB of resident probabilities */
+int mmc_cover_proba(const float* proba /* n x K */, int64_t n, int K, const int64_t* group_offsets /* n_groups + 1 */, int64_t n_groups,
+                    const double* train_prior /* K or NULL */, double strength, int iters, int64_t* count, int64_t* soft_q32,
+                    int64_t* unusable, double* prior, int k, int32_t* idx /* n x k or NULL */, float* scores /* n x k or NULL */,
+                    int device, unsigned flags, void* hip_stream);
+int mmc_head_cover(mmc_head* h, const float* feats /* (n_points*G) x input_dim */, int64_t n_points, int G,
+                   const int64_t* group_offsets, int64_t n_groups, const double* train_prior, double strength, int iters, int64_t* count,
+                   int64_t* soft_q32, int64_t* unusable, double* prior, int k, int32_t* idx, float* scores, unsigned flags,
+                   void* hip_stream);
+int mmc_head_cover_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n_points, int G, const int64_t* group_offsets,
+                       int64_t n_groups, const double* train_prior, double strength, int iters, int64_t* count, int64_t* soft_q32,
+                       int64_t* unusable, double* prior, int k, int32_t* idx, float* scores, unsigned flags, void* hip_stream);
+
 /* ---- multi-GPU: the gather of the sharded path --------------------------------------------------------------------
  * The path shards by patches (contiguous blocks of the row range per rank, weights replicated, no exchange during compute);
  * its one exchange step is the all-gather of the ranks' (n_r, 1280) feature blocks.  Replaces: nothing in the reference's

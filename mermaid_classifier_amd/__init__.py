@@ -17,6 +17,7 @@ from .validation import Validation, previous_accuracies, validate  # noqa: F401
 from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, category_bins, grouped_validate  # noqa: F401
 from .taxonomy import TaxonomicScores  # noqa: F401
 from .ranking import RankedValidation, ranking_validate, similarity_levels  # noqa: F401
+from .cover import CoverEstimate, estimate_cover, prior_from_labels  # noqa: F401
 
 __all__ = [
     "EfficientNetExtractor", "build_extractor_class", "resolve_device", "verify_device_numerics",
@@ -32,4 +33,5 @@ __all__ = [
     "grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability",
     "ranking_validate", "RankedValidation", "similarity_levels",
     "category_bins", "TaxonomicScores",
+    "estimate_cover", "CoverEstimate", "prior_from_labels",
 ]

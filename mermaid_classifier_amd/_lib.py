@@ -23,6 +23,7 @@ MMC_CATEGORY_MIN_BINS, MMC_CATEGORY_ROWS_PER_BIN = 2, 10   # calibration.py:137:
 MMC_RANKED_MAX_K = 16   # include/mmc.h: selection rounds of mmc_head_evaluate_ranked
 MMC_TRAINER_GROUP_MAX = 16   # include/mmc.h: members of one mmc_trainer_group_partial_fit_set call
 MMC_VIEWS_MAX = 16   # include/mmc.h MMC_VIEWS_MAX: view codes 0..15, and at most 16 views per point
+MMC_COVER_MAX_ITERS, MMC_COVER_MAX_CELLS = 1000, 1 << 30   # include/mmc.h: cover estimation
 
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
@@ -41,6 +42,7 @@ SYMBOLS = [
     "mmc_head_evaluate", "mmc_head_evaluate_set", "mmc_head_evaluate_grouped", "mmc_head_evaluate_grouped_set",
     "mmc_head_evaluate_categories", "mmc_head_evaluate_categories_set",
     "mmc_head_evaluate_ranked", "mmc_head_evaluate_ranked_set",
+    "mmc_cover_proba", "mmc_head_cover", "mmc_head_cover_set",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -197,6 +199,14 @@ def _load() -> C.CDLL:
     lib.mmc_head_evaluate_ranked.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + ranked + [u32, vp]
     lib.mmc_head_evaluate_ranked_set.restype = i32
     lib.mmc_head_evaluate_ranked_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp] + ranked + [vp]
+    # group_offsets, n_groups, train_prior, strength, iters, count, soft_q32, unusable, prior, k, idx, scores
+    cover = [vp, i64, vp, f64, i32, vp, vp, vp, vp, i32, vp, vp]
+    lib.mmc_cover_proba.restype = i32
+    lib.mmc_cover_proba.argtypes = [vp, i64, i32] + cover + [i32, u32, vp]
+    lib.mmc_head_cover.restype = i32
+    lib.mmc_head_cover.argtypes = [vp, vp, i64, i32] + cover + [u32, vp]
+    lib.mmc_head_cover_set.restype = i32
+    lib.mmc_head_cover_set.argtypes = [vp, vp, i64, i64, i32] + cover + [u32, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

@@ -2,7 +2,7 @@
 
     python -m mermaid_classifier_amd.build [--force]
 
-One object per translation unit (the kernels are five .hip files by layer group, plus the trainer, the calibrator, the feature set, the grouped metrics, and the two host units of the C ABI:
+One object per translation unit (the kernels are five .hip files by layer group, plus the trainer, the calibrator, the feature set, the grouped metrics, cover estimation, and the two host units of the C ABI:
 mmc_api.cpp with the backbone schedule and mmc_head.cpp with the calibrated head),
 compiled in parallel and only when the source or one of its headers is newer than the object; then one link.  Objects live in
 csrc/_obj/ (git-ignored and gpurun-ignored: only the linked library travels to the GPU box).
@@ -24,7 +24,7 @@ OUT = HERE / "libmermaid_mi355.so"
 KERNEL_HEADERS = ["device_common.h", "kernels.h"]
 # translation unit -> headers it includes
 SOURCES = {
-    "k_generic.hip": KERNEL_HEADERS,
+    "k_generic.hip": KERNEL_HEADERS + ["topk_key.h"],
     "k_mbconv.hip": KERNEL_HEADERS,
     "k_early.hip": KERNEL_HEADERS,
     "k_mid.hip": KERNEL_HEADERS,
@@ -33,6 +33,7 @@ SOURCES = {
     "calib.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "featureset.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "metrics.hip": ["kernels.h"],
+    "cover.hip": ["kernels.h", "topk_key.h"],
     "mmc_api.cpp": ["kernels.h", "api_internal.h", "../../include/mmc.h"],
     "mmc_head.cpp": ["kernels.h", "api_internal.h", "trainer_internal.h", "../../include/mmc.h"],
     "mmc_dist.cpp": ["../../include/mmc.h"],

@@ -89,6 +89,27 @@ class _Batcher(PatchBatcher):
         return hi[:count].numpy().copy(), hs[:count].numpy().copy()
 
 
+class _FeatureBatcher(PatchBatcher):
+    """PatchBatcher whose pass appends the backbone's device features to a device ``FeatureSet`` (``cover_images``): nothing comes
+    back per pass, the rows stay resident for the one cover call that follows.  One feature buffer per slot, as in
+    ``BatchedExtractor``, so the library's graph cache keeps hitting."""
+
+    def __init__(self, owner: "PointClassifier"):
+        import torch
+        super().__init__(owner.backbone, owner.batch_patches)
+        self._fdev = [torch.empty((self.cap, owner.backbone.feature_dim), dtype=torch.float32, device=self.dev) for _ in range(2)]
+
+    def _launch(self, slot, patches, fill, fs):
+        feats = self.bb.extract(patches, out=self._fdev[slot][:fill])
+        fs.append_device(feats, np.zeros(fill, np.int64))   # (synchronises the stream: the buffer is free when it returns)
+
+    def _download(self, slot, fill, fs):
+        pass
+
+    def _fetch(self, slot, count, fs):
+        return (np.empty((count, 0), np.float32),)
+
+
 class PointClassifier:
     """``Backbone`` + ``Predictor`` as one patches -> labels pipeline on the GPU.  ``batch_patches`` bounds the device patch
     buffers of ``classify_image(s)``, as in ``BatchedExtractor``.  ``k`` is the reference's ``predictions_per_point``; more than
@@ -111,6 +132,7 @@ class PointClassifier:
         self.classes = list(predictor.classes)
         self.batch_patches = int(batch_patches)
         self._batcher: Optional[_Batcher] = None     # device buffers are made on first use
+        self._feature_batcher: Optional[_FeatureBatcher] = None
 
     def _k(self, k) -> int:
         return min(_check_k(k), len(self.classes))
@@ -199,3 +221,35 @@ class PointClassifier:
         """annotation.py:239-261 for one image: ``classify_image(loaded_image, rowcols, k).as_dicts()`` are its ``annotations`` /
         ``scores`` entries."""
         return self.classify_images([image], [list(rowcols)], k)[0]
+
+    def cover_images(self, images: Iterable[np.ndarray], rowcols_per_image: Iterable[Sequence[Tuple[int, int]]], group_of_image=None,
+                     train_prior=None, strength: float = 1.0, iters: int = 20, k: int = 0):
+        """Images + points -> ``cover.CoverEstimate``: percent cover per image, or per run of consecutive images that share an id in
+        ``group_of_image`` (a transect, a source), with ``.topk`` (``k`` > 0) the labels of every point under its group's adapted
+        prior, rows in image and ``rowcols`` order.  The backbone's features go from each pass into a device ``FeatureSet`` and
+        one ``mmc_head_cover_set`` runs over it: neither features nor probabilities visit the host.  With ``views`` a point's views
+        are its G rows.  ``train_prior`` / ``strength`` / ``iters`` / ``k``: ``cover.estimate_cover``.  Host arguments are checked
+        before the GPU is touched; ``.groups`` holds the group ids (image indices without ``group_of_image``)."""
+        from .cover import check_cover_arguments, estimate_cover, image_groups
+        from .featureset import FeatureSet
+        prepared = [prepare_image(i, im, rc) for i, (im, rc) in enumerate(zip(images, rowcols_per_image))]
+        offsets, ids = image_groups([len(rc) for _, rc in prepared], group_of_image)
+        n, g = int(offsets[-1]), len(self.views)
+        check_cover_arguments(n, len(self.classes), offsets, train_prior, strength, iters, k)
+        fs = FeatureSet(self.backbone.feature_dim, [0], device=self.backbone.device_index, reserve=n * g)
+        try:
+            if n:
+                if self._feature_batcher is None:
+                    self._feature_batcher = _FeatureBatcher(self)
+                self._feature_batcher._run([im for im, _ in prepared], [rc for _, rc in prepared], ctx=fs, views=self.views)
+                est = estimate_cover(self.predictor, fs, offsets, train_prior, strength, iters, k, views_per_point=g)
+            else:
+                est = estimate_cover(self.predictor, np.zeros((0, self.predictor.input_dim), np.float32), offsets, train_prior, strength,
+                                     iters, k)
+        finally:
+            fs.close()
+        if est.topk is not None:
+            est.topk = PointPredictions([(int(r), int(c)) for _, rc in prepared for r, c in rc], est.topk.indices, est.topk.scores,
+                                        self.classes)
+        est.groups = ids
+        return est

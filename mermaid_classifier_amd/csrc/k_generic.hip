@@ -20,6 +20,7 @@
 //                           (pyspacer/trainer.py:271-291, metrics/ranking.py:54-65, metrics/probability.py:47-49)
 //   crop_kernel        pyspacer crop_patches (reflect pad + slice)
 #include "device_common.h"
+#include "topk_key.h"
 
 // ---------------------------------------------------------------------------------------------
 // Stem: u8 HWC patch -> conv3x3 stride 2 (TF-same: pad right/bottom by 1) -> +bias -> SiLU -> fp16
@@ -992,10 +993,7 @@ __global__ __launch_bounds__(256) void calibrate_kernel(const float* __restrict_
 // Wider heads keep the same algorithm with the row in `rowbuf` (M x K floats in global memory: the caller's proba or scratch).
 // ---------------------------------------------------------------------------------------------
 #define TOPK_LDS_MAX_K 2048   // 4 rows x 2048 classes x 4 B = 32 KB of LDS per workgroup
-__device__ __forceinline__ unsigned long long topk_key(float v, int cls)
-{
-    return ((unsigned long long)__float_as_uint(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)cls);
-}
+// (topk_key: topk_key.h, shared with cover.hip)
 template <bool ROW_IN_LDS>
 __global__ __launch_bounds__(256) void calibrate_topk_kernel(const float* __restrict__ logits, int M, int K,
                                                              const float* __restrict__ a, const float* __restrict__ bcal, int k,

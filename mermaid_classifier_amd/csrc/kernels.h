@@ -336,3 +336,22 @@ int launch_group_category_counts(const unsigned long long* support, const int32_
 // targets seeded from cat_rows[c] / cat_bins[c] on the device, then the same select and binned sums into this category's sel / raw
 int launch_group_select_category(const uint32_t* keys, const uint8_t* seg, int64_t n, int c, const long long* cat_rows, const int32_t* cat_bins,
                                  uint32_t* ckeys, GroupSelect* sel, uint32_t* hist, unsigned long long* raw, hipStream_t st);
+
+// ---- cover estimation (cover.hip; include/mmc.h "cover estimation") ----
+// P: the resident n x K fp32 probabilities; offsets [n_groups + 1]: offsets[0] = 0 <= ... <= offsets[n_groups] = n (device).
+constexpr int COVER_SLAB_POINTS = 64;   // points per slab of the E-step: one wave walks one slab
+// count / soft [n_groups][K], unusable [n_groups]: int64 tables the caller zeroes; integer atomics only
+int launch_cover_count(const float* P, int64_t n, int K, const int64_t* offsets, int64_t n_groups, unsigned long long* count,
+                       unsigned long long* soft, unsigned long long* unusable, hipStream_t st);
+// pi = train_prior and w = pi / train_prior for every group (pi, w: [n_groups][K] doubles)
+int launch_cover_em_init(const double* train_prior, int64_t n_groups, int K, double* pi, double* w, hipStream_t st);
+// the E-step: slab s = rows [slab_row0[s], min(slab_row0[s] + COVER_SLAB_POINTS, offsets[slab_group[s] + 1])) of group slab_group[s];
+// part [n_slabs][K]: the slab's sum of posteriors under w
+int launch_cover_em_pass(const float* P, int K, const int64_t* slab_row0, const int32_t* slab_group, const int64_t* offsets, int64_t n_slabs,
+                         const double* w, double* part, hipStream_t st);
+// the M-step: group g owns slabs [group_slab0[g], group_slab0[g + 1]); unusable: launch_cover_count's; writes pi and w
+int launch_cover_em_reduce(const double* part, const int64_t* group_slab0, const int64_t* offsets, const unsigned long long* unusable,
+                           const double* train_prior, double strength, int64_t n_groups, int K, double* pi, double* w, hipStream_t st);
+// per point the k best classes of the posterior under w, chosen as launch_calibrate_topk chooses them; idx / scores: n x k
+int launch_cover_adapt_topk(const float* P, int64_t n, int K, const int64_t* offsets, int64_t n_groups, const double* w, int k, int32_t* idx,
+                            float* scores, hipStream_t st);

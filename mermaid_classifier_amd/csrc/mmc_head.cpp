@@ -1,11 +1,13 @@
 // mmc_head.cpp -- the calibrated MLP head of the C ABI (include/mmc.h): create / predict / top-k, the validation passes
-// (mmc_head_evaluate*) and mmc_classify_patches.  Every entry point that scores rows goes through head_for_chunks.
+// (mmc_head_evaluate*), cover estimation (mmc_cover_proba, mmc_head_cover*) and mmc_classify_patches.  Every entry point that scores rows goes through head_for_chunks.
 // Host C++ only; the kernels are launched through kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <vector>
 
 #include "api_internal.h"
@@ -33,6 +35,16 @@ struct DevBuf {
     }
 };
 
+// what a cover call keeps between calls: the resident n x K probabilities, the stage's device state (tables, offsets, slab list,
+// priors, slab sums, top-k staging: cover_layout) and the host side of the slab list
+struct CoverScratch {
+    DevBuf<float> proba;
+    DevBuf<char> dev;
+    std::vector<int64_t> slab_row0, group_slab0;
+    std::vector<int32_t> slab_group;
+    std::vector<double> prior;
+};
+
 struct mmc_head {
     int device = 0, n_layers = 0, K = 0, input_dim = 0, in_pad = 0;
     std::vector<int> dims_pad;        // padded widths (multiples of 4), last = K (unpadded)
@@ -54,6 +66,8 @@ struct mmc_head {
     DevBuf<char> grp;
     // mmc_head_evaluate_ranked*: the int64 class_rank_hist and hier_hist tables, then the uploaded similarity levels
     DevBuf<char> rnk;
+    // mmc_head_cover*: the resident probabilities of the call's points and the cover stage's state
+    CoverScratch cover;
 };
 
 extern "C" void mmc_head_destroy(mmc_head* h)
@@ -896,6 +910,265 @@ extern "C" int mmc_head_evaluate_ranked_set(mmc_head* h, mmc_featureset* fs, int
     const EvalOut o{est, score, rank, p_true, totals, confusion, rank_hist};
     const RankIO k{sim_level, n_levels, kmax, class_rank_hist, hier_hist};
     return evaluate(h, set_rows(fs, first, n), label_map, n_labels, o, nullptr, &k, hip_stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// cover estimation: mmc_cover_proba / mmc_head_cover / mmc_head_cover_set (include/mmc.h, "cover estimation")
+// ------------------------------------------------------------------------------------------
+static_assert(MMC_COVER_MAX_CELLS <= (1LL << 31), "a cover call's cell count must keep every grid of cover.hip in range");
+// the group arguments and outputs of the three cover entry points, in the order of include/mmc.h
+struct CoverIO {
+    const int64_t* offsets; int64_t n_groups; const double* train_prior; double strength; int iters;
+    int64_t *count, *soft, *unusable; double* prior;
+    int k; int32_t* idx; float* scores;
+};
+
+// zeroes every host output whose size the arguments determine
+static void cover_clear(int K, int64_t n, const CoverIO& c, bool out_host)
+{
+    if (c.unusable && c.n_groups > 0 && c.n_groups <= MMC_COVER_MAX_CELLS) memset(c.unusable, 0, (size_t)c.n_groups * 8);   // (needs no K)
+    if (K < 1) return;
+    if (c.n_groups > 0 && c.n_groups <= MMC_COVER_MAX_CELLS / K) {
+        const size_t cells = (size_t)c.n_groups * K;
+        if (c.count) memset(c.count, 0, cells * 8);
+        if (c.soft) memset(c.soft, 0, cells * 8);
+        if (c.prior) memset(c.prior, 0, cells * 8);
+    }
+    if (out_host && c.idx && c.scores && c.k >= 1 && c.k <= K && n > 0 && n <= MMC_COVER_MAX_CELLS / K) {
+        memset(c.idx, 0, (size_t)n * c.k * 4);
+        memset(c.scores, 0, (size_t)n * c.k * 4);
+    }
+}
+
+static int cover_check(int K, int64_t n, const CoverIO& c)
+{
+    if (K < 1) return fail(MMC_ERR_ARG, "K = %d must be positive", K);
+    if (n < 0) return fail(MMC_ERR_ARG, "n = %lld is negative", (long long)n);
+    if (n > MMC_COVER_MAX_CELLS / K)
+        return fail(MMC_ERR_ARG, "n * K = %lld x %d resident probabilities: at most %lld cells per call", (long long)n, K, (long long)MMC_COVER_MAX_CELLS);
+    if (c.n_groups < 0) return fail(MMC_ERR_ARG, "n_groups = %lld is negative", (long long)c.n_groups);
+    if (c.n_groups > MMC_COVER_MAX_CELLS / K)
+        return fail(MMC_ERR_ARG, "n_groups * K = %lld x %d table cells: at most %lld", (long long)c.n_groups, K, (long long)MMC_COVER_MAX_CELLS);
+    if (c.n_groups > 0 && (!c.count || !c.soft || !c.unusable || !c.prior)) return fail(MMC_ERR_ARG, "count/soft_q32/unusable/prior is NULL");
+    if (!(c.strength >= 0.0) || std::isinf(c.strength)) return fail(MMC_ERR_ARG, "strength = %g must be finite and >= 0", c.strength);
+    if (c.iters < 0 || c.iters > MMC_COVER_MAX_ITERS) return fail(MMC_ERR_ARG, "iters = %d outside [0, %d]", c.iters, MMC_COVER_MAX_ITERS);
+    if ((c.idx == nullptr) != (c.scores == nullptr)) return fail(MMC_ERR_ARG, "idx and scores come together or not at all");
+    if (c.idx && (c.k < 1 || c.k > K)) return fail(MMC_ERR_ARG, "k = %d is outside [1, %d]", c.k, K);
+    if (c.train_prior) {
+        double sum = 0.0;
+        for (int j = 0; j < K; ++j) {
+            if (!(c.train_prior[j] > 0.0) || std::isinf(c.train_prior[j]))
+                return fail(MMC_ERR_ARG, "train_prior[%d] = %g must be a positive finite number", j, c.train_prior[j]);
+            sum += c.train_prior[j];
+        }
+        if (!(std::fabs(sum - 1.0) <= 1e-6)) return fail(MMC_ERR_ARG, "train_prior sums to %.9g: must be 1 within 1e-6", sum);
+    }
+    if (c.n_groups == 0) return n == 0 ? MMC_OK : fail(MMC_ERR_ARG, "no groups over %lld points", (long long)n);
+    if (!c.offsets) return fail(MMC_ERR_ARG, "group_offsets is NULL");
+    if (c.offsets[0] != 0) return fail(MMC_ERR_ARG, "group_offsets[0] = %lld: must be 0", (long long)c.offsets[0]);
+    for (int64_t g = 0; g < c.n_groups; ++g)
+        if (c.offsets[g + 1] < c.offsets[g])
+            return fail(MMC_ERR_ARG, "group_offsets[%lld] = %lld is below group_offsets[%lld] = %lld", (long long)(g + 1),
+                        (long long)c.offsets[g + 1], (long long)g, (long long)c.offsets[g]);
+    if (c.offsets[c.n_groups] != n)
+        return fail(MMC_ERR_ARG, "group_offsets[n_groups] = %lld: must be n = %lld", (long long)c.offsets[c.n_groups], (long long)n);
+    return MMC_OK;
+}
+
+// a call without points: zero tables (cover_clear has run), train_prior in every row of prior; nothing is launched
+static int cover_empty(int K, const CoverIO& c)
+{
+    for (int64_t g = 0; g < c.n_groups; ++g)
+        for (int j = 0; j < K; ++j) c.prior[(size_t)g * K + j] = c.train_prior ? c.train_prior[j] : 1.0 / K;
+    return MMC_OK;
+}
+
+// where the stage keeps its device state inside CoverScratch::dev (every part 256-byte aligned); the first `zero_bytes` are the
+// integer tables a call starts from zero
+struct CoverLayout { size_t count, soft, unusable, zero_bytes, offsets, slab_row0, slab_group, group_slab0, prior, pi, w, part, idx, scores, bytes; };
+static CoverLayout cover_layout(int64_t n, int K, int64_t n_groups, int64_t n_slabs, int k_stage)
+{
+    CoverLayout L{};
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+    const size_t cells = (size_t)n_groups * K;
+    L.count = take(cells * 8);
+    L.soft = take(cells * 8);
+    L.unusable = take((size_t)n_groups * 8);
+    L.zero_bytes = at;
+    L.offsets = take((size_t)(n_groups + 1) * 8);
+    L.slab_row0 = take((size_t)n_slabs * 8);
+    L.slab_group = take((size_t)n_slabs * 4);
+    L.group_slab0 = take((size_t)(n_groups + 1) * 8);
+    L.prior = take((size_t)K * 8);
+    L.pi = take(cells * 8);
+    L.w = take(cells * 8);
+    L.part = take((size_t)n_slabs * K * 8);
+    L.idx = take((size_t)n * k_stage * 4);
+    L.scores = take((size_t)n * k_stage * 4);
+    L.bytes = at;
+    return L;
+}
+
+// the stage on the resident probabilities P (n x K, n > 0, on the current device; every argument has been checked): enqueues the
+// uploads, the count pass, the EM iterations and the adapted top-k on `st` and ends in one synchronisation
+static int cover_stage(CoverScratch& S, const float* P, int64_t n, int K, const CoverIO& c, bool out_host, hipStream_t st)
+{
+    const int64_t G = c.n_groups;
+    // the slab list: a function of the offsets alone
+    S.slab_row0.clear(); S.slab_group.clear();
+    S.group_slab0.resize((size_t)G + 1);
+    for (int64_t g = 0; g < G; ++g) {
+        S.group_slab0[g] = (int64_t)S.slab_row0.size();
+        for (int64_t r = c.offsets[g]; r < c.offsets[g + 1]; r += COVER_SLAB_POINTS) {
+            S.slab_row0.push_back(r);
+            S.slab_group.push_back((int32_t)g);
+        }
+    }
+    const int64_t n_slabs = (int64_t)S.slab_row0.size();
+    S.group_slab0[G] = n_slabs;
+    S.prior.resize(K);
+    for (int j = 0; j < K; ++j) S.prior[j] = c.train_prior ? c.train_prior[j] : 1.0 / K;
+    const bool topk = c.idx != nullptr;
+    const CoverLayout L = cover_layout(n, K, G, n_slabs, topk && out_host ? c.k : 0);
+    int r;
+    if ((r = S.dev.reserve((int64_t)L.bytes))) return r;
+    char* b = S.dev.p;
+    auto* count = reinterpret_cast<unsigned long long*>(b + L.count);
+    auto* soft = reinterpret_cast<unsigned long long*>(b + L.soft);
+    auto* unusable = reinterpret_cast<unsigned long long*>(b + L.unusable);
+    auto* offsets = reinterpret_cast<int64_t*>(b + L.offsets);
+    auto* slab_row0 = reinterpret_cast<int64_t*>(b + L.slab_row0);
+    auto* slab_group = reinterpret_cast<int32_t*>(b + L.slab_group);
+    auto* group_slab0 = reinterpret_cast<int64_t*>(b + L.group_slab0);
+    auto* prior = reinterpret_cast<double*>(b + L.prior);
+    auto* pi = reinterpret_cast<double*>(b + L.pi);
+    auto* w = reinterpret_cast<double*>(b + L.w);
+    auto* part = reinterpret_cast<double*>(b + L.part);
+    int32_t* didx = topk ? (out_host ? reinterpret_cast<int32_t*>(b + L.idx) : c.idx) : nullptr;
+    float* dscores = topk ? (out_host ? reinterpret_cast<float*>(b + L.scores) : c.scores) : nullptr;
+    const size_t cells = (size_t)G * K;
+    HIP_TRY(hipMemsetAsync(b, 0, L.zero_bytes, st));
+    HIP_TRY(hipMemcpyAsync(offsets, c.offsets, (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(slab_row0, S.slab_row0.data(), (size_t)n_slabs * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(slab_group, S.slab_group.data(), (size_t)n_slabs * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(group_slab0, S.group_slab0.data(), (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(prior, S.prior.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
+    KTRY(launch_cover_count(P, n, K, offsets, G, count, soft, unusable, st));
+    KTRY(launch_cover_em_init(prior, G, K, pi, w, st));
+    for (int t = 0; t < c.iters; ++t) {
+        KTRY(launch_cover_em_pass(P, K, slab_row0, slab_group, offsets, n_slabs, w, part, st));
+        KTRY(launch_cover_em_reduce(part, group_slab0, offsets, unusable, prior, c.strength, G, K, pi, w, st));
+    }
+    if (topk) KTRY(launch_cover_adapt_topk(P, n, K, offsets, G, w, c.k, didx, dscores, st));
+    HIP_TRY(hipMemcpyAsync(c.count, count, cells * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c.soft, soft, cells * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c.unusable, unusable, (size_t)G * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c.prior, pi, cells * 8, hipMemcpyDeviceToHost, st));
+    if (topk && out_host) {
+        HIP_TRY(hipMemcpyAsync(c.idx, didx, (size_t)n * c.k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c.scores, dscores, (size_t)n * c.k * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return MMC_OK;
+}
+
+// mmc_cover_proba has no handle: its scratch is kept per device for the life of the process (never freed: the runtime may be gone
+// by the time static destructors run), and the calls are serialised
+static std::mutex g_cover_mutex;
+static std::map<int, CoverScratch*>* g_cover_scratch = nullptr;
+
+extern "C" int mmc_cover_proba(const float* proba, int64_t n, int K, const int64_t* group_offsets, int64_t n_groups,
+                               const double* train_prior, double strength, int iters, int64_t* count, int64_t* soft_q32, int64_t* unusable,
+                               double* prior, int k, int32_t* idx, float* scores, int device, unsigned flags, void* hip_stream)
+{
+    const CoverIO c{group_offsets, n_groups, train_prior, strength, iters, count, soft_q32, unusable, prior, k, idx, scores};
+    const bool out_host = (flags & MMC_OUT_HOST) != 0;
+    cover_clear(K, n, c, out_host);
+    int r = cover_check(K, n, c);
+    if (r) return r;
+    if (n == 0) return cover_empty(K, c);
+    if (!proba) return fail(MMC_ERR_ARG, "proba is NULL");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MMC_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(MMC_ERR_ARG, "device %d out of range (%d visible)", device, ndev);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(g_cover_mutex);
+    HIP_TRY(hipSetDevice(device));
+    if (!g_cover_scratch) g_cover_scratch = new std::map<int, CoverScratch*>();
+    CoverScratch*& S = (*g_cover_scratch)[device];
+    if (!S) S = new CoverScratch();
+    const float* P = proba;
+    if (flags & MMC_IN_HOST) {
+        if ((r = S->proba.reserve(n * K))) return r;
+        HIP_TRY(hipMemcpyAsync(S->proba.p, proba, (size_t)n * K * 4, hipMemcpyHostToDevice, st));
+        P = S->proba.p;
+    }
+    r = cover_stage(*S, P, n, K, c, out_host, st);
+    if (r) cover_clear(K, n, c, out_host);
+    return r;
+}
+
+// the two head forms: rows X (host with MMC_IN_HOST in `flags`, else on the head's device), or rows [first, ...) of `fs` when `set`
+static int head_cover(mmc_head* h, const float* X, const mmc_featureset* fs, bool set, int64_t first, int64_t n_points, int G,
+                      const CoverIO& c, unsigned flags, void* hip_stream)
+{
+    const bool out_host = (flags & MMC_OUT_HOST) != 0;
+    const int K = h ? h->K : 0;
+    cover_clear(K, n_points, c, out_host);
+    if (!h) return fail(MMC_ERR_ARG, "head handle is NULL");
+    if (G < 1 || G > VIEWS_MAX) return fail(MMC_ERR_ARG, "G = %d views per point is outside [1, %d]", G, VIEWS_MAX);
+    int r = cover_check(K, n_points, c);
+    if (r) return r;
+    const int64_t n = n_points * G;   // rows
+    if (set) {
+        if (!fs) return fail(MMC_ERR_ARG, "feature set handle is NULL");
+        if (fs->dim != h->input_dim) return fail(MMC_ERR_ARG, "feature set has %d columns, head expects %d", fs->dim, h->input_dim);
+        if (fs->device != h->device) return fail(MMC_ERR_ARG, "feature set is on device %d, head on device %d", fs->device, h->device);
+        if (first < 0 || first > fs->n || n > fs->n - first)
+            return fail(MMC_ERR_ARG, "rows [%lld, %lld + %lld) outside the set's %lld rows", (long long)first, (long long)first, (long long)n,
+                        (long long)fs->n);
+    }
+    if (n_points == 0) return cover_empty(K, c);
+    if (!set && !X) return fail(MMC_ERR_ARG, "feats is NULL");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t chunk = HEAD_CHUNK / G * G;   // rows: whole points only
+    if ((r = h->cover.proba.reserve(n_points * K))) return r;
+    if (G > 1) {   // launch_mean_topk always selects: its best class per point goes to the top-k staging and is not used
+        const int64_t stage = n_points < chunk / G ? n_points : chunk / G;
+        if ((r = h->topk_idx_stage.reserve(stage)) || (r = h->topk_score_stage.reserve(stage))) return r;
+    }
+    float* resident = h->cover.proba.p;
+    const float* rows = set ? fs->X + (size_t)first * fs->dim : X;
+    r = head_for_chunks(h, rows, n, set ? 0u : flags & MMC_IN_HOST, st, [&](int64_t off, int cur, const float* logits) -> int {
+        if (G == 1)
+            KTRY(launch_calibrate(logits, cur, K, h->a, h->bc, resident + (size_t)off * K, nullptr, st));
+        else
+            KTRY(launch_mean_topk(logits, cur / G, G, K, h->a, h->bc, 1, h->topk_idx_stage.p, h->topk_score_stage.p,
+                                  resident + (size_t)(off / G) * K, h->proba_stage.p, st));
+        return MMC_OK;
+    }, chunk);
+    if (!r) r = cover_stage(h->cover, resident, n_points, K, c, out_host, st);
+    if (r) cover_clear(K, n_points, c, out_host);
+    return r;
+}
+
+extern "C" int mmc_head_cover(mmc_head* h, const float* feats, int64_t n_points, int G, const int64_t* group_offsets, int64_t n_groups,
+                              const double* train_prior, double strength, int iters, int64_t* count, int64_t* soft_q32, int64_t* unusable,
+                              double* prior, int k, int32_t* idx, float* scores, unsigned flags, void* hip_stream)
+{
+    const CoverIO c{group_offsets, n_groups, train_prior, strength, iters, count, soft_q32, unusable, prior, k, idx, scores};
+    return head_cover(h, feats, nullptr, false, 0, n_points, G, c, flags, hip_stream);
+}
+
+extern "C" int mmc_head_cover_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n_points, int G, const int64_t* group_offsets,
+                                  int64_t n_groups, const double* train_prior, double strength, int iters, int64_t* count, int64_t* soft_q32,
+                                  int64_t* unusable, double* prior, int k, int32_t* idx, float* scores, unsigned flags, void* hip_stream)
+{
+    const CoverIO c{group_offsets, n_groups, train_prior, strength, iters, count, soft_q32, unusable, prior, k, idx, scores};
+    return head_cover(h, nullptr, fs, true, first, n_points, G, c, flags, hip_stream);
 }
 
 // ------------------------------------------------------------------------------------------

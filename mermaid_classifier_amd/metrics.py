@@ -46,6 +46,22 @@ class CoverStats:
         if self.n_images_used < 0:
             raise ValueError(f"n_images_used = {n_images_used} is negative")
 
+    @classmethod
+    def from_fractions(cls, true_cover, pred_cover) -> "CoverStats":
+        """The sums from per-image cover fractions themselves: ``true_cover`` / ``pred_cover`` (n_images, K) float64, one row per
+        image that counts (``cover.CoverEstimate.compare`` drops the images without a usable point first).  Host arithmetic."""
+        t, p = np.asarray(true_cover, np.float64), np.asarray(pred_cover, np.float64)
+        if t.ndim != 2 or t.shape != p.shape:
+            raise ValueError(f"true_cover {t.shape} / pred_cover {p.shape} must be equal (n_images, K) shapes")
+        n, K = t.shape
+        sums = np.zeros((K, len(COVER_COLUMNS)))
+        if n:
+            d = p - t
+            sums[:, 0], sums[:, 1], sums[:, 2], sums[:, 3], sums[:, 4] = t.sum(0), p.sum(0), d.sum(0), (d * d).sum(0), np.abs(d).sum(0)
+            sums[:, 5], sums[:, 6] = t.min(0), t.max(0)
+            sums[:, 7] = ((t - t.sum(0) / n) ** 2).sum(0)
+        return cls(sums, n)
+
     def table(self) -> Dict[str, np.ndarray]:
         """The columns of ``cover/per_class_cover_metrics`` (cover.py:62-86) but the names: ``class`` (index), ``mean_true_cover_pct``,
         ``bias_pct``, ``rmse_pct``, ``mae_pct``, ``r_squared`` (NaN where the true cover is the same in every image), for the classes
