@@ -45,8 +45,9 @@ class MLPTrainRef:
                 h = np.maximum(h, F32(0))
         return h
 
-    def step(self, X: np.ndarray, y: np.ndarray) -> float:
-        """One mini-batch: returns the regularised loss before the update."""
+    def step(self, X: np.ndarray, y: np.ndarray, grads: Optional[dict] = None) -> float:
+        """One mini-batch: returns the regularised loss before the update.  ``grads``, if given, receives what the step computed on
+        the way (``logits``, ``loss`` as float32, ``gW`` and ``gb`` as lists); the step itself is the same either way."""
         mb = X.shape[0]
         hs = [np.asarray(X, dtype=F32)]
         for i, (w, b) in enumerate(zip(self.W, self.b)):
@@ -69,6 +70,8 @@ class MLPTrainRef:
             gb[l] = dz.sum(axis=0, dtype=F32)
             if l > 0:
                 dz = (dz @ self.W[l]) * (hs[l] > 0)
+        if grads is not None:
+            grads.update(logits=z, loss=data + reg, gW=[g.astype(F32) for g in gW], gb=[g.astype(F32) for g in gb])
         self.t += 1
         bc1 = 1.0 - self.beta1 ** self.t
         bc2 = 1.0 - self.beta2 ** self.t

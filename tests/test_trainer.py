@@ -6,7 +6,14 @@ class weights (one of them 0).
 CPU: the numpy oracle against the fixture; the host class's initial weights and shuffle against the fixture.
 GPU (-m gpu): the HIP trainer through the C ABI against the fixture and the oracle.
 Tolerance: 12 Adam steps in fp32 with different summation orders -- weights within 2e-5 absolute (they are O(0.1)),
-loss curve within 1e-5, probabilities within 1e-5."""
+loss curve within 1e-5, probabilities within 1e-5.
+
+What this file does not see: Adam divides the first moment by the root of the second, so a gradient that is wrong by a factor
+moves the weights only through eps.  Run against the fixture under these tolerances, an oracle whose logit gradients are all
+halved (a wrong 1 / sum of weights), whose L2 term of dW is dropped or scaled by alpha / 200 on the 130-row mini-batch, or whose
+bias gradients are tripled still passes (max dW 8.4e-6, 8.4e-6, 8.6e-7, 4e-8 against W_TOL 2e-5).  The gradient's scale, the L2 gradient, the bias
+gradient and the Adam scalars are checked per element against float64 in tests/test_gpu_trainer_step.py (reference and bounds:
+oracle/mlp_step_ref.py; tests/test_trainer_step_ref.py shows on the CPU that those four mutants exceed its bounds)."""
 
 import pickle
 
