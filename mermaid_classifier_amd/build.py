@@ -34,7 +34,7 @@ SOURCES = {
     "featureset.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "metrics.hip": ["kernels.h"],
     "cover.hip": ["kernels.h", "topk_key.h"],
-    "mmc_api.cpp": ["kernels.h", "api_internal.h", "../../include/mmc.h"],
+    "mmc_api.cpp": ["kernels.h", "api_internal.h", "backbone_pack.h", "../../include/mmc.h"],
     "mmc_head.cpp": ["kernels.h", "api_internal.h", "trainer_internal.h", "../../include/mmc.h"],
     "mmc_dist.cpp": ["../../include/mmc.h"],
 }

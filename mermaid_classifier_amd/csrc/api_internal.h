@@ -1,5 +1,7 @@
 // api_internal.h -- what the two host units of the C ABI (mmc_api.cpp: backbone, schedule, crop; mmc_head.cpp: calibrated head) share:
 // the error plumbing, and the one thing the head asks of a backbone beyond include/mmc.h.
+// (The host-only half of the backbone -- architecture tables, blob reader, weight layouts -- is backbone_pack.h: no HIP, and it
+// reports through its own BlobError, so it needs nothing from here.)
 // Library-internal; not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

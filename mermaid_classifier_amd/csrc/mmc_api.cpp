@@ -1,5 +1,7 @@
 // mmc_api.cpp -- the backbone half of the C ABI (include/mmc.h): the error buffer, the EfficientNet-B0 launch schedule and the crop.
 // The calibrated head (predict, top-k, evaluate, classify) is the unit next to this one; the two share api_internal.h.
+// The architecture tables, the blob reader and every weight layout are backbone_pack.h (host-only, no HIP); this unit plans, binds the
+// packed images to the launch structs of kernels.h, and launches.
 // Host C++ only; kernels live in k_*.hip.  No torch, no CUDA shims.
 #include <hip/hip_runtime.h>
 
@@ -17,7 +19,10 @@
 
 #include "../../include/mmc.h"
 #include "api_internal.h"
+#include "backbone_pack.h"
 #include "kernels.h"
+
+static const int IMG = 224;
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -43,61 +48,6 @@ extern "C" int mmc_device_count(void)
     return n;
 }
 
-// ------------------------------------------------------------------------------------------
-// EfficientNet-B0 stage table (the published architecture; mirrors oracle/efficientnet_b0_ref.py)
-// ------------------------------------------------------------------------------------------
-struct BlockDef { int k, s, e, cin, cout; };
-static const BlockDef B0_BLOCKS[16] = {
-    {3, 1, 1, 32, 16},  {3, 2, 6, 16, 24},  {3, 1, 6, 24, 24},   {5, 2, 6, 24, 40},
-    {5, 1, 6, 40, 40},  {3, 2, 6, 40, 80},  {3, 1, 6, 80, 80},   {3, 1, 6, 80, 80},
-    {5, 1, 6, 80, 112}, {5, 1, 6, 112, 112}, {5, 1, 6, 112, 112}, {5, 2, 6, 112, 192},
-    {5, 1, 6, 192, 192}, {5, 1, 6, 192, 192}, {5, 1, 6, 192, 192}, {3, 1, 6, 192, 320}};
-static const int IMG = 224;
-// The published family: B0's stage table under compound scaling (widths to multiples of 8, never below 90 % of the scaled
-// value; repeats rounded up).  B0 is the network the reference path runs; B4 (width 1.4, depth 1.8, BASELINE.json
-// configs[4]) does not exist in the reference and runs on the generic per-layer kernels.
-struct ArchDef { int stem = 32, head_in = 320, feat = 1280; std::vector<BlockDef> blocks; };
-static int round_filters(int c, double width)
-{
-    const double v = c * width;
-    int n = (int)(v + 4) / 8 * 8;
-    if (n < 8) n = 8;
-    if (n < 0.9 * v) n += 8;
-    return n;
-}
-static ArchDef make_arch(int arch)
-{
-    ArchDef A;
-    if (arch == MMC_ARCH_B0) {
-        A.blocks.assign(B0_BLOCKS, B0_BLOCKS + 16);
-        return A;
-    }
-    const double width = 1.4, depth = 1.8;   // MMC_ARCH_B4
-    static const int STAGES[7][6] = {{1, 3, 1, 1, 32, 16},  {2, 3, 2, 6, 16, 24},   {2, 5, 2, 6, 24, 40}, {3, 3, 2, 6, 40, 80},
-                                     {3, 5, 1, 6, 80, 112}, {4, 5, 2, 6, 112, 192}, {1, 3, 1, 6, 192, 320}};
-    A.stem = round_filters(32, width);
-    for (auto& st : STAGES) {
-        const int cin = round_filters(st[4], width), cout = round_filters(st[5], width);
-        const int reps = (int)std::ceil(depth * st[0] - 1e-9);
-        for (int r = 0; r < reps; ++r) A.blocks.push_back({st[1], r == 0 ? st[2] : 1, st[3], r == 0 ? cin : cout, cout});
-    }
-    A.head_in = A.blocks.back().cout;
-    A.feat = round_filters(1280, width);
-    return A;
-}
-// Scaled activation domain (device_common.h, silu_scaled): every SiLU output is stored times log2(e).
-// Producers (stem, expand, depthwise, head) get weights/bias times LOG2E, consumers times 1/LOG2E;
-// for the depthwise taps the two cancel, so only its bias is scaled.
-static const double LOG2E = 1.4426950408889634;
-
-static void same_pad(int size, int k, int s, int* before, int* out)
-{
-    *out = (size + s - 1) / s;
-    int pad = (*out - 1) * s + k - size;
-    if (pad < 0) pad = 0;
-    *before = pad / 2;
-}
-
 // A 1x1 convolution packed for pw_gemm_kernel
 struct PwLayer {
     int N = 0, K = 0, Kp = 0, nt = 0, n_chunks = 0;
@@ -105,37 +55,6 @@ struct PwLayer {
     float* b = nullptr;     // device [n_chunks*16*nt]
     const char* label[2] = {nullptr, nullptr};   // plan: its pw_gemm instantiation with one / two row fragments per wave (gemm_mt)
 };
-
-// A project conv with e4m3 weights for pw_gemm_fp8_kernel (MMC_PRECISION_FP8)
-struct Fp8Layer {
-    int N = 0, K = 0, KS128 = 0, NFp = 0;
-    uint8_t* w8 = nullptr;  // device [NFp][KS128][64][32]
-    float* sw = nullptr;    // device [16 NFp] per-output-channel scales
-    float* b = nullptr;     // device [16 NFp]
-};
-
-// fp32 -> OCP e4m3fn (4 exponent bits, bias 7, 3 mantissa bits, no infinities, largest finite 448), round to nearest even,
-// saturating.  The device side uses v_cvt_pk_fp8_f32; the host needs the same encoding for the weights.
-static uint8_t e4m3_encode(float x)
-{
-    if (x != x) return 0x7F;
-    const uint8_t sign = std::signbit(x) ? 0x80 : 0x00;
-    float a = std::fabs(x);
-    if (a >= 448.0f) return sign | 0x7E;
-    if (a < 0.0009765625f) return sign;                        // below half of the smallest subnormal (2^-9): zero (a tie goes to even = 0)
-    int e;
-    (void)std::frexp(a, &e);                                   // a = f * 2^e, f in [0.5, 1)
-    int ex = e - 1;                                            // a in [2^ex, 2^(ex+1))
-    if (ex < -6) ex = -6;                                      // subnormals share the exponent of the smallest normal
-    const float quantum = std::ldexp(1.0f, ex - 3);
-    float qf = std::nearbyint(a / quantum);                    // round to nearest even (default rounding mode)
-    int qi = (int)qf;
-    if (qi >= 16) { qi = 8; ++ex; }
-    if (ex > 8) return sign | 0x7E;
-    if (ex == 8 && qi > 14) return sign | 0x7E;                // 448 = 1.75 * 2^8 is the largest finite value
-    if (qi < 8) return sign | (uint8_t)qi;                     // subnormal (only with ex == -6)
-    return sign | (uint8_t)(((ex + 7) << 3) | (qi - 8));
-}
 
 extern "C" int mmc_fp8_e4m3_encode(const float* in, uint8_t* out, size_t n)
 {
@@ -245,6 +164,12 @@ enum class TailRoute {
     B11All,   // b11all-head.tail (all of block 11 too)
 };
 
+// the weight half of the launch_se_gate / launch_se_small / launch_se_wide argument lists
+struct SeArgs {
+    int Cs = 0;   // squeeze width as that launcher takes it (launch_se_gate: padded to 4)
+    const float *wr = nullptr, *br = nullptr, *we = nullptr, *be = nullptr;
+};
+
 struct BlockW {
     BlockDef d;
     // ---- geometry ----
@@ -254,7 +179,7 @@ struct BlockW {
     bool fusable = false;   // mbconv_a's tile / chunk geometry (in `mb`) fits
     bool d_fits = false;    // ... and so does mbconv_d's (d_npair .. d_lds)
     int d_npair = 0, d_wl_off = 0, d_red_off = 0, d_lds = 0;
-    MbArgs mb{};            // mbconv_a / mbconv_d / mbconv_a PRE: everything but the buffers and the batch
+    MbArgs mb{};            // mbconv_a / mbconv_d / mbconv_a PRE: geometry here, weights by bind_mb; all but the buffers and the batch
     // ---- plan ----
     Front front = Front::Unfused;
     Back back = Back::SeProject;
@@ -264,24 +189,21 @@ struct BlockW {
     bool planar = false;                 // block 1: depthwise output as 32-channel planes between mb1_kernel and thin_proj_kernel
     int nparts = 0;                      // pool partials per patch left by the front half
     const char *front_label = nullptr, *back_label = nullptr;   // the templated instantiation the front half / proj_patch runs on
-    // ---- packed weights ----
-    PwLayer expand, project;
-    Fp8Layer p8;             // the project conv on fp8 operands (Proj::Fp8)
-    float *dw_w = nullptr, *dw_b = nullptr;                    // [k*k][ce], [ce]
-    float *se_br = nullptr, *se_be = nullptr;
-    float *se_wrp = nullptr, *se_wep = nullptr;   // fragment-ordered fp32 squeeze-excite weights (se_fused_kernel)
-    float *se_wr_nat = nullptr, *se_we_nat = nullptr, *se_br_nat = nullptr;   // natural fp32 copies (se_small_kernel, se_wide_kernel)
-    _Float16* exp_nat = nullptr;   // [ce][32*ksteps] natural rows (mbconv_a / mbconv_d)
-    _Float16* exp_frag = nullptr;  // expand weights in MFMA fragment order
-    uint32_t* t_dwp = nullptr;     // depthwise taps as fp16 pairs [15][ce] (mbt)
-    uint32_t* t_dwp4 = nullptr;    // taps + bias, [4][ce][4] dwords (16-byte requests: mid14, tail7)
-    _Float16* dw_diag = nullptr;   // Toeplitz depthwise fragments [ce/16][k][2][64][4] for v_mfma_f32_4x4x4_16B_f16 (mbt4, mid14m)
-    _Float16* t_wproj = nullptr;   // tail7 blocks: project weights in plain fragment order
-    _Float16 *t_wr = nullptr, *t_we = nullptr;   // squeeze-excite FCs transposed (fp16) for matrix-vector use
-    _Float16* t_wrg = nullptr;                   // ... the squeeze FC as proj_patch_kernel reads it (ProjPatchArgs::wr_g)
-    _Float16 *t_wr2 = nullptr, *t_we2 = nullptr; // ... blocks 12-15: paired rows for tail7_kernel's 16-byte requests
-    _Float16* pp_w = nullptr;                    // proj_patch_kernel: project weights / bias padded to whole fragments
-    float *pp_b = nullptr, *pp_br = nullptr;
+    // ---- weights several families read, each uploaded once ----
+    PwLayer expand, project;                  // pw_gemm image + padded bias
+    float *dw_w = nullptr, *dw_b = nullptr;   // tap-major fp32 taps [k*k][ce], bias [ce]
+    float* se_be = nullptr;                   // excite bias [ce]
+    // ---- the launch arguments of the planned kernels: weights and constant scalars, bound at create time (bind_*); forward_lane
+    // copies the struct and sets the buffers and the batch ----
+    MbtArgs mbt{};         // Front::Mbt
+    Mid14Args mid{};       // Front::Mid14
+    Mb1Args mb1{};         // Front::Mb1; Front::MbPre passes its pre_w / pre_b next to `mb`
+    DwArgs dw{};           // Front::Unfused
+    GemmArgs exp_gemm{};   // ... its expand conv
+    ProjPatchArgs pp{};    // Back::ProjPatch
+    SeArgs sea{};          // Back::SeProject / SeFolded: the squeeze-excite launch `se` picks
+    GemmArgs proj_gemm{};  // Back::SeProject on Proj::Thin / Proj::Gemm
+    Fp8GemmArgs proj8{};   // Back::SeProject on Proj::Fp8
 };
 
 // Output tile (TH x TWo) and channel chunk CC of the fused kernel, per B0 block (index 1..15):
@@ -433,9 +355,9 @@ struct mmc_backbone {
     float* dbg_clk = nullptr;        // keep mode: per-patch phase cycle counts of the patch-resident kernels
     float* mid_clk = nullptr;        // MMC_TAIL_CLK=1: [max_batch][8 workgroups][16] phase cycle counts of block 10's mid14 launch
     float* tail_clk = nullptr;       // MMC_TAIL_CLK=1: [max_batch][8 sections][8] phase cycle counts of the production tail7 launch
-    _Float16 *b0_pre_w = nullptr, *b1_exp_pre = nullptr;   // fuse_b0b1: block 0's project as one MFMA fragment, block 1's K-permuted expand
-    _Float16 *pre_wproj = nullptr, *head_wfrag = nullptr;  // tail7: block 11's project, the head conv (plain fragment order)
-    TailBlock* tail_tab = nullptr;   // device table for tail7_kernel (blocks 12..15)
+    std::vector<TailBlock> tail_rows;   // tail7_kernel's block table (blocks 12..15) as bind_tail_block fills it ...
+    TailArgs tail_args{};               // ... on the device in tail_args.blk, with block 11's (pre_*) and the head's weights and inv_hw
+    GemmArgs head_gemm{};               // the head conv on pw_gemm (no tail7 head phase)
     std::map<std::string, Saved> saved;
     // One pass at a time per handle (lane workspaces, fork/done events and the staging buffers are shared): calls are
     // serialised on the host by `mu`, and a call on a different stream than the previous one waits for that one's work.
@@ -465,29 +387,6 @@ struct PassOrder {
 struct ProfEntry { std::string name; hipEvent_t e0, e1; };
 struct Prof { std::vector<ProfEntry> entries; };
 
-// ------------------------------------------------------------------------------------------
-// blob parsing: header{magic,version,arch,n_tensors} + table{offset,nbytes} + fp32 tensors
-// ------------------------------------------------------------------------------------------
-struct BlobReader {
-    const uint8_t* base;
-    size_t nbytes;
-    uint32_t n_tensors;
-    const uint64_t* table;
-    uint32_t next = 0;
-    const float* take(size_t n_floats, const char* what, int* err)
-    {
-        if (next >= n_tensors) { *err = fail(MMC_ERR_WEIGHTS, "weights blob ended before %s", what); return nullptr; }
-        const uint64_t off = table[2 * next], nb = table[2 * next + 1];
-        if (off + nb > nbytes || nb != n_floats * sizeof(float)) {
-            *err = fail(MMC_ERR_WEIGHTS, "tensor %u (%s): expected %zu bytes, blob has %llu", next, what,
-                        n_floats * sizeof(float), (unsigned long long)nb);
-            return nullptr;
-        }
-        ++next;
-        return reinterpret_cast<const float*>(base + off);
-    }
-};
-
 template <typename T>
 static int dev_alloc(mmc_backbone* bb, T** p, size_t count)
 {
@@ -509,40 +408,22 @@ static int dev_upload(mmc_backbone* bb, T** p, const std::vector<T>& host)
     return 0;
 }
 
-// Pack a natural [N][K] fp32 1x1-conv weight into the fragment-ordered fp16 layout of pw_gemm_kernel:
-// fragment (chunk, kstep, t) = 1 KB at ((chunk*KS32 + kstep)*nt + t)*512 halves; inside it lane
-// (q*16 + m) holds W[channel(chunk, t, m)][kstep*32 + q*8 .. +8], with the row permutation
-// fragment row (t*16 + 4qr + jr) <- channel (chunk*16nt + qr*4nt + 4t + jr).
-static int pack_pw(mmc_backbone* bb, PwLayer* L, const float* w, const float* b, int N, int K, int nt, double wscale, double bscale)
+// ... into the pointer-to-const field of a launch struct
+template <typename T>
+static int dev_upload(mmc_backbone* bb, const T** p, const std::vector<T>& host)
 {
-    L->N = N;
-    L->K = K;
-    L->Kp = (K + 31) / 32 * 32;
-    L->nt = nt;
-    const int cw = 16 * L->nt;
-    L->n_chunks = (N + cw - 1) / cw;
-    const int Np = L->n_chunks * cw;
-    const int ks32 = L->Kp / 32;
-    std::vector<_Float16> wp((size_t)Np * L->Kp, (_Float16)0.0f);
-    std::vector<float> bp(Np, 0.0f);
-    for (int ch = 0; ch < L->n_chunks; ++ch)
-        for (int ks = 0; ks < ks32; ++ks)
-            for (int t = 0; t < L->nt; ++t)
-                for (int m = 0; m < 16; ++m) {
-                    const int c = ch * cw + (m >> 2) * 4 * L->nt + 4 * t + (m & 3);
-                    if (c >= N) continue;
-                    for (int q = 0; q < 4; ++q)
-                        for (int j = 0; j < 8; ++j) {
-                            const int k = ks * 32 + q * 8 + j;
-                            if (k >= K) continue;
-                            const size_t off = ((((size_t)ch * ks32 + ks) * L->nt + t) * 64 + (q * 16 + m)) * 8 + j;
-                            wp[off] = (_Float16)(float)(w[(size_t)c * K + k] * wscale);
-                        }
-                }
-    for (int c = 0; c < N; ++c) bp[c] = (float)(b[c] * bscale);
-    int r = dev_upload(bb, &L->w, wp);
+    T* d = nullptr;
+    const int r = dev_upload(bb, &d, host);
+    *p = d;
+    return r;
+}
+
+static int upload_pw(mmc_backbone* bb, PwLayer* L, const PwImage& img)
+{
+    L->N = img.N; L->K = img.K; L->Kp = img.Kp; L->nt = img.nt; L->n_chunks = img.n_chunks;
+    int r = dev_upload(bb, &L->w, img.w);
     if (r) return r;
-    return dev_upload(bb, &L->b, bp);
+    return dev_upload(bb, &L->b, img.b);
 }
 
 extern "C" void mmc_backbone_destroy(mmc_backbone* bb)
@@ -566,21 +447,6 @@ extern "C" int mmc_backbone_create(const void* packed, size_t nbytes, int arch, 
                                    mmc_backbone** out)
 {
     return mmc_backbone_create_ex(packed, nbytes, arch, device, max_batch, 0u, out);
-}
-
-// W[n][k] (rows of ld elements, n < N, k < K) times `scale` as fp16 in MFMA fragment order [nf][ks][64 lanes][8]: element (n, k)
-// at ((n/16 * ks + k/32) * 64 + (k%32)/8 * 16 + n%16) * 8 + k%8 -- lane (q*16 + m) of fragment (f, kstep) holds
-// W[16f + m][32 kstep + 8q .. +8].  Fragments and k-steps beyond the tensor stay zero.  (A source already in fp16 is only
-// permuted: the expand weights keep the rounding of their natural fp16 rows.)
-template <typename T>
-static std::vector<_Float16> pack_frag(const T* w, int N, int K, int ld, int nf, int ks, double scale)
-{
-    std::vector<_Float16> wf((size_t)nf * ks * 512, (_Float16)0.0f);
-    for (int c = 0; c < N; ++c)
-        for (int k = 0; k < K; ++k)
-            wf[((((size_t)(c / 16) * ks + k / 32) * 64) + ((k % 32) / 8) * 16 + (c % 16)) * 8 + (k % 8)] =
-                (_Float16)(float)(w[(size_t)c * ld + k] * scale);
-    return wf;
 }
 
 // 7x7 layers: few workgroups, deep K -> the gated GEMM overlaps its loads with MFMAs (pw_gemm's deferred-gate forms)
@@ -670,25 +536,294 @@ static int plan_block(const mmc_backbone* bb, BlockW& B, int i)
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// binding: one function per kernel family.  It packs that family's weight images (backbone_pack.h), uploads them and writes the
+// pointers and the constant scalars into the struct its launcher reads -- so who packs a buffer and who reads it is one place.
+// An image two families read has one upload helper, and a block runs it once.
+// ------------------------------------------------------------------------------------------
+#define BIND(expr)                                 \
+    do { int r__ = (expr); if (r__) return r__; } while (0)
+
+// (the depthwise taps see a log2(e)-scaled input and produce a scaled output, except in an expand-less block behind a project conv)
+static double dw_tap_scale(const BlockW& B, int i) { return (B.has_expand || i == 0) ? 1.0 : LOG2E; }
+
+// a pw_gemm / thin_proj launch of layer L: everything but the buffers, the row count and mt (gemm_mt, per call)
+static GemmArgs gemm_args(const PwLayer& L, int epi, bool gate, int HW)
+{
+    GemmArgs a{};
+    a.K = L.K; a.Wp = L.w; a.Kp = L.Kp; a.bias = L.b; a.N = L.N; a.nt = L.nt; a.n_chunks = L.n_chunks; a.epi = epi; a.HW = HW;
+    a.inv_hw = (float)(1.0 / ((double)HW * LOG2E));  // GAP input is log2(e)-scaled
+    a.defer_gate = gemm_defer_gate(gate, HW);
+    return a;
+}
+
+// expand weights in MFMA fragment order [ce/16][ksteps][64][8], permuted from their natural fp16 rows (mbt, mid14, tail7)
+static int upload_exp_frag(mmc_backbone* bb, const BlockW& B, const RawBlock& R, const _Float16** dst)
+{
+    const int kp = 32 * B.mb.ksteps;
+    const std::vector<_Float16> wn = pack_expand_rows(R.exp_w, B.ce, B.d.cin, kp);
+    return dev_upload(bb, dst, pack_frag(wn.data(), B.ce, B.d.cin, kp, B.ce / 16, B.mb.ksteps, 1.0));
+}
+
+// depthwise taps as fp16 pairs + the bias, in 16-byte requests [4][ce][4] (mid14, tail7)
+static int upload_dw_requests(mmc_backbone* bb, const BlockW& B, const RawBlock& R, const uint32_t** dst)
+{
+    const std::vector<uint32_t> dp = pack_dw_pairs(R.dw_w, B.ce, B.d.k);
+    const std::vector<float> db = pack_bias(R.dw_b, B.ce, B.ce, LOG2E);   // the bias exactly as dw_b holds it
+    return dev_upload(bb, dst, pack_dw_requests(dp.data(), db.data(), B.ce));
+}
+
+// Wr^T [ce][cs4] and We^T [cs4][ce] in fp16 + the squeeze bias padded to 32 (proj_patch, tail7's block 11)
+static int upload_se_t16(mmc_backbone* bb, const BlockW& B, const RawBlock& R, const _Float16** wr_t, const _Float16** we_t, const float** br)
+{
+    BIND(dev_upload(bb, wr_t, pack_se_fc1_t16(R.se_wr, B.ce, B.cs, B.cs4)));
+    BIND(dev_upload(bb, we_t, pack_se_fc2_t16(R.se_we, B.ce, B.cs, B.cs4)));
+    return dev_upload(bb, br, pack_bias(R.se_br, B.cs, B.cs4 > 32 ? B.cs4 : 32, 1.0));
+}
+
+// what every block uploads, whichever kernels run it: the pw_gemm images + padded biases of expand and project, the tap-major
+// depthwise taps, the depthwise and the excite bias
+static int bind_shared(mmc_backbone* bb, BlockW& B, int i, const RawBlock& R)
+{
+    if (B.has_expand) BIND(upload_pw(bb, &B.expand, pack_pw(R.exp_w, R.exp_b, B.ce, B.d.cin, B.expand.nt, LOG2E, LOG2E)));
+    BIND(dev_upload(bb, &B.dw_w, pack_dw_taps(R.dw_w, B.ce, B.d.k, dw_tap_scale(B, i))));
+    BIND(dev_upload(bb, &B.dw_b, pack_bias(R.dw_b, B.ce, B.ce, LOG2E)));
+    BIND(dev_upload(bb, &B.se_be, pack_bias(R.se_be, B.ce, B.ce, 1.0)));
+    return upload_pw(bb, &B.project, pack_pw(R.proj_w, R.proj_b, B.d.cout, B.ce, B.project.nt, 1.0 / LOG2E, 1.0));
+}
+
+static int bind_mbt(mmc_backbone* bb, BlockW& B, int i, const RawBlock& R)
+{
+    MbtArgs& a = B.mbt;
+    BIND(upload_exp_frag(bb, B, R, &a.wexp));
+    BIND(dev_upload(bb, &a.dwp, pack_dw_pairs(R.dw_w, B.ce, B.d.k)));
+    if (B.mbt4) BIND(dev_upload(bb, &a.dwtoe, pack_dw_toeplitz(R.dw_w, B.ce, B.d.k, dw_tap_scale(B, i))));
+    a.bexp = B.expand.b; a.bdw = B.dw_b;
+    a.H = B.H; a.Cin = B.d.cin; a.Ce = B.ce; a.ks = B.d.k; a.stride = B.d.s;
+    return 0;
+}
+
+static int bind_mid14(mmc_backbone* bb, BlockW& B, int i, const RawBlock& R)
+{
+    Mid14Args& a = B.mid;
+    BIND(upload_exp_frag(bb, B, R, &a.wexp));
+    BIND(upload_dw_requests(bb, B, R, &a.dwp));
+    if (B.mid14m) BIND(dev_upload(bb, &a.dwdiag, pack_dw_toeplitz(R.dw_w, B.ce, B.d.k, dw_tap_scale(B, i))));
+    a.bexp = B.expand.b; a.bdw = B.dw_b;
+    a.Cin = B.d.cin; a.Ce = B.ce; a.ks = B.d.k;
+    a.nsplit = B.mid14m ? 1 : 4;
+    return 0;
+}
+
+// block 1 behind block 0's folded project (mb1_kernel, or mbconv_a_kernel PRE with mb1's pre_w / pre_b next to `mb`): block 0's
+// project conv as ONE MFMA fragment (16 outputs x 32 inputs), block 1's expand rows K-permuted to match
+static int bind_mb1(mmc_backbone* bb, BlockW& B, const RawNet& raw)
+{
+    const int kp = 32 * B.mb.ksteps;
+    Mb1Args& m = B.mb1;
+    BIND(dev_upload(bb, &m.pre_w, pack_frag(raw.blk[0].proj_w, 16, 32, 32, 1, 1, 1.0 / LOG2E)));
+    const std::vector<_Float16> wn = pack_expand_rows(raw.blk[1].exp_w, B.ce, B.d.cin, kp);
+    BIND(dev_upload(bb, &m.wexp, pack_expand_kperm(wn.data(), B.ce, kp)));
+    m.pre_b = bb->blk[0].project.b; m.bexp = B.expand.b; m.wdw = B.dw_w; m.bdw = B.dw_b;
+    m.planar = B.planar ? 1 : 0;
+    if (B.front == Front::MbPre) {   // reads block 0's depthwise output: 32 input channels
+        MbArgs& a = B.mb;
+        a.Cin = 32; a.Wexp = m.wexp; a.bexp = B.expand.b; a.Wdw = B.dw_w; a.bdw = B.dw_b;
+    }
+    return 0;
+}
+
+static int bind_mb(mmc_backbone* bb, BlockW& B, const RawBlock& R)   // mbconv_a, mbconv_d
+{
+    MbArgs& a = B.mb;
+    BIND(dev_upload(bb, &a.Wexp, pack_expand_rows(R.exp_w, B.ce, B.d.cin, 32 * a.ksteps)));
+    a.bexp = B.expand.b; a.Wdw = B.dw_w; a.bdw = B.dw_b;
+    return 0;
+}
+
+static int bind_unfused(BlockW& B)   // expand GEMM + dwconv: shared images only
+{
+    if (B.has_expand) B.exp_gemm = gemm_args(B.expand, EPI_SILU, false, B.H * B.H);
+    DwArgs& d = B.dw;
+    d.wt = B.dw_w; d.bias = B.dw_b;
+    d.H = B.H; d.W = B.H; d.C = B.ce; d.Ho = B.Ho; d.Wo = B.Ho; d.pad_t = B.pad; d.pad_l = B.pad;
+    d.ks = B.d.k; d.stride = B.d.s; d.tw = B.tw; d.CG = B.CG; d.S = B.S; d.iters = B.iters; d.parts = B.parts; d.nz = B.nz;
+    return 0;
+}
+
+// tail7's front half of block i: a row of its block table (12..15), or the pre_* arguments of all of block 11 (TailRoute::B11All)
+static int bind_tail_front(mmc_backbone* bb, BlockW& B, int i, const RawBlock& R)
+{
+    if (i == 11) {
+        TailArgs& t = bb->tail_args;
+        BIND(upload_exp_frag(bb, B, R, &t.pre_wexp));
+        BIND(upload_dw_requests(bb, B, R, &t.pre_dwp));
+        t.pre_bexp = B.expand.b; t.pre_bdw = B.dw_b;
+        return 0;
+    }
+    TailBlock& t = bb->tail_rows[i - 12];
+    BIND(upload_exp_frag(bb, B, R, &t.wexp));
+    BIND(upload_dw_requests(bb, B, R, &t.dwp));
+    t.bexp = B.expand.b; t.bdw = B.dw_b; t.ks = B.d.k;
+    return 0;
+}
+
+static int bind_front(mmc_backbone* bb, BlockW& B, int i, const RawNet& raw)
+{
+    const RawBlock& R = raw.blk[i];
+    switch (B.front) {
+    case Front::StemDw: return 0;   // launch_stem_dw takes the stem's buffers and the shared taps
+    case Front::Mbt: return bind_mbt(bb, B, i, R);
+    case Front::Mid14: return bind_mid14(bb, B, i, R);
+    case Front::Mb1: case Front::MbPre: return bind_mb1(bb, B, raw);
+    case Front::MbD: case Front::MbA: return bind_mb(bb, B, R);
+    case Front::Unfused: return bind_unfused(B);
+    case Front::Tail: return bind_tail_front(bb, B, i, R);
+    }
+    return 0;
+}
+
+static int bind_proj_patch(mmc_backbone* bb, BlockW& B, const RawBlock& R)
+{
+    ProjPatchArgs& a = B.pp;
+    const _Float16* wr_t = nullptr;   // (uploaded as it always was; proj_patch_kernel reads the grouped copy)
+    BIND(upload_se_t16(bb, B, R, &wr_t, &a.we_t, &a.br));
+    const std::vector<_Float16> wrt = pack_se_fc1_t16(R.se_wr, B.ce, B.cs, B.cs4);
+    BIND(dev_upload(bb, &a.wr_g, pack_se_fc1_groups(wrt.data(), B.ce, B.cs4, proj_patch_fc1_rows(B.ce))));
+    // K and N zero-padded to whole fragments
+    const int nf = (B.d.cout + 15) / 16;
+    BIND(dev_upload(bb, &a.wfrag, pack_frag(R.proj_w, B.d.cout, B.ce, B.ce, nf, proj_patch_ksteps(B.ce), 1.0 / LOG2E)));
+    BIND(dev_upload(bb, &a.bias, pack_bias(R.proj_b, B.d.cout, 16 * nf, 1.0)));
+    a.be = B.se_be;
+    a.HW = B.Ho * B.Ho; a.K = B.ce; a.N = B.d.cout; a.CSP = B.cs4; a.nparts = B.nparts;
+    a.psc = (float)(1.0 / ((double)a.HW * LOG2E));
+    return 0;
+}
+
+// the squeeze-excite launch: se_fused_kernel's fragment order, or natural fp32 rows (se_small_kernel; se_wide_kernel reads the excite
+// FC transposed)
+static int bind_se(mmc_backbone* bb, BlockW& B, const RawBlock& R)
+{
+    SeArgs& s = B.sea;
+    const double psc = 1.0 / ((double)B.Ho * B.Ho * LOG2E);   // FC1 on pooled sums of HW log2(e)-scaled activations
+    s.be = B.se_be;
+    switch (B.se) {
+    case Se::Fused:
+        BIND(dev_upload(bb, &s.wr, pack_se_fc1_frag(R.se_wr, B.ce, B.cs, psc)));
+        BIND(dev_upload(bb, &s.we, pack_se_fc2_frag(R.se_we, B.ce, B.cs)));
+        BIND(dev_upload(bb, &s.br, pack_bias(R.se_br, B.cs, B.cs > 48 ? B.cs : 48, 1.0)));
+        s.Cs = B.cs4;
+        return 0;
+    case Se::Small:
+        BIND(dev_upload(bb, &s.wr, pack_se_fc1_nat(R.se_wr, B.ce, B.cs, psc)));
+        BIND(dev_upload(bb, &s.we, std::vector<float>(R.se_we, R.se_we + (size_t)B.ce * B.cs)));
+        break;
+    case Se::Wide:
+        BIND(dev_upload(bb, &s.wr, pack_se_fc1_nat(R.se_wr, B.ce, B.cs, psc)));
+        BIND(dev_upload(bb, &s.we, pack_se_fc2_t(R.se_we, B.ce, B.cs)));
+        break;
+    }
+    s.Cs = B.cs;
+    return dev_upload(bb, &s.br, pack_bias(R.se_br, B.cs, B.cs, 1.0));
+}
+
+static int bind_project(mmc_backbone* bb, BlockW& B, const RawBlock& R)
+{
+    const int HWo = B.Ho * B.Ho;
+    switch (B.proj) {
+    case Proj::Thin: case Proj::Gemm: B.proj_gemm = gemm_args(B.project, EPI_LINEAR, true, HWo); return 0;
+    case Proj::Fp8: {
+        const Fp8Image L = pack_fp8(R.proj_w, R.proj_b, B.d.cout, B.ce);
+        Fp8GemmArgs& a = B.proj8;
+        BIND(dev_upload(bb, &a.W8, L.w8));
+        BIND(dev_upload(bb, &a.sw, L.sw));
+        BIND(dev_upload(bb, &a.bias, L.b));
+        a.K = L.K; a.KS128 = L.KS128; a.NFp = L.NFp; a.N = L.N; a.HW = HWo;
+        return 0;
+    }
+    }
+    return 0;
+}
+
+// tail7's back half of block i: the rest of its table row (12..15), or the pre_* arguments of block 11's back half
+static int bind_tail_back(mmc_backbone* bb, BlockW& B, int i, const RawBlock& R)
+{
+    if (i == 11) {
+        TailArgs& t = bb->tail_args;
+        BIND(upload_se_t16(bb, B, R, &t.pre_wr_t, &t.pre_we_t, &t.pre_br));
+        // [12][24][64][8], k-steps 21..23 zero (its k-loop runs 4 steps at a time)
+        BIND(dev_upload(bb, &t.pre_wproj, pack_frag(R.proj_w, B.d.cout, B.ce, B.ce, 12, 24, 1.0 / LOG2E)));
+        t.pre_be = B.se_be; t.pre_bproj = B.project.b;
+        return 0;
+    }
+    TailBlock& t = bb->tail_rows[i - 12];
+    const std::vector<_Float16> wrt = pack_se_fc1_t16(R.se_wr, B.ce, B.cs, B.cs4), wet = pack_se_fc2_t16(R.se_we, B.ce, B.cs, B.cs4);
+    BIND(dev_upload(bb, &t.wr_t, pack_tail_fc1(wrt.data())));
+    BIND(dev_upload(bb, &t.we_t, pack_tail_fc2(wet.data())));
+    BIND(dev_upload(bb, &t.br, pack_bias(R.se_br, B.cs, B.cs > 48 ? B.cs : 48, 1.0)));
+    BIND(dev_upload(bb, &t.wproj, pack_frag(R.proj_w, B.d.cout, B.ce, B.ce, B.d.cout / 16, B.ce / 32, 1.0 / LOG2E)));
+    t.be = B.se_be; t.bproj = B.project.b; t.cout = B.d.cout;
+    return 0;
+}
+
+static int bind_back(mmc_backbone* bb, BlockW& B, int i, const RawBlock& R)
+{
+    switch (B.back) {
+    case Back::ProjPatch: return bind_proj_patch(bb, B, R);
+    case Back::SeFolded: return bind_se(bb, B, R);   // its project runs inside block 1's kernel (bind_mb1)
+    case Back::SeProject:
+        BIND(bind_se(bb, B, R));
+        return bind_project(bb, B, R);
+    case Back::Tail: return bind_tail_back(bb, B, i, R);
+    }
+    return 0;
+}
+
+// the stem, every block, the head and tail7's table
+static int bind_net(mmc_backbone* bb, const RawNet& raw)
+{
+    BIND(dev_upload(bb, &bb->stem_w, pack_stem(raw.stem_w, bb->stem_ch)));
+    BIND(dev_upload(bb, &bb->stem_b, pack_bias(raw.stem_b, bb->stem_ch, bb->stem_ch, LOG2E)));
+    BIND(dev_upload(bb, &bb->stem_pad, std::vector<float>{raw.stem_pad[0], raw.stem_pad[1], raw.stem_pad[2], 0.f}));
+    bb->tail_rows.assign(bb->tail != TailRoute::None ? 4 : 0, TailBlock{});
+    for (int i = 0; i < bb->nblk; ++i) {
+        BlockW& B = bb->blk[i];
+        BIND(bind_shared(bb, B, i, raw.blk[i]));
+        BIND(bind_front(bb, B, i, raw));
+        BIND(bind_back(bb, B, i, raw.blk[i]));
+    }
+    BIND(upload_pw(bb, &bb->head, pack_pw(raw.head_w, raw.head_b, bb->feat, bb->head_in, bb->head.nt, LOG2E, LOG2E)));
+    TailArgs& t = bb->tail_args;
+    if (bb->tail == TailRoute::B11 || bb->tail == TailRoute::B11All) {   // the same weights in plain fragment order for tail7's head phase
+        BIND(dev_upload(bb, &t.head_w, pack_frag(raw.head_w, bb->feat, bb->head_in, bb->head_in, bb->feat / 16, bb->head_in / 32, LOG2E)));
+        t.head_b = bb->head.b;
+    } else {
+        const int HWh = bb->blk[bb->nblk - 1].Ho * bb->blk[bb->nblk - 1].Ho;
+        bb->head_gemm = gemm_args(bb->head, EPI_GAP, false, HWh);
+    }
+    if (bb->tail != TailRoute::None) {
+        BIND(dev_upload(bb, &t.blk, bb->tail_rows));
+        t.inv_hw = (float)(1.0 / (49.0 * LOG2E));
+    }
+    return 0;
+}
+#undef BIND
+
 extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arch, int device, int max_batch, unsigned flags,
                                       mmc_backbone** out)
 {
+    // ---- 1. arguments and the blob's header ----
     if (!out) return fail(MMC_ERR_ARG, "out is NULL");
+    *out = nullptr;
     if (flags & ~(unsigned)MMC_PRECISION_FP8) return fail(MMC_ERR_ARG, "unknown flags 0x%x", flags);
     if ((flags & MMC_PRECISION_FP8) && arch != MMC_ARCH_B4)
         return fail(MMC_ERR_ARG, "MMC_PRECISION_FP8 is implemented for MMC_ARCH_B4 (BASELINE configs[4]): B0's late blocks run fused kernels without a separate project GEMM");
-    *out = nullptr;
     if (!packed || nbytes < 16) return fail(MMC_ERR_WEIGHTS, "weights blob is empty");
     if (arch != MMC_ARCH_B0 && arch != MMC_ARCH_B4) return fail(MMC_ERR_ARG, "unsupported arch %d (MMC_ARCH_B0 or MMC_ARCH_B4)", arch);
     if (max_batch < 1 || max_batch > 4096) return fail(MMC_ERR_ARG, "max_batch %d out of range [1,4096]", max_batch);
-    const uint8_t* base = static_cast<const uint8_t*>(packed);
-    uint32_t hdr[4];
-    memcpy(hdr, base, 16);
-    if (memcmp(base, "MMCW", 4) != 0) return fail(MMC_ERR_WEIGHTS, "bad magic in weights blob");
-    if (hdr[1] != 1) return fail(MMC_ERR_WEIGHTS, "weights blob version %u, expected 1", hdr[1]);
-    if ((int)hdr[2] != arch) return fail(MMC_ERR_WEIGHTS, "weights blob arch %u != requested %d", hdr[2], arch);
-    const uint32_t nt = hdr[3];
-    if (16 + (size_t)nt * 16 > nbytes) return fail(MMC_ERR_WEIGHTS, "weights blob truncated (table)");
+    BlobReader rd;
+    BlobError berr;
+    if (rd.open(packed, nbytes, arch, &berr)) return fail(berr.code, "%s", berr.msg);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(MMC_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
@@ -721,7 +856,7 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         bb->use_graph = false;
     }
 
-    // ---- 1. geometry: per block, pure arithmetic ----
+    // ---- 2. geometry (per block, pure arithmetic), then the plan: pass-level routes, then each block ----
     for (int i = 0, H = IMG / 2; i < NBLK; ++i) {
         BlockW& B = bb->blk[i];
         B.d = AD.blocks[i];
@@ -735,7 +870,6 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         B.project.n_chunks = (B.d.cout + 16 * B.project.nt - 1) / (16 * B.project.nt);
         H = B.Ho;
     }
-    // ---- 2. plan: pass-level routes, then each block ----
     {
         const std::vector<BlockW>& K = bb->blk;
         bb->fuse_stem = is_b0 && o.fuse;
@@ -789,268 +923,22 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         }
     }
 
-    // ---- 3. packing: what the plan launches, reading the blob's tensors in their fixed order ----
-    std::vector<uint64_t> table(2 * (size_t)nt);
-    memcpy(table.data(), base + 16, (size_t)nt * 16);
-    BlobReader rd{base, nbytes, nt, table.data()};
-    int err = 0;
-#define TAKE(var, n, what)                         \
-    const float* var = rd.take((n), what, &err);   \
-    if (!var) { mmc_backbone_destroy(bb); return err; }
-
-    // ---- stem: [Cstem][27] folded (ky,kx,c), bias[Cstem], padval[3] ----
+    // ---- 3. the blob's tensors in their fixed order, then what the plan launches: packed, uploaded, bound ----
     {
-        TAKE(w, (size_t)STEM_CH * 27, "stem.weight");
-        TAKE(b, STEM_CH, "stem.bias");
-        TAKE(pv, 3, "stem.padval");
-        const int snt = STEM_CH / 16;   // output fragments: lane quarter q owns channels q*4*snt + 4t + j
-        std::vector<_Float16> wp((size_t)STEM_CH * 32, (_Float16)0.0f);
-        for (int t = 0; t < snt; ++t)
-            for (int q = 0; q < 4; ++q)
-                for (int j = 0; j < 4; ++j) {
-                    const int prow = t * 16 + 4 * q + j;
-                    const int c = q * 4 * snt + 4 * t + j;
-                    const float* wc = w + (size_t)c * 27;
-                    for (int qq = 0; qq < 3; ++qq)           // kernel row qq, bytes 0..7 of its 9-byte run
-                        for (int jj = 0; jj < 8; ++jj) wp[prow * 32 + qq * 8 + jj] = (_Float16)(float)(wc[qq * 9 + jj] * LOG2E);
-                    for (int jj = 0; jj < 3; ++jj) wp[prow * 32 + 24 + jj] = (_Float16)(float)(wc[jj * 9 + 8] * LOG2E);
-                }
-        TRY_OR_FREE(dev_upload(bb, &bb->stem_w, wp));
-        std::vector<float> sb(STEM_CH);
-        for (int c = 0; c < STEM_CH; ++c) sb[c] = (float)(b[c] * LOG2E);
-        TRY_OR_FREE(dev_upload(bb, &bb->stem_b, sb));
-        std::vector<float> pvv = {pv[0], pv[1], pv[2], 0.f};
-        TRY_OR_FREE(dev_upload(bb, &bb->stem_pad, pvv));
+        RawNet raw;
+        if (read_blob(rd, AD, &raw, &berr)) {
+            mmc_backbone_destroy(bb);
+            return fail(berr.code, "%s", berr.msg);
+        }
+        TRY_OR_FREE(bind_net(bb, raw));
     }
-    // ---- blocks ----
+
+    // ---- 4. workspace and lanes ----
     size_t max_act = (size_t)(IMG / 2) * (IMG / 2) * STEM_CH, max_exp = 0, max_dw = 0, max_pool = 0;
     int max_c = 0;
     for (int i = 0; i < NBLK; ++i) {
-        BlockW& B = bb->blk[i];
+        const BlockW& B = bb->blk[i];
         const int H = B.H;
-        const bool tail_blk = B.front == Front::Tail && i >= 12;               // a row of tail7's block table
-        const bool tail_pre = i == 11 && bb->tail != TailRoute::None && bb->tail != TailRoute::B12;   // tail7's block 11
-        const bool frag_exp = B.front == Front::Mbt || B.front == Front::Mid14 || tail_blk || (tail_pre && bb->tail == TailRoute::B11All);
-        char nm[64];
-        if (B.has_expand) {
-            snprintf(nm, sizeof nm, "b%d.expand", i);
-            TAKE(w, (size_t)B.ce * B.d.cin, nm);
-            TAKE(b, B.ce, nm);
-            TRY_OR_FREE(pack_pw(bb, &B.expand, w, b, B.ce, B.d.cin, B.expand.nt, LOG2E, LOG2E));
-            const int kp = 32 * B.mb.ksteps;
-            std::vector<_Float16> wn((size_t)B.ce * kp, (_Float16)0.0f);   // natural rows, K zero padded
-            for (int c = 0; c < B.ce && B.fusable; ++c)
-                for (int k = 0; k < B.d.cin; ++k) wn[(size_t)c * kp + k] = (_Float16)(float)(w[(size_t)c * B.d.cin + k] * LOG2E);
-            if (B.front == Front::MbA || B.front == Front::MbD) TRY_OR_FREE(dev_upload(bb, &B.exp_nat, wn));
-            if (B.front == Front::Mb1 || B.front == Front::MbPre) {
-                // K-permuted copy for block 0's folded project: MFMA slot 8q+j holds input channel 4q+j (j < 4), the rest zero --
-                // the layout block 0's in-kernel project leaves in the lanes
-                std::vector<_Float16> wq((size_t)B.ce * 32, (_Float16)0.0f);
-                for (int c = 0; c < B.ce; ++c)
-                    for (int qq = 0; qq < 4; ++qq)
-                        for (int j = 0; j < 4; ++j) wq[(size_t)c * 32 + 8 * qq + j] = wn[(size_t)c * kp + 4 * qq + j];
-                TRY_OR_FREE(dev_upload(bb, &bb->b1_exp_pre, wq));
-            }
-            if (frag_exp) TRY_OR_FREE(dev_upload(bb, &B.exp_frag, pack_frag(wn.data(), B.ce, B.d.cin, kp, B.ce / 16, B.mb.ksteps, 1.0)));
-        }
-        {
-            snprintf(nm, sizeof nm, "b%d.dw", i);
-            TAKE(w, (size_t)B.ce * B.d.k * B.d.k, nm);  // [ce][k][k]
-            TAKE(b, B.ce, nm);
-            const int kk = B.d.k * B.d.k;
-            // the taps see a log2(e)-scaled input (stem or expand output) and produce a scaled output: the factors cancel --
-            // except for an expand-less block fed by a project conv (B4's block 1), whose input is in the plain domain
-            const double tsc = (B.has_expand || i == 0) ? 1.0 : LOG2E;
-            std::vector<float> wt((size_t)kk * B.ce);
-            for (int c = 0; c < B.ce; ++c)
-                for (int t = 0; t < kk; ++t) wt[(size_t)t * B.ce + c] = (float)(w[(size_t)c * kk + t] * tsc);
-            TRY_OR_FREE(dev_upload(bb, &B.dw_w, wt));
-            std::vector<float> db(B.ce);
-            for (int c = 0; c < B.ce; ++c) db[c] = (float)(b[c] * LOG2E);
-            TRY_OR_FREE(dev_upload(bb, &B.dw_b, db));
-            const bool dwp4 = B.front == Front::Mid14 || tail_blk || (tail_pre && bb->tail == TailRoute::B11All);
-            if (B.front == Front::Mbt || dwp4) {
-                // taps of tail7_kernel / mid14_kernel / mbt_kernel as fp16 pairs: kernel row ky = (k0,k1), (k2,k3), (k4,0); the kernel derives the
-                // odd-output pairs by shifts, giving the same values as mbconv_d_kernel's wl2 table
-                std::vector<uint32_t> dp((size_t)15 * B.ce, 0u);
-                auto tap = [&](int c, int ky, int kx) -> _Float16 {
-                    return kx < B.d.k ? (_Float16)w[(size_t)c * kk + ky * B.d.k + kx] : (_Float16)0.0f;
-                };
-                for (int c = 0; c < B.ce; ++c)
-                    for (int ky = 0; ky < B.d.k; ++ky)
-                        for (int d = 0; d < 3; ++d) {   // slot 3*ky + d holds taps (2d, 2d+1) of kernel row ky
-                            _Float16 h[2] = {tap(c, ky, 2 * d), tap(c, ky, 2 * d + 1)};
-                            uint32_t u;
-                            memcpy(&u, h, 4);
-                            dp[(size_t)(ky * 3 + d) * B.ce + c] = u;
-                        }
-                if (B.front == Front::Mbt) TRY_OR_FREE(dev_upload(bb, &B.t_dwp, dp));
-                if (dwp4) {
-                    // the same 15 dwords + the bias (as the 16th) in 16-byte requests: [4][ce][4] -- request j of channel c holds slots
-                    // 4j .. 4j+3; a wave's request is 1 KB contiguous (16 dword loads per thread were 16 wave-instructions of 256 bytes)
-                    std::vector<uint32_t> dp4((size_t)16 * B.ce, 0u);
-                    for (int c = 0; c < B.ce; ++c)
-                        for (int t = 0; t < 16; ++t) {
-                            uint32_t v = 0u;
-                            if (t < 15) v = dp[(size_t)t * B.ce + c];
-                            else memcpy(&v, &db[c], 4);   // the bias exactly as dw_b holds it
-                            dp4[((size_t)(t / 4) * B.ce + c) * 4 + (t % 4)] = v;
-                        }
-                    TRY_OR_FREE(dev_upload(bb, &B.t_dwp4, dp4));
-                }
-            }
-            if (B.mbt4 || B.mid14m) {
-                // Depthwise on the matrix pipe (v_mfma_f32_4x4x4_16B_f16: 16 independent blocks = 16 channels).  A operand
-                // of block c, kernel row ky, input quad h (columns x0 - 2 + 4h .. +3 of an output tile x0 .. x0+3): the Toeplitz slice
-                // A[i][k] = w[c][ky][k - i + 4h - 2 + R] (zero outside 0 .. K-1), lane 4 blk + i holding k = 0 .. 3, block blk = channel
-                // 2 (blk & 3) + ((blk >> 2) & 1) + 8 (blk >> 3) of the group (channels 2k, 2k+1 in neighbouring 16-lane rows: the kernel
-                // pairs them with v_permlane16_swap).
-                const int K = B.d.k, R = K / 2, ngr = B.ce / 16;
-                std::vector<_Float16> dd((size_t)ngr * K * 2 * 64 * 4, (_Float16)0.0f);
-                for (int g = 0; g < ngr; ++g)
-                    for (int ky = 0; ky < K; ++ky)
-                        for (int h = 0; h < 2; ++h)
-                            for (int ln = 0; ln < 64; ++ln) {
-                                const int blk = ln >> 2, ii = ln & 3;
-                                const int cc = 2 * (blk & 3) + ((blk >> 2) & 1) + 8 * (blk >> 3);
-                                for (int k = 0; k < 4; ++k) {
-                                    const int t = k - ii + 4 * h - 2 + R;
-                                    if (t < 0 || t >= K) continue;
-                                    dd[((((size_t)g * K + ky) * 2 + h) * 64 + ln) * 4 + k] = (_Float16)(float)(w[(size_t)(16 * g + cc) * kk + ky * K + t] * tsc);
-                                }
-                            }
-                TRY_OR_FREE(dev_upload(bb, &B.dw_diag, dd));
-            }
-        }
-        {
-            snprintf(nm, sizeof nm, "b%d.se", i);
-            TAKE(wr, (size_t)B.cs * B.ce, nm);
-            TAKE(br, B.cs, nm);
-            TAKE(we, (size_t)B.ce * B.cs, nm);
-            TAKE(be, B.ce, nm);
-            const bool se_launch = B.back == Back::SeProject || B.back == Back::SeFolded;
-            const double psc = 1.0 / ((double)B.Ho * B.Ho * LOG2E);   // FC1 on pooled sums of HW log2(e)-scaled activations
-            if (se_launch && B.se == Se::Fused) {
-                // Squeeze-excite weights, fp32 in MFMA fragment order (se_fused_kernel): 3 output/k fragments of 16 cover Cs <= 48
-                const int ng = B.ce / 16;
-                std::vector<float> wrp((size_t)ng * 3 * 64 * 4 + 4, 0.f), wep((size_t)ng * 3 * 64 * 4 + 4, 0.f);
-                for (int g = 0; g < ng; ++g)
-                    for (int t = 0; t < 3; ++t)
-                        for (int ln = 0; ln < 64; ++ln)
-                            for (int e = 0; e < 4; ++e) {
-                                const int ii = ln & 15, qq = ln >> 4;
-                                const size_t off = (((size_t)g * 3 + t) * 64 + ln) * 4 + e;
-                                const int j = 16 * t + ii, c = 16 * g + 4 * qq + e;         // FC1: Wr[j][c]
-                                if (j < B.cs) wrp[off] = (float)(wr[(size_t)j * B.ce + c] * psc);
-                                const int n = 16 * g + ii, k = 16 * t + 4 * qq + e;         // FC2: We[n][k] (T = g, k-group = t)
-                                if (k < B.cs) wep[off] = we[(size_t)n * B.cs + k];
-                            }
-                TRY_OR_FREE(dev_upload(bb, &B.se_wrp, wrp));
-                TRY_OR_FREE(dev_upload(bb, &B.se_wep, wep));
-            }
-            if (se_launch && B.se != Se::Fused) {   // natural fp32 rows: se_small_kernel; se_wide_kernel reads the excite FC transposed
-                std::vector<float> wrn((size_t)B.cs * B.ce);
-                for (size_t e = 0; e < wrn.size(); ++e) wrn[e] = (float)(wr[e] * psc);
-                TRY_OR_FREE(dev_upload(bb, &B.se_wr_nat, wrn));
-                if (B.se == Se::Small) {
-                    TRY_OR_FREE(dev_upload(bb, &B.se_we_nat, std::vector<float>(we, we + (size_t)B.ce * B.cs)));
-                } else {   // [Cs][C]: neighbouring lanes, neighbouring words
-                    std::vector<float> wet((size_t)B.cs * B.ce);
-                    for (int c = 0; c < B.ce; ++c)
-                        for (int j = 0; j < B.cs; ++j) wet[(size_t)j * B.ce + c] = we[(size_t)c * B.cs + j];
-                    TRY_OR_FREE(dev_upload(bb, &B.se_we_nat, wet));
-                }
-                TRY_OR_FREE(dev_upload(bb, &B.se_br_nat, std::vector<float>(br, br + B.cs)));
-            }
-            if (B.back == Back::ProjPatch || tail_pre || tail_blk) {
-                // fp16, transposed for matrix-vector use: Wr^T [ce][csp], We^T [csp][ce] (csp = Cs padded to 4)
-                const int csp = B.cs4;
-                std::vector<_Float16> wrt((size_t)B.ce * csp, (_Float16)0.0f), wet((size_t)csp * B.ce, (_Float16)0.0f);
-                for (int c = 0; c < B.ce; ++c)
-                    for (int j = 0; j < B.cs; ++j) {
-                        wrt[(size_t)c * csp + j] = (_Float16)wr[(size_t)j * B.ce + c];
-                        wet[(size_t)j * B.ce + c] = (_Float16)we[(size_t)c * B.cs + j];
-                    }
-                if (B.back == Back::ProjPatch || tail_pre) {
-                    TRY_OR_FREE(dev_upload(bb, &B.t_wr, wrt));
-                    TRY_OR_FREE(dev_upload(bb, &B.t_we, wet));
-                    std::vector<float> brp(csp > 32 ? csp : 32, 0.f);
-                    for (int j = 0; j < B.cs; ++j) brp[j] = br[j];
-                    TRY_OR_FREE(dev_upload(bb, &B.pp_br, brp));
-                }
-                if (B.back == Back::ProjPatch) {
-                    // proj_patch_kernel's FC1: [group of four outputs][channel row][4] (ProjPatchArgs::wr_g), zero beyond ce
-                    const int rows = proj_patch_fc1_rows(B.ce);
-                    std::vector<_Float16> wrg((size_t)(csp / 4) * rows * 4, (_Float16)0.0f);
-                    for (int g = 0; g < csp / 4; ++g)
-                        for (int c = 0; c < B.ce; ++c)
-                            for (int e = 0; e < 4; ++e) wrg[((size_t)g * rows + c) * 4 + e] = wrt[(size_t)c * csp + 4 * g + e];
-                    TRY_OR_FREE(dev_upload(bb, &B.t_wrg, wrg));
-                }
-                if (tail_blk) {
-                    // tail7_kernel's 16-byte request layout (TailBlock::wr_t / we_t): two rows of the transposed matrices per request
-                    std::vector<_Float16> wr2((size_t)18 * 384 * 8), we2((size_t)24 * 288 * 8);
-                    for (int p = 0; p < 18; ++p)
-                        for (int t = 0; t < 384; ++t)
-                            for (int e = 0; e < 8; ++e) {
-                                const int cr = t / 12, j4 = t % 12, c = 64 * p + (e < 4 ? 0 : 32) + cr;
-                                wr2[((size_t)p * 384 + t) * 8 + e] = wrt[(size_t)c * csp + 4 * j4 + (e & 3)];
-                            }
-                    for (int p = 0; p < 24; ++p)
-                        for (int t = 0; t < 288; ++t)
-                            for (int e = 0; e < 8; ++e) we2[((size_t)p * 288 + t) * 8 + e] = wet[(size_t)(2 * p + (e < 4 ? 0 : 1)) * B.ce + 4 * t + (e & 3)];
-                    TRY_OR_FREE(dev_upload(bb, &B.t_wr2, wr2));
-                    TRY_OR_FREE(dev_upload(bb, &B.t_we2, we2));
-                }
-            }
-            if ((se_launch && B.se == Se::Fused) || tail_blk) {   // se_fused_kernel's and tail7's FC1 bias, zero padded to 48
-                std::vector<float> brs(B.cs > 48 ? B.cs : 48, 0.f);
-                for (int j = 0; j < B.cs; ++j) brs[j] = br[j];
-                TRY_OR_FREE(dev_upload(bb, &B.se_br, brs));
-            }
-            TRY_OR_FREE(dev_upload(bb, &B.se_be, std::vector<float>(be, be + B.ce)));
-        }
-        {
-            snprintf(nm, sizeof nm, "b%d.project", i);
-            TAKE(w, (size_t)B.d.cout * B.ce, nm);
-            TAKE(b, B.d.cout, nm);
-            TRY_OR_FREE(pack_pw(bb, &B.project, w, b, B.d.cout, B.ce, B.project.nt, 1.0 / LOG2E, 1.0));
-            if (B.proj == Proj::Fp8 && (B.back == Back::SeProject || B.back == Back::SeFolded)) {
-                // e4m3 weights for pw_gemm_fp8_kernel: per-output-channel scale amax / 448 (the 1 / log2 e of the scaled domain rides in the
-                // scale), fragment f = channels 16 f .. +15, k-step of 128, lane (i, q) holds k = 128 ks + 32 q .. +31 of channel 16 f + i
-                Fp8Layer& L = B.p8;
-                L.N = B.d.cout; L.K = B.ce; L.KS128 = (B.ce + 127) / 128; L.NFp = ((B.d.cout + 15) / 16 + 6) / 7 * 7;
-                std::vector<uint8_t> w8((size_t)L.NFp * L.KS128 * 64 * 32, (uint8_t)0);
-                std::vector<float> sw((size_t)16 * L.NFp, 0.0f), bp((size_t)16 * L.NFp, 0.0f);
-                for (int nn = 0; nn < L.N; ++nn) {
-                    float amax = 0.f;
-                    for (int k = 0; k < L.K; ++k) amax = std::max(amax, std::fabs(w[(size_t)nn * L.K + k]));
-                    const float sc = amax > 0.f ? amax / 448.0f : 1.0f;
-                    sw[nn] = (float)(sc / LOG2E);
-                    bp[nn] = b[nn];
-                    for (int k = 0; k < L.K; ++k) {
-                        const int f = nn / 16, ii = nn % 16, ks = k / 128, qq = (k % 128) / 32, e = k % 32;
-                        w8[((((size_t)f * L.KS128 + ks) * 64) + qq * 16 + ii) * 32 + e] = e4m3_encode(w[(size_t)nn * L.K + k] / sc);
-                    }
-                }
-                TRY_OR_FREE(dev_upload(bb, &L.w8, w8));
-                TRY_OR_FREE(dev_upload(bb, &L.sw, sw));
-                TRY_OR_FREE(dev_upload(bb, &L.b, bp));
-            }
-            if (B.back == Back::SeFolded)   // block 0's project conv as ONE MFMA fragment (16 outputs x 32 inputs)
-                TRY_OR_FREE(dev_upload(bb, &bb->b0_pre_w, pack_frag(w, 16, 32, 32, 1, 1, 1.0 / LOG2E)));
-            if (B.back == Back::ProjPatch) {   // proj_patch_kernel: K and N zero-padded to whole fragments
-                const int nf = (B.d.cout + 15) / 16;
-                TRY_OR_FREE(dev_upload(bb, &B.pp_w, pack_frag(w, B.d.cout, B.ce, B.ce, nf, proj_patch_ksteps(B.ce), 1.0 / LOG2E)));
-                std::vector<float> bp((size_t)16 * nf, 0.f);
-                for (int c = 0; c < B.d.cout; ++c) bp[c] = b[c];
-                TRY_OR_FREE(dev_upload(bb, &B.pp_b, bp));
-            }
-            if (tail_pre)   // tail7 pre-block: [12][24][64][8], k-steps 21..23 zero (its k-loop runs 4 steps at a time)
-                TRY_OR_FREE(dev_upload(bb, &bb->pre_wproj, pack_frag(w, B.d.cout, B.ce, B.ce, 12, 24, 1.0 / LOG2E)));
-            if (tail_blk)
-                TRY_OR_FREE(dev_upload(bb, &B.t_wproj, pack_frag(w, B.d.cout, B.ce, B.ce, B.d.cout / 16, B.ce / 32, 1.0 / LOG2E)));
-        }
         if (B.fusable) max_pool = std::max(max_pool, (size_t)B.mb.tiles_x * B.mb.tiles_y * B.ce);
         if ((size_t)H * H * B.ce > max_exp && B.has_expand && !B.fusable) max_exp = (size_t)H * H * B.ce;
         max_dw = std::max(max_dw, (size_t)B.Ho * B.Ho * B.ce);
@@ -1058,26 +946,6 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         max_pool = std::max(max_pool, (size_t)B.parts * B.ce);
         if (i == 0) max_pool = std::max(max_pool, (size_t)49 * B.ce);
         max_c = std::max(max_c, B.ce);
-    }
-    {
-        TAKE(w, (size_t)FEAT * HEAD_IN, "head.weight");
-        TAKE(b, FEAT, "head.bias");
-        TRY_OR_FREE(pack_pw(bb, &bb->head, w, b, FEAT, HEAD_IN, bb->head.nt, LOG2E, LOG2E));
-        if (bb->tail == TailRoute::B11 || bb->tail == TailRoute::B11All)   // the same weights in plain fragment order for tail7's head phase
-            TRY_OR_FREE(dev_upload(bb, &bb->head_wfrag, pack_frag(w, FEAT, HEAD_IN, HEAD_IN, FEAT / 16, HEAD_IN / 32, LOG2E)));
-    }
-    if (bb->tail != TailRoute::None) {
-        std::vector<TailBlock> tab(4);
-        for (int j = 0; j < 4; ++j) {
-            const BlockW& B = bb->blk[12 + j];
-            tab[j] = TailBlock{B.exp_frag, B.expand.b, B.t_dwp4, B.dw_b, B.t_wr2, B.se_br, B.t_we2, B.se_be, B.t_wproj, B.project.b,
-                               B.d.cout, B.d.k};
-        }
-        TRY_OR_FREE(dev_upload(bb, &bb->tail_tab, tab));
-    }
-    if (rd.next != nt) {
-        mmc_backbone_destroy(bb);
-        return fail(MMC_ERR_WEIGHTS, "weights blob has %u tensors, expected %u", nt, rd.next);
     }
     if (bb->chain_first >= 0) {   // room for the chained launch's second tensor per buffer (the 112 x 112 layers already need more)
         const size_t hw = (size_t)bb->blk[bb->chain_first].Ho * bb->blk[bb->chain_first].Ho;
@@ -1115,7 +983,6 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
     }
     TRY_OR_FREE(dev_alloc(bb, &bb->in_stage, mb * (size_t)IMG * IMG * 3));
     TRY_OR_FREE(dev_alloc(bb, &bb->out_stage, mb * (size_t)FEAT));
-#undef TAKE
 #undef TRY_OR_FREE
     *out = bb;
     return MMC_OK;
@@ -1152,15 +1019,12 @@ static int gemm_mt(const PwLayer& L, int M)
     return wgs2 >= 1024 ? 2 : 1;
 }
 
-static int run_gemm(const PwLayer& L, const _Float16* X, int M, _Float16* Y, int epi, const float* gate, int HW,
-                    const _Float16* res, float* gap_out, hipStream_t st)
+// `a`: the layer's bound arguments (gemm_args)
+static int run_gemm(const PwLayer& L, GemmArgs a, const _Float16* X, int M, _Float16* Y, const float* gate, const _Float16* res,
+                    float* gap_out, hipStream_t st)
 {
-    GemmArgs a{};
-    a.X = X; a.M = M; a.K = L.K; a.Wp = L.w; a.Kp = L.Kp; a.bias = L.b; a.Y = Y; a.N = L.N;
-    a.nt = L.nt; a.n_chunks = L.n_chunks; a.epi = epi; a.gate = gate; a.HW = HW; a.res = res;
-    a.gap_out = gap_out; a.inv_hw = (float)(1.0 / ((double)HW * LOG2E));  // GAP input is log2(e)-scaled
+    a.X = X; a.M = M; a.Y = Y; a.gate = gate; a.res = res; a.gap_out = gap_out;
     a.mt = gemm_mt(L, M);
-    a.defer_gate = gemm_defer_gate(gate != nullptr, HW);
     return launch_pw_gemm(a, st);
 }
 
@@ -1222,19 +1086,14 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
                                                           bb->fuse_b0b1 ? y : ws.dwbuf, ws.pool_part, n, st));
             break;
         case Front::Mbt: {
-            MbtArgs ta{};
-            ta.X = x; ta.wexp = B.exp_frag; ta.bexp = B.expand.b; ta.dwp = B.t_dwp; ta.bdw = B.dw_b; ta.D = ws.dwbuf;
-            ta.pool = ws.pool_part; ta.B = n; ta.H = B.H; ta.Cin = B.d.cin; ta.Ce = B.ce; ta.ks = B.d.k; ta.stride = B.d.s;
-            ta.dwtoe = B.mbt4 ? B.dw_diag : nullptr;
+            MbtArgs ta = B.mbt;
+            ta.X = x; ta.D = ws.dwbuf; ta.pool = ws.pool_part; ta.B = n;
             STEP(nm, B.front_label, launch_mbt(ta, st));
             break;
         }
         case Front::Mid14: {
-            Mid14Args ma{};
-            ma.X = x; ma.wexp = B.exp_frag; ma.bexp = B.expand.b; ma.dwp = B.t_dwp4; ma.bdw = B.dw_b; ma.D = ws.dwbuf;
-            ma.pool = ws.pool_part; ma.B = n; ma.Cin = B.d.cin; ma.Ce = B.ce; ma.ks = B.d.k;
-            ma.dwdiag = B.mid14m ? B.dw_diag : nullptr;
-            ma.nsplit = B.mid14m ? 1 : 4;
+            Mid14Args ma = B.mid;
+            ma.X = x; ma.D = ws.dwbuf; ma.pool = ws.pool_part; ma.B = n;
             if (bb->mid_clk && i == 10) ma.dbg_clk = bb->mid_clk + (size_t)lane_idx * bb->lane_cap * 128;
             if (ch0 >= 0 && i > ch0 && i <= ch1) {
                 ma.D = ch_dw(B.ce);
@@ -1248,22 +1107,19 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             break;
         }
         case Front::Mb1: {
-            Mb1Args m1{};
-            m1.X = y; m1.pre_w = bb->b0_pre_w; m1.pre_b = bb->blk[0].project.b; m1.pre_gate = ws.gate; m1.wexp = bb->b1_exp_pre;
-            m1.bexp = B.expand.b; m1.wdw = B.dw_w; m1.bdw = B.dw_b; m1.D = ws.dwbuf; m1.pool = ws.pool_part; m1.B = n;
-            m1.planar = B.planar ? 1 : 0;
+            Mb1Args m1 = B.mb1;
+            m1.X = y; m1.pre_gate = ws.gate; m1.D = ws.dwbuf; m1.pool = ws.pool_part; m1.B = n;
             STEP("b0.project+b1.mbconv", "mb1", launch_mb1(m1, st));
             break;
         }
         case Front::MbPre: case Front::MbD: case Front::MbA: {
             MbArgs a = B.mb;
-            a.X = x; a.Wexp = B.exp_nat; a.bexp = B.expand.b; a.Wdw = B.dw_w; a.bdw = B.dw_b; a.out = ws.dwbuf;
-            a.pool_part = ws.pool_part; a.B = n;
+            a.X = x; a.out = ws.dwbuf; a.pool_part = ws.pool_part; a.B = n;
             if (B.front == Front::MbD) {
                 STEP(nm, B.front_label, launch_mbconv_d(a, st));
             } else if (B.front == Front::MbPre) {
-                a.X = y; a.Cin = 32; a.Wexp = bb->b1_exp_pre;   // block 0's depthwise output; its gate is in ws.gate
-                STEP("b0.project+b1.mbconv", B.front_label, launch_mbconv_pre(a, bb->b0_pre_w, bb->blk[0].project.b, ws.gate, st));
+                a.X = y;   // block 0's depthwise output; its gate is in ws.gate
+                STEP("b0.project+b1.mbconv", B.front_label, launch_mbconv_pre(a, B.mb1.pre_w, B.mb1.pre_b, ws.gate, st));
             } else {
                 STEP(nm, B.front_label, launch_mbconv_a(a, st));
             }
@@ -1274,14 +1130,12 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             if (B.has_expand) {
                 snprintf(nm, sizeof nm, "b%d.expand", i);
                 STEP(nm, B.expand.label[gemm_mt(B.expand, n * HWi) - 1],
-                     run_gemm(B.expand, x, n * HWi, ws.expbuf, EPI_SILU, nullptr, HWi, nullptr, nullptr, st));
+                     run_gemm(B.expand, B.exp_gemm, x, n * HWi, ws.expbuf, nullptr, nullptr, nullptr, st));
                 SAVE(nm, ws.expbuf, (size_t)n * HWi * B.ce, true);
                 dw_in = ws.expbuf;
             }
-            DwArgs d{};
-            d.in = dw_in; d.wt = B.dw_w; d.bias = B.dw_b; d.out = ws.dwbuf; d.pool_part = ws.pool_part;
-            d.B = n; d.H = B.H; d.W = B.H; d.C = B.ce; d.Ho = B.Ho; d.Wo = B.Ho; d.pad_t = B.pad; d.pad_l = B.pad;
-            d.ks = B.d.k; d.stride = B.d.s; d.tw = B.tw; d.CG = B.CG; d.S = B.S; d.iters = B.iters; d.parts = B.parts; d.nz = B.nz;
+            DwArgs d = B.dw;
+            d.in = dw_in; d.out = ws.dwbuf; d.pool_part = ws.pool_part; d.B = n;
             snprintf(nm, sizeof nm, "b%d.dw", i);
             STEP(nm, B.front_label, launch_dwconv(d, st));
         }
@@ -1291,13 +1145,10 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
         if (B.back == Back::Tail) break;   // block 11's back half: the tail launch below
         if (B.back == Back::ProjPatch) {
             // squeeze-excite + project, one patch per workgroup (proj_patch_kernel): no gate tensor, one launch
-            ProjPatchArgs pa{};
-            pa.X = ws.dwbuf; pa.pool_part = ws.pool_part; pa.wr_g = B.t_wrg; pa.br = B.pp_br; pa.we_t = B.t_we; pa.be = B.se_be;
-            pa.wfrag = B.pp_w; pa.bias = B.pp_b; pa.res = B.skip ? x : nullptr; pa.Y = y;
+            ProjPatchArgs pa = B.pp;
+            pa.X = ws.dwbuf; pa.pool_part = ws.pool_part; pa.res = B.skip ? x : nullptr; pa.Y = y; pa.B = n;
             pa.dbg_gate = bb->keep ? ws.gate : nullptr;
             pa.dbg_clk = bb->keep ? bb->dbg_clk : nullptr;
-            pa.B = n; pa.HW = HWo; pa.K = B.ce; pa.N = B.d.cout; pa.CSP = B.cs4; pa.nparts = B.nparts;
-            pa.psc = (float)(1.0 / ((double)HWo * LOG2E));
             if (ch0 >= 0 && i >= ch0 && i <= ch1) {
                 if (i == ch0) { xbase = x; ybase = y; }
                 pa.X = ch_dw(B.ce);
@@ -1328,53 +1179,51 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
             continue;
         }
         snprintf(nm, sizeof nm, "b%d.gate", i);
+        const SeArgs& se = B.sea;
         if (B.se == Se::Wide)
-            STEP(nm, "se_wide", launch_se_wide(ws.pool_part, B.nparts, n, B.ce, B.cs, B.se_wr_nat, B.se_br_nat, B.se_we_nat, B.se_be,
-                                               ws.gate, st));
+            STEP(nm, "se_wide", launch_se_wide(ws.pool_part, B.nparts, n, B.ce, se.Cs, se.wr, se.br, se.we, se.be, ws.gate, st));
         else if (B.se == Se::Small)
-            STEP(nm, "se_small", launch_se_small(ws.pool_part, B.nparts, n, B.ce, B.cs, B.se_wr_nat, B.se_br_nat, B.se_we_nat, B.se_be,
-                                                 ws.gate, st));
+            STEP(nm, "se_small", launch_se_small(ws.pool_part, B.nparts, n, B.ce, se.Cs, se.wr, se.br, se.we, se.be, ws.gate, st));
         else
-            STEP(nm, "se_fused", launch_se_gate(ws.pool_part, B.nparts, n, B.ce, B.cs4, B.se_wrp, B.se_br, B.se_wep, B.se_be,
-                                                ws.gate, st));
+            STEP(nm, "se_fused", launch_se_gate(ws.pool_part, B.nparts, n, B.ce, se.Cs, se.wr, se.br, se.we, se.be, ws.gate, st));
         SAVE(nm, ws.gate, (size_t)n * B.ce, false);
         if (B.back == Back::SeFolded) continue;   // block 0's project runs inside block 1's kernel
         snprintf(nm, sizeof nm, "b%d.project", i);
         if (B.proj == Proj::Thin) {
             // small-K, small-N project on a big image (B4 blocks 0, 1; B0 block 1): stream one patch's fragments per workgroup
-            GemmArgs a{};
-            a.X = ws.dwbuf; a.M = n * HWo; a.K = B.project.K; a.Wp = B.project.w; a.Kp = B.project.Kp; a.bias = B.project.b; a.Y = y;
-            a.N = B.project.N; a.nt = B.project.nt; a.n_chunks = B.project.n_chunks; a.epi = EPI_LINEAR; a.gate = ws.gate; a.HW = HWo;
-            a.res = B.skip ? x : nullptr;
+            GemmArgs a = B.proj_gemm;
+            a.X = ws.dwbuf; a.M = n * HWo; a.Y = y; a.gate = ws.gate; a.res = B.skip ? x : nullptr;
             a.x_plane_rows = B.planar ? n * HWo : 0;
             STEP(nm, "thin_proj", launch_thin_proj(a, n, st));
         } else if (B.proj == Proj::Fp8) {
-            Fp8GemmArgs fa{};
-            fa.X = ws.dwbuf; fa.M = n * HWo; fa.K = B.p8.K; fa.W8 = B.p8.w8; fa.KS128 = B.p8.KS128; fa.NFp = B.p8.NFp; fa.sw = B.p8.sw;
-            fa.bias = B.p8.b; fa.Y = y; fa.N = B.p8.N; fa.gate = ws.gate; fa.HW = HWo; fa.res = B.skip ? x : nullptr;
+            Fp8GemmArgs fa = B.proj8;
+            fa.X = ws.dwbuf; fa.M = n * HWo; fa.Y = y; fa.gate = ws.gate; fa.res = B.skip ? x : nullptr;
             STEP(nm, "pw_gemm_fp8", launch_pw_gemm_fp8(fa, st));
         } else
             STEP(nm, B.project.label[gemm_mt(B.project, n * HWo) - 1],
-                 run_gemm(B.project, ws.dwbuf, n * HWo, y, EPI_LINEAR, ws.gate, HWo, B.skip ? x : nullptr, nullptr, st));
+                 run_gemm(B.project, B.proj_gemm, ws.dwbuf, n * HWo, y, ws.gate, B.skip ? x : nullptr, nullptr, st));
         snprintf(nm, sizeof nm, "b%d.out", i);
         SAVE(nm, y, (size_t)n * HWo * B.d.cout, true);
         swap_xy();
     }
     // ---- the tail and the head ----
-    const float inv_hw7 = (float)(1.0 / (49.0 * LOG2E));
+    // Every tail7 launch starts from the handle's bound TailArgs (block table, block 11's and the head's weights, inv_hw).  The kernel
+    // runs block 11 when pre_D or pre_X is set and the head phase when head_w is: a launch without the head phase clears it.
+    auto tail_args = [&](bool head) {
+        TailArgs ta = bb->tail_args;
+        ta.B = n;
+        if (!head) ta.head_w = nullptr;
+        return ta;
+    };
     if (bb->tail == TailRoute::B11All || (bb->tail == TailRoute::B11 && !bb->keep)) {
         // from block 11's input (B11All) or its depthwise output (B11) through blocks 12..15 and the head conv to the features, ONE launch
-        const BlockW& B11 = bb->blk[11];
-        TailArgs ta{};
-        ta.B = n; ta.blk = bb->tail_tab; ta.nblk = 4;
+        TailArgs ta = tail_args(true);
+        ta.nblk = 4; ta.feat = out_dev;
         if (bb->tail == TailRoute::B11All) {
-            ta.pre_X = x; ta.pre_wexp = B11.exp_frag; ta.pre_bexp = B11.expand.b; ta.pre_dwp = B11.t_dwp4; ta.pre_bdw = B11.dw_b;
+            ta.pre_X = x;
         } else {
             ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part;
         }
-        ta.pre_wr_t = B11.t_wr; ta.pre_br = B11.pp_br; ta.pre_we_t = B11.t_we; ta.pre_be = B11.se_be; ta.pre_wproj = bb->pre_wproj;
-        ta.pre_bproj = B11.project.b; ta.inv_hw = inv_hw7;
-        ta.head_w = bb->head_wfrag; ta.head_b = bb->head.b; ta.feat = out_dev;
         if (bb->tail == TailRoute::B11All && bb->tail_clk) {   // debug clock: rows of this lane's patches
             ta.dbg_clk = bb->tail_clk + (size_t)lane_idx * bb->lane_cap * 64; ta.clk_sections = 1;
         }
@@ -1383,10 +1232,9 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
     }
     if (bb->tail == TailRoute::B11) {   // per-tensor mode: block 11's back half on its own
         const BlockW& B11 = bb->blk[11];
-        TailArgs ta{};
-        ta.B = n; ta.blk = bb->tail_tab; ta.nblk = 0; ta.Y = y; ta.dbg_gate = ws.gate;
-        ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part; ta.pre_wr_t = B11.t_wr; ta.pre_br = B11.pp_br; ta.pre_we_t = B11.t_we;
-        ta.pre_be = B11.se_be; ta.pre_wproj = bb->pre_wproj; ta.pre_bproj = B11.project.b; ta.inv_hw = inv_hw7;
+        TailArgs ta = tail_args(false);
+        ta.nblk = 0; ta.Y = y; ta.dbg_gate = ws.gate;
+        ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part;
         STEP("b11.tail", "tail7", launch_tail7(ta, st));
         SAVE("b11.gate", ws.gate, (size_t)n * B11.ce, false);
         SAVE("b11.out", y, (size_t)n * 49 * 192, true);
@@ -1394,15 +1242,15 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
     }
     if (bb->tail != TailRoute::None && !bb->keep) {
         // blocks 12..15 in one launch, one patch per workgroup, tensors resident in LDS (tail7_kernel)
-        TailArgs ta{};
-        ta.X = x; ta.Y = y; ta.B = n; ta.nblk = 4; ta.blk = bb->tail_tab;
+        TailArgs ta = tail_args(false);
+        ta.X = x; ta.Y = y; ta.nblk = 4;
         STEP("b12-15.tail", "tail7", launch_tail7(ta, st));
         swap_xy();
     } else if (bb->tail != TailRoute::None) {
         for (int j = 0; j < 4; ++j) {   // block at a time so every intermediate tensor can be read back
             const BlockW& B = bb->blk[12 + j];
-            TailArgs ta{};
-            ta.X = x; ta.Y = y; ta.B = n; ta.nblk = 1; ta.blk = bb->tail_tab + j;
+            TailArgs ta = tail_args(false);
+            ta.X = x; ta.Y = y; ta.nblk = 1; ta.blk += j;
             ta.dbg_dw = ws.dwbuf; ta.dbg_gate = ws.gate; ta.dbg_clk = ws.pool_part;
             snprintf(nm, sizeof nm, "b%d.tail", 12 + j);
             STEP(nm, "tail7", launch_tail7(ta, st));
@@ -1418,14 +1266,13 @@ static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t*
         }
     }
     if (bb->tail == TailRoute::B11) {   // per-tensor mode: the head phase of tail7_kernel on its own
-        TailArgs ta{};
-        ta.X = x; ta.B = n; ta.nblk = 0; ta.blk = bb->tail_tab; ta.in_wide = 1;
-        ta.head_w = bb->head_wfrag; ta.head_b = bb->head.b; ta.feat = out_dev; ta.inv_hw = inv_hw7;
+        TailArgs ta = tail_args(true);
+        ta.X = x; ta.nblk = 0; ta.in_wide = 1; ta.feat = out_dev;
         STEP("head.tail", "tail7", launch_tail7(ta, st));
     } else {
         const int HWh = bb->blk[bb->nblk - 1].Ho * bb->blk[bb->nblk - 1].Ho;
         STEP("head", bb->head.label[0],
-             run_gemm(bb->head, x, n * HWh, nullptr, EPI_GAP, nullptr, HWh, nullptr, out_dev, st));
+             run_gemm(bb->head, bb->head_gemm, x, n * HWh, nullptr, nullptr, nullptr, out_dev, st));
     }
 #undef SAVE
 #undef STEP

@@ -13,13 +13,13 @@ and ``|x|``.  With ``u = 2**-11`` (fp16 unit roundoff) and ``v = 2**-24`` (fp32)
 
 1. **Inputs.**  Tensors read from the device are exact.
 2. **Weights.**  Every conv, depthwise and squeeze-excite weight carries a relative error <= u: the host rounds them to
-   fp16 after folding the log2(e) of the scaled SiLU domain (``mmc_api.cpp:539``, ``:582``, ``:815``, ``:843``, ``:877``, ``:919``,
-   ``:971``); the fp32 taps of ``dwconv_kernel`` / ``mbconv_a_kernel`` and the fp32 squeeze-excite weights of ``se_small`` /
+   fp16 after folding the log2(e) of the scaled SiLU domain (``csrc/backbone_pack.h``: ``pack_pw``, ``pack_frag``, ``pack_stem``, ``pack_expand_rows``,
+   ``pack_dw_pairs``, ``pack_dw_toeplitz``, ``pack_se_fc1_t16`` / ``pack_se_fc2_t16``); the fp32 taps of ``dwconv_kernel`` / ``mbconv_a_kernel`` and the fp32 squeeze-excite weights of ``se_small`` /
    ``se_wide`` / ``se_fused`` are charged the same (an overestimate there).  Biases are exact.
 3. **Accumulation.**  A K-term dot product accumulated in fp32 (MFMA, ``v_dot2_f32_f16``, ``v_fma_mix_f32``) carries
    <= (K + 4) v (sum|w x| + |bias| + |skip|).  The ``+ 4`` is for what surrounds the dot product in fp32: the bias times log2(e)
-   (``mmc_api.cpp:820``, ``:869``), the skip addition (``k_early.hip:84``, ``k_tail.hip:207``) and the fp32 factor 1/log2(e) that
-   ``mmc_backbone_read_activation`` applies to SiLU-domain tensors on the way out (``mmc_api.cpp:1625-1626``).
+   (``pack_bias`` of the stem's and the depthwise bias), the skip addition (``k_early.hip:84``, ``k_tail.hip:207``) and the fp32 factor 1/log2(e) that
+   ``mmc_backbone_read_activation`` applies to SiLU-domain tensors on the way out (``mmc_api.cpp``, ``mmc_backbone_read_activation``).
 4. **Values held in fp16.**  Each value the kernel holds in fp16 between phases carries a relative u plus an absolute 2**-25
    (half the smallest subnormal):
    - the expanded tensor in LDS (``k_mbconv.hip:434-437``, ``k_early.hip:562``, ``k_mid.hip:360``);
