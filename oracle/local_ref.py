@@ -40,8 +40,42 @@ and ``|x|``.  With ``u = 2**-11`` (fp16 unit roundoff) and ``v = 2**-24`` (fp32)
    therefore carries u mean|d| per channel (plus its own fp32 summation, rule 3), which then passes through FC1, SiLU,
    FC2 and sigmoid under rules 2, 3 and 5.
 
-The comparison that uses these bounds (``tests/test_gpu_local.py``) allows 2 x bound per element: the factor covers the
-second-order terms this first-order model drops.
+7. **fp8 project convs** (``out_fp8``; ``pw_gemm_fp8_kernel``, ``k_generic.hip``).  The operands are not rounded values with an
+   error: they are e4m3 CODES, and the reference replicates them bit for bit with its own codec (``e4m3_encode`` /
+   ``e4m3_decode``, independent of ``backbone_pack.h``).  Weights: in float32, ``amax`` per output channel, ``sc = amax / 448`` (1
+   where ``amax == 0``), codes of ``w / sc``, ``sw = float32(float64(sc) / log2 e)`` -- what ``pack_fp8`` does.  Activations: the
+   device's fp16 depthwise tensor is recovered from ``read_activation``'s value (times fp32 log2 e, rounded to fp16: the round trip
+   errs by 2**-23 relative, and re-applying the library's factor must reproduce the input bits -- asserted); then in float32,
+   in the kernel's order, ``v = float32(d16) g``, ``mx = max |v|`` over the row, ``inv = 447 / mx``, ``sx = mx float32(1 / 447)``,
+   codes of ``v inv`` (``mx == 0``: codes 0, ``sx = 0``).  The value is ``(sum_k qw qx) sx sw + bias (+ skip)`` in float64 (the
+   code products are exact there).  What is left is rule 3, ``(K + 4) v (sum|qw qx| sx sw + |bias| + |skip|)``, and rule 4 on the
+   stored output.  No weight term ``u``: the weights are replicated, not rounded.
+   *Ambiguous operands.*  Every step above is one correctly rounded IEEE fp32 operation, so the codes should match exactly; the
+   one allowance is for a division or multiply that differs in its last bit on the device.  An activation operand whose ``v inv``
+   lies within 4 fp32 ulps of an e4m3 rounding boundary may land on the neighbouring code: for those operands only,
+   ``|qw| (the e4m3 step at that boundary) sx sw`` is added to the bound of the outputs they feed, and their count is returned.
+   Uniform fp32 products put 8 / 2**20 ~ 1e-5 of the operands there; the checks refuse a stage with more than ``AMBIGUOUS_MAX``
+   (1e-4), so the term cannot hide a kernel that quantises differently.
+   *The instruction's own sum.*  Rule 3 is applied as it stands, although ``v_mfma_scale_f32_16x16x128_f8f6f4`` does not sum its
+   128 products the way the rule assumes.
+   What the device tensors show (MI355X, the three parity patches, both schedules): every element is within 2 x bound, worst
+   1.12 at K = 336 (2 of 65856 elements over 1 x) and falling with K (0.85 at 672, 0.77 at 960, 0.71 at 1632, 0.42 at 2688); the
+   CPU emulation's plain fp32 sums give 0.86 at K = 336 and 0.42 at 2688 on the oracle's taps.  The part of |got - ref| that the
+   fp16 store cannot explain reaches 30-56 units of the accumulator (of sx sw) whatever K is, i.e. 435 x 2**-24 sum|qw qx| at
+   K = 336 (rule 3 alone: 340) down to 175 x 2**-24 at K = 2688 (2692), and only 90-93 % of the outputs equal the fp16 rounding of
+   an exact sum through the fp32 epilogue.  No structure by row, column, fragment or channel.  So the instruction's internal sum is
+   coarser than a sequential fp32 one by an amount that does not grow with K and that the factor 2 absorbs at these shapes.
+   A micro-run against exact sums (``tools/ubench/mfma_f8_sum.hip`` -> ``profiles/mfma_f8_sum.txt``) says why: the instruction sums
+   its products in groups of 8 consecutive k and drops, inside a group, whatever lies below 2**-15 of the group's largest product
+   (2**2 next to 448 x 448; 7 of 64 equal small products lost; cancellation of the large ones does not bring it back), keeps 2**-23
+   of the largest product across groups, and adds the finished sum to C with round to nearest even.  On random codes one
+   instruction errs by up to 2**-11 of its largest product, 1045-1243 x 2**-24 sum|p| where rule 3 allows 132.  Real rows, one
+   operand at 447 and most far below, stay much closer (the 435 above).  Rule 3 is therefore NOT a proven bound for this
+   instruction: it is the stated rule, it holds with the factor 2 on these tensors, and a sound replacement would add a term of the
+   form 2**-15 sum over groups of 8 of max|qw qx| -- left for a change that also re-proves the sharpness list against it.
+
+The comparison that uses these bounds (``tests/test_gpu_local.py``, ``tests/test_gpu_local_fp8.py``) allows 2 x bound per element:
+the factor covers the second-order terms this first-order model drops.
 """
 
 from __future__ import annotations
@@ -251,6 +285,119 @@ def out(W: Weights, i: int, d, g, skip=None):
     return _out(y, _held16(y, e))
 
 
+# ---- rule 7: the fp8 project conv on replicated e4m3 operands ------------------------------------------------------------
+
+LOG2E = 1.4426950408889634
+AMBIGUOUS_ULPS = 4
+AMBIGUOUS_MAX = 1e-4      # largest share of a stage's activation operands that may sit on a rounding boundary
+
+
+def e4m3_decode(codes) -> np.ndarray:
+    """OCP e4m3fn codes (uint8) -> float32: 1 sign, 4 exponent (bias 7), 3 mantissa bits; no infinities, 0x7F / 0xFF are NaN."""
+    c = np.asarray(codes, dtype=np.uint8).astype(np.int64)
+    e, m = (c >> 3) & 15, c & 7
+    mag = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e - 10.0))
+    mag = np.where((e == 15) & (m == 7), np.nan, mag)
+    return np.where(c & 0x80, -mag, mag).astype(np.float32)
+
+
+_E4M3_VALUES = e4m3_decode(np.arange(127)).astype(np.float64)             # 0 .. 448, ascending
+_E4M3_MIDS = 0.5 * (_E4M3_VALUES[:-1] + _E4M3_VALUES[1:])                  # the 126 rounding boundaries (exact)
+
+
+def e4m3_encode(x) -> np.ndarray:
+    """float32 -> OCP e4m3fn codes: round to nearest, ties to the even code, saturating at +-448, subnormals down to 2**-9
+    (below half of that, and at the tie 2**-10: zero); NaN -> 0x7F."""
+    x = np.asarray(x, dtype=np.float32)
+    with np.errstate(invalid="ignore"):                                    # a signalling NaN stays a NaN
+        a = np.abs(x).astype(np.float64)
+    idx = np.searchsorted(_E4M3_MIDS, a, side="left")                      # boundaries strictly below |x|; NaN sorts last
+    tie = (idx < 126) & (a == _E4M3_MIDS[np.minimum(idx, 125)])
+    idx = np.where(tie & (idx % 2 == 1), idx + 1, idx)
+    code = np.where(np.isnan(a), 0x7F, idx).astype(np.uint8)
+    return code | np.where(np.signbit(x) & ~np.isnan(a), 0x80, 0).astype(np.uint8)
+
+
+def _e4m3_ambiguity(t: np.ndarray) -> np.ndarray:
+    """float32 values about to be encoded -> the e4m3 step at the rounding boundary within AMBIGUOUS_ULPS fp32 ulps, else 0."""
+    a = np.abs(t).astype(np.float64)
+    ulp = np.spacing(np.abs(t)).astype(np.float64)
+    hi = np.minimum(np.searchsorted(_E4M3_MIDS, a, side="left"), 125)
+    lo = np.maximum(hi - 1, 0)
+    j = np.where(np.abs(a - _E4M3_MIDS[lo]) < np.abs(a - _E4M3_MIDS[hi]), lo, hi)
+    near = np.abs(a - _E4M3_MIDS[j]) <= AMBIGUOUS_ULPS * ulp
+    return np.where(near, _E4M3_VALUES[j + 1] - _E4M3_VALUES[j], 0.0)
+
+
+def fp8_weight_codes(w):
+    """folded fp32 project weight [N][K] -> (codes uint8 [N][K], sw float32 [N]) exactly as ``pack_fp8`` quantises it."""
+    w = np.asarray(w, dtype=np.float32)
+    amax = np.abs(w).max(axis=1)
+    sc = np.where(amax > 0, amax / np.float32(448.0), np.float32(1.0)).astype(np.float32)
+    codes = e4m3_encode(w / sc[:, None])
+    sw = (sc.astype(np.float64) / LOG2E).astype(np.float32)
+    return codes, sw
+
+
+def fp8_activation_rows(d, g):
+    """``read_activation``'s ``b{i}.dw`` (N, H, W, K) and ``b{i}.gate`` (N, K) -> the kernel's gated rows in float32, (N H W, K):
+    v = float32(d16) g on the recovered fp16 tensor."""
+    read = np.asarray(d, dtype=np.float32)
+    d16 = (read * np.float32(LOG2E)).astype(np.float16)
+    back = d16.astype(np.float32) * np.float32(1.0 / LOG2E)                # mmc_backbone_read_activation's factor
+    if not np.array_equal(back.view(np.uint32), read.view(np.uint32)):
+        raise ValueError("the depthwise tensor is not fp16 times the library's fp32 1 / log2(e): the fp16 bits cannot be recovered")
+    n, h, w_, k = read.shape
+    v = d16.astype(np.float32) * np.asarray(g, dtype=np.float32)[:, None, None, :]
+    return v.reshape(n * h * w_, k)
+
+
+def fp8_activation_codes(v):
+    """gated rows float32 (M, K) -> (codes uint8 (M, K), sx float32 (M,), t = v inv float32 (M, K)), the kernel's recipe."""
+    v = np.asarray(v, dtype=np.float32)
+    mx = np.abs(v).max(axis=1)
+    pos = mx > 0
+    safe = np.where(pos, mx, np.float32(1.0)).astype(np.float32)
+    inv = np.where(pos, np.float32(447.0) / safe, np.float32(0.0)).astype(np.float32)
+    sx = np.where(pos, mx * (np.float32(1.0) / np.float32(447.0)), np.float32(0.0)).astype(np.float32)
+    t = v * inv[:, None]
+    return e4m3_encode(t), sx, t
+
+
+class Fp8Info(NamedTuple):
+    ambiguous: int     # activation operands within AMBIGUOUS_ULPS fp32 ulps of an e4m3 rounding boundary
+    operands: int      # rows x K
+
+    @property
+    def share(self) -> float:
+        return self.ambiguous / max(self.operands, 1)
+
+
+def out_fp8(W: Weights, i: int, d, g, skip=None):
+    """``b{i}.dw``, the device's ``b{i}.gate`` (and the block input where the block has a skip) -> the project conv on e4m3
+    operands (rule 7): ``(ref, bound, Fp8Info)``."""
+    w = W[f"b{i}.project.weight"].numpy()
+    b = W[f"b{i}.project.bias"].numpy()
+    n_out, K = w.shape
+    cw, sw = fp8_weight_codes(w)
+    cx, sx, t = fp8_activation_codes(fp8_activation_rows(d, g))
+    qw, qx = e4m3_decode(cw).astype(np.float64), e4m3_decode(cx).astype(np.float64)
+    scale = sx.astype(np.float64)[:, None] * sw.astype(np.float64)[None, :]
+    y = (qx @ qw.T) * scale + b
+    mag = (np.abs(qx) @ np.abs(qw).T) * scale + np.abs(b)
+    step = _e4m3_ambiguity(t)
+    amb = (step @ np.abs(qw).T) * scale
+    shape = tuple(np.shape(d)[:3]) + (n_out,)
+    y, mag, amb = y.reshape(shape), mag.reshape(shape), amb.reshape(shape)
+    if skip is not None:
+        s = np.asarray(skip, dtype=np.float64)
+        y = y + s
+        mag = mag + np.abs(s)
+    err = (K + 4) * V * mag + amb
+    bound = err + U * np.abs(y) + TINY16                                   # rule 4: the stored fp16 output
+    return y, bound, Fp8Info(int(np.count_nonzero(step)), int(step.size))
+
+
 def features(W: Weights, x):
     """last block output -> head conv + SiLU + mean over HW: ``extract``'s return value, (N, F) fp32."""
     x = _t(x)
@@ -265,17 +412,19 @@ def features(W: Weights, x):
 
 class Stage(NamedTuple):
     name: str          # the tensor it produces
-    kind: str          # stem | expand | dw | fused_dw | stem_dw | b1_fused | gate | out | features
+    kind: str          # stem | expand | dw | fused_dw | stem_dw | b1_fused | gate | out | out_fp8 | features
     block: int         # -1 for stem / features
     inputs: Tuple[str, ...]
 
 
-def plan(arch, have) -> List[Stage]:
+def plan(arch, have, fp8_blocks=()) -> List[Stage]:
     """The stage list of a schedule that keeps the tensors ``have``.  ``b{i}.expand``, ``stem`` and ``b0.out`` decide between
-    the fused and unfused forms; any other absent tensor is an error."""
+    the fused and unfused forms; any other absent tensor is an error.  The project convs of ``fp8_blocks`` run on e4m3
+    operands: kind ``out_fp8``."""
     from mermaid_classifier_amd.weights import get_arch
     A = get_arch(arch)
     have = set(have)
+    fp8 = set(fp8_blocks)
     st: List[Stage] = []
     if "stem" in have:
         st.append(Stage("stem", "stem", -1, ("patches",)))
@@ -302,7 +451,7 @@ def plan(arch, have) -> List[Stage]:
             ins = (f"b{i}.dw", f"b{i}.gate") + ((x_in,) if s == 1 and cin == cout else ())
             if len(ins) == 3 and x_in not in have:
                 raise KeyError(f"{x_in} is not kept")
-            st.append(Stage(f"b{i}.out", "out", i, ins))
+            st.append(Stage(f"b{i}.out", "out_fp8" if i in fp8 else "out", i, ins))
         elif not (i == 0 and A.name == "b0"):
             raise KeyError(f"b{i}.out is not kept")
     st.append(Stage("features", "features", -1, (f"b{len(A.blocks) - 1}.out",)))
@@ -328,9 +477,15 @@ def tensor_shape(arch, name: str, n: int) -> Tuple[int, ...]:
     raise KeyError(name)
 
 
-def run_stage(W: Weights, st: Stage, get: Callable[[str], np.ndarray]):
-    """(ref, bound) of one stage on the inputs ``get(name)`` hands out (``"patches"``: the uint8 patches)."""
+def run_stage(W: Weights, st: Stage, get: Callable[[str], np.ndarray], info: Optional[dict] = None):
+    """(ref, bound) of one stage on the inputs ``get(name)`` hands out (``"patches"``: the uint8 patches).  An ``out_fp8`` stage
+    leaves its ``Fp8Info`` in ``info[st.name]``."""
     a = [get(n) for n in st.inputs]
+    if st.kind == "out_fp8":
+        ref, bound, amb = out_fp8(W, st.block, a[0], a[1], a[2] if len(a) == 3 else None)
+        if info is not None:
+            info[st.name] = amb
+        return ref, bound
     if st.kind == "stem":
         return stem(W, a[0])
     if st.kind == "stem_dw":

@@ -2,7 +2,8 @@
 from the device, against the float64 stage reference of ``oracle/local_ref.py``, element by element: |got - ref| <= 2 x the
 bound derived from the error model stated at the top of that module.  No RMS, no percentile, no excluded element; the factor
 2 is the only margin over the derived worst case.  ``tests/test_gpu_layers.py`` checks what this cannot: the error
-accumulated through the chain.  fp16 only (fp8 and the product-only routes per-tensor mode does not run are out of scope).
+accumulated through the chain.  fp16 only: the fp8 project convs have the same check in ``tests/test_gpu_local_fp8.py``; the
+product-only routes per-tensor mode does not run are out of scope.
 
 Measured max |got - ref| / bound per schedule and stage: ``profiles/local_parity.txt``."""
 
