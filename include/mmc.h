@@ -655,6 +655,54 @@ int mmc_head_cover_set(mmc_head* h, mmc_featureset* fs, int64_t first, int64_t n
                        int64_t n_groups, const double* train_prior, double strength, int iters, int64_t* count, int64_t* soft_q32,
                        int64_t* unusable, double* prior, int k, int32_t* idx, float* scores, unsigned flags, void* hip_stream);
 
+/* ---- feature transforms: moments, scatter, centre-and-project on a resident set -----------------------------------------------
+ * Extends: the reference trains its MLP on the raw pooled activations (mermaid_classifier/pyspacer/trainer.py:118-145);
+ *   docs/research/hidden-layer-experiments.md section 5 closes on "the next round of work should target loss formulation or feature
+ *   representation rather than head architecture".  mmc_trainer_set_loss is the first half; these entries are what the second needs
+ *   from the device: a fitted LINEAR transform of the features -- per-feature standardisation, PCA reduction, PCA whitening, on total
+ *   or pooled within-class scatter -- fitted on one resident set and applied into another.  The eigen-decomposition of the dim x dim
+ *   scatter is host work, and at calibration time the transform is folded into the first Linear layer
+ *   (mermaid_classifier_amd/feature_transform.py), so heads, artifacts and predictors keep taking raw backbone features.
+ *   No reference counterpart: THIS TEXT IS THE DEFINITION.  Whether any of these transforms improves accuracy or cover on reef data
+ *   has not been measured.
+ * All three read rows [first, first + n) of a set in place (n <= 2^31 - 1), on `hip_stream`, and synchronise it before returning (their
+ *   device scratch is allocated per call and freed).  Outputs are host memory with MMC_OUT_HOST in flags, else memory of the set's
+ *   device; centres / centre / T are host memory with MMC_IN_HOST, else on the set's device.  A rejected call (MMC_ERR_ARG) or a
+ *   failed allocation (MMC_ERR_NOMEM) writes nothing.  n = 0 is MMC_OK: zeros (moments, scatter), nothing appended (transform).
+ *   K = the set's class count, dim its width.
+ * Determinism: no float atomics.  The result bits are a function of the rows' values and labels, first, n and dim -- never of the
+ *   device, the CU count or the grid's dispatch order -- so a repeated call returns the same bits.
+ *
+ * mmc_featureset_moments: groups 0 .. K-1 are the classes, group K is every row of the range.
+ *   counts[c]           int64, c < K: the rows with label c.
+ *   mean[g*dim + j]     fp64: the sum of (double)x[j] over the group's rows, divided by the group's row count; 0 for an empty group.
+ *   m2[g*dim + j]       fp64: the sum over the group's rows of d*d, d = (double)x[j] - mean[g*dim + j] (the fp64 mean above, so slot K
+ *                       is about the global mean and a class slot about its own class mean); 0 for an empty group.
+ *   Sum order: a group's rows in ascending order are cut into slabs of 256; a slab is summed in row order (m2 by fma(d, d, acc)), a
+ *   group's slabs are added in ascending order.
+ * mmc_featureset_scatter: scatter[j*dim + k] (dim x dim fp64, symmetric bit for bit)
+ *     = sum over the rows of xc[j] * xc[k],   xc = fl32(x - c): the fp32 difference, ONE rounding,
+ *   with c = centres[0 .. dim) when by_label = 0 (total scatter about one centre) and c = centres[y*dim .. (y+1)*dim), y the row's label,
+ *   when by_label = 1 (centres is K x dim: pooled within-class scatter).  Rows are cut into chunks of MMC_SCATTER_CHUNK_ROWS consecutive
+ *   rows; inside a chunk an element is one fp32 fmaf chain in row order (the exact-f32 MFMA), the chunk's fp32 value is then added to an
+ *   fp64 accumulator.  The chunks are split over S = min(MMC_SCATTER_MAX_SPLITS, max(1, 512 / P), chunks) contiguous ranges, P = T (T + 1) / 2
+ *   and T = ceil(dim / 128) -- a function of n and dim alone --, range s holding chunks [s * chunks / S, (s + 1) * chunks / S); a range's
+ *   chunks are added in order and the S range sums are added in ascending order.  Element (j, k) is computed once for j <= k and copied
+ *   to (k, j).  dim > MMC_SCATTER_MAX_DIM is MMC_ERR_ARG.  Scratch: S * P * 128 KiB (70 MiB at dim = 1280).
+ * mmc_featureset_transform: appends n rows of width m to dst (dst's width must be m, its class count and device src's; dst = src is
+ *   MMC_ERR_ARG): row i is  y[k] = sum over j of fl32(x[j] - centre[j]) * T[k*dim + j],  one fp32 fmaf chain over j ascending from 0
+ *   (the rounding of every other fp32 GEMM here); T is m x dim.  The labels are copied with the rows.  dst grows as in
+ *   mmc_featureset_append, and its row count moves last: a failed call leaves dst's rows and count as they were. */
+#define MMC_SCATTER_CHUNK_ROWS 256
+#define MMC_SCATTER_MAX_SPLITS 16
+#define MMC_SCATTER_MAX_DIM 2048
+int mmc_featureset_moments(mmc_featureset* fs, int64_t first, int64_t n, int64_t* counts /* K */, double* mean /* (K+1) x dim */,
+                           double* m2 /* (K+1) x dim */, unsigned flags, void* hip_stream);
+int mmc_featureset_scatter(mmc_featureset* fs, int64_t first, int64_t n, const float* centres /* dim, or K x dim with by_label */,
+                           int by_label, double* scatter /* dim x dim */, unsigned flags, void* hip_stream);
+int mmc_featureset_transform(mmc_featureset* src, int64_t first, int64_t n, const float* centre /* dim */, const float* T /* m x dim */,
+                             int m, mmc_featureset* dst, unsigned flags, void* hip_stream);
+
 /* ---- multi-GPU: the gather of the sharded path --------------------------------------------------------------------
  * The path shards by patches (contiguous blocks of the row range per rank, weights replicated, no exchange during compute);
  * its one exchange step is the all-gather of the ranks' (n_r, 1280) feature blocks.  Replaces: nothing in the reference's

@@ -18,6 +18,7 @@ from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, ca
 from .taxonomy import TaxonomicScores  # noqa: F401
 from .ranking import RankedValidation, ranking_validate, similarity_levels  # noqa: F401
 from .cover import CoverEstimate, estimate_cover, prior_from_labels  # noqa: F401
+from .feature_transform import FeatureTransform  # noqa: F401
 
 __all__ = [
     "EfficientNetExtractor", "build_extractor_class", "resolve_device", "verify_device_numerics",
@@ -34,4 +35,5 @@ __all__ = [
     "ranking_validate", "RankedValidation", "similarity_levels",
     "category_bins", "TaxonomicScores",
     "estimate_cover", "CoverEstimate", "prior_from_labels",
+    "FeatureTransform",
 ]

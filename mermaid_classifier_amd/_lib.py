@@ -24,6 +24,7 @@ MMC_RANKED_MAX_K = 16   # include/mmc.h: selection rounds of mmc_head_evaluate_r
 MMC_TRAINER_GROUP_MAX = 16   # include/mmc.h: members of one mmc_trainer_group_partial_fit_set call
 MMC_VIEWS_MAX = 16   # include/mmc.h MMC_VIEWS_MAX: view codes 0..15, and at most 16 views per point
 MMC_COVER_MAX_ITERS, MMC_COVER_MAX_CELLS = 1000, 1 << 30   # include/mmc.h: cover estimation
+MMC_SCATTER_CHUNK_ROWS, MMC_SCATTER_MAX_SPLITS, MMC_SCATTER_MAX_DIM = 256, 16, 2048   # include/mmc.h: feature transforms
 
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
@@ -43,6 +44,7 @@ SYMBOLS = [
     "mmc_head_evaluate_categories", "mmc_head_evaluate_categories_set",
     "mmc_head_evaluate_ranked", "mmc_head_evaluate_ranked_set",
     "mmc_cover_proba", "mmc_head_cover", "mmc_head_cover_set",
+    "mmc_featureset_moments", "mmc_featureset_scatter", "mmc_featureset_transform",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -207,6 +209,12 @@ def _load() -> C.CDLL:
     lib.mmc_head_cover.argtypes = [vp, vp, i64, i32] + cover + [u32, vp]
     lib.mmc_head_cover_set.restype = i32
     lib.mmc_head_cover_set.argtypes = [vp, vp, i64, i64, i32] + cover + [u32, vp]
+    lib.mmc_featureset_moments.restype = i32
+    lib.mmc_featureset_moments.argtypes = [vp, i64, i64, vp, vp, vp, u32, vp]
+    lib.mmc_featureset_scatter.restype = i32
+    lib.mmc_featureset_scatter.argtypes = [vp, i64, i64, vp, i32, vp, u32, vp]
+    lib.mmc_featureset_transform.restype = i32
+    lib.mmc_featureset_transform.argtypes = [vp, i64, i64, vp, vp, i32, vp, u32, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

@@ -235,6 +235,18 @@ class CalibratedMLP:
         """The served form (``inference.Predictor``) without a round trip through files."""
         return Predictor(self._device_head(), self.classes_.tolist(), self.n_features_in_)
 
+    def folded(self, transform) -> "CalibratedMLP":
+        """This model, trained on ``transform``'s output, as a model of RAW features: ``transform.fold`` of the first Linear
+        layer (``feature_transform.FeatureTransform.fold``), the same ``a_`` / ``b_`` / ``classes_``, ``n_features_in_ ==
+        transform.dim``.  The classifier state is dropped -- its sklearn twin would take transformed features -- so ``to_sklearn``
+        raises on the result.  The transform is kept as ``transform_``."""
+        if transform.n_components != self.n_features_in_:
+            raise ValueError(f"the transform writes {transform.n_components} features, this model takes {self.n_features_in_}")
+        weights, biases = transform.fold(self.weights, self.biases)
+        out = CalibratedMLP(weights, biases, self.classes_, self.a_, self.b_, self.iterations_, device=self.device, clf_state=None)
+        out.transform_ = transform
+        return out
+
     def to_sklearn(self):
         """-> ``CalibratedClassifierCV(clf, cv="prefit")`` carrying ``_SigmoidCalibration`` objects with ``a_`` / ``b_``: the
         object the reference's ``_calibrate_in_batches`` returns (trainer.py:385-396).  ``clf`` is a ``TorchMLPClassifier``

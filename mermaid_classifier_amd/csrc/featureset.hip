@@ -23,8 +23,8 @@
         if (e_ != hipSuccess) return mmc_fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
 
-// room for `need` rows; the rows stored so far move on `st`
-static int featureset_reserve(mmc_featureset* fs, int64_t need, hipStream_t st)
+// room for `need` rows; the rows stored so far move on `st` (also features.hip's way to grow a set)
+int featureset_reserve(mmc_featureset* fs, int64_t need, hipStream_t st)
 {
     if (need <= fs->cap) return MMC_OK;
     const int64_t cap = fs->cap * 2 > need ? fs->cap * 2 : need;

@@ -18,6 +18,9 @@ struct mmc_featureset {
     std::vector<int32_t> y_host;      // host mirror of y[0..n): argument checks and per-mini-batch class-weight sums
 };
 
+// room for `need` rows in all (featureset.hip): both new buffers are allocated before anything is touched, the stored rows move on `st`
+int featureset_reserve(mmc_featureset* fs, int64_t need, hipStream_t st);
+
 // sets the thread-local message mmc_last_error() returns and hands back `code` (defined in mmc_api.cpp)
 int mmc_fail(int code, const char* fmt, ...);
 

@@ -34,7 +34,7 @@ from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tupl
 
 import numpy as np
 
-from . import _lib
+from . import _lib, feature_transform as _ft
 from .backbone import _current_stream_ptr, _device_index
 from .calibration import CalibratedMLP, calibrate, evaluate, evaluate_classes
 from .featureset import FeatureSet
@@ -176,7 +176,7 @@ def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[A
 
 def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Sequence[SweepConfig], nbr_epochs: int, *,
                 batch_size: int, early_stopping_patience: Optional[int] = None,
-                on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None, class_scores: bool = False
+                on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None, class_scores: bool = False, transform=None
                 ) -> List[Tuple[CalibratedMLP, Dict[str, Any], List[float]]]:
     """Train, early-stop and calibrate one head per configuration on three resident splits, all heads advancing in the same
     launches.  -> one ``(calibrated, info, ref_accs)`` per configuration, equal to
@@ -187,11 +187,26 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
     ``evaluate`` on ``ref`` and ``val`` per model, then each model's early-stopping decision; a stopped model drops out.  At the
     end ``calibrate`` per returned classifier.  ``on_epoch_end`` gets ``epoch_loop``'s dict plus ``"config"``.
     ``class_scores=True`` scores ``val`` through ``calibration.evaluate_classes``: the dict gains ``val_balanced_accuracy`` and
-    ``val_f1_macro`` per model and epoch, and nothing returned changes."""
+    ``val_f1_macro`` per model and epoch, and nothing returned changes.
+
+    ``transform`` as in ``train_classifier``: one transform (given, or fitted on ``train``) for the whole sweep; the splits are
+    transformed once, every head trains on the transformed sets, and every model returned is folded."""
     configs = list(configs)
     if not configs:
         raise ValueError("configs is empty")
     _check_splits(train, ref, val, batch_size)
+    if transform is not None:
+        ft = _ft.resolve(transform, train)
+        sets = []
+        try:
+            for fs in (train, ref, val):
+                sets.append(ft.apply(fs))
+            results = train_sweep(*sets, configs, nbr_epochs, batch_size=batch_size, early_stopping_patience=early_stopping_patience,
+                                  on_epoch_end=on_epoch_end, class_scores=class_scores)
+        finally:
+            for fs in sets:
+                fs.close()
+        return [(cal.folded(ft), info, accs) for cal, info, accs in results]
     classes = ref.classes.tolist()
     clfs = [cfg.classifier(ref.device) for cfg in configs]
     batches = [cfg.batches if cfg.batches is not None else _contiguous_batches(len(train), int(batch_size)) for cfg in configs]

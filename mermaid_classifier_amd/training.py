@@ -17,6 +17,7 @@ from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tupl
 
 import numpy as np
 
+from . import feature_transform as _ft
 from .calibration import CalibratedMLP, calibrate, evaluate, evaluate_classes
 from .featureset import FeatureSet
 from .torch_classifier import TorchMLPClassifier
@@ -146,7 +147,7 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
                      class_weight: Optional[dict] = None, early_stopping_patience: Optional[int] = None,
                      on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None,
                      batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None,
-                     clf: Optional[TorchMLPClassifier] = None, class_scores: bool = False
+                     clf: Optional[TorchMLPClassifier] = None, class_scores: bool = False, transform=None
                      ) -> Tuple[CalibratedMLP, Dict[str, Any], List[float]]:
     """Train, early-stop and calibrate the MLP head on three resident splits.  -> ``(calibrated, info, ref_accs)``:
     the ``CalibratedMLP`` of the returned classifier on ``ref``, ``epoch_loop``'s ``info``, and the ref accuracy after every
@@ -163,8 +164,26 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
     the classifier shuffles as ``partial_fit`` does.
 
     ``class_scores=True`` scores ``val`` through ``calibration.evaluate_classes`` instead of ``evaluate``: the ``on_epoch_end``
-    dict gains ``val_balanced_accuracy`` and ``val_f1_macro`` (see ``epoch_loop``); nothing returned changes."""
+    dict gains ``val_balanced_accuracy`` and ``val_f1_macro`` (see ``epoch_loop``); nothing returned changes.
+
+    ``transform``: a fitted ``FeatureTransform`` or a dict of ``FeatureTransform.fit`` keyword arguments (fitted on ``train``).  The
+    three splits are transformed on the device into resident sets of their own, the head is trained and calibrated on those, they
+    are freed, and the model returned is ``CalibratedMLP.folded(transform)``: it takes RAW features (``n_features_in_ ==
+    train.dim``) and carries the transform as ``transform_``.  ``None`` is the path described above, call for call."""
     _check_splits(train, ref, val, batch_size)
+    if transform is not None:
+        ft = _ft.resolve(transform, train)
+        sets = []
+        try:
+            for fs in (train, ref, val):
+                sets.append(ft.apply(fs))
+            cal, info, accs = train_classifier(*sets, nbr_epochs, batch_size=batch_size, class_weight=class_weight,
+                                               early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end,
+                                               batches=batches, clf=clf, class_scores=class_scores)
+        finally:
+            for fs in sets:
+                fs.close()
+        return cal.folded(ft), info, accs
     if clf is None:
         clf = TorchMLPClassifier(hidden_layer_sizes=(500, 300, 100), learning_rate_init=1e-4, class_weight=class_weight,
                                  random_state=0, device=ref.device)
@@ -196,7 +215,8 @@ def train_and_validate(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_
     (``Validation.val_results``) and a ``TrainClassifierReturnMsg`` with ``acc`` (the validation accuracy), ``pc_accs`` (the
     accuracy of every model in ``pc_models`` -- ``Predictor`` or ``CalibratedMLP`` -- on ``val``), ``ref_accs`` (one entry per
     epoch run) and ``runtime`` in seconds.  pyspacer's message classes are used when importable, ``spacer_shim``'s otherwise.
-    The validation rows are scored where they lie (``validation.validate``)."""
+    The validation rows are scored where they lie (``validation.validate``) -- with ``transform=`` in ``kwargs`` too: the folded
+    model takes the raw ``val`` rows."""
     t0 = time.time()
     calibrated, _info, ref_accs = train_classifier(train, ref, val, nbr_epochs, batch_size=batch_size, **kwargs)
     scored = validate(calibrated, val)
