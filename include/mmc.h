@@ -703,6 +703,54 @@ int mmc_featureset_scatter(mmc_featureset* fs, int64_t first, int64_t n, const f
 int mmc_featureset_transform(mmc_featureset* src, int64_t first, int64_t n, const float* centre /* dim */, const float* T /* m x dim */,
                              int m, mmc_featureset* dst, unsigned flags, void* hip_stream);
 
+/* ---- nearest neighbours: fused exact-f32 top-k between resident sets -----------------------------------------------------------
+ * Extends: nothing in the reference.  Three questions its data raises rest on "which rows are close to which": point labels are noisy
+ *   (a row whose neighbours from OTHER images mostly carry another label is the first candidate for review);
+ *   docs/research/balancing-experiments.md closes on a per-source accuracy floor that "may motivate a per-source feature-extraction
+ *   review", and a kNN classifier on the raw features is the standard probe for that; near-duplicate rows between train and validation
+ *   splits inflate every validation number.  The host algebra is mermaid_classifier_amd/neighbors.py.
+ *   No reference counterpart: THIS TEXT IS THE DEFINITION.  No gain on reef data has been measured.
+ * For every query row i of rows [q_first, q_first + nq) of `query`: the k best eligible rows of rows [b_first, b_first + nb) of `base`
+ *   (the same set is allowed, overlapping ranges too).  Equal dim, same device; the nq x nb score matrix is never stored.
+ * Score of query row q and base row b, in fp32; larger is better for all three metrics:
+ *   d        one fmaf chain over the dim columns in ascending order, from +0 (the exact-f32 MFMA: the rounding of every other fp32
+ *            GEMM here)
+ *   DOT      d
+ *   COSINE   (d * rq) * rb       r = fl32(1 / sqrt(ss)), ss = the fp64 sum of (double)x * x over the row's columns in ascending order
+ *                                (fma chain); r = 0 when ss is not > 0 (a zero row)
+ *   L2       -fmaf(-2, d, sq + sb)   s = fl32(ss): minus the squared distance
+ *   A score of -0 is keyed and returned as +0.
+ * Order: score descending, equal scores by ascending base row; NaN below every number (returned as 0x7FC00000).  The device orders
+ *   64-bit keys (w << 32) | (0xFFFFFFFF - j), j the row relative to b_first and w the score word: 0 = no entry, 1 = NaN, else the fp32
+ *   bits with the sign bit set for a score >= 0 and every bit inverted for a score < 0 (-inf -> 0x007FFFFF, +inf -> 0xFF800000).  The
+ *   keys of a query are distinct, the k largest of a set under a total order are unique: the output bits depend on the rows, dim, k and
+ *   metric only -- never on tiles, splits, chunks, the grid or the device.  No float atomics, no cross-workgroup flags.
+ * Eligibility, applied BEFORE selection: base row b_first + j is out for query i when both group arrays are given and
+ *   q_group[i] == b_group[j] (e.g. image ids: points of one image overlap), and, under MMC_KNN_EXCLUDE_SELF (query == base only), when
+ *   it is row q_first + i itself.  Both group arrays or neither; they are host memory with MMC_IN_HOST in flags, else device memory.
+ * Outputs (nq x k, host memory with MMC_OUT_HOST, else on the sets' device): index relative to b_first, best first; score; label
+ *   (may be NULL) = the base row's stored class index.  Where fewer than k rows are eligible the tail holds index -1, score -inf,
+ *   label -1; nb = 0 fills everything with that.  nq = 0 is MMC_OK and writes nothing.
+ * MMC_ERR_ARG, nothing written: ranges outside their set or longer than 2^31 - 1, k outside [1, MMC_KNN_MAX_K], unequal dim or device,
+ *   an unknown metric or flag, EXCLUDE_SELF on two different sets, one group array without the other, NULL index / score.
+ * Work: one workgroup owns a tile of MMC_KNN_TILE_ROWS query rows and one contiguous range of base tiles; the base tiles T_b =
+ *   ceil(nb / 128) are split over S = min(MMC_KNN_MAX_SPLITS, T_b, max(1, 1024 / T_q)) ranges, T_q = ceil(min(nq, MMC_KNN_CHUNK_ROWS) / 128)
+ *   -- a function of nq and nb alone --, range s holding tiles [s * T_b / S, (s + 1) * T_b / S); a second launch merges the S lists per
+ *   query.  Queries are walked in chunks of MMC_KNN_CHUNK_ROWS, so the per-call scratch (allocated and freed inside the call) is at most
+ *   36 MiB + 12 bytes per base row, whatever nq.  Runs on `hip_stream` and synchronises it before returning. */
+#define MMC_KNN_MAX_K 32
+#define MMC_KNN_DOT 0
+#define MMC_KNN_COSINE 1
+#define MMC_KNN_L2 2
+#define MMC_KNN_EXCLUDE_SELF 4u  /* flag; only legal when query == base */
+#define MMC_KNN_TILE_ROWS 128
+#define MMC_KNN_CHUNK_ROWS 8192
+#define MMC_KNN_MAX_SPLITS 16
+int mmc_featureset_knn(mmc_featureset* query, int64_t q_first, int64_t nq, mmc_featureset* base, int64_t b_first, int64_t nb, int k,
+                       int metric, const int32_t* q_group /* nq or NULL */, const int32_t* b_group /* nb or NULL */,
+                       int32_t* index /* nq x k */, float* score /* nq x k */, int32_t* label /* nq x k or NULL */, unsigned flags,
+                       void* hip_stream);
+
 /* ---- multi-GPU: the gather of the sharded path --------------------------------------------------------------------
  * The path shards by patches (contiguous blocks of the row range per rank, weights replicated, no exchange during compute);
  * its one exchange step is the all-gather of the ranks' (n_r, 1280) feature blocks.  Replaces: nothing in the reference's

@@ -26,6 +26,9 @@ MMC_VIEWS_MAX = 16   # include/mmc.h MMC_VIEWS_MAX: view codes 0..15, and at mos
 MMC_COVER_MAX_ITERS, MMC_COVER_MAX_CELLS = 1000, 1 << 30   # include/mmc.h: cover estimation
 MMC_SCATTER_CHUNK_ROWS, MMC_SCATTER_MAX_SPLITS, MMC_SCATTER_MAX_DIM = 256, 16, 2048   # include/mmc.h: feature transforms
 
+MMC_KNN_MAX_K, MMC_KNN_DOT, MMC_KNN_COSINE, MMC_KNN_L2, MMC_KNN_EXCLUDE_SELF = 32, 0, 1, 2, 4   # include/mmc.h: nearest neighbours
+MMC_KNN_TILE_ROWS, MMC_KNN_CHUNK_ROWS, MMC_KNN_MAX_SPLITS = 128, 8192, 16
+
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
     "mmc_last_error", "mmc_version", "mmc_device_count",
@@ -45,6 +48,7 @@ SYMBOLS = [
     "mmc_head_evaluate_ranked", "mmc_head_evaluate_ranked_set",
     "mmc_cover_proba", "mmc_head_cover", "mmc_head_cover_set",
     "mmc_featureset_moments", "mmc_featureset_scatter", "mmc_featureset_transform",
+    "mmc_featureset_knn",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -215,6 +219,8 @@ def _load() -> C.CDLL:
     lib.mmc_featureset_scatter.argtypes = [vp, i64, i64, vp, i32, vp, u32, vp]
     lib.mmc_featureset_transform.restype = i32
     lib.mmc_featureset_transform.argtypes = [vp, i64, i64, vp, vp, i32, vp, u32, vp]
+    lib.mmc_featureset_knn.restype = i32
+    lib.mmc_featureset_knn.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, u32, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32
