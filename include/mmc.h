@@ -751,6 +751,67 @@ int mmc_featureset_knn(mmc_featureset* query, int64_t q_first, int64_t nq, mmc_f
                        int32_t* index /* nq x k */, float* score /* nq x k */, int32_t* label /* nq x k or NULL */, unsigned flags,
                        void* hip_stream);
 
+/* ---- logit calibration: temperature, bias and vector scaling of the trained head's logits -----------------------------------------
+ * Extends: the reference's balancing study closes on "Platt-scaling parameters or temperature scaling on top of it should be
+ *   investigated" (docs/research/balancing-experiments.md:142).  mmc_trainer_set_loss's logit_prior is the training-time half of that
+ *   line; this is the test-time half.  The Platt stage above is linear in the softmax probability, not in the logit, and cannot undo a
+ *   plain over-confident softmax; the remedies below are affine in the logits z and fold exactly into the last Linear layer
+ *   (mermaid_classifier_amd/logit_scaling.py: LogitScaling.fold), so every consumer of a head keeps working, the Platt stage on top.
+ *   No reference counterpart: THIS TEXT IS THE DEFINITION.  No gain on reef data has been measured.
+ * Inputs: N stored rows of raw logits z_n (fp32, as mmc_trainer_logits gives them) with labels y_n; parameters a, c (K doubles each).
+ *   All arithmetic is float64 on the fp32 inputs.
+ *     u_nk  = a_k z_nk + c_k
+ *     lse_n = max_k u_nk + log sum_k exp(u_nk - max_k u_nk)        p_nk = exp(u_nk - lse_n)
+ *     F(a,c) = sum_n (lse_n - u_n,y_n)  +  (l2 N / 2) (|a - 1|^2 + |c|^2)              l2 >= 0
+ *   With theta = (a, c) in R^2K and r = p - onehot(y), the gradient of the data term is g_a = sum_n z_n (.) r_n, g_c = sum_n r_n; with
+ *   v_n = [z_n (.) p_n ; p_n] its Hessian is H = D - sum_n v_n v_n^T, D diagonal plus the a_k-c_k coupling: D_aa[k] = sum z^2 p,
+ *   D_cc[k] = sum p, D_ac[k] = sum z p.
+ * Modes pick a subspace of theta:
+ *   TEMPERATURE  a = s 1, c = 0: one parameter s = 1 / T; gradient sum_k g_a[k], Hessian sum_kl H_aa[k,l]
+ *   BIAS         a = 1, c free               VECTOR   both free
+ *   F is convex in every mode.  Two cases have no finite minimiser:
+ *   absent classes   a class with no stored row has dF/dc_k = sum_n p_nk > 0 everywhere.  In BIAS and VECTOR such classes are frozen
+ *                    at the identity (a_k = 1, c_k = 0), left out of the active parameters and reported in `frozen`, whatever l2 is.
+ *   separable rows with l2 = 0   the fit ends at the tolerance or at the trial cap and returns the last accepted, finite iterate with
+ *                    converged = 0 / 1; never NaN or inf.
+ * mmc_logitcal_stats: one pass over the store (csrc/logit_scaling.hip).  Rows are cut into blocks of MMC_LOGITCAL_BLOCK_ROWS in
+ *   stored order; a block's sums run in a fixed order, the blocks' partials are folded in block order; no float atomics.  The Hessian
+ *   is accumulated in fp64 (v_mfma_f64_16x16x4_f64 over 16 x 16 tiles of the upper triangle) and returned symmetric bit for bit.  The
+ *   row maximum is subtracted before exp: |a_k z_nk| in the thousands gives finite results.  The bits of every output depend on the
+ *   stored logits, labels, K, a, c and N only -- not on how the rows were split over add_* calls, on the device or on the environment;
+ *   hess = NULL gives the nll_sum / grad bits of the call with a Hessian.
+ * mmc_logitcal_fit: damped Newton on the active parameters from the identity (csrc/logit_newton.h, host, float64).  d solves
+ *   (H + lambda tau I) d = -g by Cholesky, tau = trace(H) / dim, H and g with the ridge: Levenberg damping with a multiple of the
+ *   IDENTITY, which keeps every step orthogonal to the null direction c -> c + t 1 (nothing frozen), so c stays zero-mean from c = 0.
+ *   lambda starts at 1e-3 (x 8 while the factorisation fails).  A trial point theta + d is accepted iff F there is finite and <= F;
+ *   then lambda <- max(lambda / 8, 1e-12), else lambda <- 8 lambda.  Stops when max|g_active| / N <= tol (converged = 1) or after
+ *   max_trials trial points (converged = 0).  Trial points are evaluated without the Hessian, accepted points once more with it.
+ *   Outputs: a, cc (K each), frozen (K or NULL), the MEAN data term (sum / N) at the identity and at the returned point, the number
+ *   of trial points.
+ * Every call synchronises `hip_stream` before it returns.  MMC_ERR_ARG, with nothing launched: a NULL handle or output, K outside
+ *   [2, MMC_LOGITCAL_MAX_CLASSES], a mode outside the three, l2 < 0, tol <= 0, max_trials outside [1, 1000], non-finite a / cc /
+ *   logits, a label outside [0, K), a trainer / set / device mismatch, fit or stats with no rows.  mmc_logitcal_create writes
+ *   *out = NULL first on every error path. */
+#define MMC_LOGITCAL_MAX_CLASSES 128
+#define MMC_LOGITCAL_BLOCK_ROWS 1024
+#define MMC_LOGITCAL_TEMPERATURE 0
+#define MMC_LOGITCAL_BIAS 1
+#define MMC_LOGITCAL_VECTOR 2
+typedef struct mmc_logitcal mmc_logitcal;
+int mmc_logitcal_create(int K, int device, mmc_logitcal** out);
+void mmc_logitcal_destroy(mmc_logitcal* c);
+int64_t mmc_logitcal_rows(const mmc_logitcal* c);
+/* raw logits of t's current parameters; they stay on the device (fp32) */
+int mmc_logitcal_add_features(mmc_logitcal* c, mmc_trainer* t, const float* X, const int32_t* y, int64_t n, void* hip_stream);
+int mmc_logitcal_add_set(mmc_logitcal* c, mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n, void* hip_stream);
+/* caller's logits (host, n x K fp32, finite) */
+int mmc_logitcal_add_logits(mmc_logitcal* c, const float* logits, const int32_t* y, int64_t n, void* hip_stream);
+/* data term, gradient (2K: a then c), Hessian (2K x 2K row-major, or NULL), per-class row counts (K, or NULL) at (a, cc) */
+int mmc_logitcal_stats(mmc_logitcal* c, const double* a, const double* cc, double* nll_sum, double* grad, double* hess,
+                       int64_t* counts, void* hip_stream);
+int mmc_logitcal_fit(mmc_logitcal* c, int mode, double l2, double tol, int max_trials, double* a, double* cc, uint8_t* frozen /* K or NULL */,
+                     double* nll_before, double* nll_after, int32_t* trials, int32_t* converged, void* hip_stream);
+
 /* ---- multi-GPU: the gather of the sharded path --------------------------------------------------------------------
  * The path shards by patches (contiguous blocks of the row range per rank, weights replicated, no exchange during compute);
  * its one exchange step is the all-gather of the ranks' (n_r, 1280) feature blocks.  Replaces: nothing in the reference's

@@ -19,6 +19,7 @@ from .taxonomy import TaxonomicScores  # noqa: F401
 from .ranking import RankedValidation, ranking_validate, similarity_levels  # noqa: F401
 from .cover import CoverEstimate, estimate_cover, prior_from_labels  # noqa: F401
 from .feature_transform import FeatureTransform  # noqa: F401
+from .logit_scaling import LogitScaling, fit_logit_scaling  # noqa: F401
 from .neighbors import KnnValidation, Neighbors, audit_labels, knn_validate, near_duplicates, nearest  # noqa: F401
 
 __all__ = [
@@ -37,5 +38,6 @@ __all__ = [
     "category_bins", "TaxonomicScores",
     "estimate_cover", "CoverEstimate", "prior_from_labels",
     "FeatureTransform",
+    "LogitScaling", "fit_logit_scaling",
     "nearest", "Neighbors", "knn_validate", "KnnValidation", "audit_labels", "near_duplicates",
 ]

@@ -28,6 +28,8 @@ MMC_SCATTER_CHUNK_ROWS, MMC_SCATTER_MAX_SPLITS, MMC_SCATTER_MAX_DIM = 256, 16, 2
 
 MMC_KNN_MAX_K, MMC_KNN_DOT, MMC_KNN_COSINE, MMC_KNN_L2, MMC_KNN_EXCLUDE_SELF = 32, 0, 1, 2, 4   # include/mmc.h: nearest neighbours
 MMC_KNN_TILE_ROWS, MMC_KNN_CHUNK_ROWS, MMC_KNN_MAX_SPLITS = 128, 8192, 16
+MMC_LOGITCAL_MAX_CLASSES, MMC_LOGITCAL_BLOCK_ROWS = 128, 1024   # include/mmc.h: logit calibration
+MMC_LOGITCAL_TEMPERATURE, MMC_LOGITCAL_BIAS, MMC_LOGITCAL_VECTOR = 0, 1, 2
 
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
@@ -49,6 +51,8 @@ SYMBOLS = [
     "mmc_cover_proba", "mmc_head_cover", "mmc_head_cover_set",
     "mmc_featureset_moments", "mmc_featureset_scatter", "mmc_featureset_transform",
     "mmc_featureset_knn",
+    "mmc_logitcal_create", "mmc_logitcal_destroy", "mmc_logitcal_rows", "mmc_logitcal_add_features", "mmc_logitcal_add_set",
+    "mmc_logitcal_add_logits", "mmc_logitcal_stats", "mmc_logitcal_fit",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -221,6 +225,22 @@ def _load() -> C.CDLL:
     lib.mmc_featureset_transform.argtypes = [vp, i64, i64, vp, vp, i32, vp, u32, vp]
     lib.mmc_featureset_knn.restype = i32
     lib.mmc_featureset_knn.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, u32, vp]
+    lib.mmc_logitcal_create.restype = i32
+    lib.mmc_logitcal_create.argtypes = [i32, i32, C.POINTER(vp)]
+    lib.mmc_logitcal_destroy.restype = None
+    lib.mmc_logitcal_destroy.argtypes = [vp]
+    lib.mmc_logitcal_rows.restype = i64
+    lib.mmc_logitcal_rows.argtypes = [vp]
+    lib.mmc_logitcal_add_features.restype = i32
+    lib.mmc_logitcal_add_features.argtypes = [vp, vp, vp, vp, i64, vp]
+    lib.mmc_logitcal_add_set.restype = i32
+    lib.mmc_logitcal_add_set.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.mmc_logitcal_add_logits.restype = i32
+    lib.mmc_logitcal_add_logits.argtypes = [vp, vp, vp, i64, vp]
+    lib.mmc_logitcal_stats.restype = i32
+    lib.mmc_logitcal_stats.argtypes = [vp, vp, vp, C.POINTER(f64), vp, vp, vp, vp]
+    lib.mmc_logitcal_fit.restype = i32
+    lib.mmc_logitcal_fit.argtypes = [vp, i32, f64, f64, i32, vp, vp, vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(i32), C.POINTER(i32), vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

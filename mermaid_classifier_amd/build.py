@@ -2,7 +2,7 @@
 
     python -m mermaid_classifier_amd.build [--force]
 
-One object per translation unit (the kernels are five .hip files by layer group, plus the trainer, the calibrator, the feature set, the feature transforms, the nearest-neighbour search, the grouped metrics, cover estimation, and the two host units of the C ABI:
+One object per translation unit (the kernels are five .hip files by layer group, plus the trainer, the calibrator, the feature set, the feature transforms, the nearest-neighbour search, logit calibration, the grouped metrics, cover estimation, and the two host units of the C ABI:
 mmc_api.cpp with the backbone schedule and mmc_head.cpp with the calibrated head),
 compiled in parallel and only when the source or one of its headers is newer than the object; then one link.  Objects live in
 csrc/_obj/ (git-ignored and gpurun-ignored: only the linked library travels to the GPU box).
@@ -34,6 +34,7 @@ SOURCES = {
     "featureset.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "features.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "neighbors.hip": ["../../include/mmc.h", "trainer_internal.h"],
+    "logit_scaling.hip": ["../../include/mmc.h", "trainer_internal.h", "logit_newton.h"],
     "metrics.hip": ["kernels.h"],
     "cover.hip": ["kernels.h", "topk_key.h"],
     "mmc_api.cpp": ["kernels.h", "api_internal.h", "backbone_pack.h", "../../include/mmc.h"],

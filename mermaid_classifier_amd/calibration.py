@@ -204,6 +204,7 @@ class CalibratedMLP:
         if len(self.classes_) < 3 or self.a_.shape != (len(self.classes_),) or self.b_.shape != self.a_.shape:
             raise ValueError(f"need K >= 3 classes and K calibrators; got {len(self.classes_)} classes, a {self.a_.shape}, b {self.b_.shape}")
         self._head = None
+        self.logit_scaling_ = None   # the LogitScaling folded into the last layer, when calibrate() was given one
 
     @property
     def n_features_in_(self) -> int:
@@ -245,6 +246,7 @@ class CalibratedMLP:
         weights, biases = transform.fold(self.weights, self.biases)
         out = CalibratedMLP(weights, biases, self.classes_, self.a_, self.b_, self.iterations_, device=self.device, clf_state=None)
         out.transform_ = transform
+        out.logit_scaling_ = self.logit_scaling_
         return out
 
     def to_sklearn(self):
@@ -271,16 +273,27 @@ class CalibratedMLP:
         return wrapper
 
 
-def calibrate(clf, data) -> CalibratedMLP:
+def calibrate(clf, data, logit_scaling=None) -> CalibratedMLP:
     """Platt calibration of ``clf`` on the ref split ``data`` (the reference's ``_calibrate_in_batches``): every batch goes
     through the classifier's current parameters into the device-resident probability store, then all K sigmoids are fitted
-    at once.  Raises ``RuntimeError`` for an unfitted classifier and ``ValueError`` for fewer than 3 classes."""
+    at once.  Raises ``RuntimeError`` for an unfitted classifier and ``ValueError`` for fewer than 3 classes.
+
+    ``logit_scaling``: a fitted ``logit_scaling.LogitScaling``, or a kind string (``"temperature"`` / ``"bias"`` / ``"vector"``) that is
+    fitted on ``data`` first (``data`` is then read twice: not a one-shot generator).  It is folded into the last layer before the
+    Platt fit, which runs on the folded classifier's probabilities; the returned model holds the folded snapshot and the scaling as
+    ``logit_scaling_``.  ``None`` is the path above, call for call."""
     _require_fitted(clf)
     K = len(clf.classes_)
     if K < 3:
         raise ValueError(f"calibrate: {K} classes; one Platt sigmoid per class is defined here for K >= 3 only")
     if isinstance(data, FeatureSet):
         data._check_against(clf)
+    if logit_scaling is not None:
+        from . import logit_scaling as _ls
+        scaling = _ls.resolve(logit_scaling, clf, data)
+        out = calibrate(scaling.fold_classifier(clf), data)
+        out.logit_scaling_ = scaling
+        return out
     weights, biases = clf.parameters()   # the snapshot (read before the forward passes: the same parameters)
     cal = _Calibrator(K, clf.device)
     try:

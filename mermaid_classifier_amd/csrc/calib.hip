@@ -401,7 +401,7 @@ struct mmc_calibrator {
         if (e_ != hipSuccess) return mmc_fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
 
-static int check_labels(const int32_t* y, int64_t n, int K)
+int check_labels(const int32_t* y, int64_t n, int K)
 {
     for (int64_t i = 0; i < n; ++i)
         if (y[i] < 0 || y[i] >= K) return mmc_fail(MMC_ERR_ARG, "label index y[%lld] = %d outside [0, %d)", (long long)i, y[i], K);
@@ -499,7 +499,7 @@ extern "C" int mmc_calibrator_add_features(mmc_calibrator* c, mmc_trainer* t, co
     return MMC_OK;
 }
 
-static int check_set_range(const mmc_featureset* fs, int64_t first, int64_t n)
+int check_set_range(const mmc_featureset* fs, int64_t first, int64_t n)
 {
     if (first < 0 || n < 0 || first > fs->n || n > fs->n - first)
         return mmc_fail(MMC_ERR_ARG, "rows [%lld, %lld + %lld) outside the set's %lld rows", (long long)first, (long long)first, (long long)n,
@@ -507,7 +507,7 @@ static int check_set_range(const mmc_featureset* fs, int64_t first, int64_t n)
     return MMC_OK;
 }
 
-static int check_set_matches(const mmc_featureset* fs, mmc_trainer* t)
+int check_set_matches(const mmc_featureset* fs, mmc_trainer* t)
 {
     if (fs->dim != trainer_input_dim(t)) return mmc_fail(MMC_ERR_ARG, "feature set has %d columns, trainer expects %d", fs->dim, trainer_input_dim(t));
     if (fs->K != trainer_classes(t)) return mmc_fail(MMC_ERR_ARG, "feature set has %d classes, trainer %d", fs->K, trainer_classes(t));

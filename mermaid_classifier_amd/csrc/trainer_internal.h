@@ -40,3 +40,8 @@ int trainer_scratch(mmc_trainer* t, size_t bytes, void** out);
 int trainer_forward(mmc_trainer* t, const float* X, int n, hipStream_t st, const float** logits);
 // The same on rows that are already on the trainer's device (a feature set's): nothing is uploaded, the first layer reads X.
 int trainer_forward_device(mmc_trainer* t, const float* X_dev, int n, hipStream_t st, const float** logits);
+
+// argument checks shared by calib.hip and logit_scaling.hip (defined in calib.hip); each sets the error message and returns MMC_ERR_ARG
+int check_labels(const int32_t* y, int64_t n, int K);                        // every y[i] in [0, K)
+int check_set_range(const mmc_featureset* fs, int64_t first, int64_t n);     // rows [first, first + n) inside the set
+int check_set_matches(const mmc_featureset* fs, mmc_trainer* t);             // width, classes and device of set and trainer agree

@@ -29,12 +29,12 @@ at 16 384 rows a chunk and fill the device on their own.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, feature_transform as _ft
+from . import _lib, feature_transform as _ft, logit_scaling as _ls
 from .backbone import _current_stream_ptr, _device_index
 from .calibration import CalibratedMLP, calibrate, evaluate, evaluate_classes
 from .featureset import FeatureSet
@@ -109,7 +109,8 @@ class SweepConfig:
     production head's, trainer.py:118-123) and ``batches``, ``train_classifier``'s row-subset hook -- a callable
     ``epoch -> iterable of row-index arrays`` into the train set, e.g. a class-balancing subsample; None takes contiguous
     slices of ``train_sweep``'s ``batch_size`` rows.  ``label_smoothing`` / ``focal_gamma`` / ``logit_prior`` are the classifier's loss
-    formulation (``mmc_trainer_set_loss``): the members of one grouped pass may each have their own."""
+    formulation (``mmc_trainer_set_loss``): the members of one grouped pass may each have their own.  ``logit_scaling`` (keyword only)
+    is ``train_classifier``'s argument of that name for this configuration."""
     hidden_layer_sizes: Tuple[int, ...] = (500, 300, 100)
     learning_rate_init: float = 1e-4
     alpha: float = 1e-4
@@ -119,6 +120,9 @@ class SweepConfig:
     beta_1: float = 0.9
     beta_2: float = 0.999
     epsilon: float = 1e-8
+    # keyword-only, so it takes no positional slot: a kind string or a fitted LogitScaling, fitted on ref after training and folded
+    # before calibrate (train_sweep's logit_scaling= for one configuration); not a classifier argument
+    logit_scaling: Any = field(default=None, kw_only=True)
     batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None
     label_smoothing: float = 0.0
     focal_gamma: float = 0.0
@@ -176,8 +180,8 @@ def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[A
 
 def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Sequence[SweepConfig], nbr_epochs: int, *,
                 batch_size: int, early_stopping_patience: Optional[int] = None,
-                on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None, class_scores: bool = False, transform=None
-                ) -> List[Tuple[CalibratedMLP, Dict[str, Any], List[float]]]:
+                on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None, class_scores: bool = False, transform=None,
+                logit_scaling=None) -> List[Tuple[CalibratedMLP, Dict[str, Any], List[float]]]:
     """Train, early-stop and calibrate one head per configuration on three resident splits, all heads advancing in the same
     launches.  -> one ``(calibrated, info, ref_accs)`` per configuration, equal to
     ``train_classifier(train, ref, val, nbr_epochs, batch_size=batch_size, early_stopping_patience=..., batches=cfg.batches,
@@ -190,11 +194,18 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
     ``val_f1_macro`` per model and epoch, and nothing returned changes.
 
     ``transform`` as in ``train_classifier``: one transform (given, or fitted on ``train``) for the whole sweep; the splits are
-    transformed once, every head trains on the transformed sets, and every model returned is folded."""
+    transformed once, every head trains on the transformed sets, and every model returned is folded.
+
+    ``logit_scaling`` as in ``train_classifier``, for every configuration; a configuration's own ``SweepConfig.logit_scaling`` wins over
+    it.  A configuration with neither is calibrated exactly as before."""
     configs = list(configs)
     if not configs:
         raise ValueError("configs is empty")
     _check_splits(train, ref, val, batch_size)
+    scalings = [cfg.logit_scaling if cfg.logit_scaling is not None else logit_scaling for cfg in configs]
+    for sc in scalings:
+        if sc is not None:
+            _ls.check_argument(sc)
     if transform is not None:
         ft = _ft.resolve(transform, train)
         sets = []
@@ -202,7 +213,7 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
             for fs in (train, ref, val):
                 sets.append(ft.apply(fs))
             results = train_sweep(*sets, configs, nbr_epochs, batch_size=batch_size, early_stopping_patience=early_stopping_patience,
-                                  on_epoch_end=on_epoch_end, class_scores=class_scores)
+                                  on_epoch_end=on_epoch_end, class_scores=class_scores, logit_scaling=logit_scaling)
         finally:
             for fs in sets:
                 fs.close()
@@ -221,7 +232,8 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
     results = sweep_loop(clfs, batches, lambda group, rows: partial_fit_rows_group(group, train, rows, classes=classes),
                          eval_ref, lambda c: eval_val(c, val), nbr_epochs, early_stopping_patience=early_stopping_patience,
                          on_epoch_end=on_epoch_end, class_scores=class_scores)
-    return [(calibrate(clf, ref), info, ref_accs[id(live)]) for (clf, info), live in zip(results, clfs)]
+    return [(calibrate(clf, ref) if sc is None else calibrate(clf, ref, logit_scaling=sc), info, ref_accs[id(live)])
+            for (clf, info), live, sc in zip(results, clfs, scalings)]
 
 
 def rank_sweep(results: Sequence[Tuple[CalibratedMLP, Dict[str, Any], Any]], val, *, image_sizes=None,

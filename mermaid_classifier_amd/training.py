@@ -17,7 +17,7 @@ from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tupl
 
 import numpy as np
 
-from . import feature_transform as _ft
+from . import feature_transform as _ft, logit_scaling as _ls
 from .calibration import CalibratedMLP, calibrate, evaluate, evaluate_classes
 from .featureset import FeatureSet
 from .torch_classifier import TorchMLPClassifier
@@ -147,7 +147,7 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
                      class_weight: Optional[dict] = None, early_stopping_patience: Optional[int] = None,
                      on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None,
                      batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None,
-                     clf: Optional[TorchMLPClassifier] = None, class_scores: bool = False, transform=None
+                     clf: Optional[TorchMLPClassifier] = None, class_scores: bool = False, transform=None, logit_scaling=None
                      ) -> Tuple[CalibratedMLP, Dict[str, Any], List[float]]:
     """Train, early-stop and calibrate the MLP head on three resident splits.  -> ``(calibrated, info, ref_accs)``:
     the ``CalibratedMLP`` of the returned classifier on ``ref``, ``epoch_loop``'s ``info``, and the ref accuracy after every
@@ -169,8 +169,16 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
     ``transform``: a fitted ``FeatureTransform`` or a dict of ``FeatureTransform.fit`` keyword arguments (fitted on ``train``).  The
     three splits are transformed on the device into resident sets of their own, the head is trained and calibrated on those, they
     are freed, and the model returned is ``CalibratedMLP.folded(transform)``: it takes RAW features (``n_features_in_ ==
-    train.dim``) and carries the transform as ``transform_``.  ``None`` is the path described above, call for call."""
+    train.dim``) and carries the transform as ``transform_``.  ``None`` is the path described above, call for call.
+
+    ``logit_scaling``: a kind string (``"temperature"`` / ``"bias"`` / ``"vector"``) or a fitted ``LogitScaling``.  After the epoch loop
+    and the best-snapshot restore the scaling is fitted on ``ref`` (``logit_scaling.fit_logit_scaling``) and folded into the last
+    layer, and ``calibrate`` runs on the folded classifier; the model carries it as ``logit_scaling_``.  Early stopping and the
+    per-epoch evaluation keep reading raw logits.  With ``transform=`` the scaling goes into the last layer and the transform into the
+    first -- on a head with no hidden layer the scaling first, then the transform.  ``None`` changes no call."""
     _check_splits(train, ref, val, batch_size)
+    if logit_scaling is not None:
+        _ls.check_argument(logit_scaling)
     if transform is not None:
         ft = _ft.resolve(transform, train)
         sets = []
@@ -179,7 +187,7 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
                 sets.append(ft.apply(fs))
             cal, info, accs = train_classifier(*sets, nbr_epochs, batch_size=batch_size, class_weight=class_weight,
                                                early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end,
-                                               batches=batches, clf=clf, class_scores=class_scores)
+                                               batches=batches, clf=clf, class_scores=class_scores, logit_scaling=logit_scaling)
         finally:
             for fs in sets:
                 fs.close()
@@ -205,7 +213,9 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
     eval_val = evaluate_classes if class_scores else evaluate
     clf, info = epoch_loop(clf, train_epoch, eval_ref, lambda c: eval_val(c, val), nbr_epochs,
                            early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end, class_scores=class_scores)
-    return calibrate(clf, ref), info, ref_accs
+    if logit_scaling is None:
+        return calibrate(clf, ref), info, ref_accs
+    return calibrate(clf, ref, logit_scaling=logit_scaling), info, ref_accs
 
 
 def train_and_validate(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_epochs: int, *, batch_size: int,
