@@ -397,6 +397,49 @@ int mmc_trainer_evaluate_classes(mmc_trainer* t, const float* X, const int32_t* 
 int mmc_trainer_evaluate_classes_set(mmc_trainer* t, mmc_featureset* fs, int64_t first, int64_t n, int64_t* n_correct,
                                      int64_t* sum_log_loss_q32, int64_t* confusion /* K*K */, void* hip_stream);
 
+/* ---- regularisers: dropout and mixup in the trainer's steps, per trainer ------------------------------------------------------
+ * Extends: the step of TorchMLPClassifier.partial_fit (torch_classifier.py:226-303), which has no stochastic regulariser, by what
+ *   docs/research/hidden-layer-experiments.md (over-fitting onset at epoch 29; "loss formulation or feature representation") asks of a
+ *   trainer of larger heads.  No counterpart in the reference.  Everything here defaults to off; with the defaults a pass launches the
+ *   kernels, and gives the bits, of a trainer none of this was ever called on.
+ * Masks.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; round
+ *   c' = [hi(M1 c2)^c1^k0, lo(M1 c2), hi(M0 c0)^c3^k1, lo(M0 c0)], key bumped after each of 10 rounds).  Element (m, n) of site s at
+ *   step t -- m the row inside the mini-batch, N = dims[s] the unpadded width, site 0 the input and site l the output of layer l - 1
+ *   (l = 1 .. n_layers - 1; the logits never drop) -- has e = m N + n (64 bit), counter (lo32 e, hi32 e, lo32 t, s), key (lo32 seed,
+ *   hi32 seed), and is KEPT iff word 0 of the output >= thresh = (uint32)floor(p 2^32) (double).  t is the trainer's Adam step count
+ *   before the step, so mmc_trainer_adam_state(set = 1) positions the mask sequence too.  Kept values become v * scale, one fp32
+ *   multiply by scale = (float)(1.0 / (1.0 - p)); dropped values become +0.0f.  A mask depends on seed, step, site and position only.
+ * Dropout.  Forward: H(l+1) = mask_{l+1}(relu(H(l) W(l)^T + b(l))) for hidden layers; backward: dZ(l) = (dZ(l+1) W(l)) * scale where
+ *   H(l) > 0, else 0 (a dropped activation is stored as +0: no stored mask).  Input dropout applies mask_0 to the trainer's staged
+ *   copy of the mini-batch, after mixing; the caller's rows and a feature set's rows are never written.  Works on every pass, host-fed
+ *   or resident, solo or grouped.  Eval-mode forwards (mmc_trainer_logits, mmc_trainer_evaluate*, mmc_calibrator_add_*,
+ *   mmc_logitcal_add_*, mmc_trainer_loss_gradient) see none of it; inverted dropout needs no rescaling at inference.
+ * p_input, p_hidden finite in [0, 0.9], else MMC_ERR_ARG and the trainer is as it was; a p whose thresh is 0 is off; (0, 0, any seed)
+ *   restores the plain step.  Allowed between passes. */
+int mmc_trainer_set_dropout(mmc_trainer* t, double p_input, double p_hidden, uint64_t seed);
+/* Mixup on resident passes: mmc_trainer_partial_fit_set / mmc_trainer_group_partial_fit_set with a mixing plan.  partner: n int64
+ *   rows of the set; lam: one fp32 in [0, 1] per mini-batch, ceil(n / mb) entries (mb = min(batch_size, n)).  Position i of the pass,
+ *   in mini-batch s, reads a = visit[i] (or i) and b = partner[i]; with oml = 1.0f - lam[s] its row is
+ *     x[k] = lam Xa[k] + oml Xb[k]        two rounded fp32 products and one rounded add, no fma: numpy fp32 gives the same bits
+ *   and its loss  l_i = lam l(z_i, ya) + oml l(z_i, yb)  with l the trainer's own row term before normalisation (the plain weighted CE or
+ *   mmc_trainer_set_loss's form), one softmax and two targets.  The normaliser is g = (float)(1 / sum_i (lam w[ya_i] + oml w[yb_i])),
+ *   summed in double in row order (lam and oml as the doubles of their fp32 values), and dlogits = g (lam dl(ya) + oml dl(yb)).
+ *   The result does not depend on MMC_TRAIN_CHUNK_ROWS.
+ * NULL partner and NULL lam: the unmixed call, bit for bit.  In the group form partner / lam are arrays of `count` pointers (or both
+ *   NULL); a member whose two entries are NULL is not mixed.
+ * Checked before the first launch, on top of the unmixed call's checks: only one of partner / lam given, partner[i] outside the set,
+ *   lam NaN or outside [0, 1], a mini-batch whose mixed weight sum is not positive -> MMC_ERR_ARG, and no member's parameters, moments
+ *   or step count change. */
+int mmc_trainer_partial_fit_set_mixed(mmc_trainer* t, mmc_featureset* fs, const int64_t* visit, const int64_t* partner, const float* lam,
+                                      int64_t n, int batch_size, double* avg_loss, void* hip_stream);
+int mmc_trainer_group_partial_fit_set_mixed(mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit,
+                                            const int64_t* const* partner, const float* const* lam, const int64_t* n,
+                                            const int* batch_size, double* avg_loss, void* hip_stream);
+/* mmc_trainer_loss_gradient for the mixed loss stage: targets y and y2 per row and one lam for all n rows; g as above over these
+ * rows.  Same checks (y2 like y; lam NaN or outside [0, 1] -> MMC_ERR_ARG).  For checking the mixed loss stage per element. */
+int mmc_trainer_loss_gradient_mixed(mmc_trainer* t, const float* logits, const int32_t* y, const int32_t* y2, float lam, int64_t n,
+                                    float* dlogits, float* row_loss, void* hip_stream);
+
 /* ---- validation of a calibrated head --------------------------------------------------------------------------------
  * Replaces: what MermaidTrainer.__call__ computes after the calibration (mermaid_classifier/pyspacer/trainer.py:267-293:
  *   evaluate_classifier on val, ValResults, acc, the previous models' accuracies) and the per-row reductions the metrics make of the

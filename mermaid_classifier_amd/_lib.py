@@ -53,6 +53,7 @@ SYMBOLS = [
     "mmc_featureset_knn",
     "mmc_logitcal_create", "mmc_logitcal_destroy", "mmc_logitcal_rows", "mmc_logitcal_add_features", "mmc_logitcal_add_set",
     "mmc_logitcal_add_logits", "mmc_logitcal_stats", "mmc_logitcal_fit",
+    "mmc_trainer_set_dropout", "mmc_trainer_partial_fit_set_mixed", "mmc_trainer_group_partial_fit_set_mixed", "mmc_trainer_loss_gradient_mixed",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 
@@ -241,6 +242,15 @@ def _load() -> C.CDLL:
     lib.mmc_logitcal_stats.argtypes = [vp, vp, vp, C.POINTER(f64), vp, vp, vp, vp]
     lib.mmc_logitcal_fit.restype = i32
     lib.mmc_logitcal_fit.argtypes = [vp, i32, f64, f64, i32, vp, vp, vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(i32), C.POINTER(i32), vp]
+    lib.mmc_trainer_set_dropout.restype = i32
+    lib.mmc_trainer_set_dropout.argtypes = [vp, f64, f64, C.c_uint64]
+    lib.mmc_trainer_partial_fit_set_mixed.restype = i32
+    lib.mmc_trainer_partial_fit_set_mixed.argtypes = [vp, vp, vp, vp, vp, i64, i32, C.POINTER(C.c_double), vp]
+    lib.mmc_trainer_group_partial_fit_set_mixed.restype = i32
+    lib.mmc_trainer_group_partial_fit_set_mixed.argtypes = [C.POINTER(vp), i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64),
+                                                            C.POINTER(i32), C.POINTER(C.c_double), vp]
+    lib.mmc_trainer_loss_gradient_mixed.restype = i32
+    lib.mmc_trainer_loss_gradient_mixed.argtypes = [vp, vp, vp, vp, f32, i64, vp, vp, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

@@ -29,7 +29,7 @@ SOURCES = {
     "k_early.hip": KERNEL_HEADERS,
     "k_mid.hip": KERNEL_HEADERS,
     "k_tail.hip": KERNEL_HEADERS,
-    "trainer.hip": ["../../include/mmc.h", "trainer_internal.h", "kernels.h"],
+    "trainer.hip": ["../../include/mmc.h", "trainer_internal.h", "kernels.h", "philox.h"],
     "calib.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "featureset.hip": ["../../include/mmc.h", "trainer_internal.h"],
     "features.hip": ["../../include/mmc.h", "trainer_internal.h"],

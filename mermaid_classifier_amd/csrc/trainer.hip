@@ -14,6 +14,12 @@
 //             db(l) = column sums of dZ(l+1)                                           colsum_kernel
 //             dZ(l) = (dZ(l+1) W(l)) * (H(l) > 0)                                      tgemm_f32_kernel<TA=0,TB=0>, EPI_MASK
 //   update    Adam exactly in torch's order of operations (lerp, addcmul, addcdiv)     adam_kernel
+// Per trainer, off by default (include/mmc.h, "regularisers"; with everything off a step is the launches above and nothing else):
+//   dropout   H(l+1) = mask(relu(...)) * 1/(1-p), counter-based Philox masks (philox.h) tgemm_f32_drop_kernel, EPI_BIAS_RELU_DROP
+//             dZ(l) = (dZ(l+1) W(l)) * 1/(1-p) * (H(l) > 0): a dropped H is a stored +0  tgemm_f32_mask_scale_kernel, EPI_MASK_SCALE
+//             the input's mask on the staged mini-batch, in place                        dropout_rows_kernel
+//   mixup     x = lam Xa + oml Xb while the rows of a resident pass are gathered         gather_set_rows_mixed_kernel
+//             l = lam l(z, ya) + oml l(z, yb): one softmax, two targets                  ce_grad_mixed_kernel, ce_grad_rows_mixed
 //
 // Every step is the step of a group of trainers (trainer_group_step): each kind of launch once, one member per blockIdx.z, the
 // member's operands in a by-value descriptor array.  A trainer on its own -- the host-fed pass, mmc_trainer_partial_fit_set, the
@@ -30,11 +36,13 @@
 
 #include "../../include/mmc.h"
 #include "kernels.h"
+#include "philox.h"
 #include "trainer_internal.h"
 
 namespace {
 
-enum { TEPI_NONE = 0, TEPI_BIAS_RELU = 1, TEPI_BIAS = 2, TEPI_MASK = 3, TEPI_L2 = 4 };
+// TEPI_BIAS_RELU_DROP and TEPI_MASK_SCALE are the two epilogues of a member with hidden dropout (mmc_trainer_set_dropout)
+enum { TEPI_NONE = 0, TEPI_BIAS_RELU = 1, TEPI_BIAS = 2, TEPI_MASK = 3, TEPI_L2 = 4, TEPI_BIAS_RELU_DROP = 5, TEPI_MASK_SCALE = 6 };
 
 // C[M][N] = op(A)[M][K] . op(B)[K][N] (+ epilogue).  TA: A is stored [K][M]; TB: B is stored [N][K].
 // 64x64 output tile per 256-thread workgroup, K in steps of 16 through LDS (k-major tiles, so every transpose flavour is
@@ -45,12 +53,17 @@ enum { TEPI_NONE = 0, TEPI_BIAS_RELU = 1, TEPI_BIAS = 2, TEPI_MASK = 3, TEPI_L2 
 // Which multiply-add pairs are fused is part of the arithmetic, and the compiler does not decide it alike for every caller of a body
 // (left alone it once fused v * beta2 + ... of adam_elems in one of two callers only).  So the bodies compile with contraction off
 // and spell out the fusions these kernels have always had: fmaf where they fuse, plain operators where they round twice.
-template <bool TA, bool TB, int EPI>
+// VARIANT tags the instantiations of the kernels that exist for dropout alone (1; everything else 0).  hipcc emits other address
+// arithmetic for a body that two kernels share, so without the tag adding those kernels would change the code of the kernels a pass
+// without dropout launches; with it their assembly is what it was before dropout existed.  The arithmetic on values is the same
+// source under either tag, so a member computes the same bits whichever kernel runs it.
+template <bool TA, bool TB, int EPI, int VARIANT = 0>
 __device__ __forceinline__ void tgemm_f32_tile(float (&As)[16][68], float (&Bs)[16][68], int tile_m, int tile_n,
                                                const float* __restrict__ A, const float* __restrict__ B,
                                                float* __restrict__ C, int M, int N, int K,
                                                const float* __restrict__ aux,   // bias[N] | mask[M][N] | W[M][N]
-                                               float scale)                     // EPI_L2: alpha / mb
+                                               float scale,                     // EPI_L2: alpha / mb; EPI_MASK_SCALE: 1 / (1 - p)
+                                               DropMask drop = DropMask{})      // EPI_BIAS_RELU_DROP alone reads it
 {
 #pragma clang fp contract(off)   // the one fused operation (EPI_L2) is written as fmaf
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -111,6 +124,12 @@ __device__ __forceinline__ void tgemm_f32_tile(float (&As)[16][68], float (&Bs)[
                 if (EPI == TEPI_BIAS_RELU) v = fmaxf(v + aux[n], 0.f);
                 if (EPI == TEPI_BIAS) v = v + aux[n];
                 if (EPI == TEPI_MASK) v = aux[(size_t)m * N + n] > 0.f ? v : 0.f;
+                // a dropped activation was stored as +0, so H > 0 is "alive and kept": no stored mask, no second draw
+                if (EPI == TEPI_MASK_SCALE) v = aux[(size_t)m * N + n] > 0.f ? v * scale : 0.f;
+                if (EPI == TEPI_BIAS_RELU_DROP) {
+                    v = fmaxf(v + aux[n], 0.f);
+                    v = dropout_keep(drop, (uint64_t)m * (uint64_t)N + (uint64_t)n) ? v * drop.scale : 0.f;
+                }
                 if (EPI == TEPI_L2) v = fmaf(scale, aux[(size_t)m * N + n], v);
                 C[(size_t)m * N + n] = v;
             }
@@ -126,6 +145,13 @@ struct GemmDesc {
     float scale;
 };
 struct GemmGroup { GemmDesc d[MMC_TRAINER_GROUP_MAX]; };
+// the forward launch of a layer in which at least one member drops: the members' mask parameters beside their descriptors
+struct GemmDropGroup {
+    GemmDesc d[MMC_TRAINER_GROUP_MAX];
+    DropMask r[MMC_TRAINER_GROUP_MAX];
+};
+// by-value kernel arguments: every group struct of this file has to stay within the 4 KB the runtime passes
+static_assert(sizeof(GemmGroup) <= 4096 && sizeof(GemmDropGroup) <= 4096, "kernel-argument limit");
 
 // EPI0 / EPI1: the epilogues the members of one launch can have (forward: hidden layer or a member's last; otherwise one kind)
 template <bool TA, bool TB, int EPI0, int EPI1>
@@ -139,6 +165,56 @@ __global__ __launch_bounds__(256) void tgemm_f32_kernel(const GemmGroup g)
         tgemm_f32_tile<TA, TB, EPI0>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale);
     else
         tgemm_f32_tile<TA, TB, EPI1>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale);
+}
+
+// The forward of a layer when a member of the launch drops its hidden activations: the two epilogues above and the dropping one.
+// Launched only then, so a pass without dropout runs tgemm_f32_kernel alone.
+__global__ __launch_bounds__(256) void tgemm_f32_drop_kernel(const GemmDropGroup g)
+{
+    __shared__ float As[16][68];
+    __shared__ float Bs[16][68];
+    const GemmDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 64 >= d.M || (int)blockIdx.y * 64 >= d.N) return;
+    const DropMask& r = g.r[blockIdx.z];
+    if (d.epi == TEPI_BIAS_RELU_DROP)
+        tgemm_f32_tile<false, true, TEPI_BIAS_RELU_DROP, 1>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale, r);
+    else if (d.epi == TEPI_BIAS_RELU)
+        tgemm_f32_tile<false, true, TEPI_BIAS_RELU, 1>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale, r);
+    else
+        tgemm_f32_tile<false, true, TEPI_BIAS, 1>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale, r);
+}
+
+// The dZ launch of a layer when a member of it dropped that layer's input in the forward: EPI_MASK for the others, the scaled mask
+// for the dropping ones.
+__global__ __launch_bounds__(256) void tgemm_f32_mask_scale_kernel(const GemmGroup g)
+{
+    __shared__ float As[16][68];
+    __shared__ float Bs[16][68];
+    const GemmDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 64 >= d.M || (int)blockIdx.y * 64 >= d.N) return;
+    if (d.epi == TEPI_MASK_SCALE)
+        tgemm_f32_tile<false, false, TEPI_MASK_SCALE, 1>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale);
+    else
+        tgemm_f32_tile<false, false, TEPI_MASK, 1>(As, Bs, blockIdx.x, blockIdx.y, d.A, d.B, d.C, d.M, d.N, d.K, d.aux, d.scale);
+}
+
+// Input dropout: X[m][n] of the member's mini-batch becomes X * scale or +0 by the mask of site 0, in place in the trainer's own
+// staging (a copy of the caller's or the set's rows, read by this step alone).  Grid-stride; the mask does not depend on the grid.
+struct DropRowsDesc {
+    float* X;
+    int M, N;
+    DropMask mask;
+};
+struct DropRowsGroup { DropRowsDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(DropRowsGroup) <= 4096, "kernel-argument limit");
+
+__global__ __launch_bounds__(256) void dropout_rows_kernel(const DropRowsGroup g)
+{
+#pragma clang fp contract(off)
+    const DropRowsDesc& d = g.d[blockIdx.z];
+    const size_t total = (size_t)d.M * (size_t)d.N;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256)
+        d.X[e] = dropout_keep(d.mask, (uint64_t)e) ? d.X[e] * d.mask.scale : 0.f;
 }
 
 // The loss formulation of a trainer (mmc_trainer_set_loss): the fp32 scalars of the general instantiation below, made from doubles
@@ -270,6 +346,102 @@ __global__ __launch_bounds__(256) void ce_grad_kernel(const CeGroup g)
         ce_grad_rows<false>(blockIdx.x, d.logits, d.y, d.M, d.K, d.cw, d.inv_wsum, d.dlogits, d.row_loss, d.loss);
 }
 
+// The loss stage of a mixed row (mmc_trainer_partial_fit_set_mixed): one softmax, two targets a = y[row], b = y2[row].
+//   l_i = lam l(z, a) + oml l(z, b),   dl_i/dz = lam dl(a)/dz + oml dl(b)/dz,   oml = 1.0f - lam
+// with l the row term of ce_grad_rows above -- the general form, which at eps = gamma = 0 and no prior is the plain weighted CE.
+// Each target's term is formed as ce_grad_rows<true> forms it; the combination is two rounded products and one rounded add.
+__device__ __forceinline__ void ce_grad_rows_mixed(int block, const float* __restrict__ logits, const int32_t* __restrict__ y,
+                                                   const int32_t* __restrict__ y2, int M, int K, const float* __restrict__ cw,
+                                                   float inv_wsum, float lam, float oml, float* __restrict__ dlogits,
+                                                   float* __restrict__ row_loss, const CeLoss& ls)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int row = block * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float* z = logits + (size_t)row * K;
+    const float* pr = ls.prior;
+    const int ya = y[row], yb = y2[row];
+    float mx = -INFINITY;
+    for (int c = lane; c < K; c += 64) mx = fmaxf(mx, pr ? z[c] + pr[c] : z[c]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    float s = 0.f, soa = 0.f, sob = 0.f;   // sum_c e_c; sum_{c != a} e_c; sum_{c != b} e_c
+    for (int c = lane; c < K; c += 64) {
+        const float e = expf((pr ? z[c] + pr[c] : z[c]) - mx);
+        s += e;
+        soa += c == ya ? 0.f : e;
+        sob += c == yb ? 0.f : e;
+    }
+    s = wave_sum(s);
+    soa = wave_sum(soa);
+    sob = wave_sum(sob);
+    const float lse = logf(s);
+    const bool smooth = ls.eps_k != 0.f;
+    float sw = 0.f;                        // sum_c w_c logp_c
+    if (smooth) {
+        for (int c = lane; c < K; c += 64) {
+            const float lp = (pr ? z[c] + pr[c] : z[c]) - mx - lse;
+            sw += cw ? cw[c] * lp : lp;
+        }
+        sw = wave_sum(sw);
+    }
+    float a2[2], af2[2], l2[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int yi = k ? yb : ya;
+        const float so = k ? sob : soa;
+        const float w = cw ? cw[yi] : 1.0f;
+        const float ut = pr ? z[yi] + pr[yi] : z[yi];
+        const float nll = lse - (ut - mx);
+        float m = 1.0f, f = 1.0f;
+        if (ls.gamma != 0.f) {
+            const float q = so / s;
+            const float pt = expf(ut - mx - lse);
+            const float pw = powf(q, ls.gamma - 1.0f);
+            m = pw * q;
+            f = m + ls.gamma * pt * pw * nll;
+        }
+        a2[k] = ls.om_eps * w;
+        af2[k] = a2[k] * f;
+        float l = a2[k] * m * nll;
+        if (smooth) l = l - ls.eps_k * sw;
+        l2[k] = l;
+    }
+    for (int c = lane; c < K; c += 64) {
+        const float p = expf((pr ? z[c] + pr[c] : z[c]) - mx - lse);
+        float da = af2[0] * (p - (c == ya ? 1.0f : 0.0f));
+        float db = af2[1] * (p - (c == yb ? 1.0f : 0.0f));
+        if (smooth) {
+            const float sm = ls.eps_k * (p * ls.w_total - (cw ? cw[c] : 1.0f));
+            da = da + sm;
+            db = db + sm;
+        }
+        dlogits[(size_t)row * K + c] = inv_wsum * (lam * da + oml * db);
+    }
+    if (lane == 0) row_loss[row] = (lam * l2[0] + oml * l2[1]) * inv_wsum;
+}
+
+struct CeMixDesc {
+    const float* logits;
+    const int32_t *y, *y2;
+    const float* cw;
+    float *dlogits, *row_loss;
+    int M, K;
+    float inv_wsum, lam, oml;
+    CeLoss loss;
+};
+struct CeMixGroup { CeMixDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(CeGroup) <= 4096 && sizeof(CeMixGroup) <= 4096, "kernel-argument limit");
+
+// the mixed members of a step; the others go through ce_grad_kernel as ever
+__global__ __launch_bounds__(256) void ce_grad_mixed_kernel(const CeMixGroup g)
+{
+    const CeMixDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 4 >= d.M) return;
+    ce_grad_rows_mixed(blockIdx.x, d.logits, d.y, d.y2, d.M, d.K, d.cw, d.inv_wsum, d.lam, d.oml, d.dlogits, d.row_loss, d.loss);
+}
+
 // db[n] = sum_m dZ[m][n]; thread per column, rows in order (four chains)
 __device__ __forceinline__ void colsum_cols(int block, const float* __restrict__ dZ, int M, int N, float* __restrict__ db)
 {
@@ -293,6 +465,7 @@ struct ColsumDesc {
     int M, N;
 };
 struct ColsumGroup { ColsumDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(ColsumGroup) <= 4096, "kernel-argument limit");
 
 __global__ __launch_bounds__(256) void colsum_kernel(const ColsumGroup g)
 {
@@ -322,6 +495,7 @@ struct SumsqDesc {
     size_t n;
 };
 struct SumsqGroup { SumsqDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(SumsqGroup) <= 4096, "kernel-argument limit");
 
 // gridDim.x is 256 blocks whatever the group, so a member's slices and partials do not depend on who trains beside it
 __global__ __launch_bounds__(256) void sumsq_kernel(const SumsqGroup g)
@@ -355,6 +529,7 @@ struct LossDesc {
     float reg_scale;
 };
 struct LossGroup { LossDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(LossGroup) <= 4096, "kernel-argument limit");
 
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const LossGroup g)
 {
@@ -391,6 +566,7 @@ struct AdamDesc {
     float om_beta1, beta2, om_beta2, eps, step_size, bc2_sqrt;
 };
 struct AdamGroup { AdamDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(AdamGroup) <= 4096, "kernel-argument limit");
 
 __global__ __launch_bounds__(256) void adam_kernel(const AdamGroup g)
 {
@@ -436,6 +612,45 @@ __global__ __launch_bounds__(256) void gather_set_rows_kernel(const float* __res
     if (lane == 0) yo[i] = ys[src];
 }
 
+// The mixing form of gather_set_rows_kernel (mmc_trainer_partial_fit_set_mixed): position i of the chunk, in the chunk's
+// mini-batch i / mb, becomes lam Xs[a] + oml Xs[b] with a = src(i), b = partner[i] and oml = 1.0f - lam[i / mb]: two rounded
+// products and one rounded add per element (no fma), so the row is what numpy fp32 makes of it.  Both labels are kept.
+template <bool V4>
+__global__ __launch_bounds__(256) void gather_set_rows_mixed_kernel(const float* __restrict__ Xs, const int32_t* __restrict__ ys,
+                                                                    const int64_t* __restrict__ visit, int64_t first,
+                                                                    const int64_t* __restrict__ partner, const float* __restrict__ lam,
+                                                                    int mb, int rows, int dim, float* __restrict__ Xo,
+                                                                    int32_t* __restrict__ yo, int32_t* __restrict__ y2o)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= rows) return;
+    const int64_t a = visit ? visit[i] : first + i, b = partner[i];
+    const float la = lam[i / mb], lb = 1.0f - la;
+    const float *sa = Xs + (size_t)a * dim, *sb = Xs + (size_t)b * dim;
+    float* d = Xo + (size_t)i * dim;
+    if (V4) {
+        const float4 *a4 = reinterpret_cast<const float4*>(sa), *b4 = reinterpret_cast<const float4*>(sb);
+        float4* d4 = reinterpret_cast<float4*>(d);
+        for (int k = lane; k < dim / 4; k += 64) {
+            const float4 u = a4[k], v = b4[k];
+            float4 o;
+            o.x = la * u.x + lb * v.x;
+            o.y = la * u.y + lb * v.y;
+            o.z = la * u.z + lb * v.z;
+            o.w = la * u.w + lb * v.w;
+            d4[k] = o;
+        }
+    } else {
+        for (int k = lane; k < dim; k += 64) d[k] = la * sa[k] + lb * sb[k];
+    }
+    if (lane == 0) {
+        yo[i] = ys[a];
+        y2o[i] = ys[b];
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -466,6 +681,16 @@ struct mmc_trainer {
     float w_total = 0.f;                                // the float of the double sum of the class weights in class order; K without
     void* scratch = nullptr;                           // trainer_scratch (calib.hip's evaluation buffers)
     size_t scratch_bytes = 0;
+    // regularisers (mmc_trainer_set_dropout; the plan of a mixed pass): all off = today's launches
+    double p_input = 0.0, p_hidden = 0.0;
+    uint64_t drop_seed = 0;
+    uint32_t thresh_input = 0, thresh_hidden = 0;       // (uint32)floor(p 2^32); 0 = off
+    float scale_input = 1.f, scale_hidden = 1.f;        // (float)(1.0 / (1.0 - p))
+    int32_t* y2 = nullptr;                              // the partner's label of every staged row of a mixed pass
+    int64_t* partner = nullptr;                         // device copy of a mixed pass's partner rows
+    float* lam = nullptr;                               // device copy of its per-mini-batch lam
+    int64_t cap_y2 = 0, cap_partner = 0;
+    int cap_lam = 0;
 };
 
 #define T_TRY(expr)                                                                                   \
@@ -494,6 +719,7 @@ extern "C" void mmc_trainer_destroy(mmc_trainer* t)
     for (size_t l = 1; l < t->dZ.size(); ++l) hipFree(t->dZ[l]);
     hipFree(t->cw); hipFree(t->prior); hipFree(t->X); hipFree(t->row_loss); hipFree(t->partials); hipFree(t->losses); hipFree(t->y);
     hipFree(t->Xn); hipFree(t->yn); hipFree(t->order); hipFree(t->visit); hipFree(t->scratch);
+    hipFree(t->y2); hipFree(t->partner); hipFree(t->lam);
     delete t;
 }
 
@@ -593,6 +819,21 @@ extern "C" int mmc_trainer_set_loss(mmc_trainer* t, double label_smoothing, doub
     return MMC_OK;
 }
 
+extern "C" int mmc_trainer_set_dropout(mmc_trainer* t, double p_input, double p_hidden, uint64_t seed)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!(std::isfinite(p_input) && p_input >= 0.0 && p_input <= 0.9)) return mmc_fail(MMC_ERR_ARG, "p_input = %g outside [0, 0.9]", p_input);
+    if (!(std::isfinite(p_hidden) && p_hidden >= 0.0 && p_hidden <= 0.9)) return mmc_fail(MMC_ERR_ARG, "p_hidden = %g outside [0, 0.9]", p_hidden);
+    t->p_input = p_input;
+    t->p_hidden = p_hidden;
+    t->drop_seed = seed;
+    t->thresh_input = (uint32_t)std::floor(p_input * 4294967296.0);
+    t->thresh_hidden = (uint32_t)std::floor(p_hidden * 4294967296.0);
+    t->scale_input = (float)(1.0 / (1.0 - p_input));
+    t->scale_hidden = (float)(1.0 / (1.0 - p_hidden));
+    return MMC_OK;
+}
+
 static int trainer_reserve(mmc_trainer* t, int64_t n, int mb, int steps)
 {
     if (n > t->cap_n) {
@@ -628,8 +869,10 @@ struct StepMember {
     mmc_trainer* t;
     int64_t off;
     int cur;
-    float inv_wsum;   // 1 / sum of the mini-batch's class weights
+    float inv_wsum;   // 1 / sum of the mini-batch's class weights (of a mixed one: of lam w[ya] + oml w[yb])
     int slot;
+    bool mixed;       // the rows were mixed: t->y2 holds the partners' labels, the loss stage takes two targets
+    float lam;
 };
 
 template <bool TA, bool TB, int EPI0, int EPI1>
@@ -650,6 +893,13 @@ GemmDesc forward_desc(const mmc_trainer* t, int l, int mb)
     return GemmDesc{t->H[l], t->W[l], t->H[l + 1], t->b[l], mb, t->dims[l + 1], t->dims[l], l == t->L - 1 ? TEPI_BIAS : TEPI_BIAS_RELU, 0.f};
 }
 
+// the masks of site `site` of t at its current step count; hidden sites share p_hidden
+DropMask drop_mask(const mmc_trainer* t, int site)
+{
+    return DropMask{site ? t->thresh_hidden : t->thresh_input, (uint32_t)t->drop_seed, (uint32_t)(t->drop_seed >> 32), (uint32_t)t->t,
+                    (uint32_t)site, site ? t->scale_hidden : t->scale_input};
+}
+
 // the loss stage on mb rows of logits: which instantiation runs is a function of the trainer's options alone
 CeDesc ce_desc(const mmc_trainer* t, const float* logits, const int32_t* y, int mb, float inv_wsum)
 {
@@ -666,22 +916,62 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
         t->H[0] = t->X + (size_t)act[i].off * t->dims[0];
         Lmax = std::max(Lmax, t->L);
     }
-    for (int l = 0; l < Lmax; ++l) {
-        GemmGroup g;
+    {   // input dropout: the mask of site 0 on the members' staged rows, before layer 0 (and after the mixing of a mixed pass)
+        DropRowsGroup g;
         int k = 0;
-        for (int i = 0; i < cnt; ++i)
-            if (l < act[i].t->L) g.d[k++] = forward_desc(act[i].t, l, act[i].cur);
-        T_K((launch_tgemm<false, true, TEPI_BIAS_RELU, TEPI_BIAS>(g, k, st)));
+        size_t emax = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i].t;
+            if (!t->thresh_input) continue;
+            g.d[k++] = DropRowsDesc{t->H[0], act[i].cur, t->dims[0], drop_mask(t, 0)};
+            emax = std::max(emax, (size_t)act[i].cur * t->dims[0]);
+        }
+        if (k) hipLaunchKernelGGL(dropout_rows_kernel, dim3((unsigned)std::min<size_t>((emax + 255) / 256, 4096), 1, k), dim3(256), 0, st, g);
+    }
+    for (int l = 0; l < Lmax; ++l) {
+        GemmDropGroup g;
+        int k = 0, tm = 0, tn = 0;
+        bool drops = false;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i].t;
+            if (l >= t->L) continue;
+            g.d[k] = forward_desc(t, l, act[i].cur);
+            g.r[k] = DropMask{};
+            if (t->thresh_hidden && l < t->L - 1) {   // the last layer never drops
+                g.d[k].epi = TEPI_BIAS_RELU_DROP;
+                g.r[k] = drop_mask(t, l + 1);
+                drops = true;
+            }
+            tm = std::max(tm, (g.d[k].M + 63) / 64);
+            tn = std::max(tn, (g.d[k].N + 63) / 64);
+            ++k;
+        }
+        if (drops) {
+            hipLaunchKernelGGL(tgemm_f32_drop_kernel, dim3(tm, tn, k), dim3(256), 0, st, g);
+            T_K((int)hipGetLastError());
+        } else {
+            GemmGroup plain;
+            std::copy(g.d, g.d + k, plain.d);
+            T_K((launch_tgemm<false, true, TEPI_BIAS_RELU, TEPI_BIAS>(plain, k, st)));
+        }
     }
     {
         CeGroup g;
-        int mmax = 0;
+        CeMixGroup gm;
+        int k = 0, km = 0, mmax = 0, mmax_mixed = 0;
         for (int i = 0; i < cnt; ++i) {
             const mmc_trainer* t = act[i].t;
-            g.d[i] = ce_desc(t, t->H[t->L], t->y + act[i].off, act[i].cur, act[i].inv_wsum);
-            mmax = std::max(mmax, act[i].cur);
+            if (act[i].mixed) {
+                gm.d[km++] = CeMixDesc{t->H[t->L], t->y + act[i].off, t->y2 + act[i].off, t->cw, t->dZ[t->L], t->row_loss, act[i].cur, t->K,
+                                       act[i].inv_wsum, act[i].lam, 1.0f - act[i].lam, trainer_ce_loss(t)};
+                mmax_mixed = std::max(mmax_mixed, act[i].cur);
+            } else {
+                g.d[k++] = ce_desc(t, t->H[t->L], t->y + act[i].off, act[i].cur, act[i].inv_wsum);
+                mmax = std::max(mmax, act[i].cur);
+            }
         }
-        hipLaunchKernelGGL(ce_grad_kernel, dim3((mmax + 3) / 4, 1, cnt), dim3(256), 0, st, g);
+        if (k) hipLaunchKernelGGL(ce_grad_kernel, dim3((mmax + 3) / 4, 1, k), dim3(256), 0, st, g);
+        if (km) hipLaunchKernelGGL(ce_grad_mixed_kernel, dim3((mmax_mixed + 3) / 4, 1, km), dim3(256), 0, st, gm);
     }
     // regularised loss of this mini-batch (before the update): data + (0.5 alpha / mb) sum W^2
     for (int l = 0; l < Lmax; ++l) {
@@ -706,6 +996,7 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
         GemmGroup gw, gz;
         ColsumGroup gc;
         int k = 0, kz = 0, nmax = 0;
+        bool drops = false;
         for (int i = 0; i < cnt; ++i) {
             const mmc_trainer* t = act[i].t;
             if (l >= t->L) continue;
@@ -714,11 +1005,29 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
             gc.d[k] = ColsumDesc{t->dZ[l + 1], t->gb[l], mb, no};
             ++k;
             nmax = std::max(nmax, no);
-            if (l > 0) gz.d[kz++] = GemmDesc{t->dZ[l + 1], t->W[l], t->dZ[l], t->H[l], mb, ni, no, TEPI_MASK, 0.f};
+            if (l > 0) {
+                gz.d[kz] = GemmDesc{t->dZ[l + 1], t->W[l], t->dZ[l], t->H[l], mb, ni, no, TEPI_MASK, 0.f};
+                if (t->thresh_hidden) {   // H(l) was dropped in the forward: the kept elements carry the scale back
+                    gz.d[kz].epi = TEPI_MASK_SCALE;
+                    gz.d[kz].scale = t->scale_hidden;
+                    drops = true;
+                }
+                ++kz;
+            }
         }
         T_K((launch_tgemm<true, false, TEPI_L2, TEPI_L2>(gw, k, st)));
         hipLaunchKernelGGL(colsum_kernel, dim3((nmax + 255) / 256, 1, k), dim3(256), 0, st, gc);
-        if (kz) T_K((launch_tgemm<false, false, TEPI_MASK, TEPI_MASK>(gz, kz, st)));
+        if (kz && drops) {
+            int tm = 0, tn = 0;
+            for (int i = 0; i < kz; ++i) {
+                tm = std::max(tm, (gz.d[i].M + 63) / 64);
+                tn = std::max(tn, (gz.d[i].N + 63) / 64);
+            }
+            hipLaunchKernelGGL(tgemm_f32_mask_scale_kernel, dim3(tm, tn, kz), dim3(256), 0, st, gz);
+            T_K((int)hipGetLastError());
+        } else if (kz) {
+            T_K((launch_tgemm<false, false, TEPI_MASK, TEPI_MASK>(gz, kz, st)));
+        }
     }
     float step_size[MMC_TRAINER_GROUP_MAX], bc2_sqrt[MMC_TRAINER_GROUP_MAX];
     for (int i = 0; i < cnt; ++i) {
@@ -767,6 +1076,29 @@ int minibatch_wsums(const char* who, const mmc_trainer* t, const int32_t* y, con
         double wsum = 0.0;
         if (t->cw) { for (int i = 0; i < cur; ++i) wsum += t->cw_host[y[idx ? idx[start + i] : start + i]]; } else wsum = cur;
         if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "%smini-batch %d has zero total class weight", who, s);
+        (*wsums)[s] = wsum;
+    }
+    return 0;
+}
+
+// minibatch_wsums of a mixed pass: position i carries lam w[ya] + oml w[yb] with ya = y[visit[i]], yb = y[partner[i]] and
+// oml = 1.0f - lam[s], summed in double in row order
+int minibatch_wsums_mixed(const char* who, const mmc_trainer* t, const int32_t* y, const int64_t* visit, const int64_t* partner,
+                          const float* lam, int64_t n, int mb, std::vector<double>* wsums)
+{
+    const int steps = (int)((n + mb - 1) / mb);
+    wsums->resize(steps);
+    for (int s = 0; s < steps; ++s) {
+        const int64_t start = (int64_t)s * mb;
+        const int cur = batch_rows(n, start, mb);
+        const double la = (double)lam[s], lb = (double)(1.0f - lam[s]);
+        double wsum = 0.0;
+        for (int i = 0; i < cur; ++i) {
+            const double wa = t->cw ? (double)t->cw_host[y[visit ? visit[start + i] : start + i]] : 1.0;
+            const double wb = t->cw ? (double)t->cw_host[y[partner[start + i]]] : 1.0;
+            wsum += la * wa + lb * wb;
+        }
+        if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "%smini-batch %d has zero total mixed class weight", who, s);
         (*wsums)[s] = wsum;
     }
     return 0;
@@ -824,7 +1156,7 @@ extern "C" int mmc_trainer_partial_fit_ordered(mmc_trainer* t, const float* X, c
     }
     for (int s = 0; s < steps; ++s) {
         const int64_t start = (int64_t)s * mb;
-        const StepMember one{t, start, batch_rows(n, start, mb), (float)(1.0 / wsums[s]), s};
+        const StepMember one{t, start, batch_rows(n, start, mb), (float)(1.0 / wsums[s]), s, false, 0.f};
         if ((r = trainer_group_step(&one, 1, st))) return r;
     }
     std::vector<float> h(steps);
@@ -847,6 +1179,8 @@ namespace {
 struct SetPass {
     mmc_trainer* t = nullptr;
     const int64_t* visit = nullptr;
+    const int64_t* partner = nullptr;   // a mixed pass: partner rows and one lam per mini-batch (both or neither)
+    const float* lam = nullptr;
     int64_t n = 0;
     int mb = 0, steps = 0;
     int64_t chunk = 0, steps_per_chunk = 0, stage_rows = 0;
@@ -869,6 +1203,20 @@ int check_set_pass(const char* who, const mmc_trainer* t, const mmc_featureset* 
     return 0;
 }
 
+// the plan of a mixed pass: both arrays or neither, every partner a row of the set, every lam in [0, 1]
+int check_mix_plan(const char* who, const mmc_featureset* fs, const int64_t* partner, const float* lam, int64_t n, int batch_size)
+{
+    if (!partner && !lam) return 0;
+    if (!partner || !lam) return mmc_fail(MMC_ERR_ARG, "%spartner and lam go together: only %s was given", who, partner ? "partner" : "lam");
+    for (int64_t i = 0; i < n; ++i)
+        if (partner[i] < 0 || partner[i] >= fs->n)
+            return mmc_fail(MMC_ERR_ARG, "%spartner[%lld] = %lld outside [0, %lld)", who, (long long)i, (long long)partner[i], (long long)fs->n);
+    const int64_t mb = batch_size < n ? batch_size : n, steps = (n + mb - 1) / mb;
+    for (int64_t s = 0; s < steps; ++s)
+        if (!(lam[s] >= 0.f && lam[s] <= 1.f)) return mmc_fail(MMC_ERR_ARG, "%slam[%lld] = %g outside [0, 1]", who, (long long)s, (double)lam[s]);
+    return 0;
+}
+
 int train_chunk_bound(int64_t* bound)
 {
     *bound = MMC_TRAIN_CHUNK_ROWS_DEFAULT;
@@ -881,12 +1229,12 @@ int train_chunk_bound(int64_t* bound)
     return 0;
 }
 
-int plan_set_pass(const char* who, mmc_trainer* t, const mmc_featureset* fs, const int64_t* visit, int64_t n, int batch_size,
-                  int64_t bound, SetPass* p)
+int plan_set_pass(const char* who, mmc_trainer* t, const mmc_featureset* fs, const int64_t* visit, const int64_t* partner,
+                  const float* lam, int64_t n, int batch_size, int64_t bound, SetPass* p)
 {
     const int mb = (int)(batch_size < n ? batch_size : n);
     if ((n + mb - 1) / mb > (int64_t)1 << 30) return mmc_fail(MMC_ERR_ARG, "%s%lld rows in mini-batches of %d: too many steps for one pass", who, (long long)n, mb);
-    p->t = t; p->visit = visit; p->n = n;
+    p->t = t; p->visit = visit; p->partner = partner; p->lam = lam; p->n = n;
     p->mb = mb;
     p->steps = (int)((n + mb - 1) / mb);
     // the largest multiple of the mini-batch not above the bound, at least one mini-batch, and no more than a gather's grid / `rows` hold
@@ -897,6 +1245,7 @@ int plan_set_pass(const char* who, mmc_trainer* t, const mmc_featureset* fs, con
     p->chunk = chunk;
     p->steps_per_chunk = chunk / mb;
     p->stage_rows = chunk < n ? chunk : n;
+    if (partner) return minibatch_wsums_mixed(who, t, fs->y_host.data(), visit, partner, lam, n, mb, &p->wsums);
     return minibatch_wsums(who, t, fs->y_host.data(), visit, n, mb, &p->wsums);
 }
 
@@ -912,13 +1261,45 @@ int reserve_set_pass(const SetPass& p)
         T_TRY(hipMalloc((void**)&t->visit, (size_t)p.n * 8 + 256));
         t->cap_visit = p.n;
     }
+    if (p.partner) {
+        if (p.stage_rows > t->cap_y2) {
+            hipFree(t->y2);
+            t->y2 = nullptr; t->cap_y2 = 0;
+            T_TRY(hipMalloc((void**)&t->y2, (size_t)p.stage_rows * 4 + 256));
+            t->cap_y2 = p.stage_rows;
+        }
+        if (p.n > t->cap_partner) {
+            hipFree(t->partner);
+            t->partner = nullptr; t->cap_partner = 0;
+            T_TRY(hipMalloc((void**)&t->partner, (size_t)p.n * 8 + 256));
+            t->cap_partner = p.n;
+        }
+        if (p.steps > t->cap_lam) {
+            hipFree(t->lam);
+            t->lam = nullptr; t->cap_lam = 0;
+            T_TRY(hipMalloc((void**)&t->lam, (size_t)p.steps * 4 + 256));
+            t->cap_lam = p.steps;
+        }
+    }
     return 0;
 }
 
 // rows [c0, c0 + rows) of the pass into the staging t->X / t->y
-int gather_chunk(mmc_trainer* t, const mmc_featureset* fs, bool visited, int64_t c0, int rows, hipStream_t st)
+int gather_chunk(mmc_trainer* t, const mmc_featureset* fs, bool visited, bool mixed, int mb, int64_t c0, int rows, hipStream_t st)
 {
     const int64_t* vis = visited ? t->visit + c0 : nullptr;
+    if (mixed) {   // c0 is a multiple of mb: the chunk's first mini-batch is c0 / mb of the pass
+        const int64_t* par = t->partner + c0;
+        const float* lam = t->lam + c0 / mb;
+        if (fs->dim & 3)
+            hipLaunchKernelGGL(gather_set_rows_mixed_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, par, lam, mb,
+                               rows, fs->dim, t->X, t->y, t->y2);
+        else
+            hipLaunchKernelGGL(gather_set_rows_mixed_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, par, lam, mb,
+                               rows, fs->dim, t->X, t->y, t->y2);
+        T_TRY(hipGetLastError());
+        return 0;
+    }
     if (fs->dim & 3)
         hipLaunchKernelGGL(gather_set_rows_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, rows, fs->dim, t->X, t->y);
     else
@@ -932,8 +1313,8 @@ int gather_chunk(mmc_trainer* t, const mmc_featureset* fs, bool visited, int64_t
 // staging (t->X / t->y) a chunk of whole mini-batches at a time, and that chunk's steps follow on the same stream, so the steps
 // run the kernels of the host-fed pass on the same values: same bits.  `grouped` is the entry point's way of naming a member and of
 // reporting a failed reservation; the solo entry is a group of one that names nobody.
-int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit, const int64_t* n,
-             const int* batch_size, double* avg_loss, hipStream_t st)
+int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit,
+             const int64_t* const* partner, const float* const* lam, const int64_t* n, const int* batch_size, double* avg_loss, hipStream_t st)
 {
     std::vector<SetPass> mem(count);
     char who[MMC_TRAINER_GROUP_MAX][32];
@@ -942,12 +1323,15 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
         who[m][0] = 0;
         if (grouped) std::snprintf(who[m], sizeof who[m], "member %d: ", m);
         if ((r = check_set_pass(who[m], trainers[m], fs, visit[m], n[m], batch_size[m]))) return r;
+        if ((r = check_mix_plan(who[m], fs, partner ? partner[m] : nullptr, lam ? lam[m] : nullptr, n[m], batch_size[m]))) return r;
     }
     int64_t bound = 0;
     if ((r = train_chunk_bound(&bound))) return r;
     int max_steps = 0;
     for (int m = 0; m < count; ++m) {
-        if ((r = plan_set_pass(who[m], trainers[m], fs, visit[m], n[m], batch_size[m], bound, &mem[m]))) return r;
+        if ((r = plan_set_pass(who[m], trainers[m], fs, visit[m], partner ? partner[m] : nullptr, lam ? lam[m] : nullptr, n[m], batch_size[m],
+                               bound, &mem[m])))
+            return r;
         max_steps = std::max(max_steps, mem[m].steps);
     }
     T_TRY(hipSetDevice(fs->device));
@@ -961,6 +1345,11 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
         }
     for (int m = 0; m < count; ++m)
         if (mem[m].visit) T_TRY(hipMemcpyAsync(mem[m].t->visit, mem[m].visit, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
+    for (int m = 0; m < count; ++m)
+        if (mem[m].partner) {
+            T_TRY(hipMemcpyAsync(mem[m].t->partner, mem[m].partner, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
+            T_TRY(hipMemcpyAsync(mem[m].t->lam, mem[m].lam, (size_t)mem[m].steps * 4, hipMemcpyHostToDevice, st));
+        }
     StepMember act[MMC_TRAINER_GROUP_MAX];
     for (int s = 0; s < max_steps; ++s) {
         int cnt = 0;
@@ -970,9 +1359,10 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
             const int64_t start = (int64_t)s * p.mb, c0 = s / p.steps_per_chunk * p.chunk;
             if (start == c0) {            // its first step of a chunk: stage the chunk's rows first
                 const int rows = (int)((p.n - c0) < p.chunk ? (p.n - c0) : p.chunk);
-                if ((r = gather_chunk(p.t, fs, p.visit != nullptr, c0, rows, st))) return r;
+                if ((r = gather_chunk(p.t, fs, p.visit != nullptr, p.partner != nullptr, p.mb, c0, rows, st))) return r;
             }
-            act[cnt++] = StepMember{p.t, start - c0, batch_rows(p.n, start, p.mb), (float)(1.0 / p.wsums[s]), s};
+            act[cnt++] = StepMember{p.t, start - c0, batch_rows(p.n, start, p.mb), (float)(1.0 / p.wsums[s]), s, p.partner != nullptr,
+                                    p.partner ? p.lam[s] : 0.f};
         }
         if ((r = trainer_group_step(act, cnt, st))) return r;
     }
@@ -995,12 +1385,30 @@ extern "C" int mmc_trainer_partial_fit_set(mmc_trainer* t, mmc_featureset* fs, c
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
-    return set_pass(false, &t, 1, fs, &visit, &n, &batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
+    return set_pass(false, &t, 1, fs, &visit, nullptr, nullptr, &n, &batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
+}
+
+// mmc_trainer_partial_fit_set on mixed rows (include/mmc.h, "regularisers"); NULL partner and lam: that call itself.
+extern "C" int mmc_trainer_partial_fit_set_mixed(mmc_trainer* t, mmc_featureset* fs, const int64_t* visit, const int64_t* partner,
+                                                 const float* lam, int64_t n, int batch_size, double* avg_loss, void* hip_stream)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
+    return set_pass(false, &t, 1, fs, &visit, &partner, &lam, &n, &batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
 }
 
 // mmc_trainer_partial_fit_set for `count` trainers over one set in the launches of one pass (include/mmc.h).
 extern "C" int mmc_trainer_group_partial_fit_set(mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit,
                                                  const int64_t* n, const int* batch_size, double* avg_loss, void* hip_stream)
+{
+    return mmc_trainer_group_partial_fit_set_mixed(trainers, count, fs, visit, nullptr, nullptr, n, batch_size, avg_loss, hip_stream);
+}
+
+// The grouped pass with a mixing plan per member (include/mmc.h, "regularisers"): partner / lam are arrays of `count` pointers, or
+// NULL for a pass in which nobody is mixed; a member whose two entries are NULL is not mixed.
+extern "C" int mmc_trainer_group_partial_fit_set_mixed(mmc_trainer* const* trainers, int count, mmc_featureset* fs,
+                                                       const int64_t* const* visit, const int64_t* const* partner, const float* const* lam,
+                                                       const int64_t* n, const int* batch_size, double* avg_loss, void* hip_stream)
 {
     if (avg_loss && count >= 1 && count <= MMC_TRAINER_GROUP_MAX)
         for (int m = 0; m < count; ++m) avg_loss[m] = 0.0;
@@ -1012,7 +1420,8 @@ extern "C" int mmc_trainer_group_partial_fit_set(mmc_trainer* const* trainers, i
             if (trainers[o] == trainers[m]) return mmc_fail(MMC_ERR_ARG, "member %d is the same trainer as member %d", m, o);
     }
     if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
-    return set_pass(true, trainers, count, fs, visit, n, batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
+    if (!partner != !lam) return mmc_fail(MMC_ERR_ARG, "partner and lam go together: only %s was given", partner ? "partner" : "lam");
+    return set_pass(true, trainers, count, fs, visit, partner, lam, n, batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
 }
 
 extern "C" int mmc_trainer_get_params(mmc_trainer* t, float* const* W, float* const* b)
@@ -1137,6 +1546,45 @@ extern "C" int mmc_trainer_loss_gradient(mmc_trainer* t, const float* logits, co
     CeGroup g;
     g.d[0] = ce_desc(t, t->H[L], static_cast<const int32_t*>(yd), mb, (float)(1.0 / wsum));
     hipLaunchKernelGGL(ce_grad_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
+    T_TRY(hipGetLastError());
+    T_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
+    T_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
+    T_TRY(hipStreamSynchronize(st));
+    return MMC_OK;
+}
+
+// mmc_trainer_loss_gradient for the mixed instantiation: two targets per row and one lam for all rows (include/mmc.h, "regularisers")
+extern "C" int mmc_trainer_loss_gradient_mixed(mmc_trainer* t, const float* logits, const int32_t* y, const int32_t* y2, float lam, int64_t n,
+                                               float* dlogits, float* row_loss, void* hip_stream)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!logits || !y || !y2 || !dlogits || !row_loss) return mmc_fail(MMC_ERR_ARG, "logits / y / y2 / dlogits / row_loss is NULL");
+    if (n < 1 || n > kTrainerForwardRows) return mmc_fail(MMC_ERR_ARG, "n = %lld outside [1, %d]", (long long)n, kTrainerForwardRows);
+    if (!(lam >= 0.f && lam <= 1.f)) return mmc_fail(MMC_ERR_ARG, "lam = %g outside [0, 1]", (double)lam);
+    const float oml = 1.0f - lam;
+    double wsum = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (y[i] < 0 || y[i] >= t->K) return mmc_fail(MMC_ERR_ARG, "label index y[%lld] = %d outside [0, %d)", (long long)i, y[i], t->K);
+        if (y2[i] < 0 || y2[i] >= t->K) return mmc_fail(MMC_ERR_ARG, "label index y2[%lld] = %d outside [0, %d)", (long long)i, y2[i], t->K);
+        wsum += (double)lam * (t->cw ? (double)t->cw_host[y[i]] : 1.0) + (double)oml * (t->cw ? (double)t->cw_host[y2[i]] : 1.0);
+    }
+    if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "the rows have zero total mixed class weight");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    T_TRY(hipSetDevice(t->device));
+    const int mb = (int)n, L = t->L;
+    int r = trainer_reserve(t, 0, mb, 1);
+    if (r) return r;
+    void* yd = nullptr;
+    if ((r = trainer_scratch(t, (size_t)mb * 8, &yd))) return r;
+    int32_t* y1d = static_cast<int32_t*>(yd);
+    int32_t* y2d = y1d + mb;
+    const size_t cells = (size_t)mb * t->K;
+    T_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
+    T_TRY(hipMemcpyAsync(y1d, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
+    T_TRY(hipMemcpyAsync(y2d, y2, (size_t)mb * 4, hipMemcpyHostToDevice, st));
+    CeMixGroup g;
+    g.d[0] = CeMixDesc{t->H[L], y1d, y2d, t->cw, t->dZ[L], t->row_loss, mb, t->K, (float)(1.0 / wsum), lam, oml, trainer_ce_loss(t)};
+    hipLaunchKernelGGL(ce_grad_mixed_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
     T_TRY(hipGetLastError());
     T_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
     T_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));

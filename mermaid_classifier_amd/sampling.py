@@ -11,6 +11,8 @@ registry.py:53-181``): ``stratified``, ``balanced``            min_per_class)``
 ``TrainingDataset._apply_subsample`` (``training/              ``subsample_rows(labels, targets, order)``: the first
 dataset.py:222-347``; ``_rn <= target_n``, :292-310)           ``target`` rows of each class in primary-key order
 one epoch's batches over the kept rows                         ``row_batches(rows, batch_size)`` -> ``SweepConfig.batches``
+(none: Zhang et al. 2018, mixup)                               ``mixup_plan(visit, batch_size, alpha, rng)`` -> the plan of
+                                                               ``mmc_trainer_partial_fit_set_mixed``
 =============================================================  ==========================================================
 
 A balancing configuration of ``docs/research/balancing-experiments.md`` is a class-weight dict, a subsample, or both, over one
@@ -26,7 +28,7 @@ import numpy as np
 
 from .featureset import FeatureSet
 
-__all__ = ["class_counts", "effective_number_weights", "logit_adjustment", "subsample_targets", "subsample_rows", "row_batches", "STRATEGIES"]
+__all__ = ["class_counts", "effective_number_weights", "logit_adjustment", "subsample_targets", "subsample_rows", "row_batches", "mixup_plan", "STRATEGIES"]
 
 STRATEGIES = ("stratified", "balanced")
 
@@ -189,3 +191,27 @@ def row_batches(rows, batch_size: int) -> Callable[[int], Iterable[np.ndarray]]:
         for first in range(0, len(rows), size):
             yield rows[first:first + size]
     return batches
+
+
+def mixup_plan(visit, batch_size: int, alpha: float, rng: np.random.Generator):
+    """The mixing plan of one pass over the rows ``visit`` (row indices of a ``FeatureSet`` in visiting order) in mini-batches of
+    ``batch_size``: -> ``(partner, lam)``.  ``partner`` (int64, one per position) is, within each mini-batch, a permutation of that
+    mini-batch's visited rows, so a row is mixed with a row of its own mini-batch (Zhang et al. 2018 mix a batch with a shuffle of
+    itself); ``lam`` (float32, one per mini-batch) is drawn from Beta(alpha, alpha).  Both come from ``rng`` alone."""
+    visit = np.ascontiguousarray(np.asarray(visit, dtype=np.int64))
+    if visit.ndim != 1 or visit.size < 1:
+        raise ValueError(f"visit must be a non-empty 1D array of row indices, got shape {visit.shape}")
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size!r}")
+    if not (float(alpha) > 0.0 and np.isfinite(float(alpha))):
+        raise ValueError(f"alpha must be a finite number > 0, got {alpha!r}")
+    n = int(visit.size)
+    mb = min(int(batch_size), n)
+    steps = -(-n // mb)
+    partner = np.empty(n, dtype=np.int64)
+    lam = np.empty(steps, dtype=np.float32)
+    for s in range(steps):
+        rows = visit[s * mb:(s + 1) * mb]
+        partner[s * mb:s * mb + rows.size] = rows[rng.permutation(rows.size)]
+        lam[s] = np.float32(rng.beta(float(alpha), float(alpha)))
+    return partner, lam

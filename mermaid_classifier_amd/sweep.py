@@ -90,14 +90,21 @@ def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, r
     for first in range(0, len(clfs), _lib.MMC_TRAINER_GROUP_MAX):
         group = clfs[first:first + _lib.MMC_TRAINER_GROUP_MAX]
         passes = [clf._begin_rows_pass(fs, r, classes) for clf, r in zip(group, entries[first:])]
+        plans = [clf._mix_plan(v, n_m, b_m) for clf, (v, n_m, b_m) in zip(group, passes)]     # (visit, partner, lam) per member
         count = len(group)
         handles = (C.c_void_p * count)(*[clf._h.value for clf in group])
-        visit = (C.c_void_p * count)(*[None if v is None else v.ctypes.data for v, _, _ in passes])
+        visit = (C.c_void_p * count)(*[None if v is None else v.ctypes.data for v, _, _ in plans])
         n = (C.c_int64 * count)(*[int(p[1]) for p in passes])
         batch = (C.c_int * count)(*[int(p[2]) for p in passes])
         avg = (C.c_double * count)()
-        _lib.check(lib.mmc_trainer_group_partial_fit_set(handles, count, fs._handle(), visit, n, batch, avg,
-                                                         _current_stream_ptr(fs.device_index)))
+        if all(partner is None for _, partner, _ in plans):
+            _lib.check(lib.mmc_trainer_group_partial_fit_set(handles, count, fs._handle(), visit, n, batch, avg,
+                                                             _current_stream_ptr(fs.device_index)))
+        else:                                                 # a member without mixup keeps a NULL pair: it is not mixed
+            partner = (C.c_void_p * count)(*[None if q is None else q.ctypes.data for _, q, _ in plans])
+            lam = (C.c_void_p * count)(*[None if w is None else w.ctypes.data for _, _, w in plans])
+            _lib.check(lib.mmc_trainer_group_partial_fit_set_mixed(handles, count, fs._handle(), visit, partner, lam, n, batch, avg,
+                                                                   _current_stream_ptr(fs.device_index)))
         for clf, a in zip(group, avg):
             clf._end_pass(a)
     return clfs
@@ -110,7 +117,8 @@ class SweepConfig:
     ``epoch -> iterable of row-index arrays`` into the train set, e.g. a class-balancing subsample; None takes contiguous
     slices of ``train_sweep``'s ``batch_size`` rows.  ``label_smoothing`` / ``focal_gamma`` / ``logit_prior`` are the classifier's loss
     formulation (``mmc_trainer_set_loss``): the members of one grouped pass may each have their own.  ``logit_scaling`` (keyword only)
-    is ``train_classifier``'s argument of that name for this configuration."""
+    is ``train_classifier``'s argument of that name for this configuration.  ``dropout`` / ``input_dropout`` / ``mixup_alpha`` /
+    ``regularizer_seed`` are the classifier's regularisers, again per member."""
     hidden_layer_sizes: Tuple[int, ...] = (500, 300, 100)
     learning_rate_init: float = 1e-4
     alpha: float = 1e-4
@@ -123,6 +131,11 @@ class SweepConfig:
     # keyword-only, so it takes no positional slot: a kind string or a fitted LogitScaling, fitted on ref after training and folded
     # before calibrate (train_sweep's logit_scaling= for one configuration); not a classifier argument
     logit_scaling: Any = field(default=None, kw_only=True)
+    # the classifier's regularisers (mmc_trainer_set_dropout, sampling.mixup_plan): keyword only, as in its constructor
+    dropout: float = field(default=0.0, kw_only=True)
+    input_dropout: float = field(default=0.0, kw_only=True)
+    mixup_alpha: float = field(default=0.0, kw_only=True)
+    regularizer_seed: Optional[int] = field(default=None, kw_only=True)
     batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None
     label_smoothing: float = 0.0
     focal_gamma: float = 0.0
@@ -134,7 +147,8 @@ class SweepConfig:
                                   alpha=self.alpha, class_weight=self.class_weight, random_state=self.random_state,
                                   batch_size=self.batch_size, beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.epsilon,
                                   device=device, label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma,
-                                  logit_prior=self.logit_prior)
+                                  logit_prior=self.logit_prior, dropout=self.dropout, input_dropout=self.input_dropout,
+                                  mixup_alpha=self.mixup_alpha, regularizer_seed=self.regularizer_seed)
 
 
 def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[Any]]],

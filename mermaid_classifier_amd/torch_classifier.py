@@ -21,7 +21,9 @@ logits call (``mmc_trainer_logits``), ``parameters`` / ``_module`` / ``_adam_sta
 ``partial_fit_rows`` (``partial_fit`` over rows of a device-resident ``FeatureSet``: ``mmc_trainer_partial_fit_set``) and its
 two halves ``_begin_rows_pass`` / ``_end_pass``, which ``sweep.partial_fit_rows_group`` puts around one grouped call; and the loss
 formulation -- ``label_smoothing`` / ``focal_gamma`` / ``logit_prior``, ``_check_loss_scalars``, ``_build_logit_prior_vector``
-(``mmc_trainer_set_loss``) -- whose defaults are the reference's weighted cross-entropy.
+(``mmc_trainer_set_loss``) -- whose defaults are the reference's weighted cross-entropy; and the regularisers -- ``dropout`` /
+``input_dropout`` / ``mixup_alpha`` / ``regularizer_seed``, ``_check_regularizers``, ``_regularizer_seed_value``, ``_mix_plan``
+(``mmc_trainer_set_dropout``, ``mmc_trainer_partial_fit_set_mixed``) -- whose defaults leave the step as it is.
 """
 
 from __future__ import annotations
@@ -54,13 +56,33 @@ def _check_loss_scalars(label_smoothing, focal_gamma) -> None:
         raise ValueError(f"focal_gamma must be 0 or lie in [1, 8], got {focal_gamma!r}.")
 
 
+def _check_regularizers(dropout, input_dropout, mixup_alpha, regularizer_seed) -> None:
+    """The ranges ``mmc_trainer_set_dropout`` accepts (include/mmc.h), a non-negative finite ``mixup_alpha`` and a seed of 64 bits."""
+    for name, p in (("dropout", dropout), ("input_dropout", input_dropout)):
+        if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 0.9:
+            raise ValueError(f"{name} must lie in [0, 0.9], got {p!r}.")
+    if isinstance(mixup_alpha, bool) or not isinstance(mixup_alpha, (int, float, np.integer, np.floating)) \
+            or not (0.0 <= float(mixup_alpha) and np.isfinite(float(mixup_alpha))):
+        raise ValueError(f"mixup_alpha must be a finite number >= 0, got {mixup_alpha!r}.")
+    if regularizer_seed is not None and (isinstance(regularizer_seed, bool) or not isinstance(regularizer_seed, (int, np.integer))
+                                         or not 0 <= int(regularizer_seed) < 2 ** 64):
+        raise ValueError(f"regularizer_seed must be None or an integer in [0, 2**64), got {regularizer_seed!r}.")
+
+
 class TorchMLPClassifier:
     """See the module docstring; argument meaning as in the reference (torch_classifier.py:93-135).  Three arguments have no
     counterpart there, the loss formulation of ``mmc_trainer_set_loss`` (include/mmc.h): ``label_smoothing`` in [0, 1) with
     ``F.cross_entropy(label_smoothing=)``'s meaning, ``focal_gamma`` (0, or in [1, 8]: focal loss) and ``logit_prior``, a dict from
     label to a finite offset added to the logits inside the loss only (``sampling.logit_adjustment``); like ``class_weight`` it is
     resolved in ``classes_`` order at the first fit.  Training alone reads them: ``predict_proba``, evaluation, calibration and
-    export see the raw logits.  The defaults train with the plain loss, bit for bit."""
+    export see the raw logits.  The defaults train with the plain loss, bit for bit.
+
+    Four more, keyword only, are the regularisers of include/mmc.h: ``dropout`` on the hidden activations and ``input_dropout`` on the
+    feature rows (each in [0, 0.9]; ``mmc_trainer_set_dropout``, on every training path), ``mixup_alpha`` > 0 mixes every row of a
+    ``partial_fit_rows`` pass with a partner of its mini-batch, ``lam ~ Beta(alpha, alpha)`` per mini-batch (``sampling.mixup_plan``;
+    the host-fed ``partial_fit`` raises), and ``regularizer_seed`` seeds both (None: ``random_state``, or one draw from numpy's global
+    RNG when that is None too).  Read when the trainer is created, like every other hyper-parameter.  Training alone sees them; the
+    defaults leave every pass as it is, bit for bit."""
 
     _estimator_type = "classifier"
 
@@ -69,12 +91,14 @@ class TorchMLPClassifier:
                  max_iter: int = 200, shuffle: bool = True, random_state: int | None = None, tol: float = 1e-4,
                  beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-8,
                  class_weight: dict | None = None, device=0, *, label_smoothing: float = 0.0, focal_gamma: float = 0.0,
-                 logit_prior: dict | None = None):
+                 logit_prior: dict | None = None, dropout: float = 0.0, input_dropout: float = 0.0, mixup_alpha: float = 0.0,
+                 regularizer_seed: int | None = None):
         if activation != "relu":
             raise ValueError(f"TorchMLPClassifier only supports activation='relu', got {activation!r}.")
         if solver != "adam":
             raise ValueError(f"TorchMLPClassifier only supports solver='adam', got {solver!r}.")
         _check_loss_scalars(label_smoothing, focal_gamma)
+        _check_regularizers(dropout, input_dropout, mixup_alpha, regularizer_seed)
         self.hidden_layer_sizes = tuple(hidden_layer_sizes)
         self.activation = activation
         self.solver = solver
@@ -93,6 +117,10 @@ class TorchMLPClassifier:
         self.label_smoothing = label_smoothing
         self.focal_gamma = focal_gamma
         self.logit_prior = logit_prior
+        self.dropout = dropout
+        self.input_dropout = input_dropout
+        self.mixup_alpha = mixup_alpha
+        self.regularizer_seed = regularizer_seed
 
     # ---- host bookkeeping, restated from the reference ------------------------------------------------------------
     def _resolve_batch_size(self, n_samples: int) -> int:
@@ -178,15 +206,43 @@ class TorchMLPClassifier:
         try:
             _lib.check(lib.mmc_trainer_set_loss(self._h, float(self.label_smoothing), float(self.focal_gamma),
                                                 prior.ctypes.data_as(C.POINTER(C.c_float)) if prior is not None else None))
+            if float(self.dropout) != 0.0 or float(self.input_dropout) != 0.0:
+                _lib.check(lib.mmc_trainer_set_dropout(self._h, float(self.input_dropout), float(self.dropout),
+                                                       self._regularizer_seed_value()))
         except Exception:
             self._release()
             raise
+
+    def _regularizer_seed_value(self) -> int:
+        """The seed of the dropout masks and the mixing plans: ``regularizer_seed``, else ``random_state``, else one draw from numpy's
+        global RNG, kept (and pickled) so that a classifier keeps one mask sequence for its lifetime."""
+        if self.regularizer_seed is not None:
+            return int(self.regularizer_seed)
+        if self.random_state is not None:
+            return int(self.random_state) % 2 ** 64
+        if getattr(self, "_regularizer_seed_drawn", None) is None:
+            self._regularizer_seed_drawn = int(np.random.randint(0, np.iinfo(np.int32).max))
+        return self._regularizer_seed_drawn
+
+    def _mix_plan(self, visit, n_samples: int, batch_size: int):
+        """The mixing plan of the pass ``_begin_rows_pass`` has just begun -> ``(visit, partner, lam)``, partner and lam None without
+        mixup.  The plan's generator is ``default_rng([seed, n_iter_])``: epochs differ even with a fixed ``random_state``."""
+        if float(self.mixup_alpha) == 0.0:
+            return visit, None, None
+        from .sampling import mixup_plan
+        if visit is None:
+            visit = np.arange(n_samples, dtype=np.int64)
+        rng = np.random.default_rng([self._regularizer_seed_value(), int(self.n_iter_)])
+        partner, lam = mixup_plan(visit, batch_size, float(self.mixup_alpha), rng)
+        return visit, partner, lam
 
     def _fitted(self) -> bool:
         return getattr(self, "_h", None) is not None and bool(self._h.value)
 
     # ---- training ------------------------------------------------------------------------------------------------
     def partial_fit(self, X, y, classes: Sequence[Any] | None = None) -> "TorchMLPClassifier":
+        if float(getattr(self, "mixup_alpha", 0.0)) != 0.0:
+            raise ValueError("mixup_alpha > 0 mixes rows of a resident FeatureSet: train with partial_fit_rows, not partial_fit.")
         X_arr = np.asarray(X, dtype=np.float32)
         if X_arr.ndim != 2:
             raise ValueError(f"X must be 2D, got shape {X_arr.shape}")
@@ -233,9 +289,15 @@ class TorchMLPClassifier:
         ``classes_`` and ``fs.dim`` ``n_features_in_`` (``ValueError``); on a first call without ``classes`` the set's class list
         is taken (``partial_fit`` would take the labels present in the rows)."""
         visit, n_samples, batch_size = self._begin_rows_pass(fs, rows, classes)
+        visit, partner, lam = self._mix_plan(visit, n_samples, batch_size)
         avg = C.c_double(0.0)
-        _lib.check(_lib.lib().mmc_trainer_partial_fit_set(self._h, fs._handle(), None if visit is None else visit.ctypes.data, n_samples,
-                                                          int(batch_size), C.byref(avg), _current_stream_ptr(_device_index(self.device))))
+        if partner is None:
+            _lib.check(_lib.lib().mmc_trainer_partial_fit_set(self._h, fs._handle(), None if visit is None else visit.ctypes.data, n_samples,
+                                                              int(batch_size), C.byref(avg), _current_stream_ptr(_device_index(self.device))))
+        else:
+            _lib.check(_lib.lib().mmc_trainer_partial_fit_set_mixed(self._h, fs._handle(), visit.ctypes.data, partner.ctypes.data,
+                                                                    lam.ctypes.data, n_samples, int(batch_size), C.byref(avg),
+                                                                    _current_stream_ptr(_device_index(self.device))))
         self._end_pass(avg.value)
         return self
 
@@ -385,7 +447,8 @@ class TorchMLPClassifier:
                 "max_iter": self.max_iter, "shuffle": self.shuffle, "random_state": self.random_state, "tol": self.tol,
                 "beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon,
                 "class_weight": getattr(self, "class_weight", None), "label_smoothing": self.label_smoothing,
-                "focal_gamma": self.focal_gamma, "logit_prior": self.logit_prior}
+                "focal_gamma": self.focal_gamma, "logit_prior": self.logit_prior, "dropout": self.dropout,
+                "input_dropout": self.input_dropout, "mixup_alpha": self.mixup_alpha, "regularizer_seed": self.regularizer_seed}
 
     def set_params(self, **params: Any) -> "TorchMLPClassifier":
         for key, value in params.items():
@@ -407,7 +470,9 @@ class TorchMLPClassifier:
         opt = state.pop("_optimizer_state", None)
         self.__dict__.update(state)
         # a pickle made before the loss options existed loads as the plain loss
-        for key, default in (("label_smoothing", 0.0), ("focal_gamma", 0.0), ("logit_prior", None), ("_logit_prior_vector", None)):
+        # ... and one made before the regularisers existed as a classifier without them
+        for key, default in (("label_smoothing", 0.0), ("focal_gamma", 0.0), ("logit_prior", None), ("_logit_prior_vector", None),
+                             ("dropout", 0.0), ("input_dropout", 0.0), ("mixup_alpha", 0.0), ("regularizer_seed", None)):
             self.__dict__.setdefault(key, default)
         self._h = None
         if params is not None:
