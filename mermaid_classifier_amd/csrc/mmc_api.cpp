@@ -193,8 +193,8 @@ struct BlockW {
     PwLayer expand, project;                  // pw_gemm image + padded bias
     float *dw_w = nullptr, *dw_b = nullptr;   // tap-major fp32 taps [k*k][ce], bias [ce]
     float* se_be = nullptr;                   // excite bias [ce]
-    // ---- the launch arguments of the planned kernels: weights and constant scalars, bound at create time (bind_*); forward_lane
-    // copies the struct and sets the buffers and the batch ----
+    // ---- the launch arguments of the planned kernels: weights and constant scalars, bound at create time (bind_*); build_lane
+    // copies the struct into the lane's launch list and sets the buffers ----
     MbtArgs mbt{};         // Front::Mbt
     Mid14Args mid{};       // Front::Mid14
     Mb1Args mb1{};         // Front::Mb1; Front::MbPre passes its pre_w / pre_b next to `mb`
@@ -301,6 +301,34 @@ struct Saved {
     bool is_half = true;
 };
 
+// ------------------------------------------------------------------------------------------
+// the launch list: one entry per kernel launch of a lane's pass, in stream order.  build_lane writes it once, at the end of
+// create; forward_lane replays it and fills in only what depends on the call (the batch, the pass's two end pointers).
+// ------------------------------------------------------------------------------------------
+enum class Op { Stem, StemDw, Mbt, Mid14, Mb1, MbA, MbD, MbPre, Gemm, ThinProj, GemmFp8, Dw, SeWide, SeSmall, SeFused, ProjPatch, Chain14, Tail7 };
+// the launchers without an argument struct in kernels.h: what they take besides the handle's stem weights, the batch and the stream
+struct StemArgs { const float *wdw, *bdw; _Float16* out; float* pool; };   // launch_stem (out), launch_stem_dw (all four)
+struct SeLaunch { const float* pool; int nparts, C; SeArgs w; float* gate; };
+struct MbPreArgs { MbArgs mb; const _Float16* pre_w; const float *pre_b, *pre_gate; };
+// a tensor per-tensor mode (MMC_KEEP_ACTIVATIONS=1) copies out after the launch
+struct KeptTensor { std::string name; const void* dev; size_t per_patch; bool is_half; };
+struct Launch {
+    std::string name;                         // as mmc_backbone_profile reports it, before the '|'
+    const char* label[2] = {nullptr, nullptr};   // ... and behind it; a pw_gemm launch has one per mt (gemm_mt), every other the same twice
+    Op op = Op::Stem;
+    const PwLayer* layer = nullptr;           // Gemm: the layer gemm_mt asks
+    int rows = 0;                             // Gemm, ThinProj, GemmFp8: rows per patch (M = n * rows)
+    bool planar = false;                      // ThinProj: X comes as 32-channel planes of n * rows rows
+    bool features = false;                    // Gemm, Tail7: writes the pass's features (Stem and StemDw read the pass's patches)
+    unsigned mid_phases = 0;                  // Chain14: bit p set when phase p is a mid14m body (clear: proj_patch); each carries its own B
+    union Args {
+        StemArgs stem; MbtArgs mbt; Mid14Args mid; Mb1Args mb1; MbArgs mb; MbPreArgs pre; GemmArgs gemm; Fp8GemmArgs fp8; DwArgs dw;
+        SeLaunch se; ProjPatchArgs pp; Chain14Args chain; TailArgs tail;
+        Args() { memset(static_cast<void*>(this), 0, sizeof *this); }
+    } a;                                      // everything but the per-call fields
+    std::vector<KeptTensor> keep;
+};
+
 #define MMC_GRAPH_CACHE 32   // captured (input, output, n) combinations kept per handle
 
 struct mmc_backbone {
@@ -319,8 +347,10 @@ struct mmc_backbone {
         float *pool_part = nullptr, *gate = nullptr;
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;
+        std::vector<Launch> list;   // this lane's pass (build_lane); immutable after create
     };
     Lane lanes[4];
+    size_t cap_act = 0, cap_exp = 0, cap_dw = 0, cap_pool = 0, cap_gate = 0;   // elements per patch of each lane buffer (create, step 4)
     // optional (MMC_GRAPH=1): a pass over device-resident buffers is captured once per (input, output, n) into a HIP graph
     // and replayed -- the ~20 launches per lane then cost one graph launch
     // (least recently used entry evicted beyond MMC_GRAPH_CACHE combinations)
@@ -350,7 +380,7 @@ struct mmc_backbone {
     bool fuse_b0b1 = false;          // block 0's SE scale + project conv folded into block 1's kernel: no b0 output tensor
     TailRoute tail = TailRoute::None;
     int chain_first = -1, chain_last = -1;   // b<first>.projse .. b<last>.projse run as ONE chain14_kernel launch (-1: separate launches)
-    int chain_cout = 0, chain_ce = 0;        // ... the widest block output / expanded tensor among them (see forward_lane)
+    int chain_cout = 0, chain_ce = 0;        // ... the widest block output / expanded tensor among them (see build_lane)
     bool fp8 = false;                // MMC_PRECISION_FP8: project convs of the narrow late blocks on e4m3 MFMA operands
     float* dbg_clk = nullptr;        // keep mode: per-patch phase cycle counts of the patch-resident kernels
     float* mid_clk = nullptr;        // MMC_TAIL_CLK=1: [max_batch][8 workgroups][16] phase cycle counts of block 10's mid14 launch
@@ -384,7 +414,7 @@ struct PassOrder {
     }
 };
 
-struct ProfEntry { std::string name; hipEvent_t e0, e1; };
+struct ProfEntry { const Launch* launch; int mt; hipEvent_t e0, e1; };   // reported as name|label[mt - 1]
 struct Prof { std::vector<ProfEntry> entries; };
 
 template <typename T>
@@ -809,6 +839,240 @@ static int bind_net(mmc_backbone* bb, const RawNet& raw)
 }
 #undef BIND
 
+// ------------------------------------------------------------------------------------------
+// the launch list of lane `lane_idx`, from the plan's enums and the bound structs, once the workspace is allocated: which buffer every
+// launch reads and writes (the x / y ping-pong of the block outputs resolved), the names, and what per-tensor mode keeps
+// ------------------------------------------------------------------------------------------
+static int build_lane(mmc_backbone* bb, int lane_idx)
+{
+    mmc_backbone::Lane& ws = bb->lanes[lane_idx];
+    std::vector<Launch>& list = ws.list;
+    const size_t lc = (size_t)bb->lane_cap;
+    int err = 0;
+    auto add = [&](const std::string& name, const char* label, Op op) -> Launch& {
+        list.emplace_back();
+        Launch& L = list.back();
+        L.name = name; L.label[0] = L.label[1] = label; L.op = op;
+        return L;
+    };
+    auto add_gemm = [&](const std::string& name, const PwLayer& P, const GemmArgs& a, int rows) -> GemmArgs& {
+        Launch& L = add(name, P.label[0], Op::Gemm);
+        L.label[1] = P.label[1]; L.layer = &P; L.rows = rows; L.a.gemm = a;
+        return L.a.gemm;
+    };
+    auto bn = [](int i, const char* what) { return "b" + std::to_string(i) + what; };
+    // The last entry writes `per_patch` elements per patch at p: with lane_cap patches that must end inside the lane buffer p lies in
+    // (step 4 of create sized the buffers from per-block maxima; this ties those sizes to what is launched).  Under a name, per-tensor
+    // mode copies the tensor out behind the launch.
+    auto writes = [&](auto* p, size_t per_patch, const std::string& keep_as = std::string()) {
+        if (bb->keep && !keep_as.empty()) list.back().keep.push_back({keep_as, p, per_patch, sizeof(*p) == 2});
+        const struct { const char* name; const void* base; size_t bytes; } bufs[] = {
+            {"act0", ws.act0, lc * bb->cap_act * 2}, {"act1", ws.act1, lc * bb->cap_act * 2}, {"expbuf", ws.expbuf, lc * bb->cap_exp * 2},
+            {"dwbuf", ws.dwbuf, lc * bb->cap_dw * 2}, {"pool_part", ws.pool_part, lc * bb->cap_pool * 4}, {"gate", ws.gate, lc * bb->cap_gate * 4}};
+        const char* b = reinterpret_cast<const char*>(p);
+        const size_t bytes = lc * per_patch * sizeof(*p);
+        for (const auto& f : bufs) {
+            const char* base = static_cast<const char*>(f.base);
+            if (b < base || b >= base + f.bytes) continue;
+            if (!err && b + bytes > base + f.bytes)
+                err = fail(MMC_ERR_ARG, "launch %s writes %zu bytes at offset %zu of lane buffer %s, which holds %zu", list.back().name.c_str(),
+                           bytes, (size_t)(b - base), f.name, f.bytes);
+            return;
+        }
+        if (!err) err = fail(MMC_ERR_ARG, "launch %s writes outside every lane buffer", list.back().name.c_str());
+    };
+    _Float16 *x = ws.act0, *y = ws.act1;   // the block's input, and where its output goes
+    // The chained launch: its members' arguments are collected in launch order into ONE entry.  Its workgroups are NOT in step: while
+    // workgroup b writes a phase's output, another may still be reading an earlier phase's input.  A buffer's patch b starts at
+    // b x (pixels x row width), so two tensors of different row width in one buffer overlap ACROSS patches -- between separate launches
+    // that is harmless, inside the chain it is a race.  So a chained tensor whose row width differs from what its buffer holds when the
+    // chain starts (block ch0's widths) lives in the buffer's upper part, beyond lane_cap patches of the widest tensor: every region
+    // then holds ONE row width, and a workgroup only ever touches its own patch's rows of it.
+    const int ch0 = bb->chain_first, ch1 = bb->chain_last;
+    const size_t ch_hw = ch0 >= 0 ? (size_t)bb->blk[ch0].Ho * bb->blk[ch0].Ho : 0;
+    auto ch_act = [&](_Float16* base, int cout) { return base + (cout == bb->blk[ch0].d.cout ? 0 : lc * ch_hw * bb->chain_cout); };
+    auto ch_dw = [&](int ce) { return ws.dwbuf + (ce == bb->blk[ch0].ce ? 0 : lc * ch_hw * bb->chain_ce); };
+    auto ch_pool = [&](int ce) { return ws.pool_part + (ce == bb->blk[ch0].ce ? 0 : lc * bb->chain_ce); };
+    _Float16 *xbase = nullptr, *ybase = nullptr;   // inside the chain: the buffers x and the next output live in
+    if (!bb->fuse_stem) {   // (fused: the stem tensor never exists in HBM, no "stem" activation to keep)
+        add("stem", "stem_conv", Op::Stem).a.stem.out = x;
+        writes(x, (size_t)112 * 112 * bb->stem_ch, "stem");
+    }
+    for (int i = 0; i < bb->nblk; ++i) {
+        const BlockW& B = bb->blk[i];
+        if (B.front == Front::Tail) break;
+        const int HWi = B.H * B.H, HWo = B.Ho * B.Ho;
+        const bool chained = ch0 >= 0 && i >= ch0 && i <= ch1;   // its back half is a phase of the chain, and behind ch0 its front half too
+        // ---- front half: the depthwise output D and its pool partials ----
+        // with block 0's project folded into block 1's kernel block 0's depthwise output goes to the spare activation buffer (block 1
+        // reads it while writing its own depthwise output to dwbuf)
+        _Float16* D = (i == 0 && bb->fuse_b0b1) ? y : (chained && i > ch0) ? ch_dw(B.ce) : ws.dwbuf;
+        float* pool = (chained && i > ch0) ? ch_pool(B.ce) : ws.pool_part;
+        switch (B.front) {
+        case Front::StemDw: add("stem+b0.dw", "stem_dw", Op::StemDw).a.stem = {B.dw_w, B.dw_b, D, pool}; break;
+        case Front::Mbt: {
+            MbtArgs& a = add(bn(i, ".mbconv"), B.front_label, Op::Mbt).a.mbt = B.mbt;
+            a.X = x; a.D = D; a.pool = pool;
+            break;
+        }
+        case Front::Mid14: {
+            Mid14Args a = B.mid;
+            a.X = x; a.D = D; a.pool = pool;
+            if (bb->mid_clk && i == 10) a.dbg_clk = bb->mid_clk + (size_t)lane_idx * lc * 128;   // debug clock: rows of this lane's patches
+            if (chained && i > ch0) {   // a phase of the chain entry
+                Chain14Args& ca = list.back().a.chain;
+                list.back().mid_phases |= 1u << ca.nph;
+                ca.ph[ca.nph].kind = chain14_mid_kind(a.Cin, a.ks, a.Ce);
+                ca.ph[ca.nph++].mid = a;
+            } else
+                add(bn(i, ".mbconv"), B.front_label, Op::Mid14).a.mid = a;
+            break;
+        }
+        case Front::Mb1: {   // reads block 0's depthwise output (in y: no swap behind Back::SeFolded) and its gate
+            Mb1Args& a = add("b0.project+b1.mbconv", "mb1", Op::Mb1).a.mb1 = B.mb1;
+            a.X = y; a.pre_gate = ws.gate; a.D = D; a.pool = pool;
+            break;
+        }
+        case Front::MbPre: {   // ... the same on mbconv_a_kernel PRE
+            MbPreArgs& a = add("b0.project+b1.mbconv", B.front_label, Op::MbPre).a.pre = {B.mb, B.mb1.pre_w, B.mb1.pre_b, ws.gate};
+            a.mb.X = y; a.mb.out = D; a.mb.pool_part = pool;
+            break;
+        }
+        case Front::MbD: case Front::MbA: {
+            MbArgs& a = add(bn(i, ".mbconv"), B.front_label, B.front == Front::MbD ? Op::MbD : Op::MbA).a.mb = B.mb;
+            a.X = x; a.out = D; a.pool_part = pool;
+            break;
+        }
+        case Front::Unfused: {
+            const _Float16* dw_in = x;
+            if (B.has_expand) {
+                GemmArgs& g = add_gemm(bn(i, ".expand"), B.expand, B.exp_gemm, HWi);
+                g.X = x; g.Y = ws.expbuf;
+                writes(ws.expbuf, (size_t)HWi * B.ce, bn(i, ".expand"));
+                dw_in = ws.expbuf;
+            }
+            DwArgs& d = add(bn(i, ".dw"), B.front_label, Op::Dw).a.dw = B.dw;
+            d.in = dw_in; d.out = D; d.pool_part = pool;
+            break;
+        }
+        case Front::Tail: break;
+        }
+        writes(D, (size_t)HWo * B.ce, bn(i, ".dw"));
+        writes(pool, (size_t)B.nparts * B.ce);
+        // ---- back half ----
+        if (B.back == Back::Tail) break;   // block 11's back half: the tail launch below
+        if (B.back == Back::ProjPatch) {
+            // squeeze-excite + project, one patch per workgroup (proj_patch_kernel): no gate tensor, one launch
+            ProjPatchArgs pa = B.pp;
+            pa.X = D; pa.pool_part = pool; pa.res = B.skip ? x : nullptr; pa.Y = y;
+            pa.dbg_gate = bb->keep ? ws.gate : nullptr;
+            pa.dbg_clk = bb->keep ? bb->dbg_clk : nullptr;
+            if (chained) {
+                if (i == ch0) {
+                    xbase = x; ybase = y;
+                    add(bn(ch0, ".projse-") + bn(ch1, ".projse.chain"), "chain14", Op::Chain14);
+                }
+                pa.Y = ch_act(ybase, B.d.cout);
+                Chain14Args& ca = list.back().a.chain;
+                ca.ph[ca.nph].kind = chain14_proj_kind(pa.K, pa.N, pa.HW, pa.res ? 1 : 0);
+                ca.ph[ca.nph++].pp = pa;
+                writes(pa.Y, (size_t)HWo * B.d.cout);
+                x = pa.Y;
+                std::swap(xbase, ybase);
+                y = ybase;   // (after the chain: the other buffer, whose tensors are dead by then)
+                continue;
+            }
+            add(bn(i, ".projse"), B.back_label, Op::ProjPatch).a.pp = pa;
+            writes(ws.gate, (size_t)B.ce, bn(i, ".gate"));   // (per-tensor mode only: dbg_gate)
+            writes(y, (size_t)HWo * B.d.cout, bn(i, ".out"));
+            if (bb->keep) list.back().keep.push_back({bn(i, ".clk"), bb->dbg_clk, 8, false});   // the handle's [max_batch][8], no lane buffer
+            std::swap(x, y);
+            continue;
+        }
+        add(bn(i, ".gate"), B.se == Se::Wide ? "se_wide" : B.se == Se::Small ? "se_small" : "se_fused",
+            B.se == Se::Wide ? Op::SeWide : B.se == Se::Small ? Op::SeSmall : Op::SeFused).a.se = {pool, B.nparts, B.ce, B.sea, ws.gate};
+        writes(ws.gate, (size_t)B.ce, bn(i, ".gate"));
+        if (B.back == Back::SeFolded) continue;  // block 0's project runs inside block 1's kernel
+        const _Float16* res = B.skip ? x : nullptr;
+        if (B.proj == Proj::Fp8) {
+            Fp8GemmArgs& a = add(bn(i, ".project"), "pw_gemm_fp8", Op::GemmFp8).a.fp8 = B.proj8;
+            a.X = D; a.Y = y; a.gate = ws.gate; a.res = res;
+            list.back().rows = HWo;
+        } else {
+            // Proj::Thin: small-K, small-N project on a big image (B4 blocks 0, 1; B0 block 1), one patch's fragments streamed per workgroup
+            GemmArgs& a = add_gemm(bn(i, ".project"), B.project, B.proj_gemm, HWo);
+            a.X = D; a.Y = y; a.gate = ws.gate; a.res = res;
+            if (B.proj == Proj::Thin) {
+                Launch& L = list.back();
+                L.op = Op::ThinProj; L.label[0] = L.label[1] = "thin_proj"; L.planar = B.planar;
+            }
+        }
+        writes(y, (size_t)HWo * B.d.cout, bn(i, ".out"));
+        std::swap(x, y);
+    }
+    // ---- the tail and the head ----
+    // Every tail7 launch starts from the handle's bound TailArgs (block table, block 11's and the head's weights, inv_hw).  The kernel
+    // runs block 11 when pre_D or pre_X is set and the head phase when head_w is: a launch without the head phase clears it.
+    auto add_tail = [&](const std::string& name, bool head) -> TailArgs& {
+        Launch& L = add(name, "tail7", Op::Tail7);
+        L.features = head;
+        L.a.tail = bb->tail_args;
+        if (!head) L.a.tail.head_w = nullptr;
+        return L.a.tail;
+    };
+    if (bb->tail == TailRoute::B11All || (bb->tail == TailRoute::B11 && !bb->keep)) {
+        // from block 11's input (B11All) or its depthwise output (B11) through blocks 12..15 and the head conv to the features, ONE launch
+        TailArgs& ta = add_tail(bb->tail == TailRoute::B11All ? "b11all-head.tail" : "b11-head.tail", true);
+        ta.nblk = 4;
+        if (bb->tail == TailRoute::B11All) {
+            ta.pre_X = x;
+        } else {
+            ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part;
+        }
+        if (bb->tail == TailRoute::B11All && bb->tail_clk) {   // debug clock: rows of this lane's patches
+            ta.dbg_clk = bb->tail_clk + (size_t)lane_idx * lc * 64; ta.clk_sections = 1;
+        }
+        return err;
+    }
+    if (bb->tail == TailRoute::B11) {   // per-tensor mode: block 11's back half on its own
+        const BlockW& B11 = bb->blk[11];
+        TailArgs& ta = add_tail("b11.tail", false);
+        ta.nblk = 0; ta.Y = y; ta.dbg_gate = ws.gate;
+        ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part;
+        writes(ws.gate, (size_t)B11.ce, "b11.gate");
+        writes(y, (size_t)49 * 192, "b11.out");
+        std::swap(x, y);
+    }
+    if (bb->tail != TailRoute::None && !bb->keep) {
+        // blocks 12..15 in one launch, one patch per workgroup, tensors resident in LDS (tail7_kernel)
+        TailArgs& ta = add_tail("b12-15.tail", false);
+        ta.X = x; ta.Y = y; ta.nblk = 4;
+        writes(y, (size_t)49 * bb->blk[15].d.cout);
+        std::swap(x, y);
+    } else if (bb->tail != TailRoute::None) {
+        for (int j = 12; j < 16; ++j) {   // block at a time so every intermediate tensor can be read back
+            const BlockW& B = bb->blk[j];
+            TailArgs& ta = add_tail(bn(j, ".tail"), false);
+            ta.X = x; ta.Y = y; ta.nblk = 1; ta.blk += j - 12;
+            ta.dbg_dw = ws.dwbuf; ta.dbg_gate = ws.gate; ta.dbg_clk = ws.pool_part;
+            writes(ws.dwbuf, (size_t)49 * B.ce, bn(j, ".dw"));
+            writes(ws.gate, (size_t)B.ce, bn(j, ".gate"));
+            writes(y, (size_t)49 * B.d.cout, bn(j, ".out"));
+            writes(ws.pool_part, 8, bn(j, ".clk"));
+            std::swap(x, y);
+        }
+    }
+    if (bb->tail == TailRoute::B11) {   // per-tensor mode: the head phase of tail7_kernel on its own
+        TailArgs& ta = add_tail("head.tail", true);
+        ta.X = x; ta.nblk = 0; ta.in_wide = 1;
+    } else {
+        const int HWh = bb->blk[bb->nblk - 1].Ho * bb->blk[bb->nblk - 1].Ho;
+        add_gemm("head", bb->head, bb->head_gemm, HWh).X = x;
+        list.back().features = true;
+    }
+    return err;
+}
+
 extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arch, int device, int max_batch, unsigned flags,
                                       mmc_backbone** out)
 {
@@ -905,7 +1169,7 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
             }
             // only the schedule the chain was built and measured for, b7.projse .. b10.projse: any other run (MMC_MID14M=0,
             // MMC_PROJSE=0, ...) stays separate launches
-            // ... whose tensors come in at most two row widths per buffer, the first block's and a wider one (forward_lane places them)
+            // ... whose tensors come in at most two row widths per buffer, the first block's and a wider one (build_lane places them)
             bool two = K[7].skip;
             int cw = K[7].d.cout, ew = K[7].ce;
             for (int i = 8; i <= 10; ++i) { cw = std::max(cw, K[i].d.cout); ew = std::max(ew, K[i].ce); }
@@ -947,7 +1211,7 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         if (i == 0) max_pool = std::max(max_pool, (size_t)49 * B.ce);
         max_c = std::max(max_c, B.ce);
     }
-    if (bb->chain_first >= 0) {   // room for the chained launch's second tensor per buffer (the 112 x 112 layers already need more)
+    if (bb->chain_first >= 0) {   // room for the chained launch's second tensor per buffer
         const size_t hw = (size_t)bb->blk[bb->chain_first].Ho * bb->blk[bb->chain_first].Ho;
         max_act = std::max(max_act, 2 * hw * bb->chain_cout);
         max_dw = std::max(max_dw, 2 * hw * bb->chain_ce);
@@ -960,14 +1224,15 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         bb->nlanes = nl;
         bb->lane_cap = (max_batch + nl - 1) / nl;
         const size_t lc = (size_t)bb->lane_cap;
+        bb->cap_act = max_act; bb->cap_exp = max_exp ? max_exp : 64; bb->cap_dw = max_dw; bb->cap_pool = max_pool; bb->cap_gate = (size_t)max_c;
         for (int l = 0; l < nl; ++l) {
             mmc_backbone::Lane& L = bb->lanes[l];
-            TRY_OR_FREE(dev_alloc(bb, &L.act0, lc * max_act));
-            TRY_OR_FREE(dev_alloc(bb, &L.act1, lc * max_act));
-            TRY_OR_FREE(dev_alloc(bb, &L.expbuf, lc * (max_exp ? max_exp : 64)));
-            TRY_OR_FREE(dev_alloc(bb, &L.dwbuf, lc * max_dw));
-            TRY_OR_FREE(dev_alloc(bb, &L.pool_part, lc * max_pool));
-            TRY_OR_FREE(dev_alloc(bb, &L.gate, lc * (size_t)max_c));
+            TRY_OR_FREE(dev_alloc(bb, &L.act0, lc * bb->cap_act));
+            TRY_OR_FREE(dev_alloc(bb, &L.act1, lc * bb->cap_act));
+            TRY_OR_FREE(dev_alloc(bb, &L.expbuf, lc * bb->cap_exp));
+            TRY_OR_FREE(dev_alloc(bb, &L.dwbuf, lc * bb->cap_dw));
+            TRY_OR_FREE(dev_alloc(bb, &L.pool_part, lc * bb->cap_pool));
+            TRY_OR_FREE(dev_alloc(bb, &L.gate, lc * bb->cap_gate));
             if (nl > 1) {
                 if (hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking) != hipSuccess ||
                     hipEventCreateWithFlags(&L.done, hipEventDisableTiming) != hipSuccess) {
@@ -983,6 +1248,9 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
     }
     TRY_OR_FREE(dev_alloc(bb, &bb->in_stage, mb * (size_t)IMG * IMG * 3));
     TRY_OR_FREE(dev_alloc(bb, &bb->out_stage, mb * (size_t)FEAT));
+
+    // ---- 5. every lane's launch list, each write checked against the buffer sizes of step 4 ----
+    for (int l = 0; l < bb->nlanes; ++l) TRY_OR_FREE(build_lane(bb, l));
 #undef TRY_OR_FREE
     *out = bb;
     return MMC_OK;
@@ -1019,265 +1287,72 @@ static int gemm_mt(const PwLayer& L, int M)
     return wgs2 >= 1024 ? 2 : 1;
 }
 
-// `a`: the layer's bound arguments (gemm_args)
-static int run_gemm(const PwLayer& L, GemmArgs a, const _Float16* X, int M, _Float16* Y, const float* gate, const _Float16* res,
-                    float* gap_out, hipStream_t st)
-{
-    a.X = X; a.M = M; a.Y = Y; a.gate = gate; a.res = res; a.gap_out = gap_out;
-    a.mt = gemm_mt(L, M);
-    return launch_pw_gemm(a, st);
-}
-
-static int forward_lane(mmc_backbone* bb, mmc_backbone::Lane& ws, const uint8_t* patches_dev, int n, float* out_dev,
+// Replays a lane's launch list on n patches.  An entry's arguments are copied before the per-call fields go in -- the batch (B, or
+// M = n x rows with the mt and label that follow from it), the pass's input and its feature output -- so a call leaves nothing behind.
+static int forward_lane(mmc_backbone* bb, const std::vector<Launch>& list, const uint8_t* patches_dev, int n, float* out_dev,
                         hipStream_t st, Prof* prof)
 {
-#define STEP(nm, label, expr)                                                           \
-    do {                                                                                \
-        ProfEntry pe_;                                                                  \
-        if (prof) {                                                                     \
-            pe_.name = std::string(nm) + "|" + std::string(label);                     \
-            HIP_TRY(hipEventCreate(&pe_.e0));                                           \
-            HIP_TRY(hipEventCreate(&pe_.e1));                                           \
-            HIP_TRY(hipEventRecord(pe_.e0, st));                                        \
-        }                                                                               \
-        KTRY(expr);                                                                     \
-        if (prof) {                                                                     \
-            HIP_TRY(hipEventRecord(pe_.e1, st));                                        \
-            prof->entries.push_back(pe_);                                               \
-        }                                                                               \
-    } while (0)
-    // per-tensor mode (MMC_KEEP_ACTIVATIONS=1): copy a tensor out under its name
-#define SAVE(name, dev, elems, is_half)                                                                  \
-    do {                                                                                                 \
-        if (bb->keep) { int r_ = save_act(bb, name, dev, elems, is_half, st); if (r_) return r_; }      \
-    } while (0)
-    char nm[64];
-    _Float16* x = ws.act0;
-    _Float16* y = ws.act1;
-    auto swap_xy = [&] { _Float16* t = x; x = y; y = t; };
-    const int lane_idx = (int)(&ws - bb->lanes);
-    // The chained launch: its members' arguments are collected in launch order and go out with the last one.  Its workgroups are
-    // NOT in step: while workgroup b writes a phase's output, another may still be reading an earlier phase's input.  A buffer's
-    // patch b starts at b x (pixels x row width), so two tensors of different row width in one buffer overlap ACROSS patches --
-    // between separate launches that is harmless, inside the chain it is a race.  So a chained tensor whose row width differs from
-    // what its buffer holds when the chain starts (block ch0's widths) lives in the buffer's upper part, beyond lane_cap patches of
-    // the widest tensor: every region then holds ONE row width, and a workgroup only ever touches its own patch's rows of it.
-    Chain14Args ca{};
-    const int ch0 = bb->chain_first, ch1 = bb->chain_last;
-    const size_t ch_hw = ch0 >= 0 ? (size_t)bb->blk[ch0].Ho * bb->blk[ch0].Ho : 0;
-    auto ch_act = [&](_Float16* base, int cout) { return base + (cout == bb->blk[ch0].d.cout ? 0 : (size_t)bb->lane_cap * ch_hw * bb->chain_cout); };
-    auto ch_dw = [&](int ce) { return ws.dwbuf + (ce == bb->blk[ch0].ce ? 0 : (size_t)bb->lane_cap * ch_hw * bb->chain_ce); };
-    auto ch_pool = [&](int ce) { return ws.pool_part + (ce == bb->blk[ch0].ce ? 0 : (size_t)bb->lane_cap * bb->chain_ce); };
-    _Float16 *xbase = nullptr, *ybase = nullptr;   // inside the chain: the buffers x and the next output live in
-    if (!bb->fuse_stem) {   // (fused: the stem tensor never exists in HBM, no "stem" activation to keep)
-        STEP("stem", "stem_conv", launch_stem(patches_dev, bb->stem_w, bb->stem_b, bb->stem_pad, x, n, bb->stem_ch, st));
-        SAVE("stem", x, (size_t)n * 112 * 112 * bb->stem_ch, true);
-    }
-    for (int i = 0; i < bb->nblk; ++i) {
-        BlockW& B = bb->blk[i];
-        if (B.front == Front::Tail) break;
-        const int HWi = B.H * B.H, HWo = B.Ho * B.Ho;
-        snprintf(nm, sizeof nm, "b%d.mbconv", i);
-        switch (B.front) {
-        case Front::StemDw:
-            // with block 0's project folded into block 1's kernel the depthwise output goes to the spare activation
-            // buffer (block 1 reads it while writing its own depthwise output to dwbuf)
-            STEP("stem+b0.dw", "stem_dw", launch_stem_dw(patches_dev, bb->stem_w, bb->stem_b, bb->stem_pad, B.dw_w, B.dw_b,
-                                                          bb->fuse_b0b1 ? y : ws.dwbuf, ws.pool_part, n, st));
+    for (const Launch& L : list) {
+        Launch::Args a = L.a;
+        ProfEntry pe{&L, 1, nullptr, nullptr};
+        if (prof) {
+            HIP_TRY(hipEventCreate(&pe.e0));
+            HIP_TRY(hipEventCreate(&pe.e1));
+            HIP_TRY(hipEventRecord(pe.e0, st));
+        }
+        const SeLaunch& se = a.se;
+        switch (L.op) {
+        case Op::Stem: KTRY(launch_stem(patches_dev, bb->stem_w, bb->stem_b, bb->stem_pad, a.stem.out, n, bb->stem_ch, st)); break;
+        case Op::StemDw:
+            KTRY(launch_stem_dw(patches_dev, bb->stem_w, bb->stem_b, bb->stem_pad, a.stem.wdw, a.stem.bdw, a.stem.out, a.stem.pool, n, st));
             break;
-        case Front::Mbt: {
-            MbtArgs ta = B.mbt;
-            ta.X = x; ta.D = ws.dwbuf; ta.pool = ws.pool_part; ta.B = n;
-            STEP(nm, B.front_label, launch_mbt(ta, st));
+        case Op::Mbt: a.mbt.B = n; KTRY(launch_mbt(a.mbt, st)); break;
+        case Op::Mid14: a.mid.B = n; KTRY(launch_mid14(a.mid, st)); break;
+        case Op::Mb1: a.mb1.B = n; KTRY(launch_mb1(a.mb1, st)); break;
+        case Op::MbA: a.mb.B = n; KTRY(launch_mbconv_a(a.mb, st)); break;
+        case Op::MbD: a.mb.B = n; KTRY(launch_mbconv_d(a.mb, st)); break;
+        case Op::MbPre: a.pre.mb.B = n; KTRY(launch_mbconv_pre(a.pre.mb, a.pre.pre_w, a.pre.pre_b, a.pre.pre_gate, st)); break;
+        case Op::Gemm:
+            a.gemm.M = n * L.rows;
+            a.gemm.mt = pe.mt = gemm_mt(*L.layer, a.gemm.M);
+            if (L.features) a.gemm.gap_out = out_dev;
+            KTRY(launch_pw_gemm(a.gemm, st));
+            break;
+        case Op::ThinProj:
+            a.gemm.M = n * L.rows;
+            a.gemm.x_plane_rows = L.planar ? n * L.rows : 0;
+            KTRY(launch_thin_proj(a.gemm, n, st));
+            break;
+        case Op::GemmFp8: a.fp8.M = n * L.rows; KTRY(launch_pw_gemm_fp8(a.fp8, st)); break;
+        case Op::Dw: a.dw.B = n; KTRY(launch_dwconv(a.dw, st)); break;
+        case Op::SeWide: KTRY(launch_se_wide(se.pool, se.nparts, n, se.C, se.w.Cs, se.w.wr, se.w.br, se.w.we, se.w.be, se.gate, st)); break;
+        case Op::SeSmall: KTRY(launch_se_small(se.pool, se.nparts, n, se.C, se.w.Cs, se.w.wr, se.w.br, se.w.we, se.w.be, se.gate, st)); break;
+        case Op::SeFused: KTRY(launch_se_gate(se.pool, se.nparts, n, se.C, se.w.Cs, se.w.wr, se.w.br, se.w.we, se.w.be, se.gate, st)); break;
+        case Op::ProjPatch: a.pp.B = n; KTRY(launch_proj_patch(a.pp, st)); break;
+        case Op::Chain14:
+            a.chain.B = n;
+            for (int p = 0; p < a.chain.nph; ++p) ((L.mid_phases >> p & 1) ? a.chain.ph[p].mid.B : a.chain.ph[p].pp.B) = n;
+            KTRY(launch_chain14(a.chain, st));
+            break;
+        case Op::Tail7:
+            a.tail.B = n;
+            if (L.features) a.tail.feat = out_dev;
+            KTRY(launch_tail7(a.tail, st));
             break;
         }
-        case Front::Mid14: {
-            Mid14Args ma = B.mid;
-            ma.X = x; ma.D = ws.dwbuf; ma.pool = ws.pool_part; ma.B = n;
-            if (bb->mid_clk && i == 10) ma.dbg_clk = bb->mid_clk + (size_t)lane_idx * bb->lane_cap * 128;
-            if (ch0 >= 0 && i > ch0 && i <= ch1) {
-                ma.D = ch_dw(B.ce);
-                ma.pool = ch_pool(B.ce);
-                Chain14Phase& ph = ca.ph[ca.nph++];
-                ph.kind = chain14_mid_kind(ma.Cin, ma.ks, ma.Ce);
-                ph.mid = ma;
-                break;
+        if (prof) {
+            HIP_TRY(hipEventRecord(pe.e1, st));
+            prof->entries.push_back(pe);
+        }
+        if (bb->keep)   // per-tensor mode (MMC_KEEP_ACTIVATIONS=1): copy the entry's tensors out under their names
+            for (const KeptTensor& k : L.keep) {
+                const int r = save_act(bb, k.name.c_str(), k.dev, (size_t)n * k.per_patch, k.is_half, st);
+                if (r) return r;
             }
-            STEP(nm, B.front_label, launch_mid14(ma, st));
-            break;
-        }
-        case Front::Mb1: {
-            Mb1Args m1 = B.mb1;
-            m1.X = y; m1.pre_gate = ws.gate; m1.D = ws.dwbuf; m1.pool = ws.pool_part; m1.B = n;
-            STEP("b0.project+b1.mbconv", "mb1", launch_mb1(m1, st));
-            break;
-        }
-        case Front::MbPre: case Front::MbD: case Front::MbA: {
-            MbArgs a = B.mb;
-            a.X = x; a.out = ws.dwbuf; a.pool_part = ws.pool_part; a.B = n;
-            if (B.front == Front::MbD) {
-                STEP(nm, B.front_label, launch_mbconv_d(a, st));
-            } else if (B.front == Front::MbPre) {
-                a.X = y;   // block 0's depthwise output; its gate is in ws.gate
-                STEP("b0.project+b1.mbconv", B.front_label, launch_mbconv_pre(a, B.mb1.pre_w, B.mb1.pre_b, ws.gate, st));
-            } else {
-                STEP(nm, B.front_label, launch_mbconv_a(a, st));
-            }
-            break;
-        }
-        default: {   // Front::Unfused
-            const _Float16* dw_in = x;
-            if (B.has_expand) {
-                snprintf(nm, sizeof nm, "b%d.expand", i);
-                STEP(nm, B.expand.label[gemm_mt(B.expand, n * HWi) - 1],
-                     run_gemm(B.expand, B.exp_gemm, x, n * HWi, ws.expbuf, nullptr, nullptr, nullptr, st));
-                SAVE(nm, ws.expbuf, (size_t)n * HWi * B.ce, true);
-                dw_in = ws.expbuf;
-            }
-            DwArgs d = B.dw;
-            d.in = dw_in; d.out = ws.dwbuf; d.pool_part = ws.pool_part; d.B = n;
-            snprintf(nm, sizeof nm, "b%d.dw", i);
-            STEP(nm, B.front_label, launch_dwconv(d, st));
-        }
-        }
-        snprintf(nm, sizeof nm, "b%d.dw", i);
-        SAVE(nm, (i == 0 && bb->fuse_b0b1) ? y : ws.dwbuf, (size_t)n * HWo * B.ce, true);
-        if (B.back == Back::Tail) break;   // block 11's back half: the tail launch below
-        if (B.back == Back::ProjPatch) {
-            // squeeze-excite + project, one patch per workgroup (proj_patch_kernel): no gate tensor, one launch
-            ProjPatchArgs pa = B.pp;
-            pa.X = ws.dwbuf; pa.pool_part = ws.pool_part; pa.res = B.skip ? x : nullptr; pa.Y = y; pa.B = n;
-            pa.dbg_gate = bb->keep ? ws.gate : nullptr;
-            pa.dbg_clk = bb->keep ? bb->dbg_clk : nullptr;
-            if (ch0 >= 0 && i >= ch0 && i <= ch1) {
-                if (i == ch0) { xbase = x; ybase = y; }
-                pa.X = ch_dw(B.ce);
-                pa.pool_part = ch_pool(B.ce);
-                pa.Y = ch_act(ybase, B.d.cout);
-                Chain14Phase& ph = ca.ph[ca.nph++];
-                ph.kind = chain14_proj_kind(pa.K, pa.N, pa.HW, pa.res ? 1 : 0);
-                ph.pp = pa;
-                x = pa.Y;
-                std::swap(xbase, ybase);
-                y = ybase;   // (after the chain: the other buffer, whose tensors are dead by then)
-                if (i == ch1) {
-                    ca.B = n;
-                    snprintf(nm, sizeof nm, "b%d.projse-b%d.projse.chain", ch0, ch1);
-                    STEP(nm, "chain14", launch_chain14(ca, st));
-                }
-                continue;
-            }
-            snprintf(nm, sizeof nm, "b%d.projse", i);
-            STEP(nm, B.back_label, launch_proj_patch(pa, st));
-            snprintf(nm, sizeof nm, "b%d.gate", i);
-            SAVE(nm, ws.gate, (size_t)n * B.ce, false);
-            snprintf(nm, sizeof nm, "b%d.out", i);
-            SAVE(nm, y, (size_t)n * HWo * B.d.cout, true);
-            snprintf(nm, sizeof nm, "b%d.clk", i);
-            SAVE(nm, bb->dbg_clk, (size_t)n * 8, false);
-            swap_xy();
-            continue;
-        }
-        snprintf(nm, sizeof nm, "b%d.gate", i);
-        const SeArgs& se = B.sea;
-        if (B.se == Se::Wide)
-            STEP(nm, "se_wide", launch_se_wide(ws.pool_part, B.nparts, n, B.ce, se.Cs, se.wr, se.br, se.we, se.be, ws.gate, st));
-        else if (B.se == Se::Small)
-            STEP(nm, "se_small", launch_se_small(ws.pool_part, B.nparts, n, B.ce, se.Cs, se.wr, se.br, se.we, se.be, ws.gate, st));
-        else
-            STEP(nm, "se_fused", launch_se_gate(ws.pool_part, B.nparts, n, B.ce, se.Cs, se.wr, se.br, se.we, se.be, ws.gate, st));
-        SAVE(nm, ws.gate, (size_t)n * B.ce, false);
-        if (B.back == Back::SeFolded) continue;   // block 0's project runs inside block 1's kernel
-        snprintf(nm, sizeof nm, "b%d.project", i);
-        if (B.proj == Proj::Thin) {
-            // small-K, small-N project on a big image (B4 blocks 0, 1; B0 block 1): stream one patch's fragments per workgroup
-            GemmArgs a = B.proj_gemm;
-            a.X = ws.dwbuf; a.M = n * HWo; a.Y = y; a.gate = ws.gate; a.res = B.skip ? x : nullptr;
-            a.x_plane_rows = B.planar ? n * HWo : 0;
-            STEP(nm, "thin_proj", launch_thin_proj(a, n, st));
-        } else if (B.proj == Proj::Fp8) {
-            Fp8GemmArgs fa = B.proj8;
-            fa.X = ws.dwbuf; fa.M = n * HWo; fa.Y = y; fa.gate = ws.gate; fa.res = B.skip ? x : nullptr;
-            STEP(nm, "pw_gemm_fp8", launch_pw_gemm_fp8(fa, st));
-        } else
-            STEP(nm, B.project.label[gemm_mt(B.project, n * HWo) - 1],
-                 run_gemm(B.project, B.proj_gemm, ws.dwbuf, n * HWo, y, ws.gate, B.skip ? x : nullptr, nullptr, st));
-        snprintf(nm, sizeof nm, "b%d.out", i);
-        SAVE(nm, y, (size_t)n * HWo * B.d.cout, true);
-        swap_xy();
     }
-    // ---- the tail and the head ----
-    // Every tail7 launch starts from the handle's bound TailArgs (block table, block 11's and the head's weights, inv_hw).  The kernel
-    // runs block 11 when pre_D or pre_X is set and the head phase when head_w is: a launch without the head phase clears it.
-    auto tail_args = [&](bool head) {
-        TailArgs ta = bb->tail_args;
-        ta.B = n;
-        if (!head) ta.head_w = nullptr;
-        return ta;
-    };
-    if (bb->tail == TailRoute::B11All || (bb->tail == TailRoute::B11 && !bb->keep)) {
-        // from block 11's input (B11All) or its depthwise output (B11) through blocks 12..15 and the head conv to the features, ONE launch
-        TailArgs ta = tail_args(true);
-        ta.nblk = 4; ta.feat = out_dev;
-        if (bb->tail == TailRoute::B11All) {
-            ta.pre_X = x;
-        } else {
-            ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part;
-        }
-        if (bb->tail == TailRoute::B11All && bb->tail_clk) {   // debug clock: rows of this lane's patches
-            ta.dbg_clk = bb->tail_clk + (size_t)lane_idx * bb->lane_cap * 64; ta.clk_sections = 1;
-        }
-        STEP(bb->tail == TailRoute::B11All ? "b11all-head.tail" : "b11-head.tail", "tail7", launch_tail7(ta, st));
-        return 0;
-    }
-    if (bb->tail == TailRoute::B11) {   // per-tensor mode: block 11's back half on its own
-        const BlockW& B11 = bb->blk[11];
-        TailArgs ta = tail_args(false);
-        ta.nblk = 0; ta.Y = y; ta.dbg_gate = ws.gate;
-        ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part;
-        STEP("b11.tail", "tail7", launch_tail7(ta, st));
-        SAVE("b11.gate", ws.gate, (size_t)n * B11.ce, false);
-        SAVE("b11.out", y, (size_t)n * 49 * 192, true);
-        swap_xy();
-    }
-    if (bb->tail != TailRoute::None && !bb->keep) {
-        // blocks 12..15 in one launch, one patch per workgroup, tensors resident in LDS (tail7_kernel)
-        TailArgs ta = tail_args(false);
-        ta.X = x; ta.Y = y; ta.nblk = 4;
-        STEP("b12-15.tail", "tail7", launch_tail7(ta, st));
-        swap_xy();
-    } else if (bb->tail != TailRoute::None) {
-        for (int j = 0; j < 4; ++j) {   // block at a time so every intermediate tensor can be read back
-            const BlockW& B = bb->blk[12 + j];
-            TailArgs ta = tail_args(false);
-            ta.X = x; ta.Y = y; ta.nblk = 1; ta.blk += j;
-            ta.dbg_dw = ws.dwbuf; ta.dbg_gate = ws.gate; ta.dbg_clk = ws.pool_part;
-            snprintf(nm, sizeof nm, "b%d.tail", 12 + j);
-            STEP(nm, "tail7", launch_tail7(ta, st));
-            snprintf(nm, sizeof nm, "b%d.dw", 12 + j);
-            SAVE(nm, ws.dwbuf, (size_t)n * 49 * B.ce, true);
-            snprintf(nm, sizeof nm, "b%d.gate", 12 + j);
-            SAVE(nm, ws.gate, (size_t)n * B.ce, false);
-            snprintf(nm, sizeof nm, "b%d.out", 12 + j);
-            SAVE(nm, y, (size_t)n * 49 * B.d.cout, true);
-            snprintf(nm, sizeof nm, "b%d.clk", 12 + j);
-            SAVE(nm, ws.pool_part, (size_t)n * 8, false);
-            swap_xy();
-        }
-    }
-    if (bb->tail == TailRoute::B11) {   // per-tensor mode: the head phase of tail7_kernel on its own
-        TailArgs ta = tail_args(true);
-        ta.X = x; ta.nblk = 0; ta.in_wide = 1; ta.feat = out_dev;
-        STEP("head.tail", "tail7", launch_tail7(ta, st));
-    } else {
-        const int HWh = bb->blk[bb->nblk - 1].Ho * bb->blk[bb->nblk - 1].Ho;
-        STEP("head", bb->head.label[0],
-             run_gemm(bb->head, bb->head_gemm, x, n * HWh, nullptr, nullptr, nullptr, out_dev, st));
-    }
-#undef SAVE
-#undef STEP
     return 0;
 }
+
 
 // One pass over n resident patches: split into lanes, fork from / join to the caller's stream ONCE.  n may exceed
 // max_batch: the pass is then a sequence of max_batch-sized chunks, and each lane walks its sub-batch of every chunk on its
@@ -1292,7 +1367,7 @@ static int forward_pass(mmc_backbone* bb, const uint8_t* patches_dev, int n, flo
     if (bb->nlanes == 1 || (prof && bb->opt.profile_serial) || n < 2 * bb->nlanes) {
         for (int off = 0; off < n; off += bb->lane_cap) {
             const int cur = n - off < bb->lane_cap ? n - off : bb->lane_cap;
-            int r = forward_lane(bb, bb->lanes[0], patches_dev + (size_t)off * psz, cur, out_dev + (size_t)off * FEAT, st, prof);
+            int r = forward_lane(bb, bb->lanes[0].list, patches_dev + (size_t)off * psz, cur, out_dev + (size_t)off * FEAT, st, prof);
             if (r) return r;
         }
         return 0;
@@ -1307,7 +1382,7 @@ static int forward_pass(mmc_backbone* bb, const uint8_t* patches_dev, int n, flo
             const int cur = cn - off < per ? cn - off : per;
             if (cur <= 0) break;
             mmc_backbone::Lane& L = bb->lanes[l];
-            int r = forward_lane(bb, L, patches_dev + (size_t)(base + off) * psz, cur, out_dev + (size_t)(base + off) * FEAT, L.stream, prof);
+            int r = forward_lane(bb, L.list, patches_dev + (size_t)(base + off) * psz, cur, out_dev + (size_t)(base + off) * FEAT, L.stream, prof);
             if (r) return r;
         }
     }
@@ -1500,7 +1575,7 @@ extern "C" int mmc_backbone_profile(mmc_backbone* bb, const void* patches_dev, i
         hipEventDestroy(e.e0);
         hipEventDestroy(e.e1);
         if (cnt < cap) {
-            snprintf(names[cnt], 64, "%s", e.name.c_str());
+            snprintf(names[cnt], 64, "%s|%s", e.launch->name.c_str(), e.launch->label[e.mt - 1]);
             ms[cnt] = t;
             if (launches) launches[cnt] = 1;
             ++cnt;

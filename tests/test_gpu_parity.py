@@ -476,6 +476,53 @@ def test_graph_replay_is_bitwise_identical_to_plain_launches(checkpoint_path, mo
     assert np.array_equal(fresh, plain)
 
 
+CHANGING_N = [slice(0, 5), slice(7, 8), slice(0, 8), slice(3, 8)]   # 2 lanes of max_batch 8: 3 + 2, one lane, 4 + 4, 3 + 2 again
+
+
+@pytest.fixture(scope="module")
+def fresh_handle_rows(checkpoint_path):
+    """The patches of test_one_handle_changing_n and, per call of its sequence, their features from a handle that has done nothing else."""
+    import torch
+    from mermaid_classifier_amd.backbone import Backbone
+    from oracle import efficientnet_b0_ref as ref
+    p = torch.from_numpy(np.concatenate([ref.natural_patches(5, seed=9), ref.synthetic_patches(3, seed=4)])).cuda()
+    want = []
+    for s in CHANGING_N:
+        bb = Backbone(str(checkpoint_path), device=0, max_batch=8)
+        try:
+            assert bb.lanes == 2
+            want.append(bb.extract(p[s].clone()).cpu().numpy())
+        finally:
+            bb.close()
+    return p, want
+
+
+@pytest.mark.parametrize("graph", ["1", "0"])
+def test_one_handle_changing_n(checkpoint_path, fresh_handle_rows, monkeypatch, graph):
+    """Every call of a handle replays the launch lists its create call built: a call must leave nothing behind for the next one.  One
+    handle extracts 5, 1, 8 and 5 patches (lane splits 3 + 2, the single-lane path, 4 + 4, 3 + 2), four times over with the same
+    buffers, so that with graphs on the later rounds are captured and replayed; MMC_GRAPH=0 runs plain launches throughout.  Every
+    result equals, bit for bit, what a fresh handle gives for the same patches."""
+    import torch
+    from mermaid_classifier_amd.backbone import Backbone
+    p, want = fresh_handle_rows
+    monkeypatch.setenv("MMC_GRAPH", graph)
+    bb = Backbone(str(checkpoint_path), device=0, max_batch=8)
+    try:
+        assert bb.lanes == 2
+        ins = [p[s].clone() for s in CHANGING_N]
+        outs = [torch.empty((len(i), 1280), dtype=torch.float32, device="cuda") for i in ins]
+        for rnd in range(4):
+            for k, (i, o) in enumerate(zip(ins, outs)):
+                o.zero_()
+                bb.extract(i, out=o)
+                assert np.array_equal(o.cpu().numpy(), want[k]), (rnd, k)
+        st = bb.graph_stats()
+        assert (st["captures"] == len(ins)) if graph == "1" else (st["captures"] == 0), st
+    finally:
+        bb.close()
+
+
 def test_graph_cache_eviction_and_stream_switches_keep_results(checkpoint_path):
     """include/mmc.h: the 32 most recently used (patches, features, n) combinations keep their HIP graph, older ones are
     evicted and fall back to plain launches until they repeat; a call on a different stream than the previous one first waits
