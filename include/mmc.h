@@ -69,7 +69,8 @@ int mmc_backbone_create(const void* packed, size_t nbytes, int arch, int device,
  * gated project convs of the 7x7 stage (env MMC_FP8_MAXH=14: of the 14x14 stages too) run on OCP e4m3 operands
  * (v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulation): weights quantised at create time with one scale per output channel,
  * activations in the kernel with one scale per pixel.  Everything else stays fp16 storage / fp32 accumulation.  Accuracy is that of
- * the operand format, not the fp16 gates: feature cosine >= 0.997 against the fp32 oracle on image-like patches (tests). */
+ * the operand format, not the fp16 gates: feature cosine >= 0.997 against the fp32 oracle on image-like patches (the floor the
+ * tests hold it to, and the one INTEGRATION.md states; measured 0.9982 - 0.9996). */
 #define MMC_PRECISION_FP8 1u
 int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arch, int device, int max_batch, unsigned flags,
                            mmc_backbone** out);
@@ -439,6 +440,67 @@ int mmc_trainer_group_partial_fit_set_mixed(mmc_trainer* const* trainers, int co
  * rows.  Same checks (y2 like y; lam NaN or outside [0, 1] -> MMC_ERR_ARG).  For checking the mixed loss stage per element. */
 int mmc_trainer_loss_gradient_mixed(mmc_trainer* t, const float* logits, const int32_t* y, const int32_t* y2, float lam, int64_t n,
                                     float* dlogits, float* row_loss, void* hip_stream);
+
+/* ---- optimiser options: learning-rate schedule, gradient-norm clipping, averaged (EMA) weights, per trainer -----------------------
+ * Extends: the torch.optim.Adam step of TorchMLPClassifier.partial_fit (torch_classifier.py:226-303), one constant learning rate
+ *   and nothing else, by the usual remedies for what docs/research/hidden-layer-experiments.md reports of it: early-step instability at
+ *   lr = 1e-3 (warm-up, a bound on the gradient norm) and a validation loss that turns up from epoch 29 (decay, averaged weights).
+ *   No counterpart in the reference and no measured gain.  Everything here defaults to off; with the defaults a step launches the
+ *   kernels, and gives the bits, of a trainer none of this was ever called on.  Each option is the trainer's own: the members of a
+ *   grouped pass may differ in all of them, and a member computes the bits it computes alone.  Allowed between passes.  A rejected
+ *   call (MMC_ERR_ARG) leaves parameters, moments, step count and every option as they were.
+ * Schedule.  With s the 1-based Adam step being taken (the step count after the increment), lr the create-time learning rate,
+ *   r = final_ratio, all in double:
+ *     w    = warmup_steps > 0 ? min(1, s / warmup_steps) : 1
+ *     u    = clamp((s - warmup_steps) / max(1, total_steps - warmup_steps), 0, 1)
+ *     d    = 1                                     MMC_LR_CONSTANT (total_steps and final_ratio are not read)
+ *          = 1 - (1 - r) u                         MMC_LR_LINEAR
+ *          = r + (1 - r) 0.5 (1 + cos(pi u))       MMC_LR_COSINE   (pi the double nearest it; cos is the C library's)
+ *     lr_s = lr w d                                (left to right)
+ *   and the step's step_size is (float)(lr_s / (1 - beta1^s)).  A pure function of the step count: a trainer resumed through
+ *   mmc_trainer_adam_state continues the schedule; no state, no device work.  Rejected: an unknown kind, warmup_steps < 0,
+ *   total_steps <= warmup_steps for a decaying kind, final_ratio outside [0, 1].  (MMC_LR_CONSTANT, 0, 0, 0) is the constant rate.
+ *   mmc_trainer_lr_at gives lr_s of the trainer for any step and mmc_lr_schedule_at the same function of explicit arguments; both
+ *   are host code and launch nothing.
+ * Clipping.  max_norm = 0: off; otherwise positive and finite (as fp32 too).  After the backward stage of a step the squares of every
+ *   gW[l] and gb[l] of the member are summed -- gW includes the L2 term alpha / mb W, so this is the norm
+ *   torch.nn.utils.clip_grad_norm_ sees on the reference's loss: per tensor 256 partial sums (block j of 256 takes the elements
+ *   i = 256 j + tid + 65536 k in order of k, one fused multiply-add each, then a binary tree over the 256 threads), then one
+ *   workgroup adds the 2L x 256 partials (thread i takes partials i, i + 256, ... in order; the same tree) and forms, in fp32 with
+ *   nothing fused,
+ *     norm = sqrtf(total),   coef = fminf(1.0f, (float)max_norm / (norm + 1e-6f))
+ *   The Adam stage reads coef from device memory and uses g * coef (one rounding) wherever it read g; coef == 1.0f leaves the step's
+ *   bits alone.  No float atomics, no host synchronisation, and a member's partials do not depend on who trains beside it.
+ *   A non-finite norm gives what torch gives with error_if_nonfinite=False and is not hidden: norm = +inf -> coef = 0 (finite
+ *   gradient elements become 0, infinite ones NaN), norm = NaN -> coef = NaN (torch's clamp hands a NaN on) and every parameter of
+ *   the member becomes NaN.  mmc_trainer_grad_norms copies the pre-clip norms of the last pass's steps, in step order, into out
+ *   (at most `capacity`) and sets *steps to their number (0 when the last pass did not clip).
+ * Averaged weights.  decay = 0: off; otherwise in (0, 1).  Turning it on allocates a shadow of every W[l], b[l], initialised with the
+ *   current parameters (so it is usable from step 0 and needs no bias correction); calling it again while on changes the decay and
+ *   keeps the shadow; turning it off frees the shadow and selects MMC_WEIGHTS_RAW.  After a step's parameter update every element takes
+ *     s = s + om_d (p_new - s),   om_d = (float)(1.0 - decay)         two rounded fp32 operations after the subtraction, nothing fused
+ *   mmc_trainer_ema_state reads (set = 0) or writes (set = 1) the shadow, buffers shaped like mmc_trainer_get_params's; MMC_ERR_ARG
+ *   without a shadow.  mmc_trainer_eval_weights chooses what the eval-mode forward reads -- mmc_trainer_logits, every
+ *   mmc_trainer_evaluate*, mmc_calibrator_add_*, mmc_logitcal_add_* -- MMC_WEIGHTS_RAW (default) or MMC_WEIGHTS_AVERAGED
+ *   (MMC_ERR_ARG without a shadow).  Training steps always read and write the raw weights, and mmc_trainer_get_params /
+ *   mmc_trainer_adam_state keep returning the raw weights and their moments.
+ * mmc_trainer_optimizer_options reads the options back (any pointer may be NULL). */
+#define MMC_LR_CONSTANT 0
+#define MMC_LR_LINEAR 1
+#define MMC_LR_COSINE 2
+#define MMC_WEIGHTS_RAW 0
+#define MMC_WEIGHTS_AVERAGED 1
+int mmc_trainer_set_lr_schedule(mmc_trainer* t, int kind, long long warmup_steps, long long total_steps, double final_ratio);
+int mmc_trainer_lr_at(mmc_trainer* t, long long step, double* lr);
+int mmc_lr_schedule_at(double lr, int kind, long long warmup_steps, long long total_steps, double final_ratio, long long step,
+                       double* out);
+int mmc_trainer_set_grad_clip(mmc_trainer* t, double max_norm);
+int mmc_trainer_grad_norms(mmc_trainer* t, float* out, int capacity, int* steps);
+int mmc_trainer_set_ema(mmc_trainer* t, double decay);
+int mmc_trainer_ema_state(mmc_trainer* t, int set, float* const* W, float* const* b);
+int mmc_trainer_eval_weights(mmc_trainer* t, int which);
+int mmc_trainer_optimizer_options(mmc_trainer* t, int* lr_kind, long long* warmup_steps, long long* total_steps, double* final_ratio,
+                                  double* max_norm, double* ema_decay, int* eval_which);
 
 /* ---- validation of a calibrated head --------------------------------------------------------------------------------
  * Replaces: what MermaidTrainer.__call__ computes after the calibration (mermaid_classifier/pyspacer/trainer.py:267-293:

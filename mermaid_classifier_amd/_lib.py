@@ -54,8 +54,13 @@ SYMBOLS = [
     "mmc_logitcal_create", "mmc_logitcal_destroy", "mmc_logitcal_rows", "mmc_logitcal_add_features", "mmc_logitcal_add_set",
     "mmc_logitcal_add_logits", "mmc_logitcal_stats", "mmc_logitcal_fit",
     "mmc_trainer_set_dropout", "mmc_trainer_partial_fit_set_mixed", "mmc_trainer_group_partial_fit_set_mixed", "mmc_trainer_loss_gradient_mixed",
+    "mmc_trainer_set_lr_schedule", "mmc_trainer_lr_at", "mmc_lr_schedule_at", "mmc_trainer_set_grad_clip", "mmc_trainer_grad_norms",
+    "mmc_trainer_set_ema", "mmc_trainer_ema_state", "mmc_trainer_eval_weights", "mmc_trainer_optimizer_options",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
+# include/mmc.h, "optimiser options"
+MMC_LR_CONSTANT, MMC_LR_LINEAR, MMC_LR_COSINE = 0, 1, 2
+MMC_WEIGHTS_RAW, MMC_WEIGHTS_AVERAGED = 0, 1
 
 
 class LibraryMissingError(ImportError):
@@ -251,6 +256,26 @@ def _load() -> C.CDLL:
                                                             C.POINTER(i32), C.POINTER(C.c_double), vp]
     lib.mmc_trainer_loss_gradient_mixed.restype = i32
     lib.mmc_trainer_loss_gradient_mixed.argtypes = [vp, vp, vp, vp, f32, i64, vp, vp, vp]
+    ll = C.c_longlong
+    lib.mmc_trainer_set_lr_schedule.restype = i32
+    lib.mmc_trainer_set_lr_schedule.argtypes = [vp, i32, ll, ll, f64]
+    lib.mmc_trainer_lr_at.restype = i32
+    lib.mmc_trainer_lr_at.argtypes = [vp, ll, C.POINTER(f64)]
+    lib.mmc_lr_schedule_at.restype = i32
+    lib.mmc_lr_schedule_at.argtypes = [f64, i32, ll, ll, f64, ll, C.POINTER(f64)]
+    lib.mmc_trainer_set_grad_clip.restype = i32
+    lib.mmc_trainer_set_grad_clip.argtypes = [vp, f64]
+    lib.mmc_trainer_grad_norms.restype = i32
+    lib.mmc_trainer_grad_norms.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    lib.mmc_trainer_set_ema.restype = i32
+    lib.mmc_trainer_set_ema.argtypes = [vp, f64]
+    lib.mmc_trainer_ema_state.restype = i32
+    lib.mmc_trainer_ema_state.argtypes = [vp, i32, C.POINTER(fp), C.POINTER(fp)]
+    lib.mmc_trainer_eval_weights.restype = i32
+    lib.mmc_trainer_eval_weights.argtypes = [vp, i32]
+    lib.mmc_trainer_optimizer_options.restype = i32
+    lib.mmc_trainer_optimizer_options.argtypes = [vp, C.POINTER(i32), C.POINTER(ll), C.POINTER(ll), C.POINTER(f64), C.POINTER(f64),
+                                                  C.POINTER(f64), C.POINTER(i32)]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

@@ -20,6 +20,10 @@
 //             the input's mask on the staged mini-batch, in place                        dropout_rows_kernel
 //   mixup     x = lam Xa + oml Xb while the rows of a resident pass are gathered         gather_set_rows_mixed_kernel
 //             l = lam l(z, ya) + oml l(z, yb): one softmax, two targets                  ce_grad_mixed_kernel, ce_grad_rows_mixed
+// Per trainer, off by default (include/mmc.h, "optimiser options"; a member with none of them runs adam_kernel as ever):
+//   schedule  lr_s = lr w(s) d(s) in double on the host, step_size = (float)(lr_s / bc1)  mmc_lr_schedule_at
+//   clipping  norm over every gW(l), gb(l); coef = fminf(1, max_norm / (norm + 1e-6))     sumsq_kernel, gnorm_finalize_kernel
+//   update    Adam on g * coef, then the shadow s = s + om_d (p - s)                      adam_opt_kernel
 //
 // Every step is the step of a group of trainers (trainer_group_step): each kind of launch once, one member per blockIdx.z, the
 // member's operands in a by-value descriptor array.  A trainer on its own -- the host-fed pass, mmc_trainer_partial_fit_set, the
@@ -574,6 +578,82 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamGroup g)
     adam_elems(d.p, d.g, d.m, d.v, d.n, d.om_beta1, d.beta2, d.om_beta2, d.eps, d.step_size, d.bc2_sqrt);
 }
 
+// ---- optimiser options (include/mmc.h, "optimiser options"): the kernels of a member that clips its gradient or averages its weights.
+// A member with neither goes through adam_kernel above, whose code these do not share, so that launch stays what it was.
+
+// The member's gradient norm from the 2L x 256 partials that sumsq_kernel left of its gW[l] / gb[l] (tensor k = 2l, 2l + 1 at
+// partials[256 k ..]), summed in a fixed order: thread i takes partials[i], [i + 256], ... in order, then the LDS tree.
+//   norm = sqrtf(total),  coef = fminf(1.0f, max_norm / (norm + 1e-6f))     torch.nn.utils.clip_grad_norm_, error_if_nonfinite=False
+// torch clamps with clamp(max=1), which hands a NaN on where fminf would drop it: a NaN norm gives a NaN coefficient here too, and
+// an infinite one gives 0.  Nothing is hidden: the Adam stage multiplies by what is written.
+struct GnormDesc {
+    const float* partials;
+    float *coef, *norm_out;
+    int P;
+    float max_norm;
+};
+struct GnormGroup { GnormDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(GnormGroup) <= 4096, "kernel-argument limit");
+
+__global__ __launch_bounds__(256) void gnorm_finalize_kernel(const GnormGroup g)
+{
+#pragma clang fp contract(off)
+    __shared__ float red[256];
+    const GnormDesc& d = g.d[blockIdx.z];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < d.P; i += 256) s += d.partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm = sqrtf(red[0]);
+        const float q = d.max_norm / (norm + 1e-6f);
+        float c = fminf(1.0f, q);
+        if (q != q) c = q;
+        d.coef[0] = c;
+        d.norm_out[0] = norm;
+    }
+}
+
+// adam_elems on gi = g[i] * *coef (one rounding; coef null: g[i] itself), then the shadow of the averaged weights from the
+// parameter just written: s = s + om_d (p_new - s), two roundings like exp_avg (shadow null: none).
+struct AdamOptDesc {
+    float* p;
+    const float* g;
+    float *m, *v;
+    size_t n;
+    float om_beta1, beta2, om_beta2, eps, step_size, bc2_sqrt;
+    const float* coef;
+    float* shadow;
+    float om_d;
+};
+struct AdamOptGroup { AdamOptDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(AdamOptGroup) <= 4096, "kernel-argument limit");
+
+__global__ __launch_bounds__(256) void adam_opt_kernel(const AdamOptGroup g)
+{
+#pragma clang fp contract(off)   // as adam_elems: the parameter update is the one fused multiply-add
+    const AdamOptDesc& d = g.d[blockIdx.z];
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= d.n) return;
+    float gi = d.g[i];
+    if (d.coef) gi = gi * d.coef[0];
+    const float mi = d.m[i] + d.om_beta1 * (gi - d.m[i]);
+    const float vi = d.v[i] * d.beta2 + d.om_beta2 * gi * gi;
+    d.m[i] = mi;
+    d.v[i] = vi;
+    const float denom = sqrtf(vi) / d.bc2_sqrt + d.eps;
+    const float pn = fmaf(-d.step_size, mi / denom, d.p[i]);
+    d.p[i] = pn;
+    if (d.shadow) {
+        const float si = d.shadow[i];
+        d.shadow[i] = si + d.om_d * (pn - si);
+    }
+}
+
 // Xo[i][:] = Xn[order[i]][:], yo[i] = yn[order[i]]: the visiting order of a pass applied on the device (one float4 per thread)
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ Xn, const int32_t* __restrict__ yn,
                                                           const int64_t* __restrict__ order, int64_t n, int d4, float* __restrict__ Xo,
@@ -691,6 +771,18 @@ struct mmc_trainer {
     float* lam = nullptr;                               // device copy of its per-mini-batch lam
     int64_t cap_y2 = 0, cap_partner = 0;
     int cap_lam = 0;
+    // optimiser options (mmc_trainer_set_lr_schedule / _set_grad_clip / _set_ema): all off = today's launches
+    int lr_kind = MMC_LR_CONSTANT;
+    long long warmup_steps = 0, total_steps = 0;
+    double final_ratio = 0.0;
+    double max_norm = 0.0;                              // 0 = no clipping
+    float* gpartials = nullptr;                         // [2 * 16][256] partial sums of squares of gW[l] (2l) and gb[l] (2l + 1)
+    float* coef = nullptr;                              // the step's clipping coefficient
+    float* gnorm = nullptr;                             // [cap_gnorm] pre-clip norm of every step of a pass, beside losses
+    int cap_gnorm = 0, gnorm_steps = 0;                 // gnorm_steps: steps of the last pass that wrote gnorm
+    double ema_decay = 0.0;                             // 0 = no averaged weights
+    std::vector<float*> sW, sb;                         // the shadow: averaged weights (empty without)
+    int eval_which = MMC_WEIGHTS_RAW;                   // what the eval-mode forward reads
 };
 
 #define T_TRY(expr)                                                                                   \
@@ -720,6 +812,8 @@ extern "C" void mmc_trainer_destroy(mmc_trainer* t)
     hipFree(t->cw); hipFree(t->prior); hipFree(t->X); hipFree(t->row_loss); hipFree(t->partials); hipFree(t->losses); hipFree(t->y);
     hipFree(t->Xn); hipFree(t->yn); hipFree(t->order); hipFree(t->visit); hipFree(t->scratch);
     hipFree(t->y2); hipFree(t->partner); hipFree(t->lam);
+    hipFree(t->gpartials); hipFree(t->coef); hipFree(t->gnorm);
+    free_all(t->sW); free_all(t->sb);
     delete t;
 }
 
@@ -834,8 +928,168 @@ extern "C" int mmc_trainer_set_dropout(mmc_trainer* t, double p_input, double p_
     return MMC_OK;
 }
 
+// ---- optimiser options (include/mmc.h) ----------------------------------------------------------------------------------
+// lr_s of the 1-based step s: a pure function of the step count, all in double
+extern "C" int mmc_lr_schedule_at(double lr, int kind, long long warmup_steps, long long total_steps, double final_ratio, long long step,
+                                  double* out)
+{
+    if (!out) return mmc_fail(MMC_ERR_ARG, "out is NULL");
+    if (kind != MMC_LR_CONSTANT && kind != MMC_LR_LINEAR && kind != MMC_LR_COSINE)
+        return mmc_fail(MMC_ERR_ARG, "kind = %d is not MMC_LR_CONSTANT, MMC_LR_LINEAR or MMC_LR_COSINE", kind);
+    if (warmup_steps < 0) return mmc_fail(MMC_ERR_ARG, "warmup_steps = %lld is negative", warmup_steps);
+    if (kind != MMC_LR_CONSTANT && !(total_steps > warmup_steps))
+        return mmc_fail(MMC_ERR_ARG, "a decaying schedule needs total_steps > warmup_steps (got %lld, %lld)", total_steps, warmup_steps);
+    if (!(final_ratio >= 0.0 && final_ratio <= 1.0)) return mmc_fail(MMC_ERR_ARG, "final_ratio = %g outside [0, 1]", final_ratio);
+    const double s = (double)step, wu = (double)warmup_steps;
+    const double w = warmup_steps > 0 ? std::min(1.0, s / wu) : 1.0;
+    const double u = std::min(1.0, std::max(0.0, (s - wu) / (double)std::max(1LL, total_steps - warmup_steps)));
+    const double r = final_ratio;
+    double d = 1.0;
+    if (kind == MMC_LR_LINEAR) d = 1.0 - (1.0 - r) * u;
+    if (kind == MMC_LR_COSINE) d = r + (1.0 - r) * 0.5 * (1.0 + std::cos(3.14159265358979323846 * u));   // the double nearest pi
+    *out = lr * w * d;
+    return MMC_OK;
+}
+
+static double trainer_lr_at(const mmc_trainer* t, long long step)
+{
+    double lr = t->lr;
+    mmc_lr_schedule_at(t->lr, t->lr_kind, t->warmup_steps, t->total_steps, t->final_ratio, step, &lr);   // the options were checked when set
+    return lr;
+}
+
+extern "C" int mmc_trainer_set_lr_schedule(mmc_trainer* t, int kind, long long warmup_steps, long long total_steps, double final_ratio)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    double probe = 0.0;
+    int r = mmc_lr_schedule_at(t->lr, kind, warmup_steps, total_steps, final_ratio, 1, &probe);
+    if (r) return r;
+    t->lr_kind = kind;
+    t->warmup_steps = warmup_steps;
+    t->total_steps = total_steps;
+    t->final_ratio = final_ratio;
+    return MMC_OK;
+}
+
+extern "C" int mmc_trainer_lr_at(mmc_trainer* t, long long step, double* lr)
+{
+    if (!t || !lr) return mmc_fail(MMC_ERR_ARG, "NULL argument");
+    return mmc_lr_schedule_at(t->lr, t->lr_kind, t->warmup_steps, t->total_steps, t->final_ratio, step, lr);
+}
+
+extern "C" int mmc_trainer_set_grad_clip(mmc_trainer* t, double max_norm)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!(max_norm == 0.0 || (max_norm > 0.0 && std::isfinite(max_norm) && std::isfinite((float)max_norm) && (float)max_norm > 0.f)))
+        return mmc_fail(MMC_ERR_ARG, "max_norm = %g is neither 0 nor a positive finite fp32 value", max_norm);
+    if (max_norm != 0.0 && !t->gpartials) {
+        T_TRY(hipSetDevice(t->device));
+        float *gp = nullptr, *cf = nullptr;
+        if (hipMalloc((void**)&gp, 2 * 16 * 256 * 4 + 256) != hipSuccess || hipMalloc((void**)&cf, 256) != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(gp);
+            return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the gradient-norm partials");
+        }
+        t->gpartials = gp;
+        t->coef = cf;
+    }
+    t->max_norm = max_norm;
+    t->gnorm_steps = 0;
+    return MMC_OK;
+}
+
+extern "C" int mmc_trainer_grad_norms(mmc_trainer* t, float* out, int capacity, int* steps)
+{
+    if (!t || !steps) return mmc_fail(MMC_ERR_ARG, "NULL argument");
+    if (capacity < 0 || (capacity > 0 && !out)) return mmc_fail(MMC_ERR_ARG, "capacity = %d with out %s", capacity, out ? "set" : "NULL");
+    *steps = t->gnorm_steps;
+    const int n = std::min(capacity, t->gnorm_steps);
+    if (n > 0) {
+        T_TRY(hipSetDevice(t->device));
+        T_TRY(hipMemcpy(out, t->gnorm, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    return MMC_OK;
+}
+
+extern "C" int mmc_trainer_set_ema(mmc_trainer* t, double decay)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!(decay == 0.0 || (decay > 0.0 && decay < 1.0))) return mmc_fail(MMC_ERR_ARG, "decay = %g is neither 0 nor in (0, 1)", decay);
+    T_TRY(hipSetDevice(t->device));
+    if (decay == 0.0) {
+        free_all(t->sW);
+        free_all(t->sb);
+        t->eval_which = MMC_WEIGHTS_RAW;
+    } else if (t->sW.empty()) {   // passes synchronise their stream before they return: the parameters copied here are settled
+        std::vector<float*> sW, sb;
+        bool ok = true;
+        auto dup = [&](std::vector<float*>& dst, const float* src, size_t n) -> bool {
+            float* d = nullptr;
+            if (hipMalloc((void**)&d, n * 4 + 256) != hipSuccess) return false;
+            dst.push_back(d);
+            return hipMemcpy(d, src, n * 4, hipMemcpyDeviceToDevice) == hipSuccess;
+        };
+        for (int l = 0; l < t->L && ok; ++l)
+            ok = dup(sW, t->W[l], (size_t)t->dims[l + 1] * t->dims[l]) && dup(sb, t->b[l], (size_t)t->dims[l + 1]);
+        if (!ok) {
+            (void)hipGetLastError();
+            free_all(sW);
+            free_all(sb);
+            return mmc_fail(MMC_ERR_NOMEM, "hipMalloc/hipMemcpy failed for the averaged weights");
+        }
+        t->sW = sW;
+        t->sb = sb;
+    }
+    t->ema_decay = decay;
+    return MMC_OK;
+}
+
+extern "C" int mmc_trainer_ema_state(mmc_trainer* t, int set, float* const* W, float* const* b)
+{
+    if (!t || !W || !b) return mmc_fail(MMC_ERR_ARG, "NULL argument");
+    if (t->sW.empty()) return mmc_fail(MMC_ERR_ARG, "the trainer keeps no averaged weights (mmc_trainer_set_ema)");
+    T_TRY(hipSetDevice(t->device));
+    T_TRY(hipDeviceSynchronize());
+    for (int l = 0; l < t->L; ++l) {
+        const size_t nw = (size_t)t->dims[l + 1] * t->dims[l] * 4, nb = (size_t)t->dims[l + 1] * 4;
+        if (set) { T_TRY(hipMemcpy(t->sW[l], W[l], nw, hipMemcpyHostToDevice)); T_TRY(hipMemcpy(t->sb[l], b[l], nb, hipMemcpyHostToDevice)); }
+        else { T_TRY(hipMemcpy(W[l], t->sW[l], nw, hipMemcpyDeviceToHost)); T_TRY(hipMemcpy(b[l], t->sb[l], nb, hipMemcpyDeviceToHost)); }
+    }
+    return MMC_OK;
+}
+
+extern "C" int mmc_trainer_eval_weights(mmc_trainer* t, int which)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (which != MMC_WEIGHTS_RAW && which != MMC_WEIGHTS_AVERAGED)
+        return mmc_fail(MMC_ERR_ARG, "which = %d is neither MMC_WEIGHTS_RAW nor MMC_WEIGHTS_AVERAGED", which);
+    if (which == MMC_WEIGHTS_AVERAGED && t->sW.empty())
+        return mmc_fail(MMC_ERR_ARG, "the trainer keeps no averaged weights (mmc_trainer_set_ema)");
+    t->eval_which = which;
+    return MMC_OK;
+}
+
+extern "C" int mmc_trainer_optimizer_options(mmc_trainer* t, int* lr_kind, long long* warmup_steps, long long* total_steps,
+                                             double* final_ratio, double* max_norm, double* ema_decay, int* eval_which)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (lr_kind) *lr_kind = t->lr_kind;
+    if (warmup_steps) *warmup_steps = t->warmup_steps;
+    if (total_steps) *total_steps = t->total_steps;
+    if (final_ratio) *final_ratio = t->final_ratio;
+    if (max_norm) *max_norm = t->max_norm;
+    if (ema_decay) *ema_decay = t->ema_decay;
+    if (eval_which) *eval_which = t->eval_which;
+    return MMC_OK;
+}
+
 static int trainer_reserve(mmc_trainer* t, int64_t n, int mb, int steps)
 {
+    if (t->max_norm > 0.0 && steps > t->cap_gnorm) {
+        hipFree(t->gnorm); t->gnorm = nullptr; t->cap_gnorm = 0; t->gnorm_steps = 0;
+        T_TRY(hipMalloc((void**)&t->gnorm, (size_t)steps * 4 + 256));
+        t->cap_gnorm = steps;
+    }
     if (n > t->cap_n) {
         hipFree(t->X); hipFree(t->y);
         t->X = nullptr; t->y = nullptr; t->cap_n = 0;
@@ -1029,31 +1283,79 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
             T_K((launch_tgemm<false, false, TEPI_MASK, TEPI_MASK>(gz, kz, st)));
         }
     }
+    // gradient clipping: the clipping members' norm over every gW[l] / gb[l] (the L2 term is in gW), their coefficient to device
+    // memory; the Adam stage reads it there, so nothing waits on the host
+    bool clips = false;
+    for (int i = 0; i < cnt; ++i) clips = clips || act[i].t->max_norm > 0.0;
+    if (clips) {
+        for (int l = 0; l < Lmax; ++l) {
+            SumsqGroup gw, gb;
+            int k = 0;
+            for (int i = 0; i < cnt; ++i) {
+                const mmc_trainer* t = act[i].t;
+                if (!(t->max_norm > 0.0) || l >= t->L) continue;
+                gw.d[k] = SumsqDesc{t->gW[l], t->gpartials + 256 * (2 * l), (size_t)t->dims[l + 1] * t->dims[l]};
+                gb.d[k] = SumsqDesc{t->gb[l], t->gpartials + 256 * (2 * l + 1), (size_t)t->dims[l + 1]};
+                ++k;
+            }
+            if (!k) continue;
+            hipLaunchKernelGGL(sumsq_kernel, dim3(256, 1, k), dim3(256), 0, st, gw);
+            hipLaunchKernelGGL(sumsq_kernel, dim3(256, 1, k), dim3(256), 0, st, gb);
+        }
+        GnormGroup g;
+        int k = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const mmc_trainer* t = act[i].t;
+            if (t->max_norm > 0.0) g.d[k++] = GnormDesc{t->gpartials, t->coef, t->gnorm + act[i].slot, 2 * 256 * t->L, (float)t->max_norm};
+        }
+        hipLaunchKernelGGL(gnorm_finalize_kernel, dim3(1, 1, k), dim3(256), 0, st, g);
+    }
     float step_size[MMC_TRAINER_GROUP_MAX], bc2_sqrt[MMC_TRAINER_GROUP_MAX];
     for (int i = 0; i < cnt; ++i) {
         mmc_trainer* t = act[i].t;
         ++t->t;
         const double bc1 = 1.0 - std::pow(t->beta1, (double)t->t), bc2 = 1.0 - std::pow(t->beta2, (double)t->t);
-        step_size[i] = (float)(t->lr / bc1);
+        step_size[i] = (float)(trainer_lr_at(t, t->t) / bc1);
         bc2_sqrt[i] = (float)std::sqrt(bc2);
     }
+    // the members that neither clip nor average go through adam_kernel, the others through adam_opt_kernel
     for (int l = 0; l < Lmax; ++l) {
         AdamGroup gw, gb;
-        int k = 0;
-        size_t wmax = 0, bmax = 0;
+        AdamOptGroup ow, ob;
+        int k = 0, ko = 0;
+        size_t wmax = 0, bmax = 0, owmax = 0, obmax = 0;
         for (int i = 0; i < cnt; ++i) {
             const mmc_trainer* t = act[i].t;
             if (l >= t->L) continue;
             const size_t nw = (size_t)t->dims[l + 1] * t->dims[l], nb = (size_t)t->dims[l + 1];
             const float om1 = (float)(1.0 - t->beta1), om2 = (float)(1.0 - t->beta2), b2f = (float)t->beta2, epsf = (float)t->eps;
+            const bool ema = !t->sW.empty();
+            if (t->max_norm > 0.0 || ema) {
+                const float* coef = t->max_norm > 0.0 ? t->coef : nullptr;
+                const float om_d = (float)(1.0 - t->ema_decay);
+                ow.d[ko] = AdamOptDesc{t->W[l], t->gW[l], t->mW[l], t->vW[l], nw, om1, b2f, om2, epsf, step_size[i], bc2_sqrt[i],
+                                       coef, ema ? t->sW[l] : nullptr, om_d};
+                ob.d[ko] = AdamOptDesc{t->b[l], t->gb[l], t->mb[l], t->vb[l], nb, om1, b2f, om2, epsf, step_size[i], bc2_sqrt[i],
+                                       coef, ema ? t->sb[l] : nullptr, om_d};
+                ++ko;
+                owmax = std::max(owmax, nw);
+                obmax = std::max(obmax, nb);
+                continue;
+            }
             gw.d[k] = AdamDesc{t->W[l], t->gW[l], t->mW[l], t->vW[l], nw, om1, b2f, om2, epsf, step_size[i], bc2_sqrt[i]};
             gb.d[k] = AdamDesc{t->b[l], t->gb[l], t->mb[l], t->vb[l], nb, om1, b2f, om2, epsf, step_size[i], bc2_sqrt[i]};
             ++k;
             wmax = std::max(wmax, nw);
             bmax = std::max(bmax, nb);
         }
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((wmax + 255) / 256), 1, k), dim3(256), 0, st, gw);
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((bmax + 255) / 256), 1, k), dim3(256), 0, st, gb);
+        if (k) {
+            hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((wmax + 255) / 256), 1, k), dim3(256), 0, st, gw);
+            hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((bmax + 255) / 256), 1, k), dim3(256), 0, st, gb);
+        }
+        if (ko) {
+            hipLaunchKernelGGL(adam_opt_kernel, dim3((unsigned)((owmax + 255) / 256), 1, ko), dim3(256), 0, st, ow);
+            hipLaunchKernelGGL(adam_opt_kernel, dim3((unsigned)((obmax + 255) / 256), 1, ko), dim3(256), 0, st, ob);
+        }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "trainer step launch failed: %s", hipGetErrorString(e));
@@ -1159,6 +1461,7 @@ extern "C" int mmc_trainer_partial_fit_ordered(mmc_trainer* t, const float* X, c
         const StepMember one{t, start, batch_rows(n, start, mb), (float)(1.0 / wsums[s]), s, false, 0.f};
         if ((r = trainer_group_step(&one, 1, st))) return r;
     }
+    t->gnorm_steps = t->max_norm > 0.0 ? steps : 0;
     std::vector<float> h(steps);
     T_TRY(hipMemcpyAsync(h.data(), t->losses, (size_t)steps * 4, hipMemcpyDeviceToHost, st));
     T_TRY(hipStreamSynchronize(st));
@@ -1366,6 +1669,7 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
         }
         if ((r = trainer_group_step(act, cnt, st))) return r;
     }
+    for (int m = 0; m < count; ++m) mem[m].t->gnorm_steps = mem[m].t->max_norm > 0.0 ? mem[m].steps : 0;
     std::vector<std::vector<float>> h(count);
     for (int m = 0; m < count; ++m) {
         h[m].resize(mem[m].steps);
@@ -1477,6 +1781,10 @@ int trainer_forward_device(mmc_trainer* t, const float* X_dev, int n, hipStream_
     for (int l = 0; l < t->L; ++l) {
         GemmGroup g;
         g.d[0] = forward_desc(t, l, n);
+        if (t->eval_which == MMC_WEIGHTS_AVERAGED) {   // mmc_trainer_eval_weights: the same launch on the shadow
+            g.d[0].B = t->sW[l];
+            g.d[0].aux = t->sb[l];
+        }
         T_K((launch_tgemm<false, true, TEPI_BIAS_RELU, TEPI_BIAS>(g, 1, st)));
     }
     *logits = t->H[t->L];

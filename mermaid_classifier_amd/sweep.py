@@ -40,7 +40,7 @@ from .calibration import CalibratedMLP, calibrate, evaluate, evaluate_classes
 from .featureset import FeatureSet
 from .metrics import grouped_validate
 from .torch_classifier import TorchMLPClassifier
-from .training import EarlyStopping, _check_splits, _contiguous_batches, _val_entries
+from .training import EarlyStopping, _check_splits, _contiguous_batches, _fill_schedule_steps, _val_entries
 from .validation import validate
 
 __all__ = ["SweepConfig", "partial_fit_rows_group", "sweep_loop", "train_sweep", "rank_sweep"]
@@ -118,7 +118,9 @@ class SweepConfig:
     slices of ``train_sweep``'s ``batch_size`` rows.  ``label_smoothing`` / ``focal_gamma`` / ``logit_prior`` are the classifier's loss
     formulation (``mmc_trainer_set_loss``): the members of one grouped pass may each have their own.  ``logit_scaling`` (keyword only)
     is ``train_classifier``'s argument of that name for this configuration.  ``dropout`` / ``input_dropout`` / ``mixup_alpha`` /
-    ``regularizer_seed`` are the classifier's regularisers, again per member."""
+    ``regularizer_seed`` are the classifier's regularisers, again per member, and so are its optimiser options ``lr_schedule`` /
+    ``warmup_steps`` / ``schedule_steps`` / ``final_lr_ratio`` / ``max_grad_norm`` / ``ema_decay`` (keyword only; a decaying schedule
+    with ``schedule_steps=None`` ends after ``nbr_epochs`` epochs of this member's own steps)."""
     hidden_layer_sizes: Tuple[int, ...] = (500, 300, 100)
     learning_rate_init: float = 1e-4
     alpha: float = 1e-4
@@ -136,6 +138,13 @@ class SweepConfig:
     input_dropout: float = field(default=0.0, kw_only=True)
     mixup_alpha: float = field(default=0.0, kw_only=True)
     regularizer_seed: Optional[int] = field(default=None, kw_only=True)
+    # the classifier's optimiser options (mmc_trainer_set_lr_schedule / _set_grad_clip / _set_ema): keyword only, as in its constructor
+    lr_schedule: str = field(default="constant", kw_only=True)
+    warmup_steps: int = field(default=0, kw_only=True)
+    schedule_steps: Optional[int] = field(default=None, kw_only=True)
+    final_lr_ratio: float = field(default=0.0, kw_only=True)
+    max_grad_norm: Optional[float] = field(default=None, kw_only=True)
+    ema_decay: float = field(default=0.0, kw_only=True)
     batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None
     label_smoothing: float = 0.0
     focal_gamma: float = 0.0
@@ -148,7 +157,9 @@ class SweepConfig:
                                   batch_size=self.batch_size, beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.epsilon,
                                   device=device, label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma,
                                   logit_prior=self.logit_prior, dropout=self.dropout, input_dropout=self.input_dropout,
-                                  mixup_alpha=self.mixup_alpha, regularizer_seed=self.regularizer_seed)
+                                  mixup_alpha=self.mixup_alpha, regularizer_seed=self.regularizer_seed,
+                                  lr_schedule=self.lr_schedule, warmup_steps=self.warmup_steps, schedule_steps=self.schedule_steps,
+                                  final_lr_ratio=self.final_lr_ratio, max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay)
 
 
 def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[Any]]],
@@ -235,6 +246,8 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
     classes = ref.classes.tolist()
     clfs = [cfg.classifier(ref.device) for cfg in configs]
     batches = [cfg.batches if cfg.batches is not None else _contiguous_batches(len(train), int(batch_size)) for cfg in configs]
+    for c, b in zip(clfs, batches):
+        _fill_schedule_steps(c, b, nbr_epochs)
     ref_accs: Dict[int, List[float]] = {id(c): [] for c in clfs}
 
     def eval_ref(c):

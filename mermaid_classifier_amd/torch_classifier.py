@@ -23,7 +23,10 @@ two halves ``_begin_rows_pass`` / ``_end_pass``, which ``sweep.partial_fit_rows_
 formulation -- ``label_smoothing`` / ``focal_gamma`` / ``logit_prior``, ``_check_loss_scalars``, ``_build_logit_prior_vector``
 (``mmc_trainer_set_loss``) -- whose defaults are the reference's weighted cross-entropy; and the regularisers -- ``dropout`` /
 ``input_dropout`` / ``mixup_alpha`` / ``regularizer_seed``, ``_check_regularizers``, ``_regularizer_seed_value``, ``_mix_plan``
-(``mmc_trainer_set_dropout``, ``mmc_trainer_partial_fit_set_mixed``) -- whose defaults leave the step as it is.
+(``mmc_trainer_set_dropout``, ``mmc_trainer_partial_fit_set_mixed``) -- whose defaults leave the step as it is; and the optimiser
+options -- ``lr_schedule`` / ``warmup_steps`` / ``schedule_steps`` / ``final_lr_ratio`` / ``max_grad_norm`` / ``ema_decay``,
+``_apply_optimizer_options``, ``raw_parameters`` / ``averaged_parameters`` / ``use_weights``, ``grad_norms_``
+(``mmc_trainer_set_lr_schedule``, ``mmc_trainer_set_grad_clip``, ``mmc_trainer_set_ema``) -- again off by default.
 """
 
 from __future__ import annotations
@@ -36,6 +39,7 @@ from typing import Any, List
 import numpy as np
 
 from . import _lib
+from .optim import LR_KINDS, check_optimizer_options
 from .backbone import _current_stream_ptr, _device_index
 
 _EXPECTED_FP_DRIFT_TOL = 1e-4   # torch_classifier.py:45-50
@@ -82,7 +86,16 @@ class TorchMLPClassifier:
     ``partial_fit_rows`` pass with a partner of its mini-batch, ``lam ~ Beta(alpha, alpha)`` per mini-batch (``sampling.mixup_plan``;
     the host-fed ``partial_fit`` raises), and ``regularizer_seed`` seeds both (None: ``random_state``, or one draw from numpy's global
     RNG when that is None too).  Read when the trainer is created, like every other hyper-parameter.  Training alone sees them; the
-    defaults leave every pass as it is, bit for bit."""
+    defaults leave every pass as it is, bit for bit.
+
+    Six more, keyword only, are the optimiser options of include/mmc.h: ``lr_schedule`` ("constant" / "linear" / "cosine") with
+    ``warmup_steps``, ``schedule_steps`` (the step at which the decay ends; a decaying schedule needs it by the first fit --
+    ``train_classifier`` and ``train_sweep`` fill a None in) and ``final_lr_ratio`` in [0, 1]; ``max_grad_norm`` (None: off) clips the
+    global gradient norm of every step, and ``grad_norms_`` then holds the last pass's pre-clip norms; ``ema_decay`` in (0, 1) keeps
+    an exponential average of the weights.  With ``ema_decay > 0`` the classifier evaluates the AVERAGED weights: ``predict_proba``,
+    ``parameters()`` and everything built on them (``calibration.evaluate`` / ``calibrate`` / ``export_artifact``,
+    ``fit_logit_scaling``, early stopping's validation loss) see them, training goes on with the raw ones, ``raw_parameters()``
+    returns those, and ``use_weights("raw")`` / ``use_weights("averaged")`` switches.  Everything with the defaults is as before."""
 
     _estimator_type = "classifier"
 
@@ -92,13 +105,16 @@ class TorchMLPClassifier:
                  beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-8,
                  class_weight: dict | None = None, device=0, *, label_smoothing: float = 0.0, focal_gamma: float = 0.0,
                  logit_prior: dict | None = None, dropout: float = 0.0, input_dropout: float = 0.0, mixup_alpha: float = 0.0,
-                 regularizer_seed: int | None = None):
+                 regularizer_seed: int | None = None, lr_schedule: str = "constant", warmup_steps: int = 0,
+                 schedule_steps: int | None = None, final_lr_ratio: float = 0.0, max_grad_norm: float | None = None,
+                 ema_decay: float = 0.0):
         if activation != "relu":
             raise ValueError(f"TorchMLPClassifier only supports activation='relu', got {activation!r}.")
         if solver != "adam":
             raise ValueError(f"TorchMLPClassifier only supports solver='adam', got {solver!r}.")
         _check_loss_scalars(label_smoothing, focal_gamma)
         _check_regularizers(dropout, input_dropout, mixup_alpha, regularizer_seed)
+        check_optimizer_options(lr_schedule, warmup_steps, schedule_steps, final_lr_ratio, max_grad_norm, ema_decay)
         self.hidden_layer_sizes = tuple(hidden_layer_sizes)
         self.activation = activation
         self.solver = solver
@@ -121,6 +137,12 @@ class TorchMLPClassifier:
         self.input_dropout = input_dropout
         self.mixup_alpha = mixup_alpha
         self.regularizer_seed = regularizer_seed
+        self.lr_schedule = lr_schedule
+        self.warmup_steps = warmup_steps
+        self.schedule_steps = schedule_steps
+        self.final_lr_ratio = final_lr_ratio
+        self.max_grad_norm = max_grad_norm
+        self.ema_decay = ema_decay
 
     # ---- host bookkeeping, restated from the reference ------------------------------------------------------------
     def _resolve_batch_size(self, n_samples: int) -> int:
@@ -209,9 +231,55 @@ class TorchMLPClassifier:
             if float(self.dropout) != 0.0 or float(self.input_dropout) != 0.0:
                 _lib.check(lib.mmc_trainer_set_dropout(self._h, float(self.input_dropout), float(self.dropout),
                                                        self._regularizer_seed_value()))
+            self._apply_optimizer_options()
         except Exception:
             self._release()
             raise
+
+    def _apply_optimizer_options(self) -> None:
+        """The optimiser options onto the trainer just created; a default makes no call.  The shadow of the averaged weights starts
+        as the parameters the trainer was created with, and a classifier that averages evaluates the average."""
+        lib = _lib.lib()
+        check_optimizer_options(self.lr_schedule, self.warmup_steps, self.schedule_steps, self.final_lr_ratio, self.max_grad_norm,
+                                self.ema_decay)
+        if self.lr_schedule != "constant" or int(self.warmup_steps) != 0:
+            if self.lr_schedule != "constant" and self.schedule_steps is None:
+                raise ValueError(f"lr_schedule={self.lr_schedule!r} needs schedule_steps, the step at which the decay ends "
+                                 f"(train_classifier / train_sweep fill it with nbr_epochs x the steps of an epoch).")
+            _lib.check(lib.mmc_trainer_set_lr_schedule(self._h, LR_KINDS[self.lr_schedule], int(self.warmup_steps),
+                                                       int(self.schedule_steps or 0), float(self.final_lr_ratio)))
+        if self.max_grad_norm is not None:
+            _lib.check(lib.mmc_trainer_set_grad_clip(self._h, float(self.max_grad_norm)))
+        if float(self.ema_decay) != 0.0:
+            _lib.check(lib.mmc_trainer_set_ema(self._h, float(self.ema_decay)))
+            if getattr(self, "_eval_weights", "averaged") == "averaged":
+                _lib.check(lib.mmc_trainer_eval_weights(self._h, _lib.MMC_WEIGHTS_AVERAGED))
+
+    def _averages(self) -> bool:
+        return float(getattr(self, "ema_decay", 0.0)) != 0.0
+
+    def use_weights(self, which: str) -> "TorchMLPClassifier":
+        """What evaluation reads from now on: "raw", the training weights, or "averaged" (``ema_decay > 0`` only; its default)."""
+        if which not in ("raw", "averaged"):
+            raise ValueError(f"which must be 'raw' or 'averaged', got {which!r}.")
+        if which == "averaged" and not self._averages():
+            raise ValueError("this classifier keeps no averaged weights (ema_decay is 0).")
+        self._eval_weights = which
+        if self._fitted():
+            _lib.check(_lib.lib().mmc_trainer_eval_weights(self._h, _lib.MMC_WEIGHTS_AVERAGED if which == "averaged"
+                                                           else _lib.MMC_WEIGHTS_RAW))
+        return self
+
+    def _read_grad_norms(self) -> None:
+        """``grad_norms_``: the pre-clip gradient norm of every step of the pass just made (clipping on only)."""
+        if getattr(self, "max_grad_norm", None) is None:
+            return
+        lib, steps = _lib.lib(), C.c_int(0)
+        _lib.check(lib.mmc_trainer_grad_norms(self._h, None, 0, C.byref(steps)))
+        out = np.empty(steps.value, np.float32)
+        if steps.value:
+            _lib.check(lib.mmc_trainer_grad_norms(self._h, out.ctypes.data, steps.value, C.byref(steps)))
+        self.grad_norms_ = out
 
     def _regularizer_seed_value(self) -> int:
         """The seed of the dropout masks and the mixing plans: ``regularizer_seed``, else ``random_state``, else one draw from numpy's
@@ -277,8 +345,7 @@ class TorchMLPClassifier:
             yo = np.ascontiguousarray(y_indices[order].astype(np.int32))
             _lib.check(_lib.lib().mmc_trainer_partial_fit(self._h, Xo.ctypes.data, yo.ctypes.data, n_samples, int(batch_size),
                                                           C.byref(avg), _current_stream_ptr(di)))
-        self.loss_curve_.append(float(avg.value))
-        self.n_iter_ += 1
+        self._end_pass(avg.value)
         return self
 
     def partial_fit_rows(self, fs, rows=None, classes: Sequence[Any] | None = None) -> "TorchMLPClassifier":
@@ -344,6 +411,7 @@ class TorchMLPClassifier:
     def _end_pass(self, avg: float) -> None:
         self.loss_curve_.append(float(avg))
         self.n_iter_ += 1
+        self._read_grad_norms()
 
     def fit(self, X, y) -> "TorchMLPClassifier":
         y_arr = np.asarray(y)
@@ -396,12 +464,30 @@ class TorchMLPClassifier:
 
     # ---- parameters ----------------------------------------------------------------------------------------------
     def parameters(self):
-        """-> (weights, biases): lists of float32 arrays in ``nn.Linear`` layout, read back from the device."""
+        """-> (weights, biases): lists of float32 arrays in ``nn.Linear`` layout, read back from the device -- the weights that
+        evaluation reads: the averaged ones of a classifier with ``ema_decay > 0`` (unless ``use_weights("raw")``), else the raw ones."""
+        if self._averages() and getattr(self, "_eval_weights", "averaged") == "averaged":
+            return self.averaged_parameters()
+        return self.raw_parameters()
+
+    def raw_parameters(self):
+        """-> (weights, biases) that the training steps read and write, whatever evaluation reads."""
         if not self._fitted():
             raise RuntimeError("TorchMLPClassifier is not fitted.")
         ws = [np.empty((o, i), np.float32) for i, o in zip(self._dims[:-1], self._dims[1:])]
         bs = [np.empty((o,), np.float32) for o in self._dims[1:]]
         _lib.check(_lib.lib().mmc_trainer_get_params(self._h, _ptr_array(ws), _ptr_array(bs)))
+        return ws, bs
+
+    def averaged_parameters(self):
+        """-> (weights, biases) of the exponential average (``ema_decay > 0`` only)."""
+        if not self._fitted():
+            raise RuntimeError("TorchMLPClassifier is not fitted.")
+        if not self._averages():
+            raise ValueError("this classifier keeps no averaged weights (ema_decay is 0).")
+        ws = [np.empty((o, i), np.float32) for i, o in zip(self._dims[:-1], self._dims[1:])]
+        bs = [np.empty((o,), np.float32) for o in self._dims[1:]]
+        _lib.check(_lib.lib().mmc_trainer_ema_state(self._h, 0, _ptr_array(ws), _ptr_array(bs)))
         return ws, bs
 
     @property
@@ -439,6 +525,8 @@ class TorchMLPClassifier:
             _lib.check(_lib.lib().mmc_trainer_adam_state(self._h, which, 0, _ptr_array(ws), _ptr_array(bs), C.byref(step)))
             out[name] = (ws, bs)
         out["step"] = int(step.value)
+        if self._averages():
+            out["ema"] = self.averaged_parameters()
         return out
 
     def get_params(self, deep: bool = True) -> dict:
@@ -448,7 +536,9 @@ class TorchMLPClassifier:
                 "beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon,
                 "class_weight": getattr(self, "class_weight", None), "label_smoothing": self.label_smoothing,
                 "focal_gamma": self.focal_gamma, "logit_prior": self.logit_prior, "dropout": self.dropout,
-                "input_dropout": self.input_dropout, "mixup_alpha": self.mixup_alpha, "regularizer_seed": self.regularizer_seed}
+                "input_dropout": self.input_dropout, "mixup_alpha": self.mixup_alpha, "regularizer_seed": self.regularizer_seed,
+                "lr_schedule": self.lr_schedule, "warmup_steps": self.warmup_steps, "schedule_steps": self.schedule_steps,
+                "final_lr_ratio": self.final_lr_ratio, "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay}
 
     def set_params(self, **params: Any) -> "TorchMLPClassifier":
         for key, value in params.items():
@@ -461,7 +551,7 @@ class TorchMLPClassifier:
     def __getstate__(self) -> dict:
         state = {k: v for k, v in self.__dict__.items() if k != "_h"}
         if self._fitted():
-            state["_module_state"] = self.parameters()
+            state["_module_state"] = self.raw_parameters()
             state["_optimizer_state"] = self._adam_state()
         return state
 
@@ -472,7 +562,10 @@ class TorchMLPClassifier:
         # a pickle made before the loss options existed loads as the plain loss
         # ... and one made before the regularisers existed as a classifier without them
         for key, default in (("label_smoothing", 0.0), ("focal_gamma", 0.0), ("logit_prior", None), ("_logit_prior_vector", None),
-                             ("dropout", 0.0), ("input_dropout", 0.0), ("mixup_alpha", 0.0), ("regularizer_seed", None)):
+                             ("dropout", 0.0), ("input_dropout", 0.0), ("mixup_alpha", 0.0), ("regularizer_seed", None),
+                             # ... and one made before the optimiser options existed with the constant rate, unclipped, unaveraged
+                             ("lr_schedule", "constant"), ("warmup_steps", 0), ("schedule_steps", None), ("final_lr_ratio", 0.0),
+                             ("max_grad_norm", None), ("ema_decay", 0.0)):
             self.__dict__.setdefault(key, default)
         self._h = None
         if params is not None:
@@ -482,6 +575,9 @@ class TorchMLPClassifier:
                 for which, name in ((0, "exp_avg"), (1, "exp_avg_sq")):
                     ws, bs = opt[name]
                     _lib.check(_lib.lib().mmc_trainer_adam_state(self._h, which, 1, _ptr_array(ws), _ptr_array(bs), C.byref(step)))
+                if self._averages() and opt.get("ema") is not None:   # without one the shadow stays the parameters just loaded
+                    ws, bs = opt["ema"]
+                    _lib.check(_lib.lib().mmc_trainer_ema_state(self._h, 1, _ptr_array(ws), _ptr_array(bs)))
 
     def _release(self) -> None:
         if self._fitted():

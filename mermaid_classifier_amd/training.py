@@ -131,6 +131,15 @@ def _contiguous_batches(n_rows: int, batch_size: int) -> Callable[[int], Iterabl
     return batches
 
 
+def _fill_schedule_steps(clf, batches, nbr_epochs: int) -> None:
+    """A decaying ``lr_schedule`` whose ``schedule_steps`` is None ends with the budget: ``nbr_epochs`` x the Adam steps of the
+    classifier's own epoch, counted on ``batches(0)`` (``optim.steps_per_epoch``).  Anything else is left alone."""
+    if getattr(clf, "lr_schedule", "constant") == "constant" or getattr(clf, "schedule_steps", None) is not None:
+        return
+    from .optim import steps_per_epoch
+    clf.schedule_steps = int(nbr_epochs) * steps_per_epoch(batches(0), clf.batch_size)
+
+
 def _check_splits(train, ref, val, batch_size) -> None:
     if int(batch_size) < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size!r}")
@@ -174,7 +183,10 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
     ``logit_scaling``: a kind string (``"temperature"`` / ``"bias"`` / ``"vector"``) or a fitted ``LogitScaling``.  After the epoch loop
     and the best-snapshot restore the scaling is fitted on ``ref`` (``logit_scaling.fit_logit_scaling``) and folded into the last
     layer, and ``calibrate`` runs on the folded classifier; the model carries it as ``logit_scaling_``.  Early stopping and the
-    per-epoch evaluation keep reading raw logits.  With ``transform=`` the scaling goes into the last layer and the transform into the
+    per-epoch evaluation keep reading raw logits.
+
+    A ``clf`` with a decaying ``lr_schedule`` and ``schedule_steps=None`` gets ``nbr_epochs`` x its steps per epoch (counted on
+    ``batches(0)``); one with ``ema_decay > 0`` is evaluated, early-stopped, scaled and calibrated on its averaged weights.  With ``transform=`` the scaling goes into the last layer and the transform into the
     first -- on a head with no hidden layer the scaling first, then the transform.  ``None`` changes no call."""
     _check_splits(train, ref, val, batch_size)
     if logit_scaling is not None:
@@ -200,6 +212,7 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
     classes = ref.classes.tolist()
     if batches is None:
         batches = _contiguous_batches(len(train), int(batch_size))
+    _fill_schedule_steps(clf, batches, nbr_epochs)
     ref_accs: List[float] = []
 
     def train_epoch(c, epoch):
