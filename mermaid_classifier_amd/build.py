@@ -29,16 +29,16 @@ SOURCES = {
     "k_early.hip": KERNEL_HEADERS,
     "k_mid.hip": KERNEL_HEADERS,
     "k_tail.hip": KERNEL_HEADERS,
-    "trainer.hip": ["../../include/mmc.h", "trainer_internal.h", "kernels.h", "philox.h"],
-    "calib.hip": ["../../include/mmc.h", "trainer_internal.h"],
-    "featureset.hip": ["../../include/mmc.h", "trainer_internal.h"],
-    "features.hip": ["../../include/mmc.h", "trainer_internal.h"],
-    "neighbors.hip": ["../../include/mmc.h", "trainer_internal.h"],
-    "logit_scaling.hip": ["../../include/mmc.h", "trainer_internal.h", "logit_newton.h"],
+    "trainer.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h", "kernels.h", "philox.h"],
+    "calib.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
+    "featureset.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
+    "features.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
+    "neighbors.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
+    "logit_scaling.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h", "logit_newton.h"],
     "metrics.hip": ["kernels.h"],
     "cover.hip": ["kernels.h", "topk_key.h"],
-    "mmc_api.cpp": ["kernels.h", "api_internal.h", "backbone_pack.h", "../../include/mmc.h"],
-    "mmc_head.cpp": ["kernels.h", "api_internal.h", "trainer_internal.h", "../../include/mmc.h"],
+    "mmc_api.cpp": ["kernels.h", "api_internal.h", "device_mem.h", "backbone_pack.h", "../../include/mmc.h"],
+    "mmc_head.cpp": ["kernels.h", "api_internal.h", "trainer_internal.h", "device_mem.h", "../../include/mmc.h"],
     "mmc_dist.cpp": ["../../include/mmc.h"],
 }
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",

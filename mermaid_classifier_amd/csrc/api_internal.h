@@ -7,20 +7,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mmc.h"
-
-// sets the thread-local message mmc_last_error() returns and hands back `code` (defined in mmc_api.cpp)
-int mmc_fail(int code, const char* fmt, ...);
+#include "device_mem.h"   // mmc_fail, HIP_TRY
 
 template <class... A>
 static inline int fail(int code, const char* fmt, A... args)
 {
     return mmc_fail(code, fmt, args...);
 }
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));    \
-    } while (0)
 #define KTRY(expr)                                                                                 \
     do {                                                                                           \
         int r_ = (expr);                                                                           \

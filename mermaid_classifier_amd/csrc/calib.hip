@@ -37,6 +37,7 @@
 
 #include <cfloat>
 #include <cmath>
+#include <utility>
 #include <vector>
 
 #include "../../include/mmc.h"
@@ -386,20 +387,14 @@ __global__ __launch_bounds__(256) void platt_step_kernel(const double* __restric
 struct mmc_calibrator {
     int K = 0, device = 0;
     int64_t n = 0, cap = 0;          // rows stored / rows allocated per class
-    float* P = nullptr;              // [K][cap] class-major probabilities / scores
-    int32_t* y = nullptr;            // [cap]
-    double* S = nullptr;             // add_scores staging [kTrainerForwardRows][K]
-    double *stats = nullptr, *part = nullptr;
-    PlattState* st = nullptr;
-    int *active = nullptr, *n_active = nullptr;
+    DevBuf<float> P;                 // [K][cap] class-major probabilities / scores
+    DevBuf<int32_t> y;               // [cap]
+    DevBuf<double> S;                // add_scores staging [kTrainerForwardRows][K]
+    DevBuf<double> stats, part;
+    DevBuf<PlattState> st;
+    DevBuf<int> active, n_active;
     int* n_active_host = nullptr;    // pinned
 };
-
-#define C_TRY(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return mmc_fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
 
 int check_labels(const int32_t* y, int64_t n, int K)
 {
@@ -414,22 +409,17 @@ static int calib_reserve(mmc_calibrator* c, int64_t need, hipStream_t st)
     if (need <= c->cap) return MMC_OK;
     int64_t cap = c->cap * 2 > need ? c->cap * 2 : need;
     cap = (cap + 1023) / 1024 * 1024;
-    float* P = nullptr;
-    int32_t* y = nullptr;
-    C_TRY(hipMalloc((void**)&P, (size_t)c->K * cap * 4));
-    if (hipMalloc((void**)&y, (size_t)cap * 4) != hipSuccess) {
-        hipFree(P);
-        return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld labels failed", (long long)cap);
-    }
+    DevBuf<float> P;
+    DevBuf<int32_t> y;
+    if (int r = P.reserve((int64_t)c->K * cap)) return r;
+    if (!y.alloc(cap)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld labels failed", (long long)cap);
     if (c->n) {
-        C_TRY(hipMemcpy2DAsync(P, (size_t)cap * 4, c->P, (size_t)c->cap * 4, (size_t)c->n * 4, (size_t)c->K, hipMemcpyDeviceToDevice, st));
-        C_TRY(hipMemcpyAsync(y, c->y, (size_t)c->n * 4, hipMemcpyDeviceToDevice, st));
-        C_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy2DAsync(P, (size_t)cap * 4, c->P, (size_t)c->cap * 4, (size_t)c->n * 4, (size_t)c->K, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(y, c->y, (size_t)c->n * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
-    hipFree(c->P);
-    hipFree(c->y);
-    c->P = P;
-    c->y = y;
+    c->P = std::move(P);
+    c->y = std::move(y);
     c->cap = cap;
     return MMC_OK;
 }
@@ -438,8 +428,6 @@ extern "C" void mmc_calibrator_destroy(mmc_calibrator* c)
 {
     if (!c) return;
     hipSetDevice(c->device);
-    hipFree(c->P); hipFree(c->y); hipFree(c->S); hipFree(c->stats); hipFree(c->part); hipFree(c->st); hipFree(c->active);
-    hipFree(c->n_active);
     hipHostFree(c->n_active_host);
     delete c;
 }
@@ -449,18 +437,13 @@ extern "C" int mmc_calibrator_create(int K, int device, mmc_calibrator** out)
     if (!out) return mmc_fail(MMC_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (K < 3) return mmc_fail(MMC_ERR_ARG, "K = %d: the calibrated head is multiclass only (K >= 3)", K);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return mmc_fail(MMC_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return mmc_fail(MMC_ERR_ARG, "device %d out of range (%d visible)", device, ndev);
-    C_TRY(hipSetDevice(device));
+    if (int r = check_device(device)) return r;
+    HIP_TRY(hipSetDevice(device));
     mmc_calibrator* c = new mmc_calibrator();
     c->K = K;
     c->device = device;
     const size_t slots = (size_t)K * kPlattMaxChunks;
-    bool ok = hipMalloc((void**)&c->stats, slots * 2 * 8) == hipSuccess && hipMalloc((void**)&c->part, slots * 6 * 8) == hipSuccess &&
-              hipMalloc((void**)&c->st, (size_t)K * sizeof(PlattState)) == hipSuccess &&
-              hipMalloc((void**)&c->active, (size_t)K * 4) == hipSuccess && hipMalloc((void**)&c->n_active, 4) == hipSuccess &&
+    bool ok = c->stats.alloc(slots * 2) && c->part.alloc(slots * 6) && c->st.alloc(K) && c->active.alloc(K) && c->n_active.alloc(1) &&
               hipHostMalloc((void**)&c->n_active_host, 4, hipHostMallocDefault) == hipSuccess;
     if (!ok) {
         mmc_calibrator_destroy(c);
@@ -481,7 +464,7 @@ extern "C" int mmc_calibrator_add_features(mmc_calibrator* c, mmc_trainer* t, co
     int r = check_labels(y, n, c->K);
     if (r) return r;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    C_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     r = calib_reserve(c, c->n + n, st);
     if (r) return r;
     const int d0 = trainer_input_dim(t);
@@ -491,10 +474,10 @@ extern "C" int mmc_calibrator_add_features(mmc_calibrator* c, mmc_trainer* t, co
         r = trainer_forward(t, X + (size_t)off * d0, cur, st, &z);
         if (r) return r;
         hipLaunchKernelGGL(softmax_store_kernel, dim3((cur + 63) / 64), dim3(256), 0, st, z, cur, c->K, c->P, c->cap, c->n + off);
-        C_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    C_TRY(hipMemcpyAsync(c->y + c->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    C_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(c->y + c->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     c->n += n;
     return MMC_OK;
 }
@@ -529,7 +512,7 @@ extern "C" int mmc_calibrator_add_set(mmc_calibrator* c, mmc_trainer* t, mmc_fea
     if (r) return r;
     if (n == 0) return MMC_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    C_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     r = calib_reserve(c, c->n + n, st);
     if (r) return r;
     for (int64_t off = 0; off < n; off += kTrainerForwardRows) {
@@ -538,10 +521,10 @@ extern "C" int mmc_calibrator_add_set(mmc_calibrator* c, mmc_trainer* t, mmc_fea
         r = trainer_forward_device(t, fs->X + (size_t)(first + off) * fs->dim, cur, st, &z);
         if (r) return r;
         hipLaunchKernelGGL(softmax_store_kernel, dim3((cur + 63) / 64), dim3(256), 0, st, z, cur, c->K, c->P, c->cap, c->n + off);
-        C_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    C_TRY(hipMemcpyAsync(c->y + c->n, fs->y + first, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    C_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(c->y + c->n, fs->y + first, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     c->n += n;
     return MMC_OK;
 }
@@ -561,20 +544,20 @@ extern "C" int mmc_calibrator_add_scores(mmc_calibrator* c, const double* scores
             return mmc_fail(MMC_ERR_ARG, "scores[%lld][%d] = %g is outside the fp32 range", (long long)(i / c->K), (int)(i % c->K), scores[i]);
     }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    C_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     r = calib_reserve(c, c->n + n, st);
     if (r) return r;
-    if (!c->S) C_TRY(hipMalloc((void**)&c->S, (size_t)kTrainerForwardRows * c->K * 8));
+    if ((r = c->S.reserve((int64_t)kTrainerForwardRows * c->K))) return r;
     for (int64_t off = 0; off < n; off += kTrainerForwardRows) {
         const int cur = (int)((n - off) < kTrainerForwardRows ? (n - off) : kTrainerForwardRows);
-        C_TRY(hipMemcpyAsync(c->S, scores + (size_t)off * c->K, (size_t)cur * c->K * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->S, scores + (size_t)off * c->K, (size_t)cur * c->K * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(scores_store_kernel, dim3((cur + 63) / 64, (c->K + 63) / 64), dim3(256), 0, st, c->S, cur, c->K, c->P, c->cap,
                            c->n + off);
-        C_TRY(hipGetLastError());
-        C_TRY(hipStreamSynchronize(st));   // the staging buffer is reused by the next chunk
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));   // the staging buffer is reused by the next chunk
     }
-    C_TRY(hipMemcpyAsync(c->y + c->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    C_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(c->y + c->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     c->n += n;
     return MMC_OK;
 }
@@ -585,7 +568,7 @@ extern "C" int mmc_calibrator_fit(mmc_calibrator* c, double* a, double* b, int32
     if (!a || !b) return mmc_fail(MMC_ERR_ARG, "a/b is NULL");
     if (c->n < 1) return mmc_fail(MMC_ERR_ARG, "fit with no rows: add features or scores first");
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    C_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     const int64_t N = c->n;
     int G = (int)((N + kPlattChunkRows - 1) / kPlattChunkRows);
     G = G < kPlattMaxChunks ? G : kPlattMaxChunks;
@@ -595,20 +578,20 @@ extern "C" int mmc_calibrator_fit(mmc_calibrator* c, double* a, double* b, int32
     const int K = c->K;
     hipLaunchKernelGGL(platt_stats_kernel, dim3(K, G), dim3(256), 0, st, c->P, c->cap, c->y, N, chunk, c->stats);
     hipLaunchKernelGGL(platt_init_kernel, dim3(1), dim3(256), 0, st, c->stats, K, G, N, c->st, c->active, c->n_active);
-    C_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     int n_active = K;
     for (int pass = 0; n_active > 0; ++pass) {
         if (pass > kPlattMaxIter + 1) return mmc_fail(MMC_ERR_HIP, "Platt fit did not stop after %d passes", pass);
         hipLaunchKernelGGL(platt_pass_kernel, dim3(n_active, G), dim3(256), 0, st, c->P, c->cap, c->y, N, chunk, c->active, c->st, c->part);
         hipLaunchKernelGGL(platt_step_kernel, dim3(1), dim3(256), 0, st, c->part, K, G, N, c->st, c->active, c->n_active);
-        C_TRY(hipGetLastError());
-        C_TRY(hipMemcpyAsync(c->n_active_host, c->n_active, 4, hipMemcpyDeviceToHost, st));
-        C_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->n_active_host, c->n_active, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         n_active = *c->n_active_host;
     }
     std::vector<PlattState> h(K);
-    C_TRY(hipMemcpyAsync(h.data(), c->st, (size_t)K * sizeof(PlattState), hipMemcpyDeviceToHost, st));
-    C_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h.data(), c->st, (size_t)K * sizeof(PlattState), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int k = 0; k < K; ++k) {
         a[k] = h[k].A * h[k].inv_scale;   // the slope back on the caller's scale of F
         b[k] = h[k].B;
@@ -634,7 +617,7 @@ static int trainer_evaluate(mmc_trainer* t, const float* X, const int32_t* y, in
     int r = check_labels(y, n, K);
     if (r) return r;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    C_TRY(hipSetDevice(trainer_device(t)));
+    HIP_TRY(hipSetDevice(trainer_device(t)));
     // scratch: slab [max_nb][2] int64, the two totals, then the chunk's labels
     const int max_nb = (kTrainerForwardRows + 3) / 4;
     void* scratch = nullptr;
@@ -652,12 +635,12 @@ static int trainer_evaluate(mmc_trainer* t, const float* X, const int32_t* y, in
         long long h[2];
         r = trainer_forward(t, X + (size_t)off * d0, cur, st, &z);
         if (r) return r;
-        C_TRY(hipMemcpyAsync(dy, y + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dy, y + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(eval_rows_kernel<false>, dim3(nb), dim3(256), 0, st, z, dy, cur, K, slab, (unsigned long long*)nullptr);
         hipLaunchKernelGGL(eval_finalize_kernel<false>, dim3(1), dim3(256), 0, st, slab, nb, totals);
-        C_TRY(hipGetLastError());
-        C_TRY(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
-        C_TRY(hipStreamSynchronize(st));   // before the next chunk reuses the labels / slab
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));   // before the next chunk reuses the labels / slab
         tot[0] += h[0];
         tot[1] += h[1];
     }
@@ -702,14 +685,14 @@ extern "C" int mmc_trainer_evaluate_set_q32(mmc_trainer* t, mmc_featureset* fs, 
     if (n == 0) return MMC_OK;
     const int K = trainer_classes(t);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    C_TRY(hipSetDevice(trainer_device(t)));
+    HIP_TRY(hipSetDevice(trainer_device(t)));
     const int max_nb = (kTrainerForwardRows + 3) / 4;
     void* scratch = nullptr;
     r = trainer_scratch(t, ((size_t)max_nb * 2 + 2) * 8, &scratch);   // slab [max_nb][2] int64, then the two totals
     if (r) return r;
     long long* slab = static_cast<long long*>(scratch);
     long long* totals = slab + 2 * max_nb;
-    C_TRY(hipMemsetAsync(totals, 0, 16, st));
+    HIP_TRY(hipMemsetAsync(totals, 0, 16, st));
     for (int64_t off = 0; off < n; off += kTrainerForwardRows) {
         const int cur = (int)((n - off) < kTrainerForwardRows ? (n - off) : kTrainerForwardRows);
         const int nb = (cur + 3) / 4;
@@ -719,11 +702,11 @@ extern "C" int mmc_trainer_evaluate_set_q32(mmc_trainer* t, mmc_featureset* fs, 
         hipLaunchKernelGGL(eval_rows_kernel<false>, dim3(nb), dim3(256), 0, st, z, fs->y + first + off, cur, K, slab,
                            (unsigned long long*)nullptr);
         hipLaunchKernelGGL(eval_finalize_kernel<true>, dim3(1), dim3(256), 0, st, slab, nb, totals);
-        C_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     long long h[2] = {0, 0};
-    C_TRY(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
-    C_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *n_correct = h[0];
     *sum_log_loss_q32 = h[1];
     return MMC_OK;
@@ -764,7 +747,7 @@ static int trainer_evaluate_classes(mmc_trainer* t, const float* X, const int32_
         if (r) return r;
     }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    C_TRY(hipSetDevice(trainer_device(t)));
+    HIP_TRY(hipSetDevice(trainer_device(t)));
     const int max_nb = (kTrainerForwardRows + 3) / 4;
     void* scratch = nullptr;
     r = trainer_scratch(t, ((size_t)max_nb * 2 + 2 + cells) * 8 + (from_set ? 0 : (size_t)kTrainerForwardRows * 4), &scratch);
@@ -774,7 +757,7 @@ static int trainer_evaluate_classes(mmc_trainer* t, const float* X, const int32_
     unsigned long long* table = reinterpret_cast<unsigned long long*>(totals + 2);
     int32_t* dy = reinterpret_cast<int32_t*>(table + cells);   // (host-fed only)
     const int d0 = trainer_input_dim(t);
-    C_TRY(hipMemsetAsync(totals, 0, (2 + cells) * 8, st));
+    HIP_TRY(hipMemsetAsync(totals, 0, (2 + cells) * 8, st));
     for (int64_t off = 0; off < n; off += kTrainerForwardRows) {
         const int cur = (int)((n - off) < kTrainerForwardRows ? (n - off) : kTrainerForwardRows);
         const int nb = (cur + 3) / 4;
@@ -784,18 +767,18 @@ static int trainer_evaluate_classes(mmc_trainer* t, const float* X, const int32_
             r = trainer_forward_device(t, fs->X + (size_t)(first + off) * fs->dim, cur, st, &z);
             labels = fs->y + first + off;
         } else {
-            if (off) C_TRY(hipStreamSynchronize(st));   // the previous chunk has read the labels this one overwrites
+            if (off) HIP_TRY(hipStreamSynchronize(st));   // the previous chunk has read the labels this one overwrites
             r = trainer_forward(t, X + (size_t)off * d0, cur, st, &z);
         }
         if (r) return r;
-        if (!from_set) C_TRY(hipMemcpyAsync(dy, y + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
+        if (!from_set) HIP_TRY(hipMemcpyAsync(dy, y + off, (size_t)cur * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(eval_rows_kernel<true>, dim3(nb), dim3(256), 0, st, z, labels, cur, K, slab, table);
         hipLaunchKernelGGL(eval_finalize_kernel<true>, dim3(1), dim3(256), 0, st, slab, nb, totals);
-        C_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     std::vector<long long> h(2 + cells, 0);
-    C_TRY(hipMemcpyAsync(h.data(), totals, (2 + cells) * 8, hipMemcpyDeviceToHost, st));
-    C_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h.data(), totals, (2 + cells) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *n_correct = h[0];
     *sum_q32 = h[1];
     for (size_t i = 0; i < cells; ++i) confusion[i] = h[2 + i];

@@ -33,11 +33,6 @@ namespace {
 constexpr int COVER_LDS_ENTRIES = 6144;   // 48 KB of 64-bit counters per workgroup
 constexpr int COVER_REG_MAX_K = 512;      // classes per lane held in registers: 1, 2, 4 or 8
 
-#define C_LAUNCH_CHECK()                        \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
 
 typedef unsigned long long u64;
 
@@ -286,7 +281,7 @@ int launch_cover_count(const float* P, int64_t n, int K, const int64_t* offsets,
     if (n < 1 || K < 1 || n_groups < 1 || (n + 255) / 256 > 0x7FFFFFFFLL) return -18;
     hipLaunchKernelGGL(cover_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, n, K, offsets, n_groups, count, soft,
                        unusable);
-    C_LAUNCH_CHECK();
+    LAUNCH_CHECK();
     return 0;
 }
 
@@ -295,7 +290,7 @@ int launch_cover_em_init(const double* train_prior, int64_t n_groups, int K, dou
     const int64_t cells = n_groups * K;
     if (n_groups < 1 || K < 1 || (cells + 255) / 256 > 0x7FFFFFFFLL) return -18;
     hipLaunchKernelGGL(cover_em_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, train_prior, cells, K, pi, w);
-    C_LAUNCH_CHECK();
+    LAUNCH_CHECK();
     return 0;
 }
 
@@ -312,7 +307,7 @@ int launch_cover_em_pass(const float* P, int K, const int64_t* slab_row0, const 
     else if (K <= COVER_REG_MAX_K) COVER_PASS(8);
     else hipLaunchKernelGGL(cover_em_pass_wide_kernel, grid, block, 0, st, P, K, slab_row0, slab_group, offsets, n_slabs, w, part);
 #undef COVER_PASS
-    C_LAUNCH_CHECK();
+    LAUNCH_CHECK();
     return 0;
 }
 
@@ -322,7 +317,7 @@ int launch_cover_em_reduce(const double* part, const int64_t* group_slab0, const
     if (n_groups < 1 || n_groups > 0x7FFFFFFFLL || K < 1 || (K + 63) / 64 > 65535) return -18;
     hipLaunchKernelGGL(cover_em_reduce_kernel, dim3((unsigned)n_groups, (unsigned)((K + 63) / 64)), dim3(256), 0, st, part, group_slab0, offsets,
                        unusable, train_prior, strength, K, pi, w);
-    C_LAUNCH_CHECK();
+    LAUNCH_CHECK();
     return 0;
 }
 
@@ -331,6 +326,6 @@ int launch_cover_adapt_topk(const float* P, int64_t n, int K, const int64_t* off
 {
     if (n < 1 || K < 1 || n_groups < 1 || k < 1 || k > K || !idx || !scores || (n + 3) / 4 > 0x7FFFFFFFLL) return -18;
     hipLaunchKernelGGL(cover_adapt_topk_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, P, n, K, offsets, n_groups, w, k, idx, scores);
-    C_LAUNCH_CHECK();
+    LAUNCH_CHECK();
     return 0;
 }

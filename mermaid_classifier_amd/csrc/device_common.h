@@ -161,12 +161,6 @@ static __device__ __forceinline__ T gload(const GLOBAL_AS void* base, unsigned b
 // No global data is exchanged between the threads of this kernel, so the LDS-only form is sufficient.
 #define T7_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-#define LAUNCH_CHECK()                          \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
-
 // Raises Kernel's dynamic LDS limit to `bytes`, once per device: one flag per kernel instantiation and device index, atomic
 // because handles on several devices may launch from several threads (a race costs a repeated call, nothing else).  Whether
 // this runtime keeps the attribute per device has not been measured; per device is the reading that cannot go wrong.

@@ -20,28 +20,9 @@
 #include "../../include/mmc.h"
 #include "trainer_internal.h"
 
-#define F_TRY(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return mmc_fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-// a per-call device allocation, freed on every way out
-struct DevMem {
-    char* p = nullptr;
-    ~DevMem() { if (p) hipFree(p); }
-    bool alloc(size_t bytes)
-    {
-        if (hipMalloc((void**)&p, bytes ? bytes : 1) == hipSuccess) return true;
-        (void)hipGetLastError();
-        p = nullptr;
-        return false;
-    }
-};
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -321,8 +302,8 @@ int put_output(void* dst, const void* host_src /* null: zeros */, size_t bytes, 
         else memset(dst, 0, bytes);
         return MMC_OK;
     }
-    if (host_src) F_TRY(hipMemcpyAsync(dst, host_src, bytes, hipMemcpyHostToDevice, st));
-    else F_TRY(hipMemsetAsync(dst, 0, bytes, st));
+    if (host_src) HIP_TRY(hipMemcpyAsync(dst, host_src, bytes, hipMemcpyHostToDevice, st));
+    else HIP_TRY(hipMemsetAsync(dst, 0, bytes, st));
     return MMC_OK;
 }
 
@@ -350,7 +331,7 @@ extern "C" int mmc_featureset_moments(mmc_featureset* fs, int64_t first, int64_t
     const int K = fs->K, dim = fs->dim;
     const size_t cells = (size_t)(K + 1) * dim;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    F_TRY(hipSetDevice(fs->device));
+    HIP_TRY(hipSetDevice(fs->device));
 
     // the slab table: a stable counting sort of the labels gives every class its rows in ascending order
     std::vector<int64_t> cnt;
@@ -384,7 +365,7 @@ extern "C" int mmc_featureset_moments(mmc_featureset* fs, int64_t first, int64_t
         if (!r) r = put_output(mean, nullptr, cells * 8, host, st);
         if (!r) r = put_output(m2, nullptr, cells * 8, host, st);
         if (r) return r;
-        F_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
         return MMC_OK;
     }
 
@@ -392,8 +373,8 @@ extern "C" int mmc_featureset_moments(mmc_featureset* fs, int64_t first, int64_t
     const size_t o_order = 0, o_slabs = o_order + align256((size_t)n * 4), o_off = o_slabs + align256(n_slabs * sizeof(Slab)),
                  o_cnt = o_off + align256(((size_t)K + 2) * 4), o_partial = o_cnt + align256(((size_t)K + 1) * 8),
                  o_mean = o_partial + align256(n_slabs * dim * 8), o_m2 = o_mean + align256(cells * 8), total = o_m2 + align256(cells * 8);
-    DevMem mem;
-    if (!mem.alloc(total)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes of moments scratch failed", total);
+    DevBuf<char> mem;   // a per-call device allocation, freed on every way out
+    if (!mem.alloc((int64_t)total)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes of moments scratch failed", total);
     int32_t* d_order = (int32_t*)(mem.p + o_order);
     Slab* d_slabs = (Slab*)(mem.p + o_slabs);
     int32_t* d_off = (int32_t*)(mem.p + o_off);
@@ -401,10 +382,10 @@ extern "C" int mmc_featureset_moments(mmc_featureset* fs, int64_t first, int64_t
     double* d_partial = (double*)(mem.p + o_partial);
     double* d_mean = host ? (double*)(mem.p + o_mean) : mean;
     double* d_m2 = host ? (double*)(mem.p + o_m2) : m2;
-    F_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    F_TRY(hipMemcpyAsync(d_slabs, slabs.data(), n_slabs * sizeof(Slab), hipMemcpyHostToDevice, st));
-    F_TRY(hipMemcpyAsync(d_off, slab_off.data(), ((size_t)K + 2) * 4, hipMemcpyHostToDevice, st));
-    F_TRY(hipMemcpyAsync(d_cnt, cnt.data(), ((size_t)K + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_slabs, slabs.data(), n_slabs * sizeof(Slab), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off, slab_off.data(), ((size_t)K + 2) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_cnt, cnt.data(), ((size_t)K + 1) * 8, hipMemcpyHostToDevice, st));
 
     const float* X = fs->X + (size_t)first * dim;
     const dim3 pass_grid((unsigned)n_slabs, (unsigned)((dim + 255) / 256)), red_grid((unsigned)(K + 1), (unsigned)((dim + 255) / 256));
@@ -412,15 +393,15 @@ extern "C" int mmc_featureset_moments(mmc_featureset* fs, int64_t first, int64_t
     moments_reduce_kernel<<<red_grid, 256, 0, st>>>(d_partial, d_off, d_cnt, dim, 1, d_mean);
     moments_pass_kernel<true><<<pass_grid, 256, 0, st>>>(X, dim, d_order, d_slabs, K, d_mean, d_partial);
     moments_reduce_kernel<<<red_grid, 256, 0, st>>>(d_partial, d_off, d_cnt, dim, 0, d_m2);
-    F_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (host) {
-        F_TRY(hipMemcpyAsync(mean, d_mean, cells * 8, hipMemcpyDeviceToHost, st));
-        F_TRY(hipMemcpyAsync(m2, d_m2, cells * 8, hipMemcpyDeviceToHost, st));
-        F_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(mean, d_mean, cells * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(m2, d_m2, cells * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         memcpy(counts, cnt.data(), (size_t)K * 8);
     } else {
-        F_TRY(hipMemcpyAsync(counts, d_cnt, (size_t)K * 8, hipMemcpyDeviceToDevice, st));
-        F_TRY(hipStreamSynchronize(st));   // the scratch is freed on return
+        HIP_TRY(hipMemcpyAsync(counts, d_cnt, (size_t)K * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));   // the scratch is freed on return
     }
     return MMC_OK;
 }
@@ -437,12 +418,12 @@ extern "C" int mmc_featureset_scatter(mmc_featureset* fs, int64_t first, int64_t
     if (dim > MMC_SCATTER_MAX_DIM) return mmc_fail(MMC_ERR_ARG, "dim = %d exceeds MMC_SCATTER_MAX_DIM = %d", dim, MMC_SCATTER_MAX_DIM);
     const bool in_host = flags & MMC_IN_HOST, out_host = flags & MMC_OUT_HOST;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    F_TRY(hipSetDevice(fs->device));
+    HIP_TRY(hipSetDevice(fs->device));
     const size_t out_bytes = (size_t)dim * dim * 8;
     if (n == 0) {
         const int r = put_output(scatter, nullptr, out_bytes, out_host, st);
         if (r) return r;
-        F_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
         return MMC_OK;
     }
     const int splits = scatter_splits(n, dim);
@@ -451,12 +432,12 @@ extern "C" int mmc_featureset_scatter(mmc_featureset* fs, int64_t first, int64_t
     const size_t centre_bytes = (size_t)(by_label ? fs->K : 1) * dim * 4;
     const size_t o_partial = 0, o_centres = o_partial + align256((size_t)splits * pairs * kST * kST * 8),
                  o_out = o_centres + align256(in_host ? centre_bytes : 0), total = o_out + align256(out_host ? out_bytes : 0);
-    DevMem mem;
-    if (!mem.alloc(total)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes of scatter scratch failed", total);
+    DevBuf<char> mem;   // a per-call device allocation, freed on every way out
+    if (!mem.alloc((int64_t)total)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes of scatter scratch failed", total);
     double* d_partial = (double*)(mem.p + o_partial);
     const float* d_centres = centres;
     if (in_host) {
-        F_TRY(hipMemcpyAsync(mem.p + o_centres, centres, centre_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(mem.p + o_centres, centres, centre_bytes, hipMemcpyHostToDevice, st));
         d_centres = (const float*)(mem.p + o_centres);
     }
     double* d_out = out_host ? (double*)(mem.p + o_out) : scatter;
@@ -467,9 +448,9 @@ extern "C" int mmc_featureset_scatter(mmc_featureset* fs, int64_t first, int64_t
     if (vec) scatter_kernel<true><<<grid, 256, 0, st>>>(X, y, d_centres, n, dim, chunks, splits, tiles, d_partial);
     else scatter_kernel<false><<<grid, 256, 0, st>>>(X, y, d_centres, n, dim, chunks, splits, tiles, d_partial);
     scatter_reduce_kernel<<<dim3((unsigned)pairs, kST * kST / 256), 256, 0, st>>>(d_partial, splits, tiles, dim, d_out);
-    F_TRY(hipGetLastError());
-    if (out_host) F_TRY(hipMemcpyAsync(scatter, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-    F_TRY(hipStreamSynchronize(st));   // the scratch is freed on return
+    HIP_TRY(hipGetLastError());
+    if (out_host) HIP_TRY(hipMemcpyAsync(scatter, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the scratch is freed on return
     return MMC_OK;
 }
 
@@ -489,19 +470,19 @@ extern "C" int mmc_featureset_transform(mmc_featureset* src, int64_t first, int6
     if (n == 0) return MMC_OK;
     const int dim = src->dim;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    F_TRY(hipSetDevice(src->device));
+    HIP_TRY(hipSetDevice(src->device));
     try {
         dst->y_host.reserve((size_t)(dst->n + n));
     } catch (const std::bad_alloc&) {
         return mmc_fail(MMC_ERR_NOMEM, "no host memory for %lld labels", (long long)(dst->n + n));
     }
-    DevMem mem;
+    DevBuf<char> mem;   // a per-call device allocation, freed on every way out
     const float *d_centre = centre, *d_T = T;
     if (flags & MMC_IN_HOST) {
         const size_t o_T = align256((size_t)dim * 4), total = o_T + align256((size_t)m * dim * 4);
-        if (!mem.alloc(total)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes for the transform's matrix failed", total);
-        F_TRY(hipMemcpyAsync(mem.p, centre, (size_t)dim * 4, hipMemcpyHostToDevice, st));
-        F_TRY(hipMemcpyAsync(mem.p + o_T, T, (size_t)m * dim * 4, hipMemcpyHostToDevice, st));
+        if (!mem.alloc((int64_t)total)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes for the transform's matrix failed", total);
+        HIP_TRY(hipMemcpyAsync(mem.p, centre, (size_t)dim * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(mem.p + o_T, T, (size_t)m * dim * 4, hipMemcpyHostToDevice, st));
         d_centre = (const float*)mem.p;
         d_T = (const float*)(mem.p + o_T);
     }
@@ -509,9 +490,9 @@ extern "C" int mmc_featureset_transform(mmc_featureset* src, int64_t first, int6
     if (r) return r;
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)((m + 63) / 64));
     transform_kernel<<<grid, 256, 0, st>>>(src->X + (size_t)first * dim, d_centre, d_T, dst->X + (size_t)dst->n * m, n, dim, m);
-    F_TRY(hipGetLastError());
-    F_TRY(hipMemcpyAsync(dst->y + dst->n, src->y + first, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    F_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dst->y + dst->n, src->y + first, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     dst->y_host.insert(dst->y_host.end(), src->y_host.begin() + first, src->y_host.begin() + first + n);   // the row count moves last
     dst->n += n;
     return MMC_OK;

@@ -12,47 +12,30 @@
 #include <stdint.h>
 
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/mmc.h"
 #include "trainer_internal.h"
-
-#define F_TRY(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return mmc_fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
 
 // room for `need` rows; the rows stored so far move on `st` (also features.hip's way to grow a set)
 int featureset_reserve(mmc_featureset* fs, int64_t need, hipStream_t st)
 {
     if (need <= fs->cap) return MMC_OK;
     const int64_t cap = fs->cap * 2 > need ? fs->cap * 2 : need;
-    float* X = nullptr;
-    int32_t* y = nullptr;
-    if (hipMalloc((void**)&X, (size_t)cap * fs->dim * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld x %d features failed", (long long)cap, fs->dim);
-    }
-    if (hipMalloc((void**)&y, (size_t)cap * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(X);
-        return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld labels failed", (long long)cap);
-    }
+    DevBuf<float> X;
+    DevBuf<int32_t> y;
+    if (!X.alloc(cap * fs->dim)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld x %d features failed", (long long)cap, fs->dim);
+    if (!y.alloc(cap)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld labels failed", (long long)cap);
     if (fs->n) {
         hipError_t e = hipMemcpyAsync(X, fs->X, (size_t)fs->n * fs->dim * 4, hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(y, fs->y, (size_t)fs->n * 4, hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            hipFree(X);
-            hipFree(y);
+        if (e != hipSuccess)
             return mmc_fail(MMC_ERR_HIP, "moving %lld rows to the grown feature set: %s", (long long)fs->n, hipGetErrorString(e));
-        }
     }
-    hipFree(fs->X);
-    hipFree(fs->y);
-    fs->X = X;
-    fs->y = y;
+    fs->X = std::move(X);
+    fs->y = std::move(y);
     fs->cap = cap;
     return MMC_OK;
 }
@@ -61,8 +44,6 @@ extern "C" void mmc_featureset_destroy(mmc_featureset* fs)
 {
     if (!fs) return;
     hipSetDevice(fs->device);
-    hipFree(fs->X);
-    hipFree(fs->y);
     delete fs;
 }
 
@@ -73,11 +54,8 @@ extern "C" int mmc_featureset_create(int dim, int n_classes, int device, int64_t
     if (dim < 1) return mmc_fail(MMC_ERR_ARG, "dim = %d must be positive", dim);
     if (n_classes < 1) return mmc_fail(MMC_ERR_ARG, "n_classes = %d must be positive", n_classes);
     if (reserve_rows < 0) return mmc_fail(MMC_ERR_ARG, "reserve_rows = %lld is negative", (long long)reserve_rows);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return mmc_fail(MMC_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return mmc_fail(MMC_ERR_ARG, "device %d out of range (%d visible)", device, ndev);
-    F_TRY(hipSetDevice(device));
+    if (int r = check_device(device)) return r;
+    HIP_TRY(hipSetDevice(device));
     mmc_featureset* fs = new mmc_featureset();
     fs->dim = dim;
     fs->K = n_classes;
@@ -106,7 +84,7 @@ extern "C" int mmc_featureset_append(mmc_featureset* fs, const float* X, const i
     for (int64_t i = 0; i < n; ++i)
         if (y[i] < 0 || y[i] >= fs->K) return mmc_fail(MMC_ERR_ARG, "label index y[%lld] = %d outside [0, %d)", (long long)i, y[i], fs->K);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    F_TRY(hipSetDevice(fs->device));
+    HIP_TRY(hipSetDevice(fs->device));
     try {
         fs->y_host.reserve((size_t)(fs->n + n));
     } catch (const std::bad_alloc&) {
@@ -114,10 +92,10 @@ extern "C" int mmc_featureset_append(mmc_featureset* fs, const float* X, const i
     }
     const int r = featureset_reserve(fs, fs->n + n, st);
     if (r) return r;
-    F_TRY(hipMemcpyAsync(fs->X + (size_t)fs->n * fs->dim, X, (size_t)n * fs->dim * 4,
+    HIP_TRY(hipMemcpyAsync(fs->X + (size_t)fs->n * fs->dim, X, (size_t)n * fs->dim * 4,
                          (flags & MMC_IN_HOST) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-    F_TRY(hipMemcpyAsync(fs->y + fs->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    F_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(fs->y + fs->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     fs->y_host.insert(fs->y_host.end(), y, y + n);   // the row count moves only once the rows are there
     fs->n += n;
     return MMC_OK;
@@ -131,9 +109,9 @@ extern "C" int mmc_featureset_read(mmc_featureset* fs, int64_t first, int64_t n,
                         (long long)fs->n);
     if (n == 0) return MMC_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    F_TRY(hipSetDevice(fs->device));
-    if (X) F_TRY(hipMemcpyAsync(X, fs->X + (size_t)first * fs->dim, (size_t)n * fs->dim * 4, hipMemcpyDeviceToHost, st));
-    if (y) F_TRY(hipMemcpyAsync(y, fs->y + first, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    F_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipSetDevice(fs->device));
+    if (X) HIP_TRY(hipMemcpyAsync(X, fs->X + (size_t)first * fs->dim, (size_t)n * fs->dim * 4, hipMemcpyDeviceToHost, st));
+    if (y) HIP_TRY(hipMemcpyAsync(y, fs->y + first, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return MMC_OK;
 }

@@ -3,6 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// after a launch, in a launch_* function: hands a launch error back as the function's result
+#define LAUNCH_CHECK()                          \
+    do {                                        \
+        hipError_t e__ = hipGetLastError();     \
+        if (e__ != hipSuccess) return (int)e__; \
+    } while (0)
+
 enum { EPI_SILU = 0, EPI_LINEAR = 1, EPI_GAP = 2 };
 
 // Each templated family keeps ONE table of its instantiations next to its launcher.  launch_<family>() dispatches on it and

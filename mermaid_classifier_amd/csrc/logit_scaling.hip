@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <utility>
 #include <vector>
 
 #include "../../include/mmc.h"
@@ -250,47 +251,30 @@ __global__ __launch_bounds__(256) void logitcal_hess_kernel(const double* __rest
 struct mmc_logitcal {
     int K = 0, device = 0;
     int64_t n = 0, cap = 0;          // rows stored / allocated
-    float* Z = nullptr;              // [cap][K] raw logits
-    int32_t* y = nullptr;            // [cap]
+    DevBuf<float> Z;                 // [cap][K] raw logits
+    DevBuf<int32_t> y;               // [cap]
     std::vector<int64_t> counts;     // rows per class
-    double *ac = nullptr, *sums = nullptr, *H = nullptr;   // [2K], [5K + 1], [2K][2K]
-    double* part = nullptr;          // the blocks' partials: sums, then tiles
-    size_t part_len = 0;             // doubles allocated
+    DevBuf<double> ac, sums, H;      // [2K], [5K + 1], [2K][2K]
+    DevBuf<double> part;             // the blocks' partials: sums, then tiles
 };
-
-#define L_TRY(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return mmc_fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
 
 static int logitcal_reserve(mmc_logitcal* c, int64_t need, hipStream_t st)
 {
     if (need <= c->cap) return MMC_OK;
     int64_t cap = c->cap * 2 > need ? c->cap * 2 : need;
     cap = (cap + 1023) / 1024 * 1024;
-    float* Z = nullptr;
-    int32_t* y = nullptr;
-    if (hipMalloc((void**)&Z, (size_t)cap * c->K * 4) != hipSuccess)
-        return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld x %d logits failed", (long long)cap, c->K);
-    if (hipMalloc((void**)&y, (size_t)cap * 4) != hipSuccess) {
-        hipFree(Z);
-        return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld labels failed", (long long)cap);
-    }
+    DevBuf<float> Z;
+    DevBuf<int32_t> y;
+    if (!Z.alloc(cap * c->K)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld x %d logits failed", (long long)cap, c->K);
+    if (!y.alloc(cap)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %lld labels failed", (long long)cap);
     if (c->n) {
         hipError_t e = hipMemcpyAsync(Z, c->Z, (size_t)c->n * c->K * 4, hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(y, c->y, (size_t)c->n * 4, hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            hipFree(Z);
-            hipFree(y);
-            return mmc_fail(MMC_ERR_HIP, "moving the logit store: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "moving the logit store: %s", hipGetErrorString(e));
     }
-    hipFree(c->Z);
-    hipFree(c->y);
-    c->Z = Z;
-    c->y = y;
+    c->Z = std::move(Z);
+    c->y = std::move(y);
     c->cap = cap;
     return MMC_OK;
 }
@@ -299,7 +283,6 @@ extern "C" void mmc_logitcal_destroy(mmc_logitcal* c)
 {
     if (!c) return;
     hipSetDevice(c->device);
-    hipFree(c->Z); hipFree(c->y); hipFree(c->ac); hipFree(c->sums); hipFree(c->H); hipFree(c->part);
     delete c;
 }
 
@@ -308,17 +291,13 @@ extern "C" int mmc_logitcal_create(int K, int device, mmc_logitcal** out)
     if (!out) return mmc_fail(MMC_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (K < 2 || K > kMaxK) return mmc_fail(MMC_ERR_ARG, "K = %d outside [2, %d]", K, kMaxK);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return mmc_fail(MMC_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return mmc_fail(MMC_ERR_ARG, "device %d out of range (%d visible)", device, ndev);
-    L_TRY(hipSetDevice(device));
+    if (int r = check_device(device)) return r;
+    HIP_TRY(hipSetDevice(device));
     mmc_logitcal* c = new mmc_logitcal();
     c->K = K;
     c->device = device;
     c->counts.assign(K, 0);
-    const bool ok = hipMalloc((void**)&c->ac, (size_t)2 * K * 8) == hipSuccess && hipMalloc((void**)&c->sums, sums_len(K) * 8) == hipSuccess &&
-                    hipMalloc((void**)&c->H, (size_t)4 * K * K * 8) == hipSuccess;
+    const bool ok = c->ac.alloc(2 * K) && c->sums.alloc((int64_t)sums_len(K)) && c->H.alloc((int64_t)4 * K * K);
     if (!ok) {
         mmc_logitcal_destroy(c);
         return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed while creating the logit calibrator");
@@ -348,7 +327,7 @@ extern "C" int mmc_logitcal_add_features(mmc_logitcal* c, mmc_trainer* t, const 
     r = check_labels(y, n, c->K);
     if (r) return r;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    L_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     r = logitcal_reserve(c, c->n + n, st);
     if (r) return r;
     const int d0 = trainer_input_dim(t);
@@ -357,10 +336,10 @@ extern "C" int mmc_logitcal_add_features(mmc_logitcal* c, mmc_trainer* t, const 
         const float* z = nullptr;
         r = trainer_forward(t, X + (size_t)off * d0, cur, st, &z);
         if (r) return r;
-        L_TRY(hipMemcpyAsync(c->Z + (size_t)(c->n + off) * c->K, z, (size_t)cur * c->K * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->Z + (size_t)(c->n + off) * c->K, z, (size_t)cur * c->K * 4, hipMemcpyDeviceToDevice, st));
     }
-    L_TRY(hipMemcpyAsync(c->y + c->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    L_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(c->y + c->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; ++i) ++c->counts[y[i]];
     c->n += n;
     return MMC_OK;
@@ -377,7 +356,7 @@ extern "C" int mmc_logitcal_add_set(mmc_logitcal* c, mmc_trainer* t, mmc_feature
     if (r) return r;
     if (n == 0) return MMC_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    L_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     r = logitcal_reserve(c, c->n + n, st);
     if (r) return r;
     for (int64_t off = 0; off < n; off += kTrainerForwardRows) {
@@ -385,10 +364,10 @@ extern "C" int mmc_logitcal_add_set(mmc_logitcal* c, mmc_trainer* t, mmc_feature
         const float* z = nullptr;
         r = trainer_forward_device(t, fs->X + (size_t)(first + off) * fs->dim, cur, st, &z);
         if (r) return r;
-        L_TRY(hipMemcpyAsync(c->Z + (size_t)(c->n + off) * c->K, z, (size_t)cur * c->K * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->Z + (size_t)(c->n + off) * c->K, z, (size_t)cur * c->K * 4, hipMemcpyDeviceToDevice, st));
     }
-    L_TRY(hipMemcpyAsync(c->y + c->n, fs->y + first, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    L_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(c->y + c->n, fs->y + first, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; ++i) ++c->counts[fs->y_host[(size_t)(first + i)]];
     c->n += n;
     return MMC_OK;
@@ -406,12 +385,12 @@ extern "C" int mmc_logitcal_add_logits(mmc_logitcal* c, const float* logits, con
         if (!std::isfinite(logits[i]))
             return mmc_fail(MMC_ERR_ARG, "logits[%lld][%d] = %g is not finite", (long long)(i / c->K), (int)(i % c->K), (double)logits[i]);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    L_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     r = logitcal_reserve(c, c->n + n, st);
     if (r) return r;
-    L_TRY(hipMemcpyAsync(c->Z + (size_t)c->n * c->K, logits, (size_t)n * c->K * 4, hipMemcpyHostToDevice, st));
-    L_TRY(hipMemcpyAsync(c->y + c->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    L_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(c->Z + (size_t)c->n * c->K, logits, (size_t)n * c->K * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->y + c->n, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; ++i) ++c->counts[y[i]];
     c->n += n;
     return MMC_OK;
@@ -432,32 +411,29 @@ static int logitcal_pass(mmc_logitcal* c, const double* a, const double* cc, dou
     if (nb64 > (int64_t)1 << 22) return mmc_fail(MMC_ERR_ARG, "%lld stored rows: more than 2^32", (long long)c->n);
     const int nb = (int)nb64;
     const size_t len_s = sums_len(K), need = (size_t)nb * len_s + (hess ? (size_t)nb * nt * 256 : 0);
-    if (need > c->part_len) {
-        double* p = nullptr;
-        if (hipMalloc((void**)&p, need * 8) != hipSuccess)
-            return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes of block partials failed", need * 8);
-        hipFree(c->part);
-        c->part = p;
-        c->part_len = need;
+    if ((int64_t)need > c->part.cap) {
+        DevBuf<double> p;
+        if (!p.alloc((int64_t)need)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes of block partials failed", need * 8);
+        c->part = std::move(p);
     }
     double* part_s = c->part;
     double* part_h = c->part + (size_t)nb * len_s;
     std::vector<double> host(P);
     for (int k = 0; k < K; ++k) { host[k] = a[k]; host[K + k] = cc[k]; }
-    L_TRY(hipMemcpyAsync(c->ac, host.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->ac, host.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
     if (hess) hipLaunchKernelGGL(logitcal_pass_kernel<true>, dim3(nb), dim3(512), 0, st, c->Z, c->y, c->n, K, c->ac, part_s, part_h);
     else hipLaunchKernelGGL(logitcal_pass_kernel<false>, dim3(nb), dim3(512), 0, st, c->Z, c->y, c->n, K, c->ac, part_s, (double*)nullptr);
-    L_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(logitcal_sums_kernel, dim3(((int)len_s + 255) / 256), dim3(256), 0, st, part_s, nb, (int)len_s, c->sums);
-    L_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (hess) {
         hipLaunchKernelGGL(logitcal_hess_kernel, dim3(nt), dim3(256), 0, st, part_h, nb, K, c->sums, c->H);
-        L_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     std::vector<double> sums(len_s);
-    L_TRY(hipMemcpyAsync(sums.data(), c->sums, len_s * 8, hipMemcpyDeviceToHost, st));
-    if (hess) L_TRY(hipMemcpyAsync(hess, c->H, (size_t)P * P * 8, hipMemcpyDeviceToHost, st));
-    L_TRY(hipStreamSynchronize(st));   // (also before `host` leaves scope)
+    HIP_TRY(hipMemcpyAsync(sums.data(), c->sums, len_s * 8, hipMemcpyDeviceToHost, st));
+    if (hess) HIP_TRY(hipMemcpyAsync(hess, c->H, (size_t)P * P * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (also before `host` leaves scope)
     for (int i = 0; i < P; ++i) grad[i] = sums[i];
     *nll = sums[5 * K];
     return MMC_OK;
@@ -472,7 +448,7 @@ extern "C" int mmc_logitcal_stats(mmc_logitcal* c, const double* a, const double
     int r = check_finite_params(a, cc, c->K);
     if (r) return r;
     if (c->n < 1) return mmc_fail(MMC_ERR_ARG, "stats with no rows: add features or logits first");
-    L_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     r = logitcal_pass(c, a, cc, nll_sum, grad, hess, static_cast<hipStream_t>(hip_stream));
     if (r) return r;
     if (counts)
@@ -493,7 +469,7 @@ extern "C" int mmc_logitcal_fit(mmc_logitcal* c, int mode, double l2, double tol
     if (max_trials < 1 || max_trials > 1000) return mmc_fail(MMC_ERR_ARG, "max_trials = %d outside [1, 1000]", max_trials);
     if (c->n < 1) return mmc_fail(MMC_ERR_ARG, "fit with no rows: add features or logits first");
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    L_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     const int K = c->K;
     std::vector<uint8_t> fz(K);
     logit_newton::frozen_mask(K, mode, c->counts.data(), fz.data());

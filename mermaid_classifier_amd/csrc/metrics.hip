@@ -47,11 +47,6 @@ constexpr int GROUP_CLS_LDS_MAX_K = 1024;    // 3 x K x 8 B of per-class sums in
 constexpr int GROUP_LDS_HIST = 8192;         // counters of a select level kept in LDS (32 KB)
 constexpr int GROUP_COVER_CHUNKS = 1024;     // at most this many image chunks
 
-#define M_LAUNCH_CHECK()                        \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
 
 template <bool CLS_IN_LDS>
 __global__ __launch_bounds__(256) void group_rows_kernel(GroupRowsArgs a)
@@ -374,7 +369,7 @@ int launch_group_rows(const GroupRowsArgs& a, hipStream_t st)
     const int grid = (a.rows + 1023) / 1024;   // a workgroup walks about 1024 rows before it flushes its per-class sums
     if (a.K <= GROUP_CLS_LDS_MAX_K) hipLaunchKernelGGL((group_rows_kernel<true>), dim3(grid), dim3(256), (size_t)3 * a.K * 8, st, a);
     else hipLaunchKernelGGL((group_rows_kernel<false>), dim3(grid), dim3(256), 0, st, a);
-    M_LAUNCH_CHECK();
+    LAUNCH_CHECK();
     return 0;
 }
 
@@ -398,7 +393,7 @@ int launch_group_cover(const int32_t* true_cnt, const int32_t* pred_cnt, const i
     hipLaunchKernelGGL(cover_reduce1_kernel, dim3((K + 255) / 256), dim3(256), 0, st, slab, chunks, K, cov, n_used);
     hipLaunchKernelGGL(cover_pass2_kernel, grid, dim3(64), 0, st, true_cnt, points, n_images, K, pc, cov, n_used, slab);
     hipLaunchKernelGGL(cover_reduce2_kernel, dim3((K + 255) / 256), dim3(256), 0, st, slab, chunks, K, cov);
-    M_LAUNCH_CHECK();
+    LAUNCH_CHECK();
     return 0;
 }
 
@@ -416,7 +411,7 @@ static int select_levels(const uint32_t* keys, int64_t n, GroupSelect* sel, uint
     }
     if (hipMemsetAsync(raw, 0, (size_t)4 * GROUP_MAX_TARGETS * 8, st) != hipSuccess) return (int)hipGetLastError();
     hipLaunchKernelGGL(bin_sums_kernel, dim3(pass_grid(n)), dim3(256), 0, st, keys, n, sel, raw);
-    M_LAUNCH_CHECK();
+    LAUNCH_CHECK();
     return 0;
 }
 
@@ -434,7 +429,7 @@ int launch_group_category_counts(const unsigned long long* support, const int32_
     if (!support || !category_of_class || K < 1 || n_categories < 1 || n_categories > GROUP_MAX_CATEGORIES || !cat_rows || !cat_bins) return -19;
     hipLaunchKernelGGL(category_counts_kernel, dim3(1), dim3(GROUP_MAX_CATEGORIES), 0, st, support, category_of_class, K, n_categories, cat_rows,
                        cat_bins);
-    M_LAUNCH_CHECK();
+    LAUNCH_CHECK();
     return 0;
 }
 

@@ -8,32 +8,12 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "api_internal.h"
 #include "kernels.h"
 #include "trainer_internal.h"
-
-// A device buffer that grows on demand and never shrinks.  Growing frees first -- hipFree blocks until whatever still reads the
-// old buffer has finished -- and allocates with 256 bytes of slack; after a failed allocation the buffer is empty.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    int64_t cap = 0;   // elements
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { hipFree(p); }
-    int reserve(int64_t count)
-    {
-        if (count <= cap) return 0;
-        hipFree(p);
-        p = nullptr; cap = 0;
-        HIP_TRY(hipMalloc((void**)&p, (size_t)count * sizeof(T) + 256));
-        cap = count;
-        return 0;
-    }
-};
 
 // what a cover call keeps between calls: the resident n x K probabilities, the stage's device state (tables, offsets, slab list,
 // priors, slab sums, top-k staging: cover_layout) and the host side of the slab list
@@ -48,8 +28,8 @@ struct CoverScratch {
 struct mmc_head {
     int device = 0, n_layers = 0, K = 0, input_dim = 0, in_pad = 0;
     std::vector<int> dims_pad;        // padded widths (multiples of 4), last = K (unpadded)
-    std::vector<float*> W, b;         // device
-    float *a = nullptr, *bc = nullptr;
+    std::vector<DevBuf<float>> W, b;  // device
+    DevBuf<float> a, bc;
     // one chunk's activations (ping-pong, as wide as the widest layer), padded input rows, probabilities and arg-max
     DevBuf<float> buf0, buf1, in_stage, proba_stage;
     DevBuf<int32_t> arg_stage;
@@ -74,10 +54,7 @@ extern "C" void mmc_head_destroy(mmc_head* h)
 {
     if (!h) return;
     hipSetDevice(h->device);
-    for (float* p : h->W) hipFree(p);
-    for (float* p : h->b) hipFree(p);
-    hipFree(h->a); hipFree(h->bc);
-    delete h;   // (the DevBuf members free themselves)
+    delete h;
 }
 
 extern "C" int mmc_head_create(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -91,10 +68,7 @@ extern "C" int mmc_head_create(const float* const* W, const float* const* b, con
     if (dims[n_layers] != K) return fail(MMC_ERR_ARG, "dims[n_layers]=%d != K=%d", dims[n_layers], K);
     for (int l = 0; l <= n_layers; ++l)
         if (dims[l] < 1) return fail(MMC_ERR_ARG, "dims[%d]=%d must be positive", l, dims[l]);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(MMC_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(MMC_ERR_ARG, "device %d out of range (%d visible)", device, ndev);
+    if (int r = check_device(device)) return r;
     HIP_TRY(hipSetDevice(device));
     mmc_head* h = new mmc_head();
     h->device = device; h->n_layers = n_layers; h->K = K; h->input_dim = dims[0];
@@ -108,16 +82,16 @@ extern "C" int mmc_head_create(const float* const* W, const float* const* b, con
             memcpy(&wp[(size_t)n * kp], W[l] + (size_t)n * kin, (size_t)kin * sizeof(float));
             bp[n] = b[l][n];
         }
-        float *dw = nullptr, *db = nullptr;
-        if (hipMalloc((void**)&dw, wp.size() * 4 + 256) != hipSuccess || hipMalloc((void**)&db, bp.size() * 4 + 256) != hipSuccess) {
+        DevBuf<float> dw, db;
+        if (!dw.alloc((int64_t)wp.size()) || !db.alloc((int64_t)bp.size())) {
             mmc_head_destroy(h);
             return fail(MMC_ERR_NOMEM, "hipMalloc failed for head layer %d", l);
         }
-        h->W.push_back(dw); h->b.push_back(db);
         hipMemcpy(dw, wp.data(), wp.size() * 4, hipMemcpyHostToDevice);
         hipMemcpy(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice);
+        h->W.push_back(std::move(dw)); h->b.push_back(std::move(db));
     }
-    if (hipMalloc((void**)&h->a, K * 4 + 256) != hipSuccess || hipMalloc((void**)&h->bc, K * 4 + 256) != hipSuccess) {
+    if (!h->a.alloc(K) || !h->bc.alloc(K)) {
         mmc_head_destroy(h);
         return fail(MMC_ERR_NOMEM, "hipMalloc failed for calibration parameters");
     }
@@ -1089,10 +1063,7 @@ extern "C" int mmc_cover_proba(const float* proba, int64_t n, int K, const int64
     if (r) return r;
     if (n == 0) return cover_empty(K, c);
     if (!proba) return fail(MMC_ERR_ARG, "proba is NULL");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(MMC_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(MMC_ERR_ARG, "device %d out of range (%d visible)", device, ndev);
+    if ((r = check_device(device))) return r;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     std::lock_guard<std::mutex> lock(g_cover_mutex);
     HIP_TRY(hipSetDevice(device));

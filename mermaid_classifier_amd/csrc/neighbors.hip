@@ -16,28 +16,10 @@
 #include "../../include/mmc.h"
 #include "trainer_internal.h"
 
-#define N_TRY(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return mmc_fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
-
-struct DevMem {   // a per-call device allocation, freed on every way out
-    char* p = nullptr;
-    ~DevMem() { if (p) hipFree(p); }
-    bool alloc(size_t bytes)
-    {
-        if (hipMalloc((void**)&p, bytes ? bytes : 1) == hipSuccess) return true;
-        (void)hipGetLastError();
-        p = nullptr;
-        return false;
-    }
-};
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -331,7 +313,7 @@ extern "C" int mmc_featureset_knn(mmc_featureset* query, int64_t q_first, int64_
     const bool in_host = flags & MMC_IN_HOST, out_host = flags & MMC_OUT_HOST, grouped = q_group != nullptr;
     const int dim = query->dim;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    N_TRY(hipSetDevice(query->device));
+    HIP_TRY(hipSetDevice(query->device));
 
     const int splits = nb ? knn_splits(nq, nb) : 0;
     const int base_tiles = (int)((nb + kT - 1) / kT);
@@ -343,14 +325,14 @@ extern "C" int mmc_featureset_knn(mmc_featureset* query, int64_t q_first, int64_
                  o_idx = o_partial + align256((size_t)splits * k * q_cap * 8), o_score = o_idx + align256(out_host ? (size_t)chunk * k * 4 : 0),
                  o_label = o_score + align256(out_host ? (size_t)chunk * k * 4 : 0),
                  total = o_label + align256(out_host && label ? (size_t)chunk * k * 4 : 0);
-    DevMem mem;
-    if (!mem.alloc(total)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes of nearest-neighbour scratch failed", total);
+    DevBuf<char> mem;   // a per-call device allocation, freed on every way out
+    if (!mem.alloc((int64_t)total)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc of %zu bytes of nearest-neighbour scratch failed", total);
     float *d_bs = (float*)(mem.p + o_bs), *d_br = (float*)(mem.p + o_br), *d_qs = (float*)(mem.p + o_qs), *d_qr = (float*)(mem.p + o_qr);
     const float* Bx = base->X + (size_t)b_first * dim;
     const int32_t* d_bg = b_group;
     if (nb) {
         if (grouped && in_host) {
-            N_TRY(hipMemcpyAsync(mem.p + o_bg, b_group, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(mem.p + o_bg, b_group, (size_t)nb * 4, hipMemcpyHostToDevice, st));
             d_bg = (const int32_t*)(mem.p + o_bg);
         }
         knn_norms_kernel<<<(unsigned)((nb + 255) / 256), 256, 0, st>>>(Bx, nb, dim, d_bs, d_br);
@@ -366,7 +348,7 @@ extern "C" int mmc_featureset_knn(mmc_featureset* query, int64_t q_first, int64_
         if (nb) {
             const int32_t* d_qg = grouped ? q_group + c0 : nullptr;
             if (grouped && in_host) {
-                N_TRY(hipMemcpyAsync(mem.p + o_qg, q_group + c0, (size_t)cn * 4, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(mem.p + o_qg, q_group + c0, (size_t)cn * 4, hipMemcpyHostToDevice, st));
                 d_qg = (const int32_t*)(mem.p + o_qg);
             }
             knn_norms_kernel<<<(unsigned)((cn + 255) / 256), 256, 0, st>>>(Qx, cn, dim, d_qs, d_qr);
@@ -396,13 +378,13 @@ extern "C" int mmc_featureset_knn(mmc_featureset* query, int64_t q_first, int64_
         }
         knn_merge_kernel<<<(unsigned)((cn + kT - 1) / kT), kT, 0, st>>>((const u64*)(mem.p + o_partial), splits, k, q_cap, (int)cn,
                                                                         base->y + b_first, d_index, d_score, d_label);
-        N_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (out_host) {
-            N_TRY(hipMemcpyAsync(index + (size_t)c0 * k, d_index, (size_t)cn * k * 4, hipMemcpyDeviceToHost, st));
-            N_TRY(hipMemcpyAsync(score + (size_t)c0 * k, d_score, (size_t)cn * k * 4, hipMemcpyDeviceToHost, st));
-            if (label) N_TRY(hipMemcpyAsync(label + (size_t)c0 * k, d_label, (size_t)cn * k * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(index + (size_t)c0 * k, d_index, (size_t)cn * k * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(score + (size_t)c0 * k, d_score, (size_t)cn * k * 4, hipMemcpyDeviceToHost, st));
+            if (label) HIP_TRY(hipMemcpyAsync(label + (size_t)c0 * k, d_label, (size_t)cn * k * 4, hipMemcpyDeviceToHost, st));
         }
     }
-    N_TRY(hipStreamSynchronize(st));   // the scratch is freed on return
+    HIP_TRY(hipStreamSynchronize(st));   // the scratch is freed on return
     return MMC_OK;
 }

@@ -739,81 +739,58 @@ __global__ __launch_bounds__(256) void gather_set_rows_mixed_kernel(const float*
 struct mmc_trainer {
     int device = 0, L = 0, K = 0;
     std::vector<int> dims;
-    std::vector<float*> W, b, gW, gb, mW, vW, mb, vb;   // device
-    std::vector<float*> H;                              // H[0] = mini-batch input, H[l+1] = layer l's output; size L+1
-    std::vector<float*> dZ;                             // dZ[l] = gradient w.r.t. layer l-1's pre-activation (size L+1, [0] unused)
-    float* cw = nullptr;                                // class weights or null
-    float *X = nullptr, *row_loss = nullptr, *partials = nullptr, *losses = nullptr;
-    int32_t* y = nullptr;
-    float* Xn = nullptr;            // natural-order staging of a pass (device-side shuffle)
-    int32_t* yn = nullptr;
-    int64_t* order = nullptr;
-    int64_t* visit = nullptr;       // visiting order of a pass over a resident feature set
-    int64_t cap_n = 0, cap_nn = 0, cap_visit = 0;
-    int cap_mb = 0, cap_steps = 0;
+    std::vector<DevBuf<float>> W, b, gW, gb, mW, vW, mb, vb;
+    std::vector<DevBuf<float>> Hbuf, dZbuf;             // the activations and their gradients of layers 1..L ([0] stays empty)
+    std::vector<float*> H;                              // views: H[0] = mini-batch input, H[l+1] = layer l's output; size L+1
+    std::vector<float*> dZ;                             // views: dZ[l] = gradient w.r.t. layer l-1's pre-activation (size L+1, [0] unused)
+    DevBuf<float> cw;                                   // class weights or empty
+    DevBuf<float> X, row_loss, partials, losses;
+    DevBuf<int32_t> y;
+    DevBuf<float> Xn;               // natural-order staging of a pass (device-side shuffle)
+    DevBuf<int32_t> yn;
+    DevBuf<int64_t> order;
+    DevBuf<int64_t> visit;          // visiting order of a pass over a resident feature set
     double lr = 1e-3, beta1 = 0.9, beta2 = 0.999, eps = 1e-8, alpha = 1e-4;   // kept in double: torch derives its fp32 scalars from python floats
     long long t = 0;                                    // Adam step count
     std::vector<float> cw_host;
     // loss formulation (mmc_trainer_set_loss); all defaults = the plain weighted cross-entropy and its instantiation of the kernel
     double label_smoothing = 0.0, focal_gamma = 0.0;
-    float* prior = nullptr;                             // logit prior [K] or null
+    DevBuf<float> prior;                                // logit prior [K] or empty
     bool general = false;
     float w_total = 0.f;                                // the float of the double sum of the class weights in class order; K without
-    void* scratch = nullptr;                           // trainer_scratch (calib.hip's evaluation buffers)
-    size_t scratch_bytes = 0;
+    DevBuf<char> scratch;                               // trainer_scratch (calib.hip's evaluation buffers)
     // regularisers (mmc_trainer_set_dropout; the plan of a mixed pass): all off = today's launches
     double p_input = 0.0, p_hidden = 0.0;
     uint64_t drop_seed = 0;
     uint32_t thresh_input = 0, thresh_hidden = 0;       // (uint32)floor(p 2^32); 0 = off
     float scale_input = 1.f, scale_hidden = 1.f;        // (float)(1.0 / (1.0 - p))
-    int32_t* y2 = nullptr;                              // the partner's label of every staged row of a mixed pass
-    int64_t* partner = nullptr;                         // device copy of a mixed pass's partner rows
-    float* lam = nullptr;                               // device copy of its per-mini-batch lam
-    int64_t cap_y2 = 0, cap_partner = 0;
-    int cap_lam = 0;
+    DevBuf<int32_t> y2;                                 // the partner's label of every staged row of a mixed pass
+    DevBuf<int64_t> partner;                            // device copy of a mixed pass's partner rows
+    DevBuf<float> lam;                                  // device copy of its per-mini-batch lam
     // optimiser options (mmc_trainer_set_lr_schedule / _set_grad_clip / _set_ema): all off = today's launches
     int lr_kind = MMC_LR_CONSTANT;
     long long warmup_steps = 0, total_steps = 0;
     double final_ratio = 0.0;
     double max_norm = 0.0;                              // 0 = no clipping
-    float* gpartials = nullptr;                         // [2 * 16][256] partial sums of squares of gW[l] (2l) and gb[l] (2l + 1)
-    float* coef = nullptr;                              // the step's clipping coefficient
-    float* gnorm = nullptr;                             // [cap_gnorm] pre-clip norm of every step of a pass, beside losses
-    int cap_gnorm = 0, gnorm_steps = 0;                 // gnorm_steps: steps of the last pass that wrote gnorm
+    DevBuf<float> gpartials;                            // [2 * 16][256] partial sums of squares of gW[l] (2l) and gb[l] (2l + 1)
+    DevBuf<float> coef;                                 // the step's clipping coefficient
+    DevBuf<float> gnorm;                                // pre-clip norm of every step of a pass, beside losses
+    int gnorm_steps = 0;                                // steps of the last pass that wrote gnorm
     double ema_decay = 0.0;                             // 0 = no averaged weights
-    std::vector<float*> sW, sb;                         // the shadow: averaged weights (empty without)
+    std::vector<DevBuf<float>> sW, sb;                  // the shadow: averaged weights (empty without)
     int eval_which = MMC_WEIGHTS_RAW;                   // what the eval-mode forward reads
 };
 
-#define T_TRY(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return mmc_fail(MMC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
 #define T_K(expr)                                                                   \
     do {                                                                            \
         int r_ = (expr);                                                            \
         if (r_ != 0) return mmc_fail(MMC_ERR_HIP, "%s failed (%d)", #expr, r_);     \
     } while (0)
 
-static void free_all(std::vector<float*>& v)
-{
-    for (float* p : v) hipFree(p);
-    v.clear();
-}
-
 extern "C" void mmc_trainer_destroy(mmc_trainer* t)
 {
     if (!t) return;
     hipSetDevice(t->device);
-    free_all(t->W); free_all(t->b); free_all(t->gW); free_all(t->gb); free_all(t->mW); free_all(t->vW); free_all(t->mb); free_all(t->vb);
-    for (size_t l = 1; l < t->H.size(); ++l) hipFree(t->H[l]);
-    for (size_t l = 1; l < t->dZ.size(); ++l) hipFree(t->dZ[l]);
-    hipFree(t->cw); hipFree(t->prior); hipFree(t->X); hipFree(t->row_loss); hipFree(t->partials); hipFree(t->losses); hipFree(t->y);
-    hipFree(t->Xn); hipFree(t->yn); hipFree(t->order); hipFree(t->visit); hipFree(t->scratch);
-    hipFree(t->y2); hipFree(t->partner); hipFree(t->lam);
-    hipFree(t->gpartials); hipFree(t->coef); hipFree(t->gnorm);
-    free_all(t->sW); free_all(t->sb);
     delete t;
 }
 
@@ -832,20 +809,18 @@ extern "C" int mmc_trainer_create(const float* const* W, const float* const* b, 
     if (class_weight)
         for (int c = 0; c < K; ++c)
             if (!(class_weight[c] >= 0.f)) return mmc_fail(MMC_ERR_ARG, "class_weight[%d] = %g is negative", c, class_weight[c]);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return mmc_fail(MMC_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return mmc_fail(MMC_ERR_ARG, "device %d out of range (%d visible)", device, ndev);
-    T_TRY(hipSetDevice(device));
+    if (int r = check_device(device)) return r;
+    HIP_TRY(hipSetDevice(device));
     mmc_trainer* t = new mmc_trainer();
     t->device = device; t->L = n_layers; t->K = K;
     t->dims.assign(dims, dims + n_layers + 1);
     t->lr = lr; t->beta1 = beta1; t->beta2 = beta2; t->eps = eps; t->alpha = alpha;
-    auto up = [&](std::vector<float*>& dst, const float* src, size_t n, bool zero) -> bool {
-        float* d = nullptr;
-        if (hipMalloc((void**)&d, n * 4 + 256) != hipSuccess) return false;
-        dst.push_back(d);
-        return (zero ? hipMemset(d, 0, n * 4) : hipMemcpy(d, src, n * 4, hipMemcpyHostToDevice)) == hipSuccess;
+    auto up = [&](std::vector<DevBuf<float>>& dst, const float* src, size_t n, bool zero) -> bool {
+        DevBuf<float> d;
+        if (!d.alloc((int64_t)n)) return false;
+        if ((zero ? hipMemset(d, 0, n * 4) : hipMemcpy(d, src, n * 4, hipMemcpyHostToDevice)) != hipSuccess) return false;
+        dst.push_back(std::move(d));
+        return true;
     };
     bool ok = true;
     for (int l = 0; l < n_layers && ok; ++l) {
@@ -854,8 +829,7 @@ extern "C" int mmc_trainer_create(const float* const* W, const float* const* b, 
              up(t->mW, nullptr, nw, true) && up(t->vW, nullptr, nw, true) && up(t->mb, nullptr, nb, true) && up(t->vb, nullptr, nb, true);
     }
     if (ok && class_weight) {
-        ok = hipMalloc((void**)&t->cw, (size_t)K * 4 + 256) == hipSuccess &&
-             hipMemcpy(t->cw, class_weight, (size_t)K * 4, hipMemcpyHostToDevice) == hipSuccess;
+        ok = t->cw.alloc(K) && hipMemcpy(t->cw, class_weight, (size_t)K * 4, hipMemcpyHostToDevice) == hipSuccess;
         t->cw_host.assign(class_weight, class_weight + K);
     }
     double wtot = (double)K;
@@ -864,11 +838,13 @@ extern "C" int mmc_trainer_create(const float* const* W, const float* const* b, 
         for (int c = 0; c < K; ++c) wtot += (double)class_weight[c];
     }
     t->w_total = (float)wtot;
-    if (ok) ok = hipMalloc((void**)&t->partials, 256 * 4 * 16 + 256) == hipSuccess;
+    if (ok) ok = t->partials.alloc(256 * 16);
     if (!ok) {
         mmc_trainer_destroy(t);
         return mmc_fail(MMC_ERR_NOMEM, "hipMalloc/hipMemcpy failed while creating the trainer");
     }
+    t->Hbuf.resize(n_layers + 1);
+    t->dZbuf.resize(n_layers + 1);
     t->H.assign(n_layers + 1, nullptr);
     t->dZ.assign(n_layers + 1, nullptr);
     *out = t;
@@ -891,25 +867,18 @@ extern "C" int mmc_trainer_set_loss(mmc_trainer* t, double label_smoothing, doub
     if (logit_prior)
         for (int c = 0; c < t->K; ++c)
             if (!std::isfinite(logit_prior[c])) return mmc_fail(MMC_ERR_ARG, "logit_prior[%d] = %g is not finite", c, logit_prior[c]);
-    T_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipSetDevice(t->device));
     // passes synchronise their stream before they return, so nothing in flight reads the prior that is replaced here
-    float* prior = nullptr;
+    DevBuf<float> prior;
     if (logit_prior) {
-        if (hipMalloc((void**)&prior, (size_t)t->K * 4 + 256) != hipSuccess) {
-            (void)hipGetLastError();
-            return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the logit prior (%d classes)", t->K);
-        }
+        if (!prior.alloc(t->K)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the logit prior (%d classes)", t->K);
         hipError_t e = hipMemcpy(prior, logit_prior, (size_t)t->K * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            hipFree(prior);
-            return mmc_fail(MMC_ERR_HIP, "uploading the logit prior: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "uploading the logit prior: %s", hipGetErrorString(e));
     }
-    hipFree(t->prior);
-    t->prior = prior;
+    t->prior = std::move(prior);
     t->label_smoothing = label_smoothing;
     t->focal_gamma = focal_gamma;
-    t->general = label_smoothing != 0.0 || focal_gamma != 0.0 || prior != nullptr;
+    t->general = label_smoothing != 0.0 || focal_gamma != 0.0 || t->prior.p != nullptr;
     return MMC_OK;
 }
 
@@ -983,15 +952,11 @@ extern "C" int mmc_trainer_set_grad_clip(mmc_trainer* t, double max_norm)
     if (!(max_norm == 0.0 || (max_norm > 0.0 && std::isfinite(max_norm) && std::isfinite((float)max_norm) && (float)max_norm > 0.f)))
         return mmc_fail(MMC_ERR_ARG, "max_norm = %g is neither 0 nor a positive finite fp32 value", max_norm);
     if (max_norm != 0.0 && !t->gpartials) {
-        T_TRY(hipSetDevice(t->device));
-        float *gp = nullptr, *cf = nullptr;
-        if (hipMalloc((void**)&gp, 2 * 16 * 256 * 4 + 256) != hipSuccess || hipMalloc((void**)&cf, 256) != hipSuccess) {
-            (void)hipGetLastError();
-            hipFree(gp);
-            return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the gradient-norm partials");
-        }
-        t->gpartials = gp;
-        t->coef = cf;
+        HIP_TRY(hipSetDevice(t->device));
+        DevBuf<float> gp, cf;
+        if (!gp.alloc(2 * 16 * 256) || !cf.alloc(1)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the gradient-norm partials");
+        t->gpartials = std::move(gp);
+        t->coef = std::move(cf);
     }
     t->max_norm = max_norm;
     t->gnorm_steps = 0;
@@ -1005,8 +970,8 @@ extern "C" int mmc_trainer_grad_norms(mmc_trainer* t, float* out, int capacity, 
     *steps = t->gnorm_steps;
     const int n = std::min(capacity, t->gnorm_steps);
     if (n > 0) {
-        T_TRY(hipSetDevice(t->device));
-        T_TRY(hipMemcpy(out, t->gnorm, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipSetDevice(t->device));
+        HIP_TRY(hipMemcpy(out, t->gnorm, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
     return MMC_OK;
 }
@@ -1015,30 +980,25 @@ extern "C" int mmc_trainer_set_ema(mmc_trainer* t, double decay)
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!(decay == 0.0 || (decay > 0.0 && decay < 1.0))) return mmc_fail(MMC_ERR_ARG, "decay = %g is neither 0 nor in (0, 1)", decay);
-    T_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipSetDevice(t->device));
     if (decay == 0.0) {
-        free_all(t->sW);
-        free_all(t->sb);
+        t->sW.clear();
+        t->sb.clear();
         t->eval_which = MMC_WEIGHTS_RAW;
     } else if (t->sW.empty()) {   // passes synchronise their stream before they return: the parameters copied here are settled
-        std::vector<float*> sW, sb;
+        std::vector<DevBuf<float>> sW(t->L), sb(t->L);
         bool ok = true;
-        auto dup = [&](std::vector<float*>& dst, const float* src, size_t n) -> bool {
-            float* d = nullptr;
-            if (hipMalloc((void**)&d, n * 4 + 256) != hipSuccess) return false;
-            dst.push_back(d);
-            return hipMemcpy(d, src, n * 4, hipMemcpyDeviceToDevice) == hipSuccess;
+        auto dup = [&](DevBuf<float>& dst, const float* src, size_t n) -> bool {
+            return dst.alloc((int64_t)n) && hipMemcpy(dst, src, n * 4, hipMemcpyDeviceToDevice) == hipSuccess;
         };
         for (int l = 0; l < t->L && ok; ++l)
-            ok = dup(sW, t->W[l], (size_t)t->dims[l + 1] * t->dims[l]) && dup(sb, t->b[l], (size_t)t->dims[l + 1]);
+            ok = dup(sW[l], t->W[l], (size_t)t->dims[l + 1] * t->dims[l]) && dup(sb[l], t->b[l], (size_t)t->dims[l + 1]);
         if (!ok) {
             (void)hipGetLastError();
-            free_all(sW);
-            free_all(sb);
             return mmc_fail(MMC_ERR_NOMEM, "hipMalloc/hipMemcpy failed for the averaged weights");
         }
-        t->sW = sW;
-        t->sb = sb;
+        t->sW = std::move(sW);
+        t->sb = std::move(sb);
     }
     t->ema_decay = decay;
     return MMC_OK;
@@ -1048,12 +1008,12 @@ extern "C" int mmc_trainer_ema_state(mmc_trainer* t, int set, float* const* W, f
 {
     if (!t || !W || !b) return mmc_fail(MMC_ERR_ARG, "NULL argument");
     if (t->sW.empty()) return mmc_fail(MMC_ERR_ARG, "the trainer keeps no averaged weights (mmc_trainer_set_ema)");
-    T_TRY(hipSetDevice(t->device));
-    T_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipDeviceSynchronize());
     for (int l = 0; l < t->L; ++l) {
         const size_t nw = (size_t)t->dims[l + 1] * t->dims[l] * 4, nb = (size_t)t->dims[l + 1] * 4;
-        if (set) { T_TRY(hipMemcpy(t->sW[l], W[l], nw, hipMemcpyHostToDevice)); T_TRY(hipMemcpy(t->sb[l], b[l], nb, hipMemcpyHostToDevice)); }
-        else { T_TRY(hipMemcpy(W[l], t->sW[l], nw, hipMemcpyDeviceToHost)); T_TRY(hipMemcpy(b[l], t->sb[l], nb, hipMemcpyDeviceToHost)); }
+        if (set) { HIP_TRY(hipMemcpy(t->sW[l], W[l], nw, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(t->sb[l], b[l], nb, hipMemcpyHostToDevice)); }
+        else { HIP_TRY(hipMemcpy(W[l], t->sW[l], nw, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(b[l], t->sb[l], nb, hipMemcpyDeviceToHost)); }
     }
     return MMC_OK;
 }
@@ -1085,33 +1045,18 @@ extern "C" int mmc_trainer_optimizer_options(mmc_trainer* t, int* lr_kind, long 
 
 static int trainer_reserve(mmc_trainer* t, int64_t n, int mb, int steps)
 {
-    if (t->max_norm > 0.0 && steps > t->cap_gnorm) {
-        hipFree(t->gnorm); t->gnorm = nullptr; t->cap_gnorm = 0; t->gnorm_steps = 0;
-        T_TRY(hipMalloc((void**)&t->gnorm, (size_t)steps * 4 + 256));
-        t->cap_gnorm = steps;
+    int r;
+    if (t->max_norm > 0.0) {
+        if (steps > t->gnorm.cap) t->gnorm_steps = 0;   // (the norms of the last pass go with the old block)
+        if ((r = t->gnorm.reserve(steps))) return r;
     }
-    if (n > t->cap_n) {
-        hipFree(t->X); hipFree(t->y);
-        t->X = nullptr; t->y = nullptr; t->cap_n = 0;
-        T_TRY(hipMalloc((void**)&t->X, (size_t)n * t->dims[0] * 4 + 256));
-        T_TRY(hipMalloc((void**)&t->y, (size_t)n * 4 + 256));
-        t->cap_n = n;
+    if ((r = t->X.reserve(n * t->dims[0])) || (r = t->y.reserve(n))) return r;
+    for (int l = 1; l <= t->L; ++l) {
+        if ((r = t->Hbuf[l].reserve((int64_t)mb * t->dims[l])) || (r = t->dZbuf[l].reserve((int64_t)mb * t->dims[l]))) return r;
+        t->H[l] = t->Hbuf[l];
+        t->dZ[l] = t->dZbuf[l];
     }
-    if (mb > t->cap_mb) {
-        for (int l = 1; l <= t->L; ++l) { hipFree(t->H[l]); hipFree(t->dZ[l]); t->H[l] = t->dZ[l] = nullptr; }
-        hipFree(t->row_loss); t->row_loss = nullptr; t->cap_mb = 0;
-        for (int l = 1; l <= t->L; ++l) {
-            T_TRY(hipMalloc((void**)&t->H[l], (size_t)mb * t->dims[l] * 4 + 256));
-            T_TRY(hipMalloc((void**)&t->dZ[l], (size_t)mb * t->dims[l] * 4 + 256));
-        }
-        T_TRY(hipMalloc((void**)&t->row_loss, (size_t)mb * 4 + 256));
-        t->cap_mb = mb;
-    }
-    if (steps > t->cap_steps) {
-        hipFree(t->losses); t->losses = nullptr; t->cap_steps = 0;
-        T_TRY(hipMalloc((void**)&t->losses, (size_t)steps * 4 + 256));
-        t->cap_steps = steps;
-    }
+    if ((r = t->row_loss.reserve(mb)) || (r = t->losses.reserve(steps))) return r;
     return 0;
 }
 
@@ -1432,7 +1377,7 @@ extern "C" int mmc_trainer_partial_fit_ordered(mmc_trainer* t, const float* X, c
         if (order && (order[i] < 0 || order[i] >= n)) return mmc_fail(MMC_ERR_ARG, "order[%lld] = %lld outside [0, %lld)", (long long)i, (long long)order[i], (long long)n);
     }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    T_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipSetDevice(t->device));
     const int mb = (int)(batch_size < n ? batch_size : n);
     std::vector<double> wsums;
     int r = minibatch_wsums("", t, y, order, n, mb, &wsums);
@@ -1440,21 +1385,14 @@ extern "C" int mmc_trainer_partial_fit_ordered(mmc_trainer* t, const float* X, c
     const int steps = (int)wsums.size();
     if ((r = trainer_reserve(t, n, mb, steps))) return r;
     if (order) {
-        if (n > t->cap_nn) {
-            hipFree(t->Xn); hipFree(t->yn); hipFree(t->order);
-            t->Xn = nullptr; t->yn = nullptr; t->order = nullptr; t->cap_nn = 0;
-            T_TRY(hipMalloc((void**)&t->Xn, (size_t)n * t->dims[0] * 4 + 256));
-            T_TRY(hipMalloc((void**)&t->yn, (size_t)n * 4 + 256));
-            T_TRY(hipMalloc((void**)&t->order, (size_t)n * 8 + 256));
-            t->cap_nn = n;
-        }
-        T_TRY(hipMemcpyAsync(t->Xn, X, (size_t)n * t->dims[0] * 4, hipMemcpyHostToDevice, st));
-        T_TRY(hipMemcpyAsync(t->yn, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        T_TRY(hipMemcpyAsync(t->order, order, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        if ((r = t->Xn.reserve(n * t->dims[0])) || (r = t->yn.reserve(n)) || (r = t->order.reserve(n))) return r;
+        HIP_TRY(hipMemcpyAsync(t->Xn, X, (size_t)n * t->dims[0] * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t->yn, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t->order, order, (size_t)n * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)n), dim3(256), 0, st, t->Xn, t->yn, t->order, n, t->dims[0] / 4, t->X, t->y);
     } else {
-        T_TRY(hipMemcpyAsync(t->X, X, (size_t)n * t->dims[0] * 4, hipMemcpyHostToDevice, st));
-        T_TRY(hipMemcpyAsync(t->y, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t->X, X, (size_t)n * t->dims[0] * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t->y, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
     }
     for (int s = 0; s < steps; ++s) {
         const int64_t start = (int64_t)s * mb;
@@ -1463,8 +1401,8 @@ extern "C" int mmc_trainer_partial_fit_ordered(mmc_trainer* t, const float* X, c
     }
     t->gnorm_steps = t->max_norm > 0.0 ? steps : 0;
     std::vector<float> h(steps);
-    T_TRY(hipMemcpyAsync(h.data(), t->losses, (size_t)steps * 4, hipMemcpyDeviceToHost, st));
-    T_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h.data(), t->losses, (size_t)steps * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (avg_loss) *avg_loss = pass_avg_loss(h, mb, n);
     return MMC_OK;
 }
@@ -1558,32 +1496,8 @@ int reserve_set_pass(const SetPass& p)
     mmc_trainer* t = p.t;
     int r = trainer_reserve(t, p.stage_rows, p.mb, p.steps);
     if (r) return r;
-    if (p.visit && p.n > t->cap_visit) {
-        hipFree(t->visit);
-        t->visit = nullptr; t->cap_visit = 0;
-        T_TRY(hipMalloc((void**)&t->visit, (size_t)p.n * 8 + 256));
-        t->cap_visit = p.n;
-    }
-    if (p.partner) {
-        if (p.stage_rows > t->cap_y2) {
-            hipFree(t->y2);
-            t->y2 = nullptr; t->cap_y2 = 0;
-            T_TRY(hipMalloc((void**)&t->y2, (size_t)p.stage_rows * 4 + 256));
-            t->cap_y2 = p.stage_rows;
-        }
-        if (p.n > t->cap_partner) {
-            hipFree(t->partner);
-            t->partner = nullptr; t->cap_partner = 0;
-            T_TRY(hipMalloc((void**)&t->partner, (size_t)p.n * 8 + 256));
-            t->cap_partner = p.n;
-        }
-        if (p.steps > t->cap_lam) {
-            hipFree(t->lam);
-            t->lam = nullptr; t->cap_lam = 0;
-            T_TRY(hipMalloc((void**)&t->lam, (size_t)p.steps * 4 + 256));
-            t->cap_lam = p.steps;
-        }
-    }
+    if (p.visit && (r = t->visit.reserve(p.n))) return r;
+    if (p.partner && ((r = t->y2.reserve(p.stage_rows)) || (r = t->partner.reserve(p.n)) || (r = t->lam.reserve(p.steps)))) return r;
     return 0;
 }
 
@@ -1600,14 +1514,14 @@ int gather_chunk(mmc_trainer* t, const mmc_featureset* fs, bool visited, bool mi
         else
             hipLaunchKernelGGL(gather_set_rows_mixed_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, par, lam, mb,
                                rows, fs->dim, t->X, t->y, t->y2);
-        T_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         return 0;
     }
     if (fs->dim & 3)
         hipLaunchKernelGGL(gather_set_rows_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, rows, fs->dim, t->X, t->y);
     else
         hipLaunchKernelGGL(gather_set_rows_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, fs->X, fs->y, vis, c0, rows, fs->dim, t->X, t->y);
-    T_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -1637,7 +1551,7 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
             return r;
         max_steps = std::max(max_steps, mem[m].steps);
     }
-    T_TRY(hipSetDevice(fs->device));
+    HIP_TRY(hipSetDevice(fs->device));
     // every member's buffers before the first launch: a pass that cannot be staged changes no member
     for (int m = 0; m < count; ++m)
         if ((r = reserve_set_pass(mem[m]))) {
@@ -1647,11 +1561,11 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
                             (long long)mem[m].stage_rows, mem[m].mb);
         }
     for (int m = 0; m < count; ++m)
-        if (mem[m].visit) T_TRY(hipMemcpyAsync(mem[m].t->visit, mem[m].visit, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
+        if (mem[m].visit) HIP_TRY(hipMemcpyAsync(mem[m].t->visit, mem[m].visit, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
     for (int m = 0; m < count; ++m)
         if (mem[m].partner) {
-            T_TRY(hipMemcpyAsync(mem[m].t->partner, mem[m].partner, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
-            T_TRY(hipMemcpyAsync(mem[m].t->lam, mem[m].lam, (size_t)mem[m].steps * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(mem[m].t->partner, mem[m].partner, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(mem[m].t->lam, mem[m].lam, (size_t)mem[m].steps * 4, hipMemcpyHostToDevice, st));
         }
     StepMember act[MMC_TRAINER_GROUP_MAX];
     for (int s = 0; s < max_steps; ++s) {
@@ -1673,9 +1587,9 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
     std::vector<std::vector<float>> h(count);
     for (int m = 0; m < count; ++m) {
         h[m].resize(mem[m].steps);
-        T_TRY(hipMemcpyAsync(h[m].data(), mem[m].t->losses, (size_t)mem[m].steps * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h[m].data(), mem[m].t->losses, (size_t)mem[m].steps * 4, hipMemcpyDeviceToHost, st));
     }
-    T_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (avg_loss)
         for (int m = 0; m < count; ++m) avg_loss[m] = pass_avg_loss(h[m], mem[m].mb, mem[m].n);
     return MMC_OK;
@@ -1731,11 +1645,11 @@ extern "C" int mmc_trainer_group_partial_fit_set_mixed(mmc_trainer* const* train
 extern "C" int mmc_trainer_get_params(mmc_trainer* t, float* const* W, float* const* b)
 {
     if (!t || !W || !b) return mmc_fail(MMC_ERR_ARG, "NULL argument");
-    T_TRY(hipSetDevice(t->device));
-    T_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipDeviceSynchronize());
     for (int l = 0; l < t->L; ++l) {
-        T_TRY(hipMemcpy(W[l], t->W[l], (size_t)t->dims[l + 1] * t->dims[l] * 4, hipMemcpyDeviceToHost));
-        T_TRY(hipMemcpy(b[l], t->b[l], (size_t)t->dims[l + 1] * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(W[l], t->W[l], (size_t)t->dims[l + 1] * t->dims[l] * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(b[l], t->b[l], (size_t)t->dims[l + 1] * 4, hipMemcpyDeviceToHost));
     }
     return MMC_OK;
 }
@@ -1746,14 +1660,14 @@ extern "C" int mmc_trainer_adam_state(mmc_trainer* t, int which, int set, float*
 {
     if (!t || !W || !b || !step) return mmc_fail(MMC_ERR_ARG, "NULL argument");
     if (which != 0 && which != 1) return mmc_fail(MMC_ERR_ARG, "which must be 0 (exp_avg) or 1 (exp_avg_sq)");
-    T_TRY(hipSetDevice(t->device));
-    T_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipDeviceSynchronize());
     for (int l = 0; l < t->L; ++l) {
         float* dw = which == 0 ? t->mW[l] : t->vW[l];
         float* db = which == 0 ? t->mb[l] : t->vb[l];
         const size_t nw = (size_t)t->dims[l + 1] * t->dims[l] * 4, nb = (size_t)t->dims[l + 1] * 4;
-        if (set) { T_TRY(hipMemcpy(dw, W[l], nw, hipMemcpyHostToDevice)); T_TRY(hipMemcpy(db, b[l], nb, hipMemcpyHostToDevice)); }
-        else { T_TRY(hipMemcpy(W[l], dw, nw, hipMemcpyDeviceToHost)); T_TRY(hipMemcpy(b[l], db, nb, hipMemcpyDeviceToHost)); }
+        if (set) { HIP_TRY(hipMemcpy(dw, W[l], nw, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(db, b[l], nb, hipMemcpyHostToDevice)); }
+        else { HIP_TRY(hipMemcpy(W[l], dw, nw, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(b[l], db, nb, hipMemcpyDeviceToHost)); }
     }
     if (set) t->t = *step; else *step = t->t;
     return MMC_OK;
@@ -1764,17 +1678,17 @@ extern "C" int mmc_trainer_adam_state(mmc_trainer* t, int which, int set, float*
 int trainer_forward(mmc_trainer* t, const float* X, int n, hipStream_t st, const float** logits)
 {
     if (n < 1 || n > kTrainerForwardRows) return mmc_fail(MMC_ERR_ARG, "trainer_forward: n = %d outside [1, %d]", n, kTrainerForwardRows);
-    T_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipSetDevice(t->device));
     int r = trainer_reserve(t, n, n, 1);
     if (r) return r;
-    T_TRY(hipMemcpyAsync(t->X, X, (size_t)n * t->dims[0] * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t->X, X, (size_t)n * t->dims[0] * 4, hipMemcpyHostToDevice, st));
     return trainer_forward_device(t, t->X, n, st, logits);
 }
 
 int trainer_forward_device(mmc_trainer* t, const float* X_dev, int n, hipStream_t st, const float** logits)
 {
     if (n < 1 || n > kTrainerForwardRows) return mmc_fail(MMC_ERR_ARG, "trainer_forward: n = %d outside [1, %d]", n, kTrainerForwardRows);
-    T_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipSetDevice(t->device));
     int r = trainer_reserve(t, 0, n, 1);   // activations only: the input is read where it lies
     if (r) return r;
     t->H[0] = const_cast<float*>(X_dev);
@@ -1793,15 +1707,11 @@ int trainer_forward_device(mmc_trainer* t, const float* X_dev, int n, hipStream_
 
 int trainer_scratch(mmc_trainer* t, size_t bytes, void** out)
 {
-    if (bytes > t->scratch_bytes) {
-        T_TRY(hipSetDevice(t->device));
-        hipFree(t->scratch);   // only on growth: the buffer is kept for the trainer's lifetime
-        t->scratch = nullptr;
-        t->scratch_bytes = 0;
-        T_TRY(hipMalloc(&t->scratch, bytes));
-        t->scratch_bytes = bytes;
+    if ((int64_t)bytes > t->scratch.cap) {   // only on growth: the buffer is kept for the trainer's lifetime
+        HIP_TRY(hipSetDevice(t->device));
+        if (int r = t->scratch.reserve((int64_t)bytes)) return r;
     }
-    *out = t->scratch;
+    *out = t->scratch.p;
     return MMC_OK;
 }
 
@@ -1822,8 +1732,8 @@ extern "C" int mmc_trainer_logits(mmc_trainer* t, const float* X, int64_t n, flo
         const float* z = nullptr;
         int r = trainer_forward(t, X + (size_t)off * t->dims[0], cur, st, &z);
         if (r) return r;
-        T_TRY(hipMemcpyAsync(logits + (size_t)off * t->K, z, (size_t)cur * t->K * 4, hipMemcpyDeviceToHost, st));
-        T_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(logits + (size_t)off * t->K, z, (size_t)cur * t->K * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     return MMC_OK;
 }
@@ -1842,22 +1752,22 @@ extern "C" int mmc_trainer_loss_gradient(mmc_trainer* t, const float* logits, co
     }
     if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "the rows have zero total class weight");
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    T_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipSetDevice(t->device));
     const int mb = (int)n, L = t->L;
     int r = trainer_reserve(t, 0, mb, 1);   // the step's own logits / gradient / row-loss buffers
     if (r) return r;
     void* yd = nullptr;
     if ((r = trainer_scratch(t, (size_t)mb * 4, &yd))) return r;
     const size_t cells = (size_t)mb * t->K;
-    T_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
-    T_TRY(hipMemcpyAsync(yd, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(yd, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
     CeGroup g;
     g.d[0] = ce_desc(t, t->H[L], static_cast<const int32_t*>(yd), mb, (float)(1.0 / wsum));
     hipLaunchKernelGGL(ce_grad_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
-    T_TRY(hipGetLastError());
-    T_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
-    T_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
-    T_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return MMC_OK;
 }
 
@@ -1878,7 +1788,7 @@ extern "C" int mmc_trainer_loss_gradient_mixed(mmc_trainer* t, const float* logi
     }
     if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "the rows have zero total mixed class weight");
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    T_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipSetDevice(t->device));
     const int mb = (int)n, L = t->L;
     int r = trainer_reserve(t, 0, mb, 1);
     if (r) return r;
@@ -1887,15 +1797,15 @@ extern "C" int mmc_trainer_loss_gradient_mixed(mmc_trainer* t, const float* logi
     int32_t* y1d = static_cast<int32_t*>(yd);
     int32_t* y2d = y1d + mb;
     const size_t cells = (size_t)mb * t->K;
-    T_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
-    T_TRY(hipMemcpyAsync(y1d, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
-    T_TRY(hipMemcpyAsync(y2d, y2, (size_t)mb * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(y1d, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(y2d, y2, (size_t)mb * 4, hipMemcpyHostToDevice, st));
     CeMixGroup g;
     g.d[0] = CeMixDesc{t->H[L], y1d, y2d, t->cw, t->dZ[L], t->row_loss, mb, t->K, (float)(1.0 / wsum), lam, oml, trainer_ce_loss(t)};
     hipLaunchKernelGGL(ce_grad_mixed_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
-    T_TRY(hipGetLastError());
-    T_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
-    T_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
-    T_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return MMC_OK;
 }

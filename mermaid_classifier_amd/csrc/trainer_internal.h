@@ -7,22 +7,21 @@
 
 #include <vector>
 
+#include "device_mem.h"
+
 struct mmc_trainer;
 
 // mmc_featureset_*: n labelled rows resident on one device.  X / y hold `cap` rows; growth is geometric (featureset.hip).
 struct mmc_featureset {
     int dim = 0, K = 0, device = 0;
     int64_t n = 0, cap = 0;
-    float* X = nullptr;               // [cap][dim] fp32, row-major
-    int32_t* y = nullptr;             // [cap] class indices
+    DevBuf<float> X;                  // [cap][dim] fp32, row-major
+    DevBuf<int32_t> y;                // [cap] class indices
     std::vector<int32_t> y_host;      // host mirror of y[0..n): argument checks and per-mini-batch class-weight sums
 };
 
 // room for `need` rows in all (featureset.hip): both new buffers are allocated before anything is touched, the stored rows move on `st`
 int featureset_reserve(mmc_featureset* fs, int64_t need, hipStream_t st);
-
-// sets the thread-local message mmc_last_error() returns and hands back `code` (defined in mmc_api.cpp)
-int mmc_fail(int code, const char* fmt, ...);
 
 // rows per trainer_forward call (the trainer's activation buffers are sized for at most this many)
 constexpr int kTrainerForwardRows = 16384;

@@ -208,6 +208,19 @@ def test_device_fit_from_scores(fx, name):
 
 
 @pytest.mark.gpu
+def test_growth_with_rows_stored_gives_the_bits_of_one_call():
+    """600 rows of K = 3 scores, then 600 more: the second add crosses the 1024-row capacity, so the class-major store is
+    reallocated and its columns move.  The fit comes out bit for bit as from a calibrator that took the 1200 rows in one call."""
+    rng = np.random.default_rng(1200)
+    y = rng.integers(0, 3, 1200)
+    S = rng.dirichlet(np.ones(3), 1200) * 0.6 + 0.4 * np.eye(3)[y] * rng.uniform(0.0, 1.0, (1200, 1))
+    a1, b1, it1 = _fit_scores(S, y, splits=[600])
+    a2, b2, it2 = _fit_scores(S, y)
+    assert np.isfinite(a1).all() and np.isfinite(b1).all() and it1.max() <= 50
+    assert a1.tobytes() == a2.tobytes() and b1.tobytes() == b2.tobytes() and np.array_equal(it1, it2)
+
+
+@pytest.mark.gpu
 def test_device_argument_errors():
     from mermaid_classifier_amd.calibration import _Calibrator
     from mermaid_classifier_amd.torch_classifier import TorchMLPClassifier

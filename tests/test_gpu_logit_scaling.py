@@ -147,6 +147,24 @@ def test_bits_do_not_depend_on_the_split_the_repeat_or_the_hessian():
     assert np.array_equal(H, H.T) and np.abs(H).max() > 0
 
 
+def test_growth_with_rows_stored_gives_the_bits_of_one_call():
+    """600 rows, then 600 more: the second add crosses the 1024-row capacity, so the store is reallocated and the stored rows
+    move.  The statistics and every fit come out bit for bit as from a store that took the 1200 rows in one call."""
+    z, y = ck.fixture(1200, 3)
+    grown, whole = _store(z, y, cuts=(600,)), _store(z, y)
+    try:
+        a, c = np.array([1.5, 0.7, 1.1]), np.array([0.2, -0.1, -0.1])
+        got, want = grown.stats(a, c), whole.stats(a, c)
+        assert _bits(*got[:3]) == _bits(*want[:3]) and np.array_equal(got[3], want[3])
+        for kind in ck.KINDS:
+            r_g, r_w = grown.fit(kind, tol=1e-9, max_trials=100), whole.fit(kind, tol=1e-9, max_trials=100)
+            assert r_g.converged and r_g.n_rows == 1200 and r_g.trials == r_w.trials
+            assert _bits(r_g.a, r_g.c, r_g.nll_before, r_g.nll_after) == _bits(r_w.a, r_w.c, r_w.nll_before, r_w.nll_after), kind
+    finally:
+        grown.close()
+        whole.close()
+
+
 @pytest.fixture(scope="module")
 def tiny():
     """dim 16 -> (8,) -> K = 5, trained for a few passes on about 600 rows per split."""

@@ -11,7 +11,8 @@ a. gradients, logits and loss at the tile / step / block edges (``mlp_step_ref.C
 b. the ragged last mini-batch of a two-step pass (lr = 1e-30: the first step leaves the parameters in place), host-fed, through
    the device gather of ``mmc_trainer_partial_fit_ordered`` and over a resident ``FeatureSet`` with a visiting order;
 c. the Adam update: moments bit-equal to ``adam_f32``, step count, parameters within ``adam_param_ref``'s bound;
-d. a heterogeneous group in one ``mmc_trainer_group_partial_fit_set`` call, each member against its own float64 reference.
+d. a heterogeneous group in one ``mmc_trainer_group_partial_fit_set`` call, each member against its own float64 reference;
+e. one trainer through passes that grow, reuse and add to its device buffers, bit for bit against a fresh trainer per pass.
 
 Measured max |got - ref| / bound per case and tensor: ``profiles/trainer_step_parity.txt`` (written per test into the directory
 ``MMC_TRAINER_STEP_PARITY_OUT`` names)."""
@@ -90,6 +91,36 @@ class _Trainer:
     def set_moments(self, which, ws, bs, step):
         ws, bs = [np.ascontiguousarray(w, np.float32) for w in ws], [np.ascontiguousarray(b, np.float32) for b in bs]
         self._lib.check(self.lib.mmc_trainer_adam_state(self.h, which, 1, self._pa(ws), self._pa(bs), C.byref(C.c_longlong(step))))
+
+    def fit_set_mixed(self, fs, visit, partner, lam, batch_size):
+        from mermaid_classifier_amd.backbone import _current_stream_ptr
+        visit, partner = np.ascontiguousarray(visit, np.int64), np.ascontiguousarray(partner, np.int64)
+        lam = np.ascontiguousarray(lam, np.float32)
+        avg = C.c_double(np.nan)
+        self._lib.check(self.lib.mmc_trainer_partial_fit_set_mixed(self.h, fs._handle(), visit.ctypes.data, partner.ctypes.data,
+                                                                   lam.ctypes.data, len(visit), batch_size, C.byref(avg),
+                                                                   _current_stream_ptr(0)))
+        return avg.value
+
+    def set_options(self, max_norm, ema_decay, p_hidden, seed):
+        self._lib.check(self.lib.mmc_trainer_set_grad_clip(self.h, max_norm))
+        self._lib.check(self.lib.mmc_trainer_set_ema(self.h, ema_decay))
+        self._lib.check(self.lib.mmc_trainer_set_dropout(self.h, 0.0, p_hidden, seed))
+
+    def grad_norms(self):
+        """The pre-clip norms of the last pass's steps (empty when it did not clip)."""
+        out, steps = np.full(64, np.nan, np.float32), C.c_int(-1)
+        self._lib.check(self.lib.mmc_trainer_grad_norms(self.h, out.ctypes.data, len(out), C.byref(steps)))
+        assert 0 <= steps.value <= len(out)
+        return out[:steps.value]
+
+    def shadow(self):
+        ws, bs = self._empty()
+        self._lib.check(self.lib.mmc_trainer_ema_state(self.h, 0, self._pa(ws), self._pa(bs)))
+        return ws, bs
+
+    def set_shadow(self, ws, bs):
+        self._lib.check(self.lib.mmc_trainer_ema_state(self.h, 1, self._pa(ws), self._pa(bs)))
 
     def close(self):
         self.lib.mmc_trainer_destroy(self.h)
@@ -297,3 +328,89 @@ def test_heterogeneous_group_each_member_against_fp64():
         assert set(got[i]) == set(ref)
         _hold(f"group-member{i}", len(members[i][0]), got[i], ref, bound, lines, failures)
     _finish("d_group", lines, failures)
+
+
+# ---- e. one trainer whose buffers grow, stay and gain the optional ones, against fresh trainers -------------------------------------
+
+def test_one_trainer_through_growing_passes_matches_fresh_trainers(monkeypatch):
+    """Handle A (8 -> 12 -> 5, class weights) takes five passes that grow its staging, activation and loss buffers, reuse them at a
+    smaller size, and allocate the ordered pass's, the visiting order's, the mixing plan's, the clipping and the shadow buffers.
+    Before each pass a fresh trainer B is made from A's parameters, moments, step count, options and shadow, and takes that pass
+    alone: afterwards A and B agree bit for bit in parameters, both moments, step count, avg_loss, the gradient norms and the
+    shadow -- what a buffer held before, or how large it once was, changes nothing."""
+    from mermaid_classifier_amd import FeatureSet
+    rng = np.random.default_rng(20261)
+    dims = [8, 12, 5]
+    ws = [(rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l])).astype(np.float32) for l in range(2)]
+    bs = [(0.1 * rng.standard_normal(dims[l + 1])).astype(np.float32) for l in range(2)]
+    cw = np.array([1.0, 0.5, 2.0, 1.5, 0.75], np.float32)
+    X = rng.standard_normal((70, 8)).astype(np.float32)
+    y = (np.arange(70) % 5).astype(np.int32)
+    order = rng.permutation(70)
+    visit9 = rng.permutation(40)[:9]
+    visit40, partner40 = rng.permutation(40), rng.integers(0, 40, 40)
+    lam = rng.uniform(0.2, 0.8, 3).astype(np.float32)                    # ceil(40 / 16) mini-batches
+    opts = dict(max_norm=0.5, ema_decay=0.9, p_hidden=0.25, seed=77)
+    fs = FeatureSet(8, np.arange(5)).append(X[:40], y[:40])
+
+    def host6(t):
+        status, avg = t.fit(X[:6], y[:6], 4)                            # 4 + 2 rows: a ragged last step
+        assert status == 0, t.lib.mmc_last_error()
+        return avg
+
+    def ordered70(t):
+        status, avg = t.fit(X, y, 32, order)
+        assert status == 0, t.lib.mmc_last_error()
+        return avg
+
+    def set9(t):                                                        # chunks of 8 and 1 rows
+        monkeypatch.setenv("MMC_TRAIN_CHUNK_ROWS", "8")
+        try:
+            return t.fit_set(fs, visit9, 4)
+        finally:
+            monkeypatch.delenv("MMC_TRAIN_CHUNK_ROWS")
+
+    def mixed40(t):
+        return t.fit_set_mixed(fs, visit40, partner40, lam, 16)
+
+    def observe(t, with_options):
+        mw, mb, step = t.moments(0)
+        vw, vb, step2 = t.moments(1)
+        assert step == step2
+        state = {"params": t.params(), "m": (mw, mb), "v": (vw, vb), "step": step, "gnorm": t.grad_norms()}
+        if with_options:
+            state["shadow"] = t.shadow()
+        return state
+
+    def flat(v):
+        return np.concatenate([np.ravel(a) for a in v[0] + v[1]]) if isinstance(v, tuple) else np.atleast_1d(np.asarray(v))
+
+    a = _Trainer(ws, bs, cw)
+    try:
+        with_options = False
+        for name, run, steps, turn_on in [("host-6", host6, 2, False), ("ordered-70", ordered70, 3, False), ("set-visit-9", set9, 3, False),
+                                          ("mixed-40", mixed40, 3, True), ("host-6-again", host6, 2, False)]:
+            if turn_on:
+                a.set_options(**opts)
+                with_options = True
+            before = observe(a, with_options)
+            b = _Trainer(*before["params"], cw)
+            try:
+                b.set_moments(0, *before["m"], before["step"])
+                b.set_moments(1, *before["v"], before["step"])
+                if with_options:
+                    b.set_options(**opts)
+                    b.set_shadow(*before["shadow"])
+                got_b = {"avg_loss": run(b), **observe(b, with_options)}
+            finally:
+                b.close()
+            got_a = {"avg_loss": run(a), **observe(a, with_options)}
+            assert got_a["step"] == before["step"] + steps and np.isfinite(got_a["avg_loss"]), name
+            assert len(got_a["gnorm"]) == (steps if with_options else 0), name
+            assert not np.array_equal(flat(got_a["params"]), flat(before["params"])), name      # the pass did train
+            for k in got_a:
+                fa, fb = flat(got_a[k]), flat(got_b[k])
+                assert fa.shape == fb.shape and fa.tobytes() == fb.tobytes(), (name, k, float(np.abs(fa - fb).max()))
+    finally:
+        a.close()
+        fs.close()
