@@ -502,6 +502,67 @@ int mmc_trainer_eval_weights(mmc_trainer* t, int which);
 int mmc_trainer_optimizer_options(mmc_trainer* t, int* lr_kind, long long* warmup_steps, long long* total_steps, double* final_ratio,
                                   double* max_norm, double* ema_decay, int* eval_which);
 
+/* ---- group-robust training: per-row weights and group DRO in the loss stage of resident passes, per trainer -----------------------
+ * Extends: the loss of TorchMLPClassifier.partial_fit (torch_classifier.py:226-303), whose only weighting is one weight per class, by
+ *   what docs/research/balancing-experiments.md:141 leaves open: per-source accuracy from 0.434 to 0.940 and "per-source rebalancing"
+ *   as the next lever.  No counterpart in the reference and no measured gain.  Group DRO is Algorithm 1 of Sagawa et al. 2020
+ *   ("Distributionally robust neural networks for group shifts").  Both sit in the loss stage alone: the forward, the backward GEMMs,
+ *   L2, clipping, EMA, the schedule, dropout and mmc_trainer_set_loss's formulations are untouched and compose with them; evaluation,
+ *   calibration and export never see them.  With nothing set a pass launches the kernels, and gives the bits, of a trainer none of
+ *   this was ever called on; in a group the members without weights or groups keep their kernels.
+ * Notation.  A mini-batch has positions i = 0..M-1; w are the class weights (ones without); l_i and dl_i/dz are the trainer's own row
+ *   term and its logit gradient before normalisation (the plain weighted CE or mmc_trainer_set_loss's form); r_i >= 0 is the row's
+ *   fp32 weight (1 without row weights); the row mass is v_i = (double)r_i (double)w[y_i].
+ * Row weights only.  g = (float)(1 / sum_i v_i), summed in double on the host in position order.  The row's normaliser is
+ *   s_i = r_i g, one rounded fp32 product, and takes the place of 1 / sum_i w[y_i] in the row's formulas: dlogits_i = s_i dl_i,
+ *   row_loss_i = s_i l_i, the operations in the unweighted kernel's order.  A pass whose weights are all 1.0f has the bits of
+ *   mmc_trainer_partial_fit_set.
+ * Group DRO.  mmc_trainer_set_group_dro(t, G, eta): G = n_groups in [1, MMC_DRO_MAX_GROUPS], eta in [0, 10]; n_groups = 0 turns it
+ *   off; any call resets q to uniform.  The trainer holds logq[G] in double on the device, sum_a exp(logq_a) = 1, across steps and
+ *   passes.  Position i carries a group a_i in [0, G).  Per step, nothing waiting on the host:
+ *     1. the loss stage runs with normaliser r_i (g = 1): R_i = r_i l_i, D_i = r_i dl_i, fp32
+ *     2. V_a = sum_{i in a} v_i in double on the host in position order, uploaded with the pass for every step and group
+ *     3. S_a = sum_{i in a} R_i in double on the device, in an order that is a function of M and G alone: the rows go in tiles of
+ *        2048; with NS = 16 / ceil(G / 64), slice s of a tile is its rows [s per, (s + 1) per), per = ceil(tile rows / NS); a slice
+ *        adds its rows in position order, tile after tile, and the slices' sums are added in slice order.  No atomics.
+ *     4. L_a = S_a / V_a for the groups with V_a > 0; the others (absent, or present without mass) have no loss this step
+ *     5. logq_a = logq_a + eta L_a for those (two roundings); then logq_a -= mx + log(sum_b exp(logq_b - mx)), mx the maximum, the sum
+ *        over all G in index order
+ *     6. c_i = (float)(exp(logq_{a_i}) / V_{a_i}), or 0 where V = 0
+ *     7. dlogits_i = c_i D_i, row_loss_i = c_i R_i: one fp32 multiply per element
+ *     8. the step's loss is the unchanged sum of the row losses plus the L2 term: sum_a q_a L_a with the updated q, as in the paper
+ *   eta = 0 never moves q: each present group counts 1 / G, a static group-balanced loss.
+ * mmc_trainer_group_dro_state reads logq (set = 0) or writes it (set = 1) for a resume: a state that is normalised already
+ *   (|log sum_a exp(logq_a)| <= 2^-40, what a read returns) is taken as it is, so the resumed trainer continues on the same bits;
+ *   anything else is renormalised as in 5.  MMC_ERR_ARG without group DRO, or for an entry that is not finite.
+ * The _weighted passes.  row_weight (n fp32) and row_group (n int32) are indexed by position of the pass, like partner; either may be
+ *   NULL, both NULL is the unweighted call, bit for bit.  In the group form each is an array of `count` pointers, or NULL; a member
+ *   whose two entries are NULL takes the plain kernels.  row_group needs mmc_trainer_set_group_dro(n_groups > 0) on that trainer;
+ *   the plain and mixed entry points on such a trainer run as ever and leave q alone, and so does a pass with row weights only.
+ *   There is no entry point for mixup with weights.  The results do not depend on MMC_TRAIN_CHUNK_ROWS, and a member of a group
+ *   matches its solo pass bit for bit, logq included.
+ * Checked before the first launch and before any member changes, on top of the unweighted call's checks: a weight that is negative
+ *   or not finite, a group outside [0, n_groups), row_group on a trainer without group DRO, a mini-batch whose total mass is zero
+ *   (no groups) or in which no group has mass (groups), eta or n_groups out of range -> MMC_ERR_ARG; parameters, moments, step
+ *   count and logq stay as they were.
+ * mmc_trainer_loss_gradient_weighted runs the stage's own kernels on caller logits, n in [1, 16384] rows taken as one mini-batch.
+ *   With row_group it takes log q explicitly (log_q_in, used as given), returns the updated one in log_q_out and, when group_loss
+ *   is not NULL, L_a (NaN for a group without loss); without row_group eta, n_groups and the three arrays are not read.  It does
+ *   not touch the trainer's own distribution.  Same checks. */
+#define MMC_DRO_MAX_GROUPS 1024
+int mmc_trainer_set_group_dro(mmc_trainer* t, int n_groups, double eta);
+int mmc_trainer_group_dro_state(mmc_trainer* t, int set, double* log_q /* n_groups */);
+int mmc_trainer_partial_fit_set_weighted(mmc_trainer* t, mmc_featureset* fs, const int64_t* visit, const float* row_weight /* n or NULL */,
+                                         const int32_t* row_group /* n or NULL */, int64_t n, int batch_size, double* avg_loss,
+                                         void* hip_stream);
+int mmc_trainer_group_partial_fit_set_weighted(mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit,
+                                               const float* const* row_weight, const int32_t* const* row_group, const int64_t* n,
+                                               const int* batch_size, double* avg_loss, void* hip_stream);
+int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* logits, const int32_t* y, const float* row_weight,
+                                       const int32_t* row_group, const double* log_q_in, double eta, int n_groups, int64_t n,
+                                       float* dlogits, float* row_loss, double* log_q_out, double* group_loss /* n_groups, NaN where none */,
+                                       void* hip_stream);
+
 /* ---- validation of a calibrated head --------------------------------------------------------------------------------
  * Replaces: what MermaidTrainer.__call__ computes after the calibration (mermaid_classifier/pyspacer/trainer.py:267-293:
  *   evaluate_classifier on val, ValResults, acc, the previous models' accuracies) and the per-row reductions the metrics make of the

@@ -12,7 +12,7 @@ from .class_scores import ClassScores  # noqa: F401
 from .featureset import FeatureSet  # noqa: F401
 from .training import epoch_loop, train_and_validate, train_classifier  # noqa: F401
 from .sweep import SweepConfig, partial_fit_rows_group, rank_sweep, sweep_loop, train_sweep  # noqa: F401
-from .sampling import class_counts, effective_number_weights, logit_adjustment, mixup_plan, row_batches, subsample_rows, subsample_targets  # noqa: F401
+from .sampling import class_counts, effective_number_weights, group_balance_weights, logit_adjustment, mixup_plan, row_batches, subsample_rows, subsample_targets  # noqa: F401
 from .validation import Validation, previous_accuracies, validate  # noqa: F401
 from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, category_bins, grouped_validate  # noqa: F401
 from .taxonomy import TaxonomicScores  # noqa: F401
@@ -31,7 +31,7 @@ __all__ = [
     "FeatureSet", "epoch_loop", "train_classifier", "train_and_validate",
     "SweepConfig", "partial_fit_rows_group", "sweep_loop", "train_sweep", "rank_sweep",
     "evaluate_classes", "ClassScores",
-    "class_counts", "effective_number_weights", "logit_adjustment", "subsample_targets", "subsample_rows", "row_batches", "mixup_plan",
+    "class_counts", "effective_number_weights", "logit_adjustment", "subsample_targets", "subsample_rows", "row_batches", "mixup_plan", "group_balance_weights",
     "Validation", "validate", "previous_accuracies",
     "grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability",
     "ranking_validate", "RankedValidation", "similarity_levels",

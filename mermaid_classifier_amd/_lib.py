@@ -56,11 +56,14 @@ SYMBOLS = [
     "mmc_trainer_set_dropout", "mmc_trainer_partial_fit_set_mixed", "mmc_trainer_group_partial_fit_set_mixed", "mmc_trainer_loss_gradient_mixed",
     "mmc_trainer_set_lr_schedule", "mmc_trainer_lr_at", "mmc_lr_schedule_at", "mmc_trainer_set_grad_clip", "mmc_trainer_grad_norms",
     "mmc_trainer_set_ema", "mmc_trainer_ema_state", "mmc_trainer_eval_weights", "mmc_trainer_optimizer_options",
+    "mmc_trainer_set_group_dro", "mmc_trainer_group_dro_state", "mmc_trainer_partial_fit_set_weighted",
+    "mmc_trainer_group_partial_fit_set_weighted", "mmc_trainer_loss_gradient_weighted",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 # include/mmc.h, "optimiser options"
 MMC_LR_CONSTANT, MMC_LR_LINEAR, MMC_LR_COSINE = 0, 1, 2
 MMC_WEIGHTS_RAW, MMC_WEIGHTS_AVERAGED = 0, 1
+MMC_DRO_MAX_GROUPS = 1024   # include/mmc.h, "group-robust training"
 
 
 class LibraryMissingError(ImportError):
@@ -276,6 +279,17 @@ def _load() -> C.CDLL:
     lib.mmc_trainer_optimizer_options.restype = i32
     lib.mmc_trainer_optimizer_options.argtypes = [vp, C.POINTER(i32), C.POINTER(ll), C.POINTER(ll), C.POINTER(f64), C.POINTER(f64),
                                                   C.POINTER(f64), C.POINTER(i32)]
+    lib.mmc_trainer_set_group_dro.restype = i32
+    lib.mmc_trainer_set_group_dro.argtypes = [vp, i32, f64]
+    lib.mmc_trainer_group_dro_state.restype = i32
+    lib.mmc_trainer_group_dro_state.argtypes = [vp, i32, vp]
+    lib.mmc_trainer_partial_fit_set_weighted.restype = i32
+    lib.mmc_trainer_partial_fit_set_weighted.argtypes = [vp, vp, vp, vp, vp, i64, i32, C.POINTER(C.c_double), vp]
+    lib.mmc_trainer_group_partial_fit_set_weighted.restype = i32
+    lib.mmc_trainer_group_partial_fit_set_weighted.argtypes = [C.POINTER(vp), i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                               C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_double), vp]
+    lib.mmc_trainer_loss_gradient_weighted.restype = i32
+    lib.mmc_trainer_loss_gradient_weighted.argtypes = [vp, vp, vp, vp, vp, vp, f64, i32, i64, vp, vp, vp, vp, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

@@ -24,6 +24,10 @@
 //   schedule  lr_s = lr w(s) d(s) in double on the host, step_size = (float)(lr_s / bc1)  mmc_lr_schedule_at
 //   clipping  norm over every gW(l), gb(l); coef = fminf(1, max_norm / (norm + 1e-6))     sumsq_kernel, gnorm_finalize_kernel
 //   update    Adam on g * coef, then the shadow s = s + om_d (p - s)                      adam_opt_kernel
+// Per pass, off by default (include/mmc.h, "group-robust training"; a member without either array runs ce_grad_kernel as ever):
+//   weights   the row's normaliser is s_i = r_i / sum of the masses r_i w(y_i), one rounded product ce_grad_weighted_kernel, ce_grad_rows<., true>
+//   group DRO q over the rows' groups moves by exp(eta L_a) per step on the device                 dro_update_kernel
+//             dZ(L) and the row losses take c_i = q_a / V_a                                        row_scale_kernel
 //
 // Every step is the step of a group of trainers (trainer_group_step): each kind of launch once, one member per blockIdx.z, the
 // member's operands in a by-value descriptor array.  A trainer on its own -- the host-fed pass, mmc_trainer_partial_fit_set, the
@@ -248,15 +252,19 @@ __device__ __forceinline__ float wave_sum(float v)
 //   dl_i/dz_c = om_eps w_t f (p_c - [c == t]) + eps_k (p_c w_total - w_c),   f = m + gamma p_t pw nll   (gamma = 0: m = f = 1)
 //   The two extra row sums are lane-strided sums and the butterfly of the softmax denominator.  Everything is finite on a finite
 //   row: q = 0 (p_t rounds to 1) gives m = 0 and pw in {0, 1}; p_t = 0 leaves f = m.
-template <bool GENERAL>
+// ROWS (ce_grad_weighted_kernel alone): the row's normaliser is s_i = rw[row] * inv_wsum, one rounded product, wherever the others
+//   read inv_wsum (include/mmc.h, "group-robust training"); rw null: inv_wsum itself.
+template <bool GENERAL, bool ROWS = false>
 __device__ __forceinline__ void ce_grad_rows(int block, const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
                                              const float* __restrict__ cw,   // [K] or null
-                                             float inv_wsum, float* __restrict__ dlogits, float* __restrict__ row_loss, const CeLoss& ls)
+                                             float inv_wsum, float* __restrict__ dlogits, float* __restrict__ row_loss, const CeLoss& ls,
+                                             const float* __restrict__ rw = nullptr)
 {
 #pragma clang fp contract(off)   // nothing here has ever been fused
     const int lane = threadIdx.x & 63;
     const int row = block * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
+    if (ROWS && rw) inv_wsum = rw[row] * inv_wsum;
     const float* z = logits + (size_t)row * K;
     if (GENERAL) {
         const float* pr = ls.prior;
@@ -444,6 +452,153 @@ __global__ __launch_bounds__(256) void ce_grad_mixed_kernel(const CeMixGroup g)
     const CeMixDesc& d = g.d[blockIdx.z];
     if ((int)blockIdx.x * 4 >= d.M) return;
     ce_grad_rows_mixed(blockIdx.x, d.logits, d.y, d.y2, d.M, d.K, d.cw, d.inv_wsum, d.lam, d.oml, d.dlogits, d.row_loss, d.loss);
+}
+
+// ---- group-robust training (include/mmc.h): the loss stage of a member with per-row weights or group DRO.  The other members of
+// the same step keep ce_grad_kernel / ce_grad_mixed_kernel.
+struct CeRowDesc {
+    CeDesc c;          // inv_wsum: g = (float)(1 / sum of the row masses), or 1.0f for a member with groups
+    const float* rw;   // the weights of the mini-batch's positions, or null (all 1)
+};
+struct CeRowGroup { CeRowDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(CeRowGroup) <= 4096, "kernel-argument limit");
+
+__global__ __launch_bounds__(256) void ce_grad_weighted_kernel(const CeRowGroup g)
+{
+    const CeRowDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 4 >= d.c.M) return;
+    if (d.c.general)
+        ce_grad_rows<true, true>(blockIdx.x, d.c.logits, d.c.y, d.c.M, d.c.K, d.c.cw, d.c.inv_wsum, d.c.dlogits, d.c.row_loss, d.c.loss, d.rw);
+    else
+        ce_grad_rows<false, true>(blockIdx.x, d.c.logits, d.c.y, d.c.M, d.c.K, d.c.cw, d.c.inv_wsum, d.c.dlogits, d.c.row_loss, d.c.loss, d.rw);
+}
+
+// The group DRO update of a member's step, one workgroup of 1024 threads: from R_i = row_loss[i] (normaliser r_i) and the groups
+// a_i it forms S_a, moves and renormalises logq, and leaves every row's scale c_i = (float)(exp(logq_a) / V_a).  All in double.
+//   S_a   thread = group: GW = ceil(G / 64) waves cover the groups once, so the 16 waves make NS = 16 / GW slices of rows.  The rows
+//         go through LDS in tiles of kDroTile; slice s takes rows [s per, (s + 1) per) of each tile, per = ceil(tile rows / NS),
+//         and adds R_i (or +0.0) to its group's register in position order, tile after tile; the slices' sums are added in slice
+//         order.  The order is a function of M and G alone: no atomics, and nothing depends on who trains beside the member.
+//   logq  logq_a += eta (S_a / V_a) where V_a > 0; lse = mx + log(sum_b exp(logq_b - mx)) with mx the maximum and the sum taken by
+//         one thread in index order; logq_a -= lse.
+// G <= 1024 = the workgroup, so per-group work is one thread each.  Latency-bound: G = 1024 scans every row in every wave and adds
+// 1024 terms serially (profiles/group_dro.txt).
+constexpr int kDroTile = 2048;
+struct DroDesc {
+    const float* row_loss;   // [M] R_i
+    const int32_t* group;    // [M] a_i in [0, G) (checked on the host)
+    const double* V;         // [G] mass of every group in this mini-batch
+    double* logq;            // [G] in / out
+    float* scale;            // [M] c_i
+    double* group_loss;      // [G] L_a, NaN where V_a = 0; or null
+    int M, G;
+    double eta;
+};
+struct DroGroup { DroDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(DroGroup) <= 4096, "kernel-argument limit");
+
+__global__ __launch_bounds__(1024) void dro_update_kernel(const DroGroup g)
+{
+#pragma clang fp contract(off)
+    __shared__ double Rs[kDroTile];
+    __shared__ int As[kDroTile];
+    __shared__ double part[1024];
+    __shared__ double lse_s;
+    const DroDesc& d = g.d[blockIdx.z];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int G = d.G, M = d.M;
+    const int GW = (G + 63) >> 6, NS = 16 / GW;
+    const int slice = wave / GW, grp = (wave % GW) * 64 + lane;
+    double acc = 0.0;
+    for (int r0 = 0; r0 < M; r0 += kDroTile) {
+        const int rows = M - r0 < kDroTile ? M - r0 : kDroTile;
+        for (int i = tid; i < rows; i += 1024) {
+            Rs[i] = (double)d.row_loss[r0 + i];
+            As[i] = d.group[r0 + i];
+        }
+        __syncthreads();
+        if (slice < NS) {
+            const int per = (rows + NS - 1) / NS;
+            const int b = slice * per, e = b + per < rows ? b + per : rows;
+            int i = b;
+            for (; i + 4 <= e; i += 4) {   // four rows' loads in flight; the adds stay in position order
+                const int a0 = As[i], a1 = As[i + 1], a2 = As[i + 2], a3 = As[i + 3];
+                const double r0 = Rs[i], r1 = Rs[i + 1], r2 = Rs[i + 2], r3 = Rs[i + 3];
+                acc += a0 == grp ? r0 : 0.0;
+                acc += a1 == grp ? r1 : 0.0;
+                acc += a2 == grp ? r2 : 0.0;
+                acc += a3 == grp ? r3 : 0.0;
+            }
+            for (; i < e; ++i) {
+                const double r0 = Rs[i];
+                acc += As[i] == grp ? r0 : 0.0;
+            }
+        }
+        __syncthreads();
+    }
+    if (slice < NS && grp < G) part[slice * G + grp] = acc;   // NS G <= (16 / GW) (64 GW) = 1024
+    __syncthreads();
+    double lqa = 0.0, Va = 0.0;
+    if (tid < G) {
+        double S = 0.0;
+        for (int s = 0; s < NS; ++s) S += part[s * G + tid];
+        Va = d.V[tid];
+        lqa = d.logq[tid];
+        double L = __builtin_nan("");
+        if (Va > 0.0) {
+            L = S / Va;
+            lqa = lqa + d.eta * L;
+        }
+        if (d.group_loss) d.group_loss[tid] = L;
+    }
+    __syncthreads();
+    part[tid] = tid < G ? lqa : -INFINITY;
+    __syncthreads();
+    for (int o = 512; o >= 1; o >>= 1) {
+        if (tid < o) part[tid] = fmax(part[tid], part[tid + o]);
+        __syncthreads();
+    }
+    const double mx = part[0];
+    __syncthreads();
+    part[tid] = tid < G ? exp(lqa - mx) : 0.0;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+#pragma unroll 16
+        for (int b = 0; b < G; ++b) s += part[b];
+        lse_s = mx + log(s);
+    }
+    __syncthreads();
+    if (tid < G) {
+        lqa = lqa - lse_s;
+        d.logq[tid] = lqa;
+        part[tid] = Va > 0.0 ? exp(lqa) / Va : 0.0;
+    }
+    __syncthreads();
+    for (int i = tid; i < M; i += 1024) d.scale[i] = (float)part[d.group[i]];
+}
+
+// dlogits[i][:] = c_i dlogits[i][:], row_loss[i] = c_i row_loss[i]: one rounded fp32 product per element.  One wave per row.
+struct RowScaleDesc {
+    float *dlogits, *row_loss;
+    const float* scale;
+    int M, K;
+};
+struct RowScaleGroup { RowScaleDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(RowScaleGroup) <= 4096, "kernel-argument limit");
+
+__global__ __launch_bounds__(256) void row_scale_kernel(const RowScaleGroup g)
+{
+#pragma clang fp contract(off)
+    const RowScaleDesc& d = g.d[blockIdx.z];
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= d.M) return;
+    const float c = d.scale[row];
+    float* z = d.dlogits + (size_t)row * d.K;
+    for (int k = lane; k < d.K; k += 64) z[k] = c * z[k];
+    if (lane == 0) d.row_loss[row] = c * d.row_loss[row];
 }
 
 // db[n] = sum_m dZ[m][n]; thread per column, rows in order (four chains)
@@ -779,6 +934,14 @@ struct mmc_trainer {
     double ema_decay = 0.0;                             // 0 = no averaged weights
     std::vector<DevBuf<float>> sW, sb;                  // the shadow: averaged weights (empty without)
     int eval_which = MMC_WEIGHTS_RAW;                   // what the eval-mode forward reads
+    // group-robust training (mmc_trainer_set_group_dro; the arrays of a weighted pass): all off = today's launches
+    int n_groups = 0;                                   // 0 = no group DRO
+    double dro_eta = 0.0;
+    DevBuf<double> logq;                                // [n_groups] log q, normalised; lives across steps and passes
+    DevBuf<float> row_w;                                // device copy of a weighted pass's row weights, by position
+    DevBuf<int32_t> row_g;                              // and of its groups
+    DevBuf<double> group_mass;                          // [steps][n_groups] V_a of every mini-batch of the pass
+    DevBuf<float> row_scale;                            // [mb] c_i of the step
 };
 
 #define T_K(expr)                                                                   \
@@ -1043,6 +1206,60 @@ extern "C" int mmc_trainer_optimizer_options(mmc_trainer* t, int* lr_kind, long 
     return MMC_OK;
 }
 
+// ---- group-robust training (include/mmc.h) -------------------------------------------------------------------------------
+// lse = mx + log(sum_b exp(logq_b - mx)), the sum in index order: the host form of dro_update_kernel's normaliser
+static double logq_lse(const double* logq, int G)
+{
+    double mx = logq[0];
+    for (int a = 1; a < G; ++a) mx = std::max(mx, logq[a]);
+    double s = 0.0;
+    for (int a = 0; a < G; ++a) s += std::exp(logq[a] - mx);
+    return mx + std::log(s);
+}
+
+extern "C" int mmc_trainer_set_group_dro(mmc_trainer* t, int n_groups, double eta)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (n_groups < 0 || n_groups > MMC_DRO_MAX_GROUPS) return mmc_fail(MMC_ERR_ARG, "n_groups = %d outside [0, %d]", n_groups, MMC_DRO_MAX_GROUPS);
+    if (!(eta >= 0.0 && eta <= 10.0)) return mmc_fail(MMC_ERR_ARG, "eta = %g outside [0, 10]", eta);
+    HIP_TRY(hipSetDevice(t->device));
+    DevBuf<double> logq;
+    if (n_groups) {   // passes synchronise their stream before they return, so nothing in flight reads the state that is replaced here
+        if (!logq.alloc(n_groups)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the group distribution (%d groups)", n_groups);
+        const std::vector<double> uniform((size_t)n_groups, -std::log((double)n_groups));
+        hipError_t e = hipMemcpy(logq, uniform.data(), (size_t)n_groups * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "uploading the group distribution: %s", hipGetErrorString(e));
+    }
+    t->logq = std::move(logq);
+    t->n_groups = n_groups;
+    t->dro_eta = eta;
+    return MMC_OK;
+}
+
+extern "C" int mmc_trainer_group_dro_state(mmc_trainer* t, int set, double* log_q)
+{
+    if (!t || !log_q) return mmc_fail(MMC_ERR_ARG, "NULL argument");
+    if (!t->n_groups) return mmc_fail(MMC_ERR_ARG, "the trainer keeps no group distribution (mmc_trainer_set_group_dro)");
+    const int G = t->n_groups;
+    HIP_TRY(hipSetDevice(t->device));
+    if (!set) {
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(log_q, t->logq, (size_t)G * 8, hipMemcpyDeviceToHost));
+        return MMC_OK;
+    }
+    for (int a = 0; a < G; ++a)
+        if (!std::isfinite(log_q[a])) return mmc_fail(MMC_ERR_ARG, "log_q[%d] = %g is not finite", a, log_q[a]);
+    // a state that is normalised already (what a read returns: |lse| at rounding level) goes back as it is, so a resume continues
+    // on the bits it left; anything else is renormalised
+    std::vector<double> q(log_q, log_q + G);
+    const double lse = logq_lse(q.data(), G);
+    if (std::fabs(lse) > 0x1p-40)
+        for (int a = 0; a < G; ++a) q[a] = q[a] - lse;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(t->logq, q.data(), (size_t)G * 8, hipMemcpyHostToDevice));
+    return MMC_OK;
+}
+
 static int trainer_reserve(mmc_trainer* t, int64_t n, int mb, int steps)
 {
     int r;
@@ -1072,6 +1289,12 @@ struct StepMember {
     int slot;
     bool mixed;       // the rows were mixed: t->y2 holds the partners' labels, the loss stage takes two targets
     float lam;
+    // group-robust training: a weighted member takes ce_grad_weighted_kernel; inv_wsum is then 1 / sum of the row masses, or 1.0f
+    // with groups, whose rows dro_update_kernel and row_scale_kernel normalise
+    bool weighted = false;
+    const float* rw = nullptr;      // device: the weights of the mini-batch's positions, or null (all 1)
+    const int32_t* rg = nullptr;    // device: their groups, or null (row weights only)
+    const double* V = nullptr;      // device: [n_groups] the groups' masses in this mini-batch
 };
 
 template <bool TA, bool TB, int EPI0, int EPI1>
@@ -1157,10 +1380,22 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
     {
         CeGroup g;
         CeMixGroup gm;
-        int k = 0, km = 0, mmax = 0, mmax_mixed = 0;
+        CeRowGroup gr;
+        DroGroup gd;
+        RowScaleGroup gs;
+        int k = 0, km = 0, kr = 0, kd = 0, mmax = 0, mmax_mixed = 0, mmax_rows = 0, mmax_dro = 0;
         for (int i = 0; i < cnt; ++i) {
             const mmc_trainer* t = act[i].t;
-            if (act[i].mixed) {
+            if (act[i].weighted) {
+                gr.d[kr++] = CeRowDesc{ce_desc(t, t->H[t->L], t->y + act[i].off, act[i].cur, act[i].inv_wsum), act[i].rw};
+                mmax_rows = std::max(mmax_rows, act[i].cur);
+                if (act[i].rg) {
+                    gd.d[kd] = DroDesc{t->row_loss, act[i].rg, act[i].V, t->logq, t->row_scale, nullptr, act[i].cur, t->n_groups, t->dro_eta};
+                    gs.d[kd] = RowScaleDesc{t->dZ[t->L], t->row_loss, t->row_scale, act[i].cur, t->K};
+                    ++kd;
+                    mmax_dro = std::max(mmax_dro, act[i].cur);
+                }
+            } else if (act[i].mixed) {
                 gm.d[km++] = CeMixDesc{t->H[t->L], t->y + act[i].off, t->y2 + act[i].off, t->cw, t->dZ[t->L], t->row_loss, act[i].cur, t->K,
                                        act[i].inv_wsum, act[i].lam, 1.0f - act[i].lam, trainer_ce_loss(t)};
                 mmax_mixed = std::max(mmax_mixed, act[i].cur);
@@ -1171,6 +1406,11 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
         }
         if (k) hipLaunchKernelGGL(ce_grad_kernel, dim3((mmax + 3) / 4, 1, k), dim3(256), 0, st, g);
         if (km) hipLaunchKernelGGL(ce_grad_mixed_kernel, dim3((mmax_mixed + 3) / 4, 1, km), dim3(256), 0, st, gm);
+        if (kr) hipLaunchKernelGGL(ce_grad_weighted_kernel, dim3((mmax_rows + 3) / 4, 1, kr), dim3(256), 0, st, gr);
+        if (kd) {   // the groups' members: q moves on the device, then every row takes its group's share
+            hipLaunchKernelGGL(dro_update_kernel, dim3(1, 1, kd), dim3(1024), 0, st, gd);
+            hipLaunchKernelGGL(row_scale_kernel, dim3((mmax_dro + 3) / 4, 1, kd), dim3(256), 0, st, gs);
+        }
     }
     // regularised loss of this mini-batch (before the update): data + (0.5 alpha / mb) sum W^2
     for (int l = 0; l < Lmax; ++l) {
@@ -1351,6 +1591,44 @@ int minibatch_wsums_mixed(const char* who, const mmc_trainer* t, const int32_t* 
     return 0;
 }
 
+// minibatch_wsums of a weighted pass (include/mmc.h, "group-robust training"): position i carries the mass
+// v_i = (double)rw[i] (double)w[y_i] (rw null: 1), summed in double in position order -- into wsums[s] without groups, into
+// vmass[s G + rg[i]] with them (wsums[s] is then 1: the loss stage runs with g = 1).  Rejects a weight that is negative or not
+// finite, a group outside [0, G), a mini-batch without mass or in which no group has mass.
+int minibatch_masses(const char* who, const mmc_trainer* t, const int32_t* y, const int64_t* idx, const float* rw, const int32_t* rg, int G,
+                     int64_t n, int mb, std::vector<double>* wsums, std::vector<double>* vmass)
+{
+    const int steps = (int)((n + mb - 1) / mb);
+    for (int64_t i = 0; i < n; ++i) {
+        if (rw && !(rw[i] >= 0.f && std::isfinite(rw[i])))
+            return mmc_fail(MMC_ERR_ARG, "%srow_weight[%lld] = %g is negative or not finite", who, (long long)i, (double)rw[i]);
+        if (rg && (rg[i] < 0 || rg[i] >= G))
+            return mmc_fail(MMC_ERR_ARG, "%srow_group[%lld] = %d outside [0, %d)", who, (long long)i, rg[i], G);
+    }
+    wsums->assign(steps, 1.0);
+    if (rg) vmass->assign((size_t)steps * G, 0.0);
+    for (int s = 0; s < steps; ++s) {
+        const int64_t start = (int64_t)s * mb;
+        const int cur = batch_rows(n, start, mb);
+        double wsum = 0.0;
+        double* V = rg ? vmass->data() + (size_t)s * G : nullptr;
+        for (int i = 0; i < cur; ++i) {
+            const double w = t->cw ? (double)t->cw_host[y[idx ? idx[start + i] : start + i]] : 1.0;
+            const double v = (rw ? (double)rw[start + i] : 1.0) * w;
+            if (rg) V[rg[start + i]] += v; else wsum += v;
+        }
+        if (rg) {
+            bool any = false;
+            for (int a = 0; a < G; ++a) any = any || V[a] > 0.0;
+            if (!any) return mmc_fail(MMC_ERR_ARG, "%sno group of mini-batch %d has mass", who, s);
+        } else {
+            if (!(wsum > 0.0)) return mmc_fail(MMC_ERR_ARG, "%smini-batch %d has zero total mass", who, s);
+            (*wsums)[s] = wsum;
+        }
+    }
+    return 0;
+}
+
 // torch_classifier.py:293-298: sum of loss.item() * mb_size over the steps, over n
 double pass_avg_loss(const std::vector<float>& h, int mb, int64_t n)
 {
@@ -1422,10 +1700,13 @@ struct SetPass {
     const int64_t* visit = nullptr;
     const int64_t* partner = nullptr;   // a mixed pass: partner rows and one lam per mini-batch (both or neither)
     const float* lam = nullptr;
+    const float* row_weight = nullptr;  // a weighted pass: either or both, by position
+    const int32_t* row_group = nullptr;
     int64_t n = 0;
     int mb = 0, steps = 0;
     int64_t chunk = 0, steps_per_chunk = 0, stage_rows = 0;
     std::vector<double> wsums;
+    std::vector<double> vmass;          // [steps][n_groups] of a pass with groups
 };
 
 // `who` prefixes the message: "" for the solo call, "member 3: " for a member of a group
@@ -1471,11 +1752,12 @@ int train_chunk_bound(int64_t* bound)
 }
 
 int plan_set_pass(const char* who, mmc_trainer* t, const mmc_featureset* fs, const int64_t* visit, const int64_t* partner,
-                  const float* lam, int64_t n, int batch_size, int64_t bound, SetPass* p)
+                  const float* lam, const float* row_weight, const int32_t* row_group, int64_t n, int batch_size, int64_t bound, SetPass* p)
 {
     const int mb = (int)(batch_size < n ? batch_size : n);
     if ((n + mb - 1) / mb > (int64_t)1 << 30) return mmc_fail(MMC_ERR_ARG, "%s%lld rows in mini-batches of %d: too many steps for one pass", who, (long long)n, mb);
     p->t = t; p->visit = visit; p->partner = partner; p->lam = lam; p->n = n;
+    p->row_weight = row_weight; p->row_group = row_group;
     p->mb = mb;
     p->steps = (int)((n + mb - 1) / mb);
     // the largest multiple of the mini-batch not above the bound, at least one mini-batch, and no more than a gather's grid / `rows` hold
@@ -1487,6 +1769,8 @@ int plan_set_pass(const char* who, mmc_trainer* t, const mmc_featureset* fs, con
     p->steps_per_chunk = chunk / mb;
     p->stage_rows = chunk < n ? chunk : n;
     if (partner) return minibatch_wsums_mixed(who, t, fs->y_host.data(), visit, partner, lam, n, mb, &p->wsums);
+    if (row_weight || row_group)
+        return minibatch_masses(who, t, fs->y_host.data(), visit, row_weight, row_group, t->n_groups, n, mb, &p->wsums, &p->vmass);
     return minibatch_wsums(who, t, fs->y_host.data(), visit, n, mb, &p->wsums);
 }
 
@@ -1498,6 +1782,9 @@ int reserve_set_pass(const SetPass& p)
     if (r) return r;
     if (p.visit && (r = t->visit.reserve(p.n))) return r;
     if (p.partner && ((r = t->y2.reserve(p.stage_rows)) || (r = t->partner.reserve(p.n)) || (r = t->lam.reserve(p.steps)))) return r;
+    if (p.row_weight && (r = t->row_w.reserve(p.n))) return r;
+    if (p.row_group && ((r = t->row_g.reserve(p.n)) || (r = t->group_mass.reserve((int64_t)p.steps * t->n_groups)) || (r = t->row_scale.reserve(p.mb))))
+        return r;
     return 0;
 }
 
@@ -1531,7 +1818,8 @@ int gather_chunk(mmc_trainer* t, const mmc_featureset* fs, bool visited, bool mi
 // run the kernels of the host-fed pass on the same values: same bits.  `grouped` is the entry point's way of naming a member and of
 // reporting a failed reservation; the solo entry is a group of one that names nobody.
 int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit,
-             const int64_t* const* partner, const float* const* lam, const int64_t* n, const int* batch_size, double* avg_loss, hipStream_t st)
+             const int64_t* const* partner, const float* const* lam, const float* const* row_weight, const int32_t* const* row_group,
+             const int64_t* n, const int* batch_size, double* avg_loss, hipStream_t st)
 {
     std::vector<SetPass> mem(count);
     char who[MMC_TRAINER_GROUP_MAX][32];
@@ -1541,13 +1829,17 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
         if (grouped) std::snprintf(who[m], sizeof who[m], "member %d: ", m);
         if ((r = check_set_pass(who[m], trainers[m], fs, visit[m], n[m], batch_size[m]))) return r;
         if ((r = check_mix_plan(who[m], fs, partner ? partner[m] : nullptr, lam ? lam[m] : nullptr, n[m], batch_size[m]))) return r;
+        const bool weighted = (row_weight && row_weight[m]) || (row_group && row_group[m]);
+        if (weighted && partner && partner[m]) return mmc_fail(MMC_ERR_ARG, "%sa mixed pass takes no row weights or groups", who[m]);
+        if (row_group && row_group[m] && !trainers[m]->n_groups)
+            return mmc_fail(MMC_ERR_ARG, "%srow_group needs mmc_trainer_set_group_dro(n_groups > 0) on the trainer", who[m]);
     }
     int64_t bound = 0;
     if ((r = train_chunk_bound(&bound))) return r;
     int max_steps = 0;
     for (int m = 0; m < count; ++m) {
-        if ((r = plan_set_pass(who[m], trainers[m], fs, visit[m], partner ? partner[m] : nullptr, lam ? lam[m] : nullptr, n[m], batch_size[m],
-                               bound, &mem[m])))
+        if ((r = plan_set_pass(who[m], trainers[m], fs, visit[m], partner ? partner[m] : nullptr, lam ? lam[m] : nullptr,
+                               row_weight ? row_weight[m] : nullptr, row_group ? row_group[m] : nullptr, n[m], batch_size[m], bound, &mem[m])))
             return r;
         max_steps = std::max(max_steps, mem[m].steps);
     }
@@ -1567,6 +1859,14 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
             HIP_TRY(hipMemcpyAsync(mem[m].t->partner, mem[m].partner, (size_t)mem[m].n * 8, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(mem[m].t->lam, mem[m].lam, (size_t)mem[m].steps * 4, hipMemcpyHostToDevice, st));
         }
+    for (int m = 0; m < count; ++m) {
+        const SetPass& p = mem[m];
+        if (p.row_weight) HIP_TRY(hipMemcpyAsync(p.t->row_w, p.row_weight, (size_t)p.n * 4, hipMemcpyHostToDevice, st));
+        if (p.row_group) {
+            HIP_TRY(hipMemcpyAsync(p.t->row_g, p.row_group, (size_t)p.n * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(p.t->group_mass, p.vmass.data(), p.vmass.size() * 8, hipMemcpyHostToDevice, st));
+        }
+    }
     StepMember act[MMC_TRAINER_GROUP_MAX];
     for (int s = 0; s < max_steps; ++s) {
         int cnt = 0;
@@ -1578,8 +1878,15 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
                 const int rows = (int)((p.n - c0) < p.chunk ? (p.n - c0) : p.chunk);
                 if ((r = gather_chunk(p.t, fs, p.visit != nullptr, p.partner != nullptr, p.mb, c0, rows, st))) return r;
             }
-            act[cnt++] = StepMember{p.t, start - c0, batch_rows(p.n, start, p.mb), (float)(1.0 / p.wsums[s]), s, p.partner != nullptr,
-                                    p.partner ? p.lam[s] : 0.f};
+            act[cnt] = StepMember{p.t, start - c0, batch_rows(p.n, start, p.mb), (float)(1.0 / p.wsums[s]), s, p.partner != nullptr,
+                                  p.partner ? p.lam[s] : 0.f};
+            if (p.row_weight || p.row_group) {   // the pass's arrays are indexed by position of the pass, not of the chunk
+                act[cnt].weighted = true;
+                act[cnt].rw = p.row_weight ? p.t->row_w + start : nullptr;
+                act[cnt].rg = p.row_group ? p.t->row_g + start : nullptr;
+                act[cnt].V = p.row_group ? p.t->group_mass + (size_t)s * p.t->n_groups : nullptr;
+            }
+            ++cnt;
         }
         if ((r = trainer_group_step(act, cnt, st))) return r;
     }
@@ -1603,7 +1910,7 @@ extern "C" int mmc_trainer_partial_fit_set(mmc_trainer* t, mmc_featureset* fs, c
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
-    return set_pass(false, &t, 1, fs, &visit, nullptr, nullptr, &n, &batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
+    return set_pass(false, &t, 1, fs, &visit, nullptr, nullptr, nullptr, nullptr, &n, &batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
 }
 
 // mmc_trainer_partial_fit_set on mixed rows (include/mmc.h, "regularisers"); NULL partner and lam: that call itself.
@@ -1612,7 +1919,7 @@ extern "C" int mmc_trainer_partial_fit_set_mixed(mmc_trainer* t, mmc_featureset*
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
-    return set_pass(false, &t, 1, fs, &visit, &partner, &lam, &n, &batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
+    return set_pass(false, &t, 1, fs, &visit, &partner, &lam, nullptr, nullptr, &n, &batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
 }
 
 // mmc_trainer_partial_fit_set for `count` trainers over one set in the launches of one pass (include/mmc.h).
@@ -1639,7 +1946,38 @@ extern "C" int mmc_trainer_group_partial_fit_set_mixed(mmc_trainer* const* train
     }
     if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
     if (!partner != !lam) return mmc_fail(MMC_ERR_ARG, "partner and lam go together: only %s was given", partner ? "partner" : "lam");
-    return set_pass(true, trainers, count, fs, visit, partner, lam, n, batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
+    return set_pass(true, trainers, count, fs, visit, partner, lam, nullptr, nullptr, n, batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
+}
+
+// mmc_trainer_partial_fit_set with per-row weights and / or groups (include/mmc.h, "group-robust training"); both NULL: that call.
+extern "C" int mmc_trainer_partial_fit_set_weighted(mmc_trainer* t, mmc_featureset* fs, const int64_t* visit, const float* row_weight,
+                                                    const int32_t* row_group, int64_t n, int batch_size, double* avg_loss, void* hip_stream)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
+    return set_pass(false, &t, 1, fs, &visit, nullptr, nullptr, &row_weight, &row_group, &n, &batch_size, avg_loss,
+                    static_cast<hipStream_t>(hip_stream));
+}
+
+// The grouped pass with weights and groups per member: arrays of `count` pointers, or NULL; a member whose two entries are NULL
+// takes the plain kernels.
+extern "C" int mmc_trainer_group_partial_fit_set_weighted(mmc_trainer* const* trainers, int count, mmc_featureset* fs,
+                                                          const int64_t* const* visit, const float* const* row_weight,
+                                                          const int32_t* const* row_group, const int64_t* n, const int* batch_size,
+                                                          double* avg_loss, void* hip_stream)
+{
+    if (avg_loss && count >= 1 && count <= MMC_TRAINER_GROUP_MAX)
+        for (int m = 0; m < count; ++m) avg_loss[m] = 0.0;
+    if (!trainers || !visit || !n || !batch_size) return mmc_fail(MMC_ERR_ARG, "trainers / visit / n / batch_size is NULL");
+    if (count < 1 || count > MMC_TRAINER_GROUP_MAX) return mmc_fail(MMC_ERR_ARG, "count = %d outside [1, %d]", count, MMC_TRAINER_GROUP_MAX);
+    for (int m = 0; m < count; ++m) {
+        if (!trainers[m]) return mmc_fail(MMC_ERR_ARG, "member %d: trainer handle is NULL", m);
+        for (int o = 0; o < m; ++o)
+            if (trainers[o] == trainers[m]) return mmc_fail(MMC_ERR_ARG, "member %d is the same trainer as member %d", m, o);
+    }
+    if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
+    return set_pass(true, trainers, count, fs, visit, nullptr, nullptr, row_weight, row_group, n, batch_size, avg_loss,
+                    static_cast<hipStream_t>(hip_stream));
 }
 
 extern "C" int mmc_trainer_get_params(mmc_trainer* t, float* const* W, float* const* b)
@@ -1804,6 +2142,71 @@ extern "C" int mmc_trainer_loss_gradient_mixed(mmc_trainer* t, const float* logi
     g.d[0] = CeMixDesc{t->H[L], y1d, y2d, t->cw, t->dZ[L], t->row_loss, mb, t->K, (float)(1.0 / wsum), lam, oml, trainer_ce_loss(t)};
     hipLaunchKernelGGL(ce_grad_mixed_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MMC_OK;
+}
+
+// The weighted loss stage of a step on caller logits and an explicit log q (include/mmc.h, "group-robust training"): the step's own
+// kernels -- ce_grad_weighted_kernel, then with groups dro_update_kernel and row_scale_kernel -- on buffers of the trainer's scratch.
+// The trainer's own distribution is neither read nor written.
+extern "C" int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* logits, const int32_t* y, const float* row_weight,
+                                                  const int32_t* row_group, const double* log_q_in, double eta, int n_groups, int64_t n,
+                                                  float* dlogits, float* row_loss, double* log_q_out, double* group_loss, void* hip_stream)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!logits || !y || !dlogits || !row_loss) return mmc_fail(MMC_ERR_ARG, "logits / y / dlogits / row_loss is NULL");
+    if (n < 1 || n > kTrainerForwardRows) return mmc_fail(MMC_ERR_ARG, "n = %lld outside [1, %d]", (long long)n, kTrainerForwardRows);
+    const int G = row_group ? n_groups : 0;
+    if (row_group) {
+        if (n_groups < 1 || n_groups > MMC_DRO_MAX_GROUPS) return mmc_fail(MMC_ERR_ARG, "n_groups = %d outside [1, %d]", n_groups, MMC_DRO_MAX_GROUPS);
+        if (!(eta >= 0.0 && eta <= 10.0)) return mmc_fail(MMC_ERR_ARG, "eta = %g outside [0, 10]", eta);
+        if (!log_q_in || !log_q_out) return mmc_fail(MMC_ERR_ARG, "row_group needs log_q_in and log_q_out");
+        for (int a = 0; a < G; ++a)
+            if (!std::isfinite(log_q_in[a])) return mmc_fail(MMC_ERR_ARG, "log_q_in[%d] = %g is not finite", a, log_q_in[a]);
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (y[i] < 0 || y[i] >= t->K) return mmc_fail(MMC_ERR_ARG, "label index y[%lld] = %d outside [0, %d)", (long long)i, y[i], t->K);
+    const int mb = (int)n, L = t->L;
+    std::vector<double> wsums, vmass;
+    int r = minibatch_masses("", t, y, nullptr, row_weight, row_group, G, n, mb, &wsums, &vmass);
+    if (r) return r;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipSetDevice(t->device));
+    if ((r = trainer_reserve(t, 0, mb, 1))) return r;
+    // scratch: V [G] and log q [G] and group loss [G] in double first (8-byte aligned), then y, groups, weights and c by row
+    void* sc = nullptr;
+    if ((r = trainer_scratch(t, (size_t)G * 24 + (size_t)mb * 16, &sc))) return r;
+    double* Vd = static_cast<double*>(sc);
+    double* lqd = Vd + G;
+    double* gld = lqd + G;
+    int32_t* yd = reinterpret_cast<int32_t*>(gld + G);
+    int32_t* gd = yd + mb;
+    float* wd = reinterpret_cast<float*>(gd + mb);
+    float* cd = wd + mb;
+    const size_t cells = (size_t)mb * t->K;
+    HIP_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(yd, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
+    if (row_weight) HIP_TRY(hipMemcpyAsync(wd, row_weight, (size_t)mb * 4, hipMemcpyHostToDevice, st));
+    CeRowGroup g;
+    g.d[0] = CeRowDesc{ce_desc(t, t->H[L], yd, mb, (float)(1.0 / wsums[0])), row_weight ? wd : nullptr};
+    hipLaunchKernelGGL(ce_grad_weighted_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
+    HIP_TRY(hipGetLastError());
+    if (row_group) {
+        HIP_TRY(hipMemcpyAsync(gd, row_group, (size_t)mb * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(Vd, vmass.data(), (size_t)G * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(lqd, log_q_in, (size_t)G * 8, hipMemcpyHostToDevice, st));
+        DroGroup du;
+        du.d[0] = DroDesc{t->row_loss, gd, Vd, lqd, cd, gld, mb, G, eta};
+        hipLaunchKernelGGL(dro_update_kernel, dim3(1), dim3(1024), 0, st, du);
+        RowScaleGroup rs;
+        rs.d[0] = RowScaleDesc{t->dZ[L], t->row_loss, cd, mb, t->K};
+        hipLaunchKernelGGL(row_scale_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, rs);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(log_q_out, lqd, (size_t)G * 8, hipMemcpyDeviceToHost, st));
+        if (group_loss) HIP_TRY(hipMemcpyAsync(group_loss, gld, (size_t)G * 8, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));

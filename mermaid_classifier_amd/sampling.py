@@ -13,6 +13,8 @@ dataset.py:222-347``; ``_rn <= target_n``, :292-310)           ``target`` rows o
 one epoch's batches over the kept rows                         ``row_batches(rows, batch_size)`` -> ``SweepConfig.batches``
 (none: Zhang et al. 2018, mixup)                               ``mixup_plan(visit, batch_size, alpha, rng)`` -> the plan of
                                                                ``mmc_trainer_partial_fit_set_mixed``
+(none: "per-source rebalancing",                               ``group_balance_weights(groups, labels)`` ->
+docs/research/balancing-experiments.md:141)                    ``partial_fit_rows(row_weight=)`` / ``SweepConfig.row_weight``
 =============================================================  ==========================================================
 
 A balancing configuration of ``docs/research/balancing-experiments.md`` is a class-weight dict, a subsample, or both, over one
@@ -28,7 +30,7 @@ import numpy as np
 
 from .featureset import FeatureSet
 
-__all__ = ["class_counts", "effective_number_weights", "logit_adjustment", "subsample_targets", "subsample_rows", "row_batches", "mixup_plan", "STRATEGIES"]
+__all__ = ["class_counts", "effective_number_weights", "logit_adjustment", "subsample_targets", "subsample_rows", "row_batches", "mixup_plan", "group_balance_weights", "STRATEGIES"]
 
 STRATEGIES = ("stratified", "balanced")
 
@@ -215,3 +217,25 @@ def mixup_plan(visit, batch_size: int, alpha: float, rng: np.random.Generator):
         partner[s * mb:s * mb + rows.size] = rows[rng.permutation(rows.size)]
         lam[s] = np.float32(rng.beta(float(alpha), float(alpha)))
     return partner, lam
+
+
+def group_balance_weights(groups, labels=None) -> np.ndarray:
+    """Static per-source rebalancing as row weights: ``r_i`` proportional to ``1 / n_group(i)``, the number of the given rows in row
+    i's group -- or, with ``labels``, to ``1 / n_(group, class)(i)`` -- scaled so that the mean over the rows given is 1.  Every
+    group (every group x class cell that occurs) then carries the same total weight.  -> float32, one weight per row: the
+    ``row_weight`` of ``TorchMLPClassifier.partial_fit_rows`` when ``groups`` covers the rows of the set.
+
+    ``groups`` (and ``labels``) are 1D and of one length; the values are only compared for equality."""
+    g = np.asarray(groups)
+    if g.ndim != 1 or g.size == 0:
+        raise ValueError(f"groups must be a non-empty 1D array, got shape {g.shape}")
+    _, cell = np.unique(g, return_inverse=True)
+    if labels is not None:
+        y = np.asarray(labels)
+        if y.shape != g.shape:
+            raise ValueError(f"labels has shape {y.shape}, groups {g.shape}")
+        _, yi = np.unique(y, return_inverse=True)
+        _, cell = np.unique(cell.astype(np.int64) * (int(yi.max()) + 1) + yi, return_inverse=True)
+    counts = np.bincount(cell)
+    w = 1.0 / counts[cell].astype(np.float64)
+    return (w * (g.size / w.sum())).astype(np.float32)

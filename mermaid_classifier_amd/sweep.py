@@ -39,7 +39,7 @@ from .backbone import _current_stream_ptr, _device_index
 from .calibration import CalibratedMLP, calibrate, evaluate, evaluate_classes
 from .featureset import FeatureSet
 from .metrics import grouped_validate
-from .torch_classifier import TorchMLPClassifier
+from .torch_classifier import TorchMLPClassifier, by_position, check_row_arrays
 from .training import EarlyStopping, _check_splits, _contiguous_batches, _fill_schedule_steps, _val_entries
 from .validation import validate
 
@@ -66,8 +66,20 @@ def _rows_per_classifier(rows, count: int) -> List[Any]:
     return entries
 
 
+def _arrays_per_classifier(name: str, arr, count: int) -> List[Any]:
+    """``row_weight`` / ``row_group`` as one entry per classifier: None and a single array stand for every classifier; a list / tuple
+    whose entries are all None or arrays is taken per classifier and must have ``count`` entries."""
+    if arr is None:
+        return [None] * count
+    if isinstance(arr, (list, tuple)) and len(arr) > 0 and all(a is None or np.ndim(a) >= 1 for a in arr):
+        if len(arr) != count:
+            raise ValueError(f"{name} has {len(arr)} entries for {count} classifiers")
+        return list(arr)
+    return [arr] * count
+
+
 def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, rows=None,
-                           classes: Optional[Sequence[Any]] = None) -> List[TorchMLPClassifier]:
+                           classes: Optional[Sequence[Any]] = None, *, row_weight=None, row_group=None) -> List[TorchMLPClassifier]:
     """``clf.partial_fit_rows(fs, rows_m, classes)`` for every classifier of ``clfs``, with the device work of all of them in one
     ``mmc_trainer_group_partial_fit_set`` call per ``MMC_TRAINER_GROUP_MAX`` (16) classifiers.  Parameters, Adam state,
     ``loss_curve_`` and ``n_iter_`` of each end up exactly as after its own ``partial_fit_rows``.
@@ -76,19 +88,31 @@ def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, r
     per classifier.  The classifiers may differ in everything a ``TorchMLPClassifier`` can be configured with (depth, widths,
     optimizer settings, class weights, mini-batch size, shuffle, seed) and in how many passes they have behind them.
 
+    ``row_weight`` / ``row_group`` as in ``partial_fit_rows`` (indexed by row of the set): None, one array for all, or a list with one
+    entry -- array or None -- per classifier.  A classifier whose two entries are None runs its plain kernels beside the others
+    (``mmc_trainer_group_partial_fit_set_weighted``).  One call of at most 16 classifiers cannot hold both a weighted member and one
+    with ``mixup_alpha > 0`` (``ValueError``): no entry point takes both.
+
     ``ValueError`` before any device work: ``rows`` that do not fit ``clfs``, the same classifier twice, a classifier on another
     device than the set.  A pass the library rejects (an index outside the set, a mini-batch of zero class weight, ...) raises
     as ``partial_fit_rows`` does and changes none of the classifiers of that call."""
     clfs = list(clfs)
     entries = _rows_per_classifier(rows, len(clfs))
+    weights = _arrays_per_classifier("row_weight", row_weight, len(clfs))
+    groups = _arrays_per_classifier("row_group", row_group, len(clfs))
     if len({id(c) for c in clfs}) != len(clfs):
         raise ValueError("the same classifier appears twice in clfs")
+    arrays = [check_row_arrays(clf, len(fs), w, g) for clf, w, g in zip(clfs, weights, groups)]
     for i, clf in enumerate(clfs):
         if _device_index(clf.device) != fs.device_index:
             raise ValueError(f"classifier {i} is on device {_device_index(clf.device)}, the feature set on device {fs.device_index}")
     lib = _lib.lib()
     for first in range(0, len(clfs), _lib.MMC_TRAINER_GROUP_MAX):
         group = clfs[first:first + _lib.MMC_TRAINER_GROUP_MAX]
+        members = arrays[first:first + _lib.MMC_TRAINER_GROUP_MAX]
+        weighted = any(w is not None or g is not None for w, g in members)
+        if weighted and any(float(clf.mixup_alpha) != 0.0 for clf in group):
+            raise ValueError("one grouped call cannot hold members with row_weight / row_group and members with mixup_alpha > 0")
         passes = [clf._begin_rows_pass(fs, r, classes) for clf, r in zip(group, entries[first:])]
         plans = [clf._mix_plan(v, n_m, b_m) for clf, (v, n_m, b_m) in zip(group, passes)]     # (visit, partner, lam) per member
         count = len(group)
@@ -97,7 +121,13 @@ def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, r
         n = (C.c_int64 * count)(*[int(p[1]) for p in passes])
         batch = (C.c_int * count)(*[int(p[2]) for p in passes])
         avg = (C.c_double * count)()
-        if all(partner is None for _, partner, _ in plans):
+        if weighted:                                          # a member without either keeps a NULL pair: its plain kernels
+            pos = [(by_position(w, v, n_m), by_position(g, v, n_m)) for (w, g), (v, _, _), (_, n_m, _) in zip(members, plans, passes)]
+            rw = (C.c_void_p * count)(*[None if w is None else w.ctypes.data for w, _ in pos])
+            rg = (C.c_void_p * count)(*[None if g is None else g.ctypes.data for _, g in pos])
+            _lib.check(lib.mmc_trainer_group_partial_fit_set_weighted(handles, count, fs._handle(), visit, rw, rg, n, batch, avg,
+                                                                      _current_stream_ptr(fs.device_index)))
+        elif all(partner is None for _, partner, _ in plans):
             _lib.check(lib.mmc_trainer_group_partial_fit_set(handles, count, fs._handle(), visit, n, batch, avg,
                                                              _current_stream_ptr(fs.device_index)))
         else:                                                 # a member without mixup keeps a NULL pair: it is not mixed
@@ -120,7 +150,9 @@ class SweepConfig:
     is ``train_classifier``'s argument of that name for this configuration.  ``dropout`` / ``input_dropout`` / ``mixup_alpha`` /
     ``regularizer_seed`` are the classifier's regularisers, again per member, and so are its optimiser options ``lr_schedule`` /
     ``warmup_steps`` / ``schedule_steps`` / ``final_lr_ratio`` / ``max_grad_norm`` / ``ema_decay`` (keyword only; a decaying schedule
-    with ``schedule_steps=None`` ends after ``nbr_epochs`` epochs of this member's own steps)."""
+    with ``schedule_steps=None`` ends after ``nbr_epochs`` epochs of this member's own steps).  ``row_weight`` / ``row_group`` (keyword
+    only; arrays indexed by row of the train set) go to every pass of this member, ``group_dro_eta`` / ``n_groups`` to its classifier:
+    one sweep can hold an ERM member, a group-balanced one (``group_dro_eta=0``) and DRO members side by side."""
     hidden_layer_sizes: Tuple[int, ...] = (500, 300, 100)
     learning_rate_init: float = 1e-4
     alpha: float = 1e-4
@@ -145,6 +177,11 @@ class SweepConfig:
     final_lr_ratio: float = field(default=0.0, kw_only=True)
     max_grad_norm: Optional[float] = field(default=None, kw_only=True)
     ema_decay: float = field(default=0.0, kw_only=True)
+    # group-robust training (include/mmc.h): the member's per-row arrays over the train set and its classifier's group DRO
+    row_weight: Any = field(default=None, kw_only=True)
+    row_group: Any = field(default=None, kw_only=True)
+    group_dro_eta: float = field(default=0.0, kw_only=True)
+    n_groups: Optional[int] = field(default=None, kw_only=True)
     batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None
     label_smoothing: float = 0.0
     focal_gamma: float = 0.0
@@ -159,7 +196,8 @@ class SweepConfig:
                                   logit_prior=self.logit_prior, dropout=self.dropout, input_dropout=self.input_dropout,
                                   mixup_alpha=self.mixup_alpha, regularizer_seed=self.regularizer_seed,
                                   lr_schedule=self.lr_schedule, warmup_steps=self.warmup_steps, schedule_steps=self.schedule_steps,
-                                  final_lr_ratio=self.final_lr_ratio, max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay)
+                                  final_lr_ratio=self.final_lr_ratio, max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay,
+                                  group_dro_eta=self.group_dro_eta, n_groups=self.n_groups)
 
 
 def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[Any]]],
@@ -222,7 +260,10 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
     transformed once, every head trains on the transformed sets, and every model returned is folded.
 
     ``logit_scaling`` as in ``train_classifier``, for every configuration; a configuration's own ``SweepConfig.logit_scaling`` wins over
-    it.  A configuration with neither is calibrated exactly as before."""
+    it.  A configuration with neither is calibrated exactly as before.
+
+    A configuration's ``row_weight`` / ``row_group`` go to each of its passes (``partial_fit_rows_group``); with ``transform=`` they
+    index the transformed train set, which has the train set's rows."""
     configs = list(configs)
     if not configs:
         raise ValueError("configs is empty")
@@ -256,7 +297,15 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
         return acc
 
     eval_val = evaluate_classes if class_scores else evaluate
-    results = sweep_loop(clfs, batches, lambda group, rows: partial_fit_rows_group(group, train, rows, classes=classes),
+    member = {id(c): cfg for c, cfg in zip(clfs, configs)}
+
+    def fit_group(group, rows):
+        if all(member[id(c)].row_weight is None and member[id(c)].row_group is None for c in group):
+            return partial_fit_rows_group(group, train, rows, classes=classes)
+        return partial_fit_rows_group(group, train, rows, classes=classes, row_weight=[member[id(c)].row_weight for c in group],
+                                      row_group=[member[id(c)].row_group for c in group])
+
+    results = sweep_loop(clfs, batches, fit_group,
                          eval_ref, lambda c: eval_val(c, val), nbr_epochs, early_stopping_patience=early_stopping_patience,
                          on_epoch_end=on_epoch_end, class_scores=class_scores)
     return [(calibrate(clf, ref) if sc is None else calibrate(clf, ref, logit_scaling=sc), info, ref_accs[id(live)])

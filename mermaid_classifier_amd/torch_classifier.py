@@ -73,6 +73,58 @@ def _check_regularizers(dropout, input_dropout, mixup_alpha, regularizer_seed) -
         raise ValueError(f"regularizer_seed must be None or an integer in [0, 2**64), got {regularizer_seed!r}.")
 
 
+def _check_group_dro(group_dro_eta, n_groups) -> None:
+    """The ranges ``mmc_trainer_set_group_dro`` accepts (include/mmc.h): ``n_groups`` None or in [1, 1024], ``group_dro_eta`` in [0, 10]."""
+    if isinstance(group_dro_eta, bool) or not isinstance(group_dro_eta, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(group_dro_eta) <= 10.0:
+        raise ValueError(f"group_dro_eta must lie in [0, 10], got {group_dro_eta!r}.")
+    if n_groups is not None and (isinstance(n_groups, bool) or not isinstance(n_groups, (int, np.integer))
+                                 or not 1 <= int(n_groups) <= _lib.MMC_DRO_MAX_GROUPS):
+        raise ValueError(f"n_groups must be None or an integer in [1, {_lib.MMC_DRO_MAX_GROUPS}], got {n_groups!r}.")
+
+
+def check_row_arrays(clf, n_rows: int, row_weight, row_group):
+    """``row_weight`` / ``row_group`` of a pass of ``clf`` over a set of ``n_rows`` rows, indexed by row of the set -> them as
+    contiguous float32 / int32 (or None).  ``ValueError``, before any device work: not 1D with ``n_rows`` entries, a dtype that is
+    not real (weights) or integer (groups), a weight that is negative or not finite, a group outside ``[0, n_groups)``, ``row_group``
+    on a classifier without ``n_groups``, either array on a classifier with ``mixup_alpha > 0``."""
+    if row_weight is None and row_group is None:
+        return None, None
+    if float(getattr(clf, "mixup_alpha", 0.0)) != 0.0:
+        raise ValueError("mixup_alpha > 0 cannot be combined with row_weight / row_group.")
+    rw = rg = None
+    if row_weight is not None:
+        arr = np.asarray(row_weight)
+        if arr.ndim != 1 or arr.shape[0] != n_rows:
+            raise ValueError(f"row_weight must have one entry per row of the set ({n_rows}), got shape {arr.shape}")
+        if arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
+            raise ValueError(f"row_weight must be a real-valued array, got dtype {arr.dtype}")
+        with np.errstate(over="ignore"):
+            rw = np.ascontiguousarray(arr, dtype=np.float32)
+        if not (np.isfinite(rw).all() and (rw >= 0).all()):
+            raise ValueError("row_weight holds a weight that is negative or not finite (as float32).")
+    if row_group is not None:
+        n_groups = getattr(clf, "n_groups", None)
+        if n_groups is None:
+            raise ValueError("row_group needs a classifier with n_groups set.")
+        arr = np.asarray(row_group)
+        if arr.ndim != 1 or arr.shape[0] != n_rows:
+            raise ValueError(f"row_group must have one entry per row of the set ({n_rows}), got shape {arr.shape}")
+        if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"row_group must be an integer array, got dtype {arr.dtype}")
+        if arr.size and (int(arr.min()) < 0 or int(arr.max()) >= int(n_groups)):
+            raise ValueError(f"row_group holds a group outside [0, {int(n_groups)}).")
+        rg = np.ascontiguousarray(arr, dtype=np.int32)
+    return rw, rg
+
+
+def by_position(arr, visit, n_samples: int):
+    """An array indexed by row of the set -> indexed by position of the pass that visits ``visit`` (None: rows 0..n-1 in order)."""
+    if arr is None:
+        return None
+    return np.ascontiguousarray(arr[:n_samples] if visit is None else arr[visit])
+
+
 class TorchMLPClassifier:
     """See the module docstring; argument meaning as in the reference (torch_classifier.py:93-135).  Three arguments have no
     counterpart there, the loss formulation of ``mmc_trainer_set_loss`` (include/mmc.h): ``label_smoothing`` in [0, 1) with
@@ -95,7 +147,12 @@ class TorchMLPClassifier:
     an exponential average of the weights.  With ``ema_decay > 0`` the classifier evaluates the AVERAGED weights: ``predict_proba``,
     ``parameters()`` and everything built on them (``calibration.evaluate`` / ``calibrate`` / ``export_artifact``,
     ``fit_logit_scaling``, early stopping's validation loss) see them, training goes on with the raw ones, ``raw_parameters()``
-    returns those, and ``use_weights("raw")`` / ``use_weights("averaged")`` switches.  Everything with the defaults is as before."""
+    returns those, and ``use_weights("raw")`` / ``use_weights("averaged")`` switches.  Everything with the defaults is as before.
+
+    Two more, keyword only, are group DRO (include/mmc.h, "group-robust training"): ``n_groups`` (None: off; else in [1, 1024]) and
+    ``group_dro_eta`` in [0, 10], the step of the groups' distribution q (0: a static group-balanced loss).  They act on the
+    ``partial_fit_rows`` passes that are given ``row_group``; ``group_weights_`` holds q after such a pass and is pickled (as log q),
+    so that a resumed classifier continues from it.  ``partial_fit_rows(row_weight=)`` needs neither."""
 
     _estimator_type = "classifier"
 
@@ -107,7 +164,7 @@ class TorchMLPClassifier:
                  logit_prior: dict | None = None, dropout: float = 0.0, input_dropout: float = 0.0, mixup_alpha: float = 0.0,
                  regularizer_seed: int | None = None, lr_schedule: str = "constant", warmup_steps: int = 0,
                  schedule_steps: int | None = None, final_lr_ratio: float = 0.0, max_grad_norm: float | None = None,
-                 ema_decay: float = 0.0):
+                 ema_decay: float = 0.0, group_dro_eta: float = 0.0, n_groups: int | None = None):
         if activation != "relu":
             raise ValueError(f"TorchMLPClassifier only supports activation='relu', got {activation!r}.")
         if solver != "adam":
@@ -115,6 +172,7 @@ class TorchMLPClassifier:
         _check_loss_scalars(label_smoothing, focal_gamma)
         _check_regularizers(dropout, input_dropout, mixup_alpha, regularizer_seed)
         check_optimizer_options(lr_schedule, warmup_steps, schedule_steps, final_lr_ratio, max_grad_norm, ema_decay)
+        _check_group_dro(group_dro_eta, n_groups)
         self.hidden_layer_sizes = tuple(hidden_layer_sizes)
         self.activation = activation
         self.solver = solver
@@ -143,6 +201,8 @@ class TorchMLPClassifier:
         self.final_lr_ratio = final_lr_ratio
         self.max_grad_norm = max_grad_norm
         self.ema_decay = ema_decay
+        self.group_dro_eta = group_dro_eta
+        self.n_groups = n_groups
 
     # ---- host bookkeeping, restated from the reference ------------------------------------------------------------
     def _resolve_batch_size(self, n_samples: int) -> int:
@@ -232,6 +292,9 @@ class TorchMLPClassifier:
                 _lib.check(lib.mmc_trainer_set_dropout(self._h, float(self.input_dropout), float(self.dropout),
                                                        self._regularizer_seed_value()))
             self._apply_optimizer_options()
+            if getattr(self, "n_groups", None) is not None:
+                _check_group_dro(self.group_dro_eta, self.n_groups)
+                _lib.check(lib.mmc_trainer_set_group_dro(self._h, int(self.n_groups), float(self.group_dro_eta)))
         except Exception:
             self._release()
             raise
@@ -280,6 +343,15 @@ class TorchMLPClassifier:
         if steps.value:
             _lib.check(lib.mmc_trainer_grad_norms(self._h, out.ctypes.data, steps.value, C.byref(steps)))
         self.grad_norms_ = out
+
+    def _read_group_weights(self) -> None:
+        """``group_weights_``: q of the groups after the pass just made (``n_groups`` set only); ``_group_logq`` is what is pickled."""
+        if getattr(self, "n_groups", None) is None:
+            return
+        logq = np.empty(int(self.n_groups), np.float64)
+        _lib.check(_lib.lib().mmc_trainer_group_dro_state(self._h, 0, logq.ctypes.data))
+        self._group_logq = logq
+        self.group_weights_ = np.exp(logq)
 
     def _regularizer_seed_value(self) -> int:
         """The seed of the dropout masks and the mixing plans: ``regularizer_seed``, else ``random_state``, else one draw from numpy's
@@ -348,17 +420,29 @@ class TorchMLPClassifier:
         self._end_pass(avg.value)
         return self
 
-    def partial_fit_rows(self, fs, rows=None, classes: Sequence[Any] | None = None) -> "TorchMLPClassifier":
+    def partial_fit_rows(self, fs, rows=None, classes: Sequence[Any] | None = None, *, row_weight=None,
+                         row_group=None) -> "TorchMLPClassifier":
         """``partial_fit(X[rows], y[rows], classes)`` for rows that are resident in the ``FeatureSet`` ``fs`` (``rows=None``: every
         row, in stored order): same first-call initialisation, mini-batch size, shuffle, ``loss_curve_`` / ``n_iter_`` -- and the
         same bits.  The shuffle is composed with ``rows`` on the host; only the indices are uploaded
         (``mmc_trainer_partial_fit_set``).  The set's label indices are the classifier's, so ``fs.classes`` must equal
         ``classes_`` and ``fs.dim`` ``n_features_in_`` (``ValueError``); on a first call without ``classes`` the set's class list
-        is taken (``partial_fit`` would take the labels present in the rows)."""
+        is taken (``partial_fit`` would take the labels present in the rows).
+
+        ``row_weight`` (real, >= 0) and ``row_group`` (integers in ``[0, n_groups)``; needs ``n_groups``) are indexed by row of the
+        SET, one entry per stored row, and gathered by the visiting order here (``mmc_trainer_partial_fit_set_weighted``): a weight per
+        row, and group DRO over the rows' groups (include/mmc.h, "group-robust training").  Both None is the pass above, bit for bit."""
+        rw, rg = check_row_arrays(self, len(fs), row_weight, row_group)
         visit, n_samples, batch_size = self._begin_rows_pass(fs, rows, classes)
         visit, partner, lam = self._mix_plan(visit, n_samples, batch_size)
         avg = C.c_double(0.0)
-        if partner is None:
+        if rw is not None or rg is not None:
+            rw, rg = by_position(rw, visit, n_samples), by_position(rg, visit, n_samples)
+            _lib.check(_lib.lib().mmc_trainer_partial_fit_set_weighted(
+                self._h, fs._handle(), None if visit is None else visit.ctypes.data, None if rw is None else rw.ctypes.data,
+                None if rg is None else rg.ctypes.data, n_samples, int(batch_size), C.byref(avg),
+                _current_stream_ptr(_device_index(self.device))))
+        elif partner is None:
             _lib.check(_lib.lib().mmc_trainer_partial_fit_set(self._h, fs._handle(), None if visit is None else visit.ctypes.data, n_samples,
                                                               int(batch_size), C.byref(avg), _current_stream_ptr(_device_index(self.device))))
         else:
@@ -412,6 +496,7 @@ class TorchMLPClassifier:
         self.loss_curve_.append(float(avg))
         self.n_iter_ += 1
         self._read_grad_norms()
+        self._read_group_weights()
 
     def fit(self, X, y) -> "TorchMLPClassifier":
         y_arr = np.asarray(y)
@@ -538,7 +623,8 @@ class TorchMLPClassifier:
                 "focal_gamma": self.focal_gamma, "logit_prior": self.logit_prior, "dropout": self.dropout,
                 "input_dropout": self.input_dropout, "mixup_alpha": self.mixup_alpha, "regularizer_seed": self.regularizer_seed,
                 "lr_schedule": self.lr_schedule, "warmup_steps": self.warmup_steps, "schedule_steps": self.schedule_steps,
-                "final_lr_ratio": self.final_lr_ratio, "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay}
+                "final_lr_ratio": self.final_lr_ratio, "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay,
+                "group_dro_eta": self.group_dro_eta, "n_groups": self.n_groups}
 
     def set_params(self, **params: Any) -> "TorchMLPClassifier":
         for key, value in params.items():
@@ -565,7 +651,9 @@ class TorchMLPClassifier:
                              ("dropout", 0.0), ("input_dropout", 0.0), ("mixup_alpha", 0.0), ("regularizer_seed", None),
                              # ... and one made before the optimiser options existed with the constant rate, unclipped, unaveraged
                              ("lr_schedule", "constant"), ("warmup_steps", 0), ("schedule_steps", None), ("final_lr_ratio", 0.0),
-                             ("max_grad_norm", None), ("ema_decay", 0.0)):
+                             ("max_grad_norm", None), ("ema_decay", 0.0),
+                             # ... and one made before group DRO existed without it
+                             ("group_dro_eta", 0.0), ("n_groups", None)):
             self.__dict__.setdefault(key, default)
         self._h = None
         if params is not None:
@@ -578,6 +666,10 @@ class TorchMLPClassifier:
                 if self._averages() and opt.get("ema") is not None:   # without one the shadow stays the parameters just loaded
                     ws, bs = opt["ema"]
                     _lib.check(_lib.lib().mmc_trainer_ema_state(self._h, 1, _ptr_array(ws), _ptr_array(bs)))
+            logq = self.__dict__.get("_group_logq")
+            if self.n_groups is not None and logq is not None and len(logq) == int(self.n_groups):   # q continues where it was
+                logq = np.ascontiguousarray(logq, dtype=np.float64)
+                _lib.check(_lib.lib().mmc_trainer_group_dro_state(self._h, 1, logq.ctypes.data))
 
     def _release(self) -> None:
         if self._fitted():

@@ -156,8 +156,8 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
                      class_weight: Optional[dict] = None, early_stopping_patience: Optional[int] = None,
                      on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None,
                      batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None,
-                     clf: Optional[TorchMLPClassifier] = None, class_scores: bool = False, transform=None, logit_scaling=None
-                     ) -> Tuple[CalibratedMLP, Dict[str, Any], List[float]]:
+                     clf: Optional[TorchMLPClassifier] = None, class_scores: bool = False, transform=None, logit_scaling=None,
+                     row_weight=None, row_group=None) -> Tuple[CalibratedMLP, Dict[str, Any], List[float]]:
     """Train, early-stop and calibrate the MLP head on three resident splits.  -> ``(calibrated, info, ref_accs)``:
     the ``CalibratedMLP`` of the returned classifier on ``ref``, ``epoch_loop``'s ``info``, and the ref accuracy after every
     epoch run (the reference's ``TrainClassifierReturnMsg.ref_accs``).
@@ -187,7 +187,10 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
 
     A ``clf`` with a decaying ``lr_schedule`` and ``schedule_steps=None`` gets ``nbr_epochs`` x its steps per epoch (counted on
     ``batches(0)``); one with ``ema_decay > 0`` is evaluated, early-stopped, scaled and calibrated on its averaged weights.  With ``transform=`` the scaling goes into the last layer and the transform into the
-    first -- on a head with no hidden layer the scaling first, then the transform.  ``None`` changes no call."""
+    first -- on a head with no hidden layer the scaling first, then the transform.  ``None`` changes no call.
+
+    ``row_weight`` / ``row_group``: arrays indexed by row of ``train``, handed to every epoch's ``partial_fit_rows`` (a weight per row;
+    group DRO over the rows' groups, on a ``clf`` with ``n_groups``).  ``None`` changes no call."""
     _check_splits(train, ref, val, batch_size)
     if logit_scaling is not None:
         _ls.check_argument(logit_scaling)
@@ -199,7 +202,8 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
                 sets.append(ft.apply(fs))
             cal, info, accs = train_classifier(*sets, nbr_epochs, batch_size=batch_size, class_weight=class_weight,
                                                early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end,
-                                               batches=batches, clf=clf, class_scores=class_scores, logit_scaling=logit_scaling)
+                                               batches=batches, clf=clf, class_scores=class_scores, logit_scaling=logit_scaling,
+                                               row_weight=row_weight, row_group=row_group)
         finally:
             for fs in sets:
                 fs.close()
@@ -217,7 +221,10 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
 
     def train_epoch(c, epoch):
         for rows in batches(epoch):
-            c.partial_fit_rows(train, rows, classes=classes)
+            if row_weight is None and row_group is None:
+                c.partial_fit_rows(train, rows, classes=classes)
+            else:
+                c.partial_fit_rows(train, rows, classes=classes, row_weight=row_weight, row_group=row_group)
 
     def eval_ref(c):
         ref_accs.append(evaluate(c, ref)[0])
