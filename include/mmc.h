@@ -563,6 +563,48 @@ int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* logits, cons
                                        float* dlogits, float* row_loss, double* log_q_out, double* group_loss /* n_groups, NaN where none */,
                                        void* hip_stream);
 
+/* ---- taxonomy-aware loss: level-marginal terms and soft labels in the loss stage, per trainer ---------------------------------------
+ * Extends: the loss of TorchMLPClassifier.partial_fit (torch_classifier.py:226-303), which treats the K classes as unrelated symbols,
+ *   by the two remedies of Bertinetto et al. 2020 ("Making better mistakes"): one loss term per level of the label hierarchy, and
+ *   soft labels spread over taxonomic neighbours.  docs/research/hidden-layer-experiments.md section 5 names the loss formulation as
+ *   the next lever; no counterpart in the reference and no measured gain on reef data.  Both sit in the loss stage alone: forward,
+ *   backward GEMMs, L2, clipping, EMA, the schedule, dropout, row weights and group DRO are untouched and compose with them;
+ *   evaluation, early stopping, calibration and export never see them.  With nothing set a pass launches the kernels, and gives the
+ *   bits, of a trainer this was never called on; in a group the members without a hierarchy keep their kernels.
+ * Notation.  u = z + prior (one fp32 add; u = z without a prior), p = softmax(u), t the row's true class, w_t its class weight (1
+ *   without class weights), s_i the row's normaliser exactly as the other loss kernels form it: inv_wsum, or rw[row] * inv_wsum (one
+ *   rounded product) on the row-weighted route.
+ * Level terms.  L = n_levels in [1, MMC_HIER_MAX_LEVELS]; level_of_class[l][c] is the int32 node id g_l(c) of class c at level l.  Two
+ *   classes share a node of level l iff their ids are equal and non-negative; a negative id is "no node at this level".  Each level has
+ *   a weight lam_l >= 0, finite, given as a double and used as (float).  With P_l = sum_{c : g_l(c) = g_l(t)} p_c the row adds
+ *     h_i       = w_t sum_l lam_l (-log P_l)
+ *     dh_i/dz_c = w_t sum_l lam_l (p_c - [g_l(c) = g_l(t)] p_c / P_l)
+ *   over the levels at which t has a node; the others add nothing.
+ * Soft labels (optional).  soft_targets is a K x K fp32 matrix T, row t the target distribution of true class t: every entry >= 0 and
+ *   finite, every row summing to 1 within 1e-5 (summed in double).  With T the base term of the row is
+ *     b_i       = w_t (-sum_c T[t,c] logp_c)
+ *     db_i/dz_c = w_t (p_c sum_c' T[t,c'] - T[t,c])
+ *   with the row sum of T as stored (a lane-strided fp32 sum), not an assumed 1.  Without T the base term is mmc_trainer_set_loss's
+ *   general form, which at its defaults is the plain weighted cross-entropy.
+ * The row.  l_i = (base + h_i) s_i; dlogits is its gradient, row_loss[row] = l_i.  Group DRO's R_i is this whole row loss.
+ * Finiteness.  Every output is finite on any finite row, a true node whose every member underflows against the row maximum and a node
+ *   that holds all the probability included: each level takes its own maximum m_l over the node's members, forms
+ *   -log P_l = (mx + lse) - (m_l + log sum exp(u_c - m_l)) and p_c / P_l = exp((u_c - m_l) - log sum ...), the softmax inside the
+ *   node; nothing divides by a sum that can underflow.
+ * mmc_trainer_set_hierarchy copies the ids and T to the device once.  n_levels = 0 with soft_targets NULL restores the default.
+ *   MMC_ERR_ARG, the trainer left as it was: n_levels outside [0, MMC_HIER_MAX_LEVELS]; a NULL array that n_levels needs; a weight
+ *   that is negative or not finite (as a float too); an entry of T that is negative or not finite; a row of T off 1 by more than
+ *   1e-5; soft_targets on a trainer with label_smoothing != 0 or focal_gamma != 0 -- and mmc_trainer_set_loss with either on a trainer
+ *   that has soft_targets: whichever of the two setters comes second refuses.  Smoothing, focal modulation and the prior compose
+ *   with level terms: the base is the general form and the level terms are added.
+ * A mixed (mixup) pass takes no hierarchy: mmc_trainer_loss_gradient_mixed on such a trainer, and mmc_trainer_partial_fit_set_mixed /
+ *   mmc_trainer_group_partial_fit_set_mixed for a member that has one and is given a partner array, return MMC_ERR_ARG before any
+ *   member changes.  mmc_trainer_loss_gradient and mmc_trainer_loss_gradient_weighted run the hierarchy's kernel on caller logits.
+ *   A member of a group matches its solo pass bit for bit, and the results do not depend on MMC_TRAIN_CHUNK_ROWS. */
+#define MMC_HIER_MAX_LEVELS 4
+int mmc_trainer_set_hierarchy(mmc_trainer* t, int n_levels, const int32_t* level_of_class /* [n_levels][K], or NULL when n_levels == 0 */,
+                              const double* level_weight /* [n_levels] */, const float* soft_targets /* [K][K], or NULL */);
+
 /* ---- validation of a calibrated head --------------------------------------------------------------------------------
  * Replaces: what MermaidTrainer.__call__ computes after the calibration (mermaid_classifier/pyspacer/trainer.py:267-293:
  *   evaluate_classifier on val, ValResults, acc, the previous models' accuracies) and the per-row reductions the metrics make of the

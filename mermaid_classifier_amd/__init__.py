@@ -15,7 +15,7 @@ from .sweep import SweepConfig, partial_fit_rows_group, rank_sweep, sweep_loop, 
 from .sampling import class_counts, effective_number_weights, group_balance_weights, logit_adjustment, mixup_plan, row_batches, subsample_rows, subsample_targets  # noqa: F401
 from .validation import Validation, previous_accuracies, validate  # noqa: F401
 from .metrics import CoverStats, GroupedValidation, Reliability, SourceStats, category_bins, grouped_validate  # noqa: F401
-from .taxonomy import TaxonomicScores  # noqa: F401
+from .taxonomy import TaxonomicScores, hierarchy_levels, soft_labels  # noqa: F401
 from .ranking import RankedValidation, ranking_validate, similarity_levels  # noqa: F401
 from .cover import CoverEstimate, estimate_cover, prior_from_labels  # noqa: F401
 from .feature_transform import FeatureTransform  # noqa: F401
@@ -35,7 +35,7 @@ __all__ = [
     "Validation", "validate", "previous_accuracies",
     "grouped_validate", "GroupedValidation", "CoverStats", "SourceStats", "Reliability",
     "ranking_validate", "RankedValidation", "similarity_levels",
-    "category_bins", "TaxonomicScores",
+    "category_bins", "TaxonomicScores", "hierarchy_levels", "soft_labels",
     "estimate_cover", "CoverEstimate", "prior_from_labels",
     "FeatureTransform",
     "LogitScaling", "fit_logit_scaling",

@@ -58,12 +58,14 @@ SYMBOLS = [
     "mmc_trainer_set_ema", "mmc_trainer_ema_state", "mmc_trainer_eval_weights", "mmc_trainer_optimizer_options",
     "mmc_trainer_set_group_dro", "mmc_trainer_group_dro_state", "mmc_trainer_partial_fit_set_weighted",
     "mmc_trainer_group_partial_fit_set_weighted", "mmc_trainer_loss_gradient_weighted",
+    "mmc_trainer_set_hierarchy",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 # include/mmc.h, "optimiser options"
 MMC_LR_CONSTANT, MMC_LR_LINEAR, MMC_LR_COSINE = 0, 1, 2
 MMC_WEIGHTS_RAW, MMC_WEIGHTS_AVERAGED = 0, 1
 MMC_DRO_MAX_GROUPS = 1024   # include/mmc.h, "group-robust training"
+MMC_HIER_MAX_LEVELS = 4   # include/mmc.h, "taxonomy-aware loss"
 
 
 class LibraryMissingError(ImportError):
@@ -290,6 +292,8 @@ def _load() -> C.CDLL:
                                                                C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_double), vp]
     lib.mmc_trainer_loss_gradient_weighted.restype = i32
     lib.mmc_trainer_loss_gradient_weighted.argtypes = [vp, vp, vp, vp, vp, vp, f64, i32, i64, vp, vp, vp, vp, vp]
+    lib.mmc_trainer_set_hierarchy.restype = i32
+    lib.mmc_trainer_set_hierarchy.argtypes = [vp, i32, vp, vp, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

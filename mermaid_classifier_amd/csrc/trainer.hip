@@ -28,6 +28,9 @@
 //   weights   the row's normaliser is s_i = r_i / sum of the masses r_i w(y_i), one rounded product ce_grad_weighted_kernel, ce_grad_rows<., true>
 //   group DRO q over the rows' groups moves by exp(eta L_a) per step on the device                 dro_update_kernel
 //             dZ(L) and the row losses take c_i = q_a / V_a                                        row_scale_kernel
+// Per trainer, off by default (include/mmc.h, "taxonomy-aware loss"; a member without a hierarchy runs the loss kernels above as ever):
+//   levels    l_i += w_t sum_l lam_l (-log P_l), P_l the softmax mass of t's node at level l    ce_grad_hier_kernel, ce_grad_rows_hier
+//   soft      the base term becomes w_t (-sum_c T[t,c] logp_c); row weights ride the same kernel (mmc_trainer_set_hierarchy)
 //
 // Every step is the step of a group of trainers (trainer_group_step): each kind of launch once, one member per blockIdx.z, the
 // member's operands in a by-value descriptor array.  A trainer on its own -- the host-fed pass, mmc_trainer_partial_fit_set, the
@@ -471,6 +474,163 @@ __global__ __launch_bounds__(256) void ce_grad_weighted_kernel(const CeRowGroup 
         ce_grad_rows<true, true>(blockIdx.x, d.c.logits, d.c.y, d.c.M, d.c.K, d.c.cw, d.c.inv_wsum, d.c.dlogits, d.c.row_loss, d.c.loss, d.rw);
     else
         ce_grad_rows<false, true>(blockIdx.x, d.c.logits, d.c.y, d.c.M, d.c.K, d.c.cw, d.c.inv_wsum, d.c.dlogits, d.c.row_loss, d.c.loss, d.rw);
+}
+
+// ---- taxonomy-aware loss (include/mmc.h): the loss stage of a member with a hierarchy (mmc_trainer_set_hierarchy), with or without
+// row weights.  A body of its own: the members without a hierarchy keep ce_grad_kernel / ce_grad_weighted_kernel and their code.
+struct HierLoss {
+    const int32_t* level;   // [n_levels][K] node ids, negative = no node; null when n_levels == 0
+    const float* T;         // [K][K] soft targets, or null
+    int n_levels;
+    float lam[MMC_HIER_MAX_LEVELS];
+};
+
+// One wave per row, classes lane-strided, every row reduction a lane-strided sum (or max) and the xor butterfly.
+//   base   with T:    b = w_t (-sum_c T[t,c] logp_c),  db/dz_c = w_t (p_c sum_c' T[t,c'] - T[t,c]); row t of T is read coalesced
+//          without T: the general form, operation for operation as ce_grad_rows<true> forms it
+//   level  for every level l at which t has a node: m_l = max of u over the node, lS_l = logf(sum over the node of expf(u_c - m_l)),
+//          the four levels' maxima in one loop and one round of butterflies, their sums in another (independent chains in flight);
+//          h += lam_l ((mx + lse) - (m_l + lS_l));  the gradient loop adds lam_l (p_c - [c in node] expf((u_c - m_l) - lS_l))
+//   row    l_i = (base + w_t h) s_i,  dl_i/dz_c = s_i (db_c + w_t hd_c),  s_i = rw ? rw[row] * inv_wsum : inv_wsum
+// Finite on any finite row: the node holds t, so m_l is finite and its sum is at least 1; nothing divides.
+__device__ __forceinline__ void ce_grad_rows_hier(int block, const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
+                                                  const float* __restrict__ cw, float inv_wsum, float* __restrict__ dlogits,
+                                                  float* __restrict__ row_loss, const CeLoss& ls, const HierLoss& hl,
+                                                  const float* __restrict__ rw)
+{
+#pragma clang fp contract(off)   // nothing here is fused
+    const int lane = threadIdx.x & 63;
+    const int row = block * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    if (rw) inv_wsum = rw[row] * inv_wsum;
+    const float* z = logits + (size_t)row * K;
+    const float* pr = ls.prior;
+    const int yi = y[row];
+    float mx = -INFINITY;
+    for (int c = lane; c < K; c += 64) mx = fmaxf(mx, pr ? z[c] + pr[c] : z[c]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    float s = 0.f, so = 0.f;   // sum_c e_c; sum_{c != t} e_c
+    for (int c = lane; c < K; c += 64) {
+        const float e = expf((pr ? z[c] + pr[c] : z[c]) - mx);
+        s += e;
+        so += c == yi ? 0.f : e;
+    }
+    s = wave_sum(s);
+    so = wave_sum(so);
+    const float w = cw ? cw[yi] : 1.0f;
+    const float lse = logf(s);
+    const float* Tt = hl.T ? hl.T + (size_t)yi * K : nullptr;
+    const bool smooth = ls.eps_k != 0.f;
+    float st = 0.f, sl = 0.f;   // with T: sum_c T[t,c]; sum_c T[t,c] logp_c.  Without, sl: sum_c w_c logp_c of the smoothing term
+    float a = 0.f, af = 0.f, lb;
+    if (Tt) {
+        for (int c = lane; c < K; c += 64) {
+            const float lp = (pr ? z[c] + pr[c] : z[c]) - mx - lse;
+            st += Tt[c];
+            sl += Tt[c] * lp;
+        }
+        st = wave_sum(st);
+        sl = wave_sum(sl);
+        lb = -(w * sl);
+    } else {
+        if (smooth) {
+            for (int c = lane; c < K; c += 64) {
+                const float lp = (pr ? z[c] + pr[c] : z[c]) - mx - lse;
+                sl += cw ? cw[c] * lp : lp;
+            }
+            sl = wave_sum(sl);
+        }
+        const float ut = pr ? z[yi] + pr[yi] : z[yi];
+        const float nll = lse - (ut - mx);
+        float m = 1.0f, f = 1.0f;
+        if (ls.gamma != 0.f) {
+            const float q = so / s;
+            const float pt = expf(ut - mx - lse);
+            const float pw = powf(q, ls.gamma - 1.0f);
+            m = pw * q;
+            f = m + ls.gamma * pt * pw * nll;
+        }
+        a = ls.om_eps * w;
+        af = a * f;
+        lb = a * m * nll;
+        if (smooth) lb = lb - ls.eps_k * sl;
+    }
+    // the levels: the true node's id, its maximum and the log of its sum against that maximum; h = sum_l lam_l (-log P_l)
+    const float top = mx + lse;
+    int gt[MMC_HIER_MAX_LEVELS];
+    float ml[MMC_HIER_MAX_LEVELS], lS[MMC_HIER_MAX_LEVELS];
+    float h = 0.f;
+    // the levels' reductions side by side: four independent butterflies in flight, each level's values formed as if it were alone.
+    // A level without a node for t (gt < 0; past n_levels too) loads nothing and carries -inf / 0 through the butterflies, unread.
+#pragma unroll
+    for (int l = 0; l < MMC_HIER_MAX_LEVELS; ++l) {
+        gt[l] = l < hl.n_levels ? hl.level[(size_t)l * K + yi] : -1;
+        ml[l] = -INFINITY;
+        lS[l] = 0.f;
+    }
+    for (int c = lane; c < K; c += 64) {
+        const float u = pr ? z[c] + pr[c] : z[c];
+#pragma unroll
+        for (int l = 0; l < MMC_HIER_MAX_LEVELS; ++l)
+            if (gt[l] >= 0 && hl.level[(size_t)l * K + c] == gt[l]) ml[l] = fmaxf(ml[l], u);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+        for (int l = 0; l < MMC_HIER_MAX_LEVELS; ++l) ml[l] = fmaxf(ml[l], __shfl_xor(ml[l], o));
+    for (int c = lane; c < K; c += 64) {
+        const float u = pr ? z[c] + pr[c] : z[c];
+#pragma unroll
+        for (int l = 0; l < MMC_HIER_MAX_LEVELS; ++l)
+            if (gt[l] >= 0) lS[l] += hl.level[(size_t)l * K + c] == gt[l] ? expf(u - ml[l]) : 0.f;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+        for (int l = 0; l < MMC_HIER_MAX_LEVELS; ++l) lS[l] += __shfl_xor(lS[l], o);
+#pragma unroll
+    for (int l = 0; l < MMC_HIER_MAX_LEVELS; ++l)
+        if (gt[l] >= 0) {
+            lS[l] = logf(lS[l]);
+            h = h + hl.lam[l] * (top - (ml[l] + lS[l]));
+        }
+    for (int c = lane; c < K; c += 64) {
+        const float u = pr ? z[c] + pr[c] : z[c];
+        const float p = expf(u - mx - lse);
+        float d;
+        if (Tt) {
+            d = w * (p * st - Tt[c]);
+        } else {
+            d = af * (p - (c == yi ? 1.0f : 0.0f));
+            if (smooth) d = d + ls.eps_k * (p * ls.w_total - (cw ? cw[c] : 1.0f));
+        }
+        float hd = 0.f;
+#pragma unroll
+        for (int l = 0; l < MMC_HIER_MAX_LEVELS; ++l)
+            if (gt[l] >= 0) {
+                const float pin = hl.level[(size_t)l * K + c] == gt[l] ? expf((u - ml[l]) - lS[l]) : 0.f;
+                hd = hd + hl.lam[l] * (p - pin);
+            }
+        d = d + w * hd;
+        dlogits[(size_t)row * K + c] = inv_wsum * d;
+    }
+    if (lane == 0) row_loss[row] = (lb + w * h) * inv_wsum;
+}
+
+struct CeHierDesc {
+    CeDesc c;          // inv_wsum as in CeDesc, or as in CeRowDesc for a member with row weights or groups
+    const float* rw;   // the weights of the mini-batch's positions, or null
+    HierLoss h;
+};
+struct CeHierGroup { CeHierDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(CeHierGroup) <= 4096, "kernel-argument limit");
+
+__global__ __launch_bounds__(256) void ce_grad_hier_kernel(const CeHierGroup g)
+{
+    const CeHierDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 4 >= d.c.M) return;
+    ce_grad_rows_hier(blockIdx.x, d.c.logits, d.c.y, d.c.M, d.c.K, d.c.cw, d.c.inv_wsum, d.c.dlogits, d.c.row_loss, d.c.loss, d.h, d.rw);
 }
 
 // The group DRO update of a member's step, one workgroup of 1024 threads: from R_i = row_loss[i] (normaliser r_i) and the groups
@@ -942,6 +1102,12 @@ struct mmc_trainer {
     DevBuf<int32_t> row_g;                              // and of its groups
     DevBuf<double> group_mass;                          // [steps][n_groups] V_a of every mini-batch of the pass
     DevBuf<float> row_scale;                            // [mb] c_i of the step
+    // taxonomy-aware loss (mmc_trainer_set_hierarchy): nothing set = today's launches
+    int hier_levels = 0;
+    float hier_lam[MMC_HIER_MAX_LEVELS] = {0.f, 0.f, 0.f, 0.f};
+    DevBuf<int32_t> hier_ids;                           // [hier_levels][K] node ids or empty
+    DevBuf<float> hier_T;                               // [K][K] soft targets or empty
+    bool hier = false;                                  // hier_levels > 0 or soft targets: the member takes ce_grad_hier_kernel
 };
 
 #define T_K(expr)                                                                   \
@@ -1030,6 +1196,9 @@ extern "C" int mmc_trainer_set_loss(mmc_trainer* t, double label_smoothing, doub
     if (logit_prior)
         for (int c = 0; c < t->K; ++c)
             if (!std::isfinite(logit_prior[c])) return mmc_fail(MMC_ERR_ARG, "logit_prior[%d] = %g is not finite", c, logit_prior[c]);
+    if (t->hier_T.p && (label_smoothing != 0.0 || focal_gamma != 0.0))
+        return mmc_fail(MMC_ERR_ARG, "label_smoothing = %g / focal_gamma = %g on a trainer with soft targets (mmc_trainer_set_hierarchy)",
+                        label_smoothing, focal_gamma);
     HIP_TRY(hipSetDevice(t->device));
     // passes synchronise their stream before they return, so nothing in flight reads the prior that is replaced here
     DevBuf<float> prior;
@@ -1043,6 +1212,64 @@ extern "C" int mmc_trainer_set_loss(mmc_trainer* t, double label_smoothing, doub
     t->focal_gamma = focal_gamma;
     t->general = label_smoothing != 0.0 || focal_gamma != 0.0 || t->prior.p != nullptr;
     return MMC_OK;
+}
+
+// ---- taxonomy-aware loss (include/mmc.h) ------------------------------------------------------------------------------------
+extern "C" int mmc_trainer_set_hierarchy(mmc_trainer* t, int n_levels, const int32_t* level_of_class, const double* level_weight,
+                                         const float* soft_targets)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (n_levels < 0 || n_levels > MMC_HIER_MAX_LEVELS) return mmc_fail(MMC_ERR_ARG, "n_levels = %d outside [0, %d]", n_levels, MMC_HIER_MAX_LEVELS);
+    if (n_levels > 0 && (!level_of_class || !level_weight)) return mmc_fail(MMC_ERR_ARG, "n_levels = %d needs level_of_class and level_weight", n_levels);
+    const int K = t->K;
+    float lam[MMC_HIER_MAX_LEVELS] = {0.f, 0.f, 0.f, 0.f};
+    for (int l = 0; l < n_levels; ++l) {
+        if (!(level_weight[l] >= 0.0 && std::isfinite(level_weight[l]) && std::isfinite((float)level_weight[l])))
+            return mmc_fail(MMC_ERR_ARG, "level_weight[%d] = %g is negative or not finite", l, level_weight[l]);
+        lam[l] = (float)level_weight[l];
+    }
+    if (soft_targets) {
+        for (int r = 0; r < K; ++r) {
+            double sum = 0.0;
+            for (int c = 0; c < K; ++c) {
+                const float v = soft_targets[(size_t)r * K + c];
+                if (!(v >= 0.f && std::isfinite(v)))
+                    return mmc_fail(MMC_ERR_ARG, "soft_targets[%d][%d] = %g is negative or not finite", r, c, (double)v);
+                sum += (double)v;
+            }
+            if (!(std::fabs(sum - 1.0) <= 1e-5)) return mmc_fail(MMC_ERR_ARG, "row %d of soft_targets sums to %.9g, not 1", r, sum);
+        }
+        if (t->label_smoothing != 0.0 || t->focal_gamma != 0.0)
+            return mmc_fail(MMC_ERR_ARG, "soft_targets on a trainer with label_smoothing = %g / focal_gamma = %g (mmc_trainer_set_loss)",
+                            t->label_smoothing, t->focal_gamma);
+    }
+    HIP_TRY(hipSetDevice(t->device));
+    // passes synchronise their stream before they return, so nothing in flight reads what is replaced here
+    DevBuf<int32_t> ids;
+    DevBuf<float> T;
+    if (n_levels) {
+        if (!ids.alloc((int64_t)n_levels * K)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the level ids (%d levels, %d classes)", n_levels, K);
+        hipError_t e = hipMemcpy(ids, level_of_class, (size_t)n_levels * K * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "uploading the level ids: %s", hipGetErrorString(e));
+    }
+    if (soft_targets) {
+        if (!T.alloc((int64_t)K * K)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the soft targets (%d classes)", K);
+        hipError_t e = hipMemcpy(T, soft_targets, (size_t)K * K * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "uploading the soft targets: %s", hipGetErrorString(e));
+    }
+    t->hier_ids = std::move(ids);
+    t->hier_T = std::move(T);
+    t->hier_levels = n_levels;
+    std::copy(lam, lam + MMC_HIER_MAX_LEVELS, t->hier_lam);
+    t->hier = n_levels > 0 || t->hier_T.p != nullptr;
+    return MMC_OK;
+}
+
+static HierLoss trainer_hier_loss(const mmc_trainer* t)
+{
+    HierLoss h{t->hier_ids, t->hier_T, t->hier_levels, {0.f, 0.f, 0.f, 0.f}};
+    std::copy(t->hier_lam, t->hier_lam + MMC_HIER_MAX_LEVELS, h.lam);
+    return h;
 }
 
 extern "C" int mmc_trainer_set_dropout(mmc_trainer* t, double p_input, double p_hidden, uint64_t seed)
@@ -1383,12 +1610,20 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
         CeRowGroup gr;
         DroGroup gd;
         RowScaleGroup gs;
-        int k = 0, km = 0, kr = 0, kd = 0, mmax = 0, mmax_mixed = 0, mmax_rows = 0, mmax_dro = 0;
+        CeHierGroup gh;
+        int k = 0, km = 0, kr = 0, kd = 0, kh = 0, mmax = 0, mmax_mixed = 0, mmax_rows = 0, mmax_dro = 0, mmax_hier = 0;
         for (int i = 0; i < cnt; ++i) {
             const mmc_trainer* t = act[i].t;
+            if (t->hier) {   // a hierarchy: one kernel with or without row weights (a mixed pass was refused before the first launch)
+                gh.d[kh++] = CeHierDesc{ce_desc(t, t->H[t->L], t->y + act[i].off, act[i].cur, act[i].inv_wsum),
+                                        act[i].weighted ? act[i].rw : nullptr, trainer_hier_loss(t)};
+                mmax_hier = std::max(mmax_hier, act[i].cur);
+            }
             if (act[i].weighted) {
-                gr.d[kr++] = CeRowDesc{ce_desc(t, t->H[t->L], t->y + act[i].off, act[i].cur, act[i].inv_wsum), act[i].rw};
-                mmax_rows = std::max(mmax_rows, act[i].cur);
+                if (!t->hier) {
+                    gr.d[kr++] = CeRowDesc{ce_desc(t, t->H[t->L], t->y + act[i].off, act[i].cur, act[i].inv_wsum), act[i].rw};
+                    mmax_rows = std::max(mmax_rows, act[i].cur);
+                }
                 if (act[i].rg) {
                     gd.d[kd] = DroDesc{t->row_loss, act[i].rg, act[i].V, t->logq, t->row_scale, nullptr, act[i].cur, t->n_groups, t->dro_eta};
                     gs.d[kd] = RowScaleDesc{t->dZ[t->L], t->row_loss, t->row_scale, act[i].cur, t->K};
@@ -1399,7 +1634,7 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
                 gm.d[km++] = CeMixDesc{t->H[t->L], t->y + act[i].off, t->y2 + act[i].off, t->cw, t->dZ[t->L], t->row_loss, act[i].cur, t->K,
                                        act[i].inv_wsum, act[i].lam, 1.0f - act[i].lam, trainer_ce_loss(t)};
                 mmax_mixed = std::max(mmax_mixed, act[i].cur);
-            } else {
+            } else if (!t->hier) {
                 g.d[k++] = ce_desc(t, t->H[t->L], t->y + act[i].off, act[i].cur, act[i].inv_wsum);
                 mmax = std::max(mmax, act[i].cur);
             }
@@ -1407,6 +1642,7 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
         if (k) hipLaunchKernelGGL(ce_grad_kernel, dim3((mmax + 3) / 4, 1, k), dim3(256), 0, st, g);
         if (km) hipLaunchKernelGGL(ce_grad_mixed_kernel, dim3((mmax_mixed + 3) / 4, 1, km), dim3(256), 0, st, gm);
         if (kr) hipLaunchKernelGGL(ce_grad_weighted_kernel, dim3((mmax_rows + 3) / 4, 1, kr), dim3(256), 0, st, gr);
+        if (kh) hipLaunchKernelGGL(ce_grad_hier_kernel, dim3((mmax_hier + 3) / 4, 1, kh), dim3(256), 0, st, gh);
         if (kd) {   // the groups' members: q moves on the device, then every row takes its group's share
             hipLaunchKernelGGL(dro_update_kernel, dim3(1, 1, kd), dim3(1024), 0, st, gd);
             hipLaunchKernelGGL(row_scale_kernel, dim3((mmax_dro + 3) / 4, 1, kd), dim3(256), 0, st, gs);
@@ -1831,6 +2067,8 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
         if ((r = check_mix_plan(who[m], fs, partner ? partner[m] : nullptr, lam ? lam[m] : nullptr, n[m], batch_size[m]))) return r;
         const bool weighted = (row_weight && row_weight[m]) || (row_group && row_group[m]);
         if (weighted && partner && partner[m]) return mmc_fail(MMC_ERR_ARG, "%sa mixed pass takes no row weights or groups", who[m]);
+        if (partner && partner[m] && trainers[m]->hier)
+            return mmc_fail(MMC_ERR_ARG, "%sa mixed pass takes no hierarchy (mmc_trainer_set_hierarchy)", who[m]);
         if (row_group && row_group[m] && !trainers[m]->n_groups)
             return mmc_fail(MMC_ERR_ARG, "%srow_group needs mmc_trainer_set_group_dro(n_groups > 0) on the trainer", who[m]);
     }
@@ -2099,9 +2337,15 @@ extern "C" int mmc_trainer_loss_gradient(mmc_trainer* t, const float* logits, co
     const size_t cells = (size_t)mb * t->K;
     HIP_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(yd, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
-    CeGroup g;
-    g.d[0] = ce_desc(t, t->H[L], static_cast<const int32_t*>(yd), mb, (float)(1.0 / wsum));
-    hipLaunchKernelGGL(ce_grad_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
+    if (t->hier) {   // the kernel a step of this trainer runs
+        CeHierGroup g;
+        g.d[0] = CeHierDesc{ce_desc(t, t->H[L], static_cast<const int32_t*>(yd), mb, (float)(1.0 / wsum)), nullptr, trainer_hier_loss(t)};
+        hipLaunchKernelGGL(ce_grad_hier_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
+    } else {
+        CeGroup g;
+        g.d[0] = ce_desc(t, t->H[L], static_cast<const int32_t*>(yd), mb, (float)(1.0 / wsum));
+        hipLaunchKernelGGL(ce_grad_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
@@ -2117,6 +2361,7 @@ extern "C" int mmc_trainer_loss_gradient_mixed(mmc_trainer* t, const float* logi
     if (!logits || !y || !y2 || !dlogits || !row_loss) return mmc_fail(MMC_ERR_ARG, "logits / y / y2 / dlogits / row_loss is NULL");
     if (n < 1 || n > kTrainerForwardRows) return mmc_fail(MMC_ERR_ARG, "n = %lld outside [1, %d]", (long long)n, kTrainerForwardRows);
     if (!(lam >= 0.f && lam <= 1.f)) return mmc_fail(MMC_ERR_ARG, "lam = %g outside [0, 1]", (double)lam);
+    if (t->hier) return mmc_fail(MMC_ERR_ARG, "a mixed loss stage takes no hierarchy (mmc_trainer_set_hierarchy)");
     const float oml = 1.0f - lam;
     double wsum = 0.0;
     for (int64_t i = 0; i < n; ++i) {
@@ -2189,9 +2434,15 @@ extern "C" int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* l
     HIP_TRY(hipMemcpyAsync(t->H[L], logits, cells * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(yd, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
     if (row_weight) HIP_TRY(hipMemcpyAsync(wd, row_weight, (size_t)mb * 4, hipMemcpyHostToDevice, st));
-    CeRowGroup g;
-    g.d[0] = CeRowDesc{ce_desc(t, t->H[L], yd, mb, (float)(1.0 / wsums[0])), row_weight ? wd : nullptr};
-    hipLaunchKernelGGL(ce_grad_weighted_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
+    if (t->hier) {
+        CeHierGroup g;
+        g.d[0] = CeHierDesc{ce_desc(t, t->H[L], yd, mb, (float)(1.0 / wsums[0])), row_weight ? wd : nullptr, trainer_hier_loss(t)};
+        hipLaunchKernelGGL(ce_grad_hier_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
+    } else {
+        CeRowGroup g;
+        g.d[0] = CeRowDesc{ce_desc(t, t->H[L], yd, mb, (float)(1.0 / wsums[0])), row_weight ? wd : nullptr};
+        hipLaunchKernelGGL(ce_grad_weighted_kernel, dim3((mb + 3) / 4), dim3(256), 0, st, g);
+    }
     HIP_TRY(hipGetLastError());
     if (row_group) {
         HIP_TRY(hipMemcpyAsync(gd, row_group, (size_t)mb * 4, hipMemcpyHostToDevice, st));

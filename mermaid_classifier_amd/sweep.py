@@ -152,7 +152,9 @@ class SweepConfig:
     ``warmup_steps`` / ``schedule_steps`` / ``final_lr_ratio`` / ``max_grad_norm`` / ``ema_decay`` (keyword only; a decaying schedule
     with ``schedule_steps=None`` ends after ``nbr_epochs`` epochs of this member's own steps).  ``row_weight`` / ``row_group`` (keyword
     only; arrays indexed by row of the train set) go to every pass of this member, ``group_dro_eta`` / ``n_groups`` to its classifier:
-    one sweep can hold an ERM member, a group-balanced one (``group_dro_eta=0``) and DRO members side by side."""
+    one sweep can hold an ERM member, a group-balanced one (``group_dro_eta=0``) and DRO members side by side.  ``class_levels`` /
+    ``level_weights`` / ``soft_targets`` (keyword only) are the classifier's taxonomy-aware loss: flat, level-weighted and soft-label
+    heads can train side by side."""
     hidden_layer_sizes: Tuple[int, ...] = (500, 300, 100)
     learning_rate_init: float = 1e-4
     alpha: float = 1e-4
@@ -182,6 +184,10 @@ class SweepConfig:
     row_group: Any = field(default=None, kw_only=True)
     group_dro_eta: float = field(default=0.0, kw_only=True)
     n_groups: Optional[int] = field(default=None, kw_only=True)
+    # the classifier's taxonomy-aware loss (mmc_trainer_set_hierarchy): keyword only, as in its constructor
+    class_levels: Optional[dict] = field(default=None, kw_only=True)
+    level_weights: Optional[Sequence[float]] = field(default=None, kw_only=True)
+    soft_targets: Optional[dict] = field(default=None, kw_only=True)
     batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None
     label_smoothing: float = 0.0
     focal_gamma: float = 0.0
@@ -197,7 +203,8 @@ class SweepConfig:
                                   mixup_alpha=self.mixup_alpha, regularizer_seed=self.regularizer_seed,
                                   lr_schedule=self.lr_schedule, warmup_steps=self.warmup_steps, schedule_steps=self.schedule_steps,
                                   final_lr_ratio=self.final_lr_ratio, max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay,
-                                  group_dro_eta=self.group_dro_eta, n_groups=self.n_groups)
+                                  group_dro_eta=self.group_dro_eta, n_groups=self.n_groups, class_levels=self.class_levels,
+                                  level_weights=self.level_weights, soft_targets=self.soft_targets)
 
 
 def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[Any]]],

@@ -19,7 +19,11 @@ hashable ids.  No pandas, sklearn or matplotlib.
 Order where the reference's depends on row order.  ``Counter.most_common`` keeps equal counts in insertion order, the order in which
 the rows of the split first produced each key; a table does not carry that.  The rules here, all over the table in row-major order
 (true class, then prediction): error-attribution rows of equal count stand in the order of the first ``(g, est)`` cell that produced
-their node; top-level categories of equal true frequency and growth forms of equal support stand in the order of their first class."""
+their node; top-level categories of equal true frequency and growth forms of equal support stand in the order of their first class.
+
+Two helpers have no counterpart in the reference: ``hierarchy_levels`` and ``soft_labels`` turn the same class paths, and the K x K
+similarity matrix ``ranking_validate`` takes, into the arrays of the taxonomy-aware training loss (include/mmc.h, "taxonomy-aware
+loss"; ``TorchMLPClassifier(class_levels=, soft_targets=)``)."""
 
 from __future__ import annotations
 
@@ -27,7 +31,7 @@ from typing import Any, Dict, Hashable, List, Optional, Sequence
 
 import numpy as np
 
-__all__ = ["TaxonomicScores", "SCALAR_NAMES"]
+__all__ = ["TaxonomicScores", "SCALAR_NAMES", "hierarchy_levels", "soft_labels"]
 
 SCALAR_NAMES = ("cross_branch_error_rate", "within_branch_error_rate", "gf_accuracy_gf_relevant", "within_ba_gf_accuracy")
 
@@ -184,3 +188,39 @@ class TaxonomicScores:
         ea, g = self.error_attribution(), self.growth_forms()
         return {"cross_branch_error_rate": float(ea["cross_branch_error_rate"]), "within_branch_error_rate": float(ea["within_branch_error_rate"]),
                 "gf_accuracy_gf_relevant": float(g["gf_accuracy_gf_relevant"]), "within_ba_gf_accuracy": float(g["within_ba_gf_accuracy"])}
+
+
+def hierarchy_levels(class_paths: Sequence[Sequence[Hashable]], depths: Sequence[int] = (1, 2), attribute: bool = True) -> np.ndarray:
+    """The level ids of the taxonomy-aware loss from the root-first paths ``TaxonomicScores`` takes -> K x L int32, row c the node of
+    class c at every level.  One level per depth d of ``depths``: the node of a class is its path prefix of length d, and a class
+    whose path is shorter than d gets its whole path.  With ``attribute=True`` one more level, the whole path: classes that share a
+    benthic attribute and differ only in growth form share its node.  A node's id is the index of the first class in it."""
+    paths = [tuple(p) for p in class_paths]
+    if any(len(p) < 1 for p in paths):
+        raise ValueError("every class path holds at least the class's own benthic attribute")
+    depths = [int(d) for d in depths]
+    if any(d < 1 for d in depths):
+        raise ValueError(f"depths must be positive, got {depths!r}")
+    keys = [[p[:d] for p in paths] for d in depths] + ([paths] if attribute else [])
+    out = np.empty((len(paths), len(keys)), np.int32)
+    for l, level in enumerate(keys):
+        first: Dict[Any, int] = {}
+        for c, key in enumerate(level):
+            out[c, l] = first.setdefault(key, c)
+    return out
+
+
+def soft_labels(similarity, beta: float) -> np.ndarray:
+    """Soft targets from a K x K similarity matrix S (the one ``ranking_validate`` takes): ``T[t, c] = exp(beta S[t, c]) /
+    sum_c' exp(beta S[t, c'])``, in float64 with a row-max shift -> K x K float32.  ``ValueError`` for a matrix that is not square or
+    holds a NaN, or a ``beta`` that is not finite."""
+    S = np.asarray(similarity, dtype=np.float64)
+    if S.ndim != 2 or S.shape[0] != S.shape[1]:
+        raise ValueError(f"similarity must be a square matrix, got shape {S.shape}")
+    if np.isnan(S).any():
+        raise ValueError("similarity holds a NaN")
+    if not np.isfinite(float(beta)):
+        raise ValueError(f"beta must be finite, got {beta!r}")
+    a = float(beta) * S
+    e = np.exp(a - a.max(axis=1, keepdims=True))
+    return (e / e.sum(axis=1, keepdims=True)).astype(np.float32)

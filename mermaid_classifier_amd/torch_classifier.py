@@ -26,7 +26,9 @@ formulation -- ``label_smoothing`` / ``focal_gamma`` / ``logit_prior``, ``_check
 (``mmc_trainer_set_dropout``, ``mmc_trainer_partial_fit_set_mixed``) -- whose defaults leave the step as it is; and the optimiser
 options -- ``lr_schedule`` / ``warmup_steps`` / ``schedule_steps`` / ``final_lr_ratio`` / ``max_grad_norm`` / ``ema_decay``,
 ``_apply_optimizer_options``, ``raw_parameters`` / ``averaged_parameters`` / ``use_weights``, ``grad_norms_``
-(``mmc_trainer_set_lr_schedule``, ``mmc_trainer_set_grad_clip``, ``mmc_trainer_set_ema``) -- again off by default.
+(``mmc_trainer_set_lr_schedule``, ``mmc_trainer_set_grad_clip``, ``mmc_trainer_set_ema``) -- again off by default; and the
+taxonomy-aware loss -- ``class_levels`` / ``level_weights`` / ``soft_targets``, ``_build_hierarchy_arrays``
+(``mmc_trainer_set_hierarchy``) -- off by default too.
 """
 
 from __future__ import annotations
@@ -152,7 +154,14 @@ class TorchMLPClassifier:
     Two more, keyword only, are group DRO (include/mmc.h, "group-robust training"): ``n_groups`` (None: off; else in [1, 1024]) and
     ``group_dro_eta`` in [0, 10], the step of the groups' distribution q (0: a static group-balanced loss).  They act on the
     ``partial_fit_rows`` passes that are given ``row_group``; ``group_weights_`` holds q after such a pass and is pickled (as log q),
-    so that a resumed classifier continues from it.  ``partial_fit_rows(row_weight=)`` needs neither."""
+    so that a resumed classifier continues from it.  ``partial_fit_rows(row_weight=)`` needs neither.
+
+    Three more, keyword only, are the taxonomy-aware loss (include/mmc.h, "taxonomy-aware loss"), keyed by label like ``class_weight``:
+    ``class_levels``, a dict from label to a sequence of L <= 4 ints, the class's node at every level (None or a negative int: no
+    node); ``level_weights``, L floats >= 0; ``soft_targets``, a dict from label to ``{label: mass}`` (a missing entry is 0; every row
+    sums to 1), which replaces the one-hot base term and cannot be combined with ``label_smoothing`` / ``focal_gamma``.
+    ``taxonomy.hierarchy_levels`` and ``taxonomy.soft_labels`` make the arrays.  Resolved in ``classes_`` order when the trainer is
+    created; training alone reads them, and ``mixup_alpha > 0`` cannot be combined with them."""
 
     _estimator_type = "classifier"
 
@@ -164,7 +173,8 @@ class TorchMLPClassifier:
                  logit_prior: dict | None = None, dropout: float = 0.0, input_dropout: float = 0.0, mixup_alpha: float = 0.0,
                  regularizer_seed: int | None = None, lr_schedule: str = "constant", warmup_steps: int = 0,
                  schedule_steps: int | None = None, final_lr_ratio: float = 0.0, max_grad_norm: float | None = None,
-                 ema_decay: float = 0.0, group_dro_eta: float = 0.0, n_groups: int | None = None):
+                 ema_decay: float = 0.0, group_dro_eta: float = 0.0, n_groups: int | None = None,
+                 class_levels: dict | None = None, level_weights: Sequence[float] | None = None, soft_targets: dict | None = None):
         if activation != "relu":
             raise ValueError(f"TorchMLPClassifier only supports activation='relu', got {activation!r}.")
         if solver != "adam":
@@ -203,6 +213,9 @@ class TorchMLPClassifier:
         self.ema_decay = ema_decay
         self.group_dro_eta = group_dro_eta
         self.n_groups = n_groups
+        self.class_levels = class_levels
+        self.level_weights = level_weights
+        self.soft_targets = soft_targets
 
     # ---- host bookkeeping, restated from the reference ------------------------------------------------------------
     def _resolve_batch_size(self, n_samples: int) -> int:
@@ -256,6 +269,55 @@ class TorchMLPClassifier:
             raise ValueError(f"logit_prior for {bad!r} is not finite.")
         return vec
 
+    def _build_hierarchy_arrays(self):
+        """``class_levels`` / ``level_weights`` / ``soft_targets`` in ``classes_`` order -> ``(levels [L][K] int32, weights [L] float64,
+        T [K][K] float32)``, each None where not given; None when nothing is given.  What ``mmc_trainer_set_hierarchy`` takes."""
+        levels_of = getattr(self, "class_levels", None)
+        weights = getattr(self, "level_weights", None)
+        soft = getattr(self, "soft_targets", None)
+        if levels_of is None and weights is None and soft is None:
+            return None
+        classes = self.classes_.tolist()
+        levels = lam = T = None
+        if (levels_of is None) != (weights is None):
+            raise ValueError("class_levels and level_weights go together: only "
+                             f"{'class_levels' if weights is None else 'level_weights'} was given.")
+        if levels_of is not None:
+            missing = [cls for cls in classes if cls not in levels_of]
+            if missing:
+                raise ValueError(f"class_levels is missing nodes for {sorted(missing)!r}. Pass the nodes of every class in classes_.")
+            lam = np.asarray([float(v) for v in weights], dtype=np.float64)
+            n_levels = len(lam)
+            if not 1 <= n_levels <= _lib.MMC_HIER_MAX_LEVELS:
+                raise ValueError(f"level_weights must hold 1 to {_lib.MMC_HIER_MAX_LEVELS} weights, got {n_levels}.")
+            if not (np.isfinite(lam).all() and (lam >= 0).all()):
+                raise ValueError(f"level_weights must be finite and >= 0, got {lam.tolist()!r}.")
+            levels = np.empty((n_levels, len(classes)), np.int32)
+            for c, cls in enumerate(classes):
+                nodes = list(levels_of[cls])
+                if len(nodes) != n_levels:
+                    raise ValueError(f"class_levels for {cls!r} has {len(nodes)} entries, level_weights {n_levels}.")
+                levels[:, c] = [-1 if v is None or int(v) < 0 else int(v) for v in nodes]
+        if soft is not None:
+            missing = [cls for cls in classes if cls not in soft]
+            if missing:
+                raise ValueError(f"soft_targets is missing rows for {sorted(missing)!r}. Pass a row for every class in classes_.")
+            index = {cls: c for c, cls in enumerate(classes)}
+            T = np.zeros((len(classes), len(classes)), np.float32)
+            for cls in classes:
+                for other, mass in soft[cls].items():
+                    if other not in index:
+                        raise ValueError(f"soft_targets for {cls!r} names {other!r}, which is not in classes_.")
+                    T[index[cls], index[other]] = float(mass)
+            if not (np.isfinite(T).all() and (T >= 0).all()):
+                raise ValueError("soft_targets holds a mass that is negative or not finite (as float32).")
+            off = np.abs(T.astype(np.float64).sum(axis=1) - 1.0)
+            if off.max() > 1e-5:
+                raise ValueError(f"soft_targets for {classes[int(off.argmax())]!r} sums to {1.0 + off.max():.7g} off 1 by more than 1e-5.")
+        if float(getattr(self, "mixup_alpha", 0.0)) != 0.0:
+            raise ValueError("mixup_alpha > 0 cannot be combined with class_levels / soft_targets.")
+        return levels, lam, T
+
     def _initial_parameters(self):
         """Glorot-uniform weights / zero biases drawn exactly as the reference's ``_MLPModule`` draws them
         (torch_classifier.py:53-76, 176-184): the Linear layers are constructed first (their default init consumes the
@@ -288,6 +350,13 @@ class TorchMLPClassifier:
         try:
             _lib.check(lib.mmc_trainer_set_loss(self._h, float(self.label_smoothing), float(self.focal_gamma),
                                                 prior.ctypes.data_as(C.POINTER(C.c_float)) if prior is not None else None))
+            hier = getattr(self, "_hierarchy_arrays", None)
+            if hier is not None:
+                levels, lam, T = hier
+                _lib.check(lib.mmc_trainer_set_hierarchy(self._h, 0 if levels is None else len(lam),
+                                                         None if levels is None else levels.ctypes.data,
+                                                         None if levels is None else lam.ctypes.data,
+                                                         None if T is None else T.ctypes.data))
             if float(self.dropout) != 0.0 or float(self.input_dropout) != 0.0:
                 _lib.check(lib.mmc_trainer_set_dropout(self._h, float(self.input_dropout), float(self.dropout),
                                                        self._regularizer_seed_value()))
@@ -393,6 +462,7 @@ class TorchMLPClassifier:
             self.loss_curve_ = []
             self._class_weight_vector = self._build_class_weight_vector()
             self._logit_prior_vector = self._build_logit_prior_vector()
+            self._hierarchy_arrays = self._build_hierarchy_arrays()
             self._create_trainer(*self._initial_parameters())
         elif X_arr.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {X_arr.shape[1]} features, expected {self.n_features_in_}")
@@ -476,6 +546,7 @@ class TorchMLPClassifier:
             self.loss_curve_ = []
             self._class_weight_vector = self._build_class_weight_vector()
             self._logit_prior_vector = self._build_logit_prior_vector()
+            self._hierarchy_arrays = self._build_hierarchy_arrays()
             self._create_trainer(*self._initial_parameters())
         else:
             fs._check_against(self)
@@ -624,7 +695,8 @@ class TorchMLPClassifier:
                 "input_dropout": self.input_dropout, "mixup_alpha": self.mixup_alpha, "regularizer_seed": self.regularizer_seed,
                 "lr_schedule": self.lr_schedule, "warmup_steps": self.warmup_steps, "schedule_steps": self.schedule_steps,
                 "final_lr_ratio": self.final_lr_ratio, "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay,
-                "group_dro_eta": self.group_dro_eta, "n_groups": self.n_groups}
+                "group_dro_eta": self.group_dro_eta, "n_groups": self.n_groups, "class_levels": self.class_levels,
+                "level_weights": self.level_weights, "soft_targets": self.soft_targets}
 
     def set_params(self, **params: Any) -> "TorchMLPClassifier":
         for key, value in params.items():
@@ -653,7 +725,9 @@ class TorchMLPClassifier:
                              ("lr_schedule", "constant"), ("warmup_steps", 0), ("schedule_steps", None), ("final_lr_ratio", 0.0),
                              ("max_grad_norm", None), ("ema_decay", 0.0),
                              # ... and one made before group DRO existed without it
-                             ("group_dro_eta", 0.0), ("n_groups", None)):
+                             ("group_dro_eta", 0.0), ("n_groups", None),
+                             # ... and one made before the taxonomy-aware loss existed with the flat loss
+                             ("class_levels", None), ("level_weights", None), ("soft_targets", None), ("_hierarchy_arrays", None)):
             self.__dict__.setdefault(key, default)
         self._h = None
         if params is not None:
