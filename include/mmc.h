@@ -605,6 +605,47 @@ int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* logits, cons
 int mmc_trainer_set_hierarchy(mmc_trainer* t, int n_levels, const int32_t* level_of_class /* [n_levels][K], or NULL when n_levels == 0 */,
                               const double* level_weight /* [n_levels] */, const float* soft_targets /* [K][K], or NULL */);
 
+/* ---- batch normalisation: between every hidden Linear and its ReLU, per trainer; folded into the Linear stack for evaluation ---------
+ * Extends: the head of TorchMLPClassifier (torch_classifier.py:53-76, Linear -> ReLU -> ... -> Linear), whose deeper forms need a
+ *   small step (docs/research/hidden-layer-experiments.md sections 2 and 3).  The meaning is torch.nn.BatchNorm1d's; no counterpart
+ *   in the reference and no measured gain on reef data.  One switch normalises every hidden layer; the last layer never is.
+ * Training forward.  Hidden layer l, mini-batch of mb rows, column j, Z = H_l W_l^T + b_l (the step's GEMM, bias epilogue):
+ *     mu_j = mean_m Z[m][j];  v_j = mean_m (Z[m][j] - mu_j)^2 (biased, two passes);  rstd_j = 1 / sqrt(v_j + eps)
+ *     xhat = (Z - mu_j) rstd_j;  H_{l+1} = relu(gamma_j xhat + beta_j)
+ * Running statistics, after each step: rm = (1 - mom) rm + mom mu;  rv = (1 - mom) rv + mom v mb / (mb - 1) (unbiased).  They start
+ *   at 0 and 1.  The scalars are the floats of eps, mom, 1 - mom and mb / (mb - 1), each formed in double.
+ * Backward, from dA, the gradient w.r.t. gamma xhat + beta (what the step's masked dZ launch leaves):
+ *     g_beta_j = sum_m dA;  g_gamma_j = sum_m dA xhat;  dZ = (gamma_j rstd_j / mb) ((mb dA - g_beta_j) - xhat g_gamma_j)
+ * Every column sum runs in an order that is a function of (mb, N) alone: rows in four quarters of ceil(mb / 4), each on four chains
+ *   in row order, (s0 + s1) + (s2 + s3), the quarters as (p0 + p1) + (p2 + p3).  No atomics; nothing is fused.
+ * Parameters.  gamma starts at 1 and beta at 0; both are Adam parameters (the trainer's betas, eps, schedule and clipping: their
+ *   gradients are part of the clipped norm) and not part of the L2 term.  The bias b_l of a normalised layer cancels exactly, so it
+ *   is frozen: its gradient is zero-filled once and no column sum writes it, and Adam's update of it is 0 / eps: bit-unchanged.
+ * Evaluation reads the folded stack: s_j = gamma_j / sqrt(rv_j + eps), W'_l[j][:] = s_j W_l[j][:], b'_l[j] = beta_j + s_j (b_l[j] - rm_j),
+ *   refreshed lazily by the first eval-mode forward after a step; relu(W' x + b') is the frozen-statistics layer, so mmc_trainer_logits,
+ *   the evaluation and calibration entry points and mmc_trainer_folded_params see one plain Linear / ReLU stack.
+ * mmc_trainer_set_batch_norm: enable != 0 with eps > 0 (finite, as a float too) and 0 < momentum <= 1; enable = 0 restores the plain
+ *   trainer, its launches and its bits (eps and momentum are then not read).  MMC_ERR_ARG, the trainer left as it was: a bad scalar;
+ *   a trainer with hidden dropout (p_hidden > 0; input dropout composes) or with averaged weights -- and mmc_trainer_set_dropout
+ *   with p_hidden > 0 or mmc_trainer_set_ema with a decay on a normalised trainer: whichever setter comes second refuses; a trainer
+ *   whose Adam eps is 0.  Enabling again keeps the state and moves the two scalars.
+ * A pass of a normalised trainer in which a mini-batch (the last one included) holds fewer than 2 rows returns MMC_ERR_ARG before
+ *   anything is uploaded or launched: weights, moments and step count are unchanged.
+ * Everything in the loss stage, the schedule, clipping, input dropout and mixup compose untouched.  A normalised member trains
+ *   beside plain ones in a group; group equals solo, host-fed equals resident, and MMC_TRAIN_CHUNK_ROWS changes nothing, bit for bit.
+ * mmc_trainer_batch_norm_state reads (set = 0) or writes the per-hidden-layer arrays: n_layers - 1 pointers each, entry l of
+ *   dims[l + 1] floats.  mmc_trainer_folded_params is mmc_trainer_get_params of the folded stack (of a trainer without the option:
+ *   that call itself).  mmc_trainer_norm_stage runs the step's two kernels on caller arrays Z, dA [mb][dims[layer + 1]], mb in
+ *   [2, 16384], with the trainer's current gamma / beta of hidden layer `layer`; batch_var is the biased v; dA NULL runs the forward
+ *   alone.  It touches neither the running statistics nor any other state. */
+int mmc_trainer_set_batch_norm(mmc_trainer* t, int enable, double eps, double momentum);
+int mmc_trainer_batch_norm_state(mmc_trainer* t, int set, float* const* gamma, float* const* beta, float* const* running_mean,
+                                 float* const* running_var, float* const* adam_m_gamma, float* const* adam_v_gamma,
+                                 float* const* adam_m_beta, float* const* adam_v_beta);
+int mmc_trainer_folded_params(mmc_trainer* t, float* const* W, float* const* b);
+int mmc_trainer_norm_stage(mmc_trainer* t, int layer, const float* Z, const float* dA, int64_t mb, float* H, float* dZ, float* g_gamma,
+                           float* g_beta, float* batch_mean, float* batch_var, void* hip_stream);
+
 /* ---- validation of a calibrated head --------------------------------------------------------------------------------
  * Replaces: what MermaidTrainer.__call__ computes after the calibration (mermaid_classifier/pyspacer/trainer.py:267-293:
  *   evaluate_classifier on val, ValResults, acc, the previous models' accuracies) and the per-row reductions the metrics make of the

@@ -20,6 +20,7 @@ from .ranking import RankedValidation, ranking_validate, similarity_levels  # no
 from .cover import CoverEstimate, estimate_cover, prior_from_labels  # noqa: F401
 from .feature_transform import FeatureTransform  # noqa: F401
 from .logit_scaling import LogitScaling, fit_logit_scaling  # noqa: F401
+from .optim import fold_batch_norm  # noqa: F401
 from .neighbors import KnnValidation, Neighbors, audit_labels, knn_validate, near_duplicates, nearest  # noqa: F401
 
 __all__ = [
@@ -38,6 +39,6 @@ __all__ = [
     "category_bins", "TaxonomicScores", "hierarchy_levels", "soft_labels",
     "estimate_cover", "CoverEstimate", "prior_from_labels",
     "FeatureTransform",
-    "LogitScaling", "fit_logit_scaling",
+    "LogitScaling", "fit_logit_scaling", "fold_batch_norm",
     "nearest", "Neighbors", "knn_validate", "KnnValidation", "audit_labels", "near_duplicates",
 ]

@@ -59,6 +59,7 @@ SYMBOLS = [
     "mmc_trainer_set_group_dro", "mmc_trainer_group_dro_state", "mmc_trainer_partial_fit_set_weighted",
     "mmc_trainer_group_partial_fit_set_weighted", "mmc_trainer_loss_gradient_weighted",
     "mmc_trainer_set_hierarchy",
+    "mmc_trainer_set_batch_norm", "mmc_trainer_batch_norm_state", "mmc_trainer_folded_params", "mmc_trainer_norm_stage",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
 ]
 # include/mmc.h, "optimiser options"
@@ -294,6 +295,14 @@ def _load() -> C.CDLL:
     lib.mmc_trainer_loss_gradient_weighted.argtypes = [vp, vp, vp, vp, vp, vp, f64, i32, i64, vp, vp, vp, vp, vp]
     lib.mmc_trainer_set_hierarchy.restype = i32
     lib.mmc_trainer_set_hierarchy.argtypes = [vp, i32, vp, vp, vp]
+    lib.mmc_trainer_set_batch_norm.restype = i32
+    lib.mmc_trainer_set_batch_norm.argtypes = [vp, i32, f64, f64]
+    lib.mmc_trainer_batch_norm_state.restype = i32
+    lib.mmc_trainer_batch_norm_state.argtypes = [vp, i32] + [C.POINTER(fp)] * 8
+    lib.mmc_trainer_folded_params.restype = i32
+    lib.mmc_trainer_folded_params.argtypes = [vp, C.POINTER(fp), C.POINTER(fp)]
+    lib.mmc_trainer_norm_stage.restype = i32
+    lib.mmc_trainer_norm_stage.argtypes = [vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     lib.mmc_dist_unique_id.restype = i32
     lib.mmc_dist_unique_id.argtypes = [vp]
     lib.mmc_dist_create.restype = i32

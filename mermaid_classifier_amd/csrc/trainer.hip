@@ -31,6 +31,12 @@
 // Per trainer, off by default (include/mmc.h, "taxonomy-aware loss"; a member without a hierarchy runs the loss kernels above as ever):
 //   levels    l_i += w_t sum_l lam_l (-log P_l), P_l the softmax mass of t's node at level l    ce_grad_hier_kernel, ce_grad_rows_hier
 //   soft      the base term becomes w_t (-sum_c T[t,c] logp_c); row weights ride the same kernel (mmc_trainer_set_hierarchy)
+// Per trainer, off by default (include/mmc.h, "batch normalisation"; a member without it launches none of these and keeps its colsum):
+//   forward   Z = H(l) W(l)^T + b(l) by the forward GEMM (EPI_BIAS) to a buffer of its own, then
+//             H(l+1) = relu(gamma xhat + beta), xhat = (Z - mu) rstd; the running statistics    bn_forward_kernel
+//   backward  dZ(l) holds dA after the masked launch: g_gamma, g_beta, dZ in place              bn_backward_kernel
+//   update    gamma, beta of every hidden layer in one more Adam launch; b(l) frozen            adam_kernel / adam_opt_kernel
+//   eval      W' = s W, b' = beta + s (b - rm), s = gamma / sqrt(rv + eps), lazily              bn_fold_kernel
 //
 // Every step is the step of a group of trainers (trainer_group_step): each kind of launch once, one member per blockIdx.z, the
 // member's operands in a by-value descriptor array.  A trainer on its own -- the host-fed pass, mmc_trainer_partial_fit_set, the
@@ -1046,6 +1052,188 @@ __global__ __launch_bounds__(256) void gather_set_rows_mixed_kernel(const float*
     }
 }
 
+// ---- batch normalisation (include/mmc.h, "batch normalisation"): the kernels of a member with mmc_trainer_set_batch_norm.  A member
+// without it launches none of them.  Both step kernels share one shape: a workgroup of 256 threads takes 64 columns, thread
+// (c, q) = (tid & 63, tid >> 6) column c of them and row quarter q, rows [q per, (q + 1) per) with per = ceil(M / 4).  A thread adds
+// its rows in order on four chains, s = (s0 + s1) + (s2 + s3); the quarters meet in LDS as (p0 + p1) + (p2 + p3), which every thread
+// of the column reads back, so all four hold the same bits.  The order is a function of (M, N) alone: no atomics, and nothing
+// depends on the grid (a workgroup past its member's columns leaves before the first barrier) or on who shares the launch.
+// Loads in flight: a wave's 64 lanes read 64 consecutive floats of one row (256 B, coalesced); the reductions keep four rows'
+// loads per thread in flight (eight in the backward, which reads dA and Z), the element-wise passes are unrolled by four too.  At
+// mb = 200, N = 500 that is 8 workgroups x 4 waves x 4 x 256 B = 32 KB requested at once on 400 KB that sit in L2 after the GEMM:
+// the kernel is latency-bound at that size and the quarters are what spreads it over 32 waves (one thread per column: 8).
+struct BnFwdDesc {
+    const float* Z;              // [M][N] H W^T + b of the layer
+    const float *gamma, *beta;   // [N]
+    float* H;                    // [M][N] relu(gamma xhat + beta)
+    float *mu, *rstd;            // [N] the mini-batch's mean and 1 / sqrt(v + eps), kept for the backward
+    float *rmean, *rvar;         // [N] running statistics, or null (mmc_trainer_norm_stage leaves them alone)
+    float* var;                  // [N] the biased variance v, or null
+    int M, N;
+    float eps, mom, om_mom, unbias;   // (float) of eps, momentum, 1 - momentum, M / (M - 1), each formed in double
+};
+struct BnFwdGroup { BnFwdDesc d[MMC_TRAINER_GROUP_MAX]; };
+struct BnBwdDesc {
+    float* dA;                   // [M][N] in: gradient w.r.t. gamma xhat + beta; out: gradient w.r.t. Z
+    const float *Z, *mu, *rstd, *gamma;
+    float *ggamma, *gbeta;       // [N]
+    int M, N;
+};
+struct BnBwdGroup { BnBwdDesc d[MMC_TRAINER_GROUP_MAX]; };
+// the fold of one trainer: one descriptor per hidden layer (n_layers <= 16, so at most 15)
+struct BnFoldDesc {
+    const float *W, *b, *gamma, *beta, *rmean, *rvar;
+    float *Wf, *bf;
+    int N, K;
+    float eps;
+};
+struct BnFoldGroup { BnFoldDesc d[MMC_TRAINER_GROUP_MAX]; };
+static_assert(sizeof(BnFwdGroup) <= 4096 && sizeof(BnBwdGroup) <= 4096 && sizeof(BnFoldGroup) <= 4096, "kernel-argument limit");
+
+// mu = mean of the column, v = mean of (z - mu)^2 (two passes: E[z^2] - mu^2 cancels on a column of mean 1000 and deviation 0.1),
+// xhat = (z - mu) rstd, H = relu(gamma xhat + beta); rm = om_mom rm + mom mu, rv = om_mom rv + mom (v unbias).  Nothing is fused.
+__global__ __launch_bounds__(256) void bn_forward_kernel(const BnFwdGroup g)
+{
+#pragma clang fp contract(off)
+    __shared__ float part[4][64];
+    const BnFwdDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 64 >= d.N) return;
+    const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int n = blockIdx.x * 64 + c;
+    const int M = d.M;
+    const size_t N = (size_t)d.N;
+    const bool live = n < d.N;
+    const int per = (M + 3) >> 2;
+    const int b = q * per < M ? q * per : M, e = b + per < M ? b + per : M;
+    const float* z = d.Z + (live ? n : 0);
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    if (live) {
+        int m = b;
+        for (; m + 3 < e; m += 4) {
+            s0 += z[(size_t)m * N];
+            s1 += z[(size_t)(m + 1) * N];
+            s2 += z[(size_t)(m + 2) * N];
+            s3 += z[(size_t)(m + 3) * N];
+        }
+        for (; m < e; ++m) s0 += z[(size_t)m * N];
+    }
+    part[q][c] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    const float mu = ((part[0][c] + part[1][c]) + (part[2][c] + part[3][c])) / (float)M;
+    __syncthreads();
+    s0 = s1 = s2 = s3 = 0.f;
+    if (live) {
+        int m = b;
+        for (; m + 3 < e; m += 4) {
+            const float d0 = z[(size_t)m * N] - mu, d1 = z[(size_t)(m + 1) * N] - mu;
+            const float d2 = z[(size_t)(m + 2) * N] - mu, d3 = z[(size_t)(m + 3) * N] - mu;
+            s0 += d0 * d0;
+            s1 += d1 * d1;
+            s2 += d2 * d2;
+            s3 += d3 * d3;
+        }
+        for (; m < e; ++m) {
+            const float d0 = z[(size_t)m * N] - mu;
+            s0 += d0 * d0;
+        }
+    }
+    part[q][c] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (!live) return;   // past the last barrier
+    const float v = ((part[0][c] + part[1][c]) + (part[2][c] + part[3][c])) / (float)M;
+    const float rstd = 1.0f / sqrtf(v + d.eps);
+    const float ga = d.gamma[n], be = d.beta[n];
+    float* h = d.H + n;
+#pragma unroll 4
+    for (int m = b; m < e; ++m) {
+        const float xh = (z[(size_t)m * N] - mu) * rstd;
+        h[(size_t)m * N] = fmaxf(ga * xh + be, 0.f);
+    }
+    if (q == 0) {
+        d.mu[n] = mu;
+        d.rstd[n] = rstd;
+        if (d.var) d.var[n] = v;
+        if (d.rmean) {
+            d.rmean[n] = d.om_mom * d.rmean[n] + d.mom * mu;
+            d.rvar[n] = d.om_mom * d.rvar[n] + d.mom * (v * d.unbias);
+        }
+    }
+}
+
+// gbeta = sum_m dA, ggamma = sum_m dA xhat, dZ = (gamma rstd / M) ((M dA - gbeta) - xhat ggamma), in place.  Nothing is fused.
+__global__ __launch_bounds__(256) void bn_backward_kernel(const BnBwdGroup g)
+{
+#pragma clang fp contract(off)
+    __shared__ float pb[4][64];
+    __shared__ float pg[4][64];
+    const BnBwdDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 64 >= d.N) return;
+    const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int n = blockIdx.x * 64 + c;
+    const int M = d.M;
+    const size_t N = (size_t)d.N;
+    const bool live = n < d.N;
+    const int per = (M + 3) >> 2;
+    const int b = q * per < M ? q * per : M, e = b + per < M ? b + per : M;
+    const float* z = d.Z + (live ? n : 0);
+    float* a = d.dA + (live ? n : 0);
+    const float mu = live ? d.mu[n] : 0.f, rstd = live ? d.rstd[n] : 0.f;
+    float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f;
+    if (live) {
+        int m = b;
+        for (; m + 3 < e; m += 4) {
+            const float a0 = a[(size_t)m * N], a1 = a[(size_t)(m + 1) * N], a2 = a[(size_t)(m + 2) * N], a3 = a[(size_t)(m + 3) * N];
+            const float x0 = (z[(size_t)m * N] - mu) * rstd, x1 = (z[(size_t)(m + 1) * N] - mu) * rstd;
+            const float x2 = (z[(size_t)(m + 2) * N] - mu) * rstd, x3 = (z[(size_t)(m + 3) * N] - mu) * rstd;
+            b0 += a0;
+            b1 += a1;
+            b2 += a2;
+            b3 += a3;
+            g0 += a0 * x0;
+            g1 += a1 * x1;
+            g2 += a2 * x2;
+            g3 += a3 * x3;
+        }
+        for (; m < e; ++m) {
+            const float a0 = a[(size_t)m * N];
+            const float x0 = (z[(size_t)m * N] - mu) * rstd;
+            b0 += a0;
+            g0 += a0 * x0;
+        }
+    }
+    pb[q][c] = (b0 + b1) + (b2 + b3);
+    pg[q][c] = (g0 + g1) + (g2 + g3);
+    __syncthreads();
+    if (!live) return;   // past the last barrier
+    const float gb = (pb[0][c] + pb[1][c]) + (pb[2][c] + pb[3][c]);
+    const float gg = (pg[0][c] + pg[1][c]) + (pg[2][c] + pg[3][c]);
+    const float mf = (float)M;
+    const float k = (d.gamma[n] * rstd) / mf;
+#pragma unroll 4
+    for (int m = b; m < e; ++m) {
+        const float xh = (z[(size_t)m * N] - mu) * rstd;
+        a[(size_t)m * N] = k * ((mf * a[(size_t)m * N] - gb) - xh * gg);
+    }
+    if (q == 0) {
+        d.ggamma[n] = gg;
+        d.gbeta[n] = gb;
+    }
+}
+
+// s = gamma / sqrt(rv + eps); W'[j][:] = s W[j][:], b'[j] = beta + s (b[j] - rm[j]).  Row j of layer blockIdx.z per workgroup.
+__global__ __launch_bounds__(256) void bn_fold_kernel(const BnFoldGroup g)
+{
+#pragma clang fp contract(off)
+    const BnFoldDesc& d = g.d[blockIdx.z];
+    const int j = blockIdx.x;
+    if (j >= d.N) return;
+    const float s = d.gamma[j] / sqrtf(d.rvar[j] + d.eps);
+    const float* w = d.W + (size_t)j * d.K;
+    float* wf = d.Wf + (size_t)j * d.K;
+    for (int k = threadIdx.x; k < d.K; k += 256) wf[k] = s * w[k];
+    if (threadIdx.x == 0) d.bf[j] = d.beta[j] + s * (d.b[j] - d.rmean[j]);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -1087,7 +1275,7 @@ struct mmc_trainer {
     long long warmup_steps = 0, total_steps = 0;
     double final_ratio = 0.0;
     double max_norm = 0.0;                              // 0 = no clipping
-    DevBuf<float> gpartials;                            // [2 * 16][256] partial sums of squares of gW[l] (2l) and gb[l] (2l + 1)
+    DevBuf<float> gpartials;                            // [2 * 16 + 1][256] partial sums of squares of gW[l] (2l), gb[l] (2l + 1), bn_g (2L)
     DevBuf<float> coef;                                 // the step's clipping coefficient
     DevBuf<float> gnorm;                                // pre-clip norm of every step of a pass, beside losses
     int gnorm_steps = 0;                                // steps of the last pass that wrote gnorm
@@ -1108,6 +1296,18 @@ struct mmc_trainer {
     DevBuf<int32_t> hier_ids;                           // [hier_levels][K] node ids or empty
     DevBuf<float> hier_T;                               // [K][K] soft targets or empty
     bool hier = false;                                  // hier_levels > 0 or soft targets: the member takes ce_grad_hier_kernel
+    // batch normalisation (mmc_trainer_set_batch_norm): off = today's launches.  Hidden layer h (0 .. L-2) owns [bn_off[h],
+    // bn_off[h] + 2 dims[h+1]) of every bn_* array: gamma then beta in bn_p (bn_g, bn_m, bn_v alike, so Adam and the clipping norm
+    // take all of them in one launch each), running mean then variance in bn_run, the step's mean then rstd in bn_stat.
+    bool bn = false;
+    double bn_eps = 1e-5, bn_mom = 0.1;
+    std::vector<int64_t> bn_off;
+    int64_t bn_total = 0;                               // 2 x the sum of the hidden widths
+    DevBuf<float> bn_p, bn_g, bn_m, bn_v, bn_run, bn_stat;
+    std::vector<DevBuf<float>> Zbuf;                    // [l + 1]: Z of hidden layer l, [mb][dims[l + 1]] (the backward reads it)
+    std::vector<DevBuf<float>> fW, fb;                  // the folded hidden layers, what the eval-mode forward reads
+    bool fold_stale = true;                             // a step or a state upload since the last fold
+    float* bn_ptr(const DevBuf<float>& a, int h, int second) const { return a.p + bn_off[h] + (second ? dims[h + 1] : 0); }
 };
 
 #define T_K(expr)                                                                   \
@@ -1277,6 +1477,8 @@ extern "C" int mmc_trainer_set_dropout(mmc_trainer* t, double p_input, double p_
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!(std::isfinite(p_input) && p_input >= 0.0 && p_input <= 0.9)) return mmc_fail(MMC_ERR_ARG, "p_input = %g outside [0, 0.9]", p_input);
     if (!(std::isfinite(p_hidden) && p_hidden >= 0.0 && p_hidden <= 0.9)) return mmc_fail(MMC_ERR_ARG, "p_hidden = %g outside [0, 0.9]", p_hidden);
+    if (t->bn && p_hidden > 0.0)
+        return mmc_fail(MMC_ERR_ARG, "p_hidden = %g on a trainer with batch normalisation (mmc_trainer_set_batch_norm)", p_hidden);
     t->p_input = p_input;
     t->p_hidden = p_hidden;
     t->drop_seed = seed;
@@ -1344,7 +1546,7 @@ extern "C" int mmc_trainer_set_grad_clip(mmc_trainer* t, double max_norm)
     if (max_norm != 0.0 && !t->gpartials) {
         HIP_TRY(hipSetDevice(t->device));
         DevBuf<float> gp, cf;
-        if (!gp.alloc(2 * 16 * 256) || !cf.alloc(1)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the gradient-norm partials");
+        if (!gp.alloc((2 * 16 + 1) * 256) || !cf.alloc(1)) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the gradient-norm partials");
         t->gpartials = std::move(gp);
         t->coef = std::move(cf);
     }
@@ -1370,6 +1572,8 @@ extern "C" int mmc_trainer_set_ema(mmc_trainer* t, double decay)
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!(decay == 0.0 || (decay > 0.0 && decay < 1.0))) return mmc_fail(MMC_ERR_ARG, "decay = %g is neither 0 nor in (0, 1)", decay);
+    if (t->bn && decay != 0.0)
+        return mmc_fail(MMC_ERR_ARG, "decay = %g on a trainer with batch normalisation (mmc_trainer_set_batch_norm)", decay);
     HIP_TRY(hipSetDevice(t->device));
     if (decay == 0.0) {
         t->sW.clear();
@@ -1487,9 +1691,158 @@ extern "C" int mmc_trainer_group_dro_state(mmc_trainer* t, int set, double* log_
     return MMC_OK;
 }
 
+// ---- batch normalisation (include/mmc.h) -----------------------------------------------------------------------------------
+extern "C" int mmc_trainer_set_batch_norm(mmc_trainer* t, int enable, double eps, double momentum)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    HIP_TRY(hipSetDevice(t->device));
+    if (!enable) {   // passes synchronise their stream before they return: nothing in flight reads what is freed here
+        t->bn = false;
+        t->bn_p.reset(); t->bn_g.reset(); t->bn_m.reset(); t->bn_v.reset(); t->bn_run.reset(); t->bn_stat.reset();
+        t->Zbuf.clear(); t->fW.clear(); t->fb.clear();
+        t->bn_off.clear();
+        t->bn_total = 0;
+        return MMC_OK;
+    }
+    if (!(eps > 0.0 && std::isfinite(eps) && (float)eps > 0.f)) return mmc_fail(MMC_ERR_ARG, "eps = %g is not a positive finite fp32 value", eps);
+    if (!(momentum > 0.0 && momentum <= 1.0)) return mmc_fail(MMC_ERR_ARG, "momentum = %g outside (0, 1]", momentum);
+    if (t->p_hidden > 0.0)
+        return mmc_fail(MMC_ERR_ARG, "batch normalisation on a trainer with hidden dropout p_hidden = %g (mmc_trainer_set_dropout)", t->p_hidden);
+    if (!t->sW.empty())
+        return mmc_fail(MMC_ERR_ARG, "batch normalisation on a trainer with averaged weights, decay = %g (mmc_trainer_set_ema)", t->ema_decay);
+    if (!(t->eps > 0.0))
+        return mmc_fail(MMC_ERR_ARG, "batch normalisation freezes the hidden biases at a zero gradient, which needs Adam's eps > 0 (got %g)", t->eps);
+    if (t->bn) {   // already on: the state stays, the two scalars move
+        t->bn_eps = eps;
+        t->bn_mom = momentum;
+        t->fold_stale = true;
+        return MMC_OK;
+    }
+    const int H = t->L - 1;
+    std::vector<int64_t> off(H);
+    int64_t total = 0;
+    for (int h = 0; h < H; ++h) {
+        off[h] = total;
+        total += 2 * (int64_t)t->dims[h + 1];
+    }
+    DevBuf<float> p, g, m, v, run, stat;
+    std::vector<DevBuf<float>> fW(H), fb(H);
+    if (total) {
+        bool ok = p.alloc(total) && g.alloc(total) && m.alloc(total) && v.alloc(total) && run.alloc(total) && stat.alloc(total);
+        for (int h = 0; h < H && ok; ++h) ok = fW[h].alloc((int64_t)t->dims[h + 1] * t->dims[h]) && fb[h].alloc(t->dims[h + 1]);
+        if (!ok) return mmc_fail(MMC_ERR_NOMEM, "hipMalloc failed for the batch-normalisation state (%lld values)", (long long)total);
+        // gamma = 1, beta = 0; running mean 0, running variance 1: the same pattern in both arrays
+        std::vector<float> init((size_t)total, 0.f);
+        for (int h = 0; h < H; ++h) {
+            std::fill(init.begin() + off[h], init.begin() + off[h] + t->dims[h + 1], 1.f);
+            std::fill(init.begin() + off[h] + t->dims[h + 1], init.begin() + off[h] + 2 * t->dims[h + 1], 0.f);
+        }
+        HIP_TRY(hipMemcpy(p, init.data(), (size_t)total * 4, hipMemcpyHostToDevice));
+        for (int h = 0; h < H; ++h) {   // the running statistics: mean first (0), variance second (1)
+            std::fill(init.begin() + off[h], init.begin() + off[h] + t->dims[h + 1], 0.f);
+            std::fill(init.begin() + off[h] + t->dims[h + 1], init.begin() + off[h] + 2 * t->dims[h + 1], 1.f);
+        }
+        HIP_TRY(hipMemcpy(run, init.data(), (size_t)total * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(g, 0, (size_t)total * 4));
+        HIP_TRY(hipMemset(m, 0, (size_t)total * 4));
+        HIP_TRY(hipMemset(v, 0, (size_t)total * 4));
+        HIP_TRY(hipMemset(stat, 0, (size_t)total * 4));
+        // the bias of a normalised layer cancels: its gradient is zero from here on (no colsum launch writes it)
+        for (int h = 0; h < H; ++h) HIP_TRY(hipMemset(t->gb[h], 0, (size_t)t->dims[h + 1] * 4));
+    }
+    t->bn_p = std::move(p); t->bn_g = std::move(g); t->bn_m = std::move(m); t->bn_v = std::move(v);
+    t->bn_run = std::move(run); t->bn_stat = std::move(stat);
+    t->fW = std::move(fW); t->fb = std::move(fb);
+    t->Zbuf.clear();
+    t->Zbuf.resize(t->L + 1);
+    t->bn_off = std::move(off);
+    t->bn_total = total;
+    t->bn_eps = eps;
+    t->bn_mom = momentum;
+    t->bn = true;
+    t->fold_stale = true;
+    return MMC_OK;
+}
+
+extern "C" int mmc_trainer_batch_norm_state(mmc_trainer* t, int set, float* const* gamma, float* const* beta, float* const* running_mean,
+                                            float* const* running_var, float* const* adam_m_gamma, float* const* adam_v_gamma,
+                                            float* const* adam_m_beta, float* const* adam_v_beta)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!gamma || !beta || !running_mean || !running_var || !adam_m_gamma || !adam_v_gamma || !adam_m_beta || !adam_v_beta)
+        return mmc_fail(MMC_ERR_ARG, "NULL argument");
+    if (!t->bn) return mmc_fail(MMC_ERR_ARG, "the trainer has no batch normalisation (mmc_trainer_set_batch_norm)");
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipDeviceSynchronize());
+    for (int h = 0; h < t->L - 1; ++h) {
+        const size_t nb = (size_t)t->dims[h + 1] * 4;
+        float* host[8] = {gamma[h], beta[h], running_mean[h], running_var[h], adam_m_gamma[h], adam_m_beta[h], adam_v_gamma[h], adam_v_beta[h]};
+        float* dev[8] = {t->bn_ptr(t->bn_p, h, 0), t->bn_ptr(t->bn_p, h, 1), t->bn_ptr(t->bn_run, h, 0), t->bn_ptr(t->bn_run, h, 1),
+                         t->bn_ptr(t->bn_m, h, 0), t->bn_ptr(t->bn_m, h, 1), t->bn_ptr(t->bn_v, h, 0), t->bn_ptr(t->bn_v, h, 1)};
+        for (int a = 0; a < 8; ++a) {
+            if (!host[a]) return mmc_fail(MMC_ERR_ARG, "NULL array for hidden layer %d", h);
+            if (set) HIP_TRY(hipMemcpy(dev[a], host[a], nb, hipMemcpyHostToDevice));
+            else HIP_TRY(hipMemcpy(host[a], dev[a], nb, hipMemcpyDeviceToHost));
+        }
+    }
+    if (set) t->fold_stale = true;
+    return MMC_OK;
+}
+
+// W' / b' of the hidden layers from the current gamma, beta and running statistics, on `st`; nothing when the fold is current
+static int trainer_refresh_fold(mmc_trainer* t, hipStream_t st)
+{
+    if (!t->bn || !t->fold_stale) return 0;
+    const int H = t->L - 1;
+    if (H > 0) {
+        BnFoldGroup g;
+        int nmax = 0;
+        for (int h = 0; h < H; ++h) {
+            g.d[h] = BnFoldDesc{t->W[h], t->b[h], t->bn_ptr(t->bn_p, h, 0), t->bn_ptr(t->bn_p, h, 1), t->bn_ptr(t->bn_run, h, 0),
+                                t->bn_ptr(t->bn_run, h, 1), t->fW[h], t->fb[h], t->dims[h + 1], t->dims[h], (float)t->bn_eps};
+            nmax = std::max(nmax, t->dims[h + 1]);
+        }
+        hipLaunchKernelGGL(bn_fold_kernel, dim3(nmax, 1, H), dim3(256), 0, st, g);
+        HIP_TRY(hipGetLastError());
+    }
+    t->fold_stale = false;
+    return 0;
+}
+
+extern "C" int mmc_trainer_folded_params(mmc_trainer* t, float* const* W, float* const* b)
+{
+    if (!t || !W || !b) return mmc_fail(MMC_ERR_ARG, "NULL argument");
+    if (!t->bn) return mmc_trainer_get_params(t, W, b);
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (int r = trainer_refresh_fold(t, nullptr)) return r;
+    HIP_TRY(hipDeviceSynchronize());
+    for (int l = 0; l < t->L; ++l) {
+        const bool folded = l < t->L - 1;
+        HIP_TRY(hipMemcpy(W[l], folded ? t->fW[l].p : t->W[l].p, (size_t)t->dims[l + 1] * t->dims[l] * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(b[l], folded ? t->fb[l].p : t->b[l].p, (size_t)t->dims[l + 1] * 4, hipMemcpyDeviceToHost));
+    }
+    return MMC_OK;
+}
+
+// A mini-batch of one row has no variance: a pass of a normalised trainer whose mini-batch, or whose last one, holds fewer than two
+// rows is refused where minibatch_wsums refuses, before anything is uploaded or launched.
+static int check_bn_minibatches(const char* who, const mmc_trainer* t, int64_t n, int mb)
+{
+    if (!t->bn) return 0;
+    const int64_t last = n - (n - 1) / mb * mb;
+    if (mb < 2 || last < 2)
+        return mmc_fail(MMC_ERR_ARG, "%sbatch normalisation needs at least 2 rows in every mini-batch: %lld rows in mini-batches of %d leave one of %lld",
+                        who, (long long)n, mb, (long long)(mb < 2 ? mb : last));
+    return 0;
+}
+
 static int trainer_reserve(mmc_trainer* t, int64_t n, int mb, int steps)
 {
     int r;
+    if (t->bn)
+        for (int l = 1; l < t->L; ++l)
+            if ((r = t->Zbuf[l].reserve((int64_t)mb * t->dims[l]))) return r;
     if (t->max_norm > 0.0) {
         if (steps > t->gnorm.cap) t->gnorm_steps = 0;   // (the norms of the last pass go with the old block)
         if ((r = t->gnorm.reserve(steps))) return r;
@@ -1579,7 +1932,8 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
     }
     for (int l = 0; l < Lmax; ++l) {
         GemmDropGroup g;
-        int k = 0, tm = 0, tn = 0;
+        BnFwdGroup gn;
+        int k = 0, tm = 0, tn = 0, kn = 0, nn = 0;
         bool drops = false;
         for (int i = 0; i < cnt; ++i) {
             const mmc_trainer* t = act[i].t;
@@ -1590,6 +1944,16 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
                 g.d[k].epi = TEPI_BIAS_RELU_DROP;
                 g.r[k] = drop_mask(t, l + 1);
                 drops = true;
+            }
+            if (t->bn && l < t->L - 1) {   // a normalised layer: Z = H W^T + b to a buffer of its own, bn_forward_kernel makes H(l+1)
+                g.d[k].C = t->Zbuf[l + 1];
+                g.d[k].epi = TEPI_BIAS;
+                const int no = t->dims[l + 1], mb = act[i].cur;
+                gn.d[kn++] = BnFwdDesc{t->Zbuf[l + 1], t->bn_ptr(t->bn_p, l, 0), t->bn_ptr(t->bn_p, l, 1), t->H[l + 1],
+                                       t->bn_ptr(t->bn_stat, l, 0), t->bn_ptr(t->bn_stat, l, 1), t->bn_ptr(t->bn_run, l, 0),
+                                       t->bn_ptr(t->bn_run, l, 1), nullptr, mb, no, (float)t->bn_eps, (float)t->bn_mom,
+                                       (float)(1.0 - t->bn_mom), (float)((double)mb / ((double)mb - 1.0))};
+                nn = std::max(nn, no);
             }
             tm = std::max(tm, (g.d[k].M + 63) / 64);
             tn = std::max(tn, (g.d[k].N + 63) / 64);
@@ -1603,6 +1967,7 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
             std::copy(g.d, g.d + k, plain.d);
             T_K((launch_tgemm<false, true, TEPI_BIAS_RELU, TEPI_BIAS>(plain, k, st)));
         }
+        if (kn) hipLaunchKernelGGL(bn_forward_kernel, dim3((nn + 63) / 64, 1, kn), dim3(256), 0, st, gn);
     }
     {
         CeGroup g;
@@ -1670,16 +2035,24 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
     for (int l = Lmax - 1; l >= 0; --l) {
         GemmGroup gw, gz;
         ColsumGroup gc;
-        int k = 0, kz = 0, nmax = 0;
+        BnBwdGroup gn;
+        int k = 0, kz = 0, nmax = 0, kc = 0, kn = 0, nn = 0;
         bool drops = false;
         for (int i = 0; i < cnt; ++i) {
             const mmc_trainer* t = act[i].t;
             if (l >= t->L) continue;
             const int no = t->dims[l + 1], ni = t->dims[l], mb = act[i].cur;
             gw.d[k] = GemmDesc{t->dZ[l + 1], t->H[l], t->gW[l], t->W[l], no, ni, mb, TEPI_L2, (float)(t->alpha / (double)mb)};
-            gc.d[k] = ColsumDesc{t->dZ[l + 1], t->gb[l], mb, no};
             ++k;
-            nmax = std::max(nmax, no);
+            if (!(t->bn && l < t->L - 1)) {   // the bias of a normalised layer is frozen: gb[l] stays the zeros it was filled with
+                gc.d[kc++] = ColsumDesc{t->dZ[l + 1], t->gb[l], mb, no};
+                nmax = std::max(nmax, no);
+            }
+            if (t->bn && l > 0) {   // dZ[l] is dA of hidden layer l - 1 once this iteration's mask launch has run: make it dZ in place
+                gn.d[kn++] = BnBwdDesc{t->dZ[l], t->Zbuf[l], t->bn_ptr(t->bn_stat, l - 1, 0), t->bn_ptr(t->bn_stat, l - 1, 1),
+                                       t->bn_ptr(t->bn_p, l - 1, 0), t->bn_ptr(t->bn_g, l - 1, 0), t->bn_ptr(t->bn_g, l - 1, 1), mb, ni};
+                nn = std::max(nn, ni);
+            }
             if (l > 0) {
                 gz.d[kz] = GemmDesc{t->dZ[l + 1], t->W[l], t->dZ[l], t->H[l], mb, ni, no, TEPI_MASK, 0.f};
                 if (t->thresh_hidden) {   // H(l) was dropped in the forward: the kept elements carry the scale back
@@ -1691,7 +2064,7 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
             }
         }
         T_K((launch_tgemm<true, false, TEPI_L2, TEPI_L2>(gw, k, st)));
-        hipLaunchKernelGGL(colsum_kernel, dim3((nmax + 255) / 256, 1, k), dim3(256), 0, st, gc);
+        if (kc) hipLaunchKernelGGL(colsum_kernel, dim3((nmax + 255) / 256, 1, kc), dim3(256), 0, st, gc);
         if (kz && drops) {
             int tm = 0, tn = 0;
             for (int i = 0; i < kz; ++i) {
@@ -1703,6 +2076,7 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
         } else if (kz) {
             T_K((launch_tgemm<false, false, TEPI_MASK, TEPI_MASK>(gz, kz, st)));
         }
+        if (kn) hipLaunchKernelGGL(bn_backward_kernel, dim3((nn + 63) / 64, 1, kn), dim3(256), 0, st, gn);
     }
     // gradient clipping: the clipping members' norm over every gW[l] / gb[l] (the L2 term is in gW), their coefficient to device
     // memory; the Adam stage reads it there, so nothing waits on the host
@@ -1723,11 +2097,23 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
             hipLaunchKernelGGL(sumsq_kernel, dim3(256, 1, k), dim3(256), 0, st, gw);
             hipLaunchKernelGGL(sumsq_kernel, dim3(256, 1, k), dim3(256), 0, st, gb);
         }
+        {   // the normalised members' g_gamma / g_beta of every hidden layer: one more tensor, its partials after the layers'
+            SumsqGroup gn;
+            int kn = 0;
+            for (int i = 0; i < cnt; ++i) {
+                const mmc_trainer* t = act[i].t;
+                if (t->max_norm > 0.0 && t->bn && t->bn_total)
+                    gn.d[kn++] = SumsqDesc{t->bn_g, t->gpartials + 256 * (2 * t->L), (size_t)t->bn_total};
+            }
+            if (kn) hipLaunchKernelGGL(sumsq_kernel, dim3(256, 1, kn), dim3(256), 0, st, gn);
+        }
         GnormGroup g;
         int k = 0;
         for (int i = 0; i < cnt; ++i) {
             const mmc_trainer* t = act[i].t;
-            if (t->max_norm > 0.0) g.d[k++] = GnormDesc{t->gpartials, t->coef, t->gnorm + act[i].slot, 2 * 256 * t->L, (float)t->max_norm};
+            if (t->max_norm > 0.0)
+                g.d[k++] = GnormDesc{t->gpartials, t->coef, t->gnorm + act[i].slot, 256 * (2 * t->L + (t->bn && t->bn_total ? 1 : 0)),
+                                     (float)t->max_norm};
         }
         hipLaunchKernelGGL(gnorm_finalize_kernel, dim3(1, 1, k), dim3(256), 0, st, g);
     }
@@ -1777,6 +2163,29 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
             hipLaunchKernelGGL(adam_opt_kernel, dim3((unsigned)((owmax + 255) / 256), 1, ko), dim3(256), 0, st, ow);
             hipLaunchKernelGGL(adam_opt_kernel, dim3((unsigned)((obmax + 255) / 256), 1, ko), dim3(256), 0, st, ob);
         }
+    }
+    {   // gamma and beta of the normalised members, every hidden layer at once: further descriptors of the same two kernels
+        AdamGroup gn;
+        AdamOptGroup on;
+        int k = 0, ko = 0;
+        size_t nmax = 0, onmax = 0;
+        for (int i = 0; i < cnt; ++i) {
+            mmc_trainer* t = act[i].t;
+            if (!t->bn) continue;
+            t->fold_stale = true;
+            if (!t->bn_total) continue;
+            const size_t n = (size_t)t->bn_total;
+            const float om1 = (float)(1.0 - t->beta1), om2 = (float)(1.0 - t->beta2), b2f = (float)t->beta2, epsf = (float)t->eps;
+            if (t->max_norm > 0.0) {
+                on.d[ko++] = AdamOptDesc{t->bn_p, t->bn_g, t->bn_m, t->bn_v, n, om1, b2f, om2, epsf, step_size[i], bc2_sqrt[i], t->coef, nullptr, 0.f};
+                onmax = std::max(onmax, n);
+            } else {
+                gn.d[k++] = AdamDesc{t->bn_p, t->bn_g, t->bn_m, t->bn_v, n, om1, b2f, om2, epsf, step_size[i], bc2_sqrt[i]};
+                nmax = std::max(nmax, n);
+            }
+        }
+        if (k) hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((nmax + 255) / 256), 1, k), dim3(256), 0, st, gn);
+        if (ko) hipLaunchKernelGGL(adam_opt_kernel, dim3((unsigned)((onmax + 255) / 256), 1, ko), dim3(256), 0, st, on);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mmc_fail(MMC_ERR_HIP, "trainer step launch failed: %s", hipGetErrorString(e));
@@ -1894,8 +2303,9 @@ extern "C" int mmc_trainer_partial_fit_ordered(mmc_trainer* t, const float* X, c
     HIP_TRY(hipSetDevice(t->device));
     const int mb = (int)(batch_size < n ? batch_size : n);
     std::vector<double> wsums;
-    int r = minibatch_wsums("", t, y, order, n, mb, &wsums);
+    int r = check_bn_minibatches("", t, n, mb);
     if (r) return r;
+    if ((r = minibatch_wsums("", t, y, order, n, mb, &wsums))) return r;
     const int steps = (int)wsums.size();
     if ((r = trainer_reserve(t, n, mb, steps))) return r;
     if (order) {
@@ -2065,6 +2475,7 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
         if (grouped) std::snprintf(who[m], sizeof who[m], "member %d: ", m);
         if ((r = check_set_pass(who[m], trainers[m], fs, visit[m], n[m], batch_size[m]))) return r;
         if ((r = check_mix_plan(who[m], fs, partner ? partner[m] : nullptr, lam ? lam[m] : nullptr, n[m], batch_size[m]))) return r;
+        if ((r = check_bn_minibatches(who[m], trainers[m], n[m], (int)(batch_size[m] < n[m] ? batch_size[m] : n[m])))) return r;
         const bool weighted = (row_weight && row_weight[m]) || (row_group && row_group[m]);
         if (weighted && partner && partner[m]) return mmc_fail(MMC_ERR_ARG, "%sa mixed pass takes no row weights or groups", who[m]);
         if (partner && partner[m] && trainers[m]->hier)
@@ -2268,12 +2679,17 @@ int trainer_forward_device(mmc_trainer* t, const float* X_dev, int n, hipStream_
     int r = trainer_reserve(t, 0, n, 1);   // activations only: the input is read where it lies
     if (r) return r;
     t->H[0] = const_cast<float*>(X_dev);
+    if ((r = trainer_refresh_fold(t, st))) return r;   // a normalised trainer: W' / b' of its hidden layers, if a step has moved them
     for (int l = 0; l < t->L; ++l) {
         GemmGroup g;
         g.d[0] = forward_desc(t, l, n);
         if (t->eval_which == MMC_WEIGHTS_AVERAGED) {   // mmc_trainer_eval_weights: the same launch on the shadow
             g.d[0].B = t->sW[l];
             g.d[0].aux = t->sb[l];
+        }
+        if (t->bn && l < t->L - 1) {   // and on the folded layers: relu(W' x + b') is the frozen-statistics layer
+            g.d[0].B = t->fW[l];
+            g.d[0].aux = t->fb[l];
         }
         T_K((launch_tgemm<false, true, TEPI_BIAS_RELU, TEPI_BIAS>(g, 1, st)));
     }
@@ -2460,6 +2876,55 @@ extern "C" int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* l
     }
     HIP_TRY(hipMemcpyAsync(dlogits, t->dZ[L], cells * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(row_loss, t->row_loss, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MMC_OK;
+}
+
+// The step's two batch-normalisation kernels on caller arrays (include/mmc.h, "batch normalisation"): bn_forward_kernel on Z with the
+// trainer's current gamma / beta of hidden layer `layer`, then, given dA, bn_backward_kernel.  Everything lives in the trainer's
+// scratch: neither the running statistics nor any other state is read or written.
+extern "C" int mmc_trainer_norm_stage(mmc_trainer* t, int layer, const float* Z, const float* dA, int64_t mb, float* H, float* dZ,
+                                      float* g_gamma, float* g_beta, float* batch_mean, float* batch_var, void* hip_stream)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!t->bn) return mmc_fail(MMC_ERR_ARG, "the trainer has no batch normalisation (mmc_trainer_set_batch_norm)");
+    if (layer < 0 || layer >= t->L - 1) return mmc_fail(MMC_ERR_ARG, "layer = %d is not a hidden layer [0, %d)", layer, t->L - 1);
+    if (!Z || !H || !batch_mean || !batch_var) return mmc_fail(MMC_ERR_ARG, "Z / H / batch_mean / batch_var is NULL");
+    if (dA && (!dZ || !g_gamma || !g_beta)) return mmc_fail(MMC_ERR_ARG, "dA needs dZ, g_gamma and g_beta");
+    if (mb < 2 || mb > kTrainerForwardRows) return mmc_fail(MMC_ERR_ARG, "mb = %lld outside [2, %d]", (long long)mb, kTrainerForwardRows);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipSetDevice(t->device));
+    const int M = (int)mb, N = t->dims[layer + 1];
+    const size_t cells = (size_t)M * N;
+    void* sc = nullptr;
+    if (int r = trainer_scratch(t, (3 * cells + 5 * (size_t)N) * 4, &sc)) return r;
+    float* Zd = static_cast<float*>(sc);
+    float* Ad = Zd + cells;
+    float* Hd = Ad + cells;
+    float* mud = Hd + cells;
+    float* rsd = mud + N;
+    float* vd = rsd + N;
+    float* ggd = vd + N;
+    float* gbd = ggd + N;
+    HIP_TRY(hipMemcpyAsync(Zd, Z, cells * 4, hipMemcpyHostToDevice, st));
+    BnFwdGroup gf;
+    gf.d[0] = BnFwdDesc{Zd, t->bn_ptr(t->bn_p, layer, 0), t->bn_ptr(t->bn_p, layer, 1), Hd, mud, rsd, nullptr, nullptr, vd, M, N,
+                        (float)t->bn_eps, (float)t->bn_mom, (float)(1.0 - t->bn_mom), (float)((double)M / ((double)M - 1.0))};
+    hipLaunchKernelGGL(bn_forward_kernel, dim3((N + 63) / 64), dim3(256), 0, st, gf);
+    HIP_TRY(hipGetLastError());
+    if (dA) {
+        HIP_TRY(hipMemcpyAsync(Ad, dA, cells * 4, hipMemcpyHostToDevice, st));
+        BnBwdGroup gb;
+        gb.d[0] = BnBwdDesc{Ad, Zd, mud, rsd, t->bn_ptr(t->bn_p, layer, 0), ggd, gbd, M, N};
+        hipLaunchKernelGGL(bn_backward_kernel, dim3((N + 63) / 64), dim3(256), 0, st, gb);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(dZ, Ad, cells * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(g_gamma, ggd, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(g_beta, gbd, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(H, Hd, cells * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(batch_mean, mud, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(batch_var, vd, (size_t)N * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return MMC_OK;
 }

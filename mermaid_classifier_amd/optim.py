@@ -7,6 +7,10 @@ cosine kind agrees with the library to a relative 1e-15, not to the bit; code th
 ``clip_coefficient`` is the fp32 arithmetic of ``gnorm_finalize_kernel`` on a given norm: what a step multiplies its gradient by.
 
 ``check_optimizer_options`` holds the argument checks that ``TorchMLPClassifier`` makes at construction; they mirror the C checks.
+
+``fold_batch_norm`` is the host mirror of include/mmc.h, "batch normalisation": the Linear / ReLU stack that a normalised head is
+with its statistics frozen (``bn_fold_kernel``'s definition, in the dtype of its inputs); ``check_batch_norm`` the argument checks
+of ``mmc_trainer_set_batch_norm``.
 """
 
 from __future__ import annotations
@@ -17,7 +21,7 @@ import numpy as np
 
 LR_KINDS = {"constant": 0, "linear": 1, "cosine": 2}   # the values of MMC_LR_CONSTANT / _LINEAR / _COSINE
 
-__all__ = ["LR_KINDS", "lr_at", "clip_coefficient", "check_optimizer_options", "steps_per_epoch"]
+__all__ = ["LR_KINDS", "lr_at", "clip_coefficient", "check_optimizer_options", "steps_per_epoch", "fold_batch_norm", "check_batch_norm"]
 
 
 def _is_number(v) -> bool:
@@ -88,3 +92,40 @@ def steps_per_epoch(batches, batch_size) -> int:
         mb = min(200, n) if batch_size == "auto" else min(int(batch_size), n)
         total += -(-n // mb)
     return total
+
+
+def check_batch_norm(batch_norm, batch_norm_eps, batch_norm_momentum) -> None:
+    """``ValueError`` for what ``mmc_trainer_set_batch_norm`` would reject: ``batch_norm`` a bool, ``batch_norm_eps`` > 0 and finite (in
+    float32 too), ``batch_norm_momentum`` in (0, 1]."""
+    if not isinstance(batch_norm, (bool, np.bool_)):
+        raise ValueError(f"batch_norm must be a bool, got {batch_norm!r}.")
+    ok = _is_number(batch_norm_eps) and float(batch_norm_eps) > 0.0 and math.isfinite(float(batch_norm_eps))
+    ok = ok and float(np.float32(batch_norm_eps)) > 0.0
+    if not ok:
+        raise ValueError(f"batch_norm_eps must be a positive finite number (in float32 too), got {batch_norm_eps!r}.")
+    if not _is_number(batch_norm_momentum) or not 0.0 < float(batch_norm_momentum) <= 1.0:
+        raise ValueError(f"batch_norm_momentum must lie in (0, 1], got {batch_norm_momentum!r}.")
+
+
+def fold_batch_norm(weights, biases, gamma, beta, mean, var, eps):
+    """The plain ``Linear -> ReLU -> ... -> Linear`` stack that equals ``Linear -> BatchNorm1d(eval) -> ReLU -> ... -> Linear``:
+    for hidden layer l, ``s = gamma / sqrt(var + eps)``, ``W' = s[:, None] * W``, ``b' = beta + s * (b - mean)``; the last layer is
+    returned as it is.  ``weights`` / ``biases`` hold every layer, the other four one array per hidden layer.  Computed in the dtype
+    of the inputs (float32 in: ``bn_fold_kernel``'s operations, one rounding each; float64 in: the definition).  -> (weights, biases)"""
+    weights, biases = [np.asarray(w) for w in weights], [np.asarray(b) for b in biases]
+    hidden = len(weights) - 1
+    if not (len(biases) == hidden + 1 and len(gamma) == len(beta) == len(mean) == len(var) == hidden):
+        raise ValueError(f"{hidden + 1} layers need {hidden} arrays each of gamma, beta, mean and var.")
+    ws, bs = [], []
+    for l in range(hidden):
+        w, b = weights[l], biases[l]
+        dt = w.dtype.type
+        g, be, mu, v = (np.asarray(a, dtype=w.dtype) for a in (gamma[l], beta[l], mean[l], var[l]))
+        if not (g.shape == be.shape == mu.shape == v.shape == b.shape == (w.shape[0],)):
+            raise ValueError(f"hidden layer {l}: gamma, beta, mean, var and the bias must each have {w.shape[0]} entries.")
+        s = g / np.sqrt(v + dt(eps))
+        ws.append(s[:, None] * w)
+        bs.append(be + s * (b - mu))
+    ws.append(weights[-1].copy())
+    bs.append(biases[-1].copy())
+    return ws, bs

@@ -154,7 +154,8 @@ class SweepConfig:
     only; arrays indexed by row of the train set) go to every pass of this member, ``group_dro_eta`` / ``n_groups`` to its classifier:
     one sweep can hold an ERM member, a group-balanced one (``group_dro_eta=0``) and DRO members side by side.  ``class_levels`` /
     ``level_weights`` / ``soft_targets`` (keyword only) are the classifier's taxonomy-aware loss: flat, level-weighted and soft-label
-    heads can train side by side."""
+    heads can train side by side.  ``batch_norm`` / ``batch_norm_eps`` / ``batch_norm_momentum`` (keyword only) are the classifier's batch
+    normalisation (``mmc_trainer_set_batch_norm``): plain and normalised heads, say at ``1e-4`` and ``1e-3``, can train side by side."""
     hidden_layer_sizes: Tuple[int, ...] = (500, 300, 100)
     learning_rate_init: float = 1e-4
     alpha: float = 1e-4
@@ -188,6 +189,10 @@ class SweepConfig:
     class_levels: Optional[dict] = field(default=None, kw_only=True)
     level_weights: Optional[Sequence[float]] = field(default=None, kw_only=True)
     soft_targets: Optional[dict] = field(default=None, kw_only=True)
+    # the classifier's batch normalisation (mmc_trainer_set_batch_norm): keyword only, as in its constructor
+    batch_norm: bool = field(default=False, kw_only=True)
+    batch_norm_eps: float = field(default=1e-5, kw_only=True)
+    batch_norm_momentum: float = field(default=0.1, kw_only=True)
     batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None
     label_smoothing: float = 0.0
     focal_gamma: float = 0.0
@@ -204,7 +209,8 @@ class SweepConfig:
                                   lr_schedule=self.lr_schedule, warmup_steps=self.warmup_steps, schedule_steps=self.schedule_steps,
                                   final_lr_ratio=self.final_lr_ratio, max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay,
                                   group_dro_eta=self.group_dro_eta, n_groups=self.n_groups, class_levels=self.class_levels,
-                                  level_weights=self.level_weights, soft_targets=self.soft_targets)
+                                  level_weights=self.level_weights, soft_targets=self.soft_targets, batch_norm=self.batch_norm,
+                                  batch_norm_eps=self.batch_norm_eps, batch_norm_momentum=self.batch_norm_momentum)
 
 
 def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[Any]]],

@@ -28,7 +28,8 @@ options -- ``lr_schedule`` / ``warmup_steps`` / ``schedule_steps`` / ``final_lr_
 ``_apply_optimizer_options``, ``raw_parameters`` / ``averaged_parameters`` / ``use_weights``, ``grad_norms_``
 (``mmc_trainer_set_lr_schedule``, ``mmc_trainer_set_grad_clip``, ``mmc_trainer_set_ema``) -- again off by default; and the
 taxonomy-aware loss -- ``class_levels`` / ``level_weights`` / ``soft_targets``, ``_build_hierarchy_arrays``
-(``mmc_trainer_set_hierarchy``) -- off by default too.
+(``mmc_trainer_set_hierarchy``) -- off by default too; and batch normalisation -- ``batch_norm`` / ``batch_norm_eps`` /
+``batch_norm_momentum``, ``batch_norm_state`` (``mmc_trainer_set_batch_norm``, ``mmc_trainer_folded_params``) -- off by default as well.
 """
 
 from __future__ import annotations
@@ -41,7 +42,7 @@ from typing import Any, List
 import numpy as np
 
 from . import _lib
-from .optim import LR_KINDS, check_optimizer_options
+from .optim import LR_KINDS, check_batch_norm, check_optimizer_options
 from .backbone import _current_stream_ptr, _device_index
 
 _EXPECTED_FP_DRIFT_TOL = 1e-4   # torch_classifier.py:45-50
@@ -161,7 +162,14 @@ class TorchMLPClassifier:
     node); ``level_weights``, L floats >= 0; ``soft_targets``, a dict from label to ``{label: mass}`` (a missing entry is 0; every row
     sums to 1), which replaces the one-hot base term and cannot be combined with ``label_smoothing`` / ``focal_gamma``.
     ``taxonomy.hierarchy_levels`` and ``taxonomy.soft_labels`` make the arrays.  Resolved in ``classes_`` order when the trainer is
-    created; training alone reads them, and ``mixup_alpha > 0`` cannot be combined with them."""
+    created; training alone reads them, and ``mixup_alpha > 0`` cannot be combined with them.
+
+    Three more, keyword only, are batch normalisation (include/mmc.h, "batch normalisation"): ``batch_norm=True`` puts
+    ``BatchNorm1d(eps=batch_norm_eps, momentum=batch_norm_momentum)`` between every hidden ``Linear`` and its ``ReLU`` while training.
+    Evaluation reads the stack with the running statistics folded in: ``predict_proba``, ``parameters()`` and everything built on them
+    (``_module``, ``calibration.evaluate`` / ``calibrate`` / ``export_artifact``, early stopping) see a plain ``Linear -> ReLU`` head;
+    ``raw_parameters()`` returns the training weights and ``batch_norm_state()`` gamma, beta and the running statistics.  It cannot be
+    combined with ``dropout > 0`` or ``ema_decay > 0`` (``input_dropout`` composes), and every mini-batch needs at least 2 rows."""
 
     _estimator_type = "classifier"
 
@@ -174,7 +182,8 @@ class TorchMLPClassifier:
                  regularizer_seed: int | None = None, lr_schedule: str = "constant", warmup_steps: int = 0,
                  schedule_steps: int | None = None, final_lr_ratio: float = 0.0, max_grad_norm: float | None = None,
                  ema_decay: float = 0.0, group_dro_eta: float = 0.0, n_groups: int | None = None,
-                 class_levels: dict | None = None, level_weights: Sequence[float] | None = None, soft_targets: dict | None = None):
+                 class_levels: dict | None = None, level_weights: Sequence[float] | None = None, soft_targets: dict | None = None,
+                 batch_norm: bool = False, batch_norm_eps: float = 1e-5, batch_norm_momentum: float = 0.1):
         if activation != "relu":
             raise ValueError(f"TorchMLPClassifier only supports activation='relu', got {activation!r}.")
         if solver != "adam":
@@ -183,6 +192,7 @@ class TorchMLPClassifier:
         _check_regularizers(dropout, input_dropout, mixup_alpha, regularizer_seed)
         check_optimizer_options(lr_schedule, warmup_steps, schedule_steps, final_lr_ratio, max_grad_norm, ema_decay)
         _check_group_dro(group_dro_eta, n_groups)
+        check_batch_norm(batch_norm, batch_norm_eps, batch_norm_momentum)
         self.hidden_layer_sizes = tuple(hidden_layer_sizes)
         self.activation = activation
         self.solver = solver
@@ -216,6 +226,9 @@ class TorchMLPClassifier:
         self.class_levels = class_levels
         self.level_weights = level_weights
         self.soft_targets = soft_targets
+        self.batch_norm = batch_norm
+        self.batch_norm_eps = batch_norm_eps
+        self.batch_norm_momentum = batch_norm_momentum
 
     # ---- host bookkeeping, restated from the reference ------------------------------------------------------------
     def _resolve_batch_size(self, n_samples: int) -> int:
@@ -361,6 +374,9 @@ class TorchMLPClassifier:
                 _lib.check(lib.mmc_trainer_set_dropout(self._h, float(self.input_dropout), float(self.dropout),
                                                        self._regularizer_seed_value()))
             self._apply_optimizer_options()
+            if self._normalises():   # after dropout and the averaged weights: the second setter refuses the combination
+                check_batch_norm(self.batch_norm, self.batch_norm_eps, self.batch_norm_momentum)
+                _lib.check(lib.mmc_trainer_set_batch_norm(self._h, 1, float(self.batch_norm_eps), float(self.batch_norm_momentum)))
             if getattr(self, "n_groups", None) is not None:
                 _check_group_dro(self.group_dro_eta, self.n_groups)
                 _lib.check(lib.mmc_trainer_set_group_dro(self._h, int(self.n_groups), float(self.group_dro_eta)))
@@ -389,6 +405,9 @@ class TorchMLPClassifier:
 
     def _averages(self) -> bool:
         return float(getattr(self, "ema_decay", 0.0)) != 0.0
+
+    def _normalises(self) -> bool:
+        return bool(getattr(self, "batch_norm", False))
 
     def use_weights(self, which: str) -> "TorchMLPClassifier":
         """What evaluation reads from now on: "raw", the training weights, or "averaged" (``ema_decay > 0`` only; its default)."""
@@ -624,7 +643,33 @@ class TorchMLPClassifier:
         evaluation reads: the averaged ones of a classifier with ``ema_decay > 0`` (unless ``use_weights("raw")``), else the raw ones."""
         if self._averages() and getattr(self, "_eval_weights", "averaged") == "averaged":
             return self.averaged_parameters()
+        if self._normalises():
+            return self.folded_parameters()
         return self.raw_parameters()
+
+    def folded_parameters(self):
+        """-> (weights, biases) of the stack with batch normalisation folded in (``mmc_trainer_folded_params``): what evaluation reads.
+        Of a classifier without ``batch_norm``: ``raw_parameters()``."""
+        if not self._fitted():
+            raise RuntimeError("TorchMLPClassifier is not fitted.")
+        ws = [np.empty((o, i), np.float32) for i, o in zip(self._dims[:-1], self._dims[1:])]
+        bs = [np.empty((o,), np.float32) for o in self._dims[1:]]
+        _lib.check(_lib.lib().mmc_trainer_folded_params(self._h, _ptr_array(ws), _ptr_array(bs)))
+        return ws, bs
+
+    def _bn_arrays(self):
+        return [[np.empty((o,), np.float32) for o in self._dims[1:-1]] for _ in range(8)]
+
+    def batch_norm_state(self) -> dict:
+        """-> ``{"gamma", "beta", "running_mean", "running_var"}``, each a list with one float32 array per hidden layer
+        (``batch_norm=True`` only); ``optim.fold_batch_norm(*raw_parameters(), ...)`` of them is ``parameters()``."""
+        if not self._fitted():
+            raise RuntimeError("TorchMLPClassifier is not fitted.")
+        if not self._normalises():
+            raise ValueError("this classifier has no batch normalisation (batch_norm is False).")
+        arrays = self._bn_arrays()
+        _lib.check(_lib.lib().mmc_trainer_batch_norm_state(self._h, 0, *[_ptr_array(a) for a in arrays]))
+        return dict(zip(("gamma", "beta", "running_mean", "running_var"), arrays[:4]))
 
     def raw_parameters(self):
         """-> (weights, biases) that the training steps read and write, whatever evaluation reads."""
@@ -683,6 +728,10 @@ class TorchMLPClassifier:
         out["step"] = int(step.value)
         if self._averages():
             out["ema"] = self.averaged_parameters()
+        if self._normalises():   # gamma, beta, running mean / variance, then the Adam moments of gamma and beta
+            arrays = self._bn_arrays()
+            _lib.check(_lib.lib().mmc_trainer_batch_norm_state(self._h, 0, *[_ptr_array(a) for a in arrays]))
+            out["batch_norm"] = arrays
         return out
 
     def get_params(self, deep: bool = True) -> dict:
@@ -696,7 +745,8 @@ class TorchMLPClassifier:
                 "lr_schedule": self.lr_schedule, "warmup_steps": self.warmup_steps, "schedule_steps": self.schedule_steps,
                 "final_lr_ratio": self.final_lr_ratio, "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay,
                 "group_dro_eta": self.group_dro_eta, "n_groups": self.n_groups, "class_levels": self.class_levels,
-                "level_weights": self.level_weights, "soft_targets": self.soft_targets}
+                "level_weights": self.level_weights, "soft_targets": self.soft_targets, "batch_norm": self.batch_norm,
+                "batch_norm_eps": self.batch_norm_eps, "batch_norm_momentum": self.batch_norm_momentum}
 
     def set_params(self, **params: Any) -> "TorchMLPClassifier":
         for key, value in params.items():
@@ -727,7 +777,9 @@ class TorchMLPClassifier:
                              # ... and one made before group DRO existed without it
                              ("group_dro_eta", 0.0), ("n_groups", None),
                              # ... and one made before the taxonomy-aware loss existed with the flat loss
-                             ("class_levels", None), ("level_weights", None), ("soft_targets", None), ("_hierarchy_arrays", None)):
+                             ("class_levels", None), ("level_weights", None), ("soft_targets", None), ("_hierarchy_arrays", None),
+                             # ... and one made before batch normalisation existed as a plain head
+                             ("batch_norm", False), ("batch_norm_eps", 1e-5), ("batch_norm_momentum", 0.1)):
             self.__dict__.setdefault(key, default)
         self._h = None
         if params is not None:
@@ -740,6 +792,9 @@ class TorchMLPClassifier:
                 if self._averages() and opt.get("ema") is not None:   # without one the shadow stays the parameters just loaded
                     ws, bs = opt["ema"]
                     _lib.check(_lib.lib().mmc_trainer_ema_state(self._h, 1, _ptr_array(ws), _ptr_array(bs)))
+                if self._normalises() and opt.get("batch_norm") is not None:   # without one the statistics start afresh
+                    arrays = [[np.ascontiguousarray(a, dtype=np.float32) for a in group] for group in opt["batch_norm"]]
+                    _lib.check(_lib.lib().mmc_trainer_batch_norm_state(self._h, 1, *[_ptr_array(a) for a in arrays]))
             logq = self.__dict__.get("_group_logq")
             if self.n_groups is not None and logq is not None and len(logq) == int(self.n_groups):   # q continues where it was
                 logq = np.ascontiguousarray(logq, dtype=np.float64)
