@@ -2,8 +2,11 @@
 
     python -m mermaid_classifier_amd.build [--force]
 
-One object per translation unit (the kernels are five .hip files by layer group, plus the trainer, the calibrator, the feature set, the feature transforms, the nearest-neighbour search, logit calibration, the grouped metrics, cover estimation, and the two host units of the C ABI:
-mmc_api.cpp with the backbone schedule and mmc_head.cpp with the calibrated head),
+One object per translation unit (the kernels are five .hip files by layer group, plus the trainer -- trainer.hip with its kernels and
+every launch of them, and its two host units, trainer_options.cpp with the handle and its options and trainer_pass.cpp with the
+passes --, the calibrator, the feature set, the feature transforms, the nearest-neighbour search, logit calibration, the grouped
+metrics, cover estimation, and the two host units of the C ABI: mmc_api.cpp with the backbone schedule and mmc_head.cpp with the
+calibrated head),
 compiled in parallel and only when the source or one of its headers is newer than the object; then one link.  Objects live in
 csrc/_obj/ (git-ignored and gpurun-ignored: only the linked library travels to the GPU box).
 """
@@ -29,7 +32,9 @@ SOURCES = {
     "k_early.hip": KERNEL_HEADERS,
     "k_mid.hip": KERNEL_HEADERS,
     "k_tail.hip": KERNEL_HEADERS,
-    "trainer.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h", "kernels.h", "philox.h"],
+    "trainer.hip": ["../../include/mmc.h", "trainer_state.h", "trainer_internal.h", "device_mem.h", "kernels.h", "philox.h"],
+    "trainer_options.cpp": ["../../include/mmc.h", "trainer_state.h", "trainer_internal.h", "device_mem.h"],
+    "trainer_pass.cpp": ["../../include/mmc.h", "trainer_state.h", "trainer_internal.h", "device_mem.h"],
     "calib.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
     "featureset.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
     "features.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],

@@ -1,5 +1,6 @@
-// trainer_internal.h -- what calib.hip takes from trainer.hip: the eval-mode forward of a trainer's current parameters; and the
-// device-resident feature set (featureset.hip) that trainer.hip and calib.hip read rows and labels from.
+// trainer_internal.h -- what calib.hip takes from the trainer: the eval-mode forward of a trainer's current parameters (trainer.hip)
+// and its scratch and shape (trainer_options.cpp); and the device-resident feature set (featureset.hip) that the trainer's passes
+// and calib.hip read rows and labels from.  The trainer's own units share trainer_state.h.
 // Library-internal; not part of the C ABI (include/mmc.h).
 #pragma once
 #include <hip/hip_runtime.h>
