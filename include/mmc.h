@@ -1082,6 +1082,60 @@ void mmc_dist_destroy(mmc_dist* d);
 int mmc_gather_features(mmc_dist* d, const float* local, int64_t n_local, int dim, const int64_t* counts, float* all,
                         void* hip_stream);
 
+/* ---- head ensembles --------------------------------------------------------------------------
+ * An ensemble is M members, 1 <= M <= MMC_ENSEMBLE_MAX: existing mmc_head handles on one device with the same input_dim and the
+ * same K <= MMC_ENSEMBLE_MAX_CLASSES (their depths and hidden widths are free: a sweep holds different architectures).  The
+ * ensemble borrows the heads -- they must outlive it and stay usable on their own; its activations, logits and staging are its own.
+ * A point is G consecutive rows, 1 <= G <= MMC_VIEWS_MAX, as in mmc_head_topk_views.  Per point and class, in fp32:
+ *   v_{j,g} = the probability mmc_head_predict of member j writes for view row g, bit for bit
+ *   m_j     = (v_{j,0} + ... + v_{j,G-1}) / (float)G      summed left to right in view order (the views definition)
+ *   e       = (m_0 + ... + m_{M-1}) / (float)M            summed left to right in member order
+ * With M = 1, e has the bits of mmc_head_topk_views; with M = 1 and G = 1 those of mmc_head_topk.  The k best classes of e are
+ * chosen as mmc_head_topk chooses them: score descending, equal scores in class order, k distinct classes even for NaN rows.
+ * Per point also MMC_ENSEMBLE_STATS floats, with H(p) = -sum_c p_c log p_c in nats and a class with p_c == 0 adding 0:
+ *   stats[0] = H(e)                    the predictive entropy
+ *   stats[1] = (1/M) sum_j H(m_j)      the expected member entropy
+ *   stats[2] = stats[0] - stats[1]     the mutual information between prediction and member: the members' disagreement.  It is >= 0
+ *                                      in exact arithmetic (Jensen); it is stored as computed and rounding can leave it just below 0
+ * and votes (int32): the members whose own first-maximum class of m_j equals the ensemble's best class.  The entropy sums are
+ * accumulated in double (lane-strided partials, a fixed butterfly, members in order) and rounded to fp32 once; there are no
+ * atomics, so the bits depend on the logits, M, G and K only.  A row with NaN features has NaN stats.
+ * The Linear layers of all members run as one launch per layer index, each output with the bits of the member's own launches; the
+ * mean, the selection and the stats run in one kernel, and nothing rows x K is written unless proba is asked for.
+ * Chunking: internal chunks hold mmc_ensemble_chunk_rows rows -- the largest multiple of G with M x rows inside one head's chunk
+ * of 65536 rows -- so a point is never split; chunking changes no bit.  Flags, streams, the feature buffer and the 4096-patch
+ * chunks of mmc_ensemble_classify_patches behave as in mmc_head_topk_views / mmc_classify_patches_views.
+ * mmc_ensemble_evaluate / _set: the contract of mmc_head_evaluate / mmc_head_evaluate_set on e (G = 1): est, score, rank, p_true per
+ * row, the MMC_EVAL_TOTALS totals, confusion and rank_hist by the same rules (label map, unknown and non-finite rows, integer
+ * atomics: independent of grid and chunking), plus stats and votes per row (host pointers, like the other per-row outputs).
+ * Errors: MMC_ERR_ARG with a message, before anything is launched or written, for a count outside [1, MMC_ENSEMBLE_MAX], a NULL
+ * member, members that differ in K, input_dim or device, K > MMC_ENSEMBLE_MAX_CLASSES, G or k out of range, NULL required pointers,
+ * and whatever mmc_head_evaluate / mmc_head_evaluate_set reject. */
+#define MMC_ENSEMBLE_MAX 16
+#define MMC_ENSEMBLE_MAX_CLASSES 2048
+#define MMC_ENSEMBLE_STATS 3
+typedef struct mmc_ensemble mmc_ensemble;
+int mmc_ensemble_create(mmc_head* const* members, int count, mmc_ensemble** out);
+void mmc_ensemble_destroy(mmc_ensemble* e);
+int mmc_ensemble_size(const mmc_ensemble* e);
+int mmc_ensemble_num_classes(const mmc_ensemble* e);
+int mmc_ensemble_input_dim(const mmc_ensemble* e);
+int mmc_ensemble_chunk_rows(const mmc_ensemble* e, int G);   /* rows per internal chunk, a multiple of G; 0 for a bad argument */
+int mmc_ensemble_topk(mmc_ensemble* e, const float* feats /* (n_points*G) x input_dim, point-major */, int64_t n_points, int G, int k,
+                      int32_t* idx /* n_points x k */, float* scores /* n_points x k */, float* proba /* n_points x K or NULL */,
+                      float* stats /* n_points x MMC_ENSEMBLE_STATS or NULL */, int32_t* votes /* n_points or NULL */,
+                      unsigned flags, void* hip_stream);
+int mmc_ensemble_classify_patches(mmc_backbone* bb, mmc_ensemble* e, const void* patches /* (n_points*G) x 224x224x3 */,
+                                  int64_t n_points, int G, int k, int32_t* idx, float* scores, float* stats /* or NULL */,
+                                  int32_t* votes /* or NULL */, unsigned flags, void* hip_stream);
+int mmc_ensemble_evaluate(mmc_ensemble* e, const float* feats, const int32_t* y, int64_t n, const int32_t* label_map, int n_labels,
+                          int32_t* est, float* score, int32_t* rank, float* p_true, float* stats /* n x MMC_ENSEMBLE_STATS or NULL */,
+                          int32_t* votes /* n or NULL */, int64_t* totals, int64_t* confusion, int64_t* rank_hist, unsigned flags,
+                          void* hip_stream);
+int mmc_ensemble_evaluate_set(mmc_ensemble* e, mmc_featureset* fs, int64_t first, int64_t n, const int32_t* label_map, int n_labels,
+                              int32_t* est, float* score, int32_t* rank, float* p_true, float* stats, int32_t* votes, int64_t* totals,
+                              int64_t* confusion, int64_t* rank_hist, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

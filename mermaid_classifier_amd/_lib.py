@@ -30,6 +30,7 @@ MMC_KNN_MAX_K, MMC_KNN_DOT, MMC_KNN_COSINE, MMC_KNN_L2, MMC_KNN_EXCLUDE_SELF = 3
 MMC_KNN_TILE_ROWS, MMC_KNN_CHUNK_ROWS, MMC_KNN_MAX_SPLITS = 128, 8192, 16
 MMC_LOGITCAL_MAX_CLASSES, MMC_LOGITCAL_BLOCK_ROWS = 128, 1024   # include/mmc.h: logit calibration
 MMC_LOGITCAL_TEMPERATURE, MMC_LOGITCAL_BIAS, MMC_LOGITCAL_VECTOR = 0, 1, 2
+MMC_ENSEMBLE_MAX, MMC_ENSEMBLE_MAX_CLASSES, MMC_ENSEMBLE_STATS = 16, 2048, 3   # include/mmc.h: head ensembles
 
 # every symbol include/mmc.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
@@ -61,6 +62,8 @@ SYMBOLS = [
     "mmc_trainer_set_hierarchy",
     "mmc_trainer_set_batch_norm", "mmc_trainer_batch_norm_state", "mmc_trainer_folded_params", "mmc_trainer_norm_stage",
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
+    "mmc_ensemble_create", "mmc_ensemble_destroy", "mmc_ensemble_size", "mmc_ensemble_num_classes", "mmc_ensemble_input_dim",
+    "mmc_ensemble_chunk_rows", "mmc_ensemble_topk", "mmc_ensemble_classify_patches", "mmc_ensemble_evaluate", "mmc_ensemble_evaluate_set",
 ]
 # include/mmc.h, "optimiser options"
 MMC_LR_CONSTANT, MMC_LR_LINEAR, MMC_LR_COSINE = 0, 1, 2
@@ -311,6 +314,24 @@ def _load() -> C.CDLL:
     lib.mmc_dist_destroy.argtypes = [vp]
     lib.mmc_gather_features.restype = i32
     lib.mmc_gather_features.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    lib.mmc_ensemble_create.restype = i32
+    lib.mmc_ensemble_create.argtypes = [C.POINTER(vp), i32, C.POINTER(vp)]
+    lib.mmc_ensemble_destroy.restype = None
+    lib.mmc_ensemble_destroy.argtypes = [vp]
+    for name in ("mmc_ensemble_size", "mmc_ensemble_num_classes", "mmc_ensemble_input_dim"):
+        getattr(lib, name).restype = i32
+        getattr(lib, name).argtypes = [vp]
+    lib.mmc_ensemble_chunk_rows.restype = i32
+    lib.mmc_ensemble_chunk_rows.argtypes = [vp, i32]
+    lib.mmc_ensemble_topk.restype = i32
+    lib.mmc_ensemble_topk.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, u32, vp]
+    lib.mmc_ensemble_classify_patches.restype = i32
+    lib.mmc_ensemble_classify_patches.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, u32, vp]
+    # the arguments of mmc_head_evaluate(_set) with stats and votes behind p_true
+    lib.mmc_ensemble_evaluate.restype = i32
+    lib.mmc_ensemble_evaluate.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+    lib.mmc_ensemble_evaluate_set.restype = i32
+    lib.mmc_ensemble_evaluate_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     return lib
 
 

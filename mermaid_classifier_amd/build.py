@@ -5,8 +5,8 @@
 One object per translation unit (the kernels are five .hip files by layer group, plus the trainer -- trainer.hip with its kernels and
 every launch of them, and its two host units, trainer_options.cpp with the handle and its options and trainer_pass.cpp with the
 passes --, the calibrator, the feature set, the feature transforms, the nearest-neighbour search, logit calibration, the grouped
-metrics, cover estimation, and the two host units of the C ABI: mmc_api.cpp with the backbone schedule and mmc_head.cpp with the
-calibrated head),
+metrics, cover estimation, and the three host units of the C ABI: mmc_api.cpp with the backbone schedule, mmc_head.cpp with the
+calibrated head and mmc_ensemble.cpp with the head ensembles),
 compiled in parallel and only when the source or one of its headers is newer than the object; then one link.  Objects live in
 csrc/_obj/ (git-ignored and gpurun-ignored: only the linked library travels to the GPU box).
 """
@@ -43,7 +43,8 @@ SOURCES = {
     "metrics.hip": ["kernels.h"],
     "cover.hip": ["kernels.h", "topk_key.h"],
     "mmc_api.cpp": ["kernels.h", "api_internal.h", "device_mem.h", "backbone_pack.h", "../../include/mmc.h"],
-    "mmc_head.cpp": ["kernels.h", "api_internal.h", "trainer_internal.h", "device_mem.h", "../../include/mmc.h"],
+    "mmc_head.cpp": ["kernels.h", "api_internal.h", "head_internal.h", "trainer_internal.h", "device_mem.h", "../../include/mmc.h"],
+    "mmc_ensemble.cpp": ["kernels.h", "api_internal.h", "head_internal.h", "trainer_internal.h", "device_mem.h", "../../include/mmc.h"],
     "mmc_dist.cpp": ["../../include/mmc.h"],
 }
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",

@@ -906,6 +906,74 @@ __global__ __launch_bounds__(256) void mlp_gemm_f32_kernel(const float* __restri
         }
 }
 
+// mlp_gemm_f32_group_kernel: one Linear layer of every member of a head ensemble in one launch (include/mmc.h, "head ensembles").
+// Member blockIdx.z has its own operands and shape (MlpGroupArgs); the grid's y extent is the widest member's, and a workgroup past
+// its member's N leaves.  An output element gets the arithmetic of mlp_gemm_f32_kernel<4, .> above, step for step: the same k order,
+// the same four chains on v_mfma_f32_16x16x4_f32, the same ((a0 + a1) + (a2 + a3)) + bias -- so a member's logits have the bits
+// of its own head's launches.  relu is per member: one member's last layer can sit beside another's hidden layer.
+__global__ __launch_bounds__(256) void mlp_gemm_f32_group_kernel(MlpGroupArgs g)
+{
+    constexpr int NT = 4;
+    const MlpGroupMember& mb = g.m[blockIdx.z];
+    const int K = mb.K, N = mb.N, M = g.M;
+    const int n0 = blockIdx.y * 16 * NT;
+    if (n0 >= N) return;   // (workgroup-uniform)
+    const float* __restrict__ X = mb.X;
+    const float* __restrict__ W = mb.W;
+    const float* __restrict__ bias = mb.bias;
+    float* __restrict__ Y = mb.Y;
+    const bool relu = mb.relu != 0;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = lane & 15, q = lane >> 4;
+    const int row = (blockIdx.x * 4 + wave) * 16 + i;
+    const bool rok = row < M;
+    f4 acc[NT][4];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc[t][s] = (f4){0.f, 0.f, 0.f, 0.f};
+    const int K16 = K & ~15;
+    for (int k0 = 0; k0 < K16; k0 += 16) {
+        f4 xv = {0.f, 0.f, 0.f, 0.f};
+        if (rok) xv = *reinterpret_cast<const f4*>(X + (size_t)row * K + k0 + 4 * q);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int n = n0 + t * 16 + i;
+            f4 wv = {0.f, 0.f, 0.f, 0.f};
+            if (n < N) wv = *reinterpret_cast<const f4*>(W + (size_t)n * K + k0 + 4 * q);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                acc[t][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[s], xv[s], acc[t][s], 0, 0, 0);
+        }
+    }
+    if (K16 < K) {  // K tail: K is padded to a multiple of 4 by mmc_head_create
+        f4 xv = {0.f, 0.f, 0.f, 0.f};
+        const int k = K16 + 4 * q;
+        if (rok && k < K) xv = *reinterpret_cast<const f4*>(X + (size_t)row * K + k);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int n = n0 + t * 16 + i;
+            f4 wv = {0.f, 0.f, 0.f, 0.f};
+            if (n < N && k < K) wv = *reinterpret_cast<const f4*>(W + (size_t)n * K + k);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                acc[t][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[s], xv[s], acc[t][s], 0, 0, 0);
+        }
+    }
+    if (!rok) return;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = n0 + t * 16 + 4 * q + j;
+            if (n < N) {
+                float v = ((acc[t][0][j] + acc[t][1][j]) + (acc[t][2][j] + acc[t][3][j])) + bias[n];
+                if (relu) v = fmaxf(v, 0.f);
+                Y[(size_t)row * N + n] = v;
+            }
+        }
+}
+
 // The calibration arithmetic of CalibratedHead.forward (head.py:75-89), one wave per row, lane l owning classes l, l + 64, ...:
 // softmax -> Platt sigmoid -> row normalise (uniform row when the sum is 0) -> sklearn overshoot clip.  calibrate_kernel and
 // calibrate_topk_kernel are both built from these pieces, so a probability has the same bits whichever of them wrote it.
@@ -1219,6 +1287,231 @@ __global__ __launch_bounds__(256) void calibrate_eval_kernel(const float* __rest
         if (s) atomicAdd(&totals[threadIdx.x], s);
     }
     if (ROW_IN_LDS && rank_hist)
+        for (int c = threadIdx.x; c < K; c += 256)
+            if (hist[c]) atomicAdd(&rank_hist[c], (unsigned long long)hist[c]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Head ensembles (include/mmc.h, "head ensembles"): M members' logits for the same rows lie in one [M][rows][K] buffer.  A point is G
+// consecutive rows.  Per class: v_{j,g} = the probability calibrate_kernel writes for member j's row g (same helpers, same lane
+// order of the row sums), m_j = (v_{j,0} + ... + v_{j,G-1}) / (float)G as mean_topk_kernel forms it, and
+// e = (m_0 + ... + m_{M-1}) / (float)M, both summed left to right in fp32.  M = 1: e = m_0 / 1.0f, the bits of mean_topk_kernel.
+// ensemble_row makes e for one point in a wave: two wave-private LDS rows, mrow for the member's mean and erow for the ensemble's;
+// a lane reads only entries it wrote (classes lane, lane + 64, ...), so there is no barrier.  It also returns the two entropies
+// H(e) and (1/M) sum_j H(m_j), H(p) = -sum_c p_c log p_c with a zero class adding 0: each lane adds its classes' terms in
+// double, a fixed xor butterfly folds the lanes, the members' sums are added in member order -- no atomics, so the bits depend on
+// the logits, M, G and K alone -- and lane j keeps member j's best class (largest topk_key of m_j: the first maximum) for the votes.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum_d(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double entropy_term(float p) { return p == 0.f ? 0.0 : -(double)p * log((double)p); }
+
+__device__ __forceinline__ void ensemble_row(const float* __restrict__ logits, size_t mstride, size_t row0, int Mn, int G, int K,
+                                             const EnsembleCal& cal, int lane, float* mrow, float* erow, bool want_stats, double& h_e,
+                                             double& h_m, int& member_best)
+{
+    const float den = (float)G;
+    h_m = 0.0;
+    member_best = -1;
+    for (int j = 0; j < Mn; ++j) {
+        const float* __restrict__ a = cal.a[j];
+        const float* __restrict__ bcal = cal.b[j];
+        for (int g = 0; g < G; ++g) {
+            const float* x = logits + (size_t)j * mstride + (row0 + g) * K;
+            float mx, se;
+            calib_softmax_stats(x, K, lane, mx, se);
+            float cs = 0.f;
+            for (int c = lane; c < K; c += 64) cs += calib_sigmoid(x[c], mx, se, a[c], bcal[c]);
+            cs = wave_sum_f(cs);
+            for (int c = lane; c < K; c += 64) {
+                const float v = calib_normalise(calib_sigmoid(x[c], mx, se, a[c], bcal[c]), cs, K);
+                mrow[c] = g == 0 ? v : mrow[c] + v;
+            }
+        }
+        unsigned long long best = 0;
+        double h = 0.0;
+        for (int c = lane; c < K; c += 64) {
+            const float m = mrow[c] / den;
+            erow[c] = j == 0 ? m : erow[c] + m;
+            const unsigned long long key = topk_key(m, c);
+            best = key > best ? key : best;
+            if (want_stats) h += entropy_term(m);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_xor(best, o);
+            best = t > best ? t : best;
+        }
+        if (lane == j) member_best = (int)(0xFFFFFFFFu - (unsigned)best);
+        if (want_stats) h_m += wave_sum_d(h);
+    }
+    const float dm = (float)Mn;
+    double h = 0.0;
+    for (int c = lane; c < K; c += 64) {
+        const float e = erow[c] / dm;
+        erow[c] = e;
+        if (want_stats) h += entropy_term(e);
+    }
+    h_e = want_stats ? wave_sum_d(h) : 0.0;
+    h_m /= (double)Mn;
+}
+// what a point keeps of them (lane 0 writes): H(e), the members' mean entropy, their difference -- the mutual information between
+// prediction and member, stored as computed (rounding can leave it a hair below 0) -- each rounded to fp32 once; and the votes:
+// the members whose own best class is the ensemble's
+__device__ __forceinline__ void ensemble_write_stats(float* __restrict__ stats, int32_t* __restrict__ votes, size_t pt, int lane, int Mn,
+                                                     double h_e, double h_m, int member_best, int best_class)
+{
+    const unsigned long long agree = __ballot(lane < Mn && member_best == best_class);
+    if (lane != 0) return;
+    if (stats) {
+        stats[pt * ENSEMBLE_STATS + 0] = (float)h_e;
+        stats[pt * ENSEMBLE_STATS + 1] = (float)h_m;
+        stats[pt * ENSEMBLE_STATS + 2] = (float)(h_e - h_m);
+    }
+    if (votes) votes[pt] = __popcll(agree);
+}
+
+// ensemble_topk_kernel: e of a point, then its k best classes by the rounds of calibrate_topk_kernel.  One wave per point, four
+// points per workgroup, LDS [4][2][K] floats (K <= TOPK_LDS_MAX_K: 64 KB at the limit).  Nothing rows x K is written unless the
+// caller wants the means (proba).
+__global__ __launch_bounds__(256) void ensemble_topk_kernel(const float* __restrict__ logits, int P, int G, int K, int Mn, size_t mstride,
+                                                            EnsembleCal cal, int k,
+                                                            int32_t* __restrict__ idx_out,   // [P][k]
+                                                            float* __restrict__ score_out,   // [P][k]
+                                                            float* __restrict__ proba,       // [P][K] or NULL
+                                                            float* __restrict__ stats,       // [P][ENSEMBLE_STATS] or NULL
+                                                            int32_t* __restrict__ votes)     // [P] or NULL
+{
+    extern __shared__ float ens_rows[];   // [4][2][K]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pt = blockIdx.x * 4 + wave;
+    if (pt >= P) return;
+    float* mrow = ens_rows + (size_t)wave * 2 * K;
+    float* r = mrow + K;
+    double h_e, h_m;
+    int member_best;
+    ensemble_row(logits, mstride, (size_t)pt * G, Mn, G, K, cal, lane, mrow, r, stats != nullptr, h_e, h_m, member_best);
+    unsigned long long cur = 0;   // this lane's largest key not yet selected (calibrate_topk_kernel)
+    for (int c = lane; c < K; c += 64) {
+        const float e = r[c];
+        if (proba) proba[(size_t)pt * K + c] = e;
+        const unsigned long long key = topk_key(e, c);
+        cur = key > cur ? key : cur;
+    }
+    int best_class = 0;
+    for (int j = 0; j < k; ++j) {
+        unsigned long long win = cur;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_xor(win, o);
+            win = t > win ? t : win;
+        }
+        if (j == 0) best_class = (int)(0xFFFFFFFFu - (unsigned)win);
+        if (lane == 0) {
+            idx_out[(size_t)pt * k + j] = (int32_t)(0xFFFFFFFFu - (unsigned)win);
+            score_out[(size_t)pt * k + j] = __uint_as_float((unsigned)(win >> 32));
+        }
+        if (cur == win) {
+            unsigned long long nb = 0;
+            for (int c = lane; c < K; c += 64) {
+                const unsigned long long key = topk_key(r[c], c);
+                nb = (key < win && key > nb) ? key : nb;
+            }
+            cur = nb;
+        }
+    }
+    ensemble_write_stats(stats, votes, (size_t)pt, lane, Mn, h_e, h_m, member_best, best_class);
+}
+
+// ensemble_eval_kernel: e of a row (G = 1), then what calibrate_eval_kernel keeps of it -- est, score, rank, p_true, the five
+// totals, confusion, rank_hist, by the same rules for the label map, unknown and non-finite rows and with the same integer atomics,
+// so the tables depend on neither the grid nor the chunking -- plus the row's entropies and votes.  LDS: [4][2][K] rows, then [K]
+// unsigned rank counts when hist_lds (the launcher sets it while both fit in 64 KB; otherwise rank_hist takes one atomic per row).
+__global__ __launch_bounds__(256) void ensemble_eval_kernel(const float* __restrict__ logits, int M, int K, int Mn, size_t mstride,
+                                                            EnsembleCal cal, const int32_t* __restrict__ y,
+                                                            const int32_t* __restrict__ label_map, int n_labels,
+                                                            int32_t* __restrict__ est_out, float* __restrict__ score_out,   // [M] or NULL
+                                                            int32_t* __restrict__ rank_out, float* __restrict__ ptrue_out,  // [M] or NULL
+                                                            float* __restrict__ stats,                    // [M][ENSEMBLE_STATS] or NULL
+                                                            int32_t* __restrict__ votes,                  // [M] or NULL
+                                                            unsigned long long* __restrict__ totals,      // [EVAL_TOTALS]
+                                                            unsigned long long* __restrict__ confusion,   // [K][K] or NULL
+                                                            unsigned long long* __restrict__ rank_hist,   // [K] or NULL
+                                                            int hist_lds)
+{
+    extern __shared__ float ens_eval_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned* hist = reinterpret_cast<unsigned*>(ens_eval_lds + (size_t)8 * K);
+    if (hist_lds) {
+        for (int c = threadIdx.x; c < K; c += 256) hist[c] = 0;
+        __syncthreads();
+    }
+    float* mrow = ens_eval_lds + (size_t)wave * 2 * K;
+    float* r = mrow + K;
+    unsigned long long tot[EVAL_TOTALS] = {0, 0, 0, 0, 0};   // lane 0's are the wave's
+    for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
+        double h_e, h_m;
+        int member_best;
+        ensemble_row(logits, mstride, (size_t)row, Mn, 1, K, cal, lane, mrow, r, stats != nullptr, h_e, h_m, member_best);
+        unsigned long long best = 0;
+        bool bad = false;
+        for (int c = lane; c < K; c += 64) {
+            const float v = r[c];
+            bad |= !(fabsf(v) <= 3.402823466e+38f);   // NaN or infinite
+            const unsigned long long key = topk_key(v, c);
+            best = key > best ? key : best;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_xor(best, o);
+            best = t > best ? t : best;
+        }
+        bad = __ballot(bad) != 0;
+        const int est = (int)(0xFFFFFFFFu - (unsigned)best);
+        ensemble_write_stats(stats, votes, (size_t)row, lane, Mn, h_e, h_m, member_best, est);
+        int g = y[row];
+        if (label_map) g = (g >= 0 && g < n_labels) ? label_map[g] : -1;
+        if (g < 0 || g >= K) g = -1;
+        int rank = 0;
+        float pt = 0.f;
+        if (g >= 0) {   // (wave-uniform)
+            const int owner = g & 63;
+            pt = __shfl(lane == owner ? r[g] : 0.f, owner);
+            const unsigned long long keyg = topk_key(pt, g);
+            int above = 0;
+            for (int c = lane; c < K; c += 64) above += topk_key(r[c], c) > keyg;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o);
+            rank = 1 + above;
+        }
+        if (lane == 0) {
+            if (est_out) est_out[row] = est;
+            if (score_out) score_out[row] = __uint_as_float((unsigned)(best >> 32));
+            if (rank_out) rank_out[row] = rank;
+            if (ptrue_out) ptrue_out[row] = pt;
+            tot[0] += 1;
+            if (g < 0) tot[2] += 1;
+            else if (bad) tot[3] += 1;
+            else {
+                tot[1] += est == g;
+                tot[4] += (unsigned long long)llrint(-log(fmin(fmax((double)pt, 1e-15), 1.0)) * 4294967296.0);
+                if (confusion) atomicAdd(&confusion[(size_t)g * K + est], 1ull);
+                if (rank_hist) {
+                    if (hist_lds) atomicAdd(&hist[rank - 1], 1u);
+                    else atomicAdd(&rank_hist[rank - 1], 1ull);
+                }
+            }
+        }
+    }
+    if (lane == 0)   // one atomic per wave and touched total (no static LDS: at K = 2048 the rows alone are the 64 KB)
+        for (int i = 0; i < EVAL_TOTALS; ++i)
+            if (tot[i]) atomicAdd(&totals[i], tot[i]);
+    __syncthreads();
+    if (hist_lds && rank_hist)
         for (int c = threadIdx.x; c < K; c += 256)
             if (hist[c]) atomicAdd(&rank_hist[c], (unsigned long long)hist[c]);
 }
@@ -1605,6 +1898,55 @@ int launch_calibrate_eval(const float* logits, int M, int K, const float* a, con
         hipLaunchKernelGGL((calibrate_eval_kernel<false>), grid, dim3(256), 0, st, logits, M, K, a, b, y, label_map, n_labels, est, score,
                            rank, p_true, t, cf, rh, scored, rowbuf);
     }
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_mlp_group(const MlpGroupArgs& g, int members, hipStream_t st)
+{
+    if (members < 1 || members > ENSEMBLE_MAX || g.M < 1) return -18;
+    int nmax = 0;
+    for (int j = 0; j < members; ++j) {
+        const MlpGroupMember& m = g.m[j];
+        if (!m.X || !m.W || !m.bias || !m.Y || m.K < 4 || (m.K & 3) || m.N < 1) return -18;
+        nmax = m.N > nmax ? m.N : nmax;
+    }
+    const dim3 grid((g.M + 63) / 64, (nmax + 63) / 64, members);
+    hipLaunchKernelGGL(mlp_gemm_f32_group_kernel, grid, dim3(256), 0, st, g);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+static int ensemble_check(int P, int K, int Mn, const EnsembleCal& cal)
+{
+    if (P < 1 || K < 1 || K > TOPK_LDS_MAX_K || Mn < 1 || Mn > ENSEMBLE_MAX) return -18;
+    for (int j = 0; j < Mn; ++j)
+        if (!cal.a[j] || !cal.b[j]) return -18;
+    return 0;
+}
+
+int launch_ensemble_topk(const float* logits, int P, int G, int K, int Mn, size_t member_stride, const EnsembleCal& cal, int k,
+                         int32_t* idx, float* scores, float* proba, float* stats, int32_t* votes, hipStream_t st)
+{
+    if (ensemble_check(P, K, Mn, cal) || G < 1 || G > VIEWS_MAX || k < 1 || k > K || !logits || !idx || !scores) return -18;
+    hipLaunchKernelGGL(ensemble_topk_kernel, dim3((P + 3) / 4), dim3(256), (size_t)8 * K * sizeof(float), st, logits, P, G, K, Mn,
+                       member_stride, cal, k, idx, scores, proba, stats, votes);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_ensemble_eval(const float* logits, int M, int K, int Mn, size_t member_stride, const EnsembleCal& cal, const int32_t* y,
+                         const int32_t* label_map, int n_labels, int32_t* est, float* score, int32_t* rank, float* p_true, float* stats,
+                         int32_t* votes, long long* totals, long long* confusion, long long* rank_hist, hipStream_t st)
+{
+    if (ensemble_check(M, K, Mn, cal) || !logits || !y || !totals || (label_map && n_labels < 1)) return -18;
+    const int nb = (M + 3) / 4;
+    const dim3 grid(nb < 2048 ? nb : 2048);   // as calibrate_eval_kernel: the partial totals stay on chip while a workgroup walks rows
+    const int hist_lds = (size_t)9 * K * sizeof(float) <= 65536;   // the rows and the counts inside 64 KB
+    const size_t lds = (size_t)(hist_lds ? 9 : 8) * K * sizeof(float);
+    hipLaunchKernelGGL(ensemble_eval_kernel, grid, dim3(256), lds, st, logits, M, K, Mn, member_stride, cal, y, label_map, n_labels, est,
+                       score, rank, p_true, stats, votes, reinterpret_cast<unsigned long long*>(totals),
+                       reinterpret_cast<unsigned long long*>(confusion), reinterpret_cast<unsigned long long*>(rank_hist), hist_lds);
     LAUNCH_CHECK();
     return 0;
 }

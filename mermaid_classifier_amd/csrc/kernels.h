@@ -280,6 +280,37 @@ int launch_crop(const uint8_t* image, int H, int W, const int32_t* rowcols, int 
 constexpr int VIEWS_MAX = 16;   // view codes 0 .. 15, and at most this many rows per point
 int launch_mean_topk(const float* logits, int P, int G, int K, const float* a, const float* b, int k, int32_t* idx, float* scores,
                      float* proba, float* rowbuf, hipStream_t st);
+// ---- head ensembles (include/mmc.h, "head ensembles") ----
+constexpr int ENSEMBLE_MAX = 16;     // members
+constexpr int ENSEMBLE_MAX_K = 2048; // classes: the two LDS rows per wave of the ensemble kernels
+constexpr int ENSEMBLE_STATS = 3;    // per point: H(e), mean member entropy, their difference
+// one member's Linear layer: Y[M][N] = act(X[M][K] W[N][K]^T + bias), K a multiple of 4 (rows 16-byte aligned), relu 0 / 1
+struct MlpGroupMember {
+    const float* X;
+    const float* W;
+    const float* bias;
+    float* Y;
+    int K, N, relu, pad;
+};
+struct MlpGroupArgs {
+    MlpGroupMember m[ENSEMBLE_MAX];
+    int M;   // rows, the same for every member
+};
+// the layer of members m[0 .. members) in one launch; each output has the bits launch_mlp_layer gives that member alone
+int launch_mlp_group(const MlpGroupArgs& g, int members, hipStream_t st);
+// the members' Platt parameters (K floats each, device)
+struct EnsembleCal {
+    const float* a[ENSEMBLE_MAX];
+    const float* b[ENSEMBLE_MAX];
+};
+// logits: member j's rows at logits + j * member_stride, (P * G) x K each.  Per point the mean over views and members, its k best
+// classes as launch_calibrate_topk chooses them; proba (P x K means), stats (P x ENSEMBLE_STATS) and votes (P) may be NULL
+int launch_ensemble_topk(const float* logits, int P, int G, int K, int Mn, size_t member_stride, const EnsembleCal& cal, int k,
+                         int32_t* idx, float* scores, float* proba, float* stats, int32_t* votes, hipStream_t st);
+// launch_calibrate_eval on the members' mean row (one row per point), plus stats and votes
+int launch_ensemble_eval(const float* logits, int M, int K, int Mn, size_t member_stride, const EnsembleCal& cal, const int32_t* y,
+                         const int32_t* label_map, int n_labels, int32_t* est, float* score, int32_t* rank, float* p_true, float* stats,
+                         int32_t* votes, long long* totals, long long* confusion, long long* rank_hist, hipStream_t st);
 // patch i = view views[i] (masked to 4 bits) of point i (include/mmc.h, "patch views")
 int launch_crop_views(const uint8_t* image, int H, int W, const int32_t* rowcols, const uint8_t* views, int n, uint8_t* out,
                       hipStream_t st);
