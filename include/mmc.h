@@ -1136,6 +1136,87 @@ int mmc_ensemble_evaluate_set(mmc_ensemble* e, mmc_featureset* fs, int64_t first
                               int32_t* est, float* score, int32_t* rank, float* p_true, float* stats, int32_t* votes, int64_t* totals,
                               int64_t* confusion, int64_t* rank_hist, void* hip_stream);
 
+/* ---- distillation: per-row soft targets in the loss stage of resident passes; a head ensemble distilled into one head ---------------
+ * Extends: the loss of TorchMLPClassifier.partial_fit (torch_classifier.py:226-303), whose targets are hard labels, and the soft-label
+ *   form of "taxonomy-aware loss", whose targets are keyed by class (K x K), by targets keyed by row (N x K): the distillation loss of
+ *   Hinton et al. 2015 ("Distilling the knowledge in a neural network").  It lets an mmc_ensemble, which no artifact format carries,
+ *   be trained into one Linear -> ReLU -> ... -> Linear head.  No counterpart in the reference and no measured gain on reef data.  It
+ *   sits in the loss stage alone: forward, backward GEMMs, L2, clipping, EMA, the schedule, dropout, batch normalisation, class
+ *   weights, the logit prior, smoothing and focal modulation (in b_i only), row weights and group DRO are untouched and compose with
+ *   it; evaluation, early stopping, calibration and export never see it.  With nothing set a pass launches the kernels, and gives the
+ *   bits, of a trainer this was never called on; in a group the members without targets keep their kernels.
+ * A target set is an N x K fp32 matrix of per-row class distributions on one device; row i belongs to row i of a feature set.  It
+ *   never holds an invalid row.  A row is valid when every entry is finite and >= 0 and its sum, taken in double in class order, is
+ *   within 1e-3 of 1 (a condition, not a measurement: a normalised fp32 row of K <= 2048 classes is off by about (K + 8) 2^-24).
+ *   Both fill routes write the new rows past the committed row count, validate them on the device (one wave per row, the first bad
+ *   row reduced with an integer atomic minimum), read one result back and commit the rows only if none is invalid; otherwise
+ *   MMC_ERR_ARG names the first bad row and why ("row 17: entry 5 = nan ...", "row 17 sums to 0.93 ...") and the row count stays.
+ *   mmc_targetset_append numbers the row within the rows of that call (row 0 is P's first row, wherever it would have landed in
+ *   the set); mmc_ensemble_predict_set numbers it by row of the feature set.
+ *   Growth allocates the new buffer first: a refused call changes nothing.  rows x K is at most MMC_TARGETSET_MAX_CELLS, checked
+ *   arithmetically before anything is allocated.
+ * mmc_targetset_append takes n x K rows from host (MMC_IN_HOST) or device (MMC_IN_DEVICE) memory; mmc_targetset_read writes rows
+ *   [first, first + n) to host memory.  mmc_ensemble_predict_set appends n rows: row j is the ensemble mean e ("head ensembles") of
+ *   set row first + j at G = 1, with the bits mmc_ensemble_topk writes into proba for that row, made in the ensemble's own chunks
+ *   straight into the target set; an ensemble of one member gives mmc_head_predict's bits.  A feature row whose NaN reaches a member's
+ *   logits (a hidden ReLU is fmaxf(., 0) and drops it) makes a NaN target row, so the fill is refused, the bad row named by its set row.
+ * mmc_trainer_set_distillation(t, alpha, temperature): alpha in [0, 1], temperature tau in [0.25, 64]; alpha = 0 restores the default.
+ * Notation (that of "group-robust training" and "taxonomy-aware loss").  u = z + prior, w the class weights, t = y_i, s_i the row's
+ *   normaliser exactly as the other loss kernels form it (inv_wsum, or rw[row] * inv_wsum, or r_i with groups); b_i and db_i/dz the
+ *   trainer's own row term and gradient before normalisation, formed operation for operation as the general form of
+ *   mmc_trainer_set_loss (at its defaults the plain weighted cross-entropy: b_i = (1.0f w_t) nll).  q_i is row rho(i) of the target
+ *   set, rho(i) = visit[pos] where the pass has a visiting order, else pos, pos the position in the pass; the row is read in place.
+ *     tau = 1:   qt = q_i as stored (not renormalised: its fp32 sum stands where 1 would), pt = softmax(u), the hard term's own
+ *     tau != 1:  qt_c = q_c^(1/tau) / sum_c' q_c'^(1/tau), formed as exp(g_c - mg - log sum exp(g_c' - mg)) with g_c = logf(q_c) it,
+ *                it = (float)(1 / tau), over the classes with q_c > 0; an entry of 0 stays 0.  pt = softmax(u it), with its own
+ *                maximum and sum.
+ *     k_i        = -sum_c qt_c log pt_c                     a class with qt_c == 0 adds 0
+ *     l_i        = s_i [ (1 - alpha) b_i + alpha tau^2 w_t k_i ]
+ *     dl_i/dz_c  = s_i [ (1 - alpha) db_i/dz_c + alpha tau w_t (pt_c sum_c' qt_c' - qt_c) ]
+ *   with (float)(1 - alpha), (float)(alpha tau) and (float)(alpha tau^2) made from doubles on the host and multiplied by w_t in the
+ *   kernel.  The reported loss is the sum of l_i plus the L2 term: the cross-entropy form, which includes the teacher's entropy, not
+ *   the KL divergence.  Every output is finite on any finite logits row and any valid target row.
+ * The _distill passes are the _weighted passes with one more argument.  ts == NULL is mmc_trainer_partial_fit_set_weighted, bit for
+ *   bit.  In the group form `targets` is an array of `count` pointers, or NULL; a member whose entry is NULL runs exactly as in the
+ *   _weighted call; members may share one set (it is only read) or use different ones.  The results do not depend on
+ *   MMC_TRAIN_CHUNK_ROWS, a member of a group matches its solo pass bit for bit, and a pass is bit-reproducible.  The plain, mixed
+ *   and weighted entry points on a trainer with distillation set run as ever.
+ * Checked before the first launch and before any member changes, on top of the _weighted call's checks: a target set whose K is not
+ *   the trainer's, whose row count is not the feature set's, or that lives on another device; targets on a trainer with alpha == 0
+ *   ("needs mmc_trainer_set_distillation(alpha > 0)"); targets on a trainer with a hierarchy -> MMC_ERR_ARG.  Distillation and
+ *   mmc_trainer_set_hierarchy (levels or soft labels) exclude each other: whichever setter comes second refuses.  Mixup with
+ *   targets is refused by construction: no entry point takes a mixing plan and a target set (the Python surface raises ValueError).  alpha or temperature out of range or NaN -> MMC_ERR_ARG, the trainer left as it was.
+ * mmc_trainer_loss_gradient_distill runs the stage's own kernel on caller logits and caller target rows q (n x K, host), n in
+ *   [1, 16384] rows taken as one mini-batch, position i reading row i; row_weight may be NULL.  The rows of q pass the same validity
+ *   rule first (a bad row is numbered within q).  mmc_trainer_loss_gradient_distill_weighted is mmc_trainer_loss_gradient_weighted
+ *   with the same q: its arguments, checks and outputs, groups and the explicit log q included, so that group DRO over the distilled
+ *   stage (normaliser r_i, then dro_update_kernel / row_scale_kernel on its row_loss / dlogits) can be checked per element; with
+ *   row_group NULL it is mmc_trainer_loss_gradient_distill, bit for bit. */
+#define MMC_TARGETSET_MAX_CELLS 1073741824LL  /* 2^30: 4 GiB of resident targets */
+typedef struct mmc_targetset mmc_targetset;
+int mmc_targetset_create(int K, int device, int64_t reserve_rows, mmc_targetset** out);
+void mmc_targetset_destroy(mmc_targetset* ts);
+int64_t mmc_targetset_rows(const mmc_targetset* ts);
+int mmc_targetset_num_classes(const mmc_targetset* ts);
+int mmc_targetset_append(mmc_targetset* ts, const float* P /* n x K */, int64_t n, unsigned flags, void* hip_stream);
+int mmc_targetset_read(mmc_targetset* ts, int64_t first, int64_t n, float* P /* n x K, host */, void* hip_stream);
+int mmc_ensemble_predict_set(mmc_ensemble* e, mmc_featureset* fs, int64_t first, int64_t n, mmc_targetset* ts, void* hip_stream);
+int mmc_trainer_set_distillation(mmc_trainer* t, double alpha, double temperature);
+int mmc_trainer_partial_fit_set_distill(mmc_trainer* t, mmc_featureset* fs, mmc_targetset* ts /* or NULL */, const int64_t* visit,
+                                        const float* row_weight /* n or NULL */, const int32_t* row_group /* n or NULL */, int64_t n,
+                                        int batch_size, double* avg_loss, void* hip_stream);
+int mmc_trainer_group_partial_fit_set_distill(mmc_trainer* const* trainers, int count, mmc_featureset* fs,
+                                              mmc_targetset* const* targets /* count pointers, or NULL */, const int64_t* const* visit,
+                                              const float* const* row_weight, const int32_t* const* row_group, const int64_t* n,
+                                              const int* batch_size, double* avg_loss, void* hip_stream);
+int mmc_trainer_loss_gradient_distill(mmc_trainer* t, const float* logits, const int32_t* y, const float* q /* n x K, host */,
+                                      const float* row_weight /* n or NULL */, int64_t n, float* dlogits, float* row_loss,
+                                      void* hip_stream);
+int mmc_trainer_loss_gradient_distill_weighted(mmc_trainer* t, const float* logits, const int32_t* y, const float* q /* n x K, host */,
+                                               const float* row_weight, const int32_t* row_group, const double* log_q_in, double eta,
+                                               int n_groups, int64_t n, float* dlogits, float* row_loss, double* log_q_out,
+                                               double* group_loss /* n_groups, NaN where none */, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

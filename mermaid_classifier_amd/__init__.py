@@ -23,6 +23,7 @@ from .logit_scaling import LogitScaling, fit_logit_scaling  # noqa: F401
 from .optim import fold_batch_norm  # noqa: F401
 from .neighbors import KnnValidation, Neighbors, audit_labels, knn_validate, near_duplicates, nearest  # noqa: F401
 from .ensemble import EnsembleValidation, HeadEnsemble, Uncertainty, ensemble_validate, export_ensemble, load_ensemble  # noqa: F401
+from .distill import TargetSet, distill, teacher_targets  # noqa: F401
 
 __all__ = [
     "EfficientNetExtractor", "build_extractor_class", "resolve_device", "verify_device_numerics",
@@ -43,4 +44,5 @@ __all__ = [
     "LogitScaling", "fit_logit_scaling", "fold_batch_norm",
     "nearest", "Neighbors", "knn_validate", "KnnValidation", "audit_labels", "near_duplicates",
     "HeadEnsemble", "Uncertainty", "ensemble_validate", "EnsembleValidation", "export_ensemble", "load_ensemble",
+    "TargetSet", "teacher_targets", "distill",
 ]

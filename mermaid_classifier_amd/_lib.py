@@ -15,6 +15,7 @@ LIB_PATH = _HERE / LIB_NAME
 MMC_OK, MMC_ERR_ARG, MMC_ERR_WEIGHTS, MMC_ERR_HIP, MMC_ERR_NOMEM = 0, 1, 2, 3, 4
 MMC_PRECISION_FP8 = 1   # include/mmc.h: flags of mmc_backbone_create_ex
 MMC_IN_HOST, MMC_OUT_HOST = 1, 2
+MMC_IN_DEVICE = 0
 MMC_EVAL_TOTALS = 5   # include/mmc.h: length of mmc_head_evaluate's totals
 MMC_GROUPED_MAX_BINS, MMC_COVER_SUMS = 64, 8   # include/mmc.h: mmc_head_evaluate_grouped
 MMC_GROUPED_MAX_SOURCE_CELLS, MMC_GROUPED_MAX_COVER_CELLS = 1 << 26, 1 << 28
@@ -64,12 +65,17 @@ SYMBOLS = [
     "mmc_dist_unique_id", "mmc_dist_create", "mmc_dist_destroy", "mmc_gather_features",
     "mmc_ensemble_create", "mmc_ensemble_destroy", "mmc_ensemble_size", "mmc_ensemble_num_classes", "mmc_ensemble_input_dim",
     "mmc_ensemble_chunk_rows", "mmc_ensemble_topk", "mmc_ensemble_classify_patches", "mmc_ensemble_evaluate", "mmc_ensemble_evaluate_set",
+    "mmc_targetset_create", "mmc_targetset_destroy", "mmc_targetset_rows", "mmc_targetset_num_classes", "mmc_targetset_append",
+    "mmc_targetset_read", "mmc_ensemble_predict_set", "mmc_trainer_set_distillation", "mmc_trainer_partial_fit_set_distill",
+    "mmc_trainer_group_partial_fit_set_distill", "mmc_trainer_loss_gradient_distill",
+    "mmc_trainer_loss_gradient_distill_weighted",
 ]
 # include/mmc.h, "optimiser options"
 MMC_LR_CONSTANT, MMC_LR_LINEAR, MMC_LR_COSINE = 0, 1, 2
 MMC_WEIGHTS_RAW, MMC_WEIGHTS_AVERAGED = 0, 1
 MMC_DRO_MAX_GROUPS = 1024   # include/mmc.h, "group-robust training"
 MMC_HIER_MAX_LEVELS = 4   # include/mmc.h, "taxonomy-aware loss"
+MMC_TARGETSET_MAX_CELLS = 1 << 30   # include/mmc.h, "distillation"
 
 
 class LibraryMissingError(ImportError):
@@ -332,6 +338,33 @@ def _load() -> C.CDLL:
     lib.mmc_ensemble_evaluate.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
     lib.mmc_ensemble_evaluate_set.restype = i32
     lib.mmc_ensemble_evaluate_set.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mmc_targetset_create.restype = i32
+    lib.mmc_targetset_create.argtypes = [i32, i32, i64, C.POINTER(vp)]
+    lib.mmc_targetset_destroy.restype = None
+    lib.mmc_targetset_destroy.argtypes = [vp]
+    lib.mmc_targetset_rows.restype = i64
+    lib.mmc_targetset_rows.argtypes = [vp]
+    lib.mmc_targetset_num_classes.restype = i32
+    lib.mmc_targetset_num_classes.argtypes = [vp]
+    lib.mmc_targetset_append.restype = i32
+    lib.mmc_targetset_append.argtypes = [vp, vp, i64, u32, vp]
+    lib.mmc_targetset_read.restype = i32
+    lib.mmc_targetset_read.argtypes = [vp, i64, i64, vp, vp]
+    lib.mmc_ensemble_predict_set.restype = i32
+    lib.mmc_ensemble_predict_set.argtypes = [vp, vp, i64, i64, vp, vp]
+    lib.mmc_trainer_set_distillation.restype = i32
+    lib.mmc_trainer_set_distillation.argtypes = [vp, f64, f64]
+    # the arguments of the _weighted passes with the target set (one, or `count` pointers) behind the feature set
+    lib.mmc_trainer_partial_fit_set_distill.restype = i32
+    lib.mmc_trainer_partial_fit_set_distill.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, C.POINTER(C.c_double), vp]
+    lib.mmc_trainer_group_partial_fit_set_distill.restype = i32
+    lib.mmc_trainer_group_partial_fit_set_distill.argtypes = [C.POINTER(vp), i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                              C.POINTER(vp), C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_double), vp]
+    lib.mmc_trainer_loss_gradient_distill.restype = i32
+    lib.mmc_trainer_loss_gradient_distill.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp]
+    # the arguments of mmc_trainer_loss_gradient_weighted with the target rows behind y
+    lib.mmc_trainer_loss_gradient_distill_weighted.restype = i32
+    lib.mmc_trainer_loss_gradient_distill_weighted.argtypes = [vp, vp, vp, vp, vp, vp, vp, f64, i32, i64, vp, vp, vp, vp, vp]
     return lib
 
 

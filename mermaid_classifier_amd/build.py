@@ -4,9 +4,9 @@
 
 One object per translation unit (the kernels are five .hip files by layer group, plus the trainer -- trainer.hip with its kernels and
 every launch of them, and its two host units, trainer_options.cpp with the handle and its options and trainer_pass.cpp with the
-passes --, the calibrator, the feature set, the feature transforms, the nearest-neighbour search, logit calibration, the grouped
-metrics, cover estimation, and the three host units of the C ABI: mmc_api.cpp with the backbone schedule, mmc_head.cpp with the
-calibrated head and mmc_ensemble.cpp with the head ensembles),
+passes --, the calibrator, the feature set, the target set, the feature transforms, the nearest-neighbour search, logit
+calibration, the grouped metrics, cover estimation, and the three host units of the C ABI: mmc_api.cpp with the backbone schedule,
+mmc_head.cpp with the calibrated head and mmc_ensemble.cpp with the head ensembles),
 compiled in parallel and only when the source or one of its headers is newer than the object; then one link.  Objects live in
 csrc/_obj/ (git-ignored and gpurun-ignored: only the linked library travels to the GPU box).
 """
@@ -37,6 +37,7 @@ SOURCES = {
     "trainer_pass.cpp": ["../../include/mmc.h", "trainer_state.h", "trainer_internal.h", "device_mem.h"],
     "calib.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
     "featureset.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
+    "targets.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
     "features.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
     "neighbors.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h"],
     "logit_scaling.hip": ["../../include/mmc.h", "trainer_internal.h", "device_mem.h", "logit_newton.h"],

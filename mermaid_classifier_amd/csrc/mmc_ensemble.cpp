@@ -325,3 +325,42 @@ extern "C" int mmc_ensemble_evaluate_set(mmc_ensemble* e, mmc_featureset* fs, in
     return ensemble_evaluate(e, fs->X + (size_t)first * fs->dim, nullptr, fs->y + first, n, 0u, label_map, n_labels, o,
                              static_cast<hipStream_t>(hip_stream));
 }
+
+// ------------------------------------------------------------------------------------------
+// mmc_ensemble_predict_set: the ensemble mean of set rows into a target set (include/mmc.h, "distillation")
+// ------------------------------------------------------------------------------------------
+// mmc_ensemble_topk's proba at G = 1 and k = 1, chunk by chunk in the ensemble's own chunks, written straight past the target set's
+// committed rows; the selection goes to the ensemble's staging and is dropped.  The rows are committed by the set's own rule.
+extern "C" int mmc_ensemble_predict_set(mmc_ensemble* e, mmc_featureset* fs, int64_t first, int64_t n, mmc_targetset* ts, void* hip_stream)
+{
+    if (!e) return fail(MMC_ERR_ARG, "ensemble handle is NULL");
+    if (!fs) return fail(MMC_ERR_ARG, "feature set handle is NULL");
+    if (!ts) return fail(MMC_ERR_ARG, "target set handle is NULL");
+    if (fs->dim != e->input_dim) return fail(MMC_ERR_ARG, "feature set has %d columns, ensemble expects %d", fs->dim, e->input_dim);
+    if (fs->device != e->device) return fail(MMC_ERR_ARG, "feature set is on device %d, ensemble on device %d", fs->device, e->device);
+    if (ts->device != e->device) return fail(MMC_ERR_ARG, "target set is on device %d, ensemble on device %d", ts->device, e->device);
+    if (ts->K != e->K) return fail(MMC_ERR_ARG, "target set has %d classes, ensemble %d", ts->K, e->K);
+    if (first < 0 || n < 0 || first > fs->n || n > fs->n - first)
+        return fail(MMC_ERR_ARG, "rows [%lld, %lld + %lld) outside the set's %lld rows", (long long)first, (long long)first, (long long)n,
+                    (long long)fs->n);
+    if (n == 0) return MMC_OK;
+    if (n > MMC_TARGETSET_MAX_CELLS / ts->K - ts->n)
+        return fail(MMC_ERR_ARG, "%lld + %lld rows x %d classes: a target set holds at most %lld cells (MMC_TARGETSET_MAX_CELLS)",
+                    (long long)ts->n, (long long)n, ts->K, (long long)MMC_TARGETSET_MAX_CELLS);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipSetDevice(e->device));
+    const int64_t chunk = ensemble_chunk(e, 1);
+    const int64_t pts = n < chunk ? n : chunk;
+    int r;
+    if ((r = e->idx_stage.reserve(pts)) || (r = e->score_stage.reserve(pts))) return r;
+    if ((r = targetset_reserve(ts, ts->n + n, st))) return r;
+    float* out = ts->P.p + (size_t)ts->n * ts->K;
+    const int K = e->K;
+    r = ensemble_for_chunks(e, fs->X + (size_t)first * fs->dim, n, chunk, 0u, st, [&](int64_t off, int cur) -> int {
+        KTRY(launch_ensemble_topk(e->logits.p, cur, 1, K, e->M, (size_t)cur * K, e->cal, 1, e->idx_stage.p, e->score_stage.p,
+                                  out + (size_t)off * K, nullptr, nullptr, st));
+        return MMC_OK;
+    });
+    if (r) return r;
+    return targetset_commit(ts, n, first, st);
+}

@@ -31,6 +31,9 @@
 // Per trainer, off by default (include/mmc.h, "taxonomy-aware loss"; a member without a hierarchy runs the loss kernels above as ever):
 //   levels    l_i += w_t sum_l lam_l (-log P_l), P_l the softmax mass of t's node at level l    ce_grad_hier_kernel, ce_grad_rows_hier
 //   soft      the base term becomes w_t (-sum_c T[t,c] logp_c); row weights ride the same kernel (mmc_trainer_set_hierarchy)
+// Per trainer and pass, off by default (include/mmc.h, "distillation"; a member without a target set runs the loss kernels above as ever):
+//   soft      l_i = s_i [(1 - alpha) b_i + alpha tau^2 w_t k_i], k_i the cross-entropy of the row's own target, read in place
+//             from a resident target set, against softmax(u / tau); row weights ride the same kernel   ce_grad_distill_kernel, ce_grad_rows_distill
 // Per trainer, off by default (include/mmc.h, "batch normalisation"; a member without it launches none of these and keeps its colsum):
 //   forward   Z = H(l) W(l)^T + b(l) by the forward GEMM (EPI_BIAS) to a buffer of its own, then
 //             H(l+1) = relu(gamma xhat + beta), xhat = (Z - mu) rstd; the running statistics    bn_forward_kernel
@@ -641,6 +644,166 @@ __global__ __launch_bounds__(256) void ce_grad_hier_kernel(const CeHierGroup g)
     const CeHierDesc& d = g.d[blockIdx.z];
     if ((int)blockIdx.x * 4 >= d.c.M) return;
     ce_grad_rows_hier(blockIdx.x, d.c.logits, d.c.y, d.c.M, d.c.K, d.c.cw, d.c.inv_wsum, d.c.dlogits, d.c.row_loss, d.c.loss, d.h, d.rw);
+}
+
+// ---- distillation (include/mmc.h): the loss stage of a member whose pass has a target set, with or without row weights.  A body of
+// its own: the members without targets keep the kernels above and their code.
+struct DistillLoss {
+    const float* q;           // the target set's rows [.][K]
+    const int64_t* visit;     // the pass's visiting order on the device, or null: position pos reads row visit ? visit[pos] : pos
+    int64_t start;            // the mini-batch's first position in the pass
+    float om_alpha;           // (float)(1 - alpha)
+    float a_grad, a_loss;     // (float)(alpha tau), (float)(alpha tau^2)
+    float inv_tau;            // (float)(1 / tau)
+    int temp;                 // tau != 1: the second instantiation
+};
+
+// One wave per row, classes lane-strided, every row reduction a lane-strided sum (or max) and the xor butterfly.  The row's target
+// q is read in place from the target set: 4 K consecutive bytes per wave, lane-strided, no gather copy.
+//   hard   b, db: the general form, operation for operation as ce_grad_rows<true> forms it (at its defaults the plain weighted CE)
+//   soft   TEMP = false: qt = q as stored, pt = p, the hard term's softmax; sq = sum_c q_c (its fp32 sum stands where 1 would)
+//          TEMP = true:  v_c = u_c inv_tau with its own maximum mv and lv = logf(sum expf(v_c - mv)), pt_c = expf(v_c - mv - lv);
+//                        g_c = logf(q_c) inv_tau over the classes with q_c > 0, its own maximum mg and lg = logf(sum expf(g_c - mg)),
+//                        qt_c = expf(g_c - mg - lg), 0 where q_c == 0; sq = sum_c qt_c
+//          k = -sum_c qt_c log pt_c, a class with qt_c == 0 adding 0
+//   row    l_i = s_i (om_alpha b + (a_loss w_t) k),  dl_i/dz_c = s_i (om_alpha db_c + (a_grad w_t) (pt_c sq - qt_c)),
+//          s_i = rw ? rw[row] * inv_wsum : inv_wsum
+// Finite on any finite logits row and any valid target row: a valid row has a positive entry, so mg is finite and its sum is at
+// least 1; log pt_c is finite; nothing divides.
+template <bool TEMP>
+__device__ __forceinline__ void ce_grad_rows_distill(int block, const float* __restrict__ logits, const int32_t* __restrict__ y, int M, int K,
+                                                     const float* __restrict__ cw, float inv_wsum, float* __restrict__ dlogits,
+                                                     float* __restrict__ row_loss, const CeLoss& ls, const DistillLoss& dl,
+                                                     const float* __restrict__ rw)
+{
+#pragma clang fp contract(off)   // nothing here is fused
+    const int lane = threadIdx.x & 63;
+    const int row = block * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    if (rw) inv_wsum = rw[row] * inv_wsum;
+    const float* z = logits + (size_t)row * K;
+    const float* pr = ls.prior;
+    const int yi = y[row];
+    const int64_t pos = dl.start + row;
+    const float* qr = dl.q + (size_t)(dl.visit ? dl.visit[pos] : pos) * K;
+    float mx = -INFINITY;
+    for (int c = lane; c < K; c += 64) mx = fmaxf(mx, pr ? z[c] + pr[c] : z[c]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    float s = 0.f, so = 0.f;   // sum_c e_c; sum_{c != t} e_c
+    for (int c = lane; c < K; c += 64) {
+        const float e = expf((pr ? z[c] + pr[c] : z[c]) - mx);
+        s += e;
+        so += c == yi ? 0.f : e;
+    }
+    s = wave_sum(s);
+    so = wave_sum(so);
+    const float w = cw ? cw[yi] : 1.0f;
+    const float lse = logf(s);
+    const bool smooth = ls.eps_k != 0.f;
+    float sl = 0.f;            // sum_c w_c logp_c of the smoothing term
+    if (smooth) {
+        for (int c = lane; c < K; c += 64) {
+            const float lp = (pr ? z[c] + pr[c] : z[c]) - mx - lse;
+            sl += cw ? cw[c] * lp : lp;
+        }
+        sl = wave_sum(sl);
+    }
+    const float ut = pr ? z[yi] + pr[yi] : z[yi];
+    const float nll = lse - (ut - mx);
+    float m = 1.0f, f = 1.0f;
+    if (ls.gamma != 0.f) {
+        const float q = so / s;
+        const float pt = expf(ut - mx - lse);
+        const float pw = powf(q, ls.gamma - 1.0f);
+        m = pw * q;
+        f = m + ls.gamma * pt * pw * nll;
+    }
+    const float a = ls.om_eps * w;
+    const float af = a * f;
+    float lb = a * m * nll;
+    if (smooth) lb = lb - ls.eps_k * sl;
+    // the soft term
+    float mv = 0.f, lv = 0.f, mg = 0.f, lg = 0.f;
+    if (TEMP) {
+        mv = -INFINITY;
+        mg = -INFINITY;
+        for (int c = lane; c < K; c += 64) {
+            const float u = pr ? z[c] + pr[c] : z[c];
+            mv = fmaxf(mv, u * dl.inv_tau);
+            const float q = qr[c];
+            if (q > 0.f) mg = fmaxf(mg, logf(q) * dl.inv_tau);
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            mv = fmaxf(mv, __shfl_xor(mv, o));
+            mg = fmaxf(mg, __shfl_xor(mg, o));
+        }
+        float sv = 0.f, sg = 0.f;
+        for (int c = lane; c < K; c += 64) {
+            const float u = pr ? z[c] + pr[c] : z[c];
+            sv += expf(u * dl.inv_tau - mv);
+            const float q = qr[c];
+            sg += q > 0.f ? expf(logf(q) * dl.inv_tau - mg) : 0.f;
+        }
+        sv = wave_sum(sv);
+        sg = wave_sum(sg);
+        lv = logf(sv);
+        lg = logf(sg);
+    }
+    float sq = 0.f, sk = 0.f;   // sum_c qt_c; sum_c qt_c log pt_c
+    for (int c = lane; c < K; c += 64) {
+        const float u = pr ? z[c] + pr[c] : z[c];
+        const float q = qr[c];
+        float qt, lpt;
+        if (TEMP) {
+            qt = q > 0.f ? expf(logf(q) * dl.inv_tau - mg - lg) : 0.f;
+            lpt = u * dl.inv_tau - mv - lv;
+        } else {
+            qt = q;
+            lpt = u - mx - lse;
+        }
+        sq += qt;
+        sk += qt != 0.f ? qt * lpt : 0.f;
+    }
+    sq = wave_sum(sq);
+    sk = wave_sum(sk);
+    const float wg = dl.a_grad * w, wl = dl.a_loss * w;
+    for (int c = lane; c < K; c += 64) {
+        const float u = pr ? z[c] + pr[c] : z[c];
+        const float p = expf(u - mx - lse);
+        float d = af * (p - (c == yi ? 1.0f : 0.0f));
+        if (smooth) d = d + ls.eps_k * (p * ls.w_total - (cw ? cw[c] : 1.0f));
+        const float q = qr[c];
+        float qt, pt;
+        if (TEMP) {
+            qt = q > 0.f ? expf(logf(q) * dl.inv_tau - mg - lg) : 0.f;
+            pt = expf(u * dl.inv_tau - mv - lv);
+        } else {
+            qt = q;
+            pt = p;
+        }
+        d = dl.om_alpha * d + wg * (pt * sq - qt);
+        dlogits[(size_t)row * K + c] = inv_wsum * d;
+    }
+    if (lane == 0) row_loss[row] = (dl.om_alpha * lb + wl * (-sk)) * inv_wsum;
+}
+
+struct CeDistillDesc {
+    CeDesc c;          // inv_wsum as in CeDesc, or as in CeRowDesc for a member with row weights or groups
+    const float* rw;   // the weights of the mini-batch's positions, or null
+    DistillLoss d;
+};
+using CeDistillGroup = Group<CeDistillDesc>;
+
+__global__ __launch_bounds__(256) void ce_grad_distill_kernel(const CeDistillGroup g)
+{
+    const CeDistillDesc& d = g.d[blockIdx.z];
+    if ((int)blockIdx.x * 4 >= d.c.M) return;
+    if (d.d.temp)
+        ce_grad_rows_distill<true>(blockIdx.x, d.c.logits, d.c.y, d.c.M, d.c.K, d.c.cw, d.c.inv_wsum, d.c.dlogits, d.c.row_loss, d.c.loss, d.d, d.rw);
+    else
+        ce_grad_rows_distill<false>(blockIdx.x, d.c.logits, d.c.y, d.c.M, d.c.K, d.c.cw, d.c.inv_wsum, d.c.dlogits, d.c.row_loss, d.c.loss, d.d, d.rw);
 }
 
 // The group DRO update of a member's step, one workgroup of 1024 threads: from R_i = row_loss[i] (normaliser r_i) and the groups
@@ -1332,24 +1495,38 @@ struct LossMember {
     double* group_loss = nullptr;   // [n_groups] L_a, or null
     int n_groups = 0;
     double eta = 0.0;
+    const float* q = nullptr;           // a member with targets: the target rows, the pass's visiting order on the device (or null)
+    const int64_t* q_visit = nullptr;   // and the mini-batch's first position in the pass
+    int64_t q_start = 0;
 };
 
-// The loss launches of `cnt` members.  Which kernel a member runs: with a hierarchy ce_grad_hier_kernel (row weights ride it);
-// else weighted ce_grad_weighted_kernel; else mixed ce_grad_mixed_kernel; else ce_grad_kernel.  A weighted member with groups then
-// moves its q on the device and every row takes its group's share.
+// the kernel's fp32 scalars of the trainer's distillation options, each the float of a double expression (include/mmc.h)
+DistillLoss trainer_distill_loss(const mmc_trainer* t, const float* q, const int64_t* visit, int64_t start)
+{
+    const double a = t->distill_alpha, tau = t->distill_tau;
+    return DistillLoss{q, visit, start, (float)(1.0 - a), (float)(a * tau), (float)(a * tau * tau), (float)(1.0 / tau), tau != 1.0 ? 1 : 0};
+}
+
+// The loss launches of `cnt` members.  Which kernel a member runs: with targets ce_grad_distill_kernel; with a hierarchy
+// ce_grad_hier_kernel (row weights ride either, and the two never meet: the setters and the passes refuse); else weighted
+// ce_grad_weighted_kernel; else mixed ce_grad_mixed_kernel; else ce_grad_kernel.  A weighted member with groups then moves its q
+// on the device and every row takes its group's share.
 void loss_stage(const LossMember* mem, int cnt, hipStream_t st)
 {
     GroupLaunch<CeDesc> plain;
     GroupLaunch<CeMixDesc> mixed;
     GroupLaunch<CeRowDesc> rows;
     GroupLaunch<CeHierDesc> hier;
+    GroupLaunch<CeDistillDesc> soft;
     GroupLaunch<DroDesc> dro;
     GroupLaunch<RowScaleDesc> scale;
     for (int i = 0; i < cnt; ++i) {
         const LossMember& m = mem[i];
         const mmc_trainer* t = m.t;
         const CeDesc c{m.logits, m.y, t->cw, t->dZ[t->L], t->row_loss, m.cur, t->K, m.inv_wsum, t->general ? 1 : 0, trainer_ce_loss(t)};
-        if (t->hier)
+        if (m.q)
+            soft.add(CeDistillDesc{c, m.weighted ? m.rw : nullptr, trainer_distill_loss(t, m.q, m.q_visit, m.q_start)}, m.cur);
+        else if (t->hier)
             hier.add(CeHierDesc{c, m.weighted ? m.rw : nullptr, trainer_hier_loss(t)}, m.cur);
         else if (m.weighted)
             rows.add(CeRowDesc{c, m.rw}, m.cur);
@@ -1366,6 +1543,7 @@ void loss_stage(const LossMember* mem, int cnt, hipStream_t st)
     mixed.launch(ce_grad_mixed_kernel, dim3(mixed.blocks(0, 4)), 256, st);
     rows.launch(ce_grad_weighted_kernel, dim3(rows.blocks(0, 4)), 256, st);
     hier.launch(ce_grad_hier_kernel, dim3(hier.blocks(0, 4)), 256, st);
+    soft.launch(ce_grad_distill_kernel, dim3(soft.blocks(0, 4)), 256, st);
     dro.launch(dro_update_kernel, dim3(1), 1024, st);
     scale.launch(row_scale_kernel, dim3(scale.blocks(0, 4)), 256, st);
 }
@@ -1491,7 +1669,7 @@ int trainer_group_step(const StepMember* act, int cnt, hipStream_t st)
             const StepMember& a = act[i];
             const mmc_trainer* t = a.t;
             mem[i] = LossMember{t, t->H[t->L], t->y + a.off, a.cur, a.inv_wsum, a.mixed ? t->y2 + a.off : nullptr, a.lam, a.weighted, a.rw, a.rg,
-                                a.V, t->logq, t->row_scale, nullptr, t->n_groups, t->dro_eta};
+                                a.V, t->logq, t->row_scale, nullptr, t->n_groups, t->dro_eta, a.q, a.q_visit, a.q_start};
         }
         loss_stage(mem, cnt, st);
     }
@@ -1782,12 +1960,15 @@ extern "C" int mmc_trainer_loss_gradient_mixed(mmc_trainer* t, const float* logi
     return MMC_OK;
 }
 
+namespace {
+
 // The weighted loss stage of a step on caller logits and an explicit log q (include/mmc.h, "group-robust training"): a weighted
 // member whether or not either array is given, its groups' state in the trainer's scratch.  The trainer's own distribution is
-// neither read nor written.
-extern "C" int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* logits, const int32_t* y, const float* row_weight,
-                                                  const int32_t* row_group, const double* log_q_in, double eta, int n_groups, int64_t n,
-                                                  float* dlogits, float* row_loss, double* log_q_out, double* group_loss, void* hip_stream)
+// neither read nor written.  `q` (n x K host target rows, or null) makes it the distilled stage: the rows go to the scratch behind
+// everything else, pass the target set's validity rule and are read in place, position i reading row i.
+int weighted_loss_probe(mmc_trainer* t, const float* logits, const int32_t* y, const float* q, const float* row_weight,
+                        const int32_t* row_group, const double* log_q_in, double eta, int n_groups, int64_t n, float* dlogits,
+                        float* row_loss, double* log_q_out, double* group_loss, void* hip_stream)
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!logits || !y || !dlogits || !row_loss) return mmc_fail(MMC_ERR_ARG, "logits / y / dlogits / row_loss is NULL");
@@ -1809,7 +1990,8 @@ extern "C" int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* l
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     // scratch: V [G] and log q [G] and group loss [G] in double first (8-byte aligned), then y, groups, weights and c by row
     void* sc = nullptr;
-    if ((r = loss_probe_begin(t, logits, mb, (size_t)G * 24 + (size_t)mb * 16, &sc, st))) return r;
+    const size_t cells = q ? (size_t)mb * t->K : 0;
+    if ((r = loss_probe_begin(t, logits, mb, (size_t)G * 24 + (size_t)mb * 16 + cells * 4 + 16, &sc, st))) return r;
     double* Vd = static_cast<double*>(sc);
     double* lqd = Vd + G;
     double* gld = lqd + G;
@@ -1817,11 +1999,17 @@ extern "C" int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* l
     int32_t* gd = yd + mb;
     float* wd = reinterpret_cast<float*>(gd + mb);
     float* cd = wd + mb;
+    float* qd = cd + mb;
+    if (q) {
+        HIP_TRY(hipMemcpyAsync(qd, q, cells * 4, hipMemcpyHostToDevice, st));
+        if ((r = target_rows_check(qd, mb, t->K, reinterpret_cast<int32_t*>(qd + cells), 0, st))) return r;
+    }
     HIP_TRY(hipMemcpyAsync(yd, y, (size_t)mb * 4, hipMemcpyHostToDevice, st));
     if (row_weight) HIP_TRY(hipMemcpyAsync(wd, row_weight, (size_t)mb * 4, hipMemcpyHostToDevice, st));
     LossMember m{t, t->H[t->L], yd, mb, (float)(1.0 / wsums[0])};
     m.weighted = true;
     m.rw = row_weight ? wd : nullptr;
+    m.q = q ? qd : nullptr;
     if (row_group) {   // the caller's log q and eta, never the trainer's
         HIP_TRY(hipMemcpyAsync(gd, row_group, (size_t)mb * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(Vd, vmass.data(), (size_t)G * 8, hipMemcpyHostToDevice, st));
@@ -1835,6 +2023,44 @@ extern "C" int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* l
     }
     HIP_TRY(hipStreamSynchronize(st));
     return MMC_OK;
+}
+
+}  // namespace
+
+extern "C" int mmc_trainer_loss_gradient_weighted(mmc_trainer* t, const float* logits, const int32_t* y, const float* row_weight,
+                                                  const int32_t* row_group, const double* log_q_in, double eta, int n_groups, int64_t n,
+                                                  float* dlogits, float* row_loss, double* log_q_out, double* group_loss, void* hip_stream)
+{
+    return weighted_loss_probe(t, logits, y, nullptr, row_weight, row_group, log_q_in, eta, n_groups, n, dlogits, row_loss, log_q_out,
+                               group_loss, hip_stream);
+}
+
+// The distilled loss stage of a step on caller logits and caller target rows (include/mmc.h, "distillation"): the weighted probe
+// with a target row per position, so row weights and groups compose with it exactly as they do in a pass.
+static int check_distill_probe(const mmc_trainer* t, const float* q)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!q) return mmc_fail(MMC_ERR_ARG, "q is NULL");
+    if (t->distill_alpha == 0.0) return mmc_fail(MMC_ERR_ARG, "targets: the trainer needs mmc_trainer_set_distillation(alpha > 0)");
+    if (t->hier) return mmc_fail(MMC_ERR_ARG, "a distilled loss stage takes no hierarchy (mmc_trainer_set_hierarchy)");
+    return 0;
+}
+
+extern "C" int mmc_trainer_loss_gradient_distill_weighted(mmc_trainer* t, const float* logits, const int32_t* y, const float* q,
+                                                          const float* row_weight, const int32_t* row_group, const double* log_q_in,
+                                                          double eta, int n_groups, int64_t n, float* dlogits, float* row_loss,
+                                                          double* log_q_out, double* group_loss, void* hip_stream)
+{
+    if (int r = check_distill_probe(t, q)) return r;
+    return weighted_loss_probe(t, logits, y, q, row_weight, row_group, log_q_in, eta, n_groups, n, dlogits, row_loss, log_q_out, group_loss,
+                               hip_stream);
+}
+
+extern "C" int mmc_trainer_loss_gradient_distill(mmc_trainer* t, const float* logits, const int32_t* y, const float* q, const float* row_weight,
+                                                 int64_t n, float* dlogits, float* row_loss, void* hip_stream)
+{
+    if (int r = check_distill_probe(t, q)) return r;
+    return weighted_loss_probe(t, logits, y, q, row_weight, nullptr, nullptr, 0.0, 0, n, dlogits, row_loss, nullptr, nullptr, hip_stream);
 }
 
 // The step's two batch-normalisation kernels on caller arrays (include/mmc.h, "batch normalisation"): bn_forward_kernel on Z with the

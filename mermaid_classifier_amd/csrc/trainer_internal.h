@@ -24,6 +24,24 @@ struct mmc_featureset {
 // room for `need` rows in all (featureset.hip): both new buffers are allocated before anything is touched, the stored rows move on `st`
 int featureset_reserve(mmc_featureset* fs, int64_t need, hipStream_t st);
 
+// mmc_targetset_*: n rows of per-row class distributions resident on one device (targets.hip); row i belongs to row i of a feature
+// set.  P holds `cap` rows and grows as a feature set does.  Rows [0, n) are valid distributions (include/mmc.h, "distillation").
+struct mmc_targetset {
+    int K = 0, device = 0;
+    int64_t n = 0, cap = 0;
+    DevBuf<float> P;                  // [cap][K] fp32, row-major
+    DevBuf<int32_t> verdict;          // the validation kernel's result: the first bad row of a launch
+};
+
+// room for `need` rows in all (targets.hip): the new buffer is allocated before anything is touched, the stored rows move on `st`;
+// more than MMC_TARGETSET_MAX_CELLS cells is refused before anything is allocated
+int targetset_reserve(mmc_targetset* ts, int64_t need, hipStream_t st);
+// the commit rule: rows [ts->n, ts->n + n) have been written on `st`; validates them on the device, reads one result back and moves
+// the row count only if every row is a distribution, else MMC_ERR_ARG naming the first bad row (numbered from `label_first`)
+int targetset_commit(mmc_targetset* ts, int64_t n, int64_t label_first, hipStream_t st);
+// the same rule for n rows x K of P that belong to no set (the distillation probe): `verdict_dev` is one int32 on the device; bad rows are numbered from `label_first`
+int target_rows_check(const float* P_dev, int64_t n, int K, int32_t* verdict_dev, int64_t label_first, hipStream_t st);
+
 // rows per trainer_forward call (the trainer's activation buffers are sized for at most this many)
 constexpr int kTrainerForwardRows = 16384;
 

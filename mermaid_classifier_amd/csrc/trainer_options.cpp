@@ -175,6 +175,8 @@ extern "C" int mmc_trainer_set_hierarchy(mmc_trainer* t, int n_levels, const int
             return mmc_fail(MMC_ERR_ARG, "soft_targets on a trainer with label_smoothing = %g / focal_gamma = %g (mmc_trainer_set_loss)",
                             t->label_smoothing, t->focal_gamma);
     }
+    if ((n_levels > 0 || soft_targets) && t->distill_alpha != 0.0)
+        return mmc_fail(MMC_ERR_ARG, "a hierarchy on a trainer with distillation (mmc_trainer_set_distillation, alpha = %g)", t->distill_alpha);
     HIP_TRY(hipSetDevice(t->device));
     // passes synchronise their stream before they return, so nothing in flight reads what is replaced here
     DevBuf<int32_t> ids;
@@ -194,6 +196,19 @@ extern "C" int mmc_trainer_set_hierarchy(mmc_trainer* t, int n_levels, const int
     t->hier_levels = n_levels;
     std::copy(lam, lam + MMC_HIER_MAX_LEVELS, t->hier_lam);
     t->hier = n_levels > 0 || t->hier_T.p != nullptr;
+    return MMC_OK;
+}
+
+// ---- distillation (include/mmc.h) ---------------------------------------------------------------------------------------------
+extern "C" int mmc_trainer_set_distillation(mmc_trainer* t, double alpha, double temperature)
+{
+    if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return mmc_fail(MMC_ERR_ARG, "alpha = %g outside [0, 1]", alpha);
+    if (!(temperature >= 0.25 && temperature <= 64.0)) return mmc_fail(MMC_ERR_ARG, "temperature = %g outside [0.25, 64]", temperature);
+    if (alpha != 0.0 && t->hier)
+        return mmc_fail(MMC_ERR_ARG, "distillation on a trainer with a hierarchy (mmc_trainer_set_hierarchy)");
+    t->distill_alpha = alpha;
+    t->distill_tau = alpha != 0.0 ? temperature : 1.0;
     return MMC_OK;
 }
 

@@ -160,6 +160,7 @@ struct SetPass {
     const float* lam = nullptr;
     const float* row_weight = nullptr;  // a weighted pass: either or both, by position
     const int32_t* row_group = nullptr;
+    const mmc_targetset* targets = nullptr;   // a distilled pass: position i reads target row visit ? visit[i] : i in place
     int64_t n = 0;
     int mb = 0, steps = 0;
     int64_t chunk = 0, steps_per_chunk = 0, stage_rows = 0;
@@ -180,6 +181,19 @@ int check_set_pass(const char* who, const mmc_trainer* t, const mmc_featureset* 
         for (int64_t i = 0; i < n; ++i)
             if (visit[i] < 0 || visit[i] >= fs->n)
                 return mmc_fail(MMC_ERR_ARG, "%svisit[%lld] = %lld outside [0, %lld)", who, (long long)i, (long long)visit[i], (long long)fs->n);
+    return 0;
+}
+
+// the targets of a distilled pass against its trainer and its feature set (include/mmc.h, "distillation"); no entry point takes
+// targets and a mixing plan, so mixup with targets needs no check here
+int check_targets(const char* who, const mmc_trainer* t, const mmc_featureset* fs, const mmc_targetset* ts)
+{
+    if (!ts) return 0;
+    if (t->distill_alpha == 0.0) return mmc_fail(MMC_ERR_ARG, "%stargets: the trainer needs mmc_trainer_set_distillation(alpha > 0)", who);
+    if (t->hier) return mmc_fail(MMC_ERR_ARG, "%sa distilled pass takes no hierarchy (mmc_trainer_set_hierarchy)", who);
+    if (ts->K != t->K) return mmc_fail(MMC_ERR_ARG, "%starget set has %d classes, trainer %d", who, ts->K, t->K);
+    if (ts->n != fs->n) return mmc_fail(MMC_ERR_ARG, "%starget set has %lld rows, feature set %lld", who, (long long)ts->n, (long long)fs->n);
+    if (ts->device != t->device) return mmc_fail(MMC_ERR_ARG, "%starget set is on device %d, trainer on device %d", who, ts->device, t->device);
     return 0;
 }
 
@@ -252,7 +266,7 @@ int reserve_set_pass(const SetPass& p)
 // reporting a failed reservation; the solo entry is a group of one that names nobody.
 int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_featureset* fs, const int64_t* const* visit,
              const int64_t* const* partner, const float* const* lam, const float* const* row_weight, const int32_t* const* row_group,
-             const int64_t* n, const int* batch_size, double* avg_loss, hipStream_t st)
+             const mmc_targetset* const* targets, const int64_t* n, const int* batch_size, double* avg_loss, hipStream_t st)
 {
     std::vector<SetPass> mem(count);
     char who[MMC_TRAINER_GROUP_MAX][32];
@@ -269,6 +283,7 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
             return mmc_fail(MMC_ERR_ARG, "%sa mixed pass takes no hierarchy (mmc_trainer_set_hierarchy)", who[m]);
         if (row_group && row_group[m] && !trainers[m]->n_groups)
             return mmc_fail(MMC_ERR_ARG, "%srow_group needs mmc_trainer_set_group_dro(n_groups > 0) on the trainer", who[m]);
+        if ((r = check_targets(who[m], trainers[m], fs, targets ? targets[m] : nullptr))) return r;
     }
     int64_t bound = 0;
     if ((r = train_chunk_bound(&bound))) return r;
@@ -277,6 +292,7 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
         if ((r = plan_set_pass(who[m], trainers[m], fs, visit[m], partner ? partner[m] : nullptr, lam ? lam[m] : nullptr,
                                row_weight ? row_weight[m] : nullptr, row_group ? row_group[m] : nullptr, n[m], batch_size[m], bound, &mem[m])))
             return r;
+        mem[m].targets = targets ? targets[m] : nullptr;
         max_steps = std::max(max_steps, mem[m].steps);
     }
     HIP_TRY(hipSetDevice(fs->device));
@@ -322,6 +338,11 @@ int set_pass(bool grouped, mmc_trainer* const* trainers, int count, mmc_features
                 act[cnt].rg = p.row_group ? p.t->row_g + start : nullptr;
                 act[cnt].V = p.row_group ? p.t->group_mass + (size_t)s * p.t->n_groups : nullptr;
             }
+            if (p.targets) {   // read in place by position of the pass, through the order the pass has uploaded
+                act[cnt].q = p.targets->P;
+                act[cnt].q_visit = p.visit ? p.t->visit.p : nullptr;
+                act[cnt].q_start = start;
+            }
             ++cnt;
         }
         if ((r = trainer_group_step(act, cnt, st))) return r;
@@ -357,11 +378,11 @@ int check_group_args(mmc_trainer* const* trainers, int count, const mmc_features
 
 // the solo entry points: a group of one; an array a pass does not take is null
 int solo_pass(mmc_trainer* t, mmc_featureset* fs, const int64_t* visit, const int64_t* partner, const float* lam, const float* row_weight,
-              const int32_t* row_group, int64_t n, int batch_size, double* avg_loss, void* hip_stream)
+              const int32_t* row_group, int64_t n, int batch_size, double* avg_loss, void* hip_stream, const mmc_targetset* targets = nullptr)
 {
     if (!t) return mmc_fail(MMC_ERR_ARG, "trainer handle is NULL");
     if (!fs) return mmc_fail(MMC_ERR_ARG, "feature set handle is NULL");
-    return set_pass(false, &t, 1, fs, &visit, &partner, &lam, &row_weight, &row_group, &n, &batch_size, avg_loss,
+    return set_pass(false, &t, 1, fs, &visit, &partner, &lam, &row_weight, &row_group, &targets, &n, &batch_size, avg_loss,
                     static_cast<hipStream_t>(hip_stream));
 }
 
@@ -396,7 +417,8 @@ extern "C" int mmc_trainer_group_partial_fit_set_mixed(mmc_trainer* const* train
 {
     if (int r = check_group_args(trainers, count, fs, visit, n, batch_size, avg_loss)) return r;
     if (!partner != !lam) return mmc_fail(MMC_ERR_ARG, "partner and lam go together: only %s was given", partner ? "partner" : "lam");
-    return set_pass(true, trainers, count, fs, visit, partner, lam, nullptr, nullptr, n, batch_size, avg_loss, static_cast<hipStream_t>(hip_stream));
+    return set_pass(true, trainers, count, fs, visit, partner, lam, nullptr, nullptr, nullptr, n, batch_size, avg_loss,
+                    static_cast<hipStream_t>(hip_stream));
 }
 
 // mmc_trainer_partial_fit_set with per-row weights and / or groups (include/mmc.h, "group-robust training"); both NULL: that call.
@@ -414,6 +436,26 @@ extern "C" int mmc_trainer_group_partial_fit_set_weighted(mmc_trainer* const* tr
                                                           double* avg_loss, void* hip_stream)
 {
     if (int r = check_group_args(trainers, count, fs, visit, n, batch_size, avg_loss)) return r;
-    return set_pass(true, trainers, count, fs, visit, nullptr, nullptr, row_weight, row_group, n, batch_size, avg_loss,
+    return set_pass(true, trainers, count, fs, visit, nullptr, nullptr, row_weight, row_group, nullptr, n, batch_size, avg_loss,
+                    static_cast<hipStream_t>(hip_stream));
+}
+
+// mmc_trainer_partial_fit_set_weighted with per-row soft targets (include/mmc.h, "distillation"); ts NULL: that call.
+extern "C" int mmc_trainer_partial_fit_set_distill(mmc_trainer* t, mmc_featureset* fs, mmc_targetset* ts, const int64_t* visit,
+                                                   const float* row_weight, const int32_t* row_group, int64_t n, int batch_size,
+                                                   double* avg_loss, void* hip_stream)
+{
+    return solo_pass(t, fs, visit, nullptr, nullptr, row_weight, row_group, n, batch_size, avg_loss, hip_stream, ts);
+}
+
+// The grouped pass with a target set per member: `targets` is an array of `count` pointers, or NULL; a member whose entry is NULL
+// runs as in mmc_trainer_group_partial_fit_set_weighted.  Members may share one set: it is only read.
+extern "C" int mmc_trainer_group_partial_fit_set_distill(mmc_trainer* const* trainers, int count, mmc_featureset* fs,
+                                                         mmc_targetset* const* targets, const int64_t* const* visit,
+                                                         const float* const* row_weight, const int32_t* const* row_group, const int64_t* n,
+                                                         const int* batch_size, double* avg_loss, void* hip_stream)
+{
+    if (int r = check_group_args(trainers, count, fs, visit, n, batch_size, avg_loss)) return r;
+    return set_pass(true, trainers, count, fs, visit, nullptr, nullptr, row_weight, row_group, targets, n, batch_size, avg_loss,
                     static_cast<hipStream_t>(hip_stream));
 }

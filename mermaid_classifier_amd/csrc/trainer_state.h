@@ -63,6 +63,8 @@ struct mmc_trainer {
     DevBuf<int32_t> hier_ids;                           // [hier_levels][K] node ids or empty
     DevBuf<float> hier_T;                               // [K][K] soft targets or empty
     bool hier = false;                                  // hier_levels > 0 or soft targets: the member takes ce_grad_hier_kernel
+    // distillation (mmc_trainer_set_distillation; the target set of a distilled pass): alpha = 0 = today's launches
+    double distill_alpha = 0.0, distill_tau = 1.0;
     // batch normalisation (mmc_trainer_set_batch_norm): off = today's launches.  Hidden layer h (0 .. L-2) owns [bn_off[h],
     // bn_off[h] + 2 dims[h+1]) of every bn_* array: gamma then beta in bn_p (bn_g, bn_m, bn_v alike, so Adam and the clipping norm
     // take all of them in one launch each), running mean then variance in bn_run, the step's mean then rstd in bn_stat.
@@ -92,6 +94,11 @@ struct StepMember {
     const float* rw = nullptr;      // device: the weights of the mini-batch's positions, or null (all 1)
     const int32_t* rg = nullptr;    // device: their groups, or null (row weights only)
     const double* V = nullptr;      // device: [n_groups] the groups' masses in this mini-batch
+    // distillation: a member with targets takes ce_grad_distill_kernel (row weights ride it); position i of the mini-batch reads
+    // row (q_visit ? q_visit[q_start + i] : q_start + i) of q in place
+    const float* q = nullptr;           // device: the target set's rows [.][K], or null (no targets)
+    const int64_t* q_visit = nullptr;   // device: the pass's visiting order (t->visit), or null
+    int64_t q_start = 0;                // the mini-batch's start in the pass
 };
 
 // rows of the mini-batch that starts at row `start` of a pass over n rows

@@ -39,8 +39,8 @@ from .backbone import _current_stream_ptr, _device_index
 from .calibration import CalibratedMLP, calibrate, evaluate, evaluate_classes
 from .featureset import FeatureSet
 from .metrics import grouped_validate
-from .torch_classifier import TorchMLPClassifier, by_position, check_row_arrays
-from .training import EarlyStopping, _check_splits, _contiguous_batches, _fill_schedule_steps, _val_entries
+from .torch_classifier import TorchMLPClassifier, by_position, check_row_arrays, check_targets
+from .training import EarlyStopping, _check_splits, _contiguous_batches, _fill_schedule_steps, _val_entries, resolve_targets
 from .validation import validate
 
 __all__ = ["SweepConfig", "partial_fit_rows_group", "sweep_loop", "train_sweep", "rank_sweep"]
@@ -78,8 +78,19 @@ def _arrays_per_classifier(name: str, arr, count: int) -> List[Any]:
     return [arr] * count
 
 
+def _targets_per_classifier(targets, count: int) -> List[Any]:
+    """``targets`` as one entry per classifier: None and a single ``TargetSet`` stand for every classifier; a list / tuple is taken
+    per classifier (``TargetSet`` or None) and must have ``count`` entries."""
+    if isinstance(targets, (list, tuple)):
+        if len(targets) != count:
+            raise ValueError(f"targets has {len(targets)} entries for {count} classifiers")
+        return list(targets)
+    return [targets] * count
+
+
 def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, rows=None,
-                           classes: Optional[Sequence[Any]] = None, *, row_weight=None, row_group=None) -> List[TorchMLPClassifier]:
+                           classes: Optional[Sequence[Any]] = None, *, row_weight=None, row_group=None,
+                           targets=None) -> List[TorchMLPClassifier]:
     """``clf.partial_fit_rows(fs, rows_m, classes)`` for every classifier of ``clfs``, with the device work of all of them in one
     ``mmc_trainer_group_partial_fit_set`` call per ``MMC_TRAINER_GROUP_MAX`` (16) classifiers.  Parameters, Adam state,
     ``loss_curve_`` and ``n_iter_`` of each end up exactly as after its own ``partial_fit_rows``.
@@ -93,6 +104,10 @@ def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, r
     (``mmc_trainer_group_partial_fit_set_weighted``).  One call of at most 16 classifiers cannot hold both a weighted member and one
     with ``mixup_alpha > 0`` (``ValueError``): no entry point takes both.
 
+    ``targets`` as in ``partial_fit_rows``: None, one ``TargetSet`` for all, or a list with one entry -- ``TargetSet`` or None -- per
+    classifier; the members may share one set or use different ones, and a member without one runs its own kernels beside the others
+    (``mmc_trainer_group_partial_fit_set_distill``).  Members with targets count as weighted ones in the rule above.
+
     ``ValueError`` before any device work: ``rows`` that do not fit ``clfs``, the same classifier twice, a classifier on another
     device than the set.  A pass the library rejects (an index outside the set, a mini-batch of zero class weight, ...) raises
     as ``partial_fit_rows`` does and changes none of the classifiers of that call."""
@@ -100,9 +115,11 @@ def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, r
     entries = _rows_per_classifier(rows, len(clfs))
     weights = _arrays_per_classifier("row_weight", row_weight, len(clfs))
     groups = _arrays_per_classifier("row_group", row_group, len(clfs))
+    soft = _targets_per_classifier(targets, len(clfs))
     if len({id(c) for c in clfs}) != len(clfs):
         raise ValueError("the same classifier appears twice in clfs")
     arrays = [check_row_arrays(clf, len(fs), w, g) for clf, w, g in zip(clfs, weights, groups)]
+    soft = [check_targets(clf, fs, t) for clf, t in zip(clfs, soft)]
     for i, clf in enumerate(clfs):
         if _device_index(clf.device) != fs.device_index:
             raise ValueError(f"classifier {i} is on device {_device_index(clf.device)}, the feature set on device {fs.device_index}")
@@ -110,9 +127,12 @@ def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, r
     for first in range(0, len(clfs), _lib.MMC_TRAINER_GROUP_MAX):
         group = clfs[first:first + _lib.MMC_TRAINER_GROUP_MAX]
         members = arrays[first:first + _lib.MMC_TRAINER_GROUP_MAX]
-        weighted = any(w is not None or g is not None for w, g in members)
+        teachers = soft[first:first + _lib.MMC_TRAINER_GROUP_MAX]
+        distilled = any(t is not None for t in teachers)
+        weighted = distilled or any(w is not None or g is not None for w, g in members)
         if weighted and any(float(clf.mixup_alpha) != 0.0 for clf in group):
-            raise ValueError("one grouped call cannot hold members with row_weight / row_group and members with mixup_alpha > 0")
+            raise ValueError(f"one grouped call cannot hold members with {'targets' if distilled else 'row_weight / row_group'} and members "
+                             "with mixup_alpha > 0")
         passes = [clf._begin_rows_pass(fs, r, classes) for clf, r in zip(group, entries[first:])]
         plans = [clf._mix_plan(v, n_m, b_m) for clf, (v, n_m, b_m) in zip(group, passes)]     # (visit, partner, lam) per member
         count = len(group)
@@ -125,8 +145,13 @@ def partial_fit_rows_group(clfs: Sequence[TorchMLPClassifier], fs: FeatureSet, r
             pos = [(by_position(w, v, n_m), by_position(g, v, n_m)) for (w, g), (v, _, _), (_, n_m, _) in zip(members, plans, passes)]
             rw = (C.c_void_p * count)(*[None if w is None else w.ctypes.data for w, _ in pos])
             rg = (C.c_void_p * count)(*[None if g is None else g.ctypes.data for _, g in pos])
-            _lib.check(lib.mmc_trainer_group_partial_fit_set_weighted(handles, count, fs._handle(), visit, rw, rg, n, batch, avg,
-                                                                      _current_stream_ptr(fs.device_index)))
+            if distilled:                                     # a member without targets keeps a NULL entry: its own kernels
+                ts = (C.c_void_p * count)(*[None if t is None else t._handle().value for t in teachers])
+                _lib.check(lib.mmc_trainer_group_partial_fit_set_distill(handles, count, fs._handle(), ts, visit, rw, rg, n, batch, avg,
+                                                                         _current_stream_ptr(fs.device_index)))
+            else:
+                _lib.check(lib.mmc_trainer_group_partial_fit_set_weighted(handles, count, fs._handle(), visit, rw, rg, n, batch, avg,
+                                                                          _current_stream_ptr(fs.device_index)))
         elif all(partner is None for _, partner, _ in plans):
             _lib.check(lib.mmc_trainer_group_partial_fit_set(handles, count, fs._handle(), visit, n, batch, avg,
                                                              _current_stream_ptr(fs.device_index)))
@@ -155,7 +180,9 @@ class SweepConfig:
     one sweep can hold an ERM member, a group-balanced one (``group_dro_eta=0``) and DRO members side by side.  ``class_levels`` /
     ``level_weights`` / ``soft_targets`` (keyword only) are the classifier's taxonomy-aware loss: flat, level-weighted and soft-label
     heads can train side by side.  ``batch_norm`` / ``batch_norm_eps`` / ``batch_norm_momentum`` (keyword only) are the classifier's batch
-    normalisation (``mmc_trainer_set_batch_norm``): plain and normalised heads, say at ``1e-4`` and ``1e-3``, can train side by side."""
+    normalisation (``mmc_trainer_set_batch_norm``): plain and normalised heads, say at ``1e-4`` and ``1e-3``, can train side by side.
+    ``distill_alpha`` / ``distill_temperature`` (keyword only) are the classifier's distillation options: with ``train_sweep(targets=)``
+    or ``(teacher=)`` the members with ``distill_alpha > 0`` read the shared target set, the others train on their labels alone."""
     hidden_layer_sizes: Tuple[int, ...] = (500, 300, 100)
     learning_rate_init: float = 1e-4
     alpha: float = 1e-4
@@ -193,6 +220,9 @@ class SweepConfig:
     batch_norm: bool = field(default=False, kw_only=True)
     batch_norm_eps: float = field(default=1e-5, kw_only=True)
     batch_norm_momentum: float = field(default=0.1, kw_only=True)
+    # the classifier's distillation options (mmc_trainer_set_distillation): keyword only, as in its constructor
+    distill_alpha: float = field(default=0.0, kw_only=True)
+    distill_temperature: float = field(default=1.0, kw_only=True)
     batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None
     label_smoothing: float = 0.0
     focal_gamma: float = 0.0
@@ -210,7 +240,8 @@ class SweepConfig:
                                   final_lr_ratio=self.final_lr_ratio, max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay,
                                   group_dro_eta=self.group_dro_eta, n_groups=self.n_groups, class_levels=self.class_levels,
                                   level_weights=self.level_weights, soft_targets=self.soft_targets, batch_norm=self.batch_norm,
-                                  batch_norm_eps=self.batch_norm_eps, batch_norm_momentum=self.batch_norm_momentum)
+                                  batch_norm_eps=self.batch_norm_eps, batch_norm_momentum=self.batch_norm_momentum,
+                                  distill_alpha=self.distill_alpha, distill_temperature=self.distill_temperature)
 
 
 def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[Any]]],
@@ -257,7 +288,7 @@ def sweep_loop(clfs: Sequence[Any], batches: Sequence[Callable[[int], Iterable[A
 def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Sequence[SweepConfig], nbr_epochs: int, *,
                 batch_size: int, early_stopping_patience: Optional[int] = None,
                 on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None, class_scores: bool = False, transform=None,
-                logit_scaling=None) -> List[Tuple[CalibratedMLP, Dict[str, Any], List[float]]]:
+                logit_scaling=None, targets=None, teacher=None) -> List[Tuple[CalibratedMLP, Dict[str, Any], List[float]]]:
     """Train, early-stop and calibrate one head per configuration on three resident splits, all heads advancing in the same
     launches.  -> one ``(calibrated, info, ref_accs)`` per configuration, equal to
     ``train_classifier(train, ref, val, nbr_epochs, batch_size=batch_size, early_stopping_patience=..., batches=cfg.batches,
@@ -276,11 +307,23 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
     it.  A configuration with neither is calibrated exactly as before.
 
     A configuration's ``row_weight`` / ``row_group`` go to each of its passes (``partial_fit_rows_group``); with ``transform=`` they
-    index the transformed train set, which has the train set's rows."""
+    index the transformed train set, which has the train set's rows.
+
+    ``targets`` / ``teacher`` as in ``train_classifier``, one or the other: one target set for the whole sweep (a teacher's is made
+    for the raw ``train`` and freed at the end).  The configurations with ``distill_alpha > 0`` read it in every pass; the others are
+    trained exactly as without it, so label-only and distilled students at several alpha, tau advance side by side."""
     configs = list(configs)
     if not configs:
         raise ValueError("configs is empty")
     _check_splits(train, ref, val, batch_size)
+    if teacher is not None:
+        targets = resolve_targets(targets, teacher, train)
+        try:
+            return train_sweep(train, ref, val, configs, nbr_epochs, batch_size=batch_size, early_stopping_patience=early_stopping_patience,
+                               on_epoch_end=on_epoch_end, class_scores=class_scores, transform=transform, logit_scaling=logit_scaling,
+                               targets=targets)
+        finally:
+            targets.close()
     scalings = [cfg.logit_scaling if cfg.logit_scaling is not None else logit_scaling for cfg in configs]
     for sc in scalings:
         if sc is not None:
@@ -292,7 +335,7 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
             for fs in (train, ref, val):
                 sets.append(ft.apply(fs))
             results = train_sweep(*sets, configs, nbr_epochs, batch_size=batch_size, early_stopping_patience=early_stopping_patience,
-                                  on_epoch_end=on_epoch_end, class_scores=class_scores, logit_scaling=logit_scaling)
+                                  on_epoch_end=on_epoch_end, class_scores=class_scores, logit_scaling=logit_scaling, targets=targets)
         finally:
             for fs in sets:
                 fs.close()
@@ -312,7 +355,13 @@ def train_sweep(train: FeatureSet, ref: FeatureSet, val: FeatureSet, configs: Se
     eval_val = evaluate_classes if class_scores else evaluate
     member = {id(c): cfg for c, cfg in zip(clfs, configs)}
 
+    def member_targets(c):   # the shared set for the members that distil, nothing for the others
+        return targets if targets is not None and float(member[id(c)].distill_alpha) != 0.0 else None
+
     def fit_group(group, rows):
+        if any(member_targets(c) is not None for c in group):
+            return partial_fit_rows_group(group, train, rows, classes=classes, row_weight=[member[id(c)].row_weight for c in group],
+                                          row_group=[member[id(c)].row_group for c in group], targets=[member_targets(c) for c in group])
         if all(member[id(c)].row_weight is None and member[id(c)].row_group is None for c in group):
             return partial_fit_rows_group(group, train, rows, classes=classes)
         return partial_fit_rows_group(group, train, rows, classes=classes, row_weight=[member[id(c)].row_weight for c in group],

@@ -86,6 +86,34 @@ def _check_group_dro(group_dro_eta, n_groups) -> None:
         raise ValueError(f"n_groups must be None or an integer in [1, {_lib.MMC_DRO_MAX_GROUPS}], got {n_groups!r}.")
 
 
+def check_distillation(distill_alpha, distill_temperature) -> None:
+    """``distill_alpha`` in [0, 1] and ``distill_temperature`` in [0.25, 64] (include/mmc.h, "distillation"); ``ValueError``."""
+    for name, v, lo, hi in (("distill_alpha", distill_alpha, 0.0, 1.0), ("distill_temperature", distill_temperature, 0.25, 64.0)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not lo <= float(v) <= hi:
+            raise ValueError(f"{name} must be a number in [{lo:g}, {hi:g}]; got {v!r}")
+
+
+def check_targets(clf, fs, targets):
+    """``targets`` of a pass of ``clf`` over ``fs``: a ``TargetSet`` with one row per row of the set and the set's classes, on a
+    classifier with ``distill_alpha > 0`` and no hierarchy or mixup.  ``ValueError`` before anything reaches the library."""
+    if targets is None:
+        return None
+    from .distill import TargetSet
+    if not isinstance(targets, TargetSet):
+        raise ValueError(f"targets must be a TargetSet, got {type(targets).__name__}")
+    if float(getattr(clf, "distill_alpha", 0.0)) == 0.0:
+        raise ValueError("targets need a classifier with distill_alpha > 0.")
+    if float(getattr(clf, "mixup_alpha", 0.0)) != 0.0:
+        raise ValueError("mixup_alpha > 0 cannot be combined with targets.")
+    if any(getattr(clf, k, None) is not None for k in ("class_levels", "soft_targets")):
+        raise ValueError("targets cannot be combined with class_levels / soft_targets (the taxonomy-aware loss).")
+    if len(targets) != len(fs):
+        raise ValueError(f"targets hold {len(targets)} rows, the feature set {len(fs)}")
+    if not np.array_equal(np.asarray(targets.classes), np.asarray(fs.classes)):
+        raise ValueError("the targets' classes differ from the feature set's")
+    return targets
+
+
 def check_row_arrays(clf, n_rows: int, row_weight, row_group):
     """``row_weight`` / ``row_group`` of a pass of ``clf`` over a set of ``n_rows`` rows, indexed by row of the set -> them as
     contiguous float32 / int32 (or None).  ``ValueError``, before any device work: not 1D with ``n_rows`` entries, a dtype that is
@@ -183,7 +211,8 @@ class TorchMLPClassifier:
                  schedule_steps: int | None = None, final_lr_ratio: float = 0.0, max_grad_norm: float | None = None,
                  ema_decay: float = 0.0, group_dro_eta: float = 0.0, n_groups: int | None = None,
                  class_levels: dict | None = None, level_weights: Sequence[float] | None = None, soft_targets: dict | None = None,
-                 batch_norm: bool = False, batch_norm_eps: float = 1e-5, batch_norm_momentum: float = 0.1):
+                 batch_norm: bool = False, batch_norm_eps: float = 1e-5, batch_norm_momentum: float = 0.1,
+                 distill_alpha: float = 0.0, distill_temperature: float = 1.0):
         if activation != "relu":
             raise ValueError(f"TorchMLPClassifier only supports activation='relu', got {activation!r}.")
         if solver != "adam":
@@ -193,6 +222,7 @@ class TorchMLPClassifier:
         check_optimizer_options(lr_schedule, warmup_steps, schedule_steps, final_lr_ratio, max_grad_norm, ema_decay)
         _check_group_dro(group_dro_eta, n_groups)
         check_batch_norm(batch_norm, batch_norm_eps, batch_norm_momentum)
+        check_distillation(distill_alpha, distill_temperature)
         self.hidden_layer_sizes = tuple(hidden_layer_sizes)
         self.activation = activation
         self.solver = solver
@@ -229,6 +259,8 @@ class TorchMLPClassifier:
         self.batch_norm = batch_norm
         self.batch_norm_eps = batch_norm_eps
         self.batch_norm_momentum = batch_norm_momentum
+        self.distill_alpha = distill_alpha
+        self.distill_temperature = distill_temperature
 
     # ---- host bookkeeping, restated from the reference ------------------------------------------------------------
     def _resolve_batch_size(self, n_samples: int) -> int:
@@ -380,6 +412,7 @@ class TorchMLPClassifier:
             if getattr(self, "n_groups", None) is not None:
                 _check_group_dro(self.group_dro_eta, self.n_groups)
                 _lib.check(lib.mmc_trainer_set_group_dro(self._h, int(self.n_groups), float(self.group_dro_eta)))
+            self._apply_distillation()
         except Exception:
             self._release()
             raise
@@ -402,6 +435,13 @@ class TorchMLPClassifier:
             _lib.check(lib.mmc_trainer_set_ema(self._h, float(self.ema_decay)))
             if getattr(self, "_eval_weights", "averaged") == "averaged":
                 _lib.check(lib.mmc_trainer_eval_weights(self._h, _lib.MMC_WEIGHTS_AVERAGED))
+
+    def _apply_distillation(self) -> None:
+        """The distillation options onto the trainer just created; the default makes no call."""
+        alpha = getattr(self, "distill_alpha", 0.0)
+        check_distillation(alpha, getattr(self, "distill_temperature", 1.0))
+        if float(alpha) != 0.0:
+            _lib.check(_lib.lib().mmc_trainer_set_distillation(self._h, float(alpha), float(self.distill_temperature)))
 
     def _averages(self) -> bool:
         return float(getattr(self, "ema_decay", 0.0)) != 0.0
@@ -510,7 +550,7 @@ class TorchMLPClassifier:
         return self
 
     def partial_fit_rows(self, fs, rows=None, classes: Sequence[Any] | None = None, *, row_weight=None,
-                         row_group=None) -> "TorchMLPClassifier":
+                         row_group=None, targets=None) -> "TorchMLPClassifier":
         """``partial_fit(X[rows], y[rows], classes)`` for rows that are resident in the ``FeatureSet`` ``fs`` (``rows=None``: every
         row, in stored order): same first-call initialisation, mini-batch size, shuffle, ``loss_curve_`` / ``n_iter_`` -- and the
         same bits.  The shuffle is composed with ``rows`` on the host; only the indices are uploaded
@@ -520,12 +560,22 @@ class TorchMLPClassifier:
 
         ``row_weight`` (real, >= 0) and ``row_group`` (integers in ``[0, n_groups)``; needs ``n_groups``) are indexed by row of the
         SET, one entry per stored row, and gathered by the visiting order here (``mmc_trainer_partial_fit_set_weighted``): a weight per
-        row, and group DRO over the rows' groups (include/mmc.h, "group-robust training").  Both None is the pass above, bit for bit."""
+        row, and group DRO over the rows' groups (include/mmc.h, "group-robust training").  Both None is the pass above, bit for bit.
+
+        ``targets`` (a ``TargetSet`` aligned with ``fs``; needs ``distill_alpha > 0``) adds the distillation term: every visited row
+        reads its own target row in place (``mmc_trainer_partial_fit_set_distill``; include/mmc.h, "distillation")."""
         rw, rg = check_row_arrays(self, len(fs), row_weight, row_group)
+        targets = check_targets(self, fs, targets)
         visit, n_samples, batch_size = self._begin_rows_pass(fs, rows, classes)
         visit, partner, lam = self._mix_plan(visit, n_samples, batch_size)
         avg = C.c_double(0.0)
-        if rw is not None or rg is not None:
+        if targets is not None:
+            rw, rg = by_position(rw, visit, n_samples), by_position(rg, visit, n_samples)
+            _lib.check(_lib.lib().mmc_trainer_partial_fit_set_distill(
+                self._h, fs._handle(), targets._handle(), None if visit is None else visit.ctypes.data,
+                None if rw is None else rw.ctypes.data, None if rg is None else rg.ctypes.data, n_samples, int(batch_size), C.byref(avg),
+                _current_stream_ptr(_device_index(self.device))))
+        elif rw is not None or rg is not None:
             rw, rg = by_position(rw, visit, n_samples), by_position(rg, visit, n_samples)
             _lib.check(_lib.lib().mmc_trainer_partial_fit_set_weighted(
                 self._h, fs._handle(), None if visit is None else visit.ctypes.data, None if rw is None else rw.ctypes.data,
@@ -746,7 +796,8 @@ class TorchMLPClassifier:
                 "final_lr_ratio": self.final_lr_ratio, "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay,
                 "group_dro_eta": self.group_dro_eta, "n_groups": self.n_groups, "class_levels": self.class_levels,
                 "level_weights": self.level_weights, "soft_targets": self.soft_targets, "batch_norm": self.batch_norm,
-                "batch_norm_eps": self.batch_norm_eps, "batch_norm_momentum": self.batch_norm_momentum}
+                "batch_norm_eps": self.batch_norm_eps, "batch_norm_momentum": self.batch_norm_momentum,
+                "distill_alpha": self.distill_alpha, "distill_temperature": self.distill_temperature}
 
     def set_params(self, **params: Any) -> "TorchMLPClassifier":
         for key, value in params.items():
@@ -779,7 +830,9 @@ class TorchMLPClassifier:
                              # ... and one made before the taxonomy-aware loss existed with the flat loss
                              ("class_levels", None), ("level_weights", None), ("soft_targets", None), ("_hierarchy_arrays", None),
                              # ... and one made before batch normalisation existed as a plain head
-                             ("batch_norm", False), ("batch_norm_eps", 1e-5), ("batch_norm_momentum", 0.1)):
+                             ("batch_norm", False), ("batch_norm_eps", 1e-5), ("batch_norm_momentum", 0.1),
+                             # ... and one made before distillation existed as a student of its labels alone
+                             ("distill_alpha", 0.0), ("distill_temperature", 1.0)):
             self.__dict__.setdefault(key, default)
         self._h = None
         if params is not None:

@@ -26,6 +26,18 @@ from .validation import previous_accuracies, validate
 __all__ = ["EarlyStopping", "epoch_loop", "train_classifier", "train_and_validate"]
 
 
+def resolve_targets(targets, teacher, train):
+    """``targets=`` / ``teacher=`` of a training call -> the target set, or None.  One or the other (``ValueError`` for both); a
+    teacher's targets are made for ``train`` as it is given (``distill.teacher_targets``) and are the caller's to close.
+    (``sweep.train_sweep`` resolves its arguments the same way.)"""
+    if targets is not None and teacher is not None:
+        raise ValueError("pass targets or teacher, not both")
+    if teacher is None:
+        return targets
+    from .distill import teacher_targets
+    return teacher_targets(teacher, train)
+
+
 class EarlyStopping:
     """``epoch_loop``'s bookkeeping for one model: best validation loss so far with its epoch and ``copy.deepcopy`` snapshot,
     epochs since the last improvement, and what the callback dict and the stop summary are made of.  ``epoch_loop`` keeps one,
@@ -157,7 +169,7 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
                      on_epoch_end: Optional[Callable[[Dict[str, Any]], None]] = None,
                      batches: Optional[Callable[[int], Iterable[np.ndarray]]] = None,
                      clf: Optional[TorchMLPClassifier] = None, class_scores: bool = False, transform=None, logit_scaling=None,
-                     row_weight=None, row_group=None) -> Tuple[CalibratedMLP, Dict[str, Any], List[float]]:
+                     row_weight=None, row_group=None, targets=None, teacher=None) -> Tuple[CalibratedMLP, Dict[str, Any], List[float]]:
     """Train, early-stop and calibrate the MLP head on three resident splits.  -> ``(calibrated, info, ref_accs)``:
     the ``CalibratedMLP`` of the returned classifier on ``ref``, ``epoch_loop``'s ``info``, and the ref accuracy after every
     epoch run (the reference's ``TrainClassifierReturnMsg.ref_accs``).
@@ -190,10 +202,24 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
     first -- on a head with no hidden layer the scaling first, then the transform.  ``None`` changes no call.
 
     ``row_weight`` / ``row_group``: arrays indexed by row of ``train``, handed to every epoch's ``partial_fit_rows`` (a weight per row;
-    group DRO over the rows' groups, on a ``clf`` with ``n_groups``).  ``None`` changes no call."""
+    group DRO over the rows' groups, on a ``clf`` with ``n_groups``).  ``None`` changes no call.
+
+    ``targets`` (a ``TargetSet`` aligned with ``train``) or ``teacher`` (a ``HeadEnsemble``, ``CalibratedMLP`` or ``Predictor``, whose
+    targets are made for ``train`` and freed at the end), one or the other: every epoch's ``partial_fit_rows`` gets the targets, on a
+    ``clf`` with ``distill_alpha > 0`` (``distill.distill`` builds one).  With ``transform=`` a teacher scores the RAW train split,
+    before it is transformed; ``FeatureTransform.apply`` keeps the row order, so the rows still align.  ``None`` changes no call."""
     _check_splits(train, ref, val, batch_size)
     if logit_scaling is not None:
         _ls.check_argument(logit_scaling)
+    if teacher is not None:   # made for the train split as given (raw, when there is a transform), freed when the training ends
+        targets = resolve_targets(targets, teacher, train)
+        try:
+            return train_classifier(train, ref, val, nbr_epochs, batch_size=batch_size, class_weight=class_weight,
+                                    early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end, batches=batches,
+                                    clf=clf, class_scores=class_scores, transform=transform, logit_scaling=logit_scaling,
+                                    row_weight=row_weight, row_group=row_group, targets=targets)
+        finally:
+            targets.close()
     if transform is not None:
         ft = _ft.resolve(transform, train)
         sets = []
@@ -203,7 +229,7 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
             cal, info, accs = train_classifier(*sets, nbr_epochs, batch_size=batch_size, class_weight=class_weight,
                                                early_stopping_patience=early_stopping_patience, on_epoch_end=on_epoch_end,
                                                batches=batches, clf=clf, class_scores=class_scores, logit_scaling=logit_scaling,
-                                               row_weight=row_weight, row_group=row_group)
+                                               row_weight=row_weight, row_group=row_group, targets=targets)
         finally:
             for fs in sets:
                 fs.close()
@@ -221,7 +247,9 @@ def train_classifier(train: FeatureSet, ref: FeatureSet, val: FeatureSet, nbr_ep
 
     def train_epoch(c, epoch):
         for rows in batches(epoch):
-            if row_weight is None and row_group is None:
+            if targets is not None:
+                c.partial_fit_rows(train, rows, classes=classes, row_weight=row_weight, row_group=row_group, targets=targets)
+            elif row_weight is None and row_group is None:
                 c.partial_fit_rows(train, rows, classes=classes)
             else:
                 c.partial_fit_rows(train, rows, classes=classes, row_weight=row_weight, row_group=row_group)

@@ -5,8 +5,8 @@ bit (run it on both checkouts in one visit; the two outputs must be identical li
 A training case hashes the parameters, both Adam moments, the step count and loss_curve_, and on an "extras" line what its options
 keep beside them (the raw parameters, grad_norms_, the averaged weights, log q, the batch-normalisation state and the folded
 parameters); the other cases hash the raw bytes of the outputs they name.  The cases: host-fed and resident passes of one
-classifier, every loss, regulariser, optimiser, group-robust, taxonomy and normalisation option on its own, two grouped passes of
-heterogeneous members, the eval-mode forward, and the four probes -- all on the 730 x 64 rows of tests/golden/trainer_fixture.npz.
+classifier, every loss, regulariser, optimiser, group-robust, taxonomy, normalisation and distillation option on its own, two grouped
+passes of heterogeneous members, the eval-mode forward, and the six probes -- all on the 730 x 64 rows of tests/golden/trainer_fixture.npz.
 Seconds in all.
 
     python tools/trainer_bits.py [--grouped-only]     (--grouped-only: the two grouped passes alone, for a kernel trace)"""
@@ -20,7 +20,7 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from mermaid_classifier_amd import FeatureSet, _lib, calibrate  # noqa: E402
+from mermaid_classifier_amd import FeatureSet, TargetSet, _lib, calibrate  # noqa: E402
 from mermaid_classifier_amd.torch_classifier import TorchMLPClassifier, _ptr_array  # noqa: E402
 
 fx = dict(np.load(ROOT / "tests" / "golden" / "trainer_fixture.npz"))
@@ -71,6 +71,10 @@ ROW_G = (np.arange(N) * 3 % 5).astype(np.int32)
 LEVELS = {c: [i // 4, None if i % 5 == 0 else i // 2] for i, c in enumerate(classes)}
 SOFT = {c: {c: 0.75, classes[(i + 1) % K]: 0.25} for i, c in enumerate(classes)}
 fp = C.POINTER(C.c_float)
+# per-row targets from the fixture's columns: a softmax in double, stored as float32 (rows sum to 1 within rounding)
+_T = np.tile(X, (1, 3))[:, :K].astype(np.float64) * 3.0
+TARGETS = np.exp(_T - _T.max(axis=1, keepdims=True))
+TARGETS = np.ascontiguousarray((TARGETS / TARGETS.sum(axis=1, keepdims=True)).astype(np.float32))
 
 
 def extras(clf):
@@ -193,12 +197,17 @@ OPTIONS = {
     "batch norm": (dict(batch_norm=True, hidden_layer_sizes=(48, 32)), {}),
 }
 fs = FeatureSet(64, classes, reserve=730).append(X, y)
+ts = TargetSet(classes, reserve_rows=730).append(TARGETS)
+OPTIONS["distillation"] = (dict(distill_alpha=0.5), dict(targets=ts))
+OPTIONS["distillation tau 2 + row weights + group DRO"] = (dict(distill_alpha=0.7, distill_temperature=2.0, n_groups=5, group_dro_eta=0.5),
+                                                           dict(targets=ts, row_weight=ROW_W, row_group=ROW_G))
 for name, (opts, arrays) in OPTIONS.items():
     clf = clf_of(weighted=True, **opts)
     for _ in range(2):
         clf.partial_fit_rows(fs, None, classes=classes.tolist(), **arrays)
     show(f"resident {name} x2", state(clf))
     show(f"resident {name} x2, extras", extras(clf))
+ts.close()
 fs.close()
 grouped_passes()
 
@@ -237,6 +246,20 @@ for Kp in (3, 130):
                 h, z.ctypes.data, yi.ctypes.data, None if a_w is None else a_w.ctypes.data, None if a_g is None else a_g.ctypes.data,
                 logq.ctypes.data, 0.7, G, n, d.ctypes.data, rl.ctypes.data, lq.ctypes.data, gl.ctypes.data, None))
             show(f"loss gradient weighted {tag} {kind}", digest(d, rl, lq, gl))
+    _lib.check(lib.mmc_trainer_set_hierarchy(h, 0, None, None, None))
+    qk = np.exp(z.astype(np.float64) * 0.5)
+    qk = np.ascontiguousarray((qk / qk.sum(axis=1, keepdims=True)).astype(np.float32))
+    for alpha, tau in ((0.5, 1.0), (0.5, 2.0)):
+        _lib.check(lib.mmc_trainer_set_distillation(h, alpha, tau))
+        d, rl = np.full(z.shape, np.nan, np.float32), np.full(n, np.nan, np.float32)
+        _lib.check(lib.mmc_trainer_loss_gradient_distill(h, z.ctypes.data, yi.ctypes.data, qk.ctypes.data, rw.ctypes.data, n, d.ctypes.data,
+                                                         rl.ctypes.data, None))
+        show(f"loss gradient distill K {Kp} tau {tau:g} weights", digest(d, rl))
+        d, rl, lq, gl = np.full(z.shape, np.nan, np.float32), np.full(n, np.nan, np.float32), np.full(G, np.nan), np.full(G, np.nan)
+        _lib.check(lib.mmc_trainer_loss_gradient_distill_weighted(h, z.ctypes.data, yi.ctypes.data, qk.ctypes.data, rw.ctypes.data,
+                                                                  rg.ctypes.data, logq.ctypes.data, 0.7, G, n, d.ctypes.data, rl.ctypes.data,
+                                                                  lq.ctypes.data, gl.ctypes.data, None))
+        show(f"loss gradient distill K {Kp} tau {tau:g} weights + groups", digest(d, rl, lq, gl))
     lib.mmc_trainer_destroy(h)
 
 for width, rows in ((24, 203), (130, 50)):
