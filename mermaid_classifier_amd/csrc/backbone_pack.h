@@ -504,3 +504,24 @@ static inline Fp8Image pack_fp8(const float* w, const float* b, int N, int K)
     }
     return L;
 }
+
+// ------------------------------------------------------------------------------------------
+// activation layouts a kernel writes that are not NHWC
+// ------------------------------------------------------------------------------------------
+// mb1_kernel<true>'s depthwise output (Mb1Args::D with `planar`, read back by thin_proj_kernel through x_plane_rows = n * hw): C / 32
+// planes of n * hw pixel rows of 32 channels, [C / 32][n * hw][32].  Where NHWC element (patch b, pixel pix, channel c) of a launch
+// over n patches stands in the planes:
+static inline size_t planes_index(int n, int hw, int b, int pix, int c)
+{
+    return (((size_t)(c >> 5) * n + b) * hw + pix) * 32 + (c & 31);
+}
+// ... and the whole tensor back as NHWC [n][hw][C] (per-tensor mode hands `b1.dw` out in that layout whatever the kernels exchanged)
+template <typename T>
+static inline std::vector<T> planes_to_nhwc(const T* planes, int n, int hw, int C)
+{
+    std::vector<T> out((size_t)n * hw * C);
+    for (int b = 0; b < n; ++b)
+        for (int pix = 0; pix < hw; ++pix)
+            for (int c = 0; c < C; ++c) out[((size_t)b * hw + pix) * C + c] = planes[planes_index(n, hw, b, pix, c)];
+    return out;
+}

@@ -299,6 +299,7 @@ struct Saved {
     size_t bytes = 0;
     size_t elems = 0;
     bool is_half = true;
+    int plane_hw = 0, plane_c = 0;   // != 0: the copy is plane_c / 32 planes of n * plane_hw rows (planes_index), read back as NHWC
 };
 
 // ------------------------------------------------------------------------------------------
@@ -311,7 +312,7 @@ struct StemArgs { const float *wdw, *bdw; _Float16* out; float* pool; };   // la
 struct SeLaunch { const float* pool; int nparts, C; SeArgs w; float* gate; };
 struct MbPreArgs { MbArgs mb; const _Float16* pre_w; const float *pre_b, *pre_gate; };
 // a tensor per-tensor mode (MMC_KEEP_ACTIVATIONS=1) copies out after the launch
-struct KeptTensor { std::string name; const void* dev; size_t per_patch; bool is_half; };
+struct KeptTensor { std::string name; const void* dev; size_t per_patch; bool is_half; int plane_hw = 0, plane_c = 0; };   // planes: see Saved
 struct Launch {
     std::string name;                         // as mmc_backbone_profile reports it, before the '|'
     const char* label[2] = {nullptr, nullptr};   // ... and behind it; a pw_gemm launch has one per mt (gemm_mt), every other the same twice
@@ -561,8 +562,8 @@ static int plan_block(const mmc_backbone* bb, BlockW& B, int i)
     if (B.back == Back::SeProject && B.proj == Proj::Gemm && !plan_gemm(P, EPI_LINEAR, true, B.skip, HWo))
         return fail(MMC_ERR_ARG, "block %d: no pw_gemm (project) instantiation for %d -> %d channels at %dx%d", i, B.ce, B.d.cout, B.Ho, B.Ho);
     // block 1's depthwise output as three 32-channel planes between mb1_kernel and thin_proj_kernel (see mb1_kernel); per-tensor
-    // mode keeps the interleaved tensor it hands out
-    B.planar = B.front == Front::Mb1 && thin && o.b1_planar && !o.keep && P.K == 96;
+    // mode runs the same two kernels and hands the planes out as NHWC (planes_to_nhwc)
+    B.planar = B.front == Front::Mb1 && thin && o.b1_planar && P.K == 96;
     return 0;
 }
 
@@ -929,7 +930,8 @@ static int build_lane(mmc_backbone* bb, int lane_idx)
             break;
         }
         case Front::Mb1: {   // reads block 0's depthwise output (in y: no swap behind Back::SeFolded) and its gate
-            Mb1Args& a = add("b0.project+b1.mbconv", "mb1", Op::Mb1).a.mb1 = B.mb1;
+            // (per-tensor mode says which instantiation ran; the product pass keeps the one label its profiles are keyed by)
+            Mb1Args& a = add("b0.project+b1.mbconv", bb->keep && B.planar ? "mb1<planar>" : "mb1", Op::Mb1).a.mb1 = B.mb1;
             a.X = y; a.pre_gate = ws.gate; a.D = D; a.pool = pool;
             break;
         }
@@ -958,6 +960,7 @@ static int build_lane(mmc_backbone* bb, int lane_idx)
         case Front::Tail: break;
         }
         writes(D, (size_t)HWo * B.ce, bn(i, ".dw"));
+        if (bb->keep && B.planar) { list.back().keep.back().plane_hw = HWo; list.back().keep.back().plane_c = B.ce; }
         writes(pool, (size_t)B.nparts * B.ce);
         // ---- back half ----
         if (B.back == Back::Tail) break;   // block 11's back half: the tail launch below
@@ -1004,7 +1007,7 @@ static int build_lane(mmc_backbone* bb, int lane_idx)
             a.X = D; a.Y = y; a.gate = ws.gate; a.res = res;
             if (B.proj == Proj::Thin) {
                 Launch& L = list.back();
-                L.op = Op::ThinProj; L.label[0] = L.label[1] = "thin_proj"; L.planar = B.planar;
+                L.op = Op::ThinProj; L.label[0] = L.label[1] = bb->keep && B.planar ? "thin_proj<planar>" : "thin_proj"; L.planar = B.planar;
             }
         }
         writes(y, (size_t)HWo * B.d.cout, bn(i, ".out"));
@@ -1020,7 +1023,7 @@ static int build_lane(mmc_backbone* bb, int lane_idx)
         if (!head) L.a.tail.head_w = nullptr;
         return L.a.tail;
     };
-    if (bb->tail == TailRoute::B11All || (bb->tail == TailRoute::B11 && !bb->keep)) {
+    if (!bb->keep && (bb->tail == TailRoute::B11All || bb->tail == TailRoute::B11)) {
         // from block 11's input (B11All) or its depthwise output (B11) through blocks 12..15 and the head conv to the features, ONE launch
         TailArgs& ta = add_tail(bb->tail == TailRoute::B11All ? "b11all-head.tail" : "b11-head.tail", true);
         ta.nblk = 4;
@@ -1034,11 +1037,17 @@ static int build_lane(mmc_backbone* bb, int lane_idx)
         }
         return err;
     }
-    if (bb->tail == TailRoute::B11) {   // per-tensor mode: block 11's back half on its own
+    const bool head_phase = bb->tail == TailRoute::B11 || bb->tail == TailRoute::B11All;   // the head conv runs on tail7_kernel
+    if (head_phase) {   // per-tensor mode: block 11 on its own, all of it from the block's input (B11All) or its back half (B11)
         const BlockW& B11 = bb->blk[11];
         TailArgs& ta = add_tail("b11.tail", false);
         ta.nblk = 0; ta.Y = y; ta.dbg_gate = ws.gate;
-        ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part;
+        if (bb->tail == TailRoute::B11All) {
+            ta.pre_X = x; ta.dbg_dw = ws.dwbuf;
+            writes(ws.dwbuf, (size_t)49 * B11.ce, "b11.dw");
+        } else {
+            ta.pre_D = ws.dwbuf; ta.pre_pool = ws.pool_part;
+        }
         writes(ws.gate, (size_t)B11.ce, "b11.gate");
         writes(y, (size_t)49 * 192, "b11.out");
         std::swap(x, y);
@@ -1062,7 +1071,7 @@ static int build_lane(mmc_backbone* bb, int lane_idx)
             std::swap(x, y);
         }
     }
-    if (bb->tail == TailRoute::B11) {   // per-tensor mode: the head phase of tail7_kernel on its own
+    if (head_phase) {   // per-tensor mode: the head phase of tail7_kernel on its own
         TailArgs& ta = add_tail("head.tail", true);
         ta.X = x; ta.nblk = 0; ta.in_wide = 1;
     } else {
@@ -1150,7 +1159,7 @@ extern "C" int mmc_backbone_create_ex(const void* packed, size_t nbytes, int arc
         const BlockW& B11 = K[11 < NBLK ? 11 : 0];
         const bool t11 = t12 && o.tail_full && HEAD_IN % 32 == 0 && B11.fusable && B11.ce == 672 && B11.d.cout == 192 &&
                          B11.cs4 == 28 && B11.mb.tiles_x * B11.mb.tiles_y == 1;
-        const bool t11all = t11 && o.tail_b11 && !o.keep && B11.mb.ksteps == 4 && B11.d.k == 5 && B11.d.s == 2 && B11.H == 14;
+        const bool t11all = t11 && o.tail_b11 && B11.mb.ksteps == 4 && B11.d.k == 5 && B11.d.s == 2 && B11.H == 14;
         bb->tail = t11all ? TailRoute::B11All : t11 ? TailRoute::B11 : t12 ? TailRoute::B12 : TailRoute::None;
         for (int i = 0; i < NBLK; ++i) TRY_OR_FREE(plan_block(bb, bb->blk[i], i));
         // chain14_kernel: the maximal run of consecutive launches that are one workgroup per patch on a body the chain kernel holds
@@ -1348,6 +1357,8 @@ static int forward_lane(mmc_backbone* bb, const std::vector<Launch>& list, const
             for (const KeptTensor& k : L.keep) {
                 const int r = save_act(bb, k.name.c_str(), k.dev, (size_t)n * k.per_patch, k.is_half, st);
                 if (r) return r;
+                Saved& s = bb->saved[k.name];
+                s.plane_hw = k.plane_hw; s.plane_c = k.plane_c;
             }
     }
     return 0;
@@ -1541,6 +1552,8 @@ extern "C" int mmc_backbone_read_activation(mmc_backbone* bb, const char* name, 
     if (s.is_half) {
         std::vector<_Float16> tmp(s.elems);
         HIP_TRY(hipMemcpy(tmp.data(), s.dev, s.elems * 2, hipMemcpyDeviceToHost));
+        if (s.plane_hw)   // the copy of a launch over n patches: elems = n * plane_hw * plane_c
+            tmp = planes_to_nhwc(tmp.data(), (int)(s.elems / ((size_t)s.plane_hw * s.plane_c)), s.plane_hw, s.plane_c);
         const size_t ln = strlen(name);
         const bool scaled = strcmp(name, "stem") == 0 || (ln > 3 && strcmp(name + ln - 3, ".dw") == 0) ||
                             (ln > 7 && strcmp(name + ln - 7, ".expand") == 0);   // SiLU outputs live times log2(e)

@@ -22,13 +22,16 @@ and ``|x|``.  With ``u = 2**-11`` (fp16 unit roundoff) and ``v = 2**-24`` (fp32)
    ``mmc_backbone_read_activation`` applies to SiLU-domain tensors on the way out (``mmc_api.cpp``, ``mmc_backbone_read_activation``).
 4. **Values held in fp16.**  Each value the kernel holds in fp16 between phases carries a relative u plus an absolute 2**-25
    (half the smallest subnormal):
-   - the expanded tensor in LDS (``k_mbconv.hip:434-437``, ``k_early.hip:562``, ``k_mid.hip:360``);
+   - the expanded tensor in LDS (``k_mbconv.hip:434-437``, ``k_early.hip:562``, ``k_mid.hip:360``; block 11 inside
+     ``tail7_kernel``: the chunk ``E[196][96]``, ``k_tail.hip:318-323``);
    - the gated operand fp16(g d) (``device_common.h:104-123`` ``gate_h8``; ``k_mid.hip:804``, ``k_tail.hip:490``, ``k_mbconv.hip:105``).
      ``thin_proj_kernel`` rounds fp16(g w) instead (``k_early.hip:24-27``, ``:66``): the same relative u on every product, and an
      absolute 2**-25 that multiplies |d| instead of |w| -- the project stage charges both;
    - the intermediate tensors of the fused B0 stem / block 0 / block 1 path (``k_early.hip:155``: gated block-0 operand;
      the projected block-0 output as the expand's MFMA operand; the stem tensor in LDS);
-   - every stored fp16 output (``k_generic.hip:110``, ``k_early.hip:264``, ``k_mid.hip:203``, ``k_tail.hip:386``).
+   - every stored fp16 output (``k_generic.hip:110``, ``k_early.hip:264``, ``k_mid.hip:203``, ``k_tail.hip:386``); block 11's
+     depthwise output inside ``tail7_kernel`` is the compact ``D11[49][672]`` in LDS (``k_tail.hip:386-390``), which per-tensor mode
+     copies out unchanged (``k_tail.hip:398-404``).
    Gates and features are fp32 and carry a relative v instead.
    The stem's padding value 255 mean - 128 is held in fp16 like the pixels beside it (``k_generic.hip:64-67``): the padded
    pixels carry a relative u, the real ones (u8 - 128) are exact.

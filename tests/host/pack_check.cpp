@@ -1,4 +1,4 @@
-// pack_check.cpp -- stand-alone host check of csrc/backbone_pack.h: every weight layout and the blob reader, no GPU and no HIP.
+// pack_check.cpp -- stand-alone host check of csrc/backbone_pack.h: every weight layout, block 1's activation planes and the blob reader, no GPU and no HIP.
 // For each packer: a tensor whose elements are all distinct (exact in fp16), then a walk over the packed IMAGE in the order the
 // kernel reads it (kernels.h field comments) that says which tensor element, or zero, must stand at each position.  The packers
 // walk the tensor; this walks the image, so gaps, duplicates and non-zero padding all show.
@@ -369,6 +369,34 @@ static void check_fp8(int N, int K)
     }
 }
 
+// ---- block 1's planes [C/32][n * hw][32] (Mb1Args::D with planar): the image is filled in mb1_kernel<true>'s own address arithmetic,
+// plane chunk at (chunk n hw + b hw + pix) 32 + c, with the NHWC position of every element as its value; planes_to_nhwc must then
+// return 0, 1, 2, ... and planes_index must name every image position exactly once ----
+static void check_planes(int n, int hw, int C)
+{
+    const size_t total = (size_t)n * hw * C;
+    std::vector<uint32_t> img(total, 0xFFFFFFFFu);
+    for (int chunk = 0; chunk < C / 32; ++chunk)
+        for (int b = 0; b < n; ++b)
+            for (int pix = 0; pix < hw; ++pix)
+                for (int c = 0; c < 32; ++c)
+                    img[((size_t)chunk * n * hw + (size_t)b * hw + pix) * 32 + c] = (uint32_t)(((size_t)b * hw + pix) * C + 32 * chunk + c);
+    const std::vector<uint32_t> nhwc = planes_to_nhwc(img.data(), n, hw, C);
+    REQUIRE(nhwc.size() == total, "size %zu", nhwc.size());
+    for (size_t i = 0; i < total; ++i) REQUIRE(nhwc[i] == (uint32_t)i, "NHWC element %zu came from the image position of element %u", i, nhwc[i]);
+    Cover cov(total);
+    for (int b = 0; b < n; ++b)
+        for (int pix = 0; pix < hw; ++pix)
+            for (int c = 0; c < C; ++c) {
+                const size_t at = planes_index(n, hw, b, pix, c);
+                REQUIRE(at < total, "patch %d pixel %d channel %d: position %zu of %zu", b, pix, c, at, total);
+                cov.hit(at);
+                // thin_proj_kernel's read of k = c, row = pix with plane_rows = n hw (k_early.hip, plane_rows != 0)
+                REQUIRE(at == ((size_t)(c >> 5) * ((size_t)n * hw) + (size_t)b * hw + pix) * 32 + (c & 31), "patch %d pixel %d channel %d", b, pix, c);
+            }
+    cov.done();
+}
+
 // ---- blobs ----
 struct Blob {
     std::vector<uint8_t> bytes;
@@ -479,6 +507,8 @@ int main()
     begin("squeeze-excite transposed + FC1 groups ce 40 cs 10 csp 12"); check_se_t(40, 10, 12, 64); ok();
     begin("tail7 requests 1152 / 48"); check_tail7(); ok();
     begin("e4m3 image N 20 K 130"); check_fp8(20, 130); ok();
+    begin("block 1 planes -> NHWC, 1 patch 56x56x96"); check_planes(1, 3136, 96); ok();
+    begin("block 1 planes -> NHWC, 3 patches 56x56x96"); check_planes(3, 3136, 96); ok();
 
     begin("blob: well-formed B0"); check_blob_good(MMC_ARCH_B0); ok();
     begin("blob: well-formed B4"); check_blob_good(MMC_ARCH_B4); ok();
